@@ -10,10 +10,14 @@ Workload at N = 1: BASELINE.json configs[1] -- par_example/emissivity.par_exampl
 rank r owns rows r, r+N, r+2N, ... (row-cyclic: neighbouring rows cost the same, so ranks stay balanced),
 i.e. per-GPU work is fixed (weak scaling); the only exchange is the all-reduce of the 5*Nr+1 histogram words.
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--rays R] [--integrator rk4|rk45|euler]
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--rays R] [--integrator rk4|rk45|euler] [--full] [--dump-outputs DIR]
         N > 1 without RANK / WORLD_SIZE in the environment: bench.py starts `python -m torch.distributed.run --nproc-per-node N bench.py ...`
         itself, as a CHILD process (one rank per GPU over RCCL), relays rank 0's JSON line and exits with the child's code; it touches no GPU
         itself.  Under torch.distributed.run (the driver's multi-GPU command) it is a rank.
+        A plain run sets up, warms up (W steps), times the K steps and prints the line.  --full adds the legs that take runs of their own:
+        the other two arithmetic modes on the same workload (`other_arithmetic_modes`) and the CPU baseline with its parity checks
+        (`cpu_baseline`; --no-cpu-baseline / --no-fast-math-extra leave one of them out).  --dump-outputs DIR writes what the last timed step
+        computed (the result buffer a caller of the pipeline receives, float64) as DIR/<name>.npy, at most 64 MB in all.
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -38,6 +42,8 @@ NR, R_DISC, GAMMA = 100, 500.0, 2.0             # emissivity.cpp defaults (Nr = 
 FLOP_PER_STEP = {"euler": 100.0, "rk4": 340.0, "rk45": 590.0}   # algorithmic fp64 FLOP per step / per RK45 attempt
 FP64_VECTOR_PEAK_TFLOPS = 78.6                   # MI355X vector fp64: 256 CU x 4 SIMD x 16 FMA lanes x 2 x 2.4 GHz
 HBM_PEAK_GBS = 8000.0
+DUMP_LIMIT_BYTES = 64 << 20                      # --dump-outputs: the most it writes
+DUMP_SAMPLE_SEED, DUMP_SAMPLE_PIXELS = 20240917, 1 << 19     # image planes larger than that: the same seeded pixel sample of every plane
 
 
 def self_launch_argv(argv, gpus, port, python=None):
@@ -354,6 +360,12 @@ class EmissivityWorkload:
     def summary(self, h):
         return {"disc_hits": float(h[5 * NR])}
 
+    def outputs(self, h):
+        """The histogram words the pipeline leaves in HBM, by field (kr_post_emissivity_dev_f64's layout)."""
+        out = {f"emissivity_{k}": h[q * NR:(q + 1) * NR] for q, k in enumerate(("count", "flux", "emis", "sum_redshift", "sum_time"))}
+        out["emissivity_disc_rays"] = h[5 * NR:5 * NR + 1]
+        return out
+
 
 class ImagePlaneWorkload:
     """BASELINE configs[3]: imageplane_disc_image geometry (par_example: dist 1e4, incl 80, +-30, r_disc 30, q = 3), img_N = N = 4096
@@ -447,6 +459,20 @@ class ImagePlaneWorkload:
 
     def summary(self, h):
         return {"disc_hits": float(h[-1]), "lit_pixels": int((h[: self.N * self.N] > 0).sum())}
+
+    def outputs(self, h):
+        """The seven image planes (api.image_planes_from_words's layout) and the disc-ray count.  Planes whose seven copies would pass the
+        dump limit are cut to the same fixed, seeded sample of pixels (DUMP_SAMPLE_PIXELS of them, ascending pixel index) in every plane."""
+        npix = self.N * self.N
+        planes = h[:7 * npix].reshape(7, npix)
+        if 7 * npix * 8 > DUMP_LIMIT_BYTES // 2:
+            pick = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(npix, size=DUMP_SAMPLE_PIXELS, replace=False))
+            planes, tag = planes[:, pick], "_sample"
+        else:
+            tag = ""
+        out = {f"imageplane_{k}{tag}": planes[q] for q, k in enumerate(("nrays", "flux", "r", "phi", "enshift", "time", "emis"))}
+        out["imageplane_disc_rays"] = h[7 * npix:7 * npix + 1]
+        return out
 
 
 class ReturnRadiationWorkload:
@@ -633,6 +659,10 @@ class ReturnRadiationWorkload:
         pick = [0, self.nr // 4, self.nr // 2, self.nr - 1]
         return {"fractions_escape_return_lost": {f"radius_index_{i}": [float(f[i, 1]), float(f[i, 0]), float(f[i, 2])] for i in pick}}
 
+    def outputs(self, h):
+        """The per-radius table the pipeline leaves in HBM: nr rows of 4 words (kr_post_return_dev_f64's layout)."""
+        return {"return_radiation_table": h.reshape(self.nr, 4)}
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -656,8 +686,12 @@ def main():
                          "auto = hybrid for euler / rk4, strict for rk45 (what the host mirror of the class API does)")
     ap.add_argument("--fast-math", action="store_true", help="same as --arithmetic fast")
     ap.add_argument("--separate-passes", action="store_true", help="emissivity / imageplane: the five O(N) passes one kernel each instead of the two fused ones")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fast-math-extra", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline: the other arithmetic modes and the CPU baseline with its parity checks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result buffer of the last timed step as DIR/<name>.npy (float64, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU baseline")
+    ap.add_argument("--no-fast-math-extra", action="store_true", help="--full: leave out the other arithmetic modes")
     ap.add_argument("--cpu-sample-rays", type=float, default=0)
     args = ap.parse_args()
 
@@ -776,9 +810,11 @@ def main():
         traced_all, steps_all = traced, steps_total
 
     h = state["last"].cpu().numpy()
-    # the other two arithmetic modes on the same workload, reported beside the headline
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, wl.outputs(h), {"trace_counters": [traced_all, steps_all]})
+    # the other two arithmetic modes on the same workload, reported beside the headline (--full)
     others = None
-    if world == 1 and not args.no_fast_math_extra:
+    if args.full and world == 1 and not args.no_fast_math_extra:
         others = {}
         for mode in ("strict", "hybrid", "fast"):
             if mode == args.arithmetic:
@@ -842,8 +878,8 @@ def main():
         if args.integrator == "rk45":
             out["rk45"] = {k: int(stats_last[k]) for k in ("rk45_attempts", "rk45_rejects", "rk45_stationary_steps", "rk45_extrapolated_steps")}
             out["rk45"]["evaluated_trial_steps"] = int(units)
-        if world > 1:
-            pass                                    # cpu_baseline is an N = 1 leg only
+        if world > 1 or not args.full:
+            pass                                    # cpu_baseline is an N = 1 leg of --full only
         elif not args.no_cpu_baseline and args.workload == "emissivity":
             out["cpu_baseline"] = cpu_baseline(args, capi, api, wl.method, wl.d, mode_flags[args.arithmetic], timed={"hist": h, "steps": steps_total})
         elif not args.no_cpu_baseline and args.workload == "imageplane":
@@ -852,6 +888,18 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(path, arrays, counters):
+    """--dump-outputs: every array as <path>/<name>.npy in float64.  The inputs of a run depend on its arguments only, so two builds run with the
+    same arguments can be compared file by file."""
+    os.makedirs(path, exist_ok=True)
+    arrays = dict(arrays, **{k: np.asarray(v, dtype=np.float64) for k, v in counters.items()})
+    total = sum(np.asarray(a).size * 8 for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT_BYTES})")
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def critical_ray(st, units, flop_per_unit):

@@ -1,10 +1,10 @@
 #!/bin/bash
-# dropin/build_apps.sh -- drop-in demonstration (build container only; needs /root/reference).
+# oracle/build_dropin_apps.sh -- drop-in demonstration (only where the reference sources are present, $REF).
 #
 # Compiles the REFERENCE's own application sources, unmodified and read where they lie, against
 #   (a) the reference's own library sources            -> oracle/_ref/apps/<app>     (CPU, the baseline)
-#   (b) this repo's host-side API mirror + libkrtrace  -> dropin/_build/<app>        (MI355X path)
-# Both output dirs are git-ignored; the binaries travel to the GPU box with the snapshot, the sources do not.
+#   (b) this repo's host-side API mirror + libkrtrace  -> oracle/_ref/dropin/<app>   (MI355X path)
+# Both output dirs lie under oracle/_ref/, which is git-ignored; the binaries travel to the GPU machine with it, the sources do not.
 #
 # Include resolution: the apps use `#include "../raytracer/imageplane.h"`-style paths, which a compiler
 # resolves relative to the including file first.  For (b) the source is therefore piped to the compiler on
@@ -22,7 +22,7 @@ REF=${REF:-/root/reference}
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 HOST=$ROOT/raytrace_cpu_amd/host
 CPUOUT=$ROOT/oracle/_ref/apps
-GPUOUT=$ROOT/dropin/_build
+GPUOUT=$ROOT/oracle/_ref/dropin
 FLAGS="-O2 -std=c++14 -ffp-contract=off -fopenmp -w"
 CFITS_INC=${CFITS_INC:-/opt/conda/include}
 CFITS_LIB=${CFITS_LIB:-/opt/conda/lib}
@@ -39,7 +39,7 @@ build() {   # name  source  extra-flags  [sed-expression]
     ( cd $(dirname $src) && $feed | g++ $FLAGS $extra -I$REF/src -I$REF/src/raytracer -x c++ - -x none $REFLIB -o $CPUOUT/$name ${LINK:-} )
     # (b) this repo: headers from $HOST first, reference utilities second
     ( cd $HOST/raytracer && $feed | g++ $FLAGS $extra -I$HOST -I$REF/src -I$(dirname $src) -x c++ - -x none -o $GPUOUT/$name \
-        -L$HOST -lkr_host -L$ROOT/raytrace_cpu_amd/csrc -lkrtrace -Wl,-rpath,'$ORIGIN/../../raytrace_cpu_amd/host' -Wl,-rpath,'$ORIGIN/../../raytrace_cpu_amd/csrc' )
+        -L$HOST -lkr_host -L$ROOT/raytrace_cpu_amd/csrc -lkrtrace -Wl,-rpath,'$ORIGIN/../../../raytrace_cpu_amd/host' -Wl,-rpath,'$ORIGIN/../../../raytrace_cpu_amd/csrc' )
     echo "built $name"
 }
 

@@ -2,7 +2,7 @@
 # GPU box: the reference's emissivity main() on the class API under different OMP_NUM_THREADS (KR_TIMING marks).  usage: scripts/app_threads.sh [threads ...]
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 PAR=$ROOT/raytrace_cpu_amd/apps/par
-DROPIN=$ROOT/dropin/_build
+DROPIN=$ROOT/oracle/_ref/dropin
 export LD_PRELOAD=/usr/lib/x86_64-linux-gnu/libstdc++.so.6
 export KR_TIMING=1
 for nt in "${@:-default}"; do

@@ -7,7 +7,7 @@ for nt in "$@"; do
   export KRTRACE_HOST_THREADS=$nt
   echo "== KRTRACE_HOST_THREADS=$nt"
   t0=$(date +%s%N)
-  ( cd $W/run && $ROOT/dropin/_build/emissivity --outfile=$W/out.dat 2>&1 | grep -E "kr_timing" | grep -E "first touched|redshift_start|staged|run_raytrace: end|dtor: end" | cut -c1-140 | head -8 )
+  ( cd $W/run && $ROOT/oracle/_ref/dropin/emissivity --outfile=$W/out.dat 2>&1 | grep -E "kr_timing" | grep -E "first touched|redshift_start|staged|run_raytrace: end|dtor: end" | cut -c1-140 | head -8 )
   t1=$(date +%s%N); echo "wall $(( (t1 - t0) / 1000000 )) ms"
   rm -rf $W
 done

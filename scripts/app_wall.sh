@@ -5,7 +5,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out; mkdir -p $OUT
 PAR=$ROOT/raytrace_cpu_amd/apps/par
 NATIVE=$ROOT/raytrace_cpu_amd/apps/_build
-DROPIN=$ROOT/dropin/_build
+DROPIN=$ROOT/oracle/_ref/dropin
 export LD_PRELOAD=/usr/lib/x86_64-linux-gnu/libstdc++.so.6
 W=$(mktemp -d)
 timed() { local t0=$(date +%s%N); "$@" 2>&1 | grep -E "timing|rror" | cut -c1-200 ; local t1=$(date +%s%N); echo "wall $(( (t1 - t0) / 1000000 )) ms"; }

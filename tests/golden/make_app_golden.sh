@@ -1,6 +1,6 @@
 #!/bin/bash
 # Regenerates tests/golden/apps/*.{dat,fits,txt}: outputs of the REFERENCE's own applications (CPU build,
-# oracle/_ref/apps/, produced by dropin/build_apps.sh from the sources under /root/reference) on the par
+# oracle/_ref/apps/, produced by oracle/build_dropin_apps.sh from the reference sources) on the par
 # files next to this script.  Build container only.  Fixtures are the apps' output files (data), nothing else.
 set -euo pipefail
 HERE=$(cd "$(dirname "$0")" && pwd)

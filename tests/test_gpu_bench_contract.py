@@ -15,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_line_and_kernel_overlap_under_rccl():
     env = dict(os.environ, KR_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29561", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"],
                        capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -86,7 +86,7 @@ def test_cpu_baseline_leg_checks_the_timed_pipeline(workload, key, rays):
     (device-built rays, fused passes) beside the checks of the reference-constructed rays -- for the PointSource every bin count, the disc-ray count
     and the step total equal the CPU's (the device constructor carries the reference's bits)."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--rays", rays, "--cpu-sample-rays", "60000", "--steps", "1", "--warmup", "1",
-                        "--no-fast-math-extra"], capture_output=True, text=True, timeout=900)
+                        "--full", "--no-fast-math-extra"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     cb = d["cpu_baseline"]
@@ -100,3 +100,27 @@ def test_cpu_baseline_leg_checks_the_timed_pipeline(workload, key, rays):
         assert chk["disc_rays_cpu"] > 1000 and abs(chk["disc_rays_device"] - chk["disc_rays_cpu"]) <= 2, chk
         assert chk["pixels_count_mismatch"] <= 4, chk
         assert max(chk["max_rel_diff_of_pixel_sums(RADIUS, ENSHIFT, FLUX, TIME)"].values()) <= 1e-6, chk
+
+
+def test_plain_run_times_only_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the headline alone (no other arithmetic modes, no CPU baseline); --steps sets the timed steps;
+    --dump-outputs writes the last timed step's histogram, which agrees with the line's own disc-hit count."""
+    import numpy as np
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--rays", "3e5",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert "other_arithmetic_modes" not in d and "cpu_baseline" not in d
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in d, key
+    names = ("count", "flux", "emis", "sum_redshift", "sum_time")
+    got = {k: np.load(out / f"emissivity_{k}.npy") for k in names}
+    assert all(a.dtype == np.float64 and a.shape == (100,) for a in got.values())
+    disc = np.load(out / "emissivity_disc_rays.npy")
+    assert disc.tolist() == [d["disc_hits"]] and 0 < got["count"].sum() <= d["disc_hits"]
+    counters = np.load(out / "trace_counters.npy")
+    assert counters.tolist() == [float(d["config"]["rays_total"]), float(d["rk_steps_per_launch"])]

@@ -1,5 +1,5 @@
 """GPU: the reference's OWN application binaries, compiled unchanged against this repo's host-side API mirror and
-libkrtrace.so (dropin/build_apps.sh -> dropin/_build/, built in the build container and shipped as binaries),
+libkrtrace.so (oracle/build_dropin_apps.sh -> oracle/_ref/dropin/, built where the reference sources are and shipped as binaries),
 produce the same output files as their CPU builds (fixtures in tests/golden/apps/).  Skipped where the binaries
 were not built (they need the reference sources at build time)."""
 import os
@@ -16,7 +16,7 @@ from test_oracle_app_outputs import APPS, load_dat
 
 pytestmark = pytest.mark.gpu
 
-BUILD = os.path.join(gc.ROOT, "dropin", "_build")
+BUILD = os.path.join(gc.ROOT, "oracle", "_ref", "dropin")
 ENV = dict(os.environ, LD_PRELOAD="/usr/lib/x86_64-linux-gnu/libstdc++.so.6", LD_LIBRARY_PATH="/opt/conda/lib")
 
 
@@ -39,7 +39,7 @@ def close_to_cpu(test, case, g, w, rtol=1e-6, atol=0.0):
 def need(app):
     path = os.path.join(BUILD, app)
     if not os.path.exists(path):
-        pytest.skip(f"{path} not built (dropin/build_apps.sh needs the reference sources)")
+        pytest.skip(f"{path} not built (oracle/build_dropin_apps.sh needs the reference sources)")
     return path
 
 
