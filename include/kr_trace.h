@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define KR_ABI_VERSION 15
+#define KR_ABI_VERSION 16
 
 /* error codes */
 #define KR_OK          0
@@ -214,6 +214,36 @@ typedef struct kr_return_bins {
     int32_t pad;
 } kr_return_bins;
 
+/* Emission-line profile / reverberation transfer function from image-plane rays (the reference builds it outside its C++, in
+ * python/line_from_image.ipynb, from the ENSHIFT and RADIUS planes of the image FITS file).  Per ray record, after redshift(-1, reverse=1):
+ *   filter   steps > 0, z = r cos(theta) < 1e-2, r_isco <= r < r_disc, g > 0 with g = rays[].redshift (the disc-image filter of
+ *            imageplane_disc_image.cpp:127-128 without the pixel-range test).  A ray that passes counts in `on_disc`.
+ *   emis     powerlaw3(r) (imageplane_disc_image.cpp:20-28) when table_emis == NULL; otherwise table_emis[ir] with the emissivity app's
+ *            index ir = (int) (log(r / table_r_min) / log(table_dr)) (table_logbin) or (int) ((r - table_r_min) / table_dr), truncated
+ *            (emissivity.cpp:58, :106).  A ray with ir outside [0, table_nr) or a non-finite table_emis[ir] passes the filter but is not binned.
+ *   E, w, tau   E = line_energy / g;  w = emis * g^(-g_index);  tau = t + table_time[ir] - t0 (the table_time term is 0 without that table).
+ *   bins     i = floor((E - e_min) / de), or floor(log(E / e_min) / log(de)) with log_e;  j = floor(tau / dt), or 0 without a time axis
+ *            (nt == 1 and dt <= 0).  A NaN index or one outside [0, ne) / [0, nt) is not binned.
+ * Output: double[2 nt ne + 2] = [count (nt x ne, time-major: [j ne + i]) | flux = sum of w (nt x ne) | on_disc | binned]; counts are doubles.
+ * The per-pixel form (kr_line_from_image_dev_f64) reads the raw-sum planes of kr_reduce_image_dev_f64 / kr_post_image_dev_f64: for each pixel with
+ * nrays > 0 (which counts in on_disc), with means e = enshift / nrays (the mean of 1/g), r = r / nrays, t = time / nrays: E = line_energy e,
+ * w = emis(r) e^g_index, tau = t (+ table_time[ir]) - t0; same bin rules.  The table is copied to the device (and cached) by the call. */
+typedef struct kr_line_bins {
+    double line_energy;            /* rest-frame line energy (e.g. 6.4) */
+    double e_min, de;              /* energy bins; log_e: de is the ratio between edges */
+    double t0, dt;                 /* time bins; dt <= 0 (and nt == 1): no time axis */
+    double r_isco, r_disc;         /* disc filter of imageplane_disc_image.cpp:127-128 */
+    double q1, rb1, q2, rb2, q3;   /* powerlaw3 emissivity (imageplane_disc_image.cpp:20-28), used when table_emis == NULL */
+    double g_index;                /* weight exponent: 3 = the notebook's enshift**3 and the FLUX plane's 1/g^3 */
+    double table_r_min, table_dr;  /* optional radial table, binned like kr_emis_bins (emissivity.cpp:58, :106) */
+    const double* table_emis;      /* HOST, table_nr values, or NULL */
+    const double* table_time;      /* HOST, table_nr values (source->disc delay), or NULL */
+    int32_t ne, nt, log_e, table_nr, table_logbin, pad;
+} kr_line_bins;
+#ifdef __cplusplus
+static_assert(sizeof(kr_line_bins) == 160, "kr_line_bins is 160 bytes (raytrace_cpu_amd/capi.py LineBins)");
+#endif
+
 /* ---- runtime ---------------------------------------------------------------------------------- */
 int         kr_abi_version(void);
 const char* kr_last_error(void);
@@ -372,6 +402,20 @@ int kr_post_return_dev_f64(double lo, double hi, const kr_return_bins* b, void* 
  * device, ADDED into); the same rays[] and, up to the order of the additions, the same sums as `count` single calls, in ceil(count / 32) launches. */
 int kr_post_return_batch_dev_f64(int32_t count, double lo, double hi, const kr_return_bins* b, void* const* d_rays, const int64_t* n, void* const* d_out4,
                                  void* stream);
+
+/* ---- emission-line profile / transfer function (kr_line_bins above) --------------------------------------------------------------------
+ * Every entry point validates the bins first, before it touches a device: KR_EINVAL (message in kr_last_error) when ne < 1 or nt < 1, de <= 0,
+ * de <= 1 with log_e, e_min <= 0 with log_e, nt > 1 with dt <= 0, table_time without table_emis, table_nr < 1 with a table, a non-finite bin
+ * parameter, or ne nt > 2^24.  The _dev forms ADD into d_line (2 nt ne + 2 doubles on the device; zero it first), so shards and batches of
+ * rays can be summed.  kr_reduce_line_f64: host records, out = 2 nt ne + 2 host doubles (overwritten). */
+int kr_reduce_line_f64(const kr_line_bins* b, const kr_ray_f64* rays, int64_t n, double* out);
+int kr_reduce_line_dev_f64(const kr_line_bins* b, const void* d_rays, int64_t n, void* d_line, void* stream);
+/* redshift(V, reverse, projradius, motion) + range_phi(lo, hi) + the line bins in one pass (the sibling of kr_post_image_dev_f64);
+ * rays[] ends up exactly as after the separate calls */
+int kr_post_line_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_line_bins* b, void* d_rays, int64_t n,
+                         void* d_line, void* stream);
+/* the notebook's per-pixel form over d_planes (7 img_nx img_ny + 1 doubles, the layout of kr_reduce_image_dev_f64) */
+int kr_line_from_image_dev_f64(const kr_line_bins* b, const kr_image_bins* ib, const void* d_planes, void* d_line, void* stream);
 
 /* ---- diagnostics ------------------------------------------------------------------------------- */
 /* out[i] = op(a[i], b[i]) evaluated ON THE DEVICE with the exact primitive the trace kernel uses (host pointers):

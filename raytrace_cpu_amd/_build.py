@@ -12,7 +12,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["kr_trace.hip", "kr_post.hip", "kr_capi.hip"]
+SOURCES = ["kr_trace.hip", "kr_post.hip", "kr_capi.hip", "kr_line.hip"]
 HEADERS = ["kr_device.hpp", "kr_crmath.hpp", "kr_arith.hpp", "kr_fast.hpp", "kr_rk45.hpp", "kr_post_device.hpp", "kr_sincos.hpp", "kr_replay.hpp", "kr_common.hpp", os.path.join("..", "..", "include", "kr_trace.h")]
 LIB = os.path.join(CSRC, "libkrtrace.so")
 ARCH = "gfx950"
@@ -52,7 +52,7 @@ def build(force=False, verbose=False, extra_flags=(), tag=""):
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)
 
-    with ThreadPoolExecutor(max_workers=3) as ex:
+    with ThreadPoolExecutor(max_workers=len(SOURCES)) as ex:
         list(ex.map(run, jobs))
     if force or jobs or _stale(lib, objs):
         run([hipcc(), "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib, *objs])

@@ -192,3 +192,85 @@ def image_planes_from_words(words, nx, ny):
     for q, k in enumerate(("flux", "r", "phi", "enshift", "time", "emis")):
         out[k] = words[(q + 1) * npix:(q + 2) * npix]
     return out
+
+
+def line_words(bins):
+    """Length of the line histogram buffer: [count (nt x ne) | flux (nt x ne) | on_disc | binned] (include/kr_trace.h, kr_line_bins)."""
+    return 2 * bins.nt * bins.ne + 2
+
+
+def line_from_words(bins, words):
+    """The histogram buffer of the line entry points as a dict: count / flux of shape (nt, ne), on_disc, binned, and the bin edges
+    (time_edges is None without a time axis)."""
+    ne, nt = bins.ne, bins.nt
+    words = np.asarray(words, dtype=np.float64)
+    k = np.arange(ne + 1)
+    e_edges = bins.e_min * bins.de ** k if bins.log_e else bins.e_min + bins.de * k
+    t_edges = None if (nt == 1 and bins.dt <= 0) else bins.t0 + bins.dt * np.arange(nt + 1)
+    return {"count": words[:nt * ne].reshape(nt, ne).copy(), "flux": words[nt * ne:2 * nt * ne].reshape(nt, ne).copy(),
+            "on_disc": int(round(float(words[2 * nt * ne]))), "binned": int(round(float(words[2 * nt * ne + 1]))),
+            "energy_edges": e_edges, "time_edges": t_edges}
+
+
+def reduce_line(bins, rays):
+    """kr_reduce_line_f64: the emission line (or transfer function) of host ray records after redshift(-1, reverse=1)."""
+    _rays_arg(rays, capi.RAY_F64)
+    out = np.zeros(line_words(bins))
+    capi.check(lib(), lib().kr_reduce_line_f64(C.byref(bins), _ptr(rays), len(rays), _ptr(out)), "kr_reduce_line")
+    return line_from_words(bins, out)
+
+
+def default_image_bins(spec, bins):
+    """One pixel per ray of the image plane `spec`, centred on it (img_dx = dx, the grid shifted by half a pixel, so no ray sits on a pixel
+    edge or off the grid), with the disc filter and powerlaw3 of the line bins."""
+    _, nx, ny = imageplane_count(spec)
+    ib = capi.ImageBins()
+    ib.x0, ib.y0, ib.img_dx, ib.img_dy = spec.x0 - spec.dx / 2, spec.y0 - spec.dy / 2, spec.dx, spec.dy
+    ib.r_isco, ib.r_disc = bins.r_isco, bins.r_disc
+    ib.q1, ib.rb1, ib.q2, ib.rb2, ib.q3 = bins.q1, bins.rb1, bins.q2, bins.rb2, bins.q3
+    ib.img_nx, ib.img_ny, ib.flip_image = nx, ny, 1
+    return ib
+
+
+def line_profile(imageplane_spec, params, bins, mode="rays", image_bins=None):
+    """The emission line of an image plane, resident on the device from start to finish, as the kr_line_profile app runs it:
+    ImagePlane ctor + redshift_start (kr_imageplane_init_emit_dev_f64) -> trace (kr_trace_dev_f64) -> either
+      mode="rays":   redshift + range_phi + line bins per ray (kr_post_line_dev_f64), or
+      mode="pixels": redshift + range_phi + the image planes (kr_post_image_dev_f64, `image_bins`; default: one pixel per ray)
+                     -> line bins per pixel, the notebook's form (kr_line_from_image_dev_f64).
+    `params` as for the image app: the stored (negated) spin, theta / r limits, integrator.  Only the histogram is read back.
+    Returns line_from_words(...) plus "stats" (the trace's kr_stats)."""
+    if mode not in ("rays", "pixels"):
+        raise KrError(f"line_profile: mode must be 'rays' or 'pixels', got {mode!r}")
+    L = lib()
+    n, _, _ = imageplane_count(imageplane_spec)
+    if n <= 0:
+        raise KrError("line_profile: empty ray grid")
+    spin = -1 * imageplane_spec.spin                     # as stored by the Raytracer of an ImagePlane (imageplane.cpp:12)
+    nw = line_words(bins)
+    d_rays, d_line, d_planes = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    st = Stats()
+    try:
+        capi.check(L, L.kr_malloc(C.byref(d_rays), n * capi.RAY_F64.itemsize), "kr_malloc")
+        capi.check(L, L.kr_malloc(C.byref(d_line), nw * 8), "kr_malloc")
+        capi.check(L, L.kr_memset(d_line, 0, nw * 8), "kr_memset")
+        capi.check(L, L.kr_imageplane_init_emit_dev_f64(C.byref(imageplane_spec), 0, 1, 0.0, 1, 0, d_rays, n, None), "kr_imageplane_init_emit")
+        capi.check(L, L.kr_trace_dev_f64(C.byref(params), d_rays, n, None, C.byref(st)), "kr_trace_dev")
+        if mode == "rays":
+            capi.check(L, L.kr_post_line_dev_f64(spin, -1.0, 1, 0, 0, -np.pi, np.pi, C.byref(bins), d_rays, n, d_line, None), "kr_post_line")
+        else:
+            ib = image_bins if image_bins is not None else default_image_bins(imageplane_spec, bins)
+            npw = 7 * ib.img_nx * ib.img_ny + 1
+            capi.check(L, L.kr_malloc(C.byref(d_planes), npw * 8), "kr_malloc")
+            capi.check(L, L.kr_memset(d_planes, 0, npw * 8), "kr_memset")
+            capi.check(L, L.kr_post_image_dev_f64(spin, -1.0, 1, 0, 0, -np.pi, np.pi, C.byref(ib), d_rays, n, d_planes, None), "kr_post_image")
+            capi.check(L, L.kr_line_from_image_dev_f64(C.byref(bins), C.byref(ib), d_planes, d_line, None), "kr_line_from_image")
+        out = np.zeros(nw)
+        capi.check(L, L.kr_memcpy_d2h(_ptr(out), d_line, nw * 8), "kr_memcpy_d2h")
+    finally:
+        for d in (d_rays, d_line, d_planes):
+            if d.value:
+                L.kr_free(d)
+    res = line_from_words(bins, out)
+    res["stats"] = st.as_dict()
+    return res

@@ -9,7 +9,7 @@ import os
 
 import numpy as np
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 KR_OK, KR_EINVAL, KR_ENODEVICE, KR_EHIP, KR_ENOMEM = 0, -1, -2, -3, -4
 EULER, RK4, RK45 = 0, 1, 2
@@ -70,6 +70,32 @@ class ImageBins(C.Structure):
 class ReturnBins(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("r_isco", "r_disc", "r_esc", "source_r", "source_phi")] + \
                [(n, C.c_int32) for n in ("plane_iso", "limb", "weight_norm", "pad")]
+
+
+class LineBins(C.Structure):
+    """kr_line_bins: emission-line energy x time bins (include/kr_trace.h has the per-ray rules).  table_emis / table_time are host
+    double arrays or None; keep the arrays alive while the struct is in use (LineBins.with_table does)."""
+    _fields_ = [(n, C.c_double) for n in ("line_energy", "e_min", "de", "t0", "dt", "r_isco", "r_disc", "q1", "rb1", "q2", "rb2", "q3", "g_index",
+                                          "table_r_min", "table_dr")] + \
+               [("table_emis", C.POINTER(C.c_double)), ("table_time", C.POINTER(C.c_double))] + \
+               [(n, C.c_int32) for n in ("ne", "nt", "log_e", "table_nr", "table_logbin", "pad")]
+
+    def with_table(self, r_min, dr, emis, time=None, logbin=True):
+        """Attach a radial emissivity (and optional source->disc time) table binned like kr_emis_bins; returns self."""
+        self._table = [np.ascontiguousarray(emis, dtype=np.float64)] + ([np.ascontiguousarray(time, dtype=np.float64)] if time is not None else [])
+        self.table_r_min, self.table_dr, self.table_logbin, self.table_nr = r_min, dr, int(logbin), len(self._table[0])
+        self.table_emis = self._table[0].ctypes.data_as(C.POINTER(C.c_double))
+        self.table_time = self._table[1].ctypes.data_as(C.POINTER(C.c_double)) if time is not None else None
+        return self
+
+
+def line_bins(line_energy=6.4, e_min=1.0, de=0.1, ne=90, log_e=False, t0=0.0, dt=0.0, nt=1, r_isco=1.0, r_disc=1000.0, q1=3.0, rb1=4.0, q2=3.0,
+              rb2=10.0, q3=3.0, g_index=3.0):
+    b = LineBins()
+    b.line_energy, b.e_min, b.de, b.ne, b.log_e = line_energy, e_min, de, ne, int(log_e)
+    b.t0, b.dt, b.nt = t0, dt, nt
+    b.r_isco, b.r_disc, b.q1, b.rb1, b.q2, b.rb2, b.q3, b.g_index = r_isco, r_disc, q1, rb1, q2, rb2, q3, g_index
+    return b
 
 
 def default_params(spin, horizon=None):
@@ -168,6 +194,10 @@ PROTOTYPES = {
     "kr_post_return_dev_f64": (_int, [_dbl, _dbl, P(ReturnBins), _vp, _i64, _vp, _vp]),
     "kr_post_return_batch_dev_f64": (_int, [_i32, _dbl, _dbl, P(ReturnBins), P(_vp), P(_i64), P(_vp), _vp]),
     "kr_pointsource_init_emit_batch_dev_f64": (_int, [_i32, P(PointSourceSpec), P(_dbl), _int, _int, P(_vp), P(_i64), _vp]),
+    "kr_reduce_line_f64": (_int, [P(LineBins), _vp, _i64, _vp]),
+    "kr_reduce_line_dev_f64": (_int, [P(LineBins), _vp, _i64, _vp, _vp]),
+    "kr_post_line_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, P(LineBins), _vp, _i64, _vp, _vp]),
+    "kr_line_from_image_dev_f64": (_int, [P(LineBins), P(ImageBins), _vp, _vp, _vp]),
     "kr_debug_arith_f64": (_int, [_int, _vp, _vp, _vp, _i64]),
     "kr_host_attach": (_int, [_vp, _i64, _i32]),
     "kr_host_detach": (_int, [_vp]),

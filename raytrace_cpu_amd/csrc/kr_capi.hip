@@ -46,6 +46,13 @@ int post_return_dev(double lo, double hi, const kr_return_bins* b, void* d, int6
 int post_return_batch_dev(int count, double lo, double hi, const kr_return_bins* b, void* const* d, const int64_t* n, void* const* d_out4, hipStream_t st);
 int pointsource_init_emit_batch_dev(int count, const kr_pointsource* s, const double* V, int reverse, int projradius, void* const* d, const int64_t* n, hipStream_t st);
 int arith_probe_dev(int op, const double* a, const double* b, double* out, int64_t n);
+// implemented in kr_line.hip
+int line_validate(const kr_line_bins* b, const char* who);
+int reduce_line_dev(const kr_line_bins* b, const void* d, int64_t n, void* d_line, hipStream_t st);
+int post_line_dev(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_line_bins* b, void* d, int64_t n,
+                  void* d_line, hipStream_t st);
+int line_from_image_dev(const kr_line_bins* b, const kr_image_bins* ib, const void* d_planes, void* d_line, hipStream_t st);
+void line_tables_shutdown();
 
 static thread_local std::string g_error;
 
@@ -702,6 +709,58 @@ int kr_reduce_image_f64(const kr_image_bins* b, const kr_ray_f64* rays, int64_t 
     return KR_OK;
 }
 
+// ---- emission line (kr_line.hip): the bins are validated before anything touches a device ----------------------------------
+int kr_reduce_line_dev_f64(const kr_line_bins* b, const void* d, int64_t n, void* d_line, void* st)
+{
+    int rc = line_validate(b, "kr_reduce_line");
+    if (rc != KR_OK) return rc;
+    if (!d_line || (n > 0 && !d)) { set_error("kr_reduce_line: null argument"); return KR_EINVAL; }
+    rc = require_device();
+    return rc != KR_OK ? rc : reduce_line_dev(b, d, n, d_line, (hipStream_t) st);
+}
+
+int kr_post_line_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_line_bins* b, void* d, int64_t n,
+                         void* d_line, void* st)
+{
+    int rc = line_validate(b, "kr_post_line");
+    if (rc != KR_OK) return rc;
+    if (!d_line || (n > 0 && !d)) { set_error("kr_post_line: null argument"); return KR_EINVAL; }
+    rc = require_device();
+    return rc != KR_OK ? rc : post_line_dev(spin, V, reverse, projradius, motion, lo, hi, b, d, n, d_line, (hipStream_t) st);
+}
+
+int kr_line_from_image_dev_f64(const kr_line_bins* b, const kr_image_bins* ib, const void* d_planes, void* d_line, void* st)
+{
+    int rc = line_validate(b, "kr_line_from_image");
+    if (rc != KR_OK) return rc;
+    if (!ib || !d_planes || !d_line) { set_error("kr_line_from_image: null argument"); return KR_EINVAL; }
+    if (ib->img_nx <= 0 || ib->img_ny <= 0) { set_error("kr_line_from_image: image size must be positive"); return KR_EINVAL; }
+    rc = require_device();
+    return rc != KR_OK ? rc : line_from_image_dev(b, ib, d_planes, d_line, (hipStream_t) st);
+}
+
+int kr_reduce_line_f64(const kr_line_bins* b, const kr_ray_f64* rays, int64_t n, double* out)
+{
+    int rc = line_validate(b, "kr_reduce_line");
+    if (rc != KR_OK) return rc;
+    if (!out || (n > 0 && !rays)) { set_error("kr_reduce_line: null argument"); return KR_EINVAL; }
+    const size_t words = (size_t) 2 * b->nt * b->ne + 2;
+    std::vector<double> h(words, 0.0);
+    rc = with_staged_rays((void*) rays, n, sizeof(kr_ray_f64), true, false, nullptr, [&](void* d) {
+        DeviceBuffer line;
+        int r2 = line.alloc(words * sizeof(double));
+        if (r2 != KR_OK) return r2;
+        KR_HIP(hipMemset(line.p, 0, words * sizeof(double)));
+        r2 = reduce_line_dev(b, d, n, line.p, nullptr);
+        if (r2 != KR_OK) return r2;
+        KR_HIP(hipMemcpy(h.data(), line.p, words * sizeof(double), hipMemcpyDeviceToHost));
+        return (int) KR_OK;
+    });
+    if (rc != KR_OK) return rc;
+    std::memcpy(out, h.data(), words * sizeof(double));
+    return KR_OK;
+}
+
 int kr_reduce_return_dev_f64(const kr_return_bins* b, const void* d, int64_t n, void* d_out4, void* st)
 {
     if (!b || !d_out4) { set_error("kr_reduce_return: null argument"); return KR_EINVAL; }
@@ -873,6 +932,7 @@ int kr_shutdown(void)
     if (!g_runtime_touched) return KR_OK;
     const int rc = trace_shutdown();       // (drains every device this library has used)
     source_tables_shutdown();
+    line_tables_shutdown();
     return rc;
 }
 

@@ -1,0 +1,311 @@
+// kr_line.hip -- emission-line profiles and reverberation transfer functions from image-plane traces (include/kr_trace.h, kr_line_bins).
+// The reference builds the line outside its C++ (python/line_from_image.ipynb: ENSHIFT and RADIUS planes of the image FITS file, weight
+// emis(r) enshift^3, summed into energy bins); here the rays (or the raw image planes) are binned where they already are, in HBM, and only
+// the 2 nt ne + 2 doubles of the histogram leave the device.
+//   reduce_line_kernel      records after redshift(-1, reverse=1) -> line bins
+//   post_line_kernel        redshift + range_phi + line bins in one pass (the sibling of post_image_kernel; same per-ray functions)
+//   line_from_image_kernel  raw-sum image planes (kr_reduce_image_dev_f64 layout) -> line bins, per pixel
+// All three are streaming passes, one record / pixel per work-item.  The histogram is privatised per workgroup in LDS when it fits
+// kLineLdsWords (ds_add_f64), flushed with one global atomic per non-zero word; above that the items add into the global histogram directly.
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <map>
+#include <mutex>
+#include <string>
+#include <tuple>
+
+#include "kr_common.hpp"
+#include "kr_device.hpp"
+#include "kr_post_device.hpp"
+
+namespace kr {
+
+namespace {
+
+constexpr int kBlock = 256;
+// Per-workgroup LDS budget of the privatised histogram: 4096 doubles = 32 KiB, i.e. ne nt <= 2047.  Registers bound the residency first
+// (-Rpass-analysis=kernel-resource-usage, gfx950: post_line 194 VGPRs -> 2 waves / SIMD = 2 workgroups / CU, reduce_line 144 -> 3,
+// line_from_image 109 -> 4), and 4 x 32 KiB fit the CU's 160 KiB: the LDS never lowers the occupancy of any of the three; a 64-KiB
+// budget would halve line_from_image's.
+constexpr int kLineLdsWords = 4096;
+
+inline int grid_for(int64_t n, int cap_blocks = 256 * 4)
+{
+    const int64_t b = (n + kBlock - 1) / kBlock;
+    return (int) std::max<int64_t>(1, std::min<int64_t>(b, cap_blocks));
+}
+
+#define KR_LAUNCH_CHECK() KR_HIP(hipGetLastError())
+
+// what the kernels need besides the records: the bins by value (their host table pointers are never dereferenced on the device), the
+// device copy of the table, and the two logarithms of the bin ratios (taken once, on the host)
+struct LineDev {
+    kr_line_bins b;
+    const double* t_emis;      // [table_nr] on the device, or null: powerlaw3
+    const double* t_time;      // [table_nr] on the device, or null
+    double log_de, log_tdr;
+    int time_axis;             // 0: j = 0 for every item (nt == 1, dt <= 0)
+    int words;                 // 2 nt ne + 2
+};
+
+// one item that passed the filter -> at most one bin.  PIXEL: x is the pixel's mean 1/g (E = line_energy x, w = emis x^g_index);
+// otherwise x is g (E = line_energy / g, w = emis g^-g_index).  Returns 1 if the item was binned.
+template <bool PIXEL>
+KR_DEV unsigned line_accumulate(double* acc, const LineDev& L, double r, double x, double t)
+{
+    const kr_line_bins& b = L.b;
+    double emis, tt = 0;
+    if (L.t_emis) {
+        // the emissivity app's index (emissivity.cpp:106): truncation, so (-1, table_nr) is the range that lands in [0, table_nr)
+        const double fi = b.table_logbin ? kr_log(r / b.table_r_min) / L.log_tdr : (r - b.table_r_min) / b.table_dr;
+        if (!(fi > -1 && fi < b.table_nr)) return 0;
+        const int ir = (int) fi;
+        emis = L.t_emis[ir];
+        if (!__builtin_isfinite(emis)) return 0;
+        if (L.t_time) tt = L.t_time[ir];
+    } else {
+        emis = powerlaw3(r, b.q1, b.rb1, b.q2, b.rb2, b.q3);
+    }
+    const double E = PIXEL ? b.line_energy * x : b.line_energy / x;
+    const double w = emis * (PIXEL ? kr_pow(x, b.g_index) : kr_pow(x, -1 * b.g_index));
+    const double fe = b.log_e ? kr_log(E / b.e_min) / L.log_de : (E - b.e_min) / b.de;
+    if (!(fe >= 0 && fe < b.ne)) return 0;              // NaN fails too
+    int j = 0;
+    if (L.time_axis) {
+        const double ft = (t + tt - b.t0) / b.dt;
+        if (!(ft >= 0 && ft < b.nt)) return 0;
+        j = (int) ft;
+    }
+    const int k = j * b.ne + (int) fe;
+    atomicAdd(&acc[k], 1.0);
+    atomicAdd(&acc[b.nt * b.ne + k], w);
+    return 1;
+}
+
+// the disc filter of imageplane_disc_image.cpp:127-128 without the pixel-range test
+KR_DEV bool line_filter(const kr_line_bins& b, int steps, double r, double theta, double g)
+{
+    if (!(steps > 0)) return false;
+    const double z = r * kr_cos(theta);
+    return z < 1E-2 && r >= b.r_isco && r < b.r_disc && g > 0;
+}
+
+template <bool USE_LDS>
+KR_DEV double* line_begin(double* lds, double* out, int words)
+{
+    if (!USE_LDS) return out;
+    for (int w = threadIdx.x; w < words; w += kBlock) lds[w] = 0;
+    __syncthreads();
+    return lds;
+}
+
+template <bool USE_LDS>
+KR_DEV void line_end(double* lds, double* out, int words, unsigned long long on_disc, unsigned long long binned)
+{
+    double* acc = USE_LDS ? lds : out;
+    if (on_disc) atomicAdd(&acc[words - 2], (double) on_disc);
+    if (binned) atomicAdd(&acc[words - 1], (double) binned);
+    if (USE_LDS) {
+        __syncthreads();
+        for (int w = threadIdx.x; w < words; w += kBlock)
+            if (lds[w] != 0) atomicAdd(&out[w], lds[w]);
+    }
+}
+
+template <bool USE_LDS>
+__global__ void __launch_bounds__(kBlock)
+reduce_line_kernel(const kr_ray_f64* __restrict__ rays, long long n, LineDev L, double* __restrict__ out)
+{
+    extern __shared__ double lds[];
+    double* acc = line_begin<USE_LDS>(lds, out, L.words);
+    unsigned long long on_disc = 0, binned = 0;
+    for (long long i = blockIdx.x * (long long) kBlock + threadIdx.x; i < n; i += (long long) gridDim.x * kBlock) {
+        const kr_ray_f64* ray = &rays[i];
+        const double r = ray->r, g = ray->redshift;
+        if (!line_filter(L.b, ray->steps, r, ray->theta, g)) continue;
+        on_disc++;
+        binned += line_accumulate<false>(acc, L, r, g, ray->t);
+    }
+    line_end<USE_LDS>(lds, out, L.words, on_disc, binned);
+}
+
+// redshift(V, reverse, projradius, motion) + range_phi(lo, hi) + the line bins: the per-ray code of post_image_kernel (kr_post.hip) with the
+// seven planes replaced by the line, so rays[] ends bit-identical to the separate passes
+template <bool USE_LDS>
+__global__ void __launch_bounds__(kBlock)
+post_line_kernel(kr_ray_f64* __restrict__ rays, long long n, double spin, double V, int reverse, int projradius, int motion, double lo, double hi,
+                 LineDev L, double* __restrict__ out)
+{
+    extern __shared__ double lds[];
+    double* acc = line_begin<USE_LDS>(lds, out, L.words);
+    unsigned long long on_disc = 0, binned = 0;
+    for (long long i = blockIdx.x * (long long) kBlock + threadIdx.x; i < n; i += (long long) gridDim.x * kBlock) {
+        kr_ray_f64* ray = &rays[i];
+        kr_ray_f64 v;
+        v.r = ray->r; v.theta = ray->theta; v.k = ray->k; v.h = ray->h; v.Q = ray->Q; v.rdot_sign = ray->rdot_sign; v.thetadot_sign = ray->thetadot_sign;
+        v.emit = ray->emit;
+        const int steps = ray->steps;
+        const double g = redshift_value(v, spin, V, reverse, projradius, motion);
+        ray->redshift = g;
+        const double phi = ray->phi;
+        const double wrapped = range_phi_value<double>(phi, steps, lo, hi);
+        if (!(wrapped == phi) && wrapped == wrapped) ray->phi = wrapped;
+        if (!line_filter(L.b, steps, v.r, v.theta, g)) continue;
+        on_disc++;
+        binned += line_accumulate<false>(acc, L, v.r, g, ray->t);
+    }
+    line_end<USE_LDS>(lds, out, L.words, on_disc, binned);
+}
+
+// planes: [nrays | flux | r | phi | enshift | time | emis](npix each) + disc_count, raw sums (kr_reduce_image_dev_f64)
+template <bool USE_LDS>
+__global__ void __launch_bounds__(kBlock)
+line_from_image_kernel(const double* __restrict__ planes, long long npix, LineDev L, double* __restrict__ out)
+{
+    extern __shared__ double lds[];
+    double* acc = line_begin<USE_LDS>(lds, out, L.words);
+    unsigned long long on_disc = 0, binned = 0;
+    for (long long p = blockIdx.x * (long long) kBlock + threadIdx.x; p < npix; p += (long long) gridDim.x * kBlock) {
+        const double nrays = planes[p];
+        if (!(nrays > 0)) continue;
+        on_disc++;
+        const double e = planes[4 * npix + p] / nrays, r = planes[2 * npix + p] / nrays, t = planes[5 * npix + p] / nrays;
+        binned += line_accumulate<true>(acc, L, r, e, t);
+    }
+    line_end<USE_LDS>(lds, out, L.words, on_disc, binned);
+}
+
+// ---- the radial table on the device: one array [emis | time] per distinct (device, contents), built by the first call that needs it (hipMalloc
+//      and a blocking copy), kept until kr_shutdown -- the pattern of the PointSource angle tables (kr_post.hip).  A full cache is released
+//      together after draining the device, since a kernel in flight may still read one of its arrays. ----------------------------------------
+std::mutex g_line_mu;
+std::map<std::pair<int, std::string>, double*> g_line_tables;
+constexpr size_t kMaxLineTables = 64;
+
+int line_table(const kr_line_bins* b, const double** emis, const double** time)
+{
+    *emis = *time = nullptr;
+    if (!b->table_emis) return KR_OK;
+    int dev = 0;
+    KR_HIP(hipGetDevice(&dev));
+    const size_t nr = (size_t) b->table_nr, cols = b->table_time ? 2 : 1;
+    std::string bytes((const char*) b->table_emis, nr * sizeof(double));
+    if (b->table_time) bytes.append((const char*) b->table_time, nr * sizeof(double));
+    bytes.push_back((char) cols);
+    const auto key = std::make_pair(dev, bytes);
+    std::lock_guard<std::mutex> lk(g_line_mu);
+    auto it = g_line_tables.find(key);
+    double* d = nullptr;
+    if (it != g_line_tables.end()) {
+        d = it->second;
+    } else {
+        if (g_line_tables.size() >= kMaxLineTables) {
+            KR_HIP(hipDeviceSynchronize());
+            for (auto& kv : g_line_tables) (void) hipFree(kv.second);
+            g_line_tables.clear();
+        }
+        KR_HIP(hipMalloc((void**) &d, cols * nr * sizeof(double)));
+        const hipError_t e = hipMemcpy(d, bytes.data(), cols * nr * sizeof(double), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void) hipFree(d); return kr::hip_fail(e, "hipMemcpy(line table)", __FILE__, __LINE__); }
+        g_line_tables.emplace(key, d);
+    }
+    *emis = d;
+    if (b->table_time) *time = d + nr;
+    return KR_OK;
+}
+
+int line_dev(const kr_line_bins* b, LineDev* L)
+{
+    L->b = *b;
+    L->log_de = b->log_e ? std::log(b->de) : 0;
+    L->log_tdr = b->table_emis && b->table_logbin ? std::log(b->table_dr) : 0;
+    L->time_axis = !(b->nt == 1 && b->dt <= 0);
+    L->words = 2 * b->nt * b->ne + 2;
+    return line_table(b, &L->t_emis, &L->t_time);
+}
+
+}  // namespace
+
+int line_validate(const kr_line_bins* b, const char* who)
+{
+    auto bad = [&](const char* why) { set_error(std::string(who) + ": " + why); return KR_EINVAL; };
+    if (!b) return bad("null bins");
+    const double params[] = {b->line_energy, b->e_min, b->de, b->t0, b->dt, b->r_isco, b->r_disc, b->q1, b->rb1, b->q2, b->rb2, b->q3, b->g_index};
+    for (double v : params)
+        if (!std::isfinite(v)) return bad("non-finite bin parameter");
+    if (b->ne < 1 || b->nt < 1) return bad("ne and nt must be >= 1");
+    if ((int64_t) b->ne * b->nt > ((int64_t) 1 << 24)) return bad("ne * nt must not exceed 2^24");
+    if (!(b->de > 0)) return bad("de must be positive");
+    if (b->log_e && !(b->de > 1)) return bad("log_e: de (the ratio between edges) must be > 1");
+    if (b->log_e && !(b->e_min > 0)) return bad("log_e: e_min must be positive");
+    if (b->nt > 1 && !(b->dt > 0)) return bad("nt > 1 needs dt > 0");
+    if (b->table_time && !b->table_emis) return bad("table_time given without table_emis");
+    if (b->table_emis) {
+        if (b->table_nr < 1) return bad("table_nr must be >= 1 with a table");
+        if (!std::isfinite(b->table_r_min) || !std::isfinite(b->table_dr)) return bad("non-finite bin parameter");
+    }
+    return KR_OK;
+}
+
+int reduce_line_dev(const kr_line_bins* b, const void* d, int64_t n, void* d_line, hipStream_t st)
+{
+    if (n <= 0) return KR_OK;
+    LineDev L;
+    int rc = line_dev(b, &L);
+    if (rc != KR_OK) return rc;
+    if (L.words <= kLineLdsWords)
+        hipLaunchKernelGGL(reduce_line_kernel<true>, dim3(grid_for(n)), dim3(kBlock), L.words * sizeof(double), st, (const kr_ray_f64*) d, (long long) n, L,
+                           (double*) d_line);
+    else
+        hipLaunchKernelGGL(reduce_line_kernel<false>, dim3(grid_for(n)), dim3(kBlock), 0, st, (const kr_ray_f64*) d, (long long) n, L, (double*) d_line);
+    KR_LAUNCH_CHECK();
+    return KR_OK;
+}
+
+int post_line_dev(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_line_bins* b, void* d, int64_t n,
+                  void* d_line, hipStream_t st)
+{
+    if (n <= 0) return KR_OK;
+    LineDev L;
+    int rc = line_dev(b, &L);
+    if (rc != KR_OK) return rc;
+    if (L.words <= kLineLdsWords)
+        hipLaunchKernelGGL(post_line_kernel<true>, dim3(grid_for(n)), dim3(kBlock), L.words * sizeof(double), st, (kr_ray_f64*) d, (long long) n, spin, V,
+                           reverse, projradius, motion, lo, hi, L, (double*) d_line);
+    else
+        hipLaunchKernelGGL(post_line_kernel<false>, dim3(grid_for(n)), dim3(kBlock), 0, st, (kr_ray_f64*) d, (long long) n, spin, V, reverse, projradius,
+                           motion, lo, hi, L, (double*) d_line);
+    KR_LAUNCH_CHECK();
+    return KR_OK;
+}
+
+int line_from_image_dev(const kr_line_bins* b, const kr_image_bins* ib, const void* d_planes, void* d_line, hipStream_t st)
+{
+    const long long npix = (long long) ib->img_nx * ib->img_ny;
+    LineDev L;
+    int rc = line_dev(b, &L);
+    if (rc != KR_OK) return rc;
+    if (L.words <= kLineLdsWords)
+        hipLaunchKernelGGL(line_from_image_kernel<true>, dim3(grid_for(npix)), dim3(kBlock), L.words * sizeof(double), st, (const double*) d_planes, npix, L,
+                           (double*) d_line);
+    else
+        hipLaunchKernelGGL(line_from_image_kernel<false>, dim3(grid_for(npix)), dim3(kBlock), 0, st, (const double*) d_planes, npix, L, (double*) d_line);
+    KR_LAUNCH_CHECK();
+    return KR_OK;
+}
+
+void line_tables_shutdown()
+{
+    std::lock_guard<std::mutex> lk(g_line_mu);
+    for (auto& kv : g_line_tables) {
+        if (hipSetDevice(kv.first.first) == hipSuccess) (void) hipFree(kv.second);
+        else (void) hipGetLastError();
+    }
+    g_line_tables.clear();
+}
+
+}  // namespace kr

@@ -328,14 +328,7 @@ post_emissivity_kernel(kr_ray_f64* __restrict__ rays, long long n, double spin, 
     }
 }
 
-// ---- image reducer (imageplane_disc_image.cpp:20-28, :122-161) -------------------------------------------------
-KR_DEV double powerlaw3(double r, double q1, double rb1, double q2, double rb2, double q3)
-{
-    if (r < rb1) return kr_pow(r, -1 * q1);
-    else if (r < rb2) return kr_pow(rb1, q2 - q1) * kr_pow(r, -1 * q2);
-    else return kr_pow(rb1, q2 - q1) * kr_pow(rb2, q3 - q2) * kr_pow(r, -1 * q3);
-}
-
+// ---- image reducer (imageplane_disc_image.cpp:122-161; powerlaw3 in kr_post_device.hpp) --------------------------------
 // d_planes layout: [nrays | flux | r | phi | enshift | time | emis](npix each) + disc_count(1), doubles.
 // one ray's contribution to the seven image planes (imageplane_disc_image.cpp:122-161); returns 1 if it was counted
 KR_DEV unsigned image_accumulate(double* planes, long long npix, const kr_image_bins& b, int steps, double r, double theta, double phi, double t, double g,

@@ -187,6 +187,14 @@ KR_DEV kr_ray_f64 pointsource_ray(const kr_pointsource& s, const SourceTables& t
     return ray;
 }
 
+// ---- powerlaw3 emissivity (imageplane_disc_image.cpp:20-28): the image reducer (kr_post.hip) and the line reducer (kr_line.hip) ----
+KR_DEV double powerlaw3(double r, double q1, double rb1, double q2, double rb2, double q3)
+{
+    if (r < rb1) return kr_pow(r, -1 * q1);
+    else if (r < rb2) return kr_pow(rb1, q2 - q1) * kr_pow(r, -1 * q2);
+    else return kr_pow(rb1, q2 - q1) * kr_pow(rb2, q3 - q2) * kr_pow(r, -1 * q3);
+}
+
 // d_hist layout: [count(nr) | flux(nr) | emis(nr) | sum_redshift(nr) | sum_time(nr) | disc_count(1)], doubles.
 // LDS holds one private copy per workgroup when it fits (5*nr+1 doubles); flushed with global f64 atomics.
 constexpr int kMaxLdsBins = 1024;
