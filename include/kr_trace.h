@@ -227,7 +227,8 @@ typedef struct kr_return_bins {
  * Output: double[2 nt ne + 2] = [count (nt x ne, time-major: [j ne + i]) | flux = sum of w (nt x ne) | on_disc | binned]; counts are doubles.
  * The per-pixel form (kr_line_from_image_dev_f64) reads the raw-sum planes of kr_reduce_image_dev_f64 / kr_post_image_dev_f64: for each pixel with
  * nrays > 0 (which counts in on_disc), with means e = enshift / nrays (the mean of 1/g), r = r / nrays, t = time / nrays: E = line_energy e,
- * w = emis(r) e^g_index, tau = t (+ table_time[ir]) - t0; same bin rules.  The table is copied to the device (and cached) by the call. */
+ * w = emis(r) e^g_index, tau = t (+ table_time[ir]) - t0; same bin rules.  The call copies the table to the device once per distinct table; the copy
+ * stays there while the device's table cache has room and is freed only when no call holds it and the device has drained (or by kr_shutdown). */
 typedef struct kr_line_bins {
     double line_energy;            /* rest-frame line energy (e.g. 6.4) */
     double e_min, de;              /* energy bins; log_e: de is the ratio between edges */
@@ -258,8 +259,9 @@ int64_t     kr_pointsource_count(const kr_pointsource* s, int32_t* n_cosalpha, i
 int64_t     kr_imageplane_count(const kr_imageplane* s, int32_t* nx, int32_t* ny);                 /* imageplane.cpp:12-14 */
 /* The transcendental values of the PointSource constructor (pointsource.cpp:38-46: alpha = acos(cosalpha0 + i dcosalpha), beta = beta0 + j dbeta;
  * raytracer.cpp:631-672: sin / cos of alpha and beta, sin / cos / tan of the source's polar angle pos[2]) computed on the HOST with the C library
- * the reference calls.  The device constructors (kr_pointsource_init*_dev_f64) read exactly these -- they upload them once per (device, grid) and
- * keep them until kr_shutdown -- so k, h, Q of a device-built ray carry the reference constructor's bits.  Needs no GPU.
+ * the reference calls.  The device constructors (kr_pointsource_init*_dev_f64) read exactly these -- they upload them once per (device, grid), and
+ * the copy stays while the device's table cache has room (freed only when no call holds it and the device has drained, or by kr_shutdown) -- so
+ * k, h, Q of a device-built ray carry the reference constructor's bits.  Needs no GPU.
  * alpha_sincos: 2 * n_cosalpha doubles (sin, cos interleaved); beta_sincos: 2 * n_beta; pos_sin_cos_tan: 3.  Any of them may be NULL. */
 int         kr_pointsource_tables(const kr_pointsource* s, double* alpha_sincos, double* beta_sincos, double* pos_sin_cos_tan);
 
@@ -457,8 +459,9 @@ int kr_stream_destroy(void* stream);                /* also releases the interna
  * package sets the default in raytrace_cpu_amd/__init__.py, i.e. at import, before `import torch` can start the runtime; bench.py, the kr_* apps
  * and the class mirror call this function first thing. */
 int kr_configure_process(void);
-/* Waits for the devices the library has used, then releases every pooled trace workspace, internal stream and PointSource table.  Refused with
- * KR_EINVAL (nothing released) while a ticket of kr_trace_async_* / kr_trace_batch_async_f64 is outstanding: wait for or release the tickets first.
+/* Waits for the devices the library has used, then releases every pooled trace workspace, internal stream and device table (the PointSource angle
+ * tables and the line emissivity tables).  Refused with KR_EINVAL (nothing released) while a ticket of kr_trace_async_* / kr_trace_batch_async_f64
+ * is outstanding: wait for or release the tickets first.
  * Optional, and never done implicitly: at process exit the HIP runtime may already be gone when this library is unloaded. */
 int kr_shutdown(void);
 

@@ -52,7 +52,6 @@ int reduce_line_dev(const kr_line_bins* b, const void* d, int64_t n, void* d_lin
 int post_line_dev(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_line_bins* b, void* d, int64_t n,
                   void* d_line, hipStream_t st);
 int line_from_image_dev(const kr_line_bins* b, const kr_image_bins* ib, const void* d_planes, void* d_line, hipStream_t st);
-void line_tables_shutdown();
 
 static thread_local std::string g_error;
 
@@ -89,6 +88,74 @@ int DeviceBuffer::alloc(size_t bytes)
 {
     KR_HIP(hipMalloc(&p, bytes ? bytes : 1));
     return KR_OK;
+}
+
+// ---- the device table store (kr_common.hpp, TablePins) --------------------------------------------------------------------------------
+struct DeviceTable { double* d; int pins; };
+
+namespace {
+constexpr size_t kMaxDeviceTables = 256;                                // per device, both kinds together
+using TableMap = std::map<std::pair<int, std::string>, DeviceTable>;     // (kind, key) -> array
+std::mutex g_tables_mu;
+std::map<int, TableMap> g_tables;                                       // per device
+
+void free_unpinned(TableMap& tables)                                    // after draining their device
+{
+    for (auto it = tables.begin(); it != tables.end();) {
+        if (it->second.pins) { ++it; continue; }
+        (void) hipFree(it->second.d);
+        it = tables.erase(it);
+    }
+}
+}  // namespace
+
+int TablePins::lookup(TableKind kind, const std::string& key, const std::function<void(std::vector<double>&)>& fill, const double** out)
+{
+    int dev = 0;
+    KR_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(g_tables_mu);
+    auto& tables = g_tables[dev];
+    const auto k = std::make_pair((int) kind, key);
+    auto it = tables.find(k);
+    if (it == tables.end()) {
+        if (tables.size() >= kMaxDeviceTables) {          // full: drain this device, then free what no call holds
+            KR_HIP(hipDeviceSynchronize());
+            free_unpinned(tables);
+        }
+        std::vector<double> h;
+        fill(h);
+        double* d = nullptr;
+        KR_HIP(hipMalloc((void**) &d, h.size() * sizeof(double)));
+        const hipError_t e = hipMemcpy(d, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void) hipFree(d); return hip_fail(e, "hipMemcpy(device table)", __FILE__, __LINE__); }
+        it = tables.emplace(k, DeviceTable{d, 0}).first;
+    }
+    it->second.pins++;
+    held_.push_back(&it->second);
+    *out = it->second.d;
+    return KR_OK;
+}
+
+TablePins::~TablePins()
+{
+    if (held_.empty()) return;
+    std::lock_guard<std::mutex> lk(g_tables_mu);
+    for (DeviceTable* t : held_) t->pins--;
+}
+
+void device_tables_shutdown()
+{
+    int keep = 0;
+    const bool have_dev = hipGetDevice(&keep) == hipSuccess;
+    std::lock_guard<std::mutex> lk(g_tables_mu);
+    for (auto& dt : g_tables) {
+        if (dt.second.empty()) continue;
+        if (hipSetDevice(dt.first) != hipSuccess) { (void) hipGetLastError(); continue; }
+        (void) hipDeviceSynchronize();
+        free_unpinned(dt.second);
+    }
+    if (have_dev) (void) hipSetDevice(keep);
+    (void) hipGetLastError();
 }
 
 namespace {
@@ -931,9 +998,9 @@ int kr_shutdown(void)
 {
     if (!g_runtime_touched) return KR_OK;
     const int rc = trace_shutdown();       // (drains every device this library has used)
-    source_tables_shutdown();
-    line_tables_shutdown();
-    return rc;
+    if (rc != KR_OK) return rc;
+    device_tables_shutdown();
+    return KR_OK;
 }
 
 }  // extern "C"

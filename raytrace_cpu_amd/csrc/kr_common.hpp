@@ -4,7 +4,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <functional>
 #include <string>
+#include <vector>
 
 #include "../../include/kr_trace.h"
 
@@ -28,6 +30,27 @@ struct DeviceBuffer {
     int alloc(size_t bytes);
 };
 
+// ---- small constant tables that the host builds and the passes read on the device (the PointSource angle tables, the line emissivity tables) ----
+// One device array per distinct (device, kind, key), built by the first lookup that needs it: fill() writes the host contents, then a hipMalloc and
+// a blocking copy.  Every lookup pins its entry until the TablePins it was made through goes out of scope: keep that alive until the kernels that
+// read the arrays have been enqueued.  When a device holds kMaxDeviceTables entries (kr_capi.hip), a miss drains that device and frees its unpinned
+// entries: a kernel that reads one was enqueued before its pin was released, so the drain has finished it.  Pinned entries and other devices'
+// entries are never freed by a lookup; while every entry is pinned the count may exceed the cap.
+enum TableKind { kAngleTable, kLineTable };            // key of kAngleTable: (alpha / beta, x0, dx, n); of kLineTable: the table's bytes, columns
+struct DeviceTable;
+class TablePins {
+public:
+    TablePins() = default;
+    TablePins(const TablePins&) = delete;                  // each pin is released once
+    TablePins& operator=(const TablePins&) = delete;
+    ~TablePins();
+    // *out: the current device's copy of the table (kind, key); key: bytes that determine the contents
+    int lookup(TableKind kind, const std::string& key, const std::function<void(std::vector<double>&)>& fill, const double** out);
+private:
+    std::vector<DeviceTable*> held_;
+};
+void device_tables_shutdown();     // per device that has tables: drain it, free what no call holds; the caller's device is restored
+
 // device-pointer implementations (defined in kr_trace.hip / kr_post.hip); stream may be null
 int trace_dev(const kr_params* p, void* d_rays, int64_t n, hipStream_t stream, kr_stats* stats, bool f32);
 int trace_async(const kr_params* p, void* d_rays, int64_t n, hipStream_t stream, bool f32, void** ticket);
@@ -37,7 +60,6 @@ int trace_poll(void* ticket, int64_t* rays_started, int32_t* finished);
 void trace_release(void* ticket);
 void side_stream_forget(hipStream_t user);
 int trace_shutdown();
-void source_tables_shutdown();
 void angle_values(int kind, double x0, double dx, int n, double* sincos_pairs);     // kind 0: x = cos(alpha); 1: x = beta
 
 }  // namespace kr

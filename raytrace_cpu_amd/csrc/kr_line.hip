@@ -13,10 +13,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <map>
-#include <mutex>
 #include <string>
-#include <tuple>
 
 #include "kr_common.hpp"
 #include "kr_device.hpp"
@@ -179,53 +176,28 @@ line_from_image_kernel(const double* __restrict__ planes, long long npix, LineDe
     line_end<USE_LDS>(lds, out, L.words, on_disc, binned);
 }
 
-// ---- the radial table on the device: one array [emis | time] per distinct (device, contents), built by the first call that needs it (hipMalloc
-//      and a blocking copy), kept until kr_shutdown -- the pattern of the PointSource angle tables (kr_post.hip).  A full cache is released
-//      together after draining the device, since a kernel in flight may still read one of its arrays. ----------------------------------------
-std::mutex g_line_mu;
-std::map<std::pair<int, std::string>, double*> g_line_tables;
-constexpr size_t kMaxLineTables = 64;
-
-int line_table(const kr_line_bins* b, const double** emis, const double** time)
-{
-    *emis = *time = nullptr;
-    if (!b->table_emis) return KR_OK;
-    int dev = 0;
-    KR_HIP(hipGetDevice(&dev));
-    const size_t nr = (size_t) b->table_nr, cols = b->table_time ? 2 : 1;
-    std::string bytes((const char*) b->table_emis, nr * sizeof(double));
-    if (b->table_time) bytes.append((const char*) b->table_time, nr * sizeof(double));
-    bytes.push_back((char) cols);
-    const auto key = std::make_pair(dev, bytes);
-    std::lock_guard<std::mutex> lk(g_line_mu);
-    auto it = g_line_tables.find(key);
-    double* d = nullptr;
-    if (it != g_line_tables.end()) {
-        d = it->second;
-    } else {
-        if (g_line_tables.size() >= kMaxLineTables) {
-            KR_HIP(hipDeviceSynchronize());
-            for (auto& kv : g_line_tables) (void) hipFree(kv.second);
-            g_line_tables.clear();
-        }
-        KR_HIP(hipMalloc((void**) &d, cols * nr * sizeof(double)));
-        const hipError_t e = hipMemcpy(d, bytes.data(), cols * nr * sizeof(double), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { (void) hipFree(d); return kr::hip_fail(e, "hipMemcpy(line table)", __FILE__, __LINE__); }
-        g_line_tables.emplace(key, d);
-    }
-    *emis = d;
-    if (b->table_time) *time = d + nr;
-    return KR_OK;
-}
-
-int line_dev(const kr_line_bins* b, LineDev* L)
+// ---- the radial table on the device: one array [emis | time] per distinct contents in the device table store (TablePins, kr_common.hpp), built by
+//      the first call that needs it (hipMalloc and a blocking copy), kept while the device's store has room, freed only when no call holds it and
+//      the device has drained.  Pinned in `pins`: keep it until the kernel that reads the table has been enqueued. ------------------------------
+int line_dev(const kr_line_bins* b, TablePins& pins, LineDev* L)
 {
     L->b = *b;
     L->log_de = b->log_e ? std::log(b->de) : 0;
     L->log_tdr = b->table_emis && b->table_logbin ? std::log(b->table_dr) : 0;
     L->time_axis = !(b->nt == 1 && b->dt <= 0);
     L->words = 2 * b->nt * b->ne + 2;
-    return line_table(b, &L->t_emis, &L->t_time);
+    L->t_emis = L->t_time = nullptr;
+    if (!b->table_emis) return KR_OK;
+    const size_t nr = (size_t) b->table_nr;
+    std::string key((const char*) b->table_emis, nr * sizeof(double));
+    if (b->table_time) key.append((const char*) b->table_time, nr * sizeof(double));
+    key.push_back(b->table_time ? 2 : 1);
+    const int rc = pins.lookup(kLineTable, key, [&](std::vector<double>& h) {
+        h.assign(b->table_emis, b->table_emis + nr);
+        if (b->table_time) h.insert(h.end(), b->table_time, b->table_time + nr);
+    }, &L->t_emis);
+    if (rc == KR_OK && b->table_time) L->t_time = L->t_emis + nr;
+    return rc;
 }
 
 }  // namespace
@@ -254,8 +226,9 @@ int line_validate(const kr_line_bins* b, const char* who)
 int reduce_line_dev(const kr_line_bins* b, const void* d, int64_t n, void* d_line, hipStream_t st)
 {
     if (n <= 0) return KR_OK;
+    TablePins pins;
     LineDev L;
-    int rc = line_dev(b, &L);
+    int rc = line_dev(b, pins, &L);
     if (rc != KR_OK) return rc;
     if (L.words <= kLineLdsWords)
         hipLaunchKernelGGL(reduce_line_kernel<true>, dim3(grid_for(n)), dim3(kBlock), L.words * sizeof(double), st, (const kr_ray_f64*) d, (long long) n, L,
@@ -270,8 +243,9 @@ int post_line_dev(double spin, double V, int reverse, int projradius, int motion
                   void* d_line, hipStream_t st)
 {
     if (n <= 0) return KR_OK;
+    TablePins pins;
     LineDev L;
-    int rc = line_dev(b, &L);
+    int rc = line_dev(b, pins, &L);
     if (rc != KR_OK) return rc;
     if (L.words <= kLineLdsWords)
         hipLaunchKernelGGL(post_line_kernel<true>, dim3(grid_for(n)), dim3(kBlock), L.words * sizeof(double), st, (kr_ray_f64*) d, (long long) n, spin, V,
@@ -286,8 +260,9 @@ int post_line_dev(double spin, double V, int reverse, int projradius, int motion
 int line_from_image_dev(const kr_line_bins* b, const kr_image_bins* ib, const void* d_planes, void* d_line, hipStream_t st)
 {
     const long long npix = (long long) ib->img_nx * ib->img_ny;
+    TablePins pins;
     LineDev L;
-    int rc = line_dev(b, &L);
+    int rc = line_dev(b, pins, &L);
     if (rc != KR_OK) return rc;
     if (L.words <= kLineLdsWords)
         hipLaunchKernelGGL(line_from_image_kernel<true>, dim3(grid_for(npix)), dim3(kBlock), L.words * sizeof(double), st, (const double*) d_planes, npix, L,
@@ -296,16 +271,6 @@ int line_from_image_dev(const kr_line_bins* b, const kr_image_bins* ib, const vo
         hipLaunchKernelGGL(line_from_image_kernel<false>, dim3(grid_for(npix)), dim3(kBlock), 0, st, (const double*) d_planes, npix, L, (double*) d_line);
     KR_LAUNCH_CHECK();
     return KR_OK;
-}
-
-void line_tables_shutdown()
-{
-    std::lock_guard<std::mutex> lk(g_line_mu);
-    for (auto& kv : g_line_tables) {
-        if (hipSetDevice(kv.first.first) == hipSuccess) (void) hipFree(kv.second);
-        else (void) hipGetLastError();
-    }
-    g_line_tables.clear();
 }
 
 }  // namespace kr

@@ -14,9 +14,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <map>
-#include <mutex>
-#include <tuple>
+#include <string>
 #include <vector>
 
 #include "kr_common.hpp"
@@ -548,22 +546,10 @@ int calculate_momentum_dev(double spin, void* d, int64_t n, hipStream_t st, bool
 }
 
 // ---- the PointSource constructor's transcendental values, from the HOST's C library (SourceTables, kr_post_device.hpp) -------------------------
-// One device array of (sin, cos) pairs per distinct (device, kind, first angle / cosine, spacing, count); built on the first call that needs
-// it (a hipMalloc and a blocking 50-KB copy: that one call waits for the copy, no later one does), kept until kr_shutdown.  The hundred sources
-// of a multi-radius driver share one pair of arrays.  A process that keeps inventing new grids fills the cache (kMaxAngleTables): the device is
-// then drained and the arrays are released together, since a kernel in flight may still be reading one.
-namespace {
-struct AngleKey {
-    int dev, kind;           // kind 0: x is cos(alpha) -> (sin, cos) of acos(x);  1: x is beta -> (sin, cos) of x
-    double x0, dx;
-    int n;
-    bool operator<(const AngleKey& o) const { return std::tie(dev, kind, x0, dx, n) < std::tie(o.dev, o.kind, o.x0, o.dx, o.n); }
-};
-std::mutex g_tables_mu;
-std::map<AngleKey, double2*> g_tables;
-constexpr size_t kMaxAngleTables = 256;
-
-}  // namespace
+// One device array of (sin, cos) pairs per distinct (kind, first angle / cosine, spacing, count) in the device table store (TablePins,
+// kr_common.hpp): built on the first call that needs it (a hipMalloc and a blocking 50-KB copy: that one call waits for the copy, no later one
+// does), kept while the device's store has room, freed only when no call holds it and the device has drained.  The hundred sources of a
+// multi-radius driver share one pair of arrays.
 
 // (sin, cos) pairs of the n angles of one grid axis, with the HOST's C library -- the one the reference's constructor calls.  sincos(), not sin()
 // and cos(): an optimising build of the reference (g++ -O2, the build the oracle is pinned to: 40 calls of sincos in oracle/_ref/libkr_ref.so) merges
@@ -579,49 +565,29 @@ void angle_values(int kind, double x0, double dx, int n, double* sincos_pairs)
 }
 
 namespace {
-int angle_table(int kind, double x0, double dx, int n, const double2** out)
+// kind 0: x is cos(alpha) -> (sin, cos) of acos(x);  1: x is beta -> (sin, cos) of x
+int angle_table(TablePins& pins, int kind, double x0, double dx, int n, const double2** out)
 {
-    int dev = 0;
-    KR_HIP(hipGetDevice(&dev));
-    const AngleKey key{dev, kind, x0, dx, n};
-    std::lock_guard<std::mutex> lk(g_tables_mu);
-    auto it = g_tables.find(key);
-    if (it != g_tables.end()) { *out = it->second; return KR_OK; }
-    if (g_tables.size() >= kMaxAngleTables) {
-        KR_HIP(hipDeviceSynchronize());
-        for (auto& kv : g_tables) (void) hipFree(kv.second);
-        g_tables.clear();
-    }
-    std::vector<double2> h((size_t) std::max(n, 1));
-    angle_values(kind, x0, dx, n, reinterpret_cast<double*>(h.data()));
-    double2* d = nullptr;
-    KR_HIP(hipMalloc((void**) &d, h.size() * sizeof(double2)));
-    const hipError_t e = hipMemcpy(d, h.data(), h.size() * sizeof(double2), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void) hipFree(d); return kr::hip_fail(e, "hipMemcpy(angle table)", __FILE__, __LINE__); }
-    g_tables.emplace(key, d);
-    *out = d;
-    return KR_OK;
+    const double key[] = {(double) kind, x0, dx, (double) n};
+    const double* d = nullptr;
+    const int rc = pins.lookup(kAngleTable, std::string((const char*) key, sizeof key), [&](std::vector<double>& h) {
+        h.resize(2 * (size_t) std::max(n, 1));
+        angle_values(kind, x0, dx, n, h.data());
+    }, &d);
+    *out = (const double2*) d;
+    return rc;
 }
 
-int source_tables(const kr_pointsource* s, int n_cosalpha, int n_beta, SourceTables* tb)
+// the tables of one source, pinned in `pins`: keep it until the kernel that reads them has been enqueued
+int source_tables(const kr_pointsource* s, int n_cosalpha, int n_beta, TablePins& pins, SourceTables* tb)
 {
-    int rc = angle_table(0, s->cosalpha0, s->dcosalpha, n_cosalpha, &tb->alpha_sc);
-    if (rc == KR_OK) rc = angle_table(1, s->beta0, s->dbeta, n_beta, &tb->beta_sc);
+    int rc = angle_table(pins, 0, s->cosalpha0, s->dcosalpha, n_cosalpha, &tb->alpha_sc);
+    if (rc == KR_OK) rc = angle_table(pins, 1, s->beta0, s->dbeta, n_beta, &tb->beta_sc);
     ::sincos(s->pos[2], &tb->sin_th, &tb->cos_th);                  // raytracer.cpp:631-672 (calculate_constants; see angle_values)
     tb->tan_th = std::tan(s->pos[2]);
     return rc;
 }
 }  // namespace
-
-void source_tables_shutdown()
-{
-    std::lock_guard<std::mutex> lk(g_tables_mu);
-    for (auto& kv : g_tables) {
-        if (hipSetDevice(kv.first.dev) == hipSuccess) (void) hipFree(kv.second);
-        else (void) hipGetLastError();
-    }
-    g_tables.clear();
-}
 
 int pointsource_init_dev(const kr_pointsource* s, void* d, int64_t n, int64_t first, int64_t stride, hipStream_t st)
 {
@@ -630,8 +596,9 @@ int pointsource_init_dev(const kr_pointsource* s, void* d, int64_t n, int64_t fi
     if (first < 0 || stride < 1) { set_error("kr_pointsource_init: bad first/stride"); return KR_EINVAL; }
     if (first == 0 && stride == 1 && n < total) { set_error("kr_pointsource_init: n smaller than kr_pointsource_count()"); return KR_EINVAL; }
     if (n <= 0) return KR_OK;
+    TablePins pins;
     SourceTables tb;
-    const int rc = source_tables(s, nc, nb, &tb);
+    const int rc = source_tables(s, nc, nb, pins, &tb);
     if (rc != KR_OK) return rc;
     hipLaunchKernelGGL(pointsource_init_kernel, dim3(grid_for(n)), dim3(kBlock), 0, st, (kr_ray_f64*) d, (long long) n, *s, tb, nc, nb, (long long) first, (long long) stride);
     KR_LAUNCH_CHECK();
@@ -644,8 +611,9 @@ int pointsource_init_emit_dev(const kr_pointsource* s, void* d, int64_t n, int64
     kr_pointsource_count(s, &nc, &nb);
     if (first < 0 || stride < 1) { set_error("kr_pointsource_init_emit: bad first/stride"); return KR_EINVAL; }
     if (n <= 0) return KR_OK;
+    TablePins pins;
     SourceTables tb;
-    const int rc = source_tables(s, nc, nb, &tb);
+    const int rc = source_tables(s, nc, nb, pins, &tb);
     if (rc != KR_OK) return rc;
     hipLaunchKernelGGL(pointsource_init_emit_kernel, dim3(grid_for(n)), dim3(kBlock), 0, st, (kr_ray_f64*) d, (long long) n, *s, tb, nc, nb, (long long) first,
                        (long long) stride, V, reverse, projradius);
@@ -772,6 +740,7 @@ int pointsource_init_emit_batch_dev(int count, const kr_pointsource* s, const do
     for (int base = 0; base < count; base += kSourceChunk) {
         SourceChunk c;
         std::memset(&c, 0, sizeof c);
+        TablePins pins;                                    // the tables of every item of the chunk, until its launch is enqueued
         int m = 0;
         int64_t n_max = 0;
         for (int i = base; i < count && i < base + kSourceChunk; i++) {
@@ -779,7 +748,7 @@ int pointsource_init_emit_batch_dev(int count, const kr_pointsource* s, const do
             int32_t nc = 0, nb = 0;
             kr_pointsource_count(&s[i], &nc, &nb);
             SourceTables tb;
-            const int rc = source_tables(&s[i], nc, nb, &tb);
+            const int rc = source_tables(&s[i], nc, nb, pins, &tb);
             if (rc != KR_OK) return rc;
             c.item[m++] = SourceItem{s[i], tb, V ? V[i] : s[i].V, (kr_ray_f64*) d[i], (long long) n[i], nc, nb};
             n_max = std::max(n_max, n[i]);

@@ -125,7 +125,7 @@ KR_DEV T range_phi_value(T phi, int steps, T lo, T hi)
 // cos(beta_j) (two small device arrays: 100 KB at 1e7 rays) and sin / cos / tan of the source's polar angle (three scalars) carry glibc's bits
 // and everything that is left for the device is + - x / sqrt, which is IEEE on both sides: k, h, Q of EVERY device-built ray are the reference
 // constructor's, bit for bit (with the device library's acos 5 % of the rays differed in the last bit of h and Q, and on chaotic rays that is
-// another bin).  kr_post.hip::source_tables builds and caches the arrays per (device, grid).
+// another bin).  kr_post.hip::source_tables builds the arrays once per (device, grid) in the device table store (TablePins, kr_common.hpp).
 struct SourceTables {
     const double2* alpha_sc;     // [n_cosalpha]  (sin, cos) of acos(cosalpha0 + i dcosalpha)     pointsource.cpp:38,46; raytracer.cpp:653
     const double2* beta_sc;      // [n_beta]      (sin, cos) of beta0 + j dbeta                   pointsource.cpp:39;    raytracer.cpp:653

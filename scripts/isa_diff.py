@@ -3,11 +3,13 @@
 
     scripts/isa_diff.py /tmp/isa_a /tmp/isa_b [--mix SUBSTR]
 
+Compares every .s file of dump A with the file of the same name in dump B (a file missing from B counts as a difference).
 Prints which functions exist only on one side and which differ (instruction counts on both sides); pc-relative call
 offsets (the s_add_u32 / s_addc_u32 pair after s_getpc_b64) are masked, since they move when other functions come or go.
 --mix SUBSTR: instruction mix of the functions of dump B whose (mangled) name contains SUBSTR.
 """
 import collections
+import os
 import re
 import sys
 
@@ -69,7 +71,15 @@ def main():
     a_dir, b_dir = sys.argv[1], sys.argv[2]
     sub = sys.argv[sys.argv.index("--mix") + 1] if "--mix" in sys.argv else None
     rc = 0
-    for f in ("kr_trace.s", "kr_post.s", "kr_capi.s"):
+    files = sorted(f for f in os.listdir(a_dir) if f.endswith(".s"))
+    if not files:
+        print(f"no .s files in {a_dir}")
+        return 1
+    for f in files:
+        if not os.path.exists(f"{b_dir}/{f}"):
+            print(f"{f}: missing in {b_dir}")
+            rc = 1
+            continue
         fa, fb = functions(f"{a_dir}/{f}"), functions(f"{b_dir}/{f}")
         only_a, only_b = sorted(set(fa) - set(fb)), sorted(set(fb) - set(fa))
         diff = [n for n in fa if n in fb and masked(fa[n]) != masked(fb[n])]

@@ -96,3 +96,59 @@ def test_batched_source_and_return_passes_equal_the_single_calls(krlib):
                     lib.kr_free(bufs[side][j])
             if outs[side]:
                 lib.kr_free(outs[side])
+
+
+def _churn_specs(count=400):
+    """Tiny sources (5 x 8 grid points) with more distinct angle tables than the device table store keeps (256 per device): each source has its own
+    cos(alpha) axis of the same length (so a freed array is reused and refilled with other values), every third one the previous source's beta axis,
+    so the entry count crosses the cap at both parities -- between the two lookups of one call, and inside a batch chunk."""
+    out = []
+    for k in range(count):
+        c0 = -0.9 + 0.9 * k / count
+        b0 = out[-1].beta0 if k % 3 == 2 else -3.0 + 0.001 * k
+        V = -1.0 if k % 2 else 0.0
+        out.append(ol.pointsource_spec([0.0, 6.0 + 0.01 * k, 1e-3, 1.5707], V, gc.SPIN, 0.2, 0.7, cosalpha0=c0, cosalphamax=c0 + 4.5 * 0.2,
+                                       beta0=b0, betamax=b0 + 7.5 * 0.7))
+    return out
+
+
+def test_source_tables_survive_churn_of_the_table_store(krlib):
+    lib = krlib
+    capi.check(lib, lib.kr_shutdown(), "kr_shutdown")                     # start from an empty store
+    specs = _churn_specs()
+    k = len(specs)
+    counts = [api.pointsource_count(s)[0] for s in specs]
+    assert all(api.pointsource_count(s)[1:] == (5, 8) for s in specs) and 40 <= min(counts)
+    offs = np.concatenate([[0], np.cumsum(counts)]) * 144
+    bufs = [C.c_void_p() for _ in range(3)]
+    try:
+        for b in bufs:
+            capi.check(lib, lib.kr_malloc(C.byref(b), int(offs[-1])), "malloc")
+
+        def fetch(side):
+            capi.check(lib, lib.kr_synchronize(None), "sync")
+            h = np.zeros(sum(counts), dtype=capi.RAY_F64)
+            capi.check(lib, lib.kr_memcpy_d2h(h.ctypes.data_as(vp), bufs[side], h.nbytes), "d2h")
+            return [h[offs[j] // 144:offs[j + 1] // 144] for j in range(k)]
+        # the plain constructor, one call per source, against the oracle's: every live record bit for bit
+        for j, s in enumerate(specs):
+            capi.check(lib, lib.kr_pointsource_init_dev_f64(C.byref(s), vp(bufs[0].value + int(offs[j])), counts[j], None), "init")
+        got = fetch(0)
+        for j, s in enumerate(specs):
+            want = ol.oracle_pointsource(s)
+            live = want["steps"] == 0
+            assert live.sum() == 40, j
+            assert not ol.rays_equal_bitwise(got[j][live], want[live], fields=("t", "r", "theta", "phi", "k", "h", "Q", "alpha", "beta")), j
+        # the fused constructor: one call per source against one batch of all of them
+        for j, s in enumerate(specs):
+            capi.check(lib, lib.kr_pointsource_init_emit_dev_f64(C.byref(s), 0, 1, s.V, 0, 0, vp(bufs[1].value + int(offs[j])), counts[j], None), "init_emit")
+        capi.check(lib, lib.kr_pointsource_init_emit_batch_dev_f64(k, (capi.PointSourceSpec * k)(*specs), (C.c_double * k)(*[s.V for s in specs]), 0, 0,
+                                                                   (C.c_void_p * k)(*[bufs[2].value + int(o) for o in offs[:-1]]),
+                                                                   (C.c_int64 * k)(*counts), None), "init_emit batch")
+        single, batch = fetch(1), fetch(2)
+        for j in range(k):
+            assert not ol.rays_equal_bitwise(single[j], batch[j]), j
+    finally:
+        for b in bufs:
+            if b:
+                lib.kr_free(b)

@@ -312,3 +312,29 @@ def test_line_profile_app_time_axis(krlib):
     assert want["binned"] > 100 and (want["count"].sum(axis=1) > 0).sum() >= 3
     np.testing.assert_allclose(rows[::60, 0], 9980 + 15 * (np.arange(5) + 0.5))
     check("test_line_profile_app_time_axis", "rays-log-t", {"count": rows[:, 3].reshape(5, 60), "flux": rows[:, 2].reshape(5, 60)}, want, rtol=1e-6)
+
+
+# ---- 9. more distinct tables than the device table store keeps --------------------------------------------------------------------
+def test_line_tables_survive_churn_of_the_table_store(traced):
+    """300 distinct emissivity tables (the fixture's, scaled) against a store of 256 per device: each one's line through kr_reduce_line_dev_f64
+    on the same records, every tenth through kr_post_line_dev_f64 as well -- each against the numpy rules for that table."""
+    L = api.lib()
+    _, rays = post_line(line_bins(), traced)
+    r_min, dr, emis, time = lr.read_emissivity_dat(EMIS_DAT)
+    d = Dev.of(rays)
+    try:
+        for i in range(300):
+            b = line_bins().with_table(r_min, dr, emis * (1 + 0.01 * i), time)
+            want = lr.line_from_rays(b, rays)
+            h = Dev.zeros(api.line_words(b))
+            capi.check(L, L.kr_reduce_line_dev_f64(C.byref(b), d.p, len(rays), h.p, None), "kr_reduce_line_dev")
+            got = api.line_from_words(b, h.get(np.zeros(api.line_words(b))))
+            h.free()
+            problems, m = lr.compare_line(got, want, rtol=1e-9, slack=1, max_excluded=2)
+            assert problems == [], (i, problems, m)
+            if i % 10 == 0:
+                got, _ = post_line(b, traced)
+                problems, m = lr.compare_line(got, want, rtol=1e-9, slack=1, max_excluded=2)
+                assert problems == [], (i, "post_line", problems, m)
+    finally:
+        d.free()
