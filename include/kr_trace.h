@@ -245,6 +245,29 @@ typedef struct kr_line_bins {
 static_assert(sizeof(kr_line_bins) == 160, "kr_line_bins is 160 bytes (raytrace_cpu_amd/capi.py LineBins)");
 #endif
 
+/* Critical-curve (caustic) maps of the disc on an image plane: src/caustic/caustic_discplane.cpp.  Per image-plane pixel (ix, iy), from the ray through
+ * the pixel (bundle mode: member 0 of its 5-ray bundle, imageplane_bundles.h) after redshift(dest, reverse) (caustic_discplane.cpp:219-251):
+ *   valid_hit   steps > 0, r_isco <= r < r_disc, redshift > 0 (:177-182)
+ *   on a hit    HIT = 1, RADIUS = r, PHI = phi_s = atan2(sin phi, cos phi) of the accumulated phi, X_DISC = r cos phi_s, Y_DISC = r sin phi_s,
+ *               ORDER = max((int) (|phi| / 2 pi), rdot_flips / 2), REDSHIFT = redshift; otherwise zeros and ORDER = -1
+ *   DET_J, SIGN_J   bundles = 1 (:279-334): NaN, 0 unless the centre and its four satellites (east, west, north, south at +- eps_x, +- eps_y) are
+ *               valid hits; 1e30, 0 unless all four have the centre's rdot_flips and an accumulated phi within pi / 2 of its; otherwise the
+ *               determinant of the central differences of (X_DISC, Y_DISC) over 2 eps_x, 2 eps_y and its sign (+1 / -1 / 0).
+ *               bundles = 0 (:403-439): the same from the X_DISC / Y_DISC planes of the four neighbouring pixels over 2 eps_x, 2 eps_y (here the
+ *               spacing of the ray grid), with HIT / ORDER of the neighbours in place of the satellite tests; border pixels stay NaN, 0.
+ * d_maps: 9 nx ny + 7 doubles on the device, [DET_J | SIGN_J | ORDER | HIT | RADIUS | PHI | X_DISC | Y_DISC | REDSHIFT], each [ix ny + iy] like
+ * Array2D, then disc_count, horizon, rlim, steplim, out_of_range, other (the diagnostic counts of :255-276 over the centre rays), suppressed. */
+typedef struct kr_caustic_map {
+    double r_isco, r_disc;         /* valid_hit */
+    double eps_x, eps_y;           /* bundles = 1: satellite offsets;  bundles = 0: dx, dy of the ray grid */
+    int32_t nx, ny;                /* pixels = bundle centres (fencepost counts) */
+    int32_t bundles;               /* 1: 5 records per pixel;  0: one record per pixel + neighbour differences */
+    int32_t pad;
+} kr_caustic_map;
+#ifdef __cplusplus
+static_assert(sizeof(kr_caustic_map) == 48, "kr_caustic_map is 48 bytes (raytrace_cpu_amd/capi.py CausticMap)");
+#endif
+
 /* ---- runtime ---------------------------------------------------------------------------------- */
 int         kr_abi_version(void);
 const char* kr_last_error(void);
@@ -257,6 +280,7 @@ double      kr_kerr_isco(double a, int sign);               /* kerr_isco(), kerr
 double      kr_disc_velocity(double r, double a, int sign); /* disc_velocity(), kerr.h:35-38 */
 int64_t     kr_pointsource_count(const kr_pointsource* s, int32_t* n_cosalpha, int32_t* n_beta);   /* pointsource.cpp:12,16-17 */
 int64_t     kr_imageplane_count(const kr_imageplane* s, int32_t* nx, int32_t* ny);                 /* imageplane.cpp:12-14 */
+int64_t     kr_bundles_count(const kr_imageplane* s, int32_t* nx, int32_t* ny);                    /* imageplane_bundles.h:150-153: 5 * int(product of doubles) */
 /* The transcendental values of the PointSource constructor (pointsource.cpp:38-46: alpha = acos(cosalpha0 + i dcosalpha), beta = beta0 + j dbeta;
  * raytracer.cpp:631-672: sin / cos of alpha and beta, sin / cos / tan of the source's polar angle pos[2]) computed on the HOST with the C library
  * the reference calls.  The device constructors (kr_pointsource_init*_dev_f64) read exactly these -- they upload them once per (device, grid), and
@@ -418,6 +442,23 @@ int kr_post_line_dev_f64(double spin, double V, int reverse, int projradius, int
                          void* d_line, void* stream);
 /* the notebook's per-pixel form over d_planes (7 img_nx img_ny + 1 doubles, the layout of kr_reduce_image_dev_f64) */
 int kr_line_from_image_dev_f64(const kr_line_bins* b, const kr_image_bins* ib, const void* d_planes, void* d_line, void* stream);
+
+/* ---- critical-curve maps (kr_caustic_map above): caustic_discplane.cpp on the device -------------------------------------------------------
+ * Every entry point validates its arguments before it touches a device: KR_EINVAL (message in kr_last_error) when nx or ny < 1, eps_x or eps_y
+ * is <= 0 or non-finite, eps_frac <= 0 or >= 0.5 (the constructor), or n is smaller than 5 nx ny (bundles) / nx ny (grid).  None of them waits
+ * for the device, allocates or frees.
+ * kr_bundles_init_emit_dev_f64: the ImagePlaneBundles constructor (imageplane_bundles.h:150-199) + redshift_start(V, reverse, projradius) in one
+ * pass (ImagePlaneBundles::redshift_start() is V = 0, reverse = 1): record s is member s % 5 (centre, east, west, north, south; satellites eps_frac of
+ * a grid step away) of bundle s / 5, bundle b the grid point (b / ny, b % ny) of kr_imageplane_init_emit_dev_f64; the same per-ray arithmetic, except
+ * that the point x = y = 0 takes beta = 0 (as the host mirror's constructor) instead of asin(0 / 0).  Records from 5 nx ny on get steps = -1. */
+int kr_bundles_init_emit_dev_f64(const kr_imageplane* s, double eps_frac, double V, int reverse, int projradius, void* d_rays, int64_t n, void* stream);
+/* redshift(dest, reverse) of every record (rays[].redshift exactly as after kr_redshift_dest_dev_f64; `spin` as stored by the Raytracer, i.e.
+ * negated) + the nine planes and the six counts in one pass over the records (caustic_discplane.cpp:217-334; bundles = 0: :349-439, the Jacobian by a
+ * second pass over the planes).  WRITES every word of d_maps (suppressed = 0). */
+int kr_post_caustic_disc_dev_f64(double spin, int reverse, const kr_caustic_map* m, void* d_rays, int64_t n, void* d_maps, void* stream);
+/* branch-boundary suppression (caustic_discplane.cpp:455-493): a pixel with SIGN_J != 0 whose 4-neighbourhood -- in the planes as they are when the
+ * call is made -- holds more opposite than equal signs, and at least two opposite ones, gets DET_J = 1e30, SIGN_J = 0; their number -> suppressed */
+int kr_caustic_suppress_dev_f64(const kr_caustic_map* m, void* d_maps, void* stream);
 
 /* ---- diagnostics ------------------------------------------------------------------------------- */
 /* out[i] = op(a[i], b[i]) evaluated ON THE DEVICE with the exact primitive the trace kernel uses (host pointers):

@@ -274,3 +274,84 @@ def line_profile(imageplane_spec, params, bins, mode="rays", image_bins=None):
     res = line_from_words(bins, out)
     res["stats"] = st.as_dict()
     return res
+
+
+CAUSTIC_PLANES = ("det_j", "sign_j", "order", "hit", "radius", "phi", "x_disc", "y_disc", "redshift")
+CAUSTIC_COUNTS = ("disc_count", "horizon", "rlim", "steplim", "out_of_range", "other", "suppressed")
+
+
+def bundles_count(spec):
+    nx, ny = C.c_int32(), C.c_int32()
+    n = lib().kr_bundles_count(C.byref(spec), C.byref(nx), C.byref(ny))
+    return n, nx.value, ny.value
+
+
+def caustic_words(cm):
+    """Length of the map buffer of the caustic entry points: nine planes of nx ny and seven counts (include/kr_trace.h, kr_caustic_map)."""
+    return len(CAUSTIC_PLANES) * cm.nx * cm.ny + len(CAUSTIC_COUNTS)
+
+
+def caustic_from_words(cm, words):
+    """The map buffer as a dict: the nine planes as (nx, ny) arrays ([ix, iy], like Array2D) and the seven counts as ints."""
+    npix = cm.nx * cm.ny
+    words = np.asarray(words, dtype=np.float64)
+    out = {k: words[q * npix:(q + 1) * npix].reshape(cm.nx, cm.ny).copy() for q, k in enumerate(CAUSTIC_PLANES)}
+    out.update({k: int(round(float(words[len(CAUSTIC_PLANES) * npix + q]))) for q, k in enumerate(CAUSTIC_COUNTS)})
+    return out
+
+
+def caustic_trace_params(imageplane_spec, r_disc, integrator=capi.RK4, rk45_tol=1e-8, precision=100, flags=0, steplim=0):
+    """The trace of the caustic_discplane program (caustic_discplane.cpp:167, :216): to a DiscWithISCODestination(r_isco, r_disc) -- its descriptor as
+    host/raytracer/ray_destination.h::describe gives it, {r_isco, r_out, theta_lim = pi / 2, 0} -- or r_max = 1.1 dist.  Returns (params, r_isco)."""
+    r_isco = lib().kr_kerr_isco(imageplane_spec.spin, 1)
+    p = capi.default_params(-1 * imageplane_spec.spin)   # as stored by the Raytracer of an ImagePlane (imageplane.cpp:12)
+    p.precision, p.integrator, p.flags, p.steplim = precision, integrator, flags, steplim
+    if integrator == capi.RK45:
+        p.rk45_tol = rk45_tol
+    p.r_max = 1.1 * imageplane_spec.dist
+    p.stop_kind = capi.STOP_DISC_ISCO
+    for i, v in enumerate((r_isco, r_disc, np.pi / 2, 0.0)):
+        p.stop_params[i] = v
+    return p, r_isco
+
+
+def caustic_map(imageplane_spec, r_disc, integrator=capi.RK4, eps_frac=0.01, rk45_tol=1e-8, precision=100, flags=0, steplim=0):
+    """The critical-curve maps of the disc on an image plane, resident on the device from start to finish, as the kr_caustic_discplane app runs
+    them: 5-ray bundles + redshift_start (kr_bundles_init_emit_dev_f64; eps_frac = 0: the plain grid, kr_imageplane_init_emit_dev_f64 and the
+    grid-neighbour Jacobian) -> trace to the disc (kr_trace_dev_f64, KR_STOP_DISC_ISCO) -> redshift + maps (kr_post_caustic_disc_dev_f64) ->
+    branch-boundary suppression (kr_caustic_suppress_dev_f64).  flags = 0 is the strict arithmetic (the app's default).  Only the maps are read
+    back.  Returns caustic_from_words(...) plus "stats" (the trace's kr_stats), "r_isco", "eps_x", "eps_y"."""
+    L = lib()
+    if integrator not in (capi.RK4, capi.RK45):
+        raise KrError("caustic_map: the integrator must be RK4 or RK45 (a RayDestination has no Euler form)")
+    bundles = eps_frac > 0
+    n, nx, ny = bundles_count(imageplane_spec) if bundles else imageplane_count(imageplane_spec)
+    if n <= 0:
+        raise KrError("caustic_map: empty ray grid")
+    p, r_isco = caustic_trace_params(imageplane_spec, r_disc, integrator, rk45_tol, precision, flags, steplim)
+    cm = capi.CausticMap()
+    cm.r_isco, cm.r_disc, cm.nx, cm.ny, cm.bundles = r_isco, r_disc, nx, ny, int(bundles)
+    cm.eps_x, cm.eps_y = (eps_frac * imageplane_spec.dx, eps_frac * imageplane_spec.dy) if bundles else (imageplane_spec.dx, imageplane_spec.dy)
+    spin = -1 * imageplane_spec.spin
+    nw = caustic_words(cm)
+    d_rays, d_maps = C.c_void_p(), C.c_void_p()
+    st = Stats()
+    try:
+        capi.check(L, L.kr_malloc(C.byref(d_rays), n * capi.RAY_F64.itemsize), "kr_malloc")
+        capi.check(L, L.kr_malloc(C.byref(d_maps), nw * 8), "kr_malloc")
+        if bundles:
+            capi.check(L, L.kr_bundles_init_emit_dev_f64(C.byref(imageplane_spec), eps_frac, 0.0, 1, 0, d_rays, n, None), "kr_bundles_init_emit")
+        else:
+            capi.check(L, L.kr_imageplane_init_emit_dev_f64(C.byref(imageplane_spec), 0, 1, 0.0, 1, 0, d_rays, n, None), "kr_imageplane_init_emit")
+        capi.check(L, L.kr_trace_dev_f64(C.byref(p), d_rays, n, None, C.byref(st)), "kr_trace_dev")
+        capi.check(L, L.kr_post_caustic_disc_dev_f64(spin, 1, C.byref(cm), d_rays, n, d_maps, None), "kr_post_caustic_disc")
+        capi.check(L, L.kr_caustic_suppress_dev_f64(C.byref(cm), d_maps, None), "kr_caustic_suppress")
+        out = np.zeros(nw)
+        capi.check(L, L.kr_memcpy_d2h(_ptr(out), d_maps, nw * 8), "kr_memcpy_d2h")
+    finally:
+        for d in (d_rays, d_maps):
+            if d.value:
+                L.kr_free(d)
+    res = caustic_from_words(cm, out)
+    res.update(stats=st.as_dict(), r_isco=r_isco, eps_x=cm.eps_x, eps_y=cm.eps_y)
+    return res

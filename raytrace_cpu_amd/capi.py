@@ -89,6 +89,11 @@ class LineBins(C.Structure):
         return self
 
 
+class CausticMap(C.Structure):
+    """kr_caustic_map: what the critical-curve passes need besides the records (include/kr_trace.h has the per-pixel rules)."""
+    _fields_ = [(n, C.c_double) for n in ("r_isco", "r_disc", "eps_x", "eps_y")] + [(n, C.c_int32) for n in ("nx", "ny", "bundles", "pad")]
+
+
 def line_bins(line_energy=6.4, e_min=1.0, de=0.1, ne=90, log_e=False, t0=0.0, dt=0.0, nt=1, r_isco=1.0, r_disc=1000.0, q1=3.0, rb1=4.0, q2=3.0,
               rb2=10.0, q3=3.0, g_index=3.0):
     b = LineBins()
@@ -140,6 +145,7 @@ PROTOTYPES = {
     "kr_disc_velocity": (_dbl, [_dbl, _dbl, _int]),
     "kr_pointsource_count": (_i64, [P(PointSourceSpec), P(_i32), P(_i32)]),
     "kr_imageplane_count": (_i64, [P(ImagePlaneSpec), P(_i32), P(_i32)]),
+    "kr_bundles_count": (_i64, [P(ImagePlaneSpec), P(_i32), P(_i32)]),
     "kr_trace_f64": (_int, [P(Params), _vp, _i64, P(Stats)]),
     "kr_trace_f32": (_int, [P(Params), _vp, _i64, P(Stats)]),
     "kr_trace_dev_f64": (_int, [P(Params), _vp, _i64, _vp, P(Stats)]),
@@ -198,6 +204,9 @@ PROTOTYPES = {
     "kr_reduce_line_dev_f64": (_int, [P(LineBins), _vp, _i64, _vp, _vp]),
     "kr_post_line_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, P(LineBins), _vp, _i64, _vp, _vp]),
     "kr_line_from_image_dev_f64": (_int, [P(LineBins), P(ImageBins), _vp, _vp, _vp]),
+    "kr_bundles_init_emit_dev_f64": (_int, [P(ImagePlaneSpec), _dbl, _dbl, _int, _int, _vp, _i64, _vp]),
+    "kr_post_caustic_disc_dev_f64": (_int, [_dbl, _int, P(CausticMap), _vp, _i64, _vp, _vp]),
+    "kr_caustic_suppress_dev_f64": (_int, [P(CausticMap), _vp, _vp]),
     "kr_debug_arith_f64": (_int, [_int, _vp, _vp, _vp, _i64]),
     "kr_host_attach": (_int, [_vp, _i64, _i32]),
     "kr_host_detach": (_int, [_vp]),

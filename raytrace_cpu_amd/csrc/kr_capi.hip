@@ -52,6 +52,11 @@ int reduce_line_dev(const kr_line_bins* b, const void* d, int64_t n, void* d_lin
 int post_line_dev(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_line_bins* b, void* d, int64_t n,
                   void* d_line, hipStream_t st);
 int line_from_image_dev(const kr_line_bins* b, const kr_image_bins* ib, const void* d_planes, void* d_line, hipStream_t st);
+// implemented in kr_caustic.hip
+int caustic_validate(const kr_caustic_map* m, const char* who);
+int bundles_init_emit_dev(const kr_imageplane* s, int nx, int ny, double eps_frac, double V, int reverse, int projradius, void* d, int64_t n, hipStream_t st);
+int post_caustic_dev(double spin, int reverse, const kr_caustic_map* m, void* d, int64_t n, void* d_maps, hipStream_t st);
+int caustic_suppress_dev(const kr_caustic_map* m, void* d_maps, hipStream_t st);
 
 static thread_local std::string g_error;
 
@@ -384,6 +389,12 @@ int64_t kr_imageplane_count(const kr_imageplane* s, int32_t* nx, int32_t* ny)
     if (nx) *nx = (int) (((s->xmax - s->x0) / s->dx) + 1);
     if (ny) *ny = (int) (((s->ymax - s->y0) / s->dy) + 1);
     return nrays;
+}
+
+// imageplane_bundles.h:150-153: the Raytracer allocation, five times the int-truncated product of doubles
+int64_t kr_bundles_count(const kr_imageplane* s, int32_t* nx, int32_t* ny)
+{
+    return 5 * kr_imageplane_count(s, nx, ny);
 }
 
 // ---- trace ---------------------------------------------------------------------------------------------
@@ -826,6 +837,40 @@ int kr_reduce_line_f64(const kr_line_bins* b, const kr_ray_f64* rays, int64_t n,
     if (rc != KR_OK) return rc;
     std::memcpy(out, h.data(), words * sizeof(double));
     return KR_OK;
+}
+
+// ---- critical-curve maps (kr_caustic.hip): everything is validated before anything touches a device --------------------------------------
+int kr_bundles_init_emit_dev_f64(const kr_imageplane* s, double eps_frac, double V, int reverse, int projradius, void* d, int64_t n, void* st)
+{
+    auto bad = [](const char* why) { set_error(std::string("kr_bundles_init_emit: ") + why); return KR_EINVAL; };
+    if (!s) return bad("null spec");
+    if (!std::isfinite(eps_frac) || !(eps_frac > 0) || !(eps_frac < 0.5)) return bad("eps_frac must lie in (0, 0.5)");
+    int32_t nx = 0, ny = 0;
+    kr_imageplane_count(s, &nx, &ny);
+    if (nx < 1 || ny < 1) return bad("empty ray grid (nx and ny must be >= 1)");
+    if (n < 5 * (int64_t) nx * ny) return bad("n smaller than 5 nx ny");
+    if (!d) return bad("null ray buffer");
+    int rc = require_device();
+    return rc != KR_OK ? rc : bundles_init_emit_dev(s, nx, ny, eps_frac, V, reverse, projradius, d, n, (hipStream_t) st);
+}
+
+int kr_post_caustic_disc_dev_f64(double spin, int reverse, const kr_caustic_map* m, void* d, int64_t n, void* d_maps, void* st)
+{
+    int rc = caustic_validate(m, "kr_post_caustic_disc");
+    if (rc != KR_OK) return rc;
+    if (n < (m->bundles ? 5 : 1) * (int64_t) m->nx * m->ny) { set_error(m->bundles ? "kr_post_caustic_disc: n smaller than 5 nx ny" : "kr_post_caustic_disc: n smaller than nx ny"); return KR_EINVAL; }
+    if (!d || !d_maps) { set_error("kr_post_caustic_disc: null argument"); return KR_EINVAL; }
+    rc = require_device();
+    return rc != KR_OK ? rc : post_caustic_dev(spin, reverse, m, d, n, d_maps, (hipStream_t) st);
+}
+
+int kr_caustic_suppress_dev_f64(const kr_caustic_map* m, void* d_maps, void* st)
+{
+    int rc = caustic_validate(m, "kr_caustic_suppress");
+    if (rc != KR_OK) return rc;
+    if (!d_maps) { set_error("kr_caustic_suppress: null argument"); return KR_EINVAL; }
+    rc = require_device();
+    return rc != KR_OK ? rc : caustic_suppress_dev(m, d_maps, (hipStream_t) st);
 }
 
 int kr_reduce_return_dev_f64(const kr_return_bins* b, const void* d, int64_t n, void* d_out4, void* st)

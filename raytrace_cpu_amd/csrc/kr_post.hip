@@ -69,16 +69,7 @@ redshift_dest_kernel(R* __restrict__ rays, long long n, T spin, int reverse)
 {
     for (long long i = blockIdx.x * (long long) kBlock + threadIdx.x; i < n; i += (long long) gridDim.x * kBlock) {
         R* ray = &rays[i];
-        const T r = ray->r, theta = ray->theta;
-        const Metric<T> m = kerr_metric<T>(r, theta, spin);
-        const T V = 1 / (spin + r * kr_sqrt(r));
-        const T gamma_factor = 1 / kr_sqrt(1 - (V - m.omega) * (V - m.omega) * m.e2psi / m.e2nu);
-        const T et[4] = {gamma_factor / kr_sqrt(m.e2nu), 0, 0, gamma_factor * V / kr_sqrt(m.e2nu)};
-        T p[4];
-        momentum<T>(p[0], p[1], p[2], p[3], ray->k, ray->h, ray->Q, ray->rdot_sign, ray->thetadot_sign, r, theta, spin);
-        if (reverse) { p[1] *= -1; p[2] *= -1; p[3] *= -1; }
-        const T recv = energy_dot<T>(m, et, p);
-        ray->redshift = reverse ? recv / ray->emit : ray->emit / recv;
+        ray->redshift = redshift_dest_value<T>(ray->r, ray->theta, ray->k, ray->h, ray->Q, ray->rdot_sign, ray->thetadot_sign, ray->emit, spin, reverse);
     }
 }
 
@@ -170,64 +161,16 @@ pointsource_init_emit_multi_kernel(SourceChunk c, int reverse, int projradius)
 }
 
 // ---- ImagePlane ctor + init_image_plane (imageplane.cpp:11-121) ---------------------------------------------
-// sin / cos of the inclination come from the host's C library (one angle per plane: PlaneTrig); the per-ray acos, atan2, asin and tan -- N^2 distinct
-// arguments, nothing to tabulate -- are kr_crmath.hpp's correctly rounded routines, sin / cos kr_sincos.hpp's: a device-built ray then differs from
-// the reference constructor's only where the host library itself is not correctly rounded (~1e-3 of the rays in some last bit; the device library's
-// 1-2 ulp routines left 21-25 % of the rays with another phi and 4-7 % with another theta or Q).
-struct PlaneTrig { double sin_incl, cos_incl; };
-
+// The per-ray arithmetic is camera_ray (kr_post_device.hpp), taken at the grid points; the bundles (kr_caustic.hip) take it at theirs.
 KR_DEV kr_ray_f64 imageplane_ray(const kr_imageplane& s, const PlaneTrig& pt_, long long n_grid, int Ny, double a, double D, double phi0, long long ix)
 {
-    kr_ray_f64 ray;
-        memset(&ray, 0, sizeof(ray));
-        ray.steps = -1;
-        if (ix < n_grid) {
-            const int i = (int) (ix / Ny), j = (int) (ix % Ny);
-            const double x = s.x0 + i * s.dy;            // sic: dy, imageplane.cpp:43
-            const double y = s.y0 + j * s.dy;
-            const double si = pt_.sin_incl, ci = pt_.cos_incl;
-
-            const double r = kr_sqrt(D * D + x * x + y * y);
-            const double theta = krcr::kr_acos_cr((D * ci + y * si) / r);
-            const double phi = phi0 + krcr::kr_atan2_cr(x, D * si - y * ci);
-
-            const double pr = D / r;
-            const double ptheta = kr_sin(krcr::kr_acos_cr(D / r)) / r;
-            const double pphi = x * si / (x * x + (D * si - y * ci) * (D * si - y * ci));
-
-            const double st = kr_sin(theta), ct = kr_cos(theta);
-            const double rhosq = r * r + (a * ct) * (a * ct);
-            const double delta = r * r - 2 * r + a * a;
-            const double sigmasq = (r * r + a * a) * (r * r + a * a) - a * a * delta * st * st;
-            const double e2nu = rhosq * delta / sigmasq;
-            const double e2psi = sigmasq * st * st / rhosq;
-            const double omega = 2 * a * r / sigmasq;
-            const double g00 = e2nu - omega * omega * e2psi, g03 = omega * e2psi, g11 = -rhosq / delta, g22 = -rhosq, g33 = -e2psi;
-
-            const double A = g00, B = 2 * g03 * pphi;
-            const double Cq = g11 * pr * pr + g22 * ptheta * ptheta + g33 * pphi * pphi;
-            double pt = (-B + kr_sqrt(B * B - 4 * A * Cq)) / (2 * A);
-            if (pt < 0) pt = (-B - kr_sqrt(B * B - 4 * A * Cq)) / (2 * A);
-
-            ray.t = 0; ray.r = r; ray.theta = theta; ray.phi = phi;
-            ray.pt = pt; ray.pr = pr; ray.ptheta = ptheta; ray.pphi = pphi;
-            ray.rdot_sign = -1;
-            ray.k = 1;                                   // calculate_constants_from_p's k/h/Q are overwritten, :100-113
-
-            const double b = kr_sqrt(x * x + y * y);
-            double beta = krcr::kr_asin_cr(y / b);
-            if (x < 0) beta = kPi - beta;
-            const double h = -1. * b * si * kr_cos(beta);
-            const double ltheta = b * kr_sin(beta);
-            const double tt = krcr::kr_tan_cr(theta);
-            ray.h = h;
-            ray.Q = (ltheta * ltheta) - (a * ct) * (a * ct) + ((h / tt)) * ((h / tt));
-            ray.thetadot_sign = (ltheta >= 0) ? 1 : -1;
-            ray.steps = 0;
-            ray.alpha = x;
-            ray.beta = y;
-        }
-    return ray;
+    if (ix < n_grid) {
+        const int i = (int) (ix / Ny), j = (int) (ix % Ny);
+        const double x = s.x0 + i * s.dy;            // sic: dy, imageplane.cpp:43
+        const double y = s.y0 + j * s.dy;
+        return camera_ray<false>(pt_, a, D, phi0, x, y);
+    }
+    return dead_ray();
 }
 
 __global__ void __launch_bounds__(kBlock)
@@ -623,7 +566,7 @@ int pointsource_init_emit_dev(const kr_pointsource* s, void* d, int64_t n, int64
 
 // sin / cos of the plane's inclination with the host's C library (sincos(): see angle_values) at the reference's own argument, incl * M_PI / 180
 // (imageplane.cpp:23)
-static PlaneTrig plane_trig(const kr_imageplane* s)
+PlaneTrig plane_trig(const kr_imageplane* s)
 {
     PlaneTrig t;
     ::sincos(s->inc_deg * M_PI / 180, &t.sin_incl, &t.cos_incl);

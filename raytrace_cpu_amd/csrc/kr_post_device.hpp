@@ -8,6 +8,7 @@
 #include <cstring>
 
 #include "kr_device.hpp"
+#include "kr_crmath.hpp"
 
 namespace kr {
 
@@ -184,6 +185,90 @@ KR_DEV kr_ray_f64 pointsource_ray(const kr_pointsource& s, const SourceTables& t
                 ray.thetadot_sign = (thetadot > 0) ? 1 : -1;
             }
         }
+    return ray;
+}
+
+// ---- redshift(RayDestination*, ...) with the default four_velocity (raytracer.cpp:450-477, :556-600; ray_destination.h:59-78): the energy ratio
+//      of one record against the equatorial Keplerian flow at its end point.  kr_post.hip::redshift_dest_kernel and the caustic epilogue
+//      (kr_caustic.hip) share it. -----------------------------------------------------------------------------------------------------
+template <typename T>
+KR_DEV T redshift_dest_value(T r, T theta, T k, T h, T Q, int rdot_sign, int thetadot_sign, T emit, T spin, int reverse)
+{
+    const Metric<T> m = kerr_metric<T>(r, theta, spin);
+    const T V = 1 / (spin + r * kr_sqrt(r));
+    const T gamma_factor = 1 / kr_sqrt(1 - (V - m.omega) * (V - m.omega) * m.e2psi / m.e2nu);
+    const T et[4] = {gamma_factor / kr_sqrt(m.e2nu), 0, 0, gamma_factor * V / kr_sqrt(m.e2nu)};
+    T p[4];
+    momentum<T>(p[0], p[1], p[2], p[3], k, h, Q, rdot_sign, thetadot_sign, r, theta, spin);
+    if (reverse) { p[1] *= -1; p[2] *= -1; p[3] *= -1; }
+    const T recv = energy_dot<T>(m, et, p);
+    return reverse ? recv / emit : emit / recv;
+}
+
+// ---- the camera ray through one point (x, y) of a distant image plane (imageplane.cpp:45-113, imageplane_bundles.h:123-196; the host mirror's
+//      host/raytracer/image_ray.h::camera_ray): ImagePlane takes it at the grid points, ImagePlaneBundles at the bundle centres and their four
+//      satellites.  sin / cos of the inclination come from the host's C library (one angle per plane: PlaneTrig); the per-ray acos, atan2, asin and
+//      tan -- N^2 distinct arguments, nothing to tabulate -- are kr_crmath.hpp's correctly rounded routines, sin / cos kr_sincos.hpp's: a device-built
+//      ray then differs from the reference constructor's only where the host library itself is not correctly rounded (~1e-3 of the rays in some last
+//      bit; the device library's 1-2 ulp routines left 21-25 % of the rays with another phi and 4-7 % with another theta or Q).
+//      GUARD_CENTRE: beta = 0 at the point x = y = 0 instead of asin(0 / 0) (the bundles; ImagePlane keeps the reference's NaN there). ----------
+struct PlaneTrig { double sin_incl, cos_incl; };
+
+// a slot beyond the source's grid: the Raytracer ctor's record (steps = -1, raytracer.cpp:45-49), the rest zeroed
+KR_DEV kr_ray_f64 dead_ray()
+{
+    kr_ray_f64 ray;
+    memset(&ray, 0, sizeof(ray));
+    ray.steps = -1;
+    return ray;
+}
+
+template <bool GUARD_CENTRE>
+KR_DEV kr_ray_f64 camera_ray(const PlaneTrig& pt_, double a, double D, double phi0, double x, double y)
+{
+    kr_ray_f64 ray;
+    memset(&ray, 0, sizeof(ray));
+    const double si = pt_.sin_incl, ci = pt_.cos_incl;
+
+    const double r = kr_sqrt(D * D + x * x + y * y);
+    const double theta = krcr::kr_acos_cr((D * ci + y * si) / r);
+    const double phi = phi0 + krcr::kr_atan2_cr(x, D * si - y * ci);
+
+    const double pr = D / r;
+    const double ptheta = kr_sin(krcr::kr_acos_cr(D / r)) / r;
+    const double pphi = x * si / (x * x + (D * si - y * ci) * (D * si - y * ci));
+
+    const double st = kr_sin(theta), ct = kr_cos(theta);
+    const double rhosq = r * r + (a * ct) * (a * ct);
+    const double delta = r * r - 2 * r + a * a;
+    const double sigmasq = (r * r + a * a) * (r * r + a * a) - a * a * delta * st * st;
+    const double e2nu = rhosq * delta / sigmasq;
+    const double e2psi = sigmasq * st * st / rhosq;
+    const double omega = 2 * a * r / sigmasq;
+    const double g00 = e2nu - omega * omega * e2psi, g03 = omega * e2psi, g11 = -rhosq / delta, g22 = -rhosq, g33 = -e2psi;
+
+    const double A = g00, B = 2 * g03 * pphi;
+    const double Cq = g11 * pr * pr + g22 * ptheta * ptheta + g33 * pphi * pphi;
+    double pt = (-B + kr_sqrt(B * B - 4 * A * Cq)) / (2 * A);
+    if (pt < 0) pt = (-B - kr_sqrt(B * B - 4 * A * Cq)) / (2 * A);
+
+    ray.t = 0; ray.r = r; ray.theta = theta; ray.phi = phi;
+    ray.pt = pt; ray.pr = pr; ray.ptheta = ptheta; ray.pphi = pphi;
+    ray.rdot_sign = -1;
+    ray.k = 1;                                   // calculate_constants_from_p's k/h/Q are overwritten, :100-113
+
+    const double b = kr_sqrt(x * x + y * y);
+    double beta = (GUARD_CENTRE && !(b > 0)) ? 0.0 : krcr::kr_asin_cr(y / b);
+    if (x < 0) beta = kPi - beta;
+    const double h = -1. * b * si * kr_cos(beta);
+    const double ltheta = b * kr_sin(beta);
+    const double tt = krcr::kr_tan_cr(theta);
+    ray.h = h;
+    ray.Q = (ltheta * ltheta) - (a * ct) * (a * ct) + ((h / tt)) * ((h / tt));
+    ray.thetadot_sign = (ltheta >= 0) ? 1 : -1;
+    ray.steps = 0;
+    ray.alpha = x;
+    ray.beta = y;
     return ray;
 }
 
