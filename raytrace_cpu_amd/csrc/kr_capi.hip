@@ -150,8 +150,7 @@ TablePins::~TablePins()
 
 void device_tables_shutdown()
 {
-    int keep = 0;
-    const bool have_dev = hipGetDevice(&keep) == hipSuccess;
+    CurrentDeviceGuard restore;
     std::lock_guard<std::mutex> lk(g_tables_mu);
     for (auto& dt : g_tables) {
         if (dt.second.empty()) continue;
@@ -159,8 +158,6 @@ void device_tables_shutdown()
         (void) hipDeviceSynchronize();
         free_unpinned(dt.second);
     }
-    if (have_dev) (void) hipSetDevice(keep);
-    (void) hipGetLastError();
 }
 
 namespace {

@@ -15,13 +15,22 @@ namespace kr {
 void set_error(const std::string& msg);
 int hip_fail(hipError_t e, const char* what, const char* file, int line);
 int require_device();   // KR_OK or KR_ENODEVICE (message set)
-int cu_count();         // compute units of the current device
 
 #define KR_HIP(call)                                                      \
     do {                                                                  \
         hipError_t e__ = (call);                                          \
         if (e__ != hipSuccess) return kr::hip_fail(e__, #call, __FILE__, __LINE__); \
     } while (0)
+
+// The current device, saved on construction and set again on destruction: for code that visits other devices (the shutdown paths).
+struct CurrentDeviceGuard {
+    int saved = 0;
+    bool have = false;
+    CurrentDeviceGuard() { have = hipGetDevice(&saved) == hipSuccess; (void) hipGetLastError(); }
+    CurrentDeviceGuard(const CurrentDeviceGuard&) = delete;
+    CurrentDeviceGuard& operator=(const CurrentDeviceGuard&) = delete;
+    ~CurrentDeviceGuard() { if (have) (void) hipSetDevice(saved); (void) hipGetLastError(); }
+};
 
 // RAII device scratch used by the host-buffer entry points
 struct DeviceBuffer {

@@ -12,7 +12,7 @@
 //     one integration step (RK45: one trial step) for every lane that holds a ray;
 //   * the grid is sized to the device (CUs x resident waves), not to n;
 //   * a launch cannot end before its longest ray does.  Large launches are therefore split in two concurrent ones
-//     (dispatch_split): the few ill-conditioned rays -- in the lamp-post workloads also the longest -- run the strict
+//     (split_front / split_back): the few ill-conditioned rays -- in the lamp-post workloads also the longest -- run the strict
 //     arithmetic on waves that own their SIMDs (HOG instances), everything else fills the rest of the chip, with the
 //     fast arithmetic (KR_FLAG_HYBRID) or the strict one (flags = 0; same bits as a single launch).
 //
@@ -62,9 +62,12 @@ constexpr int kLongRaySteps = 2048;  // a wave whose oldest ray is older than 1 
 #ifndef KR_OCC_STATS
 #define KR_OCC_STATS 0               // 1: lane-occupancy bookkeeping of the step loop (diagnostic builds: scripts/gpu_occ_stats.sh), printed by trace_wait
 #endif
-constexpr int kCounters = KR_OCC_STATS ? 13 : 8;         // [0] queue head, [1] rays traced, [2] steps, [3] rk45 attempts, [4] rk45 rejects, [5] rk45 stationary steps, [6] rk45 extrapolated steps,
-                                                         // [7] steps of the launch's longest ray (atomicMax); KR_OCC_STATS builds: [8..12] occupancy sums
-constexpr int kCounterBlocks = 4;    // main launch, strict side launch, strict overflow launch, split bookkeeping ([1] = number of ill-conditioned rays)
+// Every launch of a trace has a block of counter words of its own in the workspace (device memory; copied out at the end of the trace): the queue
+// head (slots handed out so far), rays traced, steps, rk45 attempts / rejects / stationary steps / extrapolated steps, steps of the launch's longest ray (atomicMax).
+enum CounterWord { kHead, kTraced, kSteps, kAttempts, kRejects, kStationary, kExtrapolated, kLongest, kCounterWords,
+                   kFlagged = kTraced };      // kFlagged, in the split bookkeeping block only: the number of ill-conditioned rays (classify_kernel)
+constexpr int kCounters = KR_OCC_STATS ? 13 : kCounterWords;         // words per block; KR_OCC_STATS builds: [8..12] occupancy sums
+enum CounterBlock { kMainBlock, kSideBlock, kOverflowBlock, kSplitBlock, kCounterBlocks };      // main launch, strict side launch, strict overflow launch, split bookkeeping
 constexpr int kListCap = 32768;      // index-list entries of the strict side launch
 
 template <typename T> struct RayOf;
@@ -151,11 +154,11 @@ template <typename T> struct TraceDesc {
     typename RayOf<T>::type* rays;
     long long n;
     TraceConsts<T> c;
-    unsigned long long* counters;
-    const int* list;
-    const unsigned long long* n_ptr;
-    const unsigned char* mask;
-    int n_mode, mask_want;
+    unsigned long long* counters;                 // this launch's counter block
+    const int* list = nullptr;                    // ray indices, or null for 0 .. n
+    const unsigned long long* n_ptr = nullptr;    // item count in device memory, or null (use n)
+    const unsigned char* mask = nullptr;          // per-ray launch selector, or null
+    int n_mode = 0, mask_want = 0;                // how n_ptr is applied (trace_body); the mask value this launch traces
 };
 
 template <typename T, int METHOD, bool USE_DEST, bool FAST, bool HOG, int REFILL_MIN>
@@ -234,7 +237,7 @@ KR_DEV void trace_body(typename RayOf<T>::type* __restrict__ rays, long long n, 
                 base = (unsigned long long) first_slot;
                 first_slot = -1;
             } else {
-                if (lane == leader) base = atomicAdd(&counters[0], (unsigned long long) n_need);
+                if (lane == leader) base = atomicAdd(&counters[kHead], (unsigned long long) n_need);
                 base = __shfl(base, leader, 64) + head_offset;
             }
             if (base + (unsigned long long) n_need >= (unsigned long long) n) exhausted = true;
@@ -312,13 +315,13 @@ KR_DEV void trace_body(typename RayOf<T>::type* __restrict__ rays, long long n, 
     }
 #endif
     if (lane == 0) {
-        if (w_longest) atomicMax(&counters[7], w_longest);
-        if (w_sta) atomicAdd(&counters[5], w_sta);
-        if (w_creep) atomicAdd(&counters[6], w_creep);
-        if (w_traced) atomicAdd(&counters[1], w_traced);
-        if (w_steps) atomicAdd(&counters[2], w_steps);
-        if (w_att) atomicAdd(&counters[3], w_att);
-        if (w_rej) atomicAdd(&counters[4], w_rej);
+        if (w_longest) atomicMax(&counters[kLongest], w_longest);
+        if (w_sta) atomicAdd(&counters[kStationary], w_sta);
+        if (w_creep) atomicAdd(&counters[kExtrapolated], w_creep);
+        if (w_traced) atomicAdd(&counters[kTraced], w_traced);
+        if (w_steps) atomicAdd(&counters[kSteps], w_steps);
+        if (w_att) atomicAdd(&counters[kAttempts], w_att);
+        if (w_rej) atomicAdd(&counters[kRejects], w_rej);
     }
 }
 
@@ -465,8 +468,10 @@ struct Workspace {
     int64_t n = 0;
 };
 
-std::mutex g_mu;
-std::vector<Workspace*> g_pool[64];
+unsigned long long* block(const Workspace* ws, CounterBlock which) { return ws->counters + which * kCounters; }
+const unsigned long long* host_block(const Workspace* ws, CounterBlock which) { return ws->h_counters + which * kCounters; }
+constexpr size_t kCounterBytes = kCounterBlocks * kCounters * sizeof(unsigned long long);
+
 constexpr size_t kMaxPool = 512;
 constexpr int kMaxBatch = 256;                           // traces one merged batch can hold
 constexpr int kMaxMultiGrid = 32768;                     // single-wave workgroups of a merged main launch (wave -> trace table entries)
@@ -482,14 +487,33 @@ constexpr int kMaxMultiGrid = 32768;                     // single-wave workgrou
 // a side stream is counted by everyone who may launch on it.  kr_stream_destroy / side_stream_forget drops the caller's entry and destroys the side
 // stream when its last user has gone; kr_shutdown destroys the rest.
 constexpr size_t kMaxSideStreams = 16;
-std::map<hipStream_t, hipStream_t> g_side_streams[64];      // caller's stream -> side stream
-std::map<hipStream_t, int> g_side_users[64];                // side stream -> number of entries above that point at it
+
+// What the library keeps per device.  g_mu guards the pools, the workspaces' leased / pending flags and the side-stream tables; polling has a mutex
+// of its own, so that a poll never waits behind a workspace acquisition that is blocked in hipEventSynchronize.
+constexpr int kMaxDevices = 64;
+struct DeviceState {
+    std::vector<Workspace*> pool;                        // g_mu
+    std::map<hipStream_t, hipStream_t> side_streams;     // g_mu: caller's stream -> side stream
+    std::map<hipStream_t, int> side_users;               // g_mu: side stream -> number of entries above that point at it
+    hipStream_t poll_stream = nullptr;                   // g_poll_mu (trace_poll)
+    unsigned long long* poll_word = nullptr;             // g_poll_mu: pinned, 8 bytes
+};
+std::mutex g_mu, g_poll_mu;
+DeviceState g_devices[kMaxDevices];
+
+DeviceState* device_state(int dev)
+{
+    if (dev < 0 || dev >= kMaxDevices) { set_error("device ordinal out of range"); return nullptr; }
+    return &g_devices[dev];
+}
 
 int side_stream_for(int dev, hipStream_t user, hipStream_t* out)
 {
+    DeviceState* ds = device_state(dev);
+    if (!ds) return KR_EINVAL;
     std::lock_guard<std::mutex> lk(g_mu);
-    auto& table = g_side_streams[dev];
-    auto& users = g_side_users[dev];
+    auto& table = ds->side_streams;
+    auto& users = ds->side_users;
     auto it = table.find(user);
     if (it == table.end()) {
         hipStream_t s = nullptr;
@@ -512,12 +536,8 @@ int side_stream_for(int dev, hipStream_t user, hipStream_t* out)
 void workspace_destroy(Workspace* w)
 {
     if (!w) return;
-    if (w->counters) (void) hipFree(w->counters);
-    if (w->h_counters) (void) hipHostFree(w->h_counters);
-    if (w->list) (void) hipFree(w->list);
-    if (w->mask) (void) hipFree(w->mask);
-    if (w->d_descs) (void) hipFree(w->d_descs);
-    if (w->h_descs) (void) hipHostFree(w->h_descs);
+    for (void* d : {(void*) w->counters, (void*) w->list, (void*) w->mask, w->d_descs}) if (d) (void) hipFree(d);
+    for (void* h : {(void*) w->h_counters, w->h_descs}) if (h) (void) hipHostFree(h);
     for (void* old : w->retired) (void) hipFree(old);
     for (hipEvent_t e : {w->ev0, w->ev1, w->ev_strict0, w->ev_strict1, w->ev_main0, w->ev_main1, w->ev_classified, w->done, w->ev_in})
         if (e) (void) hipEventDestroy(e);
@@ -530,18 +550,11 @@ int workspace_create(int dev, Workspace** out)
     w->device = dev;
     auto fail = [&](int rc) { workspace_destroy(w); return rc; };
 #define KR_WS(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return fail(kr::hip_fail(e__, #call, __FILE__, __LINE__)); } while (0)
-    KR_WS(hipMalloc((void**) &w->counters, kCounterBlocks * kCounters * sizeof(unsigned long long)));
-    KR_WS(hipHostMalloc((void**) &w->h_counters, kCounterBlocks * kCounters * sizeof(unsigned long long), hipHostMallocDefault));
+    KR_WS(hipMalloc((void**) &w->counters, kCounterBytes));
+    KR_WS(hipHostMalloc((void**) &w->h_counters, kCounterBytes, hipHostMallocDefault));
     KR_WS(hipMalloc((void**) &w->list, kListCap * sizeof(int)));
-    KR_WS(hipEventCreate(&w->ev0));
-    KR_WS(hipEventCreate(&w->ev1));
-    KR_WS(hipEventCreate(&w->ev_strict0));
-    KR_WS(hipEventCreate(&w->ev_strict1));
-    KR_WS(hipEventCreate(&w->ev_main0));
-    KR_WS(hipEventCreate(&w->ev_main1));
-    KR_WS(hipEventCreateWithFlags(&w->ev_classified, hipEventDisableTiming));
-    KR_WS(hipEventCreateWithFlags(&w->done, hipEventDisableTiming));
-    KR_WS(hipEventCreateWithFlags(&w->ev_in, hipEventDisableTiming));
+    for (hipEvent_t* timed : {&w->ev0, &w->ev1, &w->ev_strict0, &w->ev_strict1, &w->ev_main0, &w->ev_main1}) KR_WS(hipEventCreate(timed));
+    for (hipEvent_t* untimed : {&w->ev_classified, &w->done, &w->ev_in}) KR_WS(hipEventCreateWithFlags(untimed, hipEventDisableTiming));
     hipDeviceProp_t prop;
     KR_WS(hipGetDeviceProperties(&prop, dev));
 #undef KR_WS
@@ -571,11 +584,12 @@ int workspace_acquire(Workspace** out)
 {
     int dev = 0;
     KR_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64) { set_error("device ordinal out of range"); return KR_EINVAL; }
+    DeviceState* ds = device_state(dev);
+    if (!ds) return KR_EINVAL;
     Workspace* wait_for = nullptr;
     {
         std::lock_guard<std::mutex> lk(g_mu);
-        for (Workspace* w : g_pool[dev]) {
+        for (Workspace* w : ds->pool) {
             if (w->leased) continue;
             if (w->pending) {
                 if (hipEventQuery(w->done) != hipSuccess) { (void) hipGetLastError(); if (!wait_for) wait_for = w; continue; }
@@ -585,12 +599,12 @@ int workspace_acquire(Workspace** out)
             *out = w;
             return KR_OK;
         }
-        if (g_pool[dev].size() < kMaxPool) {
+        if (ds->pool.size() < kMaxPool) {
             Workspace* w = nullptr;
             const int rc = workspace_create(dev, &w);
             if (rc != KR_OK) return rc;
             w->leased = true;
-            g_pool[dev].push_back(w);
+            ds->pool.push_back(w);
             *out = w;
             return KR_OK;
         }
@@ -649,21 +663,32 @@ TraceConsts<T> make_consts(const kr_params* p, int steplim)
 
 constexpr int64_t kIsolateMinRays = 1 << 18;      // below this a strict launch is too short for the split to pay
 
-struct ListArgs {
-    const int* list = nullptr;                    // ray indices, or null for 0 .. n
-    const unsigned long long* n_ptr = nullptr;    // item count in device memory, or null (use n)
-    int n_mode = 0;                               // how n_ptr is applied (trace_kernel)
-    const unsigned char* mask = nullptr;          // per-ray launch selector, or null
-    int mask_want = 0;
-    int fixed_grid = 0;                           // > 0: launch exactly this many workgroups
+// (integrator, dest) -> the METHOD and USE_DEST template arguments, handed to `f` as two integral constants: the one place that knows
+// which of them exist (Euler has no stop surfaces: validate).  FAST and HOG stay compile-time at the call sites, so that only the
+// combinations in use are instantiated.
+template <typename F>
+int with_instance(int integrator, bool dest, F&& f)
+{
+    using std::integral_constant;
+    switch (integrator) {
+        case KR_EULER: return f(integral_constant<int, KR_EULER>(), std::false_type());
+        case KR_RK4: return dest ? f(integral_constant<int, KR_RK4>(), std::true_type()) : f(integral_constant<int, KR_RK4>(), std::false_type());
+        default: return dest ? f(integral_constant<int, KR_RK45>(), std::true_type()) : f(integral_constant<int, KR_RK45>(), std::false_type());
+    }
+}
+
+// how many workgroups a launch gets
+struct GridPolicy {
+    int max_blocks_per_cu = 0;                    // sized by occupancy, at most this many resident waves per SIMD (0: the table in launch)
+    int exact = 0;                                // > 0: exactly this many workgroups
+    static GridPolicy occupancy(int max_blocks_per_cu) { return GridPolicy{max_blocks_per_cu, 0}; }
+    static GridPolicy exactly(int workgroups) { return GridPolicy{0, workgroups}; }
 };
 
 template <typename T, int METHOD, bool USE_DEST, bool FAST, bool HOG = false>
-int launch(typename RayOf<T>::type* rays, int64_t n, const TraceConsts<T>& c, unsigned long long* counters, int cus,
-           hipStream_t stream, int max_blocks_per_cu, ListArgs la = ListArgs())
+int launch(const TraceDesc<T>& d, GridPolicy policy, int cus, hipStream_t stream)
 {
-    constexpr int kRefill = KR_REFILL_MIN;
-    auto kern = trace_kernel<T, METHOD, USE_DEST, FAST, HOG, kRefill>;
+    auto kern = trace_kernel<T, METHOD, USE_DEST, FAST, HOG, KR_REFILL_MIN>;
     // occupancy of each instance is a property of the code object: asked once per process
     static std::atomic<int> occ{0};                 // (host threads may race here: both would store the same value)
     int blocks_per_cu = occ.load(std::memory_order_relaxed);
@@ -680,7 +705,7 @@ int launch(typename RayOf<T>::type* rays, int64_t n, const TraceConsts<T>& c, un
     //   ImagePlane 4097^2 rays (longest ~2 000 steps)     480 / 344 / 318      fast-math 1e7 rays   176 / 121 / 110
     // Default: 3 when the launch is long enough for throughput to dominate (n >= 2e7, or fast-math with n >= 5e6),
     // else 2.  kr_params.flags bits 8..11 (KR_FLAG_BLOCKS_PER_CU) or the KR_BLOCKS_PER_CU environment variable override.
-    int want = max_blocks_per_cu > 0 ? max_blocks_per_cu : (METHOD == KR_EULER && FAST) ? 4 : ((n >= 20000000 || (FAST && n >= 5000000)) ? 3 : 2);
+    int want = policy.max_blocks_per_cu > 0 ? policy.max_blocks_per_cu : (METHOD == KR_EULER && FAST) ? 4 : ((d.n >= 20000000 || (FAST && d.n >= 5000000)) ? 3 : 2);
     if (const char* e = getenv("KR_BLOCKS_PER_CU")) {
         const int v = atoi(e);
         if (v >= 1) want = v;
@@ -688,55 +713,33 @@ int launch(typename RayOf<T>::type* rays, int64_t n, const TraceConsts<T>& c, un
     want *= 4;                                  // `want` counts waves per SIMD; a workgroup is one wave, a CU has four SIMDs
     if (want < blocks_per_cu) blocks_per_cu = want;
     const int64_t resident = (int64_t) cus * blocks_per_cu;
-    const int64_t wanted = (n + kTraceBlock - 1) / kTraceBlock;
-    int grid = (int) std::max<int64_t>(1, std::min(resident, wanted));
-    if (la.fixed_grid > 0) grid = la.fixed_grid;
-    if (!HOG && la.list) { set_error("kr_trace: only side launches work from a list"); return KR_EINVAL; }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kTraceBlock), 0, stream, rays, (long long) n, c, counters, la.list, la.n_ptr, la.n_mode, la.mask, la.mask_want);
+    const int64_t wanted = ((int64_t) d.n + kTraceBlock - 1) / kTraceBlock;
+    const int grid = policy.exact > 0 ? policy.exact : (int) std::max<int64_t>(1, std::min(resident, wanted));
+    if (!HOG && d.list) { set_error("kr_trace: only side launches work from a list"); return KR_EINVAL; }
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kTraceBlock), 0, stream, d.rays, d.n, d.c, d.counters, d.list, d.n_ptr, d.n_mode, d.mask, d.mask_want);
     KR_HIP(hipGetLastError());
     return KR_OK;
 }
 
-// one trace launch of the requested flavour (double only): FAST over `la` on `stream`, or strict HOG over `la`
+// one trace launch of the requested flavour (double only): FAST over `d` on `stream`, or strict HOG over `d`
 template <bool FAST, bool HOG>
-int launch_f64(const kr_params* p, kr_ray_f64* rays, int64_t n, const TraceConsts<double>& c, unsigned long long* counters, int cus,
-               hipStream_t stream, int mb, const ListArgs& la)
+int launch_f64(const kr_params* p, const TraceDesc<double>& d, GridPolicy policy, int cus, hipStream_t stream)
 {
-    const bool dest = (p->stop_kind != KR_STOP_THETA);
-    switch (p->integrator) {
-        case KR_EULER: return launch<double, KR_EULER, false, FAST, HOG>(rays, n, c, counters, cus, stream, mb, la);
-        case KR_RK4:
-            return dest ? launch<double, KR_RK4, true, FAST, HOG>(rays, n, c, counters, cus, stream, mb, la)
-                        : launch<double, KR_RK4, false, FAST, HOG>(rays, n, c, counters, cus, stream, mb, la);
-        default:
-            return dest ? launch<double, KR_RK45, true, FAST, HOG>(rays, n, c, counters, cus, stream, mb, la)
-                        : launch<double, KR_RK45, false, FAST, HOG>(rays, n, c, counters, cus, stream, mb, la);
-    }
+    return with_instance(p->integrator, p->stop_kind != KR_STOP_THETA, [&](auto method, auto dest) -> int {
+        return launch<double, decltype(method)::value, decltype(dest)::value, FAST, HOG>(d, policy, cus, stream);
+    });
 }
 
-// the same two for a whole batch of traces in ONE launch (trace_multi_kernel): `grid` single-wave workgroups, wave -> trace by table or modulo
-template <typename T, int METHOD, bool USE_DEST, bool FAST, bool HOG>
-int launch_multi(const TraceDesc<T>* d_descs, int n_desc, const int* d_wave_trace, int grid, hipStream_t stream)
-{
-    constexpr int kRefill = KR_REFILL_MIN;
-    auto kern = trace_multi_kernel<T, METHOD, USE_DEST, FAST, HOG, kRefill>;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kTraceBlock), 0, stream, d_descs, n_desc, d_wave_trace);
-    KR_HIP(hipGetLastError());
-    return KR_OK;
-}
-
+// the same for a whole batch of traces in ONE launch (trace_multi_kernel): `grid` single-wave workgroups, wave -> trace by table or modulo
 template <bool FAST, bool HOG>
-int launch_multi_f64(int integrator, bool dest, const TraceDesc<double>* d, int n_desc, const int* wt, int grid, hipStream_t stream)
+int launch_multi_f64(int integrator, bool dest, const TraceDesc<double>* d_descs, int n_desc, const int* d_wave_trace, int grid, hipStream_t stream)
 {
-    switch (integrator) {
-        case KR_EULER: return launch_multi<double, KR_EULER, false, FAST, HOG>(d, n_desc, wt, grid, stream);
-        case KR_RK4:
-            return dest ? launch_multi<double, KR_RK4, true, FAST, HOG>(d, n_desc, wt, grid, stream)
-                        : launch_multi<double, KR_RK4, false, FAST, HOG>(d, n_desc, wt, grid, stream);
-        default:
-            return dest ? launch_multi<double, KR_RK45, true, FAST, HOG>(d, n_desc, wt, grid, stream)
-                        : launch_multi<double, KR_RK45, false, FAST, HOG>(d, n_desc, wt, grid, stream);
-    }
+    return with_instance(integrator, dest, [&](auto method, auto use_dest) -> int {
+        auto kern = trace_multi_kernel<double, decltype(method)::value, decltype(use_dest)::value, FAST, HOG, KR_REFILL_MIN>;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(kTraceBlock), 0, stream, d_descs, n_desc, d_wave_trace);
+        KR_HIP(hipGetLastError());
+        return KR_OK;
+    });
 }
 
 // The split trace: classify -> strict HOG launch over the (listed) ill-conditioned rays, on the caller's stream, first, so that
@@ -744,108 +747,57 @@ int launch_multi_f64(int integrator, bool dest, const TraceDesc<double>* d, int 
 // stream, filling what is left (the other way round the main launch takes every SIMD's registers and the strict one waits).
 // fast_main: the main launch uses the fast arithmetic (KR_FLAG_HYBRID); otherwise it is the strict kernel too, i.e. the
 // results are those of one strict launch, bit for bit, and only the placement of the long rays differs.
-// Nothing here waits for the device: how many rays were flagged stays in device memory (counters block 3, word 1) and the
+// Nothing here waits for the device: how many rays were flagged stays in device memory (split bookkeeping block, kFlagged) and the
 // launches read it there.  The side launch is sized for the worst case the list can hold (workgroups that find the queue
 // empty leave at once); a source made mostly of ill-conditioned rays (all rays in one meridional plane, say) overflows the
 // list, and the overflow -- mask value 2 -- is traced by a third, ordinary-occupancy strict launch that is a no-op otherwise
 // (its workgroups read the count and leave).
-int split_front(const kr_params* p, kr_ray_f64* rays, int64_t n, int steplim, Workspace* ws, hipStream_t stream)
+struct SplitPlan {
+    TraceDesc<double> side;           // n_mode 1: the first min(flagged, side.n) list entries; side.n = what the list can hold of this trace
+    TraceDesc<double> main;           // every ray whose mask byte is 0
+    TraceDesc<double> overflow;       // n_mode 2: the rays with mask byte 2, if the list overflowed
+    bool has_overflow = false;        // the list can overflow at all (n > kListCap): without it there is no third launch
+};
+
+// the three launches of one split trace over the workspace's list, mask and counter blocks (the mask is grown here if need be)
+int plan_split(const kr_params* p, kr_ray_f64* rays, int64_t n, int steplim, Workspace* ws, SplitPlan* plan)
 {
     if (n > 0x7fffffff) { set_error("kr_trace: the split path indexes rays with 32 bits"); return KR_EINVAL; }
-    {
-        const int rc = workspace_mask_reserve(ws, n);
-        if (rc != KR_OK) return rc;
-    }
-    unsigned long long* split_words = ws->counters + 3 * kCounters;     // [1] n_strict (zeroed by the caller's memset)
-    const TraceConsts<double> c = make_consts<double>(p, steplim);
+    const int rc = workspace_mask_reserve(ws, n);
+    if (rc != KR_OK) return rc;
+    const unsigned long long* flagged = block(ws, kSplitBlock) + kFlagged;     // (zeroed by begin_trace)
+    const TraceDesc<double> all{rays, (long long) n, make_consts<double>(p, steplim), nullptr};
+    plan->side = plan->main = plan->overflow = all;
+    plan->side.n = (long long) std::min<int64_t>(n, kListCap);
+    plan->side.counters = block(ws, kSideBlock);
+    plan->side.list = ws->list;
+    plan->side.n_ptr = flagged;
+    plan->side.n_mode = 1;
+    plan->main.counters = block(ws, kMainBlock);
+    plan->main.mask = ws->mask;
+    plan->main.mask_want = 0;
+    plan->overflow.counters = block(ws, kOverflowBlock);
+    plan->overflow.n_ptr = flagged;
+    plan->overflow.n_mode = 2;
+    plan->overflow.mask = ws->mask;
+    plan->overflow.mask_want = 2;
+    plan->has_overflow = n > kListCap;
+    return KR_OK;
+}
+
+// fills the workspace's mask, list and flagged count for the rays of `plan`
+int enqueue_classify(const SplitPlan& plan, Workspace* ws, hipStream_t stream)
+{
+    const long long n = plan.main.n;
     const int cgrid = (int) ((n + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL(classify_kernel, dim3(cgrid), dim3(kBlock), 0, stream, rays, (long long) n, p->spin, ws->mask, ws->list, split_words + 1);
+    hipLaunchKernelGGL(classify_kernel, dim3(cgrid), dim3(kBlock), 0, stream, plan.main.rays, n, plan.main.c.a, ws->mask, ws->list, block(ws, kSplitBlock) + kFlagged);
     KR_HIP(hipGetLastError());
-    KR_HIP(hipEventRecord(ws->ev_classified, stream));
-    KR_HIP(hipEventRecord(ws->ev_strict0, stream));
-    // strict side launch: one wave, alone on its SIMD, per 64 listed rays, on at most half of the chip
-    ListArgs strict_la;
-    strict_la.list = ws->list;
-    strict_la.n_ptr = split_words + 1;
-    strict_la.n_mode = 1;
-    const int64_t list_max = std::min<int64_t>(n, kListCap);
-    strict_la.fixed_grid = (int) std::max<int64_t>(1, std::min<int64_t>((list_max + kTraceBlock - 1) / kTraceBlock, (int64_t) (ws->cus / 2) * 4));
-    const int rc = launch_f64<false, true>(p, rays, list_max, c, ws->counters + kCounters, ws->cus, stream, 1, strict_la);
-    if (rc != KR_OK) return rc;
-    KR_HIP(hipEventRecord(ws->ev_strict1, stream));
-    ws->split = true;
     return KR_OK;
-}
-
-int split_back(const kr_params* p, kr_ray_f64* rays, int64_t n, int steplim, Workspace* ws, hipStream_t stream, bool fast_main)
-{
-    unsigned long long* split_words = ws->counters + 3 * kCounters;
-    const TraceConsts<double> c = make_consts<double>(p, steplim);
-    const int mb = KR_FLAG_GET_BLOCKS_PER_CU(p->flags);
-    // main launch
-    KR_HIP(hipStreamWaitEvent(ws->side_stream, ws->ev_classified, 0));
-    KR_HIP(hipEventRecord(ws->ev_main0, ws->side_stream));
-    ListArgs main_la;
-    main_la.mask = ws->mask;
-    main_la.mask_want = 0;
-    const int main_waves = mb ? mb : (fast_main && p->integrator == KR_EULER) ? 4 : 3;      // resident waves per SIMD of the main launch
-    int rc = fast_main ? launch_f64<true, false>(p, rays, n, c, ws->counters, ws->cus, ws->side_stream, main_waves, main_la)
-                       : launch_f64<false, false>(p, rays, n, c, ws->counters, ws->cus, ws->side_stream, main_waves, main_la);
-    if (rc != KR_OK) return rc;
-    // strict overflow launch (mask == 2): only has work when more than kListCap rays were flagged, and then the main launch has
-    // next to none.  It follows the main launch on the side stream: behind the side launch on the caller's stream its idle
-    // workgroups would sit waiting for the main launch's registers (measured: 10 ms of "kernel time" doing nothing).
-    if (n > kListCap) {
-        ListArgs rest_la;
-        rest_la.n_ptr = split_words + 1;
-        rest_la.n_mode = 2;
-        rest_la.mask = ws->mask;
-        rest_la.mask_want = 2;
-        rc = launch_f64<false, false>(p, rays, n, c, ws->counters + 2 * kCounters, ws->cus, ws->side_stream, mb, rest_la);
-        if (rc != KR_OK) return rc;
-    }
-    KR_HIP(hipEventRecord(ws->ev_main1, ws->side_stream));
-    KR_HIP(hipStreamWaitEvent(stream, ws->ev_main1, 0));
-    return KR_OK;
-}
-
-template <typename T>
-int dispatch(const kr_params* p, void* d_rays, int64_t n, int steplim, unsigned long long* counters, int cus, hipStream_t stream)
-{
-    ListArgs la;
-    using R = typename RayOf<T>::type;
-    R* rays = (R*) d_rays;
-    const TraceConsts<T> c = make_consts<T>(p, steplim);
-    const bool dest = (p->stop_kind != KR_STOP_THETA);
-    const int mb = KR_FLAG_GET_BLOCKS_PER_CU(p->flags);
-    if constexpr (std::is_same<T, double>::value) {
-        if (p->flags & KR_FLAG_FAST_MATH) {
-            switch (p->integrator) {
-                case KR_EULER: return launch<T, KR_EULER, false, true>(rays, n, c, counters, cus, stream, mb, la);
-                case KR_RK4:
-                    return dest ? launch<T, KR_RK4, true, true>(rays, n, c, counters, cus, stream, mb, la)
-                                : launch<T, KR_RK4, false, true>(rays, n, c, counters, cus, stream, mb, la);
-                default:
-                    return dest ? launch<T, KR_RK45, true, true>(rays, n, c, counters, cus, stream, mb, la)
-                                : launch<T, KR_RK45, false, true>(rays, n, c, counters, cus, stream, mb, la);
-            }
-        }
-    }
-    switch (p->integrator) {
-        case KR_EULER: return launch<T, KR_EULER, false, false>(rays, n, c, counters, cus, stream, mb, la);
-        case KR_RK4:
-            return dest ? launch<T, KR_RK4, true, false>(rays, n, c, counters, cus, stream, mb, la)
-                        : launch<T, KR_RK4, false, false>(rays, n, c, counters, cus, stream, mb, la);
-        default:
-            return dest ? launch<T, KR_RK45, true, false>(rays, n, c, counters, cus, stream, mb, la)
-                        : launch<T, KR_RK45, false, false>(rays, n, c, counters, cus, stream, mb, la);
-    }
 }
 
 int validate(const kr_params* p, void* d_rays, int64_t n)
 {
-    if (p && n > 0 && !d_rays) { set_error("kr_trace: null argument or negative n"); return KR_EINVAL; }
-    if (!p || n < 0) { set_error("kr_trace: null argument or negative n"); return KR_EINVAL; }
+    if (!p || n < 0 || (n > 0 && !d_rays)) { set_error("kr_trace: null argument or negative n"); return KR_EINVAL; }
     if (p->integrator < KR_EULER || p->integrator > KR_RK45) { set_error("kr_trace: unknown integrator"); return KR_EINVAL; }
     if (p->stop_kind < KR_STOP_THETA || p->stop_kind > KR_STOP_FLATPLANE) { set_error("kr_trace: unknown stop_kind"); return KR_EINVAL; }
     if (p->stop_kind != KR_STOP_THETA && p->integrator == KR_EULER) {
@@ -854,6 +806,29 @@ int validate(const kr_params* p, void* d_rays, int64_t n)
         return KR_EINVAL;
     }
     return require_device();
+}
+
+// effective_steplim, raytracer.cpp:80
+int effective_steplim(const kr_params* p)
+{
+    return (p->steplim > 0) ? p->steplim : (p->integrator == KR_RK45) ? KR_RK45_STEPLIM : KR_STEPLIM;
+}
+
+// the two ends of every trace on its (primary) stream: counters zeroed and the clock started; the clock stopped, the counters
+// copied out and `done` recorded
+int begin_trace(Workspace* ws, hipStream_t stream)
+{
+    KR_HIP(hipMemsetAsync(ws->counters, 0, kCounterBytes, stream));
+    KR_HIP(hipEventRecord(ws->ev0, stream));
+    return KR_OK;
+}
+
+int end_trace(Workspace* ws, hipStream_t stream)
+{
+    KR_HIP(hipEventRecord(ws->ev1, stream));
+    KR_HIP(hipMemcpyAsync(ws->h_counters, ws->counters, kCounterBytes, hipMemcpyDeviceToHost, stream));
+    KR_HIP(hipEventRecord(ws->done, stream));
+    return KR_OK;
 }
 
 // One trace is enqueued in two halves, so that a batch of traces can put ALL its front halves on the device before any back half:
@@ -870,15 +845,70 @@ struct Pending {
     bool f32 = false, hybrid = false, split = false;
     int steplim = 0;
     Workspace* ws = nullptr;
+    SplitPlan plan;                   // split traces: made by the front half (launch constants included), used by both
 };
+
+int split_front(Pending& t)
+{
+    Workspace* ws = t.ws;
+    int rc = plan_split(t.p, (kr_ray_f64*) t.d_rays, t.n, t.steplim, ws, &t.plan);
+    if (rc != KR_OK) return rc;
+    rc = enqueue_classify(t.plan, ws, t.stream);
+    if (rc != KR_OK) return rc;
+    KR_HIP(hipEventRecord(ws->ev_classified, t.stream));
+    KR_HIP(hipEventRecord(ws->ev_strict0, t.stream));
+    // strict side launch: one wave, alone on its SIMD, per 64 listed rays, on at most half of the chip
+    const int grid = (int) std::max<int64_t>(1, std::min<int64_t>((t.plan.side.n + kTraceBlock - 1) / kTraceBlock, (int64_t) (ws->cus / 2) * 4));
+    rc = launch_f64<false, true>(t.p, t.plan.side, GridPolicy::exactly(grid), ws->cus, t.stream);
+    if (rc != KR_OK) return rc;
+    KR_HIP(hipEventRecord(ws->ev_strict1, t.stream));
+    ws->split = true;
+    return KR_OK;
+}
+
+int split_back(Pending& t)
+{
+    Workspace* ws = t.ws;
+    const int mb = KR_FLAG_GET_BLOCKS_PER_CU(t.p->flags);
+    // main launch
+    KR_HIP(hipStreamWaitEvent(ws->side_stream, ws->ev_classified, 0));
+    KR_HIP(hipEventRecord(ws->ev_main0, ws->side_stream));
+    const GridPolicy main_waves = GridPolicy::occupancy(mb ? mb : (t.hybrid && t.p->integrator == KR_EULER) ? 4 : 3);      // resident waves per SIMD of the main launch
+    int rc = t.hybrid ? launch_f64<true, false>(t.p, t.plan.main, main_waves, ws->cus, ws->side_stream)
+                      : launch_f64<false, false>(t.p, t.plan.main, main_waves, ws->cus, ws->side_stream);
+    if (rc != KR_OK) return rc;
+    // strict overflow launch (mask == 2): only has work when more than kListCap rays were flagged, and then the main launch has
+    // next to none.  It follows the main launch on the side stream: behind the side launch on the caller's stream its idle
+    // workgroups would sit waiting for the main launch's registers (measured: 10 ms of "kernel time" doing nothing).
+    if (t.plan.has_overflow) {
+        rc = launch_f64<false, false>(t.p, t.plan.overflow, GridPolicy::occupancy(mb), ws->cus, ws->side_stream);
+        if (rc != KR_OK) return rc;
+    }
+    KR_HIP(hipEventRecord(ws->ev_main1, ws->side_stream));
+    KR_HIP(hipStreamWaitEvent(t.stream, ws->ev_main1, 0));
+    return KR_OK;
+}
+
+// the unsplit trace: one launch over all rays, strict or (double only) fast
+template <typename T>
+int dispatch(const Pending& t)
+{
+    const TraceDesc<T> d{(typename RayOf<T>::type*) t.d_rays, (long long) t.n, make_consts<T>(t.p, t.steplim), block(t.ws, kMainBlock)};
+    const GridPolicy policy = GridPolicy::occupancy(KR_FLAG_GET_BLOCKS_PER_CU(t.p->flags));
+    return with_instance(t.p->integrator, t.p->stop_kind != KR_STOP_THETA, [&](auto method, auto dest) -> int {
+        if constexpr (std::is_same<T, double>::value) {
+            if (t.p->flags & KR_FLAG_FAST_MATH) return launch<T, decltype(method)::value, decltype(dest)::value, true>(d, policy, t.ws->cus, t.stream);
+        }
+        return launch<T, decltype(method)::value, decltype(dest)::value, false>(d, policy, t.ws->cus, t.stream);
+    });
+}
 
 int trace_front(Pending& t, bool batch)
 {
     int rc = validate(t.p, t.d_rays, t.n);
     if (rc != KR_OK) return rc;
     if (t.n == 0) return KR_OK;
-    // effective_steplim, raytracer.cpp:80
-    t.steplim = (t.p->steplim > 0) ? t.p->steplim : (t.p->integrator == KR_RK45) ? KR_RK45_STEPLIM : KR_STEPLIM;
+    t.steplim = effective_steplim(t.p);
     rc = workspace_acquire(&t.ws);
     if (rc != KR_OK) return rc;
     Workspace* ws = t.ws;
@@ -890,28 +920,19 @@ int trace_front(Pending& t, bool batch)
     // KR_NO_ISOLATE=1 keeps the single launch (A/B and bit-identity tests).
     const bool isolate = !t.f32 && !t.hybrid && !(t.p->flags & KR_FLAG_FAST_MATH) && (t.n >= kIsolateMinRays || (batch && t.n >= 4096)) && !getenv("KR_NO_ISOLATE");
     t.split = t.hybrid || isolate;
-    KR_HIP(hipMemsetAsync(ws->counters, 0, kCounterBlocks * kCounters * sizeof(unsigned long long), t.stream));
-    KR_HIP(hipEventRecord(ws->ev0, t.stream));
-    if (t.split) {
-        rc = side_stream_for(ws->device, t.stream, &ws->side_stream);
-        if (rc != KR_OK) return rc;
-        return split_front(t.p, (kr_ray_f64*) t.d_rays, t.n, t.steplim, ws, t.stream);
-    }
-    return KR_OK;
+    rc = begin_trace(ws, t.stream);
+    if (rc != KR_OK || !t.split) return rc;
+    rc = side_stream_for(ws->device, t.stream, &ws->side_stream);
+    if (rc != KR_OK) return rc;
+    return split_front(t);
 }
 
 int trace_back(Pending& t)
 {
     if (t.n == 0 || !t.ws) return KR_OK;
-    Workspace* ws = t.ws;
-    int r = t.f32 ? dispatch<float>(t.p, t.d_rays, t.n, t.steplim, ws->counters, ws->cus, t.stream)
-                  : t.split ? split_back(t.p, (kr_ray_f64*) t.d_rays, t.n, t.steplim, ws, t.stream, t.hybrid)
-                            : dispatch<double>(t.p, t.d_rays, t.n, t.steplim, ws->counters, ws->cus, t.stream);
-    if (r != KR_OK) return r;
-    KR_HIP(hipEventRecord(ws->ev1, t.stream));
-    KR_HIP(hipMemcpyAsync(ws->h_counters, ws->counters, kCounterBlocks * kCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost, t.stream));
-    KR_HIP(hipEventRecord(ws->done, t.stream));
-    return KR_OK;
+    const int rc = t.f32 ? dispatch<float>(t) : t.split ? split_back(t) : dispatch<double>(t);
+    if (rc != KR_OK) return rc;
+    return end_trace(t.ws, t.stream);
 }
 
 // After a failure part-way: whatever was enqueued must drain before the workspace is reused.  The kernels of a split trace sit on the
@@ -965,20 +986,17 @@ int merged_batch(std::vector<Pending>& ts, bool hybrid)
     const bool dest = p0->stop_kind != KR_STOP_THETA;
     hipStream_t primary = ts[0].stream;
     for (auto& t : ts) {
-        t.steplim = (t.p->steplim > 0) ? t.p->steplim : (t.p->integrator == KR_RK45) ? KR_RK45_STEPLIM : KR_STEPLIM;
+        t.steplim = effective_steplim(t.p);
         int rc = workspace_acquire(&t.ws);
         if (rc != KR_OK) return rc;
         t.ws->split = true;
         t.ws->n = t.n;
-        t.hybrid = hybrid;
-        t.split = true;
     }
     Workspace* w0 = ts[0].ws;
     hipStream_t side = nullptr;
     int rc = side_stream_for(w0->device, primary, &side);
     if (rc != KR_OK) return rc;
-    const size_t desc_bytes = sizeof(TraceDesc<double>);
-    const size_t table_off = 3 * kMaxBatch * desc_bytes;                   // [side descs | main descs | overflow descs | wave -> trace table of the main launch]
+    const size_t table_off = 3 * kMaxBatch * sizeof(TraceDesc<double>);                   // [side descs | main descs | overflow descs | wave -> trace table of the main launch]
     const size_t staging_bytes = table_off + kMaxMultiGrid * sizeof(int);
     if (!w0->d_descs) {
         KR_HIP(hipMalloc(&w0->d_descs, staging_bytes));
@@ -998,21 +1016,14 @@ int merged_batch(std::vector<Pending>& ts, bool hybrid)
         Pending& t = ts[i];
         Workspace* ws = t.ws;
         ws->side_stream = side;
-        if (t.n > 0x7fffffff) { set_error("kr_trace: the split path indexes rays with 32 bits"); return KR_EINVAL; }
-        rc = workspace_mask_reserve(ws, t.n);
+        rc = plan_split(t.p, (kr_ray_f64*) t.d_rays, t.n, t.steplim, ws, &t.plan);
+        if (rc == KR_OK) rc = begin_trace(ws, primary);
+        if (rc == KR_OK) rc = enqueue_classify(t.plan, ws, primary);
         if (rc != KR_OK) return rc;
-        KR_HIP(hipMemsetAsync(ws->counters, 0, kCounterBlocks * kCounters * sizeof(unsigned long long), primary));
-        KR_HIP(hipEventRecord(ws->ev0, primary));
-        unsigned long long* split_words = ws->counters + 3 * kCounters;
-        const int cgrid = (int) ((t.n + kBlock - 1) / kBlock);
-        hipLaunchKernelGGL(classify_kernel, dim3(cgrid), dim3(kBlock), 0, primary, (const kr_ray_f64*) t.d_rays, (long long) t.n, t.p->spin, ws->mask, ws->list, split_words + 1);
-        KR_HIP(hipGetLastError());
-        const TraceConsts<double> c = make_consts<double>(t.p, t.steplim);
-        const int64_t list_max = std::min<int64_t>(t.n, kListCap);
-        hog[i] = TraceDesc<double>{(kr_ray_f64*) t.d_rays, (long long) list_max, c, ws->counters + kCounters, ws->list, split_words + 1, nullptr, 1, 0};
-        mainv[i] = TraceDesc<double>{(kr_ray_f64*) t.d_rays, (long long) t.n, c, ws->counters, nullptr, nullptr, ws->mask, 0, 0};
-        if (t.n > kListCap) rest[n_rest++] = TraceDesc<double>{(kr_ray_f64*) t.d_rays, (long long) t.n, c, ws->counters + 2 * kCounters, nullptr, split_words + 1, ws->mask, 2, 2};
-        hog_max = std::max<int64_t>(hog_max, (list_max + kTraceBlock - 1) / kTraceBlock);
+        hog[i] = t.plan.side;
+        mainv[i] = t.plan.main;
+        if (t.plan.has_overflow) rest[n_rest++] = t.plan.overflow;
+        hog_max = std::max<int64_t>(hog_max, (t.plan.side.n + kTraceBlock - 1) / kTraceBlock);
         main_waves += (t.n + kTraceBlock - 1) / kTraceBlock;
         n_total += t.n;
     }
@@ -1057,11 +1068,9 @@ int merged_batch(std::vector<Pending>& ts, bool hybrid)
     for (auto& t : ts) KR_HIP(hipEventRecord(t.ws->ev_main1, side));
     KR_HIP(hipStreamWaitEvent(primary, ts.back().ws->ev_main1, 0));      // the last one recorded: every ev_main1 has completed by then
     for (auto& t : ts) {
-        Workspace* ws = t.ws;
-        KR_HIP(hipEventRecord(ws->ev1, primary));
-        KR_HIP(hipMemcpyAsync(ws->h_counters, ws->counters, kCounterBlocks * kCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost, primary));
-        KR_HIP(hipEventRecord(ws->done, primary));
-        if (t.stream != primary) KR_HIP(hipStreamWaitEvent(t.stream, ws->done, 0));       // the caller's next kernels on that stream see the traced rays
+        rc = end_trace(t.ws, primary);
+        if (rc != KR_OK) return rc;
+        if (t.stream != primary) KR_HIP(hipStreamWaitEvent(t.stream, t.ws->done, 0));       // the caller's next kernels on that stream see the traced rays
     }
     return KR_OK;
 }
@@ -1086,15 +1095,10 @@ int trace_batch_async(int count, const kr_params* const* p, void* const* d_rays,
     }
     if (merge) {
         rc = merged_batch(ts, (p[0]->flags & KR_FLAG_HYBRID) != 0);
-        if (rc != KR_OK) {
-            for (auto& t : ts) abandon(t);
-            return rc;
-        }
-        for (int i = 0; i < count; i++) hand_over(ts[i], &tickets[i]);
-        return KR_OK;
+    } else {
+        for (int i = 0; i < count && rc == KR_OK; i++) rc = trace_front(ts[i], true);
+        for (int i = 0; i < count && rc == KR_OK; i++) rc = trace_back(ts[i]);
     }
-    for (int i = 0; i < count && rc == KR_OK; i++) rc = trace_front(ts[i], true);
-    for (int i = 0; i < count && rc == KR_OK; i++) rc = trace_back(ts[i]);
     if (rc != KR_OK) {
         for (auto& t : ts) abandon(t);
         return rc;
@@ -1112,30 +1116,30 @@ int trace_wait(void* ticket, kr_stats* stats)
     auto body = [&]() -> int {
         KR_HIP(hipEventSynchronize(ws->done));
         if (!stats) return KR_OK;
-        const unsigned long long* h2 = ws->h_counters;
-        unsigned long long h[kCounters];
-        for (int i = 0; i < kCounters; i++) h[i] = h2[i] + h2[kCounters + i] + h2[2 * kCounters + i];
-        h[7] = std::max(h2[7], std::max(h2[kCounters + 7], h2[2 * kCounters + 7]));      // a maximum, not a sum
+        const unsigned long long* mainb = host_block(ws, kMainBlock), * side = host_block(ws, kSideBlock), * over = host_block(ws, kOverflowBlock);
+        unsigned long long h[kCounterWords];
+        for (int i = 0; i < kCounterWords; i++) h[i] = mainb[i] + side[i] + over[i];
+        h[kLongest] = std::max(mainb[kLongest], std::max(side[kLongest], over[kLongest]));      // a maximum, not a sum
 #if KR_OCC_STATS
-        for (int b = 0; b < 3; b++) {
-            const unsigned long long* q = h2 + b * kCounters;
+        for (CounterBlock b : {kMainBlock, kSideBlock, kOverflowBlock}) {
+            const unsigned long long* q = host_block(ws, b);
             if (q[8]) std::fprintf(stderr, "kr_occ: launch %d (0 main, 1 strict side, 2 overflow): steps %llu wave_iters %llu step-loop lane occupancy %.4f | after queue exhaustion: "
-                                   "wave_iters %llu (%.2f %%) lane occupancy %.4f | refills %llu lanes/refill %.2f | longest ray %llu steps\n", b, q[2], q[8], (double) q[2] / (64.0 * q[8]), q[9],
-                                   100.0 * q[9] / q[8], q[9] ? (double) q[10] / (64.0 * q[9]) : 0.0, q[11], q[11] ? (double) q[12] / q[11] : 0.0, q[7]);
+                                   "wave_iters %llu (%.2f %%) lane occupancy %.4f | refills %llu lanes/refill %.2f | longest ray %llu steps\n", (int) b, q[kSteps], q[8], (double) q[kSteps] / (64.0 * q[8]), q[9],
+                                   100.0 * q[9] / q[8], q[9] ? (double) q[10] / (64.0 * q[9]) : 0.0, q[11], q[11] ? (double) q[12] / q[11] : 0.0, q[kLongest]);
         }
 #endif
         stats->rays_total = ws->n;
-        stats->rays_strict_side = (int64_t) h2[3 * kCounters + 1];
-        stats->rays_traced = (int64_t) h[1];
-        stats->steps_total = (int64_t) h[2];
-        stats->rk45_attempts = (int64_t) h[3];
-        stats->rk45_rejects = (int64_t) h[4];
-        stats->rk45_stationary_steps = (int64_t) h[5];
-        stats->rk45_extrapolated_steps = (int64_t) h[6];
-        stats->longest_ray_steps = (int64_t) h[7];
-        stats->longest_ray_steps_strict_side = ws->split ? (int64_t) h2[kCounters + 7] : 0;
-        stats->steps_strict_side = ws->split ? (int64_t) h2[kCounters + 2] : 0;
-        stats->rk45_evaluated_strict_side = ws->split ? (int64_t) (h2[kCounters + 3] - h2[kCounters + 5] - h2[kCounters + 6]) : 0;
+        stats->rays_strict_side = (int64_t) host_block(ws, kSplitBlock)[kFlagged];
+        stats->rays_traced = (int64_t) h[kTraced];
+        stats->steps_total = (int64_t) h[kSteps];
+        stats->rk45_attempts = (int64_t) h[kAttempts];
+        stats->rk45_rejects = (int64_t) h[kRejects];
+        stats->rk45_stationary_steps = (int64_t) h[kStationary];
+        stats->rk45_extrapolated_steps = (int64_t) h[kExtrapolated];
+        stats->longest_ray_steps = (int64_t) h[kLongest];
+        stats->longest_ray_steps_strict_side = ws->split ? (int64_t) side[kLongest] : 0;
+        stats->steps_strict_side = ws->split ? (int64_t) side[kSteps] : 0;
+        stats->rk45_evaluated_strict_side = ws->split ? (int64_t) (side[kAttempts] - side[kStationary] - side[kExtrapolated]) : 0;
         float ms = 0;
         KR_HIP(hipEventElapsedTime(&ms, ws->ev0, ws->ev1));
         stats->kernel_ms = ms;
@@ -1160,12 +1164,6 @@ int trace_wait(void* ticket, kr_stats* stats)
 // counter counts, raytracer.cpp:107-112: a ray is counted when its loop iteration STARTS), and whether the trace has finished.  The queue head lives
 // in device memory; it is read with an 8-byte copy on a stream of the library's own (a DMA transfer: it needs no compute unit, so it completes while
 // the persistent kernels hold every SIMD), a few microseconds per call.  Does not wait for the trace and does not retire the ticket.
-namespace {
-std::mutex g_poll_mu;
-hipStream_t g_poll_stream[64];
-unsigned long long* g_poll_word[64];
-}  // namespace
-
 int trace_poll(void* ticket, int64_t* rays_started, int32_t* finished)
 {
     if (rays_started) *rays_started = 0;
@@ -1183,15 +1181,17 @@ int trace_poll(void* ticket, int64_t* rays_started, int32_t* finished)
     int dev = 0;
     KR_HIP(hipGetDevice(&dev));
     if (dev != ws->device) { set_error("kr_trace_poll: the ticket belongs to another device than the current one"); return KR_EINVAL; }
+    DeviceState* ds = device_state(dev);
+    if (!ds) return KR_EINVAL;
     std::lock_guard<std::mutex> lk(g_poll_mu);
-    if (!g_poll_stream[dev]) {
-        KR_HIP(hipStreamCreateWithFlags(&g_poll_stream[dev], hipStreamNonBlocking));
-        KR_HIP(hipHostMalloc((void**) &g_poll_word[dev], sizeof(unsigned long long), hipHostMallocDefault));
+    if (!ds->poll_stream) {
+        KR_HIP(hipStreamCreateWithFlags(&ds->poll_stream, hipStreamNonBlocking));
+        KR_HIP(hipHostMalloc((void**) &ds->poll_word, sizeof(unsigned long long), hipHostMallocDefault));
     }
-    // block 0 = the main launch (or the only one): its head runs over all n slots, also those whose rays belong to the side launch
-    KR_HIP(hipMemcpyAsync(g_poll_word[dev], ws->counters, sizeof(unsigned long long), hipMemcpyDeviceToHost, g_poll_stream[dev]));
-    KR_HIP(hipStreamSynchronize(g_poll_stream[dev]));
-    if (rays_started) *rays_started = (int64_t) std::min<unsigned long long>(*g_poll_word[dev], (unsigned long long) ws->n);
+    // the main launch (or the only one): its head runs over all n slots, also those whose rays belong to the side launch
+    KR_HIP(hipMemcpyAsync(ds->poll_word, block(ws, kMainBlock) + kHead, sizeof(unsigned long long), hipMemcpyDeviceToHost, ds->poll_stream));
+    KR_HIP(hipStreamSynchronize(ds->poll_stream));
+    if (rays_started) *rays_started = (int64_t) std::min<unsigned long long>(*ds->poll_word, (unsigned long long) ws->n);
     return KR_OK;
 }
 
@@ -1210,14 +1210,15 @@ void side_stream_forget(hipStream_t user)
     int side_dev = -1;
     {
         std::lock_guard<std::mutex> lk(g_mu);
-        for (int dev = 0; dev < 64 && side_dev < 0; dev++) {
-            auto it = g_side_streams[dev].find(user);
-            if (it == g_side_streams[dev].end()) continue;
+        for (int dev = 0; dev < kMaxDevices && side_dev < 0; dev++) {
+            DeviceState& ds = g_devices[dev];
+            auto it = ds.side_streams.find(user);
+            if (it == ds.side_streams.end()) continue;
             hipStream_t s = it->second;
-            g_side_streams[dev].erase(it);
-            auto u = g_side_users[dev].find(s);
-            if (u != g_side_users[dev].end() && --u->second <= 0) {
-                g_side_users[dev].erase(u);
+            ds.side_streams.erase(it);
+            auto u = ds.side_users.find(s);
+            if (u != ds.side_users.end() && --u->second <= 0) {
+                ds.side_users.erase(u);
                 side = s;                                    // its last user: nobody can be handed it any more
                 side_dev = dev;
             } else {
@@ -1226,50 +1227,41 @@ void side_stream_forget(hipStream_t user)
         }
     }
     if (!side) return;
-    int keep = 0;
-    const bool have_dev = hipGetDevice(&keep) == hipSuccess;
+    CurrentDeviceGuard restore;
     if (hipSetDevice(side_dev) == hipSuccess) {
         (void) hipStreamSynchronize(side);
         (void) hipStreamDestroy(side);
     }
-    if (have_dev) (void) hipSetDevice(keep);
-    (void) hipGetLastError();
 }
 
 // kr_shutdown: waits for the devices this library has used, then gives back every pooled workspace and side stream.  Refused (KR_EINVAL, nothing
 // released) while a trace ticket is outstanding: its kr_trace_wait / kr_trace_release would touch a freed workspace.
 int trace_shutdown()
 {
-    int keep = 0;
-    const bool have_dev = hipGetDevice(&keep) == hipSuccess;
-    (void) hipGetLastError();
+    CurrentDeviceGuard restore;
     std::lock_guard<std::mutex> lk(g_mu);
-    {
-        size_t leased = 0;
-        for (int dev = 0; dev < 64; dev++)
-            for (Workspace* w : g_pool[dev]) leased += w->leased ? 1 : 0;
-        if (leased) {
-            set_error("kr_shutdown: trace tickets are outstanding (kr_trace_wait / kr_trace_release them first)");
-            return KR_EINVAL;
-        }
-    }
-    for (int dev = 0; dev < 64; dev++) {
-        if (g_pool[dev].empty() && g_side_users[dev].empty() && !g_poll_stream[dev]) continue;
+    for (const DeviceState& ds : g_devices)
+        for (const Workspace* w : ds.pool)
+            if (w->leased) {
+                set_error("kr_shutdown: trace tickets are outstanding (kr_trace_wait / kr_trace_release them first)");
+                return KR_EINVAL;
+            }
+    for (int dev = 0; dev < kMaxDevices; dev++) {
+        DeviceState& ds = g_devices[dev];
+        if (ds.pool.empty() && ds.side_users.empty() && !ds.poll_stream) continue;
         if (hipSetDevice(dev) != hipSuccess) { (void) hipGetLastError(); continue; }
         (void) hipDeviceSynchronize();
-        for (Workspace* w : g_pool[dev]) workspace_destroy(w);
-        g_pool[dev].clear();
+        for (Workspace* w : ds.pool) workspace_destroy(w);
+        ds.pool.clear();
         {
             std::lock_guard<std::mutex> pl(g_poll_mu);
-            if (g_poll_stream[dev]) { (void) hipStreamDestroy(g_poll_stream[dev]); g_poll_stream[dev] = nullptr; }
-            if (g_poll_word[dev]) { (void) hipHostFree(g_poll_word[dev]); g_poll_word[dev] = nullptr; }
+            if (ds.poll_stream) { (void) hipStreamDestroy(ds.poll_stream); ds.poll_stream = nullptr; }
+            if (ds.poll_word) { (void) hipHostFree(ds.poll_word); ds.poll_word = nullptr; }
         }
-        for (auto& kv : g_side_users[dev]) (void) hipStreamDestroy(kv.first);
-        g_side_users[dev].clear();
-        g_side_streams[dev].clear();
+        for (auto& kv : ds.side_users) (void) hipStreamDestroy(kv.first);
+        ds.side_users.clear();
+        ds.side_streams.clear();
     }
-    if (have_dev) (void) hipSetDevice(keep);
-    (void) hipGetLastError();
     return KR_OK;
 }
 
