@@ -19,44 +19,9 @@
 #include <thread>
 #include <vector>
 
-#include "kr_common.hpp"
-#include "kr_post_device.hpp"
+#include "kr_pass.hpp"
 
 namespace kr {
-
-// implemented in kr_post.hip
-int redshift_start_dev(double spin, double V, int reverse, int projradius, void* d, int64_t n, hipStream_t st, bool f32 = false);
-int redshift_dev(double spin, double V, int reverse, int projradius, int motion, void* d, int64_t n, hipStream_t st, bool f32 = false);
-int redshift_dest_dev(double spin, int reverse, void* d, int64_t n, hipStream_t st, bool f32 = false);
-int range_phi_dev(double lo, double hi, void* d, int64_t n, hipStream_t st, bool f32 = false);
-int calculate_momentum_dev(double spin, void* d, int64_t n, hipStream_t st, bool f32 = false);
-int pointsource_init_dev(const kr_pointsource* s, void* d, int64_t n, int64_t first, int64_t stride, hipStream_t st);
-int imageplane_init_dev(const kr_imageplane* s, void* d, int64_t n, int64_t first, int64_t stride, hipStream_t st);
-int reduce_emissivity_dev(const kr_emis_bins* b, const void* d, int64_t n, void* d_hist, hipStream_t st);
-int post_emissivity_dev(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_emis_bins* b, void* d, int64_t n,
-                        void* d_hist, hipStream_t st);
-int imageplane_init_emit_dev(const kr_imageplane* s, void* d, int64_t n, int64_t first, int64_t stride, int64_t run, double spin, double V, int reverse,
-                             int projradius, hipStream_t st);
-int post_image_dev(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_image_bins* b, void* d, int64_t n,
-                   void* d_planes, hipStream_t st);
-int pointsource_init_emit_dev(const kr_pointsource* s, void* d, int64_t n, int64_t first, int64_t stride, double V, int reverse, int projradius, hipStream_t st);
-int reduce_image_dev(const kr_image_bins* b, const void* d, int64_t n, void* d_planes, hipStream_t st);
-int reduce_return_dev(const kr_return_bins* b, const void* d, int64_t n, void* d_out4, hipStream_t st);
-int post_return_dev(double lo, double hi, const kr_return_bins* b, void* d, int64_t n, void* d_out4, hipStream_t st);
-int post_return_batch_dev(int count, double lo, double hi, const kr_return_bins* b, void* const* d, const int64_t* n, void* const* d_out4, hipStream_t st);
-int pointsource_init_emit_batch_dev(int count, const kr_pointsource* s, const double* V, int reverse, int projradius, void* const* d, const int64_t* n, hipStream_t st);
-int arith_probe_dev(int op, const double* a, const double* b, double* out, int64_t n);
-// implemented in kr_line.hip
-int line_validate(const kr_line_bins* b, const char* who);
-int reduce_line_dev(const kr_line_bins* b, const void* d, int64_t n, void* d_line, hipStream_t st);
-int post_line_dev(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_line_bins* b, void* d, int64_t n,
-                  void* d_line, hipStream_t st);
-int line_from_image_dev(const kr_line_bins* b, const kr_image_bins* ib, const void* d_planes, void* d_line, hipStream_t st);
-// implemented in kr_caustic.hip
-int caustic_validate(const kr_caustic_map* m, const char* who);
-int bundles_init_emit_dev(const kr_imageplane* s, int nx, int ny, double eps_frac, double V, int reverse, int projradius, void* d, int64_t n, hipStream_t st);
-int post_caustic_dev(double spin, int reverse, const kr_caustic_map* m, void* d, int64_t n, void* d_maps, hipStream_t st);
-int caustic_suppress_dev(const kr_caustic_map* m, void* d_maps, hipStream_t st);
 
 static thread_local std::string g_error;
 
@@ -162,6 +127,8 @@ void device_tables_shutdown()
 
 namespace {
 
+int invalid(const char* what) { set_error(what); return KR_EINVAL; }
+
 using clk = std::chrono::steady_clock;
 double ms_since(clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); }
 
@@ -186,9 +153,9 @@ struct Attached {
 std::mutex g_att_mu;
 std::map<const void*, Attached> g_attached;
 
-__global__ void __launch_bounds__(256) gather_field_kernel(const char* __restrict__ rays, long long n, int ray_bytes, int off, int words, double* __restrict__ out)
+__global__ void __launch_bounds__(kBlock) gather_field_kernel(const char* __restrict__ rays, long long n, int ray_bytes, int off, int words, double* __restrict__ out)
 {
-    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long) gridDim.x * 256) {
+    KR_GRID_STRIDE(i, n) {
         const double* src = reinterpret_cast<const double*>(rays + i * ray_bytes + off);
         for (int w = 0; w < words; w++) out[i * words + w] = src[w];
     }
@@ -214,29 +181,47 @@ struct WriteBack {
 };
 constexpr WriteBack kWholeRecord = {0, 0};
 
+// what a host-pointer call moves: the records up before its kernels run, and which part of them back afterwards
+struct Staging {
+    bool copy_in, copy_out;
+    WriteBack wb;
+};
+constexpr Staging kConstructs = {false, true, kWholeRecord};      // a source constructor: nothing to upload, every record comes back
+constexpr Staging kUpdates = {true, true, kWholeRecord};          // a pass over existing records
+constexpr Staging kReads = {true, false, kWholeRecord};           // a reducer: its result leaves by another way
+constexpr Staging updates_field(int off, int words) { return {true, true, {off, words}}; }
+
+// the attached array that holds rays[0 .. n), as a whole or as a sub-range (the single-ray propagate() forms pass &rays[i]); .dev is null if none does
+Attached find_attached(const void* rays, int64_t n, size_t ray_bytes)
+{
+    std::lock_guard<std::mutex> lk(g_att_mu);
+    auto it = g_attached.upper_bound(rays);
+    if (it == g_attached.begin()) return Attached{};
+    const Attached& a = (--it)->second;
+    const char* base = (const char*) a.host;
+    const char* p = (const char*) rays;
+    const bool holds = a.ray_bytes == ray_bytes && p >= base && p + (size_t) n * ray_bytes <= base + (size_t) a.n * ray_bytes && (size_t) (p - base) % ray_bytes == 0;
+    return holds ? a : Attached{};
+}
+
+void release_buffers(const Attached& a)
+{
+    if (a.dev) (void) hipFree(a.dev);
+    if (a.d_field) (void) hipFree(a.d_field);
+    std::free(a.h_field);
+}
+
 // run `body(d_rays)` on a device copy of a host ray array and copy the result back
 template <typename Body>
-int with_staged_rays(void* rays, int64_t n, size_t ray_bytes, bool copy_in, bool copy_out, kr_stats* stats, Body body, WriteBack wb = kWholeRecord)
+int with_staged_rays(void* rays, int64_t n, size_t ray_bytes, Staging how, kr_stats* stats, Body body)
 {
-    if (n < 0 || (n > 0 && !rays)) { set_error("null rays pointer or negative n"); return KR_EINVAL; }
+    if (n < 0 || (n > 0 && !rays)) return invalid("null rays pointer or negative n");
     int rc = require_device();
     if (rc != KR_OK) return rc;
     if (n == 0) return body(nullptr);
     static const bool timing = getenv("KR_TIMING") != nullptr;      // per-call breakdown on stderr (scripts/app_wall.sh)
-    Attached att;
-    {
-        std::lock_guard<std::mutex> lk(g_att_mu);
-        // an attached array, or a sub-range of one (the single-ray propagate() forms pass &rays[i])
-        auto it = g_attached.upper_bound(rays);
-        if (it != g_attached.begin()) {
-            --it;
-            const char* base = (const char*) it->second.host;
-            const char* p = (const char*) rays;
-            if (it->second.ray_bytes == ray_bytes && p >= base && p + (size_t) n * ray_bytes <= base + (size_t) it->second.n * ray_bytes &&
-                (size_t) (p - base) % ray_bytes == 0)
-                att = it->second;
-        }
-    }
+    const Attached att = find_attached(rays, n, ray_bytes);
+    const WriteBack wb = how.wb;
     auto t0 = clk::now();
     DeviceBuffer buf;
     char* d = nullptr;
@@ -249,7 +234,7 @@ int with_staged_rays(void* rays, int64_t n, size_t ray_bytes, bool copy_in, bool
     }
     const double t_alloc = ms_since(t0);
     t0 = clk::now();
-    if (copy_in) KR_HIP(hipMemcpy(d, rays, (size_t) n * ray_bytes, hipMemcpyHostToDevice));
+    if (how.copy_in) KR_HIP(hipMemcpy(d, rays, (size_t) n * ray_bytes, hipMemcpyHostToDevice));
     const double h2d = ms_since(t0);
     t0 = clk::now();
     rc = body((void*) d);
@@ -257,9 +242,9 @@ int with_staged_rays(void* rays, int64_t n, size_t ray_bytes, bool copy_in, bool
     KR_HIP(hipDeviceSynchronize());
     const double t_body = ms_since(t0);
     t0 = clk::now();
-    if (copy_out) {
+    if (how.copy_out) {
         if (att.dev && wb.words > 0 && wb.words <= 4 && n >= 4096) {
-            hipLaunchKernelGGL(gather_field_kernel, dim3((unsigned) std::min<int64_t>((n + 255) / 256, 65536)), dim3(256), 0, nullptr, (const char*) d, (long long) n,
+            hipLaunchKernelGGL(gather_field_kernel, dim3(grid_for(n, kBlock, 65536)), dim3(kBlock), 0, nullptr, (const char*) d, (long long) n,
                                (int) ray_bytes, wb.off, wb.words, (double*) att.d_field);
             KR_HIP(hipGetLastError());
             KR_HIP(hipMemcpy(att.h_field, att.d_field, (size_t) n * wb.words * 8, hipMemcpyDeviceToHost));
@@ -273,6 +258,80 @@ int with_staged_rays(void* rays, int64_t n, size_t ray_bytes, bool copy_in, bool
     if (timing) std::fprintf(stderr, "kr_timing: staged call n=%lld%s alloc %.1f ms h2d %.1f ms kernels %.1f ms d2h %.1f ms%s\n", (long long) n, att.dev ? " (attached)" : "",
                              t_alloc, h2d, t_body, d2h, (att.dev && wb.words > 0) ? " (one field)" : "");
     return KR_OK;
+}
+
+// the shape of a device-pointer entry point: its argument check (ok, or `what` is the error), then a device, then the launcher
+template <typename Launch>
+int on_device(bool ok, const char* what, Launch launch)
+{
+    if (!ok) return invalid(what);
+    const int rc = require_device();
+    return rc != KR_OK ? rc : launch();
+}
+
+// the shape of a host reducer: the rays staged, `words` zeroed doubles on the device, reduce(d_rays, d_acc) adds into them, they come back into h
+template <typename Reduce>
+int reduce_to_host(const kr_ray_f64* rays, int64_t n, size_t words, double* h, Reduce reduce)
+{
+    return with_staged_rays((void*) rays, n, sizeof(kr_ray_f64), kReads, nullptr, [&](void* d) {
+        DeviceBuffer acc;
+        int rc = acc.alloc(words * sizeof(double));
+        if (rc != KR_OK) return rc;
+        KR_HIP(hipMemset(acc.p, 0, words * sizeof(double)));
+        rc = reduce(d, acc.p);
+        if (rc != KR_OK) return rc;
+        KR_HIP(hipMemcpy(h, acc.p, words * sizeof(double), hipMemcpyDeviceToHost));
+        return (int) KR_OK;
+    });
+}
+
+// the counters of one trace into those of several: sums, and the LARGEST of the durations and of the longest rays (include/kr_trace.h, kr_trace_wait_many)
+void accumulate_stats(kr_stats* total, const kr_stats& st)
+{
+    total->rays_total += st.rays_total; total->rays_traced += st.rays_traced; total->steps_total += st.steps_total;
+    total->rk45_attempts += st.rk45_attempts; total->rk45_rejects += st.rk45_rejects; total->rays_strict_side += st.rays_strict_side;
+    total->rk45_stationary_steps += st.rk45_stationary_steps; total->rk45_extrapolated_steps += st.rk45_extrapolated_steps;
+    total->steps_strict_side += st.steps_strict_side; total->rk45_evaluated_strict_side += st.rk45_evaluated_strict_side;
+    total->kernel_ms = std::max(total->kernel_ms, st.kernel_ms);
+    total->strict_side_ms = std::max(total->strict_side_ms, st.strict_side_ms);
+    total->main_ms = std::max(total->main_ms, st.main_ms);
+    total->longest_ray_steps = std::max(total->longest_ray_steps, st.longest_ray_steps);
+    total->longest_ray_steps_strict_side = std::max(total->longest_ray_steps_strict_side, st.longest_ray_steps_strict_side);
+}
+
+
+// run_raytrace with show_progress != 0 (raytracer.cpp:84-85, :107-115): the same trace, and while it runs the calling thread polls the work
+// queue and reports every multiple of `every` rays it sees passed
+int trace_with_progress(const kr_params* p, void* d, int64_t n, bool f32, kr_stats* stats, int64_t every, kr_progress_fn fn, void* user)
+{
+    void* ticket = nullptr;
+    int rc = trace_async(p, d, n, nullptr, f32, &ticket);
+    if (rc != KR_OK) return rc;
+    int64_t shown = 0;
+    for (;;) {
+        int64_t started = 0;
+        int32_t fin = 1;
+        rc = trace_poll(ticket, &started, &fin);
+        if (rc != KR_OK) break;                       // (the trace itself is still waited for below)
+        if (fn && every > 0) {
+            const int64_t at = started / every * every;
+            if (at > shown) { shown = at; fn(at, n, user); }
+        }
+        if (fin) break;
+        std::this_thread::sleep_for(std::chrono::milliseconds(20));
+    }
+    const int rc2 = trace_wait(ticket, stats);
+    if (stats) stats->rays_total = n;
+    return rc != KR_OK ? rc : rc2;
+}
+
+// the four host-pointer traces: params checked, counters cleared, then the trace on the staged records
+template <typename Trace>
+int trace_host(const kr_params* p, void* rays, int64_t n, size_t ray_bytes, kr_stats* stats, Trace trace)
+{
+    if (!p) return invalid("kr_trace: null params");
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    return with_staged_rays(rays, n, ray_bytes, kUpdates, stats, trace);
 }
 
 }  // namespace
@@ -370,7 +429,7 @@ int64_t kr_pointsource_count(const kr_pointsource* s, int32_t* n_cosalpha, int32
 // What the device PointSource constructor reads instead of calling acos / sin / cos / tan itself (kr_post_device.hpp::SourceTables): host values.
 int kr_pointsource_tables(const kr_pointsource* s, double* alpha_sincos, double* beta_sincos, double* pos_sin_cos_tan)
 {
-    if (!s) { set_error("kr_pointsource_tables: null spec"); return KR_EINVAL; }
+    if (!s) return invalid("kr_pointsource_tables: null spec");
     int32_t nc = 0, nb = 0;
     kr_pointsource_count(s, &nc, &nb);
     if (alpha_sincos) angle_values(0, s->cosalpha0, s->dcosalpha, nc, alpha_sincos);
@@ -407,14 +466,12 @@ int kr_trace_dev_f32(const kr_params* p, void* d_rays, int64_t n, void* stream, 
 
 int kr_trace_async_f64(const kr_params* p, void* d_rays, int64_t n, void* stream, void** ticket)
 {
-    if (!ticket) { set_error("kr_trace_async: null ticket pointer"); return KR_EINVAL; }
-    return trace_async(p, d_rays, n, (hipStream_t) stream, false, ticket);
+    return ticket ? trace_async(p, d_rays, n, (hipStream_t) stream, false, ticket) : invalid("kr_trace_async: null ticket pointer");
 }
 
 int kr_trace_async_f32(const kr_params* p, void* d_rays, int64_t n, void* stream, void** ticket)
 {
-    if (!ticket) { set_error("kr_trace_async: null ticket pointer"); return KR_EINVAL; }
-    return trace_async(p, d_rays, n, (hipStream_t) stream, true, ticket);
+    return ticket ? trace_async(p, d_rays, n, (hipStream_t) stream, true, ticket) : invalid("kr_trace_async: null ticket pointer");
 }
 
 int kr_trace_batch_async_f64(int32_t count, const kr_params* const* p, void* const* d_rays, const int64_t* n, void* const* streams, void** tickets)
@@ -426,7 +483,7 @@ int kr_trace_wait(void* ticket, kr_stats* stats) { return trace_wait(ticket, sta
 
 int kr_trace_wait_many(int32_t count, void* const* tickets, kr_stats* per_ticket, kr_stats* total)
 {
-    if (count < 0 || (count > 0 && !tickets)) { set_error("kr_trace_wait_many: null argument"); return KR_EINVAL; }
+    if (count < 0 || (count > 0 && !tickets)) return invalid("kr_trace_wait_many: null argument");
     if (total) std::memset(total, 0, sizeof(*total));
     int first_rc = KR_OK;
     for (int32_t i = 0; i < count; i++) {
@@ -434,17 +491,7 @@ int kr_trace_wait_many(int32_t count, void* const* tickets, kr_stats* per_ticket
         const int rc = trace_wait(tickets[i], (per_ticket || total) ? &st : nullptr);
         if (rc != KR_OK) { if (first_rc == KR_OK) first_rc = rc; continue; }
         if (per_ticket) per_ticket[i] = st;
-        if (total) {
-            total->rays_total += st.rays_total; total->rays_traced += st.rays_traced; total->steps_total += st.steps_total;
-            total->rk45_attempts += st.rk45_attempts; total->rk45_rejects += st.rk45_rejects; total->rays_strict_side += st.rays_strict_side;
-            total->rk45_stationary_steps += st.rk45_stationary_steps; total->rk45_extrapolated_steps += st.rk45_extrapolated_steps;
-            total->steps_strict_side += st.steps_strict_side; total->rk45_evaluated_strict_side += st.rk45_evaluated_strict_side;
-            total->kernel_ms = std::max(total->kernel_ms, st.kernel_ms);
-            total->strict_side_ms = std::max(total->strict_side_ms, st.strict_side_ms);
-            total->main_ms = std::max(total->main_ms, st.main_ms);
-            total->longest_ray_steps = std::max(total->longest_ray_steps, st.longest_ray_steps);
-            total->longest_ray_steps_strict_side = std::max(total->longest_ray_steps_strict_side, st.longest_ray_steps_strict_side);
-        }
+        if (total) accumulate_stats(total, st);
     }
     return first_rc;
 }
@@ -457,58 +504,19 @@ int kr_trace_release(void* ticket)
 
 int kr_trace_f64(const kr_params* p, kr_ray_f64* rays, int64_t n, kr_stats* stats)
 {
-    if (!p) { set_error("kr_trace: null params"); return KR_EINVAL; }
-    if (stats) std::memset(stats, 0, sizeof(*stats));
-    return with_staged_rays(rays, n, sizeof(kr_ray_f64), true, true, stats,
-                            [&](void* d) { return trace_dev(p, d, n, nullptr, stats, false); });
+    return trace_host(p, rays, n, sizeof(kr_ray_f64), stats, [&](void* d) { return trace_dev(p, d, n, nullptr, stats, false); });
 }
-
 int kr_trace_f32(const kr_params* p, kr_ray_f32* rays, int64_t n, kr_stats* stats)
 {
-    if (!p) { set_error("kr_trace: null params"); return KR_EINVAL; }
-    if (stats) std::memset(stats, 0, sizeof(*stats));
-    return with_staged_rays(rays, n, sizeof(kr_ray_f32), true, true, stats,
-                            [&](void* d) { return trace_dev(p, d, n, nullptr, stats, true); });
+    return trace_host(p, rays, n, sizeof(kr_ray_f32), stats, [&](void* d) { return trace_dev(p, d, n, nullptr, stats, true); });
 }
-
-// run_raytrace with show_progress != 0 (raytracer.cpp:84-85, :107-115): the same trace, and while it runs the calling thread polls the work
-// queue and reports every multiple of `every` rays it sees passed
-namespace {
-int trace_with_progress(const kr_params* p, void* d, int64_t n, bool f32, kr_stats* stats, int64_t every, kr_progress_fn fn, void* user)
-{
-    void* ticket = nullptr;
-    int rc = trace_async(p, d, n, nullptr, f32, &ticket);
-    if (rc != KR_OK) return rc;
-    int64_t shown = 0;
-    for (;;) {
-        int64_t started = 0;
-        int32_t fin = 1;
-        rc = trace_poll(ticket, &started, &fin);
-        if (rc != KR_OK) break;                       // (the trace itself is still waited for below)
-        if (fn && every > 0) {
-            const int64_t at = started / every * every;
-            if (at > shown) { shown = at; fn(at, n, user); }
-        }
-        if (fin) break;
-        std::this_thread::sleep_for(std::chrono::milliseconds(20));
-    }
-    const int rc2 = trace_wait(ticket, stats);
-    if (stats) stats->rays_total = n;
-    return rc != KR_OK ? rc : rc2;
-}
-}  // namespace
-
 int kr_trace_progress_f64(const kr_params* p, kr_ray_f64* rays, int64_t n, kr_stats* stats, int64_t every, kr_progress_fn fn, void* user)
 {
-    if (!p) { set_error("kr_trace: null params"); return KR_EINVAL; }
-    if (stats) std::memset(stats, 0, sizeof(*stats));
-    return with_staged_rays(rays, n, sizeof(kr_ray_f64), true, true, stats, [&](void* d) { return trace_with_progress(p, d, n, false, stats, every, fn, user); });
+    return trace_host(p, rays, n, sizeof(kr_ray_f64), stats, [&](void* d) { return trace_with_progress(p, d, n, false, stats, every, fn, user); });
 }
 int kr_trace_progress_f32(const kr_params* p, kr_ray_f32* rays, int64_t n, kr_stats* stats, int64_t every, kr_progress_fn fn, void* user)
 {
-    if (!p) { set_error("kr_trace: null params"); return KR_EINVAL; }
-    if (stats) std::memset(stats, 0, sizeof(*stats));
-    return with_staged_rays(rays, n, sizeof(kr_ray_f32), true, true, stats, [&](void* d) { return trace_with_progress(p, d, n, true, stats, every, fn, user); });
+    return trace_host(p, rays, n, sizeof(kr_ray_f32), stats, [&](void* d) { return trace_with_progress(p, d, n, true, stats, every, fn, user); });
 }
 int kr_trace_poll(void* ticket, int64_t* rays_started, int32_t* finished)
 {
@@ -516,226 +524,114 @@ int kr_trace_poll(void* ticket, int64_t* rays_started, int32_t* finished)
 }
 
 // ---- O(N) passes -------------------------------------------------------------------------------------------
-int kr_redshift_start_dev_f64(double spin, double V, int reverse, int projradius, void* d, int64_t n, void* st)
-{
-    int rc = require_device();
-    return rc != KR_OK ? rc : redshift_start_dev(spin, V, reverse, projradius, d, n, (hipStream_t) st);
-}
-int kr_redshift_start_f64(double spin, double V, int reverse, int projradius, kr_ray_f64* rays, int64_t n)
-{
-    return with_staged_rays(rays, n, sizeof(kr_ray_f64), true, true, nullptr,
-                            [&](void* d) { return redshift_start_dev(spin, V, reverse, projradius, d, n, nullptr); }, WriteBack{offsetof(kr_ray_f64, emit), 1});
-}
+// One line per pass: its scalar arguments, and the field(s) of a kr_ray_f64 it writes.  Each becomes four entry points: device and host
+// pointers, for Raytracer<double> and for Raytracer<float> (kr_ray_f32 records, float arithmetic; the scalars are float values carried in
+// doubles).  The f64 host form copies back only the written field(s) of an attached array, the f32 host form the whole 84-byte record.
+#define KR_LIST(...) __VA_ARGS__
+#define KR_PASS_FORMS(name, T, f32, params, args, staging)                                                            \
+    int kr_##name##_dev_##T(KR_LIST params, void* d, int64_t n, void* st)                                             \
+    {                                                                                                                 \
+        return on_device(true, nullptr, [&] { return name##_dev(KR_LIST args, d, n, (hipStream_t) st, f32); });       \
+    }                                                                                                                 \
+    int kr_##name##_##T(KR_LIST params, kr_ray_##T* rays, int64_t n)                                                  \
+    {                                                                                                                 \
+        return with_staged_rays(rays, n, sizeof(kr_ray_##T), staging, nullptr,                                        \
+                                [&](void* d) { return name##_dev(KR_LIST args, d, n, nullptr, f32); });               \
+    }
+#define KR_PASS(name, params, args, field, words)                                                       \
+    KR_PASS_FORMS(name, f64, false, params, args, updates_field(offsetof(kr_ray_f64, field), words))    \
+    KR_PASS_FORMS(name, f32, true, params, args, kUpdates)
 
-int kr_redshift_dev_f64(double spin, double V, int reverse, int projradius, int motion, void* d, int64_t n, void* st)
-{
-    int rc = require_device();
-    return rc != KR_OK ? rc : redshift_dev(spin, V, reverse, projradius, motion, d, n, (hipStream_t) st);
-}
-int kr_redshift_f64(double spin, double V, int reverse, int projradius, int motion, kr_ray_f64* rays, int64_t n)
-{
-    return with_staged_rays(rays, n, sizeof(kr_ray_f64), true, true, nullptr,
-                            [&](void* d) { return redshift_dev(spin, V, reverse, projradius, motion, d, n, nullptr); }, WriteBack{offsetof(kr_ray_f64, redshift), 1});
-}
-
-int kr_redshift_dest_dev_f64(double spin, int reverse, void* d, int64_t n, void* st)
-{
-    int rc = require_device();
-    return rc != KR_OK ? rc : redshift_dest_dev(spin, reverse, d, n, (hipStream_t) st);
-}
-int kr_redshift_dest_f64(double spin, int reverse, kr_ray_f64* rays, int64_t n)
-{
-    return with_staged_rays(rays, n, sizeof(kr_ray_f64), true, true, nullptr,
-                            [&](void* d) { return redshift_dest_dev(spin, reverse, d, n, nullptr); }, WriteBack{offsetof(kr_ray_f64, redshift), 1});
-}
-
-int kr_range_phi_dev_f64(double lo, double hi, void* d, int64_t n, void* st)
-{
-    int rc = require_device();
-    return rc != KR_OK ? rc : range_phi_dev(lo, hi, d, n, (hipStream_t) st);
-}
-int kr_range_phi_f64(double lo, double hi, kr_ray_f64* rays, int64_t n)
-{
-    return with_staged_rays(rays, n, sizeof(kr_ray_f64), true, true, nullptr,
-                            [&](void* d) { return range_phi_dev(lo, hi, d, n, nullptr); }, WriteBack{offsetof(kr_ray_f64, phi), 1});
-}
-
-int kr_calculate_momentum_dev_f64(double spin, void* d, int64_t n, void* st)
-{
-    int rc = require_device();
-    return rc != KR_OK ? rc : calculate_momentum_dev(spin, d, n, (hipStream_t) st);
-}
-int kr_calculate_momentum_f64(double spin, kr_ray_f64* rays, int64_t n)
-{
-    return with_staged_rays(rays, n, sizeof(kr_ray_f64), true, true, nullptr,
-                            [&](void* d) { return calculate_momentum_dev(spin, d, n, nullptr); }, WriteBack{offsetof(kr_ray_f64, pt), 4});
-}
-
-// The same passes for Raytracer<float> (kr_ray_f32 records, float arithmetic; the scalars are float values carried in doubles).
-// Host-pointer forms copy the whole 84-byte record back.
-int kr_redshift_start_dev_f32(double spin, double V, int reverse, int projradius, void* d, int64_t n, void* st)
-{
-    int rc = require_device();
-    return rc != KR_OK ? rc : redshift_start_dev(spin, V, reverse, projradius, d, n, (hipStream_t) st, true);
-}
-int kr_redshift_start_f32(double spin, double V, int reverse, int projradius, kr_ray_f32* rays, int64_t n)
-{
-    return with_staged_rays(rays, n, sizeof(kr_ray_f32), true, true, nullptr,
-                            [&](void* d) { return redshift_start_dev(spin, V, reverse, projradius, d, n, nullptr, true); });
-}
-int kr_redshift_dev_f32(double spin, double V, int reverse, int projradius, int motion, void* d, int64_t n, void* st)
-{
-    int rc = require_device();
-    return rc != KR_OK ? rc : redshift_dev(spin, V, reverse, projradius, motion, d, n, (hipStream_t) st, true);
-}
-int kr_redshift_f32(double spin, double V, int reverse, int projradius, int motion, kr_ray_f32* rays, int64_t n)
-{
-    return with_staged_rays(rays, n, sizeof(kr_ray_f32), true, true, nullptr,
-                            [&](void* d) { return redshift_dev(spin, V, reverse, projradius, motion, d, n, nullptr, true); });
-}
-int kr_redshift_dest_dev_f32(double spin, int reverse, void* d, int64_t n, void* st)
-{
-    int rc = require_device();
-    return rc != KR_OK ? rc : redshift_dest_dev(spin, reverse, d, n, (hipStream_t) st, true);
-}
-int kr_redshift_dest_f32(double spin, int reverse, kr_ray_f32* rays, int64_t n)
-{
-    return with_staged_rays(rays, n, sizeof(kr_ray_f32), true, true, nullptr,
-                            [&](void* d) { return redshift_dest_dev(spin, reverse, d, n, nullptr, true); });
-}
-int kr_range_phi_dev_f32(double lo, double hi, void* d, int64_t n, void* st)
-{
-    int rc = require_device();
-    return rc != KR_OK ? rc : range_phi_dev(lo, hi, d, n, (hipStream_t) st, true);
-}
-int kr_range_phi_f32(double lo, double hi, kr_ray_f32* rays, int64_t n)
-{
-    return with_staged_rays(rays, n, sizeof(kr_ray_f32), true, true, nullptr,
-                            [&](void* d) { return range_phi_dev(lo, hi, d, n, nullptr, true); });
-}
-int kr_calculate_momentum_dev_f32(double spin, void* d, int64_t n, void* st)
-{
-    int rc = require_device();
-    return rc != KR_OK ? rc : calculate_momentum_dev(spin, d, n, (hipStream_t) st, true);
-}
-int kr_calculate_momentum_f32(double spin, kr_ray_f32* rays, int64_t n)
-{
-    return with_staged_rays(rays, n, sizeof(kr_ray_f32), true, true, nullptr,
-                            [&](void* d) { return calculate_momentum_dev(spin, d, n, nullptr, true); });
-}
+KR_PASS(redshift_start, (double spin, double V, int reverse, int projradius), (spin, V, reverse, projradius), emit, 1)
+KR_PASS(redshift, (double spin, double V, int reverse, int projradius, int motion), (spin, V, reverse, projradius, motion), redshift, 1)
+KR_PASS(redshift_dest, (double spin, int reverse), (spin, reverse), redshift, 1)
+KR_PASS(range_phi, (double lo, double hi), (lo, hi), phi, 1)
+KR_PASS(calculate_momentum, (double spin), (spin), pt, 4)
 
 // ---- sources -----------------------------------------------------------------------------------------------
 int kr_pointsource_init_dev_f64(const kr_pointsource* s, void* d, int64_t n, void* st)
 {
-    if (!s) { set_error("kr_pointsource_init: null spec"); return KR_EINVAL; }
-    int rc = require_device();
-    return rc != KR_OK ? rc : pointsource_init_dev(s, d, n, 0, 1, (hipStream_t) st);
+    return on_device(s, "kr_pointsource_init: null spec", [&] { return pointsource_init_dev(s, d, n, 0, 1, (hipStream_t) st); });
 }
 int kr_pointsource_init_f64(const kr_pointsource* s, kr_ray_f64* rays, int64_t n)
 {
-    if (!s) { set_error("kr_pointsource_init: null spec"); return KR_EINVAL; }
-    return with_staged_rays(rays, n, sizeof(kr_ray_f64), false, true, nullptr,
-                            [&](void* d) { return pointsource_init_dev(s, d, n, 0, 1, nullptr); });
+    if (!s) return invalid("kr_pointsource_init: null spec");
+    return with_staged_rays(rays, n, sizeof(kr_ray_f64), kConstructs, nullptr, [&](void* d) { return pointsource_init_dev(s, d, n, 0, 1, nullptr); });
 }
 
 int kr_imageplane_init_dev_f64(const kr_imageplane* s, void* d, int64_t n, void* st)
 {
-    if (!s) { set_error("kr_imageplane_init: null spec"); return KR_EINVAL; }
-    int rc = require_device();
-    return rc != KR_OK ? rc : imageplane_init_dev(s, d, n, 0, 1, (hipStream_t) st);
+    return on_device(s, "kr_imageplane_init: null spec", [&] { return imageplane_init_dev(s, d, n, 0, 1, (hipStream_t) st); });
 }
 int kr_imageplane_init_f64(const kr_imageplane* s, kr_ray_f64* rays, int64_t n)
 {
-    if (!s) { set_error("kr_imageplane_init: null spec"); return KR_EINVAL; }
-    return with_staged_rays(rays, n, sizeof(kr_ray_f64), false, true, nullptr,
-                            [&](void* d) { return imageplane_init_dev(s, d, n, 0, 1, nullptr); });
+    if (!s) return invalid("kr_imageplane_init: null spec");
+    return with_staged_rays(rays, n, sizeof(kr_ray_f64), kConstructs, nullptr, [&](void* d) { return imageplane_init_dev(s, d, n, 0, 1, nullptr); });
 }
 
 // strided forms: slot k of d_rays receives ray (first + k*stride) of the source's array -- the multi-GPU shard of rank r
 // of R is (first = r, stride = R, count = ceil((total - r) / R)); no rank ever materialises another rank's rays.
 int kr_pointsource_init_strided_dev_f64(const kr_pointsource* s, int64_t first, int64_t stride, void* d, int64_t count, void* st)
 {
-    if (!s) { set_error("kr_pointsource_init: null spec"); return KR_EINVAL; }
-    int rc = require_device();
-    return rc != KR_OK ? rc : pointsource_init_dev(s, d, count, first, stride, (hipStream_t) st);
+    return on_device(s, "kr_pointsource_init: null spec", [&] { return pointsource_init_dev(s, d, count, first, stride, (hipStream_t) st); });
+}
+int kr_imageplane_init_strided_dev_f64(const kr_imageplane* s, int64_t first, int64_t stride, void* d, int64_t count, void* st)
+{
+    return on_device(s, "kr_imageplane_init: null spec", [&] { return imageplane_init_dev(s, d, count, first, stride, (hipStream_t) st); });
 }
 // fused pipeline ends (device-resident callers): source constructor + redshift_start() in one pass ...
 int kr_pointsource_init_emit_dev_f64(const kr_pointsource* s, int64_t first, int64_t stride, double V, int reverse, int projradius, void* d, int64_t count, void* st)
 {
-    if (!s) { set_error("kr_pointsource_init_emit: null spec"); return KR_EINVAL; }
-    int rc = require_device();
-    return rc != KR_OK ? rc : pointsource_init_emit_dev(s, d, count, first, stride, V, reverse, projradius, (hipStream_t) st);
+    return on_device(s, "kr_pointsource_init_emit: null spec",
+                     [&] { return pointsource_init_emit_dev(s, d, count, first, stride, V, reverse, projradius, (hipStream_t) st); });
 }
 int kr_pointsource_init_emit_batch_dev_f64(int32_t count, const kr_pointsource* s, const double* V, int reverse, int projradius, void* const* d, const int64_t* n, void* st)
 {
-    if (count < 0 || (count > 0 && (!s || !d || !n))) { set_error("kr_pointsource_init_emit_batch: null argument"); return KR_EINVAL; }
+    if (count < 0 || (count > 0 && (!s || !d || !n))) return invalid("kr_pointsource_init_emit_batch: null argument");
     for (int32_t i = 0; i < count; i++)
-        if (n[i] > 0 && !d[i]) { set_error("kr_pointsource_init_emit_batch: null ray buffer"); return KR_EINVAL; }
-    int rc = require_device();
-    return rc != KR_OK ? rc : pointsource_init_emit_batch_dev(count, s, V, reverse, projradius, d, n, (hipStream_t) st);
-}
-// ... and range_phi() + redshift() + the emissivity histogram in one pass
-int kr_post_emissivity_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_emis_bins* b, void* d, int64_t n,
-                               void* d_hist, void* st)
-{
-    if (!b || !d_hist) { set_error("kr_post_emissivity: null argument"); return KR_EINVAL; }
-    int rc = require_device();
-    return rc != KR_OK ? rc : post_emissivity_dev(spin, V, reverse, projradius, motion, lo, hi, b, d, n, d_hist, (hipStream_t) st);
+        if (n[i] > 0 && !d[i]) return invalid("kr_pointsource_init_emit_batch: null ray buffer");
+    return on_device(true, nullptr, [&] { return pointsource_init_emit_batch_dev(count, s, V, reverse, projradius, d, n, (hipStream_t) st); });
 }
 int kr_imageplane_init_emit_dev_f64(const kr_imageplane* s, int64_t first, int64_t stride, double V, int reverse, int projradius, void* d, int64_t count, void* st)
 {
-    if (!s) { set_error("kr_imageplane_init_emit: null spec"); return KR_EINVAL; }
-    int rc = require_device();
-    return rc != KR_OK ? rc : imageplane_init_emit_dev(s, d, count, first, stride, 1, -1 * s->spin, V, reverse, projradius, (hipStream_t) st);
+    return on_device(s, "kr_imageplane_init_emit: null spec",
+                     [&] { return imageplane_init_emit_dev(s, d, count, first, stride, 1, -1 * s->spin, V, reverse, projradius, (hipStream_t) st); });
 }
 int kr_imageplane_init_emit_runs_dev_f64(const kr_imageplane* s, int64_t first, int64_t stride, int64_t run, double V, int reverse, int projradius, void* d,
                                          int64_t count, void* st)
 {
-    if (!s) { set_error("kr_imageplane_init_emit_runs: null spec"); return KR_EINVAL; }
-    int rc = require_device();
-    return rc != KR_OK ? rc : imageplane_init_emit_dev(s, d, count, first, stride, run, -1 * s->spin, V, reverse, projradius, (hipStream_t) st);
+    return on_device(s, "kr_imageplane_init_emit_runs: null spec",
+                     [&] { return imageplane_init_emit_dev(s, d, count, first, stride, run, -1 * s->spin, V, reverse, projradius, (hipStream_t) st); });
+}
+// ... and range_phi() + redshift() + the emissivity histogram / the seven image planes in one pass
+int kr_post_emissivity_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_emis_bins* b, void* d, int64_t n,
+                               void* d_hist, void* st)
+{
+    return on_device(b && d_hist, "kr_post_emissivity: null argument",
+                     [&] { return post_emissivity_dev(spin, V, reverse, projradius, motion, lo, hi, b, d, n, d_hist, (hipStream_t) st); });
 }
 int kr_post_image_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_image_bins* b, void* d, int64_t n,
                           void* d_planes, void* st)
 {
-    if (!b || !d_planes) { set_error("kr_post_image: null argument"); return KR_EINVAL; }
-    int rc = require_device();
-    return rc != KR_OK ? rc : post_image_dev(spin, V, reverse, projradius, motion, lo, hi, b, d, n, d_planes, (hipStream_t) st);
-}
-int kr_imageplane_init_strided_dev_f64(const kr_imageplane* s, int64_t first, int64_t stride, void* d, int64_t count, void* st)
-{
-    if (!s) { set_error("kr_imageplane_init: null spec"); return KR_EINVAL; }
-    int rc = require_device();
-    return rc != KR_OK ? rc : imageplane_init_dev(s, d, count, first, stride, (hipStream_t) st);
+    return on_device(b && d_planes, "kr_post_image: null argument",
+                     [&] { return post_image_dev(spin, V, reverse, projradius, motion, lo, hi, b, d, n, d_planes, (hipStream_t) st); });
 }
 
 // ---- reducers ------------------------------------------------------------------------------------------------
 int kr_reduce_emissivity_dev_f64(const kr_emis_bins* b, const void* d, int64_t n, void* d_hist, void* st)
 {
-    if (!b || !d_hist) { set_error("kr_reduce_emissivity: null argument"); return KR_EINVAL; }
-    int rc = require_device();
-    return rc != KR_OK ? rc : reduce_emissivity_dev(b, d, n, d_hist, (hipStream_t) st);
+    return on_device(b && d_hist, "kr_reduce_emissivity: null argument", [&] { return reduce_emissivity_dev(b, d, n, d_hist, (hipStream_t) st); });
 }
 
 int kr_reduce_emissivity_f64(const kr_emis_bins* b, const kr_ray_f64* rays, int64_t n, int64_t* count, double* flux,
                              double* emis, double* sum_redshift, double* sum_time, int64_t* disc_count)
 {
-    if (!b || !count || !flux || !emis || !sum_redshift || !sum_time) { set_error("kr_reduce_emissivity: null argument"); return KR_EINVAL; }
-    if (b->nr <= 0) { set_error("kr_reduce_emissivity: nr must be positive"); return KR_EINVAL; }
-    const size_t words = (size_t) 5 * b->nr + 1;
-    std::vector<double> h(words, 0.0);
-    int rc = with_staged_rays((void*) rays, n, sizeof(kr_ray_f64), true, false, nullptr, [&](void* d) {
-        DeviceBuffer hist;
-        int r2 = hist.alloc(words * sizeof(double));
-        if (r2 != KR_OK) return r2;
-        KR_HIP(hipMemset(hist.p, 0, words * sizeof(double)));
-        r2 = reduce_emissivity_dev(b, d, n, hist.p, nullptr);
-        if (r2 != KR_OK) return r2;
-        KR_HIP(hipMemcpy(h.data(), hist.p, words * sizeof(double), hipMemcpyDeviceToHost));
-        return (int) KR_OK;
-    });
-    if (rc != KR_OK) return rc;
+    if (!b || !count || !flux || !emis || !sum_redshift || !sum_time) return invalid("kr_reduce_emissivity: null argument");
+    if (b->nr <= 0) return invalid("kr_reduce_emissivity: nr must be positive");
     const int nr = b->nr;
+    std::vector<double> h((size_t) 5 * nr + 1, 0.0);
+    const int rc = reduce_to_host(rays, n, h.size(), h.data(), [&](void* d, void* d_hist) { return reduce_emissivity_dev(b, d, n, d_hist, nullptr); });
+    if (rc != KR_OK) return rc;
     for (int i = 0; i < nr; i++) {
         count[i] = (int64_t) h[i];
         flux[i] = h[nr + i];
@@ -749,169 +645,118 @@ int kr_reduce_emissivity_f64(const kr_emis_bins* b, const kr_ray_f64* rays, int6
 
 int kr_reduce_image_dev_f64(const kr_image_bins* b, const void* d, int64_t n, void* d_planes, void* st)
 {
-    if (!b || !d_planes) { set_error("kr_reduce_image: null argument"); return KR_EINVAL; }
-    int rc = require_device();
-    return rc != KR_OK ? rc : reduce_image_dev(b, d, n, d_planes, (hipStream_t) st);
+    return on_device(b && d_planes, "kr_reduce_image: null argument", [&] { return reduce_image_dev(b, d, n, d_planes, (hipStream_t) st); });
 }
 
 int kr_reduce_image_f64(const kr_image_bins* b, const kr_ray_f64* rays, int64_t n, int32_t* nrays, double* flux, double* r,
                         double* phi, double* enshift, double* time, double* emis, int64_t* disc_count)
 {
-    if (!b || !nrays || !flux || !r || !phi || !enshift || !time || !emis) { set_error("kr_reduce_image: null argument"); return KR_EINVAL; }
-    if (b->img_nx <= 0 || b->img_ny <= 0) { set_error("kr_reduce_image: image size must be positive"); return KR_EINVAL; }
+    if (!b || !nrays || !flux || !r || !phi || !enshift || !time || !emis) return invalid("kr_reduce_image: null argument");
+    if (b->img_nx <= 0 || b->img_ny <= 0) return invalid("kr_reduce_image: image size must be positive");
     const size_t npix = (size_t) b->img_nx * b->img_ny;
-    const size_t words = 7 * npix + 1;
-    std::vector<double> h(words, 0.0);
-    int rc = with_staged_rays((void*) rays, n, sizeof(kr_ray_f64), true, false, nullptr, [&](void* d) {
-        DeviceBuffer planes;
-        int r2 = planes.alloc(words * sizeof(double));
-        if (r2 != KR_OK) return r2;
-        KR_HIP(hipMemset(planes.p, 0, words * sizeof(double)));
-        r2 = reduce_image_dev(b, d, n, planes.p, nullptr);
-        if (r2 != KR_OK) return r2;
-        KR_HIP(hipMemcpy(h.data(), planes.p, words * sizeof(double), hipMemcpyDeviceToHost));
-        return (int) KR_OK;
-    });
+    std::vector<double> h(7 * npix + 1, 0.0);
+    const int rc = reduce_to_host(rays, n, h.size(), h.data(), [&](void* d, void* d_planes) { return reduce_image_dev(b, d, n, d_planes, nullptr); });
     if (rc != KR_OK) return rc;
     for (size_t i = 0; i < npix; i++) nrays[i] = (int32_t) h[i];
-    std::memcpy(flux, &h[npix], npix * sizeof(double));
-    std::memcpy(r, &h[2 * npix], npix * sizeof(double));
-    std::memcpy(phi, &h[3 * npix], npix * sizeof(double));
-    std::memcpy(enshift, &h[4 * npix], npix * sizeof(double));
-    std::memcpy(time, &h[5 * npix], npix * sizeof(double));
-    std::memcpy(emis, &h[6 * npix], npix * sizeof(double));
+    double* const planes[] = {flux, r, phi, enshift, time, emis};
+    for (size_t k = 0; k < 6; k++) std::memcpy(planes[k], &h[(k + 1) * npix], npix * sizeof(double));
     if (disc_count) *disc_count = (int64_t) h[7 * npix];
     return KR_OK;
+}
+
+int kr_reduce_return_dev_f64(const kr_return_bins* b, const void* d, int64_t n, void* d_out4, void* st)
+{
+    return on_device(b && d_out4, "kr_reduce_return: null argument", [&] { return reduce_return_dev(b, d, n, d_out4, (hipStream_t) st); });
+}
+
+int kr_post_return_dev_f64(double lo, double hi, const kr_return_bins* b, void* d, int64_t n, void* d_out4, void* st)
+{
+    return on_device(b && d_out4, "kr_post_return: null argument", [&] { return post_return_dev(lo, hi, b, d, n, d_out4, (hipStream_t) st); });
+}
+
+int kr_post_return_batch_dev_f64(int32_t count, double lo, double hi, const kr_return_bins* b, void* const* d, const int64_t* n, void* const* d_out4, void* st)
+{
+    if (count < 0 || (count > 0 && (!b || !d || !n || !d_out4))) return invalid("kr_post_return_batch: null argument");
+    for (int32_t i = 0; i < count; i++)
+        if (n[i] > 0 && (!d[i] || !d_out4[i])) return invalid("kr_post_return_batch: null buffer");
+    return on_device(true, nullptr, [&] { return post_return_batch_dev(count, lo, hi, b, d, n, d_out4, (hipStream_t) st); });
+}
+
+int kr_reduce_return_f64(const kr_return_bins* b, const kr_ray_f64* rays, int64_t n, double out[4])
+{
+    if (!b || !out) return invalid("kr_reduce_return: null argument");
+    return reduce_to_host(rays, n, 4, out, [&](void* d, void* d_out4) { return reduce_return_dev(b, d, n, d_out4, nullptr); });
 }
 
 // ---- emission line (kr_line.hip): the bins are validated before anything touches a device ----------------------------------
 int kr_reduce_line_dev_f64(const kr_line_bins* b, const void* d, int64_t n, void* d_line, void* st)
 {
-    int rc = line_validate(b, "kr_reduce_line");
+    const int rc = line_validate(b, "kr_reduce_line");
     if (rc != KR_OK) return rc;
-    if (!d_line || (n > 0 && !d)) { set_error("kr_reduce_line: null argument"); return KR_EINVAL; }
-    rc = require_device();
-    return rc != KR_OK ? rc : reduce_line_dev(b, d, n, d_line, (hipStream_t) st);
+    return on_device(d_line && (n <= 0 || d), "kr_reduce_line: null argument", [&] { return reduce_line_dev(b, d, n, d_line, (hipStream_t) st); });
 }
 
 int kr_post_line_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_line_bins* b, void* d, int64_t n,
                          void* d_line, void* st)
 {
-    int rc = line_validate(b, "kr_post_line");
+    const int rc = line_validate(b, "kr_post_line");
     if (rc != KR_OK) return rc;
-    if (!d_line || (n > 0 && !d)) { set_error("kr_post_line: null argument"); return KR_EINVAL; }
-    rc = require_device();
-    return rc != KR_OK ? rc : post_line_dev(spin, V, reverse, projradius, motion, lo, hi, b, d, n, d_line, (hipStream_t) st);
+    return on_device(d_line && (n <= 0 || d), "kr_post_line: null argument",
+                     [&] { return post_line_dev(spin, V, reverse, projradius, motion, lo, hi, b, d, n, d_line, (hipStream_t) st); });
 }
 
 int kr_line_from_image_dev_f64(const kr_line_bins* b, const kr_image_bins* ib, const void* d_planes, void* d_line, void* st)
 {
-    int rc = line_validate(b, "kr_line_from_image");
+    const int rc = line_validate(b, "kr_line_from_image");
     if (rc != KR_OK) return rc;
-    if (!ib || !d_planes || !d_line) { set_error("kr_line_from_image: null argument"); return KR_EINVAL; }
-    if (ib->img_nx <= 0 || ib->img_ny <= 0) { set_error("kr_line_from_image: image size must be positive"); return KR_EINVAL; }
-    rc = require_device();
-    return rc != KR_OK ? rc : line_from_image_dev(b, ib, d_planes, d_line, (hipStream_t) st);
+    if (!ib || !d_planes || !d_line) return invalid("kr_line_from_image: null argument");
+    return on_device(ib->img_nx > 0 && ib->img_ny > 0, "kr_line_from_image: image size must be positive",
+                     [&] { return line_from_image_dev(b, ib, d_planes, d_line, (hipStream_t) st); });
 }
 
 int kr_reduce_line_f64(const kr_line_bins* b, const kr_ray_f64* rays, int64_t n, double* out)
 {
-    int rc = line_validate(b, "kr_reduce_line");
+    const int rc = line_validate(b, "kr_reduce_line");
     if (rc != KR_OK) return rc;
-    if (!out || (n > 0 && !rays)) { set_error("kr_reduce_line: null argument"); return KR_EINVAL; }
-    const size_t words = (size_t) 2 * b->nt * b->ne + 2;
-    std::vector<double> h(words, 0.0);
-    rc = with_staged_rays((void*) rays, n, sizeof(kr_ray_f64), true, false, nullptr, [&](void* d) {
-        DeviceBuffer line;
-        int r2 = line.alloc(words * sizeof(double));
-        if (r2 != KR_OK) return r2;
-        KR_HIP(hipMemset(line.p, 0, words * sizeof(double)));
-        r2 = reduce_line_dev(b, d, n, line.p, nullptr);
-        if (r2 != KR_OK) return r2;
-        KR_HIP(hipMemcpy(h.data(), line.p, words * sizeof(double), hipMemcpyDeviceToHost));
-        return (int) KR_OK;
-    });
-    if (rc != KR_OK) return rc;
-    std::memcpy(out, h.data(), words * sizeof(double));
-    return KR_OK;
+    if (!out || (n > 0 && !rays)) return invalid("kr_reduce_line: null argument");
+    std::vector<double> h((size_t) 2 * b->nt * b->ne + 2, 0.0);        // out is written only by a call that succeeds
+    const int rc2 = reduce_to_host(rays, n, h.size(), h.data(), [&](void* d, void* d_line) { return reduce_line_dev(b, d, n, d_line, nullptr); });
+    if (rc2 == KR_OK) std::memcpy(out, h.data(), h.size() * sizeof(double));
+    return rc2;
 }
 
 // ---- critical-curve maps (kr_caustic.hip): everything is validated before anything touches a device --------------------------------------
 int kr_bundles_init_emit_dev_f64(const kr_imageplane* s, double eps_frac, double V, int reverse, int projradius, void* d, int64_t n, void* st)
 {
-    auto bad = [](const char* why) { set_error(std::string("kr_bundles_init_emit: ") + why); return KR_EINVAL; };
-    if (!s) return bad("null spec");
-    if (!std::isfinite(eps_frac) || !(eps_frac > 0) || !(eps_frac < 0.5)) return bad("eps_frac must lie in (0, 0.5)");
+    if (!s) return invalid("kr_bundles_init_emit: null spec");
+    if (!std::isfinite(eps_frac) || !(eps_frac > 0) || !(eps_frac < 0.5)) return invalid("kr_bundles_init_emit: eps_frac must lie in (0, 0.5)");
     int32_t nx = 0, ny = 0;
     kr_imageplane_count(s, &nx, &ny);
-    if (nx < 1 || ny < 1) return bad("empty ray grid (nx and ny must be >= 1)");
-    if (n < 5 * (int64_t) nx * ny) return bad("n smaller than 5 nx ny");
-    if (!d) return bad("null ray buffer");
-    int rc = require_device();
-    return rc != KR_OK ? rc : bundles_init_emit_dev(s, nx, ny, eps_frac, V, reverse, projradius, d, n, (hipStream_t) st);
+    if (nx < 1 || ny < 1) return invalid("kr_bundles_init_emit: empty ray grid (nx and ny must be >= 1)");
+    if (n < 5 * (int64_t) nx * ny) return invalid("kr_bundles_init_emit: n smaller than 5 nx ny");
+    return on_device(d, "kr_bundles_init_emit: null ray buffer",
+                     [&] { return bundles_init_emit_dev(s, nx, ny, eps_frac, V, reverse, projradius, d, n, (hipStream_t) st); });
 }
 
 int kr_post_caustic_disc_dev_f64(double spin, int reverse, const kr_caustic_map* m, void* d, int64_t n, void* d_maps, void* st)
 {
-    int rc = caustic_validate(m, "kr_post_caustic_disc");
+    const int rc = caustic_validate(m, "kr_post_caustic_disc");
     if (rc != KR_OK) return rc;
-    if (n < (m->bundles ? 5 : 1) * (int64_t) m->nx * m->ny) { set_error(m->bundles ? "kr_post_caustic_disc: n smaller than 5 nx ny" : "kr_post_caustic_disc: n smaller than nx ny"); return KR_EINVAL; }
-    if (!d || !d_maps) { set_error("kr_post_caustic_disc: null argument"); return KR_EINVAL; }
-    rc = require_device();
-    return rc != KR_OK ? rc : post_caustic_dev(spin, reverse, m, d, n, d_maps, (hipStream_t) st);
+    if (n < (m->bundles ? 5 : 1) * (int64_t) m->nx * m->ny) return invalid(m->bundles ? "kr_post_caustic_disc: n smaller than 5 nx ny" : "kr_post_caustic_disc: n smaller than nx ny");
+    return on_device(d && d_maps, "kr_post_caustic_disc: null argument", [&] { return post_caustic_dev(spin, reverse, m, d, n, d_maps, (hipStream_t) st); });
 }
 
 int kr_caustic_suppress_dev_f64(const kr_caustic_map* m, void* d_maps, void* st)
 {
-    int rc = caustic_validate(m, "kr_caustic_suppress");
+    const int rc = caustic_validate(m, "kr_caustic_suppress");
     if (rc != KR_OK) return rc;
-    if (!d_maps) { set_error("kr_caustic_suppress: null argument"); return KR_EINVAL; }
-    rc = require_device();
-    return rc != KR_OK ? rc : caustic_suppress_dev(m, d_maps, (hipStream_t) st);
-}
-
-int kr_reduce_return_dev_f64(const kr_return_bins* b, const void* d, int64_t n, void* d_out4, void* st)
-{
-    if (!b || !d_out4) { set_error("kr_reduce_return: null argument"); return KR_EINVAL; }
-    int rc = require_device();
-    return rc != KR_OK ? rc : reduce_return_dev(b, d, n, d_out4, (hipStream_t) st);
-}
-
-int kr_post_return_dev_f64(double lo, double hi, const kr_return_bins* b, void* d, int64_t n, void* d_out4, void* st)
-{
-    if (!b || !d_out4) { set_error("kr_post_return: null argument"); return KR_EINVAL; }
-    int rc = require_device();
-    return rc != KR_OK ? rc : post_return_dev(lo, hi, b, d, n, d_out4, (hipStream_t) st);
-}
-
-int kr_post_return_batch_dev_f64(int32_t count, double lo, double hi, const kr_return_bins* b, void* const* d, const int64_t* n, void* const* d_out4, void* st)
-{
-    if (count < 0 || (count > 0 && (!b || !d || !n || !d_out4))) { set_error("kr_post_return_batch: null argument"); return KR_EINVAL; }
-    for (int32_t i = 0; i < count; i++)
-        if (n[i] > 0 && (!d[i] || !d_out4[i])) { set_error("kr_post_return_batch: null buffer"); return KR_EINVAL; }
-    int rc = require_device();
-    return rc != KR_OK ? rc : post_return_batch_dev(count, lo, hi, b, d, n, d_out4, (hipStream_t) st);
-}
-
-int kr_reduce_return_f64(const kr_return_bins* b, const kr_ray_f64* rays, int64_t n, double out[4])
-{
-    if (!b || !out) { set_error("kr_reduce_return: null argument"); return KR_EINVAL; }
-    return with_staged_rays((void*) rays, n, sizeof(kr_ray_f64), true, false, nullptr, [&](void* d) {
-        DeviceBuffer acc;
-        int r2 = acc.alloc(4 * sizeof(double));
-        if (r2 != KR_OK) return r2;
-        KR_HIP(hipMemset(acc.p, 0, 4 * sizeof(double)));
-        r2 = reduce_return_dev(b, d, n, acc.p, nullptr);
-        if (r2 != KR_OK) return r2;
-        KR_HIP(hipMemcpy(out, acc.p, 4 * sizeof(double), hipMemcpyDeviceToHost));
-        return (int) KR_OK;
-    });
+    return on_device(d_maps, "kr_caustic_suppress: null argument", [&] { return caustic_suppress_dev(m, d_maps, (hipStream_t) st); });
 }
 
 // ---- diagnostics ---------------------------------------------------------------------------------------------
 int kr_debug_arith_f64(int op, const double* a, const double* b, double* out, int64_t n)
 {
-    if (!a || !b || !out || n < 0) { set_error("kr_debug_arith: bad argument"); return KR_EINVAL; }
+    if (!a || !b || !out || n < 0) return invalid("kr_debug_arith: bad argument");
     int rc = require_device();
     if (rc != KR_OK) return rc;
     if (n == 0) return KR_OK;
@@ -929,20 +774,19 @@ int kr_debug_arith_f64(int op, const double* a, const double* b, double* out, in
 // ---- attached host arrays (see with_staged_rays) --------------------------------------------------------------------------
 int kr_host_attach(void* rays, int64_t n, int32_t ray_bytes)
 {
-    if (!rays || n <= 0 || (ray_bytes != (int32_t) sizeof(kr_ray_f64) && ray_bytes != (int32_t) sizeof(kr_ray_f32))) { set_error("kr_host_attach: bad argument"); return KR_EINVAL; }
+    if (!rays || n <= 0 || (ray_bytes != (int32_t) sizeof(kr_ray_f64) && ray_bytes != (int32_t) sizeof(kr_ray_f32))) return invalid("kr_host_attach: bad argument");
     int rc = require_device();
     if (rc != KR_OK) return rc;
     Attached a;
     a.host = rays; a.n = n; a.ray_bytes = (size_t) ray_bytes;
     {
         std::lock_guard<std::mutex> lk(g_att_mu);
-        if (g_attached.count(rays)) { set_error("kr_host_attach: array is already attached"); return KR_EINVAL; }
+        if (g_attached.count(rays)) return invalid("kr_host_attach: array is already attached");
     }
-    auto undo = [&]() { if (a.dev) (void) hipFree(a.dev); if (a.d_field) (void) hipFree(a.d_field); std::free(a.h_field); };
     hipError_t e = hipMalloc(&a.dev, (size_t) n * ray_bytes);
     if (e == hipSuccess) e = hipMalloc(&a.d_field, (size_t) n * 32);
     if (e == hipSuccess && !(a.h_field = std::malloc((size_t) n * 32))) e = hipErrorOutOfMemory;
-    if (e != hipSuccess) { undo(); return hip_fail(e, "kr_host_attach allocation", __FILE__, __LINE__); }
+    if (e != hipSuccess) { release_buffers(a); return hip_fail(e, "kr_host_attach allocation", __FILE__, __LINE__); }
     std::lock_guard<std::mutex> lk(g_att_mu);
     g_attached[rays] = a;
     return KR_OK;
@@ -958,9 +802,7 @@ int kr_host_detach(void* rays)
         a = it->second;
         g_attached.erase(it);
     }
-    (void) hipFree(a.dev);
-    (void) hipFree(a.d_field);
-    std::free(a.h_field);
+    release_buffers(a);
     (void) hipGetLastError();
     return KR_OK;
 }
@@ -968,7 +810,7 @@ int kr_host_detach(void* rays)
 // ---- memory helpers ------------------------------------------------------------------------------------------
 int kr_malloc(void** d_ptr, int64_t bytes)
 {
-    if (!d_ptr || bytes < 0) { set_error("kr_malloc: bad argument"); return KR_EINVAL; }
+    if (!d_ptr || bytes < 0) return invalid("kr_malloc: bad argument");
     int rc = require_device();
     if (rc != KR_OK) return rc;
     KR_HIP(hipMalloc(d_ptr, (size_t) (bytes ? bytes : 1)));
@@ -981,7 +823,7 @@ int kr_free(void* d_ptr)
 }
 int kr_host_alloc(void** h_ptr, int64_t bytes)
 {
-    if (!h_ptr || bytes < 0) { set_error("kr_host_alloc: bad argument"); return KR_EINVAL; }
+    if (!h_ptr || bytes < 0) return invalid("kr_host_alloc: bad argument");
     int rc = require_device();
     if (rc != KR_OK) return rc;
     KR_HIP(hipHostMalloc(h_ptr, (size_t) (bytes ? bytes : 1), hipHostMallocDefault));
@@ -1014,7 +856,7 @@ int kr_synchronize(void* stream)
 }
 int kr_stream_create(void** stream)
 {
-    if (!stream) { set_error("kr_stream_create: null argument"); return KR_EINVAL; }
+    if (!stream) return invalid("kr_stream_create: null argument");
     int rc = require_device();
     if (rc != KR_OK) return rc;
     hipStream_t s = nullptr;

@@ -18,30 +18,17 @@
 #include <cstring>
 #include <string>
 
-#include "kr_common.hpp"
-#include "kr_device.hpp"
-#include "kr_post_device.hpp"
+#include "kr_pass.hpp"
 
 namespace kr {
 
-PlaneTrig plane_trig(const kr_imageplane* s);        // kr_post.hip
-
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int kBundle = 5;                 // ImagePlaneBundles::RAYS_PER_BUNDLE: centre, east, west, north, south
 constexpr double kSentinel = 1e30;         // caustic_discplane.cpp:152
 constexpr int kPlanes = 9, kCounts = 7;
 enum Plane { P_DET = 0, P_SIGN, P_ORDER, P_HIT, P_RADIUS, P_PHI, P_X, P_Y, P_REDSHIFT };
 enum Count { C_DISC = 0, C_HORIZON, C_RLIM, C_STEPLIM, C_OUT_OF_RANGE, C_OTHER, C_SUPPRESSED };
-
-inline int grid_for(int64_t items, int per_block, int cap_blocks = 256 * 16)
-{
-    const int64_t b = (items + per_block - 1) / per_block;
-    return (int) std::max<int64_t>(1, std::min<int64_t>(b, cap_blocks));
-}
-
-#define KR_LAUNCH_CHECK() KR_HIP(hipGetLastError())
 
 // ---- ImagePlaneBundles ctor (imageplane_bundles.h:150-199) + redshift_start(0, true) in one pass: slot s is member s % 5 of bundle s / 5 ------
 KR_DEV kr_ray_f64 bundle_ray(const kr_imageplane& s, const PlaneTrig& tr, long long n_grid, int Ny, double eps_x, double eps_y, double a, long long slot)
@@ -68,7 +55,7 @@ bundles_init_emit_kernel(kr_ray_f64* __restrict__ rays, long long n, kr_imagepla
         const kr_ray_f64 r0 = bundle_ray(s, tr, n_grid, Ny, eps_x, eps_y, a, 0);      // record 0 of the source (raytracer.cpp:389-393)
         V = keplerian_V<double>(am, r0.r, r0.theta, projradius != 0);
     }
-    for (long long slot = blockIdx.x * (long long) kBlock + threadIdx.x; slot < n; slot += (long long) gridDim.x * kBlock) {
+    KR_GRID_STRIDE(slot, n) {
         kr_ray_f64 ray = bundle_ray(s, tr, n_grid, Ny, eps_x, eps_y, a, slot);
         ray.emit = emit_value(ray, spin, am, V, reverse);
         rays[slot] = ray;
@@ -217,7 +204,7 @@ grid_jacobian_kernel(kr_caustic_map m, double* __restrict__ maps)
     const double* order = maps + P_ORDER * npix;
     const double* xd = maps + P_X * npix;
     const double* yd = maps + P_Y * npix;
-    for (long long px = blockIdx.x * (long long) kBlock + threadIdx.x; px < npix; px += (long long) gridDim.x * kBlock) {
+    KR_GRID_STRIDE(px, npix) {
         const int ix = (int) (px / ny), iy = (int) (px % ny);
         double det = __builtin_nan(""), sign = 0;
         if (hit[px] != 0 && !(ix == 0 || ix == nx - 1 || iy == 0 || iy == ny - 1)) {
@@ -252,7 +239,7 @@ suppress_mark_kernel(kr_caustic_map m, double* __restrict__ maps)
     const long long npix = (long long) nx * ny;
     double* sign = maps + P_SIGN * npix;
     unsigned suppressed = 0;
-    for (long long px = blockIdx.x * (long long) kBlock + threadIdx.x; px < npix; px += (long long) gridDim.x * kBlock) {
+    KR_GRID_STRIDE(px, npix) {
         const double s = sign[px];
         if (s == 0.0) continue;
         const int ix = (int) (px / ny), iy = (int) (px % ny);
@@ -288,7 +275,7 @@ suppress_mark_kernel(kr_caustic_map m, double* __restrict__ maps)
 __global__ void __launch_bounds__(kBlock)
 suppress_clear_kernel(long long npix, double* __restrict__ sign)
 {
-    for (long long px = blockIdx.x * (long long) kBlock + threadIdx.x; px < npix; px += (long long) gridDim.x * kBlock) {
+    KR_GRID_STRIDE(px, npix) {
         const double s = sign[px];
         if (s == 2.0 || s == -2.0) sign[px] = 0.0;
     }
@@ -309,7 +296,7 @@ int caustic_validate(const kr_caustic_map* m, const char* who)
 int bundles_init_emit_dev(const kr_imageplane* s, int nx, int ny, double eps_frac, double V, int reverse, int projradius, void* d, int64_t n, hipStream_t st)
 {
     if (n <= 0) return KR_OK;
-    hipLaunchKernelGGL(bundles_init_emit_kernel, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, st, (kr_ray_f64*) d, (long long) n, *s, plane_trig(s), nx, ny,
+    hipLaunchKernelGGL(bundles_init_emit_kernel, dim3(grid_for(n, kBlock, kCapStream)), dim3(kBlock), 0, st, (kr_ray_f64*) d, (long long) n, *s, plane_trig(s), nx, ny,
                        eps_frac * s->dx, eps_frac * s->dy, -1 * s->spin, V, reverse, projradius);
     KR_LAUNCH_CHECK();
     return KR_OK;
@@ -322,13 +309,13 @@ int post_caustic_dev(double spin, int reverse, const kr_caustic_map* m, void* d,
     KR_HIP(hipMemsetAsync(maps + kPlanes * npix, 0, kCounts * sizeof(double), st));
     if (m->bundles) {
         constexpr int kPixels = 64;                 // 320 work-items: five waves, one pixel per lane of the first in the gather
-        hipLaunchKernelGGL((post_caustic_kernel<kBundle, kPixels>), dim3(grid_for(n, kBundle * kPixels)), dim3(kBundle * kPixels), 0, st, (kr_ray_f64*) d,
+        hipLaunchKernelGGL((post_caustic_kernel<kBundle, kPixels>), dim3(grid_for(n, kBundle * kPixels, kCapStream)), dim3(kBundle * kPixels), 0, st, (kr_ray_f64*) d,
                            (long long) n, spin, reverse, *m, maps);
         KR_LAUNCH_CHECK();
     } else {
-        hipLaunchKernelGGL((post_caustic_kernel<1, kBlock>), dim3(grid_for(n, kBlock)), dim3(kBlock), 0, st, (kr_ray_f64*) d, (long long) n, spin, reverse, *m, maps);
+        hipLaunchKernelGGL((post_caustic_kernel<1, kBlock>), dim3(grid_for(n, kBlock, kCapStream)), dim3(kBlock), 0, st, (kr_ray_f64*) d, (long long) n, spin, reverse, *m, maps);
         KR_LAUNCH_CHECK();
-        hipLaunchKernelGGL(grid_jacobian_kernel, dim3(grid_for(npix, kBlock)), dim3(kBlock), 0, st, *m, maps);
+        hipLaunchKernelGGL(grid_jacobian_kernel, dim3(grid_for(npix, kBlock, kCapStream)), dim3(kBlock), 0, st, *m, maps);
         KR_LAUNCH_CHECK();
     }
     return KR_OK;
@@ -339,9 +326,9 @@ int caustic_suppress_dev(const kr_caustic_map* m, void* d_maps, hipStream_t st)
     const long long npix = (long long) m->nx * m->ny;
     double* maps = (double*) d_maps;
     KR_HIP(hipMemsetAsync(maps + kPlanes * npix + C_SUPPRESSED, 0, sizeof(double), st));
-    hipLaunchKernelGGL(suppress_mark_kernel, dim3(grid_for(npix, kBlock)), dim3(kBlock), 0, st, *m, maps);
+    hipLaunchKernelGGL(suppress_mark_kernel, dim3(grid_for(npix, kBlock, kCapStream)), dim3(kBlock), 0, st, *m, maps);
     KR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(suppress_clear_kernel, dim3(grid_for(npix, kBlock)), dim3(kBlock), 0, st, npix, maps + P_SIGN * npix);
+    hipLaunchKernelGGL(suppress_clear_kernel, dim3(grid_for(npix, kBlock, kCapStream)), dim3(kBlock), 0, st, npix, maps + P_SIGN * npix);
     KR_LAUNCH_CHECK();
     return KR_OK;
 }

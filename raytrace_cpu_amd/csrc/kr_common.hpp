@@ -60,7 +60,7 @@ private:
 };
 void device_tables_shutdown();     // per device that has tables: drain it, free what no call holds; the caller's device is restored
 
-// device-pointer implementations (defined in kr_trace.hip / kr_post.hip); stream may be null
+// device-pointer implementations of the trace (kr_trace.hip); stream may be null.  The passes around it are declared in kr_pass.hpp.
 int trace_dev(const kr_params* p, void* d_rays, int64_t n, hipStream_t stream, kr_stats* stats, bool f32);
 int trace_async(const kr_params* p, void* d_rays, int64_t n, hipStream_t stream, bool f32, void** ticket);
 int trace_batch_async(int count, const kr_params* const* p, void* const* d_rays, const int64_t* n, void* const* streams, void** tickets);
@@ -69,6 +69,6 @@ int trace_poll(void* ticket, int64_t* rays_started, int32_t* finished);
 void trace_release(void* ticket);
 void side_stream_forget(hipStream_t user);
 int trace_shutdown();
-void angle_values(int kind, double x0, double dx, int n, double* sincos_pairs);     // kind 0: x = cos(alpha); 1: x = beta
+void angle_values(int kind, double x0, double dx, int n, double* sincos_pairs);     // kr_post.hip; kind 0: x = cos(alpha); 1: x = beta
 
 }  // namespace kr

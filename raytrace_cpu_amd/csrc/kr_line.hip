@@ -15,28 +15,17 @@
 #include <cstring>
 #include <string>
 
-#include "kr_common.hpp"
-#include "kr_device.hpp"
-#include "kr_post_device.hpp"
+#include "kr_pass.hpp"
 
 namespace kr {
 
 namespace {
 
-constexpr int kBlock = 256;
 // Per-workgroup LDS budget of the privatised histogram: 4096 doubles = 32 KiB, i.e. ne nt <= 2047.  Registers bound the residency first
 // (-Rpass-analysis=kernel-resource-usage, gfx950: post_line 194 VGPRs -> 2 waves / SIMD = 2 workgroups / CU, reduce_line 144 -> 3,
 // line_from_image 109 -> 4), and 4 x 32 KiB fit the CU's 160 KiB: the LDS never lowers the occupancy of any of the three; a 64-KiB
 // budget would halve line_from_image's.
 constexpr int kLineLdsWords = 4096;
-
-inline int grid_for(int64_t n, int cap_blocks = 256 * 4)
-{
-    const int64_t b = (n + kBlock - 1) / kBlock;
-    return (int) std::max<int64_t>(1, std::min<int64_t>(b, cap_blocks));
-}
-
-#define KR_LAUNCH_CHECK() KR_HIP(hipGetLastError())
 
 // what the kernels need besides the records: the bins by value (their host table pointers are never dereferenced on the device), the
 // device copy of the table, and the two logarithms of the bin ratios (taken once, on the host)
@@ -120,7 +109,7 @@ reduce_line_kernel(const kr_ray_f64* __restrict__ rays, long long n, LineDev L, 
     extern __shared__ double lds[];
     double* acc = line_begin<USE_LDS>(lds, out, L.words);
     unsigned long long on_disc = 0, binned = 0;
-    for (long long i = blockIdx.x * (long long) kBlock + threadIdx.x; i < n; i += (long long) gridDim.x * kBlock) {
+    KR_GRID_STRIDE(i, n) {
         const kr_ray_f64* ray = &rays[i];
         const double r = ray->r, g = ray->redshift;
         if (!line_filter(L.b, ray->steps, r, ray->theta, g)) continue;
@@ -140,17 +129,13 @@ post_line_kernel(kr_ray_f64* __restrict__ rays, long long n, double spin, double
     extern __shared__ double lds[];
     double* acc = line_begin<USE_LDS>(lds, out, L.words);
     unsigned long long on_disc = 0, binned = 0;
-    for (long long i = blockIdx.x * (long long) kBlock + threadIdx.x; i < n; i += (long long) gridDim.x * kBlock) {
+    KR_GRID_STRIDE(i, n) {
         kr_ray_f64* ray = &rays[i];
-        kr_ray_f64 v;
-        v.r = ray->r; v.theta = ray->theta; v.k = ray->k; v.h = ray->h; v.Q = ray->Q; v.rdot_sign = ray->rdot_sign; v.thetadot_sign = ray->thetadot_sign;
-        v.emit = ray->emit;
+        const kr_ray_f64 v = geodesic_of(ray);
         const int steps = ray->steps;
         const double g = redshift_value(v, spin, V, reverse, projradius, motion);
         ray->redshift = g;
-        const double phi = ray->phi;
-        const double wrapped = range_phi_value<double>(phi, steps, lo, hi);
-        if (!(wrapped == phi) && wrapped == wrapped) ray->phi = wrapped;
+        wrap_phi(ray, steps, lo, hi);
         if (!line_filter(L.b, steps, v.r, v.theta, g)) continue;
         on_disc++;
         binned += line_accumulate<false>(acc, L, v.r, g, ray->t);
@@ -166,7 +151,7 @@ line_from_image_kernel(const double* __restrict__ planes, long long npix, LineDe
     extern __shared__ double lds[];
     double* acc = line_begin<USE_LDS>(lds, out, L.words);
     unsigned long long on_disc = 0, binned = 0;
-    for (long long p = blockIdx.x * (long long) kBlock + threadIdx.x; p < npix; p += (long long) gridDim.x * kBlock) {
+    KR_GRID_STRIDE(p, npix) {
         const double nrays = planes[p];
         if (!(nrays > 0)) continue;
         on_disc++;
@@ -230,12 +215,8 @@ int reduce_line_dev(const kr_line_bins* b, const void* d, int64_t n, void* d_lin
     LineDev L;
     int rc = line_dev(b, pins, &L);
     if (rc != KR_OK) return rc;
-    if (L.words <= kLineLdsWords)
-        hipLaunchKernelGGL(reduce_line_kernel<true>, dim3(grid_for(n)), dim3(kBlock), L.words * sizeof(double), st, (const kr_ray_f64*) d, (long long) n, L,
-                           (double*) d_line);
-    else
-        hipLaunchKernelGGL(reduce_line_kernel<false>, dim3(grid_for(n)), dim3(kBlock), 0, st, (const kr_ray_f64*) d, (long long) n, L, (double*) d_line);
-    KR_LAUNCH_CHECK();
+    KR_LAUNCH_LDS_OR_GLOBAL(reduce_line_kernel, L.words <= kLineLdsWords, grid_for(n, kBlock, kCapHist), L.words * sizeof(double), st, (const kr_ray_f64*) d,
+                            (long long) n, L, (double*) d_line);
     return KR_OK;
 }
 
@@ -247,13 +228,8 @@ int post_line_dev(double spin, double V, int reverse, int projradius, int motion
     LineDev L;
     int rc = line_dev(b, pins, &L);
     if (rc != KR_OK) return rc;
-    if (L.words <= kLineLdsWords)
-        hipLaunchKernelGGL(post_line_kernel<true>, dim3(grid_for(n)), dim3(kBlock), L.words * sizeof(double), st, (kr_ray_f64*) d, (long long) n, spin, V,
-                           reverse, projradius, motion, lo, hi, L, (double*) d_line);
-    else
-        hipLaunchKernelGGL(post_line_kernel<false>, dim3(grid_for(n)), dim3(kBlock), 0, st, (kr_ray_f64*) d, (long long) n, spin, V, reverse, projradius,
-                           motion, lo, hi, L, (double*) d_line);
-    KR_LAUNCH_CHECK();
+    KR_LAUNCH_LDS_OR_GLOBAL(post_line_kernel, L.words <= kLineLdsWords, grid_for(n, kBlock, kCapHist), L.words * sizeof(double), st, (kr_ray_f64*) d, (long long) n,
+                            spin, V, reverse, projradius, motion, lo, hi, L, (double*) d_line);
     return KR_OK;
 }
 
@@ -264,12 +240,8 @@ int line_from_image_dev(const kr_line_bins* b, const kr_image_bins* ib, const vo
     LineDev L;
     int rc = line_dev(b, pins, &L);
     if (rc != KR_OK) return rc;
-    if (L.words <= kLineLdsWords)
-        hipLaunchKernelGGL(line_from_image_kernel<true>, dim3(grid_for(npix)), dim3(kBlock), L.words * sizeof(double), st, (const double*) d_planes, npix, L,
-                           (double*) d_line);
-    else
-        hipLaunchKernelGGL(line_from_image_kernel<false>, dim3(grid_for(npix)), dim3(kBlock), 0, st, (const double*) d_planes, npix, L, (double*) d_line);
-    KR_LAUNCH_CHECK();
+    KR_LAUNCH_LDS_OR_GLOBAL(line_from_image_kernel, L.words <= kLineLdsWords, grid_for(npix, kBlock, kCapHist), L.words * sizeof(double), st,
+                            (const double*) d_planes, npix, L, (double*) d_line);
     return KR_OK;
 }
 

@@ -1,0 +1,131 @@
+// kr_pass.hpp -- what the O(N) passes either side of the trace kernel share (kr_post.hip, kr_line.hip, kr_caustic.hip) and what kr_capi.hip calls
+// them through: the launch helpers, the per-record pieces that several kernels repeat, and the one declaration of every launcher.
+// The device helpers are plain forced-inline functions and one loop macro: each kernel compiles to the code it had with the lines written out.
+#pragma once
+
+#include <algorithm>
+#include <cstring>
+
+#include "kr_common.hpp"
+#include "kr_post_device.hpp"
+
+namespace kr {
+
+// ---- launching ---------------------------------------------------------------------------------------------------------------------------
+constexpr int kBlock = 256;
+
+// workgroups for `items` at `per_block` items each, at most `cap_blocks` (the kernels stride over the rest)
+inline int grid_for(int64_t items, int per_block, int cap_blocks)
+{
+    const int64_t b = (items + per_block - 1) / per_block;
+    return (int) std::max<int64_t>(1, std::min<int64_t>(b, cap_blocks));
+}
+constexpr int kCapStream = 256 * 16;       // streaming passes
+constexpr int kCapHist = 256 * 4;          // few, fat workgroups: every workgroup flushes its whole LDS histogram, so keep the flush traffic below the ray traffic
+
+#define KR_LAUNCH_CHECK() KR_HIP(hipGetLastError())
+
+// kernel<true> with its histogram privatised in LDS (lds_bytes of dynamic LDS; 0 when the kernel sizes it statically) when it fits, else
+// kernel<false> adding into the global histogram directly
+#define KR_LAUNCH_LDS_OR_GLOBAL(kernel, fits, grid, lds_bytes, st, ...)                                   \
+    do {                                                                                                  \
+        if (fits) hipLaunchKernelGGL(kernel<true>, dim3(grid), dim3(kBlock), lds_bytes, st, __VA_ARGS__); \
+        else hipLaunchKernelGGL(kernel<false>, dim3(grid), dim3(kBlock), 0, st, __VA_ARGS__);             \
+        KR_LAUNCH_CHECK();                                                                                \
+    } while (0)
+
+// Several small launches in one: the items of a chunk ride in the kernel arguments (no staging buffer whose lifetime a later call would have
+// to track), blockIdx.y picks the item.  Chunk is struct { Item item[K]; }; fill(i, pins, &item) describes launch i (n[i] > 0; empty ones are
+// skipped) and may pin device tables, which stay pinned until the chunk's launch is enqueued.  Blocks per item: block_budget over the items
+// of the chunk but at least 64, never more than the largest item's rays need.
+template <typename Chunk, typename Fill, typename Kernel, typename... Args>
+int launch_chunked(int count, const int64_t* n, int block_budget, hipStream_t st, Fill fill, Kernel kernel, Args... args)
+{
+    constexpr int kChunk = (int) (sizeof(Chunk::item) / sizeof(Chunk::item[0]));
+    for (int base = 0; base < count; base += kChunk) {
+        Chunk c;
+        std::memset(&c, 0, sizeof c);
+        TablePins pins;
+        int m = 0;
+        int64_t n_max = 0;
+        for (int i = base; i < count && i < base + kChunk; i++) {
+            if (n[i] <= 0) continue;
+            const int rc = fill(i, pins, &c.item[m++]);
+            if (rc != KR_OK) return rc;
+            n_max = std::max(n_max, n[i]);
+        }
+        if (m == 0) continue;
+        const int per_item = (int) std::max<int64_t>(1, std::min<int64_t>((n_max + kBlock - 1) / kBlock, std::max(64, block_budget / m)));
+        hipLaunchKernelGGL(kernel, dim3(per_item, m), dim3(kBlock), 0, st, c, args...);
+        KR_LAUNCH_CHECK();
+    }
+    return KR_OK;
+}
+
+// ---- device side: one record / pixel per work-item ---------------------------------------------------------------------------------------
+#define KR_GRID_STRIDE(i, n) for (long long i = blockIdx.x * (long long) kBlock + threadIdx.x; i < (n); i += (long long) gridDim.x * kBlock)
+
+// the constants of motion and the end point that emit_value / redshift_value read, copied out of a record that the pass goes on to write to
+template <typename R>
+KR_DEV R geodesic_start_of(const R* ray)
+{
+    R v;
+    v.r = ray->r; v.theta = ray->theta; v.k = ray->k; v.h = ray->h; v.Q = ray->Q; v.rdot_sign = ray->rdot_sign; v.thetadot_sign = ray->thetadot_sign;
+    return v;
+}
+
+template <typename R>
+KR_DEV R geodesic_of(const R* ray)
+{
+    R v = geodesic_start_of(ray);
+    v.emit = ray->emit;
+    return v;
+}
+
+// range_phi of one record: phi is written back only when wrapping changed it (NaN never is); returns the wrapped value
+template <typename R, typename T>
+KR_DEV T wrap_phi(R* ray, int steps, T lo, T hi)
+{
+    const T phi = ray->phi;
+    const T wrapped = range_phi_value<T>(phi, steps, lo, hi);
+    if (!(wrapped == phi) && wrapped == wrapped) ray->phi = wrapped;
+    return wrapped;
+}
+
+// ---- launchers (device pointers; the stream may be null) and validators behind the C API ---------------------------------------------------
+// kr_post.hip.  f32: the records are kr_ray_f32 and the pass computes in float (the scalars are float values carried in doubles)
+int redshift_start_dev(double spin, double V, int reverse, int projradius, void* d, int64_t n, hipStream_t st, bool f32);
+int redshift_dev(double spin, double V, int reverse, int projradius, int motion, void* d, int64_t n, hipStream_t st, bool f32);
+int redshift_dest_dev(double spin, int reverse, void* d, int64_t n, hipStream_t st, bool f32);
+int range_phi_dev(double lo, double hi, void* d, int64_t n, hipStream_t st, bool f32);
+int calculate_momentum_dev(double spin, void* d, int64_t n, hipStream_t st, bool f32);
+int pointsource_init_dev(const kr_pointsource* s, void* d, int64_t n, int64_t first, int64_t stride, hipStream_t st);
+int pointsource_init_emit_dev(const kr_pointsource* s, void* d, int64_t n, int64_t first, int64_t stride, double V, int reverse, int projradius, hipStream_t st);
+int pointsource_init_emit_batch_dev(int count, const kr_pointsource* s, const double* V, int reverse, int projradius, void* const* d, const int64_t* n, hipStream_t st);
+PlaneTrig plane_trig(const kr_imageplane* s);
+int imageplane_init_dev(const kr_imageplane* s, void* d, int64_t n, int64_t first, int64_t stride, hipStream_t st);
+int imageplane_init_emit_dev(const kr_imageplane* s, void* d, int64_t n, int64_t first, int64_t stride, int64_t run, double spin, double V, int reverse,
+                             int projradius, hipStream_t st);
+int reduce_emissivity_dev(const kr_emis_bins* b, const void* d, int64_t n, void* d_hist, hipStream_t st);
+int post_emissivity_dev(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_emis_bins* b, void* d, int64_t n,
+                        void* d_hist, hipStream_t st);
+int reduce_image_dev(const kr_image_bins* b, const void* d, int64_t n, void* d_planes, hipStream_t st);
+int post_image_dev(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_image_bins* b, void* d, int64_t n,
+                   void* d_planes, hipStream_t st);
+int reduce_return_dev(const kr_return_bins* b, const void* d, int64_t n, void* d_out4, hipStream_t st);
+int post_return_dev(double lo, double hi, const kr_return_bins* b, void* d, int64_t n, void* d_out4, hipStream_t st);
+int post_return_batch_dev(int count, double lo, double hi, const kr_return_bins* b, void* const* d, const int64_t* n, void* const* d_out4, hipStream_t st);
+int arith_probe_dev(int op, const double* a, const double* b, double* out, int64_t n);
+// kr_line.hip
+int line_validate(const kr_line_bins* b, const char* who);
+int reduce_line_dev(const kr_line_bins* b, const void* d, int64_t n, void* d_line, hipStream_t st);
+int post_line_dev(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_line_bins* b, void* d, int64_t n,
+                  void* d_line, hipStream_t st);
+int line_from_image_dev(const kr_line_bins* b, const kr_image_bins* ib, const void* d_planes, void* d_line, hipStream_t st);
+// kr_caustic.hip
+int caustic_validate(const kr_caustic_map* m, const char* who);
+int bundles_init_emit_dev(const kr_imageplane* s, int nx, int ny, double eps_frac, double V, int reverse, int projradius, void* d, int64_t n, hipStream_t st);
+int post_caustic_dev(double spin, int reverse, const kr_caustic_map* m, void* d, int64_t n, void* d_maps, hipStream_t st);
+int caustic_suppress_dev(const kr_caustic_map* m, void* d_maps, hipStream_t st);
+
+}  // namespace kr

@@ -17,22 +17,12 @@
 #include <string>
 #include <vector>
 
-#include "kr_common.hpp"
-#include "kr_device.hpp"
-#include "kr_post_device.hpp"
+#include "kr_pass.hpp"
 #include "kr_crmath.hpp"
 
 namespace kr {
 
 namespace {
-
-constexpr int kBlock = 256;
-
-inline int grid_for(int64_t n, int cap_blocks = 256 * 16)
-{
-    const int64_t b = (n + kBlock - 1) / kBlock;
-    return (int) std::max<int64_t>(1, std::min<int64_t>(b, cap_blocks));
-}
 
 template <typename R, typename T = typename ScalarOf<R>::type>
 __global__ void __launch_bounds__(kBlock)
@@ -40,10 +30,9 @@ redshift_start_kernel(R* __restrict__ rays, long long n, T spin, T V, int revers
 {
     const T a = reverse ? -1 * spin : spin;
     if (V == -1) V = keplerian_V<T>(a, rays[0].r, rays[0].theta, projradius != 0);
-    for (long long i = blockIdx.x * (long long) kBlock + threadIdx.x; i < n; i += (long long) gridDim.x * kBlock) {
+    KR_GRID_STRIDE(i, n) {
         R* ray = &rays[i];
-        R v;
-        v.r = ray->r; v.theta = ray->theta; v.k = ray->k; v.h = ray->h; v.Q = ray->Q; v.rdot_sign = ray->rdot_sign; v.thetadot_sign = ray->thetadot_sign;
+        const R v = geodesic_start_of(ray);
         ray->emit = emit_value(v, spin, a, V, reverse);
     }
 }
@@ -52,11 +41,9 @@ template <typename R, typename T = typename ScalarOf<R>::type>
 __global__ void __launch_bounds__(kBlock)
 redshift_kernel(R* __restrict__ rays, long long n, T spin, T V_in, int reverse, int projradius, int motion)
 {
-    for (long long i = blockIdx.x * (long long) kBlock + threadIdx.x; i < n; i += (long long) gridDim.x * kBlock) {
+    KR_GRID_STRIDE(i, n) {
         R* ray = &rays[i];
-        R v;
-        v.r = ray->r; v.theta = ray->theta; v.k = ray->k; v.h = ray->h; v.Q = ray->Q; v.rdot_sign = ray->rdot_sign; v.thetadot_sign = ray->thetadot_sign;
-        v.emit = ray->emit;
+        const R v = geodesic_of(ray);
         ray->redshift = redshift_value(v, spin, V_in, reverse, projradius, motion);
     }
 }
@@ -67,7 +54,7 @@ template <typename R, typename T = typename ScalarOf<R>::type>
 __global__ void __launch_bounds__(kBlock)
 redshift_dest_kernel(R* __restrict__ rays, long long n, T spin, int reverse)
 {
-    for (long long i = blockIdx.x * (long long) kBlock + threadIdx.x; i < n; i += (long long) gridDim.x * kBlock) {
+    KR_GRID_STRIDE(i, n) {
         R* ray = &rays[i];
         ray->redshift = redshift_dest_value<T>(ray->r, ray->theta, ray->k, ray->h, ray->Q, ray->rdot_sign, ray->thetadot_sign, ray->emit, spin, reverse);
     }
@@ -76,18 +63,14 @@ redshift_dest_kernel(R* __restrict__ rays, long long n, T spin, int reverse)
 template <typename R, typename T = typename ScalarOf<R>::type>
 __global__ void __launch_bounds__(kBlock) range_phi_kernel(R* __restrict__ rays, long long n, T lo, T hi)
 {
-    for (long long i = blockIdx.x * (long long) kBlock + threadIdx.x; i < n; i += (long long) gridDim.x * kBlock) {
-        const T phi = rays[i].phi;
-        const T wrapped = range_phi_value<T>(phi, rays[i].steps, lo, hi);
-        if (!(wrapped == phi) && wrapped == wrapped) rays[i].phi = wrapped;
-    }
+    KR_GRID_STRIDE(i, n) wrap_phi(&rays[i], rays[i].steps, lo, hi);
 }
 
 // ---- calculate_momentum (raytracer.cpp:704-753) ---------------------------------------------------------
 template <typename R, typename T = typename ScalarOf<R>::type>
 __global__ void __launch_bounds__(kBlock) calculate_momentum_kernel(R* __restrict__ rays, long long n, T spin)
 {
-    for (long long i = blockIdx.x * (long long) kBlock + threadIdx.x; i < n; i += (long long) gridDim.x * kBlock) {
+    KR_GRID_STRIDE(i, n) {
         R* ray = &rays[i];
         T pt, pr, ptheta, pphi;
         momentum<T>(pt, pr, ptheta, pphi, ray->k, ray->h, ray->Q, ray->rdot_sign, ray->thetadot_sign, ray->r, ray->theta, spin);
@@ -99,7 +82,7 @@ __global__ void __launch_bounds__(kBlock)
 pointsource_init_kernel(kr_ray_f64* __restrict__ rays, long long n, kr_pointsource s, SourceTables tb, int n_cosalpha, int n_beta, long long first, long long stride)
 {
     const long long n_grid = (long long) n_cosalpha * n_beta;
-    for (long long slot = blockIdx.x * (long long) kBlock + threadIdx.x; slot < n; slot += (long long) gridDim.x * kBlock)
+    KR_GRID_STRIDE(slot, n)
         rays[slot] = pointsource_ray(s, tb, n_grid, n_beta, first + slot * stride);
 }
 
@@ -117,7 +100,7 @@ pointsource_init_emit_kernel(kr_ray_f64* __restrict__ rays, long long n, kr_poin
         const kr_ray_f64 r0 = pointsource_ray(s, tb, n_grid, n_beta, 0);
         V = keplerian_V<double>(a, r0.r, r0.theta, projradius != 0);
     }
-    for (long long slot = blockIdx.x * (long long) kBlock + threadIdx.x; slot < n; slot += (long long) gridDim.x * kBlock) {
+    KR_GRID_STRIDE(slot, n) {
         kr_ray_f64 ray = pointsource_ray(s, tb, n_grid, n_beta, first + slot * stride);
         ray.emit = emit_value(ray, s.spin, a, V, reverse);
         rays[slot] = ray;
@@ -153,7 +136,7 @@ pointsource_init_emit_multi_kernel(SourceChunk c, int reverse, int projradius)
         const kr_ray_f64 r0 = pointsource_ray(s, tb, n_grid, n_beta, 0);
         V = keplerian_V<double>(a, r0.r, r0.theta, projradius != 0);
     }
-    for (long long slot = blockIdx.x * (long long) kBlock + threadIdx.x; slot < n; slot += (long long) gridDim.x * kBlock) {
+    KR_GRID_STRIDE(slot, n) {
         kr_ray_f64 ray = pointsource_ray(s, tb, n_grid, n_beta, slot);
         ray.emit = emit_value(ray, s.spin, a, V, reverse);
         rays[slot] = ray;
@@ -179,7 +162,7 @@ imageplane_init_kernel(kr_ray_f64* __restrict__ rays, long long n, kr_imageplane
     const long long n_grid = (long long) Nx * Ny;
     const double a = -1 * s.spin;                       // imageplane.cpp:12
     const double D = s.dist, phi0 = s.phi0;
-    for (long long slot = blockIdx.x * (long long) kBlock + threadIdx.x; slot < n; slot += (long long) gridDim.x * kBlock)
+    KR_GRID_STRIDE(slot, n)
         rays[slot] = imageplane_ray(s, tr, n_grid, Ny, a, D, phi0, first + slot * stride);
 }
 
@@ -197,7 +180,7 @@ imageplane_init_emit_kernel(kr_ray_f64* __restrict__ rays, long long n, kr_image
         const kr_ray_f64 r0 = imageplane_ray(s, tr, n_grid, Ny, a, D, phi0, 0);      // source ray 0 (raytracer.cpp:389-393), not the shard's first
         V = keplerian_V<double>(am, r0.r, r0.theta, projradius != 0);
     }
-    for (long long slot = blockIdx.x * (long long) kBlock + threadIdx.x; slot < n; slot += (long long) gridDim.x * kBlock) {
+    KR_GRID_STRIDE(slot, n) {
         // slot -> source ray: runs of `run` consecutive rays, `stride` apart (run = 1: plain ray-cyclic)
         const long long src = (run == 1) ? first + slot * stride : first + (slot / run) * stride + (slot % run);
         kr_ray_f64 ray = imageplane_ray(s, tr, n_grid, Ny, a, D, phi0, src);
@@ -221,7 +204,7 @@ reduce_emissivity_kernel(const kr_ray_f64* __restrict__ rays, long long n, kr_em
     }
     double* acc = USE_LDS ? lds : hist;
     const double log_dr = kr_log(b.dr);
-    for (long long i = blockIdx.x * (long long) kBlock + threadIdx.x; i < n; i += (long long) gridDim.x * kBlock) {
+    KR_GRID_STRIDE(i, n) {
         const kr_ray_f64* ray = &rays[i];
         emissivity_accumulate(acc, b, log_dr, ray->steps, ray->r, ray->theta, ray->redshift, ray->t);
     }
@@ -249,15 +232,11 @@ post_emissivity_kernel(kr_ray_f64* __restrict__ rays, long long n, double spin, 
     }
     double* acc = USE_LDS ? lds : hist;
     const double log_dr = kr_log(b.dr);
-    for (long long i = blockIdx.x * (long long) kBlock + threadIdx.x; i < n; i += (long long) gridDim.x * kBlock) {
+    KR_GRID_STRIDE(i, n) {
         kr_ray_f64* ray = &rays[i];
-        kr_ray_f64 v;
-        v.r = ray->r; v.theta = ray->theta; v.k = ray->k; v.h = ray->h; v.Q = ray->Q; v.rdot_sign = ray->rdot_sign; v.thetadot_sign = ray->thetadot_sign;
-        v.emit = ray->emit;
+        const kr_ray_f64 v = geodesic_of(ray);
         const int steps = ray->steps;
-        const double phi = ray->phi;
-        const double wrapped = range_phi_value<double>(phi, steps, lo, hi);
-        if (!(wrapped == phi) && wrapped == wrapped) ray->phi = wrapped;
+        wrap_phi(ray, steps, lo, hi);
         const double g = redshift_value(v, spin, V, reverse, projradius, motion);
         ray->redshift = g;
         emissivity_accumulate(acc, b, log_dr, steps, v.r, v.theta, g, ray->t);
@@ -300,7 +279,7 @@ reduce_image_kernel(const kr_ray_f64* __restrict__ rays, long long n, kr_image_b
 {
     const long long npix = (long long) b.img_nx * b.img_ny;
     unsigned long long hits = 0;
-    for (long long i = blockIdx.x * (long long) kBlock + threadIdx.x; i < n; i += (long long) gridDim.x * kBlock) {
+    KR_GRID_STRIDE(i, n) {
         const kr_ray_f64* ray = &rays[i];
         hits += image_accumulate(planes, npix, b, ray->steps, ray->r, ray->theta, ray->phi, ray->t, ray->redshift, ray->alpha, ray->beta);
     }
@@ -315,17 +294,13 @@ post_image_kernel(kr_ray_f64* __restrict__ rays, long long n, double spin, doubl
 {
     const long long npix = (long long) b.img_nx * b.img_ny;
     unsigned long long hits = 0;
-    for (long long i = blockIdx.x * (long long) kBlock + threadIdx.x; i < n; i += (long long) gridDim.x * kBlock) {
+    KR_GRID_STRIDE(i, n) {
         kr_ray_f64* ray = &rays[i];
-        kr_ray_f64 v;
-        v.r = ray->r; v.theta = ray->theta; v.k = ray->k; v.h = ray->h; v.Q = ray->Q; v.rdot_sign = ray->rdot_sign; v.thetadot_sign = ray->thetadot_sign;
-        v.emit = ray->emit;
+        const kr_ray_f64 v = geodesic_of(ray);
         const int steps = ray->steps;
         const double g = redshift_value(v, spin, V, reverse, projradius, motion);
         ray->redshift = g;
-        const double phi = ray->phi;
-        const double wrapped = range_phi_value<double>(phi, steps, lo, hi);
-        if (!(wrapped == phi) && wrapped == wrapped) ray->phi = wrapped;
+        const double wrapped = wrap_phi(ray, steps, lo, hi);
         hits += image_accumulate(planes, npix, b, steps, v.r, v.theta, wrapped, ray->t, g, ray->alpha, ray->beta);
     }
     if (hits) atomicAdd(&planes[7 * npix], (double) hits);
@@ -340,10 +315,12 @@ template <bool FUSED>
 KR_DEV void reduce_return_body(kr_ray_f64* __restrict__ rays, long long n, const kr_return_bins& b, double* __restrict__ out4, double lo, double hi)
 {
     double acc[4] = {0, 0, 0, 0};
-    for (long long i = blockIdx.x * (long long) kBlock + threadIdx.x; i < n; i += (long long) gridDim.x * kBlock) {
+    KR_GRID_STRIDE(i, n) {
         kr_ray_f64* ray = &rays[i];
         double phi = ray->phi;
         if (FUSED) {
+            // (written out, not wrap_phi: the classification below goes on with the value that was written back, and taking wrap_phi's
+            // result for it instead changed the code of both fused instances)
             const double wrapped = range_phi_value<double>(phi, ray->steps, lo, hi);
             if (!(wrapped == phi) && wrapped == wrapped) { ray->phi = wrapped; phi = wrapped; }
         }
@@ -410,7 +387,7 @@ reduce_return_multi_kernel(ReturnChunk c, double lo, double hi)
 //      test can compare them with the host's IEEE results (tests/test_gpu_primitives.py) ------------------------------
 __global__ void __launch_bounds__(kBlock) arith_probe_kernel(int op, const double* __restrict__ a, const double* __restrict__ b, double* __restrict__ out, long long n)
 {
-    for (long long i = blockIdx.x * (long long) kBlock + threadIdx.x; i < n; i += (long long) gridDim.x * kBlock) {
+    KR_GRID_STRIDE(i, n) {
         const double x = a[i], y = b[i];
         double r = 0, s, c;
         switch (op) {
@@ -443,12 +420,10 @@ __global__ void __launch_bounds__(kBlock) arith_probe_kernel(int op, const doubl
 }
 
 // ---- launchers (device pointers) ---------------------------------------------------------------------------
-#define KR_LAUNCH_CHECK() KR_HIP(hipGetLastError())
-
 int arith_probe_dev(int op, const double* a, const double* b, double* out, int64_t n)
 {
     if (n <= 0) return KR_OK;
-    hipLaunchKernelGGL(arith_probe_kernel, dim3(grid_for(n)), dim3(kBlock), 0, nullptr, op, a, b, out, (long long) n);
+    hipLaunchKernelGGL(arith_probe_kernel, dim3(grid_for(n, kBlock, kCapStream)), dim3(kBlock), 0, nullptr, op, a, b, out, (long long) n);
     KR_LAUNCH_CHECK();
     return KR_OK;
 }
@@ -457,8 +432,8 @@ int arith_probe_dev(int op, const double* a, const double* b, double* out, int64
 #define KR_POST_LAUNCH(kernel, ...)                                                                                      \
     do {                                                                                                                 \
         if (n <= 0) return KR_OK;                                                                                        \
-        if (f32) hipLaunchKernelGGL((kernel<kr_ray_f32, float>), dim3(grid_for(n)), dim3(kBlock), 0, st, (kr_ray_f32*) d, (long long) n, __VA_ARGS__); \
-        else hipLaunchKernelGGL((kernel<kr_ray_f64, double>), dim3(grid_for(n)), dim3(kBlock), 0, st, (kr_ray_f64*) d, (long long) n, __VA_ARGS__);   \
+        if (f32) hipLaunchKernelGGL((kernel<kr_ray_f32, float>), dim3(grid_for(n, kBlock, kCapStream)), dim3(kBlock), 0, st, (kr_ray_f32*) d, (long long) n, __VA_ARGS__); \
+        else hipLaunchKernelGGL((kernel<kr_ray_f64, double>), dim3(grid_for(n, kBlock, kCapStream)), dim3(kBlock), 0, st, (kr_ray_f64*) d, (long long) n, __VA_ARGS__);   \
         KR_LAUNCH_CHECK();                                                                                               \
         return KR_OK;                                                                                                    \
     } while (0)
@@ -543,7 +518,7 @@ int pointsource_init_dev(const kr_pointsource* s, void* d, int64_t n, int64_t fi
     SourceTables tb;
     const int rc = source_tables(s, nc, nb, pins, &tb);
     if (rc != KR_OK) return rc;
-    hipLaunchKernelGGL(pointsource_init_kernel, dim3(grid_for(n)), dim3(kBlock), 0, st, (kr_ray_f64*) d, (long long) n, *s, tb, nc, nb, (long long) first, (long long) stride);
+    hipLaunchKernelGGL(pointsource_init_kernel, dim3(grid_for(n, kBlock, kCapStream)), dim3(kBlock), 0, st, (kr_ray_f64*) d, (long long) n, *s, tb, nc, nb, (long long) first, (long long) stride);
     KR_LAUNCH_CHECK();
     return KR_OK;
 }
@@ -558,7 +533,7 @@ int pointsource_init_emit_dev(const kr_pointsource* s, void* d, int64_t n, int64
     SourceTables tb;
     const int rc = source_tables(s, nc, nb, pins, &tb);
     if (rc != KR_OK) return rc;
-    hipLaunchKernelGGL(pointsource_init_emit_kernel, dim3(grid_for(n)), dim3(kBlock), 0, st, (kr_ray_f64*) d, (long long) n, *s, tb, nc, nb, (long long) first,
+    hipLaunchKernelGGL(pointsource_init_emit_kernel, dim3(grid_for(n, kBlock, kCapStream)), dim3(kBlock), 0, st, (kr_ray_f64*) d, (long long) n, *s, tb, nc, nb, (long long) first,
                        (long long) stride, V, reverse, projradius);
     KR_LAUNCH_CHECK();
     return KR_OK;
@@ -580,7 +555,7 @@ int imageplane_init_dev(const kr_imageplane* s, void* d, int64_t n, int64_t firs
     if (first < 0 || stride < 1) { set_error("kr_imageplane_init: bad first/stride"); return KR_EINVAL; }
     if (first == 0 && stride == 1 && n < total) { set_error("kr_imageplane_init: n smaller than kr_imageplane_count()"); return KR_EINVAL; }
     if (n <= 0) return KR_OK;
-    hipLaunchKernelGGL(imageplane_init_kernel, dim3(grid_for(n)), dim3(kBlock), 0, st, (kr_ray_f64*) d, (long long) n, *s, plane_trig(s), nx, ny, (long long) first, (long long) stride);
+    hipLaunchKernelGGL(imageplane_init_kernel, dim3(grid_for(n, kBlock, kCapStream)), dim3(kBlock), 0, st, (kr_ray_f64*) d, (long long) n, *s, plane_trig(s), nx, ny, (long long) first, (long long) stride);
     KR_LAUNCH_CHECK();
     return KR_OK;
 }
@@ -592,7 +567,7 @@ int imageplane_init_emit_dev(const kr_imageplane* s, void* d, int64_t n, int64_t
     kr_imageplane_count(s, &nx, &ny);
     if (first < 0 || stride < 1 || run < 1 || run > stride) { set_error("kr_imageplane_init_emit: bad first/stride/run"); return KR_EINVAL; }
     if (n <= 0) return KR_OK;
-    hipLaunchKernelGGL(imageplane_init_emit_kernel, dim3(grid_for(n)), dim3(kBlock), 0, st, (kr_ray_f64*) d, (long long) n, *s, plane_trig(s), nx, ny, (long long) first,
+    hipLaunchKernelGGL(imageplane_init_emit_kernel, dim3(grid_for(n, kBlock, kCapStream)), dim3(kBlock), 0, st, (kr_ray_f64*) d, (long long) n, *s, plane_trig(s), nx, ny, (long long) first,
                        (long long) stride, (long long) run, spin, V, reverse, projradius);
     KR_LAUNCH_CHECK();
     return KR_OK;
@@ -603,7 +578,7 @@ int post_image_dev(double spin, double V, int reverse, int projradius, int motio
 {
     if (b->img_nx <= 0 || b->img_ny <= 0) { set_error("kr_post_image: image size must be positive"); return KR_EINVAL; }
     if (n <= 0) return KR_OK;
-    hipLaunchKernelGGL(post_image_kernel, dim3(grid_for(n)), dim3(kBlock), 0, st, (kr_ray_f64*) d, (long long) n, spin, V, reverse, projradius, motion, lo, hi, *b,
+    hipLaunchKernelGGL(post_image_kernel, dim3(grid_for(n, kBlock, kCapStream)), dim3(kBlock), 0, st, (kr_ray_f64*) d, (long long) n, spin, V, reverse, projradius, motion, lo, hi, *b,
                        (double*) d_planes);
     KR_LAUNCH_CHECK();
     return KR_OK;
@@ -613,13 +588,8 @@ int reduce_emissivity_dev(const kr_emis_bins* b, const void* d, int64_t n, void*
 {
     if (b->nr <= 0) { set_error("kr_reduce_emissivity: nr must be positive"); return KR_EINVAL; }
     if (n <= 0) return KR_OK;
-    // few, fat workgroups: every workgroup flushes 5*nr+1 atomics, so keep the flush traffic below the ray traffic
-    const int grid = grid_for(n, 256 * 4);
-    if (b->nr <= kMaxLdsBins)
-        hipLaunchKernelGGL(reduce_emissivity_kernel<true>, dim3(grid), dim3(kBlock), 0, st, (const kr_ray_f64*) d, (long long) n, *b, (double*) d_hist);
-    else
-        hipLaunchKernelGGL(reduce_emissivity_kernel<false>, dim3(grid), dim3(kBlock), 0, st, (const kr_ray_f64*) d, (long long) n, *b, (double*) d_hist);
-    KR_LAUNCH_CHECK();
+    KR_LAUNCH_LDS_OR_GLOBAL(reduce_emissivity_kernel, b->nr <= kMaxLdsBins, grid_for(n, kBlock, kCapHist), 0, st, (const kr_ray_f64*) d, (long long) n, *b,
+                            (double*) d_hist);
     return KR_OK;
 }
 
@@ -628,21 +598,15 @@ int post_emissivity_dev(double spin, double V, int reverse, int projradius, int 
 {
     if (b->nr <= 0) { set_error("kr_post_emissivity: nr must be positive"); return KR_EINVAL; }
     if (n <= 0) return KR_OK;
-    const int grid = grid_for(n, 256 * 4);
-    if (b->nr <= kMaxLdsBins)
-        hipLaunchKernelGGL(post_emissivity_kernel<true>, dim3(grid), dim3(kBlock), 0, st, (kr_ray_f64*) d, (long long) n, spin, V, reverse, projradius, motion, lo, hi, *b,
-                           (double*) d_hist);
-    else
-        hipLaunchKernelGGL(post_emissivity_kernel<false>, dim3(grid), dim3(kBlock), 0, st, (kr_ray_f64*) d, (long long) n, spin, V, reverse, projradius, motion, lo, hi, *b,
-                           (double*) d_hist);
-    KR_LAUNCH_CHECK();
+    KR_LAUNCH_LDS_OR_GLOBAL(post_emissivity_kernel, b->nr <= kMaxLdsBins, grid_for(n, kBlock, kCapHist), 0, st, (kr_ray_f64*) d, (long long) n, spin, V, reverse,
+                            projradius, motion, lo, hi, *b, (double*) d_hist);
     return KR_OK;
 }
 
 int reduce_return_dev(const kr_return_bins* b, const void* d, int64_t n, void* d_out4, hipStream_t st)
 {
     if (n <= 0) return KR_OK;
-    hipLaunchKernelGGL(reduce_return_kernel<false>, dim3(grid_for(n, 512)), dim3(kBlock), 0, st, (kr_ray_f64*) d, (long long) n, *b, (double*) d_out4, 0.0, 0.0);
+    hipLaunchKernelGGL(reduce_return_kernel<false>, dim3(grid_for(n, kBlock, 512)), dim3(kBlock), 0, st, (kr_ray_f64*) d, (long long) n, *b, (double*) d_out4, 0.0, 0.0);
     KR_LAUNCH_CHECK();
     return KR_OK;
 }
@@ -650,7 +614,7 @@ int reduce_return_dev(const kr_return_bins* b, const void* d, int64_t n, void* d
 int post_return_dev(double lo, double hi, const kr_return_bins* b, void* d, int64_t n, void* d_out4, hipStream_t st)
 {
     if (n <= 0) return KR_OK;
-    hipLaunchKernelGGL(reduce_return_kernel<true>, dim3(grid_for(n, 512)), dim3(kBlock), 0, st, (kr_ray_f64*) d, (long long) n, *b, (double*) d_out4, lo, hi);
+    hipLaunchKernelGGL(reduce_return_kernel<true>, dim3(grid_for(n, kBlock, 512)), dim3(kBlock), 0, st, (kr_ray_f64*) d, (long long) n, *b, (double*) d_out4, lo, hi);
     KR_LAUNCH_CHECK();
     return KR_OK;
 }
@@ -658,57 +622,31 @@ int post_return_dev(double lo, double hi, const kr_return_bins* b, void* d, int6
 int post_return_batch_dev(int count, double lo, double hi, const kr_return_bins* b, void* const* d, const int64_t* n, void* const* d_out4, hipStream_t st)
 {
     static_assert(sizeof(ReturnChunk) <= 3840, "kernel arguments are limited to 4 KB");
-    for (int base = 0; base < count; base += kReturnChunk) {
-        ReturnChunk c;
-        std::memset(&c, 0, sizeof c);
-        int m = 0;
-        int64_t n_max = 0;
-        for (int i = base; i < count && i < base + kReturnChunk; i++) {
-            if (n[i] <= 0) continue;
-            c.item[m++] = ReturnItem{b[i], (kr_ray_f64*) d[i], (long long) n[i], (double*) d_out4[i]};
-            n_max = std::max(n_max, n[i]);
-        }
-        if (m == 0) continue;
-        // blocks per item: enough to keep ~16 waves per SIMD in flight over the whole chunk, never more than an item's rays need
-        const int per_item = (int) std::max<int64_t>(1, std::min<int64_t>((n_max + kBlock - 1) / kBlock, std::max(64, 8192 / m)));
-        hipLaunchKernelGGL(reduce_return_multi_kernel, dim3(per_item, m), dim3(kBlock), 0, st, c, lo, hi);
-        KR_LAUNCH_CHECK();
-    }
-    return KR_OK;
+    // 8192 blocks over a chunk: enough to keep ~16 waves per SIMD in flight
+    return launch_chunked<ReturnChunk>(count, n, 8192, st, [&](int i, TablePins&, ReturnItem* it) {
+        *it = ReturnItem{b[i], (kr_ray_f64*) d[i], (long long) n[i], (double*) d_out4[i]};
+        return (int) KR_OK;
+    }, reduce_return_multi_kernel, lo, hi);
 }
 
 int pointsource_init_emit_batch_dev(int count, const kr_pointsource* s, const double* V, int reverse, int projradius, void* const* d, const int64_t* n, hipStream_t st)
 {
     static_assert(sizeof(SourceChunk) <= 3968, "kernel arguments are limited to 4 KB");
-    for (int base = 0; base < count; base += kSourceChunk) {
-        SourceChunk c;
-        std::memset(&c, 0, sizeof c);
-        TablePins pins;                                    // the tables of every item of the chunk, until its launch is enqueued
-        int m = 0;
-        int64_t n_max = 0;
-        for (int i = base; i < count && i < base + kSourceChunk; i++) {
-            if (n[i] <= 0) continue;
-            int32_t nc = 0, nb = 0;
-            kr_pointsource_count(&s[i], &nc, &nb);
-            SourceTables tb;
-            const int rc = source_tables(&s[i], nc, nb, pins, &tb);
-            if (rc != KR_OK) return rc;
-            c.item[m++] = SourceItem{s[i], tb, V ? V[i] : s[i].V, (kr_ray_f64*) d[i], (long long) n[i], nc, nb};
-            n_max = std::max(n_max, n[i]);
-        }
-        if (m == 0) continue;
-        const int per_item = (int) std::max<int64_t>(1, std::min<int64_t>((n_max + kBlock - 1) / kBlock, std::max(64, 16384 / m)));
-        hipLaunchKernelGGL(pointsource_init_emit_multi_kernel, dim3(per_item, m), dim3(kBlock), 0, st, c, reverse, projradius);
-        KR_LAUNCH_CHECK();
-    }
-    return KR_OK;
+    return launch_chunked<SourceChunk>(count, n, 16384, st, [&](int i, TablePins& pins, SourceItem* it) {
+        int32_t nc = 0, nb = 0;
+        kr_pointsource_count(&s[i], &nc, &nb);
+        SourceTables tb;
+        const int rc = source_tables(&s[i], nc, nb, pins, &tb);           // pinned until the chunk's launch is enqueued
+        *it = SourceItem{s[i], tb, V ? V[i] : s[i].V, (kr_ray_f64*) d[i], (long long) n[i], nc, nb};
+        return rc;
+    }, pointsource_init_emit_multi_kernel, reverse, projradius);
 }
 
 int reduce_image_dev(const kr_image_bins* b, const void* d, int64_t n, void* d_planes, hipStream_t st)
 {
     if (b->img_nx <= 0 || b->img_ny <= 0) { set_error("kr_reduce_image: image size must be positive"); return KR_EINVAL; }
     if (n <= 0) return KR_OK;
-    hipLaunchKernelGGL(reduce_image_kernel, dim3(grid_for(n)), dim3(kBlock), 0, st, (const kr_ray_f64*) d, (long long) n, *b, (double*) d_planes);
+    hipLaunchKernelGGL(reduce_image_kernel, dim3(grid_for(n, kBlock, kCapStream)), dim3(kBlock), 0, st, (const kr_ray_f64*) d, (long long) n, *b, (double*) d_planes);
     KR_LAUNCH_CHECK();
     return KR_OK;
 }
