@@ -268,6 +268,16 @@ typedef struct kr_caustic_map {
 static_assert(sizeof(kr_caustic_map) == 48, "kr_caustic_map is 48 bytes (raytrace_cpu_amd/capi.py CausticMap)");
 #endif
 
+/* What run_raytrace's trajectory dump takes besides the trace parameters (raytracer.h:112-122: write_step, write_rmax, write_rmin).  A struct of
+ * its own: kr_params and kr_stats keep their sizes.  write_rmin / write_rmax < 0: that side of the radial window is open. */
+typedef struct kr_path_spec {
+    double write_rmin, write_rmax;
+    int32_t write_step, pad;
+} kr_path_spec;
+#ifdef __cplusplus
+static_assert(sizeof(kr_path_spec) == 24, "kr_path_spec is 24 bytes (raytrace_cpu_amd/capi.py PathSpec)");
+#endif
+
 /* ---- runtime ---------------------------------------------------------------------------------- */
 int         kr_abi_version(void);
 const char* kr_last_error(void);
@@ -331,6 +341,37 @@ typedef void (*kr_progress_fn)(int64_t rays_started, int64_t rays_total, void* u
 int kr_trace_poll(void* ticket, int64_t* rays_started, int32_t* finished);
 int kr_trace_progress_f64(const kr_params* p, kr_ray_f64* rays, int64_t n, kr_stats* stats, int64_t every, kr_progress_fn fn, void* user);
 int kr_trace_progress_f32(const kr_params* p, kr_ray_f32* rays, int64_t n, kr_stats* stats, int64_t every, kr_progress_fn fn, void* user);
+
+/* ---- per-step ray paths: run_raytrace(method, theta_max, r_max, show_progress, outfile, write_step, write_rmax, write_rmin, write_cartesian),
+ * the serial branch raytracer.cpp:86-100, for Integrator::Euler and Integrator::RK4 in double precision with the strict arithmetic (flags = 0:
+ * a recorded ray takes exactly the steps, and ends with exactly the record, of kr_trace_dev_f64 with flags = 0).
+ * Write rule (raytracer.cpp:293-312 Euler, :923-942 and :1209-1228 RK4): with `steps` this call's own counter, incremented at the top of every
+ * iteration, a row {t, r, theta, phi} is written after the state update of an iteration when steps % write_step == 0 and
+ * (write_rmax < 0 || r < write_rmax) && (write_rmin < 0 || r > write_rmin).  A theta-flip iteration (`continue`), one that ends on r <= horizon and one
+ * that ends on dest->reached() write nothing; an iteration whose update makes the loop condition false does.  When a row is due, the window
+ * test fails and this ray has written a row before, the ray stops there (:308-311) and its record is what the epilogue makes of that state.
+ * Rays skipped by the skip rule (steps < 0 || steps >= steplim, :91-92) have no rows and traced = 0: a text writer puts the reference's two
+ * blank lines (:99) after traced rays only.
+ * Layout: ray i owns rows[offsets[i] .. offsets[i + 1]), a row is four doubles; always Boyer-Lindquist -- write_cartesian is applied by the host-side
+ * writers with cartesian() (src/include/kerr.h:41-48) and the C library, O(rows) next to formatting them.
+ * Two passes: kr_trace_paths_count_dev_f64 integrates every ray, stores the row counts, scans them into d_offsets[0 .. n] and returns
+ * *total_rows = offsets[n]; d_rays is NOT modified.  It SYNCHRONISES `stream` (the total goes to the host).  The caller allocates d_rows and calls
+ * kr_trace_paths_record_dev_f64 with the same params, spec and rays: it integrates again, stores the rows and the final ray records (as a trace
+ * does) and fills *stats (may be NULL: rays_total, rays_traced, steps_total, longest_ray_steps, kernel_ms).  It SYNCHRONISES `stream` too: it returns
+ * KR_EINVAL if any ray wrote another number of rows than its slab holds (nothing is ever stored outside a ray's slab or beyond total_rows).
+ * Refused with KR_EINVAL before any device work: null pointers, n < 0, write_step <= 0, NaN window bounds, KR_FLAG_FAST_MATH / KR_FLAG_HYBRID (paths carry
+ * the reference's arithmetic), KR_RK45, Euler with a destination stop kind (raytracer.cpp:983), d_rows not 32-byte aligned; total_rows < offsets[n] once
+ * the device has been asked for it.  Without a device: KR_ENODEVICE.
+ * RK45 is deliberately left out: its step is one TRIAL per wave iteration with retries, a replay mode and extrapolation (kr_rk45.hpp), and
+ * none of the reference's programs records it (trace_rays.cpp:71, trace_rays_imageplane.cpp:61 hard-wire Euler).
+ * kr_trace_paths_f64: host pointers; stages rays[], runs both passes and returns with rays[], offsets[0 .. n], traced[0 .. n) (may be NULL) filled and
+ * *rows pointing at 4 * *total_rows doubles of page-locked memory that the CALLER frees with kr_host_free. */
+int kr_trace_paths_count_dev_f64(const kr_params* p, const kr_path_spec* w, const void* d_rays, int64_t n, void* d_offsets /* int64[n + 1] */,
+                                 void* d_traced /* uint8[n] or NULL */, int64_t* total_rows, void* stream);
+int kr_trace_paths_record_dev_f64(const kr_params* p, const kr_path_spec* w, void* d_rays, int64_t n, const void* d_offsets, void* d_rows /* double[total_rows][4] */,
+                                  int64_t total_rows, void* stream, kr_stats* stats);
+int kr_trace_paths_f64(const kr_params* p, const kr_path_spec* w, kr_ray_f64* rays, int64_t n, int64_t* offsets /* n + 1 */, uint8_t* traced /* n or NULL */,
+                       double** rows, int64_t* total_rows, kr_stats* stats);
 
 /* ---- O(N) passes either side of it ----------------------------------------------------------- */
 /* Raytracer<T>::redshift_start(V, reverse, projradius)  raytracer.cpp:342-417 */

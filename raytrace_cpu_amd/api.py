@@ -355,3 +355,69 @@ def caustic_map(imageplane_spec, r_disc, integrator=capi.RK4, eps_frac=0.01, rk4
     res = caustic_from_words(cm, out)
     res.update(stats=st.as_dict(), r_isco=r_isco, eps_x=cm.eps_x, eps_y=cm.eps_y)
     return res
+
+
+def path_spec(write_step=1, write_rmin=-1.0, write_rmax=-1.0):
+    w = capi.PathSpec()
+    w.write_step, w.write_rmin, w.write_rmax = int(write_step), write_rmin, write_rmax
+    return w
+
+
+def rows_to_cartesian(rows, spin):
+    """(t, r, theta, phi) rows -> (t, x, y, z) with cartesian() of the reference (src/include/kerr.h:41-48), evaluated on the host with the C
+    library's sqrt / sin / cos through the math module (numpy's vectorised sin / cos need not round like it), one row at a time."""
+    import math
+    out = np.empty_like(rows)
+    a = float(spin)
+    for i, (t, r, theta, phi) in enumerate(rows.tolist()):
+        rho = math.sqrt(r * r + a * a) if r == r else r
+        st, ct = (math.sin(theta), math.cos(theta)) if math.isfinite(theta) else (math.nan, math.nan)
+        sp, cp = (math.sin(phi), math.cos(phi)) if math.isfinite(phi) else (math.nan, math.nan)
+        out[i] = (t, rho * st * cp, rho * st * sp, r * ct)
+    return out
+
+
+def trace_paths(params, rays, write_step=1, write_rmin=-1.0, write_rmax=-1.0, cartesian=False, spin=None):
+    """run_raytrace(..., outfile, write_step, write_rmax, write_rmin, write_cartesian) on a host array of Ray<double> records
+    (kr_trace_paths_f64: Euler / RK4, strict arithmetic).  Returns (offsets, rows, traced, rays_out, stats): ray i owns
+    rows[offsets[i]:offsets[i + 1]], a row is (t, r, theta, phi) -- or (t, x, y, z) with cartesian=True (spin: the Raytracer's, default
+    params.spin); traced[i] == 0 for rays the skip rule left out; rays_out are the final records, as trace() gives them."""
+    _rays_arg(rays, capi.RAY_F64)
+    L = lib()
+    out = rays.copy()
+    n = len(out)
+    w = path_spec(write_step, write_rmin, write_rmax)
+    offsets = np.zeros(n + 1, dtype=np.int64)
+    traced = np.zeros(n, dtype=np.uint8)
+    h_rows, total, st = C.c_void_p(), C.c_int64(), Stats()
+    capi.check(L, L.kr_trace_paths_f64(C.byref(params), C.byref(w), _ptr(out), n, _ptr(offsets), _ptr(traced), C.byref(h_rows), C.byref(total), C.byref(st)),
+               "kr_trace_paths")
+    try:
+        rows = np.empty((total.value, 4), dtype=np.float64)
+        if total.value > 0:
+            C.memmove(rows.ctypes.data, h_rows.value, rows.nbytes)
+    finally:
+        L.kr_host_free(h_rows)
+    if cartesian:
+        rows = rows_to_cartesian(rows, params.spin if spin is None else spin)
+    return offsets, rows, traced, out, st.as_dict()
+
+
+def _path_field(v):
+    # operator<< of an ofstream with setw(20), scientific, precision 8 (src/include/text_output.h); a NaN carries its sign
+    if v != v:
+        return "%20s" % ("-nan" if np.signbit(v) else "nan")
+    return "%20.8e" % v
+
+
+def paths_text(offsets, rows, traced):
+    """The reference's trajectory file of a recording: one row per line, every field setw(20) scientific precision 8, and two blank lines after
+    each ray that was traced (raytracer.cpp:99) -- also after one that wrote no row."""
+    parts = []
+    for i in range(len(offsets) - 1):
+        if not traced[i]:
+            continue
+        for row in rows[offsets[i]:offsets[i + 1]].tolist():
+            parts.append("".join(_path_field(v) for v in row) + "\n")
+        parts.append("\n\n")
+    return "".join(parts)

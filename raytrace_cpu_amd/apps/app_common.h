@@ -19,6 +19,12 @@ inline void check(int rc, const char* what)
     if (rc != KR_OK) throw std::runtime_error(std::string(what) + ": " + kr_last_error());
 }
 
+// a program that creates its output file before its first device call asks first: exit 1 with the reason, no file
+inline void require_device()
+{
+    if (kr_device_count() < 0) throw std::runtime_error(kr_last_error());
+}
+
 // KRTRACE_ARITHMETIC = hybrid | strict | fast, as in the host mirror of the class API; unset: hybrid for the
 // fixed-step integrators, strict for RK45
 inline int arithmetic_flags(const std::string& choice, int integrator)

@@ -94,6 +94,11 @@ class CausticMap(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("r_isco", "r_disc", "eps_x", "eps_y")] + [(n, C.c_int32) for n in ("nx", "ny", "bundles", "pad")]
 
 
+class PathSpec(C.Structure):
+    """kr_path_spec: write_step and the radial window of run_raytrace's trajectory dump (include/kr_trace.h has the write rule)."""
+    _fields_ = [("write_rmin", C.c_double), ("write_rmax", C.c_double), ("write_step", C.c_int32), ("pad", C.c_int32)]
+
+
 def line_bins(line_energy=6.4, e_min=1.0, de=0.1, ne=90, log_e=False, t0=0.0, dt=0.0, nt=1, r_isco=1.0, r_disc=1000.0, q1=3.0, rb1=4.0, q2=3.0,
               rb2=10.0, q3=3.0, g_index=3.0):
     b = LineBins()
@@ -156,6 +161,9 @@ PROTOTYPES = {
     "kr_trace_wait": (_int, [_vp, P(Stats)]),
     "kr_trace_wait_many": (_int, [_i32, P(_vp), P(Stats), P(Stats)]),
     "kr_trace_release": (_int, [_vp]),
+    "kr_trace_paths_count_dev_f64": (_int, [P(Params), P(PathSpec), _vp, _i64, _vp, _vp, P(_i64), _vp]),
+    "kr_trace_paths_record_dev_f64": (_int, [P(Params), P(PathSpec), _vp, _i64, _vp, _vp, _i64, _vp, P(Stats)]),
+    "kr_trace_paths_f64": (_int, [P(Params), P(PathSpec), _vp, _i64, _vp, _vp, P(_vp), P(_i64), P(Stats)]),
     "kr_redshift_start_f64": (_int, [_dbl, _dbl, _int, _int, _vp, _i64]),
     "kr_redshift_start_dev_f64": (_int, [_dbl, _dbl, _int, _int, _vp, _i64, _vp]),
     "kr_redshift_f64": (_int, [_dbl, _dbl, _int, _int, _int, _vp, _i64]),

@@ -523,6 +523,65 @@ int kr_trace_poll(void* ticket, int64_t* rays_started, int32_t* finished)
     return trace_poll(ticket, rays_started, finished);
 }
 
+// ---- per-step ray paths (kr_paths.hip): the serial branch of run_raytrace, raytracer.cpp:86-100 -------------------------------------------------
+// everything is validated before anything touches a device
+int kr_trace_paths_count_dev_f64(const kr_params* p, const kr_path_spec* w, const void* d_rays, int64_t n, void* d_offsets, void* d_traced, int64_t* total_rows,
+                                 void* stream)
+{
+    const int rc = paths_validate(p, w, "kr_trace_paths_count");
+    if (rc != KR_OK) return rc;
+    return on_device(n >= 0 && (n == 0 || d_rays) && d_offsets && total_rows, "kr_trace_paths_count: null argument or negative n",
+                     [&] { return paths_count_dev(p, w, d_rays, n, d_offsets, d_traced, total_rows, (hipStream_t) stream); });
+}
+
+int kr_trace_paths_record_dev_f64(const kr_params* p, const kr_path_spec* w, void* d_rays, int64_t n, const void* d_offsets, void* d_rows, int64_t total_rows,
+                                  void* stream, kr_stats* stats)
+{
+    const int rc = paths_validate(p, w, "kr_trace_paths_record");
+    if (rc != KR_OK) return rc;
+    if (n < 0 || (n > 0 && !d_rays) || !d_offsets || !d_rows || total_rows < 0) return invalid("kr_trace_paths_record: null argument, negative n or negative total_rows");
+    if ((uintptr_t) d_rows % 32 != 0) return invalid("kr_trace_paths_record: d_rows must be 32-byte aligned");
+    return on_device(true, nullptr, [&] { return paths_record_dev(p, w, d_rays, n, d_offsets, d_rows, total_rows, (hipStream_t) stream, stats); });
+}
+
+int kr_trace_paths_f64(const kr_params* p, const kr_path_spec* w, kr_ray_f64* rays, int64_t n, int64_t* offsets, uint8_t* traced, double** rows, int64_t* total_rows,
+                       kr_stats* stats)
+{
+    const int rc = paths_validate(p, w, "kr_trace_paths");
+    if (rc != KR_OK) return rc;
+    if (!offsets || !rows || !total_rows) return invalid("kr_trace_paths: null argument");
+    *rows = nullptr;
+    *total_rows = 0;
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    void* h_rows = nullptr;               // handed out only when the whole call, copy-back of rays[] included, has succeeded
+    int64_t total = 0;
+    const int rc_all = with_staged_rays(rays, n, sizeof(kr_ray_f64), kUpdates, stats, [&](void* d) -> int {
+        DeviceBuffer d_off, d_traced, d_rows;
+        int rc2 = d_off.alloc((size_t) (n + 1) * sizeof(int64_t));
+        if (rc2 == KR_OK) rc2 = d_traced.alloc((size_t) n);
+        if (rc2 != KR_OK) return rc2;
+        rc2 = paths_count_dev(p, w, d, n, d_off.p, d_traced.p, &total, nullptr);
+        if (rc2 != KR_OK) return rc2;
+        rc2 = d_rows.alloc((size_t) total * 4 * sizeof(double));
+        if (rc2 != KR_OK) return rc2;
+        rc2 = paths_record_dev(p, w, d, n, d_off.p, d_rows.p, total, nullptr, stats);
+        if (rc2 != KR_OK) return rc2;
+        KR_HIP(hipHostMalloc(&h_rows, total > 0 ? (size_t) total * 4 * sizeof(double) : 1, hipHostMallocDefault));
+        hipError_t e = hipMemcpy(offsets, d_off.p, (size_t) (n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && traced && n > 0) e = hipMemcpy(traced, d_traced.p, (size_t) n, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && total > 0) e = hipMemcpy(h_rows, d_rows.p, (size_t) total * 4 * sizeof(double), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return hip_fail(e, "hipMemcpy(paths)", __FILE__, __LINE__);
+        return (int) KR_OK;
+    });
+    if (rc_all != KR_OK) {
+        if (h_rows) (void) hipHostFree(h_rows);
+        return rc_all;
+    }
+    *rows = (double*) h_rows;
+    *total_rows = total;
+    return KR_OK;
+}
+
 // ---- O(N) passes -------------------------------------------------------------------------------------------
 // One line per pass: its scalar arguments, and the field(s) of a kr_ray_f64 it writes.  Each becomes four entry points: device and host
 // pointers, for Raytracer<double> and for Raytracer<float> (kr_ray_f32 records, float arithmetic; the scalars are float values carried in

@@ -127,5 +127,10 @@ int caustic_validate(const kr_caustic_map* m, const char* who);
 int bundles_init_emit_dev(const kr_imageplane* s, int nx, int ny, double eps_frac, double V, int reverse, int projradius, void* d, int64_t n, hipStream_t st);
 int post_caustic_dev(double spin, int reverse, const kr_caustic_map* m, void* d, int64_t n, void* d_maps, hipStream_t st);
 int caustic_suppress_dev(const kr_caustic_map* m, void* d_maps, hipStream_t st);
+// kr_paths.hip: the two passes of the recording trace; both wait for `st` (the count pass hands the total to the host, the record pass its verdict)
+int paths_validate(const kr_params* p, const kr_path_spec* w, const char* who);
+int paths_count_dev(const kr_params* p, const kr_path_spec* w, const void* d_rays, int64_t n, void* d_offsets, void* d_traced, int64_t* total_rows, hipStream_t st);
+int paths_record_dev(const kr_params* p, const kr_path_spec* w, void* d_rays, int64_t n, const void* d_offsets, void* d_rows, int64_t total_rows, hipStream_t st,
+                     kr_stats* stats);
 
 }  // namespace kr
