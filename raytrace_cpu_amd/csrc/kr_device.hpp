@@ -546,6 +546,149 @@ KR_DEV bool step_fixed(Lane<T>& s, const TraceConsts<T>& c)
     return !loop_cond<T, USE_DEST>(s, c);
 }
 
+// ---- radial rays (strict double precision, Euler / RK4, theta-limit stop) ------------------------------------------------------------------------
+// The polar numerator C = Q + (k a cos + h cos / sin)(k a cos - h cos / sin) of thetadot^2 = C / rho^4 depends on (Q, k, h, a, theta) only, not on r.
+// A ray for which it rounds to exactly +-0 at its theta is RADIAL: thetadot^2 = +-0 / rho^4 = +-0, so no polar turning point is seen, thetadot =
+// sqrt(+0) x sign = +-0, every stage angle is theta + x (+-0) = theta, the update adds +-0 -- the next step starts from the same theta and the same C,
+// and by induction the whole ray is a one-dimensional problem in r.  (The beta = -pi column of a lamp-post PointSource, emitted with thetadot = 0: Q is
+// built so that C cancels at the source's theta.  DESIGN.md 4.1.)  step_radial below is step_fixed's strict lone-wave path with everything that is a
+// constant of such a ray taken from a block computed once, when a lane takes the ray, and everything that is an exact zero or a comparison that cannot
+// hold left out; what remains has the same operands in the same association, hence the same bits.  The induction needs two things of every step that
+// only the step itself can tell: a finite step length (x above) and, at the base point and at each stage, a rho^2 whose square and reciprocals neither
+// overflow nor underflow (so that +-0 / rho^4 IS +-0 through the assembled reciprocal, and rho^2 x 0 x 0 is +0).  A step that does not meet them --
+// r or rdot NaN or infinite, practically -- is taken back and done by step_fixed, as is the rest of that ray.
+struct RadialRay {
+    double sin2theta, acs2;     // sin^2 theta, (a cos theta)^2
+    double y_sin;               // StageRecips::y_sin
+    double ptheta0;             // +0 x thetadot_sign: the ray's thetadot, signed zero included
+    bool general;               // not (or no longer) provably radial: this lane's ray takes step_fixed
+};
+
+// Is a ray with these constants radial at `theta`?  sn, cs, y_sin: kr_sincos of theta and lean_recip(sn), i.e. what k1_with_flips / momentum_impl
+// hold at that angle; C is formed as they form it.  theta must also be a fixed point of reflect_poles and inside the theta limits (the loop condition
+// and the epilogue then see a constant).  A NaN anywhere makes C NaN.
+KR_DEV bool ray_is_radial(double k, double h, double Q, double r, double theta, double a, double theta_lo, double theta_hi, double sn, double cs, double y_sin)
+{
+    const double hcs = lean_div_y(h * cs, sn, y_sin);
+    const double C = Q + (k * a * cs + hcs) * (k * a * cs - hcs);
+    return C == 0.0 && kr_finite(k) && kr_finite(h) && kr_finite(Q) && kr_finite(r) && theta > 0.0 && theta < kPi && theta > theta_lo && theta < theta_hi;
+}
+
+// when a lane takes a ray: the block, and the decision itself -- made here again, from the state the lane holds, whatever put the ray on the list
+KR_DEV void radial_claim(const Lane<double>& s, const TraceConsts<double>& c, RadialRay& q)
+{
+    double sn, cs;
+    kr_sincos<true>(s.theta, sn, cs);
+    q.sin2theta = sn * sn;
+    q.acs2 = (c.a * cs) * (c.a * cs);
+    q.y_sin = lean_recip(sn);
+    q.ptheta0 = 0.0 * s.thetadot_sign;
+    q.general = !ray_is_radial(s.k, s.h, s.Q, s.r, s.theta, c.a, c.theta_lo, c.theta_hi, sn, cs, q.y_sin);
+}
+
+KR_DEV bool radial_rhosq_in_range(double rhosq) { return rhosq > 0x1p-500 && rhosq < 0x1p500; }      // (NaN: false)
+
+// tdot, phidot and rdot^2 at radius r: momentum_impl / k1_with_flips with the ray's constants, without the polar half
+KR_DEV void radial_eval(double& pt, double& pphi, double& rdotsq, double& rhosq_o, double& y_rhosq_o, double k, double h, double r, double a, const RadialRay& q)
+{
+    const double sin2theta = q.sin2theta;
+    const double rhosq = r * r + q.acs2;
+    const double delta = r * r - 2 * r + a * a;
+    const double rhosq_delta = rhosq * delta;
+    const double sin2_rhosq_delta = sin2theta * rhosq_delta;
+    const double y_rhosq_delta = lean_recip(rhosq_delta);
+    const double y_rhosq = lean_recip(rhosq);
+    const double y_sin2_rhosq_delta = lean_recip_from(sin2_rhosq_delta, q.y_sin * (q.y_sin * y_rhosq_delta));
+    pt = lean_div_y((rhosq * (r * r + a * a) + 2 * a * a * r * sin2theta) * k - 2 * a * r * h, rhosq_delta, y_rhosq_delta);
+    pphi = lean_div_y(2 * a * r * sin2theta * k + (rhosq - 2 * r) * h, sin2_rhosq_delta, y_sin2_rhosq_delta);
+    rdotsq = lean_div_y((k * pt - h * pphi) * delta, rhosq, y_rhosq);       // (- rho^2 x 0 x 0 = - (+0): the identity, also on -0, inf and NaN)
+    rhosq_o = rhosq;
+    y_rhosq_o = y_rhosq;
+}
+
+// One iteration of the Euler / RK4 loop body for a radial ray on a wave that owns its SIMD.  Returns true when the ray has finished; sets q.general
+// and leaves `s` as it found it when the step has to be done by step_fixed instead.
+template <bool RK4>
+KR_DEV bool step_radial(Lane<double>& s, RadialRay& q, const TraceConsts<double>& c)
+{
+    const double a = c.a, k = s.k, h = s.h;
+    const double t0 = s.t, r0 = s.r, phi0 = s.phi, pt0 = s.pt, pr0 = s.pr, ptheta0 = s.ptheta, pphi0 = s.pphi;
+    const int32_t rdot_sign0 = s.rdot_sign, rdot_flips0 = s.rdot_flips, status0 = s.status;
+    const bool r_was_positive0 = s.r_was_positive;
+    ++s.steps;
+
+    double rhosq, y_rhosq, rdotsq;
+    radial_eval(s.pt, s.pphi, rdotsq, rhosq, y_rhosq, k, h, r0, a, q);
+    bool ok = radial_rhosq_in_range(rhosq);
+    s.ptheta = q.ptheta0;
+    {
+        const bool flip = rdotsq <= 0 && s.r_was_positive;
+        s.rdot_sign = flip ? -s.rdot_sign : s.rdot_sign;
+        s.rdot_flips += flip ? 1 : 0;
+        s.r_was_positive = !flip && (s.r_was_positive || rdotsq > 0);
+    }
+    s.pr = sq(kr_abs(rdotsq)) * s.rdot_sign;
+    const double pt1 = s.pt, pr1 = s.pr, pphi1 = s.pphi;
+
+    // step-size heuristic: the theta clause compares against |theta / +-0|, which is not a number, and the theta landing clip against theta itself
+    double step = div_const(kr_abs(dv(r0 - c.horizon, pr1)), c.precision, c.inv_precision, c.inv_ok);
+    if (r0 < c.tstep_rlim_eff) {
+        const double st = kr_abs(dv(c.max_tstep, pt1));
+        if (step > st) step = st;
+    }
+    {
+        const double sp = kr_abs(dv(c.phistep_eff, pphi1));
+        if (step > sp) step = sp;
+    }
+    if (step < KR_MIN_STEP) step = KR_MIN_STEP;
+    if (r0 + pr1 * step > c.rlim) step = kr_abs(dv(c.rlim - r0, pr1));
+    ok = ok && kr_finite(step);
+
+    if (pt1 <= 0) s.status |= KR_STATUS_ERGO;
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(energy_flag_needed(s, r0 - c.horizon)) != 0, false)) {
+        if ((1 - dv_y(2 * r0, rhosq, y_rhosq)) * pt1 + dv_y(2 * a * r0 * q.sin2theta, rhosq, y_rhosq) * pphi1 < 0) s.status |= KR_STATUS_NEG_ENERGY;
+    }
+
+    if (!RK4) {
+        s.t += pt1 * step;
+        s.r += pr1 * step;
+        s.phi += pphi1 * step;
+    } else {
+        auto stage = [&](double& pt, double& pr, double& pphi, double r_stage) {
+            double rdotsq_s, rhosq_s, y_s;
+            radial_eval(pt, pphi, rdotsq_s, rhosq_s, y_s, k, h, r_stage, a, q);
+            ok = ok && radial_rhosq_in_range(rhosq_s);
+            pr = sq(kr_abs(rdotsq_s)) * s.rdot_sign;
+        };
+        const double half = step / 2;
+        double pt2, pr2, pphi2, pt3, pr3, pphi3, pt4, pr4, pphi4;
+        stage(pt2, pr2, pphi2, r0 + half * pr1);
+        double acc_t = kr_fma2(pt2, pt1);
+        double acc_phi = kr_fma2(pphi2, pphi1);
+        stage(pt3, pr3, pphi3, r0 + half * pr2);
+        acc_t = kr_fma2(pt3, acc_t);
+        acc_phi = kr_fma2(pphi3, acc_phi);
+        const double acc_r = kr_fma2(pr3, kr_fma2(pr2, pr1));
+        stage(pt4, pr4, pphi4, r0 + step * pr3);
+        const double w = div_const(step, 6.0, 1.0 / 6.0, true);
+        s.t += w * (acc_t + pt4);
+        s.r += w * (acc_r + pr4);
+        s.phi += w * (acc_phi + pphi4);
+    }
+
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(!ok) != 0, false)) {
+        if (!ok) {
+            s.t = t0; s.r = r0; s.phi = phi0; s.pt = pt0; s.pr = pr0; s.ptheta = ptheta0; s.pphi = pphi0;
+            s.rdot_sign = rdot_sign0; s.rdot_flips = rdot_flips0; s.status = status0; s.r_was_positive = r_was_positive0;
+            --s.steps;
+            q.general = true;
+            return false;
+        }
+    }
+    if (s.r <= c.horizon) { s.status |= KR_STATUS_HORIZON; return true; }
+    return !(s.r < c.rlim && s.steps < c.steplim);
+}
+
 // Epilogue shared by all propagators (raytracer.cpp:315-339, :945-969, :1231-1253, :1574-1597, :1872-1893):
 // final status bits and the value of rays[i].steps to store.
 template <typename T, bool USE_DEST>

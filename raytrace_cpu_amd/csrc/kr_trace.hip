@@ -66,10 +66,13 @@ constexpr int kLongRaySteps = 2048;  // a wave whose oldest ray is older than 1 
 // Every launch of a trace has a block of counter words of its own in the workspace (device memory; copied out at the end of the trace): the queue
 // head (slots handed out so far), rays traced, steps, rk45 attempts / rejects / stationary steps / extrapolated steps, steps of the launch's longest ray (atomicMax).
 enum CounterWord { kHead, kTraced, kSteps, kAttempts, kRejects, kStationary, kExtrapolated, kLongest, kCounterWords,
-                   kFlagged = kTraced };      // kFlagged, in the split bookkeeping block only: the number of ill-conditioned rays (classify_kernel)
+                   // in the split bookkeeping block only (classify_kernel): the ill-conditioned rays that are not radial, the radial ones (both counts
+                   // run on past what their lists hold), and whether either list overflowed
+                   kFlagged = kTraced, kRadial = kSteps, kListsOverflowed = kAttempts };
 constexpr int kCounters = KR_OCC_STATS ? 13 : kCounterWords;         // words per block; KR_OCC_STATS builds: [8..12] occupancy sums
-enum CounterBlock { kMainBlock, kSideBlock, kOverflowBlock, kSplitBlock, kCounterBlocks };      // main launch, strict side launch, strict overflow launch, split bookkeeping
-constexpr int kListCap = 32768;      // index-list entries of the strict side launch
+// main launch, strict side launch (its general waves), strict overflow launch, split bookkeeping, the side launch's radial waves
+enum CounterBlock { kMainBlock, kSideBlock, kOverflowBlock, kSplitBlock, kRadialBlock, kCounterBlocks };
+constexpr int kListCap = 32768;      // entries of each of the side launch's two index lists (general, radial)
 
 template <typename T> struct RayOf;
 template <> struct RayOf<double> { using type = kr_ray_f64; };
@@ -100,7 +103,8 @@ template <typename T> KR_DEV unsigned long long wave_sum(unsigned long long v)
 // from device memory (the classification kernel of the split path produced it; see n_mode below); `mask` (optional): only
 // rays with mask[i] == mask_want are traced (the others belong to another launch of the split).  HOG: the kernel claims the whole register
 // file (512 VGPR+AGPR per lane), so each of its waves owns its SIMD and no other kernel's wave can be co-resident on
-// the CUs it occupies -- used for the few ill-conditioned / long rays that define the critical path.
+// the CUs it occupies -- used for the few ill-conditioned / long rays that define the critical path.  RADIAL (trace_body; trace_side_kernel's
+// radial waves): the wave's rays are integrated with step_radial, a lane whose ray turns out not to be radial with step_fixed.
 // Resident waves per SIMD the register allocation must allow: HOG 1 (the scheduler may trade registers for ILP; capping it at (1, 1) measured 2 %
 // slower), RK4 3 (<= 168 VGPRs), RK45 2, Euler 4 (its step is short and branchy: at 3 waves per SIMD the vector unit is 78 % busy; 1e7 rays
 // 38.5 / 31.4 / 28.3 ms at 2 / 3 / 4 resident waves, profiles/r03_ab_experiments.txt).
@@ -119,21 +123,22 @@ template <typename T> struct TraceDesc {
     int n_mode = 0, mask_want = 0;                // how n_ptr is applied (trace_body); the mask value this launch traces
 };
 
-template <typename T, int METHOD, bool USE_DEST, bool FAST, bool HOG, int REFILL_MIN>
+template <typename T, int METHOD, bool USE_DEST, bool FAST, bool HOG, int REFILL_MIN, bool RADIAL = false>
 KR_DEV void trace_body(typename RayOf<T>::type* __restrict__ rays, long long n, const TraceConsts<T>& c, unsigned long long* __restrict__ counters,
                        const int* __restrict__ list, const unsigned long long* __restrict__ n_ptr, int n_mode, const unsigned char* __restrict__ mask, int mask_want,
                        int& has_prio, long long first_slot = -1, unsigned long long head_offset = 0)
 {
     if (n_ptr) {
         // the item count was produced on the device (classify_kernel) and never visits the host:
-        // n_mode 1: the first min(n, *n_ptr) list entries;  n_mode 2: all n slots, but only if the list overflowed (else nothing)
+        // n_mode 1: the first min(n, *n_ptr) list entries;  n_mode 2: all n slots, but only if *n_ptr says that a list overflowed (else nothing)
         const long long m = (long long) *n_ptr;
-        n = (n_mode == 1) ? (m < n ? m : n) : (m > (long long) kListCap ? n : 0);
+        n = (n_mode == 1) ? (m < n ? m : n) : (m != 0 ? n : 0);
     }
     const int lane = threadIdx.x & 63;
     const unsigned long long lane_bit = 1ull << lane;
 
     Lane<T> s;
+    [[maybe_unused]] RadialRay radial;      // RADIAL: the constants of this lane's ray (step_radial)
     long long idx = -1;
     bool have = false;          // this lane holds a ray
     bool pend = false;          // this lane's ray has ended and is still in its registers: written out at the wave's next visit to the queue (or on exit)
@@ -224,6 +229,7 @@ KR_DEV void trace_body(typename RayOf<T>::type* __restrict__ rays, long long n, 
                         s.fsal_valid = false;
                         energy_guard_set(s);
                         if (METHOD == KR_RK45) rk45_seed(s, c);
+                        if constexpr (RADIAL) radial_claim(s, c, radial);
                         if (!loop_cond<T, USE_DEST>(s, c)) {
                             // zero-iteration call: only the epilogue runs (at the next visit)
                             have = false;
@@ -244,7 +250,20 @@ KR_DEV void trace_body(typename RayOf<T>::type* __restrict__ rays, long long n, 
         ++occ_iters;
         if (exhausted) { ++occ_tail_iters; occ_tail_steps += have ? 1 : 0; }
 #endif
-        if (have) {
+        if constexpr (RADIAL) {
+            // every wave of a radial launch runs the radial body only; a lane whose ray is not provably radial (radial_claim, or a step that step_radial
+            // handed back) is the exception, out of line
+            bool fin = false;
+            if (have && !radial.general) fin = step_radial<METHOD == KR_RK4>(s, radial, c);
+            const bool general = have && radial.general;
+            if (__builtin_expect(__builtin_amdgcn_ballot_w64(general) != 0, false)) {
+                if (general) fin = step_fixed<T, METHOD == KR_RK4, USE_DEST, FAST, HOG>(s, c);
+            }
+            if (fin) {
+                have = false;
+                pend = true;
+            }
+        } else if (have) {
             bool fin;
             if (METHOD == KR_EULER) fin = step_fixed<T, false, USE_DEST, FAST, HOG>(s, c);
             else if (METHOD == KR_RK4) fin = step_fixed<T, true, USE_DEST, FAST, HOG>(s, c);
@@ -312,6 +331,29 @@ trace_kernel(typename RayOf<T>::type* __restrict__ rays, long long n, TraceConst
     }
 }
 
+// The strict side launch of an Euler / RK4 trace with a theta-limit stop: its first `radial_workgroups` single-wave workgroups work on the list of
+// radial rays with the radial body (a wave is all-radial or not radial at all: no per-lane choice in the step), the others on the general list with
+// the body of trace_kernel's HOG instance.  One launch, so that both kinds start side by side while the chip is empty; two queues, counter blocks
+// and lists.  Either count is read from device memory (n_mode 1).
+template <int METHOD, int REFILL_MIN>
+__global__ void __attribute__((amdgpu_flat_work_group_size(kTraceBlock, kTraceBlock))) __attribute__((amdgpu_waves_per_eu(1, 8)))
+trace_side_kernel(kr_ray_f64* __restrict__ rays, long long n_list, TraceConsts<double> c, unsigned long long* __restrict__ counters_general,
+                  unsigned long long* __restrict__ counters_radial, const int* __restrict__ list_general, const int* __restrict__ list_radial,
+                  const unsigned long long* __restrict__ n_general, const unsigned long long* __restrict__ n_radial, int radial_workgroups)
+{
+    asm volatile("; claim the whole register file" ::: "v255", "a255");
+    int has_prio = 0;
+    if constexpr (METHOD != KR_RK4) consts_into_vector_registers(c);
+    const int b = (int) blockIdx.x, g = (int) gridDim.x;
+    if (b < radial_workgroups) {
+        trace_body<double, METHOD, false, false, true, REFILL_MIN, true>(rays, n_list, c, counters_radial, list_radial, n_radial, 1, nullptr, 0, has_prio, (long long) b * 64,
+                                                                         (unsigned long long) radial_workgroups * 64);
+    } else {
+        trace_body<double, METHOD, false, false, true, REFILL_MIN>(rays, n_list, c, counters_general, list_general, n_general, 1, nullptr, 0, has_prio,
+                                                                   (long long) (b - radial_workgroups) * 64, (unsigned long long) (g - radial_workgroups) * 64);
+    }
+}
+
 // ONE grid over MANY traces (kr_trace_batch_async_f64 when all traces of the batch use the same kernel instances).  Every wave serves
 // ONE trace -- wave_trace[workgroup index], or workgroup index mod n_desc when no table is given -- with the persistent loop above,
 // and leaves when that trace's queue is exhausted and its own lanes have drained.  The table interleaves the traces in proportion to
@@ -351,8 +393,9 @@ trace_multi_kernel(const TraceDesc<T>* __restrict__ descs, int n_desc, const int
 // (PointSource rays emitted at beta = -pi: sin(beta) = -1.2e-16; ImagePlane rays on x = 0 / y = 0; NaN rays).  The
 // reference's outcome for such a ray is decided by the rounding of exactly its own operation sequence, so only the
 // strict path reproduces it; every other ray is insensitive to a few ulp per operation (tests/parity.py) and may
-// take the fast path.  In the lamp-post workloads the ill-conditioned rays are also the longest ones (they ride the
-// polar axis in MIN_STEP steps), which is why they get SIMDs of their own (HOG launch).
+// take the fast path.  In the lamp-post workloads the ill-conditioned rays are also the longest ones: most of the beta = -pi column is held at the
+// source's theta_0 next to the polar axis (the sum above is exactly zero there: RADIAL rays, kr_device.hpp) and winds round it, its step set by the
+// max_phistep cap -- phi advances by ~0.4-0.6 rad per step, to -12 389 rad on the longest ray -- which is why they get SIMDs of their own (HOG launch).
 KR_DEV bool ill_conditioned(double k, double h, double Q, double theta, double a)
 {
     double sn, cs;
@@ -365,8 +408,8 @@ KR_DEV bool ill_conditioned(double k, double h, double Q, double theta, double a
 }
 
 // wave-aggregated append; ill-conditioned rays are rare (a column / a row of the source grid), so are the atomics.
-// mask: 0 = main launch, 1 = listed (strict side launch), 2 = ill-conditioned but the list is full (strict overflow launch)
-KR_DEV unsigned char classify_append(bool strict, long long i, int* __restrict__ list_strict, unsigned long long* __restrict__ n_strict)
+// mask: 0 = main launch, 1 = listed (strict side launch), 2 = ill-conditioned but its list is full (strict overflow launch)
+KR_DEV unsigned char classify_append(bool strict, long long i, int* __restrict__ list_strict, unsigned long long* __restrict__ n_strict, unsigned long long* __restrict__ overflowed)
 {
     const unsigned long long m = __ballot(strict);
     unsigned char mine = 0;
@@ -379,7 +422,7 @@ KR_DEV unsigned char classify_append(bool strict, long long i, int* __restrict__
         if (strict) {
             const unsigned long long slot = base + __popcll(m & ((1ull << lane) - 1));
             if (slot < (unsigned long long) kListCap) { list_strict[slot] = (int) i; mine = 1; }
-            else mine = 2;
+            else { *overflowed = 1; mine = 2; }
         }
     }
     return mine;
@@ -387,15 +430,25 @@ KR_DEV unsigned char classify_append(bool strict, long long i, int* __restrict__
 
 __global__ void __launch_bounds__(kBlock)
 classify_kernel(const kr_ray_f64* __restrict__ rays, long long n, double a, unsigned char* __restrict__ strict_mask, int* __restrict__ list_strict,
-                unsigned long long* __restrict__ n_strict)
+                unsigned long long* __restrict__ split_words, bool radial_lists, double theta_lo, double theta_hi)
 {
     // one ray per work-item: the pass is a 4-field gather over 144-byte records, so it wants every load in flight at once
     const long long i = blockIdx.x * (long long) kBlock + threadIdx.x;
     if (i >= n) return;
     const kr_ray_f64* ray = &rays[i];
-    bool strict = false;
+    bool strict = false, radial = false;
     if (ray->steps >= 0) strict = ill_conditioned(ray->k, ray->h, ray->Q, ray->theta, a);       // unused slots (steps == -1) are skipped by either launch
-    strict_mask[i] = classify_append(strict, i, list_strict, n_strict);
+    // radial_lists (the trace's side launch has radial waves): the flagged rays whose polar numerator is exactly zero at the state they are stored
+    // in -- a ray that has been traced part of its way included: the proof needs k, h, Q and theta only -- go to the second list.  The lane that
+    // takes such a ray decides again (radial_claim): this choice only says which waves a ray rides on.
+    if (strict && radial_lists) {
+        double sn, cs;
+        kr_sincos<true>(ray->theta, sn, cs);
+        radial = ray_is_radial(ray->k, ray->h, ray->Q, ray->r, ray->theta, a, theta_lo, theta_hi, sn, cs, lean_recip(sn));
+    }
+    const unsigned char general = classify_append(strict && !radial, i, list_strict, split_words + kFlagged, split_words + kListsOverflowed);
+    const unsigned char listed = classify_append(radial, i, list_strict + kListCap, split_words + kRadial, split_words + kListsOverflowed);
+    strict_mask[i] = general | listed;
 }
 
 // ---- host side ---------------------------------------------------------------------------------------
@@ -408,7 +461,7 @@ struct Workspace {
     int cus = 0;
     unsigned long long* counters = nullptr;      // device: kCounterBlocks x kCounters
     unsigned long long* h_counters = nullptr;    // pinned host copy, filled by an async copy at the end of the call
-    int* list = nullptr;                         // device: kListCap ray indices
+    int* list = nullptr;                         // device: 2 x kListCap ray indices (the general list, then the radial one)
     unsigned char* mask = nullptr;               // device: one byte per ray
     int64_t mask_capacity = 0;
     std::vector<void*> retired;                  // outgrown masks (workspace_mask_reserve)
@@ -510,7 +563,7 @@ int workspace_create(int dev, Workspace** out)
 #define KR_WS(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return fail(kr::hip_fail(e__, #call, __FILE__, __LINE__)); } while (0)
     KR_WS(hipMalloc((void**) &w->counters, kCounterBytes));
     KR_WS(hipHostMalloc((void**) &w->h_counters, kCounterBytes, hipHostMallocDefault));
-    KR_WS(hipMalloc((void**) &w->list, kListCap * sizeof(int)));
+    KR_WS(hipMalloc((void**) &w->list, 2 * kListCap * sizeof(int)));
     for (hipEvent_t* timed : {&w->ev0, &w->ev1, &w->ev_strict0, &w->ev_strict1, &w->ev_main0, &w->ev_main1}) KR_WS(hipEventCreate(timed));
     for (hipEvent_t* untimed : {&w->ev_classified, &w->done, &w->ev_in}) KR_WS(hipEventCreateWithFlags(untimed, hipEventDisableTiming));
     hipDeviceProp_t prop;
@@ -674,13 +727,15 @@ int launch_multi_f64(int integrator, bool dest, const TraceDesc<double>* d_descs
 // (its workgroups read the count and leave).
 struct SplitPlan {
     TraceDesc<double> side;           // n_mode 1: the first min(flagged, side.n) list entries; side.n = what the list can hold of this trace
+    TraceDesc<double> radial;         // the same over the list of radial rays, if has_radial (else that list stays empty)
     TraceDesc<double> main;           // every ray whose mask byte is 0
-    TraceDesc<double> overflow;       // n_mode 2: the rays with mask byte 2, if the list overflowed
-    bool has_overflow = false;        // the list can overflow at all (n > kListCap): without it there is no third launch
+    TraceDesc<double> overflow;       // n_mode 2: the rays with mask byte 2, if a list overflowed
+    bool has_overflow = false;        // a list can overflow at all (n > kListCap): without it there is no third launch
+    bool has_radial = false;          // the side launch has radial waves (trace_side_kernel): strict Euler / RK4 with a theta-limit stop, not in a merged batch
 };
 
 // the three launches of one split trace over the workspace's list, mask and counter blocks (the mask is grown here if need be)
-int plan_split(const kr_params* p, kr_ray_f64* rays, int64_t n, int steplim, Workspace* ws, SplitPlan* plan)
+int plan_split(const kr_params* p, kr_ray_f64* rays, int64_t n, int steplim, Workspace* ws, SplitPlan* plan, bool radial_waves)
 {
     if (n > 0x7fffffff) { set_error("kr_trace: the split path indexes rays with 32 bits"); return KR_EINVAL; }
     const int rc = workspace_mask_reserve(ws, n);
@@ -693,11 +748,17 @@ int plan_split(const kr_params* p, kr_ray_f64* rays, int64_t n, int steplim, Wor
     plan->side.list = ws->list;
     plan->side.n_ptr = flagged;
     plan->side.n_mode = 1;
+    plan->radial = plan->side;
+    plan->radial.counters = block(ws, kRadialBlock);
+    plan->radial.list = ws->list + kListCap;
+    plan->radial.n_ptr = block(ws, kSplitBlock) + kRadial;
+    // KR_NO_RADIAL=1 keeps every flagged ray on the general waves (A/B and bit-identity tests)
+    plan->has_radial = radial_waves && p->integrator != KR_RK45 && p->stop_kind == KR_STOP_THETA && !getenv("KR_NO_RADIAL");
     plan->main.counters = block(ws, kMainBlock);
     plan->main.mask = ws->mask;
     plan->main.mask_want = 0;
     plan->overflow.counters = block(ws, kOverflowBlock);
-    plan->overflow.n_ptr = flagged;
+    plan->overflow.n_ptr = block(ws, kSplitBlock) + kListsOverflowed;
     plan->overflow.n_mode = 2;
     plan->overflow.mask = ws->mask;
     plan->overflow.mask_want = 2;
@@ -710,7 +771,8 @@ int enqueue_classify(const SplitPlan& plan, Workspace* ws, hipStream_t stream)
 {
     const long long n = plan.main.n;
     const int cgrid = (int) ((n + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL(classify_kernel, dim3(cgrid), dim3(kBlock), 0, stream, plan.main.rays, n, plan.main.c.a, ws->mask, ws->list, block(ws, kSplitBlock) + kFlagged);
+    hipLaunchKernelGGL(classify_kernel, dim3(cgrid), dim3(kBlock), 0, stream, plan.main.rays, n, plan.main.c.a, ws->mask, ws->list, block(ws, kSplitBlock), plan.has_radial,
+                       plan.main.c.theta_lo, plan.main.c.theta_hi);
     KR_HIP(hipGetLastError());
     return KR_OK;
 }
@@ -765,7 +827,7 @@ struct Pending {
 int split_front(Pending& t)
 {
     Workspace* ws = t.ws;
-    int rc = plan_split(t.p, (kr_ray_f64*) t.d_rays, t.n, t.steplim, ws, &t.plan);
+    int rc = plan_split(t.p, (kr_ray_f64*) t.d_rays, t.n, t.steplim, ws, &t.plan, true);
     if (rc != KR_OK) return rc;
     rc = enqueue_classify(t.plan, ws, t.stream);
     if (rc != KR_OK) return rc;
@@ -773,8 +835,20 @@ int split_front(Pending& t)
     KR_HIP(hipEventRecord(ws->ev_strict0, t.stream));
     // strict side launch: one wave, alone on its SIMD, per 64 listed rays, on at most half of the chip
     const int grid = (int) std::max<int64_t>(1, std::min<int64_t>((t.plan.side.n + kTraceBlock - 1) / kTraceBlock, (int64_t) (ws->cus / 2) * 4));
-    rc = launch_f64<false, true>(t.p, t.plan.side, GridPolicy::exactly(grid), ws->cus, t.stream);
-    if (rc != KR_OK) return rc;
+    if (t.plan.has_radial) {
+        // ... of either kind: the radial waves first (theirs are the longest rays), each kind on at most a quarter of the chip
+        const int each = std::max(1, std::min(grid, (ws->cus / 4) * 4));
+        const TraceDesc<double>& g = t.plan.side, & q = t.plan.radial;
+        auto side = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(2 * each), dim3(kTraceBlock), 0, t.stream, g.rays, g.n, g.c, g.counters, q.counters, g.list, q.list, g.n_ptr, q.n_ptr, each);
+        };
+        if (t.p->integrator == KR_EULER) side(trace_side_kernel<KR_EULER, KR_REFILL_MIN>);
+        else side(trace_side_kernel<KR_RK4, KR_REFILL_MIN>);
+        KR_HIP(hipGetLastError());
+    } else {
+        rc = launch_f64<false, true>(t.p, t.plan.side, GridPolicy::exactly(grid), ws->cus, t.stream);
+        if (rc != KR_OK) return rc;
+    }
     KR_HIP(hipEventRecord(ws->ev_strict1, t.stream));
     ws->split = true;
     return KR_OK;
@@ -930,7 +1004,7 @@ int merged_batch(std::vector<Pending>& ts, bool hybrid)
         Pending& t = ts[i];
         Workspace* ws = t.ws;
         ws->side_stream = side;
-        rc = plan_split(t.p, (kr_ray_f64*) t.d_rays, t.n, t.steplim, ws, &t.plan);
+        rc = plan_split(t.p, (kr_ray_f64*) t.d_rays, t.n, t.steplim, ws, &t.plan, false);      // (merged side launches have no radial waves)
         if (rc == KR_OK) rc = begin_trace(ws, primary);
         if (rc == KR_OK) rc = enqueue_classify(t.plan, ws, primary);
         if (rc != KR_OK) return rc;
@@ -1030,20 +1104,23 @@ int trace_wait(void* ticket, kr_stats* stats)
     auto body = [&]() -> int {
         KR_HIP(hipEventSynchronize(ws->done));
         if (!stats) return KR_OK;
-        const unsigned long long* mainb = host_block(ws, kMainBlock), * side = host_block(ws, kSideBlock), * over = host_block(ws, kOverflowBlock);
+        const unsigned long long* mainb = host_block(ws, kMainBlock), * over = host_block(ws, kOverflowBlock);
+        unsigned long long side[kCounterWords];             // the side launch: its general and its radial waves
+        for (int i = 0; i < kCounterWords; i++) side[i] = host_block(ws, kSideBlock)[i] + host_block(ws, kRadialBlock)[i];
+        side[kLongest] = std::max(host_block(ws, kSideBlock)[kLongest], host_block(ws, kRadialBlock)[kLongest]);
         unsigned long long h[kCounterWords];
         for (int i = 0; i < kCounterWords; i++) h[i] = mainb[i] + side[i] + over[i];
         h[kLongest] = std::max(mainb[kLongest], std::max(side[kLongest], over[kLongest]));      // a maximum, not a sum
 #if KR_OCC_STATS
-        for (CounterBlock b : {kMainBlock, kSideBlock, kOverflowBlock}) {
+        for (CounterBlock b : {kMainBlock, kSideBlock, kOverflowBlock, kRadialBlock}) {
             const unsigned long long* q = host_block(ws, b);
-            if (q[8]) std::fprintf(stderr, "kr_occ: launch %d (0 main, 1 strict side, 2 overflow): steps %llu wave_iters %llu step-loop lane occupancy %.4f | after queue exhaustion: "
+            if (q[8]) std::fprintf(stderr, "kr_occ: launch %d (0 main, 1 strict side, 2 overflow, 4 radial side): steps %llu wave_iters %llu step-loop lane occupancy %.4f | after queue exhaustion: "
                                    "wave_iters %llu (%.2f %%) lane occupancy %.4f | refills %llu lanes/refill %.2f | longest ray %llu steps\n", (int) b, q[kSteps], q[8], (double) q[kSteps] / (64.0 * q[8]), q[9],
                                    100.0 * q[9] / q[8], q[9] ? (double) q[10] / (64.0 * q[9]) : 0.0, q[11], q[11] ? (double) q[12] / q[11] : 0.0, q[kLongest]);
         }
 #endif
         stats->rays_total = ws->n;
-        stats->rays_strict_side = (int64_t) host_block(ws, kSplitBlock)[kFlagged];
+        stats->rays_strict_side = (int64_t) (host_block(ws, kSplitBlock)[kFlagged] + host_block(ws, kSplitBlock)[kRadial]);
         stats->rays_traced = (int64_t) h[kTraced];
         stats->steps_total = (int64_t) h[kSteps];
         stats->rk45_attempts = (int64_t) h[kAttempts];
