@@ -7,6 +7,7 @@
 #include <stdexcept>
 #include <vector>
 
+#include "kr_trace.h"
 #include "raytracer/imageplane.h"
 #include "raytracer/pointsource.h"
 #include "raytracer/ray_destination.h"
@@ -58,6 +59,67 @@ int main(int argc, char** argv)
         int traced = 0;
         for (int i = 0; i < a.get_count(); i++) traced += a.rays[i].steps > 0;
         CHECK(traced > 1900000, "traced %d", traced);
+        std::printf(failures ? "FAIL\n" : "PASS\n");
+        return failures ? 1 : 0;
+    }
+
+    // `host_api_test step-control`: the constructor's tol and the three setters reach the kernels as the kr_params fields of the C ABI.  A source run
+    // through the class must leave, bit for bit, the records of kr_trace_f64 called with the same kr_params on the same initial rays -- under
+    // tol = 7, set_max_tstep(0.3, 20), set_max_phistep(0.01), set_boundary(3.0), and again after set_boundary() has put the event horizon back.
+    // set_precision(1, 1) changes nothing: the reference's setter assigns its parameters to themselves, and that no-op is part of the contract.
+    if (argc > 1 && !std::strcmp(argv[1], "step-control")) {
+        static_assert(sizeof(Ray<double>) == sizeof(kr_ray_f64), "Ray<double> is the C ABI's record");
+        for (int pass = 0; pass < 2; pass++) {
+            PointSource<double> a(pos, 0.0, spin, 7.0, 0.05, 0.05, -0.995, 0.995, -M_PI, M_PI);
+            a.redshift_start();
+            std::vector<kr_ray_f64> direct(a.get_count());
+            std::memcpy(direct.data(), a.rays, sizeof(kr_ray_f64) * direct.size());
+            a.set_max_tstep(0.3, 20.0);
+            a.set_max_phistep(0.01);
+            a.set_boundary(3.0);
+            if (pass == 1) a.set_boundary();
+            a.set_precision(1.0, 1.0);
+            a.set_precision(1.0);
+            a.run_raytrace(Integrator::RK4, M_PI_2, 1000.0, 0);
+
+            kr_params p;
+            std::memset(&p, 0, sizeof p);
+            p.spin = spin;
+            p.horizon = pass == 0 ? 3.0 : kr_kerr_horizon(spin);
+            p.precision = 7.0;
+            p.theta_precision = THETA_PRECISION;
+            p.max_tstep = 0.3;
+            p.maxtstep_rlim = 20.0;
+            p.max_phistep = 0.01;
+            p.rk45_tol = 1e-8;
+            p.r_max = 1000.0;
+            p.theta_max = M_PI_2;
+            p.integrator = KR_RK4;
+            p.stop_kind = KR_STOP_THETA;
+            p.steplim = -1;
+            p.flags = KR_FLAG_HYBRID;             // the class's arithmetic for the theta-limit overloads (KRTRACE_ARITHMETIC unset)
+            CHECK(a.calculate_horizon() == kr_kerr_horizon(spin), "calculate_horizon() %.17g vs kr_kerr_horizon %.17g", a.calculate_horizon(), kr_kerr_horizon(spin));
+            const int rc = kr_trace_f64(&p, direct.data(), (int64_t) direct.size(), nullptr);
+            CHECK(rc == 0, "kr_trace_f64: %d (%s)", rc, kr_last_error());
+            int live = 0, differ = 0, deep = 0;
+            for (int i = 0; i < a.get_count(); i++) {
+                if (direct[i].steps == -1) { CHECK(a.rays[i].steps == -1, "ray %d: unused slot was traced", i); continue; }
+                ++live;
+                // (a ray that ends with every coordinate NaN is the same ray whatever the NaN's sign bit)
+                const double* x = &a.rays[i].t; const double* y = &direct[i].t;
+                bool same = a.rays[i].steps == direct[i].steps && a.rays[i].status == direct[i].status && a.rays[i].rdot_sign == direct[i].rdot_sign &&
+                            a.rays[i].thetadot_sign == direct[i].thetadot_sign && a.rays[i].rdot_flips == direct[i].rdot_flips &&
+                            a.rays[i].equatorial_crossings == direct[i].equatorial_crossings;
+                for (int f = 0; f < 13; f++) same = same && (!std::memcmp(x + f, y + f, sizeof(double)) || (std::isnan(x[f]) && std::isnan(y[f])));
+                if (!same && differ++ < 5) std::printf("pass %d ray %d: class steps %d r %.17g, direct steps %d r %.17g\n", pass, i, a.rays[i].steps, a.rays[i].r, direct[i].steps, direct[i].r);
+                if (direct[i].r < 2.9) ++deep;
+            }
+            CHECK(live == 5040, "pass %d: %d live rays", pass, live);
+            CHECK(differ == 0, "pass %d: %d of %d records differ from kr_trace_f64 with the same kr_params", pass, differ, live);
+            // the boundary is felt: while it is set a ray stops within a step of r = 3 (the MIN_STEP floor carries it just across), none goes on
+            // towards the event horizon; once that is back, many do
+            CHECK(pass == 0 ? deep == 0 : deep > 100, "pass %d: %d rays ended inside r = 2.9", pass, deep);
+        }
         std::printf(failures ? "FAIL\n" : "PASS\n");
         return failures ? 1 : 0;
     }

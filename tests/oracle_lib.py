@@ -171,11 +171,11 @@ class RefSource:
             pos = (C.c_double * 4)(*spec.pos)
             self.h = self.lib.ref_pointsource_new(pos, spec.V, spec.spin, spec.tol, spec.dcosalpha, spec.dbeta,
                                                   spec.cosalpha0, spec.cosalphamax, spec.beta0, spec.betamax, spec.E)
-            self.is_imageplane = False
+            self.is_imageplane, self.precision = False, spec.tol
         else:
             self.h = self.lib.ref_imageplane_new(spec.dist, spec.inc_deg, spec.x0, spec.xmax, spec.dx, spec.y0,
                                                  spec.ymax, spec.dy, spec.spin, spec.phi0, spec.precision)
-            self.is_imageplane = True
+            self.is_imageplane, self.precision = True, spec.precision
         self.n = self.lib.ref_count(self.h)
         buf = (C.c_char * (self.n * capi.RAY_F64.itemsize)).from_address(self.lib.ref_rays(self.h))
         self.rays = np.frombuffer(buf, dtype=capi.RAY_F64)   # a VIEW of the reference's rays[]
@@ -200,6 +200,10 @@ class RefSource:
 
     def run(self, params):
         lib = self.lib
+        # the reference takes precision through its constructor only (set_precision assigns its parameters to themselves)
+        assert params.precision == self.precision, (params.precision, self.precision)
+        # set_boundary(): an inner radius other than the event horizon; no argument (r <= 0) puts the horizon back
+        lib.ref_set_boundary(self.h, params.horizon if params.horizon != capi.default_params(params.spin).horizon else -1.0)
         lib.ref_set_rk45_tol(self.h, params.rk45_tol)
         lib.ref_set_max_tstep(self.h, params.max_tstep, params.maxtstep_rlim)
         lib.ref_set_max_phistep(self.h, params.max_phistep)

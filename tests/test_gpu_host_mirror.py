@@ -17,6 +17,15 @@ def test_host_api_program():
     assert r.returncode == 0 and r.stdout.strip().endswith("PASS"), r.stdout[-3000:] + r.stderr[-1000:]
 
 
+def test_class_setters_reach_the_kernels():
+    """`host_api_test step-control`: a PointSource<double> built with tol = 7, then set_max_tstep(0.3, 20), set_max_phistep(0.01), set_boundary(3.0),
+    leaves the records of kr_trace_f64 called with those kr_params on the same rays, bit for bit; set_boundary() with no argument puts the event
+    horizon back; set_precision() changes nothing, as in the reference (tests/step_control_cases.py has the regimes these values come from)."""
+    d = os.path.join(gc.ROOT, "tests", "cpp")
+    r = subprocess.run([os.path.join(d, "host_api_test"), "step-control"], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and r.stdout.strip().endswith("PASS"), r.stdout[-3000:] + r.stderr[-1000:]
+
+
 def test_krtrace_steplim_environment_knob():
     """KRTRACE_STEPLIM bounds the rays of an unchanged program where it passes no step limit itself ('one ray is one sequential chain')."""
     d = os.path.join(gc.ROOT, "tests", "cpp")

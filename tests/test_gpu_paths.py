@@ -10,6 +10,7 @@ import pytest
 import golden_cases as gc
 import parity
 import paths_rules as pr
+import step_control_cases as sc
 from raytrace_cpu_amd import api, capi
 
 pytestmark = pytest.mark.gpu
@@ -88,11 +89,16 @@ def test_lanes_are_refilled_from_the_queue():
 CONSISTENCY = [("ps_h10", "euler"), ("ps_h10", "rk4"), ("ip15", "rk4"), ("ip15", "rk4_isco"), ("ip15", "rk4_plane"), ("ps_h5", "rk4_flatdisc"), ("ps_h5", "rk4_steplim300")]
 
 
-@pytest.mark.parametrize("case,run", CONSISTENCY, ids=[f"{c}-{r}" for c, r in CONSISTENCY])
-def test_recording_is_the_strict_trace_with_rows(case, run):
+# ... and off the default step-control parameters (the recorder reuses the strict step): kr_params overrides on top of a golden run
+CONSISTENCY_OVERRIDES = {("ps_h10", "rk4", "tight_caps"): sc.REGIMES["tight_caps"], ("ps_h10", "rk4", "boundary"): sc.REGIMES["boundary"]}
+CONSISTENCY_RUNS = [(c, r, None) for c, r in CONSISTENCY] + list(CONSISTENCY_OVERRIDES)
+
+
+@pytest.mark.parametrize("case,run,regime", CONSISTENCY_RUNS, ids=[f"{c}-{r}" + (f"-{g}" if g else "") for c, r, g in CONSISTENCY_RUNS])
+def test_recording_is_the_strict_trace_with_rows(case, run, regime):
     """No window, on an existing golden init: a recording ends with the records of api.trace(flags = 0), its write_step = 7 rows are every seventh
     write_step = 1 row, and a ray that ended by the loop condition has its final (t, r, theta, phi) as its last row -- all bit for bit."""
-    p = capi.copy_params(gc.cases()[case]["runs"][run], flags=0)
+    p = capi.copy_params(gc.cases()[case]["runs"][run], flags=0, **(CONSISTENCY_OVERRIDES[case, run, regime] if regime else {}))
     init = np.load(gc.golden_path(case))["init"].copy()
     init["steps"][::17] = -1                       # rays the skip rule leaves out (raytracer.cpp:91-92) ...
     init["steps"][5] = capi.STEPLIM + 1            # ... on either side of it
@@ -130,7 +136,7 @@ def test_recording_is_the_strict_trace_with_rows(case, run):
     # that catches every ray, or a step limit below the rays' lengths, may leave none, and then the other checks are what the case is for)
     if p.stop_kind == capi.STOP_THETA and p.steplim <= 0:
         assert n_checked_last > (~skipped).sum() // 2
-    print(f"paths consistency {case}/{run}: rays {int((~skipped).sum())}, rows ws=1 {len(rows1)}, ws=7 {len(rows7)}, steps {st1['steps_total']}, last-row checks {n_checked_last}")
+    print(f"paths consistency {case}/{run}{'/' + regime if regime else ''}: rays {int((~skipped).sum())}, rows ws=1 {len(rows1)}, ws=7 {len(rows7)}, steps {st1['steps_total']}, last-row checks {n_checked_last}")
 
 
 def test_count_pass_leaves_the_rays_alone_and_record_checks_its_slabs():

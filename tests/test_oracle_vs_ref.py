@@ -13,6 +13,7 @@ import pytest
 
 import golden_cases as gc
 import oracle_lib as ol
+import step_control_cases as sc
 from raytrace_cpu_amd import capi
 
 DIGESTS = os.path.join(gc.GOLDEN_DIR, "oracle_vs_ref_digests.json")
@@ -93,9 +94,32 @@ def _rk45_case(tol):
     return f"rk45_tolerance-{tol:g}", spec, p, (0.0, 0, 0)
 
 
+def _without_theta_precision(over):
+    return {k: v for k, v in over.items() if k != "theta_precision"}
+
+
+def _step_control_case(regime, method):
+    # the perf_test grid at h = 5 under a step-control regime (tests/step_control_cases.py)
+    grid = sc.lamp()
+    p = sc.grid_params(sc.DEFAULT, method, grid, **_without_theta_precision(sc.REGIMES[regime]))
+    return f"step_control-{regime}-m{method}", sc.source_spec(grid, p.precision), p, sc.redshift_start_args(grid)
+
+
+# the 33 x 33 image plane: a coarse precision with an inner boundary inside the photon orbit's reach, and both caps off
+PLANE_REGIMES = {"coarse_boundary": dict(precision=20.0, horizon=2.5), "caps_off": sc.REGIMES["caps_off"]}
+
+
+def _step_control_plane_case(regime, method):
+    grid = sc.plane33()
+    p = sc.grid_params(sc.DEFAULT, method, grid, **PLANE_REGIMES[regime])
+    return f"step_control-plane33-{regime}-m{method}", sc.source_spec(grid, p.precision), p, sc.redshift_start_args(grid)
+
+
 PERF = [(m, h) for h in (5.0, 10.0) for m in (capi.EULER, capi.RK4, capi.RK45)]
 IMAGEPLANE = [capi.EULER, capi.RK4]
 RK45_TOL = [1e-6, 1e-10]
+STEP_CONTROL = [(r, m) for r in sc.NAMES for m in (capi.EULER, capi.RK4, capi.RK45)]
+STEP_CONTROL_PLANE = [(r, m) for r in PLANE_REGIMES for m in IMAGEPLANE]
 
 
 @pytest.mark.parametrize("method", [capi.EULER, capi.RK4, capi.RK45])
@@ -116,12 +140,29 @@ def test_rk45_tolerance_bitwise(tol):
     _check(*_rk45_case(tol))
 
 
+@pytest.mark.parametrize("regime,method", STEP_CONTROL, ids=[f"{r}-m{m}" for r, m in STEP_CONTROL])
+def test_step_control_regimes_bitwise(regime, method):
+    """The oracle off the default step-control parameters: precision (the constructor's tol), set_max_tstep, set_max_phistep and set_boundary, each
+    moved to where the heuristic takes another branch.  theta_precision stays at its default here: the reference cannot vary it -- its set_precision
+    assigns its parameters to themselves (raytracer.h:169-178), which the host mirror copies on purpose -- so that the oracle divides by
+    theta_precision where the reference does (kr_oracle.c:276,359 against raytracer.cpp:227,858,1139,1353) is established by reading only."""
+    out = _check(*_step_control_case(regime, method))
+    assert len(out) == 5167 and (out["steps"] != -1).sum() == 5040
+
+
+@pytest.mark.parametrize("regime,method", STEP_CONTROL_PLANE, ids=[f"{r}-m{m}" for r, m in STEP_CONTROL_PLANE])
+def test_step_control_imageplane_33_bitwise(regime, method):
+    out = _check(*_step_control_plane_case(regime, method))
+    assert len(out) == 33 * 33
+
+
 def record():
     """Runs every case on the live compiled reference and writes its digests."""
     assert ol.ref() is not None, "compiled reference (oracle/_ref) not available"
     cases = {}
     for name, spec, p, start in ([_perf_case(m, h) for m, h in PERF] + [_imageplane_case(m) for m in IMAGEPLANE] +
-                                 [_rk45_case(t) for t in RK45_TOL]):
+                                 [_rk45_case(t) for t in RK45_TOL] + [_step_control_case(r, m) for r, m in STEP_CONTROL] +
+                                 [_step_control_plane_case(r, m) for r, m in STEP_CONTROL_PLANE]):
         cases[name] = field_digests(_ref_run(spec, p, start))
     with open(DIGESTS, "w") as fh:
         json.dump({"what": "SHA-256 per ray field of the compiled reference's rays after redshift_start + run_raytrace "
