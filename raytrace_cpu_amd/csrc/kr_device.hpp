@@ -18,6 +18,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/kr_trace.h"
 #include "kr_arith.hpp"
 
@@ -346,10 +348,16 @@ KR_DEV bool crossed_equator(T before, T after)
     return ((double) before < kPi2 && (double) after >= kPi2) || ((double) before > kPi2 && (double) after <= kPi2);
 }
 
+// What a lane keeps of its ray's constants besides the lane state, from the moment it takes the ray (trace_body): the instances that carry them hold
+// a FastRayConsts, every other instance an empty struct that nothing reads -- those kernels compile to what they were without it.
+struct NoRayConsts {};
+template <bool CARRIED> using RayConstsOf = std::conditional_t<CARRIED, FastRayConsts, NoRayConsts>;
+
 // One iteration of the Euler (raytracer.cpp:172-313) or RK4 (:799-943, :1080-1229) loop body.
 // Returns true when the ray has finished (break, or the loop condition no longer holds).
+// rayc: the ray's constant terms, filled where the lane took the ray -- the fast path reads them, the others are called without.
 template <typename T, bool RK4, bool USE_DEST, bool FAST, bool LONE = false>
-KR_DEV bool step_fixed(Lane<T>& s, const TraceConsts<T>& c)
+KR_DEV bool step_fixed(Lane<T>& s, const TraceConsts<T>& c, const FastRayConsts* rayc = nullptr)
 {
     const T a = c.a;
     ++s.steps;
@@ -360,7 +368,7 @@ KR_DEV bool step_fixed(Lane<T>& s, const TraceConsts<T>& c)
     if constexpr (FAST) {
         // (carrying sin / cos of the base point from step to step by angle addition was measured and rejected: it removes 7 of 406 vector instructions
         // per RK4 step but costs registers the stage code needs -- 63.2 ms against 62.7 at 1e7 rays, Euler 31.6 against 30.9; profiles/r03_ab_experiments.txt)
-        if (k1_with_flips_fast(s, a, aux)) return !(s.steps < c.steplim);
+        if (k1_with_flips_fast(s, a, *rayc, aux)) return !(s.steps < c.steplim);
         pt1 = s.pt; pr1 = s.pr; ptheta1 = s.ptheta; pphi1 = s.pphi;
         // The same heuristic (:855-871) with ONE quarter-rate instruction instead of four.  1 / |rdot| and 1 / |thetadot| come out of the
         // square roots that produced them (fast_sqrt); the time and azimuth caps, min(dt / |tdot|, dphi / |phidot|), share one reciprocal:
@@ -481,7 +489,7 @@ KR_DEV bool step_fixed(Lane<T>& s, const TraceConsts<T>& c)
                     } else {
                         kr_sincos_fast_f64(s.theta + dtheta, sn, cs);
                     }
-                    momentum_fast_sc(pt, pr, ptheta, pphi, s.k, s.h, s.Q, s.rdot_sign, s.thetadot_sign, r_stage, sn, cs, a);
+                    momentum_fast_sc(pt, pr, ptheta, pphi, s.k, s.h, s.Q, *rayc, s.rdot_sign, s.thetadot_sign, r_stage, sn, cs, a);
                 } else if constexpr (kNear) {
                     const T theta_stage = s.theta + dtheta;
                     within = within && (kr_abs(theta_stage) < T(KR_SMALL_ANGLE_LIMIT));

@@ -77,7 +77,31 @@ struct FastAux { double sin2theta, inv_rhosq, sn, cs, inv_abs_pr, inv_abs_ptheta
 // instance, and the same ray came out an ulp apart from the single-trace and the multi-trace kernels.
 struct FastPotentials { double N, R, inv_rho, s2, rhosq; };
 
-KR_DEV FastPotentials potentials_fast(double& pt, double& pphi, double k, double h, double Q, double r, double s, double c, double a)
+// What the potentials need of (k, h, Q, a) alone: constant along a ray.  The persistent kernels fill it ONCE, where a lane takes its ray
+// (kr_trace.hip: trace_body, beside energy_guard_set), and hand it to every step; the compiler shares such terms among the evaluations of one
+// step but cannot lift them out of a loop in which a lane changes its ray.  Each member is the expression potentials_fast used to evaluate in
+// place -- same operands, same order, every fused multiply-add written out -- so a record keeps its bits whichever way the terms reach it.
+// (-(h^2) and -(a h) stay negations at the point of use: source modifiers, no instruction.)
+struct FastRayConsts {
+    double ak, ah, a_ak;        // a k, a h, a (a k)
+    double h2, ak2;             // h^2, (a k)^2
+    double q_hmak;              // Q + (h - a k)^2
+};
+
+KR_DEV FastRayConsts fast_ray_consts(double k, double h, double Q, double a)
+{
+    FastRayConsts f;
+    f.ak = a * k;
+    f.ah = a * h;
+    f.a_ak = a * f.ak;
+    f.h2 = h * h;
+    f.ak2 = f.ak * f.ak;
+    const double hmak = h - f.ak;
+    f.q_hmak = __builtin_fma(hmak, hmak, Q);
+    return f;
+}
+
+KR_DEV FastPotentials potentials_fast(double& pt, double& pphi, double k, double h, double Q, const FastRayConsts& f, double r, double s, double c, double a)
 {
     const double s2 = s * s;
     const double c2 = c * c;
@@ -91,14 +115,13 @@ KR_DEV FastPotentials potentials_fast(double& pt, double& pphi, double k, double
     const double inv_rd = inv * s2;                // 1 / (rho^2 Delta)
     const double inv_rho = inv_rd * delta;         // 1 / rho^2
     const double inv_s2 = inv * rd;                // 1 / sin^2
-    const double ak = a * k, ah = a * h;           // (invariant along a ray, like h^2, k^2 a^2 and Q + (h - a k)^2 below: computed once per step)
-    const double P = __builtin_fma(r2a2, k, -ah);
-    pt = __builtin_fma(-(__builtin_fma(a * ak, s2, -ah)), inv_rho, (r2a2 * P) * inv_rd);
-    pphi = __builtin_fma(__builtin_fma(h, inv_s2, -ak), inv_rho, (a * P) * inv_rd);
+    // (a k, a h, a (a k), h^2, (a k)^2 and Q + (h - a k)^2 are invariant along a ray: FastRayConsts, computed once per ray)
+    const double P = __builtin_fma(r2a2, k, -f.ah);
+    pt = __builtin_fma(-(__builtin_fma(f.a_ak, s2, -f.ah)), inv_rho, (r2a2 * P) * inv_rd);
+    pphi = __builtin_fma(__builtin_fma(h, inv_s2, -f.ak), inv_rho, (a * P) * inv_rd);
     FastPotentials o;
-    o.N = __builtin_fma(c2, __builtin_fma(-(h * h), inv_s2, ak * ak), Q);
-    const double hmak = h - ak;
-    o.R = __builtin_fma(-delta, __builtin_fabs(o.N) - o.N, __builtin_fma(-delta, __builtin_fma(hmak, hmak, Q), P * P));
+    o.N = __builtin_fma(c2, __builtin_fma(-f.h2, inv_s2, f.ak2), Q);
+    o.R = __builtin_fma(-delta, __builtin_fabs(o.N) - o.N, __builtin_fma(-delta, f.q_hmak, P * P));
     o.inv_rho = inv_rho;
     o.s2 = s2;
     o.rhosq = rhosq;
@@ -106,10 +129,10 @@ KR_DEV FastPotentials potentials_fast(double& pt, double& pphi, double k, double
 }
 
 // momentum_from_consts (kerr.h:300-335)
-KR_DEV void momentum_fast_sc(double& pt, double& pr, double& ptheta, double& pphi, double k, double h, double Q, int rdot_sign,
+KR_DEV void momentum_fast_sc(double& pt, double& pr, double& ptheta, double& pphi, double k, double h, double Q, const FastRayConsts& f, int rdot_sign,
                              int thetadot_sign, double r, double s, double c, double a)
 {
-    const FastPotentials o = potentials_fast(pt, pphi, k, h, Q, r, s, c, a);
+    const FastPotentials o = potentials_fast(pt, pphi, k, h, Q, f, r, s, c, a);
     ptheta = fast_sqrt(o.N) * (o.inv_rho * thetadot_sign);
     pr = fast_sqrt(o.R) * (o.inv_rho * rdot_sign);
 }
@@ -117,9 +140,10 @@ KR_DEV void momentum_fast_sc(double& pt, double& pr, double& ptheta, double& pph
 KR_DEV void momentum_fast(double& pt, double& pr, double& ptheta, double& pphi, double k, double h, double Q, int rdot_sign,
                           int thetadot_sign, double r, double theta, double a)
 {
+    // (the entry that is given (k, h, Q) only -- eval<T, true>, i.e. the RK45 trial's stages: the ray's terms are formed here, per evaluation, as before)
     double s, c;
     kr_sincos_fast_f64(theta, s, c);
-    momentum_fast_sc(pt, pr, ptheta, pphi, k, h, Q, rdot_sign, thetadot_sign, r, s, c, a);
+    momentum_fast_sc(pt, pr, ptheta, pphi, k, h, Q, fast_ray_consts(k, h, Q, a), rdot_sign, thetadot_sign, r, s, c, a);
 }
 
 // sin/cos of theta0 + d from those of theta0 (the stages of one Runge-Kutta step sit within a few per cent of a radian of its
@@ -153,11 +177,11 @@ KR_DEV void sincos_near(double s0, double c0, double d, double& s, double& c)   
 }
 
 // k1 with the turning-point logic (see k1_with_flips) on the fast path
-KR_DEV bool k1_with_flips_fast(Lane<double>& s, double a, FastAux& aux)
+KR_DEV bool k1_with_flips_fast(Lane<double>& s, double a, const FastRayConsts& f, FastAux& aux)
 {
     double sn, c;
     kr_sincos_fast_f64(s.theta, sn, c);
-    const FastPotentials o = potentials_fast(s.pt, s.pphi, s.k, s.h, s.Q, s.r, sn, c, a);
+    const FastPotentials o = potentials_fast(s.pt, s.pphi, s.k, s.h, s.Q, f, s.r, sn, c, a);
     // thetadot^2 = N / rho^4 and rdot^2 = R / rho^4 have the signs of N and R
     if (o.N < 0 && s.theta_was_positive) {
         s.thetadot_sign = -s.thetadot_sign;

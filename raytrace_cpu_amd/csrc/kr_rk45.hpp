@@ -64,7 +64,7 @@ KR_DEV int creep_step(Lane<T>& s, const TraceConsts<T>& c, uint32_t& attempts, u
     bool confirmed;
     if constexpr (FAST) {
         FastAux aux;
-        confirmed = !k1_with_flips_fast(s, a, aux);
+        confirmed = !k1_with_flips_fast(s, a, fast_ray_consts(s.k, s.h, s.Q, a), aux);
         if (confirmed) {
             if (s.pt <= 0) s.status |= KR_STATUS_ERGO;
             const T two_r_rho = 2 * s.r * aux.inv_rhosq;
@@ -135,7 +135,7 @@ KR_DEV bool step_rk45(Lane<T>& s, const TraceConsts<T>& c, uint32_t& attempts, u
         T step_max;
         if constexpr (FAST) {
             FastAux aux;
-            if (k1_with_flips_fast(s, a, aux)) return !(s.steps < c.steplim);
+            if (k1_with_flips_fast(s, a, fast_ray_consts(s.k, s.h, s.Q, a), aux)) return !(s.steps < c.steplim);
             if (s.pt <= 0) s.status |= KR_STATUS_ERGO;
             const T two_r_rho = 2 * s.r * aux.inv_rhosq;
             if ((1 - two_r_rho) * s.pt + (two_r_rho * a * aux.sin2theta) * s.pphi < 0) s.status |= KR_STATUS_NEG_ENERGY;

@@ -139,6 +139,12 @@ KR_DEV void trace_body(typename RayOf<T>::type* __restrict__ rays, long long n, 
 
     Lane<T> s;
     [[maybe_unused]] RadialRay radial;      // RADIAL: the constants of this lane's ray (step_radial)
+    // The fast Euler / RK4 instances keep the terms of (k, h, Q, a) that the potentials need (kr_fast.hpp: FastRayConsts) beside the lane state, like
+    // `radial` above: computed once per ray instead of once per step.  (Not the fast RK45 instances: the trial's stages go through eval(), which forms
+    // the terms itself, and that kernel has no registers to spare at 2 waves per SIMD.)  Every other instance: an empty struct.
+    constexpr bool kRayConsts = FAST && sizeof(T) == 8 && METHOD != KR_RK45;
+    static_assert(!(RADIAL && FAST), "the radial waves call step_fixed without a ray's constant terms: strict arithmetic only");
+    [[maybe_unused]] RayConstsOf<kRayConsts> ray_consts;
     long long idx = -1;
     bool have = false;          // this lane holds a ray
     bool pend = false;          // this lane's ray has ended and is still in its registers: written out at the wave's next visit to the queue (or on exit)
@@ -228,6 +234,8 @@ KR_DEV void trace_body(typename RayOf<T>::type* __restrict__ rays, long long n, 
                         s.creep_mode = false;
                         s.fsal_valid = false;
                         energy_guard_set(s);
+                        // (the one place a lane takes a ray: its lanes only -- the others keep the terms of the rays they hold)
+                        if constexpr (kRayConsts) ray_consts = fast_ray_consts(s.k, s.h, s.Q, c.a);
                         if (METHOD == KR_RK45) rk45_seed(s, c);
                         if constexpr (RADIAL) radial_claim(s, c, radial);
                         if (!loop_cond<T, USE_DEST>(s, c)) {
@@ -257,7 +265,7 @@ KR_DEV void trace_body(typename RayOf<T>::type* __restrict__ rays, long long n, 
             if (have && !radial.general) fin = step_radial<METHOD == KR_RK4>(s, radial, c);
             const bool general = have && radial.general;
             if (__builtin_expect(__builtin_amdgcn_ballot_w64(general) != 0, false)) {
-                if (general) fin = step_fixed<T, METHOD == KR_RK4, USE_DEST, FAST, HOG>(s, c);
+                if (general) fin = step_fixed<T, METHOD == KR_RK4, USE_DEST, FAST, HOG>(s, c);      // (radial waves are strict: no ray constants)
             }
             if (fin) {
                 have = false;
@@ -265,7 +273,8 @@ KR_DEV void trace_body(typename RayOf<T>::type* __restrict__ rays, long long n, 
             }
         } else if (have) {
             bool fin;
-            if (METHOD == KR_EULER) fin = step_fixed<T, false, USE_DEST, FAST, HOG>(s, c);
+            if constexpr (kRayConsts) fin = step_fixed<T, METHOD == KR_RK4, USE_DEST, FAST, HOG>(s, c, &ray_consts);
+            else if (METHOD == KR_EULER) fin = step_fixed<T, false, USE_DEST, FAST, HOG>(s, c);
             else if (METHOD == KR_RK4) fin = step_fixed<T, true, USE_DEST, FAST, HOG>(s, c);
             else fin = step_rk45<T, USE_DEST, FAST, HOG>(s, c, my_attempts, my_rejects, my_stationary, my_creep, replay_batch);
             if (fin) {
