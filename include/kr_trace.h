@@ -180,7 +180,12 @@ typedef struct kr_imageplane {
     double spin, phi0, precision;
 } kr_imageplane;
 
-/* radial histogram of src/emissivity/emissivity.cpp:96-126 */
+/* radial histogram of src/emissivity/emissivity.cpp:96-126.  Per ray record:
+ *   filter   steps > 0, z = r cos(theta) < 1e-2, g > 0 with g = rays[].redshift, r >= r_isco.  A ray that passes counts in disc_count, binned or not.
+ *   index    q = log(r / r_min) / log(dr) (logbin) or (r - r_min) / dr, truncated toward zero like the reference's `(int) q` (emissivity.cpp:105):
+ *            the ray is binned iff -1 < q < nr, at bin (int) q -- so the band -1 < q <= 0 below the first edge belongs to bin 0, as in the reference.
+ *            The test is made on q itself: a NaN or out-of-range index (r_min <= 0 with logbin, dr == 0, an infinite quotient, one beyond the int
+ *            range) is not binned; on-disc still counts. */
 typedef struct kr_emis_bins {
     double r_min;            /* first bin edge */
     double dr;               /* logbin: ratio between edges; linear: width */
@@ -192,7 +197,13 @@ typedef struct kr_emis_bins {
     int32_t logbin;
 } kr_emis_bins;
 
-/* image accumulation of src/imageplane/imageplane_disc_image.cpp:122-161 */
+/* image accumulation of src/imageplane/imageplane_disc_image.cpp:122-161.  Per ray record:
+ *   filter   steps > 0, z = r cos(theta) < 1e-2, r_isco <= r < r_disc, g > 0 with g = rays[].redshift
+ *   pixel    qx = (alpha - x0) / img_dx, qy = (beta - y0) / img_dy with alpha, beta = rays[].alpha, rays[].beta, each truncated toward zero like the
+ *            reference's `(int) q` (:134-135): the ray is counted iff -1 < qx < img_nx and -1 < qy < img_ny -- the band -1 < q <= 0 below the first
+ *            edge belongs to column / row 0, as in the reference -- in pixel [ix img_ny + iy], ix = (int) qx, iy = (int) qy, or with flip_image
+ *            iy = img_ny - 1 - (int) qy.  The test is made on qx, qy themselves: a NaN or out-of-range index (NaN or infinite alpha / beta, one
+ *            beyond the int range) is not binned, and such a ray does not count in disc_count, which counts the rays that reached a pixel. */
 typedef struct kr_image_bins {
     double x0, y0, img_dx, img_dy;
     double r_isco, r_disc;

@@ -838,8 +838,11 @@ void kro_reduce_emissivity_f64(const kr_emis_bins* b, const kr_ray_f64* rays, in
         if (ray->steps > 0) {
             const double z = ray->r * cos(ray->theta);     /* cartesian(), kerr.h:55 */
             if (z < 1E-2 && ray->redshift > 0 && ray->r >= b->r_isco) {
-                const int ir = b->logbin ? (int) (log(ray->r / b->r_min) / log(b->dr)) : (int) ((ray->r - b->r_min) / b->dr);
-                if (ir >= 0 && ir < b->nr) {
+                /* the index rule on the floating quotient: (int) q followed by 0 <= ir < nr keeps -1 < q < nr (the band (-1, 0] truncates to 0)
+                 * and drops NaN and every q outside the int range, whose conversion is undefined (INT_MIN on x86) */
+                const double q = b->logbin ? log(ray->r / b->r_min) / log(b->dr) : (ray->r - b->r_min) / b->dr;
+                if (q > -1 && q < b->nr) {
+                    const int ir = (int) q;
                     ++count[ir];
                     flux[ir] += 1 / (b->num_primary_rays * pow(ray->redshift, 1));
                     emis[ir] += 1 / pow(ray->redshift, b->gamma);
@@ -875,10 +878,11 @@ void kro_reduce_image_f64(const kr_image_bins* b, const kr_ray_f64* rays, int64_
             const double z = ray->r * cos(ray->theta);
             if (z < 1E-2 && ray->r >= b->r_isco && ray->r < b->r_disc && ray->redshift > 0) {
                 const double x = ray->alpha, y = ray->beta;
-                int ix = (int) ((x - b->x0) / b->img_dx);
-                int iy = (int) ((y - b->y0) / b->img_dy);
-                if (b->flip_image) iy = b->img_ny - iy - 1;
-                if (ix >= 0 && ix < b->img_nx && iy >= 0 && iy < b->img_ny) {
+                /* the same rule per axis, tested before the conversion (see kro_reduce_emissivity_f64) */
+                const double qx = (x - b->x0) / b->img_dx, qy = (y - b->y0) / b->img_dy;
+                if (qx > -1 && qx < b->img_nx && qy > -1 && qy < b->img_ny) {
+                    const int ix = (int) qx;
+                    const int iy = b->flip_image ? b->img_ny - (int) qy - 1 : (int) qy;
                     const int64_t px = (int64_t) ix * b->img_ny + iy;
                     ++nrays[px];
                     const double e = powerlaw3(ray->r, b->q1, b->rb1, b->q2, b->rb2, b->q3);

@@ -257,10 +257,11 @@ KR_DEV unsigned image_accumulate(double* planes, long long npix, const kr_image_
     if (!(steps > 0)) return 0;
     const double z = r * kr_cos(theta);
     if (!(z < 1E-2 && r >= b.r_isco && r < b.r_disc && g > 0)) return 0;
-    int ix = (int) ((alpha - b.x0) / b.img_dx);
-    int iy = (int) ((beta - b.y0) / b.img_dy);
-    if (b.flip_image) iy = b.img_ny - iy - 1;
-    if (!(ix >= 0 && ix < b.img_nx && iy >= 0 && iy < b.img_ny)) return 0;
+    // the index rule of kr_image_bins per axis, on the floating quotient before the conversion (see emissivity_accumulate): NaN fails too
+    const double qx = (alpha - b.x0) / b.img_dx, qy = (beta - b.y0) / b.img_dy;
+    if (!(qx > -1 && qx < b.img_nx && qy > -1 && qy < b.img_ny)) return 0;
+    const int ix = (int) qx;
+    const int iy = b.flip_image ? b.img_ny - (int) qy - 1 : (int) qy;
     const long long px = (long long) ix * b.img_ny + iy;
     const double e = powerlaw3(r, b.q1, b.rb1, b.q2, b.rb2, b.q3);
     atomicAdd(&planes[px], 1.0);

@@ -291,8 +291,12 @@ KR_DEV void emissivity_accumulate(double* acc, const kr_emis_bins& b, double log
     const int nr = b.nr;
     const double z = r * kr_cos(theta);         // cartesian(), kerr.h:55
     if (z < 1E-2 && g > 0 && r >= b.r_isco) {
-        const int ir = b.logbin ? (int) (kr_log(r / b.r_min) / log_dr) : (int) ((r - b.r_min) / b.dr);
-        if (ir >= 0 && ir < nr) {
+        // the index rule of kr_emis_bins, decided on the floating quotient BEFORE the conversion (as kr_line.hip does): -1 < q < nr is what the
+        // reference's `(int) q` followed by 0 <= ir < nr keeps on the CPU -- the band (-1, 0] truncates to 0 -- and a NaN, infinite or out-of-int-range
+        // q fails it, where v_cvt_i32_f64 would saturate and turn NaN into 0, i.e. into bin 0
+        const double q = b.logbin ? kr_log(r / b.r_min) / log_dr : (r - b.r_min) / b.dr;
+        if (q > -1 && q < nr) {
+            const int ir = (int) q;
             atomicAdd(&acc[ir], 1.0);
             atomicAdd(&acc[nr + ir], 1 / (b.num_primary_rays * kr_pow(g, 1.0)));
             atomicAdd(&acc[2 * nr + ir], 1 / kr_pow(g, b.gamma));
