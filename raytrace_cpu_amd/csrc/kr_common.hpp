@@ -69,6 +69,8 @@ int trace_poll(void* ticket, int64_t* rays_started, int32_t* finished);
 void trace_release(void* ticket);
 void side_stream_forget(hipStream_t user);
 int trace_shutdown();
+int validate_run(const kr_params* p, const char* who);   // integrator / stop_kind / Euler-with-destination; message "<who>: ..."
+int device_cus(int dev, int* cus);
 void angle_values(int kind, double x0, double dx, int n, double* sincos_pairs);     // kr_post.hip; kind 0: x = cos(alpha); 1: x = beta
 
 }  // namespace kr

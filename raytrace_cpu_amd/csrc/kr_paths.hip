@@ -1,12 +1,11 @@
 // kr_paths.hip -- the per-step trajectory dump of Raytracer<T>::run_raytrace(..., outfile, write_step, write_rmax, write_rmin, write_cartesian)
 // (reference raytracer.cpp:86-100; the write rule :293-312 Euler, :923-942 and :1209-1228 RK4) as two passes of a persistent gfx950 kernel.
 //
-// fp64, strict arithmetic, Euler and RK4 only.  A recorded ray is integrated by the very step function a flags = 0 trace uses
-// (step_fixed<double, RK4, USE_DEST, false>, kr_device.hpp), so it takes the same steps and ends with the same record, bit for bit.
-//
-// Mapping onto the hardware: one ray per lane, persistent single-wave workgroups that refill their free lanes from a global queue through
-// one wave-aggregated atomicAdd (ballot + popcount), as the trace does -- rays need 60 ... 40 000 steps, and a launch without refill would
-// idle 63 of 64 lanes on its longest ray.
+// fp64, strict arithmetic, Euler and RK4 only.  The kernel is the trace's own persistent-wave loop (trace_body, kr_trace_loop.hpp: one ray per lane,
+// single-wave workgroups that refill their free lanes from a global queue) in its strict, non-HOG instance, with a recorder (PathRecorder below)
+// called at the loop's hook points: a recorded ray is claimed, reset, stepped (step_fixed<double, RK4, USE_DEST, false>, kr_device.hpp) and stored by
+// the very code a flags = 0 trace runs, so it takes the same steps and ends with the same record, bit for bit.  This file has no loop of its own;
+// the recorder only counts and stores rows, and may end a ray that leaves the window.
 //
 // Rows are stored compressed: ray i owns rows[offsets[i] .. offsets[i + 1]).  Two passes make that possible without a worst-case allocation:
 //   count   integrates every ray and stores only how many rows it writes (and whether it was traced at all); rays[] is not modified;
@@ -27,18 +26,14 @@
 #include <cstring>
 
 #include "kr_pass.hpp"
-#include "kr_ray_io.hpp"
+#include "kr_trace_loop.hpp"
 
 namespace kr {
 
 namespace {
 
-constexpr int kPathBlock = 64;        // one wave per workgroup: a wave gives its registers back when IT has finished (kr_trace.hip)
-constexpr int kPathRefillMin = 4;     // a wave goes back to the queue when this many of its lanes are free (kr_trace.hip, KR_REFILL_MIN)
 constexpr int kScanBlock = 1024;
-
-// device words of one pass: queue head, rays traced, steps, longest ray, rays whose row count differs from their slab
-enum PathWord { kPHead, kPTraced, kPSteps, kPLongest, kPMismatch, kPWords };
+constexpr int kPathWords = kRecorderWord + 1;      // the trace's counter words, then the rays whose row count differs from their slab
 
 struct PathWindow {
     double rmin, rmax;        // write_rmin, write_rmax: < 0 switches that side off
@@ -51,145 +46,81 @@ KR_DEV bool in_window(const PathWindow& w, double r)
     return (w.rmax < 0 || r < w.rmax) && (w.rmin < 0 || r > w.rmin);
 }
 
-KR_DEV unsigned long long wave_sum_u64(unsigned long long v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
-KR_DEV unsigned long long wave_max_u64(unsigned long long v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_down(v, off, 64);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
+// The recorder of trace_body (kr_trace_loop.hpp lists the hooks).
 // RECORD = false: the count pass.  offsets[i] receives ray i's row count (the scan below turns the counts into offsets), traced[i] (optional)
-// whether the ray passed the skip rule; rays[] is read only.
+// whether the ray passed the skip rule; rays[] is read only -- kStoresRays is false, so the instance has no store to it.
 // RECORD = true: offsets[0 .. n] are the scanned offsets; rows and the final ray records are stored.
+template <bool RECORD> struct PathRecorder {
+    static constexpr bool kActive = true, kStoresRays = RECORD;
+    PathWindow w;                     // the launch
+    long long* __restrict__ offsets; unsigned char* __restrict__ traced; double* __restrict__ rows; long long total_rows;
+    // this lane's ray
+    long long slab = 0, cap = 0;      // RECORD: its first row and how many it may write
+    int32_t n_rows = 0;               // rows it has written so far (write_started == n_rows > 0)
+    int32_t until_write = 0;          // iterations left until steps % write_step == 0
+    bool flip_armed = false; int32_t status_before = 0;       // before_step -> after_step
+    uint32_t mismatch = 0;            // this lane's rays whose row count differed from their slab (32 bits: one register less across the step)
+
+    KR_DEV void at_slot(long long slot, bool take)
+    {
+        if constexpr (!RECORD) {
+            if (traced) traced[slot] = take ? 1 : 0;
+            if (!take) offsets[slot] = 0;
+        }
+    }
+    KR_DEV void claim(long long slot)
+    {
+        n_rows = 0;
+        until_write = w.write_step;
+        if constexpr (RECORD) { slab = offsets[slot]; cap = offsets[slot + 1] - slab; }
+    }
+    KR_DEV void before_step(Lane<double>& s) { flip_armed = s.theta_was_positive; status_before = s.status; s.status = 0; }
+    template <bool USE_DEST> KR_DEV bool after_step(Lane<double>& s, bool fin)
+    {
+        const int32_t added = s.status;
+        s.status = status_before | added;
+        const bool due = (--until_write == 0);            // steps % write_step == 0: every iteration increments steps once
+        if (due) until_write = w.write_step;
+        const bool flipped = flip_armed && !s.theta_was_positive;                               // `continue`
+        const bool broke = (added & (KR_STATUS_HORIZON | (USE_DEST ? KR_STATUS_DEST : 0))) != 0;  // `break` before the write
+        if (due && !flipped && !broke) {
+            if (in_window(w, s.r)) {
+                if constexpr (RECORD) {
+                    const long long at = slab + n_rows;
+                    if ((long long) n_rows < cap && at >= 0 && at < total_rows) {
+                        double2* q = reinterpret_cast<double2*>(rows + 4 * at);
+                        q[0] = make_double2(s.t, s.r);
+                        q[1] = make_double2(s.theta, s.phi);
+                    }
+                }
+                ++n_rows;
+            } else if (n_rows > 0) {
+                fin = true;           // `else if (write_started) break;`  (:308-311)
+            }
+        }
+        return fin;
+    }
+    KR_DEV void leave(long long idx)
+    {
+        if constexpr (RECORD) mismatch += (long long) n_rows != cap;
+        else offsets[idx] = (long long) n_rows;
+    }
+    KR_DEV void at_exit(int lane, unsigned long long* __restrict__ counters)
+    {
+        const unsigned long long w_mismatch = wave_sum((unsigned long long) mismatch);
+        if (lane == 0 && w_mismatch) atomicAdd(&counters[kRecorderWord], w_mismatch);
+    }
+};
+
+// resident waves per SIMD the register allocation must allow: as the strict trace kernels, RK4 3, Euler 4 (kr_trace.hip)
 template <bool RK4, bool USE_DEST, bool RECORD>
-__global__ void __attribute__((amdgpu_flat_work_group_size(kPathBlock, kPathBlock))) __attribute__((amdgpu_waves_per_eu(RK4 ? 3 : 4, 8)))
+__global__ void __attribute__((amdgpu_flat_work_group_size(kTraceBlock, kTraceBlock))) __attribute__((amdgpu_waves_per_eu(RK4 ? 3 : 4, 8)))
 paths_kernel(kr_ray_f64* __restrict__ rays, long long n, TraceConsts<double> c, PathWindow w, long long* __restrict__ offsets, unsigned char* __restrict__ traced,
              double* __restrict__ rows, long long total_rows, unsigned long long* __restrict__ counters)
 {
-    const int lane = threadIdx.x & 63;
-    const unsigned long long lane_bit = 1ull << lane;
-
-    Lane<double> s;
-    long long idx = -1;
-    long long slab = 0, cap = 0;      // RECORD: first row of this lane's ray and how many it may write
-    int32_t n_rows = 0;               // rows this lane's ray has written so far (write_started == n_rows > 0)
-    int32_t until_write = 0;          // iterations left until steps % write_step == 0
-    bool have = false, pend = false, exhausted = false;
-    unsigned long long my_steps = 0, my_traced = 0, my_mismatch = 0;
-    int32_t my_longest = 0;
-
-    for (;;) {
-        const unsigned long long need = __builtin_amdgcn_ballot_w64(!have);
-        const int n_need = __popcll(need);
-        const bool any_have = (need != ~0ull);
-        const bool visit = !exhausted && n_need > 0 && (n_need >= kPathRefillMin || !any_have);
-        const bool leaving = !visit && !any_have;
-        if (visit || leaving) {
-            if (pend) {
-                // the one place where a ray's results leave its lane
-                my_steps += (unsigned long long) s.steps;
-                my_longest = s.steps > my_longest ? s.steps : my_longest;
-                if constexpr (RECORD) {
-                    store_ray(&rays[idx], s, finish_status<double, USE_DEST>(s, c));
-                    if ((long long) n_rows != cap) ++my_mismatch;
-                } else {
-                    offsets[idx] = (long long) n_rows;
-                }
-                pend = false;
-            }
-            if (leaving) break;
-            // wave-aggregated dequeue: one atomic for all free lanes
-            const int leader = __ffsll((long long) need) - 1;
-            unsigned long long base = 0;
-            if (lane == leader) base = atomicAdd(&counters[kPHead], (unsigned long long) n_need);
-            base = __shfl(base, leader, 64);
-            if (base + (unsigned long long) n_need >= (unsigned long long) n) exhausted = true;
-            if (!have) {
-                const long long slot = (long long) base + __popcll(need & (lane_bit - 1));
-                if (slot < n) {
-                    load_ray(&rays[slot], s);
-                    // skip rule of run_raytrace's serial path (raytracer.cpp:91-92): a skipped ray has no rows and no blank lines
-                    const bool take = s.steps0 >= 0 && s.steps0 < c.steplim;
-                    if constexpr (!RECORD) {
-                        if (traced) traced[slot] = take ? 1 : 0;
-                        if (!take) offsets[slot] = 0;
-                    }
-                    if (take) {
-                        idx = slot;
-                        have = true;
-                        ++my_traced;
-                        n_rows = 0;
-                        until_write = w.write_step;
-                        if constexpr (RECORD) {
-                            slab = offsets[slot];
-                            cap = offsets[slot + 1] - slab;
-                        }
-                        s.steps = 0;
-                        s.r_was_positive = false;
-                        s.theta_was_positive = true;
-                        energy_guard_set(s);
-                        if (!loop_cond<double, USE_DEST>(s, c)) {      // zero-iteration call: only the epilogue runs
-                            have = false;
-                            pend = true;
-                        }
-                    }
-                }
-            }
-            continue;
-        }
-
-        if (have) {
-            const bool flip_armed = s.theta_was_positive;
-            const int32_t status_before = s.status;
-            s.status = 0;
-            bool fin = step_fixed<double, RK4, USE_DEST, false>(s, c);
-            const int32_t added = s.status;
-            s.status = status_before | added;
-            const bool due = (--until_write == 0);            // steps % write_step == 0: every iteration increments steps once
-            if (due) until_write = w.write_step;
-            const bool flipped = flip_armed && !s.theta_was_positive;                               // `continue`
-            const bool broke = (added & (KR_STATUS_HORIZON | (USE_DEST ? KR_STATUS_DEST : 0))) != 0;  // `break` before the write
-            if (due && !flipped && !broke) {
-                if (in_window(w, s.r)) {
-                    if constexpr (RECORD) {
-                        const long long at = slab + n_rows;
-                        if ((long long) n_rows < cap && at >= 0 && at < total_rows) {
-                            double2* q = reinterpret_cast<double2*>(rows + 4 * at);
-                            q[0] = make_double2(s.t, s.r);
-                            q[1] = make_double2(s.theta, s.phi);
-                        }
-                    }
-                    ++n_rows;
-                } else if (n_rows > 0) {
-                    fin = true;           // `else if (write_started) break;`  (:308-311)
-                }
-            }
-            if (fin) {
-                have = false;
-                pend = true;
-            }
-        }
-    }
-    const unsigned long long w_traced = wave_sum_u64(my_traced);
-    const unsigned long long w_steps = wave_sum_u64(my_steps);
-    const unsigned long long w_mismatch = wave_sum_u64(my_mismatch);
-    const unsigned long long w_longest = wave_max_u64((unsigned long long) my_longest);
-    if (lane == 0) {
-        if (w_traced) atomicAdd(&counters[kPTraced], w_traced);
-        if (w_steps) atomicAdd(&counters[kPSteps], w_steps);
-        if (w_mismatch) atomicAdd(&counters[kPMismatch], w_mismatch);
-        if (w_longest) atomicMax(&counters[kPLongest], w_longest);
-    }
+    int has_prio = 0;
+    trace_body<double, RK4 ? KR_RK4 : KR_EULER, USE_DEST, false, false, KR_REFILL_MIN, false, PathRecorder<RECORD>>(
+        rays, n, c, counters, nullptr, nullptr, 0, nullptr, 0, has_prio, -1, 0, PathRecorder<RECORD>{w, offsets, traced, rows, total_rows});
 }
 
 // In-place exclusive scan of v[0 .. n) with the total in v[n], by ONE workgroup: every work-item sums a contiguous piece, the 1024 piece sums are
@@ -226,18 +157,15 @@ int launch_paths(kr_ray_f64* rays, long long n, const TraceConsts<double>& c, co
                  long long total_rows, unsigned long long* counters, hipStream_t stream)
 {
     auto kern = paths_kernel<RK4, USE_DEST, RECORD>;
-    int dev = 0, per_cu = 0;
+    int dev = 0, cus = 0, per_cu = 0;
     KR_HIP(hipGetDevice(&dev));
-    hipDeviceProp_t prop;
-    KR_HIP(hipGetDeviceProperties(&prop, dev));
-    KR_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kPathBlock, 0));
+    const int rc = device_cus(dev, &cus);
+    if (rc != KR_OK) return rc;
+    KR_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kTraceBlock, 0));
     // resident waves per SIMD as the strict trace sizes its launches (kr_trace.hip::launch): 2 for RK4 -- the pass ends with its longest ray,
     // which advances one step per turn of its wave -- 4 for the short Euler step
     per_cu = std::max(1, std::min(per_cu, 4 * (RK4 ? 2 : 4)));
-    const long long resident = (long long) prop.multiProcessorCount * per_cu;
-    const long long wanted = (n + kPathBlock - 1) / kPathBlock;
-    const int grid = (int) std::max<long long>(1, std::min(resident, wanted));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kPathBlock), 0, stream, rays, n, c, w, offsets, traced, rows, total_rows, counters);
+    hipLaunchKernelGGL(kern, dim3(persistent_grid(cus, per_cu, n)), dim3(kTraceBlock), 0, stream, rays, n, c, w, offsets, traced, rows, total_rows, counters);
     KR_LAUNCH_CHECK();
     return KR_OK;
 }
@@ -271,19 +199,15 @@ int paths_validate(const kr_params* p, const kr_path_spec* w, const char* who)
     if (p->flags & (KR_FLAG_FAST_MATH | KR_FLAG_HYBRID))
         return fail(who, "paths carry the reference's arithmetic: KR_FLAG_FAST_MATH / KR_FLAG_HYBRID are not accepted");
     if (p->integrator == KR_RK45) return fail(who, "RK45 paths are not recorded (Euler and RK4 only)");
-    if (p->integrator != KR_EULER && p->integrator != KR_RK4) return fail(who, "unknown integrator");
-    if (p->stop_kind < KR_STOP_THETA || p->stop_kind > KR_STOP_FLATPLANE) return fail(who, "unknown stop_kind");
-    // assert(method != Integrator::Euler), raytracer.cpp:983
-    if (p->stop_kind != KR_STOP_THETA && p->integrator == KR_EULER) return fail(who, "Integrator::Euler does not support RayDestination stopping conditions");
-    return KR_OK;
+    return validate_run(p, who);      // (the checks the trace makes, under this call's name)
 }
 
 int paths_count_dev(const kr_params* p, const kr_path_spec* w, const void* d_rays, int64_t n, void* d_offsets, void* d_traced, int64_t* total_rows, hipStream_t st)
 {
     DeviceBuffer counters;
-    int rc = counters.alloc(kPWords * sizeof(unsigned long long));
+    int rc = counters.alloc(kPathWords * sizeof(unsigned long long));
     if (rc != KR_OK) return rc;
-    KR_HIP(hipMemsetAsync(counters.p, 0, kPWords * sizeof(unsigned long long), st));
+    KR_HIP(hipMemsetAsync(counters.p, 0, kPathWords * sizeof(unsigned long long), st));
     if (n > 0) {
         // (the count pass only reads the records: the kernel's RECORD = false instance has no store to rays[])
         rc = launch_paths_for<false>(p, const_cast<kr_ray_f64*>((const kr_ray_f64*) d_rays), (long long) n, window_of(w), (long long*) d_offsets,
@@ -309,31 +233,31 @@ int paths_record_dev(const kr_params* p, const kr_path_spec* w, void* d_rays, in
     if (need < 0 || (long long) total_rows < need) return fail("kr_trace_paths_record", "total_rows is smaller than offsets[n]");
     if (n == 0) return KR_OK;
     DeviceBuffer counters;
-    int rc = counters.alloc(kPWords * sizeof(unsigned long long));
+    int rc = counters.alloc(kPathWords * sizeof(unsigned long long));
     if (rc != KR_OK) return rc;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     KR_HIP(hipEventCreate(&ev0));
     if (hipEventCreate(&ev1) != hipSuccess) { (void) hipEventDestroy(ev0); return hip_fail(hipGetLastError(), "hipEventCreate", __FILE__, __LINE__); }
     auto body = [&]() -> int {
-        KR_HIP(hipMemsetAsync(counters.p, 0, kPWords * sizeof(unsigned long long), st));
+        KR_HIP(hipMemsetAsync(counters.p, 0, kPathWords * sizeof(unsigned long long), st));
         KR_HIP(hipEventRecord(ev0, st));
         const int rc2 = launch_paths_for<true>(p, (kr_ray_f64*) d_rays, (long long) n, window_of(w), const_cast<long long*>((const long long*) d_offsets), nullptr,
                                                (double*) d_rows, (long long) total_rows, (unsigned long long*) counters.p, st);
         if (rc2 != KR_OK) return rc2;
         KR_HIP(hipEventRecord(ev1, st));
-        unsigned long long h[kPWords];
+        unsigned long long h[kPathWords];
         KR_HIP(hipMemcpyAsync(h, counters.p, sizeof h, hipMemcpyDeviceToHost, st));
         KR_HIP(hipStreamSynchronize(st));
         if (stats) {
             float ms = 0;
             KR_HIP(hipEventElapsedTime(&ms, ev0, ev1));
             stats->kernel_ms = ms;
-            stats->rays_traced = (int64_t) h[kPTraced];
-            stats->steps_total = (int64_t) h[kPSteps];
-            stats->longest_ray_steps = (int64_t) h[kPLongest];
+            stats->rays_traced = (int64_t) h[kTraced];
+            stats->steps_total = (int64_t) h[kSteps];
+            stats->longest_ray_steps = (int64_t) h[kLongest];
         }
-        if (h[kPMismatch] != 0) {
-            set_error("kr_trace_paths_record: " + std::to_string(h[kPMismatch]) + " rays wrote a different number of rows than the count pass gave them "
+        if (h[kRecorderWord] != 0) {
+            set_error("kr_trace_paths_record: " + std::to_string(h[kRecorderWord]) + " rays wrote a different number of rows than the count pass gave them "
                       "(offsets from another call, other parameters, or rays[] modified in between?)");
             return KR_EINVAL;
         }

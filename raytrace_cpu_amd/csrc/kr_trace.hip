@@ -19,6 +19,7 @@
 // Work-queue exit: every wave leaves the loop once the queue head has passed n AND none of its lanes holds a
 // ray; every ray ends after at most steplim iterations (steps is incremented on every path through a step,
 // and RK45 retries either shrink the step to MIN_STEP and force-accept, or end the ray on a NaN error norm).
+// The loop itself (trace_body) lives in kr_trace_loop.hpp, where the recording kernel of kr_paths.hip takes it from too.
 
 #include <hip/hip_runtime.h>
 
@@ -36,75 +37,20 @@
 #include <vector>
 
 #include "kr_common.hpp"
-#include "kr_device.hpp"
 #include "kr_post_device.hpp"
-#include "kr_ray_io.hpp"
+#include "kr_trace_loop.hpp"
 
 namespace kr {
 
 namespace {
 
 constexpr int kBlock = 256;          // classification kernel
-// Trace kernels: ONE wave per workgroup -- a wave gives its registers back the moment IT has finished, not when the slowest of four has
-// (main launch 93.1 -> 87.2 ms at 1e7 rays against 256-thread workgroups).  The HOG instances (the strict side launch) too: their first claims
-// are static (wave g takes list slots 64 g ..), so the listed rays go to the lowest-numbered workgroups -- which the dispatcher spreads over as
-// many compute units -- and every other workgroup leaves at once.  (Four HOG waves per workgroup, i.e. a workgroup that owns its compute unit,
-// measured worse: four lone waves on one CU slow one another down more than nine waves of the main launch do; profiles/r03_ab_experiments.txt.)
-constexpr int kTraceBlock = 64;
-// A wave goes back to the queue when at least this many of its lanes are free (or none holds a ray).  The refill / finish / store code runs with
-// only the free lanes active, ~500 vector instructions per visit -- as much as an RK4 step: visiting for every single finished lane cost the image
-// plane (1.25 lanes per visit) 11 % and the Euler launches 26 %; waiting for 4 leaves ~1.5 lanes of 64 idle on average.
-// Measured 1 -> 4 (8 is the same): image plane 170.4 -> 151.7 ms, Euler 1e7 rays 55.2 -> 40.8, returning radiation 318 -> 307, headline 81.8 -> 80.7,
-// RK45 412 -> 406 (profiles/r02_ab_experiments.txt).
-#ifndef KR_REFILL_MIN
-#define KR_REFILL_MIN 4
-#endif
-constexpr int kLongRaySteps = 2048;  // a wave whose oldest ray is older than 1 x / 3 x / 8 x this raises its issue priority to 1 / 2 / 3 (trace_body)
-#ifndef KR_OCC_STATS
-#define KR_OCC_STATS 0               // 1: lane-occupancy bookkeeping of the step loop (diagnostic builds: scripts/gpu_occ_stats.sh), printed by trace_wait
-#endif
-// Every launch of a trace has a block of counter words of its own in the workspace (device memory; copied out at the end of the trace): the queue
-// head (slots handed out so far), rays traced, steps, rk45 attempts / rejects / stationary steps / extrapolated steps, steps of the launch's longest ray (atomicMax).
-enum CounterWord { kHead, kTraced, kSteps, kAttempts, kRejects, kStationary, kExtrapolated, kLongest, kCounterWords,
-                   // in the split bookkeeping block only (classify_kernel): the ill-conditioned rays that are not radial, the radial ones (both counts
-                   // run on past what their lists hold), and whether either list overflowed
-                   kFlagged = kTraced, kRadial = kSteps, kListsOverflowed = kAttempts };
-constexpr int kCounters = KR_OCC_STATS ? 13 : kCounterWords;         // words per block; KR_OCC_STATS builds: [8..12] occupancy sums
 // main launch, strict side launch (its general waves), strict overflow launch, split bookkeeping, the side launch's radial waves
 enum CounterBlock { kMainBlock, kSideBlock, kOverflowBlock, kSplitBlock, kRadialBlock, kCounterBlocks };
 constexpr int kListCap = 32768;      // entries of each of the side launch's two index lists (general, radial)
 
-template <typename T> struct RayOf;
-template <> struct RayOf<double> { using type = kr_ray_f64; };
-template <> struct RayOf<float> { using type = kr_ray_f32; };
-// (load_ray / store_ray, make_consts, effective_steplim: kr_ray_io.hpp)
-
-KR_DEV unsigned long long wave_max(unsigned long long v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_down(v, off, 64);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
-template <typename T> KR_DEV unsigned long long wave_sum(unsigned long long v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
-// ---- the persistent kernel ------------------------------------------------------------------------
-// METHOD: KR_EULER / KR_RK4 / KR_RK45.  REFILL_MIN: a wave goes back to the queue when at least this many of its
-// lanes are free (or when none holds a ray).
-// `list` (optional): the launch works on rays list[0 .. n) instead of rays 0 .. n); `n_ptr` (optional): the item count is read
-// from device memory (the classification kernel of the split path produced it; see n_mode below); `mask` (optional): only
-// rays with mask[i] == mask_want are traced (the others belong to another launch of the split).  HOG: the kernel claims the whole register
-// file (512 VGPR+AGPR per lane), so each of its waves owns its SIMD and no other kernel's wave can be co-resident on
-// the CUs it occupies -- used for the few ill-conditioned / long rays that define the critical path.  RADIAL (trace_body; trace_side_kernel's
-// radial waves): the wave's rays are integrated with step_radial, a lane whose ray turns out not to be radial with step_fixed.
+// ---- the persistent kernels ----------------------------------------------------------------------
+// Their body is trace_body (kr_trace_loop.hpp), which explains METHOD, REFILL_MIN, `list`, `n_ptr`, `mask`, HOG and RADIAL.
 // Resident waves per SIMD the register allocation must allow: HOG 1 (the scheduler may trade registers for ILP; capping it at (1, 1) measured 2 %
 // slower), RK4 3 (<= 168 VGPRs), RK45 2, Euler 4 (its step is short and branchy: at 3 waves per SIMD the vector unit is 78 % busy; 1e7 rays
 // 38.5 / 31.4 / 28.3 ms at 2 / 3 / 4 resident waves, profiles/r03_ab_experiments.txt).
@@ -122,194 +68,6 @@ template <typename T> struct TraceDesc {
     const unsigned char* mask = nullptr;          // per-ray launch selector, or null
     int n_mode = 0, mask_want = 0;                // how n_ptr is applied (trace_body); the mask value this launch traces
 };
-
-template <typename T, int METHOD, bool USE_DEST, bool FAST, bool HOG, int REFILL_MIN, bool RADIAL = false>
-KR_DEV void trace_body(typename RayOf<T>::type* __restrict__ rays, long long n, const TraceConsts<T>& c, unsigned long long* __restrict__ counters,
-                       const int* __restrict__ list, const unsigned long long* __restrict__ n_ptr, int n_mode, const unsigned char* __restrict__ mask, int mask_want,
-                       int& has_prio, long long first_slot = -1, unsigned long long head_offset = 0)
-{
-    if (n_ptr) {
-        // the item count was produced on the device (classify_kernel) and never visits the host:
-        // n_mode 1: the first min(n, *n_ptr) list entries;  n_mode 2: all n slots, but only if *n_ptr says that a list overflowed (else nothing)
-        const long long m = (long long) *n_ptr;
-        n = (n_mode == 1) ? (m < n ? m : n) : (m != 0 ? n : 0);
-    }
-    const int lane = threadIdx.x & 63;
-    const unsigned long long lane_bit = 1ull << lane;
-
-    Lane<T> s;
-    [[maybe_unused]] RadialRay radial;      // RADIAL: the constants of this lane's ray (step_radial)
-    // The fast Euler / RK4 instances keep the terms of (k, h, Q, a) that the potentials need (kr_fast.hpp: FastRayConsts) beside the lane state, like
-    // `radial` above: computed once per ray instead of once per step.  (Not the fast RK45 instances: the trial's stages go through eval(), which forms
-    // the terms itself, and that kernel has no registers to spare at 2 waves per SIMD.)  Every other instance: an empty struct.
-    constexpr bool kRayConsts = FAST && sizeof(T) == 8 && METHOD != KR_RK45;
-    static_assert(!(RADIAL && FAST), "the radial waves call step_fixed without a ray's constant terms: strict arithmetic only");
-    [[maybe_unused]] RayConstsOf<kRayConsts> ray_consts;
-    long long idx = -1;
-    bool have = false;          // this lane holds a ray
-    bool pend = false;          // this lane's ray has ended and is still in its registers: written out at the wave's next visit to the queue (or on exit)
-    bool exhausted = false;     // wave-uniform: the queue head has passed n
-    unsigned long long my_steps = 0, my_traced = 0;
-    int32_t my_longest = 0;     // most steps any of this lane's rays took in this call
-    uint32_t my_attempts = 0, my_rejects = 0, my_stationary = 0, my_creep = 0;
-
-#if KR_OCC_STATS
-    unsigned long long occ_iters = 0, occ_tail_iters = 0, occ_tail_steps = 0, occ_refills = 0, occ_refill_lanes = 0;
-#endif
-    for (;;) {
-        const unsigned long long need = __builtin_amdgcn_ballot_w64(!have);      // (not __ballot: that one takes its predicate through a vector register and a compare)
-        const int n_need = __popcll(need);
-        const bool any_have = (need != ~0ull);
-
-        // A wave visits the queue when enough of its lanes are free, and once more when it leaves: rays that have ended since the last visit are
-        // written out there -- the ONE place in the kernel where a ray is stored.
-        const bool visit = !exhausted && n_need > 0 && (n_need >= REFILL_MIN || !any_have);
-        const bool leaving = !visit && !any_have;          // nothing held and nothing left to take
-        if (visit || leaving) {
-            if (pend) {
-                // (not under a divergent branch of its own in the step loop: that branch ran in one wave iteration out of nine for a single
-                // lane's ~40 instructions)
-                my_steps += (unsigned long long) s.steps;
-                my_longest = s.steps > my_longest ? s.steps : my_longest;
-                store_ray(&rays[idx], s, finish_status<T, USE_DEST>(s, c));
-                pend = false;
-            }
-            if (leaving) break;
-            // The launch cannot end before its longest ray does, and a ray advances one step per iteration of ITS wave: a wave that carries a long
-            // ray (orbiting / polar-axis rays: 2e4..1e7 steps against a median of ~450) is given issue priority over its SIMD neighbours so that the
-            // critical path runs at single-wave speed instead of at 1/(waves per SIMD) of it -- graded: the longer the wave's oldest ray, the higher
-            // its priority (0..3), so that the rays that define the critical path do not share their level with the many merely "longish" ones.
-            // Re-evaluated here, at the queue visits (a wave that carries a long ray keeps visiting for its other 63 lanes until the queue is empty;
-            // a counter in the step loop cost three vector instructions per step).  A wave that owns its SIMD (HOG) has nobody to overtake.
-            if constexpr (!HOG) {
-                const int32_t st = have ? s.steps : 0;
-                auto any = [](bool x) { return __builtin_amdgcn_ballot_w64(x) != 0; };
-                const int want_prio = any(st > 8 * kLongRaySteps) ? 3 : any(st > 3 * kLongRaySteps) ? 2 : any(st > kLongRaySteps) ? 1 : 0;
-                if (want_prio != has_prio) {
-                    has_prio = want_prio;
-                    switch (want_prio) {
-                        case 3: __builtin_amdgcn_s_setprio(3); break;
-                        case 2: __builtin_amdgcn_s_setprio(2); break;
-                        case 1: __builtin_amdgcn_s_setprio(1); break;
-                        default: __builtin_amdgcn_s_setprio(0); break;
-                    }
-                }
-            }
-#if KR_OCC_STATS
-            ++occ_refills; occ_refill_lanes += n_need;
-#endif
-            // wave-aggregated dequeue: one atomic for all free lanes
-            const int leader = __ffsll((long long) need) - 1;
-            unsigned long long base = 0;
-            if (first_slot >= 0) {
-                // (HOG instances: this wave's first 64 slots are its own by position; the shared queue head counts from head_offset on)
-                base = (unsigned long long) first_slot;
-                first_slot = -1;
-            } else {
-                if (lane == leader) base = atomicAdd(&counters[kHead], (unsigned long long) n_need);
-                base = __shfl(base, leader, 64) + head_offset;
-            }
-            if (base + (unsigned long long) n_need >= (unsigned long long) n) exhausted = true;
-            if (!have) {
-                const long long slot = (long long) base + __popcll(need & (lane_bit - 1));
-                if (slot < n) {
-                    // (the record is loaded beside its mask byte, not after it -- one memory round trip per visit instead of two; a ray that belongs to
-                    // the other launch of a split, 0.03 % of them, is dropped again)
-                    long long mine = slot;
-                    if constexpr (HOG) { if (list) mine = (long long) list[slot]; }          // (only side launches work from a list)
-                    const unsigned char* launch = mask ? mask + slot : (const unsigned char*) &rays[mine];      // one straight line of loads, mask or not
-                    const unsigned char launch_of_ray = *launch;
-                    load_ray(&rays[mine], s);
-                    // skip rule of run_raytrace (raytracer.cpp:116-117)
-                    if ((!mask || launch_of_ray == (unsigned char) mask_want) && s.steps0 >= 0 && s.steps0 < c.steplim) {
-                        idx = mine;
-                        have = true;
-                        ++my_traced;
-                        s.steps = 0;
-                        s.r_was_positive = false;
-                        s.theta_was_positive = true;
-                        s.in_retry = false;
-                        s.creep_m = 0;
-                        s.creep_run = 0;
-                        s.creep_mode = false;
-                        s.fsal_valid = false;
-                        energy_guard_set(s);
-                        // (the one place a lane takes a ray: its lanes only -- the others keep the terms of the rays they hold)
-                        if constexpr (kRayConsts) ray_consts = fast_ray_consts(s.k, s.h, s.Q, c.a);
-                        if (METHOD == KR_RK45) rk45_seed(s, c);
-                        if constexpr (RADIAL) radial_claim(s, c, radial);
-                        if (!loop_cond<T, USE_DEST>(s, c)) {
-                            // zero-iteration call: only the epilogue runs (at the next visit)
-                            have = false;
-                            pend = true;
-                        }
-                    }
-                }
-            }
-            continue;   // re-evaluate the ballots (skipped / zero-iteration rays leave lanes free)
-        }
-
-        int replay_batch = 1;
-        if constexpr (METHOD == KR_RK45 && sizeof(T) == 8) {
-            // the tail of an RK45 launch is waves that hold nothing but creeping captured rays: they take 16 cheap steps per iteration
-            if (!__any(have && !s.creep_mode)) replay_batch = 16;      // (__any, not the ballot builtin: with the builtin this kernel's allocation came out 19 % slower)
-        }
-#if KR_OCC_STATS
-        ++occ_iters;
-        if (exhausted) { ++occ_tail_iters; occ_tail_steps += have ? 1 : 0; }
-#endif
-        if constexpr (RADIAL) {
-            // every wave of a radial launch runs the radial body only; a lane whose ray is not provably radial (radial_claim, or a step that step_radial
-            // handed back) is the exception, out of line
-            bool fin = false;
-            if (have && !radial.general) fin = step_radial<METHOD == KR_RK4>(s, radial, c);
-            const bool general = have && radial.general;
-            if (__builtin_expect(__builtin_amdgcn_ballot_w64(general) != 0, false)) {
-                if (general) fin = step_fixed<T, METHOD == KR_RK4, USE_DEST, FAST, HOG>(s, c);      // (radial waves are strict: no ray constants)
-            }
-            if (fin) {
-                have = false;
-                pend = true;
-            }
-        } else if (have) {
-            bool fin;
-            if constexpr (kRayConsts) fin = step_fixed<T, METHOD == KR_RK4, USE_DEST, FAST, HOG>(s, c, &ray_consts);
-            else if (METHOD == KR_EULER) fin = step_fixed<T, false, USE_DEST, FAST, HOG>(s, c);
-            else if (METHOD == KR_RK4) fin = step_fixed<T, true, USE_DEST, FAST, HOG>(s, c);
-            else fin = step_rk45<T, USE_DEST, FAST, HOG>(s, c, my_attempts, my_rejects, my_stationary, my_creep, replay_batch);
-            if (fin) {
-                have = false;
-                pend = true;
-            }
-        }
-    }
-    // per-wave totals -> global counters (4 atomics per wave, once)
-    const unsigned long long w_traced = wave_sum<T>(my_traced);
-    const unsigned long long w_steps = wave_sum<T>(my_steps);
-    const unsigned long long w_att = wave_sum<T>((unsigned long long) my_attempts);
-    const unsigned long long w_rej = wave_sum<T>((unsigned long long) my_rejects);
-    const unsigned long long w_sta = wave_sum<T>((unsigned long long) my_stationary);
-    const unsigned long long w_creep = wave_sum<T>((unsigned long long) my_creep);
-    const unsigned long long w_longest = wave_max((unsigned long long) my_longest);
-#if KR_OCC_STATS
-    {
-        const unsigned long long w_tail_steps = wave_sum<T>(occ_tail_steps);
-        if (lane == 0) {
-            atomicAdd(&counters[8], occ_iters); atomicAdd(&counters[9], occ_tail_iters); atomicAdd(&counters[10], w_tail_steps);
-            atomicAdd(&counters[11], occ_refills); atomicAdd(&counters[12], occ_refill_lanes);
-        }
-    }
-#endif
-    if (lane == 0) {
-        if (w_longest) atomicMax(&counters[kLongest], w_longest);
-        if (w_sta) atomicAdd(&counters[kStationary], w_sta);
-        if (w_creep) atomicAdd(&counters[kExtrapolated], w_creep);
-        if (w_traced) atomicAdd(&counters[kTraced], w_traced);
-        if (w_steps) atomicAdd(&counters[kSteps], w_steps);
-        if (w_att) atomicAdd(&counters[kAttempts], w_att);
-        if (w_rej) atomicAdd(&counters[kRejects], w_rej);
-    }
-}
 
 // A wave that owns its SIMD has 512 vector registers to itself and the same ~100 scalar ones as any other wave: in the side launch's kernels the launch
 // constants live in vector registers (the empty asm makes them opaque to the compiler's uniformity analysis) instead of being spilled to lanes and
@@ -515,6 +273,7 @@ struct DeviceState {
     std::vector<Workspace*> pool;                        // g_mu
     std::map<hipStream_t, hipStream_t> side_streams;     // g_mu: caller's stream -> side stream
     std::map<hipStream_t, int> side_users;               // g_mu: side stream -> number of entries above that point at it
+    std::atomic<int> cus{0};                             // compute units, asked once (device_cus)
     hipStream_t poll_stream = nullptr;                   // g_poll_mu (trace_poll)
     unsigned long long* poll_word = nullptr;             // g_poll_mu: pinned, 8 bytes
 };
@@ -575,10 +334,9 @@ int workspace_create(int dev, Workspace** out)
     KR_WS(hipMalloc((void**) &w->list, 2 * kListCap * sizeof(int)));
     for (hipEvent_t* timed : {&w->ev0, &w->ev1, &w->ev_strict0, &w->ev_strict1, &w->ev_main0, &w->ev_main1}) KR_WS(hipEventCreate(timed));
     for (hipEvent_t* untimed : {&w->ev_classified, &w->done, &w->ev_in}) KR_WS(hipEventCreateWithFlags(untimed, hipEventDisableTiming));
-    hipDeviceProp_t prop;
-    KR_WS(hipGetDeviceProperties(&prop, dev));
 #undef KR_WS
-    w->cus = prop.multiProcessorCount;
+    const int rc = device_cus(dev, &w->cus);
+    if (rc != KR_OK) return fail(rc);
     *out = w;
     return KR_OK;
 }
@@ -694,9 +452,7 @@ int launch(const TraceDesc<T>& d, GridPolicy policy, int cus, hipStream_t stream
     }
     want *= 4;                                  // `want` counts waves per SIMD; a workgroup is one wave, a CU has four SIMDs
     if (want < blocks_per_cu) blocks_per_cu = want;
-    const int64_t resident = (int64_t) cus * blocks_per_cu;
-    const int64_t wanted = ((int64_t) d.n + kTraceBlock - 1) / kTraceBlock;
-    const int grid = policy.exact > 0 ? policy.exact : (int) std::max<int64_t>(1, std::min(resident, wanted));
+    const int grid = policy.exact > 0 ? policy.exact : persistent_grid(cus, blocks_per_cu, d.n);
     if (!HOG && d.list) { set_error("kr_trace: only side launches work from a list"); return KR_EINVAL; }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kTraceBlock), 0, stream, d.rays, d.n, d.c, d.counters, d.list, d.n_ptr, d.n_mode, d.mask, d.mask_want);
     KR_HIP(hipGetLastError());
@@ -789,14 +545,8 @@ int enqueue_classify(const SplitPlan& plan, Workspace* ws, hipStream_t stream)
 int validate(const kr_params* p, void* d_rays, int64_t n)
 {
     if (!p || n < 0 || (n > 0 && !d_rays)) { set_error("kr_trace: null argument or negative n"); return KR_EINVAL; }
-    if (p->integrator < KR_EULER || p->integrator > KR_RK45) { set_error("kr_trace: unknown integrator"); return KR_EINVAL; }
-    if (p->stop_kind < KR_STOP_THETA || p->stop_kind > KR_STOP_FLATPLANE) { set_error("kr_trace: unknown stop_kind"); return KR_EINVAL; }
-    if (p->stop_kind != KR_STOP_THETA && p->integrator == KR_EULER) {
-        // assert(method != Integrator::Euler), raytracer.cpp:983
-        set_error("kr_trace: Integrator::Euler does not support RayDestination stopping conditions");
-        return KR_EINVAL;
-    }
-    return require_device();
+    const int rc = validate_run(p, "kr_trace");
+    return rc != KR_OK ? rc : require_device();
 }
 
 // the two ends of every trace on its (primary) stream: counters zeroed and the clock started; the clock stopped, the counters
@@ -958,6 +708,32 @@ void hand_over(Pending& t, void** ticket)
 }
 
 }  // namespace
+
+// what a kr_params must satisfy whichever kernel integrates its rays (the trace, the recording trace of kr_paths.hip); `who` prefixes the message
+int validate_run(const kr_params* p, const char* who)
+{
+    const char* what = nullptr;
+    if (p->integrator < KR_EULER || p->integrator > KR_RK45) what = "unknown integrator";
+    else if (p->stop_kind < KR_STOP_THETA || p->stop_kind > KR_STOP_FLATPLANE) what = "unknown stop_kind";
+    // assert(method != Integrator::Euler), raytracer.cpp:983
+    else if (p->stop_kind != KR_STOP_THETA && p->integrator == KR_EULER) what = "Integrator::Euler does not support RayDestination stopping conditions";
+    if (what) set_error(std::string(who) + ": " + what);
+    return what ? KR_EINVAL : KR_OK;
+}
+
+// compute units of device `dev`, asked once per process (host threads may race here: both would store the same value)
+int device_cus(int dev, int* cus)
+{
+    DeviceState* ds = device_state(dev);
+    if (!ds) return KR_EINVAL;
+    if (ds->cus.load(std::memory_order_relaxed) == 0) {
+        hipDeviceProp_t prop;
+        KR_HIP(hipGetDeviceProperties(&prop, dev));
+        ds->cus.store(prop.multiProcessorCount, std::memory_order_relaxed);
+    }
+    *cus = ds->cus.load(std::memory_order_relaxed);
+    return KR_OK;
+}
 
 // Enqueues one trace on `stream` and returns at once; *ticket (never null on success, unless n == 0) must go to trace_wait or
 // trace_release.  Nothing in here synchronises with the device.

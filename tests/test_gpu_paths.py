@@ -139,6 +139,49 @@ def test_recording_is_the_strict_trace_with_rows(case, run, regime):
     print(f"paths consistency {case}/{run}{'/' + regime if regime else ''}: rays {int((~skipped).sum())}, rows ws=1 {len(rows1)}, ws=7 {len(rows7)}, steps {st1['steps_total']}, last-row checks {n_checked_last}")
 
 
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 129])
+@pytest.mark.parametrize("run", ["euler", "rk4"])
+def test_wave_boundaries_with_skipped_slots(run, n):
+    """The recorder rides the trace's own loop (kr_trace_loop.hpp): what the 35-ray fixtures do not reach is a launch of one wave exactly full,
+    one slot short, one slot over and three waves, with slots among them that the skip rule leaves out -- every third one unused (steps = -1;
+    at n = 65 the second wave's only slot), one at the step limit.  The first n ps_h10 records: the traced slots end with the golden file's
+    records under test_trace_vs_golden's bar for the strict fixed-step kernels (and with those of api.trace, bit for bit), the skipped slots keep
+    their bytes, and traced[] / offsets / the last rows say the same."""
+    case = gc.cases()["ps_h10"]
+    p = capi.copy_params(case["runs"][run], flags=0)
+    g = np.load(gc.golden_path("ps_h10"))
+    steplim = p.steplim if p.steplim > 0 else capi.STEPLIM
+    init = g["init"][:n].copy()
+    init["steps"][1::3] = -1
+    if n > 3:
+        init["steps"][3] = steplim
+    skipped = (init["steps"] < 0) | (init["steps"] >= steplim)
+    offsets, rows, traced, out, st = api.trace_paths(p, init, write_step=1)
+    # the skip rule: traced[], zero-width slabs, untouched records
+    assert (traced == (~skipped).astype(np.uint8)).all() and st["rays_traced"] == int((~skipped).sum())
+    assert offsets[0] == 0 and (np.diff(offsets) >= 0).all() and (np.diff(offsets)[skipped] == 0).all()
+    assert offsets[n] == len(rows)
+    assert out[skipped].tobytes() == init[skipped].tobytes()
+    # the last row of a ray that ended by the loop condition is its final record
+    by_loop_condition = ~skipped & ((out["status"] & (capi.STATUS_HORIZON | capi.STATUS_STEPLIM)) == 0) & (np.abs(out["steps"]) > 0)
+    u = rows.view(np.uint64)
+    for i in np.flatnonzero(by_loop_condition):
+        last = np.array([out[f][i] for f in ("t", "r", "theta", "phi")]).view(np.uint64)
+        assert offsets[i + 1] > offsets[i] and (u[offsets[i + 1] - 1] == last).all(), i
+    want_trace, st_trace = api.trace(p, init)
+    assert parity.same_records(out, want_trace) and st["steps_total"] == st_trace["steps_total"]
+    # the traced slots against the reference's records, as test_gpu_parity.test_trace_vs_golden holds the strict Euler / RK4 trace to them
+    got = out[~skipped]
+    api.range_phi(got)
+    V, rev, proj = case["post"]
+    api.redshift(p.spin, V, rev, proj, got)
+    res = parity.compare_rays(got, g[f"final__{run}"][:n][~skipped], rtol=parity.rtol_for(p), check_redshift=True, steps_slack=parity.steps_slack_for(p, 0))
+    allowed = parity.allowed_bad_frac_strict(p, res["n_traced"])
+    print(f"paths wave boundaries {run} n={n}: traced {res['n_traced']}, rows {len(rows)}, bad {res['n_bad']} (allowed share {allowed:.4f}), "
+          f"bit-identical share {res['frac_bit_identical']:.4f}, last-row checks {int(by_loop_condition.sum())}")
+    assert res["n_traced"] == int((~skipped).sum()) and res["frac_bad"] <= allowed, res
+
+
 def test_count_pass_leaves_the_rays_alone_and_record_checks_its_slabs():
     """Device-pointer forms: the count pass does not modify d_rays; the record pass refuses a rows buffer smaller than offsets[n], and reports rays whose
     row count differs from the slab the offsets give them (here: offsets counted with another write_step) without writing outside the buffer."""
