@@ -279,6 +279,38 @@ typedef struct kr_caustic_map {
 static_assert(sizeof(kr_caustic_map) == 48, "kr_caustic_map is 48 bytes (raytrace_cpu_amd/capi.py CausticMap)");
 #endif
 
+/* Caustic maps of the source sphere (src/caustic/caustic_sourceplane.cpp: rays run free, theta_max = 0, to the sphere r = r_lim; det J of
+ * d(theta_s, phi_s) / d(x_img, y_img)) and of a flat source plane behind the hole (src/caustic/caustic_plane.cpp: rays stop on a
+ * FlatPlaneDestination; det J of d(x_s, y_s) / d(x_img, y_img)).  Per image-plane pixel (ix, iy), from the ray through the pixel (bundle mode:
+ * member 0 of its 5-ray bundle), as it comes out of the trace -- no redshift, no range_phi:
+ *   kind = 0    ESCAPED = steps > 0 && (status & KR_STATUS_RLIM) (caustic_sourceplane.cpp:191); then THETA_S = theta, PHI_S = atan2(sin phi, cos phi)
+ *               of the accumulated phi, ORDER = max(floor(|phi| / pi) - 1, 0) (:202-219); otherwise NaN, NaN, -1 (:225-228)
+ *   kind = 1    HIT_PLANE = steps > 0 && (status & KR_STATUS_DEST) (caustic_plane.cpp:187-189); then (X_S, Y_S) = source_coords(r, theta, phi)
+ *               (ray_destination.h:195-203: X = r sin theta cos phi, Y = r sin theta sin phi, Z = r cos theta, X_S = -X sin phi0 + Y cos phi0,
+ *               Y_S = -X cos incl cos phi0 - Y cos incl sin phi0 + Z sin incl), ORDER = max((int) (|phi| / 2 pi), rdot_flips / 2) (:180-184);
+ *               otherwise NaN, NaN, -1 (:232-238).  The caller evaluates the four sines and cosines with the C library, as the reference does.
+ *   RDOT_FLIPS, EQUAT_CROSS   rdot_flips, equatorial_crossings of that ray, whatever became of it
+ *   DET_J, SIGN_J   bundles = 1 (kind = 1 only; caustic_plane.cpp:249-299): NaN, 0 unless the centre and its four satellites (east, west, north, south at
+ *               +- eps_x, +- eps_y) are hits; 1e30, 0 unless all four have the centre's rdot_flips and an accumulated phi within pi / 2 of its;
+ *               otherwise the determinant of the central differences of (X_S, Y_S) over 2 eps_x, 2 eps_y and its sign (+1 / -1 / 0).
+ *               bundles = 0 (caustic_sourceplane.cpp:264-305, caustic_plane.cpp:357-392): the same from the two coordinate planes of the four
+ *               neighbouring pixels over 2 eps_x, 2 eps_y (here the spacing of the ray grid), with their ESCAPED / HIT_PLANE and ORDER in place of
+ *               the satellite tests; border pixels stay NaN, 0.  kind = 0 wraps the two PHI_S differences into [-pi, pi] (wrap_dphi, :68-73).
+ * d_maps: 8 nx ny + 3 doubles on the device, [DET_J | SIGN_J | ORDER | ESCAPED or HIT_PLANE | THETA_S or X_S | PHI_S or Y_S | RDOT_FLIPS |
+ * EQUAT_CROSS], each [ix ny + iy] like Array2D, then the three counts over the rays through the pixels: escaped or hit, captured (KR_STATUS_HORIZON
+ * among the others), steplim (steps <= 0 or KR_STATUS_STEPLIM). */
+typedef struct kr_source_map {
+    int32_t kind;                  /* 0: source sphere;  1: flat source plane */
+    int32_t bundles;               /* 1: 5 records per pixel (kind = 1 only);  0: one record per pixel + neighbour differences */
+    int32_t nx, ny;                /* pixels = bundle centres (fencepost counts) */
+    double eps_x, eps_y;           /* bundles = 1: satellite offsets;  bundles = 0: dx, dy of the ray grid */
+    double sin_incl, cos_incl;     /* kind = 1: of the FlatPlaneDestination's incl (radians) ... */
+    double sin_phi0, cos_phi0;     /* ... and phi0;  unused by kind = 0 */
+} kr_source_map;
+#ifdef __cplusplus
+static_assert(sizeof(kr_source_map) == 64, "kr_source_map is 64 bytes (raytrace_cpu_amd/capi.py SourceMap)");
+#endif
+
 /* What run_raytrace's trajectory dump takes besides the trace parameters (raytracer.h:112-122: write_step, write_rmax, write_rmin).  A struct of
  * its own: kr_params and kr_stats keep their sizes.  write_rmin / write_rmax < 0: that side of the radial window is open. */
 typedef struct kr_path_spec {
@@ -511,6 +543,13 @@ int kr_post_caustic_disc_dev_f64(double spin, int reverse, const kr_caustic_map*
 /* branch-boundary suppression (caustic_discplane.cpp:455-493): a pixel with SIGN_J != 0 whose 4-neighbourhood -- in the planes as they are when the
  * call is made -- holds more opposite than equal signs, and at least two opposite ones, gets DET_J = 1e30, SIGN_J = 0; their number -> suppressed */
 int kr_caustic_suppress_dev_f64(const kr_caustic_map* m, void* d_maps, void* stream);
+/* the gather and the Jacobian of caustic_sourceplane.cpp:180-232, :264-305 (kind = 0) and caustic_plane.cpp:207-299 / :315-392 (kind = 1) over traced
+ * records (kr_source_map above): rays from kr_imageplane_init_dev_f64 (grid) or kr_bundles_init_emit_dev_f64 (bundles; its `emit` is not read), traced
+ * with stop_kind = KR_STOP_THETA, theta_max = 0, r_max = r_lim, or to KR_STOP_FLATPLANE.  The records are only read; those from nx ny (grid) or 5 nx ny
+ * (bundles) on are ignored.  WRITES every word of d_maps.  KR_EINVAL (message in kr_last_error) before anything touches a device when the map is
+ * null, nx or ny < 1, eps_x or eps_y is <= 0 or non-finite, the kind is unknown, kind = 0 comes with bundles, a sine or cosine of kind = 1 is not
+ * finite, or n is smaller than 5 nx ny (bundles) / nx ny (grid).  Does not wait for the device, allocate or free. */
+int kr_post_caustic_source_dev_f64(const kr_source_map* m, const void* d_rays, int64_t n, void* d_maps, void* stream);
 
 /* ---- diagnostics ------------------------------------------------------------------------------- */
 /* out[i] = op(a[i], b[i]) evaluated ON THE DEVICE with the exact primitive the trace kernel uses (host pointers):

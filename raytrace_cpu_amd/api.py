@@ -357,6 +357,103 @@ def caustic_map(imageplane_spec, r_disc, integrator=capi.RK4, eps_frac=0.01, rk4
     return res
 
 
+SOURCE_CAUSTIC_PLANES = {"sphere": ("det_j", "sign_j", "order", "escaped", "theta_s", "phi_s", "rdot_flips", "equat_cross"),
+                         "plane": ("det_j", "sign_j", "order", "hit_plane", "x_s", "y_s", "rdot_flips", "equat_cross")}
+SOURCE_CAUSTIC_COUNTS = {"sphere": ("escaped_count", "captured", "steplim"), "plane": ("hit_count", "captured", "steplim")}
+SOURCE_KINDS = ("sphere", "plane")
+
+
+def source_caustic_words(sm):
+    """Length of the map buffer of kr_post_caustic_source_dev_f64: eight planes of nx ny and three counts (include/kr_trace.h, kr_source_map)."""
+    return 8 * sm.nx * sm.ny + 3
+
+
+def source_caustic_from_words(sm, words):
+    """The map buffer as a dict: the eight planes as (nx, ny) arrays ([ix, iy], like Array2D), named after the kind's FITS extensions, and the three
+    counts as ints."""
+    kind = SOURCE_KINDS[sm.kind]
+    npix = sm.nx * sm.ny
+    words = np.asarray(words, dtype=np.float64)
+    out = {k: words[q * npix:(q + 1) * npix].reshape(sm.nx, sm.ny).copy() for q, k in enumerate(SOURCE_CAUSTIC_PLANES[kind])}
+    out.update({k: int(round(float(words[8 * npix + q]))) for q, k in enumerate(SOURCE_CAUSTIC_COUNTS[kind])})
+    return out
+
+
+def caustic_trace_params_source(imageplane_spec, kind, r_lim=None, z_s=None, r_max=None, integrator=capi.RK45, rk45_tol=1e-8, precision=100, flags=0, steplim=0):
+    """The trace of the caustic_sourceplane program (kind "sphere", caustic_sourceplane.cpp:155: the theta-limit overload with theta_max = 0, which
+    switches the equatorial stop off, to r_max = r_lim, default 1.5 dist) or of the caustic_plane program (kind "plane", caustic_plane.cpp:151, :203:
+    to a FlatPlaneDestination(incl pi / 180, phi0, z_s) -- its descriptor as host/raytracer/ray_destination.h::describe gives it, {incl, phi0, z_s, 0} --
+    or r_max; z_s defaults to dist, r_max to 4 z_s).  Returns (params, geometry): geometry holds r_lim, or z_s, r_max and incl_rad."""
+    if kind not in SOURCE_KINDS:
+        raise KrError(f"caustic_trace_params_source: kind must be one of {SOURCE_KINDS}, got {kind!r}")
+    p = capi.default_params(-1 * imageplane_spec.spin)   # as stored by the Raytracer of an ImagePlane (imageplane.cpp:12)
+    p.precision, p.integrator, p.flags, p.steplim = precision, integrator, flags, steplim
+    if integrator == capi.RK45:
+        p.rk45_tol = rk45_tol
+    if kind == "sphere":
+        r_lim = 1.5 * imageplane_spec.dist if r_lim is None else r_lim
+        p.stop_kind, p.theta_max, p.r_max = capi.STOP_THETA, 0.0, r_lim
+        return p, {"r_lim": r_lim}
+    z_s = imageplane_spec.dist if z_s is None else z_s
+    r_max = 4.0 * z_s if r_max is None else r_max
+    incl_rad = imageplane_spec.inc_deg * np.pi / 180.0
+    p.stop_kind, p.r_max = capi.STOP_FLATPLANE, r_max
+    for i, v in enumerate((incl_rad, imageplane_spec.phi0, z_s, 0.0)):
+        p.stop_params[i] = v
+    return p, {"z_s": z_s, "r_max": r_max, "incl_rad": incl_rad}
+
+
+def source_map_struct(kind, nx, ny, eps_x, eps_y, bundles=False, incl_rad=0.0, phi0=0.0):
+    """kr_source_map with the four sines and cosines of a FlatPlaneDestination evaluated by the C library (math.sin / math.cos), as the reference
+    evaluates them in source_coords."""
+    import math
+    sm = capi.SourceMap()
+    sm.kind, sm.bundles, sm.nx, sm.ny, sm.eps_x, sm.eps_y = SOURCE_KINDS.index(kind), int(bundles), nx, ny, eps_x, eps_y
+    sm.sin_incl, sm.cos_incl, sm.sin_phi0, sm.cos_phi0 = math.sin(incl_rad), math.cos(incl_rad), math.sin(phi0), math.cos(phi0)
+    return sm
+
+
+def caustic_source_map(imageplane_spec, kind, r_lim=None, z_s=None, r_max=None, integrator=capi.RK45, eps_frac=0.01, rk45_tol=1e-8, precision=100, flags=0,
+                       steplim=0):
+    """The caustic maps of the source sphere (kind "sphere") or of a flat source plane behind the hole (kind "plane"), resident on the device from
+    start to finish, as the kr_caustic_sourceplane / kr_caustic_plane apps run them: the ray grid (kr_imageplane_init_dev_f64) or, for the plane with
+    eps_frac > 0, 5-ray bundles (kr_bundles_init_emit_dev_f64) -> trace (kr_trace_dev_f64 with caustic_trace_params_source) -> gather + Jacobian
+    (kr_post_caustic_source_dev_f64).  The sphere has no bundle mode: eps_frac is not read.  flags = 0 is the strict arithmetic (the apps' default).
+    Only the maps are read back.  Returns source_caustic_from_words(...) plus "stats" (the trace's kr_stats), "eps_x", "eps_y" and the geometry of
+    caustic_trace_params_source."""
+    L = lib()
+    if integrator not in (capi.RK4, capi.RK45):
+        raise KrError("caustic_source_map: the integrator must be RK4 or RK45")
+    p, geo = caustic_trace_params_source(imageplane_spec, kind, r_lim, z_s, r_max, integrator, rk45_tol, precision, flags, steplim)
+    bundles = kind == "plane" and eps_frac > 0
+    n, nx, ny = bundles_count(imageplane_spec) if bundles else imageplane_count(imageplane_spec)
+    if n <= 0:
+        raise KrError("caustic_source_map: empty ray grid")
+    eps_x, eps_y = (eps_frac * imageplane_spec.dx, eps_frac * imageplane_spec.dy) if bundles else (imageplane_spec.dx, imageplane_spec.dy)
+    sm = source_map_struct(kind, nx, ny, eps_x, eps_y, bundles, geo.get("incl_rad", 0.0), imageplane_spec.phi0)
+    nw = source_caustic_words(sm)
+    d_rays, d_maps = C.c_void_p(), C.c_void_p()
+    st = Stats()
+    try:
+        capi.check(L, L.kr_malloc(C.byref(d_rays), n * capi.RAY_F64.itemsize), "kr_malloc")
+        capi.check(L, L.kr_malloc(C.byref(d_maps), nw * 8), "kr_malloc")
+        if bundles:
+            capi.check(L, L.kr_bundles_init_emit_dev_f64(C.byref(imageplane_spec), eps_frac, 0.0, 1, 0, d_rays, n, None), "kr_bundles_init_emit")
+        else:
+            capi.check(L, L.kr_imageplane_init_dev_f64(C.byref(imageplane_spec), d_rays, n, None), "kr_imageplane_init")
+        capi.check(L, L.kr_trace_dev_f64(C.byref(p), d_rays, n, None, C.byref(st)), "kr_trace_dev")
+        capi.check(L, L.kr_post_caustic_source_dev_f64(C.byref(sm), d_rays, n, d_maps, None), "kr_post_caustic_source")
+        out = np.zeros(nw)
+        capi.check(L, L.kr_memcpy_d2h(_ptr(out), d_maps, nw * 8), "kr_memcpy_d2h")
+    finally:
+        for d in (d_rays, d_maps):
+            if d.value:
+                L.kr_free(d)
+    res = source_caustic_from_words(sm, out)
+    res.update(geo, stats=st.as_dict(), eps_x=eps_x, eps_y=eps_y)
+    return res
+
+
 def path_spec(write_step=1, write_rmin=-1.0, write_rmax=-1.0):
     w = capi.PathSpec()
     w.write_step, w.write_rmin, w.write_rmax = int(write_step), write_rmin, write_rmax

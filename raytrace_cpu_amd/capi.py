@@ -94,6 +94,11 @@ class CausticMap(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("r_isco", "r_disc", "eps_x", "eps_y")] + [(n, C.c_int32) for n in ("nx", "ny", "bundles", "pad")]
 
 
+class SourceMap(C.Structure):
+    """kr_source_map: what the source-sphere / source-plane caustic pass needs besides the records (include/kr_trace.h has the per-pixel rules)."""
+    _fields_ = [(n, C.c_int32) for n in ("kind", "bundles", "nx", "ny")] + [(n, C.c_double) for n in ("eps_x", "eps_y", "sin_incl", "cos_incl", "sin_phi0", "cos_phi0")]
+
+
 class PathSpec(C.Structure):
     """kr_path_spec: write_step and the radial window of run_raytrace's trajectory dump (include/kr_trace.h has the write rule)."""
     _fields_ = [("write_rmin", C.c_double), ("write_rmax", C.c_double), ("write_step", C.c_int32), ("pad", C.c_int32)]
@@ -215,6 +220,7 @@ PROTOTYPES = {
     "kr_bundles_init_emit_dev_f64": (_int, [P(ImagePlaneSpec), _dbl, _dbl, _int, _int, _vp, _i64, _vp]),
     "kr_post_caustic_disc_dev_f64": (_int, [_dbl, _int, P(CausticMap), _vp, _i64, _vp, _vp]),
     "kr_caustic_suppress_dev_f64": (_int, [P(CausticMap), _vp, _vp]),
+    "kr_post_caustic_source_dev_f64": (_int, [P(SourceMap), _vp, _i64, _vp, _vp]),
     "kr_debug_arith_f64": (_int, [_int, _vp, _vp, _vp, _i64]),
     "kr_host_attach": (_int, [_vp, _i64, _i32]),
     "kr_host_detach": (_int, [_vp]),

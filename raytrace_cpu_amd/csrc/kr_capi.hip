@@ -812,6 +812,13 @@ int kr_caustic_suppress_dev_f64(const kr_caustic_map* m, void* d_maps, void* st)
     return on_device(d_maps, "kr_caustic_suppress: null argument", [&] { return caustic_suppress_dev(m, d_maps, (hipStream_t) st); });
 }
 
+int kr_post_caustic_source_dev_f64(const kr_source_map* m, const void* d, int64_t n, void* d_maps, void* st)
+{
+    const int rc = source_map_validate(m, n, "kr_post_caustic_source");
+    if (rc != KR_OK) return rc;
+    return on_device(d && d_maps, "kr_post_caustic_source: null argument", [&] { return post_caustic_source_dev(m, d, d_maps, (hipStream_t) st); });
+}
+
 // ---- diagnostics ---------------------------------------------------------------------------------------------
 int kr_debug_arith_f64(int op, const double* a, const double* b, double* out, int64_t n)
 {
