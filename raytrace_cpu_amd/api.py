@@ -286,18 +286,50 @@ def bundles_count(spec):
     return n, nx.value, ny.value
 
 
+def _map_words(m, planes, counts, words=None):
+    """Length of a map buffer of len(planes) planes of nx ny and len(counts) counts; with `words`, that buffer as a dict instead."""
+    npix = m.nx * m.ny
+    if words is None:
+        return len(planes) * npix + len(counts)
+    words = np.asarray(words, dtype=np.float64)
+    out = {k: words[q * npix:(q + 1) * npix].reshape(m.nx, m.ny).copy() for q, k in enumerate(planes)}
+    out.update({k: int(round(float(words[len(planes) * npix + q]))) for q, k in enumerate(counts)})
+    return out
+
+
+def _resident_maps(imageplane_spec, p, n, nw, bundle_eps_frac, grid_init, passes):
+    """What the caustic maps share on the device: the 5-ray bundles (bundle_eps_frac > 0) or grid_init(d_rays) -> trace -> every pass(d_rays, d_maps),
+    each a (name, call) pair -> the nw map words read back.  Returns (words, stats)."""
+    L = lib()
+    d_rays, d_maps = C.c_void_p(), C.c_void_p()
+    st = Stats()
+    try:
+        capi.check(L, L.kr_malloc(C.byref(d_rays), n * capi.RAY_F64.itemsize), "kr_malloc")
+        capi.check(L, L.kr_malloc(C.byref(d_maps), nw * 8), "kr_malloc")
+        if bundle_eps_frac > 0:
+            capi.check(L, L.kr_bundles_init_emit_dev_f64(C.byref(imageplane_spec), bundle_eps_frac, 0.0, 1, 0, d_rays, n, None), "kr_bundles_init_emit")
+        else:
+            capi.check(L, grid_init[1](d_rays), grid_init[0])
+        capi.check(L, L.kr_trace_dev_f64(C.byref(p), d_rays, n, None, C.byref(st)), "kr_trace_dev")
+        for name, call in passes:
+            capi.check(L, call(d_rays, d_maps), name)
+        out = np.zeros(nw)
+        capi.check(L, L.kr_memcpy_d2h(_ptr(out), d_maps, nw * 8), "kr_memcpy_d2h")
+    finally:
+        for d in (d_rays, d_maps):
+            if d.value:
+                L.kr_free(d)
+    return out, st.as_dict()
+
+
 def caustic_words(cm):
     """Length of the map buffer of the caustic entry points: nine planes of nx ny and seven counts (include/kr_trace.h, kr_caustic_map)."""
-    return len(CAUSTIC_PLANES) * cm.nx * cm.ny + len(CAUSTIC_COUNTS)
+    return _map_words(cm, CAUSTIC_PLANES, CAUSTIC_COUNTS)
 
 
 def caustic_from_words(cm, words):
     """The map buffer as a dict: the nine planes as (nx, ny) arrays ([ix, iy], like Array2D) and the seven counts as ints."""
-    npix = cm.nx * cm.ny
-    words = np.asarray(words, dtype=np.float64)
-    out = {k: words[q * npix:(q + 1) * npix].reshape(cm.nx, cm.ny).copy() for q, k in enumerate(CAUSTIC_PLANES)}
-    out.update({k: int(round(float(words[len(CAUSTIC_PLANES) * npix + q]))) for q, k in enumerate(CAUSTIC_COUNTS)})
-    return out
+    return _map_words(cm, CAUSTIC_PLANES, CAUSTIC_COUNTS, words)
 
 
 def caustic_trace_params(imageplane_spec, r_disc, integrator=capi.RK4, rk45_tol=1e-8, precision=100, flags=0, steplim=0):
@@ -333,27 +365,12 @@ def caustic_map(imageplane_spec, r_disc, integrator=capi.RK4, eps_frac=0.01, rk4
     cm.r_isco, cm.r_disc, cm.nx, cm.ny, cm.bundles = r_isco, r_disc, nx, ny, int(bundles)
     cm.eps_x, cm.eps_y = (eps_frac * imageplane_spec.dx, eps_frac * imageplane_spec.dy) if bundles else (imageplane_spec.dx, imageplane_spec.dy)
     spin = -1 * imageplane_spec.spin
-    nw = caustic_words(cm)
-    d_rays, d_maps = C.c_void_p(), C.c_void_p()
-    st = Stats()
-    try:
-        capi.check(L, L.kr_malloc(C.byref(d_rays), n * capi.RAY_F64.itemsize), "kr_malloc")
-        capi.check(L, L.kr_malloc(C.byref(d_maps), nw * 8), "kr_malloc")
-        if bundles:
-            capi.check(L, L.kr_bundles_init_emit_dev_f64(C.byref(imageplane_spec), eps_frac, 0.0, 1, 0, d_rays, n, None), "kr_bundles_init_emit")
-        else:
-            capi.check(L, L.kr_imageplane_init_emit_dev_f64(C.byref(imageplane_spec), 0, 1, 0.0, 1, 0, d_rays, n, None), "kr_imageplane_init_emit")
-        capi.check(L, L.kr_trace_dev_f64(C.byref(p), d_rays, n, None, C.byref(st)), "kr_trace_dev")
-        capi.check(L, L.kr_post_caustic_disc_dev_f64(spin, 1, C.byref(cm), d_rays, n, d_maps, None), "kr_post_caustic_disc")
-        capi.check(L, L.kr_caustic_suppress_dev_f64(C.byref(cm), d_maps, None), "kr_caustic_suppress")
-        out = np.zeros(nw)
-        capi.check(L, L.kr_memcpy_d2h(_ptr(out), d_maps, nw * 8), "kr_memcpy_d2h")
-    finally:
-        for d in (d_rays, d_maps):
-            if d.value:
-                L.kr_free(d)
+    out, stats = _resident_maps(imageplane_spec, p, n, caustic_words(cm), eps_frac if bundles else 0.0,
+                                ("kr_imageplane_init_emit", lambda d_rays: L.kr_imageplane_init_emit_dev_f64(C.byref(imageplane_spec), 0, 1, 0.0, 1, 0, d_rays, n, None)),
+                                (("kr_post_caustic_disc", lambda d_rays, d_maps: L.kr_post_caustic_disc_dev_f64(spin, 1, C.byref(cm), d_rays, n, d_maps, None)),
+                                 ("kr_caustic_suppress", lambda d_rays, d_maps: L.kr_caustic_suppress_dev_f64(C.byref(cm), d_maps, None))))
     res = caustic_from_words(cm, out)
-    res.update(stats=st.as_dict(), r_isco=r_isco, eps_x=cm.eps_x, eps_y=cm.eps_y)
+    res.update(stats=stats, r_isco=r_isco, eps_x=cm.eps_x, eps_y=cm.eps_y)
     return res
 
 
@@ -365,18 +382,15 @@ SOURCE_KINDS = ("sphere", "plane")
 
 def source_caustic_words(sm):
     """Length of the map buffer of kr_post_caustic_source_dev_f64: eight planes of nx ny and three counts (include/kr_trace.h, kr_source_map)."""
-    return 8 * sm.nx * sm.ny + 3
+    kind = SOURCE_KINDS[sm.kind]
+    return _map_words(sm, SOURCE_CAUSTIC_PLANES[kind], SOURCE_CAUSTIC_COUNTS[kind])
 
 
 def source_caustic_from_words(sm, words):
     """The map buffer as a dict: the eight planes as (nx, ny) arrays ([ix, iy], like Array2D), named after the kind's FITS extensions, and the three
     counts as ints."""
     kind = SOURCE_KINDS[sm.kind]
-    npix = sm.nx * sm.ny
-    words = np.asarray(words, dtype=np.float64)
-    out = {k: words[q * npix:(q + 1) * npix].reshape(sm.nx, sm.ny).copy() for q, k in enumerate(SOURCE_CAUSTIC_PLANES[kind])}
-    out.update({k: int(round(float(words[8 * npix + q]))) for q, k in enumerate(SOURCE_CAUSTIC_COUNTS[kind])})
-    return out
+    return _map_words(sm, SOURCE_CAUSTIC_PLANES[kind], SOURCE_CAUSTIC_COUNTS[kind], words)
 
 
 def caustic_trace_params_source(imageplane_spec, kind, r_lim=None, z_s=None, r_max=None, integrator=capi.RK45, rk45_tol=1e-8, precision=100, flags=0, steplim=0):
@@ -431,26 +445,11 @@ def caustic_source_map(imageplane_spec, kind, r_lim=None, z_s=None, r_max=None, 
         raise KrError("caustic_source_map: empty ray grid")
     eps_x, eps_y = (eps_frac * imageplane_spec.dx, eps_frac * imageplane_spec.dy) if bundles else (imageplane_spec.dx, imageplane_spec.dy)
     sm = source_map_struct(kind, nx, ny, eps_x, eps_y, bundles, geo.get("incl_rad", 0.0), imageplane_spec.phi0)
-    nw = source_caustic_words(sm)
-    d_rays, d_maps = C.c_void_p(), C.c_void_p()
-    st = Stats()
-    try:
-        capi.check(L, L.kr_malloc(C.byref(d_rays), n * capi.RAY_F64.itemsize), "kr_malloc")
-        capi.check(L, L.kr_malloc(C.byref(d_maps), nw * 8), "kr_malloc")
-        if bundles:
-            capi.check(L, L.kr_bundles_init_emit_dev_f64(C.byref(imageplane_spec), eps_frac, 0.0, 1, 0, d_rays, n, None), "kr_bundles_init_emit")
-        else:
-            capi.check(L, L.kr_imageplane_init_dev_f64(C.byref(imageplane_spec), d_rays, n, None), "kr_imageplane_init")
-        capi.check(L, L.kr_trace_dev_f64(C.byref(p), d_rays, n, None, C.byref(st)), "kr_trace_dev")
-        capi.check(L, L.kr_post_caustic_source_dev_f64(C.byref(sm), d_rays, n, d_maps, None), "kr_post_caustic_source")
-        out = np.zeros(nw)
-        capi.check(L, L.kr_memcpy_d2h(_ptr(out), d_maps, nw * 8), "kr_memcpy_d2h")
-    finally:
-        for d in (d_rays, d_maps):
-            if d.value:
-                L.kr_free(d)
+    out, stats = _resident_maps(imageplane_spec, p, n, source_caustic_words(sm), eps_frac if bundles else 0.0,
+                                ("kr_imageplane_init", lambda d_rays: L.kr_imageplane_init_dev_f64(C.byref(imageplane_spec), d_rays, n, None)),
+                                (("kr_post_caustic_source", lambda d_rays, d_maps: L.kr_post_caustic_source_dev_f64(C.byref(sm), d_rays, n, d_maps, None)),))
     res = source_caustic_from_words(sm, out)
-    res.update(geo, stats=st.as_dict(), eps_x=eps_x, eps_y=eps_y)
+    res.update(geo, stats=stats, eps_x=eps_x, eps_y=eps_y)
     return res
 
 

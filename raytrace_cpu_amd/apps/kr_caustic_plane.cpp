@@ -17,7 +17,7 @@
 using namespace std;
 
 #include "../host/raytracer/ray_destination.h"
-#include "source_caustic.h"
+#include "caustic_app.h"
 
 int main(int argc, char** argv)
 try {
@@ -25,7 +25,8 @@ try {
     ParameterArgs args(argc, argv);
     const string par_name = args.key_exists("--parfile") ? args.get_string_parameter("--parfile") : string("../par/caustic_plane.par");
     ParameterFile par(par_name);
-    const krapp::SourceCausticSetup s(args, par);
+    const krapp::CausticSetup s(args, par, [] { return 20.0; }, -1,
+                                [](const string& name) { cerr << "Warning: unknown integrator '" << name << "'; using RK45" << endl; });
     const double z_s = args.key_exists("--z_s") ? args.get_parameter<double>("--z_s") : par.get_parameter<double>("z_s", s.dist);
     const double r_max = args.key_exists("--r_max") ? args.get_parameter<double>("--r_max") : par.get_parameter<double>("r_max", 4.0 * z_s);
     const double bundle_eps_frac = par.get_parameter<double>("bundle_eps_frac", 0.01);
@@ -52,9 +53,16 @@ try {
     sm.sin_incl = sin(incl_rad); sm.cos_incl = cos(incl_rad);        // the C library's, as source_coords evaluates them (ray_destination.h)
     sm.sin_phi0 = sin(s.plane_phi0); sm.cos_phi0 = cos(s.plane_phi0);
 
-    krapp::SourceCausticTimes t;
-    const unique_ptr<krapp::PinnedDoubles> h = krapp::run_source_caustic(s, p, sm, bundle_eps_frac, t);
+    sm.bundles = use_bundles ? 1 : 0;
+    const int64_t n = s.rays(bundle_eps_frac, sm.nx, sm.ny);
     const int64_t npix = static_cast<int64_t>(sm.nx) * sm.ny;
+    const kr_imageplane plane = s.plane();
+    krapp::require_device();
+    krapp::CausticTimes t;
+    const unique_ptr<krapp::PinnedDoubles> h = krapp::run_caustic(
+        s, p, bundle_eps_frac, n, 8 * npix + 3, {"imageplane_init", [&](void* rays, int64_t m, void*) { return kr_imageplane_init_dev_f64(&plane, rays, m, nullptr); }},
+        {"bundles_init", [&](void* rays, int64_t m, void*) { return kr_bundles_init_emit_dev_f64(&plane, bundle_eps_frac, 0.0, 1, 0, rays, m, nullptr); }},
+        {{"maps", [&](void* rays, int64_t m, void* maps) { return kr_post_caustic_source_dev_f64(&sm, rays, m, maps, nullptr); }}}, t);
     const double* counts = h->data() + 8 * npix;
     const long hit_count = static_cast<long>(counts[0]), captured_count = static_cast<long>(counts[1]), steplim_count = static_cast<long>(counts[2]);
     cout << hit_count << " rays hit source plane" << endl;
@@ -64,7 +72,7 @@ try {
     // ---- FITS (caustic_plane.cpp:397-483) -------------------------------------------------------------------------------------
     krapp::Stopwatch clock;
     const double SENTINEL = 1e30;
-    vector<vector<double*>> rows = krapp::plane_rows(h->data(), sm.nx, sm.ny);
+    vector<vector<double*>> rows = krapp::plane_rows(h->data(), 8, sm.nx, sm.ny);
     FITSOutput<double> fits(s.out_name);
     fits.create_primary();
     fits.write_comment("Kerr BH caustic / critical curve mapping \xe2\x80\x94 flat source plane");
@@ -98,7 +106,7 @@ try {
     write_plane(7, "EQUAT_CROSS", {"Equatorial-plane (theta=pi/2) crossing count during propagation"});
     fits.close();
 
-    if (s.timing) krapp::print_timing(t, clock.lap_ms());
+    if (s.timing) krapp::print_source_timing(t, clock.lap_ms());
     cout << "Written to " << s.out_name << endl;
     return 0;
 } catch (const exception& e) {

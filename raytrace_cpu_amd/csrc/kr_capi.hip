@@ -799,15 +799,14 @@ int kr_bundles_init_emit_dev_f64(const kr_imageplane* s, double eps_frac, double
 
 int kr_post_caustic_disc_dev_f64(double spin, int reverse, const kr_caustic_map* m, void* d, int64_t n, void* d_maps, void* st)
 {
-    const int rc = caustic_validate(m, "kr_post_caustic_disc");
+    const int rc = caustic_validate(m, n, "kr_post_caustic_disc");
     if (rc != KR_OK) return rc;
-    if (n < (m->bundles ? 5 : 1) * (int64_t) m->nx * m->ny) return invalid(m->bundles ? "kr_post_caustic_disc: n smaller than 5 nx ny" : "kr_post_caustic_disc: n smaller than nx ny");
     return on_device(d && d_maps, "kr_post_caustic_disc: null argument", [&] { return post_caustic_dev(spin, reverse, m, d, n, d_maps, (hipStream_t) st); });
 }
 
 int kr_caustic_suppress_dev_f64(const kr_caustic_map* m, void* d_maps, void* st)
 {
-    const int rc = caustic_validate(m, "kr_caustic_suppress");
+    const int rc = caustic_validate(m, INT64_MAX, "kr_caustic_suppress");       // no records here
     if (rc != KR_OK) return rc;
     return on_device(d_maps, "kr_caustic_suppress: null argument", [&] { return caustic_suppress_dev(m, d_maps, (hipStream_t) st); });
 }

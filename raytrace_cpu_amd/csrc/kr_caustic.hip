@@ -1,15 +1,22 @@
-// kr_caustic.hip -- critical-curve (caustic) maps of the disc seen on an image plane (include/kr_trace.h, kr_caustic_map): the reference's
-// src/caustic/caustic_discplane.cpp with the rays where they already are, in HBM.  The reference builds the 5-ray bundles in a serial host loop
-// (imageplane_bundles.h:150-199), and gathers, differences and filters rays[] on one core (caustic_discplane.cpp:219-493); here
+// kr_caustic.hip -- critical-curve (caustic) maps of the lens map image plane -> a surface, per image-plane pixel (include/kr_trace.h): of the disc
+// (kr_caustic_map; the reference's src/caustic/caustic_discplane.cpp), of the source sphere and of a flat source plane behind the hole (kr_source_map;
+// src/caustic/caustic_sourceplane.cpp, src/caustic/caustic_plane.cpp), with the rays where they already are, in HBM.  The reference builds the 5-ray
+// bundles in a serial host loop (imageplane_bundles.h:150-199), and gathers, differences and filters rays[] on one core; here
 //   bundles_init_emit_kernel   ImagePlaneBundles ctor + redshift_start(0, reverse = true)                 imageplane_bundles.h:150-199, raytracer.cpp:342-417
-//   post_caustic_kernel        redshift(dest, reverse) + the seven per-pixel planes + the diagnostic counts  caustic_discplane.cpp:217-276 / :349-401
-//                              and, for bundles, the Jacobian from the four satellites                        :279-334
-//   grid_jacobian_kernel       grid-neighbour mode: central differences of the X_DISC / Y_DISC planes         :403-439
-//   suppress_mark_kernel, suppress_clear_kernel   the branch-boundary filter on a snapshot of SIGN_J        :455-493
+//   bundle_gather_kernel       5-ray bundles: the per-pixel planes and counts from the centre rays and     caustic_discplane.cpp:217-334, caustic_plane.cpp:207-299
+//                              the Jacobian from the four satellites
+//   grid_gather_kernel         one ray per pixel: the per-pixel planes and counts                          caustic_discplane.cpp:349-401, caustic_sourceplane.cpp:180-232,
+//                                                                                                          caustic_plane.cpp:315-349
+//   neighbour_jacobian_kernel  grid-neighbour mode: central differences of the two coordinate planes;      caustic_discplane.cpp:403-439, caustic_sourceplane.cpp:264-305,
+//                              the sphere wraps its phi differences                                        caustic_plane.cpp:357-392
+//   suppress_mark_kernel, suppress_clear_kernel   the disc's branch-boundary filter on a snapshot of SIGN_J  caustic_discplane.cpp:455-493
+// What differs between the three maps is a "surface" (DiscSurface, SphereSurface, PlaneSurface below): what a record becomes, what the pixel's own ray
+// keeps, the planes and counts of a pixel, and whether the pass stores to the records -- a property of the surface's type: the disc computes
+// redshift(dest, reverse) and stores it, the other two take const records.
 // All of them are streaming passes.  Records are read ONE PER WORK-ITEM, like every other pass over the 144-byte records (adjacent lanes read
 // adjacent records: a wave covers 9216 contiguous bytes, every 128-byte line it touches is used whole), NOT one bundle (720 bytes) per work-item:
 // the per-ray work -- redshift_dest_value, sincos, atan2, sincos -- is what the pass computes, so it gets five times the lanes; the five end points
-// of a bundle meet in LDS (32 bytes per ray), and the lanes that own a pixel then write the nine planes at consecutive addresses.  DESIGN.md 4.2.
+// of a bundle meet in LDS (32 bytes per ray), and the lanes that own a pixel then write the planes at consecutive addresses.  DESIGN.md 4.2.
 
 #include <hip/hip_runtime.h>
 
@@ -25,10 +32,17 @@ namespace kr {
 namespace {
 
 constexpr int kBundle = 5;                 // ImagePlaneBundles::RAYS_PER_BUNDLE: centre, east, west, north, south
-constexpr double kSentinel = 1e30;         // caustic_discplane.cpp:152
-constexpr int kPlanes = 9, kCounts = 7;
-enum Plane { P_DET = 0, P_SIGN, P_ORDER, P_HIT, P_RADIUS, P_PHI, P_X, P_Y, P_REDSHIFT };
-enum Count { C_DISC = 0, C_HORIZON, C_RLIM, C_STEPLIM, C_OUT_OF_RANGE, C_OTHER, C_SUPPRESSED };
+constexpr double kSentinel = 1e30;         // caustic_discplane.cpp:152, caustic_sourceplane.cpp:259, caustic_plane.cpp:161
+enum Plane { P_DET = 0, P_SIGN, P_ORDER, P_HIT };          // the first four planes of every map; a surface names the rest
+enum Kind { K_SPHERE = 0, K_PLANE = 1 };                   // kr_source_map::kind
+
+// the pixel grid of either map description
+struct Pixels {
+    int nx, ny;
+    double eps_x, eps_y;
+};
+template <typename M>
+Pixels pixels_of(const M& m) { return Pixels{m.nx, m.ny, m.eps_x, m.eps_y}; }
 
 // ---- ImagePlaneBundles ctor (imageplane_bundles.h:150-199) + redshift_start(0, true) in one pass: slot s is member s % 5 of bundle s / 5 ------
 KR_DEV kr_ray_f64 bundle_ray(const kr_imageplane& s, const PlaneTrig& tr, long long n_grid, int Ny, double eps_x, double eps_y, double a, long long slot)
@@ -62,148 +76,294 @@ bundles_init_emit_kernel(kr_ray_f64* __restrict__ rays, long long n, kr_imagepla
     }
 }
 
-// ---- the epilogue.  RPB rays per pixel (5: bundles, 1: the plain ImagePlane grid), BPB pixels per workgroup pass -----------------------------
-// what a satellite contributes to the Jacobian, and the centre to everything else
+// ---- the surfaces ---------------------------------------------------------------------------------------------------------------------------
+// what one record contributes: to its own pixel when it is the ray through the pixel, to the Jacobian when it is a satellite
 struct EndPoint {
-    double phi, x, y;
-    int valid, flips;
+    double phi, u, v;
+    int hit, flips;
 };
+
+// the disc (caustic_discplane.cpp:170-202, :255-276): (u, v) = (X_DISC, Y_DISC)
+struct DiscSurface {
+    using Ray = kr_ray_f64;                // redshift is stored back
+    static constexpr int kPlanes = 9, kCounts = 7, kU = 6, kV = 7;
+    static constexpr bool kHasBundles = true, kWrapsV = false;
+    enum { P_RADIUS = 4, P_PHI, P_X, P_Y, P_REDSHIFT };
+    enum { C_DISC = 0, C_HORIZON, C_RLIM, C_STEPLIM, C_OUT_OF_RANGE, C_OTHER, C_SUPPRESSED };
+    struct Centre {
+        double r, phi_s, g;
+        int order, cls;           // cls: 0 none, else the count of its failure mode
+    };
+    double spin, r_isco, r_disc;
+    int reverse;
+
+    // (the centre's order and failure mode are worked out here, by every lane beside its neighbours, not by the one wave that writes the pixels)
+    KR_DEV EndPoint end(Ray* ray, Centre& c) const
+    {
+        const double r = ray->r, phi = ray->phi;
+        const int steps = ray->steps, status = ray->status, flips = ray->rdot_flips;
+        const double g = redshift_dest_value<double>(r, ray->theta, ray->k, ray->h, ray->Q, ray->rdot_sign, ray->thetadot_sign, ray->emit, spin, reverse);
+        ray->redshift = g;
+        // valid_hit, caustic_discplane.cpp:177-182
+        const bool valid = steps > 0 && r >= r_isco && r < r_disc && g > 0;
+        EndPoint e = {phi, 0, 0, valid ? 1 : 0, flips};
+        c = Centre{r, 0, g, -1, 0};
+        if (valid) {
+            // disc_xy, :170-174: phi_s = atan2(sin phi, cos phi) of the ACCUMULATED phi, then r cos / r sin of phi_s
+            double sp, cp;
+            kr_sincos_f64(phi, sp, cp);
+            c.phi_s = krcr::kr_atan2_cr(sp, cp);
+            kr_sincos_f64(c.phi_s, sp, cp);
+            e.u = r * cp;
+            e.v = r * sp;
+            // disc_order, :198-202
+            const int phi_ord = (int) (kr_abs(phi) / (2 * kPi));
+            const int r_ord = flips / 2;
+            c.order = phi_ord > r_ord ? phi_ord : r_ord;
+        }
+        // the failure modes of the centre rays, :255-276
+        if (steps > 0 && (r < r_isco || r >= r_disc || g <= 0)) {
+            c.cls = C_OUT_OF_RANGE;
+        } else if (steps <= 0 || !(status & KR_STATUS_DEST)) {
+            if (status & KR_STATUS_HORIZON) c.cls = C_HORIZON;
+            else if (status & KR_STATUS_RLIM) c.cls = C_RLIM;
+            else if (status & KR_STATUS_STEPLIM) c.cls = C_STEPLIM;
+            else c.cls = C_OTHER;
+        }
+        return e;
+    }
+
+    KR_DEV void write_pixel(double* __restrict__ maps, long long npix, long long px, const EndPoint& e, const Centre& c, unsigned* cnt) const
+    {
+        const bool hit = e.hit != 0;
+        cnt[C_DISC] += hit;
+#pragma unroll
+        for (int k = C_HORIZON; k <= C_OTHER; k++) cnt[k] += c.cls == k;         // every index a constant: the counters stay in registers
+        maps[P_ORDER * npix + px] = (double) c.order;
+        maps[P_HIT * npix + px] = hit ? 1.0 : 0.0;
+        maps[P_RADIUS * npix + px] = hit ? c.r : 0.0;
+        maps[P_PHI * npix + px] = hit ? c.phi_s : 0.0;
+        maps[P_X * npix + px] = hit ? e.u : 0.0;
+        maps[P_Y * npix + px] = hit ? e.v : 0.0;
+        maps[P_REDSHIFT * npix + px] = hit ? c.g : 0.0;
+    }
+};
+
+// the sphere at r_lim (caustic_sourceplane.cpp:191-219): escaped = steps > 0 && RLIM, THETA_S = theta, PHI_S = atan2(sin, cos) of the ACCUMULATED phi
+// (thousands of pi on rays that wind round the axis: kr_sincos_f64 hands |phi| >= 1024 to the library's full argument reduction),
+// ORDER = max(floor(|phi| / pi) - 1, 0)
+KR_DEV EndPoint sphere_end(const kr_ray_f64* ray, int& order)
+{
+    const double phi = ray->phi;
+    EndPoint e = {phi, 0, 0, (ray->steps > 0 && (ray->status & KR_STATUS_RLIM)) ? 1 : 0, ray->rdot_flips};
+    order = -1;
+    if (e.hit) {
+        double sp, cp;
+        kr_sincos_f64(phi, sp, cp);
+        e.u = ray->theta;
+        e.v = krcr::kr_atan2_cr(sp, cp);
+        const int phi_order = (int) floor(kr_abs(phi) / kPi);
+        order = phi_order > 0 ? phi_order - 1 : 0;
+    }
+    return e;
+}
+
+// the flat plane (caustic_plane.cpp:180-189, ray_destination.h:151-160): valid_hit = steps > 0 && DEST, (X_S, Y_S) = source_coords(r, theta, phi) in
+// the reference's association, ORDER = max((int) (|phi| / 2 pi), rdot_flips / 2)
+KR_DEV EndPoint plane_end(const kr_ray_f64* ray, const kr_source_map& m, int& order)
+{
+    const double r = ray->r, theta = ray->theta, phi = ray->phi;
+    EndPoint e = {phi, 0, 0, (ray->steps > 0 && (ray->status & KR_STATUS_DEST)) ? 1 : 0, ray->rdot_flips};
+    order = -1;
+    if (e.hit) {
+        double st, ct, sp, cp;
+        kr_sincos_f64(theta, st, ct);
+        kr_sincos_f64(phi, sp, cp);
+        const double X = r * st * cp;
+        const double Y = r * st * sp;
+        const double Z = r * ct;
+        e.u = -X * m.sin_phi0 + Y * m.cos_phi0;
+        e.v = -X * m.cos_incl * m.cos_phi0 - Y * m.cos_incl * m.sin_phi0 + Z * m.sin_incl;
+        const int phi_ord = (int) (kr_abs(phi) / (2 * kPi));
+        const int r_ord = e.flips / 2;
+        order = phi_ord > r_ord ? phi_ord : r_ord;
+    }
+    return e;
+}
+
+// what the two source maps share: (u, v) = (THETA_S, PHI_S) or (X_S, Y_S), the six planes and the three counts of the ray through pixel px
+// (caustic_sourceplane.cpp:187-231, caustic_plane.cpp:213-239)
+struct SourceSurface {
+    using Ray = const kr_ray_f64;          // the records are only read
+    static constexpr int kPlanes = 8, kCounts = 3, kU = 4, kV = 5;
+    enum { P_U = 4, P_V, P_FLIPS, P_EQUAT };
+    enum { C_HIT = 0, C_CAPTURED, C_STEPLIM };
+    struct Centre {
+        int order, steps, status, equat;
+    };
+    static KR_DEV Centre centre_of(Ray* ray, int order) { return Centre{order, ray->steps, ray->status, ray->equatorial_crossings}; }
+
+    KR_DEV void write_pixel(double* __restrict__ maps, long long npix, long long px, const EndPoint& e, const Centre& c, unsigned* cnt) const
+    {
+        const bool hit = e.hit != 0;
+        if (hit) cnt[C_HIT]++;
+        else if (c.status & KR_STATUS_HORIZON) cnt[C_CAPTURED]++;
+        if (c.steps <= 0 || (c.status & KR_STATUS_STEPLIM)) cnt[C_STEPLIM]++;
+        maps[P_ORDER * npix + px] = (double) c.order;
+        maps[P_HIT * npix + px] = hit ? 1.0 : 0.0;
+        maps[P_U * npix + px] = hit ? e.u : __builtin_nan("");
+        maps[P_V * npix + px] = hit ? e.v : __builtin_nan("");
+        maps[P_FLIPS * npix + px] = (double) e.flips;
+        maps[P_EQUAT * npix + px] = (double) c.equat;
+    }
+};
+struct SphereSurface : SourceSurface {
+    static constexpr bool kHasBundles = false, kWrapsV = true;         // V is an angle in [-pi, pi]
+    KR_DEV EndPoint end(Ray* ray, Centre& c) const
+    {
+        int order;
+        const EndPoint e = sphere_end(ray, order);
+        c = centre_of(ray, order);
+        return e;
+    }
+};
+struct PlaneSurface : SourceSurface {
+    static constexpr bool kHasBundles = true, kWrapsV = false;
+    kr_source_map m;
+    KR_DEV EndPoint end(Ray* ray, Centre& c) const
+    {
+        int order;
+        const EndPoint e = plane_end(ray, m, order);
+        c = centre_of(ray, order);
+        return e;
+    }
+};
+
+// COUNTS counters per work-item: wave shuffle -> workgroup (LDS) -> one atomic per non-zero word and workgroup.  Every work-item of the workgroup calls this.
+template <int WAVES, int COUNTS>
+KR_DEV void flush_counts(const unsigned* cnt, unsigned (*part)[COUNTS], double* __restrict__ counts)
+{
+    const int t = threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < COUNTS; k++) {
+        const unsigned v = wave_sum(cnt[k]);
+        if ((t & 63) == 0) part[t >> 6][k] = v;
+    }
+    __syncthreads();
+    if (t < COUNTS) {
+        unsigned v = 0;
+#pragma unroll
+        for (int w = 0; w < WAVES; w++) v += part[w][t];
+        if (v) atomicAdd(&counts[t], (double) v);
+    }
+}
+
+// ---- grid mode: record px is the ray through pixel px = ix ny + iy (ImagePlane's order); records from npix on are not pixels ----------------------
+template <typename S>
+__global__ void __launch_bounds__(kBlock)
+grid_gather_kernel(typename S::Ray* __restrict__ rays, long long n, S s, long long npix, double* __restrict__ maps)
+{
+    __shared__ unsigned part[kBlock / 64][S::kCounts];
+    unsigned cnt[S::kCounts] = {};
+    KR_GRID_STRIDE(i, n) {
+        typename S::Centre c;
+        const EndPoint e = s.end(&rays[i], c);
+        if (i < npix) s.write_pixel(maps, npix, i, e, c, cnt);
+    }
+    flush_counts<kBlock / 64, S::kCounts>(cnt, part, maps + S::kPlanes * npix);
+}
+
+// ---- bundles: record 5 px + k is member k of the bundle of pixel px; BPB pixels per workgroup pass ----------------------------------------------
 // ... one array per member in LDS: the gather reads members 5 t + k of lane t, 40 bytes apart as doubles (a 2-way bank conflict) instead of 160 as records (8-way)
 template <int N>
 struct EndPoints {
-    double phi[N], x[N], y[N];
-    int valid[N], flips[N];
-    KR_DEV void put(int i, const EndPoint& e) { phi[i] = e.phi; x[i] = e.x; y[i] = e.y; valid[i] = e.valid; flips[i] = e.flips; }
-    KR_DEV EndPoint get(int i) const { return EndPoint{phi[i], x[i], y[i], valid[i], flips[i]}; }
-};
-struct Centre {
-    double r, phi_s, g;
-    int order, cls;           // cls: 0 none, else the Count of its failure mode
+    double phi[N], u[N], v[N];
+    int hit[N], flips[N];
+    KR_DEV void put(int i, const EndPoint& e) { phi[i] = e.phi; u[i] = e.u; v[i] = e.v; hit[i] = e.hit; flips[i] = e.flips; }
+    KR_DEV EndPoint get(int i) const { return EndPoint{phi[i], u[i], v[i], hit[i], flips[i]}; }
 };
 
-template <int RPB, int BPB>
-__global__ void __launch_bounds__(RPB * BPB)
-post_caustic_kernel(kr_ray_f64* __restrict__ rays, long long n, double spin, int reverse, kr_caustic_map m, double* __restrict__ maps)
+// Jacobian from the satellites (caustic_discplane.cpp:279-334, caustic_plane.cpp:249-299)
+KR_DEV void satellite_jacobian(const EndPoint& ec, const EndPoint& ee, const EndPoint& ew, const EndPoint& en, const EndPoint& es, double eps_x, double eps_y,
+                               double& det, double& sign)
 {
-    constexpr int kThreads = RPB * BPB;
+    det = __builtin_nan("");
+    sign = 0;
+    if (ec.hit && ee.hit && ew.hit && en.hit && es.hit) {
+        const bool order_match = ee.flips == ec.flips && ew.flips == ec.flips && en.flips == ec.flips && es.flips == ec.flips &&
+                                 kr_abs(ee.phi - ec.phi) < kPi2 && kr_abs(ew.phi - ec.phi) < kPi2 && kr_abs(en.phi - ec.phi) < kPi2 &&
+                                 kr_abs(es.phi - ec.phi) < kPi2;
+        if (!order_match) {
+            det = kSentinel;
+        } else {
+            const double du_da = (ee.u - ew.u) / (2 * eps_x);
+            const double du_db = (en.u - es.u) / (2 * eps_y);
+            const double dv_da = (ee.v - ew.v) / (2 * eps_x);
+            const double dv_db = (en.v - es.v) / (2 * eps_y);
+            det = du_da * dv_db - du_db * dv_da;
+            sign = (det > 0) ? 1.0 : (det < 0) ? -1.0 : 0.0;
+        }
+    }
+}
+
+template <typename S, int BPB>
+__global__ void __launch_bounds__(kBundle * BPB)
+bundle_gather_kernel(typename S::Ray* __restrict__ rays, long long n, S s, Pixels g, double* __restrict__ maps)
+{
+    constexpr int kThreads = kBundle * BPB;
+    constexpr int kWaves = (kThreads + 63) / 64;
     __shared__ EndPoints<kThreads> ends;
-    __shared__ Centre centres[BPB];
-    __shared__ unsigned part[(BPB + 63) / 64][C_SUPPRESSED];
-    const long long npix = (long long) m.nx * m.ny;
+    __shared__ typename S::Centre centres[BPB];
+    __shared__ unsigned part[kWaves][S::kCounts];
+    const long long npix = (long long) g.nx * g.ny;
     const long long chunks = (n + kThreads - 1) / kThreads;
     const int t = threadIdx.x;
-    unsigned cnt[C_SUPPRESSED] = {0, 0, 0, 0, 0, 0};
+    unsigned cnt[S::kCounts] = {};
     for (long long chunk = blockIdx.x; chunk < chunks; chunk += gridDim.x) {       // uniform per workgroup: the barriers below are safe
         const long long i = chunk * kThreads + t;
         if (i < n) {
-            kr_ray_f64* ray = &rays[i];
-            const double r = ray->r, phi = ray->phi;
-            const int steps = ray->steps, status = ray->status, flips = ray->rdot_flips;
-            const double g = redshift_dest_value<double>(r, ray->theta, ray->k, ray->h, ray->Q, ray->rdot_sign, ray->thetadot_sign, ray->emit, spin, reverse);
-            ray->redshift = g;
-            // valid_hit, caustic_discplane.cpp:177-182
-            const bool valid = steps > 0 && r >= m.r_isco && r < m.r_disc && g > 0;
-            EndPoint e = {phi, 0, 0, valid ? 1 : 0, flips};
-            double phi_s = 0;
-            if (valid) {
-                // disc_xy, :170-174: phi_s = atan2(sin phi, cos phi) of the ACCUMULATED phi, then r cos / r sin of phi_s
-                double sp, cp;
-                kr_sincos_f64(phi, sp, cp);
-                phi_s = krcr::kr_atan2_cr(sp, cp);
-                kr_sincos_f64(phi_s, sp, cp);
-                e.x = r * cp;
-                e.y = r * sp;
-            }
-            ends.put(t, e);
-            if (t % RPB == 0) {
-                Centre c = {r, phi_s, g, -1, 0};
-                if (valid) {
-                    // disc_order, :198-202
-                    const int phi_ord = (int) (kr_abs(phi) / (2 * kPi));
-                    const int r_ord = flips / 2;
-                    c.order = phi_ord > r_ord ? phi_ord : r_ord;
-                }
-                // the failure modes of the centre rays, :255-276
-                if (steps > 0 && (r < m.r_isco || r >= m.r_disc || g <= 0)) {
-                    c.cls = C_OUT_OF_RANGE;
-                } else if (steps <= 0 || !(status & KR_STATUS_DEST)) {
-                    if (status & KR_STATUS_HORIZON) c.cls = C_HORIZON;
-                    else if (status & KR_STATUS_RLIM) c.cls = C_RLIM;
-                    else if (status & KR_STATUS_STEPLIM) c.cls = C_STEPLIM;
-                    else c.cls = C_OTHER;
-                }
-                centres[t / RPB] = c;
-            }
+            typename S::Centre c;
+            ends.put(t, s.end(&rays[i], c));
+            if (t % kBundle == 0) centres[t / kBundle] = c;
         }
         __syncthreads();
         const long long px = chunk * BPB + t;
         if (t < BPB && px < npix) {
-            const Centre c = centres[t];
-            const EndPoint ec = ends.get(t * RPB);
-            const bool hit = ec.valid != 0;
-            if (hit) cnt[C_DISC]++;
-            if (c.cls) cnt[c.cls]++;
-            maps[P_ORDER * npix + px] = hit ? (double) c.order : -1.0;
-            maps[P_HIT * npix + px] = hit ? 1.0 : 0.0;
-            maps[P_RADIUS * npix + px] = hit ? c.r : 0.0;
-            maps[P_PHI * npix + px] = hit ? c.phi_s : 0.0;
-            maps[P_X * npix + px] = hit ? ec.x : 0.0;
-            maps[P_Y * npix + px] = hit ? ec.y : 0.0;
-            maps[P_REDSHIFT * npix + px] = hit ? c.g : 0.0;
-            if (RPB == kBundle) {
-                // Jacobian from the satellites, :279-334
-                double det = __builtin_nan(""), sign = 0;
-                const EndPoint ee = ends.get(t * RPB + 1), ew = ends.get(t * RPB + 2), en = ends.get(t * RPB + 3), es = ends.get(t * RPB + 4);
-                if (hit && ee.valid && ew.valid && en.valid && es.valid) {
-                    const bool order_match = ee.flips == ec.flips && ew.flips == ec.flips && en.flips == ec.flips && es.flips == ec.flips &&
-                                             kr_abs(ee.phi - ec.phi) < kPi2 && kr_abs(ew.phi - ec.phi) < kPi2 && kr_abs(en.phi - ec.phi) < kPi2 &&
-                                             kr_abs(es.phi - ec.phi) < kPi2;
-                    if (!order_match) {
-                        det = kSentinel;
-                    } else {
-                        const double dxd_da = (ee.x - ew.x) / (2 * m.eps_x);
-                        const double dxd_db = (en.x - es.x) / (2 * m.eps_y);
-                        const double dyd_da = (ee.y - ew.y) / (2 * m.eps_x);
-                        const double dyd_db = (en.y - es.y) / (2 * m.eps_y);
-                        det = dxd_da * dyd_db - dxd_db * dyd_da;
-                        sign = (det > 0) ? 1.0 : (det < 0) ? -1.0 : 0.0;
-                    }
-                }
-                maps[P_DET * npix + px] = det;
-                maps[P_SIGN * npix + px] = sign;
-            }
+            const EndPoint ec = ends.get(t * kBundle);
+            s.write_pixel(maps, npix, px, ec, centres[t], cnt);
+            double det, sign;
+            satellite_jacobian(ec, ends.get(t * kBundle + 1), ends.get(t * kBundle + 2), ends.get(t * kBundle + 3), ends.get(t * kBundle + 4), g.eps_x, g.eps_y, det, sign);
+            maps[P_DET * npix + px] = det;
+            maps[P_SIGN * npix + px] = sign;
         }
         __syncthreads();
     }
-    // the six counters: wave shuffle -> workgroup (LDS) -> one atomic per non-zero word and workgroup (only the first BPB lanes hold any)
-    if (t < BPB) {
-#pragma unroll
-        for (int k = 0; k < C_SUPPRESSED; k++) {
-            unsigned v = cnt[k];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-            if ((t & 63) == 0) part[t >> 6][k] = v;
-        }
-    }
-    __syncthreads();
-    if (t < C_SUPPRESSED) {
-        unsigned v = 0;
-#pragma unroll
-        for (int w = 0; w < (BPB + 63) / 64; w++) v += part[w][t];
-        if (v) atomicAdd(&maps[kPlanes * npix + t], (double) v);
-    }
+    flush_counts<kWaves, S::kCounts>(cnt, part, maps + S::kPlanes * npix);
 }
 
-// ---- grid-neighbour Jacobian (caustic_discplane.cpp:403-439): one pixel per work-item over the HIT / ORDER / X_DISC / Y_DISC planes ------------
-__global__ void __launch_bounds__(kBlock)
-grid_jacobian_kernel(kr_caustic_map m, double* __restrict__ maps)
+// ---- grid-neighbour Jacobian: one pixel per work-item over the HIT / ORDER planes and the two coordinate planes pu, pv.  WRAP: v is an angle in
+//      [-pi, pi], its differences are wrapped back into that range as wrap_dphi does (caustic_sourceplane.cpp:68-73; |d| <= 2 pi, so each of its loops
+//      runs at most once) ------------------------------------------------------------------------------------------------------------------------
+template <bool WRAP>
+KR_DEV double wrapped(double d)
 {
-    const int nx = m.nx, ny = m.ny;
+    if (WRAP) {
+        if (d > kPi) d -= 2 * kPi;
+        if (d < -kPi) d += 2 * kPi;
+    }
+    return d;
+}
+
+template <bool WRAP>
+__global__ void __launch_bounds__(kBlock)
+neighbour_jacobian_kernel(Pixels g, int pu, int pv, double* __restrict__ maps)
+{
+    const int nx = g.nx, ny = g.ny;
     const long long npix = (long long) nx * ny;
     const double* hit = maps + P_HIT * npix;
     const double* order = maps + P_ORDER * npix;
-    const double* xd = maps + P_X * npix;
-    const double* yd = maps + P_Y * npix;
+    const double* u = maps + pu * npix;
+    const double* v = maps + pv * npix;
     KR_GRID_STRIDE(px, npix) {
         const int ix = (int) (px / ny), iy = (int) (px % ny);
         double det = __builtin_nan(""), sign = 0;
@@ -214,11 +374,11 @@ grid_jacobian_kernel(kr_caustic_map m, double* __restrict__ maps)
                 if (!(order[e] == ord && order[w] == ord && order[nn] == ord && order[s] == ord)) {
                     det = kSentinel;
                 } else {
-                    const double dxd_dx = (xd[e] - xd[w]) / (2 * m.eps_x);
-                    const double dxd_dy = (xd[nn] - xd[s]) / (2 * m.eps_y);
-                    const double dyd_dx = (yd[e] - yd[w]) / (2 * m.eps_x);
-                    const double dyd_dy = (yd[nn] - yd[s]) / (2 * m.eps_y);
-                    det = dxd_dx * dyd_dy - dxd_dy * dyd_dx;
+                    const double du_dx = (u[e] - u[w]) / (2 * g.eps_x);
+                    const double du_dy = (u[nn] - u[s]) / (2 * g.eps_y);
+                    const double dv_dx = wrapped<WRAP>(v[e] - v[w]) / (2 * g.eps_x);
+                    const double dv_dy = wrapped<WRAP>(v[nn] - v[s]) / (2 * g.eps_y);
+                    det = du_dx * dv_dy - du_dy * dv_dx;
                     sign = (det > 0) ? 1.0 : (det < 0) ? -1.0 : 0.0;
                 }
             }
@@ -234,7 +394,7 @@ grid_jacobian_kernel(kr_caustic_map m, double* __restrict__ maps)
 __global__ void __launch_bounds__(kBlock)
 suppress_mark_kernel(kr_caustic_map m, double* __restrict__ maps)
 {
-    __shared__ unsigned part[kBlock / 64];
+    __shared__ unsigned part[kBlock / 64][1];
     const int nx = m.nx, ny = m.ny;
     const long long npix = (long long) nx * ny;
     double* sign = maps + P_SIGN * npix;
@@ -260,16 +420,7 @@ suppress_mark_kernel(kr_caustic_map m, double* __restrict__ maps)
             ++suppressed;
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) suppressed += __shfl_down(suppressed, off, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = suppressed;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned v = 0;
-#pragma unroll
-        for (int w = 0; w < kBlock / 64; w++) v += part[w];
-        if (v) atomicAdd(&maps[kPlanes * npix + C_SUPPRESSED], (double) v);
-    }
+    flush_counts<kBlock / 64, 1>(&suppressed, part, maps + DiscSurface::kPlanes * npix + DiscSurface::C_SUPPRESSED);
 }
 
 __global__ void __launch_bounds__(kBlock)
@@ -281,16 +432,58 @@ suppress_clear_kernel(long long npix, double* __restrict__ sign)
     }
 }
 
-}  // namespace
+// the counts cleared, then the gather of surface s over the n records and, in grid mode, the neighbour Jacobian
+template <typename S>
+int gather(const S& s, Pixels g, bool bundles, typename S::Ray* rays, long long n, double* maps, hipStream_t st)
+{
+    const long long npix = (long long) g.nx * g.ny;
+    KR_HIP(hipMemsetAsync(maps + S::kPlanes * npix, 0, S::kCounts * sizeof(double), st));
+    if constexpr (S::kHasBundles) {
+        if (bundles) {
+            constexpr int kPixels = 64;             // 320 work-items: five waves, one pixel per lane of the first in the gather
+            hipLaunchKernelGGL((bundle_gather_kernel<S, kPixels>), dim3(grid_for(n, kBundle * kPixels, kCapStream)), dim3(kBundle * kPixels), 0, st, rays, n, s, g, maps);
+            KR_LAUNCH_CHECK();
+            return KR_OK;
+        }
+    }
+    hipLaunchKernelGGL((grid_gather_kernel<S>), dim3(grid_for(n, kBlock, kCapStream)), dim3(kBlock), 0, st, rays, n, s, npix, maps);
+    KR_LAUNCH_CHECK();
+    hipLaunchKernelGGL((neighbour_jacobian_kernel<S::kWrapsV>), dim3(grid_for(npix, kBlock, kCapStream)), dim3(kBlock), 0, st, g, (int) S::kU, (int) S::kV, maps);
+    KR_LAUNCH_CHECK();
+    return KR_OK;
+}
 
-int caustic_validate(const kr_caustic_map* m, const char* who)
+// what the two map descriptions have in common; `rest` answers for the fields of its own (nullptr, or what is wrong).  n: the records the caller has
+template <typename M, typename Rest>
+int map_validate(const M* m, int64_t n, const char* who, Rest rest)
 {
     auto bad = [&](const char* why) { set_error(std::string(who) + ": " + why); return KR_EINVAL; };
     if (!m) return bad("null map description");
     if (m->nx < 1 || m->ny < 1) return bad("nx and ny must be >= 1");
     if (!std::isfinite(m->eps_x) || !std::isfinite(m->eps_y) || !(m->eps_x > 0) || !(m->eps_y > 0)) return bad("eps_x and eps_y must be positive and finite");
-    if (!std::isfinite(m->r_isco) || !std::isfinite(m->r_disc)) return bad("non-finite disc radius");
+    if (const char* why = rest(*m)) return bad(why);
+    if (n < (m->bundles ? kBundle : 1) * (int64_t) m->nx * m->ny) return bad(m->bundles ? "n smaller than 5 nx ny" : "n smaller than nx ny");
     return KR_OK;
+}
+
+}  // namespace
+
+int caustic_validate(const kr_caustic_map* m, int64_t n, const char* who)
+{
+    return map_validate(m, n, who, [](const kr_caustic_map& c) -> const char* {
+        return !std::isfinite(c.r_isco) || !std::isfinite(c.r_disc) ? "non-finite disc radius" : nullptr;
+    });
+}
+
+int source_map_validate(const kr_source_map* m, int64_t n, const char* who)
+{
+    return map_validate(m, n, who, [](const kr_source_map& s) -> const char* {
+        if (s.kind != K_SPHERE && s.kind != K_PLANE) return "unknown kind (0: source sphere, 1: flat source plane)";
+        if (s.kind == K_SPHERE && s.bundles) return "the source sphere has no bundle mode";
+        if (s.kind == K_PLANE && !(std::isfinite(s.sin_incl) && std::isfinite(s.cos_incl) && std::isfinite(s.sin_phi0) && std::isfinite(s.cos_phi0)))
+            return "non-finite sine or cosine of incl / phi0";
+        return nullptr;
+    });
 }
 
 int bundles_init_emit_dev(const kr_imageplane* s, int nx, int ny, double eps_frac, double V, int reverse, int projradius, void* d, int64_t n, hipStream_t st)
@@ -302,35 +495,35 @@ int bundles_init_emit_dev(const kr_imageplane* s, int nx, int ny, double eps_fra
     return KR_OK;
 }
 
+// every one of the n records gets its redshift, whether or not it belongs to a pixel
 int post_caustic_dev(double spin, int reverse, const kr_caustic_map* m, void* d, int64_t n, void* d_maps, hipStream_t st)
 {
-    const long long npix = (long long) m->nx * m->ny;
-    double* maps = (double*) d_maps;
-    KR_HIP(hipMemsetAsync(maps + kPlanes * npix, 0, kCounts * sizeof(double), st));
-    if (m->bundles) {
-        constexpr int kPixels = 64;                 // 320 work-items: five waves, one pixel per lane of the first in the gather
-        hipLaunchKernelGGL((post_caustic_kernel<kBundle, kPixels>), dim3(grid_for(n, kBundle * kPixels, kCapStream)), dim3(kBundle * kPixels), 0, st, (kr_ray_f64*) d,
-                           (long long) n, spin, reverse, *m, maps);
-        KR_LAUNCH_CHECK();
-    } else {
-        hipLaunchKernelGGL((post_caustic_kernel<1, kBlock>), dim3(grid_for(n, kBlock, kCapStream)), dim3(kBlock), 0, st, (kr_ray_f64*) d, (long long) n, spin, reverse, *m, maps);
-        KR_LAUNCH_CHECK();
-        hipLaunchKernelGGL(grid_jacobian_kernel, dim3(grid_for(npix, kBlock, kCapStream)), dim3(kBlock), 0, st, *m, maps);
-        KR_LAUNCH_CHECK();
-    }
-    return KR_OK;
+    DiscSurface s;
+    s.spin = spin; s.r_isco = m->r_isco; s.r_disc = m->r_disc; s.reverse = reverse;
+    return gather(s, pixels_of(*m), m->bundles != 0, (kr_ray_f64*) d, (long long) n, (double*) d_maps, st);
 }
 
 int caustic_suppress_dev(const kr_caustic_map* m, void* d_maps, hipStream_t st)
 {
     const long long npix = (long long) m->nx * m->ny;
     double* maps = (double*) d_maps;
-    KR_HIP(hipMemsetAsync(maps + kPlanes * npix + C_SUPPRESSED, 0, sizeof(double), st));
+    KR_HIP(hipMemsetAsync(maps + DiscSurface::kPlanes * npix + DiscSurface::C_SUPPRESSED, 0, sizeof(double), st));
     hipLaunchKernelGGL(suppress_mark_kernel, dim3(grid_for(npix, kBlock, kCapStream)), dim3(kBlock), 0, st, *m, maps);
     KR_LAUNCH_CHECK();
     hipLaunchKernelGGL(suppress_clear_kernel, dim3(grid_for(npix, kBlock, kCapStream)), dim3(kBlock), 0, st, npix, maps + P_SIGN * npix);
     KR_LAUNCH_CHECK();
     return KR_OK;
+}
+
+// only the records of the pixels are read
+int post_caustic_source_dev(const kr_source_map* m, const void* d, void* d_maps, hipStream_t st)
+{
+    const long long npix = (long long) m->nx * m->ny;
+    const kr_ray_f64* rays = (const kr_ray_f64*) d;
+    if (m->kind == K_SPHERE) return gather(SphereSurface(), pixels_of(*m), false, rays, npix, (double*) d_maps, st);
+    PlaneSurface s;
+    s.m = *m;
+    return gather(s, pixels_of(*m), m->bundles != 0, rays, (m->bundles ? kBundle : 1) * npix, (double*) d_maps, st);
 }
 
 }  // namespace kr

@@ -1,4 +1,4 @@
-// kr_common.hpp -- host-side plumbing shared by the .hip translation units of libkrtrace.so.
+// kr_common.hpp -- host-side plumbing shared by the .hip translation units of libkrtrace.so, and the one wave reduction that the trace loop and the passes share.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -21,6 +21,15 @@ int require_device();   // KR_OK or KR_ENODEVICE (message set)
         hipError_t e__ = (call);                                          \
         if (e__ != hipSuccess) return kr::hip_fail(e__, #call, __FILE__, __LINE__); \
     } while (0)
+
+// device side: the sum of v over the 64 lanes of a wave, in lane 0 (the trace loop's counters, the caustic passes' counts)
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
 
 // The current device, saved on construction and set again on destruction: for code that visits other devices (the shutdown paths).
 struct CurrentDeviceGuard {

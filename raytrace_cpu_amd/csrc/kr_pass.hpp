@@ -1,4 +1,4 @@
-// kr_pass.hpp -- what the O(N) passes either side of the trace kernel share (kr_post.hip, kr_line.hip, kr_caustic.hip, kr_source_caustic.hip) and what kr_capi.hip calls
+// kr_pass.hpp -- what the O(N) passes either side of the trace kernel share (kr_post.hip, kr_line.hip, kr_caustic.hip) and what kr_capi.hip calls
 // them through: the launch helpers, the per-record pieces that several kernels repeat, and the one declaration of every launcher.
 // The device helpers are plain forced-inline functions and one loop macro: each kernel compiles to the code it had with the lines written out.
 #pragma once
@@ -122,12 +122,11 @@ int reduce_line_dev(const kr_line_bins* b, const void* d, int64_t n, void* d_lin
 int post_line_dev(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_line_bins* b, void* d, int64_t n,
                   void* d_line, hipStream_t st);
 int line_from_image_dev(const kr_line_bins* b, const kr_image_bins* ib, const void* d_planes, void* d_line, hipStream_t st);
-// kr_caustic.hip
-int caustic_validate(const kr_caustic_map* m, const char* who);
+// kr_caustic.hip.  The validators take the records the caller has (n; "n smaller than ..." is theirs to say)
+int caustic_validate(const kr_caustic_map* m, int64_t n, const char* who);
 int bundles_init_emit_dev(const kr_imageplane* s, int nx, int ny, double eps_frac, double V, int reverse, int projradius, void* d, int64_t n, hipStream_t st);
 int post_caustic_dev(double spin, int reverse, const kr_caustic_map* m, void* d, int64_t n, void* d_maps, hipStream_t st);
 int caustic_suppress_dev(const kr_caustic_map* m, void* d_maps, hipStream_t st);
-// kr_source_caustic.hip
 int source_map_validate(const kr_source_map* m, int64_t n, const char* who);
 int post_caustic_source_dev(const kr_source_map* m, const void* d, void* d_maps, hipStream_t st);
 // kr_paths.hip: the two passes of the recording trace; both wait for `st` (the count pass hands the total to the host, the record pass its verdict)

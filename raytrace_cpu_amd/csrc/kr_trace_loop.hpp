@@ -13,6 +13,7 @@
 
 #include <algorithm>
 
+#include "kr_common.hpp"
 #include "kr_device.hpp"
 #include "kr_ray_io.hpp"
 
@@ -62,12 +63,7 @@ KR_DEV unsigned long long wave_max(unsigned long long v)
     return v;
 }
 
-KR_DEV unsigned long long wave_sum(unsigned long long v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
+// (wave_sum: kr_common.hpp)
 
 // workgroups of a persistent launch over n rays: what the device holds at once (single-wave workgroups per CU times CUs), never more than 64-ray loads
 inline int persistent_grid(int cus, int blocks_per_cu, long long n)

@@ -82,57 +82,78 @@ def centre_planes(c, r_isco, r_disc):
             "Y_DISC": np.where(hit, y, 0.0), "ORDER": np.where(hit, order, -1).astype(float), "REDSHIFT": np.where(hit, c["redshift"], 0.0)}
 
 
+def wrap_dphi(d):
+    """caustic_sourceplane.cpp:68-73 on differences of two angles in [-pi, pi]: each loop runs at most once"""
+    d = np.where(d > math.pi, d - 2 * math.pi, d)
+    return np.where(d < -math.pi, d + 2 * math.pi, d)
+
+
+def satellite_jacobian(c, sat, coords, eps_x, eps_y):
+    """The Jacobian of a pixel from its four satellites (caustic_discplane.cpp:279-334, caustic_plane.cpp:249-299): c = the (nx, ny) centre rays,
+    sat = [east, west, north, south], coords(records) -> (hit, u, v).  Returns (det, sign, G): G = the largest |derivative| of each pixel (NaN where
+    no determinant was formed)."""
+    allhit = coords(c)[0]
+    match = np.ones(c.shape, bool)
+    for s in sat:
+        with np.errstate(invalid="ignore"):
+            match &= (s["rdot_flips"] == c["rdot_flips"]) & (np.abs(s["phi"] - c["phi"]) < math.pi / 2)
+    (he, ue, ve), (hw, uw, vw), (hn, un, vn), (hs, us, vs) = [coords(s) for s in sat]
+    allhit = allhit & he & hw & hn & hs
+    with np.errstate(invalid="ignore"):
+        a11, a12, a21, a22 = (ue - uw) / (2 * eps_x), (un - us) / (2 * eps_y), (ve - vw) / (2 * eps_x), (vn - vs) / (2 * eps_y)
+        d = a11 * a22 - a12 * a21
+    ok = allhit & match
+    det = np.where(ok, d, np.where(allhit, SENTINEL, np.nan))
+    G = np.where(ok, np.maximum.reduce([np.abs(a11), np.abs(a12), np.abs(a21), np.abs(a22)]), np.nan)
+    return det, np.where(ok, _sign(d), 0.0), G
+
+
+def neighbour_jacobian(hit, order, U, V, dx, dy, wrap=False):
+    """The Jacobian of a pixel from its four grid neighbours (caustic_discplane.cpp:403-439, caustic_sourceplane.cpp:264-305, caustic_plane.cpp:357-392)
+    over the (nx, ny) planes; wrap: V is an angle, its differences go through wrap_dphi.  Returns (det, sign, G, raw): G as satellite_jacobian's;
+    raw = with wrap, per pixel the |raw V difference| of the two neighbour pairs that lies closest to pi (NaN where no determinant was formed), else None."""
+    nx, ny = hit.shape
+    det = np.full((nx, ny), np.nan)
+    sign = np.zeros((nx, ny))
+    G = np.full((nx, ny), np.nan)
+    raw = np.full((nx, ny), np.nan) if wrap else None
+    if nx > 2 and ny > 2:
+        i = (slice(1, -1), slice(1, -1))
+        e, w, n, s = (slice(2, None), slice(1, -1)), (slice(0, -2), slice(1, -1)), (slice(1, -1), slice(2, None)), (slice(1, -1), slice(0, -2))
+        allhit = hit[i] & hit[e] & hit[w] & hit[n] & hit[s]
+        match = (order[e] == order[i]) & (order[w] == order[i]) & (order[n] == order[i]) & (order[s] == order[i])
+        with np.errstate(invalid="ignore"):
+            dvx, dvy = V[e] - V[w], V[n] - V[s]
+            if wrap:
+                near = np.minimum(np.abs(np.abs(dvx) - math.pi), np.abs(np.abs(dvy) - math.pi))
+                dvx, dvy = wrap_dphi(dvx), wrap_dphi(dvy)
+            a11, a12, a21, a22 = (U[e] - U[w]) / (2 * dx), (U[n] - U[s]) / (2 * dy), dvx / (2 * dx), dvy / (2 * dy)
+            d = a11 * a22 - a12 * a21
+        ok = allhit & match
+        det[i] = np.where(ok, d, np.where(allhit, SENTINEL, np.nan))
+        sign[i] = np.where(ok, _sign(d), 0.0)
+        G[i] = np.where(ok, np.maximum.reduce([np.abs(a11), np.abs(a12), np.abs(a21), np.abs(a22)]), np.nan)
+        if wrap:
+            raw[i] = np.where(ok, near, np.nan)
+    return det, sign, G, raw
+
+
 def bundle_maps(rays, nx, ny, r_isco, r_disc, eps_x, eps_y):
     """Bundle mode, before suppression: rays[(ix ny + iy) 5 + m], m = centre, east, west, north, south (:219-334).
     Returns (planes, counts, G): G = the largest |derivative| of each pixel (NaN where no determinant was formed)."""
     B = rays[:5 * nx * ny].reshape(nx, ny, 5)
-    c, sat = B[:, :, 0], [B[:, :, m] for m in (1, 2, 3, 4)]
+    c = B[:, :, 0]
     maps = centre_planes(c, r_isco, r_disc)
-    hit = maps["HIT"] != 0
-    allhit = hit.copy()
-    match = np.ones((nx, ny), bool)
-    for s in sat:
-        allhit &= valid_hit(s, r_isco, r_disc)
-        with np.errstate(invalid="ignore"):
-            match &= (s["rdot_flips"] == c["rdot_flips"]) & (np.abs(s["phi"] - c["phi"]) < math.pi / 2)
-    (xe, ye, _), (xw, yw, _), (xn, yn, _), (xs, ys, _) = [disc_xy(s) for s in sat]
-    with np.errstate(invalid="ignore"):
-        a11, a12, a21, a22 = (xe - xw) / (2 * eps_x), (xn - xs) / (2 * eps_y), (ye - yw) / (2 * eps_x), (yn - ys) / (2 * eps_y)
-        d = a11 * a22 - a12 * a21
-    det = np.full((nx, ny), np.nan)
-    sign = np.zeros((nx, ny))
-    det[allhit & ~match] = SENTINEL
-    ok = allhit & match
-    det[ok] = d[ok]
-    sign[ok] = _sign(d[ok])
-    maps["DET_J"], maps["SIGN_J"] = det, sign
-    G = np.where(ok, np.maximum.reduce([np.abs(a11), np.abs(a12), np.abs(a21), np.abs(a22)]), np.nan)
-    counts = dict(diagnostics(c, r_isco, r_disc), disc_count=int(hit.sum()))
-    return maps, counts, G
+    maps["DET_J"], maps["SIGN_J"], G = satellite_jacobian(c, [B[:, :, m] for m in (1, 2, 3, 4)], lambda r: (valid_hit(r, r_isco, r_disc),) + disc_xy(r)[:2], eps_x, eps_y)
+    return maps, dict(diagnostics(c, r_isco, r_disc), disc_count=int((maps["HIT"] != 0).sum())), G
 
 
 def grid_maps(rays, nx, ny, r_isco, r_disc, dx, dy):
     """Grid-neighbour mode, before suppression: rays[ix ny + iy] (:349-439).  Returns (planes, counts, G)."""
     c = rays[:nx * ny].reshape(nx, ny)
     maps = centre_planes(c, r_isco, r_disc)
-    hit, order, X, Y = maps["HIT"] != 0, maps["ORDER"], maps["X_DISC"], maps["Y_DISC"]
-    det = np.full((nx, ny), np.nan)
-    sign = np.zeros((nx, ny))
-    G = np.full((nx, ny), np.nan)
-    if nx > 2 and ny > 2:
-        i = (slice(1, -1), slice(1, -1))
-        e, w, n, s = (slice(2, None), slice(1, -1)), (slice(0, -2), slice(1, -1)), (slice(1, -1), slice(2, None)), (slice(1, -1), slice(0, -2))
-        allhit = hit[i] & hit[e] & hit[w] & hit[n] & hit[s]
-        match = (order[e] == order[i]) & (order[w] == order[i]) & (order[n] == order[i]) & (order[s] == order[i])
-        a11, a12, a21, a22 = (X[e] - X[w]) / (2 * dx), (X[n] - X[s]) / (2 * dy), (Y[e] - Y[w]) / (2 * dx), (Y[n] - Y[s]) / (2 * dy)
-        d = a11 * a22 - a12 * a21
-        ok = allhit & match
-        det[i] = np.where(ok, d, np.where(allhit, SENTINEL, np.nan))
-        sign[i] = np.where(ok, _sign(d), 0.0)
-        G[i] = np.where(ok, np.maximum.reduce([np.abs(a11), np.abs(a12), np.abs(a21), np.abs(a22)]), np.nan)
-    maps["DET_J"], maps["SIGN_J"] = det, sign
-    counts = dict(diagnostics(c, r_isco, r_disc), disc_count=int(hit.sum()))
-    return maps, counts, G
+    maps["DET_J"], maps["SIGN_J"], G, _ = neighbour_jacobian(maps["HIT"] != 0, maps["ORDER"], maps["X_DISC"], maps["Y_DISC"], dx, dy)
+    return maps, dict(diagnostics(c, r_isco, r_disc), disc_count=int((maps["HIT"] != 0).sum())), G
 
 
 def suppress(maps):

@@ -8,14 +8,15 @@ import math
 
 import numpy as np
 
-from caustic_rules import SENTINEL, bits_equal, det_bound, read_par, plane_geometry as _disc_geometry, fits_planes as _disc_fits_planes, golden  # noqa: F401
+from caustic_rules import (SENTINEL, bits_equal, det_bound, golden, neighbour_jacobian, read_par, satellite_jacobian, wrap_dphi,  # noqa: F401
+                           plane_geometry as _disc_geometry)
+from raytrace_cpu_amd.capi import STATUS_DEST, STATUS_HORIZON, STATUS_RLIM, STATUS_STEPLIM
 
 PLANES = {"sphere": ("DET_J", "SIGN_J", "ORDER", "ESCAPED", "THETA_S", "PHI_S", "RDOT_FLIPS", "EQUAT_CROSS"),
           "plane": ("DET_J", "SIGN_J", "ORDER", "HIT_PLANE", "X_S", "Y_S", "RDOT_FLIPS", "EQUAT_CROSS")}
 HIT = {"sphere": "ESCAPED", "plane": "HIT_PLANE"}
 COORDS = {"sphere": ("THETA_S", "PHI_S"), "plane": ("X_S", "Y_S")}
 COUNT_CARDS = {"sphere": ("N_ESC", "N_CAP", "N_SLIM"), "plane": ("N_HIT", "N_CAP", "N_SLIM")}
-STATUS_DEST, STATUS_HORIZON, STATUS_RLIM, STATUS_STEPLIM = 1, 2, 4, 8
 
 _sin, _cos, _atan2 = np.vectorize(math.sin, otypes=[float]), np.vectorize(math.cos, otypes=[float]), np.vectorize(math.atan2, otypes=[float])
 
@@ -46,10 +47,6 @@ def fits_planes(path, kind):
     hdus = fits_lite.read(path)
     assert [h["name"] for h in hdus] == ["PRIMARY"] + list(PLANES[kind]), [h["name"] for h in hdus]
     return {h["name"]: np.asarray(h["data"], dtype=np.float64).T.copy() for h in hdus[1:]}, hdus[0]["header"]
-
-
-def _sign(det):
-    return np.where(det > 0, 1.0, np.where(det < 0, -1.0, 0.0))
 
 
 def sphere_hit(r):
@@ -100,67 +97,20 @@ def centre_planes(c, kind, incl=0.0, phi0=0.0):
     return maps, counts
 
 
-def wrap_dphi(d):
-    """caustic_sourceplane.cpp:68-73 on differences of two angles in [-pi, pi]: each loop runs at most once"""
-    d = np.where(d > math.pi, d - 2 * math.pi, d)
-    return np.where(d < -math.pi, d + 2 * math.pi, d)
-
-
 def grid_maps(rays, nx, ny, kind, dx, dy, incl=0.0, phi0=0.0):
     """Grid-neighbour mode: rays[ix ny + iy] (caustic_sourceplane.cpp:180-305, caustic_plane.cpp:315-392).  Returns (planes, counts, G, raw): G = the
     largest |derivative| of each pixel (NaN where no determinant was formed); raw = for the sphere, per pixel the |raw phi difference| of the two
     neighbour pairs that lies closest to pi (NaN where no determinant was formed), else None."""
-    c = rays[:nx * ny].reshape(nx, ny)
-    maps, counts = centre_planes(c, kind, incl, phi0)
+    maps, counts = centre_planes(rays[:nx * ny].reshape(nx, ny), kind, incl, phi0)
     ku, kv = COORDS[kind]
-    hit, order, U, V = maps[HIT[kind]] != 0, maps["ORDER"], maps[ku], maps[kv]
-    det = np.full((nx, ny), np.nan)
-    sign = np.zeros((nx, ny))
-    G = np.full((nx, ny), np.nan)
-    raw = np.full((nx, ny), np.nan) if kind == "sphere" else None
-    if nx > 2 and ny > 2:
-        i = (slice(1, -1), slice(1, -1))
-        e, w, n, s = (slice(2, None), slice(1, -1)), (slice(0, -2), slice(1, -1)), (slice(1, -1), slice(2, None)), (slice(1, -1), slice(0, -2))
-        allhit = hit[i] & hit[e] & hit[w] & hit[n] & hit[s]
-        match = (order[e] == order[i]) & (order[w] == order[i]) & (order[n] == order[i]) & (order[s] == order[i])
-        with np.errstate(invalid="ignore"):
-            dvx, dvy = V[e] - V[w], V[n] - V[s]
-            if kind == "sphere":
-                near = np.minimum(np.abs(np.abs(dvx) - math.pi), np.abs(np.abs(dvy) - math.pi))
-                dvx, dvy = wrap_dphi(dvx), wrap_dphi(dvy)
-            a11, a12, a21, a22 = (U[e] - U[w]) / (2 * dx), (U[n] - U[s]) / (2 * dy), dvx / (2 * dx), dvy / (2 * dy)
-            d = a11 * a22 - a12 * a21
-        ok = allhit & match
-        det[i] = np.where(ok, d, np.where(allhit, SENTINEL, np.nan))
-        sign[i] = np.where(ok, _sign(d), 0.0)
-        G[i] = np.where(ok, np.maximum.reduce([np.abs(a11), np.abs(a12), np.abs(a21), np.abs(a22)]), np.nan)
-        if kind == "sphere":
-            raw[i] = np.where(ok, near, np.nan)
-    maps["DET_J"], maps["SIGN_J"] = det, sign
+    maps["DET_J"], maps["SIGN_J"], G, raw = neighbour_jacobian(maps[HIT[kind]] != 0, maps["ORDER"], maps[ku], maps[kv], dx, dy, wrap=kind == "sphere")
     return maps, counts, G, raw
 
 
 def bundle_maps(rays, nx, ny, eps_x, eps_y, incl, phi0):
     """Plane kind, bundle mode: rays[(ix ny + iy) 5 + m], m = centre, east, west, north, south (caustic_plane.cpp:207-299).  Returns (planes, counts, G)."""
     B = rays[:5 * nx * ny].reshape(nx, ny, 5)
-    c, sat = B[:, :, 0], [B[:, :, m] for m in (1, 2, 3, 4)]
-    maps, counts = centre_planes(c, "plane", incl, phi0)
-    allhit = maps["HIT_PLANE"] != 0
-    match = np.ones((nx, ny), bool)
-    for s in sat:
-        allhit = allhit & plane_hit(s)
-        with np.errstate(invalid="ignore"):
-            match &= (s["rdot_flips"] == c["rdot_flips"]) & (np.abs(s["phi"] - c["phi"]) < math.pi / 2)
-    (xe, ye, _), (xw, yw, _), (xn, yn, _), (xs, ys, _) = [plane_coords(s, incl, phi0) for s in sat]
-    with np.errstate(invalid="ignore"):
-        a11, a12, a21, a22 = (xe - xw) / (2 * eps_x), (xn - xs) / (2 * eps_y), (ye - yw) / (2 * eps_x), (yn - ys) / (2 * eps_y)
-        d = a11 * a22 - a12 * a21
-    det = np.full((nx, ny), np.nan)
-    sign = np.zeros((nx, ny))
-    det[allhit & ~match] = SENTINEL
-    ok = allhit & match
-    det[ok] = d[ok]
-    sign[ok] = _sign(d[ok])
-    maps["DET_J"], maps["SIGN_J"] = det, sign
-    G = np.where(ok, np.maximum.reduce([np.abs(a11), np.abs(a12), np.abs(a21), np.abs(a22)]), np.nan)
+    maps, counts = centre_planes(B[:, :, 0], "plane", incl, phi0)
+    maps["DET_J"], maps["SIGN_J"], G = satellite_jacobian(B[:, :, 0], [B[:, :, m] for m in (1, 2, 3, 4)], lambda r: (plane_hit(r),) + plane_coords(r, incl, phi0)[:2],
+                                                          eps_x, eps_y)
     return maps, counts, G

@@ -14,31 +14,10 @@ import pytest
 
 import caustic_rules as cr
 import oracle_lib as ol
+from caustic_testlib import build_bundle_dump, mirror_bundles
 from raytrace_cpu_amd import capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "raytrace_cpu_amd", "host")
-CSRC = os.path.join(ROOT, "raytrace_cpu_amd", "csrc")
-
-
-def build_bundle_dump(tmp_path):
-    """tests/cpp/bundle_ctor_dump.cpp -> tmp_path, with the flags tests/cpp/Makefile uses for host_ctor_dump and absolute rpaths"""
-    subprocess.run(["make", "-s", "-C", HOST], check=True)
-    exe = os.path.join(str(tmp_path), "bundle_ctor_dump")
-    subprocess.run(["g++", "-O2", "-std=c++14", "-ffp-contract=off", "-Wall", "-Wno-unused-parameter", "-I" + HOST, "-o", exe,
-                    os.path.join(ROOT, "tests", "cpp", "bundle_ctor_dump.cpp"), "-L" + HOST, "-lkr_host", "-L" + CSRC, "-lkrtrace",
-                    "-Wl,-rpath," + HOST, "-Wl,-rpath," + CSRC], check=True)
-    return exe
-
-
-def mirror_bundles(exe, tmp_path, g, eps_frac):
-    """The host mirror's ImagePlaneBundles<double> rays of the plane `g` (caustic_rules.plane_geometry)."""
-    out = os.path.join(str(tmp_path), "bundles.bin")
-    args = [g["dist"], g["incl"], g["x0"], g["xmax"], g["dx"], g["y0"], g["ymax"], g["dy"], g["spin"], g["phi0"], eps_frac]
-    subprocess.run([exe, out] + [repr(float(a)) for a in args], check=True, stdout=subprocess.DEVNULL, timeout=300)
-    raw = open(out, "rb").read()
-    n = int(np.frombuffer(raw[:4], dtype=np.int32)[0])
-    return np.frombuffer(raw[4:], dtype=capi.RAY_F64, count=n).copy()
 
 
 def oracle_pipeline(g, rays):

@@ -2,7 +2,7 @@
 apps/kr_caustic_discplane) against
   * the host mirror's ImagePlaneBundles constructor and the oracle's redshift_start (the bundle constructor),
   * tests/caustic_rules.py -- pinned to the compiled reference by tests/test_caustic_rules.py -- applied to the very records the device kernels
-    read (the map kernels in isolation),
+    read (the map kernels in isolation), and to hand-made records at the smallest shapes at which the gather can go wrong,
   * the compiled reference's FITS files (the application end to end, with the rules of test_gpu_dropin_apps.py::test_caustic_apps_match_cpu_output),
   * the reference's own program on the host mirror (the path users have today), where it was built."""
 import ctypes as C
@@ -15,58 +15,22 @@ import numpy as np
 import pytest
 
 import caustic_rules as cr
+from caustic_testlib import FLOATS, INTS, OFF, SHAPES, Dev, bundle_identity_mask, device_bundles, same_bits, spec_of, synthetic
 import fits_lite
 import oracle_lib as ol
 import parity
 from raytrace_cpu_amd import api, capi
-from test_caustic_rules import build_bundle_dump, mirror_bundles
 from test_gpu_dropin_apps import COUNT_KEYS, NATIVE
 
 pytestmark = pytest.mark.gpu
 
-FLOATS = ("t", "r", "theta", "phi", "pt", "pr", "ptheta", "pphi", "k", "h", "Q", "alpha", "beta")
-INTS = ("rdot_sign", "thetadot_sign", "status")
-
 # the 41 x 41 plane of tests/golden/apps/caustic_discplane.par, and one away from the fixtures that contains the point (0, 0): 65 x 49 grid points
 # (64 x 48 steps of 0.5), inclination 45 degrees, a = 0.9
 GOLDEN = cr.plane_geometry(cr.read_par(cr.golden("caustic_discplane.par")))
-OFF = dict(dist=500.0, incl=45.0, spin=0.9, r_disc=20.0, x0=-16.0, xmax=16.0, y0=-12.0, ymax=12.0, phi0=0.0, Nx=64, Ny=48, dx=0.5, dy=0.5, nx=65, ny=49,
-           eps_frac=0.01, precision=100.0, rk45_tol=1e-8)
 PLANES = {"golden": GOLDEN, "off": OFF}
 # a photon trapped inside the ISCO is not stopped by a DiscWithISCODestination and runs to the step limit (1e7: 16-38 s of
 # one launch).  A ray that ends on the limit has steps < 0 and is no hit in either implementation.
 STEPLIM = {"golden": 0, "off": 1000000}
-
-
-def spec_of(g):
-    return ol.imageplane_spec(g["dist"], g["incl"], g["x0"], g["xmax"], g["dx"], g["y0"], g["ymax"], g["dy"], g["spin"], phi0=g["phi0"], precision=g["precision"])
-
-
-class Dev:
-    """device buffers of one test, freed at the end"""
-
-    def __init__(self, L):
-        self.L, self.ptrs = L, []
-
-    def alloc(self, nbytes):
-        p = C.c_void_p()
-        capi.check(self.L, self.L.kr_malloc(C.byref(p), nbytes), "kr_malloc")
-        self.ptrs.append(p)
-        return p
-
-    def rays(self, d, n):
-        out = np.zeros(n, dtype=capi.RAY_F64)
-        capi.check(self.L, self.L.kr_memcpy_d2h(ol.ptr(out), d, out.nbytes), "d2h")
-        return out
-
-    def doubles(self, d, n):
-        out = np.zeros(n)
-        capi.check(self.L, self.L.kr_memcpy_d2h(ol.ptr(out), d, out.nbytes), "d2h")
-        return out
-
-    def close(self):
-        for p in self.ptrs:
-            self.L.kr_free(p)
 
 
 @pytest.fixture
@@ -76,15 +40,6 @@ def dev(krlib):
     d.close()
 
 
-def device_bundles(dev, g):
-    L, spec = dev.L, spec_of(g)
-    n, nx, ny = api.bundles_count(spec)
-    assert (nx, ny) == (g["nx"], g["ny"]) and n == 5 * nx * ny
-    d = dev.alloc(n * 144)
-    capi.check(L, L.kr_bundles_init_emit_dev_f64(C.byref(spec), g["eps_frac"], 0.0, 1, 0, d, n, None), "kr_bundles_init_emit")
-    return d, n
-
-
 def device_grid(dev, g):
     L, spec = dev.L, spec_of(g)
     n, nx, ny = api.imageplane_count(spec)
@@ -92,26 +47,6 @@ def device_grid(dev, g):
     d = dev.alloc(n * 144)
     capi.check(L, L.kr_imageplane_init_emit_dev_f64(C.byref(spec), 0, 1, 0.0, 1, 0, d, n, None), "kr_imageplane_init_emit")
     return d, n
-
-
-def same_bits(a, b):
-    if a.dtype.kind == "f":
-        return (a.view(np.int64) == b.view(np.int64)) | (np.isnan(a) & np.isnan(b))
-    return a == b
-
-
-def bundle_identity_mask(dev, g, tmp_path):
-    """[nx, ny]: True where all five device-built rays of the bundle carry the host mirror's bits in every field (emit against the oracle's
-    redshift_start on the mirror's rays).  Also returns (device rays, mirror rays with emit)."""
-    d, n = device_bundles(dev, g)
-    got = dev.rays(d, n)
-    want = mirror_bundles(build_bundle_dump(tmp_path), tmp_path, g, g["eps_frac"])
-    assert len(want) == n
-    ol.oracle().kro_redshift_start_f64(-g["spin"], 0.0, 1, 0, ol.ptr(want), n)
-    same = np.ones(n, bool)
-    for f in FLOATS + INTS + ("emit", "steps"):
-        same &= same_bits(got[f], want[f])
-    return same.reshape(g["nx"], g["ny"], 5).all(axis=2), got, want
 
 
 # ---- 5. the constructor ------------------------------------------------------------------------------------------------------------------
@@ -249,6 +184,149 @@ def test_map_kernels_match_the_rules_on_the_same_records(dev, plane, integrator,
     if not ambiguous.any():
         assert cr.suppress(want) == n_supp
         assert np.array_equal(after["SIGN_J"], want["SIGN_J"]) and np.array_equal(after["DET_J"] == cr.SENTINEL, want["DET_J"] == cr.SENTINEL)
+
+
+# ---- 6b. the map kernels on hand-made records, at the smallest shapes at which the gather can go wrong ---------------------------------------------
+HAND = dict(spin=0.9, r_disc=20.0, dx=0.5, dy=0.25, eps_frac=0.01)
+
+
+def disc_records(bundles, nx, ny, r_isco, seed, trailing):
+    """caustic_testlib.synthetic's pattern (steps <= 0, the status bits, another winding next door, satellites with another rdot_flips / far away in
+    phi) as records that end on the disc: r varies smoothly inside [r_isco, r_disc), so determinants exist (of either sign on the long
+    planes); theta near the equator, constants of motion and emit for which redshift(dest, reverse) is positive.  Sprinkled on top:
+    centre rays with r < r_isco, with r >= r_disc, with emit < 0 (g < 0) and emit = NaN (g = NaN); in bundle mode satellites beyond r_disc (no
+    determinant) and pixels whose east and west satellites are swapped (the opposite sign among its neighbours: the suppression pass has work).
+    `trailing` records that would be hits follow: they are no pixels, but the pass owes them their redshift."""
+    rng = np.random.default_rng(seed + 77)
+    rpb = 5 if bundles else 1
+    rays = synthetic("plane", bundles, nx, ny, seed).reshape(nx, ny, rpb)
+    ix, iy = np.meshgrid(np.arange(nx), np.arange(ny), indexing="ij")
+    da, db = (0.0, 1.0, -1.0, 0.0, 0.0), (0.0, 0.0, 0.0, 1.0, -1.0)
+    span = HAND["r_disc"] - r_isco - 2.0
+    for m in range(rpb):
+        a, b = ix + 0.01 * da[m], iy + 0.01 * db[m]
+        q = rays[:, :, m]
+        q["r"] = r_isco + 1.0 + span * (0.4 + 0.6 * a / nx - 0.4 * b / ny)
+        q["theta"] = math.pi / 2 - 1e-3 * (1 + (ix + iy) % 3)
+        q["k"], q["h"], q["Q"] = 1.0, 0.5 + 0.02 * a - 0.01 * b, 4.0 + 0.05 * b
+        q["rdot_sign"], q["thetadot_sign"] = np.where((ix + iy) % 2 == 0, 1, -1), np.where(ix % 2 == 0, 1, -1)
+        q["emit"] = 0.9 + 0.001 * a
+        q["redshift"] = -5.0                                               # overwritten by the pass
+    c = rays[:, :, 0]
+    pick = rng.random((nx, ny))
+    c["r"][pick < 0.04] = 0.5 * r_isco + 0.6
+    c["r"][(pick >= 0.04) & (pick < 0.08)] = HAND["r_disc"] + 0.03 * ix[(pick >= 0.04) & (pick < 0.08)]
+    c["r"][(pick >= 0.08) & (pick < 0.09)] = HAND["r_disc"]                 # the outer edge itself is outside
+    c["emit"][(pick >= 0.09) & (pick < 0.12)] *= -1
+    c["emit"][(pick >= 0.12) & (pick < 0.14)] = math.nan
+    if bundles:
+        spick, sat = rng.random((nx, ny)), rng.integers(1, 5, size=(nx, ny))
+        for m in range(1, 5):
+            rays[:, :, m]["r"][(sat == m) & (spick < 0.05)] = HAND["r_disc"] + 1.0
+        swap = (spick >= 0.05) & (spick < 0.15)
+        east = rays[:, :, 1][swap].copy()
+        rays[:, :, 1][swap] = rays[:, :, 2][swap]
+        rays[:, :, 2][swap] = east
+    out = rays.reshape(-1)
+    if trailing:
+        tail = np.repeat(rays[nx // 2, ny // 2, :1], trailing)
+        tail["r"], tail["steps"], tail["status"], tail["emit"] = 0.5 * (r_isco + HAND["r_disc"]), 50, capi.STATUS_DEST, 0.9
+        out = np.concatenate([out, tail])
+    return out
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+@pytest.mark.parametrize("mode", ["bundles", "grid"])
+def test_disc_maps_on_hand_made_records(dev, mode, shape):
+    """kr_post_caustic_disc_dev_f64 + kr_caustic_suppress_dev_f64 on hand-made records at the last-chunk shapes of the 64-pixel bundle pass and the
+    256-thread grid pass and on planes that are all border, with 37 trailing records, judged by caustic_rules on the records read back (they carry the
+    device's redshift) with the bars of test_map_kernels_match_the_rules_on_the_same_records: c = 1e-12 r_disc on PHI, X_DISC, Y_DISC, det_bound on
+    DET_J, SIGN_J wherever |det| is not below that bound (no such pixel may exist here); everything else equal.  Every word of the 0xFF-prefilled
+    buffer is written; the records, trailing ones included, equal kr_redshift_dest_dev_f64 on a copy in every field; suppression is bit-exact against
+    the rules on the device's own maps; the same words come out with the trailing records cut off."""
+    L, (nx, ny), bundles = dev.L, shape, mode == "bundles"
+    r_isco = L.kr_kerr_isco(HAND["spin"], 1)
+    g = dict(HAND, nx=nx, ny=ny)
+    cm = caustic_struct(g, r_isco, bundles)
+    nw, npix, rpb = api.caustic_words(cm), nx * ny, 5 if bundles else 1
+    rays = disc_records(bundles, nx, ny, r_isco, seed=nx * 1000 + ny, trailing=37)
+    n = len(rays)
+    assert n == rpb * npix + 37
+
+    def run(records):
+        d = dev.alloc(records.nbytes)
+        capi.check(L, L.kr_memcpy_h2d(d, ol.ptr(records), records.nbytes), "h2d")
+        d_maps = dev.alloc(nw * 8)
+        capi.check(L, L.kr_memset(d_maps, 0xff, nw * 8), "kr_memset")
+        capi.check(L, L.kr_post_caustic_disc_dev_f64(-HAND["spin"], 1, C.byref(cm), d, len(records), d_maps, None), "kr_post_caustic_disc")
+        before = dev.doubles(d_maps, nw)
+        capi.check(L, L.kr_caustic_suppress_dev_f64(C.byref(cm), d_maps, None), "kr_caustic_suppress")
+        return before, dev.doubles(d_maps, nw), dev.rays(d, len(records))
+
+    words_before, words_after, fused = run(rays)
+    d_copy = dev.alloc(rays.nbytes)
+    capi.check(L, L.kr_memcpy_h2d(d_copy, ol.ptr(rays), rays.nbytes), "h2d")
+    capi.check(L, L.kr_redshift_dest_dev_f64(-HAND["spin"], 1, d_copy, n, None), "kr_redshift_dest")
+    separate = dev.rays(d_copy, n)
+    for f in fused.dtype.names:
+        assert same_bits(fused[f], separate[f]).all(), f
+    with np.errstate(invalid="ignore"):
+        positive = fused["redshift"] > 0
+    assert positive.mean() > 0.8 and positive[-37:].all()
+    for w in (words_before, words_after):
+        assert not (w.view(np.uint64) == 0xFFFFFFFFFFFFFFFF).any() and not np.isnan(w[9 * npix:]).any(), "a word was not written"
+    before, counts_before = planes_of(cm, words_before)
+    after, counts = planes_of(cm, words_after)
+
+    want, want_counts, G = (cr.bundle_maps if bundles else cr.grid_maps)(fused, nx, ny, r_isco, HAND["r_disc"], cm.eps_x, cm.eps_y)
+    assert counts_before["suppressed"] == 0
+    for k, v in want_counts.items():
+        assert counts_before[k] == v == counts[k], (k, counts_before[k], v)
+    for k in ("HIT", "ORDER"):
+        assert np.array_equal(before[k], want[k]), k
+    for k in ("RADIUS", "REDSHIFT"):
+        assert cr.bits_equal(before[k], want[k]).all(), k
+    c = 1e-12 * HAND["r_disc"]
+    worst = {}
+    for k in ("PHI", "X_DISC", "Y_DISC"):
+        diff = np.abs(before[k] - want[k])
+        worst[k] = float(diff.max())
+        assert (diff <= c).all(), (k, worst[k], c)
+    gd, wd = before["DET_J"], want["DET_J"]
+    assert np.array_equal(np.isnan(gd), np.isnan(wd)) and np.array_equal(gd == cr.SENTINEL, wd == cr.SENTINEL)
+    defined = ~np.isnan(wd) & (wd != cr.SENTINEL)
+    bound = cr.det_bound(c, min(cm.eps_x, cm.eps_y), G)
+    ratio = (np.abs(gd - wd)[defined] / bound[defined]) if defined.any() else np.zeros(1)
+    hits, n_sentinel = want_counts["disc_count"], int((wd == cr.SENTINEL).sum())
+    print(mode, shape, "hits", hits, "defined", int(defined.sum()), "sentinel", n_sentinel, "g <= 0 or NaN", int((~positive).sum()), "worst coordinate differences",
+          worst, "worst |d det| / bound", float(ratio.max()), "suppressed", counts["suppressed"])
+    assert (ratio <= 1).all(), float(ratio.max())
+    ambiguous = defined & (np.abs(wd) < bound)
+    assert not ambiguous.any()
+    assert np.array_equal(before["SIGN_J"], want["SIGN_J"])
+    parity.record_margin("test_disc_maps_on_hand_made_records", f"{mode}-{nx}x{ny}",
+                         {"n_traced": int(defined.sum()), "n_bad": 0, "frac_bad": 0.0, "worst_ok": float(ratio.max())}, worst_coordinate_difference=max(worst.values()))
+    if not bundles and (nx < 3 or ny < 3):
+        assert np.isnan(gd).all() and (before["SIGN_J"] == 0).all()
+    if npix >= 63:
+        assert 0 < hits < npix and (~positive).any()
+        if bundles or (nx >= 3 and ny >= 3):
+            assert defined.any()
+    if npix >= 129 and (bundles or min(nx, ny) >= 5):
+        assert n_sentinel > 0
+
+    # the suppression pass on the device's own maps: no tolerance
+    expect = {"DET_J": before["DET_J"].copy(), "SIGN_J": before["SIGN_J"].copy()}
+    n_supp = cr.suppress(expect)
+    assert counts["suppressed"] == n_supp
+    assert cr.bits_equal(after["DET_J"], expect["DET_J"]).all() and np.array_equal(after["SIGN_J"], expect["SIGN_J"])
+    for k in ("ORDER", "HIT", "RADIUS", "PHI", "X_DISC", "Y_DISC", "REDSHIFT"):
+        assert cr.bits_equal(after[k], before[k]).all(), k
+    if bundles and npix >= 129:
+        assert n_supp > 0
+    # trailing records are no pixels
+    cut_before, cut_after, _ = run(rays[:rpb * npix])
+    assert cut_before.tobytes() == words_before.tobytes() and cut_after.tobytes() == words_after.tobytes()
 
 
 # ---- 7. the application end to end against the reference's files ----------------------------------------------------------------------------------

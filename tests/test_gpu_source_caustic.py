@@ -1,4 +1,4 @@
-"""GPU: the device-resident caustic maps of the source sphere and of a flat source plane (raytrace_cpu_amd/csrc/kr_source_caustic.hip,
+"""GPU: the device-resident caustic maps of the source sphere and of a flat source plane (raytrace_cpu_amd/csrc/kr_caustic.hip,
 include/kr_trace.h kr_source_map, api.caustic_source_map, apps/kr_caustic_sourceplane and apps/kr_caustic_plane) against
   * tests/source_caustic_rules.py -- pinned to the compiled reference by tests/test_source_caustic_rules.py -- applied to hand-made records (the
     gather and the Jacobian at the smallest shapes at which they can go wrong) and to the very records the device traced,
@@ -18,15 +18,13 @@ import fits_lite
 import oracle_lib as ol
 import parity
 import source_caustic_rules as sr
+from caustic_testlib import COORD_ULPS, FIXTURES, OFF, SHAPES, Dev, bundle_identity_mask, same_bits, spec_of, synthetic
 from raytrace_cpu_amd import api, capi
-from test_gpu_caustic import OFF, Dev, bundle_identity_mask, same_bits
 from test_gpu_dropin_apps import COUNT_KEYS, NATIVE
-from test_source_caustic_rules import COORD_ULPS, FIXTURES, spec_of
 
 pytestmark = pytest.mark.gpu
 
 ROOT = ol.ROOT
-RLIM_OR_DEST = capi.STATUS_RLIM | capi.STATUS_DEST          # a synthetic record that is a hit for either kind
 INCL, PHI0 = math.radians(30.0), 0.25
 
 
@@ -99,69 +97,12 @@ def judge(kind, bundles, sm, words, rays, c, incl=0.0, phi0=0.0):
 
 
 # ---- 1. hand-made records -----------------------------------------------------------------------------------------------------------------------
-def synthetic(kind, bundles, nx, ny, seed, trailing=0, sprinkle=True):
-    """Records of a smooth map image plane -> source (so that determinants exist) with every branch of the rules sprinkled in: steps <= 0, HORIZON,
-    STEPLIM, a winding number of their own (another ORDER next door -> SENTINEL), satellites with another rdot_flips / more than pi / 2 away in phi /
-    that missed.  The sphere's phi runs through pi inside the grid, so neighbour pairs straddle the branch cut of PHI_S.  `trailing` records with
-    steps = -1 follow, full of values that would be hits: they are no pixels."""
-    rng = np.random.default_rng(seed)
-    rpb = 5 if bundles else 1
-    ix, iy = np.meshgrid(np.arange(nx), np.arange(ny), indexing="ij")
-    rays = np.zeros((nx, ny, rpb), dtype=capi.RAY_F64)
-    da = (0.0, 1.0, -1.0, 0.0, 0.0)
-    db = (0.0, 0.0, 0.0, 1.0, -1.0)
-    for m in range(rpb):
-        a, b = ix + 0.01 * da[m], iy + 0.01 * db[m]                       # image-plane position in pixels
-        q = rays[:, :, m]
-        q["r"] = 1000.0 if kind == "sphere" else 800.0 + 3.0 * a + 2.0 * b
-        q["theta"] = 1.0 + 0.011 * a - 0.004 * b + 0.0003 * a * b
-        q["phi"] = (3.06 if kind == "sphere" else 2.9) + 0.021 * a + 0.013 * b - 0.0002 * a * a
-        q["steps"] = 100 + ix
-        q["status"] = RLIM_OR_DEST
-        q["rdot_flips"] = 1
-        q["equatorial_crossings"] = (ix + 2 * iy) % 4
-        q["t"], q["k"], q["emit"], q["redshift"] = 5.0, 1.0, 0.5, 0.25        # never read
-    c = rays[:, :, 0]
-    pick = rng.random((nx, ny)) if sprinkle else np.ones((nx, ny))
-    c["steps"][pick < 0.04] = 0
-    c["steps"][(pick >= 0.04) & (pick < 0.07)] = -7
-    c["status"][(pick >= 0.07) & (pick < 0.11)] = capi.STATUS_HORIZON
-    c["status"][(pick >= 0.11) & (pick < 0.14)] = capi.STATUS_STEPLIM | RLIM_OR_DEST
-    c["status"][(pick >= 0.14) & (pick < 0.16)] = capi.STATUS_STEPLIM | capi.STATUS_HORIZON
-    wound = (pick >= 0.16) & (pick < 0.22)
-    for m in range(rpb):                                                  # a whole bundle on another winding: another ORDER, still a hit
-        rays[:, :, m]["phi"][wound] += 2 * math.pi * 3
-    c["rdot_flips"][(pick >= 0.22) & (pick < 0.25)] = 5
-    c["phi"][(pick >= 0.25) & (pick < 0.27)] *= -1
-    if bundles and sprinkle:
-        spick = rng.random((nx, ny))
-        sat = rng.integers(1, 5, size=(nx, ny))
-        for m in range(1, 5):
-            q, mine = rays[:, :, m], sat == m
-            q["rdot_flips"][mine & (spick < 0.08)] += 2                                   # another rdot_flips -> SENTINEL
-            q["phi"][mine & (spick >= 0.08) & (spick < 0.16)] += 1.6                      # more than pi / 2 away -> SENTINEL
-            q["phi"][mine & (spick >= 0.16) & (spick < 0.20)] -= 1.5                      # within pi / 2: a (large) determinant
-            q["status"][mine & (spick >= 0.20) & (spick < 0.26)] = capi.STATUS_RLIM       # no DEST: the satellite missed -> NaN
-            q["steps"][mine & (spick >= 0.26) & (spick < 0.30)] = 0
-    out = rays.reshape(-1)
-    if trailing:
-        tail = np.zeros(trailing, dtype=capi.RAY_F64)
-        tail["r"], tail["theta"], tail["phi"], tail["status"], tail["steps"] = 900.0, 1.2, 0.4, RLIM_OR_DEST, -1
-        out = np.concatenate([out, tail])
-    return out
-
-
 def struct_for(kind, bundles, nx, ny):
     eps = (0.01 * 0.5, 0.01 * 0.25) if bundles else (0.5, 0.25)            # dx = 0.5, dy = 0.25
     return api.source_map_struct(kind, nx, ny, eps[0], eps[1], bundles, INCL, PHI0)
 
 
 MODES = [("sphere", False), ("plane", False), ("plane", True)]
-# pixel counts 1, 63, 64, 65, 129: the last-chunk cases of the 64-pixel bundle pass and, with 255, 256, 257 (the 15 x 17, 16 x 16 planes and one beyond),
-# of the 256-thread grid pass; nx or ny < 3: every pixel is border
-SHAPES = [(1, 1), (7, 9), (8, 8), (5, 13), (3, 43), (15, 17), (16, 16), (257, 3), (2, 9), (9, 2), (1, 70), (70, 1)]
-
-
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
 @pytest.mark.parametrize("kind,bundles", MODES, ids=["sphere", "plane-grid", "plane-bundles"])
 def test_gather_and_jacobian_on_hand_made_records(dev, kind, bundles, shape):
@@ -297,7 +238,7 @@ OFF_STEPLIM = {capi.RK4: 1000000, capi.RK45: 0}
 
 
 def geometry(plane, case, integrator):
-    """the fixture's own plane, or the 65 x 49 plane of test_gpu_caustic.OFF with the programs' defaults (r_lim = 1.5 dist, z_s = dist, r_max = 4 z_s)"""
+    """the fixture's own plane, or the 65 x 49 plane caustic_testlib.OFF with the programs' defaults (r_lim = 1.5 dist, z_s = dist, r_max = 4 z_s)"""
     if plane == "golden":
         return dict(GOLDEN[case])
     g = dict(OFF, steplim=OFF_STEPLIM[integrator])

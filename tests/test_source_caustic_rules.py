@@ -1,4 +1,4 @@
-"""CPU: the caustic maps of the source sphere and of a flat source plane (include/kr_trace.h, kr_source_map; raytrace_cpu_amd/csrc/kr_source_caustic.hip)
+"""CPU: the caustic maps of the source sphere and of a flat source plane (include/kr_trace.h, kr_source_map; raytrace_cpu_amd/csrc/kr_caustic.hip)
 without a GPU.
   * tests/source_caustic_rules.py, the numpy restatement of the reference's caustic_sourceplane.cpp and caustic_plane.cpp that
     tests/test_gpu_source_caustic.py judges the device kernels with, is pinned to the compiled reference's own output first: the oracle's ImagePlane
@@ -21,19 +21,10 @@ import pytest
 
 import oracle_lib as ol
 import source_caustic_rules as sr
+from caustic_testlib import COORD_ULPS, FIXTURES, build_bundle_dump, mirror_bundles, spec_of
 from raytrace_cpu_amd import api, capi
-from test_caustic_rules import build_bundle_dump, mirror_bundles
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COORD_ULPS = 16 * 2.0 ** -52
-
-FIXTURES = {"sphere": ("caustic_sourceplane", "sphere"), "plane-bundles": ("caustic_plane", "plane"), "plane-grid": ("caustic_plane_grid", "plane")}
-
-
-def spec_of(g):
-    return ol.imageplane_spec(g["dist"], g["incl"], g["x0"], g["xmax"], g["dx"], g["y0"], g["ymax"], g["dy"], g["spin"], phi0=g["phi0"], precision=g["precision"])
-
-
 def trace_params(g, kind):
     integrator = capi.RK4 if g["integrator"] == "rk4" else capi.RK45
     p, _ = api.caustic_trace_params_source(spec_of(g), kind, r_lim=g.get("r_lim"), z_s=g.get("z_s"), r_max=g.get("r_max"), integrator=integrator,
