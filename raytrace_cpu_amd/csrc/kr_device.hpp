@@ -329,8 +329,9 @@ KR_DEV T dest_step_limit(const TraceConsts<T>& c, T r, T theta, T ptheta)
 }
 
 // polar reflection, raytracer.cpp:282-283 / :914-915 / :1498-1499
+// sign_d (optional): the same sign as a double (FastRaySigns::thetadot), converted again where the integer flips
 template <typename T, bool LONE = false>
-KR_DEV void reflect_poles(T& theta, T& phi, int32_t& thetadot_sign)
+KR_DEV void reflect_poles(T& theta, T& phi, int32_t& thetadot_sign, double* sign_d = nullptr)
 {
     // a pole crossing is rare: one wave-uniform test, and the per-lane selects only in a wave that has one
     if constexpr (LONE) {
@@ -338,8 +339,8 @@ KR_DEV void reflect_poles(T& theta, T& phi, int32_t& thetadot_sign)
     } else {
         if (__builtin_amdgcn_ballot_w64(theta < T(0) || theta > T(kPi)) == 0) return;
     }
-    if (theta < T(0)) { theta = -theta; thetadot_sign = -thetadot_sign; phi += T(kPi); }
-    if (theta > T(kPi)) { theta = T(2) * T(kPi) - theta; thetadot_sign = -thetadot_sign; phi += T(kPi); }
+    if (theta < T(0)) { theta = -theta; thetadot_sign = -thetadot_sign; if (sign_d) *sign_d = (double) thetadot_sign; phi += T(kPi); }
+    if (theta > T(kPi)) { theta = T(2) * T(kPi) - theta; thetadot_sign = -thetadot_sign; if (sign_d) *sign_d = (double) thetadot_sign; phi += T(kPi); }
 }
 
 template <typename T>
@@ -352,12 +353,32 @@ KR_DEV bool crossed_equator(T before, T after)
 // a FastRayConsts, every other instance an empty struct that nothing reads -- those kernels compile to what they were without it.
 struct NoRayConsts {};
 template <bool CARRIED> using RayConstsOf = std::conditional_t<CARRIED, FastRayConsts, NoRayConsts>;
+// Likewise the signs as doubles and the launch's values in vector registers (kr_fast.hpp: FastRaySigns, FastLaunchRegs): the fast Euler / RK4 instances
+// with a theta-limit stop.  Not the RayDestination ones: their RK4 kernels sit on the 168-register ceiling of three waves per SIMD with scratch in use.
+template <bool CARRIED> using RaySignsOf = std::conditional_t<CARRIED, FastRaySigns, NoRayConsts>;
+template <bool CARRIED> using LaunchRegsOf = std::conditional_t<CARRIED, FastLaunchRegs, NoRayConsts>;
+
+// What a kernel instance carries through its step loop (trace_body's STEP_REGS, a sum of these): a group that is not carried reaches the step as the
+// launch constant / literal it always was, and the step compiles to what it was without.
+enum StepRegs { kStepSigns = 1, kStepTimeCap = 2, kStepNearLead = 4, kStepRegsAll = 7 };
+
+template <int WHAT> KR_DEV FastLaunchRegs fast_launch_regs(const TraceConsts<double>& c)
+{
+    FastLaunchRegs l;
+    l.tstep_rlim = c.tstep_rlim_eff; l.near_s9 = 1.0 / 362880.0; l.near_c8 = 1.0 / 40320.0; l.tstep_lo = c.tstep_lo; l.tstep_on_hi = c.tstep_on_hi; l.tstep_off_hi = c.tstep_off_hi;
+    // (opaque to the compiler from here on, as consts_into_vector_registers' are: values in vector registers, neither uniform nor constant)
+    if constexpr ((WHAT & kStepTimeCap) != 0) asm("" : "+v"(l.tstep_rlim), "+v"(l.tstep_lo), "+v"(l.tstep_on_hi), "+v"(l.tstep_off_hi));
+    if constexpr ((WHAT & kStepNearLead) != 0) asm("" : "+v"(l.near_s9), "+v"(l.near_c8));
+    return l;
+}
 
 // One iteration of the Euler (raytracer.cpp:172-313) or RK4 (:799-943, :1080-1229) loop body.
 // Returns true when the ray has finished (break, or the loop condition no longer holds).
 // rayc: the ray's constant terms, filled where the lane took the ray -- the fast path reads them, the others are called without.
+// sg, lr (fast path, theta-limit stop): the ray's signs as doubles, kept in step with the integers here, and the launch's values in
+// vector registers.  The step computes the same operations on the same operands with or without them.
 template <typename T, bool RK4, bool USE_DEST, bool FAST, bool LONE = false>
-KR_DEV bool step_fixed(Lane<T>& s, const TraceConsts<T>& c, const FastRayConsts* rayc = nullptr)
+KR_DEV bool step_fixed(Lane<T>& s, const TraceConsts<T>& c, const FastRayConsts* rayc = nullptr, FastRaySigns* sg = nullptr, const FastLaunchRegs* lr = nullptr)
 {
     const T a = c.a;
     ++s.steps;
@@ -368,7 +389,7 @@ KR_DEV bool step_fixed(Lane<T>& s, const TraceConsts<T>& c, const FastRayConsts*
     if constexpr (FAST) {
         // (carrying sin / cos of the base point from step to step by angle addition was measured and rejected: it removes 7 of 406 vector instructions
         // per RK4 step but costs registers the stage code needs -- 63.2 ms against 62.7 at 1e7 rays, Euler 31.6 against 30.9; profiles/r03_ab_experiments.txt)
-        if (k1_with_flips_fast(s, a, *rayc, aux)) return !(s.steps < c.steplim);
+        if (k1_with_flips_fast(s, a, *rayc, aux, sg)) return !(s.steps < c.steplim);
         pt1 = s.pt; pr1 = s.pr; ptheta1 = s.ptheta; pphi1 = s.pphi;
         // The same heuristic (:855-871) with ONE quarter-rate instruction instead of four.  1 / |rdot| and 1 / |thetadot| come out of the
         // square roots that produced them (fast_sqrt); the time and azimuth caps, min(dt / |tdot|, dphi / |phidot|), share one reciprocal:
@@ -386,7 +407,9 @@ KR_DEV bool step_fixed(Lane<T>& s, const TraceConsts<T>& c, const FastRayConsts*
             const T apt = kr_abs(pt1), aphi = abs_floor(pphi1);
             // the time cap applies inside maxtstep_rlim only: outside, "dt" is a huge number with max_tstep's LOW word (TraceConsts::tstep_off_hi),
             // so that the choice is one select on the high word instead of two on a 64-bit pair
-            const T dt_eff = __builtin_bit_cast(double, ((unsigned long long) (unsigned) ((s.r < c.tstep_rlim_eff) ? c.tstep_on_hi : c.tstep_off_hi) << 32) | c.tstep_lo);
+            const bool capped = s.r < (lr ? lr->tstep_rlim : c.tstep_rlim_eff);
+            const uint32_t dt_hi = capped ? (lr ? lr->tstep_on_hi : c.tstep_on_hi) : (lr ? lr->tstep_off_hi : c.tstep_off_hi);
+            const T dt_eff = __builtin_bit_cast(double, ((unsigned long long) dt_hi << 32) | (lr ? lr->tstep_lo : c.tstep_lo));
             const T num = __builtin_fmin(dt_eff * aphi, c.phistep_eff * apt);
             step = __builtin_fmin(step, num * fast_rcp_heur(apt * aphi));
         }
@@ -415,6 +438,8 @@ KR_DEV bool step_fixed(Lane<T>& s, const TraceConsts<T>& c, const FastRayConsts*
             }
         }
         if (__builtin_amdgcn_ballot_w64(pt1 <= 0) != 0) {        // (inside the ergosphere only: one compare and a scalar branch instead of compare, or, select)
+            asm volatile("");        // (cannot be speculated: without it the branch comes back as "or" and select on every step.  No memory clobber --
+                                     // this block is on every step's way, and the merged kernels read their constants through a pointer)
             if (pt1 <= 0) s.status |= KR_STATUS_ERGO;
         }
         // (1 - 2r/rho^2) tdot + (2 a r sin^2/rho^2) phidot IS the conserved energy k (= -p_t): analytically it cannot turn negative, and
@@ -485,11 +510,12 @@ KR_DEV bool step_fixed(Lane<T>& s, const TraceConsts<T>& c, const FastRayConsts*
                     double sn, cs;
                     if constexpr (kNear) {
                         within = within && (__builtin_fabs(dtheta) <= near_limit);
-                        sincos_near(aux.sn, aux.cs, dtheta, sn, cs);
+                        sincos_near(aux.sn, aux.cs, dtheta, sn, cs, lr);
                     } else {
                         kr_sincos_fast_f64(s.theta + dtheta, sn, cs);
                     }
-                    momentum_fast_sc(pt, pr, ptheta, pphi, s.k, s.h, s.Q, *rayc, s.rdot_sign, s.thetadot_sign, r_stage, sn, cs, a);
+                    if (sg) momentum_fast_sc(pt, pr, ptheta, pphi, s.k, s.h, s.Q, *rayc, sg->rdot, sg->thetadot, r_stage, sn, cs, a);
+                    else momentum_fast_sc(pt, pr, ptheta, pphi, s.k, s.h, s.Q, *rayc, s.rdot_sign, s.thetadot_sign, r_stage, sn, cs, a);
                 } else if constexpr (kNear) {
                     const T theta_stage = s.theta + dtheta;
                     within = within && (kr_abs(theta_stage) < T(KR_SMALL_ANGLE_LIMIT));
@@ -545,7 +571,7 @@ KR_DEV bool step_fixed(Lane<T>& s, const TraceConsts<T>& c, const FastRayConsts*
         }
     }
     if (crossed_equator(theta_prev, s.theta)) ++s.eq_cross;
-    reflect_poles<T, LONE>(s.theta, s.phi, s.thetadot_sign);
+    reflect_poles<T, LONE>(s.theta, s.phi, s.thetadot_sign, sg ? &sg->thetadot : nullptr);
 
     if (s.r <= c.horizon) { s.status |= KR_STATUS_HORIZON; return true; }
     if (USE_DEST) {

@@ -101,6 +101,18 @@ KR_DEV FastRayConsts fast_ray_consts(double k, double h, double Q, double a)
     return f;
 }
 
+// The two velocity signs of a ray as doubles, beside the integers of the lane state (which stay what the record stores): rdot = (double) rdot_sign,
+// thetadot = (double) thetadot_sign.  The theta-limit Euler / RK4 instances keep the pair next to FastRayConsts -- set where a lane takes its ray (trace_body),
+// converted again wherever the integers flip (the two turning-point sites of k1_with_flips_fast, reflect_poles) -- so that k1 does not convert both
+// integers in every step.  Always the conversion of the integer the record holds: the products 1/rho^2 x sign see the operand they always saw.
+struct FastRaySigns { double rdot, thetadot; };
+
+// What those instances keep of the LAUNCH in vector registers through the step loop (trace_body fills it once, fast_launch_regs): values the step otherwise
+// reads back from spilled scalar registers (v_readlane), or builds in vector registers again in every step (v_mov).
+//   tstep_rlim, tstep_lo, tstep_on_hi, tstep_off_hi   TraceConsts::tstep_rlim_eff / tstep_lo / tstep_on_hi / tstep_off_hi (the time cap's select)
+//   near_s9, near_c8                    1/9! and 1/8!: the leading Horner coefficients of sincos_near, whose first step has two constant operands
+struct FastLaunchRegs { double tstep_rlim, near_s9, near_c8; uint32_t tstep_lo, tstep_on_hi, tstep_off_hi; };
+
 KR_DEV FastPotentials potentials_fast(double& pt, double& pphi, double k, double h, double Q, const FastRayConsts& f, double r, double s, double c, double a)
 {
     const double s2 = s * s;
@@ -128,9 +140,10 @@ KR_DEV FastPotentials potentials_fast(double& pt, double& pphi, double k, double
     return o;
 }
 
-// momentum_from_consts (kerr.h:300-335)
-KR_DEV void momentum_fast_sc(double& pt, double& pr, double& ptheta, double& pphi, double k, double h, double Q, const FastRayConsts& f, int rdot_sign,
-                             int thetadot_sign, double r, double s, double c, double a)
+// momentum_from_consts (kerr.h:300-335).  SIGN: int (converted here, per evaluation) or double (FastRaySigns: the same +-1.0, carried).
+template <typename SIGN>
+KR_DEV void momentum_fast_sc(double& pt, double& pr, double& ptheta, double& pphi, double k, double h, double Q, const FastRayConsts& f, SIGN rdot_sign,
+                             SIGN thetadot_sign, double r, double s, double c, double a)
 {
     const FastPotentials o = potentials_fast(pt, pphi, k, h, Q, f, r, s, c, a);
     ptheta = fast_sqrt(o.N) * (o.inv_rho * thetadot_sign);
@@ -156,19 +169,26 @@ constexpr double kNearLimit = 0.07;
 // largest |d| for which sincos_near() uses the angle addition from theta0 (computed once per step, shared by its stages)
 KR_DEV double sincos_near_limit(double theta0)
 {
-    return __builtin_fmin(kNearLimit, 0.5 * __builtin_fmin(__builtin_fabs(theta0), __builtin_fabs(kPi - theta0)));
+    // min(|theta0|, |pi - theta0|) as ONE v_min_f64 with both |.| source modifiers (as abs_floor): left to the compiler, fmin(fabs, fabs) costs a
+    // canonicalising v_max |x|, |x| first.  A NaN angle makes both operands NaN and the minimum NaN, as before; the outer fmin then answers
+    // kNearLimit, and the stage's |d| <= limit test fails on its own NaN d: the full routine, as before.
+    double m;
+    asm("v_min_f64 %0, |%1|, |%2|" : "=v"(m) : "v"(theta0), "v"(kPi - theta0));
+    return __builtin_fmin(kNearLimit, 0.5 * m);
 }
 
-KR_DEV void sincos_near(double s0, double c0, double d, double& s, double& c)   // valid for |d| <= sincos_near_limit(theta0)
+// lead (optional): the two leading coefficients in vector registers that outlive the step (FastLaunchRegs) -- the first Horner step of either kernel has
+// two constant operands, of which an instruction takes one from a scalar register: the other is then a v_mov_b64 per step, unless it is already there.
+KR_DEV void sincos_near(double s0, double c0, double d, double& s, double& c, const FastLaunchRegs* lead = nullptr)   // valid for |d| <= sincos_near_limit(theta0)
 {
     // |d| <= 0.07 (the step heuristic keeps a whole RK4 step within theta / 50 <= 0.063): sin d through d^9 (next term d^11 / 11! <= 5e-21),
     // cos d - 1 through d^8 (next d^10 / 10! <= 8e-19 of a sum of magnitude ~1): one Horner step less on each side than the 1/8 version
     const double d2 = d * d;
-    double ps = kr_fma3s(d2, 1.0 / 362880.0, -1.0 / 5040.0);
+    double ps = kr_fma3s(d2, lead ? lead->near_s9 : 1.0 / 362880.0, -1.0 / 5040.0);
     ps = kr_fma3s(ps, d2, 1.0 / 120.0);
     ps = kr_fma3s(ps, d2, -1.0 / 6.0);
     const double sd = __builtin_fma(d * d2, ps, d);                 // sin d
-    double pc = kr_fma3s(d2, 1.0 / 40320.0, -1.0 / 720.0);
+    double pc = kr_fma3s(d2, lead ? lead->near_c8 : 1.0 / 40320.0, -1.0 / 720.0);
     pc = kr_fma3s(pc, d2, 1.0 / 24.0);
     pc = __builtin_fma(pc, d2, -0.5);
     const double cm = d2 * pc;                                       // cos d - 1
@@ -176,8 +196,8 @@ KR_DEV void sincos_near(double s0, double c0, double d, double& s, double& c)   
     c = __builtin_fma(-s0, sd, __builtin_fma(c0, cm, c0));
 }
 
-// k1 with the turning-point logic (see k1_with_flips) on the fast path
-KR_DEV bool k1_with_flips_fast(Lane<double>& s, double a, const FastRayConsts& f, FastAux& aux)
+// k1 with the turning-point logic (see k1_with_flips) on the fast path.  sg (optional): the ray's signs as doubles, flipped here with the integers.
+KR_DEV bool k1_with_flips_fast(Lane<double>& s, double a, const FastRayConsts& f, FastAux& aux, FastRaySigns* sg = nullptr)
 {
     double sn, c;
     kr_sincos_fast_f64(s.theta, sn, c);
@@ -185,21 +205,23 @@ KR_DEV bool k1_with_flips_fast(Lane<double>& s, double a, const FastRayConsts& f
     // thetadot^2 = N / rho^4 and rdot^2 = R / rho^4 have the signs of N and R
     if (o.N < 0 && s.theta_was_positive) {
         s.thetadot_sign = -s.thetadot_sign;
+        if (sg) sg->thetadot = (double) s.thetadot_sign;
         s.theta_was_positive = false;
         return true;
     }
     if (o.N >= 0) s.theta_was_positive = true;
     double inv_root;
-    s.ptheta = fast_sqrt(o.N, &inv_root) * (o.inv_rho * s.thetadot_sign);
+    s.ptheta = fast_sqrt(o.N, &inv_root) * (sg ? o.inv_rho * sg->thetadot : o.inv_rho * s.thetadot_sign);
     aux.inv_abs_ptheta = inv_root * o.rhosq;                   // 1 / |thetadot| = rho^2 / sqrt |N|
     if (o.R <= 0 && s.r_was_positive) {
         s.rdot_sign = -s.rdot_sign;
+        if (sg) sg->rdot = (double) s.rdot_sign;
         s.r_was_positive = false;
         s.rdot_flips++;
     } else if (o.R > 0) {
         s.r_was_positive = true;
     }
-    s.pr = fast_sqrt(o.R, &inv_root) * (o.inv_rho * s.rdot_sign);
+    s.pr = fast_sqrt(o.R, &inv_root) * (sg ? o.inv_rho * sg->rdot : o.inv_rho * s.rdot_sign);
     aux.inv_abs_pr = inv_root * o.rhosq;
     aux.sin2theta = o.s2; aux.inv_rhosq = o.inv_rho; aux.sn = sn; aux.cs = c;
     return false;

@@ -244,11 +244,16 @@ KR_SC_FN void kr_sincos_fast_core_f64(double x, double& s, double& c)
     pc = kr_fma3(z, pc, 4.16666666666666019037e-02);
     pc = __builtin_fma(z, pc, -0.5);
     const double cr = __builtin_fma(z, pc, 1.0);
+    // quadrant: sin -> {s, c, -s, -c}[n & 3], cos -> {c, -s, -c, s}[n & 3].  The sine's sign is bit 1 of n, the cosine's bit 1 of n + 1 (= bit 1 xor
+    // bit 0 of n): either is shifted to bit 31 whole, its neighbour with it, and ONE three-input operation -- high word ^ (shifted & 0x80000000),
+    // v_bitop3_b32 on gfx950 -- both masks the neighbour off and flips the sign; (n + 1) << 30 is one shift-add.  Four instructions for the two signs
+    // where "& 2" / "<< 30" / "^" per sign and the "+ 1" took seven; the same sign bits on the same values.
     const bool odd = (n & 1) != 0;
     const double ss = odd ? cr : sr;
     const double cc = odd ? sr : cr;
-    const unsigned long long sgn_s = ((unsigned long long) (unsigned) (n & 2)) << 62;
-    const unsigned long long sgn_c = ((unsigned long long) (unsigned) ((n + 1) & 2)) << 62;
-    s = __builtin_bit_cast(double, __builtin_bit_cast(unsigned long long, ss) ^ sgn_s);
-    c = __builtin_bit_cast(double, __builtin_bit_cast(unsigned long long, cc) ^ sgn_c);
+    const unsigned long long bs = __builtin_bit_cast(unsigned long long, ss), bc = __builtin_bit_cast(unsigned long long, cc);
+    const unsigned hi_s = (unsigned) (bs >> 32) ^ (((unsigned) n << 30) & 0x80000000u);
+    const unsigned hi_c = (unsigned) (bc >> 32) ^ ((((unsigned) n + 1u) << 30) & 0x80000000u);
+    s = __builtin_bit_cast(double, ((unsigned long long) hi_s << 32) | (unsigned) bs);
+    c = __builtin_bit_cast(double, ((unsigned long long) hi_c << 32) | (unsigned) bc);
 }

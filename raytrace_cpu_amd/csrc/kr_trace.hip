@@ -150,7 +150,9 @@ trace_multi_kernel(const TraceDesc<T>* __restrict__ descs, int n_desc, const int
                                                                    (unsigned long long) (gridDim.x / (unsigned) n_desc) * 64);
         }
     } else {
-        trace_body<T, METHOD, USE_DEST, FAST, HOG, REFILL_MIN>(d->rays, d->n, d->c, d->counters, d->list, d->n_ptr, d->n_mode, d->mask, d->mask_want, has_prio);
+        // (the merged kernels read their launch constants through `d`: with the time cap's words held in vector registers as well, the fast theta-limit
+        // instances' allocation re-reads constants from memory inside the step loop -- they carry the signs and the Horner coefficients only)
+        trace_body<T, METHOD, USE_DEST, FAST, HOG, REFILL_MIN, false, NoRecorder, kStepSigns | kStepNearLead>(d->rays, d->n, d->c, d->counters, d->list, d->n_ptr, d->n_mode, d->mask, d->mask_want, has_prio);
     }
 }
 

@@ -88,7 +88,8 @@ struct NoRecorder { static constexpr bool kActive = false, kStoresRays = true; }
 // the CUs it occupies -- used for the few ill-conditioned / long rays that define the critical path.  RADIAL (trace_side_kernel's
 // radial waves): the wave's rays are integrated with step_radial, a lane whose ray turns out not to be radial with step_fixed.
 // REC: the recorder (above); strict fp64 Euler / RK4 instances without radial waves only.
-template <typename T, int METHOD, bool USE_DEST, bool FAST, bool HOG, int REFILL_MIN, bool RADIAL = false, typename REC = NoRecorder>
+// STEP_REGS: what the fast theta-limit Euler / RK4 instances carry through the step loop besides a ray's constant terms (kr_device.hpp: StepRegs).
+template <typename T, int METHOD, bool USE_DEST, bool FAST, bool HOG, int REFILL_MIN, bool RADIAL = false, typename REC = NoRecorder, int STEP_REGS = kStepRegsAll>
 KR_DEV void trace_body(typename RayOf<T>::type* __restrict__ rays, long long n, const TraceConsts<T>& c, unsigned long long* __restrict__ counters,
                        const int* __restrict__ list, const unsigned long long* __restrict__ n_ptr, int n_mode, const unsigned char* __restrict__ mask, int mask_want,
                        int& has_prio, long long first_slot = -1, unsigned long long head_offset = 0, [[maybe_unused]] REC rec = REC())
@@ -111,6 +112,14 @@ KR_DEV void trace_body(typename RayOf<T>::type* __restrict__ rays, long long n, 
     constexpr bool kRayConsts = FAST && sizeof(T) == 8 && METHOD != KR_RK45;
     static_assert(!(RADIAL && FAST), "the radial waves call step_fixed without a ray's constant terms: strict arithmetic only");
     [[maybe_unused]] RayConstsOf<kRayConsts> ray_consts;
+    // The theta-limit ones among them also keep the ray's two signs as doubles (per ray, beside ray_consts) and a few of the launch's values in vector
+    // registers (once, here): what k1 otherwise converts, reads back from spilled scalars or builds again in every step (kr_fast.hpp: FastRaySigns,
+    // FastLaunchRegs).  Every other instance: empty structs.
+    constexpr int kStepRegs = (kRayConsts && !USE_DEST) ? (STEP_REGS & (METHOD == KR_RK4 ? kStepRegsAll : ~kStepNearLead)) : 0;      // (Euler has no stages)
+    constexpr bool kSigns = (kStepRegs & kStepSigns) != 0, kLaunchRegs = (kStepRegs & (kStepTimeCap | kStepNearLead)) != 0;
+    [[maybe_unused]] RaySignsOf<kSigns> ray_signs;
+    [[maybe_unused]] LaunchRegsOf<kLaunchRegs> launch_regs;
+    if constexpr (kLaunchRegs) launch_regs = fast_launch_regs<kStepRegs>(c);
     long long idx = -1;
     bool have = false;          // this lane holds a ray
     bool pend = false;          // this lane's ray has ended and is still in its registers: written out at the wave's next visit to the queue (or on exit)
@@ -205,6 +214,7 @@ KR_DEV void trace_body(typename RayOf<T>::type* __restrict__ rays, long long n, 
                         energy_guard_set(s);
                         // (the one place a lane takes a ray: its lanes only -- the others keep the terms of the rays they hold)
                         if constexpr (kRayConsts) ray_consts = fast_ray_consts(s.k, s.h, s.Q, c.a);
+                        if constexpr (kSigns) { ray_signs.rdot = (double) s.rdot_sign; ray_signs.thetadot = (double) s.thetadot_sign; }      // (whatever the record holds: a ray mid-flight too)
                         if (METHOD == KR_RK45) rk45_seed(s, c);
                         if constexpr (RADIAL) radial_claim(s, c, radial);
                         if constexpr (REC::kActive) rec.claim(slot);
@@ -244,7 +254,10 @@ KR_DEV void trace_body(typename RayOf<T>::type* __restrict__ rays, long long n, 
         } else if (have) {
             if constexpr (REC::kActive) rec.before_step(s);
             bool fin;
-            if constexpr (kRayConsts) fin = step_fixed<T, METHOD == KR_RK4, USE_DEST, FAST, HOG>(s, c, &ray_consts);
+            if constexpr (kSigns && kLaunchRegs) fin = step_fixed<T, METHOD == KR_RK4, USE_DEST, FAST, HOG>(s, c, &ray_consts, &ray_signs, &launch_regs);
+            else if constexpr (kSigns) fin = step_fixed<T, METHOD == KR_RK4, USE_DEST, FAST, HOG>(s, c, &ray_consts, &ray_signs);
+            else if constexpr (kLaunchRegs) fin = step_fixed<T, METHOD == KR_RK4, USE_DEST, FAST, HOG>(s, c, &ray_consts, nullptr, &launch_regs);
+            else if constexpr (kRayConsts) fin = step_fixed<T, METHOD == KR_RK4, USE_DEST, FAST, HOG>(s, c, &ray_consts);
             else if (METHOD == KR_EULER) fin = step_fixed<T, false, USE_DEST, FAST, HOG>(s, c);
             else if (METHOD == KR_RK4) fin = step_fixed<T, true, USE_DEST, FAST, HOG>(s, c);
             else fin = step_rk45<T, USE_DEST, FAST, HOG>(s, c, my_attempts, my_rejects, my_stationary, my_creep, replay_batch);
