@@ -225,6 +225,29 @@ typedef struct kr_return_bins {
     int32_t pad;
 } kr_return_bins;
 
+/* Landing map of the returning radiation: for one source radius, WHERE on the disc the rays of the ring come back, with which energy shift and after
+ * how long -- a weighted radial histogram of the `return` class of kr_return_bins, made in the pass that classifies the rays.  Per ray record with
+ * steps > 0:
+ *   g, w     g = rays[].redshift, the value after redshift(-1) (disc_source_photonfrac_r.cpp:94: emitted over received energy for a Keplerian receiver
+ *            at the landing point); w the weight of kr_return_bins (plane_iso, limb; rays[].alpha holds cos(alpha)).  ray_count, return, escape and
+ *            lost are accumulated exactly as kr_reduce_return_f64 accumulates them.
+ *   return   theta >= pi/2, r_isco <= r < r_disc, and |r - source_r| > 0.1 source_r or |phi - source_phi| > 0.1: on_disc += 1.  Such a ray is binned
+ *            iff g > 0 (a NaN fails) and -1 < q < nr with q = log(r / r_min) / log(dr) (logbin) or (r - r_min) / dr -- the quotient and index rule of
+ *            kr_emis_bins, the test made on q itself, so r_min <= 0, dr == 0 and the like are not errors: a NaN quotient is not binned.
+ *   binned   at ir = (int) q:  count[ir] += 1, weight[ir] += w, flux[ir] += w / g, emis[ir] += w / g^gamma, time[ir] += w t;  binned += 1.
+ * Rays in the self-zone of the source are in none of the sums and not in the map, as in the reference; escaped and lost rays are not in the map.
+ * Output per source: double[5 nr + 6] = [count | weight | flux | emis | time | ray_count, return, escape, lost, on_disc, binned]; counts are doubles.
+ * The fractions follow a loop whose program is stale in the reference (kr_return_bins above); the planes follow the emissivity histogram's rule. */
+typedef struct kr_return_map {
+    kr_return_bins cls;      /* classification and ray weight: exactly kr_reduce_return_f64's */
+    double r_min, dr;        /* landing-radius bins; quotient and index rule of kr_emis_bins */
+    double gamma;            /* emis += w * g^-gamma */
+    int32_t nr, logbin;
+} kr_return_map;
+#ifdef __cplusplus
+static_assert(sizeof(kr_return_map) == 88, "kr_return_map is 88 bytes (raytrace_cpu_amd/capi.py ReturnMap)");
+#endif
+
 /* Emission-line profile / reverberation transfer function from image-plane rays (the reference builds it outside its C++, in
  * python/line_from_image.ipynb, from the ENSHIFT and RADIUS planes of the image FITS file).  Per ray record, after redshift(-1, reverse=1):
  *   filter   steps > 0, z = r cos(theta) < 1e-2, r_isco <= r < r_disc, g > 0 with g = rays[].redshift (the disc-image filter of
@@ -512,6 +535,23 @@ int kr_post_return_dev_f64(double lo, double hi, const kr_return_bins* b, void* 
  * device, ADDED into); the same rays[] and, up to the order of the additions, the same sums as `count` single calls, in ceil(count / 32) launches. */
 int kr_post_return_batch_dev_f64(int32_t count, double lo, double hi, const kr_return_bins* b, void* const* d_rays, const int64_t* n, void* const* d_out4,
                                  void* stream);
+
+/* ---- landing map of the returning radiation (kr_return_map above) ---------------------------------------------------------------------------
+ * KR_EINVAL (message in kr_last_error) before anything touches a device: null pointers, n < 0, nr <= 0, count < 0.  Without a device: KR_ENODEVICE.
+ * The _dev forms ADD into d_out (5 nr + 6 doubles on the device; zero it first) and neither wait for the device nor allocate;
+ * kr_reduce_return_map_f64: host records, out = 5 nr + 6 host doubles (overwritten). */
+int kr_reduce_return_map_f64(const kr_return_map* m, const kr_ray_f64* rays, int64_t n, double* out);
+int kr_reduce_return_map_dev_f64(const kr_return_map* m, const void* d_rays, int64_t n, void* d_out, void* stream);
+/* range_phi(lo, hi) + redshift(V, reverse, projradius, motion) + the classification on the wrapped phi + the map in ONE pass over the records (the
+ * returning-radiation driver's passes after a trace, disc_source_photonfrac_r.cpp:93-126, with V = -1); rays[] ends up bit for bit as after
+ * kr_range_phi_dev_f64 + kr_redshift_dev_f64 */
+int kr_post_return_map_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_return_map* m, void* d_rays, int64_t n,
+                               void* d_out, void* stream);
+/* the same for `count` launches' rays at once: m, d_rays, n, d_out are HOST arrays of `count` entries (d_out[i]: 5 m[i].nr + 6 doubles on the device,
+ * ADDED into; the nr may differ); the same rays[] and counts and, up to the order of the additions, the same sums as `count` single calls, in
+ * ceil(count / 24) launches.  count == 0: KR_OK; an item with n[i] == 0 adds nothing. */
+int kr_post_return_map_batch_dev_f64(int32_t count, double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_return_map* m,
+                                     void* const* d_rays, const int64_t* n, void* const* d_out, void* stream);
 
 /* ---- emission-line profile / transfer function (kr_line_bins above) --------------------------------------------------------------------
  * Every entry point validates the bins first, before it touches a device: KR_EINVAL (message in kr_last_error) when ne < 1 or nt < 1, de <= 0,

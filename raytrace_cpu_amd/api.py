@@ -194,6 +194,141 @@ def image_planes_from_words(words, nx, ny):
     return out
 
 
+RETURN_MAP_PLANES = ("count", "weight", "flux", "emis", "time")
+RETURN_MAP_SCALARS = ("ray_count", "return", "escape", "lost", "on_disc", "binned")
+
+
+def return_map_words(m):
+    """Length of the landing-map buffer: five planes of nr and six scalars (include/kr_trace.h, kr_return_map)."""
+    return 5 * m.nr + 6
+
+
+def return_map_from_words(m, words):
+    """The landing-map buffer as a dict: count / weight / flux / emis / time (nr raw sums each; count stays a double array of whole numbers),
+    ray_count / return / escape / lost (weighted sums, as kr_reduce_return_f64 gives them), on_disc / binned (ints) and the nr + 1 bin edges."""
+    nr = m.nr
+    words = np.asarray(words, dtype=np.float64)
+    out = {k: words[q * nr:(q + 1) * nr].copy() for q, k in enumerate(RETURN_MAP_PLANES)}
+    out.update({k: float(words[5 * nr + q]) for q, k in enumerate(RETURN_MAP_SCALARS[:4])})
+    out.update({k: int(round(float(words[5 * nr + 4 + q]))) for q, k in enumerate(RETURN_MAP_SCALARS[4:])})
+    k = np.arange(nr + 1)
+    out["r_edges"] = m.r_min * m.dr ** k if m.logbin else m.r_min + m.dr * k
+    return out
+
+
+def reduce_return_map(m, rays):
+    """kr_reduce_return_map_f64: the landing map of host ray records after range_phi() and redshift(-1)."""
+    _rays_arg(rays, capi.RAY_F64)
+    out = np.zeros(return_map_words(m))
+    capi.check(lib(), lib().kr_reduce_return_map_f64(C.byref(m), _ptr(rays), len(rays), _ptr(out)), "kr_reduce_return_map")
+    return return_map_from_words(m, out)
+
+
+def return_map_struct(r_isco, r_disc, r_esc, source_r, source_phi, r_min, dr, nr, logbin, gamma=2.0, plane_iso=1, limb=0, weight_norm=1):
+    m = capi.ReturnMap()
+    c = m.cls
+    c.r_isco, c.r_disc, c.r_esc, c.source_r, c.source_phi = r_isco, r_disc, r_esc, source_r, source_phi
+    c.plane_iso, c.limb, c.weight_norm, c.pad = int(plane_iso), int(limb), int(weight_norm), 0
+    m.r_min, m.dr, m.gamma, m.nr, m.logbin = r_min, dr, gamma, int(nr), int(logbin)
+    return m
+
+
+def return_radiation_sources(spin, source_radii, dcosalpha, dbeta, source_phi=1.5707, cosalpha0=-0.995, cosalphamax=0.995):
+    """The PointSources of disc_source_photonfrac_r.cpp:66-89, one per radius: on the disc (theta = pi / 2 - 1e-6), in Keplerian motion
+    (V = kr_disc_velocity), beta in [0, pi)."""
+    specs = []
+    for r_s in source_radii:
+        s = capi.PointSourceSpec()
+        for i, v in enumerate((0.0, float(r_s), np.pi / 2 - 1e-6, source_phi)):
+            s.pos[i] = v
+        s.V, s.spin, s.tol, s.E = lib().kr_disc_velocity(float(r_s), spin, 1), spin, 100.0, 1.0
+        s.cosalpha0, s.cosalphamax, s.dcosalpha = cosalpha0, cosalphamax, dcosalpha
+        s.beta0, s.betamax, s.dbeta = 0.0, np.pi, dbeta
+        specs.append(s)
+    return specs
+
+
+def _add_stats(total, st):
+    for k, v in st.items():
+        total[k] = v if k not in total else max(total[k], v) if k.startswith("longest_") else total[k] + v
+    return total
+
+
+def return_radiation(spin, source_radii, dcosalpha, dbeta, r_disc=500.0, r_esc=1000.0, r_min=None, nr=100, logbin=False, gamma=2.0, plane_iso=1, limb=0,
+                     weight_norm=1, source_phi=1.5707, integrator=capi.EULER, flags=0, cosalpha0=-0.995, cosalphamax=0.995, return_records=False):
+    """The disc -> disc returning-radiation sweep with its landing map, resident on the device from start to finish, as the kr_return_radiation
+    app runs it: for every source radius a PointSource on the disc + redshift_start (kr_pointsource_init_emit_batch_dev_f64) -> the merged batch
+    trace to theta = pi / 2 or r = 1.1 r_esc (kr_trace_batch_async_f64) -> range_phi + redshift(-1) + classification + landing map
+    (kr_post_return_map_batch_dev_f64).  The landing bins are nr bins from r_min (default: the ISCO) to r_disc, linear or logarithmic.  Radii are
+    processed in groups whose ray buffers stay under a quarter of the device's memory; only the (5 nr + 6)-word results are read back (and, with
+    return_records, the final records: a list of arrays, for tests).
+    Returns the planes count / weight / flux / emis / time as (len(source_radii), nr) arrays, the six scalars as arrays over the radii, "stats" (the
+    trace counters summed over the groups), "r_isco", "r_min", "dr", "r_edges"."""
+    import math
+    L = lib()
+    radii = [float(r) for r in source_radii]
+    r_isco = L.kr_kerr_isco(spin, 1)
+    r_min = r_isco if r_min is None or r_min < 0 else float(r_min)
+    if nr <= 0:
+        raise KrError("return_radiation: nr must be positive")
+    dr = math.exp(math.log(r_disc / r_min) / nr) if logbin else (r_disc - r_min) / nr       # the C library's, as the app computes it
+    specs = return_radiation_sources(spin, radii, dcosalpha, dbeta, source_phi, cosalpha0, cosalphamax)
+    counts = [pointsource_count(s)[0] for s in specs]
+    if any(c <= 0 for c in counts):
+        raise KrError("return_radiation: empty ray grid")
+    maps = [return_map_struct(r_isco, r_disc, r_esc, r_s, source_phi, r_min, dr, nr, logbin, gamma, plane_iso, limb, weight_norm) for r_s in radii]
+    p = capi.default_params(spin)
+    p.integrator, p.theta_max, p.r_max, p.stop_kind, p.flags = integrator, np.pi / 2, 1.1 * r_esc, capi.STOP_THETA, flags
+    nsrc, nw = len(radii), 5 * nr + 6
+    words = np.zeros((nsrc, nw))
+    stats, records = {}, []
+    if nsrc == 0:
+        per_group = 1
+    else:
+        slot = (max(counts) * capi.RAY_F64.itemsize + 255) // 256 * 256
+        per_group = int(max(1, min(256, (device_info()["hbm_bytes"] // 4) // slot)))
+    d_rays, d_out = C.c_void_p(), C.c_void_p()
+    try:
+        if nsrc:
+            capi.check(L, L.kr_malloc(C.byref(d_out), nsrc * nw * 8), "kr_malloc")
+            capi.check(L, L.kr_memset(d_out, 0, nsrc * nw * 8), "kr_memset")
+            capi.check(L, L.kr_malloc(C.byref(d_rays), min(per_group, nsrc) * slot), "kr_malloc")
+        for first in range(0, nsrc, per_group):
+            idx = range(first, min(first + per_group, nsrc))
+            k = len(idx)
+            ss = (capi.PointSourceSpec * k)(*[specs[j] for j in idx])
+            V = (C.c_double * k)(*[specs[j].V for j in idx])
+            ptr_values = [d_rays.value + q * slot for q in range(k)]
+            ptrs = (C.c_void_p * k)(*ptr_values)
+            ns = (C.c_int64 * k)(*[counts[j] for j in idx])
+            mm = (capi.ReturnMap * k)(*[maps[j] for j in idx])
+            outs = (C.c_void_p * k)(*[d_out.value + 8 * nw * j for j in idx])
+            capi.check(L, L.kr_pointsource_init_emit_batch_dev_f64(k, ss, V, 0, 0, ptrs, ns, None), "kr_pointsource_init_emit_batch")
+            tickets = trace_batch_async([p] * k, ptr_values, [counts[j] for j in idx])
+            rc = L.kr_post_return_map_batch_dev_f64(k, spin, -1.0, 0, 0, 0, -np.pi, np.pi, mm, ptrs, ns, outs, None)
+            _add_stats(stats, trace_wait_many(tickets))          # the tickets are retired whatever the pass said
+            capi.check(L, rc, "kr_post_return_map_batch")
+            capi.check(L, L.kr_synchronize(None), "kr_synchronize")
+            if return_records:
+                for q, j in enumerate(idx):
+                    rec = np.zeros(counts[j], dtype=capi.RAY_F64)
+                    capi.check(L, L.kr_memcpy_d2h(_ptr(rec), C.c_void_p(ptr_values[q]), rec.nbytes), "kr_memcpy_d2h")
+                    records.append(rec)
+        if nsrc:
+            capi.check(L, L.kr_memcpy_d2h(_ptr(words), d_out, words.nbytes), "kr_memcpy_d2h")
+    finally:
+        for d in (d_rays, d_out):
+            if d.value:
+                L.kr_free(d)
+    res = {k: words[:, q * nr:(q + 1) * nr].copy() for q, k in enumerate(RETURN_MAP_PLANES)}
+    res.update({k: words[:, 5 * nr + q].copy() for q, k in enumerate(RETURN_MAP_SCALARS)})
+    e = np.arange(nr + 1)
+    res.update(stats=stats, r_isco=r_isco, r_min=r_min, dr=dr, r_edges=r_min * dr ** e if logbin else r_min + dr * e, maps=maps, specs=specs)
+    if return_records:
+        res["records"] = records
+    return res
+
+
 def line_words(bins):
     """Length of the line histogram buffer: [count (nt x ne) | flux (nt x ne) | on_disc | binned] (include/kr_trace.h, kr_line_bins)."""
     return 2 * bins.nt * bins.ne + 2

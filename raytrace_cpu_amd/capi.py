@@ -72,6 +72,12 @@ class ReturnBins(C.Structure):
                [(n, C.c_int32) for n in ("plane_iso", "limb", "weight_norm", "pad")]
 
 
+class ReturnMap(C.Structure):
+    """kr_return_map: the landing map of the returning radiation -- kr_return_bins (cls) plus the landing-radius bins (include/kr_trace.h has the
+    per-ray rule)."""
+    _fields_ = [("cls", ReturnBins), ("r_min", C.c_double), ("dr", C.c_double), ("gamma", C.c_double), ("nr", C.c_int32), ("logbin", C.c_int32)]
+
+
 class LineBins(C.Structure):
     """kr_line_bins: emission-line energy x time bins (include/kr_trace.h has the per-ray rules).  table_emis / table_time are host
     double arrays or None; keep the arrays alive while the struct is in use (LineBins.with_table does)."""
@@ -213,6 +219,10 @@ PROTOTYPES = {
     "kr_post_return_dev_f64": (_int, [_dbl, _dbl, P(ReturnBins), _vp, _i64, _vp, _vp]),
     "kr_post_return_batch_dev_f64": (_int, [_i32, _dbl, _dbl, P(ReturnBins), P(_vp), P(_i64), P(_vp), _vp]),
     "kr_pointsource_init_emit_batch_dev_f64": (_int, [_i32, P(PointSourceSpec), P(_dbl), _int, _int, P(_vp), P(_i64), _vp]),
+    "kr_reduce_return_map_f64": (_int, [P(ReturnMap), _vp, _i64, _vp]),
+    "kr_reduce_return_map_dev_f64": (_int, [P(ReturnMap), _vp, _i64, _vp, _vp]),
+    "kr_post_return_map_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, P(ReturnMap), _vp, _i64, _vp, _vp]),
+    "kr_post_return_map_batch_dev_f64": (_int, [_i32, _dbl, _dbl, _int, _int, _int, _dbl, _dbl, P(ReturnMap), P(_vp), P(_i64), P(_vp), _vp]),
     "kr_reduce_line_f64": (_int, [P(LineBins), _vp, _i64, _vp]),
     "kr_reduce_line_dev_f64": (_int, [P(LineBins), _vp, _i64, _vp, _vp]),
     "kr_post_line_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, P(LineBins), _vp, _i64, _vp, _vp]),

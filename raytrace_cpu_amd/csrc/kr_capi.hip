@@ -748,6 +748,44 @@ int kr_reduce_return_f64(const kr_return_bins* b, const kr_ray_f64* rays, int64_
 }
 
 // ---- emission line (kr_line.hip): the bins are validated before anything touches a device ----------------------------------
+int kr_reduce_return_map_dev_f64(const kr_return_map* m, const void* d, int64_t n, void* d_out, void* st)
+{
+    const int rc = return_map_validate(m, "kr_reduce_return_map");
+    if (rc != KR_OK) return rc;
+    return on_device(n >= 0 && d_out && (n == 0 || d), "kr_reduce_return_map: null argument or negative n", [&] { return reduce_return_map_dev(m, d, n, d_out, (hipStream_t) st); });
+}
+
+int kr_post_return_map_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_return_map* m, void* d, int64_t n,
+                               void* d_out, void* st)
+{
+    const int rc = return_map_validate(m, "kr_post_return_map");
+    if (rc != KR_OK) return rc;
+    return on_device(n >= 0 && d_out && (n == 0 || d), "kr_post_return_map: null argument or negative n",
+                     [&] { return post_return_map_dev(spin, V, reverse, projradius, motion, lo, hi, m, d, n, d_out, (hipStream_t) st); });
+}
+
+int kr_post_return_map_batch_dev_f64(int32_t count, double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_return_map* m,
+                                     void* const* d, const int64_t* n, void* const* d_out, void* st)
+{
+    if (count < 0 || (count > 0 && (!m || !d || !n || !d_out))) return invalid("kr_post_return_map_batch: null argument or negative count");
+    for (int32_t i = 0; i < count; i++) {
+        const int rc = return_map_validate(&m[i], "kr_post_return_map_batch");
+        if (rc != KR_OK) return rc;
+        if (n[i] < 0) return invalid("kr_post_return_map_batch: negative n");
+        if (n[i] > 0 && (!d[i] || !d_out[i])) return invalid("kr_post_return_map_batch: null buffer");
+    }
+    if (count == 0) return KR_OK;
+    return on_device(true, nullptr, [&] { return post_return_map_batch_dev(count, spin, V, reverse, projradius, motion, lo, hi, m, d, n, d_out, (hipStream_t) st); });
+}
+
+int kr_reduce_return_map_f64(const kr_return_map* m, const kr_ray_f64* rays, int64_t n, double* out)
+{
+    const int rc = return_map_validate(m, "kr_reduce_return_map");
+    if (rc != KR_OK) return rc;
+    if (!out) return invalid("kr_reduce_return_map: null argument");
+    return reduce_to_host(rays, n, 5 * (size_t) m->nr + 6, out, [&](void* d, void* d_out) { return reduce_return_map_dev(m, d, n, d_out, nullptr); });
+}
+
 int kr_reduce_line_dev_f64(const kr_line_bins* b, const void* d, int64_t n, void* d_line, void* st)
 {
     const int rc = line_validate(b, "kr_reduce_line");

@@ -1,4 +1,4 @@
-// kr_pass.hpp -- what the O(N) passes either side of the trace kernel share (kr_post.hip, kr_line.hip, kr_caustic.hip) and what kr_capi.hip calls
+// kr_pass.hpp -- what the O(N) passes either side of the trace kernel share (kr_post.hip, kr_return_map.hip, kr_line.hip, kr_caustic.hip) and what kr_capi.hip calls
 // them through: the launch helpers, the per-record pieces that several kernels repeat, and the one declaration of every launcher.
 // The device helpers are plain forced-inline functions and one loop macro: each kernel compiles to the code it had with the lines written out.
 #pragma once
@@ -116,6 +116,13 @@ int reduce_return_dev(const kr_return_bins* b, const void* d, int64_t n, void* d
 int post_return_dev(double lo, double hi, const kr_return_bins* b, void* d, int64_t n, void* d_out4, hipStream_t st);
 int post_return_batch_dev(int count, double lo, double hi, const kr_return_bins* b, void* const* d, const int64_t* n, void* const* d_out4, hipStream_t st);
 int arith_probe_dev(int op, const double* a, const double* b, double* out, int64_t n);
+// kr_return_map.hip: the landing map of the returning radiation (kr_return_map); the validator refuses a null map and nr <= 0
+int return_map_validate(const kr_return_map* m, const char* who);
+int reduce_return_map_dev(const kr_return_map* m, const void* d, int64_t n, void* d_out, hipStream_t st);
+int post_return_map_dev(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_return_map* m, void* d, int64_t n, void* d_out,
+                        hipStream_t st);
+int post_return_map_batch_dev(int count, double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_return_map* m, void* const* d,
+                              const int64_t* n, void* const* d_out, hipStream_t st);
 // kr_line.hip
 int line_validate(const kr_line_bins* b, const char* who);
 int reduce_line_dev(const kr_line_bins* b, const void* d, int64_t n, void* d_line, hipStream_t st);
