@@ -344,6 +344,19 @@ typedef struct kr_path_spec {
 static_assert(sizeof(kr_path_spec) == 24, "kr_path_spec is 24 bytes (raytrace_cpu_amd/capi.py PathSpec)");
 #endif
 
+/* The (r, theta, phi) grid of a volume illumination map and the observers that measure a ray's energy shift in it (kr_trace_volume_* below has the
+ * rule).  Radial edges r_min dr^i (logbin) or r_min + i dr; polar cells of dtheta from theta = 0; azimuthal cells of dphi from phi = -pi.
+ * mode 0: one deposit per passage of a cell; 1: one per row (Mapper::map_ray's literal behaviour).  V, reverse, projradius, motion: as kr_redshift_dev_f64
+ * takes them (V = -1, projradius = 1: the mapper's own 1 / (a + r sin(theta) sqrt(r sin(theta)))). */
+typedef struct kr_volume_map {
+    double r_min, dr, dtheta, dphi;
+    double V;
+    int32_t nr, ntheta, nphi, logbin, mode, reverse, projradius, motion;
+} kr_volume_map;
+#ifdef __cplusplus
+static_assert(sizeof(kr_volume_map) == 72, "kr_volume_map is 72 bytes (raytrace_cpu_amd/capi.py VolumeMap)");
+#endif
+
 /* ---- runtime ---------------------------------------------------------------------------------- */
 int         kr_abi_version(void);
 const char* kr_last_error(void);
@@ -438,6 +451,36 @@ int kr_trace_paths_record_dev_f64(const kr_params* p, const kr_path_spec* w, voi
                                   int64_t total_rows, void* stream, kr_stats* stats);
 int kr_trace_paths_f64(const kr_params* p, const kr_path_spec* w, kr_ray_f64* rays, int64_t n, int64_t* offsets /* n + 1 */, uint8_t* traced /* n or NULL */,
                        double** rows, int64_t* total_rows, kr_stats* stats);
+
+/* ---- volume illumination maps: Mapper::map_ray (src/mapper/mapper.cpp:110-281) restated against the loop above -- every ray is binned into the
+ * (r, theta, phi) grid of a kr_volume_map AS IT STEPS, with its arrival time and energy shift.  Euler and RK4, double precision, strict arithmetic.
+ * Rows: a ray produces a row {t, r, theta, phi} after the state update of every iteration that is neither a theta flip nor one that ended on
+ * r <= horizon or on dest->reached(): exactly the rows kr_trace_paths_* writes with write_step = 1 and an open window (an iteration whose update
+ * makes the loop condition false has a row, the start point has none).
+ * Cell: q_r = logbin ? log(r / r_min) / log(dr) : (r - r_min) / dr;  q_th = theta / dtheta;  q_ph = (phi_w + M_PI) / dphi with
+ * phi_w = phi - 2 M_PI floor((phi + M_PI) / (2 M_PI)); with nphi == 1 there is no phi test and no wrap, iphi = 0 (the axisymmetric map).  The row is
+ * in the grid iff 0 <= q < n on every axis, decided on q itself (a NaN or infinite q is outside, and no error: kr_emis_bins' convention); its cell
+ * is ((int) q_r * ntheta + (int) q_th) * nphi + (int) q_ph (Array3D's layout).  Apart from the log each is a single IEEE operation.
+ * Deposit: mode 0 (passage) -- every ray keeps last_cell, -1 when it starts; a row deposits iff it is in the grid and its cell differs from
+ * last_cell; last_cell then becomes the row's cell, or -1 for a row outside the grid, whether or not g passed.  mode 1 -- every row in the grid deposits.
+ * A due deposit evaluates g = ray_redshift(V, reverse, projradius, r, theta, phi, k, h, Q, rdot_sign, thetadot_sign, emit, motion) (raytracer.cpp:480-553,
+ * as kr_redshift_dev_f64 does) at the row, emit from the ray's record; g > 0 and finite: count[cell] += 1, time[cell] += t, redshift[cell] += g;
+ * otherwise only bad_g moves.
+ * Departures from mapper.cpp, both deliberate: its range test `ir > 0 && ...` (:247) drops cell 0 of every axis -- here cell 0 is a cell; it never
+ * assigns last_ir / last_itheta / last_iphi, so it deposits at every step (mode 1) where the consumers of the map expect mode 0.  vel_mode 1 / 2 are
+ * not offered.
+ * d_map: double[3 ncell + 4], ncell = nr ntheta nphi: [count | time | redshift | rows, in_grid, deposits, bad_g]; counts are whole-numbered doubles,
+ * rows == offsets[n] of the write_step = 1 recording, deposits == the sum of count.
+ * kr_trace_volume_dev_f64 integrates every ray as kr_trace_dev_f64 with flags = 0 does -- d_rays ends with that trace's records, bit for bit -- and
+ * ADDS into d_map, so sources, shards and batches sum into one map (calls into one map from several streams may overlap: every addition is atomic).
+ * It fills *stats (may be NULL: rays_total, rays_traced, steps_total, longest_ray_steps, kernel_ms: the map launch and the kernel that adds its
+ * tallies) and SYNCHRONISES `stream` before it returns (the launch's counters come back to the host).
+ * n == 0 leaves d_map untouched.  kr_trace_volume_f64: host pointers; stages rays[], and map[0 .. 3 ncell + 4) is OVERWRITTEN.
+ * Refused with KR_EINVAL before any device work: null pointers, n < 0, nr / ntheta / nphi < 1, ncell > 2^27, dr / dtheta / dphi not finite or <= 0,
+ * logbin with dr <= 1 or r_min <= 0, an unknown mode or motion, and what kr_trace_paths_* refuses of a kr_params: KR_FLAG_FAST_MATH / KR_FLAG_HYBRID,
+ * KR_RK45, Euler with a destination stop kind.  Without a device: KR_ENODEVICE. */
+int kr_trace_volume_dev_f64(const kr_params* p, const kr_volume_map* m, void* d_rays, int64_t n, void* d_map /* double[3 ncell + 4] */, void* stream, kr_stats* stats);
+int kr_trace_volume_f64(const kr_params* p, const kr_volume_map* m, kr_ray_f64* rays, int64_t n, double* map /* 3 ncell + 4 */, kr_stats* stats);
 
 /* ---- O(N) passes either side of it ----------------------------------------------------------- */
 /* Raytracer<T>::redshift_start(V, reverse, projradius)  raytracer.cpp:342-417 */

@@ -652,3 +652,108 @@ def paths_text(offsets, rows, traced):
             parts.append("".join(_path_field(v) for v in row) + "\n")
         parts.append("\n\n")
     return "".join(parts)
+
+
+VOLUME_PLANES = ("count", "time", "redshift")
+VOLUME_TALLIES = ("rows", "in_grid", "deposits", "bad_g")
+
+
+def volume_map_struct(r0, rmax, nr, ntheta, nphi, logbin, V=-1.0, mode=0, reverse=0, projradius=1, motion=0):
+    """A kr_volume_map with the bin widths of Mapper's constructor (src/mapper/mapper.cpp:14-16), from the C library as it computes them:
+    dr = exp(log(rmax / r0) / (nr - 1)) or (rmax - r0) / (nr - 1), dtheta = (pi / 2) / (ntheta - 1), dphi = 2 pi / (nphi - 1) -- n cells of that
+    width, so the last cell starts at the upper bound.  An axis of ONE cell (where the constructor divides by zero) spans the whole range:
+    rmax / r0 or rmax - r0, pi / 2, 2 pi.  mode 0: one deposit per passage of a cell, 1: one per row; V, reverse, projradius, motion: as redshift()."""
+    import math
+    m = capi.VolumeMap()
+    m.r_min = float(r0)
+    m.dr = math.exp(math.log(rmax / r0) / max(nr - 1, 1)) if logbin else (rmax - r0) / max(nr - 1, 1)
+    m.dtheta = (math.pi / 2) / max(ntheta - 1, 1)
+    m.dphi = (2 * math.pi) / max(nphi - 1, 1)
+    m.V = float(V)
+    m.nr, m.ntheta, m.nphi, m.logbin = int(nr), int(ntheta), int(nphi), int(bool(logbin))
+    m.mode, m.reverse, m.projradius, m.motion = int(mode), int(reverse), int(projradius), int(motion)
+    return m
+
+
+def volume_words(m):
+    """Length of a volume map buffer: three planes of nr ntheta nphi cells and four tallies (include/kr_trace.h, kr_trace_volume_*)."""
+    return 3 * m.nr * m.ntheta * m.nphi + 4
+
+
+def volume_from_words(m, words):
+    """The volume map buffer as a dict: count / time / redshift (raw sums, shaped (nr, ntheta, nphi); count stays a double array of whole numbers)
+    and the tallies rows / in_grid / deposits / bad_g (ints)."""
+    shape = (m.nr, m.ntheta, m.nphi)
+    ncell = m.nr * m.ntheta * m.nphi
+    words = np.asarray(words, dtype=np.float64)
+    out = {k: words[q * ncell:(q + 1) * ncell].reshape(shape).copy() for q, k in enumerate(VOLUME_PLANES)}
+    out.update({k: int(round(float(words[3 * ncell + q]))) for q, k in enumerate(VOLUME_TALLIES)})
+    return out
+
+
+def cell_volume(m, spin):
+    """Mapper::calculate_volume (src/mapper/mapper.cpp:311-338) on the host: sqrt(-g_rr g_thth g_phph) dr dtheta dphi at the lower corner of every
+    cell, shaped (nr, ntheta, nphi).  O(cells)."""
+    a = float(spin)
+    ir = np.arange(m.nr, dtype=np.float64)
+    r = (m.r_min * np.power(m.dr, ir) if m.logbin else m.r_min + m.dr * ir)[:, None]
+    this_dr = r * (m.dr - 1) if m.logbin else np.full_like(r, m.dr)
+    theta = (np.arange(m.ntheta, dtype=np.float64) * m.dtheta)[None, :]
+    rhosq = r * r + (a * np.cos(theta)) * (a * np.cos(theta))
+    delta = r * r - 2 * r + a * a
+    sigmasq = (r * r + a * a) * (r * r + a * a) - a * a * delta * np.sin(theta) * np.sin(theta)
+    e2psi = sigmasq * np.sin(theta) * np.sin(theta) / rhosq
+    grr, gthth, gphph = -rhosq / delta, -rhosq, -e2psi
+    with np.errstate(invalid="ignore"):
+        vol = np.sqrt(-1 * grr * gthth * gphph) * this_dr * m.dtheta * m.dphi
+    return np.repeat(vol[:, :, None], m.nphi, axis=2)
+
+
+def trace_volume(params, rays, m):
+    """kr_trace_volume_f64 on a host array of Ray<double> records (Euler / RK4, strict arithmetic): the rays are integrated as trace(flags = 0)
+    integrates them and binned into the grid of `m` as they step.  Returns a dict: count / time / redshift shaped (nr, ntheta, nphi), the tallies
+    rows / in_grid / deposits / bad_g, "rays" (the final records, as trace() gives them) and "stats"."""
+    _rays_arg(rays, capi.RAY_F64)
+    out = rays.copy()
+    words = np.zeros(volume_words(m))
+    st = Stats()
+    capi.check(lib(), lib().kr_trace_volume_f64(C.byref(params), C.byref(m), _ptr(out), len(out), _ptr(words), C.byref(st)), "kr_trace_volume")
+    res = volume_from_words(m, words)
+    res.update(rays=out, stats=st.as_dict())
+    return res
+
+
+def volume_map(sources, params, m, reverse=0, projradius=0):
+    """The map of an extended source as a sum over point sources, resident on the device: for every PointSourceSpec the rays with their emitted
+    energy (kr_pointsource_init_emit_dev_f64: redshift_start with the source's own V) -> kr_trace_volume_dev_f64, all adding into ONE map.
+    Returns the sums count / time / redshift, the tallies, "mean_time" = time / count and "mean_redshift" = redshift / count (Mapper::average_rays;
+    NaN in cells no ray crossed), "num_rays" (rays traced) and "stats" (summed over the sources)."""
+    L = lib()
+    nw = volume_words(m)
+    words = np.zeros(nw)
+    stats, d_map = {}, C.c_void_p()
+    try:
+        capi.check(L, L.kr_malloc(C.byref(d_map), nw * 8), "kr_malloc")
+        capi.check(L, L.kr_memset(d_map, 0, nw * 8), "kr_memset")
+        for s in sources:
+            n = pointsource_count(s)[0]
+            if n <= 0:
+                raise KrError("volume_map: empty ray grid")
+            d_rays = C.c_void_p()
+            capi.check(L, L.kr_malloc(C.byref(d_rays), n * capi.RAY_F64.itemsize), "kr_malloc")
+            try:
+                capi.check(L, L.kr_pointsource_init_emit_dev_f64(C.byref(s), 0, 1, s.V, int(reverse), int(projradius), d_rays, n, None), "kr_pointsource_init_emit")
+                st = Stats()
+                capi.check(L, L.kr_trace_volume_dev_f64(C.byref(params), C.byref(m), d_rays, n, d_map, None, C.byref(st)), "kr_trace_volume")
+                _add_stats(stats, st.as_dict())
+            finally:
+                L.kr_free(d_rays)
+        capi.check(L, L.kr_memcpy_d2h(_ptr(words), d_map, words.nbytes), "kr_memcpy_d2h")
+    finally:
+        if d_map.value:
+            L.kr_free(d_map)
+    res = volume_from_words(m, words)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        res.update(mean_time=res["time"] / res["count"], mean_redshift=res["redshift"] / res["count"])
+    res.update(num_rays=int(stats.get("rays_traced", 0)), stats=stats)
+    return res

@@ -110,6 +110,12 @@ class PathSpec(C.Structure):
     _fields_ = [("write_rmin", C.c_double), ("write_rmax", C.c_double), ("write_step", C.c_int32), ("pad", C.c_int32)]
 
 
+class VolumeMap(C.Structure):
+    """kr_volume_map: the (r, theta, phi) grid of a volume illumination map and the observers of its energy shift (include/kr_trace.h has the rule)."""
+    _fields_ = [(n, C.c_double) for n in ("r_min", "dr", "dtheta", "dphi", "V")] + \
+               [(n, C.c_int32) for n in ("nr", "ntheta", "nphi", "logbin", "mode", "reverse", "projradius", "motion")]
+
+
 def line_bins(line_energy=6.4, e_min=1.0, de=0.1, ne=90, log_e=False, t0=0.0, dt=0.0, nt=1, r_isco=1.0, r_disc=1000.0, q1=3.0, rb1=4.0, q2=3.0,
               rb2=10.0, q3=3.0, g_index=3.0):
     b = LineBins()
@@ -175,6 +181,8 @@ PROTOTYPES = {
     "kr_trace_paths_count_dev_f64": (_int, [P(Params), P(PathSpec), _vp, _i64, _vp, _vp, P(_i64), _vp]),
     "kr_trace_paths_record_dev_f64": (_int, [P(Params), P(PathSpec), _vp, _i64, _vp, _vp, _i64, _vp, P(Stats)]),
     "kr_trace_paths_f64": (_int, [P(Params), P(PathSpec), _vp, _i64, _vp, _vp, P(_vp), P(_i64), P(Stats)]),
+    "kr_trace_volume_dev_f64": (_int, [P(Params), P(VolumeMap), _vp, _i64, _vp, _vp, P(Stats)]),
+    "kr_trace_volume_f64": (_int, [P(Params), P(VolumeMap), _vp, _i64, _vp, P(Stats)]),
     "kr_redshift_start_f64": (_int, [_dbl, _dbl, _int, _int, _vp, _i64]),
     "kr_redshift_start_dev_f64": (_int, [_dbl, _dbl, _int, _int, _vp, _i64, _vp]),
     "kr_redshift_f64": (_int, [_dbl, _dbl, _int, _int, _int, _vp, _i64]),

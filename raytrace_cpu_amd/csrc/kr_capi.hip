@@ -582,6 +582,34 @@ int kr_trace_paths_f64(const kr_params* p, const kr_path_spec* w, kr_ray_f64* ra
     return KR_OK;
 }
 
+// ---- volume illumination maps (kr_volume.hip): Mapper::map_ray, mapper.cpp:110-281 ---------------------------------------------------------------
+int kr_trace_volume_dev_f64(const kr_params* p, const kr_volume_map* m, void* d_rays, int64_t n, void* d_map, void* stream, kr_stats* stats)
+{
+    const int rc = volume_validate(p, m, "kr_trace_volume");
+    if (rc != KR_OK) return rc;
+    return on_device(n >= 0 && (n == 0 || d_rays) && d_map, "kr_trace_volume: null argument or negative n",
+                     [&] { return trace_volume_dev(p, m, d_rays, n, d_map, (hipStream_t) stream, stats); });
+}
+
+int kr_trace_volume_f64(const kr_params* p, const kr_volume_map* m, kr_ray_f64* rays, int64_t n, double* map, kr_stats* stats)
+{
+    const int rc = volume_validate(p, m, "kr_trace_volume");
+    if (rc != KR_OK) return rc;
+    if (!map || n < 0 || (n > 0 && !rays)) return invalid("kr_trace_volume: null argument or negative n");
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    const size_t words = 3 * (size_t) m->nr * m->ntheta * m->nphi + 4;
+    return with_staged_rays(rays, n, sizeof(kr_ray_f64), kUpdates, stats, [&](void* d) -> int {
+        DeviceBuffer d_map;
+        int rc2 = d_map.alloc(words * sizeof(double));
+        if (rc2 != KR_OK) return rc2;
+        KR_HIP(hipMemset(d_map.p, 0, words * sizeof(double)));
+        rc2 = trace_volume_dev(p, m, d, n, d_map.p, nullptr, stats);
+        if (rc2 != KR_OK) return rc2;
+        KR_HIP(hipMemcpy(map, d_map.p, words * sizeof(double), hipMemcpyDeviceToHost));
+        return (int) KR_OK;
+    });
+}
+
 // ---- O(N) passes -------------------------------------------------------------------------------------------
 // One line per pass: its scalar arguments, and the field(s) of a kr_ray_f64 it writes.  Each becomes four entry points: device and host
 // pointers, for Raytracer<double> and for Raytracer<float> (kr_ray_f32 records, float arithmetic; the scalars are float values carried in

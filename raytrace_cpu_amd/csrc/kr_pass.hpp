@@ -141,5 +141,8 @@ int paths_validate(const kr_params* p, const kr_path_spec* w, const char* who);
 int paths_count_dev(const kr_params* p, const kr_path_spec* w, const void* d_rays, int64_t n, void* d_offsets, void* d_traced, int64_t* total_rows, hipStream_t st);
 int paths_record_dev(const kr_params* p, const kr_path_spec* w, void* d_rays, int64_t n, const void* d_offsets, void* d_rows, int64_t total_rows, hipStream_t st,
                      kr_stats* stats);
+// kr_volume.hip: the mapping trace; the validator refuses a bad grid and what paths_validate refuses of the params; the launcher waits for `st`
+int volume_validate(const kr_params* p, const kr_volume_map* m, const char* who);
+int trace_volume_dev(const kr_params* p, const kr_volume_map* m, void* d_rays, int64_t n, void* d_map, hipStream_t st, kr_stats* stats);
 
 }  // namespace kr

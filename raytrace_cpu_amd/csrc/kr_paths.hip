@@ -51,7 +51,7 @@ KR_DEV bool in_window(const PathWindow& w, double r)
 // whether the ray passed the skip rule; rays[] is read only -- kStoresRays is false, so the instance has no store to it.
 // RECORD = true: offsets[0 .. n] are the scanned offsets; rows and the final ray records are stored.
 template <bool RECORD> struct PathRecorder {
-    static constexpr bool kActive = true, kStoresRays = RECORD;
+    static constexpr bool kActive = true, kStoresRays = RECORD, kWaveHook = false;
     PathWindow w;                     // the launch
     long long* __restrict__ offsets; unsigned char* __restrict__ traced; double* __restrict__ rows; long long total_rows;
     // this lane's ray

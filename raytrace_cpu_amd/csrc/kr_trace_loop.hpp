@@ -76,6 +76,7 @@ inline int persistent_grid(int cus, int blocks_per_cu, long long n)
 //   at_slot(slot, take)     a lane has loaded the record of `slot`; take: it passed the skip rule          claim(slot)     the lane takes that ray
 //   before_step(s), after_step<USE_DEST>(s, fin) -> fin     either side of the lane's step_fixed call     leave(idx)      ray idx leaves its lane
 //   at_exit(lane, counters)     the wave has left the loop: per-lane tallies -> counters[kRecorderWord]
+//   kWaveHook: wave_step_end() is called by ALL 64 lanes after every step of the wave (whole-wave reductions are valid there, not in after_step)
 struct NoRecorder { static constexpr bool kActive = false, kStoresRays = true; };
 
 // ---- the persistent loop ----------------------------------------------------------------------------
@@ -267,6 +268,7 @@ KR_DEV void trace_body(typename RayOf<T>::type* __restrict__ rays, long long n, 
                 pend = true;
             }
         }
+        if constexpr (REC::kActive) { if constexpr (REC::kWaveHook) rec.wave_step_end(); }
     }
     // per-wave totals -> global counters (4 atomics per wave, once)
     const unsigned long long w_traced = wave_sum(my_traced);
