@@ -357,6 +357,16 @@ typedef struct kr_volume_map {
 static_assert(sizeof(kr_volume_map) == 72, "kr_volume_map is 72 bytes (raytrace_cpu_amd/capi.py VolumeMap)");
 #endif
 
+/* The energy and time bins of an observed volume map (kr_trace_observe_* below has the rule).  Energy edges en0 + i den, or en0 den^i with logbin_en;
+ * time edges t0 + i dt; nt = 0: no response. */
+typedef struct kr_observe_bins {
+    double en0, den, t0, dt;
+    int32_t nen, nt, logbin_en, pad;
+} kr_observe_bins;
+#ifdef __cplusplus
+static_assert(sizeof(kr_observe_bins) == 48, "kr_observe_bins is 48 bytes (raytrace_cpu_amd/capi.py ObserveBins)");
+#endif
+
 /* ---- runtime ---------------------------------------------------------------------------------- */
 int         kr_abi_version(void);
 const char* kr_last_error(void);
@@ -481,6 +491,48 @@ int kr_trace_paths_f64(const kr_params* p, const kr_path_spec* w, kr_ray_f64* ra
  * KR_RK45, Euler with a destination stop kind.  Without a device: KR_ENODEVICE. */
 int kr_trace_volume_dev_f64(const kr_params* p, const kr_volume_map* m, void* d_rays, int64_t n, void* d_map /* double[3 ncell + 4] */, void* stream, kr_stats* stats);
 int kr_trace_volume_f64(const kr_params* p, const kr_volume_map* m, kr_ray_f64* rays, int64_t n, double* map /* 3 ncell + 4 */, kr_stats* stats);
+
+/* ---- observing a volume map: SourceTracer::propagate_source (src/source_tracer/source_tracer.cpp:102-310) restated against the loop above -- camera
+ * rays are marched back through the emitting volume and gather, AS THEY STEP, the emissivity of the cells they cross into an energy spectrum, an
+ * energy-time response and a per-ray total.  Euler and RK4, double precision, strict arithmetic.
+ * Rows: those of kr_trace_volume_*: the state after the update of every iteration that is neither a theta flip nor one that ended on r <= horizon or
+ * on dest->reached().
+ * Step displacement: the position before the step is the previous row, or the ray's initial record for its first row (a flip iteration moves nothing,
+ * so this is the ray's state as the iteration begins); dr, dtheta, dphi = row - before.
+ * Cell: as in the volume map -- the same kr_volume_map and the same quotients; the phi used is the ray's own (an ImagePlane ray in the mirrored spin
+ * carries the physical phi of the photon it reverses: no mirroring).  m->mode is validated and otherwise unused (this is a line integral);
+ * V, reverse, projradius, motion describe the emitter's frame as they do for the map.
+ * Inputs per cell, device arrays of ncell doubles: emis, the volume emissivity j; kappa, the absorption per unit proper length (NULL: optically thin);
+ * delay, the time from the flash to the cell (NULL: 0).
+ * Bins: kr_observe_bins.  q_e = logbin_en ? log(E / en0) / log(den) : (E - en0) / den;  q_t = (T - t0) / dt.  Range tests are decided on q itself
+ * (a NaN or infinite q is outside).
+ * Per row, in this order:
+ *  1. cell < 0: stop.  Otherwise ++in_grid.
+ *  2. j = emis[cell], kap = kappa ? kappa[cell] : 0.  !(j > 0) && !(kap > 0): stop.  Otherwise ++lit.
+ *  3. l = sqrt((Sigma / Delta) dr^2 + Sigma dtheta^2 + (A sin^2 theta / Sigma) dphi^2) at the row, Sigma = r^2 + a^2 cos^2 theta,
+ *     Delta = r^2 - 2 r + a^2, A = (r^2 + a^2)^2 - a^2 Delta sin^2 theta.  !(l > 0 && l < inf && |dphi| < pi / 2): ++degenerate, stop (the polar
+ *     reflection adds pi to phi: that row is dropped here).
+ *  4. j > 0: z = ray_redshift(...) at the row as kr_trace_volume_* evaluates it (the lane's signs, the ray's emit).  !(z > 0 && z < inf): ++bad_g.
+ *     Otherwise E = 1 / z, w = j l E E E, times exp(-tau) when kappa != NULL; image_ray += w, ++contributions; if 0 <= q_e < nen:
+ *     spectrum[(int) q_e] += w, hits[(int) q_e] += 1, and when nt > 0, T = t_row + (delay ? delay[cell] : 0), if 0 <= q_t < nt:
+ *     response[(int) q_e * nt + (int) q_t] += w.
+ *  5. tau += l kap.  tau is per ray and 0 when the ray starts.
+ * Departures from source_tracer.cpp, all deliberate: the square root in l (its `len`, :234, is a squared length); ONE grey tau per ray where it keeps
+ * absorb[ray][ien] per observed-energy bin; the time bin uses the bin width, not the step's dt that shadows it (:208, :263); the region and the
+ * emissivity come from the grid, not the hard-wired shell (:232, :247-258); no per-ray spectra (n x nen doubles is not a product) -- the per-ray total
+ * replaces them.
+ * d_out: double[2 nen + nen nt + 6]: [spectrum | hits | response | rows, in_grid, lit, contributions, bad_g, degenerate]; counts are whole-numbered
+ * doubles.  kr_trace_observe_dev_f64 integrates every ray as kr_trace_dev_f64 with flags = 0 does -- d_rays ends with that trace's records, bit for
+ * bit -- and ADDS into d_out, so shards and several planes sum into one result (every addition is atomic).  d_image: double[n] or NULL, OVERWRITTEN:
+ * the ray's total, 0 for a ray the skip rule passed over.  It fills *stats (may be NULL) and SYNCHRONISES `stream` before it returns, as
+ * kr_trace_volume_dev_f64 does.  n == 0 leaves d_out untouched.  kr_trace_observe_f64: host pointers; stages everything, out[] is OVERWRITTEN.
+ * Refused with KR_EINVAL before any device work: everything kr_trace_volume_* refuses; null b, emis, out or (n > 0) rays; nen < 1, nt < 0,
+ * 2 nen + nen nt > 2^27; den not finite or <= 0; logbin_en with den <= 1 or en0 <= 0; nt > 0 with dt not finite or <= 0; a non-finite en0 or t0.
+ * Without a device: KR_ENODEVICE. */
+int kr_trace_observe_dev_f64(const kr_params* p, const kr_volume_map* m, const kr_observe_bins* b, const void* d_emis, const void* d_kappa, const void* d_delay,
+                             void* d_rays, int64_t n, void* d_out /* double[2 nen + nen nt + 6] */, void* d_image /* double[n] or NULL */, void* stream, kr_stats* stats);
+int kr_trace_observe_f64(const kr_params* p, const kr_volume_map* m, const kr_observe_bins* b, const double* emis, const double* kappa, const double* delay,
+                         kr_ray_f64* rays, int64_t n, double* out /* 2 nen + nen nt + 6 */, double* image /* n or NULL */, kr_stats* stats);
 
 /* ---- O(N) passes either side of it ----------------------------------------------------------- */
 /* Raytracer<T>::redshift_start(V, reverse, projradius)  raytracer.cpp:342-417 */

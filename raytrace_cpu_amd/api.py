@@ -757,3 +757,123 @@ def volume_map(sources, params, m, reverse=0, projradius=0):
         res.update(mean_time=res["time"] / res["count"], mean_redshift=res["redshift"] / res["count"])
     res.update(num_rays=int(stats.get("rays_traced", 0)), stats=stats)
     return res
+
+
+OBSERVE_TALLIES = ("rows", "in_grid", "lit", "contributions", "bad_g", "degenerate")
+
+
+def observe_bins_struct(en0, enmax, nen, logbin_en=False, t0=0.0, tmax=0.0, nt=0):
+    """A kr_observe_bins of nen energy bins over [en0, enmax) -- den = (enmax - en0) / nen, or the ratio exp(log(enmax / en0) / nen) with
+    logbin_en -- and nt time bins over [t0, tmax) (nt = 0: no response)."""
+    import math
+    b = capi.ObserveBins()
+    b.en0, b.t0 = float(en0), float(t0)
+    b.den = math.exp(math.log(enmax / en0) / nen) if logbin_en else (enmax - en0) / nen
+    b.dt = (tmax - t0) / nt if nt > 0 else 0.0
+    b.nen, b.nt, b.logbin_en, b.pad = int(nen), int(nt), int(bool(logbin_en)), 0
+    return b
+
+
+def observe_words(b):
+    """Length of an observe output buffer: spectrum and hits of nen bins, the nen x nt response and six tallies (include/kr_trace.h, kr_trace_observe_*)."""
+    return 2 * b.nen + b.nen * b.nt + 6
+
+
+def observe_from_words(b, words):
+    """The observe output buffer as a dict: "energy" (the nen + 1 bin edges), spectrum, hits (a double array of whole numbers), response shaped
+    (nen, nt) and the tallies rows / in_grid / lit / contributions / bad_g / degenerate (ints)."""
+    words = np.asarray(words, dtype=np.float64)
+    nen, nt = b.nen, b.nt
+    i = np.arange(nen + 1, dtype=np.float64)
+    out = {"energy": b.en0 * np.power(b.den, i) if b.logbin_en else b.en0 + b.den * i,
+           "spectrum": words[:nen].copy(), "hits": words[nen:2 * nen].copy(), "response": words[2 * nen:2 * nen + nen * nt].reshape(nen, nt).copy()}
+    out.update({k: int(round(float(words[2 * nen + nen * nt + q]))) for q, k in enumerate(OBSERVE_TALLIES)})
+    return out
+
+
+def _cells_arg(a, m, name):
+    if a is None:
+        return None
+    a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+    if a.size != m.nr * m.ntheta * m.nphi:
+        raise KrError(f"trace_observe: {name} has {a.size} values, the grid has {m.nr * m.ntheta * m.nphi} cells")
+    return a
+
+
+def trace_observe(params, rays, m, bins, emis, kappa=None, delay=None, want_image=True):
+    """kr_trace_observe_f64 on a host array of Ray<double> records (Euler / RK4, strict arithmetic): the rays are integrated as trace(flags = 0)
+    integrates them and gather the emissivity `emis` (absorption `kappa`, flash delay `delay`; arrays of one value per cell of `m`) of the cells they
+    cross as they step.  Returns a dict: energy / spectrum / hits / response, the six tallies, "image" (the per-ray totals, or None), "rays" (the final
+    records, as trace() gives them) and "stats"."""
+    _rays_arg(rays, capi.RAY_F64)
+    out = rays.copy()
+    emis, kappa, delay = _cells_arg(emis, m, "emis"), _cells_arg(kappa, m, "kappa"), _cells_arg(delay, m, "delay")
+    if emis is None:
+        raise KrError("trace_observe: emis is required")
+    words = np.zeros(observe_words(bins))
+    image = np.zeros(len(out)) if want_image else None
+    st = Stats()
+    opt = lambda a: _ptr(a) if a is not None else None      # noqa: E731
+    capi.check(lib(), lib().kr_trace_observe_f64(C.byref(params), C.byref(m), C.byref(bins), _ptr(emis), opt(kappa), opt(delay), _ptr(out), len(out), _ptr(words),
+                                                 opt(image), C.byref(st)), "kr_trace_observe")
+    res = observe_from_words(bins, words)
+    res.update(image=image, rays=out, stats=st.as_dict())
+    return res
+
+
+def volume_emissivity(vmap, m, spin, gamma=2.0):
+    """(emis, delay) of a volume map (the dict volume_map returns), shaped (nr, ntheta, nphi): emis = count / (num_rays cell_volume) mean_redshift^-gamma,
+    the expression commented out at source_tracer.cpp:257 (gamma = 2 there), and delay = mean_time (:258).  Both are 0 where nothing crossed; emis is
+    also 0 in a cell of no volume (the lower corner of the first polar cell lies on the axis).  O(cells), on the host."""
+    count = np.asarray(vmap["count"], dtype=np.float64)
+    vol = cell_volume(m, spin)
+    ok = (count > 0) & (vol > 0) & np.isfinite(vol)
+    emis, delay = np.zeros(count.shape), np.zeros(count.shape)
+    mean_g = vmap["redshift"][ok] / count[ok]
+    emis[ok] = count[ok] / (float(vmap["num_rays"]) * vol[ok]) * np.power(mean_g, -1 * gamma)
+    hit = count > 0
+    delay[hit] = vmap["time"][hit] / count[hit]
+    return emis, delay
+
+
+def volume_spectrum(sources, plane_spec, p_source, p_plane, m, bins, gamma=2.0, kappa=None, reverse=1):
+    """Corona geometry -> observed spectrum and response of the illuminated volume, resident on the device: volume_map(sources, p_source, m) ->
+    volume_emissivity (host, O(cells)) -> the ImagePlane `plane_spec` built on the device with redshift_start(0, reverse)
+    (kr_imageplane_init_emit_dev_f64) -> kr_trace_observe_dev_f64 with `p_plane` (the stored, negated spin of an ImagePlane) and `m` with
+    reverse = `reverse` (the camera's rays run backwards).  The rays never leave the device.  kappa: one value per cell, or None.
+    Returns observe_from_words(...) plus "image" shaped (nx, ny), "map" (the volume map), "emis", "delay" and "stats" (the observing trace's)."""
+    L = lib()
+    vmap = volume_map(sources, p_source, m)
+    emis, delay = volume_emissivity(vmap, m, p_source.spin, gamma)
+    n, nx, ny = imageplane_count(plane_spec)
+    if n <= 0:
+        raise KrError("volume_spectrum: empty ray grid")
+    mo = capi.VolumeMap.from_buffer_copy(m)
+    mo.reverse = int(reverse)
+    cells = [_cells_arg(emis, m, "emis"), _cells_arg(kappa, m, "kappa"), _cells_arg(delay, m, "delay")]
+    nw = observe_words(bins)
+    words, image = np.zeros(nw), np.zeros(n)
+    d_rays, d_out, d_image = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    d_cells = [C.c_void_p() for _ in cells]
+    st = Stats()
+    try:
+        capi.check(L, L.kr_malloc(C.byref(d_rays), n * capi.RAY_F64.itemsize), "kr_malloc")
+        capi.check(L, L.kr_malloc(C.byref(d_out), nw * 8), "kr_malloc")
+        capi.check(L, L.kr_malloc(C.byref(d_image), n * 8), "kr_malloc")
+        capi.check(L, L.kr_memset(d_out, 0, nw * 8), "kr_memset")
+        for d, a in zip(d_cells, cells):
+            if a is not None:
+                capi.check(L, L.kr_malloc(C.byref(d), a.nbytes), "kr_malloc")
+                capi.check(L, L.kr_memcpy_h2d(d, _ptr(a), a.nbytes), "kr_memcpy_h2d")
+        capi.check(L, L.kr_imageplane_init_emit_dev_f64(C.byref(plane_spec), 0, 1, 0.0, int(reverse), 0, d_rays, n, None), "kr_imageplane_init_emit")
+        capi.check(L, L.kr_trace_observe_dev_f64(C.byref(p_plane), C.byref(mo), C.byref(bins), d_cells[0], d_cells[1] if cells[1] is not None else None,
+                                                 d_cells[2], d_rays, n, d_out, d_image, None, C.byref(st)), "kr_trace_observe")
+        capi.check(L, L.kr_memcpy_d2h(_ptr(words), d_out, words.nbytes), "kr_memcpy_d2h")
+        capi.check(L, L.kr_memcpy_d2h(_ptr(image), d_image, image.nbytes), "kr_memcpy_d2h")
+    finally:
+        for d in [d_rays, d_out, d_image] + d_cells:
+            if d.value:
+                L.kr_free(d)
+    res = observe_from_words(bins, words)
+    res.update(image=image.reshape(nx, ny), map=vmap, emis=emis, delay=delay, stats=st.as_dict())
+    return res

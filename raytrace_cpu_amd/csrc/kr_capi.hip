@@ -610,6 +610,49 @@ int kr_trace_volume_f64(const kr_params* p, const kr_volume_map* m, kr_ray_f64* 
     });
 }
 
+// ---- observing a volume map (kr_observe.hip): SourceTracer::propagate_source, source_tracer.cpp:102-310 -------------------------------------------
+int kr_trace_observe_dev_f64(const kr_params* p, const kr_volume_map* m, const kr_observe_bins* b, const void* d_emis, const void* d_kappa, const void* d_delay,
+                             void* d_rays, int64_t n, void* d_out, void* d_image, void* stream, kr_stats* stats)
+{
+    const int rc = observe_validate(p, m, b, "kr_trace_observe");
+    if (rc != KR_OK) return rc;
+    return on_device(n >= 0 && (n == 0 || d_rays) && d_emis && d_out, "kr_trace_observe: null argument (emis, out or rays) or negative n",
+                     [&] { return trace_observe_dev(p, m, b, d_emis, d_kappa, d_delay, d_rays, n, d_out, d_image, (hipStream_t) stream, stats); });
+}
+
+int kr_trace_observe_f64(const kr_params* p, const kr_volume_map* m, const kr_observe_bins* b, const double* emis, const double* kappa, const double* delay,
+                         kr_ray_f64* rays, int64_t n, double* out, double* image, kr_stats* stats)
+{
+    const int rc = observe_validate(p, m, b, "kr_trace_observe");
+    if (rc != KR_OK) return rc;
+    if (!emis || !out || n < 0 || (n > 0 && !rays)) return invalid("kr_trace_observe: null argument (emis, out or rays) or negative n");
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    const size_t ncell = (size_t) m->nr * m->ntheta * m->nphi;
+    const size_t words = 2 * (size_t) b->nen + (size_t) b->nen * b->nt + 6;
+    return with_staged_rays(rays, n, sizeof(kr_ray_f64), kUpdates, stats, [&](void* d) -> int {
+        DeviceBuffer d_out, d_image, d_cells[3];
+        const double* h_cells[3] = {emis, kappa, delay};
+        int rc2 = d_out.alloc(words * sizeof(double));
+        if (rc2 != KR_OK) return rc2;
+        KR_HIP(hipMemset(d_out.p, 0, words * sizeof(double)));
+        for (int q = 0; q < 3; ++q) {
+            if (!h_cells[q]) continue;
+            rc2 = d_cells[q].alloc(ncell * sizeof(double));
+            if (rc2 != KR_OK) return rc2;
+            KR_HIP(hipMemcpy(d_cells[q].p, h_cells[q], ncell * sizeof(double), hipMemcpyHostToDevice));
+        }
+        if (image && n > 0) {
+            rc2 = d_image.alloc((size_t) n * sizeof(double));
+            if (rc2 != KR_OK) return rc2;
+        }
+        rc2 = trace_observe_dev(p, m, b, d_cells[0].p, d_cells[1].p, d_cells[2].p, d, n, d_out.p, d_image.p, nullptr, stats);
+        if (rc2 != KR_OK) return rc2;
+        KR_HIP(hipMemcpy(out, d_out.p, words * sizeof(double), hipMemcpyDeviceToHost));
+        if (d_image.p) KR_HIP(hipMemcpy(image, d_image.p, (size_t) n * sizeof(double), hipMemcpyDeviceToHost));
+        return (int) KR_OK;
+    });
+}
+
 // ---- O(N) passes -------------------------------------------------------------------------------------------
 // One line per pass: its scalar arguments, and the field(s) of a kr_ray_f64 it writes.  Each becomes four entry points: device and host
 // pointers, for Raytracer<double> and for Raytracer<float> (kr_ray_f32 records, float arithmetic; the scalars are float values carried in

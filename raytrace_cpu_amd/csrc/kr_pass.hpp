@@ -144,5 +144,9 @@ int paths_record_dev(const kr_params* p, const kr_path_spec* w, void* d_rays, in
 // kr_volume.hip: the mapping trace; the validator refuses a bad grid and what paths_validate refuses of the params; the launcher waits for `st`
 int volume_validate(const kr_params* p, const kr_volume_map* m, const char* who);
 int trace_volume_dev(const kr_params* p, const kr_volume_map* m, void* d_rays, int64_t n, void* d_map, hipStream_t st, kr_stats* stats);
+// kr_observe.hip: the observing trace; the validator refuses what volume_validate refuses, then bad bins; the launcher waits for `st`
+int observe_validate(const kr_params* p, const kr_volume_map* m, const kr_observe_bins* b, const char* who);
+int trace_observe_dev(const kr_params* p, const kr_volume_map* m, const kr_observe_bins* b, const void* d_emis, const void* d_kappa, const void* d_delay, void* d_rays,
+                      int64_t n, void* d_out, void* d_image, hipStream_t st, kr_stats* stats);
 
 }  // namespace kr

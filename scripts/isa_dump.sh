@@ -8,7 +8,7 @@ OUT=${1:-/tmp/isa}
 CSRC="$(dirname "$0")/../raytrace_cpu_amd/csrc"
 LLVM=/opt/rocm/lib/llvm/bin
 mkdir -p "$OUT"
-for f in kr_trace kr_post kr_capi kr_line kr_caustic kr_paths kr_return_map kr_volume; do
+for f in kr_trace kr_post kr_capi kr_line kr_caustic kr_paths kr_return_map kr_volume kr_observe; do
     [ -f "$CSRC/$f.o" ] || continue          # (an object a build of an older commit does not have)
     objcopy -O binary --only-section=.hip_fatbin "$CSRC/$f.o" "$OUT/$f.fat"
     $LLVM/clang-offload-bundler --type=o --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --input="$OUT/$f.fat" --output="$OUT/$f.hsaco" --unbundle
