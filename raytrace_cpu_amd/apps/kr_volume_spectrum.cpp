@@ -30,6 +30,7 @@ using namespace std;
 #include "../host/include/par_args.h"
 #include "../host/include/par_file.h"
 #include "app_common.h"
+#include "volume_app.h"
 
 int main(int argc, char** argv)
 try {
@@ -42,22 +43,14 @@ try {
     const double spin = args.key_exists("--spin") ? args.get_parameter<double>("--spin") : par.get_parameter<double>("spin");
     const bool timing = args.key_exists("--timing");
     // the source grid
-    double source[4];
-    par.get_parameter_array("source", source, 4);
-    if (args.key_exists("--source_h")) source[1] = args.get_parameter<double>("--source_h");
+    const double V = par.get_parameter<double>("V", 0);
+    kr_pointsource src0 = krapp::read_point_source(par, spin, V);
+    if (args.key_exists("--source_h")) src0.pos[1] = args.get_parameter<double>("--source_h");
+    const double* source = src0.pos;
     const double source_h_max = par.get_parameter<double>("source_h_max", source[1]);
     const int Nsource = par.get_parameter<int>("Nsource", 1);
-    const double V = par.get_parameter<double>("V", 0);
-    const double r0 = par.get_parameter<double>("r0");
-    const double rmax = par.get_parameter<double>("rmax");
-    const int Nr = par.get_parameter<int>("Nr");
-    const int Ntheta = par.get_parameter<int>("Ntheta");
-    const int Nphi = par.get_parameter<int>("Nphi", 1);
-    const bool logbin_r = par.get_parameter<bool>("logbin_r", false);
-    const double theta_max = par.get_parameter<double>("theta_max", M_PI_2);
-    const double r_esc = par.get_parameter<double>("r_esc", 1000);
-    const int mode = par.get_parameter<int>("mode", 0);
-    const string integ = args.key_exists("--integrator") ? args.get_parameter<string>("--integrator") : par.get_parameter<string>("integrator", "rk4");
+    const krapp::VolumeGridPar grid(args, par);
+    const int Nr = grid.Nr, Ntheta = grid.Ntheta, Nphi = grid.Nphi;
     // the plane
     const double dist = par.get_parameter<double>("dist");
     const double incl = par.get_parameter<double>("incl");
@@ -78,19 +71,10 @@ try {
     const int Nt = par.get_parameter<int>("Nt", 0);
     const double gamma = par.get_parameter<double>("gamma", 2);
     const double kappa = par.get_parameter<double>("kappa", 0);
-    if (Nr < 1 || Ntheta < 1 || Nphi < 1) throw runtime_error("Nr, Ntheta and Nphi must be at least 1");
     if (Nx < 2 || Ny < 2) throw runtime_error("Nx and Ny must be at least 2");
     if (Nen < 1 || Nt < 0 || Nsource < 1) throw runtime_error("Nen and Nsource must be at least 1, Nt must not be negative");
 
-    // Mapper's constructor, mapper.cpp:14-16 (as kr_volume_map)
-    kr_volume_map m;
-    memset(&m, 0, sizeof m);
-    m.r_min = r0;
-    m.dr = logbin_r ? exp(log(rmax / r0) / max(Nr - 1, 1)) : (rmax - r0) / max(Nr - 1, 1);
-    m.dtheta = (M_PI_2) / max(Ntheta - 1, 1);
-    m.dphi = (2 * M_PI) / max(Nphi - 1, 1);
-    m.V = -1; m.projradius = 1; m.reverse = 0; m.motion = 0;
-    m.nr = Nr; m.ntheta = Ntheta; m.nphi = Nphi; m.logbin = logbin_r ? 1 : 0; m.mode = mode;
+    const kr_volume_map m = grid.map();
 
     kr_observe_bins b;
     memset(&b, 0, sizeof b);
@@ -98,13 +82,7 @@ try {
     b.t0 = t0; b.dt = Nt > 0 ? (tmax - t0) / Nt : 0;
     b.nen = Nen; b.nt = Nt; b.logbin_en = logbin_en ? 1 : 0;
 
-    kr_params p_source;
-    kr_params_default(&p_source, spin);
-    p_source.integrator = krapp::integrator_code(integ, KR_RK4);
-    p_source.theta_max = theta_max;
-    p_source.r_max = r_esc;
-    p_source.stop_kind = KR_STOP_THETA;
-    p_source.flags = 0;                  // both traces ride the strict recording loop
+    const kr_params p_source = grid.params(spin);      // both traces ride the strict recording loop
     kr_params p_plane;
     kr_params_default(&p_plane, -1 * spin);      // as stored by the Raytracer of an ImagePlane (imageplane.cpp:12)
     p_plane.integrator = p_source.integrator;
@@ -128,17 +106,8 @@ try {
     int64_t num_rays = 0;
     double ms_map = 0;
     for (int is = 0; is < Nsource; ++is) {
-        kr_pointsource src;
-        memset(&src, 0, sizeof src);
-        for (int i = 0; i < 4; ++i) src.pos[i] = source[i];
+        kr_pointsource src = src0;
         if (Nsource > 1) src.pos[1] = source[1] + is * (source_h_max - source[1]) / (Nsource - 1);
-        src.V = V; src.spin = spin; src.tol = 100; src.E = 1;
-        src.cosalpha0 = par.get_parameter<double>("cosalpha0", -0.995);
-        src.cosalphamax = par.get_parameter<double>("cosalphamax", 0.995);
-        src.dcosalpha = par.get_parameter<double>("dcosalpha");
-        src.beta0 = par.get_parameter<double>("beta0", -1 * M_PI);
-        src.betamax = par.get_parameter<double>("betamax", M_PI);
-        src.dbeta = par.get_parameter<double>("dbeta");
         const int64_t n = kr_pointsource_count(&src, nullptr, nullptr);
         if (n <= 0) throw runtime_error("empty source ray grid");
         krapp::DeviceBuffer rays(n * (int64_t) sizeof(kr_ray_f64));
@@ -155,17 +124,8 @@ try {
     // 2. emissivity and delay per cell: count / (num_rays volume) mean_g^-gamma and mean_time (source_tracer.cpp:257-258; calculate_volume, mapper.cpp:311-338)
     vector<double> emis(static_cast<size_t>(ncell), 0.0), delay(static_cast<size_t>(ncell), 0.0), kap(static_cast<size_t>(ncell), kappa);
     for (int ir = 0; ir < Nr; ++ir) {
-        const double a = spin;
-        const double r = logbin_r ? r0 * pow(m.dr, ir) : r0 + m.dr * ir;
-        const double this_bin_dr = logbin_r ? r * (m.dr - 1) : m.dr;
         for (int itheta = 0; itheta < Ntheta; ++itheta) {
-            const double theta = itheta * m.dtheta;
-            const double rhosq = r * r + (a * cos(theta)) * (a * cos(theta));
-            const double delta = r * r - 2 * r + a * a;
-            const double sigmasq = (r * r + a * a) * (r * r + a * a) - a * a * delta * sin(theta) * sin(theta);
-            const double e2psi = sigmasq * sin(theta) * sin(theta) / rhosq;
-            const double grr = -rhosq / delta, gthth = -rhosq, gphph = -e2psi;
-            const double volume = sqrt(-1 * grr * gthth * gphph) * this_bin_dr * m.dtheta * m.dphi;
+            const double volume = krapp::cell_volume(m, spin, ir, itheta);
             for (int iphi = 0; iphi < Nphi; ++iphi) {
                 const size_t c = ((size_t) ir * Ntheta + itheta) * Nphi + iphi;
                 const double count = h[c];
@@ -213,17 +173,13 @@ try {
     fits.write_keyword("SOURCE_T", "Source polar angle", source[2]);
     fits.write_keyword("SOURCE_P", "Source azimuth", source[3]);
     fits.write_keyword("V", "Source angular velocity", V);
-    fits.write_keyword("R0", "First radial edge (rg)", r0);
-    fits.write_keyword("RMAX", "Lower edge of the last radial cell (rg)", rmax);
-    fits.write_keyword("NR", "Radial cells", Nr);
-    fits.write_keyword("DR", "Cell width (rg), or ratio between edges with LOGBIN_R", m.dr);
-    fits.write_keyword("LOGBIN_R", "1 = logarithmic radial cells", logbin_r ? 1 : 0);
-    fits.write_keyword("THETAMAX", "Polar angle at which the source trace stops", theta_max);
+    krapp::write_grid_keywords(fits, grid, m);
+    fits.write_keyword("THETAMAX", "Polar angle at which the source trace stops", grid.theta_max);
     fits.write_keyword("NTHETA", "Polar cells, from theta = 0", Ntheta);
     fits.write_keyword("NPHI", "Azimuthal cells, from phi = -pi", Nphi);
-    fits.write_keyword("R_ESC", "Radius at which the source trace stops (rg)", r_esc);
-    fits.write_keyword("MODE", "0 = one deposit per passage of a cell, 1 = per step", mode);
-    fits.write_keyword("INTEGRAT", "Integrator of both traces", integ);
+    fits.write_keyword("R_ESC", "Radius at which the source trace stops (rg)", grid.r_esc);
+    fits.write_keyword("MODE", "0 = one deposit per passage of a cell, 1 = per step", grid.mode);
+    fits.write_keyword("INTEGRAT", "Integrator of both traces", grid.integ);
     fits.write_keyword("DIST", "Distance of the image plane (rg)", dist);
     fits.write_keyword("INCL", "Inclination of the image plane (degrees)", incl);
     fits.write_keyword("PHI0", "Azimuth of the image plane", plane_phi0);

@@ -60,6 +60,23 @@ int DeviceBuffer::alloc(size_t bytes)
     return KR_OK;
 }
 
+int DeviceBuffer::alloc_zeroed(size_t bytes)
+{
+    const int rc = alloc(bytes);
+    if (rc != KR_OK) return rc;
+    KR_HIP(hipMemset(p, 0, bytes));
+    return KR_OK;
+}
+
+int DeviceBuffer::upload(const void* host, size_t bytes)
+{
+    if (!host) return KR_OK;
+    const int rc = alloc(bytes);
+    if (rc != KR_OK) return rc;
+    KR_HIP(hipMemcpy(p, host, bytes, hipMemcpyHostToDevice));
+    return KR_OK;
+}
+
 // ---- the device table store (kr_common.hpp, TablePins) --------------------------------------------------------------------------------
 struct DeviceTable { double* d; int pins; };
 
@@ -275,9 +292,8 @@ int reduce_to_host(const kr_ray_f64* rays, int64_t n, size_t words, double* h, R
 {
     return with_staged_rays((void*) rays, n, sizeof(kr_ray_f64), kReads, nullptr, [&](void* d) {
         DeviceBuffer acc;
-        int rc = acc.alloc(words * sizeof(double));
+        int rc = acc.alloc_zeroed(words * sizeof(double));
         if (rc != KR_OK) return rc;
-        KR_HIP(hipMemset(acc.p, 0, words * sizeof(double)));
         rc = reduce(d, acc.p);
         if (rc != KR_OK) return rc;
         KR_HIP(hipMemcpy(h, acc.p, words * sizeof(double), hipMemcpyDeviceToHost));
@@ -600,9 +616,8 @@ int kr_trace_volume_f64(const kr_params* p, const kr_volume_map* m, kr_ray_f64* 
     const size_t words = 3 * (size_t) m->nr * m->ntheta * m->nphi + 4;
     return with_staged_rays(rays, n, sizeof(kr_ray_f64), kUpdates, stats, [&](void* d) -> int {
         DeviceBuffer d_map;
-        int rc2 = d_map.alloc(words * sizeof(double));
+        int rc2 = d_map.alloc_zeroed(words * sizeof(double));
         if (rc2 != KR_OK) return rc2;
-        KR_HIP(hipMemset(d_map.p, 0, words * sizeof(double)));
         rc2 = trace_volume_dev(p, m, d, n, d_map.p, nullptr, stats);
         if (rc2 != KR_OK) return rc2;
         KR_HIP(hipMemcpy(map, d_map.p, words * sizeof(double), hipMemcpyDeviceToHost));
@@ -632,19 +647,10 @@ int kr_trace_observe_f64(const kr_params* p, const kr_volume_map* m, const kr_ob
     return with_staged_rays(rays, n, sizeof(kr_ray_f64), kUpdates, stats, [&](void* d) -> int {
         DeviceBuffer d_out, d_image, d_cells[3];
         const double* h_cells[3] = {emis, kappa, delay};
-        int rc2 = d_out.alloc(words * sizeof(double));
+        int rc2 = d_out.alloc_zeroed(words * sizeof(double));
+        for (int q = 0; q < 3 && rc2 == KR_OK; ++q) rc2 = d_cells[q].upload(h_cells[q], ncell * sizeof(double));
+        if (rc2 == KR_OK && image && n > 0) rc2 = d_image.alloc((size_t) n * sizeof(double));
         if (rc2 != KR_OK) return rc2;
-        KR_HIP(hipMemset(d_out.p, 0, words * sizeof(double)));
-        for (int q = 0; q < 3; ++q) {
-            if (!h_cells[q]) continue;
-            rc2 = d_cells[q].alloc(ncell * sizeof(double));
-            if (rc2 != KR_OK) return rc2;
-            KR_HIP(hipMemcpy(d_cells[q].p, h_cells[q], ncell * sizeof(double), hipMemcpyHostToDevice));
-        }
-        if (image && n > 0) {
-            rc2 = d_image.alloc((size_t) n * sizeof(double));
-            if (rc2 != KR_OK) return rc2;
-        }
         rc2 = trace_observe_dev(p, m, b, d_cells[0].p, d_cells[1].p, d_cells[2].p, d, n, d_out.p, d_image.p, nullptr, stats);
         if (rc2 != KR_OK) return rc2;
         KR_HIP(hipMemcpy(out, d_out.p, words * sizeof(double), hipMemcpyDeviceToHost));
@@ -936,9 +942,7 @@ int kr_debug_arith_f64(int op, const double* a, const double* b, double* out, in
     if (n == 0) return KR_OK;
     DeviceBuffer da, db, dout;
     const size_t bytes = (size_t) n * sizeof(double);
-    if ((rc = da.alloc(bytes)) != KR_OK || (rc = db.alloc(bytes)) != KR_OK || (rc = dout.alloc(bytes)) != KR_OK) return rc;
-    KR_HIP(hipMemcpy(da.p, a, bytes, hipMemcpyHostToDevice));
-    KR_HIP(hipMemcpy(db.p, b, bytes, hipMemcpyHostToDevice));
+    if ((rc = da.upload(a, bytes)) != KR_OK || (rc = db.upload(b, bytes)) != KR_OK || (rc = dout.alloc(bytes)) != KR_OK) return rc;
     rc = arith_probe_dev(op, (const double*) da.p, (const double*) db.p, (double*) dout.p, n);
     if (rc != KR_OK) return rc;
     KR_HIP(hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost));

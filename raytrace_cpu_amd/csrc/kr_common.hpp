@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cmath>
 #include <functional>
 #include <string>
 #include <vector>
@@ -15,6 +16,9 @@ namespace kr {
 void set_error(const std::string& msg);
 int hip_fail(hipError_t e, const char* what, const char* file, int line);
 int require_device();   // KR_OK or KR_ENODEVICE (message set)
+// a refused argument: the message "<who>: <what>", KR_EINVAL
+inline int invalid_arg(const char* who, const char* what) { set_error(std::string(who) + ": " + what); return KR_EINVAL; }
+inline bool positive_finite(double x) { return x > 0 && std::isfinite(x); }
 
 #define KR_HIP(call)                                                      \
     do {                                                                  \
@@ -46,6 +50,8 @@ struct DeviceBuffer {
     void* p = nullptr;
     ~DeviceBuffer() { if (p) (void) hipFree(p); }
     int alloc(size_t bytes);
+    int alloc_zeroed(size_t bytes);                  // alloc, then a blocking memset
+    int upload(const void* host, size_t bytes);      // alloc, then a blocking copy of host[0 .. bytes); host == null: nothing, p stays null
 };
 
 // ---- small constant tables that the host builds and the passes read on the device (the PointSource angle tables, the line emissivity tables) ----

@@ -15,18 +15,14 @@
 //           ever stored outside the ray's slab or the buffer.
 // A row is {t, r, theta, phi}: four doubles, 32 aligned bytes, two 16-byte vector stores.  Boyer-Lindquist always: write_cartesian is applied by
 // the host-side writers (host/include/kerr.h cartesian()), with the C library the reference calls.
-//
-// Why an iteration of step_fixed ended is read off the lane afterwards, so the step functions stay as the trace kernels compile them:
-//   theta flip (`continue`, writes nothing)   theta_was_positive went from true to false: only the flip clears it (k1_with_flips);
-//   horizon / destination (`break` before the write)   the status bit the iteration added (the lane's status is parked during the step).
+// Which iterations leave a row (RowGate), the launch and the host's timed run are the recorders' shared ones (kr_recorder.hpp).
 
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
 
-#include "kr_pass.hpp"
-#include "kr_trace_loop.hpp"
+#include "kr_recorder.hpp"
 
 namespace kr {
 
@@ -58,7 +54,7 @@ template <bool RECORD> struct PathRecorder {
     long long slab = 0, cap = 0;      // RECORD: its first row and how many it may write
     int32_t n_rows = 0;               // rows it has written so far (write_started == n_rows > 0)
     int32_t until_write = 0;          // iterations left until steps % write_step == 0
-    bool flip_armed = false; int32_t status_before = 0;       // before_step -> after_step
+    RowGate gate;
     uint32_t mismatch = 0;            // this lane's rays whose row count differed from their slab (32 bits: one register less across the step)
 
     KR_DEV void at_slot(long long slot, bool take)
@@ -74,16 +70,13 @@ template <bool RECORD> struct PathRecorder {
         until_write = w.write_step;
         if constexpr (RECORD) { slab = offsets[slot]; cap = offsets[slot + 1] - slab; }
     }
-    KR_DEV void before_step(Lane<double>& s) { flip_armed = s.theta_was_positive; status_before = s.status; s.status = 0; }
+    KR_DEV void before_step(Lane<double>& s) { gate.before_step(s); }
     template <bool USE_DEST> KR_DEV bool after_step(Lane<double>& s, bool fin)
     {
-        const int32_t added = s.status;
-        s.status = status_before | added;
         const bool due = (--until_write == 0);            // steps % write_step == 0: every iteration increments steps once
         if (due) until_write = w.write_step;
-        const bool flipped = flip_armed && !s.theta_was_positive;                               // `continue`
-        const bool broke = (added & (KR_STATUS_HORIZON | (USE_DEST ? KR_STATUS_DEST : 0))) != 0;  // `break` before the write
-        if (due && !flipped && !broke) {
+        const bool row = gate.template row<USE_DEST>(s);
+        if (due && row) {
             if (in_window(w, s.r)) {
                 if constexpr (RECORD) {
                     const long long at = slab + n_rows;
@@ -107,8 +100,8 @@ template <bool RECORD> struct PathRecorder {
     }
     KR_DEV void at_exit(int lane, unsigned long long* __restrict__ counters)
     {
-        const unsigned long long w_mismatch = wave_sum((unsigned long long) mismatch);
-        if (lane == 0 && w_mismatch) atomicAdd(&counters[kRecorderWord], w_mismatch);
+        const unsigned long long tally[1] = {mismatch};
+        flush_tallies(tally, lane, counters);
     }
 };
 
@@ -152,53 +145,30 @@ __global__ void __launch_bounds__(kScanBlock) scan_counts_kernel(long long* __re
     if (t == kScanBlock - 1) v[n] = part[t];
 }
 
-template <bool RK4, bool USE_DEST, bool RECORD>
-int launch_paths(kr_ray_f64* rays, long long n, const TraceConsts<double>& c, const PathWindow& w, long long* offsets, unsigned char* traced, double* rows,
-                 long long total_rows, unsigned long long* counters, hipStream_t stream)
-{
-    auto kern = paths_kernel<RK4, USE_DEST, RECORD>;
-    int dev = 0, cus = 0, per_cu = 0;
-    KR_HIP(hipGetDevice(&dev));
-    const int rc = device_cus(dev, &cus);
-    if (rc != KR_OK) return rc;
-    KR_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kTraceBlock, 0));
-    // resident waves per SIMD as the strict trace sizes its launches (kr_trace.hip::launch): 2 for RK4 -- the pass ends with its longest ray,
-    // which advances one step per turn of its wave -- 4 for the short Euler step
-    per_cu = std::max(1, std::min(per_cu, 4 * (RK4 ? 2 : 4)));
-    hipLaunchKernelGGL(kern, dim3(persistent_grid(cus, per_cu, n)), dim3(kTraceBlock), 0, stream, rays, n, c, w, offsets, traced, rows, total_rows, counters);
-    KR_LAUNCH_CHECK();
-    return KR_OK;
-}
-
 template <bool RECORD>
-int launch_paths_for(const kr_params* p, kr_ray_f64* rays, long long n, const PathWindow& w, long long* offsets, unsigned char* traced, double* rows,
-                     long long total_rows, unsigned long long* counters, hipStream_t stream)
+int launch_paths(const kr_params* p, kr_ray_f64* rays, long long n, const PathWindow& w, long long* offsets, unsigned char* traced, double* rows, long long total_rows,
+                 unsigned long long* counters, hipStream_t stream)
 {
     const TraceConsts<double> c = make_consts<double>(p, effective_steplim(p));
-    if (p->integrator == KR_EULER) return launch_paths<false, false, RECORD>(rays, n, c, w, offsets, traced, rows, total_rows, counters, stream);
-    if (p->stop_kind == KR_STOP_THETA) return launch_paths<true, false, RECORD>(rays, n, c, w, offsets, traced, rows, total_rows, counters, stream);
-    return launch_paths<true, true, RECORD>(rays, n, c, w, offsets, traced, rows, total_rows, counters, stream);
+    return dispatch_instance(p, [&](auto rk4, auto dest) {
+        constexpr bool RK4 = decltype(rk4)::value, USE_DEST = decltype(dest)::value;
+        return launch_recorder(paths_kernel<RK4, USE_DEST, RECORD>, RK4, n, stream, rays, n, c, w, offsets, traced, rows, total_rows, counters);
+    });
 }
 
 PathWindow window_of(const kr_path_spec* w) { return PathWindow{w->write_rmin, w->write_rmax, w->write_step}; }
-
-int fail(const char* who, const char* what)
-{
-    set_error(std::string(who) + ": " + what);
-    return KR_EINVAL;
-}
 
 }  // namespace
 
 // everything that can be refused without a device (include/kr_trace.h lists it)
 int paths_validate(const kr_params* p, const kr_path_spec* w, const char* who)
 {
-    if (!p || !w) return fail(who, "null argument");
-    if (w->write_step <= 0) return fail(who, "write_step must be positive (the reference takes steps % write_step)");
-    if (std::isnan(w->write_rmin) || std::isnan(w->write_rmax)) return fail(who, "write_rmin / write_rmax must not be NaN");
+    if (!p || !w) return invalid_arg(who, "null argument");
+    if (w->write_step <= 0) return invalid_arg(who, "write_step must be positive (the reference takes steps % write_step)");
+    if (std::isnan(w->write_rmin) || std::isnan(w->write_rmax)) return invalid_arg(who, "write_rmin / write_rmax must not be NaN");
     if (p->flags & (KR_FLAG_FAST_MATH | KR_FLAG_HYBRID))
-        return fail(who, "paths carry the reference's arithmetic: KR_FLAG_FAST_MATH / KR_FLAG_HYBRID are not accepted");
-    if (p->integrator == KR_RK45) return fail(who, "RK45 paths are not recorded (Euler and RK4 only)");
+        return invalid_arg(who, "paths carry the reference's arithmetic: KR_FLAG_FAST_MATH / KR_FLAG_HYBRID are not accepted");
+    if (p->integrator == KR_RK45) return invalid_arg(who, "RK45 paths are not recorded (Euler and RK4 only)");
     return validate_run(p, who);      // (the checks the trace makes, under this call's name)
 }
 
@@ -210,8 +180,8 @@ int paths_count_dev(const kr_params* p, const kr_path_spec* w, const void* d_ray
     KR_HIP(hipMemsetAsync(counters.p, 0, kPathWords * sizeof(unsigned long long), st));
     if (n > 0) {
         // (the count pass only reads the records: the kernel's RECORD = false instance has no store to rays[])
-        rc = launch_paths_for<false>(p, const_cast<kr_ray_f64*>((const kr_ray_f64*) d_rays), (long long) n, window_of(w), (long long*) d_offsets,
-                                     (unsigned char*) d_traced, nullptr, 0, (unsigned long long*) counters.p, st);
+        rc = launch_paths<false>(p, const_cast<kr_ray_f64*>((const kr_ray_f64*) d_rays), (long long) n, window_of(w), (long long*) d_offsets,
+                                 (unsigned char*) d_traced, nullptr, 0, (unsigned long long*) counters.p, st);
         if (rc != KR_OK) return rc;
     }
     hipLaunchKernelGGL(scan_counts_kernel, dim3(1), dim3(kScanBlock), 0, st, (long long*) d_offsets, (long long) n);
@@ -230,43 +200,20 @@ int paths_record_dev(const kr_params* p, const kr_path_spec* w, void* d_rays, in
     long long need = 0;
     KR_HIP(hipMemcpyAsync(&need, (const long long*) d_offsets + n, sizeof need, hipMemcpyDeviceToHost, st));
     KR_HIP(hipStreamSynchronize(st));
-    if (need < 0 || (long long) total_rows < need) return fail("kr_trace_paths_record", "total_rows is smaller than offsets[n]");
+    if (need < 0 || (long long) total_rows < need) return invalid_arg("kr_trace_paths_record", "total_rows is smaller than offsets[n]");
     if (n == 0) return KR_OK;
-    DeviceBuffer counters;
-    int rc = counters.alloc(kPathWords * sizeof(unsigned long long));
+    unsigned long long h[kPathWords];
+    const int rc = run_recorder(st, kPathWords, stats, [&](unsigned long long* counters) {
+        return launch_paths<true>(p, (kr_ray_f64*) d_rays, (long long) n, window_of(w), const_cast<long long*>((const long long*) d_offsets), nullptr, (double*) d_rows,
+                                  (long long) total_rows, counters, st);
+    }, h);
     if (rc != KR_OK) return rc;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    KR_HIP(hipEventCreate(&ev0));
-    if (hipEventCreate(&ev1) != hipSuccess) { (void) hipEventDestroy(ev0); return hip_fail(hipGetLastError(), "hipEventCreate", __FILE__, __LINE__); }
-    auto body = [&]() -> int {
-        KR_HIP(hipMemsetAsync(counters.p, 0, kPathWords * sizeof(unsigned long long), st));
-        KR_HIP(hipEventRecord(ev0, st));
-        const int rc2 = launch_paths_for<true>(p, (kr_ray_f64*) d_rays, (long long) n, window_of(w), const_cast<long long*>((const long long*) d_offsets), nullptr,
-                                               (double*) d_rows, (long long) total_rows, (unsigned long long*) counters.p, st);
-        if (rc2 != KR_OK) return rc2;
-        KR_HIP(hipEventRecord(ev1, st));
-        unsigned long long h[kPathWords];
-        KR_HIP(hipMemcpyAsync(h, counters.p, sizeof h, hipMemcpyDeviceToHost, st));
-        KR_HIP(hipStreamSynchronize(st));
-        if (stats) {
-            float ms = 0;
-            KR_HIP(hipEventElapsedTime(&ms, ev0, ev1));
-            stats->kernel_ms = ms;
-            stats->rays_traced = (int64_t) h[kTraced];
-            stats->steps_total = (int64_t) h[kSteps];
-            stats->longest_ray_steps = (int64_t) h[kLongest];
-        }
-        if (h[kRecorderWord] != 0) {
-            set_error("kr_trace_paths_record: " + std::to_string(h[kRecorderWord]) + " rays wrote a different number of rows than the count pass gave them "
-                      "(offsets from another call, other parameters, or rays[] modified in between?)");
-            return KR_EINVAL;
-        }
-        return KR_OK;
-    };
-    rc = body();
-    (void) hipEventDestroy(ev0);
-    (void) hipEventDestroy(ev1);
-    return rc;
+    if (h[kRecorderWord] != 0) {
+        set_error("kr_trace_paths_record: " + std::to_string(h[kRecorderWord]) + " rays wrote a different number of rows than the count pass gave them "
+                  "(offsets from another call, other parameters, or rays[] modified in between?)");
+        return KR_EINVAL;
+    }
+    return KR_OK;
 }
 
 }  // namespace kr

@@ -1,5 +1,6 @@
 // kr_trace_loop.hpp -- the persistent-wave ray loop (trace_body), once: the body of every trace kernel of kr_trace.hip and of the recording
-// kernel of kr_paths.hip, with its constants, counter words and wave reductions.  Free lanes, queue visits, the wave-aggregated claim, the skip
+// kernels of kr_paths.hip, kr_volume.hip and kr_observe.hip, with its constants, counter words and wave reductions.
+// Free lanes, queue visits, the wave-aggregated claim, the skip
 // rule, the per-ray reset, the zero-iteration case and the one store of a ray exist here and nowhere else, so "a recorded ray takes the very
 // steps of a flags = 0 trace" holds by construction.
 // A recorder (trace_body's last template parameter; NoRecorder below lists the hooks) is called at fixed points and nowhere else, every call
@@ -46,7 +47,7 @@ enum CounterWord { kHead, kTraced, kSteps, kAttempts, kRejects, kStationary, kEx
                    // run on past what their lists hold), and whether either list overflowed
                    kFlagged = kTraced, kRadial = kSteps, kListsOverflowed = kAttempts };
 constexpr int kCounters = KR_OCC_STATS ? 13 : kCounterWords;         // words per block; KR_OCC_STATS builds: [8..12] occupancy sums
-constexpr int kRecorderWord = kCounters;                             // a launch with a recorder: one more word, the recorder's own (at_exit)
+constexpr int kRecorderWord = kCounters;                             // a launch with a recorder: the recorder's words from kRecorderWord on (at_exit)
 
 template <typename T> struct RayOf;
 template <> struct RayOf<double> { using type = kr_ray_f64; };
@@ -71,11 +72,12 @@ inline int persistent_grid(int cus, int blocks_per_cu, long long n)
     return (int) std::max<long long>(1, std::min<long long>((long long) cus * blocks_per_cu, (n + kTraceBlock - 1) / kTraceBlock));
 }
 
-// The recorder of a launch that records nothing.  What a recorder type provides (kr_paths.hip: PathRecorder):
+// The recorder of a launch that records nothing.  What a recorder type provides (PathRecorder, kr_paths.hip; VolumeRecorder, kr_volume.hip;
+// ObserveRecorder, kr_observe.hip; what the three share: kr_recorder.hpp):
 //   kActive: the hooks below exist and are called;   kStoresRays: a ray's final record is stored to rays[] where it leaves its lane
 //   at_slot(slot, take)     a lane has loaded the record of `slot`; take: it passed the skip rule          claim(slot)     the lane takes that ray
 //   before_step(s), after_step<USE_DEST>(s, fin) -> fin     either side of the lane's step_fixed call     leave(idx)      ray idx leaves its lane
-//   at_exit(lane, counters)     the wave has left the loop: per-lane tallies -> counters[kRecorderWord]
+//   at_exit(lane, counters)     the wave has left the loop: per-lane tallies -> counters[kRecorderWord ..]
 //   kWaveHook: wave_step_end() is called by ALL 64 lanes after every step of the wave (whole-wave reductions are valid there, not in after_step)
 struct NoRecorder { static constexpr bool kActive = false, kStoresRays = true; };
 

@@ -8,8 +8,9 @@ OUT=${1:-/tmp/isa}
 CSRC="$(dirname "$0")/../raytrace_cpu_amd/csrc"
 LLVM=/opt/rocm/lib/llvm/bin
 mkdir -p "$OUT"
-for f in kr_trace kr_post kr_capi kr_line kr_caustic kr_paths kr_return_map kr_volume kr_observe; do
-    [ -f "$CSRC/$f.o" ] || continue          # (an object a build of an older commit does not have)
+for o in "$CSRC"/kr_*.o; do                  # (every object the build left there: _build.py has the list of sources)
+    [ -f "$o" ] || continue
+    f=$(basename "$o" .o)
     objcopy -O binary --only-section=.hip_fatbin "$CSRC/$f.o" "$OUT/$f.fat"
     $LLVM/clang-offload-bundler --type=o --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --input="$OUT/$f.fat" --output="$OUT/$f.hsaco" --unbundle
     $LLVM/llvm-objdump -d --no-show-raw-insn --no-leading-addr "$OUT/$f.hsaco" | sed -E 's/[[:space:]]*\/\/ [0-9A-Fa-f]+:.*$//' > "$OUT/$f.s"

@@ -30,7 +30,7 @@ def proper_length(spin, r, theta, dr, dth, dph):
 def measure(m, spin, offsets, rows, start, z_of, emis, kappa=None, delay=None):
     """Steps 1-5 of the rule for every row.  offsets, rows: a write_step = 1 recording; start[ray] = (r, theta, phi) of the ray's initial record;
     z_of(mask) -> z of the rows in the boolean mask; emis / kappa / delay: one value per cell (kappa, delay may be None).
-    Returns a dict: the six tallies, "image" (per ray), and for the CONTRIBUTING rows (in row order) "ray", "w", "E", "T", "cell", "len", "tau";
+    Returns a dict: the six tallies, "image" (per ray), and for the CONTRIBUTING rows (in row order) "row" (their indices), "ray", "w", "E", "T", "cell", "len", "tau";
     "t_in_grid": t of every row in the grid."""
     offsets = np.asarray(offsets, dtype=np.int64)
     rows = np.asarray(rows, dtype=np.float64).reshape(-1, 4)
@@ -74,7 +74,7 @@ def measure(m, spin, offsets, rows, start, z_of, emis, kappa=None, delay=None):
         w = w * np.exp(-tau[good])
     return {"rows": int(n), "in_grid": int(inside.sum()), "lit": int(lit.sum()), "contributions": int(good.sum()), "bad_g": int((emitting & ~good).sum()),
             "degenerate": int(degenerate.sum()), "image": np.bincount(ray[good], weights=w, minlength=n_rays),
-            "ray": ray[good], "w": w, "E": E, "T": rows[good, 0] + dly[good], "cell": cell[good], "len": length[good], "tau": tau[good],
+            "row": np.flatnonzero(good), "ray": ray[good], "w": w, "E": E, "T": rows[good, 0] + dly[good], "cell": cell[good], "len": length[good], "tau": tau[good],
             "t_in_grid": rows[inside, 0]}
 
 
