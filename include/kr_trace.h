@@ -367,6 +367,18 @@ typedef struct kr_observe_bins {
 static_assert(sizeof(kr_observe_bins) == 48, "kr_observe_bins is 48 bytes (raytrace_cpu_amd/capi.py ObserveBins)");
 #endif
 
+/* What a crossing-recording trace takes besides the trace parameters (kr_trace_crossings_* below has the rule).  V, reverse, projradius, motion: the
+ * emitter on the equatorial plane, as kr_redshift_dev_f64 takes them. */
+typedef struct kr_crossing_spec {
+    double  V;                 /* observer on the plane, as kr_redshift_dev_f64 takes it; -1: Keplerian at r_c */
+    int32_t max_crossings;     /* M, 1..16: crossings stored per ray */
+    int32_t stop_when_full;    /* 1: the ray ends with the iteration that made its M-th crossing */
+    int32_t reverse, projradius, motion, pad;
+} kr_crossing_spec;
+#ifdef __cplusplus
+static_assert(sizeof(kr_crossing_spec) == 32, "kr_crossing_spec is 32 bytes (raytrace_cpu_amd/capi.py CrossingSpec)");
+#endif
+
 /* ---- runtime ---------------------------------------------------------------------------------- */
 int         kr_abi_version(void);
 const char* kr_last_error(void);
@@ -533,6 +545,50 @@ int kr_trace_observe_dev_f64(const kr_params* p, const kr_volume_map* m, const k
                              void* d_rays, int64_t n, void* d_out /* double[2 nen + nen nt + 6] */, void* d_image /* double[n] or NULL */, void* stream, kr_stats* stats);
 int kr_trace_observe_f64(const kr_params* p, const kr_volume_map* m, const kr_observe_bins* b, const double* emis, const double* kappa, const double* delay,
                          kr_ray_f64* rays, int64_t n, double* out /* 2 nen + nen nt + 6 */, double* image /* n or NULL */, kr_stats* stats);
+
+/* ---- equatorial crossings: where and when a ray meets the plane theta = pi / 2, EVERY time it does, with the energy shift of an emitter on the plane
+ * there.  Crossing number m of a camera ray is the image of order m of an equatorial disc: the direct image (0), the underside seen over the top of
+ * the hole (1), the photon ring (>= 2).  Euler and RK4, double precision, strict arithmetic, on the loop above.
+ * Crossing: an iteration crossed iff it moved the trace's own counter rays[i].equatorial_crossings -- with theta before and after the state update
+ * (before the reflection at the poles), (before < M_PI/2 && after >= M_PI/2) || (before > M_PI/2 && after <= M_PI/2).  A theta-flip iteration moves
+ * nothing and never crosses; an iteration that ends on r <= horizon or on dest->reached() counts like any other (the disc of a KR_STOP_DISC_ISCO trace
+ * is met in exactly such an iteration).
+ * Where: with (t0, r0, theta0, phi0) the ray's state before the iteration and (t1, r1, theta1, phi1) after it (after the reflection at the poles),
+ *     f   = (M_PI/2 - theta0) / (theta1 - theta0)
+ *     r_c = r0 + f (r1 - r0)     phi_c = phi0 + f (phi1 - phi0)     t_c = t0 + f (t1 - t0)
+ * each a single IEEE operation in this association, no contraction.
+ * g = ray_redshift(V, reverse, projradius, r_c, M_PI/2, ., k, h, Q, rdot_sign, thetadot_sign, emit, motion) (raytracer.cpp:480-553, as kr_redshift_dev_f64
+ * does) with the ray's k, h, Q, the signs the ray has after that iteration and emit from the ray's record.
+ * Storing: every ray counts its crossings in this call, `seen`, from 0.  A crossing made with seen < M = max_crossings is stored as
+ * d_rows[(i M + seen) 4 ..] = {r_c, phi_c, t_c, g}; g is stored as computed (NaN and g <= 0 included: consumers filter).  Then ++seen, always.  Rows
+ * m >= min(seen, M) of a ray are NOT written (fill d_rows beforehand to tell them apart); nothing is ever stored outside a ray's slab of M rows.
+ * d_seen[i] = seen, 0 for a ray the skip rule (steps < 0 || steps >= steplim) passed over: for every traced ray the increase of
+ * rays[i].equatorial_crossings in this call (with stop_when_full, at most M).
+ * stop_when_full: the iteration that makes a ray's M-th crossing is its last: the ray ends with that iteration's state and its record is what the
+ * epilogue makes of it (the mechanism of a path recording that leaves its window): no status bit of its own -- whatever ERGO / NEG_ENERGY flags its steps
+ * raised, HORIZON or DEST if that iteration ended on one anyway, STEPLIM / RLIM / DEST only if that state meets the epilogue's tests; a ray cut short in
+ * mid-flight has status 0 and steps > 0.  It removes the rays that whirl at the photon sphere for 1e6 steps and more, each half orbit a crossing.
+ * Every ray the recorder did not end -- every ray, without stop_when_full -- finishes with the record of kr_trace_dev_f64 with flags = 0, bit for bit.
+ * kr_trace_crossings_dev_f64 fills *stats (may be NULL: rays_total, rays_traced, steps_total, longest_ray_steps, kernel_ms) and SYNCHRONISES `stream`
+ * before it returns (the launch's counters come back to the host).  No atomics: a ray's rows and d_seen[i] are written by the lane that holds it.
+ * n == 0 touches nothing.  kr_trace_crossings_f64: host pointers; stages rays[], rows[] and seen[]; rows[] is copied to the device first and back as
+ * it is there afterwards, so rows that were not written keep the caller's values.
+ * Refused with KR_EINVAL before any device work: null pointers, n < 0, max_crossings outside 1..16, an unknown motion, d_rows not 32-byte aligned (a
+ * row is two 16-byte stores), and what kr_trace_paths_* refuses of a kr_params: KR_FLAG_FAST_MATH / KR_FLAG_HYBRID, KR_RK45, Euler with a destination
+ * stop kind.  Without a device: KR_ENODEVICE.
+ * kr_reduce_crossing_image_dev_f64: the image of ONE order, one work-item per ray.  order >= 0 takes crossing `order` of every ray with
+ * order < min(seen, M); order = -1 (the opaque disc) takes a ray's first stored crossing with r_isco <= r_c < r_disc (a NaN fails the test; g plays
+ * no part in the choice).  The chosen crossing is accumulated as kr_reduce_image_dev_f64 accumulates a record with steps = 1, r = r_c, theta = M_PI/2,
+ * phi = range_phi(phi_c; lo, hi), t = t_c, redshift = g and the alpha, beta of d_rays[i]: the same tests (g > 0, the radial range, the pixel) and the same
+ * sums.  It ADDS into d_planes, double[7 img_nx img_ny + 1] in that reducer's layout, so whatever reads a direct image's planes reads an order's
+ * (kr_line_from_image_dev_f64 on them gives the order's line profile); it does not wait for `stream`.  Refused with KR_EINVAL: null pointers (d_rays,
+ * d_rows, d_seen only when n > 0), n < 0, a non-positive image size, max_crossings outside 1..16, order outside [-1, max_crossings). */
+int kr_trace_crossings_dev_f64(const kr_params* p, const kr_crossing_spec* spec, void* d_rays, int64_t n, void* d_rows /* double[n][M][4] */,
+                               void* d_seen /* int32[n] */, void* stream, kr_stats* stats);
+int kr_trace_crossings_f64(const kr_params* p, const kr_crossing_spec* spec, kr_ray_f64* rays, int64_t n, double* rows /* n M 4 */, int32_t* seen /* n */,
+                           kr_stats* stats);
+int kr_reduce_crossing_image_dev_f64(const kr_image_bins* b, int32_t max_crossings, int32_t order, double lo, double hi, const void* d_rays, const void* d_rows,
+                                     const void* d_seen, int64_t n, void* d_planes, void* stream);
 
 /* ---- O(N) passes either side of it ----------------------------------------------------------- */
 /* Raytracer<T>::redshift_start(V, reverse, projradius)  raytracer.cpp:342-417 */

@@ -877,3 +877,95 @@ def volume_spectrum(sources, plane_spec, p_source, p_plane, m, bins, gamma=2.0, 
     res = observe_from_words(bins, words)
     res.update(image=image.reshape(nx, ny), map=vmap, emis=emis, delay=delay, stats=st.as_dict())
     return res
+
+
+def crossing_spec(max_crossings=4, stop_when_full=True, V=-1.0, reverse=0, projradius=0, motion=0):
+    """A kr_crossing_spec: up to max_crossings (1..16) equatorial crossings stored per ray; stop_when_full: a ray ends with the iteration that made its
+    last storable crossing; V, reverse, projradius, motion: the emitter on the plane, as redshift() takes them (V = -1: Keplerian at the crossing)."""
+    s = capi.CrossingSpec()
+    s.V, s.max_crossings, s.stop_when_full = float(V), int(max_crossings), int(bool(stop_when_full))
+    s.reverse, s.projradius, s.motion, s.pad = int(reverse), int(projradius), int(motion), 0
+    return s
+
+
+def trace_crossings(params, rays, spec):
+    """kr_trace_crossings_f64 on a host array of Ray<double> records (Euler / RK4, strict arithmetic): the rays are integrated as trace(flags = 0)
+    integrates them and every meeting with the equatorial plane is recorded (include/kr_trace.h has the rule).  Returns a dict: "rows" shaped
+    (n, M, 4), {r_c, phi_c, t_c, g} per stored crossing and NaN where a ray stored none; "seen" (n,), the crossings each ray made in this call; "rays"
+    (the final records) and "stats"."""
+    _rays_arg(rays, capi.RAY_F64)
+    out = rays.copy()
+    rows = np.full((len(out), int(spec.max_crossings), 4), np.nan)
+    seen = np.zeros(len(out), dtype=np.int32)
+    st = Stats()
+    capi.check(lib(), lib().kr_trace_crossings_f64(C.byref(params), C.byref(spec), _ptr(out), len(out), _ptr(rows), _ptr(seen), C.byref(st)), "kr_trace_crossings")
+    return {"rows": rows, "seen": seen, "rays": out, "stats": st.as_dict()}
+
+
+def _crossing_planes(L, bins, max_crossings, order, lo, hi, d_rays, d_rows, d_seen, n, d_planes):
+    """One order's image planes from device-resident crossings, through the zeroed scratch d_planes: the dict of image_planes_from_words."""
+    nw = 7 * bins.img_nx * bins.img_ny + 1
+    words = np.zeros(nw)
+    capi.check(L, L.kr_memset(d_planes, 0, nw * 8), "kr_memset")
+    capi.check(L, L.kr_reduce_crossing_image_dev_f64(C.byref(bins), int(max_crossings), int(order), lo, hi, d_rays, d_rows, d_seen, n, d_planes, None),
+               "kr_reduce_crossing_image")
+    capi.check(L, L.kr_memcpy_d2h(_ptr(words), d_planes, nw * 8), "kr_memcpy_d2h")
+    return image_planes_from_words(words, bins.img_nx, bins.img_ny)
+
+
+def reduce_crossing_image(bins, rays, rows, seen, order, lo=-np.pi, hi=np.pi):
+    """The image of one order from what trace_crossings returned (kr_reduce_crossing_image_dev_f64): order >= 0 takes every ray's crossing `order`,
+    order = -1 (the opaque disc) its first stored crossing inside [r_isco, r_disc).  Returns the dict of image_planes_from_words (raw sums, as
+    reduce_image gives them)."""
+    _rays_arg(rays, capi.RAY_F64)
+    rows = np.ascontiguousarray(rows, dtype=np.float64)
+    seen = np.ascontiguousarray(seen, dtype=np.int32)
+    n = len(rays)
+    if rows.ndim != 3 or rows.shape[0] != n or rows.shape[2] != 4 or seen.shape != (n,):
+        raise KrError("reduce_crossing_image: rows must be shaped (n, M, 4) and seen (n,)")
+    L = lib()
+    bufs = [C.c_void_p() for _ in range(4)]
+    d_rays, d_rows, d_seen, d_planes = bufs
+    try:
+        for d, a in ((d_rays, rays), (d_rows, rows), (d_seen, seen)):
+            capi.check(L, L.kr_malloc(C.byref(d), max(a.nbytes, 1)), "kr_malloc")
+            capi.check(L, L.kr_memcpy_h2d(d, _ptr(a), a.nbytes), "kr_memcpy_h2d")
+        capi.check(L, L.kr_malloc(C.byref(d_planes), (7 * bins.img_nx * bins.img_ny + 1) * 8), "kr_malloc")
+        return _crossing_planes(L, bins, rows.shape[1], order, lo, hi, d_rays, d_rows, d_seen, n, d_planes)
+    finally:
+        for d in bufs:
+            if d.value:
+                L.kr_free(d)
+
+
+def order_images(imageplane_spec, params, bins, spec, orders, lo=-np.pi, hi=np.pi):
+    """The order-resolved images of an equatorial disc, resident on the device: ImagePlane ctor + redshift_start(0, spec.reverse)
+    (kr_imageplane_init_emit_dev_f64) -> kr_trace_crossings_dev_f64 with `params` (the stored, negated spin of an ImagePlane; theta_max = 0 lets the
+    rays run on through the plane) -> kr_reduce_crossing_image_dev_f64 once per entry of `orders` (-1: the opaque disc).  The rays never leave the
+    device.  Returns {"images": {order: the dict of image_planes_from_words}, "seen_histogram": how many rays made 0, 1, .. crossings,
+    "stats": the trace's}."""
+    L = lib()
+    n, _, _ = imageplane_count(imageplane_spec)
+    if n <= 0:
+        raise KrError("order_images: empty ray grid")
+    M = int(spec.max_crossings)
+    bufs = [C.c_void_p() for _ in range(4)]
+    d_rays, d_rows, d_seen, d_planes = bufs
+    st = Stats()
+    seen = np.zeros(n, dtype=np.int32)
+    images = {}
+    try:
+        capi.check(L, L.kr_malloc(C.byref(d_rays), n * capi.RAY_F64.itemsize), "kr_malloc")
+        capi.check(L, L.kr_malloc(C.byref(d_rows), n * M * 32), "kr_malloc")
+        capi.check(L, L.kr_malloc(C.byref(d_seen), n * 4), "kr_malloc")
+        capi.check(L, L.kr_malloc(C.byref(d_planes), (7 * bins.img_nx * bins.img_ny + 1) * 8), "kr_malloc")
+        capi.check(L, L.kr_imageplane_init_emit_dev_f64(C.byref(imageplane_spec), 0, 1, 0.0, int(spec.reverse), 0, d_rays, n, None), "kr_imageplane_init_emit")
+        capi.check(L, L.kr_trace_crossings_dev_f64(C.byref(params), C.byref(spec), d_rays, n, d_rows, d_seen, None, C.byref(st)), "kr_trace_crossings")
+        for order in orders:
+            images[int(order)] = _crossing_planes(L, bins, M, order, lo, hi, d_rays, d_rows, d_seen, n, d_planes)
+        capi.check(L, L.kr_memcpy_d2h(_ptr(seen), d_seen, seen.nbytes), "kr_memcpy_d2h")
+    finally:
+        for d in bufs:
+            if d.value:
+                L.kr_free(d)
+    return {"images": images, "seen_histogram": np.bincount(seen), "stats": st.as_dict()}

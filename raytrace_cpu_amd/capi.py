@@ -121,6 +121,12 @@ class ObserveBins(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("en0", "den", "t0", "dt")] + [(n, C.c_int32) for n in ("nen", "nt", "logbin_en", "pad")]
 
 
+class CrossingSpec(C.Structure):
+    """kr_crossing_spec: how many equatorial crossings a recording trace stores per ray, whether the last of them ends the ray, and the emitter on the
+    plane (include/kr_trace.h has the rule)."""
+    _fields_ = [("V", C.c_double)] + [(n, C.c_int32) for n in ("max_crossings", "stop_when_full", "reverse", "projradius", "motion", "pad")]
+
+
 def line_bins(line_energy=6.4, e_min=1.0, de=0.1, ne=90, log_e=False, t0=0.0, dt=0.0, nt=1, r_isco=1.0, r_disc=1000.0, q1=3.0, rb1=4.0, q2=3.0,
               rb2=10.0, q3=3.0, g_index=3.0):
     b = LineBins()
@@ -190,6 +196,9 @@ PROTOTYPES = {
     "kr_trace_volume_f64": (_int, [P(Params), P(VolumeMap), _vp, _i64, _vp, P(Stats)]),
     "kr_trace_observe_dev_f64": (_int, [P(Params), P(VolumeMap), P(ObserveBins), _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, P(Stats)]),
     "kr_trace_observe_f64": (_int, [P(Params), P(VolumeMap), P(ObserveBins), _vp, _vp, _vp, _vp, _i64, _vp, _vp, P(Stats)]),
+    "kr_trace_crossings_dev_f64": (_int, [P(Params), P(CrossingSpec), _vp, _i64, _vp, _vp, _vp, P(Stats)]),
+    "kr_trace_crossings_f64": (_int, [P(Params), P(CrossingSpec), _vp, _i64, _vp, _vp, P(Stats)]),
+    "kr_reduce_crossing_image_dev_f64": (_int, [P(ImageBins), _i32, _i32, _dbl, _dbl, _vp, _vp, _vp, _i64, _vp, _vp]),
     "kr_redshift_start_f64": (_int, [_dbl, _dbl, _int, _int, _vp, _i64]),
     "kr_redshift_start_dev_f64": (_int, [_dbl, _dbl, _int, _int, _vp, _i64, _vp]),
     "kr_redshift_f64": (_int, [_dbl, _dbl, _int, _int, _int, _vp, _i64]),

@@ -625,6 +625,48 @@ int kr_trace_volume_f64(const kr_params* p, const kr_volume_map* m, kr_ray_f64* 
     });
 }
 
+// ---- equatorial crossings (kr_crossings.hip) and the image of one order from them (kr_post.hip) ----------------------------------------------------
+int kr_trace_crossings_dev_f64(const kr_params* p, const kr_crossing_spec* sp, void* d_rays, int64_t n, void* d_rows, void* d_seen, void* stream, kr_stats* stats)
+{
+    const int rc = crossings_validate(p, sp, "kr_trace_crossings");
+    if (rc != KR_OK) return rc;
+    if (n < 0 || (n > 0 && !d_rays) || !d_rows || !d_seen) return invalid("kr_trace_crossings: null argument or negative n");
+    if ((uintptr_t) d_rows % 32 != 0) return invalid("kr_trace_crossings: d_rows must be 32-byte aligned");
+    return on_device(true, nullptr, [&] { return trace_crossings_dev(p, sp, d_rays, n, d_rows, d_seen, (hipStream_t) stream, stats); });
+}
+
+int kr_trace_crossings_f64(const kr_params* p, const kr_crossing_spec* sp, kr_ray_f64* rays, int64_t n, double* rows, int32_t* seen, kr_stats* stats)
+{
+    const int rc = crossings_validate(p, sp, "kr_trace_crossings");
+    if (rc != KR_OK) return rc;
+    if (n < 0 || (n > 0 && !rays) || !rows || !seen) return invalid("kr_trace_crossings: null argument or negative n");
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    const size_t row_bytes = (size_t) n * sp->max_crossings * 4 * sizeof(double);
+    return with_staged_rays(rays, n, sizeof(kr_ray_f64), kUpdates, stats, [&](void* d) -> int {
+        DeviceBuffer d_rows, d_seen;          // (hipMalloc: 256-byte aligned)
+        int rc2 = d_rows.upload(rows, row_bytes);
+        if (rc2 == KR_OK) rc2 = d_seen.alloc((size_t) n * sizeof(int32_t));
+        if (rc2 != KR_OK) return rc2;
+        rc2 = trace_crossings_dev(p, sp, d, n, d_rows.p, d_seen.p, nullptr, stats);
+        if (rc2 != KR_OK) return rc2;
+        if (n > 0) {
+            KR_HIP(hipMemcpy(rows, d_rows.p, row_bytes, hipMemcpyDeviceToHost));
+            KR_HIP(hipMemcpy(seen, d_seen.p, (size_t) n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        }
+        return (int) KR_OK;
+    });
+}
+
+int kr_reduce_crossing_image_dev_f64(const kr_image_bins* b, int32_t max_crossings, int32_t order, double lo, double hi, const void* d_rays, const void* d_rows,
+                                     const void* d_seen, int64_t n, void* d_planes, void* stream)
+{
+    if (!b || !d_planes || n < 0 || (n > 0 && (!d_rays || !d_rows || !d_seen))) return invalid("kr_reduce_crossing_image: null argument or negative n");
+    if (b->img_nx <= 0 || b->img_ny <= 0) return invalid("kr_reduce_crossing_image: image size must be positive");
+    if (max_crossings < 1 || max_crossings > 16) return invalid("kr_reduce_crossing_image: max_crossings must be 1..16");
+    if (order < -1 || order >= max_crossings) return invalid("kr_reduce_crossing_image: order must be -1 (the opaque disc) or 0 .. max_crossings - 1");
+    return on_device(true, nullptr, [&] { return reduce_crossing_image_dev(b, max_crossings, order, lo, hi, d_rays, d_rows, d_seen, n, d_planes, (hipStream_t) stream); });
+}
+
 // ---- observing a volume map (kr_observe.hip): SourceTracer::propagate_source, source_tracer.cpp:102-310 -------------------------------------------
 int kr_trace_observe_dev_f64(const kr_params* p, const kr_volume_map* m, const kr_observe_bins* b, const void* d_emis, const void* d_kappa, const void* d_delay,
                              void* d_rays, int64_t n, void* d_out, void* d_image, void* stream, kr_stats* stats)

@@ -148,5 +148,11 @@ int trace_volume_dev(const kr_params* p, const kr_volume_map* m, void* d_rays, i
 int observe_validate(const kr_params* p, const kr_volume_map* m, const kr_observe_bins* b, const char* who);
 int trace_observe_dev(const kr_params* p, const kr_volume_map* m, const kr_observe_bins* b, const void* d_emis, const void* d_kappa, const void* d_delay, void* d_rays,
                       int64_t n, void* d_out, void* d_image, hipStream_t st, kr_stats* stats);
+// kr_crossings.hip: the crossing-recording trace; the validator refuses a bad spec and what paths_validate refuses of the params; the launcher waits
+// for `st`.  kr_post.hip: the image of one order from what it recorded
+int crossings_validate(const kr_params* p, const kr_crossing_spec* sp, const char* who);
+int trace_crossings_dev(const kr_params* p, const kr_crossing_spec* sp, void* d_rays, int64_t n, void* d_rows, void* d_seen, hipStream_t st, kr_stats* stats);
+int reduce_crossing_image_dev(const kr_image_bins* b, int max_crossings, int order, double lo, double hi, const void* d_rays, const void* d_rows, const void* d_seen,
+                              int64_t n, void* d_planes, hipStream_t st);
 
 }  // namespace kr

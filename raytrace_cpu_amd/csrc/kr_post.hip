@@ -287,6 +287,36 @@ reduce_image_kernel(const kr_ray_f64* __restrict__ rays, long long n, kr_image_b
     if (hits) atomicAdd(&planes[7 * npix], (double) hits);
 }
 
+// ---- the image of ONE ORDER from recorded equatorial crossings (kr_crossings.hip: rows[n][M][4] = {r_c, phi_c, t_c, g}, seen[n]) ----------------
+// order >= 0: crossing `order` of every ray that stored it; order = -1, the opaque disc: a ray's first stored crossing with r_isco <= r_c < r_disc
+// (a NaN fails; g plays no part in the choice).  The chosen crossing goes through image_accumulate as a record with steps = 1 at (r_c, pi/2)
+// with phi wrapped as range_phi wraps it, so the planes of an order are filtered and summed exactly as the direct image's are.
+__global__ void __launch_bounds__(kBlock)
+reduce_crossing_image_kernel(const kr_ray_f64* __restrict__ rays, const double* __restrict__ rows, const int32_t* __restrict__ seen, long long n, kr_image_bins b,
+                             int max_crossings, int order, double lo, double hi, double* __restrict__ planes)
+{
+    const long long npix = (long long) b.img_nx * b.img_ny;
+    unsigned long long hits = 0;
+    KR_GRID_STRIDE(i, n) {
+        const int stored = seen[i] < max_crossings ? seen[i] : max_crossings;
+        const double* mine = rows + i * (long long) (4 * max_crossings);
+        int pick = -1;
+        if (order >= 0) {
+            if (order < stored) pick = order;
+        } else {
+            for (int m = 0; m < stored && pick < 0; ++m) {
+                const double r_c = mine[4 * m];
+                if (r_c >= b.r_isco && r_c < b.r_disc) pick = m;
+            }
+        }
+        if (pick < 0) continue;
+        const double* row = mine + 4 * pick;
+        const double phi = range_phi_value<double>(row[1], 1, lo, hi);
+        hits += image_accumulate(planes, npix, b, 1, row[0], kPi2, phi, row[2], row[3], rays[i].alpha, rays[i].beta);
+    }
+    if (hits) atomicAdd(&planes[7 * npix], (double) hits);
+}
+
 // ---- fused epilogue of the image pipeline: redshift(V, reverse, projradius, motion) + range_phi + the seven planes in one pass
 //      (imageplane_disc_image.cpp:117-161) -----------------------------------------------------------------------------------
 __global__ void __launch_bounds__(kBlock)
@@ -648,6 +678,16 @@ int reduce_image_dev(const kr_image_bins* b, const void* d, int64_t n, void* d_p
     if (b->img_nx <= 0 || b->img_ny <= 0) { set_error("kr_reduce_image: image size must be positive"); return KR_EINVAL; }
     if (n <= 0) return KR_OK;
     hipLaunchKernelGGL(reduce_image_kernel, dim3(grid_for(n, kBlock, kCapStream)), dim3(kBlock), 0, st, (const kr_ray_f64*) d, (long long) n, *b, (double*) d_planes);
+    KR_LAUNCH_CHECK();
+    return KR_OK;
+}
+
+int reduce_crossing_image_dev(const kr_image_bins* b, int max_crossings, int order, double lo, double hi, const void* d_rays, const void* d_rows, const void* d_seen,
+                              int64_t n, void* d_planes, hipStream_t st)
+{
+    if (n <= 0) return KR_OK;
+    hipLaunchKernelGGL(reduce_crossing_image_kernel, dim3(grid_for(n, kBlock, kCapStream)), dim3(kBlock), 0, st, (const kr_ray_f64*) d_rays, (const double*) d_rows,
+                       (const int32_t*) d_seen, (long long) n, *b, max_crossings, order, lo, hi, (double*) d_planes);
     KR_LAUNCH_CHECK();
     return KR_OK;
 }

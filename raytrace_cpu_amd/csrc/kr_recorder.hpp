@@ -1,5 +1,5 @@
 // kr_recorder.hpp -- what the recorders that ride trace_body (kr_trace_loop.hpp lists the hooks) share: PathRecorder (kr_paths.hip), VolumeRecorder
-// (kr_volume.hip) and ObserveRecorder (kr_observe.hip).  Which iterations are rows, which cell a row lies in, the energy shift at a row, the
+// (kr_volume.hip), ObserveRecorder (kr_observe.hip) and CrossingRecorder (kr_crossings.hip: the launch helpers only).  Which iterations are rows, which cell a row lies in, the energy shift at a row, the
 // wave-aggregated add, the tallies and the way such a launch is sized, enqueued and read back are stated here once; the three files keep only what
 // is particular to them.  The device helpers are forced-inline: each kernel compiles to the code it had with the lines written out.
 #pragma once

@@ -1,6 +1,6 @@
 #!/bin/bash
 # prints VGPR / SGPR / scratch / occupancy of every trace kernel instance (hipcc cross-compile, no GPU needed)
-# KR_SRC=kr_observe.hip (or kr_volume.hip, kr_paths.hip): the kernels of that file instead
+# KR_SRC=kr_observe.hip (or kr_volume.hip, kr_paths.hip, kr_crossings.hip): the kernels of that file instead
 SRC=${KR_SRC:-kr_trace.hip}
 cd "$(dirname "$0")/../raytrace_cpu_amd/csrc"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -munsafe-fp-atomics "$@" -c "$SRC" -o /tmp/kr_trace_res.o -Rpass-analysis=kernel-resource-usage 2>&1 \
