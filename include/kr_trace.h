@@ -248,6 +248,90 @@ typedef struct kr_return_map {
 static_assert(sizeof(kr_return_map) == 88, "kr_return_map is 88 bytes (raytrace_cpu_amd/capi.py ReturnMap)");
 #endif
 
+/* HealpixPointSource<T> ctor arguments (healpix_pointsource.cpp:112-172): the sky of a point source sampled by the pixels of a HEALPix sphere of
+ * 12 * 4^order pixels, RING ordering, and the source either orbiting (motion 0, as PointSource) or moving radially (motion 1: V is dr/dt, the
+ * emitter of JetPointSource, which the reference folds into calc_consts_from_vector(..., motion = 1)).
+ *   geometry   (healpix.h: ring2xyf, xyf2loc, get_pixel_vectors, quirks kept)  pixel -> (ix, iy, face) in 32-bit integers with
+ *              isqrt(x) = (int) sqrt(x + 0.5) in double;  xc = (ix + 0.5) / nside, yc = (iy + 0.5) / nside, dc = 0.5 / nside;  the four corners in the
+ *              order (xc + dc, yc + dc), (xc - dc, yc + dc), (xc - dc, yc - dc), (xc + dc, yc - dc), each through
+ *                jr = jrll[face] - x - y;  jr < 1: nr = jr, z = 1 - nr nr / 3;  jr > 3: nr = 4 - jr, z = nr nr / 3 - 1;  else nr = 1, z = (2 - jr) 2 / 3;
+ *                tmp = jpll[face] nr + x - y, brought into [0, 8) by one +8 / one -8;  phi = (nr < 1e-15) ? 0 : (0.25 pi tmp) / nr;
+ *                sinTheta = sqrt((1 - z)(1 + z));  vec = (sinTheta cos(phi + 0.05), sinTheta sin(phi + 0.05), z)   -- the fixed rotation 0.05 is the reference's;
+ *              the centre is 0.25 * (((c0 + c1) + c2) + c3) per component and NOT normalised (|centre| is 0.726-0.777 at order 0, 0.9946-0.9960 at
+ *              order 3).  unit_center = 1 (an extension) divides it by sqrt((x x + y y) + z z).  sin / cos of phi + 0.05 are the correctly rounded pair
+ *              of the strict trace; every other operation is one IEEE operation (no contraction).
+ *   layout     rays_per_pixel = 5 (the reference's): the ray of vector i of pixel pix is 5 pix + i, corners i = 0..3, centre i = 4;  rays_per_pixel = 1:
+ *              ray pix is the centre (still the average of the four corners).  Both of the reference's programs read only the centres.
+ *   record     zeroed; t, r, theta, phi = pos;  steps = 0;  alpha = vec[2], beta = atan2(vec[1], vec[0]) (correctly rounded).
+ *   disc_source  = 1 is HealpixPointSource::set_disc_source() (healpix_pointsource.h:39-43), which healpix_disc_source_photonfrac.cpp:77 calls for its
+ *              source on the disc: every ray with thetadot_sign > 0 -- it starts towards increasing theta, into the disc under the source -- gets
+ *              steps = -1, the rest of its record as built.  The trace passes over such a slot and the fate pass gives it class 0, so the fractions of
+ *              that program are over the rays that leave the disc, about half the sphere.
+ *   constants  calc_consts_from_vector (healpix_pointsource.cpp:11-109), its association kept operation for operation, with the source-frame momentum
+ *              p' = {1, v0, v1, v2} -- UNIT energy, which is what the reference's class passes -- and sin / cos / tan of pos[2] from the host's C library:
+ *                motion 0, basis 0   calculate_constants' tetrad (et0, et3, e10, e13, e22 = -1 / sqrt(rhosq), e31 = sqrt(delta / rhosq)):
+ *                                    tdot = p'0 et0 + p'1 e10, phidot = p'0 et3 + p'1 e13, rdot = p'3 e31, thetadot = p'2 e22
+ *                motion 0, basis 1   the same tdot, phidot;  rdot = p'2 (-1 sqrt(delta / rhosq)), thetadot = p'3 (-1 / sqrt(rhosq))
+ *                motion 1            et0 = 1 / sqrt(g00 + g11 V V), et1 = V et0, e12 = 1 / sqrt(rhosq), e23 = sqrt(g00 / (g03 g03 - g00 g33)),
+ *                                    e20 = -(g03 / g00) e23, e30 = sqrt(-g11 / g00) V / sqrt(g00 + g11 V V), e31 = sqrt(-g00 / g11) / sqrt(g00 + g11 V V):
+ *                                    tdot = p'0 et0 + p'1 e20 + p'3 e30, phidot = p'1 e23, rdot = p'0 et1 + p'3 e31, thetadot = p'2 e12
+ *              then k, h, Q by :99-105 and rdot_sign = rdot > 0 ? 1 : -1 (strict, unlike PointSource), thetadot_sign = thetadot > 0 ? 1 : -1.
+ *   energy     CHANGED from calc_consts_from_vector's own rule, which carries E through the sums as p' = {E, E v0, E v1, E v2}: the record holds
+ *              k E, h E, Q (E E) and emit E of the unit record.  That is the reference's arithmetic at E = 1, the only value its class passes, and
+ *              exactly homogeneous in E otherwise; the reference's rule is not (at E = 2.5, h and Q are up to 589 and 53 ulp from 2.5 x and 6.25 x
+ *              their unit values where their terms cancel).  With it goes a refusal the reference does not have: E must be positive.
+ *   emit       (the _init_emit form) motion 0: redshift_start(V, reverse) of the orbiting source, as kr_redshift_start_dev_f64 computes it on the unit
+ *              record (bit for bit at E = 1).  Motion 1: the same product g_ij u^i p^j with the four-velocity of the MOVING source,
+ *              u = (u_t, V u_t, 0, 0), u_t = 1 / sqrt(g00 + g11 V V), and with p = (tdot, rdot, thetadot, phidot) as the tetrad launched the photon
+ *              (spatial parts negated and the metric's spin negated under reverse), not as rebuilt from k, h, Q: the rebuilding takes p^r from the
+ *              null condition, the un-normalised centre vector is not null (1 - |v|^2 ~ 1e-2 at order 3), and a radially moving emitter reads p^r
+ *              where an orbiting one does not (rebuilt, the centre rays' emit is off by up to 4e-2).  Both depart from the reference on purpose:
+ *              HealpixPointSource::redshift_start takes the orbital frame for both motions, which for a source moving at dr/dt = 0.3 spreads the
+ *              "emitted" energy over 0.587 ... 1.704 E; in the source's own frame it is E to rounding.
+ *   refused    (KR_EINVAL, the field named in kr_last_error, before any device call; the metric at pos from the host's C library)  order outside 0..13
+ *              (at 13, 2 pix still fits the reference's int);  motion / basis not 0 or 1;  rays_per_pixel not 1 or 5;  basis = 1 with motion = 1;
+ *              E not positive (or NaN);
+ *              a four-velocity that is not timelike: motion 0 with 1 - (V - omega)^2 e2psi / e2nu <= 0 or NaN, motion 1 with g00 + g11 V V <= 0 or NaN.
+ *              V = -1 ("Keplerian") is refused this way: a program resolves it (kr_disc_velocity) before it fills the spec.
+ * Shards: `first` and `stride` count PIXELS -- slot s of a shard holds vector s % rays_per_pixel of pixel first + (s / rays_per_pixel) stride. */
+typedef struct kr_healpix_source {
+    double pos[4];
+    double V, spin, E;
+    int32_t order;
+    int32_t motion;          /* 0 orbital, 1 radial: V is dr/dt */
+    int32_t basis;           /* 0, 1; motion 0 only */
+    int32_t rays_per_pixel;  /* 5: the reference's layout, or 1: centres only */
+    int32_t unit_center;     /* 1: normalise the centre (extension) */
+    int32_t disc_source;     /* 1: set_disc_source() -- rays that start towards the disc below the source are unused slots */
+} kr_healpix_source;
+#ifdef __cplusplus
+static_assert(sizeof(kr_healpix_source) == 80, "kr_healpix_source is 80 bytes (raytrace_cpu_amd/capi.py HealpixSource)");
+#endif
+
+/* The fate of every direction of a HEALPix source's sky (healpix_to_disc.cpp:60-84, healpix_disc_source_photonfrac.cpp:84-108), one pass over the
+ * CENTRE rays of a shard after the trace: slot k of a 1-ray layout, or slot 5 k + 4 of a 5-ray layout, belongs to pixel first + k stride.
+ * Per centre record, with phi and g the values after range_phi and redshift (the kr_post_ form computes and stores them, the kr_reduce_ form reads
+ * rays[].phi and rays[].redshift as they are):
+ *   class 0  dead       steps <= 0
+ *   class 4  self-zone  only if self_zone: on the disc (the rule of class 1) and |r - source_r| <= 0.1 source_r and |phi - source_phi| <= 0.1 -- the
+ *                       complement of healpix_disc_source_photonfrac.cpp:95
+ *   class 1  disc       theta >= pi/2 - theta_tol and r_isco <= r < r_disc
+ *   class 2  escape     not on the disc and r > r_esc
+ *   class 3  lost       everything else that is live.  The tests are made on the values themselves, so a NaN falls through to lost.
+ * theta_tol = 0 is the photon-fraction program's rule (:94); 1e-2 is healpix_to_disc's (:65) up to its `r > r_isco` against `r >= r_isco` here.
+ * Output: double[7 npix + 6] = seven planes [class | r | theta | phi | g | t | emis](npix each), written at the pixel for EVERY pixel of the shard
+ * with the record's values (emis = powerlaw3(r) / g^3 for class 1, else 0), then six tallies {live, disc, escape, lost, self, 0}, counts as doubles,
+ * ADDED: zero the buffer once; shards and several launches write disjoint pixels and sum the tallies. */
+typedef struct kr_healpix_map {
+    double r_isco, r_disc, r_esc, theta_tol, source_r, source_phi;
+    double q1, rb1, q2, rb2, q3;            /* powerlaw3, imageplane_disc_image.cpp:20-28 */
+    int64_t npix;
+    int32_t rays_per_pixel, self_zone;
+} kr_healpix_map;
+#ifdef __cplusplus
+static_assert(sizeof(kr_healpix_map) == 104, "kr_healpix_map is 104 bytes (raytrace_cpu_amd/capi.py HealpixMap)");
+#endif
+
 /* Emission-line profile / reverberation transfer function from image-plane rays (the reference builds it outside its C++, in
  * python/line_from_image.ipynb, from the ENSHIFT and RADIUS planes of the image FITS file).  Per ray record, after redshift(-1, reverse=1):
  *   filter   steps > 0, z = r cos(theta) < 1e-2, r_isco <= r < r_disc, g > 0 with g = rays[].redshift (the disc-image filter of
@@ -703,6 +787,28 @@ int kr_post_return_map_dev_f64(double spin, double V, int reverse, int projradiu
  * ceil(count / 24) launches.  count == 0: KR_OK; an item with n[i] == 0 adds nothing. */
 int kr_post_return_map_batch_dev_f64(int32_t count, double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_return_map* m,
                                      void* const* d_rays, const int64_t* n, void* const* d_out, void* stream);
+
+/* ---- HEALPix point source and the fate map of its sky (kr_healpix_source, kr_healpix_map above) ------------------------------------------------
+ * Every entry point checks its arguments before it touches a device (KR_EINVAL, message in kr_last_error): what kr_healpix_source refuses, null
+ * pointers, first < 0, stride < 1, count < 0, a shard whose last pixel lies beyond the sphere (or beyond m->npix), a record count that is no
+ * multiple of rays_per_pixel in the map passes.  Without a device: KR_ENODEVICE.  The _dev forms neither wait for the device nor allocate.
+ * kr_healpix_count: rays_per_pixel * npix, npix in *npix when given; KR_EINVAL (negative) for a refused spec.
+ * kr_healpix_vectors_dev_f64: the geometry alone -- for pixel first_pix + k stride, k < count, out[k] = four corners then the centre, 15 doubles.
+ * kr_healpix_init_dev_f64: the records with emit = 0;  kr_healpix_init_emit_dev_f64: with their emitted energy, one pass;  `count` records.
+ * kr_healpix_init_f64: the whole source into host records, n = kr_healpix_count(), staged through the device. */
+int64_t kr_healpix_count(const kr_healpix_source* s, int64_t* npix);
+int kr_healpix_vectors_dev_f64(int32_t order, int32_t unit_center, int64_t first_pix, int64_t stride, int64_t count, void* d_out, void* stream);
+int kr_healpix_init_dev_f64(const kr_healpix_source* s, int64_t first, int64_t stride, void* d_rays, int64_t count, void* stream);
+int kr_healpix_init_emit_dev_f64(const kr_healpix_source* s, int64_t first, int64_t stride, int reverse, void* d_rays, int64_t count, void* stream);
+int kr_healpix_init_f64(const kr_healpix_source* s, kr_ray_f64* rays, int64_t n);
+/* The fate pass over n records (n / rays_per_pixel pixels).  kr_post_: range_phi(lo, hi) + redshift(V, reverse, projradius, motion) on the centre
+ * records, phi and g stored back as kr_range_phi_dev_f64 + kr_redshift_dev_f64 leave them (corner records are not touched), then the classes.
+ * kr_reduce_: no wrap, no redshift, the records read as they are.  Both ADD the tallies into d_out (7 npix + 6 doubles; zero it first).
+ * kr_reduce_healpix_map_f64: host records of the WHOLE sphere (first 0, stride 1), out = 7 npix + 6 host doubles (overwritten). */
+int kr_post_healpix_map_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_healpix_map* m, void* d_rays,
+                                int64_t n, int64_t first, int64_t stride, void* d_out, void* stream);
+int kr_reduce_healpix_map_dev_f64(const kr_healpix_map* m, const void* d_rays, int64_t n, int64_t first, int64_t stride, void* d_out, void* stream);
+int kr_reduce_healpix_map_f64(const kr_healpix_map* m, const kr_ray_f64* rays, int64_t n, double* out);
 
 /* ---- emission-line profile / transfer function (kr_line_bins above) --------------------------------------------------------------------
  * Every entry point validates the bins first, before it touches a device: KR_EINVAL (message in kr_last_error) when ne < 1 or nt < 1, de <= 0,

@@ -969,3 +969,157 @@ def order_images(imageplane_spec, params, bins, spec, orders, lo=-np.pi, hi=np.p
             if d.value:
                 L.kr_free(d)
     return {"images": images, "seen_histogram": np.bincount(seen), "stats": st.as_dict()}
+
+
+# ---- HEALPix point source and the fate map of its sky (include/kr_trace.h: kr_healpix_source, kr_healpix_map) ----------------------------------
+HEALPIX_PLANES = ("class", "r", "theta", "phi", "g", "t", "emis")
+HEALPIX_TALLIES = ("live", "disc", "escape", "lost", "self")
+
+
+def healpix_spec(pos, V, spin, order, motion=0, basis=0, rays_per_pixel=5, unit_center=0, E=1.0, disc_source=0):
+    """A kr_healpix_source: the reference's HealpixPointSource(pos, V, spin, order, motion, basis), five rays per pixel or the centres alone;
+    disc_source = 1 is its set_disc_source(): rays that start into the disc under the source are unused slots (steps = -1)."""
+    s = capi.HealpixSource()
+    for i in range(4):
+        s.pos[i] = pos[i]
+    s.V, s.spin, s.E = V, spin, E
+    s.order, s.motion, s.basis, s.rays_per_pixel, s.unit_center = int(order), int(motion), int(basis), int(rays_per_pixel), int(unit_center)
+    s.disc_source = int(disc_source)
+    return s
+
+
+def healpix_count(spec):
+    """(rays, pixels) of the source; raises for a spec the library refuses."""
+    npix = C.c_int64()
+    n = lib().kr_healpix_count(C.byref(spec), C.byref(npix))
+    if n < 0:
+        capi.check(lib(), int(n), "kr_healpix_count")
+    return int(n), int(npix.value)
+
+
+def healpix_vectors(order, first_pix=0, stride=1, count=None, unit_center=0):
+    """kr_healpix_vectors_dev_f64: [count, 15] -- four corners then the centre of pixel first_pix + k stride (default: the whole sphere)."""
+    L = lib()
+    if count is None:
+        count = (12 * 4 ** int(order) - first_pix + stride - 1) // stride if 0 <= order <= 13 else 0
+    out = np.zeros((max(count, 0), 15))
+    d = C.c_void_p()
+    try:
+        if count > 0:
+            capi.check(L, L.kr_malloc(C.byref(d), out.nbytes), "kr_malloc")
+        capi.check(L, L.kr_healpix_vectors_dev_f64(int(order), int(unit_center), int(first_pix), int(stride), int(count), d, None), "kr_healpix_vectors")
+        if count > 0:
+            capi.check(L, L.kr_memcpy_d2h(_ptr(out), d, out.nbytes), "kr_memcpy_d2h")
+    finally:
+        if d.value:
+            L.kr_free(d)
+    return out
+
+
+def healpix_init(spec, emit=True, reverse=0, first=0, stride=1, count=None):
+    """The source's ray records, built on the device: with their emitted energy (kr_healpix_init_emit_dev_f64) or with emit = 0
+    (kr_healpix_init_dev_f64).  first / stride count pixels; count records (default: every pixel from `first` on at that stride)."""
+    L = lib()
+    n, npix = healpix_count(spec)
+    if count is None:
+        count = spec.rays_per_pixel * ((npix - first + stride - 1) // stride)
+    rays = np.zeros(max(count, 0), dtype=capi.RAY_F64)
+    d = C.c_void_p()
+    try:
+        if count > 0:
+            capi.check(L, L.kr_malloc(C.byref(d), rays.nbytes), "kr_malloc")
+        if emit:
+            capi.check(L, L.kr_healpix_init_emit_dev_f64(C.byref(spec), int(first), int(stride), int(reverse), d, int(count), None), "kr_healpix_init_emit")
+        else:
+            capi.check(L, L.kr_healpix_init_dev_f64(C.byref(spec), int(first), int(stride), d, int(count), None), "kr_healpix_init")
+        if count > 0:
+            capi.check(L, L.kr_memcpy_d2h(_ptr(rays), d, rays.nbytes), "kr_memcpy_d2h")
+    finally:
+        if d.value:
+            L.kr_free(d)
+    return rays
+
+
+def healpix_map_struct(npix, r_isco, r_disc, r_esc, theta_tol=0.0, source_r=0.0, source_phi=0.0, self_zone=0, rays_per_pixel=5, q1=3.0, rb1=4.0, q2=3.0,
+                       rb2=10.0, q3=3.0):
+    m = capi.HealpixMap()
+    m.r_isco, m.r_disc, m.r_esc, m.theta_tol, m.source_r, m.source_phi = r_isco, r_disc, r_esc, theta_tol, source_r, source_phi
+    m.q1, m.rb1, m.q2, m.rb2, m.q3 = q1, rb1, q2, rb2, q3
+    m.npix, m.rays_per_pixel, m.self_zone = int(npix), int(rays_per_pixel), int(self_zone)
+    return m
+
+
+def healpix_map_words(m):
+    """Length of the fate-map buffer: seven planes of npix and six tallies."""
+    return 7 * m.npix + 6
+
+
+def healpix_map_from_words(m, words):
+    """The fate-map buffer as a dict: the planes by name ("class" as int64), the tallies live / disc / escape / lost / self (ints) and the fractions
+    of the live rays "disc_frac" / "escape_frac" / "lost_frac" / "self_frac" (the reference's Return / Escape / Lost, healpix_disc_source_photonfrac.cpp:111-113)."""
+    npix = m.npix
+    words = np.asarray(words, dtype=np.float64)
+    out = {k: words[q * npix:(q + 1) * npix].copy() for q, k in enumerate(HEALPIX_PLANES)}
+    out["class"] = np.rint(out["class"]).astype(np.int64)
+    out.update({k: int(round(float(words[7 * npix + q]))) for q, k in enumerate(HEALPIX_TALLIES)})
+    live = float(words[7 * npix])
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out.update({k + "_frac": float(np.float64(words[7 * npix + 1 + q]) / np.float64(live)) for q, k in enumerate(HEALPIX_TALLIES[1:])})
+    return out
+
+
+def reduce_healpix_map(m, rays):
+    """kr_reduce_healpix_map_f64: the fate map of the host records of a whole sphere, read as they are (after range_phi() and redshift())."""
+    _rays_arg(rays, capi.RAY_F64)
+    out = np.zeros(healpix_map_words(m))
+    capi.check(lib(), lib().kr_reduce_healpix_map_f64(C.byref(m), _ptr(rays), len(rays), _ptr(out)), "kr_reduce_healpix_map")
+    return healpix_map_from_words(m, out)
+
+
+def healpix_map(spec, params, m, reverse=0, projradius=0, V=-1.0, motion=0, lo=-np.pi, hi=np.pi, return_records=False):
+    """The fate of every direction of a HEALPix source's sky, resident on the device: the rays with their emitted energy
+    (kr_healpix_init_emit_dev_f64) -> kr_trace_dev_f64 with `params` -> range_phi + redshift(V, reverse, projradius, motion) + the classes
+    (kr_post_healpix_map_dev_f64).  The rays never leave the device (return_records copies the final records back, for tests).  Returns the dict of
+    healpix_map_from_words plus "stats"."""
+    L = lib()
+    n, npix = healpix_count(spec)
+    if m.npix != npix or m.rays_per_pixel != spec.rays_per_pixel:
+        raise KrError("healpix_map: the map's npix / rays_per_pixel are not the source's")
+    nw = healpix_map_words(m)
+    words = np.zeros(nw)
+    d_rays, d_out = C.c_void_p(), C.c_void_p()
+    st = Stats()
+    rec = None
+    try:
+        capi.check(L, L.kr_malloc(C.byref(d_rays), n * capi.RAY_F64.itemsize), "kr_malloc")
+        capi.check(L, L.kr_malloc(C.byref(d_out), nw * 8), "kr_malloc")
+        capi.check(L, L.kr_memset(d_out, 0, nw * 8), "kr_memset")
+        capi.check(L, L.kr_healpix_init_emit_dev_f64(C.byref(spec), 0, 1, int(reverse), d_rays, n, None), "kr_healpix_init_emit")
+        capi.check(L, L.kr_trace_dev_f64(C.byref(params), d_rays, n, None, C.byref(st)), "kr_trace_dev")
+        capi.check(L, L.kr_post_healpix_map_dev_f64(params.spin, V, int(reverse), int(projradius), int(motion), lo, hi, C.byref(m), d_rays, n, 0, 1, d_out, None),
+                   "kr_post_healpix_map")
+        capi.check(L, L.kr_memcpy_d2h(_ptr(words), d_out, words.nbytes), "kr_memcpy_d2h")
+        if return_records:
+            rec = np.zeros(n, dtype=capi.RAY_F64)
+            capi.check(L, L.kr_memcpy_d2h(_ptr(rec), d_rays, rec.nbytes), "kr_memcpy_d2h")
+    finally:
+        for d in (d_rays, d_out):
+            if d.value:
+                L.kr_free(d)
+    res = healpix_map_from_words(m, words)
+    res["stats"] = st.as_dict()
+    if return_records:
+        res["records"] = rec
+    return res
+
+
+def healpix_to_disc_text(res):
+    """The table kr_healpix_to_disc writes for the result of healpix_map(): `pix r phi redshift emis` per pixel, every field setw(20), doubles
+    scientific with precision 8 (host/include/text_output.h); a pixel whose class is not 1 (disc) is `pix nan nan nan 0`."""
+    rows = []
+    for pix, c in enumerate(res["class"].tolist()):
+        if c == 1:
+            rows.append("%20d" % pix + "".join(_path_field(float(res[k][pix])) for k in ("r", "phi", "g", "emis")) + "\n")
+        else:
+            rows.append("%20d%20s%20s%20s%20d\n" % (pix, "nan", "nan", "nan", 0))
+    return "".join(rows)

@@ -78,6 +78,19 @@ class ReturnMap(C.Structure):
     _fields_ = [("cls", ReturnBins), ("r_min", C.c_double), ("dr", C.c_double), ("gamma", C.c_double), ("nr", C.c_int32), ("logbin", C.c_int32)]
 
 
+class HealpixSource(C.Structure):
+    """kr_healpix_source: a point source whose sky is sampled by HEALPix pixels, orbiting (motion 0) or moving radially (motion 1)
+    (include/kr_trace.h has the geometry, the ray rule and what is refused)."""
+    _fields_ = [("pos", C.c_double * 4)] + [(n, C.c_double) for n in ("V", "spin", "E")] + \
+               [(n, C.c_int32) for n in ("order", "motion", "basis", "rays_per_pixel", "unit_center", "disc_source")]
+
+
+class HealpixMap(C.Structure):
+    """kr_healpix_map: the classes of the fate pass over a HEALPix source's centre rays (include/kr_trace.h has the rule)."""
+    _fields_ = [(n, C.c_double) for n in ("r_isco", "r_disc", "r_esc", "theta_tol", "source_r", "source_phi", "q1", "rb1", "q2", "rb2", "q3")] + \
+               [("npix", C.c_int64), ("rays_per_pixel", C.c_int32), ("self_zone", C.c_int32)]
+
+
 class LineBins(C.Structure):
     """kr_line_bins: emission-line energy x time bins (include/kr_trace.h has the per-ray rules).  table_emis / table_time are host
     double arrays or None; keep the arrays alive while the struct is in use (LineBins.with_table does)."""
@@ -247,6 +260,14 @@ PROTOTYPES = {
     "kr_reduce_return_map_dev_f64": (_int, [P(ReturnMap), _vp, _i64, _vp, _vp]),
     "kr_post_return_map_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, P(ReturnMap), _vp, _i64, _vp, _vp]),
     "kr_post_return_map_batch_dev_f64": (_int, [_i32, _dbl, _dbl, _int, _int, _int, _dbl, _dbl, P(ReturnMap), P(_vp), P(_i64), P(_vp), _vp]),
+    "kr_healpix_count": (_i64, [P(HealpixSource), P(_i64)]),
+    "kr_healpix_vectors_dev_f64": (_int, [_i32, _i32, _i64, _i64, _i64, _vp, _vp]),
+    "kr_healpix_init_dev_f64": (_int, [P(HealpixSource), _i64, _i64, _vp, _i64, _vp]),
+    "kr_healpix_init_emit_dev_f64": (_int, [P(HealpixSource), _i64, _i64, _int, _vp, _i64, _vp]),
+    "kr_healpix_init_f64": (_int, [P(HealpixSource), _vp, _i64]),
+    "kr_post_healpix_map_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, P(HealpixMap), _vp, _i64, _i64, _i64, _vp, _vp]),
+    "kr_reduce_healpix_map_dev_f64": (_int, [P(HealpixMap), _vp, _i64, _i64, _i64, _vp, _vp]),
+    "kr_reduce_healpix_map_f64": (_int, [P(HealpixMap), _vp, _i64, _vp]),
     "kr_reduce_line_f64": (_int, [P(LineBins), _vp, _i64, _vp]),
     "kr_reduce_line_dev_f64": (_int, [P(LineBins), _vp, _i64, _vp, _vp]),
     "kr_post_line_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, P(LineBins), _vp, _i64, _vp, _vp]),

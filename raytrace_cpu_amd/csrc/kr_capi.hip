@@ -905,6 +905,72 @@ int kr_reduce_return_map_f64(const kr_return_map* m, const kr_ray_f64* rays, int
     return reduce_to_host(rays, n, 5 * (size_t) m->nr + 6, out, [&](void* d, void* d_out) { return reduce_return_map_dev(m, d, n, d_out, nullptr); });
 }
 
+// ---- HEALPix point source and the fate map of its sky (kr_healpix.hip) ---------------------------------------------------------------------
+int64_t kr_healpix_count(const kr_healpix_source* s, int64_t* npix)
+{
+    const int rc = healpix_validate(s, "kr_healpix_count");
+    if (rc != KR_OK) return rc;
+    const int64_t np = 12LL << (2 * s->order);
+    if (npix) *npix = np;
+    return s->rays_per_pixel * np;
+}
+
+int kr_healpix_vectors_dev_f64(int32_t order, int32_t unit_center, int64_t first_pix, int64_t stride, int64_t count, void* d_out, void* st)
+{
+    const int rc = healpix_vectors_validate(order, first_pix, stride, count, "kr_healpix_vectors");
+    if (rc != KR_OK) return rc;
+    return on_device(count == 0 || d_out, "kr_healpix_vectors: null output buffer",
+                     [&] { return healpix_vectors_dev(order, unit_center, first_pix, stride, count, d_out, (hipStream_t) st); });
+}
+
+int kr_healpix_init_dev_f64(const kr_healpix_source* s, int64_t first, int64_t stride, void* d, int64_t count, void* st)
+{
+    const int rc = healpix_shard_validate(s, first, stride, count, "kr_healpix_init");
+    if (rc != KR_OK) return rc;
+    return on_device(count == 0 || d, "kr_healpix_init: null ray buffer", [&] { return healpix_init_dev(s, d, count, first, stride, false, 0, (hipStream_t) st); });
+}
+
+int kr_healpix_init_emit_dev_f64(const kr_healpix_source* s, int64_t first, int64_t stride, int reverse, void* d, int64_t count, void* st)
+{
+    const int rc = healpix_shard_validate(s, first, stride, count, "kr_healpix_init_emit");
+    if (rc != KR_OK) return rc;
+    return on_device(count == 0 || d, "kr_healpix_init_emit: null ray buffer",
+                     [&] { return healpix_init_dev(s, d, count, first, stride, true, reverse, (hipStream_t) st); });
+}
+
+int kr_healpix_init_f64(const kr_healpix_source* s, kr_ray_f64* rays, int64_t n)
+{
+    const int rc = healpix_validate(s, "kr_healpix_init");
+    if (rc != KR_OK) return rc;
+    if (n != kr_healpix_count(s, nullptr)) return invalid("kr_healpix_init: n is not kr_healpix_count()");
+    return with_staged_rays(rays, n, sizeof(kr_ray_f64), kConstructs, nullptr, [&](void* d) { return healpix_init_dev(s, d, n, 0, 1, false, 0, nullptr); });
+}
+
+int kr_post_healpix_map_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_healpix_map* m, void* d, int64_t n,
+                                int64_t first, int64_t stride, void* d_out, void* st)
+{
+    const int rc = healpix_map_validate(m, n, first, stride, "kr_post_healpix_map");
+    if (rc != KR_OK) return rc;
+    return on_device(d_out && (n == 0 || d), "kr_post_healpix_map: null argument",
+                     [&] { return post_healpix_map_dev(spin, V, reverse, projradius, motion, lo, hi, m, d, n, first, stride, d_out, (hipStream_t) st); });
+}
+
+int kr_reduce_healpix_map_dev_f64(const kr_healpix_map* m, const void* d, int64_t n, int64_t first, int64_t stride, void* d_out, void* st)
+{
+    const int rc = healpix_map_validate(m, n, first, stride, "kr_reduce_healpix_map");
+    if (rc != KR_OK) return rc;
+    return on_device(d_out && (n == 0 || d), "kr_reduce_healpix_map: null argument",
+                     [&] { return reduce_healpix_map_dev(m, d, n, first, stride, d_out, (hipStream_t) st); });
+}
+
+int kr_reduce_healpix_map_f64(const kr_healpix_map* m, const kr_ray_f64* rays, int64_t n, double* out)
+{
+    const int rc = healpix_map_validate(m, n, 0, 1, "kr_reduce_healpix_map");
+    if (rc != KR_OK) return rc;
+    if (!out) return invalid("kr_reduce_healpix_map: null argument");
+    return reduce_to_host(rays, n, 7 * (size_t) m->npix + 6, out, [&](void* d, void* d_out) { return reduce_healpix_map_dev(m, d, n, 0, 1, d_out, nullptr); });
+}
+
 int kr_reduce_line_dev_f64(const kr_line_bins* b, const void* d, int64_t n, void* d_line, void* st)
 {
     const int rc = line_validate(b, "kr_reduce_line");

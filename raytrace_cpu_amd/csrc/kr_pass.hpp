@@ -123,6 +123,17 @@ int post_return_map_dev(double spin, double V, int reverse, int projradius, int 
                         hipStream_t st);
 int post_return_map_batch_dev(int count, double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_return_map* m, void* const* d,
                               const int64_t* n, void* const* d_out, hipStream_t st);
+// kr_healpix.hip: the HEALPix point source (kr_healpix_source) and the fate map of its sky (kr_healpix_map).  The validators refuse what the structs'
+// comments refuse and a shard that reaches beyond the sphere; first / stride count pixels
+int healpix_validate(const kr_healpix_source* s, const char* who);
+int healpix_shard_validate(const kr_healpix_source* s, int64_t first, int64_t stride, int64_t count, const char* who);
+int healpix_vectors_validate(int order, int64_t first, int64_t stride, int64_t count, const char* who);
+int healpix_map_validate(const kr_healpix_map* m, int64_t n, int64_t first, int64_t stride, const char* who);
+int healpix_vectors_dev(int order, int unit_center, int64_t first, int64_t stride, int64_t count, void* d_out, hipStream_t st);
+int healpix_init_dev(const kr_healpix_source* s, void* d, int64_t n, int64_t first, int64_t stride, bool emit, int reverse, hipStream_t st);
+int reduce_healpix_map_dev(const kr_healpix_map* m, const void* d, int64_t n, int64_t first, int64_t stride, void* d_out, hipStream_t st);
+int post_healpix_map_dev(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_healpix_map* m, void* d, int64_t n, int64_t first,
+                         int64_t stride, void* d_out, hipStream_t st);
 // kr_line.hip
 int line_validate(const kr_line_bins* b, const char* who);
 int reduce_line_dev(const kr_line_bins* b, const void* d, int64_t n, void* d_line, hipStream_t st);
