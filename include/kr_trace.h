@@ -363,6 +363,31 @@ typedef struct kr_line_bins {
 static_assert(sizeof(kr_line_bins) == 160, "kr_line_bins is 160 bytes (raytrace_cpu_amd/capi.py LineBins)");
 #endif
 
+/* The angle at which a photon meets the disc, in the rest frame of the orbiting gas.  For a record with steps > 0 the observer is the one of
+ * kr_redshift_dev_f64(spin, V, reverse, projradius, motion = 0), quirks included: the metric takes a = reverse ? -spin : spin, the momentum p comes
+ * from the constants of motion (k, h, Q, the two signs) with `spin`, its spatial part negated with reverse, and V == -1 means Keplerian at the record's r.
+ * On the reference's Tetrad (kerr.h:127-170: e_t, e1 along phi, e2 along theta, e3 along r) the frame components are
+ *   E = g(p, e_t)  (the `recv` of redshift(), to the bit),   P_phi = -g(p, e1),   P_th = -g(p, e2) = rho thetadot,   P_r = -g(p, e3) = rdot rho / sqrt(delta)
+ * and the two angles
+ *   mu  = |P_th| / E          the cosine of the angle to the disc normal, in [0, 1]
+ *   chi = atan2(P_phi, P_r)   the azimuth about the normal: 0 radially outward, +pi/2 along the orbital motion.
+ * A record is BAD-ANGLE when mu is not finite, mu > 1 or E <= 0.  Such records exist in the reference's own results: a ray that the integrator has
+ * stepped past a radial turning point has rdot^2 < 0 under the sqrt(|.|) of the momentum, and its state is not a null vector.
+ * kr_limb_law: the weight of the emission angle in the line.  law 0: 1 (isotropic);  1: 1 + coeff mu (Laor: coeff 2.06);  2: log(1 + 1 / mu)
+ * (limb brightening).  Any other law is refused. */
+typedef struct kr_limb_law {
+    double coeff;
+    int32_t law, pad;
+} kr_limb_law;
+/* the mu axis of the emissivity by incidence angle: nmu >= 1 equal bins of [0, 1], im = min((int) (mu nmu), nmu - 1) */
+typedef struct kr_mu_bins {
+    int32_t nmu, pad;
+} kr_mu_bins;
+#ifdef __cplusplus
+static_assert(sizeof(kr_limb_law) == 16, "kr_limb_law is 16 bytes (raytrace_cpu_amd/capi.py LimbLaw)");
+static_assert(sizeof(kr_mu_bins) == 8, "kr_mu_bins is 8 bytes (raytrace_cpu_amd/capi.py MuBins)");
+#endif
+
 /* Critical-curve (caustic) maps of the disc on an image plane: src/caustic/caustic_discplane.cpp.  Per image-plane pixel (ix, iy), from the ray through
  * the pixel (bundle mode: member 0 of its 5-ray bundle, imageplane_bundles.h) after redshift(dest, reverse) (caustic_discplane.cpp:219-251):
  *   valid_hit   steps > 0, r_isco <= r < r_disc, redshift > 0 (:177-182)
@@ -823,6 +848,27 @@ int kr_post_line_dev_f64(double spin, double V, int reverse, int projradius, int
                          void* d_line, void* stream);
 /* the notebook's per-pixel form over d_planes (7 img_nx img_ny + 1 doubles, the layout of kr_reduce_image_dev_f64) */
 int kr_line_from_image_dev_f64(const kr_line_bins* b, const kr_image_bins* ib, const void* d_planes, void* d_line, void* stream);
+
+/* ---- photon angles in the disc frame (kr_limb_law / kr_mu_bins above have the rule) ---------------------------------------------------------
+ * Every entry point validates its arguments before it touches a device: KR_EINVAL (message in kr_last_error) for a null pointer, n < 0, a limb law
+ * other than 0, 1, 2, nmu < 1, nr < 1, motion != 0 (only the orbiting observer has this frame) and whatever the line bins refuse.  n == 0 is KR_OK
+ * and adds nothing.
+ * kr_angles_dev_f64 reads the records and never writes them: d_angles[2 i] = mu, d_angles[2 i + 1] = chi (2 n doubles); NaN in both for a record with
+ * steps <= 0; a bad-angle record gets its values as computed -- consumers filter.  kr_angles_f64: host records, host angles. */
+int kr_angles_dev_f64(double spin, double V, int reverse, int projradius, int motion, const void* d_rays, int64_t n, void* d_angles, void* stream);
+int kr_angles_f64(double spin, double V, int reverse, int projradius, int motion, const kr_ray_f64* rays, int64_t n, double* angles);
+/* kr_post_line_dev_f64 with w *= limb(mu), mu from the metric and momentum evaluation that gives g: rays[] ends up exactly as after
+ * kr_post_line_dev_f64.  ADDS into d_line, 2 nt ne + 3 doubles: the layout of kr_post_line_dev_f64, then bad_angle.  A bad-angle ray that passes the
+ * filter counts in on_disc and bad_angle; with law != 0 it is not binned, with law 0 every ray is binned as kr_post_line_dev_f64 bins it. */
+int kr_post_line_limb_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_line_bins* b, const kr_limb_law* law,
+                              void* d_rays, int64_t n, void* d_line, void* stream);
+/* kr_post_emissivity_dev_f64 with the histogram split by incidence angle.  d_hist (5 nr + 1 doubles) receives exactly what kr_post_emissivity_dev_f64
+ * puts there, bad-angle rays included, and rays[] ends up the same.  ADDS into d_mu, (2 nmu + 1) nr + 3 doubles:
+ *   [count2 (nr x nmu: [ir nmu + im]) | flux2 (nr x nmu; each ray adds 1 / (num_primary_rays g)) | sum_mu (nr) | disc_count | binned | bad_angle]
+ * A bad-angle ray that was binned radially moves only bad_angle: sum(count2) == binned - bad_angle, and each row of count2 sums to the radial count
+ * minus that bin's bad-angle rays. */
+int kr_post_emissivity_mu_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_emis_bins* b, const kr_mu_bins* mb,
+                                  void* d_rays, int64_t n, void* d_hist, void* d_mu, void* stream);
 
 /* ---- critical-curve maps (kr_caustic_map above): caustic_discplane.cpp on the device -------------------------------------------------------
  * Every entry point validates its arguments before it touches a device: KR_EINVAL (message in kr_last_error) when nx or ny < 1, eps_x or eps_y

@@ -367,22 +367,27 @@ def default_image_bins(spec, bins):
     return ib
 
 
-def line_profile(imageplane_spec, params, bins, mode="rays", image_bins=None):
+def line_profile(imageplane_spec, params, bins, mode="rays", image_bins=None, limb=None):
     """The emission line of an image plane, resident on the device from start to finish, as the kr_line_profile app runs it:
     ImagePlane ctor + redshift_start (kr_imageplane_init_emit_dev_f64) -> trace (kr_trace_dev_f64) -> either
       mode="rays":   redshift + range_phi + line bins per ray (kr_post_line_dev_f64), or
       mode="pixels": redshift + range_phi + the image planes (kr_post_image_dev_f64, `image_bins`; default: one pixel per ray)
                      -> line bins per pixel, the notebook's form (kr_line_from_image_dev_f64).
     `params` as for the image app: the stored (negated) spin, theta / r limits, integrator.  Only the histogram is read back.
-    Returns line_from_words(...) plus "stats" (the trace's kr_stats)."""
+    limb (mode="rays" only): None for the isotropic line through kr_post_line_dev_f64, or a limb law of the emission angle in the disc frame --
+    (law, coeff) or "isotropic", "laor" (1 + 2.06 mu), "brightening" (log(1 + 1 / mu)) -- through kr_post_line_limb_dev_f64.
+    Returns line_from_words(...) plus "stats" (the trace's kr_stats) and, with a limb law, "bad_angle"."""
     if mode not in ("rays", "pixels"):
         raise KrError(f"line_profile: mode must be 'rays' or 'pixels', got {mode!r}")
+    if limb is not None and mode != "rays":
+        raise KrError("line_profile: a limb law needs mode='rays' (a pixel's mean has no emission angle)")
+    law = capi.limb_law(limb) if limb is not None else None
     L = lib()
     n, _, _ = imageplane_count(imageplane_spec)
     if n <= 0:
         raise KrError("line_profile: empty ray grid")
     spin = -1 * imageplane_spec.spin                     # as stored by the Raytracer of an ImagePlane (imageplane.cpp:12)
-    nw = line_words(bins)
+    nw = line_words(bins) + (1 if law is not None else 0)
     d_rays, d_line, d_planes = C.c_void_p(), C.c_void_p(), C.c_void_p()
     st = Stats()
     try:
@@ -391,7 +396,9 @@ def line_profile(imageplane_spec, params, bins, mode="rays", image_bins=None):
         capi.check(L, L.kr_memset(d_line, 0, nw * 8), "kr_memset")
         capi.check(L, L.kr_imageplane_init_emit_dev_f64(C.byref(imageplane_spec), 0, 1, 0.0, 1, 0, d_rays, n, None), "kr_imageplane_init_emit")
         capi.check(L, L.kr_trace_dev_f64(C.byref(params), d_rays, n, None, C.byref(st)), "kr_trace_dev")
-        if mode == "rays":
+        if law is not None:
+            capi.check(L, L.kr_post_line_limb_dev_f64(spin, -1.0, 1, 0, 0, -np.pi, np.pi, C.byref(bins), C.byref(law), d_rays, n, d_line, None), "kr_post_line_limb")
+        elif mode == "rays":
             capi.check(L, L.kr_post_line_dev_f64(spin, -1.0, 1, 0, 0, -np.pi, np.pi, C.byref(bins), d_rays, n, d_line, None), "kr_post_line")
         else:
             ib = image_bins if image_bins is not None else default_image_bins(imageplane_spec, bins)
@@ -408,7 +415,85 @@ def line_profile(imageplane_spec, params, bins, mode="rays", image_bins=None):
                 L.kr_free(d)
     res = line_from_words(bins, out)
     res["stats"] = st.as_dict()
+    if law is not None:
+        res["bad_angle"] = int(round(float(out[-1])))
     return res
+
+
+def arrival_angles(rays, spin, V=-1.0, reverse=0, projradius=0):
+    """kr_angles_f64 / kr_angles_dev_f64: (mu, chi) of every record in the rest frame of the orbiting gas, the observer of redshift(spin, V, reverse,
+    projradius).  mu = |P_th| / E is the cosine of the angle to the disc normal, chi = atan2(P_phi, P_r) the azimuth about it; NaN for records with
+    steps <= 0; a bad-angle record (mu not finite or > 1: include/kr_trace.h) keeps its values.  rays: a host array of Ray<double> records, or
+    (device pointer, n) for records that are already on the device."""
+    L = lib()
+    if isinstance(rays, tuple):
+        d_ptr, n = rays
+        out = np.zeros(2 * n)
+        d_out = C.c_void_p()
+        if n > 0:
+            capi.check(L, L.kr_malloc(C.byref(d_out), out.nbytes), "kr_malloc")
+        try:
+            d = d_ptr if isinstance(d_ptr, C.c_void_p) else C.c_void_p(d_ptr)
+            capi.check(L, L.kr_angles_dev_f64(spin, V, int(reverse), int(projradius), 0, d, n, d_out, None), "kr_angles_dev")
+            if n > 0:
+                capi.check(L, L.kr_memcpy_d2h(_ptr(out), d_out, out.nbytes), "kr_memcpy_d2h")
+        finally:
+            if d_out.value:
+                L.kr_free(d_out)
+    else:
+        _rays_arg(rays, capi.RAY_F64)
+        out = np.zeros(2 * len(rays))
+        capi.check(L, L.kr_angles_f64(spin, V, int(reverse), int(projradius), 0, _ptr(rays), len(rays), _ptr(out)), "kr_angles")
+    return out[0::2].copy(), out[1::2].copy()
+
+
+def emissivity_mu_words(bins, nmu):
+    """Length of the by-angle buffer of kr_post_emissivity_mu_dev_f64: [count2 (nr x nmu) | flux2 (nr x nmu) | sum_mu (nr) | disc_count, binned, bad_angle]."""
+    return (2 * nmu + 1) * bins.nr + 3
+
+
+def emissivity_angles(pointsource_spec, params, bins, nmu, V=-1.0, reverse=0, projradius=0):
+    """The emissivity of a point source split by incidence angle, resident on the device from start to finish, as the kr_emissivity app runs it:
+    PointSource ctor + redshift_start (kr_pointsource_init_emit_dev_f64, the source's own V) -> trace (kr_trace_dev_f64) -> range_phi + redshift(V) +
+    the radial histogram + its split by mu (kr_post_emissivity_mu_dev_f64).  Only the two histograms are read back.
+    Returns (hist, count2, flux2, mean_mu, tallies): hist as reduce_emissivity returns it (raw sums); count2 (int64) and flux2 of shape (nr, nmu);
+    mean_mu per radial bin over the rays of count2 (NaN where there are none); tallies = {"disc_count", "binned", "bad_angle", "stats"}."""
+    L = lib()
+    n, _, _ = pointsource_count(pointsource_spec)
+    if n <= 0:
+        raise KrError("emissivity_angles: empty ray grid")
+    nr, nh, nm = bins.nr, 5 * bins.nr + 1, emissivity_mu_words(bins, nmu)
+    mb = capi.MuBins(int(nmu), 0)
+    d_rays, d_hist, d_mu = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    st = Stats()
+    h, m = np.zeros(nh), np.zeros(max(nm, 0))
+    try:
+        if bins.nr > 0 and nmu >= 1:               # (the call below refuses the rest)
+            capi.check(L, L.kr_malloc(C.byref(d_hist), nh * 8), "kr_malloc")
+            capi.check(L, L.kr_memset(d_hist, 0, nh * 8), "kr_memset")
+            capi.check(L, L.kr_malloc(C.byref(d_mu), nm * 8), "kr_malloc")
+            capi.check(L, L.kr_memset(d_mu, 0, nm * 8), "kr_memset")
+        capi.check(L, L.kr_malloc(C.byref(d_rays), n * capi.RAY_F64.itemsize), "kr_malloc")
+        capi.check(L, L.kr_pointsource_init_emit_dev_f64(C.byref(pointsource_spec), 0, 1, pointsource_spec.V, int(reverse), int(projradius), d_rays, n, None),
+                   "kr_pointsource_init_emit")
+        capi.check(L, L.kr_trace_dev_f64(C.byref(params), d_rays, n, None, C.byref(st)), "kr_trace_dev")
+        capi.check(L, L.kr_post_emissivity_mu_dev_f64(pointsource_spec.spin, V, int(reverse), int(projradius), 0, -np.pi, np.pi, C.byref(bins), C.byref(mb), d_rays, n,
+                                                      d_hist, d_mu, None), "kr_post_emissivity_mu")
+        capi.check(L, L.kr_memcpy_d2h(_ptr(h), d_hist, h.nbytes), "kr_memcpy_d2h")
+        capi.check(L, L.kr_memcpy_d2h(_ptr(m), d_mu, m.nbytes), "kr_memcpy_d2h")
+    finally:
+        for d in (d_rays, d_hist, d_mu):
+            if d.value:
+                L.kr_free(d)
+    hist = {"count": h[:nr].astype(np.int64), "flux": h[nr:2 * nr].copy(), "emis": h[2 * nr:3 * nr].copy(), "sum_redshift": h[3 * nr:4 * nr].copy(),
+            "sum_time": h[4 * nr:5 * nr].copy(), "disc_count": int(h[5 * nr])}
+    plane = nr * nmu
+    count2 = m[:plane].reshape(nr, nmu).astype(np.int64)
+    flux2 = m[plane:2 * plane].reshape(nr, nmu).copy()
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean_mu = m[2 * plane:2 * plane + nr] / count2.sum(axis=1)
+    tallies = {"disc_count": int(m[-3]), "binned": int(m[-2]), "bad_angle": int(m[-1]), "stats": st.as_dict()}
+    return hist, count2, flux2, mean_mu, tallies
 
 
 CAUSTIC_PLANES = ("det_j", "sign_j", "order", "hit", "radius", "phi", "x_disc", "y_disc", "redshift")

@@ -8,7 +8,9 @@
 // (outer radius of the trace), --rmin | rmin = -1 (-> ISCO), --Nr | Nr = 100, r_disc := r_esc key, default 500 (sic, :51),
 // logbin_r = true, gamma = 2, --source_h.  Extensions: --integrator | integrator = rk45 (the reference hard-codes RK45,
 // :91; BASELINE configs[1] is the same run with rk4), --arithmetic | KRTRACE_ARITHMETIC = hybrid|strict|fast,
-// --device = 0, --timing.
+// --device = 0, --timing.  --Nmu | Nmu = 0 and --mu_outfile | mu_outfile: with Nmu >= 1 the histogram is also split by the incidence angle in the
+// disc frame (kr_post_emissivity_mu_dev_f64) and a second table goes to mu_outfile: per radial bin r, then Nmu columns count2 / count (the share
+// of the bin's rays in each mu bin) and the mean mu, in TextOutput's format.  Without Nmu the program does what it did before the key existed.
 //
 // What is NOT taken from the reference: with logbin_r = 0 its bin areas do not compile (`disc_r + dr`, :79); the
 // intended upper edge r + dr (as in emissivity_rd.cpp:88 ... which passes `dr` alone) is used here.
@@ -47,6 +49,10 @@ try {
     const string integ = args.key_exists("--integrator") ? args.get_parameter<string>("--integrator") : par.get_parameter<string>("integrator", "rk45");
     const string arith = args.key_exists("--arithmetic") ? args.get_parameter<string>("--arithmetic") : krapp::arithmetic_from_env();
     const bool timing = args.key_exists("--timing");
+    const int Nmu = args.key_exists("--Nmu") ? args.get_parameter<int>("--Nmu") : par.get_parameter<int>("Nmu", 0);
+    const string mu_out_name = args.key_exists("--mu_outfile") ? args.get_parameter<string>("--mu_outfile") : par.get_parameter<string>("mu_outfile", "");
+    if (Nmu < 0) throw invalid_argument("Nmu must be >= 0");
+    if (Nmu > 0 && mu_out_name.empty()) throw invalid_argument("Nmu needs mu_outfile");
 
     kr_pointsource src;
     memset(&src, 0, sizeof src);
@@ -106,13 +112,42 @@ try {
     kr_stats st;
     krapp::check(kr_trace_dev_f64(&p, rays.get(), n, nullptr, &st), "trace");
     const double ms_trace = clock.lap_ms();
-    krapp::check(kr_post_emissivity_dev_f64(spin, -1.0, 0, 0, 0, -1 * M_PI, M_PI, &bins, rays.get(), n, hist.get(), nullptr), "range_phi + redshift + histogram");
+    vector<double> hmu;
+    if (Nmu > 0) {
+        kr_mu_bins mb;
+        memset(&mb, 0, sizeof mb);
+        mb.nmu = Nmu;
+        hmu.resize((2 * (size_t) Nmu + 1) * (size_t) Nr + 3);
+        krapp::DeviceBuffer by_mu((int64_t) (hmu.size() * sizeof(double)));
+        by_mu.zero();
+        krapp::check(kr_post_emissivity_mu_dev_f64(spin, -1.0, 0, 0, 0, -1 * M_PI, M_PI, &bins, &mb, rays.get(), n, hist.get(), by_mu.get(), nullptr),
+                     "range_phi + redshift + histogram by angle");
+        krapp::check(kr_memcpy_d2h(hmu.data(), by_mu.get(), (int64_t) (hmu.size() * sizeof(double))), "d2h");
+    } else {
+        krapp::check(kr_post_emissivity_dev_f64(spin, -1.0, 0, 0, 0, -1 * M_PI, M_PI, &bins, rays.get(), n, hist.get(), nullptr), "range_phi + redshift + histogram");
+    }
     vector<double> h(5 * (size_t) Nr + 1);
     krapp::check(kr_memcpy_d2h(h.data(), hist.get(), (int64_t) (h.size() * sizeof(double))), "d2h");
     const double ms_post = clock.lap_ms();
 
     // ---- the divisions of emissivity.cpp:128-134 and the table ---------------------------------------------------------
     krapp::write_emissivity_table(out_name, Nr, bin_r.data(), bin_area.data(), &h[0], &h[Nr], &h[2 * (size_t) Nr], &h[3 * (size_t) Nr], &h[4 * (size_t) Nr]);
+
+    if (Nmu > 0) {
+        // count2 / count per mu bin (count: the radial histogram's, so a bin's bad-angle rays are missing from its row) and the mean mu over the
+        // rays that have an angle (the row sum of count2); 0/0 -> NaN in empty bins
+        const size_t plane = (size_t) Nr * Nmu;
+        TextOutput mu_out(mu_out_name.c_str());
+        for (int ir = 0; ir < Nr; ++ir) {
+            double row = 0;
+            for (int im = 0; im < Nmu; ++im) row += hmu[(size_t) ir * Nmu + im];
+            mu_out << bin_r[ir];
+            for (int im = 0; im < Nmu; ++im) mu_out << hmu[(size_t) ir * Nmu + im] / h[ir];
+            mu_out << hmu[2 * plane + ir] / row << endl;
+        }
+        mu_out.close();
+        cout << static_cast<long>(hmu[hmu.size() - 1]) << " of " << static_cast<long>(hmu[hmu.size() - 2]) << " binned rays have no incidence angle (bad-angle)" << endl;
+    }
 
     if (timing)
         cout << "timing: rays " << st.rays_traced << " steps " << st.steps_total << " | init+redshift_start " << ms_init << " ms | trace " << ms_trace

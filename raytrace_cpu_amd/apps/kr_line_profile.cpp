@@ -15,9 +15,12 @@
 //   emis_file                optional 7-column emissivity table (kr_emissivity / the reference's emissivity: r, area, rays, flux, emis,
 //                            redshift, time) used instead of powerlaw3: its emis column and its time column (the source->disc delay);
 //                            the r column must be log-spaced
+//   limb, limb_coeff = 2.06  optional limb law of the emission angle mu in the disc frame (line_mode = rays): 0 isotropic, 1 the weight
+//                            1 + limb_coeff mu (Laor), 2 log(1 + 1 / mu) (limb brightening); kr_limb_law in include/kr_trace.h
 // Every key may also be given as --key=value, which takes precedence over the file.
 // Output: TextOutput (width 20, precision 8), one row per bin: t_mid E_mid flux count (t_mid is nan without a time axis), a blank line
-// after each time bin.
+// after each time bin.  With `limb` given two comment rows "# LIMB" and "# LIMBCOEF" with their values come first; without it the file is
+// what it was before the key existed.
 #include <cmath>
 #include <cstdlib>
 #include <fstream>
@@ -113,6 +116,12 @@ try {
     const string mode = str("line_mode", "rays");
     if (mode != "rays" && mode != "pixels") throw invalid_argument("line_mode: expected rays or pixels, got '" + mode + "'");
     const string emis_file = str("emis_file", "");
+    const bool with_limb = has("limb");
+    kr_limb_law limb;
+    memset(&limb, 0, sizeof limb);
+    limb.law = (int32_t) num("limb", 0);
+    limb.coeff = num("limb_coeff", 2.06);
+    if (with_limb && mode != "rays") throw invalid_argument("limb: a limb law needs line_mode = rays (a pixel's mean has no emission angle)");
 
     const double dx = (xmax - x0) / Nx, dy = (ymax - y0) / Ny;
     const double r_isco = kerr_isco<double>(spin, +1);
@@ -171,7 +180,7 @@ try {
     krapp::Stopwatch clock;
     const int64_t n = kr_imageplane_count(&plane, nullptr, nullptr);
     if (n <= 0) throw runtime_error("empty ray grid");
-    const int64_t words = 2 * (int64_t) nt * ne + 2;
+    const int64_t words = 2 * (int64_t) nt * ne + 2 + (with_limb ? 1 : 0);      // the limb pass closes its histogram with bad_angle
     krapp::DeviceBuffer rays(n * (int64_t) sizeof(kr_ray_f64));
     krapp::DeviceBuffer line(words * (int64_t) sizeof(double));
     line.zero();
@@ -181,7 +190,9 @@ try {
     kr_stats st;
     krapp::check(kr_trace_dev_f64(&p, rays.get(), n, nullptr, &st), "trace");
     const double ms_trace = clock.lap_ms();
-    if (mode == "rays") {
+    if (with_limb) {
+        krapp::check(kr_post_line_limb_dev_f64(-spin, -1.0, 1, 0, 0, -1 * M_PI, M_PI, &lb, &limb, rays.get(), n, line.get(), nullptr), "redshift + range_phi + limb-law line");
+    } else if (mode == "rays") {
         krapp::check(kr_post_line_dev_f64(-spin, -1.0, 1, 0, 0, -1 * M_PI, M_PI, &lb, rays.get(), n, line.get(), nullptr), "redshift + range_phi + line");
     } else {
         const int64_t npix = (int64_t) img_nx * img_ny;
@@ -197,8 +208,13 @@ try {
 
     const int64_t nb = (int64_t) nt * ne;
     cout << static_cast<long>(h[nb * 2]) << (mode == "rays" ? " rays" : " pixels") << " on the disc, " << static_cast<long>(h[nb * 2 + 1]) << " binned" << endl;
+    if (with_limb) cout << static_cast<long>(h[nb * 2 + 2]) << " rays on the disc have no emission angle (bad-angle)" << endl;
     {
         TextOutput outfile(out_name);
+        if (with_limb) {
+            outfile << "# LIMB" << limb.law << endl;
+            outfile << "# LIMBCOEF" << limb.coeff << endl;
+        }
         const bool time_axis = !(nt == 1 && dt <= 0);
         for (int j = 0; j < nt; ++j) {
             const double t_mid = time_axis ? t0 + (j + 0.5) * dt : NAN;

@@ -108,6 +108,35 @@ class LineBins(C.Structure):
         return self
 
 
+class LimbLaw(C.Structure):
+    """kr_limb_law: the weight of the emission angle mu in the line.  law 0: 1; 1: 1 + coeff mu; 2: log(1 + 1 / mu) (include/kr_trace.h)."""
+    _fields_ = [("coeff", C.c_double), ("law", C.c_int32), ("pad", C.c_int32)]
+
+
+class MuBins(C.Structure):
+    """kr_mu_bins: nmu >= 1 equal bins of mu in [0, 1] (include/kr_trace.h)."""
+    _fields_ = [("nmu", C.c_int32), ("pad", C.c_int32)]
+
+
+assert C.sizeof(LimbLaw) == 16 and C.sizeof(MuBins) == 8
+
+LIMB_LAWS = {"isotropic": (0, 0.0), "laor": (1, 2.06), "brightening": (2, 0.0)}
+
+
+def limb_law(limb):
+    """A LimbLaw from (law, coeff) or one of the names of LIMB_LAWS."""
+    if isinstance(limb, LimbLaw):
+        return limb
+    if isinstance(limb, str):
+        if limb not in LIMB_LAWS:
+            raise ValueError(f"unknown limb law {limb!r}: one of {sorted(LIMB_LAWS)} or (law, coeff)")
+        limb = LIMB_LAWS[limb]
+    law, coeff = limb
+    out = LimbLaw()
+    out.law, out.coeff = int(law), float(coeff)
+    return out
+
+
 class CausticMap(C.Structure):
     """kr_caustic_map: what the critical-curve passes need besides the records (include/kr_trace.h has the per-pixel rules)."""
     _fields_ = [(n, C.c_double) for n in ("r_isco", "r_disc", "eps_x", "eps_y")] + [(n, C.c_int32) for n in ("nx", "ny", "bundles", "pad")]
@@ -272,6 +301,10 @@ PROTOTYPES = {
     "kr_reduce_line_dev_f64": (_int, [P(LineBins), _vp, _i64, _vp, _vp]),
     "kr_post_line_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, P(LineBins), _vp, _i64, _vp, _vp]),
     "kr_line_from_image_dev_f64": (_int, [P(LineBins), P(ImageBins), _vp, _vp, _vp]),
+    "kr_angles_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _vp, _i64, _vp, _vp]),
+    "kr_angles_f64": (_int, [_dbl, _dbl, _int, _int, _int, _vp, _i64, _vp]),
+    "kr_post_line_limb_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, P(LineBins), P(LimbLaw), _vp, _i64, _vp, _vp]),
+    "kr_post_emissivity_mu_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, P(EmisBins), P(MuBins), _vp, _i64, _vp, _vp, _vp]),
     "kr_bundles_init_emit_dev_f64": (_int, [P(ImagePlaneSpec), _dbl, _dbl, _int, _int, _vp, _i64, _vp]),
     "kr_post_caustic_disc_dev_f64": (_int, [_dbl, _int, P(CausticMap), _vp, _i64, _vp, _vp]),
     "kr_caustic_suppress_dev_f64": (_int, [P(CausticMap), _vp, _vp]),

@@ -1007,6 +1007,53 @@ int kr_reduce_line_f64(const kr_line_bins* b, const kr_ray_f64* rays, int64_t n,
     return rc2;
 }
 
+// ---- photon angles in the disc frame (kr_angles.hip; the limb-darkened line: kr_line.hip): everything is validated before anything touches a device ----
+int kr_angles_dev_f64(double spin, double V, int reverse, int projradius, int motion, const void* d, int64_t n, void* d_angles, void* st)
+{
+    const int rc = angles_validate(motion, "kr_angles");
+    if (rc != KR_OK) return rc;
+    return on_device(n >= 0 && (n == 0 || (d && d_angles)), "kr_angles: null argument or negative n",
+                     [&] { return angles_dev(spin, V, reverse, projradius, d, n, d_angles, (hipStream_t) st); });
+}
+
+int kr_angles_f64(double spin, double V, int reverse, int projradius, int motion, const kr_ray_f64* rays, int64_t n, double* angles)
+{
+    const int rc = angles_validate(motion, "kr_angles");
+    if (rc != KR_OK) return rc;
+    if (n < 0 || (n > 0 && (!rays || !angles))) return invalid("kr_angles: null argument or negative n");
+    return with_staged_rays((void*) rays, n, sizeof(kr_ray_f64), kReads, nullptr, [&](void* d) -> int {
+        if (n == 0) return KR_OK;
+        DeviceBuffer d_angles;
+        int rc2 = d_angles.alloc((size_t) n * 2 * sizeof(double));
+        if (rc2 != KR_OK) return rc2;
+        rc2 = angles_dev(spin, V, reverse, projradius, d, n, d_angles.p, nullptr);
+        if (rc2 != KR_OK) return rc2;
+        KR_HIP(hipMemcpy(angles, d_angles.p, (size_t) n * 2 * sizeof(double), hipMemcpyDeviceToHost));
+        return (int) KR_OK;
+    });
+}
+
+int kr_post_line_limb_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_line_bins* b, const kr_limb_law* law,
+                              void* d, int64_t n, void* d_line, void* st)
+{
+    int rc = line_validate(b, "kr_post_line_limb");
+    if (rc == KR_OK) rc = limb_validate(law, "kr_post_line_limb");
+    if (rc == KR_OK) rc = angles_validate(motion, "kr_post_line_limb");
+    if (rc != KR_OK) return rc;
+    return on_device(n >= 0 && d_line && (n == 0 || d), "kr_post_line_limb: null argument or negative n",
+                     [&] { return post_line_limb_dev(spin, V, reverse, projradius, lo, hi, b, law, d, n, d_line, (hipStream_t) st); });
+}
+
+int kr_post_emissivity_mu_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_emis_bins* b, const kr_mu_bins* mb,
+                                  void* d, int64_t n, void* d_hist, void* d_mu, void* st)
+{
+    int rc = emissivity_mu_validate(b, mb, "kr_post_emissivity_mu");
+    if (rc == KR_OK) rc = angles_validate(motion, "kr_post_emissivity_mu");
+    if (rc != KR_OK) return rc;
+    return on_device(n >= 0 && d_hist && d_mu && (n == 0 || d), "kr_post_emissivity_mu: null argument or negative n",
+                     [&] { return post_emissivity_mu_dev(spin, V, reverse, projradius, lo, hi, b, mb, d, n, d_hist, d_mu, (hipStream_t) st); });
+}
+
 // ---- critical-curve maps (kr_caustic.hip): everything is validated before anything touches a device --------------------------------------
 int kr_bundles_init_emit_dev_f64(const kr_imageplane* s, double eps_frac, double V, int reverse, int projradius, void* d, int64_t n, void* st)
 {

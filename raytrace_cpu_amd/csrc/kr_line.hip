@@ -4,6 +4,7 @@
 // the 2 nt ne + 2 doubles of the histogram leave the device.
 //   reduce_line_kernel      records after redshift(-1, reverse=1) -> line bins
 //   post_line_kernel        redshift + range_phi + line bins in one pass (the sibling of post_image_kernel; same per-ray functions)
+//   post_line_limb_kernel   the same with the weight times a limb law of the emission angle mu in the disc frame (kr_limb_law; frame_value)
 //   line_from_image_kernel  raw-sum image planes (kr_reduce_image_dev_f64 layout) -> line bins, per pixel
 // All three are streaming passes, one record / pixel per work-item.  The histogram is privatised per workgroup in LDS when it fits
 // kLineLdsWords (ds_add_f64), flushed with one global atomic per non-zero word; above that the items add into the global histogram directly.
@@ -22,7 +23,7 @@ namespace kr {
 namespace {
 
 // Per-workgroup LDS budget of the privatised histogram: 4096 doubles = 32 KiB, i.e. ne nt <= 2047.  Registers bound the residency first
-// (-Rpass-analysis=kernel-resource-usage, gfx950: post_line 194 VGPRs -> 2 waves / SIMD = 2 workgroups / CU, reduce_line 144 -> 3,
+// (-Rpass-analysis=kernel-resource-usage, gfx950: post_line and post_line_limb 194 VGPRs -> 2 waves / SIMD = 2 workgroups / CU, reduce_line 144 -> 3,
 // line_from_image 109 -> 4), and 4 x 32 KiB fit the CU's 160 KiB: the LDS never lowers the occupancy of any of the three; a 64-KiB
 // budget would halve line_from_image's.
 constexpr int kLineLdsWords = 4096;
@@ -39,9 +40,9 @@ struct LineDev {
 };
 
 // one item that passed the filter -> at most one bin.  PIXEL: x is the pixel's mean 1/g (E = line_energy x, w = emis x^g_index);
-// otherwise x is g (E = line_energy / g, w = emis g^-g_index).  Returns 1 if the item was binned.
-template <bool PIXEL>
-KR_DEV unsigned line_accumulate(double* acc, const LineDev& L, double r, double x, double t)
+// otherwise x is g (E = line_energy / g, w = emis g^-g_index).  LIMB: w times `limb`.  Returns 1 if the item was binned.
+template <bool PIXEL, bool LIMB = false>
+KR_DEV unsigned line_accumulate(double* acc, const LineDev& L, double r, double x, double t, double limb = 1)
 {
     const kr_line_bins& b = L.b;
     double emis, tt = 0;
@@ -57,7 +58,8 @@ KR_DEV unsigned line_accumulate(double* acc, const LineDev& L, double r, double 
         emis = powerlaw3(r, b.q1, b.rb1, b.q2, b.rb2, b.q3);
     }
     const double E = PIXEL ? b.line_energy * x : b.line_energy / x;
-    const double w = emis * (PIXEL ? kr_pow(x, b.g_index) : kr_pow(x, -1 * b.g_index));
+    const double w0 = emis * (PIXEL ? kr_pow(x, b.g_index) : kr_pow(x, -1 * b.g_index));
+    const double w = LIMB ? w0 * limb : w0;
     const double fe = b.log_e ? kr_log(E / b.e_min) / L.log_de : (E - b.e_min) / b.de;
     if (!(fe >= 0 && fe < b.ne)) return 0;              // NaN fails too
     int j = 0;
@@ -89,12 +91,15 @@ KR_DEV double* line_begin(double* lds, double* out, int words)
     return lds;
 }
 
-template <bool USE_LDS>
-KR_DEV void line_end(double* lds, double* out, int words, unsigned long long on_disc, unsigned long long binned)
+// the tallies close the histogram: on_disc, binned and -- the limb pass, whose `words` count one more -- bad_angle
+template <bool USE_LDS, bool LIMB = false>
+KR_DEV void line_end(double* lds, double* out, int words, unsigned long long on_disc, unsigned long long binned, unsigned long long bad_angle = 0)
 {
     double* acc = USE_LDS ? lds : out;
-    if (on_disc) atomicAdd(&acc[words - 2], (double) on_disc);
-    if (binned) atomicAdd(&acc[words - 1], (double) binned);
+    const int tallies = words - (LIMB ? 3 : 2);
+    if (on_disc) atomicAdd(&acc[tallies], (double) on_disc);
+    if (binned) atomicAdd(&acc[tallies + 1], (double) binned);
+    if (LIMB && bad_angle) atomicAdd(&acc[tallies + 2], (double) bad_angle);
     if (USE_LDS) {
         __syncthreads();
         for (int w = threadIdx.x; w < words; w += kBlock)
@@ -141,6 +146,38 @@ post_line_kernel(kr_ray_f64* __restrict__ rays, long long n, double spin, double
         binned += line_accumulate<false>(acc, L, v.r, g, ray->t);
     }
     line_end<USE_LDS>(lds, out, L.words, on_disc, binned);
+}
+
+// post_line_kernel with w *= limb(mu): g and mu come from ONE metric and momentum evaluation (frame_value; its E is redshift_value's recv to the
+// bit, so rays[] ends as after post_line_kernel).  A bad-angle ray that passed the filter counts in on_disc and bad_angle; under law 0 it is binned
+// like every other ray, under the other laws -- whose weight it would poison -- it is not.  Layout: post_line_kernel's, then bad_angle.
+template <bool USE_LDS>
+__global__ void __launch_bounds__(kBlock)
+post_line_limb_kernel(kr_ray_f64* __restrict__ rays, long long n, double spin, double V, int reverse, int projradius, double lo, double hi, LineDev L,
+                      kr_limb_law law, double* __restrict__ out)
+{
+    extern __shared__ double lds[];
+    const int words = L.words + 1;
+    double* acc = line_begin<USE_LDS>(lds, out, words);
+    unsigned long long on_disc = 0, binned = 0, bad_angle = 0;
+    KR_GRID_STRIDE(i, n) {
+        kr_ray_f64* ray = &rays[i];
+        const kr_ray_f64 v = geodesic_of(ray);
+        const int steps = ray->steps;
+        const Frame f = frame_value(v, spin, V, reverse, projradius);
+        const double g = frame_redshift(f, v.emit, reverse);
+        ray->redshift = g;
+        wrap_phi(ray, steps, lo, hi);
+        if (!line_filter(L.b, steps, v.r, v.theta, g)) continue;
+        on_disc++;
+        const double mu = frame_mu(f);
+        if (frame_bad_angle(f, mu)) {
+            bad_angle++;
+            if (law.law != 0) continue;
+        }
+        binned += line_accumulate<false, true>(acc, L, v.r, g, ray->t, limb_weight(law.law, law.coeff, mu));
+    }
+    line_end<USE_LDS, true>(lds, out, words, on_disc, binned, bad_angle);
 }
 
 // planes: [nrays | flux | r | phi | enshift | time | emis](npix each) + disc_count, raw sums (kr_reduce_image_dev_f64)
@@ -230,6 +267,19 @@ int post_line_dev(double spin, double V, int reverse, int projradius, int motion
     if (rc != KR_OK) return rc;
     KR_LAUNCH_LDS_OR_GLOBAL(post_line_kernel, L.words <= kLineLdsWords, grid_for(n, kBlock, kCapHist), L.words * sizeof(double), st, (kr_ray_f64*) d, (long long) n,
                             spin, V, reverse, projradius, motion, lo, hi, L, (double*) d_line);
+    return KR_OK;
+}
+
+int post_line_limb_dev(double spin, double V, int reverse, int projradius, double lo, double hi, const kr_line_bins* b, const kr_limb_law* law, void* d, int64_t n,
+                       void* d_line, hipStream_t st)
+{
+    if (n <= 0) return KR_OK;
+    TablePins pins;
+    LineDev L;
+    int rc = line_dev(b, pins, &L);
+    if (rc != KR_OK) return rc;
+    KR_LAUNCH_LDS_OR_GLOBAL(post_line_limb_kernel, L.words + 1 <= kLineLdsWords, grid_for(n, kBlock, kCapHist), (L.words + 1) * sizeof(double), st, (kr_ray_f64*) d,
+                            (long long) n, spin, V, reverse, projradius, lo, hi, L, *law, (double*) d_line);
     return KR_OK;
 }
 

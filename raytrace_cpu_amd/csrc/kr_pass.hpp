@@ -140,6 +140,16 @@ int reduce_line_dev(const kr_line_bins* b, const void* d, int64_t n, void* d_lin
 int post_line_dev(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_line_bins* b, void* d, int64_t n,
                   void* d_line, hipStream_t st);
 int line_from_image_dev(const kr_line_bins* b, const kr_image_bins* ib, const void* d_planes, void* d_line, hipStream_t st);
+int post_line_limb_dev(double spin, double V, int reverse, int projradius, double lo, double hi, const kr_line_bins* b, const kr_limb_law* law, void* d, int64_t n,
+                       void* d_line, hipStream_t st);
+// kr_angles.hip: the photon's angles in the disc frame (the observer of redshift_dev with motion 0; the validators refuse any other motion, a bad
+// limb law, and nr < 1 or nmu < 1)
+int angles_validate(int motion, const char* who);
+int limb_validate(const kr_limb_law* law, const char* who);
+int emissivity_mu_validate(const kr_emis_bins* b, const kr_mu_bins* mb, const char* who);
+int angles_dev(double spin, double V, int reverse, int projradius, const void* d, int64_t n, void* d_angles, hipStream_t st);
+int post_emissivity_mu_dev(double spin, double V, int reverse, int projradius, double lo, double hi, const kr_emis_bins* b, const kr_mu_bins* mb, void* d, int64_t n,
+                           void* d_hist, void* d_mu, hipStream_t st);
 // kr_caustic.hip.  The validators take the records the caller has (n; "n smaller than ..." is theirs to say)
 int caustic_validate(const kr_caustic_map* m, int64_t n, const char* who);
 int bundles_init_emit_dev(const kr_imageplane* s, int nx, int ny, double eps_frac, double V, int reverse, int projradius, void* d, int64_t n, hipStream_t st);

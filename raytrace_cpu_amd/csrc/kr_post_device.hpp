@@ -107,6 +107,55 @@ KR_DEV T redshift_value(const R& ray, T spin, T V_in, int reverse, int projradiu
     return reverse ? recv / ray.emit : ray.emit / recv;
 }
 
+// ---- the photon in the rest frame of the orbiting observer of redshift(V, ..., motion = 0): its momentum on the four legs of the reference's
+//      Tetrad (kerr.h:127-170: e_t, e1 along phi, e2 along theta, e3 along r), each by the reference's DotProduct (energy_dot above).  E is the
+//      `recv` of redshift_value -- the same metric, e_t and momentum expressions, hence the same bits -- and frame_redshift turns it into that
+//      function's return value; P_r = -g(p, e3), P_th = -g(p, e2), P_phi = -g(p, e1).  include/kr_trace.h (kr_angles_dev_f64) has the rule. ----
+struct Frame { double E, P_r, P_th, P_phi; };
+
+KR_DEV Frame frame_value(const kr_ray_f64& ray, double spin, double V_in, int reverse, int projradius)
+{
+    using T = double;
+    const T a = reverse ? -1 * spin : spin;
+    const T r = ray.r, theta = ray.theta;
+    const Metric<T> m = kerr_metric<T>(r, theta, a);
+    T V = V_in;
+    if (V == -1) V = keplerian_V<T>(a, r, theta, projradius != 0);
+    const T et[4] = {(1 / kr_sqrt(m.e2nu)) / kr_sqrt(1 - (V - m.omega) * (V - m.omega) * m.e2psi / m.e2nu), 0, 0,
+                     (1 / kr_sqrt(m.e2nu)) * V / kr_sqrt(1 - (V - m.omega) * (V - m.omega) * m.e2psi / m.e2nu)};
+    const T e1[4] = {(V - m.omega) * kr_sqrt(m.e2psi / m.e2nu) / kr_sqrt(m.e2nu - (V - m.omega) * (V - m.omega) * m.e2psi), 0, 0,
+                     (1 / kr_sqrt(m.e2nu * m.e2psi)) * (m.e2nu + V * m.omega * m.e2psi - m.omega * m.omega * m.e2psi) /
+                         kr_sqrt(m.e2nu - (V - m.omega) * (V - m.omega) * m.e2psi)};
+    const T e2[4] = {0, 0, 1 / kr_sqrt(m.rhosq), 0};
+    const T e3[4] = {0, kr_sqrt(m.delta / m.rhosq), 0, 0};
+    T p[4];
+    momentum<T>(p[0], p[1], p[2], p[3], ray.k, ray.h, ray.Q, ray.rdot_sign, ray.thetadot_sign, r, theta, spin);
+    if (reverse) { p[1] *= -1; p[2] *= -1; p[3] *= -1; }
+    Frame f;
+    f.E = energy_dot<T>(m, et, p);
+    f.P_phi = -1 * energy_dot<T>(m, e1, p);
+    f.P_th = -1 * energy_dot<T>(m, e2, p);
+    f.P_r = -1 * energy_dot<T>(m, e3, p);
+    return f;
+}
+
+KR_DEV double frame_redshift(const Frame& f, double emit, int reverse) { return reverse ? f.E / emit : emit / f.E; }
+
+// mu = |P_th| / E, the cosine of the angle to the disc normal; chi = atan2(P_phi, P_r), the azimuth about it (0 radially outward, +pi/2 along
+// the orbital motion).  A record is bad-angle when mu is not finite, mu > 1 or E <= 0: a ray the integrator stepped past a radial turning point
+// has rdot^2 < 0 under the sqrt(|.|) of the momentum, and its state is not a null vector.
+KR_DEV double frame_mu(const Frame& f) { return kr_abs(f.P_th) / f.E; }
+KR_DEV double frame_chi(const Frame& f) { return atan2(f.P_phi, f.P_r); }
+KR_DEV bool frame_bad_angle(const Frame& f, double mu) { return !__builtin_isfinite(mu) || mu > 1 || !(f.E > 0); }
+
+// the limb law of kr_limb_law at mu (law validated on the host: 0, 1 or 2)
+KR_DEV double limb_weight(int law, double coeff, double mu)
+{
+    if (law == 1) return 1 + coeff * mu;
+    if (law == 2) return kr_log(1 + 1 / mu);
+    return 1;
+}
+
 // ---- range_phi (raytracer.cpp:603-622): repeated +-2pi like the reference, so the result is bit-identical.  2 * M_PI is a double:
 //      in the float build each `phi -= 2 * M_PI` is a double subtraction rounded back to float, here as there. ----
 template <typename T>
