@@ -4,11 +4,13 @@ Every function goes through libkrtrace.so (HIP, gfx950).  Nothing here computes 
 falls back: if the library is missing or no GPU is visible the call raises KrError.
 """
 import ctypes as C
+import math
 
 import numpy as np
 
 from . import capi
 from .capi import KrError, Params, Stats  # noqa: F401
+from .devmem import DeviceScope
 
 _lib = None
 
@@ -159,6 +161,42 @@ def imageplane_init(spec):
     return rays
 
 
+def _rounded(word):
+    return int(round(float(word)))
+
+
+def _layout(planes, tallies, words=None):
+    """The one description of a result buffer: the planes [(name, shape), ..] one after the other, then one word per tally [(name, cast), ..] (name
+    None: a word without a name).  Without `words`: the buffer's length.  With words -- one buffer, or a stack of them along the leading axes -- the
+    dict: every plane a copy shaped leading axes + shape, every named tally cast(its word)."""
+    if words is None:
+        return sum(math.prod(shape) for _, shape in planes) + len(tallies)
+    words = np.asarray(words, dtype=np.float64)
+    lead, out, at = words.shape[:-1], {}, 0
+    for name, shape in planes:
+        size = math.prod(shape)
+        out[name] = words[..., at:at + size].reshape(lead + shape).copy()
+        at += size
+    out.update({name: cast(words[..., at + q]) for q, (name, cast) in enumerate(tallies) if name is not None})
+    return out
+
+
+def _emissivity_layout(bins, words=None):
+    return _layout([(k, (bins.nr,)) for k in ("count", "flux", "emis", "sum_redshift", "sum_time")], [("disc_count", int)], words)
+
+
+def emissivity_words(bins):
+    """Length of the radial histogram buffer of kr_reduce_emissivity_dev_f64 / kr_post_emissivity_*_dev_f64: five planes of nr and disc_count."""
+    return _emissivity_layout(bins)
+
+
+def emissivity_from_words(bins, words):
+    """The radial histogram buffer as the dict reduce_emissivity() returns (raw sums; count as int64)."""
+    out = _emissivity_layout(bins, words)
+    out["count"] = out["count"].astype(np.int64)
+    return out
+
+
 def reduce_emissivity(bins, rays):
     _rays_arg(rays, capi.RAY_F64)
     nr = bins.nr
@@ -183,37 +221,48 @@ def reduce_image(bins, rays):
     return out
 
 
+def _image_layout(nx, ny, words=None):
+    return _layout([(k, (nx * ny,)) for k in ("nrays", "flux", "r", "phi", "enshift", "time", "emis")], [("disc_count", _rounded)], words)
+
+
+def image_words(bins):
+    """Length of the image buffer of kr_reduce_image_dev_f64 / kr_post_image_dev_f64: seven planes of img_nx img_ny and disc_count."""
+    return _image_layout(bins.img_nx, bins.img_ny)
+
+
 def image_planes_from_words(words, nx, ny):
     """The device-resident reducers' result buffer (kr_reduce_image_dev_f64 / kr_post_image_dev_f64: 7 nx ny + 1 doubles,
     [nrays | flux | r | phi | enshift | time | emis | disc_count]) as the dict reduce_image() returns."""
-    npix = nx * ny
-    words = np.asarray(words)
-    out = {"nrays": np.rint(words[:npix]).astype(np.int32), "disc_count": int(round(float(words[7 * npix])))}
-    for q, k in enumerate(("flux", "r", "phi", "enshift", "time", "emis")):
-        out[k] = words[(q + 1) * npix:(q + 2) * npix]
-    return out
+    out = _image_layout(nx, ny, words)
+    return {"nrays": np.rint(out.pop("nrays")).astype(np.int32), "disc_count": out.pop("disc_count"), **out}
 
 
 RETURN_MAP_PLANES = ("count", "weight", "flux", "emis", "time")
 RETURN_MAP_SCALARS = ("ray_count", "return", "escape", "lost", "on_disc", "binned")
 
 
+def _return_map_layout(nr, casts=(None,) * 6, words=None):
+    return _layout([(k, (nr,)) for k in RETURN_MAP_PLANES], list(zip(RETURN_MAP_SCALARS, casts)), words)
+
+
 def return_map_words(m):
     """Length of the landing-map buffer: five planes of nr and six scalars (include/kr_trace.h, kr_return_map)."""
-    return 5 * m.nr + 6
+    return _return_map_layout(m.nr)
 
 
 def return_map_from_words(m, words):
     """The landing-map buffer as a dict: count / weight / flux / emis / time (nr raw sums each; count stays a double array of whole numbers),
     ray_count / return / escape / lost (weighted sums, as kr_reduce_return_f64 gives them), on_disc / binned (ints) and the nr + 1 bin edges."""
-    nr = m.nr
-    words = np.asarray(words, dtype=np.float64)
-    out = {k: words[q * nr:(q + 1) * nr].copy() for q, k in enumerate(RETURN_MAP_PLANES)}
-    out.update({k: float(words[5 * nr + q]) for q, k in enumerate(RETURN_MAP_SCALARS[:4])})
-    out.update({k: int(round(float(words[5 * nr + 4 + q]))) for q, k in enumerate(RETURN_MAP_SCALARS[4:])})
-    k = np.arange(nr + 1)
+    out = _return_map_layout(m.nr, [float] * 4 + [_rounded] * 2, words)
+    k = np.arange(m.nr + 1)
     out["r_edges"] = m.r_min * m.dr ** k if m.logbin else m.r_min + m.dr * k
     return out
+
+
+def return_radiation_from_words(nr, words):
+    """The landing-map buffers of several source radii, shaped (nsrc, return_map_words): the planes as (nsrc, nr) arrays and the six scalars as
+    arrays over the radii, as return_radiation() returns them."""
+    return _return_map_layout(nr, [np.copy] * 6, words)
 
 
 def reduce_return_map(m, rays):
@@ -264,7 +313,6 @@ def return_radiation(spin, source_radii, dcosalpha, dbeta, r_disc=500.0, r_esc=1
     return_records, the final records: a list of arrays, for tests).
     Returns the planes count / weight / flux / emis / time as (len(source_radii), nr) arrays, the six scalars as arrays over the radii, "stats" (the
     trace counters summed over the groups), "r_isco", "r_min", "dr", "r_edges"."""
-    import math
     L = lib()
     radii = [float(r) for r in source_radii]
     r_isco = L.kr_kerr_isco(spin, 1)
@@ -279,7 +327,7 @@ def return_radiation(spin, source_radii, dcosalpha, dbeta, r_disc=500.0, r_esc=1
     maps = [return_map_struct(r_isco, r_disc, r_esc, r_s, source_phi, r_min, dr, nr, logbin, gamma, plane_iso, limb, weight_norm) for r_s in radii]
     p = capi.default_params(spin)
     p.integrator, p.theta_max, p.r_max, p.stop_kind, p.flags = integrator, np.pi / 2, 1.1 * r_esc, capi.STOP_THETA, flags
-    nsrc, nw = len(radii), 5 * nr + 6
+    nsrc, nw = len(radii), _return_map_layout(nr)
     words = np.zeros((nsrc, nw))
     stats, records = {}, []
     if nsrc == 0:
@@ -287,12 +335,10 @@ def return_radiation(spin, source_radii, dcosalpha, dbeta, r_disc=500.0, r_esc=1
     else:
         slot = (max(counts) * capi.RAY_F64.itemsize + 255) // 256 * 256
         per_group = int(max(1, min(256, (device_info()["hbm_bytes"] // 4) // slot)))
-    d_rays, d_out = C.c_void_p(), C.c_void_p()
-    try:
+    with DeviceScope(L) as dev:
         if nsrc:
-            capi.check(L, L.kr_malloc(C.byref(d_out), nsrc * nw * 8), "kr_malloc")
-            capi.check(L, L.kr_memset(d_out, 0, nsrc * nw * 8), "kr_memset")
-            capi.check(L, L.kr_malloc(C.byref(d_rays), min(per_group, nsrc) * slot), "kr_malloc")
+            d_out = dev.zeros(words.nbytes)
+            d_rays = dev.alloc(min(per_group, nsrc) * slot)         # one slab, reused by every group
         for first in range(0, nsrc, per_group):
             idx = range(first, min(first + per_group, nsrc))
             k = len(idx)
@@ -310,18 +356,10 @@ def return_radiation(spin, source_radii, dcosalpha, dbeta, r_disc=500.0, r_esc=1
             capi.check(L, rc, "kr_post_return_map_batch")
             capi.check(L, L.kr_synchronize(None), "kr_synchronize")
             if return_records:
-                for q, j in enumerate(idx):
-                    rec = np.zeros(counts[j], dtype=capi.RAY_F64)
-                    capi.check(L, L.kr_memcpy_d2h(_ptr(rec), C.c_void_p(ptr_values[q]), rec.nbytes), "kr_memcpy_d2h")
-                    records.append(rec)
+                records += [dev.fetch(C.c_void_p(ptr_values[q]), counts[j], capi.RAY_F64) for q, j in enumerate(idx)]
         if nsrc:
-            capi.check(L, L.kr_memcpy_d2h(_ptr(words), d_out, words.nbytes), "kr_memcpy_d2h")
-    finally:
-        for d in (d_rays, d_out):
-            if d.value:
-                L.kr_free(d)
-    res = {k: words[:, q * nr:(q + 1) * nr].copy() for q, k in enumerate(RETURN_MAP_PLANES)}
-    res.update({k: words[:, 5 * nr + q].copy() for q, k in enumerate(RETURN_MAP_SCALARS)})
+            dev.fetch_into(d_out, words)
+    res = return_radiation_from_words(nr, words)
     e = np.arange(nr + 1)
     res.update(stats=stats, r_isco=r_isco, r_min=r_min, dr=dr, r_edges=r_min * dr ** e if logbin else r_min + dr * e, maps=maps, specs=specs)
     if return_records:
@@ -329,22 +367,23 @@ def return_radiation(spin, source_radii, dcosalpha, dbeta, r_disc=500.0, r_esc=1
     return res
 
 
+def _line_layout(bins, words=None):
+    return _layout([("count", (bins.nt, bins.ne)), ("flux", (bins.nt, bins.ne))], [("on_disc", _rounded), ("binned", _rounded)], words)
+
+
 def line_words(bins):
     """Length of the line histogram buffer: [count (nt x ne) | flux (nt x ne) | on_disc | binned] (include/kr_trace.h, kr_line_bins)."""
-    return 2 * bins.nt * bins.ne + 2
+    return _line_layout(bins)
 
 
 def line_from_words(bins, words):
     """The histogram buffer of the line entry points as a dict: count / flux of shape (nt, ne), on_disc, binned, and the bin edges
     (time_edges is None without a time axis)."""
-    ne, nt = bins.ne, bins.nt
-    words = np.asarray(words, dtype=np.float64)
-    k = np.arange(ne + 1)
-    e_edges = bins.e_min * bins.de ** k if bins.log_e else bins.e_min + bins.de * k
-    t_edges = None if (nt == 1 and bins.dt <= 0) else bins.t0 + bins.dt * np.arange(nt + 1)
-    return {"count": words[:nt * ne].reshape(nt, ne).copy(), "flux": words[nt * ne:2 * nt * ne].reshape(nt, ne).copy(),
-            "on_disc": int(round(float(words[2 * nt * ne]))), "binned": int(round(float(words[2 * nt * ne + 1]))),
-            "energy_edges": e_edges, "time_edges": t_edges}
+    out = _line_layout(bins, words)
+    k = np.arange(bins.ne + 1)
+    out["energy_edges"] = bins.e_min * bins.de ** k if bins.log_e else bins.e_min + bins.de * k
+    out["time_edges"] = None if (bins.nt == 1 and bins.dt <= 0) else bins.t0 + bins.dt * np.arange(bins.nt + 1)
+    return out
 
 
 def reduce_line(bins, rays):
@@ -388,12 +427,10 @@ def line_profile(imageplane_spec, params, bins, mode="rays", image_bins=None, li
         raise KrError("line_profile: empty ray grid")
     spin = -1 * imageplane_spec.spin                     # as stored by the Raytracer of an ImagePlane (imageplane.cpp:12)
     nw = line_words(bins) + (1 if law is not None else 0)
-    d_rays, d_line, d_planes = C.c_void_p(), C.c_void_p(), C.c_void_p()
     st = Stats()
-    try:
-        capi.check(L, L.kr_malloc(C.byref(d_rays), n * capi.RAY_F64.itemsize), "kr_malloc")
-        capi.check(L, L.kr_malloc(C.byref(d_line), nw * 8), "kr_malloc")
-        capi.check(L, L.kr_memset(d_line, 0, nw * 8), "kr_memset")
+    with DeviceScope(L) as dev:
+        d_rays = dev.alloc(n * capi.RAY_F64.itemsize)
+        d_line = dev.zeros(nw * 8)
         capi.check(L, L.kr_imageplane_init_emit_dev_f64(C.byref(imageplane_spec), 0, 1, 0.0, 1, 0, d_rays, n, None), "kr_imageplane_init_emit")
         capi.check(L, L.kr_trace_dev_f64(C.byref(params), d_rays, n, None, C.byref(st)), "kr_trace_dev")
         if law is not None:
@@ -402,21 +439,14 @@ def line_profile(imageplane_spec, params, bins, mode="rays", image_bins=None, li
             capi.check(L, L.kr_post_line_dev_f64(spin, -1.0, 1, 0, 0, -np.pi, np.pi, C.byref(bins), d_rays, n, d_line, None), "kr_post_line")
         else:
             ib = image_bins if image_bins is not None else default_image_bins(imageplane_spec, bins)
-            npw = 7 * ib.img_nx * ib.img_ny + 1
-            capi.check(L, L.kr_malloc(C.byref(d_planes), npw * 8), "kr_malloc")
-            capi.check(L, L.kr_memset(d_planes, 0, npw * 8), "kr_memset")
+            d_planes = dev.zeros(image_words(ib) * 8)
             capi.check(L, L.kr_post_image_dev_f64(spin, -1.0, 1, 0, 0, -np.pi, np.pi, C.byref(ib), d_rays, n, d_planes, None), "kr_post_image")
             capi.check(L, L.kr_line_from_image_dev_f64(C.byref(bins), C.byref(ib), d_planes, d_line, None), "kr_line_from_image")
-        out = np.zeros(nw)
-        capi.check(L, L.kr_memcpy_d2h(_ptr(out), d_line, nw * 8), "kr_memcpy_d2h")
-    finally:
-        for d in (d_rays, d_line, d_planes):
-            if d.value:
-                L.kr_free(d)
+        out = dev.fetch(d_line, nw)
     res = line_from_words(bins, out)
     res["stats"] = st.as_dict()
     if law is not None:
-        res["bad_angle"] = int(round(float(out[-1])))
+        res["bad_angle"] = _rounded(out[-1])
     return res
 
 
@@ -428,18 +458,11 @@ def arrival_angles(rays, spin, V=-1.0, reverse=0, projradius=0):
     L = lib()
     if isinstance(rays, tuple):
         d_ptr, n = rays
-        out = np.zeros(2 * n)
-        d_out = C.c_void_p()
-        if n > 0:
-            capi.check(L, L.kr_malloc(C.byref(d_out), out.nbytes), "kr_malloc")
-        try:
-            d = d_ptr if isinstance(d_ptr, C.c_void_p) else C.c_void_p(d_ptr)
+        d = d_ptr if isinstance(d_ptr, C.c_void_p) else C.c_void_p(d_ptr)
+        with DeviceScope(L) as dev:
+            d_out = dev.alloc(2 * n * 8) if n > 0 else C.c_void_p()
             capi.check(L, L.kr_angles_dev_f64(spin, V, int(reverse), int(projradius), 0, d, n, d_out, None), "kr_angles_dev")
-            if n > 0:
-                capi.check(L, L.kr_memcpy_d2h(_ptr(out), d_out, out.nbytes), "kr_memcpy_d2h")
-        finally:
-            if d_out.value:
-                L.kr_free(d_out)
+            out = dev.fetch(d_out, 2 * n)
     else:
         _rays_arg(rays, capi.RAY_F64)
         out = np.zeros(2 * len(rays))
@@ -447,9 +470,20 @@ def arrival_angles(rays, spin, V=-1.0, reverse=0, projradius=0):
     return out[0::2].copy(), out[1::2].copy()
 
 
+def _emissivity_mu_layout(bins, nmu, words=None):
+    return _layout([("count2", (bins.nr, nmu)), ("flux2", (bins.nr, nmu)), ("sum_mu", (bins.nr,))], [(k, int) for k in ("disc_count", "binned", "bad_angle")], words)
+
+
 def emissivity_mu_words(bins, nmu):
     """Length of the by-angle buffer of kr_post_emissivity_mu_dev_f64: [count2 (nr x nmu) | flux2 (nr x nmu) | sum_mu (nr) | disc_count, binned, bad_angle]."""
-    return (2 * nmu + 1) * bins.nr + 3
+    return _emissivity_mu_layout(bins, nmu)
+
+
+def emissivity_mu_from_words(bins, nmu, words):
+    """The by-angle buffer as a dict: count2 (int64) and flux2 of shape (nr, nmu), sum_mu (nr) and the tallies disc_count / binned / bad_angle."""
+    out = _emissivity_mu_layout(bins, nmu, words)
+    out["count2"] = out["count2"].astype(np.int64)
+    return out
 
 
 def emissivity_angles(pointsource_spec, params, bins, nmu, V=-1.0, reverse=0, projradius=0):
@@ -462,38 +496,25 @@ def emissivity_angles(pointsource_spec, params, bins, nmu, V=-1.0, reverse=0, pr
     n, _, _ = pointsource_count(pointsource_spec)
     if n <= 0:
         raise KrError("emissivity_angles: empty ray grid")
-    nr, nh, nm = bins.nr, 5 * bins.nr + 1, emissivity_mu_words(bins, nmu)
+    nh, nm = emissivity_words(bins), emissivity_mu_words(bins, nmu)
     mb = capi.MuBins(int(nmu), 0)
-    d_rays, d_hist, d_mu = C.c_void_p(), C.c_void_p(), C.c_void_p()
     st = Stats()
-    h, m = np.zeros(nh), np.zeros(max(nm, 0))
-    try:
-        if bins.nr > 0 and nmu >= 1:               # (the call below refuses the rest)
-            capi.check(L, L.kr_malloc(C.byref(d_hist), nh * 8), "kr_malloc")
-            capi.check(L, L.kr_memset(d_hist, 0, nh * 8), "kr_memset")
-            capi.check(L, L.kr_malloc(C.byref(d_mu), nm * 8), "kr_malloc")
-            capi.check(L, L.kr_memset(d_mu, 0, nm * 8), "kr_memset")
-        capi.check(L, L.kr_malloc(C.byref(d_rays), n * capi.RAY_F64.itemsize), "kr_malloc")
+    with DeviceScope(L) as dev:
+        sized = bins.nr > 0 and nmu >= 1           # (the pass below refuses the rest: it gets null buffers, no allocation of a negative size)
+        d_hist = dev.zeros(nh * 8) if sized else C.c_void_p()
+        d_mu = dev.zeros(nm * 8) if sized else C.c_void_p()
+        d_rays = dev.alloc(n * capi.RAY_F64.itemsize)
         capi.check(L, L.kr_pointsource_init_emit_dev_f64(C.byref(pointsource_spec), 0, 1, pointsource_spec.V, int(reverse), int(projradius), d_rays, n, None),
                    "kr_pointsource_init_emit")
         capi.check(L, L.kr_trace_dev_f64(C.byref(params), d_rays, n, None, C.byref(st)), "kr_trace_dev")
         capi.check(L, L.kr_post_emissivity_mu_dev_f64(pointsource_spec.spin, V, int(reverse), int(projradius), 0, -np.pi, np.pi, C.byref(bins), C.byref(mb), d_rays, n,
                                                       d_hist, d_mu, None), "kr_post_emissivity_mu")
-        capi.check(L, L.kr_memcpy_d2h(_ptr(h), d_hist, h.nbytes), "kr_memcpy_d2h")
-        capi.check(L, L.kr_memcpy_d2h(_ptr(m), d_mu, m.nbytes), "kr_memcpy_d2h")
-    finally:
-        for d in (d_rays, d_hist, d_mu):
-            if d.value:
-                L.kr_free(d)
-    hist = {"count": h[:nr].astype(np.int64), "flux": h[nr:2 * nr].copy(), "emis": h[2 * nr:3 * nr].copy(), "sum_redshift": h[3 * nr:4 * nr].copy(),
-            "sum_time": h[4 * nr:5 * nr].copy(), "disc_count": int(h[5 * nr])}
-    plane = nr * nmu
-    count2 = m[:plane].reshape(nr, nmu).astype(np.int64)
-    flux2 = m[plane:2 * plane].reshape(nr, nmu).copy()
+        hist = emissivity_from_words(bins, dev.fetch(d_hist, nh))
+        by_mu = emissivity_mu_from_words(bins, nmu, dev.fetch(d_mu, nm))
+    count2, flux2, sum_mu = (by_mu.pop(k) for k in ("count2", "flux2", "sum_mu"))
     with np.errstate(invalid="ignore", divide="ignore"):
-        mean_mu = m[2 * plane:2 * plane + nr] / count2.sum(axis=1)
-    tallies = {"disc_count": int(m[-3]), "binned": int(m[-2]), "bad_angle": int(m[-1]), "stats": st.as_dict()}
-    return hist, count2, flux2, mean_mu, tallies
+        mean_mu = sum_mu / count2.sum(axis=1)
+    return hist, count2, flux2, mean_mu, {**by_mu, "stats": st.as_dict()}
 
 
 CAUSTIC_PLANES = ("det_j", "sign_j", "order", "hit", "radius", "phi", "x_disc", "y_disc", "redshift")
@@ -508,38 +529,7 @@ def bundles_count(spec):
 
 def _map_words(m, planes, counts, words=None):
     """Length of a map buffer of len(planes) planes of nx ny and len(counts) counts; with `words`, that buffer as a dict instead."""
-    npix = m.nx * m.ny
-    if words is None:
-        return len(planes) * npix + len(counts)
-    words = np.asarray(words, dtype=np.float64)
-    out = {k: words[q * npix:(q + 1) * npix].reshape(m.nx, m.ny).copy() for q, k in enumerate(planes)}
-    out.update({k: int(round(float(words[len(planes) * npix + q]))) for q, k in enumerate(counts)})
-    return out
-
-
-def _resident_maps(imageplane_spec, p, n, nw, bundle_eps_frac, grid_init, passes):
-    """What the caustic maps share on the device: the 5-ray bundles (bundle_eps_frac > 0) or grid_init(d_rays) -> trace -> every pass(d_rays, d_maps),
-    each a (name, call) pair -> the nw map words read back.  Returns (words, stats)."""
-    L = lib()
-    d_rays, d_maps = C.c_void_p(), C.c_void_p()
-    st = Stats()
-    try:
-        capi.check(L, L.kr_malloc(C.byref(d_rays), n * capi.RAY_F64.itemsize), "kr_malloc")
-        capi.check(L, L.kr_malloc(C.byref(d_maps), nw * 8), "kr_malloc")
-        if bundle_eps_frac > 0:
-            capi.check(L, L.kr_bundles_init_emit_dev_f64(C.byref(imageplane_spec), bundle_eps_frac, 0.0, 1, 0, d_rays, n, None), "kr_bundles_init_emit")
-        else:
-            capi.check(L, grid_init[1](d_rays), grid_init[0])
-        capi.check(L, L.kr_trace_dev_f64(C.byref(p), d_rays, n, None, C.byref(st)), "kr_trace_dev")
-        for name, call in passes:
-            capi.check(L, call(d_rays, d_maps), name)
-        out = np.zeros(nw)
-        capi.check(L, L.kr_memcpy_d2h(_ptr(out), d_maps, nw * 8), "kr_memcpy_d2h")
-    finally:
-        for d in (d_rays, d_maps):
-            if d.value:
-                L.kr_free(d)
-    return out, st.as_dict()
+    return _layout([(k, (m.nx, m.ny)) for k in planes], [(k, _rounded) for k in counts], words)
 
 
 def caustic_words(cm):
@@ -585,12 +575,19 @@ def caustic_map(imageplane_spec, r_disc, integrator=capi.RK4, eps_frac=0.01, rk4
     cm.r_isco, cm.r_disc, cm.nx, cm.ny, cm.bundles = r_isco, r_disc, nx, ny, int(bundles)
     cm.eps_x, cm.eps_y = (eps_frac * imageplane_spec.dx, eps_frac * imageplane_spec.dy) if bundles else (imageplane_spec.dx, imageplane_spec.dy)
     spin = -1 * imageplane_spec.spin
-    out, stats = _resident_maps(imageplane_spec, p, n, caustic_words(cm), eps_frac if bundles else 0.0,
-                                ("kr_imageplane_init_emit", lambda d_rays: L.kr_imageplane_init_emit_dev_f64(C.byref(imageplane_spec), 0, 1, 0.0, 1, 0, d_rays, n, None)),
-                                (("kr_post_caustic_disc", lambda d_rays, d_maps: L.kr_post_caustic_disc_dev_f64(spin, 1, C.byref(cm), d_rays, n, d_maps, None)),
-                                 ("kr_caustic_suppress", lambda d_rays, d_maps: L.kr_caustic_suppress_dev_f64(C.byref(cm), d_maps, None))))
-    res = caustic_from_words(cm, out)
-    res.update(stats=stats, r_isco=r_isco, eps_x=cm.eps_x, eps_y=cm.eps_y)
+    st = Stats()
+    with DeviceScope(L) as dev:
+        d_rays = dev.alloc(n * capi.RAY_F64.itemsize)
+        d_maps = dev.alloc(caustic_words(cm) * 8)
+        if bundles:
+            capi.check(L, L.kr_bundles_init_emit_dev_f64(C.byref(imageplane_spec), eps_frac, 0.0, 1, 0, d_rays, n, None), "kr_bundles_init_emit")
+        else:
+            capi.check(L, L.kr_imageplane_init_emit_dev_f64(C.byref(imageplane_spec), 0, 1, 0.0, 1, 0, d_rays, n, None), "kr_imageplane_init_emit")
+        capi.check(L, L.kr_trace_dev_f64(C.byref(p), d_rays, n, None, C.byref(st)), "kr_trace_dev")
+        capi.check(L, L.kr_post_caustic_disc_dev_f64(spin, 1, C.byref(cm), d_rays, n, d_maps, None), "kr_post_caustic_disc")
+        capi.check(L, L.kr_caustic_suppress_dev_f64(C.byref(cm), d_maps, None), "kr_caustic_suppress")
+        res = caustic_from_words(cm, dev.fetch(d_maps, caustic_words(cm)))
+    res.update(stats=st.as_dict(), r_isco=r_isco, eps_x=cm.eps_x, eps_y=cm.eps_y)
     return res
 
 
@@ -640,7 +637,6 @@ def caustic_trace_params_source(imageplane_spec, kind, r_lim=None, z_s=None, r_m
 def source_map_struct(kind, nx, ny, eps_x, eps_y, bundles=False, incl_rad=0.0, phi0=0.0):
     """kr_source_map with the four sines and cosines of a FlatPlaneDestination evaluated by the C library (math.sin / math.cos), as the reference
     evaluates them in source_coords."""
-    import math
     sm = capi.SourceMap()
     sm.kind, sm.bundles, sm.nx, sm.ny, sm.eps_x, sm.eps_y = SOURCE_KINDS.index(kind), int(bundles), nx, ny, eps_x, eps_y
     sm.sin_incl, sm.cos_incl, sm.sin_phi0, sm.cos_phi0 = math.sin(incl_rad), math.cos(incl_rad), math.sin(phi0), math.cos(phi0)
@@ -665,11 +661,18 @@ def caustic_source_map(imageplane_spec, kind, r_lim=None, z_s=None, r_max=None, 
         raise KrError("caustic_source_map: empty ray grid")
     eps_x, eps_y = (eps_frac * imageplane_spec.dx, eps_frac * imageplane_spec.dy) if bundles else (imageplane_spec.dx, imageplane_spec.dy)
     sm = source_map_struct(kind, nx, ny, eps_x, eps_y, bundles, geo.get("incl_rad", 0.0), imageplane_spec.phi0)
-    out, stats = _resident_maps(imageplane_spec, p, n, source_caustic_words(sm), eps_frac if bundles else 0.0,
-                                ("kr_imageplane_init", lambda d_rays: L.kr_imageplane_init_dev_f64(C.byref(imageplane_spec), d_rays, n, None)),
-                                (("kr_post_caustic_source", lambda d_rays, d_maps: L.kr_post_caustic_source_dev_f64(C.byref(sm), d_rays, n, d_maps, None)),))
-    res = source_caustic_from_words(sm, out)
-    res.update(geo, stats=stats, eps_x=eps_x, eps_y=eps_y)
+    st = Stats()
+    with DeviceScope(L) as dev:
+        d_rays = dev.alloc(n * capi.RAY_F64.itemsize)
+        d_maps = dev.alloc(source_caustic_words(sm) * 8)
+        if bundles:
+            capi.check(L, L.kr_bundles_init_emit_dev_f64(C.byref(imageplane_spec), eps_frac, 0.0, 1, 0, d_rays, n, None), "kr_bundles_init_emit")
+        else:
+            capi.check(L, L.kr_imageplane_init_dev_f64(C.byref(imageplane_spec), d_rays, n, None), "kr_imageplane_init")
+        capi.check(L, L.kr_trace_dev_f64(C.byref(p), d_rays, n, None, C.byref(st)), "kr_trace_dev")
+        capi.check(L, L.kr_post_caustic_source_dev_f64(C.byref(sm), d_rays, n, d_maps, None), "kr_post_caustic_source")
+        res = source_caustic_from_words(sm, dev.fetch(d_maps, source_caustic_words(sm)))
+    res.update(geo, stats=st.as_dict(), eps_x=eps_x, eps_y=eps_y)
     return res
 
 
@@ -682,7 +685,6 @@ def path_spec(write_step=1, write_rmin=-1.0, write_rmax=-1.0):
 def rows_to_cartesian(rows, spin):
     """(t, r, theta, phi) rows -> (t, x, y, z) with cartesian() of the reference (src/include/kerr.h:41-48), evaluated on the host with the C
     library's sqrt / sin / cos through the math module (numpy's vectorised sin / cos need not round like it), one row at a time."""
-    import math
     out = np.empty_like(rows)
     a = float(spin)
     for i, (t, r, theta, phi) in enumerate(rows.tolist()):
@@ -748,7 +750,6 @@ def volume_map_struct(r0, rmax, nr, ntheta, nphi, logbin, V=-1.0, mode=0, revers
     dr = exp(log(rmax / r0) / (nr - 1)) or (rmax - r0) / (nr - 1), dtheta = (pi / 2) / (ntheta - 1), dphi = 2 pi / (nphi - 1) -- n cells of that
     width, so the last cell starts at the upper bound.  An axis of ONE cell (where the constructor divides by zero) spans the whole range:
     rmax / r0 or rmax - r0, pi / 2, 2 pi.  mode 0: one deposit per passage of a cell, 1: one per row; V, reverse, projradius, motion: as redshift()."""
-    import math
     m = capi.VolumeMap()
     m.r_min = float(r0)
     m.dr = math.exp(math.log(rmax / r0) / max(nr - 1, 1)) if logbin else (rmax - r0) / max(nr - 1, 1)
@@ -760,20 +761,19 @@ def volume_map_struct(r0, rmax, nr, ntheta, nphi, logbin, V=-1.0, mode=0, revers
     return m
 
 
+def _volume_layout(m, words=None):
+    return _layout([(k, (m.nr, m.ntheta, m.nphi)) for k in VOLUME_PLANES], [(k, _rounded) for k in VOLUME_TALLIES], words)
+
+
 def volume_words(m):
     """Length of a volume map buffer: three planes of nr ntheta nphi cells and four tallies (include/kr_trace.h, kr_trace_volume_*)."""
-    return 3 * m.nr * m.ntheta * m.nphi + 4
+    return _volume_layout(m)
 
 
 def volume_from_words(m, words):
     """The volume map buffer as a dict: count / time / redshift (raw sums, shaped (nr, ntheta, nphi); count stays a double array of whole numbers)
     and the tallies rows / in_grid / deposits / bad_g (ints)."""
-    shape = (m.nr, m.ntheta, m.nphi)
-    ncell = m.nr * m.ntheta * m.nphi
-    words = np.asarray(words, dtype=np.float64)
-    out = {k: words[q * ncell:(q + 1) * ncell].reshape(shape).copy() for q, k in enumerate(VOLUME_PLANES)}
-    out.update({k: int(round(float(words[3 * ncell + q]))) for q, k in enumerate(VOLUME_TALLIES)})
-    return out
+    return _volume_layout(m, words)
 
 
 def cell_volume(m, spin):
@@ -815,29 +815,20 @@ def volume_map(sources, params, m, reverse=0, projradius=0):
     NaN in cells no ray crossed), "num_rays" (rays traced) and "stats" (summed over the sources)."""
     L = lib()
     nw = volume_words(m)
-    words = np.zeros(nw)
-    stats, d_map = {}, C.c_void_p()
-    try:
-        capi.check(L, L.kr_malloc(C.byref(d_map), nw * 8), "kr_malloc")
-        capi.check(L, L.kr_memset(d_map, 0, nw * 8), "kr_memset")
+    stats = {}
+    with DeviceScope(L) as dev:
+        d_map = dev.zeros(nw * 8)
         for s in sources:
             n = pointsource_count(s)[0]
             if n <= 0:
                 raise KrError("volume_map: empty ray grid")
-            d_rays = C.c_void_p()
-            capi.check(L, L.kr_malloc(C.byref(d_rays), n * capi.RAY_F64.itemsize), "kr_malloc")
-            try:
+            with DeviceScope(L) as one:                          # a source's rays are freed before the next source's are allocated
+                d_rays = one.alloc(n * capi.RAY_F64.itemsize)
                 capi.check(L, L.kr_pointsource_init_emit_dev_f64(C.byref(s), 0, 1, s.V, int(reverse), int(projradius), d_rays, n, None), "kr_pointsource_init_emit")
                 st = Stats()
                 capi.check(L, L.kr_trace_volume_dev_f64(C.byref(params), C.byref(m), d_rays, n, d_map, None, C.byref(st)), "kr_trace_volume")
                 _add_stats(stats, st.as_dict())
-            finally:
-                L.kr_free(d_rays)
-        capi.check(L, L.kr_memcpy_d2h(_ptr(words), d_map, words.nbytes), "kr_memcpy_d2h")
-    finally:
-        if d_map.value:
-            L.kr_free(d_map)
-    res = volume_from_words(m, words)
+        res = volume_from_words(m, dev.fetch(d_map, nw))
     with np.errstate(invalid="ignore", divide="ignore"):
         res.update(mean_time=res["time"] / res["count"], mean_redshift=res["redshift"] / res["count"])
     res.update(num_rays=int(stats.get("rays_traced", 0)), stats=stats)
@@ -850,7 +841,6 @@ OBSERVE_TALLIES = ("rows", "in_grid", "lit", "contributions", "bad_g", "degenera
 def observe_bins_struct(en0, enmax, nen, logbin_en=False, t0=0.0, tmax=0.0, nt=0):
     """A kr_observe_bins of nen energy bins over [en0, enmax) -- den = (enmax - en0) / nen, or the ratio exp(log(enmax / en0) / nen) with
     logbin_en -- and nt time bins over [t0, tmax) (nt = 0: no response)."""
-    import math
     b = capi.ObserveBins()
     b.en0, b.t0 = float(en0), float(t0)
     b.den = math.exp(math.log(enmax / en0) / nen) if logbin_en else (enmax - en0) / nen
@@ -859,21 +849,20 @@ def observe_bins_struct(en0, enmax, nen, logbin_en=False, t0=0.0, tmax=0.0, nt=0
     return b
 
 
+def _observe_layout(b, words=None):
+    return _layout([("spectrum", (b.nen,)), ("hits", (b.nen,)), ("response", (b.nen, b.nt))], [(k, _rounded) for k in OBSERVE_TALLIES], words)
+
+
 def observe_words(b):
     """Length of an observe output buffer: spectrum and hits of nen bins, the nen x nt response and six tallies (include/kr_trace.h, kr_trace_observe_*)."""
-    return 2 * b.nen + b.nen * b.nt + 6
+    return _observe_layout(b)
 
 
 def observe_from_words(b, words):
     """The observe output buffer as a dict: "energy" (the nen + 1 bin edges), spectrum, hits (a double array of whole numbers), response shaped
     (nen, nt) and the tallies rows / in_grid / lit / contributions / bad_g / degenerate (ints)."""
-    words = np.asarray(words, dtype=np.float64)
-    nen, nt = b.nen, b.nt
-    i = np.arange(nen + 1, dtype=np.float64)
-    out = {"energy": b.en0 * np.power(b.den, i) if b.logbin_en else b.en0 + b.den * i,
-           "spectrum": words[:nen].copy(), "hits": words[nen:2 * nen].copy(), "response": words[2 * nen:2 * nen + nen * nt].reshape(nen, nt).copy()}
-    out.update({k: int(round(float(words[2 * nen + nen * nt + q]))) for q, k in enumerate(OBSERVE_TALLIES)})
-    return out
+    i = np.arange(b.nen + 1, dtype=np.float64)
+    return {"energy": b.en0 * np.power(b.den, i) if b.logbin_en else b.en0 + b.den * i, **_observe_layout(b, words)}
 
 
 def _cells_arg(a, m, name):
@@ -937,29 +926,18 @@ def volume_spectrum(sources, plane_spec, p_source, p_plane, m, bins, gamma=2.0, 
     mo.reverse = int(reverse)
     cells = [_cells_arg(emis, m, "emis"), _cells_arg(kappa, m, "kappa"), _cells_arg(delay, m, "delay")]
     nw = observe_words(bins)
-    words, image = np.zeros(nw), np.zeros(n)
-    d_rays, d_out, d_image = C.c_void_p(), C.c_void_p(), C.c_void_p()
-    d_cells = [C.c_void_p() for _ in cells]
     st = Stats()
-    try:
-        capi.check(L, L.kr_malloc(C.byref(d_rays), n * capi.RAY_F64.itemsize), "kr_malloc")
-        capi.check(L, L.kr_malloc(C.byref(d_out), nw * 8), "kr_malloc")
-        capi.check(L, L.kr_malloc(C.byref(d_image), n * 8), "kr_malloc")
-        capi.check(L, L.kr_memset(d_out, 0, nw * 8), "kr_memset")
-        for d, a in zip(d_cells, cells):
-            if a is not None:
-                capi.check(L, L.kr_malloc(C.byref(d), a.nbytes), "kr_malloc")
-                capi.check(L, L.kr_memcpy_h2d(d, _ptr(a), a.nbytes), "kr_memcpy_h2d")
+    with DeviceScope(L) as dev:
+        d_rays = dev.alloc(n * capi.RAY_F64.itemsize)
+        d_out = dev.alloc(nw * 8)
+        d_image = dev.alloc(n * 8)
+        dev.zero(d_out, nw * 8)
+        d_emis, d_kappa, d_delay = (dev.upload(a) if a is not None else None for a in cells)
         capi.check(L, L.kr_imageplane_init_emit_dev_f64(C.byref(plane_spec), 0, 1, 0.0, int(reverse), 0, d_rays, n, None), "kr_imageplane_init_emit")
-        capi.check(L, L.kr_trace_observe_dev_f64(C.byref(p_plane), C.byref(mo), C.byref(bins), d_cells[0], d_cells[1] if cells[1] is not None else None,
-                                                 d_cells[2], d_rays, n, d_out, d_image, None, C.byref(st)), "kr_trace_observe")
-        capi.check(L, L.kr_memcpy_d2h(_ptr(words), d_out, words.nbytes), "kr_memcpy_d2h")
-        capi.check(L, L.kr_memcpy_d2h(_ptr(image), d_image, image.nbytes), "kr_memcpy_d2h")
-    finally:
-        for d in [d_rays, d_out, d_image] + d_cells:
-            if d.value:
-                L.kr_free(d)
-    res = observe_from_words(bins, words)
+        capi.check(L, L.kr_trace_observe_dev_f64(C.byref(p_plane), C.byref(mo), C.byref(bins), d_emis, d_kappa, d_delay, d_rays, n, d_out, d_image, None, C.byref(st)),
+                   "kr_trace_observe")
+        res = observe_from_words(bins, dev.fetch(d_out, nw))
+        image = dev.fetch(d_image, n)
     res.update(image=image.reshape(nx, ny), map=vmap, emis=emis, delay=delay, stats=st.as_dict())
     return res
 
@@ -987,15 +965,13 @@ def trace_crossings(params, rays, spec):
     return {"rows": rows, "seen": seen, "rays": out, "stats": st.as_dict()}
 
 
-def _crossing_planes(L, bins, max_crossings, order, lo, hi, d_rays, d_rows, d_seen, n, d_planes):
-    """One order's image planes from device-resident crossings, through the zeroed scratch d_planes: the dict of image_planes_from_words."""
-    nw = 7 * bins.img_nx * bins.img_ny + 1
-    words = np.zeros(nw)
-    capi.check(L, L.kr_memset(d_planes, 0, nw * 8), "kr_memset")
+def _crossing_planes(dev, bins, max_crossings, order, lo, hi, d_rays, d_rows, d_seen, n, d_planes):
+    """One order's image planes from device-resident crossings, through the scratch d_planes (zeroed here): the dict of image_planes_from_words."""
+    L, nw = dev.lib, image_words(bins)
+    dev.zero(d_planes, nw * 8)
     capi.check(L, L.kr_reduce_crossing_image_dev_f64(C.byref(bins), int(max_crossings), int(order), lo, hi, d_rays, d_rows, d_seen, n, d_planes, None),
                "kr_reduce_crossing_image")
-    capi.check(L, L.kr_memcpy_d2h(_ptr(words), d_planes, nw * 8), "kr_memcpy_d2h")
-    return image_planes_from_words(words, bins.img_nx, bins.img_ny)
+    return image_planes_from_words(dev.fetch(d_planes, nw), bins.img_nx, bins.img_ny)
 
 
 def reduce_crossing_image(bins, rays, rows, seen, order, lo=-np.pi, hi=np.pi):
@@ -1008,19 +984,9 @@ def reduce_crossing_image(bins, rays, rows, seen, order, lo=-np.pi, hi=np.pi):
     n = len(rays)
     if rows.ndim != 3 or rows.shape[0] != n or rows.shape[2] != 4 or seen.shape != (n,):
         raise KrError("reduce_crossing_image: rows must be shaped (n, M, 4) and seen (n,)")
-    L = lib()
-    bufs = [C.c_void_p() for _ in range(4)]
-    d_rays, d_rows, d_seen, d_planes = bufs
-    try:
-        for d, a in ((d_rays, rays), (d_rows, rows), (d_seen, seen)):
-            capi.check(L, L.kr_malloc(C.byref(d), max(a.nbytes, 1)), "kr_malloc")
-            capi.check(L, L.kr_memcpy_h2d(d, _ptr(a), a.nbytes), "kr_memcpy_h2d")
-        capi.check(L, L.kr_malloc(C.byref(d_planes), (7 * bins.img_nx * bins.img_ny + 1) * 8), "kr_malloc")
-        return _crossing_planes(L, bins, rows.shape[1], order, lo, hi, d_rays, d_rows, d_seen, n, d_planes)
-    finally:
-        for d in bufs:
-            if d.value:
-                L.kr_free(d)
+    with DeviceScope(lib()) as dev:
+        d_rays, d_rows, d_seen = dev.upload(rays), dev.upload(rows), dev.upload(seen)
+        return _crossing_planes(dev, bins, rows.shape[1], order, lo, hi, d_rays, d_rows, d_seen, n, dev.alloc(image_words(bins) * 8))
 
 
 def order_images(imageplane_spec, params, bins, spec, orders, lo=-np.pi, hi=np.pi):
@@ -1034,25 +1000,16 @@ def order_images(imageplane_spec, params, bins, spec, orders, lo=-np.pi, hi=np.p
     if n <= 0:
         raise KrError("order_images: empty ray grid")
     M = int(spec.max_crossings)
-    bufs = [C.c_void_p() for _ in range(4)]
-    d_rays, d_rows, d_seen, d_planes = bufs
     st = Stats()
-    seen = np.zeros(n, dtype=np.int32)
     images = {}
-    try:
-        capi.check(L, L.kr_malloc(C.byref(d_rays), n * capi.RAY_F64.itemsize), "kr_malloc")
-        capi.check(L, L.kr_malloc(C.byref(d_rows), n * M * 32), "kr_malloc")
-        capi.check(L, L.kr_malloc(C.byref(d_seen), n * 4), "kr_malloc")
-        capi.check(L, L.kr_malloc(C.byref(d_planes), (7 * bins.img_nx * bins.img_ny + 1) * 8), "kr_malloc")
+    with DeviceScope(L) as dev:
+        d_rays, d_rows, d_seen = dev.alloc(n * capi.RAY_F64.itemsize), dev.alloc(n * M * 32), dev.alloc(n * 4)
+        d_planes = dev.alloc(image_words(bins) * 8)
         capi.check(L, L.kr_imageplane_init_emit_dev_f64(C.byref(imageplane_spec), 0, 1, 0.0, int(spec.reverse), 0, d_rays, n, None), "kr_imageplane_init_emit")
         capi.check(L, L.kr_trace_crossings_dev_f64(C.byref(params), C.byref(spec), d_rays, n, d_rows, d_seen, None, C.byref(st)), "kr_trace_crossings")
         for order in orders:
-            images[int(order)] = _crossing_planes(L, bins, M, order, lo, hi, d_rays, d_rows, d_seen, n, d_planes)
-        capi.check(L, L.kr_memcpy_d2h(_ptr(seen), d_seen, seen.nbytes), "kr_memcpy_d2h")
-    finally:
-        for d in bufs:
-            if d.value:
-                L.kr_free(d)
+            images[int(order)] = _crossing_planes(dev, bins, M, order, lo, hi, d_rays, d_rows, d_seen, n, d_planes)
+        seen = dev.fetch(d_seen, n, np.int32)
     return {"images": images, "seen_histogram": np.bincount(seen), "stats": st.as_dict()}
 
 
@@ -1087,18 +1044,10 @@ def healpix_vectors(order, first_pix=0, stride=1, count=None, unit_center=0):
     L = lib()
     if count is None:
         count = (12 * 4 ** int(order) - first_pix + stride - 1) // stride if 0 <= order <= 13 else 0
-    out = np.zeros((max(count, 0), 15))
-    d = C.c_void_p()
-    try:
-        if count > 0:
-            capi.check(L, L.kr_malloc(C.byref(d), out.nbytes), "kr_malloc")
+    with DeviceScope(L) as dev:
+        d = dev.alloc(count * 15 * 8) if count > 0 else C.c_void_p()
         capi.check(L, L.kr_healpix_vectors_dev_f64(int(order), int(unit_center), int(first_pix), int(stride), int(count), d, None), "kr_healpix_vectors")
-        if count > 0:
-            capi.check(L, L.kr_memcpy_d2h(_ptr(out), d, out.nbytes), "kr_memcpy_d2h")
-    finally:
-        if d.value:
-            L.kr_free(d)
-    return out
+        return dev.fetch(d, max(count, 0) * 15).reshape(-1, 15)
 
 
 def healpix_init(spec, emit=True, reverse=0, first=0, stride=1, count=None):
@@ -1108,21 +1057,13 @@ def healpix_init(spec, emit=True, reverse=0, first=0, stride=1, count=None):
     n, npix = healpix_count(spec)
     if count is None:
         count = spec.rays_per_pixel * ((npix - first + stride - 1) // stride)
-    rays = np.zeros(max(count, 0), dtype=capi.RAY_F64)
-    d = C.c_void_p()
-    try:
-        if count > 0:
-            capi.check(L, L.kr_malloc(C.byref(d), rays.nbytes), "kr_malloc")
+    with DeviceScope(L) as dev:
+        d = dev.alloc(count * capi.RAY_F64.itemsize) if count > 0 else C.c_void_p()
         if emit:
             capi.check(L, L.kr_healpix_init_emit_dev_f64(C.byref(spec), int(first), int(stride), int(reverse), d, int(count), None), "kr_healpix_init_emit")
         else:
             capi.check(L, L.kr_healpix_init_dev_f64(C.byref(spec), int(first), int(stride), d, int(count), None), "kr_healpix_init")
-        if count > 0:
-            capi.check(L, L.kr_memcpy_d2h(_ptr(rays), d, rays.nbytes), "kr_memcpy_d2h")
-    finally:
-        if d.value:
-            L.kr_free(d)
-    return rays
+        return dev.fetch(d, max(count, 0), capi.RAY_F64)
 
 
 def healpix_map_struct(npix, r_isco, r_disc, r_esc, theta_tol=0.0, source_r=0.0, source_phi=0.0, self_zone=0, rays_per_pixel=5, q1=3.0, rb1=4.0, q2=3.0,
@@ -1134,22 +1075,23 @@ def healpix_map_struct(npix, r_isco, r_disc, r_esc, theta_tol=0.0, source_r=0.0,
     return m
 
 
+def _healpix_map_layout(m, words=None):
+    return _layout([(k, (m.npix,)) for k in HEALPIX_PLANES], [(k, _rounded) for k in HEALPIX_TALLIES] + [(None, None)], words)
+
+
 def healpix_map_words(m):
     """Length of the fate-map buffer: seven planes of npix and six tallies."""
-    return 7 * m.npix + 6
+    return _healpix_map_layout(m)
 
 
 def healpix_map_from_words(m, words):
     """The fate-map buffer as a dict: the planes by name ("class" as int64), the tallies live / disc / escape / lost / self (ints) and the fractions
     of the live rays "disc_frac" / "escape_frac" / "lost_frac" / "self_frac" (the reference's Return / Escape / Lost, healpix_disc_source_photonfrac.cpp:111-113)."""
-    npix = m.npix
-    words = np.asarray(words, dtype=np.float64)
-    out = {k: words[q * npix:(q + 1) * npix].copy() for q, k in enumerate(HEALPIX_PLANES)}
+    out = _healpix_map_layout(m, words)
     out["class"] = np.rint(out["class"]).astype(np.int64)
-    out.update({k: int(round(float(words[7 * npix + q]))) for q, k in enumerate(HEALPIX_TALLIES)})
-    live = float(words[7 * npix])
+    tail = np.asarray(words, dtype=np.float64)[-6:-1]                      # live, then the four fates
     with np.errstate(invalid="ignore", divide="ignore"):
-        out.update({k + "_frac": float(np.float64(words[7 * npix + 1 + q]) / np.float64(live)) for q, k in enumerate(HEALPIX_TALLIES[1:])})
+        out.update(zip((k + "_frac" for k in HEALPIX_TALLIES[1:]), (tail[1:] / tail[0]).tolist()))
     return out
 
 
@@ -1171,30 +1113,18 @@ def healpix_map(spec, params, m, reverse=0, projradius=0, V=-1.0, motion=0, lo=-
     if m.npix != npix or m.rays_per_pixel != spec.rays_per_pixel:
         raise KrError("healpix_map: the map's npix / rays_per_pixel are not the source's")
     nw = healpix_map_words(m)
-    words = np.zeros(nw)
-    d_rays, d_out = C.c_void_p(), C.c_void_p()
     st = Stats()
-    rec = None
-    try:
-        capi.check(L, L.kr_malloc(C.byref(d_rays), n * capi.RAY_F64.itemsize), "kr_malloc")
-        capi.check(L, L.kr_malloc(C.byref(d_out), nw * 8), "kr_malloc")
-        capi.check(L, L.kr_memset(d_out, 0, nw * 8), "kr_memset")
+    with DeviceScope(L) as dev:
+        d_rays = dev.alloc(n * capi.RAY_F64.itemsize)
+        d_out = dev.zeros(nw * 8)
         capi.check(L, L.kr_healpix_init_emit_dev_f64(C.byref(spec), 0, 1, int(reverse), d_rays, n, None), "kr_healpix_init_emit")
         capi.check(L, L.kr_trace_dev_f64(C.byref(params), d_rays, n, None, C.byref(st)), "kr_trace_dev")
         capi.check(L, L.kr_post_healpix_map_dev_f64(params.spin, V, int(reverse), int(projradius), int(motion), lo, hi, C.byref(m), d_rays, n, 0, 1, d_out, None),
                    "kr_post_healpix_map")
-        capi.check(L, L.kr_memcpy_d2h(_ptr(words), d_out, words.nbytes), "kr_memcpy_d2h")
+        res = healpix_map_from_words(m, dev.fetch(d_out, nw))
+        res["stats"] = st.as_dict()
         if return_records:
-            rec = np.zeros(n, dtype=capi.RAY_F64)
-            capi.check(L, L.kr_memcpy_d2h(_ptr(rec), d_rays, rec.nbytes), "kr_memcpy_d2h")
-    finally:
-        for d in (d_rays, d_out):
-            if d.value:
-                L.kr_free(d)
-    res = healpix_map_from_words(m, words)
-    res["stats"] = st.as_dict()
-    if return_records:
-        res["records"] = rec
+            res["records"] = dev.fetch(d_rays, n, capi.RAY_F64)
     return res
 
 

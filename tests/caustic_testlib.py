@@ -1,5 +1,6 @@
 """TEST INFRASTRUCTURE: what the caustic test modules share besides the rules (tests/caustic_rules.py, tests/source_caustic_rules.py): the fixtures'
-names and planes, the coordinate bound of the CPU rule tests, the host mirror's bundle constructor, and the device-buffer helpers of the GPU tests."""
+names and planes, the coordinate bound of the CPU rule tests, the host mirror's bundle constructor, and the device bundles of the GPU tests
+(dev: a raytrace_cpu_amd.devmem.DeviceScope)."""
 import ctypes as C
 import math
 import os
@@ -30,33 +31,6 @@ def spec_of(g):
     return ol.imageplane_spec(g["dist"], g["incl"], g["x0"], g["xmax"], g["dx"], g["y0"], g["ymax"], g["dy"], g["spin"], phi0=g["phi0"], precision=g["precision"])
 
 
-class Dev:
-    """device buffers of one test, freed at the end"""
-
-    def __init__(self, L):
-        self.L, self.ptrs = L, []
-
-    def alloc(self, nbytes):
-        p = C.c_void_p()
-        capi.check(self.L, self.L.kr_malloc(C.byref(p), nbytes), "kr_malloc")
-        self.ptrs.append(p)
-        return p
-
-    def rays(self, d, n):
-        out = np.zeros(n, dtype=capi.RAY_F64)
-        capi.check(self.L, self.L.kr_memcpy_d2h(ol.ptr(out), d, out.nbytes), "d2h")
-        return out
-
-    def doubles(self, d, n):
-        out = np.zeros(n)
-        capi.check(self.L, self.L.kr_memcpy_d2h(ol.ptr(out), d, out.nbytes), "d2h")
-        return out
-
-    def close(self):
-        for p in self.ptrs:
-            self.L.kr_free(p)
-
-
 def build_bundle_dump(tmp_path):
     """tests/cpp/bundle_ctor_dump.cpp -> tmp_path, with the flags tests/cpp/Makefile uses for host_ctor_dump and absolute rpaths"""
     subprocess.run(["make", "-s", "-C", HOST], check=True)
@@ -78,7 +52,7 @@ def mirror_bundles(exe, tmp_path, g, eps_frac):
 
 
 def device_bundles(dev, g):
-    L, spec = dev.L, spec_of(g)
+    L, spec = dev.lib, spec_of(g)
     n, nx, ny = api.bundles_count(spec)
     assert (nx, ny) == (g["nx"], g["ny"]) and n == 5 * nx * ny
     d = dev.alloc(n * 144)
@@ -96,7 +70,7 @@ def bundle_identity_mask(dev, g, tmp_path):
     """[nx, ny]: True where all five device-built rays of the bundle carry the host mirror's bits in every field (emit against the oracle's
     redshift_start on the mirror's rays).  Also returns (device rays, mirror rays with emit)."""
     d, n = device_bundles(dev, g)
-    got = dev.rays(d, n)
+    got = dev.fetch(d, n, capi.RAY_F64)
     want = mirror_bundles(build_bundle_dump(tmp_path), tmp_path, g, g["eps_frac"])
     assert len(want) == n
     ol.oracle().kro_redshift_start_f64(-g["spin"], 0.0, 1, 0, ol.ptr(want), n)

@@ -19,13 +19,13 @@ import parity
 import reducer_rules as rr
 import test_gpu_line_profile as tlp
 from raytrace_cpu_amd import api, capi
+from raytrace_cpu_amd.devmem import DeviceScope
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 APPS = os.path.join(ROOT, "tests", "golden", "apps")
 PI = math.pi
-Dev = tlp.Dev
 
 
 def fixture_run(case, run):
@@ -45,11 +45,11 @@ def dev_angles(rays, spin, V, reverse, projradius):
     """kr_angles_dev_f64 on a device copy of `rays`: (mu, chi, the records after the call)."""
     L = api.lib()
     n = len(rays)
-    d, a = Dev.of(rays), Dev.of(np.full(2 * n, 7.0))
-    capi.check(L, L.kr_angles_dev_f64(spin, V, reverse, projradius, 0, d.p, n, a.p, None), "kr_angles_dev")
-    capi.check(L, L.kr_synchronize(None), "sync")
-    out, after = a.get(np.zeros(2 * n)), d.get(rays)
-    d.free(); a.free()
+    with DeviceScope(L) as dev:
+        d, a = dev.upload(rays), dev.upload(np.full(2 * n, 7.0))
+        capi.check(L, L.kr_angles_dev_f64(spin, V, reverse, projradius, 0, d, n, a, None), "kr_angles_dev")
+        capi.check(L, L.kr_synchronize(None), "sync")
+        out, after = dev.fetch(a, 2 * n), dev.fetch(d, n, rays.dtype)
     return out[0::2], out[1::2], after
 
 
@@ -94,11 +94,11 @@ def test_angles_at_the_edges_of_a_workgroup(krlib, n):
     part = np.ascontiguousarray(rays[first:first + n])
     if n == 0:
         L = api.lib()
-        a = Dev.of(np.full(4, 7.0))
-        capi.check(L, L.kr_angles_dev_f64(spin, post[0], post[1], post[2], 0, None, 0, a.p, None), "kr_angles_dev")
-        capi.check(L, L.kr_angles_dev_f64(spin, post[0], post[1], post[2], 0, None, 0, None, None), "kr_angles_dev")
-        assert (a.get(np.zeros(4)) == 7.0).all()
-        a.free()
+        with DeviceScope(L) as dev:
+            a = dev.upload(np.full(4, 7.0))
+            capi.check(L, L.kr_angles_dev_f64(spin, post[0], post[1], post[2], 0, None, 0, a, None), "kr_angles_dev")
+            capi.check(L, L.kr_angles_dev_f64(spin, post[0], post[1], post[2], 0, None, 0, None, None), "kr_angles_dev")
+            assert (dev.fetch(a, 4) == 7.0).all()
         mu, chi = api.arrival_angles(part, spin, *post)
         assert len(mu) == 0 and len(chi) == 0
         return
@@ -106,9 +106,8 @@ def test_angles_at_the_edges_of_a_workgroup(krlib, n):
     assert len(mu) == n and np.isfinite(mu).sum() >= 1
     # the host-array form and the api's two forms give the same bits
     h_mu, h_chi = api.arrival_angles(part, spin, *post)
-    d = Dev.of(part)
-    d_mu, d_chi = api.arrival_angles((d.p, n), spin, *post)
-    d.free()
+    with DeviceScope(api.lib()) as dev:
+        d_mu, d_chi = api.arrival_angles((dev.upload(part), n), spin, *post)
     for got in (h_mu, d_mu):
         assert got.tobytes() == np.ascontiguousarray(mu).tobytes()
     for got in (h_chi, d_chi):
@@ -121,15 +120,15 @@ def limb_line(b, law, rays, spin, post, calls=1):
     L = api.lib()
     V, reverse, projradius = post
     nw = api.line_words(b) + 1
-    h = Dev.zeros(nw)
-    for _ in range(calls):
-        d = Dev.of(rays)
-        capi.check(L, L.kr_post_line_limb_dev_f64(spin, V, reverse, projradius, 0, -PI, PI, C.byref(b), C.byref(law), d.p, len(rays), h.p, None), "kr_post_line_limb")
-        capi.check(L, L.kr_synchronize(None), "sync")
-        after = d.get(rays)
-        d.free()
-    words = h.get(np.zeros(nw))
-    h.free()
+    with DeviceScope(L) as dev:
+        h = dev.zeros(nw * 8)
+        for _ in range(calls):
+            with DeviceScope(L) as one:
+                d = one.upload(rays)
+                capi.check(L, L.kr_post_line_limb_dev_f64(spin, V, reverse, projradius, 0, -PI, PI, C.byref(b), C.byref(law), d, len(rays), h, None), "kr_post_line_limb")
+                capi.check(L, L.kr_synchronize(None), "sync")
+                after = one.fetch(d, len(rays), rays.dtype)
+        words = dev.fetch(h, nw)
     out = api.line_from_words(b, words[:-1])
     out["bad_angle"] = int(words[-1])
     out["words"] = words
@@ -139,11 +138,11 @@ def limb_line(b, law, rays, spin, post, calls=1):
 def plain_line(b, rays, spin, post):
     L = api.lib()
     V, reverse, projradius = post
-    d, h = Dev.of(rays), Dev.zeros(api.line_words(b))
-    capi.check(L, L.kr_post_line_dev_f64(spin, V, reverse, projradius, 0, -PI, PI, C.byref(b), d.p, len(rays), h.p, None), "kr_post_line")
-    capi.check(L, L.kr_synchronize(None), "sync")
-    after, words = d.get(rays), h.get(np.zeros(api.line_words(b)))
-    d.free(); h.free()
+    with DeviceScope(L) as dev:
+        d, h = dev.upload(rays), dev.zeros(api.line_words(b) * 8)
+        capi.check(L, L.kr_post_line_dev_f64(spin, V, reverse, projradius, 0, -PI, PI, C.byref(b), d, len(rays), h, None), "kr_post_line")
+        capi.check(L, L.kr_synchronize(None), "sync")
+        after, words = dev.fetch(d, len(rays), rays.dtype), dev.fetch(h, api.line_words(b))
     return api.line_from_words(b, words), after
 
 
@@ -218,15 +217,13 @@ def run_emissivity_mu(b, nmu, rays, spin, post):
     V, reverse, projradius = post
     n, nh, nm = len(rays), 5 * b.nr + 1, api.emissivity_mu_words(b, nmu)
     mb = capi.MuBins(nmu, 0)
-    d0, h0 = Dev.of(rays), Dev.zeros(nh)
-    capi.check(L, L.kr_post_emissivity_dev_f64(spin, V, reverse, projradius, 0, -PI, PI, C.byref(b), d0.p, n, h0.p, None), "kr_post_emissivity")
-    d1, h1, m1 = Dev.of(rays), Dev.zeros(nh), Dev.zeros(nm)
-    capi.check(L, L.kr_post_emissivity_mu_dev_f64(spin, V, reverse, projradius, 0, -PI, PI, C.byref(b), C.byref(mb), d1.p, n, h1.p, m1.p, None), "kr_post_emissivity_mu")
-    capi.check(L, L.kr_synchronize(None), "sync")
-    out = (h0.get(np.zeros(nh)), h1.get(np.zeros(nh)), m1.get(np.zeros(nm)), d0.get(rays), d1.get(rays))
-    for d in (d0, h0, d1, h1, m1):
-        d.free()
-    return out
+    with DeviceScope(L) as dev:
+        d0, h0 = dev.upload(rays), dev.zeros(nh * 8)
+        capi.check(L, L.kr_post_emissivity_dev_f64(spin, V, reverse, projradius, 0, -PI, PI, C.byref(b), d0, n, h0, None), "kr_post_emissivity")
+        d1, h1, m1 = dev.upload(rays), dev.zeros(nh * 8), dev.zeros(nm * 8)
+        capi.check(L, L.kr_post_emissivity_mu_dev_f64(spin, V, reverse, projradius, 0, -PI, PI, C.byref(b), C.byref(mb), d1, n, h1, m1, None), "kr_post_emissivity_mu")
+        capi.check(L, L.kr_synchronize(None), "sync")
+        return dev.fetch(h0, nh), dev.fetch(h1, nh), dev.fetch(m1, nm), dev.fetch(d0, n, rays.dtype), dev.fetch(d1, n, rays.dtype)
 
 
 def check_emissivity_mu(b, nmu, rays, spin, post, label):
@@ -285,13 +282,13 @@ def test_api_line_profile_with_limb_equals_the_c_abi_sequence(krlib):
     n = api.imageplane_count(spec)[0]
     law = capi.limb_law((1, 2.06))
     nw = api.line_words(b) + 1
-    d, h = Dev(n * 144), Dev.zeros(nw)
-    capi.check(L, L.kr_imageplane_init_emit_dev_f64(C.byref(spec), 0, 1, 0.0, 1, 0, d.p, n, None), "init")
-    capi.check(L, L.kr_trace_dev_f64(C.byref(p), d.p, n, None, None), "trace")
-    capi.check(L, L.kr_post_line_limb_dev_f64(-tlp.SPIN, -1.0, 1, 0, 0, -PI, PI, C.byref(b), C.byref(law), d.p, n, h.p, None), "kr_post_line_limb")
-    capi.check(L, L.kr_synchronize(None), "sync")
-    words = h.get(np.zeros(nw))
-    d.free(); h.free()
+    with DeviceScope(L) as dev:
+        d, h = dev.alloc(n * 144), dev.zeros(nw * 8)
+        capi.check(L, L.kr_imageplane_init_emit_dev_f64(C.byref(spec), 0, 1, 0.0, 1, 0, d, n, None), "init")
+        capi.check(L, L.kr_trace_dev_f64(C.byref(p), d, n, None, None), "trace")
+        capi.check(L, L.kr_post_line_limb_dev_f64(-tlp.SPIN, -1.0, 1, 0, 0, -PI, PI, C.byref(b), C.byref(law), d, n, h, None), "kr_post_line_limb")
+        capi.check(L, L.kr_synchronize(None), "sync")
+        words = dev.fetch(h, nw)
     want = api.line_from_words(b, words[:-1])
     assert got["binned"] > 30 and (got["on_disc"], got["binned"], got["bad_angle"]) == (want["on_disc"], want["binned"], int(words[-1]))
     assert np.array_equal(got["count"], want["count"])

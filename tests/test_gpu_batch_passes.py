@@ -10,6 +10,7 @@ import pytest
 import golden_cases as gc
 import oracle_lib as ol
 from raytrace_cpu_amd import api, capi
+from raytrace_cpu_amd.devmem import DeviceScope
 
 pytestmark = pytest.mark.gpu
 vp = C.c_void_p
@@ -30,14 +31,9 @@ def test_batched_source_and_return_passes_equal_the_single_calls(krlib):
     k = len(specs)
     counts = [api.pointsource_count(s)[0] for s in specs]
     counts[5] = 0                                                   # an empty launch in the middle of a chunk
-    bufs = [[C.c_void_p() for _ in range(k)] for _ in range(2)]
-    outs = [C.c_void_p() for _ in range(2)]
-    try:
-        for side in range(2):
-            for j in range(k):
-                capi.check(lib, lib.kr_malloc(C.byref(bufs[side][j]), max(counts[j], 1) * 144), "malloc")
-            capi.check(lib, lib.kr_malloc(C.byref(outs[side]), k * 32), "malloc")
-            capi.check(lib, lib.kr_memset(outs[side], 0, k * 32), "memset")
+    with DeviceScope(lib) as dev:
+        bufs = [[dev.alloc(max(counts[j], 1) * 144) for j in range(k)] for _ in range(2)]
+        outs = [dev.zeros(k * 32) for _ in range(2)]
         bins = (capi.ReturnBins * k)()
         for j, s in enumerate(specs):
             b = bins[j]
@@ -57,10 +53,7 @@ def test_batched_source_and_return_passes_equal_the_single_calls(krlib):
         capi.check(lib, lib.kr_synchronize(None), "sync")
 
         def fetch(d, n):
-            h = np.zeros(n, dtype=capi.RAY_F64)
-            if n:
-                capi.check(lib, lib.kr_memcpy_d2h(h.ctypes.data_as(vp), d, h.nbytes), "d2h")
-            return h
+            return dev.fetch(d, n, capi.RAY_F64)
         for j in range(k):
             assert not ol.rays_equal_bitwise(fetch(bufs[0][j], counts[j]), fetch(bufs[1][j], counts[j])), j
         # V = NULL takes the specs' own velocities
@@ -78,9 +71,7 @@ def test_batched_source_and_return_passes_equal_the_single_calls(krlib):
         out_ptrs = (C.c_void_p * k)(*[outs[1].value + 32 * j for j in range(k)])
         capi.check(lib, lib.kr_post_return_batch_dev_f64(k, -math.pi, math.pi, bins, ptrs, ns, out_ptrs, None), "post batch")
         capi.check(lib, lib.kr_synchronize(None), "sync")
-        t = [np.zeros(4 * k) for _ in range(2)]
-        for side in range(2):
-            capi.check(lib, lib.kr_memcpy_d2h(t[side].ctypes.data_as(vp), outs[side], t[side].nbytes), "d2h")
+        t = [dev.fetch(outs[side], 4 * k) for side in range(2)]
         assert t[0].reshape(k, 4)[:, 0].min() == 0 and (t[0].reshape(k, 4)[:, 0] > 0).sum() == k - 1          # the empty launch adds nothing
         np.testing.assert_allclose(t[1], t[0], rtol=1e-12, atol=0)
         for j in range(k):                                           # range_phi ran inside both: the records agree bit for bit afterwards too
@@ -89,13 +80,6 @@ def test_batched_source_and_return_passes_equal_the_single_calls(krlib):
         assert lib.kr_post_return_batch_dev_f64(k, -math.pi, math.pi, bins, ptrs, ns, None, None) == capi.KR_EINVAL
         assert lib.kr_pointsource_init_emit_batch_dev_f64(k, None, V, 0, 0, ptrs, ns, None) == capi.KR_EINVAL
         assert lib.kr_pointsource_init_emit_batch_dev_f64(0, None, None, 0, 0, None, None, None) == 0
-    finally:
-        for side in range(2):
-            for j in range(k):
-                if bufs[side][j]:
-                    lib.kr_free(bufs[side][j])
-            if outs[side]:
-                lib.kr_free(outs[side])
 
 
 def _churn_specs(count=400):
@@ -120,15 +104,12 @@ def test_source_tables_survive_churn_of_the_table_store(krlib):
     counts = [api.pointsource_count(s)[0] for s in specs]
     assert all(api.pointsource_count(s)[1:] == (5, 8) for s in specs) and 40 <= min(counts)
     offs = np.concatenate([[0], np.cumsum(counts)]) * 144
-    bufs = [C.c_void_p() for _ in range(3)]
-    try:
-        for b in bufs:
-            capi.check(lib, lib.kr_malloc(C.byref(b), int(offs[-1])), "malloc")
+    with DeviceScope(lib) as dev:
+        bufs = [dev.alloc(int(offs[-1])) for _ in range(3)]
 
         def fetch(side):
             capi.check(lib, lib.kr_synchronize(None), "sync")
-            h = np.zeros(sum(counts), dtype=capi.RAY_F64)
-            capi.check(lib, lib.kr_memcpy_d2h(h.ctypes.data_as(vp), bufs[side], h.nbytes), "d2h")
+            h = dev.fetch(bufs[side], sum(counts), capi.RAY_F64)
             return [h[offs[j] // 144:offs[j + 1] // 144] for j in range(k)]
         # the plain constructor, one call per source, against the oracle's: every live record bit for bit
         for j, s in enumerate(specs):
@@ -148,7 +129,3 @@ def test_source_tables_survive_churn_of_the_table_store(krlib):
         single, batch = fetch(1), fetch(2)
         for j in range(k):
             assert not ol.rays_equal_bitwise(single[j], batch[j]), j
-    finally:
-        for b in bufs:
-            if b:
-                lib.kr_free(b)

@@ -15,11 +15,12 @@ import numpy as np
 import pytest
 
 import caustic_rules as cr
-from caustic_testlib import FLOATS, INTS, OFF, SHAPES, Dev, bundle_identity_mask, device_bundles, same_bits, spec_of, synthetic
+from caustic_testlib import FLOATS, INTS, OFF, SHAPES, bundle_identity_mask, device_bundles, same_bits, spec_of, synthetic
 import fits_lite
 import oracle_lib as ol
 import parity
 from raytrace_cpu_amd import api, capi
+from raytrace_cpu_amd.devmem import DeviceScope
 from test_gpu_dropin_apps import COUNT_KEYS, NATIVE
 
 pytestmark = pytest.mark.gpu
@@ -35,13 +36,13 @@ STEPLIM = {"golden": 0, "off": 1000000}
 
 @pytest.fixture
 def dev(krlib):
-    d = Dev(krlib)
-    yield d
-    d.close()
+    """Device buffers of one test, freed at its end."""
+    with DeviceScope(krlib) as scope:
+        yield scope
 
 
 def device_grid(dev, g):
-    L, spec = dev.L, spec_of(g)
+    L, spec = dev.lib, spec_of(g)
     n, nx, ny = api.imageplane_count(spec)
     assert (nx, ny) == (g["nx"], g["ny"]) and n == nx * ny
     d = dev.alloc(n * 144)
@@ -61,7 +62,7 @@ def test_device_bundle_constructor_carries_the_reference_bits(dev, plane, tmp_pa
     n, nx, ny = len(got), g["nx"], g["ny"]
     # member 0 against the ImagePlane constructor
     d_grid, n_grid = device_grid(dev, g)
-    grid = dev.rays(d_grid, n_grid)
+    grid = dev.fetch(d_grid, n_grid, capi.RAY_F64)
     centre = got[0::5]
     assert len(centre) == n_grid
     away = ~((centre["alpha"] == 0) & (centre["beta"] == 0))
@@ -111,27 +112,26 @@ def test_map_kernels_match_the_rules_on_the_same_records(dev, plane, integrator,
     DET_J within 4 (c / eps) G; SIGN_J wherever |det| is not below that bound -- no such pixel may exist on the golden RK4 plane, at most 0.1 % of the
     hits elsewhere.  The suppression pass is also held, bit for bit, to the rules applied to the device's own maps before it.  rays[].redshift after
     the fused call equals kr_redshift_dest_dev_f64 on a copy."""
-    L, g, bundles = dev.L, PLANES[plane], mode == "bundles"
+    L, g, bundles = dev.lib, PLANES[plane], mode == "bundles"
     d, n = device_bundles(dev, g) if bundles else device_grid(dev, g)
     p, r_isco = api.caustic_trace_params(spec_of(g), g["r_disc"], capi.RK4 if integrator == "rk4" else capi.RK45, g["rk45_tol"], g["precision"], 0,
                                          STEPLIM[plane])
     st = capi.Stats()
     capi.check(L, L.kr_trace_dev_f64(C.byref(p), d, n, None, C.byref(st)), "kr_trace_dev")
-    traced = dev.rays(d, n)
-    d_copy = dev.alloc(n * 144)
-    capi.check(L, L.kr_memcpy_h2d(d_copy, ol.ptr(traced), traced.nbytes), "h2d")
+    traced = dev.fetch(d, n, capi.RAY_F64)
+    d_copy = dev.upload(traced)
     capi.check(L, L.kr_redshift_dest_dev_f64(-g["spin"], 1, d_copy, n, None), "kr_redshift_dest")
-    separate = dev.rays(d_copy, n)
+    separate = dev.fetch(d_copy, n, capi.RAY_F64)
 
     cm = caustic_struct(g, r_isco, bundles)
     nw = api.caustic_words(cm)
     d_maps = dev.alloc(nw * 8)
     capi.check(L, L.kr_memset(d_maps, 0xff, nw * 8), "kr_memset")        # the post call must WRITE every word
     capi.check(L, L.kr_post_caustic_disc_dev_f64(-g["spin"], 1, C.byref(cm), d, n, d_maps, None), "kr_post_caustic_disc")
-    before, counts_before = planes_of(cm, dev.doubles(d_maps, nw))
+    before, counts_before = planes_of(cm, dev.fetch(d_maps, nw))
     capi.check(L, L.kr_caustic_suppress_dev_f64(C.byref(cm), d_maps, None), "kr_caustic_suppress")
-    after, counts = planes_of(cm, dev.doubles(d_maps, nw))
-    fused = dev.rays(d, n)
+    after, counts = planes_of(cm, dev.fetch(d_maps, nw))
+    fused = dev.fetch(d, n, capi.RAY_F64)
     for f in fused.dtype.names:                                          # the fused pass leaves the records as the separate one does
         assert same_bits(fused[f], separate[f]).all(), f
 
@@ -244,7 +244,7 @@ def test_disc_maps_on_hand_made_records(dev, mode, shape):
     DET_J, SIGN_J wherever |det| is not below that bound (no such pixel may exist here); everything else equal.  Every word of the 0xFF-prefilled
     buffer is written; the records, trailing ones included, equal kr_redshift_dest_dev_f64 on a copy in every field; suppression is bit-exact against
     the rules on the device's own maps; the same words come out with the trailing records cut off."""
-    L, (nx, ny), bundles = dev.L, shape, mode == "bundles"
+    L, (nx, ny), bundles = dev.lib, shape, mode == "bundles"
     r_isco = L.kr_kerr_isco(HAND["spin"], 1)
     g = dict(HAND, nx=nx, ny=ny)
     cm = caustic_struct(g, r_isco, bundles)
@@ -254,20 +254,18 @@ def test_disc_maps_on_hand_made_records(dev, mode, shape):
     assert n == rpb * npix + 37
 
     def run(records):
-        d = dev.alloc(records.nbytes)
-        capi.check(L, L.kr_memcpy_h2d(d, ol.ptr(records), records.nbytes), "h2d")
+        d = dev.upload(records)
         d_maps = dev.alloc(nw * 8)
         capi.check(L, L.kr_memset(d_maps, 0xff, nw * 8), "kr_memset")
         capi.check(L, L.kr_post_caustic_disc_dev_f64(-HAND["spin"], 1, C.byref(cm), d, len(records), d_maps, None), "kr_post_caustic_disc")
-        before = dev.doubles(d_maps, nw)
+        before = dev.fetch(d_maps, nw)
         capi.check(L, L.kr_caustic_suppress_dev_f64(C.byref(cm), d_maps, None), "kr_caustic_suppress")
-        return before, dev.doubles(d_maps, nw), dev.rays(d, len(records))
+        return before, dev.fetch(d_maps, nw), dev.fetch(d, len(records), capi.RAY_F64)
 
     words_before, words_after, fused = run(rays)
-    d_copy = dev.alloc(rays.nbytes)
-    capi.check(L, L.kr_memcpy_h2d(d_copy, ol.ptr(rays), rays.nbytes), "h2d")
+    d_copy = dev.upload(rays)
     capi.check(L, L.kr_redshift_dest_dev_f64(-HAND["spin"], 1, d_copy, n, None), "kr_redshift_dest")
-    separate = dev.rays(d_copy, n)
+    separate = dev.fetch(d_copy, n, capi.RAY_F64)
     for f in fused.dtype.names:
         assert same_bits(fused[f], separate[f]).all(), f
     with np.errstate(invalid="ignore"):

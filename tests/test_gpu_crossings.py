@@ -24,9 +24,9 @@ import golden_cases as gc
 import parity
 import reducer_rules as rr
 from raytrace_cpu_amd import api, capi
+from raytrace_cpu_amd.devmem import DeviceScope
 
 pytestmark = pytest.mark.gpu
-vp = C.c_void_p
 
 
 def free_running(spin, integrator, r_max, steplim, **kw):
@@ -226,20 +226,12 @@ def test_image_of_one_order(krlib, order):
     parity.record_margin("test_image_of_one_order", f"ip16-order{order}", {"n_traced": int(img["disc_count"]), "n_bad": 0, "frac_bad": 0.0, "worst_ok": float(worst)},
                          allowed=parity.BIN_RTOL, bar="counts exact; worst_ok = worst |sum - rules| / per-bin sum of absolute terms")
     # it adds: a pre-filled buffer ends as the pre-fill plus the image
-    nw = 7 * bins.img_nx * bins.img_ny + 1
-    bufs = [vp() for _ in range(4)]
-    try:
-        for d, a in zip(bufs, (rays, np.ascontiguousarray(rows), seen, np.full(nw, PREFILL))):
-            capi.check(L, L.kr_malloc(C.byref(d), a.nbytes), "kr_malloc")
-            capi.check(L, L.kr_memcpy_h2d(d, a.ctypes.data_as(vp), a.nbytes), "h2d")
+    nw = api.image_words(bins)
+    with DeviceScope(L) as dev:
+        bufs = [dev.upload(a) for a in (rays, np.ascontiguousarray(rows), seen, np.full(nw, PREFILL))]
         capi.check(L, L.kr_reduce_crossing_image_dev_f64(C.byref(bins), rows.shape[1], order, -np.pi, np.pi, bufs[0], bufs[1], bufs[2], len(rays), bufs[3], None), "reduce")
         capi.check(L, L.kr_synchronize(None), "sync")
-        words = np.zeros(nw)
-        capi.check(L, L.kr_memcpy_d2h(words.ctypes.data_as(vp), bufs[3], words.nbytes), "d2h")
-    finally:
-        for d in bufs:
-            if d.value:
-                L.kr_free(d)
+        words = dev.fetch(bufs[3], nw)
     filled = api.image_planes_from_words(words - PREFILL, bins.img_nx, bins.img_ny)
     assert np.array_equal(filled["nrays"], want["nrays"]) and filled["disc_count"] == want["disc_count"]
     untouched = want["nrays"] == 0

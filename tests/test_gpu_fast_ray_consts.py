@@ -8,7 +8,6 @@ equals the trace, record for record and bit for bit; (b) the merged batch (trace
 trace; (c) the first claim alone -- a 5040-ray grid, no refills -- against the oracle under tests/parity.py's bars, nothing wider.
 
 The fast RK45 kernels do not carry the terms (their stages form them per evaluation, as before) and are not part of this file."""
-import ctypes as C
 import functools
 import math
 
@@ -18,6 +17,7 @@ import pytest
 import parity
 import step_control_cases as sc
 from raytrace_cpu_amd import api, capi
+from raytrace_cpu_amd.devmem import DeviceScope
 
 pytestmark = pytest.mark.gpu
 
@@ -89,21 +89,10 @@ def test_merged_batch_equals_the_single_trace(krlib, integrator, flags):
     want, st_want = single_trace(integrator, flags)
     inputs = [np.ascontiguousarray(rays), np.ascontiguousarray(rays[::-1])]
     p = params(integrator, flags, grid)
-    bufs = [C.c_void_p() for _ in inputs]
-    try:
-        for d, h in zip(bufs, inputs):
-            capi.check(krlib, krlib.kr_malloc(C.byref(d), h.nbytes), "kr_malloc")
-            capi.check(krlib, krlib.kr_memcpy_h2d(d, h.ctypes.data_as(C.c_void_p), h.nbytes), "h2d")
+    with DeviceScope(krlib) as dev:
+        bufs = [dev.upload(h) for h in inputs]
         stats = [api.trace_wait(t) for t in api.trace_batch_async([p, p], [d.value for d in bufs], [len(h) for h in inputs])]
-        outs = []
-        for d, h in zip(bufs, inputs):
-            out = np.zeros_like(h)
-            capi.check(krlib, krlib.kr_memcpy_d2h(out.ctypes.data_as(C.c_void_p), d, out.nbytes), "d2h")
-            outs.append(out)
-    finally:
-        for d in bufs:
-            if d:
-                krlib.kr_free(d)
+        outs = [dev.fetch(d, len(h), h.dtype) for d, h in zip(bufs, inputs)]
     for st in stats:
         assert st["rays_traced"] == st_want["rays_traced"] and st["steps_total"] == st_want["steps_total"]
     assert parity.same_records(outs[0], want)

@@ -14,7 +14,6 @@
     neighbourhood of the multiples of pi/2 down to single ulps -- against a digest taken from the library before the change
     (tests/golden/fast_sincos_digest.json), against the strict routine (2 ulp: kr_sincos.hpp's "<= ~1.5 ulp", the 2 ulp tests/test_sincos_accuracy.py holds the
     routine to on the host), and with the exact sign in every quadrant."""
-import ctypes as C
 import functools
 import hashlib
 import json
@@ -28,6 +27,7 @@ import parity
 import step_control_cases as sc
 import test_gpu_fast_ray_consts as frc
 from raytrace_cpu_amd import api, capi
+from raytrace_cpu_amd.devmem import DeviceScope
 from test_gpu_primitives import probe, ulps
 
 pytestmark = pytest.mark.gpu
@@ -81,21 +81,10 @@ def test_permuted_trace_equals_the_index_order_trace(krlib, integrator, flags):
 def batch_of(p, inputs):
     """One kr_trace_batch_async_f64 batch over `inputs` (host arrays): the traced arrays and the stats."""
     krlib = api.lib()
-    bufs = [C.c_void_p() for _ in inputs]
-    try:
-        for d, h in zip(bufs, inputs):
-            capi.check(krlib, krlib.kr_malloc(C.byref(d), h.nbytes), "kr_malloc")
-            capi.check(krlib, krlib.kr_memcpy_h2d(d, h.ctypes.data_as(C.c_void_p), h.nbytes), "h2d")
+    with DeviceScope(krlib) as dev:
+        bufs = [dev.upload(h) for h in inputs]
         stats = [api.trace_wait(t) for t in api.trace_batch_async([p] * len(inputs), [d.value for d in bufs], [len(h) for h in inputs])]
-        outs = []
-        for d, h in zip(bufs, inputs):
-            out = np.zeros_like(h)
-            capi.check(krlib, krlib.kr_memcpy_d2h(out.ctypes.data_as(C.c_void_p), d, out.nbytes), "d2h")
-            outs.append(out)
-    finally:
-        for d in bufs:
-            if d:
-                krlib.kr_free(d)
+        outs = [dev.fetch(d, len(h), h.dtype) for d, h in zip(bufs, inputs)]
     return outs, stats
 
 

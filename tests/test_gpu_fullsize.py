@@ -13,9 +13,17 @@ import golden_cases as gc
 import oracle_lib as ol
 import parity
 from raytrace_cpu_amd import api, capi
+from raytrace_cpu_amd.devmem import DeviceScope
 
 pytestmark = pytest.mark.gpu
 vp = C.c_void_p
+
+
+@pytest.fixture
+def dev(krlib):
+    """Device buffers of one test, freed at its end."""
+    with DeviceScope(krlib) as scope:
+        yield scope
 
 
 def _spec(d):
@@ -29,91 +37,85 @@ def _spec(d):
 
 
 @pytest.mark.parametrize("flags", [pytest.param(capi.FLAG_HYBRID, id="hybrid"), pytest.param(0, id="strict")])
-def test_full_size_properties(krlib, flags):
+def test_full_size_properties(krlib, dev, flags):
     lib = krlib
     spec = _spec(1.99 / (math.sqrt(1e7) - 1.0))
     n_beta = C.c_int32()
     n = lib.kr_pointsource_count(C.byref(spec), None, C.byref(n_beta))
     assert n >= 9_990_000
-    d_rays = vp()
-    capi.check(lib, lib.kr_malloc(C.byref(d_rays), n * 144), "malloc")
-    try:
-        capi.check(lib, lib.kr_pointsource_init_dev_f64(C.byref(spec), d_rays, n, None), "init")
-        capi.check(lib, lib.kr_redshift_start_dev_f64(gc.SPIN, 0.0, 0, 0, d_rays, n, None), "redshift_start")
-        rng = np.random.default_rng(20261004)
-        idx = np.sort(rng.choice(n, 3000, replace=False))
-        # plus rays of the beta = -pi column, which holds the longest rays of this grid (2e4 .. 3.5e4 steps)
-        idx = np.unique(np.concatenate([idx, np.arange(150, 800, 25) * n_beta.value]))
-        before = np.zeros(len(idx), dtype=capi.RAY_F64)
-        for k, i in enumerate(idx):
-            capi.check(lib, lib.kr_memcpy_d2h(before[k:k + 1].ctypes.data_as(vp), vp(d_rays.value + int(i) * 144), 144), "d2h")
-        p = capi.default_params(gc.SPIN)
-        p.integrator, p.r_max, p.flags = capi.RK4, 1000.0, flags
-        st = capi.Stats()
-        capi.check(lib, lib.kr_trace_dev_f64(C.byref(p), d_rays, n, None, C.byref(st)), "trace")
-        assert st.rays_traced > 9_990_000 and 4e9 < st.steps_total < 7e9
-        assert st.rays_strict_side == 3162      # either way exactly the beta = -pi column (one ray per row) goes to the side launch
-        after = np.zeros(len(idx), dtype=capi.RAY_F64)
-        for k, i in enumerate(idx):
-            capi.check(lib, lib.kr_memcpy_d2h(after[k:k + 1].ctypes.data_as(vp), vp(d_rays.value + int(i) * 144), 144), "d2h")
-        # (1) sample vs oracle on identical inputs
-        want, _ = ol.oracle_trace(p, before)
-        res = parity.compare_rays(after, want, rtol=parity.RAY_RTOL, steps_slack=0)
-        parity.record_margin("test_full_size_properties", f"ps1e7-rk4-flags{flags}-sample", res, parity.CHAOTIC_FRAC)
-        assert res["frac_bad"] <= parity.CHAOTIC_FRAC, res
-        longest = int(np.argmax(want["steps"]))
-        assert want["steps"][longest] > 20000 and after["steps"][longest] == want["steps"][longest]
-        # (4) every sampled ray ended in exactly one way
-        live = after["steps"] != -1
-        term = parity.terminal_bits(after["status"][live])
-        assert (np.isin(term, [capi.STATUS_DEST, capi.STATUS_HORIZON, capi.STATUS_RLIM])).all()
-        assert (after["steps"][live] > 0).all() and (after["r"][live] <= 1000.0 * (1 + 1e-6)).all() and (after["r"][live] > 1.0).all()
-        # (2) idempotence
-        st2 = capi.Stats()
-        capi.check(lib, lib.kr_trace_dev_f64(C.byref(p), d_rays, n, None, C.byref(st2)), "trace again")
-        # rays that ended on their stop surface or at r_max take no further step; a ray that ended inside the horizon still
-        # satisfies the loop condition and takes exactly one more step per call -- in the reference as well (raytracer.cpp:799, :917)
-        again = np.zeros(len(idx), dtype=capi.RAY_F64)
-        for k, i in enumerate(idx):
-            capi.check(lib, lib.kr_memcpy_d2h(again[k:k + 1].ctypes.data_as(vp), vp(d_rays.value + int(i) * 144), 144), "d2h")
-        sunk = (after["status"] & capi.STATUS_HORIZON) != 0
-        assert ol.rays_equal_bitwise(after[~sunk], again[~sunk]) == []
-        assert (again["steps"][sunk] == after["steps"][sunk] + 1).all()
-        assert st2.rays_traced == st.rays_traced and st2.steps_total < 1e-4 * st.steps_total
-        # (3) histogram additivity over ray-cyclic shards (strided init -> trace -> redshift -> reduce, per shard)
-        capi.check(lib, lib.kr_range_phi_dev_f64(-math.pi, math.pi, d_rays, n, None), "range_phi")
-        capi.check(lib, lib.kr_redshift_dev_f64(gc.SPIN, -1.0, 0, 0, 0, d_rays, n, None), "redshift")
-        bins = gc.emis_bins(spec, nr=100)
-        words = 5 * bins.nr + 1
-        d_hist = vp()
-        capi.check(lib, lib.kr_malloc(C.byref(d_hist), words * 8), "malloc")
-        whole = np.zeros(words)
+    d_rays = dev.alloc(n * 144)
+    capi.check(lib, lib.kr_pointsource_init_dev_f64(C.byref(spec), d_rays, n, None), "init")
+    capi.check(lib, lib.kr_redshift_start_dev_f64(gc.SPIN, 0.0, 0, 0, d_rays, n, None), "redshift_start")
+    rng = np.random.default_rng(20261004)
+    idx = np.sort(rng.choice(n, 3000, replace=False))
+    # plus rays of the beta = -pi column, which holds the longest rays of this grid (2e4 .. 3.5e4 steps)
+    idx = np.unique(np.concatenate([idx, np.arange(150, 800, 25) * n_beta.value]))
+    before = np.zeros(len(idx), dtype=capi.RAY_F64)
+    for k, i in enumerate(idx):
+        capi.check(lib, lib.kr_memcpy_d2h(before[k:k + 1].ctypes.data_as(vp), vp(d_rays.value + int(i) * 144), 144), "d2h")
+    p = capi.default_params(gc.SPIN)
+    p.integrator, p.r_max, p.flags = capi.RK4, 1000.0, flags
+    st = capi.Stats()
+    capi.check(lib, lib.kr_trace_dev_f64(C.byref(p), d_rays, n, None, C.byref(st)), "trace")
+    assert st.rays_traced > 9_990_000 and 4e9 < st.steps_total < 7e9
+    assert st.rays_strict_side == 3162      # either way exactly the beta = -pi column (one ray per row) goes to the side launch
+    after = np.zeros(len(idx), dtype=capi.RAY_F64)
+    for k, i in enumerate(idx):
+        capi.check(lib, lib.kr_memcpy_d2h(after[k:k + 1].ctypes.data_as(vp), vp(d_rays.value + int(i) * 144), 144), "d2h")
+    # (1) sample vs oracle on identical inputs
+    want, _ = ol.oracle_trace(p, before)
+    res = parity.compare_rays(after, want, rtol=parity.RAY_RTOL, steps_slack=0)
+    parity.record_margin("test_full_size_properties", f"ps1e7-rk4-flags{flags}-sample", res, parity.CHAOTIC_FRAC)
+    assert res["frac_bad"] <= parity.CHAOTIC_FRAC, res
+    longest = int(np.argmax(want["steps"]))
+    assert want["steps"][longest] > 20000 and after["steps"][longest] == want["steps"][longest]
+    # (4) every sampled ray ended in exactly one way
+    live = after["steps"] != -1
+    term = parity.terminal_bits(after["status"][live])
+    assert (np.isin(term, [capi.STATUS_DEST, capi.STATUS_HORIZON, capi.STATUS_RLIM])).all()
+    assert (after["steps"][live] > 0).all() and (after["r"][live] <= 1000.0 * (1 + 1e-6)).all() and (after["r"][live] > 1.0).all()
+    # (2) idempotence
+    st2 = capi.Stats()
+    capi.check(lib, lib.kr_trace_dev_f64(C.byref(p), d_rays, n, None, C.byref(st2)), "trace again")
+    # rays that ended on their stop surface or at r_max take no further step; a ray that ended inside the horizon still
+    # satisfies the loop condition and takes exactly one more step per call -- in the reference as well (raytracer.cpp:799, :917)
+    again = np.zeros(len(idx), dtype=capi.RAY_F64)
+    for k, i in enumerate(idx):
+        capi.check(lib, lib.kr_memcpy_d2h(again[k:k + 1].ctypes.data_as(vp), vp(d_rays.value + int(i) * 144), 144), "d2h")
+    sunk = (after["status"] & capi.STATUS_HORIZON) != 0
+    assert ol.rays_equal_bitwise(after[~sunk], again[~sunk]) == []
+    assert (again["steps"][sunk] == after["steps"][sunk] + 1).all()
+    assert st2.rays_traced == st.rays_traced and st2.steps_total < 1e-4 * st.steps_total
+    # (3) histogram additivity over ray-cyclic shards (strided init -> trace -> redshift -> reduce, per shard)
+    capi.check(lib, lib.kr_range_phi_dev_f64(-math.pi, math.pi, d_rays, n, None), "range_phi")
+    capi.check(lib, lib.kr_redshift_dev_f64(gc.SPIN, -1.0, 0, 0, 0, d_rays, n, None), "redshift")
+    bins = gc.emis_bins(spec, nr=100)
+    words = 5 * bins.nr + 1
+    d_hist = dev.alloc(words * 8)
+    whole = np.zeros(words)
+    capi.check(lib, lib.kr_memset(d_hist, 0, words * 8), "memset")
+    capi.check(lib, lib.kr_reduce_emissivity_dev_f64(C.byref(bins), d_rays, n, d_hist, None), "reduce")
+    capi.check(lib, lib.kr_memcpy_d2h(whole.ctypes.data_as(vp), d_hist, words * 8), "d2h")
+    parts = np.zeros(words)
+    shards = 4
+    for r in range(shards):
+        cnt = (n - r + shards - 1) // shards
+        capi.check(lib, lib.kr_pointsource_init_strided_dev_f64(C.byref(spec), r, shards, d_rays, cnt, None), "init shard")
+        capi.check(lib, lib.kr_redshift_start_dev_f64(gc.SPIN, 0.0, 0, 0, d_rays, cnt, None), "redshift_start")
+        capi.check(lib, lib.kr_trace_dev_f64(C.byref(p), d_rays, cnt, None, None), "trace shard")
+        capi.check(lib, lib.kr_range_phi_dev_f64(-math.pi, math.pi, d_rays, cnt, None), "range_phi")
+        capi.check(lib, lib.kr_redshift_dev_f64(gc.SPIN, -1.0, 0, 0, 0, d_rays, cnt, None), "redshift")
         capi.check(lib, lib.kr_memset(d_hist, 0, words * 8), "memset")
-        capi.check(lib, lib.kr_reduce_emissivity_dev_f64(C.byref(bins), d_rays, n, d_hist, None), "reduce")
-        capi.check(lib, lib.kr_memcpy_d2h(whole.ctypes.data_as(vp), d_hist, words * 8), "d2h")
-        parts = np.zeros(words)
-        shards = 4
-        for r in range(shards):
-            cnt = (n - r + shards - 1) // shards
-            capi.check(lib, lib.kr_pointsource_init_strided_dev_f64(C.byref(spec), r, shards, d_rays, cnt, None), "init shard")
-            capi.check(lib, lib.kr_redshift_start_dev_f64(gc.SPIN, 0.0, 0, 0, d_rays, cnt, None), "redshift_start")
-            capi.check(lib, lib.kr_trace_dev_f64(C.byref(p), d_rays, cnt, None, None), "trace shard")
-            capi.check(lib, lib.kr_range_phi_dev_f64(-math.pi, math.pi, d_rays, cnt, None), "range_phi")
-            capi.check(lib, lib.kr_redshift_dev_f64(gc.SPIN, -1.0, 0, 0, 0, d_rays, cnt, None), "redshift")
-            capi.check(lib, lib.kr_memset(d_hist, 0, words * 8), "memset")
-            capi.check(lib, lib.kr_reduce_emissivity_dev_f64(C.byref(bins), d_rays, cnt, d_hist, None), "reduce")
-            one = np.zeros(words)
-            capi.check(lib, lib.kr_memcpy_d2h(one.ctypes.data_as(vp), d_hist, words * 8), "d2h")
-            parts += one
-        capi.check(lib, lib.kr_free(d_hist), "free")
-        assert whole[5 * bins.nr] > 5e6
-        np.testing.assert_array_equal(parts[:bins.nr], whole[:bins.nr])           # counts: exact
-        np.testing.assert_allclose(parts, whole, rtol=1e-11)                      # sums: order of addition only
-    finally:
-        lib.kr_free(d_rays)
+        capi.check(lib, lib.kr_reduce_emissivity_dev_f64(C.byref(bins), d_rays, cnt, d_hist, None), "reduce")
+        one = np.zeros(words)
+        capi.check(lib, lib.kr_memcpy_d2h(one.ctypes.data_as(vp), d_hist, words * 8), "d2h")
+        parts += one
+    assert whole[5 * bins.nr] > 5e6
+    np.testing.assert_array_equal(parts[:bins.nr], whole[:bins.nr])           # counts: exact
+    np.testing.assert_allclose(parts, whole, rtol=1e-11)                      # sums: order of addition only
 
 
-def test_timed_pipeline_equals_the_cpu_reference_at_full_size(krlib):
+def test_timed_pipeline_equals_the_cpu_reference_at_full_size(krlib, dev):
     """BASELINE configs[1] end to end, the way bench.py TIMES it -- device PointSource constructor + redshift_start (fused), hybrid trace, fused
     range_phi + redshift + histogram, nothing leaving HBM but the 501 histogram words -- against the CPU on the same 3162^2 grid: the reference's
     own PointSource constructor and run_raytrace (oracle/_ref; the oracle port where it was not built) + the oracle's O(N) passes and reducer.
@@ -156,30 +158,24 @@ def test_timed_pipeline_equals_the_cpu_reference_at_full_size(krlib):
     dc = C.c_int64()
     o.kro_reduce_emissivity_f64(C.byref(bins), ol.ptr(cpu), len(cpu), ol.ptr(cnt), ol.ptr(flux), ol.ptr(emis), ol.ptr(sg), ol.ptr(stt), C.byref(dc))
     # device leg: the fused pipeline
-    d_rays, d_hist = vp(), vp()
     words = 5 * nr + 1
-    capi.check(lib, lib.kr_malloc(C.byref(d_rays), n * 144), "malloc")
-    capi.check(lib, lib.kr_malloc(C.byref(d_hist), words * 8), "malloc")
-    try:
-        capi.check(lib, lib.kr_pointsource_init_emit_dev_f64(C.byref(spec), 0, 1, 0.0, 0, 0, d_rays, n, None), "init_emit")
-        dev_init = np.zeros(n, dtype=capi.RAY_F64)
-        capi.check(lib, lib.kr_memcpy_d2h(dev_init.ctypes.data_as(vp), d_rays, n * 144), "d2h")
-        assert np.array_equal(dev_init["steps"], init["steps"])
-        fresh = init["steps"] == 0
-        for f in ("t", "r", "theta", "phi", "k", "h", "Q", "emit", "alpha", "beta"):
-            assert np.array_equal(dev_init[f][fresh].view(np.int64), init[f][fresh].view(np.int64)), f
-        for f in ("rdot_sign", "thetadot_sign", "status"):
-            assert np.array_equal(dev_init[f][fresh], init[f][fresh]), f
-        del dev_init
-        st = capi.Stats()
-        capi.check(lib, lib.kr_trace_dev_f64(C.byref(p), d_rays, n, None, C.byref(st)), "trace")
-        capi.check(lib, lib.kr_memset(d_hist, 0, words * 8), "memset")
-        capi.check(lib, lib.kr_post_emissivity_dev_f64(gc.SPIN, -1.0, 0, 0, 0, -math.pi, math.pi, C.byref(bins), d_rays, n, d_hist, None), "post")
-        h = np.zeros(words)
-        capi.check(lib, lib.kr_memcpy_d2h(h.ctypes.data_as(vp), d_hist, words * 8), "d2h")
-    finally:
-        lib.kr_free(d_rays)
-        lib.kr_free(d_hist)
+    d_rays, d_hist = dev.alloc(n * 144), dev.alloc(words * 8)
+    capi.check(lib, lib.kr_pointsource_init_emit_dev_f64(C.byref(spec), 0, 1, 0.0, 0, 0, d_rays, n, None), "init_emit")
+    dev_init = np.zeros(n, dtype=capi.RAY_F64)
+    capi.check(lib, lib.kr_memcpy_d2h(dev_init.ctypes.data_as(vp), d_rays, n * 144), "d2h")
+    assert np.array_equal(dev_init["steps"], init["steps"])
+    fresh = init["steps"] == 0
+    for f in ("t", "r", "theta", "phi", "k", "h", "Q", "emit", "alpha", "beta"):
+        assert np.array_equal(dev_init[f][fresh].view(np.int64), init[f][fresh].view(np.int64)), f
+    for f in ("rdot_sign", "thetadot_sign", "status"):
+        assert np.array_equal(dev_init[f][fresh], init[f][fresh]), f
+    del dev_init
+    st = capi.Stats()
+    capi.check(lib, lib.kr_trace_dev_f64(C.byref(p), d_rays, n, None, C.byref(st)), "trace")
+    capi.check(lib, lib.kr_memset(d_hist, 0, words * 8), "memset")
+    capi.check(lib, lib.kr_post_emissivity_dev_f64(gc.SPIN, -1.0, 0, 0, 0, -math.pi, math.pi, C.byref(bins), d_rays, n, d_hist, None), "post")
+    h = np.zeros(words)
+    capi.check(lib, lib.kr_memcpy_d2h(h.ctypes.data_as(vp), d_hist, words * 8), "d2h")
     assert st.rays_traced == int(live.sum())
     assert st.steps_total == cpu_steps, (st.steps_total, cpu_steps)
     assert np.array_equal(np.rint(h[:nr]).astype(np.int64), cnt)
@@ -227,7 +223,7 @@ def _fetch(lib, d_rays, idx):
     return out
 
 
-def test_imageplane_4097_full_size_properties(krlib):
+def test_imageplane_4097_full_size_properties(krlib, dev):
     """BASELINE configs[3]: the 4097 x 4097-ray observer plane (par_example/imageplane_disc_image.par_example geometry, img 4096^2),
     RK4, hybrid launch, whole pipeline in HBM.  The CPU cannot trace 1.7e7 rays inside a test, so:
       * a sample (random + the x = 0 column + the y = 0 row, where the ill-conditioned rays live) equals the oracle's trace of the
@@ -251,52 +247,46 @@ def test_imageplane_4097_full_size_properties(krlib):
     words = 7 * N * N + 1
     p = capi.default_params(-gc.SPIN)
     p.integrator, p.r_max, p.flags = capi.RK4, 1.1 * s.dist, capi.FLAG_HYBRID
-    d_rays, d_pl = vp(), vp()
-    capi.check(lib, lib.kr_malloc(C.byref(d_rays), total * 144), "malloc")
-    capi.check(lib, lib.kr_malloc(C.byref(d_pl), words * 8), "malloc")
-    try:
-        capi.check(lib, lib.kr_imageplane_init_emit_dev_f64(C.byref(s), 0, 1, 0.0, 1, 0, d_rays, total, None), "init_emit")
-        rng = np.random.default_rng(4097)
-        mid = N // 2                                      # x = 0 is grid column 2048, y = 0 grid row 2048
-        idx = np.unique(np.concatenate([rng.choice(total, 2500, replace=False), mid * ny + np.arange(0, ny, 16), np.arange(0, nx, 16) * ny + mid]))
-        before = _fetch(lib, d_rays, idx)
-        st = capi.Stats()
-        capi.check(lib, lib.kr_trace_dev_f64(C.byref(p), d_rays, total, None, C.byref(st)), "trace")
-        assert st.rays_traced == total
-        assert 8000 <= st.rays_strict_side <= 8400                           # the x = 0 column and the y = 0 row
-        after = _fetch(lib, d_rays, idx)
-        want, _ = ol.oracle_trace(p, before)
-        res = parity.compare_rays(after, want, rtol=parity.RAY_RTOL, steps_slack=0)
-        parity.record_margin("test_imageplane_4097_full_size_properties", "ip4097-rk4-hybrid-sample", res, parity.CHAOTIC_FRAC)
-        assert res["frac_bad"] <= parity.CHAOTIC_FRAC, res
-        live = after["steps"] != -1
-        assert (np.abs(after["steps"][live]) > 0).all()
-        # planes of the whole grid
-        capi.check(lib, lib.kr_memset(d_pl, 0, words * 8), "memset")
-        capi.check(lib, lib.kr_post_image_dev_f64(-gc.SPIN, -1.0, 1, 0, 0, -math.pi, math.pi, C.byref(b), d_rays, total, d_pl, None), "post")
-        whole = np.zeros(words)
-        capi.check(lib, lib.kr_memcpy_d2h(whole.ctypes.data_as(vp), d_pl, words * 8), "d2h")
-        # ... and accumulated over 4 ray-cyclic shards (rank r of 4 generates rays r, r + 4, ...; kr_post_image ADDS into d_planes)
-        capi.check(lib, lib.kr_memset(d_pl, 0, words * 8), "memset")
-        shards = 4
-        for r in range(shards):
-            cnt = (total - r + shards - 1) // shards
-            capi.check(lib, lib.kr_imageplane_init_emit_dev_f64(C.byref(s), r, shards, 0.0, 1, 0, d_rays, cnt, None), "init shard")
-            capi.check(lib, lib.kr_trace_dev_f64(C.byref(p), d_rays, cnt, None, None), "trace shard")
-            capi.check(lib, lib.kr_post_image_dev_f64(-gc.SPIN, -1.0, 1, 0, 0, -math.pi, math.pi, C.byref(b), d_rays, cnt, d_pl, None), "post shard")
-        parts = np.zeros(words)
-        capi.check(lib, lib.kr_memcpy_d2h(parts.ctypes.data_as(vp), d_pl, words * 8), "d2h")
-        npix = N * N
-        assert whole[-1] > 1e6 and whole[-1] == parts[-1] == whole[:npix].sum()        # disc_count == rays binned
-        np.testing.assert_array_equal(parts[:npix], whole[:npix])                        # ray count per pixel (hence the empty-pixel / NaN pattern)
-        assert 0 < (whole[:npix] == 0).sum() < npix
-        lit = whole[:npix] > 0
-        for k in range(1, 7):
-            np.testing.assert_allclose(parts[k * npix:(k + 1) * npix][lit], whole[k * npix:(k + 1) * npix][lit], rtol=1e-11, atol=1e-300)
-            assert (whole[k * npix:(k + 1) * npix][~lit] == 0).all()
-    finally:
-        lib.kr_free(d_rays)
-        lib.kr_free(d_pl)
+    d_rays, d_pl = dev.alloc(total * 144), dev.alloc(words * 8)
+    capi.check(lib, lib.kr_imageplane_init_emit_dev_f64(C.byref(s), 0, 1, 0.0, 1, 0, d_rays, total, None), "init_emit")
+    rng = np.random.default_rng(4097)
+    mid = N // 2                                      # x = 0 is grid column 2048, y = 0 grid row 2048
+    idx = np.unique(np.concatenate([rng.choice(total, 2500, replace=False), mid * ny + np.arange(0, ny, 16), np.arange(0, nx, 16) * ny + mid]))
+    before = _fetch(lib, d_rays, idx)
+    st = capi.Stats()
+    capi.check(lib, lib.kr_trace_dev_f64(C.byref(p), d_rays, total, None, C.byref(st)), "trace")
+    assert st.rays_traced == total
+    assert 8000 <= st.rays_strict_side <= 8400                           # the x = 0 column and the y = 0 row
+    after = _fetch(lib, d_rays, idx)
+    want, _ = ol.oracle_trace(p, before)
+    res = parity.compare_rays(after, want, rtol=parity.RAY_RTOL, steps_slack=0)
+    parity.record_margin("test_imageplane_4097_full_size_properties", "ip4097-rk4-hybrid-sample", res, parity.CHAOTIC_FRAC)
+    assert res["frac_bad"] <= parity.CHAOTIC_FRAC, res
+    live = after["steps"] != -1
+    assert (np.abs(after["steps"][live]) > 0).all()
+    # planes of the whole grid
+    capi.check(lib, lib.kr_memset(d_pl, 0, words * 8), "memset")
+    capi.check(lib, lib.kr_post_image_dev_f64(-gc.SPIN, -1.0, 1, 0, 0, -math.pi, math.pi, C.byref(b), d_rays, total, d_pl, None), "post")
+    whole = np.zeros(words)
+    capi.check(lib, lib.kr_memcpy_d2h(whole.ctypes.data_as(vp), d_pl, words * 8), "d2h")
+    # ... and accumulated over 4 ray-cyclic shards (rank r of 4 generates rays r, r + 4, ...; kr_post_image ADDS into d_planes)
+    capi.check(lib, lib.kr_memset(d_pl, 0, words * 8), "memset")
+    shards = 4
+    for r in range(shards):
+        cnt = (total - r + shards - 1) // shards
+        capi.check(lib, lib.kr_imageplane_init_emit_dev_f64(C.byref(s), r, shards, 0.0, 1, 0, d_rays, cnt, None), "init shard")
+        capi.check(lib, lib.kr_trace_dev_f64(C.byref(p), d_rays, cnt, None, None), "trace shard")
+        capi.check(lib, lib.kr_post_image_dev_f64(-gc.SPIN, -1.0, 1, 0, 0, -math.pi, math.pi, C.byref(b), d_rays, cnt, d_pl, None), "post shard")
+    parts = np.zeros(words)
+    capi.check(lib, lib.kr_memcpy_d2h(parts.ctypes.data_as(vp), d_pl, words * 8), "d2h")
+    npix = N * N
+    assert whole[-1] > 1e6 and whole[-1] == parts[-1] == whole[:npix].sum()        # disc_count == rays binned
+    np.testing.assert_array_equal(parts[:npix], whole[:npix])                        # ray count per pixel (hence the empty-pixel / NaN pattern)
+    assert 0 < (whole[:npix] == 0).sum() < npix
+    lit = whole[:npix] > 0
+    for k in range(1, 7):
+        np.testing.assert_allclose(parts[k * npix:(k + 1) * npix][lit], whole[k * npix:(k + 1) * npix][lit], rtol=1e-11, atol=1e-300)
+        assert (whole[k * npix:(k + 1) * npix][~lit] == 0).all()
 
 
 def test_return_radiation_full_size_properties(krlib):
@@ -389,7 +379,7 @@ def test_return_radiation_full_size_properties(krlib):
     assert resc["frac_bad"] <= parity.CHAOTIC_FRAC, resc
 
 
-def test_ray_buffer_beyond_4_gib(krlib):
+def test_ray_buffer_beyond_4_gib(krlib, dev):
     """One ray buffer of 3.3e7 records = 4.75 GB (BASELINE sizes stay under 2^32 bytes: 1e7 x 144 = 1.44e9, 4097^2 x 144 = 2.4e9), so that
     every kernel's record addressing is exercised past the 32-bit byte offset: source + redshift_start fused and separate, the hybrid trace,
     the fused post pass and the separate ones.  Checks: a sample of rays from BEYOND the 4 GiB mark equals the oracle's trace of the same
@@ -400,11 +390,9 @@ def test_ray_buffer_beyond_4_gib(krlib):
     n = lib.kr_pointsource_count(C.byref(spec), C.byref(n_rows), C.byref(n_beta))
     assert n * 144 > (1 << 32) + (1 << 28)
     first_beyond = (1 << 32) // 144 + 1
-    d_rays, d_hist = vp(), vp()
-    capi.check(lib, lib.kr_malloc(C.byref(d_rays), n * 144), "malloc")
     bins = gc.emis_bins(spec, nr=100)
     words = 5 * bins.nr + 1
-    capi.check(lib, lib.kr_malloc(C.byref(d_hist), words * 8), "malloc")
+    d_rays, d_hist = dev.alloc(n * 144), dev.alloc(words * 8)
 
     def fetch(idx):
         out = np.zeros(len(idx), dtype=capi.RAY_F64)
@@ -417,57 +405,53 @@ def test_ray_buffer_beyond_4_gib(krlib):
         capi.check(lib, lib.kr_memcpy_d2h(h.ctypes.data_as(vp), d_hist, words * 8), "d2h")
         return h
 
-    try:
-        rng = np.random.default_rng(4097)
-        idx = np.sort(rng.choice(np.arange(first_beyond, n), 1500, replace=False))
-        idx = np.unique(np.concatenate([idx, [first_beyond, n - 1, (n_rows.value - 2) * n_beta.value]]))      # + a beta = -pi ray (strict side launch)
-        p = capi.default_params(gc.SPIN)
-        p.integrator, p.r_max, p.flags = capi.RK4, 1000.0, capi.FLAG_HYBRID
-        # separate passes
-        capi.check(lib, lib.kr_pointsource_init_dev_f64(C.byref(spec), d_rays, n, None), "init")
-        capi.check(lib, lib.kr_redshift_start_dev_f64(gc.SPIN, 0.0, 0, 0, d_rays, n, None), "redshift_start")
-        before = fetch(idx)
-        st = capi.Stats()
-        capi.check(lib, lib.kr_trace_dev_f64(C.byref(p), d_rays, n, None, C.byref(st)), "trace")
-        assert st.rays_traced == n_rows.value * n_beta.value <= n          # (nRays is the truncated product of doubles: a few surplus slots stay unused)
-        assert st.rays_strict_side == n_rows.value                         # the beta = -pi column, one ray per row
-        after = fetch(idx)
-        want, _ = ol.oracle_trace(p, before)
-        res = parity.compare_rays(after, want, rtol=parity.RAY_RTOL, steps_slack=0)
-        parity.record_margin("test_ray_buffer_beyond_4_gib", "ps3.3e7-rk4-hybrid-sample-beyond-4GiB", res, parity.CHAOTIC_FRAC)
-        assert res["frac_bad"] <= parity.CHAOTIC_FRAC, res
-        assert (after["steps"][before["steps"] == 0] > 0).all()
-        capi.check(lib, lib.kr_range_phi_dev_f64(-math.pi, math.pi, d_rays, n, None), "range_phi")
-        capi.check(lib, lib.kr_redshift_dev_f64(gc.SPIN, -1.0, 0, 0, 0, d_rays, n, None), "redshift")
-        capi.check(lib, lib.kr_memset(d_hist, 0, words * 8), "memset")
-        capi.check(lib, lib.kr_reduce_emissivity_dev_f64(C.byref(bins), d_rays, n, d_hist, None), "reduce")
-        sep_rays, sep_hist = fetch(idx), histogram()
-        # the two passes vs the oracle on the sampled (device-traced) records: one evaluation deep
-        want_post = after.copy()
-        ol.oracle().kro_range_phi_f64(-math.pi, math.pi, ol.ptr(want_post), len(want_post))
-        ol.oracle().kro_redshift_f64(gc.SPIN, -1.0, 0, 0, 0, ol.ptr(want_post), len(want_post))
-        assert ol.rays_equal_bitwise(sep_rays, want_post, fields=["phi"]) == []
-        live = (after["steps"] > 0) & np.isfinite(want_post["redshift"])
-        np.testing.assert_allclose(sep_rays["redshift"][live], want_post["redshift"][live], rtol=1e-10)
-        # fused passes over the same buffer
-        capi.check(lib, lib.kr_pointsource_init_emit_dev_f64(C.byref(spec), 0, 1, 0.0, 0, 0, d_rays, n, None), "init_emit")
-        assert ol.rays_equal_bitwise(fetch(idx), before) == []
-        st2 = capi.Stats()
-        capi.check(lib, lib.kr_trace_dev_f64(C.byref(p), d_rays, n, None, C.byref(st2)), "trace")
-        assert (st2.rays_traced, st2.steps_total, st2.rays_strict_side) == (st.rays_traced, st.steps_total, st.rays_strict_side)
-        capi.check(lib, lib.kr_memset(d_hist, 0, words * 8), "memset")
-        capi.check(lib, lib.kr_post_emissivity_dev_f64(gc.SPIN, -1.0, 0, 0, 0, -math.pi, math.pi, C.byref(bins), d_rays, n, d_hist, None), "post")
-        fused_rays, fused_hist = fetch(idx), histogram()
-        assert ol.rays_equal_bitwise(fused_rays, sep_rays) == []
-        assert sep_hist[5 * bins.nr] > 0.5 * n
-        np.testing.assert_array_equal(fused_hist[:bins.nr], sep_hist[:bins.nr])
-        np.testing.assert_allclose(fused_hist, sep_hist, rtol=1e-11)
-    finally:
-        lib.kr_free(d_rays)
-        lib.kr_free(d_hist)
+    rng = np.random.default_rng(4097)
+    idx = np.sort(rng.choice(np.arange(first_beyond, n), 1500, replace=False))
+    idx = np.unique(np.concatenate([idx, [first_beyond, n - 1, (n_rows.value - 2) * n_beta.value]]))      # + a beta = -pi ray (strict side launch)
+    p = capi.default_params(gc.SPIN)
+    p.integrator, p.r_max, p.flags = capi.RK4, 1000.0, capi.FLAG_HYBRID
+    # separate passes
+    capi.check(lib, lib.kr_pointsource_init_dev_f64(C.byref(spec), d_rays, n, None), "init")
+    capi.check(lib, lib.kr_redshift_start_dev_f64(gc.SPIN, 0.0, 0, 0, d_rays, n, None), "redshift_start")
+    before = fetch(idx)
+    st = capi.Stats()
+    capi.check(lib, lib.kr_trace_dev_f64(C.byref(p), d_rays, n, None, C.byref(st)), "trace")
+    assert st.rays_traced == n_rows.value * n_beta.value <= n          # (nRays is the truncated product of doubles: a few surplus slots stay unused)
+    assert st.rays_strict_side == n_rows.value                         # the beta = -pi column, one ray per row
+    after = fetch(idx)
+    want, _ = ol.oracle_trace(p, before)
+    res = parity.compare_rays(after, want, rtol=parity.RAY_RTOL, steps_slack=0)
+    parity.record_margin("test_ray_buffer_beyond_4_gib", "ps3.3e7-rk4-hybrid-sample-beyond-4GiB", res, parity.CHAOTIC_FRAC)
+    assert res["frac_bad"] <= parity.CHAOTIC_FRAC, res
+    assert (after["steps"][before["steps"] == 0] > 0).all()
+    capi.check(lib, lib.kr_range_phi_dev_f64(-math.pi, math.pi, d_rays, n, None), "range_phi")
+    capi.check(lib, lib.kr_redshift_dev_f64(gc.SPIN, -1.0, 0, 0, 0, d_rays, n, None), "redshift")
+    capi.check(lib, lib.kr_memset(d_hist, 0, words * 8), "memset")
+    capi.check(lib, lib.kr_reduce_emissivity_dev_f64(C.byref(bins), d_rays, n, d_hist, None), "reduce")
+    sep_rays, sep_hist = fetch(idx), histogram()
+    # the two passes vs the oracle on the sampled (device-traced) records: one evaluation deep
+    want_post = after.copy()
+    ol.oracle().kro_range_phi_f64(-math.pi, math.pi, ol.ptr(want_post), len(want_post))
+    ol.oracle().kro_redshift_f64(gc.SPIN, -1.0, 0, 0, 0, ol.ptr(want_post), len(want_post))
+    assert ol.rays_equal_bitwise(sep_rays, want_post, fields=["phi"]) == []
+    live = (after["steps"] > 0) & np.isfinite(want_post["redshift"])
+    np.testing.assert_allclose(sep_rays["redshift"][live], want_post["redshift"][live], rtol=1e-10)
+    # fused passes over the same buffer
+    capi.check(lib, lib.kr_pointsource_init_emit_dev_f64(C.byref(spec), 0, 1, 0.0, 0, 0, d_rays, n, None), "init_emit")
+    assert ol.rays_equal_bitwise(fetch(idx), before) == []
+    st2 = capi.Stats()
+    capi.check(lib, lib.kr_trace_dev_f64(C.byref(p), d_rays, n, None, C.byref(st2)), "trace")
+    assert (st2.rays_traced, st2.steps_total, st2.rays_strict_side) == (st.rays_traced, st.steps_total, st.rays_strict_side)
+    capi.check(lib, lib.kr_memset(d_hist, 0, words * 8), "memset")
+    capi.check(lib, lib.kr_post_emissivity_dev_f64(gc.SPIN, -1.0, 0, 0, 0, -math.pi, math.pi, C.byref(bins), d_rays, n, d_hist, None), "post")
+    fused_rays, fused_hist = fetch(idx), histogram()
+    assert ol.rays_equal_bitwise(fused_rays, sep_rays) == []
+    assert sep_hist[5 * bins.nr] > 0.5 * n
+    np.testing.assert_array_equal(fused_hist[:bins.nr], sep_hist[:bins.nr])
+    np.testing.assert_allclose(fused_hist, sep_hist, rtol=1e-11)
 
 
-def test_imageplane_buffer_beyond_4_gib(krlib):
+def test_imageplane_buffer_beyond_4_gib(krlib, dev):
     """The same for the observer plane: 5801 x 5801 rays = 4.85 GB in one buffer, img 1024^2.  A sample of rays from beyond the 4 GiB mark
     equals the oracle's trace of the same records; the fused ends (init + redshift_start, redshift + range_phi + planes) equal the
     separate passes over the whole buffer (sampled records bit for bit, pixel counts exactly, plane sums to the order of the atomics)."""
@@ -489,48 +473,42 @@ def test_imageplane_buffer_beyond_4_gib(krlib):
     npix = IMG * IMG
     p = capi.default_params(-gc.SPIN)
     p.integrator, p.r_max, p.flags = capi.RK4, 1.1 * s.dist, capi.FLAG_HYBRID
-    d_rays, d_pl = vp(), vp()
-    capi.check(lib, lib.kr_malloc(C.byref(d_rays), total * 144), "malloc")
-    capi.check(lib, lib.kr_malloc(C.byref(d_pl), words * 8), "malloc")
+    d_rays, d_pl = dev.alloc(total * 144), dev.alloc(words * 8)
 
     def planes():
         out = np.zeros(words)
         capi.check(lib, lib.kr_memcpy_d2h(out.ctypes.data_as(vp), d_pl, words * 8), "d2h")
         return out
 
-    try:
-        rng = np.random.default_rng(5801)
-        idx = np.unique(np.concatenate([rng.choice(np.arange(first_beyond, total), 1200, replace=False), [first_beyond, total - 1]]))
-        # separate passes
-        capi.check(lib, lib.kr_imageplane_init_dev_f64(C.byref(s), d_rays, total, None), "init")
-        capi.check(lib, lib.kr_redshift_start_dev_f64(-gc.SPIN, 0.0, 1, 0, d_rays, total, None), "redshift_start")
-        before = _fetch(lib, d_rays, idx)
-        st = capi.Stats()
-        capi.check(lib, lib.kr_trace_dev_f64(C.byref(p), d_rays, total, None, C.byref(st)), "trace")
-        assert st.rays_traced == total and 0 < st.rays_strict_side < 3 * (N + 1)
-        after = _fetch(lib, d_rays, idx)
-        want, _ = ol.oracle_trace(p, before)
-        res = parity.compare_rays(after, want, rtol=parity.RAY_RTOL, steps_slack=0)
-        parity.record_margin("test_imageplane_buffer_beyond_4_gib", "ip5801-rk4-hybrid-sample-beyond-4GiB", res, parity.CHAOTIC_FRAC)
-        assert res["frac_bad"] <= parity.CHAOTIC_FRAC, res
-        capi.check(lib, lib.kr_redshift_dev_f64(-gc.SPIN, -1.0, 1, 0, 0, d_rays, total, None), "redshift")
-        capi.check(lib, lib.kr_range_phi_dev_f64(-math.pi, math.pi, d_rays, total, None), "range_phi")
-        capi.check(lib, lib.kr_memset(d_pl, 0, words * 8), "memset")
-        capi.check(lib, lib.kr_reduce_image_dev_f64(C.byref(b), d_rays, total, d_pl, None), "reduce")
-        sep_rays, sep = _fetch(lib, d_rays, idx), planes()
-        # fused ends
-        capi.check(lib, lib.kr_imageplane_init_emit_dev_f64(C.byref(s), 0, 1, 0.0, 1, 0, d_rays, total, None), "init_emit")
-        assert ol.rays_equal_bitwise(_fetch(lib, d_rays, idx), before) == []
-        st2 = capi.Stats()
-        capi.check(lib, lib.kr_trace_dev_f64(C.byref(p), d_rays, total, None, C.byref(st2)), "trace")
-        assert (st2.rays_traced, st2.steps_total, st2.rays_strict_side) == (st.rays_traced, st.steps_total, st.rays_strict_side)
-        capi.check(lib, lib.kr_memset(d_pl, 0, words * 8), "memset")
-        capi.check(lib, lib.kr_post_image_dev_f64(-gc.SPIN, -1.0, 1, 0, 0, -math.pi, math.pi, C.byref(b), d_rays, total, d_pl, None), "post")
-        fused_rays, fused = _fetch(lib, d_rays, idx), planes()
-        assert ol.rays_equal_bitwise(fused_rays, sep_rays) == []
-        assert sep[-1] > 1e6 and sep[-1] == fused[-1] == sep[:npix].sum()
-        np.testing.assert_array_equal(fused[:npix], sep[:npix])
-        np.testing.assert_allclose(fused, sep, rtol=1e-9, atol=1e-300)       # order of the atomic additions only (the phi plane's sums cancel: 1e-11 seen)
-    finally:
-        lib.kr_free(d_rays)
-        lib.kr_free(d_pl)
+    rng = np.random.default_rng(5801)
+    idx = np.unique(np.concatenate([rng.choice(np.arange(first_beyond, total), 1200, replace=False), [first_beyond, total - 1]]))
+    # separate passes
+    capi.check(lib, lib.kr_imageplane_init_dev_f64(C.byref(s), d_rays, total, None), "init")
+    capi.check(lib, lib.kr_redshift_start_dev_f64(-gc.SPIN, 0.0, 1, 0, d_rays, total, None), "redshift_start")
+    before = _fetch(lib, d_rays, idx)
+    st = capi.Stats()
+    capi.check(lib, lib.kr_trace_dev_f64(C.byref(p), d_rays, total, None, C.byref(st)), "trace")
+    assert st.rays_traced == total and 0 < st.rays_strict_side < 3 * (N + 1)
+    after = _fetch(lib, d_rays, idx)
+    want, _ = ol.oracle_trace(p, before)
+    res = parity.compare_rays(after, want, rtol=parity.RAY_RTOL, steps_slack=0)
+    parity.record_margin("test_imageplane_buffer_beyond_4_gib", "ip5801-rk4-hybrid-sample-beyond-4GiB", res, parity.CHAOTIC_FRAC)
+    assert res["frac_bad"] <= parity.CHAOTIC_FRAC, res
+    capi.check(lib, lib.kr_redshift_dev_f64(-gc.SPIN, -1.0, 1, 0, 0, d_rays, total, None), "redshift")
+    capi.check(lib, lib.kr_range_phi_dev_f64(-math.pi, math.pi, d_rays, total, None), "range_phi")
+    capi.check(lib, lib.kr_memset(d_pl, 0, words * 8), "memset")
+    capi.check(lib, lib.kr_reduce_image_dev_f64(C.byref(b), d_rays, total, d_pl, None), "reduce")
+    sep_rays, sep = _fetch(lib, d_rays, idx), planes()
+    # fused ends
+    capi.check(lib, lib.kr_imageplane_init_emit_dev_f64(C.byref(s), 0, 1, 0.0, 1, 0, d_rays, total, None), "init_emit")
+    assert ol.rays_equal_bitwise(_fetch(lib, d_rays, idx), before) == []
+    st2 = capi.Stats()
+    capi.check(lib, lib.kr_trace_dev_f64(C.byref(p), d_rays, total, None, C.byref(st2)), "trace")
+    assert (st2.rays_traced, st2.steps_total, st2.rays_strict_side) == (st.rays_traced, st.steps_total, st.rays_strict_side)
+    capi.check(lib, lib.kr_memset(d_pl, 0, words * 8), "memset")
+    capi.check(lib, lib.kr_post_image_dev_f64(-gc.SPIN, -1.0, 1, 0, 0, -math.pi, math.pi, C.byref(b), d_rays, total, d_pl, None), "post")
+    fused_rays, fused = _fetch(lib, d_rays, idx), planes()
+    assert ol.rays_equal_bitwise(fused_rays, sep_rays) == []
+    assert sep[-1] > 1e6 and sep[-1] == fused[-1] == sep[:npix].sum()
+    np.testing.assert_array_equal(fused[:npix], sep[:npix])
+    np.testing.assert_allclose(fused, sep, rtol=1e-9, atol=1e-300)       # order of the atomic additions only (the phi plane's sums cancel: 1e-11 seen)

@@ -17,6 +17,7 @@ import healpix_rules as hr
 import oracle_lib as ol
 import parity
 from raytrace_cpu_amd import api, capi
+from raytrace_cpu_amd.devmem import DeviceScope
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -57,39 +58,11 @@ def same_bits(a, b):
     return bool(((bits(a) == bits(b)) | (np.isnan(a) & np.isnan(b))).all())
 
 
-class Buffers:
-    """Device buffers of one test, freed at its end."""
-
-    def __init__(self):
-        self.L, self.held = api.lib(), []
-
-    def alloc(self, nbytes, zero=False):
-        d = vp()
-        capi.check(self.L, self.L.kr_malloc(C.byref(d), max(int(nbytes), 8)), "kr_malloc")
-        self.held.append(d)
-        if zero:
-            capi.check(self.L, self.L.kr_memset(d, 0, max(int(nbytes), 8)), "kr_memset")
-        return d
-
-    def upload(self, a):
-        d = self.alloc(a.nbytes)
-        capi.check(self.L, self.L.kr_memcpy_h2d(d, ol.ptr(a), a.nbytes), "kr_memcpy_h2d")
-        return d
-
-    def fetch(self, d, like):
-        capi.check(self.L, self.L.kr_memcpy_d2h(ol.ptr(like), d, like.nbytes), "kr_memcpy_d2h")
-        return like
-
-    def close(self):
-        for d in self.held:
-            self.L.kr_free(d)
-
-
 @pytest.fixture
 def dev(krlib):
-    b = Buffers()
-    yield b
-    b.close()
+    """Device buffers of one test, freed at its end."""
+    with DeviceScope(api.lib()) as scope:
+        yield scope
 
 
 @pytest.fixture(scope="module")
@@ -110,13 +83,13 @@ def test_vectors_match_reference_fixture(dev, fixture):
     got = np.zeros_like(want)
     for o in np.unique(order):
         idx = np.flatnonzero(order == o)
-        d = dev.alloc(len(idx) * 120)
+        d = dev.alloc(max(len(idx) * 120, 8))
         if o <= 3:
-            capi.check(dev.L, dev.L.kr_healpix_vectors_dev_f64(int(o), 0, 0, 1, len(idx), d, None), "kr_healpix_vectors")
+            capi.check(dev.lib, dev.lib.kr_healpix_vectors_dev_f64(int(o), 0, 0, 1, len(idx), d, None), "kr_healpix_vectors")
         else:
             for q, p in enumerate(pix[idx]):
-                capi.check(dev.L, dev.L.kr_healpix_vectors_dev_f64(int(o), 0, int(p), 1, 1, vp(d.value + 120 * q), None), "kr_healpix_vectors")
-        got[idx] = dev.fetch(d, np.zeros((len(idx), 15)))
+                capi.check(dev.lib, dev.lib.kr_healpix_vectors_dev_f64(int(o), 0, int(p), 1, 1, vp(d.value + 120 * q), None), "kr_healpix_vectors")
+        got[idx] = dev.fetch(d, len(idx) * 15).reshape(-1, 15)
     worst = float(np.abs(got - want).max())
     differ = int((bits(got) != bits(want)).sum())
     print(f"device vectors against the reference's: worst |difference| {worst:.3e}, {differ} of {want.size} components not bit-identical")
@@ -262,10 +235,10 @@ def traced(name, integrator, rays_per_pixel=1):
 
 def post_on_device(dev, spec, m, rays, first=0, stride=1, d_out=None):
     d_rays = dev.upload(np.ascontiguousarray(rays))
-    d_out = d_out or dev.alloc(8 * api.healpix_map_words(m), zero=True)
-    capi.check(dev.L, dev.L.kr_post_healpix_map_dev_f64(spec.spin, -1.0, 0, 0, 0, -math.pi, math.pi, C.byref(m), d_rays, len(rays), first, stride, d_out, None), "kr_post_healpix_map")
-    words = dev.fetch(d_out, np.zeros(api.healpix_map_words(m)))
-    return api.healpix_map_from_words(m, words), dev.fetch(d_rays, np.zeros(len(rays), dtype=capi.RAY_F64)), d_out
+    d_out = d_out or dev.zeros(8 * api.healpix_map_words(m))
+    capi.check(dev.lib, dev.lib.kr_post_healpix_map_dev_f64(spec.spin, -1.0, 0, 0, 0, -math.pi, math.pi, C.byref(m), d_rays, len(rays), first, stride, d_out, None), "kr_post_healpix_map")
+    words = dev.fetch(d_out, api.healpix_map_words(m))
+    return api.healpix_map_from_words(m, words), dev.fetch(d_rays, len(rays), capi.RAY_F64), d_out
 
 
 def separate_passes(spec, rays):
@@ -320,11 +293,11 @@ def check_same_map(a, b, label):
 
 def reduce_on_device(dev, m, rays, first=0, stride=1, d_out=None):
     d_rays = dev.upload(np.ascontiguousarray(rays))
-    d_out = d_out or dev.alloc(8 * api.healpix_map_words(m), zero=True)
-    capi.check(dev.L, dev.L.kr_reduce_healpix_map_dev_f64(C.byref(m), d_rays, len(rays), first, stride, d_out, None), "kr_reduce_healpix_map_dev")
-    after = dev.fetch(d_rays, np.zeros(len(rays), dtype=capi.RAY_F64))
+    d_out = d_out or dev.zeros(8 * api.healpix_map_words(m))
+    capi.check(dev.lib, dev.lib.kr_reduce_healpix_map_dev_f64(C.byref(m), d_rays, len(rays), first, stride, d_out, None), "kr_reduce_healpix_map_dev")
+    after = dev.fetch(d_rays, len(rays), capi.RAY_F64)
     assert not ol.rays_equal_bitwise(after, rays)                          # the reducing form reads
-    return api.healpix_map_from_words(m, dev.fetch(d_out, np.zeros(api.healpix_map_words(m)))), d_out
+    return api.healpix_map_from_words(m, dev.fetch(d_out, api.healpix_map_words(m))), d_out
 
 
 @pytest.mark.parametrize("rpp", (1, 5))

@@ -14,6 +14,7 @@ import line_rules as lr
 import oracle_lib as ol
 import parity
 from raytrace_cpu_amd import api, capi
+from raytrace_cpu_amd.devmem import DeviceScope
 
 pytestmark = pytest.mark.gpu
 
@@ -64,51 +65,22 @@ def table_bins(b):
     return b.with_table(r_min, dr, emis, time)
 
 
-class Dev:
-    """A device buffer through the C ABI's own allocator."""
-
-    def __init__(self, nbytes):
-        self.p, self.n = C.c_void_p(), nbytes
-        capi.check(api.lib(), api.lib().kr_malloc(C.byref(self.p), nbytes), "kr_malloc")
-
-    @classmethod
-    def of(cls, a):
-        d = cls(a.nbytes)
-        capi.check(api.lib(), api.lib().kr_memcpy_h2d(d.p, a.ctypes.data_as(C.c_void_p), a.nbytes), "h2d")
-        return d
-
-    @classmethod
-    def zeros(cls, words):
-        d = cls(words * 8)
-        capi.check(api.lib(), api.lib().kr_memset(d.p, 0, words * 8), "memset")
-        return d
-
-    def get(self, like):
-        out = np.empty_like(like)
-        capi.check(api.lib(), api.lib().kr_memcpy_d2h(out.ctypes.data_as(C.c_void_p), self.p, out.nbytes), "d2h")
-        return out
-
-    def free(self):
-        api.lib().kr_free(self.p)
-
-
 def post_line(b, rays):
     """kr_post_line_dev_f64 on a device copy of `rays` (traced, not yet redshifted): (histogram dict, rays after the pass)."""
     L = api.lib()
-    d, h = Dev.of(rays), Dev.zeros(api.line_words(b))
-    capi.check(L, L.kr_post_line_dev_f64(-SPIN, -1.0, 1, 0, 0, -math.pi, math.pi, C.byref(b), d.p, len(rays), h.p, None), "kr_post_line")
-    out, words = d.get(rays), h.get(np.zeros(api.line_words(b)))
-    d.free(); h.free()
+    with DeviceScope(L) as dev:
+        d, h = dev.upload(rays), dev.zeros(api.line_words(b) * 8)
+        capi.check(L, L.kr_post_line_dev_f64(-SPIN, -1.0, 1, 0, 0, -math.pi, math.pi, C.byref(b), d, len(rays), h, None), "kr_post_line")
+        out, words = dev.fetch(d, len(rays), rays.dtype), dev.fetch(h, api.line_words(b))
     return api.line_from_words(b, words), out
 
 
 def reduce_line_dev(b, rays):
     L = api.lib()
-    d, h = Dev.of(rays), Dev.zeros(api.line_words(b))
-    capi.check(L, L.kr_reduce_line_dev_f64(C.byref(b), d.p, len(rays), h.p, None), "kr_reduce_line_dev")
-    words = h.get(np.zeros(api.line_words(b)))
-    d.free(); h.free()
-    return api.line_from_words(b, words)
+    with DeviceScope(L) as dev:
+        d, h = dev.upload(rays), dev.zeros(api.line_words(b) * 8)
+        capi.check(L, L.kr_reduce_line_dev_f64(C.byref(b), d, len(rays), h, None), "kr_reduce_line_dev")
+        return api.line_from_words(b, dev.fetch(h, api.line_words(b)))
 
 
 def check(test, case, got, want, rtol=1e-6, slack=1, max_excluded=None):
@@ -321,20 +293,18 @@ def test_line_tables_survive_churn_of_the_table_store(traced):
     L = api.lib()
     _, rays = post_line(line_bins(), traced)
     r_min, dr, emis, time = lr.read_emissivity_dat(EMIS_DAT)
-    d = Dev.of(rays)
-    try:
+    with DeviceScope(L) as dev:
+        d = dev.upload(rays)
         for i in range(300):
             b = line_bins().with_table(r_min, dr, emis * (1 + 0.01 * i), time)
             want = lr.line_from_rays(b, rays)
-            h = Dev.zeros(api.line_words(b))
-            capi.check(L, L.kr_reduce_line_dev_f64(C.byref(b), d.p, len(rays), h.p, None), "kr_reduce_line_dev")
-            got = api.line_from_words(b, h.get(np.zeros(api.line_words(b))))
-            h.free()
+            with DeviceScope(L) as one:
+                h = one.zeros(api.line_words(b) * 8)
+                capi.check(L, L.kr_reduce_line_dev_f64(C.byref(b), d, len(rays), h, None), "kr_reduce_line_dev")
+                got = api.line_from_words(b, one.fetch(h, api.line_words(b)))
             problems, m = lr.compare_line(got, want, rtol=1e-9, slack=1, max_excluded=2)
             assert problems == [], (i, problems, m)
             if i % 10 == 0:
                 got, _ = post_line(b, traced)
                 problems, m = lr.compare_line(got, want, rtol=1e-9, slack=1, max_excluded=2)
                 assert problems == [], (i, "post_line", problems, m)
-    finally:
-        d.free()

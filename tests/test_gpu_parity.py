@@ -9,6 +9,7 @@ import golden_cases as gc
 import oracle_lib as ol
 import parity
 from raytrace_cpu_amd import api, capi
+from raytrace_cpu_amd.devmem import DeviceScope
 
 pytestmark = pytest.mark.gpu
 
@@ -469,27 +470,23 @@ def test_f32_device_pointer_passes_equal_the_host_pointer_ones(krlib):
     want_start = g["init"].copy()
     want_start["emit"] = 0
     api.redshift_start(spin, 0.0, 0, 0, want_start)
-    d = vp()
-    capi.check(lib, lib.kr_malloc(C.byref(d), n * 84), "malloc")
-    try:
+    with DeviceScope(lib) as dev:
         got = fin.copy()
-        capi.check(lib, lib.kr_memcpy_h2d(d, got.ctypes.data_as(vp), n * 84), "h2d")
+        d = dev.upload(got)
         capi.check(lib, lib.kr_range_phi_dev_f32(float(np.float32(-np.pi)), float(np.float32(np.pi)), d, n, None), "range_phi")
         capi.check(lib, lib.kr_redshift_dev_f32(spin, -1.0, 0, 0, 0, d, n, None), "redshift")
         capi.check(lib, lib.kr_calculate_momentum_dev_f32(spin, d, n, None), "momentum")
-        capi.check(lib, lib.kr_memcpy_d2h(got.ctypes.data_as(vp), d, n * 84), "d2h")
+        dev.fetch_into(d, got)
         assert got.tobytes() == want.tobytes()
         capi.check(lib, lib.kr_redshift_dest_dev_f32(spin, 0, d, n, None), "redshift_dest")
-        capi.check(lib, lib.kr_memcpy_d2h(got.ctypes.data_as(vp), d, n * 84), "d2h")
+        dev.fetch_into(d, got)
         assert got.tobytes() == want_dest.tobytes()
         start = g["init"].copy()
         start["emit"] = 0
         capi.check(lib, lib.kr_memcpy_h2d(d, start.ctypes.data_as(vp), n * 84), "h2d")
         capi.check(lib, lib.kr_redshift_start_dev_f32(spin, 0.0, 0, 0, d, n, None), "redshift_start")
-        capi.check(lib, lib.kr_memcpy_d2h(start.ctypes.data_as(vp), d, n * 84), "d2h")
+        dev.fetch_into(d, start)
         assert start.tobytes() == want_start.tobytes()
-    finally:
-        lib.kr_free(d)
 
 
 def test_degenerate_denominators_match_oracle(krlib):
@@ -643,7 +640,7 @@ def test_fused_pipeline_ends_equal_the_separate_passes(krlib):
     """kr_pointsource_init_emit_dev_f64 == init + redshift_start, kr_post_emissivity_dev_f64 == range_phi + redshift + reduce:
     rays bit-identical, histogram counts identical, sums equal up to the order of the atomic additions."""
     import bench
-    lib, vp = krlib, C.c_void_p
+    lib = krlib
     spec = bench.make_spec(capi, bench.grid_spacing_for(2e5))
     n = lib.kr_pointsource_count(C.byref(spec), None, None)
     bins = gc.emis_bins(spec, nr=100)
@@ -652,30 +649,22 @@ def test_fused_pipeline_ends_equal_the_separate_passes(krlib):
     p.integrator, p.r_max = capi.RK4, 1000.0
     bufs = []
     for fused in (False, True):
-        d_rays, d_hist = vp(), vp()
-        capi.check(lib, lib.kr_malloc(C.byref(d_rays), n * 144), "malloc")
-        capi.check(lib, lib.kr_malloc(C.byref(d_hist), words * 8), "malloc")
-        capi.check(lib, lib.kr_memset(d_hist, 0, words * 8), "memset")
-        if fused:
-            capi.check(lib, lib.kr_pointsource_init_emit_dev_f64(C.byref(spec), 0, 1, 0.0, 0, 0, d_rays, n, None), "init_emit")
-        else:
-            capi.check(lib, lib.kr_pointsource_init_dev_f64(C.byref(spec), d_rays, n, None), "init")
-            capi.check(lib, lib.kr_redshift_start_dev_f64(gc.SPIN, 0.0, 0, 0, d_rays, n, None), "redshift_start")
-        start = np.zeros(n, dtype=capi.RAY_F64)
-        capi.check(lib, lib.kr_memcpy_d2h(start.ctypes.data_as(vp), d_rays, n * 144), "d2h")
-        capi.check(lib, lib.kr_trace_dev_f64(C.byref(p), d_rays, n, None, None), "trace")
-        if fused:
-            capi.check(lib, lib.kr_post_emissivity_dev_f64(gc.SPIN, -1.0, 0, 0, 0, -np.pi, np.pi, C.byref(bins), d_rays, n, d_hist, None), "post")
-        else:
-            capi.check(lib, lib.kr_range_phi_dev_f64(-np.pi, np.pi, d_rays, n, None), "range_phi")
-            capi.check(lib, lib.kr_redshift_dev_f64(gc.SPIN, -1.0, 0, 0, 0, d_rays, n, None), "redshift")
-            capi.check(lib, lib.kr_reduce_emissivity_dev_f64(C.byref(bins), d_rays, n, d_hist, None), "reduce")
-        end = np.zeros(n, dtype=capi.RAY_F64)
-        hist = np.zeros(words)
-        capi.check(lib, lib.kr_memcpy_d2h(end.ctypes.data_as(vp), d_rays, n * 144), "d2h")
-        capi.check(lib, lib.kr_memcpy_d2h(hist.ctypes.data_as(vp), d_hist, words * 8), "d2h")
-        lib.kr_free(d_rays)
-        lib.kr_free(d_hist)
+        with DeviceScope(lib) as dev:
+            d_rays, d_hist = dev.alloc(n * 144), dev.zeros(words * 8)
+            if fused:
+                capi.check(lib, lib.kr_pointsource_init_emit_dev_f64(C.byref(spec), 0, 1, 0.0, 0, 0, d_rays, n, None), "init_emit")
+            else:
+                capi.check(lib, lib.kr_pointsource_init_dev_f64(C.byref(spec), d_rays, n, None), "init")
+                capi.check(lib, lib.kr_redshift_start_dev_f64(gc.SPIN, 0.0, 0, 0, d_rays, n, None), "redshift_start")
+            start = dev.fetch(d_rays, n, capi.RAY_F64)
+            capi.check(lib, lib.kr_trace_dev_f64(C.byref(p), d_rays, n, None, None), "trace")
+            if fused:
+                capi.check(lib, lib.kr_post_emissivity_dev_f64(gc.SPIN, -1.0, 0, 0, 0, -np.pi, np.pi, C.byref(bins), d_rays, n, d_hist, None), "post")
+            else:
+                capi.check(lib, lib.kr_range_phi_dev_f64(-np.pi, np.pi, d_rays, n, None), "range_phi")
+                capi.check(lib, lib.kr_redshift_dev_f64(gc.SPIN, -1.0, 0, 0, 0, d_rays, n, None), "redshift")
+                capi.check(lib, lib.kr_reduce_emissivity_dev_f64(C.byref(bins), d_rays, n, d_hist, None), "reduce")
+            end, hist = dev.fetch(d_rays, n, capi.RAY_F64), dev.fetch(d_hist, words)
         bufs.append((start, end, hist))
     (s0, e0, h0), (s1, e1, h1) = bufs
     assert ol.rays_equal_bitwise(s0, s1) == [] and ol.rays_equal_bitwise(e0, e1) == []
@@ -686,7 +675,7 @@ def test_fused_pipeline_ends_equal_the_separate_passes(krlib):
 
 def test_fused_image_pipeline_ends_equal_the_separate_passes(krlib):
     """kr_imageplane_init_emit_dev_f64 / kr_post_image_dev_f64 against the five separate image-pipeline passes."""
-    lib, vp = krlib, C.c_void_p
+    lib = krlib
     N = 301
     spec = ol.imageplane_spec(10000.0, 80.0, -30.0, 30.0, 60.0 / N, -30.0, 30.0, 60.0 / N, gc.SPIN)
     n = lib.kr_imageplane_count(C.byref(spec), None, None)
@@ -700,30 +689,22 @@ def test_fused_image_pipeline_ends_equal_the_separate_passes(krlib):
     p.integrator, p.r_max = capi.RK4, 11000.0
     res = []
     for fused in (False, True):
-        d_rays, d_pl = vp(), vp()
-        capi.check(lib, lib.kr_malloc(C.byref(d_rays), n * 144), "malloc")
-        capi.check(lib, lib.kr_malloc(C.byref(d_pl), words * 8), "malloc")
-        capi.check(lib, lib.kr_memset(d_pl, 0, words * 8), "memset")
-        if fused:
-            capi.check(lib, lib.kr_imageplane_init_emit_dev_f64(C.byref(spec), 0, 1, 0.0, 1, 0, d_rays, n, None), "init_emit")
-        else:
-            capi.check(lib, lib.kr_imageplane_init_dev_f64(C.byref(spec), d_rays, n, None), "init")
-            capi.check(lib, lib.kr_redshift_start_dev_f64(-gc.SPIN, 0.0, 1, 0, d_rays, n, None), "redshift_start")
-        start = np.zeros(n, dtype=capi.RAY_F64)
-        capi.check(lib, lib.kr_memcpy_d2h(start.ctypes.data_as(vp), d_rays, n * 144), "d2h")
-        capi.check(lib, lib.kr_trace_dev_f64(C.byref(p), d_rays, n, None, None), "trace")
-        if fused:
-            capi.check(lib, lib.kr_post_image_dev_f64(-gc.SPIN, -1.0, 1, 0, 0, -np.pi, np.pi, C.byref(b), d_rays, n, d_pl, None), "post")
-        else:
-            capi.check(lib, lib.kr_redshift_dev_f64(-gc.SPIN, -1.0, 1, 0, 0, d_rays, n, None), "redshift")
-            capi.check(lib, lib.kr_range_phi_dev_f64(-np.pi, np.pi, d_rays, n, None), "range_phi")
-            capi.check(lib, lib.kr_reduce_image_dev_f64(C.byref(b), d_rays, n, d_pl, None), "reduce")
-        end = np.zeros(n, dtype=capi.RAY_F64)
-        planes = np.zeros(words)
-        capi.check(lib, lib.kr_memcpy_d2h(end.ctypes.data_as(vp), d_rays, n * 144), "d2h")
-        capi.check(lib, lib.kr_memcpy_d2h(planes.ctypes.data_as(vp), d_pl, words * 8), "d2h")
-        lib.kr_free(d_rays)
-        lib.kr_free(d_pl)
+        with DeviceScope(lib) as dev:
+            d_rays, d_pl = dev.alloc(n * 144), dev.zeros(words * 8)
+            if fused:
+                capi.check(lib, lib.kr_imageplane_init_emit_dev_f64(C.byref(spec), 0, 1, 0.0, 1, 0, d_rays, n, None), "init_emit")
+            else:
+                capi.check(lib, lib.kr_imageplane_init_dev_f64(C.byref(spec), d_rays, n, None), "init")
+                capi.check(lib, lib.kr_redshift_start_dev_f64(-gc.SPIN, 0.0, 1, 0, d_rays, n, None), "redshift_start")
+            start = dev.fetch(d_rays, n, capi.RAY_F64)
+            capi.check(lib, lib.kr_trace_dev_f64(C.byref(p), d_rays, n, None, None), "trace")
+            if fused:
+                capi.check(lib, lib.kr_post_image_dev_f64(-gc.SPIN, -1.0, 1, 0, 0, -np.pi, np.pi, C.byref(b), d_rays, n, d_pl, None), "post")
+            else:
+                capi.check(lib, lib.kr_redshift_dev_f64(-gc.SPIN, -1.0, 1, 0, 0, d_rays, n, None), "redshift")
+                capi.check(lib, lib.kr_range_phi_dev_f64(-np.pi, np.pi, d_rays, n, None), "range_phi")
+                capi.check(lib, lib.kr_reduce_image_dev_f64(C.byref(b), d_rays, n, d_pl, None), "reduce")
+            end, planes = dev.fetch(d_rays, n, capi.RAY_F64), dev.fetch(d_pl, words)
         res.append((start, end, planes))
     (s0, e0, p0), (s1, e1, p1) = res
     assert ol.rays_equal_bitwise(s0, s1) == [] and ol.rays_equal_bitwise(e0, e1) == []
@@ -735,33 +716,28 @@ def test_fused_image_pipeline_ends_equal_the_separate_passes(krlib):
 def test_fused_init_with_keplerian_V_on_a_shard_equals_the_unsharded_source(krlib):
     """V = -1 makes redshift_start use the orbital velocity at rays[0] of the WHOLE source for every ray (raytracer.cpp:389-393).
     A strided shard (first = 1, stride = 2: what rank 1 of 2 generates) must use that same velocity, not its own first ray's."""
-    lib, vp = krlib, C.c_void_p
+    lib = krlib
     spec = ol.pointsource_spec([0.0, 6.0, np.pi / 2 - 1e-3, 0.3], gc.kep_velocity(6.0), gc.SPIN, 0.05, 0.05, cosalpha0=-0.995, cosalphamax=0.995, beta0=-np.pi, betamax=np.pi)
     n = lib.kr_pointsource_count(C.byref(spec), None, None)
-    full = np.zeros(n, dtype=capi.RAY_F64)
-    d = vp()
-    capi.check(lib, lib.kr_malloc(C.byref(d), n * 144), "malloc")
-    try:
+    with DeviceScope(lib) as dev:
+        d = dev.alloc(n * 144)
         capi.check(lib, lib.kr_pointsource_init_emit_dev_f64(C.byref(spec), 0, 1, -1.0, 0, 0, d, n, None), "init_emit")
-        capi.check(lib, lib.kr_memcpy_d2h(full.ctypes.data_as(vp), d, n * 144), "d2h")
+        full = dev.fetch(d, n, capi.RAY_F64)
         # the separate passes on the whole source are the reference semantics
         sep = api.pointsource_init(spec)
         api.redshift_start(gc.SPIN, -1.0, 0, 0, sep)
         assert ol.rays_equal_bitwise(full, sep) == []
         m = (n - 1 + 1) // 2
-        shard = np.zeros(m, dtype=capi.RAY_F64)
         capi.check(lib, lib.kr_pointsource_init_emit_dev_f64(C.byref(spec), 1, 2, -1.0, 0, 0, d, m, None), "init_emit shard")
-        capi.check(lib, lib.kr_memcpy_d2h(shard.ctypes.data_as(vp), d, m * 144), "d2h")
+        shard = dev.fetch(d, m, capi.RAY_F64)
         assert ol.rays_equal_bitwise(shard, full[1::2][:m]) == []
         live = shard["steps"] == 0
         assert live.sum() > 100 and np.isfinite(shard["emit"][live]).all() and np.ptp(shard["emit"][live]) > 0
-    finally:
-        lib.kr_free(d)
 
 
 def test_fused_return_post_pass_equals_the_separate_passes(krlib):
     """kr_post_return_dev_f64 == kr_range_phi_dev_f64 + kr_reduce_return_dev_f64: records bit-identical, the four sums equal to the order of the atomics."""
-    lib, vp = krlib, C.c_void_p
+    lib = krlib
     g = np.load(gc.golden_path("ps_h5"))
     fin = g["final__rk4"].copy()
     fin["phi"] += 40.0                          # so that range_phi has something to wrap
@@ -771,21 +747,14 @@ def test_fused_return_post_pass_equals_the_separate_passes(krlib):
     b.plane_iso, b.limb, b.weight_norm, b.pad = 1, 1, 1, 0
     res = []
     for fused in (False, True):
-        d, d_out = vp(), vp()
-        capi.check(lib, lib.kr_malloc(C.byref(d), n * 144), "malloc")
-        capi.check(lib, lib.kr_malloc(C.byref(d_out), 32), "malloc")
-        capi.check(lib, lib.kr_memset(d_out, 0, 32), "memset")
-        capi.check(lib, lib.kr_memcpy_h2d(d, fin.ctypes.data_as(vp), n * 144), "h2d")
-        if fused:
-            capi.check(lib, lib.kr_post_return_dev_f64(-np.pi, np.pi, C.byref(b), d, n, d_out, None), "post")
-        else:
-            capi.check(lib, lib.kr_range_phi_dev_f64(-np.pi, np.pi, d, n, None), "range_phi")
-            capi.check(lib, lib.kr_reduce_return_dev_f64(C.byref(b), d, n, d_out, None), "reduce")
-        rays, out = np.zeros(n, dtype=capi.RAY_F64), np.zeros(4)
-        capi.check(lib, lib.kr_memcpy_d2h(rays.ctypes.data_as(vp), d, n * 144), "d2h")
-        capi.check(lib, lib.kr_memcpy_d2h(out.ctypes.data_as(vp), d_out, 32), "d2h")
-        lib.kr_free(d)
-        lib.kr_free(d_out)
+        with DeviceScope(lib) as dev:
+            d, d_out = dev.upload(fin), dev.zeros(32)
+            if fused:
+                capi.check(lib, lib.kr_post_return_dev_f64(-np.pi, np.pi, C.byref(b), d, n, d_out, None), "post")
+            else:
+                capi.check(lib, lib.kr_range_phi_dev_f64(-np.pi, np.pi, d, n, None), "range_phi")
+                capi.check(lib, lib.kr_reduce_return_dev_f64(C.byref(b), d, n, d_out, None), "reduce")
+            rays, out = dev.fetch(d, n, capi.RAY_F64), dev.fetch(d_out, 4)
         res.append((rays, out))
     (r0, o0), (r1, o1) = res
     assert ol.rays_equal_bitwise(r0, r1) == []

@@ -12,6 +12,7 @@ import parity
 import paths_rules as pr
 import step_control_cases as sc
 from raytrace_cpu_amd import api, capi
+from raytrace_cpu_amd.devmem import DeviceScope
 
 pytestmark = pytest.mark.gpu
 
@@ -190,22 +191,15 @@ def test_count_pass_leaves_the_rays_alone_and_record_checks_its_slabs():
     init = np.load(gc.golden_path("ps_h10"))["init"].copy()
     n = len(init)
     w = api.path_spec(write_step=3)
-    d_rays, d_off, d_traced, d_rows = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
-    try:
-        capi.check(L, L.kr_malloc(C.byref(d_rays), init.nbytes), "kr_malloc")
-        capi.check(L, L.kr_malloc(C.byref(d_off), (n + 1) * 8), "kr_malloc")
-        capi.check(L, L.kr_malloc(C.byref(d_traced), n), "kr_malloc")
-        capi.check(L, L.kr_memcpy_h2d(d_rays, init.ctypes.data_as(C.c_void_p), init.nbytes), "h2d")
+    with DeviceScope(L) as dev:
+        d_rays, d_off, d_traced = dev.upload(init), dev.alloc((n + 1) * 8), dev.alloc(n)
         total = C.c_int64()
         capi.check(L, L.kr_trace_paths_count_dev_f64(C.byref(p), C.byref(w), d_rays, n, d_off, d_traced, C.byref(total), None), "count")
-        back = np.empty_like(init)
-        capi.check(L, L.kr_memcpy_d2h(back.ctypes.data_as(C.c_void_p), d_rays, init.nbytes), "d2h")
-        assert back.tobytes() == init.tobytes()
-        offsets = np.empty(n + 1, dtype=np.int64)
-        capi.check(L, L.kr_memcpy_d2h(offsets.ctypes.data_as(C.c_void_p), d_off, offsets.nbytes), "d2h")
+        assert dev.fetch(d_rays, n, init.dtype).tobytes() == init.tobytes()
+        offsets = dev.fetch(d_off, n + 1, np.int64)
         assert offsets[0] == 0 and offsets[-1] == total.value > 0
         guard = 64                                                # rows beyond the buffer's nominal end, filled with a pattern
-        capi.check(L, L.kr_malloc(C.byref(d_rows), (total.value + guard) * 32), "kr_malloc")
+        d_rows = dev.alloc((total.value + guard) * 32)
         capi.check(L, L.kr_memset(d_rows, 0xA5, (total.value + guard) * 32), "memset")
         # too small a buffer: refused, nothing written
         rc = L.kr_trace_paths_record_dev_f64(C.byref(p), C.byref(w), d_rays, n, d_off, d_rows, total.value - 1, None, None)
@@ -214,22 +208,16 @@ def test_count_pass_leaves_the_rays_alone_and_record_checks_its_slabs():
         w2 = api.path_spec(write_step=1)
         rc = L.kr_trace_paths_record_dev_f64(C.byref(p), C.byref(w2), d_rays, n, d_off, d_rows, total.value, None, None)
         assert rc == capi.KR_EINVAL and b"different number of rows" in L.kr_last_error()
-        tail = np.empty(guard * 4, dtype=np.uint64)
-        capi.check(L, L.kr_memcpy_d2h(tail.ctypes.data_as(C.c_void_p), C.c_void_p(d_rows.value + total.value * 32), tail.nbytes), "d2h")
+        tail = dev.fetch(C.c_void_p(d_rows.value + total.value * 32), guard * 4, np.uint64)
         assert (tail == 0xA5A5A5A5A5A5A5A5).all()
         # the matching call on fresh rays succeeds and agrees with the host-pointer form
         capi.check(L, L.kr_memcpy_h2d(d_rays, init.ctypes.data_as(C.c_void_p), init.nbytes), "h2d")
         st = capi.Stats()
         capi.check(L, L.kr_trace_paths_record_dev_f64(C.byref(p), C.byref(w), d_rays, n, d_off, d_rows, total.value, None, C.byref(st)), "record")
-        rows = np.empty((total.value, 4))
-        capi.check(L, L.kr_memcpy_d2h(rows.ctypes.data_as(C.c_void_p), d_rows, rows.nbytes), "d2h")
+        rows = dev.fetch(d_rows, total.value * 4).reshape(-1, 4)
         off_h, rows_h, _, out_h, st_h = api.trace_paths(p, init, write_step=3)
         assert off_h.tobytes() == offsets.tobytes() and rows_h.tobytes() == rows.tobytes()
         assert st.rays_traced == st_h["rays_traced"] and st.steps_total == st_h["steps_total"] and st.kernel_ms > 0
-    finally:
-        for d in (d_rays, d_off, d_traced, d_rows):
-            if d.value:
-                L.kr_free(d)
 
 
 def test_empty_input():

@@ -4,7 +4,6 @@ A flagged ray whose polar numerator is exactly zero never leaves its theta; the 
 which instructions run, never what is computed: every record must equal, field for field (parity.same_records), what the general strict step gives --
 the same trace with KR_NO_RADIAL=1 (all flagged rays on the general waves) and the single strict launch (KR_NO_ISOLATE=1, flags = 0)."""
 import contextlib
-import ctypes as C
 import functools
 import os
 
@@ -16,6 +15,7 @@ import golden_cases as gc
 import parity
 import radial_cases as rc
 from raytrace_cpu_amd import api, capi
+from raytrace_cpu_amd.devmem import DeviceScope
 
 pytestmark = pytest.mark.gpu
 
@@ -94,15 +94,10 @@ def test_hybrid_and_strict_split_equal_the_single_strict_launch(krlib, integrato
     assert st["steps_total"] == st_general["steps_total"]
     # the all-strict trace with a side launch (flags = 0): traces of a batch split from 4096 rays on, so the grid goes in seven times over
     tiled = np.tile(rays, 7)
-    d = C.c_void_p()
-    capi.check(krlib, krlib.kr_malloc(C.byref(d), tiled.nbytes), "kr_malloc")
-    try:
-        capi.check(krlib, krlib.kr_memcpy_h2d(d, tiled.ctypes.data_as(C.c_void_p), tiled.nbytes), "h2d")
+    with DeviceScope(krlib) as dev:
+        d = dev.upload(tiled)
         st_split = api.trace_wait(api.trace_batch_async([capi.copy_params(p, flags=0)], [d.value], [len(tiled)])[0])
-        out = np.zeros_like(tiled)
-        capi.check(krlib, krlib.kr_memcpy_d2h(out.ctypes.data_as(C.c_void_p), d, out.nbytes), "d2h")
-    finally:
-        krlib.kr_free(d)
+        out = dev.fetch(d, len(tiled), tiled.dtype)
     assert st_split["rays_strict_side"] == 7 * int(column.sum())
     assert st_split["steps_strict_side"] == 7 * int(steps[column].sum()) and st_split["steps_total"] == 7 * int(steps[rays["steps"] >= 0].sum())
     assert same(out, np.tile(want, 7))

@@ -18,60 +18,42 @@ import parity
 import reducer_cases as rc
 import reducer_rules as rr
 from raytrace_cpu_amd import api, capi
+from raytrace_cpu_amd.devmem import DeviceScope
 
 pytestmark = pytest.mark.gpu
 vp = C.c_void_p
 RTOL = parity.BIN_RTOL
 
 
-class Device:
-    """Device buffers of one test, freed at its end."""
-
-    def __init__(self, lib):
-        self.lib, self.held = lib, []
-
-    def alloc(self, nbytes):
-        d = vp()
-        capi.check(self.lib, self.lib.kr_malloc(C.byref(d), max(int(nbytes), 8)), "malloc")
-        self.held.append(d)
-        return d
-
-    def upload(self, a):
-        a = np.ascontiguousarray(a)
-        d = self.alloc(a.nbytes)
-        if a.nbytes:
-            capi.check(self.lib, self.lib.kr_memcpy_h2d(d, a.ctypes.data_as(vp), a.nbytes), "h2d")
-        return d
-
-    def words(self, n, fill=0.0):
-        return self.upload(np.full(n, fill))
-
-    def fetch(self, d, n, dtype=np.float64):
-        h = np.zeros(n, dtype=dtype)
-        capi.check(self.lib, self.lib.kr_synchronize(None), "sync")
-        if h.nbytes:
-            capi.check(self.lib, self.lib.kr_memcpy_d2h(h.ctypes.data_as(vp), d, h.nbytes), "d2h")
-        return h
-
-    def close(self):
-        for d in self.held:
-            self.lib.kr_free(d)
-
-
 @pytest.fixture
 def dev(krlib):
-    d = Device(krlib)
-    yield d
-    d.close()
+    """Device buffers of one test, freed at its end."""
+    with DeviceScope(krlib) as scope:
+        yield scope
+
+
+def upload(dev, a):
+    """A device copy of `a`, in a buffer of at least 8 bytes."""
+    a = np.ascontiguousarray(a)
+    return dev.upload(a) if a.nbytes >= 8 else dev.alloc(8)
+
+
+def device_words(dev, n, fill=0.0):
+    return upload(dev, np.full(n, fill))
+
+
+def fetch(dev, d, n, dtype=np.float64):
+    capi.check(dev.lib, dev.lib.kr_synchronize(None), "sync")
+    return dev.fetch(d, n, dtype)
 
 
 def hist_dict(words, nr):
     """The 5 nr + 1 words of the device histogram as the dict api.reduce_emissivity returns."""
-    assert np.isfinite(words[:nr]).all() and np.isfinite(words[5 * nr])
-    out = {"count": np.rint(words[:nr]).astype(np.int64), "disc_count": int(round(float(words[5 * nr])))}
-    assert np.array_equal(out["count"], words[:nr])                             # counts are whole numbers
-    for q, k in enumerate(rr.EMIS_SUMS):
-        out[k] = words[(q + 1) * nr:(q + 2) * nr]
+    raw = api._emissivity_layout(capi.EmisBins(nr=nr), words)                   # the planes and disc_count as they are, not yet cast
+    assert np.isfinite(raw["count"]).all() and np.isfinite(raw["disc_count"])
+    out = {"count": np.rint(raw["count"]).astype(np.int64), "disc_count": int(round(float(raw["disc_count"])))}
+    assert np.array_equal(out["count"], raw["count"])                           # counts are whole numbers
+    out.update({k: raw[k] for k in rr.EMIS_SUMS})
     return out
 
 
@@ -87,19 +69,19 @@ def margin(test, case, n, worst, **extra):
 
 
 def dev_emissivity(dev, b, d_rays, n, d_hist=None, first=0):
-    d_hist = d_hist or dev.words(5 * b.nr + 1)
+    d_hist = d_hist or device_words(dev, 5 * b.nr + 1)
     capi.check(dev.lib, dev.lib.kr_reduce_emissivity_dev_f64(C.byref(b), vp(d_rays.value + 144 * first), n, d_hist, None), "kr_reduce_emissivity_dev")
     return d_hist
 
 
 def dev_image(dev, b, d_rays, n, d_planes=None, first=0):
-    d_planes = d_planes or dev.words(7 * b.img_nx * b.img_ny + 1)
+    d_planes = d_planes or device_words(dev, 7 * b.img_nx * b.img_ny + 1)
     capi.check(dev.lib, dev.lib.kr_reduce_image_dev_f64(C.byref(b), vp(d_rays.value + 144 * first), n, d_planes, None), "kr_reduce_image_dev")
     return d_planes
 
 
 def dev_return(dev, b, d_rays, n, d_out=None, first=0):
-    d_out = d_out or dev.words(4)
+    d_out = d_out or device_words(dev, 4)
     capi.check(dev.lib, dev.lib.kr_reduce_return_dev_f64(C.byref(b), vp(d_rays.value + 144 * first), n, d_out, None), "kr_reduce_return_dev")
     return d_out
 
@@ -118,7 +100,7 @@ def test_emissivity_reducer_matches_the_rules(dev, case, size):
     for name, rays in sets:
         want = rr.reduce_emissivity(b, rays)
         label = f"{case}-{size}-{name}"
-        worst = rr.check_reduction(hist_dict(dev.fetch(dev_emissivity(dev, b, dev.upload(rays), len(rays)), 5 * b.nr + 1), b.nr), want, "count",
+        worst = rr.check_reduction(hist_dict(fetch(dev, dev_emissivity(dev, b, upload(dev, rays), len(rays)), 5 * b.nr + 1), b.nr), want, "count",
                                    rr.EMIS_SUMS, RTOL, label + " (device form)")
         if size == "small":
             worst = max(worst, rr.check_reduction(api.reduce_emissivity(b, np.ascontiguousarray(rays)), want, "count", rr.EMIS_SUMS, RTOL, label + " (host form)"))
@@ -133,7 +115,7 @@ def test_emissivity_linear_table_on_the_device(dev):
     rec, b = rc.small(), rc.emis_bins(4, 0)
     for v, want_bin in rc.LINEAR_TABLE:
         ray = rec.rays[rec.edge(f"r={v!r}"):][:1]
-        got = hist_dict(dev.fetch(dev_emissivity(dev, b, dev.upload(ray), 1), 21), 4)
+        got = hist_dict(fetch(dev, dev_emissivity(dev, b, upload(dev, ray), 1), 21), 4)
         assert got["disc_count"] == 1 and np.flatnonzero(got["count"]).tolist() == ([] if want_bin is None else [want_bin]), (v, got["count"])
 
 
@@ -147,7 +129,7 @@ def test_image_reducer_matches_the_rules(dev, case):
     for name, rays in (("all", small.rays), ("finite", small.rays[~small.poison]), ("large", large.rays)):
         want = rr.reduce_image(b, rays)
         label = f"{case}-{name}"
-        worst = rr.check_reduction(image_dict(dev.fetch(dev_image(dev, b, dev.upload(rays), len(rays)), 7 * npix + 1), b), want, "nrays", rr.IMAGE_SUMS,
+        worst = rr.check_reduction(image_dict(fetch(dev, dev_image(dev, b, upload(dev, rays), len(rays)), 7 * npix + 1), b), want, "nrays", rr.IMAGE_SUMS,
                                    RTOL, label + " (device form)")
         if name != "large":
             worst = max(worst, rr.check_reduction(api.reduce_image(b, np.ascontiguousarray(rays)), want, "nrays", rr.IMAGE_SUMS, RTOL, label + " (host form)"))
@@ -166,11 +148,11 @@ def test_image_edge_records_land_in_the_pixel_the_rules_name(dev, shape, flip):
     edges = rec.rays[rec.first_edge:rec.first_edge + len(rec.labels)]
     keep = rr.image_filter(b, edges)
     ok, _, _, px = rr.image_pixel(b, edges["alpha"], edges["beta"])
-    d_rays = dev.upload(edges)
-    d_planes = dev.words(len(edges) * (7 * npix + 1))
+    d_rays = upload(dev, edges)
+    d_planes = device_words(dev, len(edges) * (7 * npix + 1))
     for i in range(len(edges)):
         dev_image(dev, b, d_rays, 1, vp(d_planes.value + 8 * i * (7 * npix + 1)), first=i)
-    words = dev.fetch(d_planes, len(edges) * (7 * npix + 1)).reshape(len(edges), 7 * npix + 1)
+    words = fetch(dev, d_planes, len(edges) * (7 * npix + 1)).reshape(len(edges), 7 * npix + 1)
     for i, label in enumerate(rec.labels):
         hit = np.flatnonzero(words[i, :npix])
         want = [int(px[i])] if keep[i] and ok[i] else []
@@ -202,7 +184,7 @@ def test_return_reducer_matches_the_rules(krlib, dev, case):
         else:
             assert np.isfinite(want).all() and (want > 0).all()
         label = f"{case}-{name}"
-        worst = rr.check_return(dev.fetch(dev_return(dev, b, dev.upload(rays), len(rays)), 4), want, RTOL, not b.weight_norm, label + " (device form)")
+        worst = rr.check_return(fetch(dev, dev_return(dev, b, upload(dev, rays), len(rays)), 4), want, RTOL, not b.weight_norm, label + " (device form)")
         if not name.startswith("large"):
             out = (C.c_double * 4)()
             rays = np.ascontiguousarray(rays)
@@ -225,15 +207,15 @@ def test_return_batch_of_33_equals_the_single_calls_and_the_rules(krlib, dev):
     starts = np.concatenate([[0], np.cumsum(sizes)]).astype(int)
     cases = sorted(rc.return_cases())
     bins = (capi.ReturnBins * k)(*[rc.return_cases()[cases[j % 8]] for j in range(k)])
-    d_single, d_batch = dev.upload(rays), dev.upload(rays)
-    out_single, out_batch = dev.words(4 * k), dev.words(4 * k)
+    d_single, d_batch = upload(dev, rays), upload(dev, rays)
+    out_single, out_batch = device_words(dev, 4 * k), device_words(dev, 4 * k)
     for j in range(k):
         capi.check(lib, lib.kr_post_return_dev_f64(-math.pi, math.pi, C.byref(bins[j]), vp(d_single.value + 144 * int(starts[j])), sizes[j],
                                                    vp(out_single.value + 32 * j), None), "kr_post_return_dev")
     ptrs = (vp * k)(*[d_batch.value + 144 * int(starts[j]) for j in range(k)])
     outs = (vp * k)(*[out_batch.value + 32 * j for j in range(k)])
     capi.check(lib, lib.kr_post_return_batch_dev_f64(k, -math.pi, math.pi, bins, ptrs, (C.c_int64 * k)(*sizes), outs, None), "kr_post_return_batch_dev")
-    single, batch = dev.fetch(out_single, 4 * k).reshape(k, 4), dev.fetch(out_batch, 4 * k).reshape(k, 4)
+    single, batch = fetch(dev, out_single, 4 * k).reshape(k, 4), fetch(dev, out_batch, 4 * k).reshape(k, 4)
     worst = 0.0
     for j in range(k):
         b = bins[j]
@@ -246,7 +228,7 @@ def test_return_batch_of_33_equals_the_single_calls_and_the_rules(krlib, dev):
     wrapped["phi"] = rr.range_phi(rays["phi"], rays["steps"])
     assert (wrapped["phi"] != rays["phi"]).sum() > 1000
     for d in (d_single, d_batch):
-        assert parity.same_records(dev.fetch(d, len(rays), capi.RAY_F64), wrapped)
+        assert parity.same_records(fetch(dev, d, len(rays), capi.RAY_F64), wrapped)
     print(f"return batch: worst sum error {worst:.3g}")
     margin("test_return_batch_of_33_equals_the_single_calls_and_the_rules", "33 items", len(rays), worst)
 
@@ -263,11 +245,11 @@ def test_emissivity_reducer_adds_into_the_callers_buffer(dev, case):
     rays = rec.rays[~rec.poison]
     n, half, words = len(rays), len(rays) // 2 + 1, 5 * b.nr + 1
     want = rr.reduce_emissivity(b, rays)
-    d_rays = dev.upload(rays)
+    d_rays = upload(dev, rays)
     halves = dev_emissivity(dev, b, d_rays, half)
     dev_emissivity(dev, b, d_rays, n - half, halves, first=half)
-    filled = dev_emissivity(dev, b, d_rays, n, dev.words(words, PREFILL))
-    for name, h in (("halves", dev.fetch(halves, words)), ("prefilled", dev.fetch(filled, words) - PREFILL)):
+    filled = dev_emissivity(dev, b, d_rays, n, device_words(dev, words, PREFILL))
+    for name, h in (("halves", fetch(dev, halves, words)), ("prefilled", fetch(dev, filled, words) - PREFILL)):
         got = hist_dict(h, b.nr)
         if name == "prefilled":                                             # the subtraction costs the sums up to an ulp of the pre-fill: counts only
             assert np.array_equal(got["count"], want["count"]) and got["disc_count"] == want["disc_count"]
@@ -282,11 +264,11 @@ def test_image_reducer_adds_into_the_callers_buffer(dev, case):
     rays = rec.rays[~rec.poison]
     n, half, words = len(rays), len(rays) // 2 + 1, 7 * b.img_nx * b.img_ny + 1
     want = rr.reduce_image(b, rays)
-    d_rays = dev.upload(rays)
+    d_rays = upload(dev, rays)
     halves = dev_image(dev, b, d_rays, half)
     dev_image(dev, b, d_rays, n - half, halves, first=half)
-    filled = dev_image(dev, b, d_rays, n, dev.words(words, PREFILL))
-    for name, h in (("halves", dev.fetch(halves, words)), ("prefilled", dev.fetch(filled, words) - PREFILL)):
+    filled = dev_image(dev, b, d_rays, n, device_words(dev, words, PREFILL))
+    for name, h in (("halves", fetch(dev, halves, words)), ("prefilled", fetch(dev, filled, words) - PREFILL)):
         got = image_dict(h, b)
         if name == "prefilled":
             assert np.array_equal(got["nrays"], want["nrays"]) and got["disc_count"] == want["disc_count"]
@@ -298,14 +280,14 @@ def test_return_reducer_adds_into_the_callers_buffer(dev):
     rec = rc.small()
     rays = rec.return_rays[~rec.nan_weight]
     n, half = len(rays), len(rays) // 2 + 1
-    d_rays = dev.upload(rays)
+    d_rays = upload(dev, rays)
     for case in ("iso0-limb0-norm0", "iso1-limb1-norm1"):
         b = rc.return_cases()[case]
         want = rr.reduce_return(b, rays)
         halves = dev_return(dev, b, d_rays, half)
         dev_return(dev, b, d_rays, n - half, halves, first=half)
-        margin("test_return_reducer_adds_into_the_callers_buffer", case, n, rr.check_return(dev.fetch(halves, 4), want, RTOL, not b.weight_norm, case))
-        filled = dev.fetch(dev_return(dev, b, d_rays, n, dev.words(4, PREFILL)), 4) - PREFILL
+        margin("test_return_reducer_adds_into_the_callers_buffer", case, n, rr.check_return(fetch(dev, halves, 4), want, RTOL, not b.weight_norm, case))
+        filled = fetch(dev, dev_return(dev, b, d_rays, n, device_words(dev, 4, PREFILL)), 4) - PREFILL
         if not b.weight_norm and not b.plane_iso and not b.limb:            # whole numbers: exact
             assert np.array_equal(filled, want)
 
@@ -326,17 +308,17 @@ def test_fused_emissivity_pass_equals_the_separate_passes(krlib, dev, case):
     b = rc.emis_cases()[case]
     rays = fused_records("ps_h5", "rk4")
     n, words = len(rays), 5 * b.nr + 1
-    d_sep, d_fused = dev.upload(rays), dev.upload(rays)
-    h_sep, h_fused = dev.words(words), dev.words(words)
+    d_sep, d_fused = upload(dev, rays), upload(dev, rays)
+    h_sep, h_fused = device_words(dev, words), device_words(dev, words)
     capi.check(lib, lib.kr_range_phi_dev_f64(-np.pi, np.pi, d_sep, n, None), "range_phi")
     capi.check(lib, lib.kr_redshift_dev_f64(gc.SPIN, -1.0, 0, 0, 0, d_sep, n, None), "redshift")
     capi.check(lib, lib.kr_reduce_emissivity_dev_f64(C.byref(b), d_sep, n, h_sep, None), "reduce")
     capi.check(lib, lib.kr_post_emissivity_dev_f64(gc.SPIN, -1.0, 0, 0, 0, -np.pi, np.pi, C.byref(b), d_fused, n, h_fused, None), "post")
-    sep, fused = dev.fetch(d_sep, n, capi.RAY_F64), dev.fetch(d_fused, n, capi.RAY_F64)
+    sep, fused = fetch(dev, d_sep, n, capi.RAY_F64), fetch(dev, d_fused, n, capi.RAY_F64)
     assert parity.same_records(sep, fused)
     assert (sep["phi"] != rays["phi"]).sum() > 1000 and (sep["redshift"] > 0).sum() > rc.N_CONTENTION
     want = rr.reduce_emissivity(b, sep)
-    worst = max(rr.check_reduction(hist_dict(dev.fetch(h, words), b.nr), want, "count", rr.EMIS_SUMS, RTOL, (case, name)) for name, h in (("separate", h_sep), ("fused", h_fused)))
+    worst = max(rr.check_reduction(hist_dict(fetch(dev, h, words), b.nr), want, "count", rr.EMIS_SUMS, RTOL, (case, name)) for name, h in (("separate", h_sep), ("fused", h_fused)))
     assert want["disc_count"] > rc.N_CONTENTION and (case == "log-rmin-negative" or want["count"].max() >= rc.N_CONTENTION)
     margin("test_fused_emissivity_pass_equals_the_separate_passes", case, n, worst, on_disc=want["disc_count"])
 
@@ -348,16 +330,16 @@ def test_fused_image_pass_equals_the_separate_passes(krlib, dev, case):
     b = rc.image_cases()[case]
     rays = fused_records("ip16", "rk4")
     n, words = len(rays), 7 * b.img_nx * b.img_ny + 1
-    d_sep, d_fused = dev.upload(rays), dev.upload(rays)
-    p_sep, p_fused = dev.words(words), dev.words(words)
+    d_sep, d_fused = upload(dev, rays), upload(dev, rays)
+    p_sep, p_fused = device_words(dev, words), device_words(dev, words)
     capi.check(lib, lib.kr_redshift_dev_f64(-gc.SPIN, -1.0, 1, 0, 0, d_sep, n, None), "redshift")
     capi.check(lib, lib.kr_range_phi_dev_f64(-np.pi, np.pi, d_sep, n, None), "range_phi")
     capi.check(lib, lib.kr_reduce_image_dev_f64(C.byref(b), d_sep, n, p_sep, None), "reduce")
     capi.check(lib, lib.kr_post_image_dev_f64(-gc.SPIN, -1.0, 1, 0, 0, -np.pi, np.pi, C.byref(b), d_fused, n, p_fused, None), "post")
-    sep, fused = dev.fetch(d_sep, n, capi.RAY_F64), dev.fetch(d_fused, n, capi.RAY_F64)
+    sep, fused = fetch(dev, d_sep, n, capi.RAY_F64), fetch(dev, d_fused, n, capi.RAY_F64)
     assert parity.same_records(sep, fused)
     assert (sep["phi"] != rays["phi"]).sum() > 1000
     want = rr.reduce_image(b, sep)
-    worst = max(rr.check_reduction(image_dict(dev.fetch(p, words), b), want, "nrays", rr.IMAGE_SUMS, RTOL, (case, name)) for name, p in (("separate", p_sep), ("fused", p_fused)))
+    worst = max(rr.check_reduction(image_dict(fetch(dev, p, words), b), want, "nrays", rr.IMAGE_SUMS, RTOL, (case, name)) for name, p in (("separate", p_sep), ("fused", p_fused)))
     assert want["nrays"].max() >= rc.N_CONTENTION
     margin("test_fused_image_pass_equals_the_separate_passes", case, n, worst, counted=want["disc_count"])

@@ -24,7 +24,8 @@ import reducer_cases as rc
 import reducer_rules as rr
 import return_map_rules as rm
 from raytrace_cpu_amd import api, capi
-from test_gpu_reducers import Device
+from raytrace_cpu_amd.devmem import DeviceScope
+from test_gpu_reducers import device_words, fetch, upload
 
 pytestmark = pytest.mark.gpu
 vp = C.c_void_p
@@ -37,9 +38,9 @@ PASS = (gc.SPIN, -1.0, 0, 0, 0) + WRAP
 
 @pytest.fixture
 def dev(krlib):
-    d = Device(krlib)
-    yield d
-    d.close()
+    """Device buffers of one test, freed at its end."""
+    with DeviceScope(krlib) as scope:
+        yield scope
 
 
 def landing_map(case, nr, logbin):
@@ -59,21 +60,20 @@ def check(got, want, m, label):
 
 
 def dev_reduce(dev, m, d_rays, n, d_out=None, first=0):
-    d_out = d_out or dev.words(5 * m.nr + 6)
+    d_out = d_out or device_words(dev, 5 * m.nr + 6)
     capi.check(dev.lib, dev.lib.kr_reduce_return_map_dev_f64(C.byref(m), vp(d_rays.value + 144 * first), n, d_out, None), "kr_reduce_return_map_dev")
     return d_out
 
 
 def fetch_map(dev, m, d_out):
-    return api.return_map_from_words(m, dev.fetch(d_out, 5 * m.nr + 6))
+    return api.return_map_from_words(m, fetch(dev, d_out, 5 * m.nr + 6))
 
 
 # ---- the reducing forms ---------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def small_on_device(krlib):
-    d = Device(krlib)
-    yield d.upload(rc.small().return_rays)
-    d.close()
+    with DeviceScope(krlib) as scope:
+        yield upload(scope, rc.small().return_rays)
 
 
 REDUCE_CASES = [(case, nr, lb) for case in sorted(rc.return_cases()) for nr in NRS for lb in (0, 1)]
@@ -100,7 +100,7 @@ def test_reduce_form_on_the_large_set(dev):
     assert len(rays) > 1024 * 256 and len(rays) % 256
     m = landing_map("iso1-limb1-norm1", 7, 1)
     want = rm.reduce_return_map(m, rays)
-    worst = check(fetch_map(dev, m, dev_reduce(dev, m, dev.upload(rays), len(rays))), want, m, "large")
+    worst = check(fetch_map(dev, m, dev_reduce(dev, m, upload(dev, rays), len(rays))), want, m, "large")
     assert want["binned"] > 10 * rc.N_CONTENTION
     margin("test_reduce_form_on_the_large_set", "iso1-limb1-norm1-log-nr7", len(rays), worst, binned=want["binned"])
 
@@ -113,11 +113,11 @@ def test_reduce_form_adds_into_the_callers_buffer(dev, nr):
     m = landing_map("iso0-limb0-norm0", nr, 1)
     n, half, words, prefill = len(rays), len(rays) // 2 + 1, 5 * nr + 6, 1000.0
     want = rm.reduce_return_map(m, rays)
-    d_rays = dev.upload(rays)
+    d_rays = upload(dev, rays)
     halves = dev_reduce(dev, m, d_rays, half)
     dev_reduce(dev, m, d_rays, n - half, halves, first=half)
     margin("test_reduce_form_adds_into_the_callers_buffer", f"nr{nr}", n, check(fetch_map(dev, m, halves), want, m, "halves"))
-    filled = api.return_map_from_words(m, dev.fetch(dev_reduce(dev, m, d_rays, n, dev.words(words, prefill)), words) - prefill)
+    filled = api.return_map_from_words(m, fetch(dev, dev_reduce(dev, m, d_rays, n, device_words(dev, words, prefill)), words) - prefill)
     assert np.array_equal(filled["count"], want["count"]) and np.array_equal(filled["weight"], want["count"])     # unit weights: whole numbers, exact
     assert filled["on_disc"] == want["on_disc"] and filled["binned"] == want["binned"] and np.array_equal(rm.scalars_of(filled), want["scalars"])
 
@@ -140,13 +140,13 @@ def test_fused_pass_equals_the_separate_passes(krlib, dev, case, nr, logbin):
     m = landing_map(case, nr, logbin)
     rays = records_with_a_poisoned_redshift()
     n = len(rays)
-    d_sep, d_fused = dev.upload(rays), dev.upload(rays)
+    d_sep, d_fused = upload(dev, rays), upload(dev, rays)
     capi.check(lib, lib.kr_range_phi_dev_f64(*WRAP, d_sep, n, None), "range_phi")
     capi.check(lib, lib.kr_redshift_dev_f64(gc.SPIN, -1.0, 0, 0, 0, d_sep, n, None), "redshift")
     o_sep = dev_reduce(dev, m, d_sep, n)
-    o_fused = dev.words(5 * nr + 6)
+    o_fused = device_words(dev, 5 * nr + 6)
     capi.check(lib, lib.kr_post_return_map_dev_f64(*PASS, C.byref(m), d_fused, n, o_fused, None), "kr_post_return_map_dev")
-    sep, fused = dev.fetch(d_sep, n, capi.RAY_F64), dev.fetch(d_fused, n, capi.RAY_F64)
+    sep, fused = fetch(dev, d_sep, n, capi.RAY_F64), fetch(dev, d_fused, n, capi.RAY_F64)
     assert parity.same_records(sep, fused)
     live = rays["steps"] > 0
     assert (sep["phi"] != rays["phi"]).sum() > 1000 and (sep["redshift"][live] > 0).sum() > rc.N_CONTENTION
@@ -179,16 +179,16 @@ def test_batch_of_49_equals_the_single_calls(krlib, dev):
         m.cls.limb = j % 2
         maps.append(m)
     offs = np.concatenate([[0], np.cumsum([5 * m.nr + 6 for m in maps])]).astype(int)
-    d_single, d_batch = dev.upload(rays), dev.upload(rays)
-    o_single, o_batch = dev.words(int(offs[-1])), dev.words(int(offs[-1]))
+    d_single, d_batch = upload(dev, rays), upload(dev, rays)
+    o_single, o_batch = device_words(dev, int(offs[-1])), device_words(dev, int(offs[-1]))
     for j in range(k):
         capi.check(lib, lib.kr_post_return_map_dev_f64(*PASS, C.byref(maps[j]), vp(d_single.value + 144 * int(starts[j])), sizes[j],
                                                        vp(o_single.value + 8 * int(offs[j])), None), "kr_post_return_map_dev")
     ptrs = (vp * k)(*[d_batch.value + 144 * int(starts[j]) for j in range(k)])
     outs = (vp * k)(*[o_batch.value + 8 * int(offs[j]) for j in range(k)])
     capi.check(lib, lib.kr_post_return_map_batch_dev_f64(k, *PASS, (capi.ReturnMap * k)(*maps), ptrs, (C.c_int64 * k)(*sizes), outs, None), "kr_post_return_map_batch_dev")
-    single, batch = dev.fetch(o_single, int(offs[-1])), dev.fetch(o_batch, int(offs[-1]))
-    assert parity.same_records(dev.fetch(d_single, len(rays), capi.RAY_F64), dev.fetch(d_batch, len(rays), capi.RAY_F64))
+    single, batch = fetch(dev, o_single, int(offs[-1])), fetch(dev, o_batch, int(offs[-1]))
+    assert parity.same_records(fetch(dev, d_single, len(rays), capi.RAY_F64), fetch(dev, d_batch, len(rays), capi.RAY_F64))
     worst, binned = 0.0, 0
     for j in range(k):
         m = maps[j]
@@ -202,7 +202,7 @@ def test_batch_of_49_equals_the_single_calls(krlib, dev):
         else:
             assert b["ray_count"] > 0
     # the last item (the contention block) and a small one of each nr against the rules as well
-    sep = dev.fetch(d_batch, len(rays), capi.RAY_F64)
+    sep = fetch(dev, d_batch, len(rays), capi.RAY_F64)
     for j in (0, 1, 2, k - 1):
         want = rm.reduce_return_map(maps[j], sep[starts[j]:starts[j + 1]])
         worst = max(worst, check(api.return_map_from_words(maps[j], batch[offs[j]:offs[j + 1]]), want, maps[j], (j, "batch against the rules")))

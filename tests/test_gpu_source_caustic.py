@@ -18,8 +18,9 @@ import fits_lite
 import oracle_lib as ol
 import parity
 import source_caustic_rules as sr
-from caustic_testlib import COORD_ULPS, FIXTURES, OFF, SHAPES, Dev, bundle_identity_mask, same_bits, spec_of, synthetic
+from caustic_testlib import COORD_ULPS, FIXTURES, OFF, SHAPES, bundle_identity_mask, same_bits, spec_of, synthetic
 from raytrace_cpu_amd import api, capi
+from raytrace_cpu_amd.devmem import DeviceScope
 from test_gpu_dropin_apps import COUNT_KEYS, NATIVE
 
 pytestmark = pytest.mark.gpu
@@ -30,15 +31,15 @@ INCL, PHI0 = math.radians(30.0), 0.25
 
 @pytest.fixture
 def dev(krlib):
-    d = Dev(krlib)
-    yield d
-    d.close()
+    """Device buffers of one test, freed at its end."""
+    with DeviceScope(krlib) as scope:
+        yield scope
 
 
 def run_maps(dev, sm, rays, n=None):
     """kr_post_caustic_source_dev_f64 on a host array of records: uploaded, d_maps prefilled with 0xFF (the call must WRITE every word), the records
     read back afterwards (the call must not touch them).  Returns the words."""
-    L = dev.L
+    L = dev.lib
     n = len(rays) if n is None else n
     d = dev.alloc(max(rays.nbytes, 144))
     capi.check(L, L.kr_memcpy_h2d(d, ol.ptr(rays), rays.nbytes), "h2d")
@@ -46,8 +47,8 @@ def run_maps(dev, sm, rays, n=None):
     d_maps = dev.alloc(nw * 8)
     capi.check(L, L.kr_memset(d_maps, 0xff, nw * 8), "kr_memset")
     capi.check(L, L.kr_post_caustic_source_dev_f64(C.byref(sm), d, n, d_maps, None), "kr_post_caustic_source")
-    words = dev.doubles(d_maps, nw)
-    after = dev.rays(d, len(rays))
+    words = dev.fetch(d_maps, nw)
+    after = dev.fetch(d, len(rays), capi.RAY_F64)
     assert after.tobytes() == rays.tobytes(), "the pass modified the records"
     return words
 
@@ -252,7 +253,7 @@ def geometry(plane, case, integrator):
 
 def device_records(dev, g, kind, integrator):
     """device-built, device-traced (strict) records of the plane g -> (d_rays, n, sm, scale)"""
-    L, spec = dev.L, spec_of(g)
+    L, spec = dev.lib, spec_of(g)
     bundles = g["eps_frac"] > 0
     n, nx, ny = api.bundles_count(spec) if bundles else api.imageplane_count(spec)
     assert (nx, ny) == (g["nx"], g["ny"])
@@ -277,17 +278,17 @@ def test_source_map_kernels_match_the_rules_on_the_same_records(dev, plane, inte
     of test_gpu_caustic.py::test_map_kernels_match_the_rules_on_the_same_records and c = 1e-12 scale (scale = pi / r_max): integers, NaN / SENTINEL
     positions, counts and THETA_S equal; coordinates within c; DET_J within det_bound; SIGN_J wherever |det| is not below that bound; ambiguous pixels
     (those, and for the sphere a raw phi difference within c of +-pi) at most 0.1 % of the hits, none on the golden RK4 plane."""
-    L, kind = dev.L, KIND_OF[case]
+    L, kind = dev.lib, KIND_OF[case]
     method = capi.RK4 if integrator == "rk4" else capi.RK45
     g = geometry(plane, case, method)
     d, n, sm, scale = device_records(dev, g, kind, method)
-    traced = dev.rays(d, n)
+    traced = dev.fetch(d, n, capi.RAY_F64)
     nw = api.source_caustic_words(sm)
     d_maps = dev.alloc(nw * 8)
     capi.check(L, L.kr_memset(d_maps, 0xff, nw * 8), "kr_memset")
     capi.check(L, L.kr_post_caustic_source_dev_f64(C.byref(sm), d, n, d_maps, None), "kr_post_caustic_source")
-    words = dev.doubles(d_maps, nw)
-    assert dev.rays(d, n).tobytes() == traced.tobytes()
+    words = dev.fetch(d_maps, nw)
+    assert dev.fetch(d, n, capi.RAY_F64).tobytes() == traced.tobytes()
     c = 1e-12 * scale
     got, want, facts = judge(kind, bool(sm.bundles), sm, words, traced, c, g.get("incl_rad", 0.0), g["phi0"])
     print(plane, integrator, case, facts)
@@ -372,11 +373,11 @@ def test_native_source_caustic_apps_match_cpu_output(case):
 # ---- 5. the same answer as the reference's programs on the host mirror -----------------------------------------------------------------------------
 def grid_identity_mask(dev, g, tmp_path):
     """[nx, ny]: True where the device-built ray of the pixel carries the bits of the host mirror's ImagePlane constructor in every field"""
-    L, spec = dev.L, spec_of(g)
+    L, spec = dev.lib, spec_of(g)
     n, nx, ny = api.imageplane_count(spec)
     d = dev.alloc(n * 144)
     capi.check(L, L.kr_imageplane_init_dev_f64(C.byref(spec), d, n, None), "kr_imageplane_init")
-    got = dev.rays(d, n)
+    got = dev.fetch(d, n, capi.RAY_F64)
     exe = os.path.join(ROOT, "tests", "cpp", "host_ctor_dump")
     subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "cpp"), exe])
     out = tmp_path / "ip.bin"

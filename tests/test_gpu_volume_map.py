@@ -18,6 +18,7 @@ import golden_cases as gc
 import parity
 import volume_map_rules as vr
 from raytrace_cpu_amd import api, capi
+from raytrace_cpu_amd.devmem import DeviceScope
 
 pytestmark = pytest.mark.gpu
 
@@ -173,29 +174,19 @@ def test_adds_and_does_not_overwrite():
     m = grid(12, 8, 12, 0)
     nw = api.volume_words(m)
     single = api.trace_volume(p, init, m)
-    d_rays, d_map = C.c_void_p(), C.c_void_p()
-    try:
-        capi.check(L, L.kr_malloc(C.byref(d_rays), init.nbytes), "kr_malloc")
-        capi.check(L, L.kr_malloc(C.byref(d_map), nw * 8), "kr_malloc")
-        capi.check(L, L.kr_memset(d_map, 0, nw * 8), "kr_memset")
+    with DeviceScope(L) as dev:
+        d_rays, d_map = dev.alloc(init.nbytes), dev.zeros(nw * 8)
         st = capi.Stats()
         for _ in range(2):
             capi.check(L, L.kr_memcpy_h2d(d_rays, init.ctypes.data_as(C.c_void_p), init.nbytes), "h2d")
             capi.check(L, L.kr_trace_volume_dev_f64(C.byref(p), C.byref(m), d_rays, len(init), d_map, None, C.byref(st)), "kr_trace_volume_dev")
-        words = np.zeros(nw)
-        capi.check(L, L.kr_memcpy_d2h(words.ctypes.data_as(C.c_void_p), d_map, words.nbytes), "d2h")
+        words = dev.fetch(d_map, nw)
         twice = api.volume_from_words(m, words)
         assert not vr.compare(twice, vr.add_maps(single, single), parity.BIN_RTOL)
         assert st.rays_traced == single["stats"]["rays_traced"] and st.steps_total == single["stats"]["steps_total"] and st.kernel_ms > 0
         # n = 0: the map is left untouched, whatever it holds
         capi.check(L, L.kr_trace_volume_dev_f64(C.byref(p), C.byref(m), None, 0, d_map, None, C.byref(st)), "kr_trace_volume_dev n = 0")
-        again = np.zeros(nw)
-        capi.check(L, L.kr_memcpy_d2h(again.ctypes.data_as(C.c_void_p), d_map, again.nbytes), "d2h")
-        assert again.tobytes() == words.tobytes() and st.rays_total == 0 and st.rays_traced == 0
-    finally:
-        for d in (d_rays, d_map):
-            if d.value:
-                L.kr_free(d)
+        assert dev.fetch(d_map, nw).tobytes() == words.tobytes() and st.rays_total == 0 and st.rays_traced == 0
     empty = api.trace_volume(p, np.zeros(0, dtype=capi.RAY_F64), m)
     assert empty["count"].sum() == 0 and empty["rows"] == 0
 

@@ -20,6 +20,7 @@ import golden_cases as gc
 import parity
 import volume_observe_rules as vo
 from raytrace_cpu_amd import api, capi
+from raytrace_cpu_amd.devmem import DeviceScope
 
 pytestmark = pytest.mark.gpu
 
@@ -216,20 +217,14 @@ def test_adds_and_does_not_overwrite_and_image_is_optional():
     no_image = api.trace_observe(p, init, m, b, emis, kappa, delay, want_image=False)
     assert no_image["image"] is None and np.array_equal(no_image["hits"], single["hits"]) and not vo.compare(no_image, single, parity.BIN_RTOL)
     ptr = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
-    bufs = {k: C.c_void_p() for k in ("rays", "out", "emis", "kappa", "delay")}
-    try:
-        for k, nbytes in (("rays", init.nbytes), ("out", nw * 8), ("emis", emis.nbytes), ("kappa", kappa.nbytes), ("delay", delay.nbytes)):
-            capi.check(L, L.kr_malloc(C.byref(bufs[k]), nbytes), "kr_malloc")
-        for k, a in (("emis", emis), ("kappa", kappa), ("delay", delay)):
-            capi.check(L, L.kr_memcpy_h2d(bufs[k], ptr(a), a.nbytes), "h2d")
-        capi.check(L, L.kr_memset(bufs["out"], 0, nw * 8), "kr_memset")
+    with DeviceScope(L) as dev:
+        bufs = {"rays": dev.alloc(init.nbytes), "out": dev.zeros(nw * 8), "emis": dev.upload(emis), "kappa": dev.upload(kappa), "delay": dev.upload(delay)}
         st = capi.Stats()
         for _ in range(2):          # d_image = NULL
             capi.check(L, L.kr_memcpy_h2d(bufs["rays"], ptr(init), init.nbytes), "h2d")
             capi.check(L, L.kr_trace_observe_dev_f64(C.byref(p), C.byref(m), C.byref(b), bufs["emis"], bufs["kappa"], bufs["delay"], bufs["rays"], len(init), bufs["out"],
                                                      None, None, C.byref(st)), "kr_trace_observe_dev")
-        words = np.zeros(nw)
-        capi.check(L, L.kr_memcpy_d2h(ptr(words), bufs["out"], words.nbytes), "d2h")
+        words = dev.fetch(bufs["out"], nw)
         twice = api.observe_from_words(b, words)
         twice["image"] = None
         doubled = {k: 2 * single[k] for k in vo.TALLIES + ("hits", "spectrum", "response")}
@@ -237,13 +232,7 @@ def test_adds_and_does_not_overwrite_and_image_is_optional():
         assert st.rays_traced == single["stats"]["rays_traced"] and st.steps_total == single["stats"]["steps_total"] and st.kernel_ms > 0
         # n = 0: the output is left untouched, whatever it holds
         capi.check(L, L.kr_trace_observe_dev_f64(C.byref(p), C.byref(m), C.byref(b), bufs["emis"], None, None, None, 0, bufs["out"], None, None, C.byref(st)), "n = 0")
-        again = np.zeros(nw)
-        capi.check(L, L.kr_memcpy_d2h(ptr(again), bufs["out"], again.nbytes), "d2h")
-        assert again.tobytes() == words.tobytes() and st.rays_total == 0 and st.rays_traced == 0
-    finally:
-        for d in bufs.values():
-            if d.value:
-                L.kr_free(d)
+        assert dev.fetch(bufs["out"], nw).tobytes() == words.tobytes() and st.rays_total == 0 and st.rays_traced == 0
     empty = api.trace_observe(p, np.zeros(0, dtype=capi.RAY_F64), m, b, emis)
     assert empty["spectrum"].sum() == 0 and empty["rows"] == 0 and len(empty["image"]) == 0
 
