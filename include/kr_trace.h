@@ -488,6 +488,92 @@ typedef struct kr_crossing_spec {
 static_assert(sizeof(kr_crossing_spec) == 32, "kr_crossing_spec is 32 bytes (raytrace_cpu_amd/capi.py CrossingSpec)");
 #endif
 
+/* PointSourceVel<T> ctor arguments (pointsource_vel.h, pointsource_vel.cpp:11-110): a point source whose emitter has ANY timelike four-velocity -- an
+ * orbiting and outflowing corona, a blob plunging inside the ISCO, a source drifting in theta -- sampled on the (cos alpha, beta) grid of kr_pointsource.
+ *   count      rays = (int) ((((cosalphamax - cosalpha0) / dcosalpha) + 1) * (((betamax - beta0) / dbeta) + 1)), the int-truncated PRODUCT of doubles (:12);
+ *              n_cosalpha, n_beta the truncated factors (:15-16).  Ray ix = i n_beta + j; slots from n_cosalpha n_beta on are unused (steps = -1).
+ *   tetrad     SolveTetrad (:113-260), once per call ON THE HOST in plain C++ (csrc/kr_vel_tetrad.hpp), sin / cos / tan of pos[2] from the C library, every
+ *              other line one IEEE operation in the reference's association:
+ *                metric    rhosq = r r + (a cos)(a cos);  delta = r r - 2 r + a a;  sigmasq = (r r + a a)(r r + a a) - a a delta sin sin;
+ *                          e2nu = rhosq delta / sigmasq;  e2psi = sigmasq sin sin / rhosq;  omega = 2 a r / sigmasq;
+ *                          g00 = e2nu - omega omega e2psi, g03 = g30 = omega e2psi, g11 = -rhosq / delta, g22 = -rhosq, g33 = -e2psi
+ *                start     v0 = u AS GIVEN (not normalised), v1 = d_r, v2 = d_theta, v3 = d_phi -- the radial one first
+ *                G-S       e_i = v_i - sum_{j<i} (g(v_i, e_j) / g(e_j, e_j)) e_j, the projections of v_i (classical Gram-Schmidt) subtracted in the order
+ *                          j = 0, 1, 2;  g(x, y) = the sum over all sixteen (a, b) in row-major order, zeros included, of (g_ab x^a) y^b
+ *                normalise e_i /= sqrt(|g(e_i, e_i)|), component by component
+ *                permute   leg 0 = e_0, leg 3 = e_1, leg 1 = e_2, leg 2 = e_3
+ *                signs     leg 1 negated if its theta component < 0, leg 2 if its phi component < 0, leg 3 if its r component < 0
+ *              so leg 1 has a positive theta component, leg 2 a positive phi component, leg 3 a positive r component.  kr_pointsource_vel_tetrad returns it.
+ *   record     InitPointSourceVel (:34-110) against this record, each step literal.  cosalpha = cosalpha0 + i dcosalpha, beta = beta0 + j dbeta.
+ *              cosalpha >= cosalphamax or beta >= betamax: the record is zeroed with steps = -1.  DIFFERS from the reference, which RETURNS from the whole
+ *              constructor at the first such ray (:50) and leaves every later ray unbuilt; here only that ray is marked, the PointSource rule
+ *              (pointsource.cpp:40-44).  Otherwise the record is zeroed, then t, r, theta, phi = pos; steps = 0; alpha = cosalpha (sic, as PointSource),
+ *              beta = beta; rdot_flips = equatorial_crossings = status = 0, and with alpha = acos(cosalpha):
+ *                p' = {E, E sin(alpha) cos(beta), E sin(alpha) sin(beta), E cos(alpha)}        (products left to right; cos(alpha) of the acos, not cosalpha)
+ *                tdot = p'0 leg0[t] + p'1 leg1[t] + p'2 leg2[t] + p'3 leg3[t], summed left to right; rdot, thetadot, phidot likewise with [r], [theta], [phi]
+ *                k = (1 - 2 r / rhosq) tdot + (2 a r sin sin / rhosq) phidot
+ *                h = phidot ((r r + a a)(r r + a a cos cos - 2 r) sin sin + 2 a a r sin sin sin sin);  h = h - 2 a r k sin sin;  h = h / (r r + a a cos cos - 2 r)
+ *                Q = rhosq rhosq thetadot thetadot - (a k cos + h / tan)(a k cos - h / tan)
+ *                rdot_sign = rdot > 0 ? 1 : -1, thetadot_sign = thetadot > 0 ? 1 : -1
+ *              acos is the correctly rounded routine of csrc/kr_crmath.hpp, sin / cos of alpha and beta those of csrc/kr_sincos.hpp (on the device); sin, cos,
+ *              tan of pos[2] are the host C library's values; no contraction.
+ *   emit       (the _init_emit form)  the photon's energy in the emitter's OWN frame, g_ab u^a p^b:  N = g(u, u) of the input u by the sum above;
+ *              un[a] = u[a] / sqrt(N) (host, four divisions);  p = (tdot, rdot, thetadot, phidot) as the tetrad launched the photon;  emit = the sum over
+ *              all sixteen (a, b) in row-major order, zeros included, of (g_ab un^a) p^b, starting from 0.  It is E to rounding on every ray.
+ *              DIFFERS from the reference on purpose, as the HEALPix source's moving emitter does: PointSourceVel::RedshiftStart (:263-269) calls
+ *              Raytracer::RedshiftStart(velocity), the frame of an ORBIT of angular velocity `velocity` whatever the emitter's motion.
+ *   refused    (KR_EINVAL, message in kr_last_error, before any device work)  a null pointer, n < 0;  n that is not the spec's ray count;  a non-finite
+ *              pos or u;  u that is not timelike, g(u, u) <= 0 or NaN;  u^t <= 0;  r <= horizon = 1 + sqrt((1 - a)(1 + a)) (or a NaN horizon);  a grid whose
+ *              ray count is negative, NaN or beyond int. */
+typedef struct kr_pointsource_vel_spec {
+    double pos[4];
+    double u[4];             /* contravariant (u^t, u^r, u^theta, u^phi); need not be normalised */
+    double spin, tol, E;     /* tol: carried for the constructor's signature (the trace reads kr_params) */
+    double dcosalpha, dbeta;
+    double cosalpha0, cosalphamax, beta0, betamax;
+} kr_pointsource_vel_spec;
+#ifdef __cplusplus
+static_assert(sizeof(kr_pointsource_vel_spec) == 136, "kr_pointsource_vel_spec is 136 bytes (raytrace_cpu_amd/capi.py PointSourceVelSpec)");
+#endif
+
+/* Where the rays of ONE source end, by emission angle: the loop of src/return_radiation/disc_source_return_angdist.cpp:132-196 (a program that is stale
+ * in the reference: it calls map_results, ray_cosalpha and ray_beta, which no longer exist) against the live record fields.  Per record with steps > 0,
+ * with c = rays[].alpha (which holds cos alpha) and beta = rays[].beta:
+ *   bad_g      += 1 when rays[].redshift is not > 0 (the reference does not compute it, :125-128; nothing else reads it)
+ *   skipped    c == 0: skipped += 1 and nothing else (:136)
+ *   angles     alpha = acos(c);  s = sin(alpha) sin(beta);  norm = acos(|s|);  az = acos(-c / sqrt(1 - s s)), negated when sin(alpha) cos(beta) < 0.
+ *              acos / sin / cos are the correctly rounded routines of csrc/kr_crmath.hpp / csrc/kr_sincos.hpp.
+ *   labels     The rule above is the reference's, for records of kr_pointsource (labels = 0): calculate_constants puts sin(alpha) cos(beta) on its leg
+ *              along +phi and sin(alpha) sin(beta) on -theta, so |s| is the cosine of the angle to the disc normal.  SolveTetrad's leg 1 is +theta and
+ *              its leg 2 +phi: the ray (alpha, beta) of kr_pointsource_vel_spec is the ray (alpha, beta - pi/2) of kr_pointsource.  labels = 1 (an
+ *              extension) reads such records: sin(beta) is replaced by -1 cos(beta) and cos(beta) by sin(beta) in s and in the sign test of az --
+ *              both exact -- so norm and az keep their meaning; the alpha and beta histograms bin the stored values either way.
+ *   bins       Nangle = (int) (2 pi / dangle);  bin(x) = (int) q with q = (x + pi) / dangle, M_PI as a double.  The test is made on q itself, the index
+ *              rule of kr_emis_bins: the ray is binned iff -1 < q < Nangle for ALL FOUR angles.  Otherwise -- a NaN angle (az at |s| = 1, or where
+ *              rounding takes |c / sqrt(1 - s s)| past 1), beta outside [-pi, pi) -- out_of_range += 1 and the ray is in no histogram and no sum.
+ *              DIFFERS from the reference, which would index its arrays out of bounds there.
+ *   weight     w = plane_iso ? |s| : 1, times 1 + 2.06 |s| with limb (cls.plane_iso, cls.limb);  ray_count += cls.weight_norm ? w : 1
+ *   totals     total_norm[bin(norm)] += 1, total_az[bin(az)] += 1 (:156-157: unweighted)
+ *   class      the rule of kr_return_bins, exactly as kr_reduce_return_f64 and the landing map apply it, phi as stored:
+ *                return  theta >= pi/2, r_isco <= r < r_disc, and |r - source_r| > 0.1 source_r or |phi - source_phi| > 0.1
+ *                escape  not on the disc and r > r_esc;   lost  not on the disc, not escaped, r < r_isco;   anything else: other += 1
+ *              (the reference has the self-zone test commented out, :161; source_r = 0 switches it off here.)  A classified ray adds w to its class sum
+ *              and to hist[class][alpha][bin(alpha)], [beta][bin(beta)], [norm][bin(norm)], [az][bin(az)].
+ * Output: double[14 Nangle + 8], ADDED into (zero it once; beta-halves, shards and several sources sum):
+ *   [escape: alpha | beta | norm | az] [return: alpha | beta | norm | az] [lost: alpha | beta | norm | az] [total_norm | total_az]   (Nangle each)
+ *   {ray_count, escape, return, lost, other, skipped, out_of_range, bad_g}                                                             (counts as doubles)
+ * The per-bin normalisation of the az histograms (:200-209) is left to the caller.
+ * Refused (KR_EINVAL): a null pointer, n < 0, dangle that is not positive or gives Nangle < 1 or > 4096, labels not 0 or 1. */
+typedef struct kr_angdist_spec {
+    kr_return_bins cls;      /* classification and ray weight: kr_reduce_return_f64's (with labels = 1 the weight's |s| is the relabelled one) */
+    double dangle;
+    int32_t labels;          /* 0: records of kr_pointsource (the reference's rule); 1: records of kr_pointsource_vel_spec */
+    int32_t pad;
+} kr_angdist_spec;
+#ifdef __cplusplus
+static_assert(sizeof(kr_angdist_spec) == 72, "kr_angdist_spec is 72 bytes (raytrace_cpu_amd/capi.py AngdistSpec)");
+#endif
+
 /* ---- runtime ---------------------------------------------------------------------------------- */
 int         kr_abi_version(void);
 const char* kr_last_error(void);
@@ -834,6 +920,32 @@ int kr_post_healpix_map_dev_f64(double spin, double V, int reverse, int projradi
                                 int64_t n, int64_t first, int64_t stride, void* d_out, void* stream);
 int kr_reduce_healpix_map_dev_f64(const kr_healpix_map* m, const void* d_rays, int64_t n, int64_t first, int64_t stride, void* d_out, void* stream);
 int kr_reduce_healpix_map_f64(const kr_healpix_map* m, const kr_ray_f64* rays, int64_t n, double* out);
+
+/* ---- point source with any four-velocity (kr_pointsource_vel_spec above has the rule and the refusals) -------------------------------------
+ * Every entry point checks its arguments before it touches a device (KR_EINVAL, message in kr_last_error); without a device: KR_ENODEVICE.  The _dev
+ * forms neither wait for the device nor allocate; the tetrad is solved on the host in each call and travels in the kernel's arguments.
+ * kr_pointsource_vel_count: the ray count, the factors in *n_cosalpha / *n_beta when given; -1 for a null spec or a grid whose count is no int (it does
+ *   not look at pos or u).
+ * kr_pointsource_vel_tetrad: the sixteen doubles tetrad[leg][t, r, theta, phi] of a spec that passes every check (host only, no device needed).
+ * kr_pointsource_vel_init_dev_f64: n = kr_pointsource_vel_count() records with emit = 0;  _init_emit_: with their emitted energy, one pass.
+ * kr_pointsource_vel_init_f64: the same into host records, staged through the device. */
+int64_t kr_pointsource_vel_count(const kr_pointsource_vel_spec* s, int32_t* n_cosalpha, int32_t* n_beta);
+int kr_pointsource_vel_tetrad(const kr_pointsource_vel_spec* s, double* tetrad16);
+int kr_pointsource_vel_init_dev_f64(const kr_pointsource_vel_spec* s, void* d_rays, int64_t n, void* stream);
+int kr_pointsource_vel_init_emit_dev_f64(const kr_pointsource_vel_spec* s, void* d_rays, int64_t n, void* stream);
+int kr_pointsource_vel_init_f64(const kr_pointsource_vel_spec* s, kr_ray_f64* rays, int64_t n);
+
+/* ---- where a source's rays end, by emission angle (kr_angdist_spec above has the rule) ------------------------------------------------------
+ * kr_angdist_nangle: Nangle of a spec, or -1 when it is refused.
+ * kr_post_: range_phi(lo, hi) + redshift(V, reverse, projradius, motion) on every record, phi and g stored back as kr_range_phi_dev_f64 +
+ * kr_redshift_dev_f64 leave them, then the reduction, in one pass.  kr_reduce_: no wrap, no redshift, the records read as they are.  Both ADD into d_out
+ * (14 Nangle + 8 doubles on the device; zero it first).  n == 0 is KR_OK and adds nothing.  kr_reduce_angdist_f64: host records, out = 14 Nangle + 8
+ * host doubles (overwritten). */
+int kr_angdist_nangle(const kr_angdist_spec* sp);
+int kr_post_angdist_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_angdist_spec* sp, void* d_rays,
+                            int64_t n, void* d_out, void* stream);
+int kr_reduce_angdist_dev_f64(const kr_angdist_spec* sp, const void* d_rays, int64_t n, void* d_out, void* stream);
+int kr_reduce_angdist_f64(const kr_angdist_spec* sp, const kr_ray_f64* rays, int64_t n, double* out);
 
 /* ---- emission-line profile / transfer function (kr_line_bins above) --------------------------------------------------------------------
  * Every entry point validates the bins first, before it touches a device: KR_EINVAL (message in kr_last_error) when ne < 1 or nt < 1, de <= 0,

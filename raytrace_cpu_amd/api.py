@@ -1138,3 +1138,173 @@ def healpix_to_disc_text(res):
         else:
             rows.append("%20d%20s%20s%20s%20d\n" % (pix, "nan", "nan", "nan", 0))
     return "".join(rows)
+
+
+# ---- point source with any four-velocity, and where its rays end by emission angle (include/kr_trace.h: kr_pointsource_vel_spec, kr_angdist_spec) ----
+def pointsource_vel_spec(pos, u, spin, dcosalpha, dbeta, cosalpha0=-0.995, cosalphamax=0.995, beta0=-np.pi, betamax=np.pi, E=1.0, tol=100.0):
+    """A kr_pointsource_vel_spec: the reference's PointSourceVel(pos, u, spin, tol, dcosalpha, dbeta, cosalpha0, cosalphamax, beta0, betamax, E); u is the
+    contravariant four-velocity (u^t, u^r, u^theta, u^phi) and need not be normalised (four_velocity() builds one from coordinate velocities)."""
+    s = capi.PointSourceVelSpec()
+    for i in range(4):
+        s.pos[i], s.u[i] = pos[i], u[i]
+    s.spin, s.tol, s.E = spin, tol, E
+    s.dcosalpha, s.dbeta, s.cosalpha0, s.cosalphamax, s.beta0, s.betamax = dcosalpha, dbeta, cosalpha0, cosalphamax, beta0, betamax
+    return s
+
+
+def four_velocity(pos, spin, omega=None, dr_dt=0.0, dtheta_dt=0.0):
+    """The normalised four-velocity u^t (1, dr/dt, dtheta/dt, omega) of an emitter at pos = (t, r, theta, phi) with the given coordinate velocities;
+    omega=None takes the frame-dragging rate of the zero-angular-momentum observer, -g_tphi / g_phiphi.  Raises ValueError for a velocity that is
+    not timelike (g(u, u) <= 0 for u = (1, dr/dt, dtheta/dt, omega))."""
+    r, theta, a = float(pos[1]), float(pos[2]), float(spin)
+    st, ct = math.sin(theta), math.cos(theta)
+    rhosq = r * r + (a * ct) * (a * ct)
+    delta = r * r - 2 * r + a * a
+    sigmasq = (r * r + a * a) * (r * r + a * a) - a * a * delta * st * st
+    e2nu, e2psi, w = rhosq * delta / sigmasq, sigmasq * st * st / rhosq, 2 * a * r / sigmasq
+    g00, g03, g11, g22, g33 = e2nu - w * w * e2psi, w * e2psi, -rhosq / delta, -rhosq, -e2psi
+    if omega is None:
+        omega = w
+    norm = g00 + 2 * g03 * omega + g11 * dr_dt * dr_dt + g22 * dtheta_dt * dtheta_dt + g33 * omega * omega
+    if not norm > 0:
+        raise ValueError(f"four_velocity: (1, {dr_dt}, {dtheta_dt}, {omega}) is not timelike at r = {r}, theta = {theta} (g(u, u) = {norm})")
+    ut = 1 / math.sqrt(norm)
+    return (ut, ut * dr_dt, ut * dtheta_dt, ut * omega)
+
+
+def pointsource_vel_count(spec):
+    """(rays, n_cosalpha, n_beta) of the source; raises for a grid the library refuses."""
+    nc, nb = C.c_int32(), C.c_int32()
+    n = lib().kr_pointsource_vel_count(C.byref(spec), C.byref(nc), C.byref(nb))
+    if n < 0:
+        capi.check(lib(), capi.KR_EINVAL, "kr_pointsource_vel_count")
+    return int(n), nc.value, nb.value
+
+
+def pointsource_vel_tetrad(spec):
+    """The emitter's tetrad [leg, (t, r, theta, phi)] as the library solves it on the host (no device needed)."""
+    out = np.zeros((4, 4))
+    capi.check(lib(), lib().kr_pointsource_vel_tetrad(C.byref(spec), _ptr(out)), "kr_pointsource_vel_tetrad")
+    return out
+
+
+def pointsource_vel_init(spec, emit=False):
+    """The source's ray records, built on the device: with emit = 0 (kr_pointsource_vel_init_dev_f64) or with the photon energy in the emitter's own
+    frame (kr_pointsource_vel_init_emit_dev_f64)."""
+    L = lib()
+    n = pointsource_vel_count(spec)[0]
+    with DeviceScope(L) as dev:
+        d = dev.alloc(n * capi.RAY_F64.itemsize) if n > 0 else C.c_void_p()
+        if emit:
+            capi.check(L, L.kr_pointsource_vel_init_emit_dev_f64(C.byref(spec), d, n, None), "kr_pointsource_vel_init_emit")
+        else:
+            capi.check(L, L.kr_pointsource_vel_init_dev_f64(C.byref(spec), d, n, None), "kr_pointsource_vel_init")
+        return dev.fetch(d, n, capi.RAY_F64)
+
+
+ANGDIST_CLASSES = ("escape", "return", "lost")
+ANGDIST_ANGLES = ("alpha", "beta", "norm", "az")
+ANGDIST_TALLIES = ("ray_count", "escape", "return", "lost", "other", "skipped", "out_of_range", "bad_g")
+
+
+def angdist_spec(r_isco, r_disc, r_esc, dangle=0.1, source_r=0.0, source_phi=0.0, plane_iso=1, limb=0, weight_norm=1, labels=0):
+    """A kr_angdist_spec; source_r = 0 (the default) switches the self-zone of kr_return_bins off, as in the reference's program.  labels: whose
+    (alpha, beta) the records carry -- 0 for a PointSource (pointsource_init), 1 for a PointSourceVel (pointsource_vel_init, source_angdist), whose
+    beta is a quarter turn ahead of PointSource's."""
+    sp = capi.AngdistSpec()
+    c = sp.cls
+    c.r_isco, c.r_disc, c.r_esc, c.source_r, c.source_phi = r_isco, r_disc, r_esc, source_r, source_phi
+    c.plane_iso, c.limb, c.weight_norm, c.pad = int(plane_iso), int(limb), int(weight_norm), 0
+    sp.dangle, sp.labels, sp.pad = dangle, int(labels), 0
+    return sp
+
+
+def angdist_nangle(spec):
+    n = lib().kr_angdist_nangle(C.byref(spec))
+    if n < 0:
+        capi.check(lib(), capi.KR_EINVAL, "kr_angdist_nangle")
+    return n
+
+
+def _angdist_layout(nangle, words=None):
+    planes = [(f"{c}_{a}", (nangle,)) for c in ANGDIST_CLASSES for a in ANGDIST_ANGLES] + [("total_norm", (nangle,)), ("total_az", (nangle,))]
+    tallies = [(k if k not in ANGDIST_CLASSES else k + "_sum", float if q < 4 else _rounded) for q, k in enumerate(ANGDIST_TALLIES)]
+    return _layout(planes, tallies, words)
+
+
+def angdist_words(spec):
+    """Length of the angular-distribution buffer: fourteen histograms of Nangle and eight tallies."""
+    return _angdist_layout(angdist_nangle(spec))
+
+
+def angdist_from_words(spec, words, normalise_az=False):
+    """The buffer as a dict of named arrays: "<class>_<angle>" for class in escape / return / lost and angle in alpha / beta / norm / az,
+    "total_norm", "total_az", the tallies ray_count, escape_sum, return_sum, lost_sum (weighted) and other, skipped, out_of_range, bad_g (ints), the
+    fractions "escape_frac" / "return_frac" / "lost_frac" = class sum / ray_count, and "angle" = -pi + i dangle.  normalise_az divides the three az
+    histograms by their per-bin sum, as disc_source_return_angdist.cpp:200-209 does (0 / 0 is NaN there too)."""
+    nangle = angdist_nangle(spec)
+    out = _angdist_layout(nangle, words)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for c in ANGDIST_CLASSES:
+            out[c + "_frac"] = float(np.float64(out[c + "_sum"]) / np.float64(out["ray_count"]))        # no rays: NaN, as the program prints
+        if normalise_az:
+            total = out["escape_az"] + out["return_az"] + out["lost_az"]
+            for c in ANGDIST_CLASSES:
+                out[c + "_az"] = out[c + "_az"] / total
+    out["angle"] = -1 * np.pi + np.arange(nangle) * spec.dangle
+    return out
+
+
+def angdist(params, rays, spec, V=-1.0, reverse=0, projradius=0, motion=0, lo=-np.pi, hi=np.pi, fused=True, normalise_az=False):
+    """Where traced host records end, by emission angle.  fused: range_phi(lo, hi) + redshift(V, reverse, projradius, motion) + the reduction in one
+    pass (kr_post_angdist_dev_f64; `rays` itself is not modified); otherwise the records are reduced as they are (kr_reduce_angdist_dev_f64).
+    params gives the spin.  Returns the dict of angdist_from_words."""
+    _rays_arg(rays, capi.RAY_F64)
+    L = lib()
+    nw, n = angdist_words(spec), len(rays)
+    with DeviceScope(L) as dev:
+        d_rays = dev.upload(rays) if n > 0 else C.c_void_p()
+        d_out = dev.zeros(nw * 8)
+        if fused:
+            capi.check(L, L.kr_post_angdist_dev_f64(params.spin, V, int(reverse), int(projradius), int(motion), lo, hi, C.byref(spec), d_rays, n, d_out, None),
+                       "kr_post_angdist")
+        else:
+            capi.check(L, L.kr_reduce_angdist_dev_f64(C.byref(spec), d_rays, n, d_out, None), "kr_reduce_angdist")
+        return angdist_from_words(spec, dev.fetch(d_out, nw), normalise_az)
+
+
+def source_angdist(vel_spec, params, angdist_spec, V=-1.0, reverse=0, projradius=0, motion=0, lo=-np.pi, hi=np.pi, normalise_az=False, return_records=False):
+    """From an emitter's geometry to the histograms of where its light ends, inside one DeviceScope: kr_pointsource_vel_init_emit_dev_f64 ->
+    kr_trace_dev_f64 with `params` -> kr_post_angdist_dev_f64.  The records never leave the device (return_records copies the final ones back, for
+    tests).  vel_spec may also be a PointSourceSpec -- the orbiting emitter of the reference's program, built with its own emitted energy
+    (kr_pointsource_init_emit_dev_f64); the angdist_spec's labels must say which of the two the records come from.  Returns the dict of
+    angdist_from_words plus "stats"."""
+    L = lib()
+    orbital = isinstance(vel_spec, capi.PointSourceSpec)
+    if angdist_spec.labels != (0 if orbital else 1):
+        raise KrError("source_angdist: angdist_spec.labels must be 0 for a PointSourceSpec and 1 for a PointSourceVelSpec")
+    n = pointsource_count(vel_spec)[0] if orbital else pointsource_vel_count(vel_spec)[0]
+    nw = angdist_words(angdist_spec)
+    st = Stats()
+    with DeviceScope(L) as dev:
+        d_rays = dev.alloc(n * capi.RAY_F64.itemsize) if n > 0 else C.c_void_p()
+        d_out = dev.zeros(nw * 8)
+        if orbital:
+            capi.check(L, L.kr_pointsource_init_emit_dev_f64(C.byref(vel_spec), 0, 1, vel_spec.V, int(reverse), int(projradius), d_rays, n, None), "kr_pointsource_init_emit")
+        else:
+            capi.check(L, L.kr_pointsource_vel_init_emit_dev_f64(C.byref(vel_spec), d_rays, n, None), "kr_pointsource_vel_init_emit")
+        capi.check(L, L.kr_trace_dev_f64(C.byref(params), d_rays, n, None, C.byref(st)), "kr_trace_dev")
+        capi.check(L, L.kr_post_angdist_dev_f64(params.spin, V, int(reverse), int(projradius), int(motion), lo, hi, C.byref(angdist_spec), d_rays, n, d_out, None),
+                   "kr_post_angdist")
+        res = angdist_from_words(angdist_spec, dev.fetch(d_out, nw), normalise_az)
+        res["stats"] = st.as_dict()
+        if return_records:
+            res["records"] = dev.fetch(d_rays, n, capi.RAY_F64)
+    return res
+
+
+def angdist_text(res):
+    """The table kr_angdist writes for a result of angdist() / source_angdist() made with normalise_az=True: `angle` and the alpha, beta, norm, az
+    columns of escape, return, lost per bin, every field setw(20) scientific with precision 8 (host/include/text_output.h)."""
+    cols = [res["angle"]] + [res[f"{c}_{a}"] for c in ANGDIST_CLASSES for a in ANGDIST_ANGLES]
+    return "".join("".join(_path_field(float(col[i])) for col in cols) + "\n" for i in range(len(res["angle"])))

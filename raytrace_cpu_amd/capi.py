@@ -169,6 +169,22 @@ class CrossingSpec(C.Structure):
     _fields_ = [("V", C.c_double)] + [(n, C.c_int32) for n in ("max_crossings", "stop_when_full", "reverse", "projradius", "motion", "pad")]
 
 
+class PointSourceVelSpec(C.Structure):
+    """kr_pointsource_vel_spec: a point source whose emitter has any timelike four-velocity u = (u^t, u^r, u^theta, u^phi), not necessarily
+    normalised (include/kr_trace.h has the tetrad, the ray rule and what is refused)."""
+    _fields_ = [("pos", C.c_double * 4), ("u", C.c_double * 4)] + \
+               [(n, C.c_double) for n in ("spin", "tol", "E", "dcosalpha", "dbeta", "cosalpha0", "cosalphamax", "beta0", "betamax")]
+
+
+class AngdistSpec(C.Structure):
+    """kr_angdist_spec: the classes and weights of kr_return_bins (cls), the bin width of the emission-angle histograms and whose (alpha, beta) labels the
+    records carry -- 0: PointSource's, 1: PointSourceVel's (include/kr_trace.h)."""
+    _fields_ = [("cls", ReturnBins), ("dangle", C.c_double), ("labels", C.c_int32), ("pad", C.c_int32)]
+
+
+assert C.sizeof(PointSourceVelSpec) == 136 and C.sizeof(AngdistSpec) == 72
+
+
 def line_bins(line_energy=6.4, e_min=1.0, de=0.1, ne=90, log_e=False, t0=0.0, dt=0.0, nt=1, r_isco=1.0, r_disc=1000.0, q1=3.0, rb1=4.0, q2=3.0,
               rb2=10.0, q3=3.0, g_index=3.0):
     b = LineBins()
@@ -297,6 +313,15 @@ PROTOTYPES = {
     "kr_post_healpix_map_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, P(HealpixMap), _vp, _i64, _i64, _i64, _vp, _vp]),
     "kr_reduce_healpix_map_dev_f64": (_int, [P(HealpixMap), _vp, _i64, _i64, _i64, _vp, _vp]),
     "kr_reduce_healpix_map_f64": (_int, [P(HealpixMap), _vp, _i64, _vp]),
+    "kr_pointsource_vel_count": (_i64, [P(PointSourceVelSpec), P(_i32), P(_i32)]),
+    "kr_pointsource_vel_tetrad": (_int, [P(PointSourceVelSpec), _vp]),
+    "kr_pointsource_vel_init_dev_f64": (_int, [P(PointSourceVelSpec), _vp, _i64, _vp]),
+    "kr_pointsource_vel_init_emit_dev_f64": (_int, [P(PointSourceVelSpec), _vp, _i64, _vp]),
+    "kr_pointsource_vel_init_f64": (_int, [P(PointSourceVelSpec), _vp, _i64]),
+    "kr_angdist_nangle": (_int, [P(AngdistSpec)]),
+    "kr_post_angdist_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, P(AngdistSpec), _vp, _i64, _vp, _vp]),
+    "kr_reduce_angdist_dev_f64": (_int, [P(AngdistSpec), _vp, _i64, _vp, _vp]),
+    "kr_reduce_angdist_f64": (_int, [P(AngdistSpec), _vp, _i64, _vp]),
     "kr_reduce_line_f64": (_int, [P(LineBins), _vp, _i64, _vp]),
     "kr_reduce_line_dev_f64": (_int, [P(LineBins), _vp, _i64, _vp, _vp]),
     "kr_post_line_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, P(LineBins), _vp, _i64, _vp, _vp]),

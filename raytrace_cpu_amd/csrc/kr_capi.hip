@@ -971,6 +971,92 @@ int kr_reduce_healpix_map_f64(const kr_healpix_map* m, const kr_ray_f64* rays, i
     return reduce_to_host(rays, n, 7 * (size_t) m->npix + 6, out, [&](void* d, void* d_out) { return reduce_healpix_map_dev(m, d, n, 0, 1, d_out, nullptr); });
 }
 
+// ---- point source with any four-velocity (kr_source_vel.hip) and the angular distribution of where its rays end (kr_angdist.hip) ------------
+int64_t kr_pointsource_vel_count(const kr_pointsource_vel_spec* s, int32_t* n_cosalpha, int32_t* n_beta)
+{
+    int64_t total;
+    int nc, nb;
+    if (!s || !pointsource_vel_grid(s, &total, &nc, &nb)) { set_error("kr_pointsource_vel_count: null spec or a grid whose ray count is not a non-negative int"); return -1; }
+    if (n_cosalpha) *n_cosalpha = nc;
+    if (n_beta) *n_beta = nb;
+    return total;
+}
+
+int kr_pointsource_vel_tetrad(const kr_pointsource_vel_spec* s, double* tetrad16)
+{
+    krvel::Frame f;
+    const int rc = pointsource_vel_validate(s, "kr_pointsource_vel_tetrad", &f);
+    if (rc != KR_OK) return rc;
+    if (!tetrad16) return invalid("kr_pointsource_vel_tetrad: null argument");
+    std::memcpy(tetrad16, f.tetrad, sizeof f.tetrad);
+    return KR_OK;
+}
+
+// the checks every init form makes, in the header's order; *f: the emitter's frame of a spec that passed
+static int pointsource_vel_check(const kr_pointsource_vel_spec* s, const void* rays, int64_t n, const char* who, krvel::Frame* f)
+{
+    if (!s) return invalid_arg(who, "null spec");
+    if (n < 0) return invalid_arg(who, "negative n");
+    if (n > 0 && !rays) return invalid_arg(who, "null ray buffer");
+    const int rc = pointsource_vel_validate(s, who, f);
+    if (rc != KR_OK) return rc;
+    if (n != kr_pointsource_vel_count(s, nullptr, nullptr)) return invalid_arg(who, "n is not kr_pointsource_vel_count()");
+    return KR_OK;
+}
+
+int kr_pointsource_vel_init_dev_f64(const kr_pointsource_vel_spec* s, void* d, int64_t n, void* st)
+{
+    krvel::Frame f;
+    const int rc = pointsource_vel_check(s, d, n, "kr_pointsource_vel_init", &f);
+    if (rc != KR_OK) return rc;
+    return on_device(true, nullptr, [&] { return pointsource_vel_init_dev(s, &f, d, n, false, (hipStream_t) st); });
+}
+
+int kr_pointsource_vel_init_emit_dev_f64(const kr_pointsource_vel_spec* s, void* d, int64_t n, void* st)
+{
+    krvel::Frame f;
+    const int rc = pointsource_vel_check(s, d, n, "kr_pointsource_vel_init_emit", &f);
+    if (rc != KR_OK) return rc;
+    return on_device(true, nullptr, [&] { return pointsource_vel_init_dev(s, &f, d, n, true, (hipStream_t) st); });
+}
+
+int kr_pointsource_vel_init_f64(const kr_pointsource_vel_spec* s, kr_ray_f64* rays, int64_t n)
+{
+    krvel::Frame f;
+    const int rc = pointsource_vel_check(s, rays, n, "kr_pointsource_vel_init", &f);
+    if (rc != KR_OK) return rc;
+    return with_staged_rays(rays, n, sizeof(kr_ray_f64), kConstructs, nullptr, [&](void* d) { return pointsource_vel_init_dev(s, &f, d, n, false, nullptr); });
+}
+
+int kr_angdist_nangle(const kr_angdist_spec* sp)
+{
+    return angdist_validate(sp, "kr_angdist_nangle") == KR_OK ? angdist_nangle(sp) : -1;
+}
+
+int kr_reduce_angdist_dev_f64(const kr_angdist_spec* sp, const void* d, int64_t n, void* d_out, void* st)
+{
+    const int rc = angdist_validate(sp, "kr_reduce_angdist");
+    if (rc != KR_OK) return rc;
+    return on_device(n >= 0 && d_out && (n == 0 || d), "kr_reduce_angdist: null argument or negative n", [&] { return reduce_angdist_dev(sp, d, n, d_out, (hipStream_t) st); });
+}
+
+int kr_post_angdist_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_angdist_spec* sp, void* d, int64_t n,
+                            void* d_out, void* st)
+{
+    const int rc = angdist_validate(sp, "kr_post_angdist");
+    if (rc != KR_OK) return rc;
+    return on_device(n >= 0 && d_out && (n == 0 || d), "kr_post_angdist: null argument or negative n",
+                     [&] { return post_angdist_dev(spin, V, reverse, projradius, motion, lo, hi, sp, d, n, d_out, (hipStream_t) st); });
+}
+
+int kr_reduce_angdist_f64(const kr_angdist_spec* sp, const kr_ray_f64* rays, int64_t n, double* out)
+{
+    const int rc = angdist_validate(sp, "kr_reduce_angdist");
+    if (rc != KR_OK) return rc;
+    if (!out || n < 0 || (n > 0 && !rays)) return invalid("kr_reduce_angdist: null argument or negative n");
+    return reduce_to_host(rays, n, 14 * (size_t) angdist_nangle(sp) + 8, out, [&](void* d, void* d_out) { return reduce_angdist_dev(sp, d, n, d_out, nullptr); });
+}
+
 int kr_reduce_line_dev_f64(const kr_line_bins* b, const void* d, int64_t n, void* d_line, void* st)
 {
     const int rc = line_validate(b, "kr_reduce_line");

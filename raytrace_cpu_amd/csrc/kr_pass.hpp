@@ -8,6 +8,7 @@
 
 #include "kr_common.hpp"
 #include "kr_post_device.hpp"
+#include "kr_vel_tetrad.hpp"
 
 namespace kr {
 
@@ -150,6 +151,17 @@ int emissivity_mu_validate(const kr_emis_bins* b, const kr_mu_bins* mb, const ch
 int angles_dev(double spin, double V, int reverse, int projradius, const void* d, int64_t n, void* d_angles, hipStream_t st);
 int post_emissivity_mu_dev(double spin, double V, int reverse, int projradius, double lo, double hi, const kr_emis_bins* b, const kr_mu_bins* mb, void* d, int64_t n,
                            void* d_hist, void* d_mu, hipStream_t st);
+// kr_source_vel.hip: the point source with an arbitrary four-velocity.  The validator refuses what kr_pointsource_vel_spec's comment refuses and hands
+// back the emitter's frame (kr_vel_tetrad.hpp), solved on the host; the grid helper gives the reference's truncated counts (false: no int)
+bool pointsource_vel_grid(const kr_pointsource_vel_spec* s, int64_t* total, int* n_cosalpha, int* n_beta);
+int pointsource_vel_validate(const kr_pointsource_vel_spec* s, const char* who, krvel::Frame* frame);
+int pointsource_vel_init_dev(const kr_pointsource_vel_spec* s, const krvel::Frame* f, void* d, int64_t n, bool emit, hipStream_t st);
+// kr_angdist.hip: where a source's rays end, by emission angle; the validator refuses a null spec and a dangle that gives no 1 ... 4096 bins
+int angdist_nangle(const kr_angdist_spec* sp);
+int angdist_validate(const kr_angdist_spec* sp, const char* who);
+int reduce_angdist_dev(const kr_angdist_spec* sp, const void* d, int64_t n, void* d_out, hipStream_t st);
+int post_angdist_dev(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_angdist_spec* sp, void* d, int64_t n, void* d_out,
+                     hipStream_t st);
 // kr_caustic.hip.  The validators take the records the caller has (n; "n smaller than ..." is theirs to say)
 int caustic_validate(const kr_caustic_map* m, int64_t n, const char* who);
 int bundles_init_emit_dev(const kr_imageplane* s, int nx, int ny, double eps_frac, double V, int reverse, int projradius, void* d, int64_t n, hipStream_t st);
