@@ -49,6 +49,23 @@ extern "C" {
 #define KR_STOP_FLATDISC   1   /* stop_params = {theta_lim} */
 #define KR_STOP_DISC_ISCO  2   /* stop_params = {r_isco, r_out, theta_lim} */
 #define KR_STOP_FLATPLANE  3   /* stop_params = {incl, phi0, z_s} */
+/* A disc of finite thickness, handed to the reference as a user-defined RayDestination (ray_destination.h:36-41): the body |z| <= H(rho) over
+ * r_in <= rho <= r_out (r_out <= 0: open), rho = r sin(theta) the cylindrical radius, z = r cos(theta), H(rho) = slope rho + scale (1 - sqrt(r_in / rho)):
+ * `slope` a constant opening ratio H / rho, `scale` the radiation-pressure Shakura-Sunyaev height (3 mdot / (2 eta)); both zero: the thin annulus.
+ * Every line one IEEE operation in this association, sin / cos the strict trace's:
+ *   in_range = (rho >= r_in) && !(r_out > 0 && rho > r_out)                                                          (a NaN: false)
+ *   reached(r, theta, phi, prev) = in_range && (fabs(z) <= H || (prev < pi/2 && theta >= pi/2) || (prev > pi/2 && theta <= pi/2))
+ *   reached(r, theta, phi)       = reached(r, theta, phi, theta)
+ *   step_limit(r, theta, phi, pr, ptheta, pphi):  max unless in_range;  sg = z < 0 ? -1 : 1;  f = sg z - H;
+ *     zdot = pr cos(theta) - (r sin(theta)) ptheta;  rhodot = sin(theta) pr + (r cos(theta)) ptheta;
+ *     Hp = slope + (scale 0.5 sqrt(r_in / rho)) / rho;  fdot = sg zdot - Hp rhodot;
+ *     (f > 0 && fdot < 0) ? max(f / -fdot, KR_MIN_STEP) : max
+ * The equator clause keeps the thin limit and the thin inner parts of the body from being stepped over.  The floor at KR_MIN_STEP: on a curved
+ * surface the bare linear extrapolation shrinks the clamped RK45 step geometrically and reached() never fires.
+ * Known limits: RK4 has no landing clamp in the reference's RayDestination overload, so an RK4 ray stops up to one step INSIDE the body; rays that
+ * enter through the vertical walls at r_in / r_out are not step-limited.
+ * Refused (KR_EINVAL, the parameter named): r_in not positive, slope or scale negative, any of the four not finite. */
+#define KR_STOP_THICKDISC  4   /* stop_params = {r_in, r_out, slope, scale} */
 
 /* ray status bit flags (raytracer.h:58-63) + one extension */
 #define KR_STATUS_DEST        (1 << 0)
@@ -870,6 +887,26 @@ int kr_reduce_image_f64(const kr_image_bins* b, const kr_ray_f64* rays, int64_t 
 /* d_planes: device buffer of 7*img_nx*img_ny+1 doubles [nrays | flux | r | phi | enshift | time | emis | disc_count],
  * nrays held as doubles.  ADDS into d_planes. */
 int kr_reduce_image_dev_f64(const kr_image_bins* b, const void* d_rays, int64_t n, void* d_planes, void* stream);
+
+/* ---- the same two reducers for rays that LANDED ON A SURFACE (a RayDestination stop such as KR_STOP_THICKDISC).  The reducers above hard-wire
+ * z = r cos(theta) < 1e-2 and bin by r; these take the stop itself for the filter and the cylindrical radius of the landing point for the bins.
+ * Per ray record, with rho = r sin(theta), z = r cos(theta) (the strict trace's sin / cos) and g = rays[].redshift:
+ *   filter   steps > 0, status & KR_STATUS_DEST, g > 0 (a NaN fails)
+ * Emissivity:  further rho >= b.r_isco (a NaN fails).  A ray that passes counts in disc_count, in upper if z > 0 and in lower if z < 0.  It is
+ *   binned iff -1 < q < nr with q = log(rho / r_min) / log(dr) (logbin) or (rho - r_min) / dr -- the quotient and index rule of kr_emis_bins, the
+ *   test made on q itself -- at ir = (int) q:  count += 1, flux += 1 / (num_primary_rays g), emis += g^-gamma, sum_redshift += g, sum_time += t,
+ *   sum_z += z;  binned += 1.  sum_z / count is the mean landing height of a bin (about zero for a symmetric illumination: upper / lower tell).
+ *   d_hist: double[6 nr + 4] = [count | flux | emis | sum_redshift | sum_time | sum_z](nr each) + disc_count, binned, upper, lower; counts are
+ *   doubles.  ADDS into d_hist (zero it first).
+ * Image:  further b.r_isco <= rho < b.r_disc, then the pixel rule of kr_image_bins unchanged.  d_planes: double[7 img_nx img_ny + 1], the layout of
+ *   kr_reduce_image_dev_f64, with the powerlaw3 emissivity evaluated at rho and the radius plane holding rho.  ADDS into d_planes.
+ * kr_post_*_surface = range_phi(lo, hi) + redshift(V = -1, reverse, projradius = 1, motion = 0) -- the Keplerian observer at the cylindrical radius,
+ * 1 / (a + rho sqrt(rho)), `spin` as stored by the Raytracer -- + the reducer in one pass; rays[] ends up exactly as after the separate calls.
+ * Refused with KR_EINVAL: null bins or result buffer, null d_rays with n > 0, nr <= 0, a non-positive image size. */
+int kr_reduce_emissivity_surface_dev_f64(const kr_emis_bins* b, const void* d_rays, int64_t n, void* d_hist, void* stream);
+int kr_post_emissivity_surface_dev_f64(double spin, int reverse, double lo, double hi, const kr_emis_bins* b, void* d_rays, int64_t n, void* d_hist, void* stream);
+int kr_reduce_image_surface_dev_f64(const kr_image_bins* b, const void* d_rays, int64_t n, void* d_planes, void* stream);
+int kr_post_image_surface_dev_f64(double spin, int reverse, double lo, double hi, const kr_image_bins* b, void* d_rays, int64_t n, void* d_planes, void* stream);
 
 /* disc_source_photonfrac_r.cpp:97-126: out[4] = {ray_count, return_count, escape_count, lost_count} (weighted sums);
  * the app's three fractions are out[1..3] / out[0].  _dev ADDS into d_out4 (4 doubles, zero first). */

@@ -237,6 +237,140 @@ def image_planes_from_words(words, nx, ny):
     return {"nrays": np.rint(out.pop("nrays")).astype(np.int32), "disc_count": out.pop("disc_count"), **out}
 
 
+# ---- a disc of finite thickness (KR_STOP_THICKDISC) and the reducers for rays that landed on a surface (include/kr_trace.h) ----
+def thick_disc_params(p, r_in, r_out, slope, scale):
+    """A copy of the trace parameters `p` that stops on the body |z| <= H(rho), r_in <= rho <= r_out (r_out <= 0: open) of KR_STOP_THICKDISC."""
+    return capi.copy_params(p, stop_kind=capi.STOP_THICKDISC, stop_params=(float(r_in), float(r_out), float(slope), float(scale)))
+
+
+def surface_height(rho, r_in, slope, scale):
+    """H(rho) = slope rho + scale (1 - sqrt(r_in / rho)), the half-thickness of KR_STOP_THICKDISC at the cylindrical radius rho (host numpy)."""
+    rho = np.asarray(rho, dtype=np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return slope * rho + scale * (1 - np.sqrt(r_in / rho))
+
+
+def surface_area_density(rho, r_in, slope, scale, spin):
+    """Proper area of the surface z = H(rho) per unit rho and phi for the gas on circular orbits at the cylindrical radius, Omega = 1 / (a + rho
+    sqrt(rho)) -- surface_area_density of host/include/disc.h (INTEGRATION.md 3m has the formula), host numpy.  With the tangent along the surface
+    T = (0, (rho + H H') / r, (H - rho H') / r^2, 0) at r = sqrt(rho^2 + H^2), theta = atan2(rho, H):
+        sqrt((Sigma / Delta) T_r^2 + Sigma T_theta^2) sqrt(e2psi) / sqrt(1 - (Omega - omega)^2 e2psi / e2nu)."""
+    rho = np.asarray(rho, dtype=np.float64)
+    a = float(spin)
+    with np.errstate(all="ignore"):
+        root = np.sqrt(r_in / rho)
+        H = slope * rho + scale * (1 - root)
+        Hp = slope + (scale * 0.5 * root) / rho
+        r = np.sqrt(rho * rho + H * H)
+        theta = np.arctan2(rho, H)
+        Tr, Tth = (rho + H * Hp) / r, (H - rho * Hp) / (r * r)
+        st, ct = np.sin(theta), np.cos(theta)
+        rhosq = r * r + (a * ct) * (a * ct)
+        delta = r * r - 2 * r + a * a
+        sigmasq = (r * r + a * a) * (r * r + a * a) - a * a * delta * st * st
+        e2nu, e2psi, omega = rhosq * delta / sigmasq, sigmasq * st * st / rhosq, 2 * a * r / sigmasq
+        V = 1 / (a + rho * np.sqrt(rho))
+        lorentz = 1 / np.sqrt(1 - (V - omega) * (V - omega) * e2psi / e2nu)
+        return np.sqrt((rhosq / delta) * Tr * Tr + rhosq * Tth * Tth) * np.sqrt(e2psi) * lorentz
+
+
+def surface_area(edges, r_in, slope, scale, spin, dphi=0.1, n_sub=50):
+    """The proper area of each ring [edges[i], edges[i + 1]) of the surface z = H(rho) of KR_STOP_THICKDISC, per azimuthal width dphi, for the orbiting
+    gas: integrate_surface_area of host/include/disc.h, which is the rule of the project's disc-area function integrate_disc_area -- n_sub - 1
+    log-spaced sub-rings, each taken at its inner edge, non-positive and NaN pieces skipped, dphi = 0.1 as the emissivity programs pass it -- with
+    the line element along the surface (surface_area_density).  At slope = scale = 0 it is integrate_disc_area(..., force_keplerian).  Host numpy."""
+    edges = [float(e) for e in edges]
+    out = np.zeros(max(len(edges) - 1, 0))
+    for i, (lo, hi) in enumerate(zip(edges[:-1], edges[1:])):
+        step = math.exp(math.log(hi / lo) / (n_sub - 1))
+        subs, rho = [], lo
+        while rho < hi:                                    # (the running product, as the C++ loop forms it)
+            subs.append(rho)
+            rho = rho * step
+        subs = np.array(subs)
+        pieces = surface_area_density(subs, r_in, slope, scale, spin) * (subs * (step - 1)) * dphi
+        total = 0.0
+        for piece in pieces.tolist():
+            if piece > 0:
+                total += piece
+        out[i] = total
+    return out
+
+
+SURFACE_PLANES = ("count", "flux", "emis", "sum_redshift", "sum_time", "sum_z")
+SURFACE_TALLIES = ("disc_count", "binned", "upper", "lower")
+
+
+def _emissivity_surface_layout(bins, words=None):
+    return _layout([(k, (bins.nr,)) for k in SURFACE_PLANES], [(k, _rounded) for k in SURFACE_TALLIES], words)
+
+
+def emissivity_surface_words(bins):
+    """Length of the buffer of kr_reduce_emissivity_surface_dev_f64 / kr_post_emissivity_surface_dev_f64: six planes of nr and four tallies."""
+    return _emissivity_surface_layout(bins)
+
+
+def emissivity_surface_from_words(bins, words):
+    """That buffer as a dict: count (int64), flux, emis, sum_redshift, sum_time, sum_z (nr raw sums each), disc_count / binned / upper / lower."""
+    out = _emissivity_surface_layout(bins, words)
+    out["count"] = np.rint(out["count"]).astype(np.int64)
+    return out
+
+
+def surface_emissivity(pointsource_spec, params, bins, return_records=False):
+    """The emissivity profile of a point source on a disc with a surface, resident on the device from start to finish: PointSource ctor +
+    redshift_start (kr_pointsource_init_emit_dev_f64, the source's own V) -> trace (kr_trace_dev_f64; `params` with a RayDestination stop, e.g.
+    thick_disc_params) -> range_phi + redshift for the Keplerian gas at the cylindrical radius + the histogram over rho
+    (kr_post_emissivity_surface_dev_f64).  Only the histogram is read back (and, with return_records, the final records: for tests).
+    Returns emissivity_surface_from_words(...) plus "stats" (the trace's kr_stats)."""
+    L = lib()
+    n, _, _ = pointsource_count(pointsource_spec)
+    if n <= 0:
+        raise KrError("surface_emissivity: empty ray grid")
+    nw = emissivity_surface_words(bins)
+    st = Stats()
+    with DeviceScope(L) as dev:
+        d_hist = dev.zeros(nw * 8) if bins.nr > 0 else C.c_void_p()          # (the pass refuses nr <= 0: no allocation of a negative size)
+        d_rays = dev.alloc(n * capi.RAY_F64.itemsize)
+        capi.check(L, L.kr_pointsource_init_emit_dev_f64(C.byref(pointsource_spec), 0, 1, pointsource_spec.V, 0, 0, d_rays, n, None), "kr_pointsource_init_emit")
+        capi.check(L, L.kr_trace_dev_f64(C.byref(params), d_rays, n, None, C.byref(st)), "kr_trace_dev")
+        capi.check(L, L.kr_post_emissivity_surface_dev_f64(pointsource_spec.spin, 0, -np.pi, np.pi, C.byref(bins), d_rays, n, d_hist, None), "kr_post_emissivity_surface")
+        capi.check(L, L.kr_synchronize(None), "kr_synchronize")
+        res = emissivity_surface_from_words(bins, dev.fetch(d_hist, nw))
+        if return_records:
+            res["records"] = dev.fetch(d_rays, n, capi.RAY_F64)
+    res["stats"] = st.as_dict()
+    return res
+
+
+def surface_image(imageplane_spec, params, image_bins, return_records=False):
+    """The image of a disc with a surface, resident on the device from start to finish: ImagePlane ctor + redshift_start
+    (kr_imageplane_init_emit_dev_f64) -> trace (kr_trace_dev_f64; `params` as for the image app -- the stored, negated spin -- with a RayDestination
+    stop, e.g. thick_disc_params) -> redshift for the Keplerian gas at the cylindrical radius + range_phi + the seven planes
+    (kr_post_image_surface_dev_f64).  Only the planes are read back (and, with return_records, the final records: for tests).
+    Returns image_planes_from_words(...) plus "stats" (the trace's kr_stats)."""
+    L = lib()
+    n, _, _ = imageplane_count(imageplane_spec)
+    if n <= 0:
+        raise KrError("surface_image: empty ray grid")
+    sized = image_bins.img_nx > 0 and image_bins.img_ny > 0
+    nw = image_words(image_bins) if sized else 0
+    spin = -1 * imageplane_spec.spin                     # as stored by the Raytracer of an ImagePlane (imageplane.cpp:12)
+    st = Stats()
+    with DeviceScope(L) as dev:
+        d_planes = dev.zeros(nw * 8) if sized else C.c_void_p()
+        d_rays = dev.alloc(n * capi.RAY_F64.itemsize)
+        capi.check(L, L.kr_imageplane_init_emit_dev_f64(C.byref(imageplane_spec), 0, 1, 0.0, 1, 0, d_rays, n, None), "kr_imageplane_init_emit")
+        capi.check(L, L.kr_trace_dev_f64(C.byref(params), d_rays, n, None, C.byref(st)), "kr_trace_dev")
+        capi.check(L, L.kr_post_image_surface_dev_f64(spin, 1, -np.pi, np.pi, C.byref(image_bins), d_rays, n, d_planes, None), "kr_post_image_surface")
+        capi.check(L, L.kr_synchronize(None), "kr_synchronize")
+        res = image_planes_from_words(dev.fetch(d_planes, nw), image_bins.img_nx, image_bins.img_ny)
+        if return_records:
+            res["records"] = dev.fetch(d_rays, n, capi.RAY_F64)
+    res["stats"] = st.as_dict()
+    return res
+
+
 RETURN_MAP_PLANES = ("count", "weight", "flux", "emis", "time")
 RETURN_MAP_SCALARS = ("ray_count", "return", "escape", "lost", "on_disc", "binned")
 

@@ -11,6 +11,10 @@
 // --device = 0, --timing.  --Nmu | Nmu = 0 and --mu_outfile | mu_outfile: with Nmu >= 1 the histogram is also split by the incidence angle in the
 // disc frame (kr_post_emissivity_mu_dev_f64) and a second table goes to mu_outfile: per radial bin r, then Nmu columns count2 / count (the share
 // of the bin's rays in each mu bin) and the mean mu, in TextOutput's format.  Without Nmu the program does what it did before the key existed.
+// disc_slope, disc_scale (and disc_rin = ISCO): with either key the disc has a surface, z = +-H(rho), H = disc_slope rho + disc_scale (1 - sqrt(disc_rin / rho))
+// between disc_rin and r_disc (KR_STOP_THICKDISC, include/kr_trace.h): the rays stop on it (RK4 / RK45), the gas orbits at the cylindrical radius rho,
+// the histogram is over rho (kr_post_emissivity_surface_dev_f64), the areas are those of the surface's rings (integrate_surface_area, disc.h) and the
+// table gets an eighth column, the mean landing height <z> of the bin.  Not with Nmu.  Without the keys the program and its output are what they were.
 //
 // What is NOT taken from the reference: with logbin_r = 0 its bin areas do not compile (`disc_r + dr`, :79); the
 // intended upper edge r + dr (as in emissivity_rd.cpp:88 ... which passes `dr` alone) is used here.
@@ -53,6 +57,9 @@ try {
     const string mu_out_name = args.key_exists("--mu_outfile") ? args.get_parameter<string>("--mu_outfile") : par.get_parameter<string>("mu_outfile", "");
     if (Nmu < 0) throw invalid_argument("Nmu must be >= 0");
     if (Nmu > 0 && mu_out_name.empty()) throw invalid_argument("Nmu needs mu_outfile");
+    const bool thick = par.key_exists("disc_slope") || par.key_exists("disc_scale");
+    const double disc_slope = par.get_parameter<double>("disc_slope", 0), disc_scale = par.get_parameter<double>("disc_scale", 0);
+    if (thick && Nmu > 0) throw invalid_argument("disc_slope / disc_scale: the incidence angle to a tilted surface is not offered (no Nmu)");
 
     kr_pointsource src;
     memset(&src, 0, sizeof src);
@@ -71,11 +78,13 @@ try {
     // radial bins and their proper areas (host: Nr x 49 small tetrad evaluations)
     const double r_isco = kerr_isco<double>(spin, +1);
     if (r_min < 0) r_min = r_isco;
+    const double disc_rin = par.get_parameter<double>("disc_rin", r_isco);
     const double dr = logbin_r ? exp(log(r_disc / r_min) / Nr) : (r_disc - r_min) / Nr;
     vector<double> bin_r(Nr), bin_area(Nr);
     for (int ir = 0; ir < Nr; ++ir) {
         bin_r[ir] = logbin_r ? r_min * pow(dr, ir) : r_min + ir * dr;
-        bin_area[ir] = integrate_disc_area(bin_r[ir], logbin_r ? bin_r[ir] * dr : bin_r[ir] + dr, spin);
+        const double bin_top = logbin_r ? bin_r[ir] * dr : bin_r[ir] + dr;
+        bin_area[ir] = thick ? integrate_surface_area(bin_r[ir], bin_top, disc_rin, disc_slope, disc_scale, spin) : integrate_disc_area(bin_r[ir], bin_top, spin);
     }
     const long num_primary_rays = (((src.cosalphamax - src.cosalpha0) / src.dcosalpha) * ((src.betamax - src.beta0) / src.dbeta));
 
@@ -97,6 +106,10 @@ try {
     p.r_max = r_max;
     p.stop_kind = KR_STOP_THETA;
     p.flags = krapp::arithmetic_flags(arith, p.integrator);
+    if (thick) {
+        p.stop_kind = KR_STOP_THICKDISC;
+        p.stop_params[0] = disc_rin; p.stop_params[1] = r_disc; p.stop_params[2] = disc_slope; p.stop_params[3] = disc_scale;
+    }
 
     // ---- device pipeline ------------------------------------------------------------------------------------------
     krapp::check(kr_set_device(args.get_parameter<int>("--device", 0)), "kr_set_device");
@@ -104,7 +117,7 @@ try {
     const int64_t n = kr_pointsource_count(&src, nullptr, nullptr);
     if (n <= 0) throw runtime_error("empty ray grid");
     krapp::DeviceBuffer rays(n * (int64_t) sizeof(kr_ray_f64));
-    krapp::DeviceBuffer hist((5 * (int64_t) Nr + 1) * (int64_t) sizeof(double));
+    krapp::DeviceBuffer hist((6 * (int64_t) Nr + 4) * (int64_t) sizeof(double));      // (the surface form's six planes and four tallies; the flat form uses 5 Nr + 1)
     hist.zero();
     krapp::check(kr_pointsource_init_emit_dev_f64(&src, 0, 1, V, 0, 0, rays.get(), n, nullptr), "pointsource_init + redshift_start");
     krapp::check(kr_synchronize(nullptr), "sync");
@@ -123,15 +136,18 @@ try {
         krapp::check(kr_post_emissivity_mu_dev_f64(spin, -1.0, 0, 0, 0, -1 * M_PI, M_PI, &bins, &mb, rays.get(), n, hist.get(), by_mu.get(), nullptr),
                      "range_phi + redshift + histogram by angle");
         krapp::check(kr_memcpy_d2h(hmu.data(), by_mu.get(), (int64_t) (hmu.size() * sizeof(double))), "d2h");
+    } else if (thick) {
+        krapp::check(kr_post_emissivity_surface_dev_f64(spin, 0, -1 * M_PI, M_PI, &bins, rays.get(), n, hist.get(), nullptr), "range_phi + redshift + surface histogram");
     } else {
         krapp::check(kr_post_emissivity_dev_f64(spin, -1.0, 0, 0, 0, -1 * M_PI, M_PI, &bins, rays.get(), n, hist.get(), nullptr), "range_phi + redshift + histogram");
     }
-    vector<double> h(5 * (size_t) Nr + 1);
+    vector<double> h(thick ? 6 * (size_t) Nr + 4 : 5 * (size_t) Nr + 1);
     krapp::check(kr_memcpy_d2h(h.data(), hist.get(), (int64_t) (h.size() * sizeof(double))), "d2h");
     const double ms_post = clock.lap_ms();
 
     // ---- the divisions of emissivity.cpp:128-134 and the table ---------------------------------------------------------
-    krapp::write_emissivity_table(out_name, Nr, bin_r.data(), bin_area.data(), &h[0], &h[Nr], &h[2 * (size_t) Nr], &h[3 * (size_t) Nr], &h[4 * (size_t) Nr]);
+    krapp::write_emissivity_table(out_name, Nr, bin_r.data(), bin_area.data(), &h[0], &h[Nr], &h[2 * (size_t) Nr], &h[3 * (size_t) Nr], &h[4 * (size_t) Nr],
+                                  thick ? &h[5 * (size_t) Nr] : nullptr);
 
     if (Nmu > 0) {
         // count2 / count per mu bin (count: the radial histogram's, so a bin's bad-angle rays are missing from its row) and the mean mu over the
@@ -151,7 +167,7 @@ try {
 
     if (timing)
         cout << "timing: rays " << st.rays_traced << " steps " << st.steps_total << " | init+redshift_start " << ms_init << " ms | trace " << ms_trace
-             << " ms (kernel " << st.kernel_ms << ") | range_phi+redshift+histogram+readback " << ms_post << " ms | disc rays " << static_cast<long>(h[5 * Nr]) << endl;
+             << " ms (kernel " << st.kernel_ms << ") | range_phi+redshift+histogram+readback " << ms_post << " ms | disc rays " << static_cast<long>(h[(thick ? 6 : 5) * (size_t) Nr]) << endl;
     cout << "Done" << endl;
     return 0;
 } catch (const exception& e) {

@@ -9,6 +9,9 @@
 // img_Nx = Nx, img_Ny = img_Nx, q1 = 3, rb1 = 4, q2 = 3, rb2 = 10, q3 = 3, precision = 100, flip_image = true,
 // integrator = rk45, rk45_tol = 1e-8.  (max_tstep is read and ignored by the reference, :63, :109.)
 // Extensions: --integrator, --arithmetic | KRTRACE_ARITHMETIC, --device, --timing.
+// disc_slope, disc_scale (and disc_rin = ISCO): with either key the disc has a surface, z = +-H(rho), H = disc_slope rho + disc_scale (1 - sqrt(disc_rin / rho))
+// between disc_rin and r_disc (KR_STOP_THICKDISC, include/kr_trace.h): the rays stop on it (RK4 / RK45), the gas orbits at the cylindrical radius rho, the
+// emissivity is taken at rho and the RADIUS plane holds rho (kr_post_image_surface_dev_f64).  Without the keys the program and its output are what they were.
 // Difference: under RK45 a pixel exactly at (0, 0) never returns in the reference; here it ends with KR_STATUS_NAN.
 #include <cmath>
 #include <iostream>
@@ -54,6 +57,8 @@ try {
     const double rk45_tol = par.get_parameter<double>("rk45_tol", 1e-8);
     const string arith = args.key_exists("--arithmetic") ? args.get_parameter<string>("--arithmetic") : krapp::arithmetic_from_env();
     const bool timing = args.key_exists("--timing");
+    const bool thick = par.key_exists("disc_slope") || par.key_exists("disc_scale");
+    const double disc_slope = par.get_parameter<double>("disc_slope", 0), disc_scale = par.get_parameter<double>("disc_scale", 0);
 
     ax.dx = (ax.xmax - ax.x0) / Nx;
     ax.dy = (ax.ymax - ax.y0) / Ny;
@@ -89,6 +94,10 @@ try {
     p.r_max = 1.1 * dist;
     p.stop_kind = KR_STOP_THETA;
     p.flags = krapp::arithmetic_flags(arith, p.integrator);
+    if (thick) {
+        p.stop_kind = KR_STOP_THICKDISC;
+        p.stop_params[0] = par.get_parameter<double>("disc_rin", r_isco); p.stop_params[1] = r_disc; p.stop_params[2] = disc_slope; p.stop_params[3] = disc_scale;
+    }
 
     // ---- device pipeline ------------------------------------------------------------------------------------------
     krapp::check(kr_set_device(args.get_parameter<int>("--device", 0)), "kr_set_device");
@@ -105,7 +114,10 @@ try {
     kr_stats st;
     krapp::check(kr_trace_dev_f64(&p, rays.get(), n, nullptr, &st), "trace");
     const double ms_trace = clock.lap_ms();
-    krapp::check(kr_post_image_dev_f64(-spin, -1.0, 1, 0, 0, -1 * M_PI, M_PI, &bins, rays.get(), n, planes.get(), nullptr), "redshift + range_phi + image planes");
+    if (thick)
+        krapp::check(kr_post_image_surface_dev_f64(-spin, 1, -1 * M_PI, M_PI, &bins, rays.get(), n, planes.get(), nullptr), "redshift + range_phi + image planes of the surface");
+    else
+        krapp::check(kr_post_image_dev_f64(-spin, -1.0, 1, 0, 0, -1 * M_PI, M_PI, &bins, rays.get(), n, planes.get(), nullptr), "redshift + range_phi + image planes");
     krapp::PinnedDoubles h(7 * npix + 1);     // 0.94 GB at 4096^2: page-locked, or the read-back runs at a tenth of the PCIe rate
     krapp::check(kr_memcpy_d2h(h.data(), planes.get(), h.size() * (int64_t) sizeof(double)), "d2h");
     const double ms_post = clock.lap_ms();

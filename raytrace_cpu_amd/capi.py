@@ -13,7 +13,7 @@ ABI_VERSION = 16
 
 KR_OK, KR_EINVAL, KR_ENODEVICE, KR_EHIP, KR_ENOMEM = 0, -1, -2, -3, -4
 EULER, RK4, RK45 = 0, 1, 2
-STOP_THETA, STOP_FLATDISC, STOP_DISC_ISCO, STOP_FLATPLANE = 0, 1, 2, 3
+STOP_THETA, STOP_FLATDISC, STOP_DISC_ISCO, STOP_FLATPLANE, STOP_THICKDISC = 0, 1, 2, 3, 4
 STATUS_DEST, STATUS_HORIZON, STATUS_RLIM, STATUS_STEPLIM = 1, 2, 4, 8
 STATUS_ERGO, STATUS_NEG_ENERGY, STATUS_NAN = 16, 32, 64
 STEPLIM, RK45_STEPLIM, MIN_STEP = 10_000_000, 100_000, 1e-3
@@ -296,6 +296,10 @@ PROTOTYPES = {
     "kr_post_emissivity_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, P(EmisBins), _vp, _i64, _vp, _vp]),
     "kr_reduce_image_f64": (_int, [P(ImageBins), _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, P(_i64)]),
     "kr_reduce_image_dev_f64": (_int, [P(ImageBins), _vp, _i64, _vp, _vp]),
+    "kr_reduce_emissivity_surface_dev_f64": (_int, [P(EmisBins), _vp, _i64, _vp, _vp]),
+    "kr_post_emissivity_surface_dev_f64": (_int, [_dbl, _int, _dbl, _dbl, P(EmisBins), _vp, _i64, _vp, _vp]),
+    "kr_reduce_image_surface_dev_f64": (_int, [P(ImageBins), _vp, _i64, _vp, _vp]),
+    "kr_post_image_surface_dev_f64": (_int, [_dbl, _int, _dbl, _dbl, P(ImageBins), _vp, _i64, _vp, _vp]),
     "kr_reduce_return_f64": (_int, [P(ReturnBins), _vp, _i64, P(_dbl * 4)]),
     "kr_reduce_return_dev_f64": (_int, [P(ReturnBins), _vp, _i64, _vp, _vp]),
     "kr_post_return_dev_f64": (_int, [_dbl, _dbl, P(ReturnBins), _vp, _i64, _vp, _vp]),

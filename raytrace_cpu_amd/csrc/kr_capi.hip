@@ -346,6 +346,8 @@ template <typename Trace>
 int trace_host(const kr_params* p, void* rays, int64_t n, size_t ray_bytes, kr_stats* stats, Trace trace)
 {
     if (!p) return invalid("kr_trace: null params");
+    const int rc = validate_run(p, "kr_trace");          // (before any device work, as the device-pointer forms do: a bad kr_params is KR_EINVAL on every machine)
+    if (rc != KR_OK) return rc;
     if (stats) std::memset(stats, 0, sizeof(*stats));
     return with_staged_rays(rays, n, ray_bytes, kUpdates, stats, trace);
 }
@@ -840,6 +842,26 @@ int kr_reduce_image_f64(const kr_image_bins* b, const kr_ray_f64* rays, int64_t 
     for (size_t k = 0; k < 6; k++) std::memcpy(planes[k], &h[(k + 1) * npix], npix * sizeof(double));
     if (disc_count) *disc_count = (int64_t) h[7 * npix];
     return KR_OK;
+}
+
+// the two reducers for rays that ended on a stop surface (kr_surface.hip), and their fused forms
+int kr_reduce_emissivity_surface_dev_f64(const kr_emis_bins* b, const void* d, int64_t n, void* d_hist, void* st)
+{
+    return on_device(b && d_hist && (n <= 0 || d), "kr_reduce_emissivity_surface: null argument", [&] { return reduce_emissivity_surface_dev(b, d, n, d_hist, (hipStream_t) st); });
+}
+int kr_post_emissivity_surface_dev_f64(double spin, int reverse, double lo, double hi, const kr_emis_bins* b, void* d, int64_t n, void* d_hist, void* st)
+{
+    return on_device(b && d_hist && (n <= 0 || d), "kr_post_emissivity_surface: null argument",
+                     [&] { return post_emissivity_surface_dev(spin, reverse, lo, hi, b, d, n, d_hist, (hipStream_t) st); });
+}
+int kr_reduce_image_surface_dev_f64(const kr_image_bins* b, const void* d, int64_t n, void* d_planes, void* st)
+{
+    return on_device(b && d_planes && (n <= 0 || d), "kr_reduce_image_surface: null argument", [&] { return reduce_image_surface_dev(b, d, n, d_planes, (hipStream_t) st); });
+}
+int kr_post_image_surface_dev_f64(double spin, int reverse, double lo, double hi, const kr_image_bins* b, void* d, int64_t n, void* d_planes, void* st)
+{
+    return on_device(b && d_planes && (n <= 0 || d), "kr_post_image_surface: null argument",
+                     [&] { return post_image_surface_dev(spin, reverse, lo, hi, b, d, n, d_planes, (hipStream_t) st); });
 }
 
 int kr_reduce_return_dev_f64(const kr_return_bins* b, const void* d, int64_t n, void* d_out4, void* st)

@@ -29,7 +29,7 @@ namespace kr {
 template <typename T> struct TraceConsts {
     T a, horizon, rlim, thetalim;
     T precision, theta_precision, max_tstep, maxtstep_rlim, max_phistep, tol;
-    T sp0, sp1, sp2;        // stop_params
+    T sp0, sp1, sp2, sp3;   // stop_params
     T inv_precision, inv_theta_precision;   // RN(1/precision), RN(1/theta_precision): fast path, and div_by_uniform on the strict one
     bool inv_ok;                            // both divisors qualify for div_by_uniform
     bool rk45_extrapolate;                  // RK45: creeping captured rays are extrapolated to the step limit (default)
@@ -281,11 +281,35 @@ KR_DEV bool loop_cond(const Lane<T>& s, const TraceConsts<T>& c)
     return ok;
 }
 
+// KR_STOP_THICKDISC (include/kr_trace.h has the rule, one IEEE operation per line): the point (r, theta) against the body |z| <= H(rho) over
+// r_in <= rho <= r_out.  False: out of range, nothing else is set.  |r| < r_in implies |rho| = |RN(r sin)| <= |r| < r_in (|sin| <= 1, rounding is
+// monotone), which is out of range whatever theta is: that test comes before any trigonometry -- it is the answer for every ray inside r_in,
+// the captured ones above all.  The sine and cosine are evaluated here: the strict step keeps sin^2 of the new point, not the pair.
+template <typename T> struct ThickDiscPoint { T sn, cs, rho, z, H, root; };      // root = sqrt(r_in / rho)
+template <typename T>
+KR_DEV bool thick_disc_point(const TraceConsts<T>& c, T r, T theta, ThickDiscPoint<T>& p)
+{
+    const T r_in = c.sp0, r_out = c.sp1, slope = c.sp2, scale = c.sp3;
+    if (kr_abs(r) < r_in) return false;
+    kr_sincos(theta, p.sn, p.cs);
+    p.rho = r * p.sn;
+    p.z = r * p.cs;
+    if (!((p.rho >= r_in) && !(r_out > 0 && p.rho > r_out))) return false;
+    p.root = kr_sqrt(r_in / p.rho);
+    p.H = slope * p.rho + scale * (1 - p.root);
+    return true;
+}
+
 // RayDestination::reached(r, theta, phi, prev_theta): ray_destination.h:90-94 (FlatDisc, through the
-// default crossing-aware overload :52-54), :130-142 (DiscWithISCO), :184-190 (FlatPlane)
+// default crossing-aware overload :52-54), :130-142 (DiscWithISCO), :184-190 (FlatPlane); KR_STOP_THICKDISC: include/kr_trace.h
 template <typename T>
 KR_DEV bool dest_reached(const TraceConsts<T>& c, T r, T theta, T phi, T prev_theta)
 {
+    if (c.stop_kind == KR_STOP_THICKDISC) {
+        ThickDiscPoint<T> p;
+        if (!thick_disc_point(c, r, theta, p)) return false;
+        return kr_abs(p.z) <= p.H || (prev_theta < T(kPi2) && theta >= T(kPi2)) || (prev_theta > T(kPi2) && theta <= T(kPi2));
+    }
     if (c.stop_kind == KR_STOP_FLATDISC) {
         const T tl = c.sp0;
         if (tl > 0) return theta >= tl;
@@ -311,9 +335,26 @@ KR_DEV bool dest_reached(const TraceConsts<T>& c, T r, T theta, T phi, T prev_th
 
 // RayDestination::step_limit(): ray_destination.h:55-57 (base), :95-101, :143-151
 template <typename T>
-KR_DEV T dest_step_limit(const TraceConsts<T>& c, T r, T theta, T ptheta)
+KR_DEV T dest_step_limit(const TraceConsts<T>& c, T r, T theta, T pr, T ptheta)
 {
     T tl;
+    if (c.stop_kind == KR_STOP_THICKDISC) {
+        // linear extrapolation of f = |z| - H(rho) along the stage-1 momenta, floored at KR_MIN_STEP: on a curved surface the bare quotient shrinks
+        // the clamped step geometrically and reached() never fires
+        ThickDiscPoint<T> p;
+        if (!thick_disc_point(c, r, theta, p)) return Lim<T>::max();
+        const T sg = p.z < 0 ? T(-1) : T(1);
+        const T f = sg * p.z - p.H;
+        const T zdot = pr * p.cs - (r * p.sn) * ptheta;
+        const T rhodot = p.sn * pr + (r * p.cs) * ptheta;
+        const T Hp = c.sp2 + (c.sp3 * T(0.5) * p.root) / p.rho;
+        const T fdot = sg * zdot - Hp * rhodot;
+        if (f > 0 && fdot < 0) {
+            const T q = f / -fdot;
+            return q < T(KR_MIN_STEP) ? T(KR_MIN_STEP) : q;
+        }
+        return Lim<T>::max();
+    }
     if (c.stop_kind == KR_STOP_FLATDISC) {
         tl = c.sp0;
     } else if (c.stop_kind == KR_STOP_DISC_ISCO) {

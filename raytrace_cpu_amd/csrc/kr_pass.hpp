@@ -117,6 +117,12 @@ int reduce_return_dev(const kr_return_bins* b, const void* d, int64_t n, void* d
 int post_return_dev(double lo, double hi, const kr_return_bins* b, void* d, int64_t n, void* d_out4, hipStream_t st);
 int post_return_batch_dev(int count, double lo, double hi, const kr_return_bins* b, void* const* d, const int64_t* n, void* const* d_out4, hipStream_t st);
 int arith_probe_dev(int op, const double* a, const double* b, double* out, int64_t n);
+// kr_surface.hip: the emissivity histogram and the image of rays that ended on a stop surface (KR_STATUS_DEST), binned by rho = r sin(theta); the
+// post_ forms take the Keplerian observer at rho, redshift(V = -1, projradius = 1, motion = 0)
+int reduce_emissivity_surface_dev(const kr_emis_bins* b, const void* d, int64_t n, void* d_hist, hipStream_t st);
+int post_emissivity_surface_dev(double spin, int reverse, double lo, double hi, const kr_emis_bins* b, void* d, int64_t n, void* d_hist, hipStream_t st);
+int reduce_image_surface_dev(const kr_image_bins* b, const void* d, int64_t n, void* d_planes, hipStream_t st);
+int post_image_surface_dev(double spin, int reverse, double lo, double hi, const kr_image_bins* b, void* d, int64_t n, void* d_planes, hipStream_t st);
 // kr_return_map.hip: the landing map of the returning radiation (kr_return_map); the validator refuses a null map and nr <= 0
 int return_map_validate(const kr_return_map* m, const char* who);
 int reduce_return_map_dev(const kr_return_map* m, const void* d, int64_t n, void* d_out, hipStream_t st);

@@ -64,7 +64,7 @@ TraceConsts<T> make_consts(const kr_params* p, int steplim)
     c.precision = (T) p->precision; c.theta_precision = (T) p->theta_precision;
     c.max_tstep = (T) p->max_tstep; c.maxtstep_rlim = (T) p->maxtstep_rlim; c.max_phistep = (T) p->max_phistep;
     c.tol = (T) p->rk45_tol;
-    c.sp0 = (T) p->stop_params[0]; c.sp1 = (T) p->stop_params[1]; c.sp2 = (T) p->stop_params[2];
+    c.sp0 = (T) p->stop_params[0]; c.sp1 = (T) p->stop_params[1]; c.sp2 = (T) p->stop_params[2]; c.sp3 = (T) p->stop_params[3];
     c.inv_precision = (T) (1.0 / p->precision);
     c.inv_theta_precision = (T) (1.0 / p->theta_precision);
     c.rk45_extrapolate = !(p->flags & KR_FLAG_RK45_ITERATE_ALL);

@@ -195,7 +195,7 @@ KR_DEV bool step_rk45(Lane<T>& s, const TraceConsts<T>& c, uint32_t& attempts, u
         }
     } else {
         if (r + pr1 * h_try > c.rlim) { h_try = kr_abs((c.rlim - r) / pr1); clamped = true; }      // rlim > 0 && ...
-        const T h_dest = dest_step_limit(c, r, theta, ptheta1);
+        const T h_dest = dest_step_limit(c, r, theta, pr1, ptheta1);
         if (h_dest < h_try) { h_try = h_dest; clamped = true; }
     }
     ++attempts;
@@ -338,10 +338,12 @@ KR_DEV bool step_rk45(Lane<T>& s, const TraceConsts<T>& c, uint32_t& attempts, u
     // same pure function of the same inputs: it adds the same two increments to t and phi, sets the same status
     // bits, and counts one step.  Replaying only those two additions gives bit-identical results; t and phi are
     // accumulated one addition at a time, exactly as the full loop would round them.  (phi feeds back only
-    // through FlatPlaneDestination::reached, so that stop kind is excluded.)
+    // through FlatPlaneDestination::reached, so that stop kind is excluded.  KR_STOP_THICKDISC's reached() does not read phi either, and at a fixed
+    // point its equator clause is false (theta_prev == theta): what is left is the body test at this one point, the same for every later step, so it
+    // is made here -- inside the body the step falls through to the stop test below, which ends the ray.)
     if (fresh && inside_poles && s.r == r && s.theta == theta && s.step == step_in && s.rdot_sign == rs_in && s.thetadot_sign == ts_in &&
         s.r_was_positive == rwp_in && s.theta_was_positive == twp_in && !(s.r <= c.horizon) && (!USE_DEST || c.stop_kind != KR_STOP_FLATPLANE) &&
-        s.steps < c.steplim) {
+        s.steps < c.steplim && (!USE_DEST || c.stop_kind != KR_STOP_THICKDISC || !dest_reached(c, s.r, s.theta, s.phi, s.theta))) {
         const T dt = h_try * sum_t, dphi = h_try * sum_phi;
         const int32_t remaining = c.steplim - s.steps;
         if constexpr (sizeof(T) == 8) {
@@ -375,7 +377,10 @@ KR_DEV bool step_rk45(Lane<T>& s, const TraceConsts<T>& c, uint32_t& attempts, u
         bool creeping = false;
         if (c.rk45_extrapolate && fresh && inside_poles && s.r == r && s.rdot_sign == rs_in && s.thetadot_sign == ts_in && s.r_was_positive == rwp_in &&
             s.theta_was_positive == twp_in && !(s.r <= c.horizon) && err_norm <= T(0.5) && !clamped &&
-            (!USE_DEST || c.stop_kind != KR_STOP_FLATPLANE) && theta > T(0)) {
+            (!USE_DEST || c.stop_kind != KR_STOP_FLATPLANE) && theta > T(0) &&
+            // (creep mode does not evaluate reached(): for KR_STOP_THICKDISC it is known to be false for EVERY theta only while |r| < r_in --
+            // thick_disc_point -- and r is stationary here; a ray that creeps at or beyond r_in is iterated)
+            (!USE_DEST || c.stop_kind != KR_STOP_THICKDISC || kr_abs(s.r) < c.sp0)) {
             const long long b0 = (long long) __builtin_bit_cast(unsigned long long, (double) theta);
             const long long b1 = (long long) __builtin_bit_cast(unsigned long long, (double) s.theta);
             const long long m = b1 - b0;

@@ -716,9 +716,17 @@ int validate_run(const kr_params* p, const char* who)
 {
     const char* what = nullptr;
     if (p->integrator < KR_EULER || p->integrator > KR_RK45) what = "unknown integrator";
-    else if (p->stop_kind < KR_STOP_THETA || p->stop_kind > KR_STOP_FLATPLANE) what = "unknown stop_kind";
+    else if (p->stop_kind < KR_STOP_THETA || p->stop_kind > KR_STOP_THICKDISC) what = "unknown stop_kind";
     // assert(method != Integrator::Euler), raytracer.cpp:983
     else if (p->stop_kind != KR_STOP_THETA && p->integrator == KR_EULER) what = "Integrator::Euler does not support RayDestination stopping conditions";
+    else if (p->stop_kind == KR_STOP_THICKDISC) {
+        // stop_params = {r_in, r_out, slope, scale} (include/kr_trace.h); r_out <= 0: open
+        const double* sp = p->stop_params;
+        if (!std::isfinite(sp[0]) || !(sp[0] > 0)) what = "KR_STOP_THICKDISC: r_in (stop_params[0]) must be positive and finite";
+        else if (!std::isfinite(sp[1])) what = "KR_STOP_THICKDISC: r_out (stop_params[1]) must be finite (<= 0: open)";
+        else if (!std::isfinite(sp[2]) || sp[2] < 0) what = "KR_STOP_THICKDISC: slope (stop_params[2]) must be non-negative and finite";
+        else if (!std::isfinite(sp[3]) || sp[3] < 0) what = "KR_STOP_THICKDISC: scale (stop_params[3]) must be non-negative and finite";
+    }
     if (what) set_error(std::string(who) + ": " + what);
     return what ? KR_EINVAL : KR_OK;
 }

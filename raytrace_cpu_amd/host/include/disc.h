@@ -118,4 +118,42 @@ T integrate_disc_area(T rmin, T rmax, T a, bool force_keplerian = false, int Nr 
     return integrate_disc_area_varplungeradius(rmin, rmax, a, force_keplerian ? T(0) : kerr_isco(a, +1), Nr, dphi, logbin_r);
 }
 
+// ---- the surface of a disc of finite thickness (an extension; include/kr_trace.h, KR_STOP_THICKDISC): z = H(rho), H = slope rho + scale (1 - sqrt(r_in / rho)) ----
+// Proper area per unit rho and phi of the surface for the gas on circular orbits at the cylindrical radius, Omega = 1 / (a + rho sqrt(rho)) -- the
+// observer of redshift(V = -1, projradius = true).  The patch is spanned by the tangent along the surface, T = (0, dr / drho, dtheta / drho, 0) at
+// r = sqrt(rho^2 + H^2), theta = atan2(rho, H) with dr / drho = (rho + H H') / r, dtheta / drho = (H - rho H') / r^2, and by d / dphi; in the rest
+// space of u = u^t (1, 0, 0, Omega), h_ab = -g_ab + u_a u_b, both sides are orthogonal (u has no r or theta component), so the area is
+//   sqrt(h_TT) sqrt(h_phiphi) = sqrt((rhosq / delta) T_r^2 + rhosq T_theta^2) * sqrt(e2psi) / sqrt(1 - (Omega - omega)^2 e2psi / e2nu),
+// which on the equatorial plane (H = 0) is the patch of rel_vector_disc_area.
+template <typename T>
+T surface_area_density(T rho, T r_in, T slope, T scale, T a)
+{
+    using std::sqrt;
+    const T root = sqrt(r_in / rho);
+    const T H = slope * rho + scale * (1 - root);
+    const T Hp = slope + (scale * T(0.5) * root) / rho;
+    const T r = sqrt(rho * rho + H * H);
+    const T theta = std::atan2(rho, H);
+    const T Tr = (rho + H * Hp) / r;
+    const T Tth = (H - rho * Hp) / (r * r);
+    const krhost::BLCoefficients<T> m(r, theta, a);
+    const T V = 1 / (a + rho * sqrt(rho));
+    const T lorentz = 1 / sqrt(1 - (V - m.omega) * (V - m.omega) * m.e2psi / m.e2nu);
+    return sqrt((m.rhosq / m.delta) * Tr * Tr + m.rhosq * Tth * Tth) * sqrt(m.e2psi) * lorentz;
+}
+
+// area of the ring [rho_min, rho_max) of the surface per dphi: integrate_disc_area's own rule -- Nr - 1 log-spaced sub-rings, each taken at its
+// inner edge, non-positive / NaN ones skipped -- with the line element along the surface.  slope = scale = 0: integrate_disc_area(force_keplerian).
+template <typename T>
+T integrate_surface_area(T rho_min, T rho_max, T r_in, T slope, T scale, T a, int Nr = 50, T dphi = 0.1)
+{
+    const T step = std::exp(std::log(rho_max / rho_min) / (Nr - 1));
+    T total = 0;
+    for (T rho = rho_min; rho < rho_max; rho = rho * step) {
+        const T piece = surface_area_density(rho, r_in, slope, scale, a) * (rho * (step - 1)) * dphi;
+        if (piece > 0) total += piece;
+    }
+    return total;
+}
+
 #endif /* CUDAKERR_DISC_H */

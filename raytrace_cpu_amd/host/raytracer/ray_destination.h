@@ -7,8 +7,9 @@
 // How the HIP path uses them: the per-step virtual calls of the reference (raytracer.cpp:1203, :1753,
 // :1844) cannot run on the device, so every built-in destination also describes itself as a POD record
 // (`describe()`), which Raytracer<T> hands to the trace kernel as kr_params.stop_kind / stop_params.
-// A user-defined subclass has no such description (describe() returns false): run_raytrace() then
-// throws instead of silently falling back to a CPU loop.
+// ThickDiscDestination (below; not in the reference) is the one curved surface the device knows.
+// Any other user-defined subclass has no such description (describe() returns false): run_raytrace()
+// then throws instead of silently falling back to a CPU loop.
 #ifndef RAY_DESTINATION_H_
 #define RAY_DESTINATION_H_
 
@@ -163,6 +164,85 @@ public:
         stop_kind = KR_STOP_FLATPLANE;
         sp[0] = incl; sp[1] = phi0; sp[2] = z_s; sp[3] = 0;
         default_velocity = true;
+        return true;
+    }
+};
+
+// A disc of finite thickness (an extension: the reference leaves such geometry to a user-defined subclass, which the device cannot call): the body
+// |z| <= H(rho) over r_in <= rho <= r_out (r_out <= 0: open), rho = r sin(theta), z = r cos(theta), H(rho) = slope rho + scale (1 - sqrt(r_in / rho)).
+// include/kr_trace.h (KR_STOP_THICKDISC) has the rules; every line below is one IEEE operation in that association (build with -ffp-contract=off).
+// Known limits: an RK4 ray stops up to one step inside the body (the reference's RK4 overload has no landing clamp); rays that enter through the
+// vertical walls at r_in / r_out are not step-limited.
+template <typename T>
+class ThickDiscDestination : public RayDestination<T> {
+    T r_in;
+    T r_out;
+    T slope;
+    T scale;
+
+    bool in_range(T rho) const { return (rho >= r_in) && !(r_out > 0 && rho > r_out); }      // (a NaN: false)
+
+public:
+    ThickDiscDestination(T r_in, T r_out, T slope, T scale) : r_in(r_in), r_out(r_out), slope(slope), scale(scale) {}
+
+    // half-thickness at the cylindrical radius rho, whatever the radial range
+    T height(T rho) const
+    {
+        using std::sqrt;
+        return slope * rho + scale * (1 - sqrt(r_in / rho));
+    }
+    bool reached(T r, T theta, T phi) const override { return reached(r, theta, phi, theta); }
+    bool reached(T r, T theta, T phi, T prev_theta) const override
+    {
+        using std::cos;
+        using std::fabs;
+        using std::sin;
+        const T rho = r * sin(theta), z = r * cos(theta);
+        if (!in_range(rho)) return false;
+        const T H = height(rho);
+        return fabs(z) <= H || (prev_theta < T(M_PI_2) && theta >= T(M_PI_2)) || (prev_theta > T(M_PI_2) && theta <= T(M_PI_2));
+    }
+    // linear extrapolation of f = |z| - H(rho) along the stage-1 momenta, floored at KR_MIN_STEP (on a curved surface the bare quotient stalls RK45)
+    T step_limit(T r, T theta, T phi, T pr, T ptheta, T pphi) const override
+    {
+        using std::cos;
+        using std::sin;
+        using std::sqrt;
+        const T rho = r * sin(theta), z = r * cos(theta);
+        if (!in_range(rho)) return std::numeric_limits<T>::max();
+        const T H = height(rho);
+        const T sg = z < 0 ? T(-1) : T(1);
+        const T f = sg * z - H;
+        const T zdot = pr * cos(theta) - (r * sin(theta)) * ptheta;
+        const T rhodot = sin(theta) * pr + (r * cos(theta)) * ptheta;
+        const T Hp = slope + (scale * T(0.5) * sqrt(r_in / rho)) / rho;
+        const T fdot = sg * zdot - Hp * rhodot;
+        if (f > 0 && fdot < 0) {
+            const T q = f / -fdot;
+            return q < T(KR_MIN_STEP) ? T(KR_MIN_STEP) : q;
+        }
+        return std::numeric_limits<T>::max();
+    }
+    // velocity() has no spin to work with: -1, and four_velocity() is the circular orbit at the CYLINDRICAL radius, V = 1 / (spin + rho sqrt(rho)),
+    // in the association of Raytracer::ray_redshift(V = -1, projradius = true), so that redshift(dest) is that pass
+    T velocity(T r, T theta, T phi) const override { return -1; }
+    void four_velocity(T r, T theta, T phi, T spin, T et[4]) const override
+    {
+        using std::sin;
+        using std::sqrt;
+        const krhost::BLCoefficients<T> m(r, theta, spin);
+        const T V = 1 / (spin + r * sin(theta) * sqrt(r * sin(theta)));
+        et[0] = (1 / sqrt(m.e2nu)) / sqrt(1 - (V - m.omega) * (V - m.omega) * m.e2psi / m.e2nu);
+        et[1] = 0;
+        et[2] = 0;
+        et[3] = (1 / sqrt(m.e2nu)) * V / sqrt(1 - (V - m.omega) * (V - m.omega) * m.e2psi / m.e2nu);
+    }
+    // (default_velocity = false: the material does not move as the base class's equatorial field does; Raytracer<T>::redshift(dest) knows this kind)
+    bool describe(int& stop_kind, double sp[4], bool& default_velocity) const override
+    {
+        stop_kind = KR_STOP_THICKDISC;
+        sp[0] = r_in; sp[1] = r_out; sp[2] = slope; sp[3] = scale;
+        default_velocity = false;
         return true;
     }
 };

@@ -104,7 +104,8 @@ bool builtin_destination(const RayDestination<T>* dest, int& kind, double sp[4],
 {
     if (!dest) return false;
     const std::type_info& ti = typeid(*dest);
-    const bool exact = ti == typeid(FlatDiscDestination<T>) || ti == typeid(DiscWithISCODestination<T>) || ti == typeid(FlatPlaneDestination<T>);
+    const bool exact = ti == typeid(FlatDiscDestination<T>) || ti == typeid(DiscWithISCODestination<T>) || ti == typeid(FlatPlaneDestination<T>) ||
+                       ti == typeid(ThickDiscDestination<T>);
     return exact && dest->describe(kind, sp, default_velocity);
 }
 
@@ -301,8 +302,8 @@ void Raytracer<T>::run_raytrace(RayDestination<T>* dest, Integrator method, T r_
     fill_params(&p, method, r_max, steplim);
     bool default_velocity = false;
     if (!builtin_destination(dest, p.stop_kind, p.stop_params, default_velocity))
-        throw std::runtime_error("Raytracer::run_raytrace: only FlatDiscDestination, DiscWithISCODestination and FlatPlaneDestination "
-                                 "can be evaluated by the HIP kernel; a user-defined RayDestination would need per-step host callbacks");
+        throw std::runtime_error("Raytracer::run_raytrace: only FlatDiscDestination, DiscWithISCODestination, FlatPlaneDestination and "
+                                 "ThickDiscDestination can be evaluated by the HIP kernel; a user-defined RayDestination would need per-step host callbacks");
     p.flags = arithmetic_flags(p.integrator, true);
     trace(&p, rays, nRays, show_progress);
 }
@@ -491,9 +492,17 @@ void Raytracer<T>::redshift(RayDestination<T>* dest, bool reverse, bool projradi
     int kind = 0;
     double sp[4];
     bool default_velocity = false;
-    if (builtin_destination(dest, kind, sp, default_velocity) && default_velocity) {
+    const bool builtin = builtin_destination(dest, kind, sp, default_velocity);
+    if (builtin && default_velocity) {
         g_warm_up.ready(rays);
         check(PassOf<T>::type::redshift_dest(spin, reverse, as_kr<T>(rays), nRays), "kr_redshift_dest");
+        return;
+    }
+    // ThickDiscDestination::four_velocity is the observer of redshift(V = -1, projradius = true, motion = 0), operation for operation: that pass.
+    // (Forwards only: with `reverse` that pass takes the metric at -spin, ray_redshift(et, ...) below at spin, as in the reference.)
+    if (builtin && kind == KR_STOP_THICKDISC && !reverse) {
+        g_warm_up.ready(rays);
+        check(PassOf<T>::type::redshift(spin, -1, 0, 1, 0, as_kr<T>(rays), nRays), "kr_redshift");
         return;
     }
     // user-defined velocity field: per-ray virtual call, host loop as in the reference (:467-476)
