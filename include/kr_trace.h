@@ -405,6 +405,36 @@ static_assert(sizeof(kr_limb_law) == 16, "kr_limb_law is 16 bytes (raytrace_cpu_
 static_assert(sizeof(kr_mu_bins) == 8, "kr_mu_bins is 8 bytes (raytrace_cpu_amd/capi.py MuBins)");
 #endif
 
+/* The polarisation of disc emission seen on a distant image plane.  The records are an image plane's (reverse = 1), the gas is the orbiting observer
+ * above (motion = 0), the observer sits at inclination i = inc_deg pi / 180; sin(i) is taken once on the host.
+ *   frame      exactly the one above: a = reverse ? -spin : spin, the metric g(a) at the record's (r, theta), the Tetrad legs e_t, e1 (phi), e2 (theta),
+ *              e3 (r), p from the constants of motion with `spin`, its spatial part negated; E, P_r, P_th, P_phi, mu (E and mu to the bit)
+ *   emitted    the polarisation vector lies in the disc plane, perpendicular to the projection of the photon direction (Chandrasekhar's orientation; a
+ *              negative degree turns it by 90 degrees):  nrm = sqrt(P_r P_r + P_phi P_phi),  f = (P_phi e3 - P_r e1) / nrm,  in coordinates
+ *              f^t = -P_r e1^t / nrm,  f^r = P_phi e3^r / nrm,  f^theta = 0,  f^phi = -P_r e1^phi / nrm;  g(f, p) = 0 and g(f, f) = -1 by construction
+ *   transport  the Walker-Penrose constant, conserved along the null geodesic; with s = sin(theta), c = cos(theta)
+ *              A = (p^t f^r - p^r f^t) + a s^2 (p^r f^phi - p^phi f^r)
+ *              B = ((r^2 + a^2) (p^phi f^theta - p^theta f^phi) - a (p^t f^theta - p^theta f^t)) s
+ *              kappa1 = r A - a c B,   kappa2 = -(r B + a c A)          i.e. kappa = (A - iB)(r - i a cos theta);  kappa1^2 + kappa2^2 = Q + (L - a E)^2
+ *   observer   with x = rays[].alpha, y = rays[].beta:  al = -x, be = -y (the plane gives pixel (x, y) the impact parameters (-x, -y): h = -x sin(i),
+ *              thetadot_sign = sign(y)),  nu = -(al + a sin(i)),  d = nu^2 + be^2,
+ *              f_al = (be kappa2 - nu kappa1) / d,   f_be = (be kappa1 + nu kappa2) / d,
+ *              c2 = (f_al^2 - f_be^2) / (f_al^2 + f_be^2),   s2 = 2 f_al f_be / (f_al^2 + f_be^2)
+ *              = cos(2 psi), sin(2 psi) of the polarisation angle psi, measured from the image's x axis towards its y axis (the half-turn from (al, be)
+ *              to (x, y) keeps angles modulo pi).  Sign convention: far from the hole a vector along e_phi comes out as (f_al, f_be) = (1, 0), one along
+ *              -e_theta as (0, 1).
+ * A record is BAD-POL when it is bad-angle, nrm == 0, or any of kappa1, kappa2, c2, s2 is not finite.
+ * kr_pol_law: the emitted degree delta(mu).  law 0: delta = coeff;  1: delta = coeff (1 - mu) / (1 + 3.582 mu) -- with coeff = 0.1171 the usual fit to
+ * Chandrasekhar's pure-scattering atmosphere (both numbers quoted from memory of the literature, not re-derived here).  Any other law, a non-finite coeff
+ * and |coeff| > 1 are refused. */
+typedef struct kr_pol_law {
+    double coeff;
+    int32_t law, pad;
+} kr_pol_law;
+#ifdef __cplusplus
+static_assert(sizeof(kr_pol_law) == 16, "kr_pol_law is 16 bytes (raytrace_cpu_amd/capi.py PolLaw)");
+#endif
+
 /* Critical-curve (caustic) maps of the disc on an image plane: src/caustic/caustic_discplane.cpp.  Per image-plane pixel (ix, iy), from the ray through
  * the pixel (bundle mode: member 0 of its 5-ray bundle, imageplane_bundles.h) after redshift(dest, reverse) (caustic_discplane.cpp:219-251):
  *   valid_hit   steps > 0, r_isco <= r < r_disc, redshift > 0 (:177-182)
@@ -1018,6 +1048,27 @@ int kr_post_line_limb_dev_f64(double spin, double V, int reverse, int projradius
  * minus that bin's bad-angle rays. */
 int kr_post_emissivity_mu_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_emis_bins* b, const kr_mu_bins* mb,
                                   void* d_rays, int64_t n, void* d_hist, void* d_mu, void* stream);
+
+/* ---- polarisation of disc emission on an image plane (kr_pol_law above has the rule) ------------------------------------------------------------
+ * Every entry point validates its arguments before it touches a device: KR_EINVAL (message in kr_last_error) for a null pointer, n < 0, reverse != 1
+ * (the rule is stated for image-plane records), motion != 0, a non-finite inc_deg, a bad limb law, a bad pol law, an image without pixels and whatever
+ * the line bins refuse.  n == 0 is KR_OK and adds nothing.
+ * kr_polarisation_dev_f64 reads the records and never writes them: d_out[4 i .. 4 i + 3] = {kappa1, kappa2, c2, s2} (4 n doubles); four NaNs for a
+ * record with steps <= 0; a bad-pol record gets its values as computed -- consumers filter.  kr_polarisation_f64: host records, host output. */
+int kr_polarisation_dev_f64(double spin, double V, int reverse, int projradius, int motion, double inc_deg, const void* d_rays, int64_t n, void* d_out, void* stream);
+int kr_polarisation_f64(double spin, double V, int reverse, int projradius, int motion, double inc_deg, const kr_ray_f64* rays, int64_t n, double* out);
+/* range_phi + redshift + the Stokes planes in one pass: rays[] ends up exactly as after kr_post_image_dev_f64, and the filter and the pixel rule are
+ * its own (flip_image included; Q and U always refer to the plane's own x and y axes).  ADDS into d_stokes, 4 img_nx img_ny + 2 doubles:
+ *   [nrays | I | Q | U] (each [ix img_ny + iy]) + disc_count, bad_pol
+ * A ray that reaches a pixel and is not bad-pol adds 1, w, w delta c2, w delta s2 with w = powerlaw3(r) limb(mu) / g^3 (limb law 0: the FLUX plane's
+ * term) and delta = the degree law at mu; a bad-pol ray that reaches a pixel moves only disc_count and bad_pol. */
+int kr_post_image_stokes_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, double inc_deg, const kr_image_bins* b,
+                                 const kr_limb_law* limb, const kr_pol_law* pol, void* d_rays, int64_t n, void* d_stokes, void* stream);
+/* The energy-resolved form: the items of kr_post_line_limb_dev_f64 (E, w, tau, the bins, the table emissivity), each adding 1, w, w delta c2, w delta s2.
+ * ADDS into d_out, 4 nt ne + 3 doubles: [count | I | Q | U] (nt x ne each) + on_disc, binned, bad_pol.  Bad-pol rays are never binned, whatever the limb
+ * law.  rays[] ends up exactly as after kr_post_line_dev_f64. */
+int kr_post_line_stokes_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, double inc_deg, const kr_line_bins* b,
+                                const kr_limb_law* limb, const kr_pol_law* pol, void* d_rays, int64_t n, void* d_out, void* stream);
 
 /* ---- critical-curve maps (kr_caustic_map above): caustic_discplane.cpp on the device -------------------------------------------------------
  * Every entry point validates its arguments before it touches a device: KR_EINVAL (message in kr_last_error) when nx or ny < 1, eps_x or eps_y

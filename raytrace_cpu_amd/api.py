@@ -651,6 +651,118 @@ def emissivity_angles(pointsource_spec, params, bins, nmu, V=-1.0, reverse=0, pr
     return hist, count2, flux2, mean_mu, {**by_mu, "stats": st.as_dict()}
 
 
+# ---- polarisation of disc emission on an image plane (include/kr_trace.h, kr_pol_law) ----
+def polarisation(rays, spin, inc_deg, V=-1.0, projradius=0):
+    """kr_polarisation_f64 / kr_polarisation_dev_f64: the Walker-Penrose constant and the polarisation angle at the observer of every record of an
+    image plane seen at inclination inc_deg, for emission polarised in the disc plane perpendicular to the projected photon direction, in the rest
+    frame of the orbiting gas (the observer of redshift(spin, V, reverse = 1, projradius)).  Returns {"kappa1", "kappa2", "c2", "s2"}: c2, s2 = cos, sin
+    of twice the angle, from the image's x axis towards its y axis; NaN for records with steps <= 0; a bad-pol record (include/kr_trace.h) keeps its
+    values.  rays: a host array of Ray<double> records, or (device pointer, n) for records that are already on the device."""
+    L = lib()
+    if isinstance(rays, tuple):
+        d_ptr, n = rays
+        d = d_ptr if isinstance(d_ptr, C.c_void_p) else C.c_void_p(d_ptr)
+        with DeviceScope(L) as dev:
+            d_out = dev.alloc(4 * n * 8) if n > 0 else C.c_void_p()
+            capi.check(L, L.kr_polarisation_dev_f64(spin, V, 1, int(projradius), 0, inc_deg, d, n, d_out, None), "kr_polarisation_dev")
+            out = dev.fetch(d_out, 4 * n)
+    else:
+        _rays_arg(rays, capi.RAY_F64)
+        out = np.zeros(4 * len(rays))
+        capi.check(L, L.kr_polarisation_f64(spin, V, 1, int(projradius), 0, inc_deg, _ptr(rays), len(rays), _ptr(out)), "kr_polarisation")
+    return {k: out[q::4].copy() for q, k in enumerate(("kappa1", "kappa2", "c2", "s2"))}
+
+
+def _degree_and_angle(out):
+    """pdeg = sqrt(Q^2 + U^2) / I (NaN where I == 0) and evpa = atan2(U, Q) / 2 of a dict with I, Q, U; returns it."""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out["pdeg"] = np.where(out["I"] == 0, np.nan, np.hypot(out["Q"], out["U"]) / out["I"])
+    out["evpa"] = 0.5 * np.arctan2(out["U"], out["Q"])
+    return out
+
+
+def _stokes_image_layout(nx, ny, words=None):
+    return _layout([(k, (nx * ny,)) for k in ("nrays", "I", "Q", "U")], [("disc_count", _rounded), ("bad_pol", _rounded)], words)
+
+
+def stokes_image_words(bins):
+    """Length of the buffer of kr_post_image_stokes_dev_f64: four planes of img_nx img_ny, disc_count and bad_pol."""
+    return _stokes_image_layout(bins.img_nx, bins.img_ny)
+
+
+def stokes_image_from_words(bins, words):
+    """The buffer of kr_post_image_stokes_dev_f64 as a dict: nrays (int32), I, Q, U (raw sums, [ix img_ny + iy]), disc_count, bad_pol, and per pixel
+    pdeg and evpa (radians, from the image's x axis towards its y axis)."""
+    out = _stokes_image_layout(bins.img_nx, bins.img_ny, words)
+    out["nrays"] = np.rint(out["nrays"]).astype(np.int32)
+    return _degree_and_angle(out)
+
+
+def _stokes_line_layout(bins, words=None):
+    return _layout([(k, (bins.nt, bins.ne)) for k in ("count", "I", "Q", "U")], [(k, _rounded) for k in ("on_disc", "binned", "bad_pol")], words)
+
+
+def stokes_line_words(bins):
+    """Length of the buffer of kr_post_line_stokes_dev_f64: [count | I | Q | U] (nt x ne each) + on_disc, binned, bad_pol."""
+    return _stokes_line_layout(bins)
+
+
+def stokes_line_from_words(bins, words):
+    """The buffer of kr_post_line_stokes_dev_f64 as a dict: count, I, Q, U of shape (nt, ne), on_disc, binned, bad_pol, pdeg, evpa and the bin edges of
+    line_from_words."""
+    out = _degree_and_angle(_stokes_line_layout(bins, words))
+    edges = line_from_words(bins, np.zeros(line_words(bins)))
+    out["energy_edges"], out["time_edges"] = edges["energy_edges"], edges["time_edges"]
+    return out
+
+
+def _stokes_run(what, imageplane_spec, params, nw, post, return_records=False):
+    """ImagePlane ctor + redshift_start -> trace -> post(L, d_rays, n, d_out, spin as the Raytracer stored it): (the nw words, stats, records or None)."""
+    L = lib()
+    n, _, _ = imageplane_count(imageplane_spec)
+    if n <= 0:
+        raise KrError(f"{what}: empty ray grid")
+    st = Stats()
+    with DeviceScope(L) as dev:
+        d_out = dev.zeros(nw * 8) if nw > 0 else C.c_void_p()
+        d_rays = dev.alloc(n * capi.RAY_F64.itemsize)
+        capi.check(L, L.kr_imageplane_init_emit_dev_f64(C.byref(imageplane_spec), 0, 1, 0.0, 1, 0, d_rays, n, None), "kr_imageplane_init_emit")
+        capi.check(L, L.kr_trace_dev_f64(C.byref(params), d_rays, n, None, C.byref(st)), "kr_trace_dev")
+        post(L, d_rays, n, d_out, -1 * imageplane_spec.spin)                 # (imageplane.cpp:12)
+        capi.check(L, L.kr_synchronize(None), "kr_synchronize")
+        return dev.fetch(d_out, nw), st.as_dict(), dev.fetch(d_rays, n, capi.RAY_F64) if return_records else None
+
+
+def stokes_image(imageplane_spec, params, image_bins, pol, limb=None, return_records=False):
+    """The polarised image of the disc, resident on the device from start to finish: ImagePlane ctor + redshift_start
+    (kr_imageplane_init_emit_dev_f64) -> trace (kr_trace_dev_f64; `params` as for the image app: the stored, negated spin) -> redshift + range_phi +
+    the Stokes planes (kr_post_image_stokes_dev_f64) at the plane's own inclination.  pol: (law, coeff) or a name of capi.POL_LAWS; limb: None
+    (isotropic) or a limb law as for line_profile.  Only the planes are read back (and, with return_records, the final records: for tests).
+    Returns stokes_image_from_words(...) plus "stats" (the trace's kr_stats)."""
+    law, plaw = capi.limb_law(limb if limb is not None else "isotropic"), capi.pol_law(pol)
+    sized = image_bins.img_nx > 0 and image_bins.img_ny > 0          # (the pass refuses the rest: it gets a null buffer)
+    words, stats, records = _stokes_run("stokes_image", imageplane_spec, params, stokes_image_words(image_bins) if sized else 0, lambda L, d_rays, n, d_out, spin: capi.check(
+        L, L.kr_post_image_stokes_dev_f64(spin, -1.0, 1, 0, 0, -np.pi, np.pi, imageplane_spec.inc_deg, C.byref(image_bins), C.byref(law), C.byref(plaw), d_rays, n, d_out,
+                                          None), "kr_post_image_stokes"), return_records)
+    res = stokes_image_from_words(image_bins, words)
+    res["stats"] = stats
+    if return_records:
+        res["records"] = records
+    return res
+
+
+def stokes_line(imageplane_spec, params, line_bins, pol, limb=None):
+    """The energy-resolved (and, with a time axis, time-resolved) Stokes parameters of the disc's line emission: stokes_image's pipeline with
+    kr_post_line_stokes_dev_f64 as its last pass.  Returns stokes_line_from_words(...) plus "stats"."""
+    law, plaw = capi.limb_law(limb if limb is not None else "isotropic"), capi.pol_law(pol)
+    words, stats, _ = _stokes_run("stokes_line", imageplane_spec, params, stokes_line_words(line_bins), lambda L, d_rays, n, d_out, spin: capi.check(
+        L, L.kr_post_line_stokes_dev_f64(spin, -1.0, 1, 0, 0, -np.pi, np.pi, imageplane_spec.inc_deg, C.byref(line_bins), C.byref(law), C.byref(plaw), d_rays, n, d_out,
+                                         None), "kr_post_line_stokes"))
+    res = stokes_line_from_words(line_bins, words)
+    res["stats"] = stats
+    return res
+
+
 CAUSTIC_PLANES = ("det_j", "sign_j", "order", "hit", "radius", "phi", "x_disc", "y_disc", "redshift")
 CAUSTIC_COUNTS = ("disc_count", "horizon", "rlim", "steplim", "out_of_range", "other", "suppressed")
 

@@ -137,6 +137,30 @@ def limb_law(limb):
     return out
 
 
+class PolLaw(C.Structure):
+    """kr_pol_law: the emitted polarisation degree at mu.  law 0: coeff; 1: coeff (1 - mu) / (1 + 3.582 mu) (include/kr_trace.h)."""
+    _fields_ = [("coeff", C.c_double), ("law", C.c_int32), ("pad", C.c_int32)]
+
+
+assert C.sizeof(PolLaw) == 16
+
+POL_LAWS = {"full": (0, 1.0), "chandrasekhar": (1, 0.1171)}
+
+
+def pol_law(pol):
+    """A PolLaw from (law, coeff) or one of the names of POL_LAWS."""
+    if isinstance(pol, PolLaw):
+        return pol
+    if isinstance(pol, str):
+        if pol not in POL_LAWS:
+            raise ValueError(f"unknown pol law {pol!r}: one of {sorted(POL_LAWS)} or (law, coeff)")
+        pol = POL_LAWS[pol]
+    law, coeff = pol
+    out = PolLaw()
+    out.law, out.coeff = int(law), float(coeff)
+    return out
+
+
 class CausticMap(C.Structure):
     """kr_caustic_map: what the critical-curve passes need besides the records (include/kr_trace.h has the per-pixel rules)."""
     _fields_ = [(n, C.c_double) for n in ("r_isco", "r_disc", "eps_x", "eps_y")] + [(n, C.c_int32) for n in ("nx", "ny", "bundles", "pad")]
@@ -334,6 +358,10 @@ PROTOTYPES = {
     "kr_angles_f64": (_int, [_dbl, _dbl, _int, _int, _int, _vp, _i64, _vp]),
     "kr_post_line_limb_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, P(LineBins), P(LimbLaw), _vp, _i64, _vp, _vp]),
     "kr_post_emissivity_mu_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, P(EmisBins), P(MuBins), _vp, _i64, _vp, _vp, _vp]),
+    "kr_polarisation_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _vp, _i64, _vp, _vp]),
+    "kr_polarisation_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _vp, _i64, _vp]),
+    "kr_post_image_stokes_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, _dbl, P(ImageBins), P(LimbLaw), P(PolLaw), _vp, _i64, _vp, _vp]),
+    "kr_post_line_stokes_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, _dbl, P(LineBins), P(LimbLaw), P(PolLaw), _vp, _i64, _vp, _vp]),
     "kr_bundles_init_emit_dev_f64": (_int, [P(ImagePlaneSpec), _dbl, _dbl, _int, _int, _vp, _i64, _vp]),
     "kr_post_caustic_disc_dev_f64": (_int, [_dbl, _int, P(CausticMap), _vp, _i64, _vp, _vp]),
     "kr_caustic_suppress_dev_f64": (_int, [P(CausticMap), _vp, _vp]),

@@ -1162,6 +1162,57 @@ int kr_post_emissivity_mu_dev_f64(double spin, double V, int reverse, int projra
                      [&] { return post_emissivity_mu_dev(spin, V, reverse, projradius, lo, hi, b, mb, d, n, d_hist, d_mu, (hipStream_t) st); });
 }
 
+// ---- polarisation of disc emission (kr_polarisation.hip; the Stokes line: kr_line.hip): everything is validated before anything touches a device ----
+int kr_polarisation_dev_f64(double spin, double V, int reverse, int projradius, int motion, double inc_deg, const void* d, int64_t n, void* d_out, void* st)
+{
+    const int rc = polarisation_validate(reverse, motion, inc_deg, "kr_polarisation");
+    if (rc != KR_OK) return rc;
+    return on_device(n >= 0 && (n == 0 || (d && d_out)), "kr_polarisation: null argument or negative n",
+                     [&] { return polarisation_dev(spin, V, reverse, projradius, inc_deg, d, n, d_out, (hipStream_t) st); });
+}
+
+int kr_polarisation_f64(double spin, double V, int reverse, int projradius, int motion, double inc_deg, const kr_ray_f64* rays, int64_t n, double* out)
+{
+    const int rc = polarisation_validate(reverse, motion, inc_deg, "kr_polarisation");
+    if (rc != KR_OK) return rc;
+    if (n < 0 || (n > 0 && (!rays || !out))) return invalid("kr_polarisation: null argument or negative n");
+    return with_staged_rays((void*) rays, n, sizeof(kr_ray_f64), kReads, nullptr, [&](void* d) -> int {
+        if (n == 0) return KR_OK;
+        DeviceBuffer d_out;
+        int rc2 = d_out.alloc((size_t) n * 4 * sizeof(double));
+        if (rc2 != KR_OK) return rc2;
+        rc2 = polarisation_dev(spin, V, reverse, projradius, inc_deg, d, n, d_out.p, nullptr);
+        if (rc2 != KR_OK) return rc2;
+        KR_HIP(hipMemcpy(out, d_out.p, (size_t) n * 4 * sizeof(double), hipMemcpyDeviceToHost));
+        return (int) KR_OK;
+    });
+}
+
+int kr_post_image_stokes_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, double inc_deg, const kr_image_bins* b,
+                                 const kr_limb_law* limb, const kr_pol_law* pol, void* d, int64_t n, void* d_stokes, void* st)
+{
+    if (!b) return invalid("kr_post_image_stokes: null bins");
+    if (b->img_nx <= 0 || b->img_ny <= 0) return invalid("kr_post_image_stokes: image size must be positive");
+    int rc = limb_validate(limb, "kr_post_image_stokes");
+    if (rc == KR_OK) rc = pol_validate(pol, "kr_post_image_stokes");
+    if (rc == KR_OK) rc = polarisation_validate(reverse, motion, inc_deg, "kr_post_image_stokes");
+    if (rc != KR_OK) return rc;
+    return on_device(n >= 0 && d_stokes && (n == 0 || d), "kr_post_image_stokes: null argument or negative n",
+                     [&] { return post_image_stokes_dev(spin, V, reverse, projradius, lo, hi, inc_deg, b, limb, pol, d, n, d_stokes, (hipStream_t) st); });
+}
+
+int kr_post_line_stokes_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, double inc_deg, const kr_line_bins* b,
+                                const kr_limb_law* limb, const kr_pol_law* pol, void* d, int64_t n, void* d_out, void* st)
+{
+    int rc = line_validate(b, "kr_post_line_stokes");
+    if (rc == KR_OK) rc = limb_validate(limb, "kr_post_line_stokes");
+    if (rc == KR_OK) rc = pol_validate(pol, "kr_post_line_stokes");
+    if (rc == KR_OK) rc = polarisation_validate(reverse, motion, inc_deg, "kr_post_line_stokes");
+    if (rc != KR_OK) return rc;
+    return on_device(n >= 0 && d_out && (n == 0 || d), "kr_post_line_stokes: null argument or negative n",
+                     [&] { return post_line_stokes_dev(spin, V, reverse, projradius, lo, hi, inc_deg, b, limb, pol, d, n, d_out, (hipStream_t) st); });
+}
+
 // ---- critical-curve maps (kr_caustic.hip): everything is validated before anything touches a device --------------------------------------
 int kr_bundles_init_emit_dev_f64(const kr_imageplane* s, double eps_frac, double V, int reverse, int projradius, void* d, int64_t n, void* st)
 {

@@ -5,8 +5,9 @@
 //   reduce_line_kernel      records after redshift(-1, reverse=1) -> line bins
 //   post_line_kernel        redshift + range_phi + line bins in one pass (the sibling of post_image_kernel; same per-ray functions)
 //   post_line_limb_kernel   the same with the weight times a limb law of the emission angle mu in the disc frame (kr_limb_law; frame_value)
+//   post_line_stokes_kernel the limb-law line with the Stokes parameters I, Q, U of the polarised emission per bin (kr_pol_law; polar_value)
 //   line_from_image_kernel  raw-sum image planes (kr_reduce_image_dev_f64 layout) -> line bins, per pixel
-// All three are streaming passes, one record / pixel per work-item.  The histogram is privatised per workgroup in LDS when it fits
+// All of them are streaming passes, one record / pixel per work-item.  The histogram is privatised per workgroup in LDS when it fits
 // kLineLdsWords (ds_add_f64), flushed with one global atomic per non-zero word; above that the items add into the global histogram directly.
 
 #include <hip/hip_runtime.h>
@@ -39,38 +40,48 @@ struct LineDev {
     int words;                 // 2 nt ne + 2
 };
 
-// one item that passed the filter -> at most one bin.  PIXEL: x is the pixel's mean 1/g (E = line_energy x, w = emis x^g_index);
-// otherwise x is g (E = line_energy / g, w = emis g^-g_index).  LIMB: w times `limb`.  Returns 1 if the item was binned.
-template <bool PIXEL, bool LIMB = false>
-KR_DEV unsigned line_accumulate(double* acc, const LineDev& L, double r, double x, double t, double limb = 1)
+// one item that passed the filter -> at most one bin k = j ne + i and its weight w; false: the item is not binned.  PIXEL: x is the pixel's mean 1/g
+// (E = line_energy x, w = emis x^g_index); otherwise x is g (E = line_energy / g, w = emis g^-g_index).  LIMB: w times `limb`.
+template <bool PIXEL, bool LIMB>
+KR_DEV bool line_item(const LineDev& L, double r, double x, double t, double limb, int* k, double* w)
 {
     const kr_line_bins& b = L.b;
     double emis, tt = 0;
     if (L.t_emis) {
         // the emissivity app's index (emissivity.cpp:106): truncation, so (-1, table_nr) is the range that lands in [0, table_nr)
         const double fi = b.table_logbin ? kr_log(r / b.table_r_min) / L.log_tdr : (r - b.table_r_min) / b.table_dr;
-        if (!(fi > -1 && fi < b.table_nr)) return 0;
+        if (!(fi > -1 && fi < b.table_nr)) return false;
         const int ir = (int) fi;
         emis = L.t_emis[ir];
-        if (!__builtin_isfinite(emis)) return 0;
+        if (!__builtin_isfinite(emis)) return false;
         if (L.t_time) tt = L.t_time[ir];
     } else {
         emis = powerlaw3(r, b.q1, b.rb1, b.q2, b.rb2, b.q3);
     }
     const double E = PIXEL ? b.line_energy * x : b.line_energy / x;
     const double w0 = emis * (PIXEL ? kr_pow(x, b.g_index) : kr_pow(x, -1 * b.g_index));
-    const double w = LIMB ? w0 * limb : w0;
+    *w = LIMB ? w0 * limb : w0;
     const double fe = b.log_e ? kr_log(E / b.e_min) / L.log_de : (E - b.e_min) / b.de;
-    if (!(fe >= 0 && fe < b.ne)) return 0;              // NaN fails too
+    if (!(fe >= 0 && fe < b.ne)) return false;          // NaN fails too
     int j = 0;
     if (L.time_axis) {
         const double ft = (t + tt - b.t0) / b.dt;
-        if (!(ft >= 0 && ft < b.nt)) return 0;
+        if (!(ft >= 0 && ft < b.nt)) return false;
         j = (int) ft;
     }
-    const int k = j * b.ne + (int) fe;
+    *k = j * b.ne + (int) fe;
+    return true;
+}
+
+// the item into [count | flux].  Returns 1 if the item was binned.
+template <bool PIXEL, bool LIMB = false>
+KR_DEV unsigned line_accumulate(double* acc, const LineDev& L, double r, double x, double t, double limb = 1)
+{
+    int k;
+    double w;
+    if (!line_item<PIXEL, LIMB>(L, r, x, t, limb, &k, &w)) return 0;
     atomicAdd(&acc[k], 1.0);
-    atomicAdd(&acc[b.nt * b.ne + k], w);
+    atomicAdd(&acc[L.b.nt * L.b.ne + k], w);
     return 1;
 }
 
@@ -180,6 +191,43 @@ post_line_limb_kernel(kr_ray_f64* __restrict__ rays, long long n, double spin, d
     line_end<USE_LDS, true>(lds, out, words, on_disc, binned, bad_angle);
 }
 
+// post_line_limb_kernel with the Stokes parameters of the polarised line (include/kr_trace.h, kr_pol_law): g, mu and the polarisation angle at the
+// observer come from ONE metric and momentum evaluation (polar_value; its E is redshift_value's recv to the bit, so rays[] ends as after
+// post_line_kernel).  An item adds 1, w, w delta c2, w delta s2 to its bin.  A bad-pol ray that passed the filter counts in on_disc and bad_pol and is
+// never binned, whatever the limb law.  Layout: [count | I | Q | U](nt ne each) + on_disc, binned, bad_pol.
+template <bool USE_LDS>
+__global__ void __launch_bounds__(kBlock)
+post_line_stokes_kernel(kr_ray_f64* __restrict__ rays, long long n, double spin, double V, int reverse, int projradius, double lo, double hi, double sin_incl,
+                        LineDev L, kr_limb_law limb, kr_pol_law pol, double* __restrict__ out)
+{
+    extern __shared__ double lds[];
+    const int plane = L.b.nt * L.b.ne, words = 4 * plane + 3;
+    double* acc = line_begin<USE_LDS>(lds, out, words);
+    unsigned long long on_disc = 0, binned = 0, bad_pol = 0;
+    KR_GRID_STRIDE(i, n) {
+        kr_ray_f64* ray = &rays[i];
+        const kr_ray_f64 v = polar_record_of(ray);
+        const int steps = ray->steps;
+        const Polar q = polar_value(v, spin, V, reverse, projradius, sin_incl);
+        const double g = q.redshift;
+        ray->redshift = g;
+        wrap_phi(ray, steps, lo, hi);
+        if (!line_filter(L.b, steps, v.r, v.theta, g)) continue;
+        on_disc++;
+        if (q.bad) { bad_pol++; continue; }
+        int k;
+        double w;
+        if (!line_item<false, true>(L, v.r, g, ray->t, limb_weight(limb.law, limb.coeff, q.mu), &k, &w)) continue;
+        binned++;
+        const double wd = w * pol_degree(pol.law, pol.coeff, q.mu);
+        atomicAdd(&acc[k], 1.0);
+        atomicAdd(&acc[plane + k], w);
+        atomicAdd(&acc[2 * plane + k], wd * q.c2);
+        atomicAdd(&acc[3 * plane + k], wd * q.s2);
+    }
+    line_end<USE_LDS, true>(lds, out, words, on_disc, binned, bad_pol);
+}
+
 // planes: [nrays | flux | r | phi | enshift | time | emis](npix each) + disc_count, raw sums (kr_reduce_image_dev_f64)
 template <bool USE_LDS>
 __global__ void __launch_bounds__(kBlock)
@@ -280,6 +328,20 @@ int post_line_limb_dev(double spin, double V, int reverse, int projradius, doubl
     if (rc != KR_OK) return rc;
     KR_LAUNCH_LDS_OR_GLOBAL(post_line_limb_kernel, L.words + 1 <= kLineLdsWords, grid_for(n, kBlock, kCapHist), (L.words + 1) * sizeof(double), st, (kr_ray_f64*) d,
                             (long long) n, spin, V, reverse, projradius, lo, hi, L, *law, (double*) d_line);
+    return KR_OK;
+}
+
+int post_line_stokes_dev(double spin, double V, int reverse, int projradius, double lo, double hi, double inc_deg, const kr_line_bins* b, const kr_limb_law* limb,
+                         const kr_pol_law* pol, void* d, int64_t n, void* d_out, hipStream_t st)
+{
+    if (n <= 0) return KR_OK;
+    TablePins pins;
+    LineDev L;
+    int rc = line_dev(b, pins, &L);
+    if (rc != KR_OK) return rc;
+    const int64_t words = 4 * (int64_t) b->nt * b->ne + 3;
+    KR_LAUNCH_LDS_OR_GLOBAL(post_line_stokes_kernel, words <= kLineLdsWords, grid_for(n, kBlock, kCapHist), (size_t) words * sizeof(double), st, (kr_ray_f64*) d,
+                            (long long) n, spin, V, reverse, projradius, lo, hi, sin_inclination(inc_deg), L, *limb, *pol, (double*) d_out);
     return KR_OK;
 }
 

@@ -157,6 +157,16 @@ int emissivity_mu_validate(const kr_emis_bins* b, const kr_mu_bins* mb, const ch
 int angles_dev(double spin, double V, int reverse, int projradius, const void* d, int64_t n, void* d_angles, hipStream_t st);
 int post_emissivity_mu_dev(double spin, double V, int reverse, int projradius, double lo, double hi, const kr_emis_bins* b, const kr_mu_bins* mb, void* d, int64_t n,
                            void* d_hist, void* d_mu, hipStream_t st);
+// kr_polarisation.hip: the polarisation of disc emission on an image plane (the validators refuse reverse != 1, motion != 0, a non-finite inclination
+// and a bad pol law); the Stokes line lives in kr_line.hip
+int polarisation_validate(int reverse, int motion, double inc_deg, const char* who);
+int pol_validate(const kr_pol_law* law, const char* who);
+double sin_inclination(double inc_deg);
+int polarisation_dev(double spin, double V, int reverse, int projradius, double inc_deg, const void* d, int64_t n, void* d_out, hipStream_t st);
+int post_image_stokes_dev(double spin, double V, int reverse, int projradius, double lo, double hi, double inc_deg, const kr_image_bins* b, const kr_limb_law* limb,
+                          const kr_pol_law* pol, void* d, int64_t n, void* d_stokes, hipStream_t st);
+int post_line_stokes_dev(double spin, double V, int reverse, int projradius, double lo, double hi, double inc_deg, const kr_line_bins* b, const kr_limb_law* limb,
+                         const kr_pol_law* pol, void* d, int64_t n, void* d_out, hipStream_t st);
 // kr_source_vel.hip: the point source with an arbitrary four-velocity.  The validator refuses what kr_pointsource_vel_spec's comment refuses and hands
 // back the emitter's frame (kr_vel_tetrad.hpp), solved on the host; the grid helper gives the reference's truncated counts (false: no int)
 bool pointsource_vel_grid(const kr_pointsource_vel_spec* s, int64_t* total, int* n_cosalpha, int* n_beta);

@@ -156,6 +156,81 @@ KR_DEV double limb_weight(int law, double coeff, double mu)
     return 1;
 }
 
+// ---- the polarisation of disc emission carried to a distant image plane (include/kr_trace.h, kr_polarisation_dev_f64).  The frame is frame_value's,
+//      expression for expression -- E and mu keep its bits, so `redshift` is redshift_value's return value -- and the legs e1, e3 and the momentum p it
+//      is built from go on into the emitted polarisation vector f = (P_phi e3 - P_r e1) / nrm and the Walker-Penrose constant
+//      kappa = (A - iB)(r - i a cos theta), which is inverted at the observer with the ray's own image-plane coordinates (alpha, beta) and the sine of
+//      the plane's inclination.  c2, s2 = cos, sin of twice the polarisation angle, from the image's x axis towards its y axis. ----
+struct Polar {
+    Frame f;
+    double redshift, mu, kappa1, kappa2, c2, s2;
+    bool bad;           // bad-pol: bad-angle, nrm == 0, or a kappa1, kappa2, c2, s2 that is not finite
+};
+
+KR_DEV Polar polar_value(const kr_ray_f64& ray, double spin, double V_in, int reverse, int projradius, double sin_incl)
+{
+    using T = double;
+    const T a = reverse ? -1 * spin : spin;
+    const T r = ray.r, theta = ray.theta;
+    const Metric<T> m = kerr_metric<T>(r, theta, a);
+    T V = V_in;
+    if (V == -1) V = keplerian_V<T>(a, r, theta, projradius != 0);
+    const T et[4] = {(1 / kr_sqrt(m.e2nu)) / kr_sqrt(1 - (V - m.omega) * (V - m.omega) * m.e2psi / m.e2nu), 0, 0,
+                     (1 / kr_sqrt(m.e2nu)) * V / kr_sqrt(1 - (V - m.omega) * (V - m.omega) * m.e2psi / m.e2nu)};
+    const T e1[4] = {(V - m.omega) * kr_sqrt(m.e2psi / m.e2nu) / kr_sqrt(m.e2nu - (V - m.omega) * (V - m.omega) * m.e2psi), 0, 0,
+                     (1 / kr_sqrt(m.e2nu * m.e2psi)) * (m.e2nu + V * m.omega * m.e2psi - m.omega * m.omega * m.e2psi) /
+                         kr_sqrt(m.e2nu - (V - m.omega) * (V - m.omega) * m.e2psi)};
+    const T e2[4] = {0, 0, 1 / kr_sqrt(m.rhosq), 0};
+    const T e3[4] = {0, kr_sqrt(m.delta / m.rhosq), 0, 0};
+    T p[4];
+    momentum<T>(p[0], p[1], p[2], p[3], ray.k, ray.h, ray.Q, ray.rdot_sign, ray.thetadot_sign, r, theta, spin);
+    if (reverse) { p[1] *= -1; p[2] *= -1; p[3] *= -1; }
+    Polar q;
+    q.f.E = energy_dot<T>(m, et, p);
+    q.f.P_phi = -1 * energy_dot<T>(m, e1, p);
+    q.f.P_th = -1 * energy_dot<T>(m, e2, p);
+    q.f.P_r = -1 * energy_dot<T>(m, e3, p);
+    q.redshift = frame_redshift(q.f, ray.emit, reverse);
+    q.mu = frame_mu(q.f);
+
+    // f in coordinates (f^theta = 0): g(f, p) = 0 and g(f, f) = -1 by construction
+    const T nrm = kr_sqrt(q.f.P_r * q.f.P_r + q.f.P_phi * q.f.P_phi);
+    const T f_t = -1 * q.f.P_r * e1[0] / nrm, f_r = q.f.P_phi * e3[1] / nrm, f_th = 0, f_phi = -1 * q.f.P_r * e1[3] / nrm;
+    const T s = kr_sin(theta), c = kr_cos(theta);
+    const T A = (p[0] * f_r - p[1] * f_t) + a * s * s * (p[1] * f_phi - p[3] * f_r);
+    const T B = ((r * r + a * a) * (p[3] * f_th - p[2] * f_phi) - a * (p[0] * f_th - p[2] * f_t)) * s;     // the zero terms stay: 0 * inf poisons as in the rule
+    q.kappa1 = r * A - a * c * B;
+    q.kappa2 = -1 * (r * B + a * c * A);
+
+    // the observer: pixel (x, y) = (alpha, beta) has the impact parameters (-x, -y)
+    const T al = -1 * ray.alpha, be = -1 * ray.beta;
+    const T nu = -1 * (al + a * sin_incl);
+    const T d = nu * nu + be * be;
+    const T f_al = (be * q.kappa2 - nu * q.kappa1) / d, f_be = (be * q.kappa1 + nu * q.kappa2) / d;
+    const T n2 = f_al * f_al + f_be * f_be;
+    q.c2 = (f_al * f_al - f_be * f_be) / n2;
+    q.s2 = 2 * f_al * f_be / n2;
+    q.bad = frame_bad_angle(q.f, q.mu) || nrm == 0 || !__builtin_isfinite(q.kappa1) || !__builtin_isfinite(q.kappa2) || !__builtin_isfinite(q.c2) ||
+            !__builtin_isfinite(q.s2);
+    return q;
+}
+
+// the degree law of kr_pol_law at mu (law validated on the host: 0 or 1)
+KR_DEV double pol_degree(int law, double coeff, double mu)
+{
+    if (law == 1) return coeff * (1 - mu) / (1 + 3.582 * mu);
+    return coeff;
+}
+
+// the geodesic, `emit` and the image-plane coordinates that polar_value reads, copied out of a record that the pass goes on to write to
+KR_DEV kr_ray_f64 polar_record_of(const kr_ray_f64* ray)
+{
+    kr_ray_f64 v;
+    v.r = ray->r; v.theta = ray->theta; v.k = ray->k; v.h = ray->h; v.Q = ray->Q; v.rdot_sign = ray->rdot_sign; v.thetadot_sign = ray->thetadot_sign;
+    v.emit = ray->emit; v.alpha = ray->alpha; v.beta = ray->beta;
+    return v;
+}
+
 // ---- range_phi (raytracer.cpp:603-622): repeated +-2pi like the reference, so the result is bit-identical.  2 * M_PI is a double:
 //      in the float build each `phi -= 2 * M_PI` is a double subtraction rounded back to float, here as there. ----
 template <typename T>
