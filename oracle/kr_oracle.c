@@ -29,6 +29,55 @@
 typedef kr_ray_f64 ray_t;
 
 /* ---------------------------------------------------------------------------------------------- */
+/* Two builds of this file (oracle/Makefile):
+ *   libkr_oracle.so      the KRO_* macros below are the C library's names: the object code of the restatement as it always was, pinned to the
+ *                        compiled reference bit for bit (tests/test_oracle_vs_ref.py, tests/test_oracle_golden.py);
+ *   libkr_oracle_cr.so   -DKRO_CR_MATH: the same expression trees with the DEVICE's own routines at the call sites below -- kr_sincos_f64
+ *                        (csrc/kr_sincos.hpp) and krcr::kr_acos_cr / kr_asin_cr / kr_atan2_cr / kr_tan_cr (csrc/kr_crmath.hpp), compiled for the host by
+ *                        oracle/cr_math_shim.cpp.  What the strict device arithmetic (flags = 0) documents is then an EQUALITY with this build:
+ *                        every Euler / RK4 ray, every field, every bit (tests/test_gpu_exact_parity.py).
+ *
+ * A call site is switched if and only if its device counterpart calls kr_sincos_f64 / krcr::*:
+ *
+ *   site in this file                               calls                      device counterpart (raytrace_cpu_amd/csrc/)
+ *   ----------------------------------------------  -------------------------  ------------------------------------------------------------
+ *   momentum_from_consts (stages k2.., the passes)  sin, cos (theta)           kr_device.hpp:133  momentum_impl -> kr_sincos
+ *   k1_with_flips                                   sin, cos (theta)           kr_device.hpp:174  k1_with_flips -> kr_sincos
+ *   propagate_rk45, seed of the running step        sin, cos (theta)           kr_rk45.hpp:30     kr_sincos
+ *   dest_reached, KR_STOP_FLATPLANE                 sin, cos (theta), sin, cos kr_device.hpp:332  kr_sin / kr_cos of theta, incl and phi - phi0,
+ *                                                   (incl), cos (phi - phi0)                      evaluated per ray on the device
+ *   dest_step_limit                                 (none: quotients only)     kr_device.hpp:338
+ *   kro_imageplane_init_f64, per ray                acos x2, atan2, asin, tan  kr_post_device.hpp:358, :359, :362, :385, :389  krcr::*
+ *                                                   sin (acos(D / r))          kr_post_device.hpp:362  kr_sin
+ *                                                   sin, cos (theta)           kr_post_device.hpp:365  kr_sin / kr_cos
+ *                                                   cos, sin (beta)            kr_post_device.hpp:387, :388
+ *
+ * Sites that stay on the C library, because the device takes the value from the HOST's C library too:
+ *   kro_imageplane_init_f64  sin (incl), cos (incl)     one pair per plane: kr_post.hip:575 plane_trig -> PlaneTrig
+ *   calculate_constants, kro_pointsource_init_f64       host-made tables, kr_post_device.hpp:248-262 (alpha_sc, beta_sc) and kr_capi.hip:455
+ *                                                       (sin / cos / tan of the source's polar angle)
+ * and the sites outside the trace and the image-plane constructor (kerr_metric_at, the redshift passes' own terms, the reducers), which
+ * tests/test_gpu_exact_parity.py does not reach.  (momentum_from_consts is shared with the redshift passes: the device's passes evaluate it with
+ * kr_sincos_f64 as well.)
+ * For |x| >= 1024 kr_sincos_f64 itself hands the argument to the library's sincos(): glibc's here, the device library's there. */
+#ifdef KRO_CR_MATH
+double kro_cr_sin(double), kro_cr_cos(double), kro_cr_acos(double), kro_cr_asin(double), kro_cr_atan2(double, double), kro_cr_tan(double);
+#define KRO_SIN(x) kro_cr_sin(x)
+#define KRO_COS(x) kro_cr_cos(x)
+#define KRO_ACOS(x) kro_cr_acos(x)
+#define KRO_ASIN(x) kro_cr_asin(x)
+#define KRO_ATAN2(y, x) kro_cr_atan2((y), (x))
+#define KRO_TAN(x) kro_cr_tan(x)
+#else
+#define KRO_SIN(x) sin(x)
+#define KRO_COS(x) cos(x)
+#define KRO_ACOS(x) acos(x)
+#define KRO_ASIN(x) asin(x)
+#define KRO_ATAN2(y, x) atan2((y), (x))
+#define KRO_TAN(x) tan(x)
+#endif
+
+/* ---------------------------------------------------------------------------------------------- */
 /* src/include/kerr.h:14-20 */
 double kro_kerr_horizon(double a) { return 1 + 1 * sqrt((1 - a) * (1 + a)); }
 
@@ -51,8 +100,8 @@ double kro_disc_velocity(double r, double a, int sign) { return 1 / (a + sign * 
 static inline void momentum_from_consts(double* pt, double* pr, double* ptheta, double* pphi, double k, double h,
                                         double Q, int rdot_sign, int thetadot_sign, double r, double theta, double a)
 {
-    const double sin_theta = sin(theta);
-    const double cos_theta = cos(theta);
+    const double sin_theta = KRO_SIN(theta);
+    const double cos_theta = KRO_COS(theta);
     const double sin2theta = sin_theta * sin_theta;
     const double rhosq = r * r + (a * cos_theta) * (a * cos_theta);
     const double delta = r * r - 2 * r + a * a;
@@ -105,7 +154,7 @@ static int dest_reached(const kr_params* p, double r, double theta, double phi, 
         }
         case KR_STOP_FLATPLANE: {
             const double incl = p->stop_params[0], phi0 = p->stop_params[1], z_s = p->stop_params[2];
-            const double proj = r * (sin(theta) * sin(incl) * cos(phi - phi0) + cos(theta) * cos(incl));
+            const double proj = r * (KRO_SIN(theta) * KRO_SIN(incl) * KRO_COS(phi - phi0) + KRO_COS(theta) * KRO_COS(incl));
             return proj <= -z_s;
         }
     }
@@ -162,8 +211,8 @@ static inline int k1_with_flips(state_t* s, double k, double h, double Q, double
                                 double* sin2theta_out)
 {
     const double r = s->r, theta = s->theta;
-    const double sin_theta = sin(theta);
-    const double cos_theta = cos(theta);
+    const double sin_theta = KRO_SIN(theta);
+    const double cos_theta = KRO_COS(theta);
     const double sin2theta = sin_theta * sin_theta;
     const double rhosq = r * r + (a * cos_theta) * (a * cos_theta);
     const double delta = r * r - 2 * r + a * a;
@@ -345,7 +394,7 @@ static int propagate_rk45(ray_t* ray, const kr_params* p, int steplim, int64_t* 
     /* seed the running step  :1341-1359 (no flip logic, no boundary clips) */
     {
         const double r = s.r, theta = s.theta;
-        const double sin_theta = sin(theta), cos_theta = cos(theta), sin2theta = sin_theta * sin_theta;
+        const double sin_theta = KRO_SIN(theta), cos_theta = KRO_COS(theta), sin2theta = sin_theta * sin_theta;
         const double rhosq = r * r + (a * cos_theta) * (a * cos_theta);
         const double delta = r * r - 2 * r + a * a;
         s.pt = ((rhosq * (r * r + a * a) + 2 * a * a * r * sin2theta) * k - 2 * a * r * h) / (rhosq * delta);
@@ -769,18 +818,18 @@ int kro_imageplane_init_f64(const kr_imageplane* s, kr_ray_f64* rays, int64_t n)
 
             const double t = 0;
             const double r = sqrt(D * D + x * x + y * y);
-            const double theta = acos((D * cos(incl) + y * sin(incl)) / r);
-            const double phi = phi0 + atan2(x, D * sin(incl) - y * cos(incl));
+            const double theta = KRO_ACOS((D * cos(incl) + y * sin(incl)) / r);
+            const double phi = phi0 + KRO_ATAN2(x, D * sin(incl) - y * cos(incl));
 
             const double pr = D / r;
-            const double ptheta = sin(acos(D / r)) / r;
+            const double ptheta = KRO_SIN(KRO_ACOS(D / r)) / r;
             const double pphi = x * sin(incl) / (x * x + (D * sin(incl) - y * cos(incl)) * (D * sin(incl) - y * cos(incl)));
 
-            const double rhosq = r * r + (a * cos(theta)) * (a * cos(theta));
+            const double rhosq = r * r + (a * KRO_COS(theta)) * (a * KRO_COS(theta));
             const double delta = r * r - 2 * r + a * a;
-            const double sigmasq = (r * r + a * a) * (r * r + a * a) - a * a * delta * sin(theta) * sin(theta);
+            const double sigmasq = (r * r + a * a) * (r * r + a * a) - a * a * delta * KRO_SIN(theta) * KRO_SIN(theta);
             const double e2nu = rhosq * delta / sigmasq;
-            const double e2psi = sigmasq * sin(theta) * sin(theta) / rhosq;
+            const double e2psi = sigmasq * KRO_SIN(theta) * KRO_SIN(theta) / rhosq;
             const double omega = 2 * a * r / sigmasq;
 
             const double g00 = e2nu - omega * omega * e2psi;
@@ -806,12 +855,12 @@ int kro_imageplane_init_f64(const kr_imageplane* s, kr_ray_f64* rays, int64_t n)
             ray->k = 1;
 
             const double b = sqrt(x * x + y * y);
-            double beta = asin(y / b);
+            double beta = KRO_ASIN(y / b);
             if (x < 0) beta = M_PI - beta;
 
-            const double h = -1. * b * sin(incl) * cos(beta);
-            const double ltheta = b * sin(beta);
-            const double Q = (ltheta * ltheta) - (a * cos(theta)) * (a * cos(theta)) + ((h / tan(theta))) * ((h / tan(theta)));
+            const double h = -1. * b * sin(incl) * KRO_COS(beta);
+            const double ltheta = b * KRO_SIN(beta);
+            const double Q = (ltheta * ltheta) - (a * KRO_COS(theta)) * (a * KRO_COS(theta)) + ((h / KRO_TAN(theta))) * ((h / KRO_TAN(theta)));
 
             ray->h = h;
             ray->Q = Q;

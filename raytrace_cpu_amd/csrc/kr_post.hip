@@ -445,6 +445,10 @@ __global__ void __launch_bounds__(kBlock) arith_probe_kernel(int op, const doubl
             case 21: { const StageRecips<double> q(1.0, 1.0, 1.0, x, 1.0); r = q.over_rho4(y); } break;                                       // x = rho^2:               put together
             case 15: kr_sincos_fast_f64(x, s, c); r = s; break;
             case 16: kr_sincos_fast_f64(x, s, c); r = c; break;
+            case 22: r = krcr::kr_acos_cr(x); break;                                 // kr_crmath.hpp, as the device ImagePlane constructor calls them
+            case 23: r = krcr::kr_asin_cr(x); break;
+            case 24: r = krcr::kr_atan2_cr(x, y); break;
+            case 25: r = krcr::kr_tan_cr(x); break;
         }
         out[i] = r;
     }

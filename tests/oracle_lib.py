@@ -1,6 +1,8 @@
 """TEST INFRASTRUCTURE: ctypes loaders for the two CPU checkers under oracle/.
 
   oracle()  -> oracle/libkr_oracle.so   (C restatement; built on demand with oracle/Makefile)
+  oracle_cr() -> oracle/libkr_oracle_cr.so (the same restatement with the device's correctly rounded sin / cos / acos / asin / atan2 / tan at the
+               call sites listed at the top of oracle/kr_oracle.c; what a strict device trace must equal bit for bit)
   ref()     -> oracle/_ref/libkr_ref.so (the reference's own sources compiled with a shim; None when
                neither the prebuilt .so nor /root/reference is available)
 
@@ -18,51 +20,94 @@ sys.path.insert(0, ROOT)
 from raytrace_cpu_amd import capi  # noqa: E402  (interface structs only)
 
 ORACLE_SO = os.path.join(ROOT, "oracle", "libkr_oracle.so")
+ORACLE_CR_SO = os.path.join(ROOT, "oracle", "libkr_oracle_cr.so")
 REF_SO = os.path.join(ROOT, "oracle", "_ref", "libkr_ref.so")
+CR_SOURCES = [os.path.join(ROOT, "oracle", "kr_oracle.c"), os.path.join(ROOT, "oracle", "cr_math_shim.cpp"),
+              os.path.join(ROOT, "raytrace_cpu_amd", "csrc", "kr_sincos.hpp"), os.path.join(ROOT, "raytrace_cpu_amd", "csrc", "kr_crmath.hpp")]
 
 P = C.POINTER
 _vp, _i64, _i32, _dbl, _int = C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_int
 
 
+def _stale(so, sources):
+    return (not os.path.exists(so)) or any(os.path.getmtime(so) < os.path.getmtime(src) for src in sources)
+
+
 def build_oracle(force=False):
     src = os.path.join(ROOT, "oracle", "kr_oracle.c")
-    stale = (not os.path.exists(ORACLE_SO)) or os.path.getmtime(ORACLE_SO) < os.path.getmtime(src)
-    if force or stale:
+    if force or _stale(ORACLE_SO, [src]):
         subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), ORACLE_SO])
     return ORACLE_SO
 
 
+def build_oracle_cr(force=False):
+    """The same staleness rule, extended to the shim and the two device headers it compiles for the host."""
+    if force or _stale(ORACLE_CR_SO, CR_SOURCES):
+        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), ORACLE_CR_SO])
+    return ORACLE_CR_SO
+
+
+def _bind(lib, protos):
+    for name, (res, args) in protos.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = res, args
+    return lib
+
+
+def _oracle_protos():
+    return {
+        "kro_kerr_horizon": (_dbl, [_dbl]),
+        "kro_kerr_isco": (_dbl, [_dbl, _int]),
+        "kro_disc_velocity": (_dbl, [_dbl, _dbl, _int]),
+        "kro_trace_f64": (_int, [P(capi.Params), _vp, _i64, _int, P(capi.Stats)]),
+        "kro_redshift_start_f64": (None, [_dbl, _dbl, _int, _int, _vp, _i64]),
+        "kro_redshift_f64": (None, [_dbl, _dbl, _int, _int, _int, _vp, _i64]),
+        "kro_redshift_dest_f64": (None, [_dbl, _int, _vp, _i64]),
+        "kro_range_phi_f64": (None, [_dbl, _dbl, _vp, _i64]),
+        "kro_calculate_momentum_f64": (None, [_dbl, _vp, _i64]),
+        "kro_pointsource_count": (_i64, [P(capi.PointSourceSpec), P(_i32), P(_i32)]),
+        "kro_pointsource_init_f64": (_int, [P(capi.PointSourceSpec), _vp, _i64]),
+        "kro_imageplane_count": (_i64, [P(capi.ImagePlaneSpec), P(_i32), P(_i32)]),
+        "kro_imageplane_init_f64": (_int, [P(capi.ImagePlaneSpec), _vp, _i64]),
+        "kro_reduce_emissivity_f64": (None, [P(capi.EmisBins), _vp, _i64, _vp, _vp, _vp, _vp, _vp, P(_i64)]),
+        "kro_reduce_image_f64": (None, [P(capi.ImageBins), _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, P(_i64)]),
+        "kro_reduce_return_f64": (None, [P(capi.ReturnBins), _vp, _i64, P(_dbl * 4)]),
+        "kro_max_threads": (_int, []),
+    }
+
+
 _oracle = None
+_oracle_cr = None
 
 
 def oracle():
     global _oracle
     if _oracle is None:
-        lib = C.CDLL(build_oracle())
-        protos = {
-            "kro_kerr_horizon": (_dbl, [_dbl]),
-            "kro_kerr_isco": (_dbl, [_dbl, _int]),
-            "kro_disc_velocity": (_dbl, [_dbl, _dbl, _int]),
-            "kro_trace_f64": (_int, [P(capi.Params), _vp, _i64, _int, P(capi.Stats)]),
-            "kro_redshift_start_f64": (None, [_dbl, _dbl, _int, _int, _vp, _i64]),
-            "kro_redshift_f64": (None, [_dbl, _dbl, _int, _int, _int, _vp, _i64]),
-            "kro_redshift_dest_f64": (None, [_dbl, _int, _vp, _i64]),
-            "kro_range_phi_f64": (None, [_dbl, _dbl, _vp, _i64]),
-            "kro_calculate_momentum_f64": (None, [_dbl, _vp, _i64]),
-            "kro_pointsource_count": (_i64, [P(capi.PointSourceSpec), P(_i32), P(_i32)]),
-            "kro_pointsource_init_f64": (_int, [P(capi.PointSourceSpec), _vp, _i64]),
-            "kro_imageplane_count": (_i64, [P(capi.ImagePlaneSpec), P(_i32), P(_i32)]),
-            "kro_imageplane_init_f64": (_int, [P(capi.ImagePlaneSpec), _vp, _i64]),
-            "kro_reduce_emissivity_f64": (None, [P(capi.EmisBins), _vp, _i64, _vp, _vp, _vp, _vp, _vp, P(_i64)]),
-            "kro_reduce_image_f64": (None, [P(capi.ImageBins), _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, P(_i64)]),
-            "kro_reduce_return_f64": (None, [P(capi.ReturnBins), _vp, _i64, P(_dbl * 4)]),
-            "kro_max_threads": (_int, []),
-        }
-        for name, (res, args) in protos.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
-        _oracle = lib
+        _oracle = _bind(C.CDLL(build_oracle()), _oracle_protos())
     return _oracle
+
+
+CR_OPS = {"sin": 0, "cos": 1, "acos": 2, "asin": 3, "atan2": 4, "tan": 5}
+
+
+def oracle_cr():
+    """The correctly rounded build: the oracle's prototypes, and the shim's own entry points (oracle/cr_math_shim.cpp)."""
+    global _oracle_cr
+    if _oracle_cr is None:
+        protos = _oracle_protos()
+        protos.update({f"kro_cr_{f}": (_dbl, [_dbl, _dbl] if f == "atan2" else [_dbl]) for f in CR_OPS})
+        protos["kro_cr_apply"] = (_int, [_int, _vp, _vp, _vp, _i64])
+        _oracle_cr = _bind(C.CDLL(build_oracle_cr()), protos)
+    return _oracle_cr
+
+
+def cr_apply(name, a, b=None):
+    """The shim's `name` (a key of CR_OPS) over an array of arguments."""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    b = a if b is None else np.ascontiguousarray(b, dtype=np.float64)
+    out = np.empty_like(a)
+    assert a.shape == b.shape and oracle_cr().kro_cr_apply(CR_OPS[name], ptr(a), ptr(b), ptr(out), a.size) == 0
+    return out
 
 
 _ref = False
@@ -101,9 +146,7 @@ def ref():
             "ref_kerr_isco": (_dbl, [_dbl, _int]),
             "ref_disc_velocity": (_dbl, [_dbl, _dbl, _int]),
         }
-        for name, (res, args) in protos.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
+        _bind(lib, protos)
         assert lib.ref_sizeof_ray() == capi.RAY_F64.itemsize
         _ref = lib
     return _ref
@@ -143,8 +186,9 @@ def oracle_pointsource(spec):
     return rays
 
 
-def oracle_imageplane(spec):
-    lib = oracle()
+def oracle_imageplane(spec, cr=False):
+    """The ImagePlane constructor's rays; cr: with the device's correctly rounded acos / atan2 / asin / tan / sin / cos per ray."""
+    lib = oracle_cr() if cr else oracle()
     n = lib.kro_imageplane_count(C.byref(spec), None, None)
     rays = np.zeros(n, dtype=capi.RAY_F64)
     rc = lib.kro_imageplane_init_f64(C.byref(spec), ptr(rays), n)
@@ -152,11 +196,11 @@ def oracle_imageplane(spec):
     return rays
 
 
-def oracle_trace(params, rays, nthreads=0):
-    """Traces a COPY of rays through the oracle; returns (rays_out, stats dict)."""
+def oracle_trace(params, rays, nthreads=0, cr=False):
+    """Traces a COPY of rays through the oracle (cr: the correctly rounded build); returns (rays_out, stats dict)."""
     out = rays.copy()
     st = capi.Stats()
-    rc = oracle().kro_trace_f64(C.byref(params), ptr(out), len(out), nthreads, C.byref(st))
+    rc = (oracle_cr() if cr else oracle()).kro_trace_f64(C.byref(params), ptr(out), len(out), nthreads, C.byref(st))
     assert rc == 0, rc
     return out, st.as_dict()
 
