@@ -435,6 +435,51 @@ typedef struct kr_pol_law {
 static_assert(sizeof(kr_pol_law) == 16, "kr_pol_law is 16 bytes (raytrace_cpu_amd/capi.py PolLaw)");
 #endif
 
+/* Continuum spectrum of the disc from image-plane rays: a multicolour blackbody (what kerrbb computes) or any tabulated rest-frame spectrum (a
+ * reflection table, a cut-off power law) smeared by the rays.  Where kr_line_bins puts a ray into ONE energy bin, here every disc ray adds to EVERY
+ * output energy.  Per ray record, after redshift(V, reverse, projradius, motion):
+ *   filter   the one of kr_line_bins: steps > 0, r cos(theta) < 1e-2, r_isco <= r < r_disc, g > 0 with g = rays[].redshift (E_rest = g E_obs, as the
+ *            line uses it).  A ray that passes counts in `on_disc`.
+ *   energies ne points; E_i is the CENTRE of bin i of the grid (e_min, de, log_e) of kr_line_bins: E_i = e_min + (i + 0.5) de, or the geometric
+ *            centre E_i = e_min de^(i + 0.5) with log_e.  The spectrum is SAMPLED at E_i, not integrated over the bin.
+ *   sum      flux[i] += w g^-3 I_rest(g E_i)  for every i (invariance of I / E^3; g^-3 = 1 / (g g g)).  Every ray is an equal image-plane pixel: the
+ *            solid-angle factor dx dy / D^2 is the caller's.
+ *   limb     limb(mu) of kr_limb_law, mu from the frame evaluation that gives g.  A bad-angle ray that passed the filter counts in `bad_angle`; with
+ *            law != 0 it is not used, with law 0 it is used like every other ray.  The reduce forms are isotropic (law 0, no mu, bad_angle = 0).
+ *   ir       the truncated radial-table index of kr_line_bins: fi = log(r / table_r_min) / log(table_dr) (table_logbin) or (r - table_r_min) / table_dr,
+ *            ir = (int) fi for fi in (-1, table_nr); outside: no ir.
+ * model 0, thermal:  I_rest(E') = f_col^-4 E'^3 / expm1(E' / (f_col kT)),  kT = table_kt[ir] (the units of E),  w = limb(mu).  A ray without ir, or
+ *            whose kT is not finite or not positive, passes the filter but is not used.  (The kernel multiplies E' by 1 / (f_col kT), rounded once per
+ *            ray; the rays' common factor f_col^-4 multiplies w g^-3.)
+ * model 1, table:    I_rest(E') = S_z(E'),  w = emis(r) limb(mu),  emis = powerlaw3(r), or table_emis[ir] when table_emis != NULL -- a ray without
+ *            ir or with a non-finite table_emis[ir] is not used: exactly the line's emissivity.
+ *            S is a host array [nz][s_ne] on a log-energy grid: node k at s_e_min s_de^k, s_de > 1.  Linear interpolation in log E' between neighbouring
+ *            nodes; exactly 0 for E' < s_e_min or E' > s_e_last = s_e_min pow(s_de, s_ne - 1) (in double, taken once): the last node itself is inside.
+ *            The node position is p = u_g + u_i with u_g = log(g) / log(s_de) per ray and u_i = (log(E_i) - log(s_e_min)) / log(s_de) per energy,
+ *            each taken once; p clamped to [0, s_ne - 1], k = min((int) p, s_ne - 2), S_z(E') = S[z][k] + (p - k) (S[z][k + 1] - S[z][k]).
+ *            z is the radial zone (ionisation gradients): nz >= 1 zones, log-spaced over [r_isco, r_disc):
+ *            z = (int) (nz log(r / r_isco) / log(r_disc / r_isco)), clamped to [0, nz - 1].
+ * A ray that adds to the sums counts in `used`.
+ * Output: double[ne + 4] = [flux (ne) | on_disc | used | bad_angle | 0], ADDED into: shards, several planes and several calls sum.
+ * Refused (KR_EINVAL): a null model, ne < 1 or ne > 4096, de <= 0, log_e with de <= 1 or e_min <= 0, an unknown model, a non-finite parameter;
+ * model 0 without table_kt, with table_nr < 1 or f_col <= 0; model 1 with s == NULL, s_ne < 2, s_de <= 1, s_e_min <= 0, nz < 1, nz s_ne > 2^20, or
+ * table_emis with table_nr < 1.  The tables are copied to the device once per distinct contents (the table cache of kr_line_bins). */
+typedef struct kr_spectrum_model {
+    double e_min, de;              /* output energies: the centres of these bins; log_e: de is the ratio between edges */
+    double r_isco, r_disc;         /* disc filter; the span of the zones */
+    double q1, rb1, q2, rb2, q3;   /* powerlaw3 emissivity (model 1 without table_emis) */
+    double f_col;                  /* colour-correction factor (model 0) */
+    double table_r_min, table_dr;  /* the radial table of table_kt / table_emis, binned like kr_emis_bins */
+    double s_e_min, s_de;          /* model 1: first node and node ratio of the rest-frame grid */
+    const double* table_kt;        /* HOST, table_nr values of kT (model 0) */
+    const double* table_emis;      /* HOST, table_nr values, or NULL: powerlaw3 (model 1) */
+    const double* s;               /* HOST, nz x s_ne values (model 1) */
+    int32_t model, ne, log_e, table_nr, table_logbin, s_ne, nz, pad;
+} kr_spectrum_model;
+#ifdef __cplusplus
+static_assert(sizeof(kr_spectrum_model) == 168, "kr_spectrum_model is 168 bytes (raytrace_cpu_amd/capi.py SpectrumModel)");
+#endif
+
 /* Critical-curve (caustic) maps of the disc on an image plane: src/caustic/caustic_discplane.cpp.  Per image-plane pixel (ix, iy), from the ray through
  * the pixel (bundle mode: member 0 of its 5-ray bundle, imageplane_bundles.h) after redshift(dest, reverse) (caustic_discplane.cpp:219-251):
  *   valid_hit   steps > 0, r_isco <= r < r_disc, redshift > 0 (:177-182)
@@ -1069,6 +1114,19 @@ int kr_post_image_stokes_dev_f64(double spin, double V, int reverse, int projrad
  * law.  rays[] ends up exactly as after kr_post_line_dev_f64. */
 int kr_post_line_stokes_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, double inc_deg, const kr_line_bins* b,
                                 const kr_limb_law* limb, const kr_pol_law* pol, void* d_rays, int64_t n, void* d_out, void* stream);
+
+/* ---- continuum spectrum of the disc (kr_spectrum_model above has the rule) --------------------------------------------------------------------
+ * Every entry point validates its arguments before it touches a device: KR_EINVAL (message in kr_last_error) for a null pointer, n < 0, whatever the
+ * model's comment refuses, a limb law other than 0, 1, 2, and motion != 0 with a limb law other than 0 (only the orbiting observer has the frame of
+ * mu).  n == 0 is KR_OK and adds nothing.  None of the _dev forms waits for the device or allocates, beyond the table cache's first copy of a table.
+ * kr_post_spectrum_dev_f64: redshift(V, reverse, projradius, motion) + range_phi(lo, hi) + the spectrum in one pass; rays[] ends up exactly as after
+ * kr_post_line_dev_f64.  ADDS into d_out (ne + 4 doubles; zero it first).
+ * kr_reduce_spectrum_dev_f64: records that already carry their redshift; reads the records and never writes them; isotropic (law 0, no mu).
+ * kr_reduce_spectrum_f64: host records, out = ne + 4 host doubles (overwritten). */
+int kr_post_spectrum_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_spectrum_model* m,
+                             const kr_limb_law* law, void* d_rays, int64_t n, void* d_out, void* stream);
+int kr_reduce_spectrum_dev_f64(const kr_spectrum_model* m, const void* d_rays, int64_t n, void* d_out, void* stream);
+int kr_reduce_spectrum_f64(const kr_spectrum_model* m, const kr_ray_f64* rays, int64_t n, double* out);
 
 /* ---- critical-curve maps (kr_caustic_map above): caustic_discplane.cpp on the device -------------------------------------------------------
  * Every entry point validates its arguments before it touches a device: KR_EINVAL (message in kr_last_error) when nx or ny < 1, eps_x or eps_y

@@ -1554,3 +1554,132 @@ def angdist_text(res):
     columns of escape, return, lost per bin, every field setw(20) scientific with precision 8 (host/include/text_output.h)."""
     cols = [res["angle"]] + [res[f"{c}_{a}"] for c in ANGDIST_CLASSES for a in ANGDIST_ANGLES]
     return "".join("".join(_path_field(float(col[i])) for col in cols) + "\n" for i in range(len(res["angle"])))
+
+
+# ---- continuum spectrum of the disc (include/kr_trace.h, kr_spectrum_model) ----
+def _spectrum_layout(model, words=None):
+    return _layout([("flux", (model.ne,))], [("on_disc", _rounded), ("used", _rounded), ("bad_angle", _rounded), (None, None)], words)
+
+
+def spectrum_words(model):
+    """Length of the buffer of kr_post_spectrum_dev_f64 / kr_reduce_spectrum_dev_f64: [flux (ne) | on_disc | used | bad_angle | 0]."""
+    return _spectrum_layout(model)
+
+
+def spectrum_energies(model):
+    """The ne energies at which the spectrum is sampled: the centres of the bins (e_min, de, log_e) -- geometric centres with log_e."""
+    i = np.arange(model.ne) + 0.5
+    return model.e_min * np.float64(model.de) ** i if model.log_e else model.e_min + i * model.de
+
+
+def spectrum_from_words(model, words):
+    """The buffer of the spectrum entry points as a dict: flux (ne), on_disc, used, bad_angle, and `energy`, the ne sampling energies."""
+    out = _spectrum_layout(model, words)
+    out["energy"] = spectrum_energies(model)
+    return out
+
+
+def reduce_spectrum(model, rays):
+    """kr_reduce_spectrum_f64: the isotropic continuum spectrum of host ray records that carry their redshift."""
+    _rays_arg(rays, capi.RAY_F64)
+    out = np.zeros(spectrum_words(model))
+    capi.check(lib(), lib().kr_reduce_spectrum_f64(C.byref(model), _ptr(rays), len(rays), _ptr(out)), "kr_reduce_spectrum")
+    return spectrum_from_words(model, out)
+
+
+def isco_radius(spin):
+    """The prograde ISCO of Bardeen, Press & Teukolsky (1972) in double precision (kr_kerr_isco keeps the reference's float-rounded intermediates)."""
+    a = float(spin)
+    z1 = 1 + np.cbrt((1 - a) * (1 + a)) * (np.cbrt(1 + a) + np.cbrt(1 - a))
+    z2 = np.sqrt(3 * a * a + z1 * z1)
+    return float(3 + z2 - np.sqrt((3 - z1) * (3 + z1 + 2 * z2)))
+
+
+def novikov_thorne_flux(r, spin, r_isco=None):
+    """The flux of a Novikov-Thorne disc per unit proper area of one face, for Mdot = 1 and M = 1 (G = c = 1), prograde orbits: the closed form of
+    Page & Thorne (1974), in x = sqrt(r):
+      F = 3 / (8 pi) [x - x0 - 1.5 a ln(x / x0) - sum_k 3 (x_k - a)^2 / (x_k prod_{j != k} (x_k - x_j)) ln((x - x_k) / (x0 - x_k))] / (x^4 (x^3 - 3 x + 2 a))
+    with x0 = sqrt(r_isco), x_1,2 = 2 cos((acos(a) -+ pi) / 3), x_3 = -2 cos(acos(a) / 3), the roots of x^3 - 3 x + 2 a.  Exactly 0 at r_isco (default:
+    isco_radius(spin)), NaN inside it."""
+    a = float(spin)
+    r = np.asarray(r, dtype=np.float64)
+    x0 = np.sqrt(isco_radius(a) if r_isco is None else float(r_isco))
+    ac = np.arccos(a)
+    roots = [2 * np.cos((ac - np.pi) / 3), 2 * np.cos((ac + np.pi) / 3), -2 * np.cos(ac / 3)]
+    with np.errstate(all="ignore"):
+        x = np.sqrt(r)
+        bracket = x - x0 - 1.5 * a * np.log(x / x0)
+        for k, xk in enumerate(roots):
+            others = [xj for j, xj in enumerate(roots) if j != k]
+            bracket = bracket - 3 * (xk - a) ** 2 / (xk * (xk - others[0]) * (xk - others[1])) * np.log((x - xk) / (x0 - xk))
+        F = 3 / (8 * np.pi) * bracket / (x ** 4 * (x ** 3 - 3 * x + 2 * a))
+        return np.where(x >= x0, F, np.nan)
+
+
+# CODATA 2018 / IAU 2015 values, cgs
+K_B_KEV_PER_K = 8.617333262e-8
+SIGMA_SB_CGS = 5.670374419e-5
+G_CGS = 6.67430e-8
+C_CGS = 2.99792458e10
+M_SUN_G = 1.98841e33
+
+
+def thermal_kt_table(spin, r_min, dr, nr, mass_msun, mdot_g_s, f_col=1.0, logbin=True):
+    """kT in keV of the Novikov-Thorne disc at the CENTRE of each of the nr radial bins (r_min, dr, logbin) of a kr_spectrum_model's table_kt --
+    geometric centres r_min dr^(i + 0.5) with logbin, r_min + (i + 0.5) dr otherwise:  kT = k_B (F Mdot c^6 / (G^2 M^2) / sigma_SB)^(1/4), the
+    EFFECTIVE temperature.  f_col does not enter the table: the model's rule applies it (I = f_col^-4 B(E, f_col kT)); the argument is accepted so
+    that one set of keywords describes the disc, and is checked.  NaN inside the ISCO."""
+    if not f_col > 0:
+        raise KrError("thermal_kt_table: f_col must be positive")
+    i = np.arange(int(nr)) + 0.5
+    r = r_min * np.float64(dr) ** i if logbin else r_min + i * dr
+    scale = mdot_g_s * C_CGS ** 6 / (G_CGS ** 2 * (mass_msun * M_SUN_G) ** 2)
+    with np.errstate(invalid="ignore"):
+        return K_B_KEV_PER_K * (novikov_thorne_flux(r, spin) * scale / SIGMA_SB_CGS) ** 0.25
+
+
+def resample_spectrum(energy, counts, spec_bins):
+    """A two-column rest-frame spectrum (energies ascending and positive) onto the log grid of a kr_spectrum_model: spec_bins nodes from the first to the
+    last energy, each value interpolated linearly in log E between the file's neighbouring points.  Returns (s_e_min, s_de, S of shape (spec_bins,))."""
+    energy, counts = np.asarray(energy, dtype=np.float64), np.asarray(counts, dtype=np.float64)
+    if len(energy) < 2 or spec_bins < 2 or not (np.diff(energy) > 0).all() or not energy[0] > 0:
+        raise KrError("resample_spectrum: needs at least two ascending positive energies and spec_bins >= 2")
+    s_de = float(np.exp(np.log(energy[-1] / energy[0]) / (spec_bins - 1)))
+    nodes = energy[0] * s_de ** np.arange(spec_bins)
+    nodes[-1] = min(nodes[-1], energy[-1])
+    return float(energy[0]), s_de, np.interp(np.log(nodes), np.log(energy), counts)
+
+
+def disc_spectrum(imageplane_spec, params, model, limb=None, return_records=False):
+    """The continuum spectrum of the disc seen on an image plane, resident on the device from start to finish, as the kr_disc_spectrum app runs it:
+    ImagePlane ctor + redshift_start (kr_imageplane_init_emit_dev_f64) -> trace (kr_trace_dev_f64; `params` as for the image app: the stored, negated
+    spin) -> redshift + range_phi + the spectrum (kr_post_spectrum_dev_f64).  model: a capi.SpectrumModel; limb: None (isotropic) or a limb law as for
+    line_profile.  Only the ne + 4 words are read back (and, with return_records, the final records: for tests).  Returns spectrum_from_words(...)
+    plus "stats" (the trace's kr_stats).  The flux is per image-plane pixel: multiply by dx dy / D^2 for a flux density."""
+    law = capi.limb_law(limb if limb is not None else "isotropic")
+    L = lib()
+    n, _, _ = imageplane_count(imageplane_spec)
+    if n <= 0:
+        raise KrError("disc_spectrum: empty ray grid")
+    sized = 1 <= model.ne <= 4096                      # (the pass refuses the rest: it gets a null buffer)
+    nw = spectrum_words(model) if sized else 0
+    st = Stats()
+    with DeviceScope(L) as dev:
+        d_out = dev.zeros(nw * 8) if sized else C.c_void_p()
+        d_rays = dev.alloc(n * capi.RAY_F64.itemsize)
+        capi.check(L, L.kr_imageplane_init_emit_dev_f64(C.byref(imageplane_spec), 0, 1, 0.0, 1, 0, d_rays, n, None), "kr_imageplane_init_emit")
+        capi.check(L, L.kr_trace_dev_f64(C.byref(params), d_rays, n, None, C.byref(st)), "kr_trace_dev")
+        capi.check(L, L.kr_post_spectrum_dev_f64(-1 * imageplane_spec.spin, -1.0, 1, 0, 0, -np.pi, np.pi, C.byref(model), C.byref(law), d_rays, n, d_out, None),
+                   "kr_post_spectrum")
+        res = spectrum_from_words(model, dev.fetch(d_out, nw))
+        res["stats"] = st.as_dict()
+        if return_records:
+            res["records"] = dev.fetch(d_rays, n, capi.RAY_F64)
+    return res
+
+
+def spectrum_text(res):
+    """The file kr_disc_spectrum writes for a result of disc_spectrum(): three comment rows with the tallies ("# ON_DISC", "# USED", "# BAD_ANGLE" and
+    their counts), then one row per energy: E flux.  Every field setw(20), the numbers scientific with precision 8 (host/include/text_output.h)."""
+    head = "".join("%20s%20d\n" % (f"# {k.upper()}", res[k]) for k in ("on_disc", "used", "bad_angle"))
+    return head + "".join(_path_field(float(e)) + _path_field(float(f)) + "\n" for e, f in zip(res["energy"], res["flux"]))

@@ -5,7 +5,13 @@
 #ifndef KR_EMISSIVITY_TABLE_H_
 #define KR_EMISSIVITY_TABLE_H_
 
+#include <cmath>
+#include <cstdlib>
+#include <fstream>
+#include <sstream>
+#include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "../host/include/text_output.h"
 
@@ -27,6 +33,40 @@ inline void write_emissivity_table(const std::string& out_name, int Nr, const do
         outfile << endl;
     }
     outfile.close();
+}
+
+// reading one back (kr_line_profile, kr_disc_spectrum: emis_file): r and the emis / time columns of a 7-column emissivity table; table_r_min and the
+// edge ratio from the r column, which must be log-spaced
+struct EmisTable {
+    std::vector<double> emis, time;
+    double r_min = 0, dr = 0;
+};
+
+inline EmisTable read_emis_table(const std::string& name)
+{
+    std::ifstream f(name);
+    if (!f) throw std::runtime_error("emis_file: cannot open " + name);
+    std::vector<double> r;
+    EmisTable t;
+    std::string line;
+    while (std::getline(f, line)) {
+        std::istringstream ss(line);
+        std::vector<double> cols;
+        std::string tok;
+        while (ss >> tok) cols.push_back(strtod(tok.c_str(), nullptr));
+        if (cols.empty()) continue;
+        if (cols.size() != 7) throw std::runtime_error("emis_file: expected 7 columns (r, area, rays, flux, emis, redshift, time) in " + name);
+        r.push_back(cols[0]);
+        t.emis.push_back(cols[4]);
+        t.time.push_back(cols[6]);
+    }
+    if (r.size() < 2) throw std::runtime_error("emis_file: fewer than two radial bins in " + name);
+    const size_t nr = r.size();
+    t.r_min = r[0];
+    t.dr = std::exp(std::log(r[nr - 1] / r[0]) / (double) (nr - 1));
+    for (size_t i = 0; i < nr; ++i)
+        if (!(std::fabs(r[i] / (t.r_min * std::pow(t.dr, (double) i)) - 1) <= 1e-7)) throw std::runtime_error("emis_file: the r column is not log-spaced to 1e-7 in " + name);
+    return t;
 }
 
 }   // namespace krapp

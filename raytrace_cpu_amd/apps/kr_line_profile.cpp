@@ -35,43 +35,7 @@ using namespace std;
 #include "../host/include/par_file.h"
 #include "../host/include/text_output.h"
 #include "app_common.h"
-
-namespace {
-
-// r and the emis / time columns of a 7-column emissivity table; table_r_min and the edge ratio from the r column, which must be log-spaced
-struct EmisTable {
-    vector<double> emis, time;
-    double r_min = 0, dr = 0;
-};
-
-EmisTable read_emis_table(const string& name)
-{
-    ifstream f(name);
-    if (!f) throw runtime_error("emis_file: cannot open " + name);
-    vector<double> r;
-    EmisTable t;
-    string line;
-    while (getline(f, line)) {
-        istringstream ss(line);
-        vector<double> cols;
-        string tok;
-        while (ss >> tok) cols.push_back(strtod(tok.c_str(), nullptr));
-        if (cols.empty()) continue;
-        if (cols.size() != 7) throw runtime_error("emis_file: expected 7 columns (r, area, rays, flux, emis, redshift, time) in " + name);
-        r.push_back(cols[0]);
-        t.emis.push_back(cols[4]);
-        t.time.push_back(cols[6]);
-    }
-    if (r.size() < 2) throw runtime_error("emis_file: fewer than two radial bins in " + name);
-    const size_t nr = r.size();
-    t.r_min = r[0];
-    t.dr = exp(log(r[nr - 1] / r[0]) / (double) (nr - 1));
-    for (size_t i = 0; i < nr; ++i)
-        if (!(fabs(r[i] / (t.r_min * pow(t.dr, (double) i)) - 1) <= 1e-7)) throw runtime_error("emis_file: the r column is not log-spaced to 1e-7 in " + name);
-    return t;
-}
-
-}  // namespace
+#include "emissivity_table.h"
 
 int main(int argc, char** argv)
 try {
@@ -145,9 +109,9 @@ try {
     lb.r_isco = r_isco; lb.r_disc = r_disc;
     lb.q1 = q1; lb.rb1 = rb1; lb.q2 = q2; lb.rb2 = rb2; lb.q3 = q3;
     lb.g_index = g_index;
-    EmisTable table;
+    krapp::EmisTable table;
     if (!emis_file.empty()) {
-        table = read_emis_table(emis_file);
+        table = krapp::read_emis_table(emis_file);
         lb.table_r_min = table.r_min; lb.table_dr = table.dr; lb.table_logbin = 1;
         lb.table_nr = (int32_t) table.emis.size();
         lb.table_emis = table.emis.data();

@@ -161,6 +161,42 @@ def pol_law(pol):
     return out
 
 
+class SpectrumModel(C.Structure):
+    """kr_spectrum_model: the continuum spectrum of the disc -- model 0 thermal (table_kt, f_col), model 1 a tabulated rest-frame spectrum (s, nz x s_ne
+    on a log-energy grid) -- sampled at the centres of the energy bins (include/kr_trace.h has the per-ray rule).  table_kt / table_emis / s are host double
+    arrays or None; keep the arrays alive while the struct is in use (spectrum_model does)."""
+    _fields_ = [(n, C.c_double) for n in ("e_min", "de", "r_isco", "r_disc", "q1", "rb1", "q2", "rb2", "q3", "f_col", "table_r_min", "table_dr", "s_e_min", "s_de")] + \
+               [(n, C.POINTER(C.c_double)) for n in ("table_kt", "table_emis", "s")] + \
+               [(n, C.c_int32) for n in ("model", "ne", "log_e", "table_nr", "table_logbin", "s_ne", "nz", "pad")]
+
+
+assert C.sizeof(SpectrumModel) == 168
+
+SPECTRUM_MODELS = {"thermal": 0, "table": 1}
+
+
+def spectrum_model(model, e_min, de, ne, log_e=False, r_isco=1.0, r_disc=1000.0, q1=3.0, rb1=4.0, q2=3.0, rb2=10.0, q3=3.0, f_col=1.0, table_r_min=0.0,
+                   table_dr=0.0, table_logbin=True, table_kt=None, table_emis=None, s=None, s_e_min=0.0, s_de=0.0):
+    """A SpectrumModel.  model: "thermal" / 0 (needs table_kt, binned by table_r_min, table_dr, table_logbin like kr_emis_bins) or "table" / 1 (needs s of
+    shape (nz, s_ne) or (s_ne,), nodes at s_e_min s_de^k; emissivity powerlaw3 or table_emis).  The arrays are copied and kept alive by the struct."""
+    m = SpectrumModel()
+    m.model = SPECTRUM_MODELS.get(model, model) if isinstance(model, str) else int(model)
+    m.e_min, m.de, m.ne, m.log_e = e_min, de, ne, int(log_e)
+    m.r_isco, m.r_disc, m.q1, m.rb1, m.q2, m.rb2, m.q3, m.f_col = r_isco, r_disc, q1, rb1, q2, rb2, q3, f_col
+    m.table_r_min, m.table_dr, m.table_logbin, m.s_e_min, m.s_de = table_r_min, table_dr, int(table_logbin), s_e_min, s_de
+    m._keep = {}
+    for name, a in (("table_kt", table_kt), ("table_emis", table_emis)):
+        if a is not None:
+            m._keep[name] = np.ascontiguousarray(a, dtype=np.float64).copy()
+            setattr(m, name, m._keep[name].ctypes.data_as(C.POINTER(C.c_double)))
+            m.table_nr = len(m._keep[name])
+    if s is not None:
+        m._keep["s"] = np.atleast_2d(np.ascontiguousarray(s, dtype=np.float64)).copy()
+        m.s = m._keep["s"].ctypes.data_as(C.POINTER(C.c_double))
+        m.nz, m.s_ne = m._keep["s"].shape
+    return m
+
+
 class CausticMap(C.Structure):
     """kr_caustic_map: what the critical-curve passes need besides the records (include/kr_trace.h has the per-pixel rules)."""
     _fields_ = [(n, C.c_double) for n in ("r_isco", "r_disc", "eps_x", "eps_y")] + [(n, C.c_int32) for n in ("nx", "ny", "bundles", "pad")]
@@ -362,6 +398,9 @@ PROTOTYPES = {
     "kr_polarisation_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _vp, _i64, _vp]),
     "kr_post_image_stokes_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, _dbl, P(ImageBins), P(LimbLaw), P(PolLaw), _vp, _i64, _vp, _vp]),
     "kr_post_line_stokes_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, _dbl, P(LineBins), P(LimbLaw), P(PolLaw), _vp, _i64, _vp, _vp]),
+    "kr_post_spectrum_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, P(SpectrumModel), P(LimbLaw), _vp, _i64, _vp, _vp]),
+    "kr_reduce_spectrum_dev_f64": (_int, [P(SpectrumModel), _vp, _i64, _vp, _vp]),
+    "kr_reduce_spectrum_f64": (_int, [P(SpectrumModel), _vp, _i64, _vp]),
     "kr_bundles_init_emit_dev_f64": (_int, [P(ImagePlaneSpec), _dbl, _dbl, _int, _int, _vp, _i64, _vp]),
     "kr_post_caustic_disc_dev_f64": (_int, [_dbl, _int, P(CausticMap), _vp, _i64, _vp, _vp]),
     "kr_caustic_suppress_dev_f64": (_int, [P(CausticMap), _vp, _vp]),

@@ -1162,6 +1162,35 @@ int kr_post_emissivity_mu_dev_f64(double spin, double V, int reverse, int projra
                      [&] { return post_emissivity_mu_dev(spin, V, reverse, projradius, lo, hi, b, mb, d, n, d_hist, d_mu, (hipStream_t) st); });
 }
 
+// ---- continuum spectrum of the disc (kr_spectrum.hip): everything is validated before anything touches a device ----
+int kr_post_spectrum_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_spectrum_model* m, const kr_limb_law* law,
+                             void* d, int64_t n, void* d_out, void* st)
+{
+    int rc = spectrum_validate(m, "kr_post_spectrum");
+    if (rc == KR_OK) rc = spectrum_law_validate(law, motion, "kr_post_spectrum");
+    if (rc != KR_OK) return rc;
+    return on_device(n >= 0 && d_out && (n == 0 || d), "kr_post_spectrum: null argument or negative n",
+                     [&] { return post_spectrum_dev(spin, V, reverse, projradius, motion, lo, hi, m, law, d, n, d_out, (hipStream_t) st); });
+}
+
+int kr_reduce_spectrum_dev_f64(const kr_spectrum_model* m, const void* d, int64_t n, void* d_out, void* st)
+{
+    const int rc = spectrum_validate(m, "kr_reduce_spectrum");
+    if (rc != KR_OK) return rc;
+    return on_device(n >= 0 && d_out && (n == 0 || d), "kr_reduce_spectrum: null argument or negative n", [&] { return reduce_spectrum_dev(m, d, n, d_out, (hipStream_t) st); });
+}
+
+int kr_reduce_spectrum_f64(const kr_spectrum_model* m, const kr_ray_f64* rays, int64_t n, double* out)
+{
+    const int rc = spectrum_validate(m, "kr_reduce_spectrum");
+    if (rc != KR_OK) return rc;
+    if (!out || n < 0 || (n > 0 && !rays)) return invalid("kr_reduce_spectrum: null argument or negative n");
+    std::vector<double> h((size_t) m->ne + 4, 0.0);        // out is written only by a call that succeeds
+    const int rc2 = reduce_to_host(rays, n, h.size(), h.data(), [&](void* d, void* d_out) { return reduce_spectrum_dev(m, d, n, d_out, nullptr); });
+    if (rc2 == KR_OK) std::memcpy(out, h.data(), h.size() * sizeof(double));
+    return rc2;
+}
+
 // ---- polarisation of disc emission (kr_polarisation.hip; the Stokes line: kr_line.hip): everything is validated before anything touches a device ----
 int kr_polarisation_dev_f64(double spin, double V, int reverse, int projradius, int motion, double inc_deg, const void* d, int64_t n, void* d_out, void* st)
 {

@@ -1,4 +1,4 @@
-// kr_pass.hpp -- what the O(N) passes either side of the trace kernel share (kr_post.hip, kr_return_map.hip, kr_line.hip, kr_caustic.hip) and what kr_capi.hip calls
+// kr_pass.hpp -- what the O(N) passes either side of the trace kernel share (kr_post.hip, kr_return_map.hip, kr_line.hip, kr_spectrum.hip, kr_caustic.hip) and what kr_capi.hip calls
 // them through: the launch helpers, the per-record pieces that several kernels repeat, and the one declaration of every launcher.
 // The device helpers are plain forced-inline functions and one loop macro: each kernel compiles to the code it had with the lines written out.
 #pragma once
@@ -149,6 +149,13 @@ int post_line_dev(double spin, double V, int reverse, int projradius, int motion
 int line_from_image_dev(const kr_line_bins* b, const kr_image_bins* ib, const void* d_planes, void* d_line, hipStream_t st);
 int post_line_limb_dev(double spin, double V, int reverse, int projradius, double lo, double hi, const kr_line_bins* b, const kr_limb_law* law, void* d, int64_t n,
                        void* d_line, hipStream_t st);
+// kr_spectrum.hip: the continuum spectrum (kr_spectrum_model); the validators refuse what the struct's comment refuses, a bad limb law, and motion != 0
+// with a law other than 0
+int spectrum_validate(const kr_spectrum_model* m, const char* who);
+int spectrum_law_validate(const kr_limb_law* law, int motion, const char* who);
+int post_spectrum_dev(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_spectrum_model* m, const kr_limb_law* law, void* d,
+                      int64_t n, void* d_out, hipStream_t st);
+int reduce_spectrum_dev(const kr_spectrum_model* m, const void* d, int64_t n, void* d_out, hipStream_t st);
 // kr_angles.hip: the photon's angles in the disc frame (the observer of redshift_dev with motion 0; the validators refuse any other motion, a bad
 // limb law, and nr < 1 or nmu < 1)
 int angles_validate(int motion, const char* who);
