@@ -480,6 +480,51 @@ typedef struct kr_spectrum_model {
 static_assert(sizeof(kr_spectrum_model) == 168, "kr_spectrum_model is 168 bytes (raytrace_cpu_amd/capi.py SpectrumModel)");
 #endif
 
+/* An orbiting hot spot on the disc, seen on an image plane: the light curve, the flux-weighted image position and the energy-time spectrogram of a line
+ * emitted by the spot.  The spot is a PATTERN of enhanced emission on the disc surface, centred at radius r_spot, at azimuth phi0 at coordinate time 0,
+ * moving at the pattern speed Om.  The gas under it stays on its Keplerian orbits: g, mu and bad-angle are exactly what the redshift / limb passes give
+ * today.  It is not a rigid body with a four-velocity of its own, and the rule is good for sigma << r_spot only.
+ * Time and sense of rotation: an image plane is traced backwards by negating the spin, so a record's t grows into the past and its phi is the true
+ * azimuth.  A photon that reaches the observer at time T left the disc at T - rays[].t, when the spot stood at phi0 + Om (T - rays[].t).  With
+ * a' = reverse ? -spin : spin (the a' of the redshift pass, i.e. the true spin), Om > 0 is prograde for a' > 0.
+ * Per ray record, after redshift(V, reverse, projradius, motion) and range_phi(lo, hi):
+ *   filter   the one of kr_line_bins: steps > 0, r cos(theta) < 1e-2, r_isco <= r < r_disc, g > 0 with g = rays[].redshift (E_rest = g E_obs).  A ray that
+ *            passes counts in `on_disc`.
+ *   limb     limb(mu) of kr_limb_law, as in kr_spectrum_model: a bad-angle ray that passed the filter counts in `bad_angle`; with law != 0 it is dropped,
+ *            with law 0 it is used like every other ray.  The reduce forms are isotropic (law 0, no mu, bad_angle = 0).
+ *   ring     fabs(r - r_spot) < cut sigma, the product rounded once: a necessary condition for a non-zero contribution.  A ray that passes counts in
+ *            `used`.
+ *   Om       omega when shear == 0.  With shear == 1, Om = 1 / (a_orbit + r sqrt(r)): each radius moves at its own Keplerian rate and the spot winds
+ *            into an arc.  omega == 0 is a static pattern.
+ *   weight   c = limb pow(g, -g_index): g_index 4 gives the bolometric intensity, 3 the specific intensity of a line, as the line pass uses it.
+ *   energy   only with ne > 0: E = line_energy / g on the grid (e_min, de, log_e) with the index rule of kr_line_bins, ie = floor((E - e_min) / de) or
+ *            floor(log(E / e_min) / log(de)).  A NaN index or one outside [0, ne): the ray adds to no spectrogram cell, but still to the light curve.
+ *   samples  for every T_k = t0 + k dt, k = 0 .. nt - 1 (SAMPLED, not integrated over the step):
+ *              d2 = r r + r_spot r_spot - 2 r r_spot cos(phi - (phi0 + Om (T_k - t)))
+ *              s  = exp(-d2 / (2 sigma sigma)) - exp(-cut cut / 2)
+ *              if s > 0:  flux[k] += c s,  sx[k] += c s x,  sy[k] += c s y  (x = rays[].alpha, y = rays[].beta),  spec[k][ie] += c s
+ *            The Gaussian is SHIFTED: s is continuous and reaches 0 at d = cut sigma, so a last-bit difference in d2 moves a sum by a last-bit amount and
+ *            never adds or removes a whole term.  (The kernel multiplies d2 by -1 / (2 sigma sigma), rounded once.)
+ * Output: double[nt (3 + ne) + 4] = [flux (nt) | sx (nt) | sy (nt) | spec (nt x ne, time-major: [k ne + ie]) | on_disc | used | bad_angle | 0], ADDED
+ * into: shards, several planes, several spots and several calls sum.  The centroid sx / flux, sy / flux is the caller's to take.
+ * Refused (KR_EINVAL): a null spot; a non-finite parameter; nt < 1 or nt > 4096; ne < 0 or ne > 4096; nt ne > 2^20; sigma <= 0; cut <= 0; r_spot <= 0;
+ * with ne > 0: de <= 0, log_e with de <= 1 or e_min <= 0, line_energy <= 0; shear other than 0 or 1; with shear == 1, a_orbit + r_isco sqrt(r_isco) <= 0.
+ * The struct holds no host pointer: nothing goes through the table cache.  The pad words are reserved (Stokes light curves would select there). */
+typedef struct kr_hotspot {
+    double r_spot, sigma, cut;     /* centre radius, Gaussian width and the cut-off in units of sigma */
+    double phi0, omega;            /* azimuth at coordinate time 0; pattern speed (shear == 0) */
+    double a_orbit;                /* the spin of the Keplerian rate under shear == 1 */
+    double t0, dt;                 /* observer times T_k = t0 + k dt */
+    double g_index;                /* weight exponent: c = limb g^-g_index */
+    double line_energy;            /* rest-frame line energy of the spectrogram (ne > 0) */
+    double e_min, de;              /* energy bins of the spectrogram; log_e: de is the ratio between edges */
+    double r_isco, r_disc;         /* disc filter */
+    int32_t nt, ne, log_e, shear, pad[2];
+} kr_hotspot;
+#ifdef __cplusplus
+static_assert(sizeof(kr_hotspot) == 136, "kr_hotspot is 136 bytes (raytrace_cpu_amd/capi.py HotSpot)");
+#endif
+
 /* Critical-curve (caustic) maps of the disc on an image plane: src/caustic/caustic_discplane.cpp.  Per image-plane pixel (ix, iy), from the ray through
  * the pixel (bundle mode: member 0 of its 5-ray bundle, imageplane_bundles.h) after redshift(dest, reverse) (caustic_discplane.cpp:219-251):
  *   valid_hit   steps > 0, r_isco <= r < r_disc, redshift > 0 (:177-182)
@@ -1127,6 +1172,19 @@ int kr_post_spectrum_dev_f64(double spin, double V, int reverse, int projradius,
                              const kr_limb_law* law, void* d_rays, int64_t n, void* d_out, void* stream);
 int kr_reduce_spectrum_dev_f64(const kr_spectrum_model* m, const void* d_rays, int64_t n, void* d_out, void* stream);
 int kr_reduce_spectrum_f64(const kr_spectrum_model* m, const kr_ray_f64* rays, int64_t n, double* out);
+
+/* ---- orbiting hot spot on the disc (kr_hotspot above has the rule) ------------------------------------------------------------------------------
+ * Every entry point validates its arguments before it touches a device: KR_EINVAL (message in kr_last_error) for a null pointer, n < 0, whatever the
+ * spot's comment refuses, a limb law other than 0, 1, 2, and motion != 0 with a limb law other than 0.  n == 0 is KR_OK and adds nothing.  None of the
+ * _dev forms waits for the device or allocates.
+ * kr_post_hotspot_dev_f64: redshift(V, reverse, projradius, motion) + range_phi(lo, hi) + the spot in one pass; rays[] ends up exactly as after
+ * kr_post_line_dev_f64.  ADDS into d_out (nt (3 + ne) + 4 doubles; zero it first).
+ * kr_reduce_hotspot_dev_f64: records that already carry their redshift and wrapped phi; reads the records and never writes them; isotropic.
+ * kr_reduce_hotspot_f64: host records, out = nt (3 + ne) + 4 host doubles (overwritten). */
+int kr_post_hotspot_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_hotspot* h, const kr_limb_law* law,
+                            void* d_rays, int64_t n, void* d_out, void* stream);
+int kr_reduce_hotspot_dev_f64(const kr_hotspot* h, const void* d_rays, int64_t n, void* d_out, void* stream);
+int kr_reduce_hotspot_f64(const kr_hotspot* h, const kr_ray_f64* rays, int64_t n, double* out);
 
 /* ---- critical-curve maps (kr_caustic_map above): caustic_discplane.cpp on the device -------------------------------------------------------
  * Every entry point validates its arguments before it touches a device: KR_EINVAL (message in kr_last_error) when nx or ny < 1, eps_x or eps_y

@@ -1683,3 +1683,111 @@ def spectrum_text(res):
     their counts), then one row per energy: E flux.  Every field setw(20), the numbers scientific with precision 8 (host/include/text_output.h)."""
     head = "".join("%20s%20d\n" % (f"# {k.upper()}", res[k]) for k in ("on_disc", "used", "bad_angle"))
     return head + "".join(_path_field(float(e)) + _path_field(float(f)) + "\n" for e, f in zip(res["energy"], res["flux"]))
+
+
+# ---- orbiting hot spot on the disc (include/kr_trace.h, kr_hotspot) ----
+def keplerian_omega(r, spin):
+    """The angular velocity d phi / d t of a prograde circular equatorial orbit at r: 1 / (spin + r^1.5)."""
+    r = np.asarray(r, dtype=np.float64)
+    om = 1.0 / (spin + r * np.sqrt(r))
+    return float(om) if om.ndim == 0 else om
+
+
+def _hotspot_layout(h, words=None):
+    return _layout([("flux", (h.nt,)), ("sx", (h.nt,)), ("sy", (h.nt,)), ("spectrogram", (h.nt, h.ne))],
+                   [("on_disc", _rounded), ("used", _rounded), ("bad_angle", _rounded), (None, None)], words)
+
+
+def hotspot_words(h):
+    """Length of the buffer of kr_post_hotspot_dev_f64 / kr_reduce_hotspot_dev_f64: [flux | sx | sy (nt each) | spec (nt x ne) | on_disc | used | bad_angle | 0]."""
+    return _hotspot_layout(h)
+
+
+def hotspot_times(h):
+    """The nt observer times T_k = t0 + k dt at which the spot is sampled."""
+    return h.t0 + np.arange(h.nt) * h.dt
+
+
+def hotspot_energies(h):
+    """The centres of the ne energy bins of the spectrogram (geometric centres with log_e)."""
+    i = np.arange(h.ne) + 0.5
+    return h.e_min * np.float64(h.de) ** i if h.log_e else h.e_min + i * h.de
+
+
+def hotspot_from_words(h, words):
+    """The buffer of the hot-spot entry points as a dict: time (nt), flux, sx, sy, the centroids x = sx / flux and y = sy / flux (NaN where flux == 0),
+    spectrogram (nt x ne) with `energy` (ne), and the tallies on_disc, used, bad_angle.  With several spots added into one buffer the tallies count
+    every spot's pass."""
+    out = _hotspot_layout(h, words)
+    out["time"], out["energy"] = hotspot_times(h), hotspot_energies(h)
+    with np.errstate(all="ignore"):
+        lit = out["flux"] != 0
+        out["x"] = np.where(lit, out["sx"] / np.where(lit, out["flux"], 1.0), np.nan)
+        out["y"] = np.where(lit, out["sy"] / np.where(lit, out["flux"], 1.0), np.nan)
+    return out
+
+
+def reduce_hotspot(h, rays):
+    """kr_reduce_hotspot_f64: the isotropic light curve of one spot from host ray records that carry their redshift and wrapped phi."""
+    _rays_arg(rays, capi.RAY_F64)
+    out = np.zeros(hotspot_words(h))
+    capi.check(lib(), lib().kr_reduce_hotspot_f64(C.byref(h), _ptr(rays), len(rays), _ptr(out)), "kr_reduce_hotspot")
+    return hotspot_from_words(h, out)
+
+
+def hotspot_lightcurve(imageplane_spec, params, spots, limb=None, return_records=False):
+    """The light curve, centroid track and spectrogram of hot spots on the disc seen on an image plane, resident on the device from start to finish, as
+    the kr_hotspot_lightcurve app runs it: ImagePlane ctor + redshift_start -> trace (`params` as for the image app: the stored, negated spin) ->
+    redshift + range_phi + the first spot (kr_post_hotspot_dev_f64) -> every further spot on the records that pass left (kr_reduce_hotspot_dev_f64: those
+    are isotropic, so several spots need limb=None) into the same buffer.  spots: a capi.HotSpot or a list of them on the same observer times and energy
+    grid (anything else is refused; the line energies may differ); their outputs add.  Every spot is validated by the library before the plane is traced.
+    Only the words are read back (and, with return_records, the final records: for tests).  Returns hotspot_from_words(...) plus "stats".  The sums are
+    per image-plane pixel: multiply by dx dy / D^2 for a flux."""
+    spots = [spots] if isinstance(spots, capi.HotSpot) else list(spots)
+    if not spots:
+        raise KrError("hotspot_lightcurve: no spot")
+    h = spots[0]
+
+    def axes(s):
+        return (s.nt, s.t0, s.dt, s.ne) + ((s.log_e, s.e_min, s.de) if s.ne > 0 else ())
+    if any(axes(s) != axes(h) for s in spots):
+        raise KrError("hotspot_lightcurve: the spots must share the observer times (nt, t0, dt) and the energy grid (ne, log_e, e_min, de): they add into one buffer")
+    law = capi.limb_law(limb if limb is not None else "isotropic")
+    if len(spots) > 1 and law.law != 0:
+        raise KrError("hotspot_lightcurve: several spots need the isotropic law (the further spots go through the reduce form)")
+    L = lib()
+    n, _, _ = imageplane_count(imageplane_spec)
+    if n <= 0:
+        raise KrError("hotspot_lightcurve: empty ray grid")
+    st = Stats()
+    post = (-1 * imageplane_spec.spin, -1.0, 1, 0, 0, -np.pi, np.pi)
+    with DeviceScope(L) as dev:
+        # the library's own refusals, before anything is traced: n = 0 validates the spot and the law and adds nothing (the buffer is not touched)
+        d_probe = dev.zeros(8)
+        capi.check(L, L.kr_post_hotspot_dev_f64(*post, C.byref(h), C.byref(law), None, 0, d_probe, None), "kr_post_hotspot")
+        for s in spots[1:]:
+            capi.check(L, L.kr_reduce_hotspot_dev_f64(C.byref(s), None, 0, d_probe, None), "kr_reduce_hotspot")
+        nw = hotspot_words(h)
+        d_out = dev.zeros(nw * 8)
+        d_rays = dev.alloc(n * capi.RAY_F64.itemsize)
+        capi.check(L, L.kr_imageplane_init_emit_dev_f64(C.byref(imageplane_spec), 0, 1, 0.0, 1, 0, d_rays, n, None), "kr_imageplane_init_emit")
+        capi.check(L, L.kr_trace_dev_f64(C.byref(params), d_rays, n, None, C.byref(st)), "kr_trace_dev")
+        capi.check(L, L.kr_post_hotspot_dev_f64(*post, C.byref(h), C.byref(law), d_rays, n, d_out, None), "kr_post_hotspot")
+        for s in spots[1:]:
+            capi.check(L, L.kr_reduce_hotspot_dev_f64(C.byref(s), d_rays, n, d_out, None), "kr_reduce_hotspot")
+        res = hotspot_from_words(h, dev.fetch(d_out, nw))
+        res["stats"] = st.as_dict()
+        if return_records:
+            res["records"] = dev.fetch(d_rays, n, capi.RAY_F64)
+    return res
+
+
+def hotspot_text(res):
+    """The file kr_hotspot_lightcurve writes for a result of hotspot_lightcurve(): three comment rows with the tallies ("# ON_DISC", "# USED",
+    "# BAD_ANGLE"), one row per observer time: T flux x_c y_c, and, with a spectrogram, one block per observer time after a blank line each: a row
+    T E_mid value per energy bin.  Every field setw(20), the numbers scientific with precision 8 (host/include/text_output.h)."""
+    head = "".join("%20s%20d\n" % (f"# {k.upper()}", res[k]) for k in ("on_disc", "used", "bad_angle"))
+    rows = "".join("".join(_path_field(float(v)) for v in row) + "\n" for row in zip(res["time"], res["flux"], res["x"], res["y"]))
+    blocks = "".join("\n" + "".join(_path_field(float(t)) + _path_field(float(e)) + _path_field(float(v)) + "\n" for e, v in zip(res["energy"], row))
+                     for t, row in zip(res["time"], res["spectrogram"])) if len(res["energy"]) else ""
+    return head + rows + blocks

@@ -197,6 +197,29 @@ def spectrum_model(model, e_min, de, ne, log_e=False, r_isco=1.0, r_disc=1000.0,
     return m
 
 
+class HotSpot(C.Structure):
+    """kr_hotspot: a Gaussian pattern of enhanced emission that moves over the disc -- light curve, image position and spectrogram at nt observer times
+    (include/kr_trace.h has the per-ray rule).  A pattern on the disc, good for sigma << r_spot; not a body with a four-velocity of its own."""
+    _fields_ = [(n, C.c_double) for n in ("r_spot", "sigma", "cut", "phi0", "omega", "a_orbit", "t0", "dt", "g_index", "line_energy", "e_min", "de", "r_isco", "r_disc")] + \
+               [(n, C.c_int32) for n in ("nt", "ne", "log_e", "shear")] + [("pad", C.c_int32 * 2)]
+
+
+assert C.sizeof(HotSpot) == 136
+
+
+def hot_spot(r_spot, sigma, cut=3.0, phi0=0.0, omega=None, shear=0, spin=0.0, t0=0.0, dt=1.0, nt=64, g_index=4.0, line_energy=6.4, e_min=1.0, de=0.1, ne=0,
+             log_e=False, r_isco=1.0, r_disc=1000.0):
+    """A HotSpot.  omega=None: the Keplerian rate 1 / (spin + r_spot^1.5) at the spot's centre; shear=1: every radius at its own Keplerian rate for
+    `spin` (omega is then not used).  ne=0: no spectrogram."""
+    h = HotSpot()
+    h.r_spot, h.sigma, h.cut, h.phi0, h.a_orbit = r_spot, sigma, cut, phi0, spin
+    h.omega = 1.0 / (spin + r_spot * float(np.sqrt(r_spot))) if omega is None else omega
+    h.t0, h.dt, h.nt, h.g_index = t0, dt, nt, g_index
+    h.line_energy, h.e_min, h.de, h.ne, h.log_e = line_energy, e_min, de, ne, int(log_e)
+    h.r_isco, h.r_disc, h.shear = r_isco, r_disc, int(shear)
+    return h
+
+
 class CausticMap(C.Structure):
     """kr_caustic_map: what the critical-curve passes need besides the records (include/kr_trace.h has the per-pixel rules)."""
     _fields_ = [(n, C.c_double) for n in ("r_isco", "r_disc", "eps_x", "eps_y")] + [(n, C.c_int32) for n in ("nx", "ny", "bundles", "pad")]
@@ -401,6 +424,9 @@ PROTOTYPES = {
     "kr_post_spectrum_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, P(SpectrumModel), P(LimbLaw), _vp, _i64, _vp, _vp]),
     "kr_reduce_spectrum_dev_f64": (_int, [P(SpectrumModel), _vp, _i64, _vp, _vp]),
     "kr_reduce_spectrum_f64": (_int, [P(SpectrumModel), _vp, _i64, _vp]),
+    "kr_post_hotspot_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, P(HotSpot), P(LimbLaw), _vp, _i64, _vp, _vp]),
+    "kr_reduce_hotspot_dev_f64": (_int, [P(HotSpot), _vp, _i64, _vp, _vp]),
+    "kr_reduce_hotspot_f64": (_int, [P(HotSpot), _vp, _i64, _vp]),
     "kr_bundles_init_emit_dev_f64": (_int, [P(ImagePlaneSpec), _dbl, _dbl, _int, _int, _vp, _i64, _vp]),
     "kr_post_caustic_disc_dev_f64": (_int, [_dbl, _int, P(CausticMap), _vp, _i64, _vp, _vp]),
     "kr_caustic_suppress_dev_f64": (_int, [P(CausticMap), _vp, _vp]),

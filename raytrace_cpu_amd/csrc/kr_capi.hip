@@ -1191,6 +1191,35 @@ int kr_reduce_spectrum_f64(const kr_spectrum_model* m, const kr_ray_f64* rays, i
     return rc2;
 }
 
+// ---- orbiting hot spot (kr_hotspot.hip): everything is validated before anything touches a device ----
+int kr_post_hotspot_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_hotspot* h, const kr_limb_law* law, void* d,
+                            int64_t n, void* d_out, void* st)
+{
+    int rc = hotspot_validate(h, "kr_post_hotspot");
+    if (rc == KR_OK) rc = spectrum_law_validate(law, motion, "kr_post_hotspot");
+    if (rc != KR_OK) return rc;
+    return on_device(n >= 0 && d_out && (n == 0 || d), "kr_post_hotspot: null argument or negative n",
+                     [&] { return post_hotspot_dev(spin, V, reverse, projradius, motion, lo, hi, h, law, d, n, d_out, (hipStream_t) st); });
+}
+
+int kr_reduce_hotspot_dev_f64(const kr_hotspot* h, const void* d, int64_t n, void* d_out, void* st)
+{
+    const int rc = hotspot_validate(h, "kr_reduce_hotspot");
+    if (rc != KR_OK) return rc;
+    return on_device(n >= 0 && d_out && (n == 0 || d), "kr_reduce_hotspot: null argument or negative n", [&] { return reduce_hotspot_dev(h, d, n, d_out, (hipStream_t) st); });
+}
+
+int kr_reduce_hotspot_f64(const kr_hotspot* h, const kr_ray_f64* rays, int64_t n, double* out)
+{
+    const int rc = hotspot_validate(h, "kr_reduce_hotspot");
+    if (rc != KR_OK) return rc;
+    if (!out || n < 0 || (n > 0 && !rays)) return invalid("kr_reduce_hotspot: null argument or negative n");
+    std::vector<double> w((size_t) h->nt * (3 + (size_t) h->ne) + 4, 0.0);        // out is written only by a call that succeeds
+    const int rc2 = reduce_to_host(rays, n, w.size(), w.data(), [&](void* d, void* d_out) { return reduce_hotspot_dev(h, d, n, d_out, nullptr); });
+    if (rc2 == KR_OK) std::memcpy(out, w.data(), w.size() * sizeof(double));
+    return rc2;
+}
+
 // ---- polarisation of disc emission (kr_polarisation.hip; the Stokes line: kr_line.hip): everything is validated before anything touches a device ----
 int kr_polarisation_dev_f64(double spin, double V, int reverse, int projradius, int motion, double inc_deg, const void* d, int64_t n, void* d_out, void* st)
 {

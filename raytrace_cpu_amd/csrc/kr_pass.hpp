@@ -156,6 +156,11 @@ int spectrum_law_validate(const kr_limb_law* law, int motion, const char* who);
 int post_spectrum_dev(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_spectrum_model* m, const kr_limb_law* law, void* d,
                       int64_t n, void* d_out, hipStream_t st);
 int reduce_spectrum_dev(const kr_spectrum_model* m, const void* d, int64_t n, void* d_out, hipStream_t st);
+// kr_hotspot.hip: the orbiting hot spot (kr_hotspot); the validator refuses what the struct's comment refuses (the limb law: spectrum_law_validate)
+int hotspot_validate(const kr_hotspot* h, const char* who);
+int post_hotspot_dev(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_hotspot* h, const kr_limb_law* law, void* d, int64_t n,
+                     void* d_out, hipStream_t st);
+int reduce_hotspot_dev(const kr_hotspot* h, const void* d, int64_t n, void* d_out, hipStream_t st);
 // kr_angles.hip: the photon's angles in the disc frame (the observer of redshift_dev with motion 0; the validators refuse any other motion, a bad
 // limb law, and nr < 1 or nmu < 1)
 int angles_validate(int motion, const char* who);
