@@ -716,19 +716,22 @@ def stokes_line_from_words(bins, words):
     return out
 
 
-def _stokes_run(what, imageplane_spec, params, nw, post, return_records=False):
-    """ImagePlane ctor + redshift_start -> trace -> post(L, d_rays, n, d_out, spin as the Raytracer stored it): (the nw words, stats, records or None)."""
+def _imageplane_run(what, imageplane_spec, params, nw, post, return_records=False, before=None):
+    """ImagePlane ctor + redshift_start -> trace -> post(L, dev, d_rays, n, d_out), one pass or several into the nw zeroed words of d_out (nw == 0: a
+    null buffer, for sizes the pass refuses): (the words, stats, records or None).  before(L, dev) runs inside the scope before anything is traced."""
     L = lib()
     n, _, _ = imageplane_count(imageplane_spec)
     if n <= 0:
         raise KrError(f"{what}: empty ray grid")
     st = Stats()
     with DeviceScope(L) as dev:
+        if before is not None:
+            before(L, dev)
         d_out = dev.zeros(nw * 8) if nw > 0 else C.c_void_p()
         d_rays = dev.alloc(n * capi.RAY_F64.itemsize)
         capi.check(L, L.kr_imageplane_init_emit_dev_f64(C.byref(imageplane_spec), 0, 1, 0.0, 1, 0, d_rays, n, None), "kr_imageplane_init_emit")
         capi.check(L, L.kr_trace_dev_f64(C.byref(params), d_rays, n, None, C.byref(st)), "kr_trace_dev")
-        post(L, d_rays, n, d_out, -1 * imageplane_spec.spin)                 # (imageplane.cpp:12)
+        post(L, dev, d_rays, n, d_out)
         capi.check(L, L.kr_synchronize(None), "kr_synchronize")
         return dev.fetch(d_out, nw), st.as_dict(), dev.fetch(d_rays, n, capi.RAY_F64) if return_records else None
 
@@ -741,8 +744,8 @@ def stokes_image(imageplane_spec, params, image_bins, pol, limb=None, return_rec
     Returns stokes_image_from_words(...) plus "stats" (the trace's kr_stats)."""
     law, plaw = capi.limb_law(limb if limb is not None else "isotropic"), capi.pol_law(pol)
     sized = image_bins.img_nx > 0 and image_bins.img_ny > 0          # (the pass refuses the rest: it gets a null buffer)
-    words, stats, records = _stokes_run("stokes_image", imageplane_spec, params, stokes_image_words(image_bins) if sized else 0, lambda L, d_rays, n, d_out, spin: capi.check(
-        L, L.kr_post_image_stokes_dev_f64(spin, -1.0, 1, 0, 0, -np.pi, np.pi, imageplane_spec.inc_deg, C.byref(image_bins), C.byref(law), C.byref(plaw), d_rays, n, d_out,
+    words, stats, records = _imageplane_run("stokes_image", imageplane_spec, params, stokes_image_words(image_bins) if sized else 0, lambda L, dev, d_rays, n, d_out: capi.check(
+        L, L.kr_post_image_stokes_dev_f64(-1 * imageplane_spec.spin, -1.0, 1, 0, 0, -np.pi, np.pi, imageplane_spec.inc_deg, C.byref(image_bins), C.byref(law), C.byref(plaw), d_rays, n, d_out,
                                           None), "kr_post_image_stokes"), return_records)
     res = stokes_image_from_words(image_bins, words)
     res["stats"] = stats
@@ -755,8 +758,8 @@ def stokes_line(imageplane_spec, params, line_bins, pol, limb=None):
     """The energy-resolved (and, with a time axis, time-resolved) Stokes parameters of the disc's line emission: stokes_image's pipeline with
     kr_post_line_stokes_dev_f64 as its last pass.  Returns stokes_line_from_words(...) plus "stats"."""
     law, plaw = capi.limb_law(limb if limb is not None else "isotropic"), capi.pol_law(pol)
-    words, stats, _ = _stokes_run("stokes_line", imageplane_spec, params, stokes_line_words(line_bins), lambda L, d_rays, n, d_out, spin: capi.check(
-        L, L.kr_post_line_stokes_dev_f64(spin, -1.0, 1, 0, 0, -np.pi, np.pi, imageplane_spec.inc_deg, C.byref(line_bins), C.byref(law), C.byref(plaw), d_rays, n, d_out,
+    words, stats, _ = _imageplane_run("stokes_line", imageplane_spec, params, stokes_line_words(line_bins), lambda L, dev, d_rays, n, d_out: capi.check(
+        L, L.kr_post_line_stokes_dev_f64(-1 * imageplane_spec.spin, -1.0, 1, 0, 0, -np.pi, np.pi, imageplane_spec.inc_deg, C.byref(line_bins), C.byref(law), C.byref(plaw), d_rays, n, d_out,
                                          None), "kr_post_line_stokes"))
     res = stokes_line_from_words(line_bins, words)
     res["stats"] = stats
@@ -1657,24 +1660,14 @@ def disc_spectrum(imageplane_spec, params, model, limb=None, return_records=Fals
     line_profile.  Only the ne + 4 words are read back (and, with return_records, the final records: for tests).  Returns spectrum_from_words(...)
     plus "stats" (the trace's kr_stats).  The flux is per image-plane pixel: multiply by dx dy / D^2 for a flux density."""
     law = capi.limb_law(limb if limb is not None else "isotropic")
-    L = lib()
-    n, _, _ = imageplane_count(imageplane_spec)
-    if n <= 0:
-        raise KrError("disc_spectrum: empty ray grid")
     sized = 1 <= model.ne <= 4096                      # (the pass refuses the rest: it gets a null buffer)
-    nw = spectrum_words(model) if sized else 0
-    st = Stats()
-    with DeviceScope(L) as dev:
-        d_out = dev.zeros(nw * 8) if sized else C.c_void_p()
-        d_rays = dev.alloc(n * capi.RAY_F64.itemsize)
-        capi.check(L, L.kr_imageplane_init_emit_dev_f64(C.byref(imageplane_spec), 0, 1, 0.0, 1, 0, d_rays, n, None), "kr_imageplane_init_emit")
-        capi.check(L, L.kr_trace_dev_f64(C.byref(params), d_rays, n, None, C.byref(st)), "kr_trace_dev")
-        capi.check(L, L.kr_post_spectrum_dev_f64(-1 * imageplane_spec.spin, -1.0, 1, 0, 0, -np.pi, np.pi, C.byref(model), C.byref(law), d_rays, n, d_out, None),
-                   "kr_post_spectrum")
-        res = spectrum_from_words(model, dev.fetch(d_out, nw))
-        res["stats"] = st.as_dict()
-        if return_records:
-            res["records"] = dev.fetch(d_rays, n, capi.RAY_F64)
+    words, stats, records = _imageplane_run("disc_spectrum", imageplane_spec, params, spectrum_words(model) if sized else 0, lambda L, dev, d_rays, n, d_out: capi.check(
+        L, L.kr_post_spectrum_dev_f64(-1 * imageplane_spec.spin, -1.0, 1, 0, 0, -np.pi, np.pi, C.byref(model), C.byref(law), d_rays, n, d_out, None), "kr_post_spectrum"),
+        return_records)
+    res = spectrum_from_words(model, words)
+    res["stats"] = stats
+    if return_records:
+        res["records"] = records
     return res
 
 
@@ -1755,30 +1748,18 @@ def hotspot_lightcurve(imageplane_spec, params, spots, limb=None, return_records
     law = capi.limb_law(limb if limb is not None else "isotropic")
     if len(spots) > 1 and law.law != 0:
         raise KrError("hotspot_lightcurve: several spots need the isotropic law (the further spots go through the reduce form)")
-    L = lib()
-    n, _, _ = imageplane_count(imageplane_spec)
-    if n <= 0:
-        raise KrError("hotspot_lightcurve: empty ray grid")
-    st = Stats()
-    post = (-1 * imageplane_spec.spin, -1.0, 1, 0, 0, -np.pi, np.pi)
-    with DeviceScope(L) as dev:
-        # the library's own refusals, before anything is traced: n = 0 validates the spot and the law and adds nothing (the buffer is not touched)
-        d_probe = dev.zeros(8)
-        capi.check(L, L.kr_post_hotspot_dev_f64(*post, C.byref(h), C.byref(law), None, 0, d_probe, None), "kr_post_hotspot")
-        for s in spots[1:]:
-            capi.check(L, L.kr_reduce_hotspot_dev_f64(C.byref(s), None, 0, d_probe, None), "kr_reduce_hotspot")
-        nw = hotspot_words(h)
-        d_out = dev.zeros(nw * 8)
-        d_rays = dev.alloc(n * capi.RAY_F64.itemsize)
-        capi.check(L, L.kr_imageplane_init_emit_dev_f64(C.byref(imageplane_spec), 0, 1, 0.0, 1, 0, d_rays, n, None), "kr_imageplane_init_emit")
-        capi.check(L, L.kr_trace_dev_f64(C.byref(params), d_rays, n, None, C.byref(st)), "kr_trace_dev")
-        capi.check(L, L.kr_post_hotspot_dev_f64(*post, C.byref(h), C.byref(law), d_rays, n, d_out, None), "kr_post_hotspot")
+    def passes(L, dev, d_rays, n, d_out):
+        capi.check(L, L.kr_post_hotspot_dev_f64(-1 * imageplane_spec.spin, -1.0, 1, 0, 0, -np.pi, np.pi, C.byref(h), C.byref(law), d_rays, n, d_out, None), "kr_post_hotspot")
         for s in spots[1:]:
             capi.check(L, L.kr_reduce_hotspot_dev_f64(C.byref(s), d_rays, n, d_out, None), "kr_reduce_hotspot")
-        res = hotspot_from_words(h, dev.fetch(d_out, nw))
-        res["stats"] = st.as_dict()
-        if return_records:
-            res["records"] = dev.fetch(d_rays, n, capi.RAY_F64)
+
+    # the library's own refusals, before anything is traced: n = 0 validates the spots and the law and adds nothing (the buffer is not touched)
+    words, stats, records = _imageplane_run("hotspot_lightcurve", imageplane_spec, params, hotspot_words(h), passes, return_records,
+                                            before=lambda L, dev: passes(L, dev, None, 0, dev.zeros(8)))
+    res = hotspot_from_words(h, words)
+    res["stats"] = stats
+    if return_records:
+        res["records"] = records
     return res
 
 

@@ -2,8 +2,8 @@
 // image position and the energy-time spectrogram of a Gaussian pattern of enhanced emission that moves over the disc.  A ray near the spot's annulus adds
 // to EVERY observer time, n_ring x nt evaluations of a cosine and an exponential, so the kernel has the two phases of kr_spectrum.hip, per tile of kBlock
 // records:
-//   phase A  one RECORD per lane: the per-ray code of post_line_limb_kernel (redshift, range_phi, filter, mu, limb law) and the ring test; a ray that
-//            survives leaves one compact item in LDS, placed by a ballot and a prefix count.  The item carries what does not depend on the time sample:
+//   phase A  one RECORD per lane: the steps of disc_ray (kr_disc_pass.hpp: redshift, range_phi, filter, mu, limb law) and the ring test; a ray that
+//            survives leaves one compact item in LDS, placed as tile_compact places it.  The item carries what does not depend on the time sample:
 //            head {psi, om, half}   the folded angle (phi - phi0 + Om t) / 2 pi, Om / 2 pi and the spot's half-width in turns as seen from this radius,
 //                                   widened by a margin: |frac(psi - om T)| > half means s <= 0 for certain (the sparsity test)
 //            body {A, B, phi, t, Om, c, cx, cy, ie}   A = r r + r_s r_s, B = 2 r r_s, the weight c = limb g^-g_index, its moments, the energy bin
@@ -25,7 +25,7 @@
 #include <cstring>
 #include <type_traits>
 
-#include "kr_pass.hpp"
+#include "kr_disc_pass.hpp"
 
 namespace kr {
 
@@ -54,7 +54,6 @@ constexpr int kSparseMinSlots = KR_HOTSPOT_SPARSE_MIN_SLOTS;
 #else
 constexpr int kSparseMinSlots = 2;
 #endif
-constexpr int kMaxSlots = 16;                    // nt <= kMaxSlots kBlock = 4096
 #ifdef KR_HOTSPOT_TWO_WAVE_SLOTS                 // A/B builds only
 constexpr int kTwoWaveSlots = KR_HOTSPOT_TWO_WAVE_SLOTS;
 #else
@@ -81,14 +80,6 @@ struct HotDev {
     int nes;                   // the row stride of the spectrogram block in LDS: ne | 1
 };
 
-// the disc filter of the line (kr_line.hip, line_filter)
-KR_DEV bool hotspot_filter(const kr_hotspot& h, int steps, double r, double theta, double g)
-{
-    if (!(steps > 0)) return false;
-    const double z = r * kr_cos(theta);
-    return z < 1E-2 && r >= h.r_isco && r < h.r_disc && g > 0;
-}
-
 struct HotItem {
     double psi, om, half, A, B, phi, t, Om, c, cx, cy;
     int ie;
@@ -109,7 +100,7 @@ KR_DEV bool hotspot_item(const HotDev& D, double r, double phi, double t, double
     it->ie = -1;
     if (h.ne > 0) {
         const double E = h.line_energy / g;
-        const double fe = h.log_e ? kr_log(E / h.e_min) / D.log_de : (E - h.e_min) / h.de;
+        const double fe = energy_bin_coord(h.log_e, h.e_min, h.de, D.log_de, E);
         if (fe >= 0 && fe < h.ne) it->ie = (int) fe;          // NaN fails too
     }
     it->psi = it->om = 0;
@@ -163,6 +154,8 @@ hotspot_kernel(typename std::conditional<FUSED, kr_ray_f64, const kr_ray_f64>::t
         const long long i = base + tid;
         bool live = false;
         HotItem it;
+        // disc_ray and tile_compact (kr_disc_pass.hpp), written out: through the calls the fused two- and four-slot forms, which spill across phase A,
+        // and the one-slot reduce forms run 1 ... 3 % slower (profiles/disc_pass_shared_ab.txt)
         if (i < n) {
             auto* ray = &rays[i];
             double r, theta, g, phi, limb = 1;
@@ -176,7 +169,7 @@ hotspot_kernel(typename std::conditional<FUSED, kr_ray_f64, const kr_ray_f64>::t
                     g = frame_redshift(f, v.emit, reverse);
                     ray->redshift = g;
                     phi = wrap_phi(ray, steps, lo, hi);
-                    if (hotspot_filter(h, steps, r, theta, g)) {
+                    if (disc_filter(h.r_isco, h.r_disc, steps, r, theta, g)) {
                         on_disc++;
                         const double mu = frame_mu(f);
                         if (frame_bad_angle(f, mu)) {
@@ -191,12 +184,12 @@ hotspot_kernel(typename std::conditional<FUSED, kr_ray_f64, const kr_ray_f64>::t
                     g = redshift_value(v, spin, V, reverse, projradius, motion);
                     ray->redshift = g;
                     phi = wrap_phi(ray, steps, lo, hi);
-                    if (hotspot_filter(h, steps, r, theta, g)) on_disc++;
+                    if (disc_filter(h.r_isco, h.r_disc, steps, r, theta, g)) on_disc++;
                     else drop = true;
                 }
             } else {
                 r = ray->r; theta = ray->theta; g = ray->redshift; phi = ray->phi;
-                if (hotspot_filter(h, steps, r, theta, g)) on_disc++;
+                if (disc_filter(h.r_isco, h.r_disc, steps, r, theta, g)) on_disc++;
                 else drop = true;
             }
             if (!drop) live = hotspot_item<SPARSE>(D, r, phi, ray->t, g, limb, ray->alpha, ray->beta, &it);
@@ -248,7 +241,7 @@ hotspot_kernel(typename std::conditional<FUSED, kr_ray_f64, const kr_ray_f64>::t
                 }
             }
         }
-        // (no barrier here: a wave that runs ahead writes wave_count, which every wave has read before the barrier above, and it_*[] only after the next one)
+        // (no barrier here: tile_compact has the argument)
     }
 
     // ---- the flush: one global atomic per non-zero sum, the spectrogram block, and the tallies
@@ -294,17 +287,6 @@ HotDev hotspot_dev(const kr_hotspot* h)
     return D;
 }
 
-template <bool FUSED, int SLOTS, typename Rays>
-void launch_one(int spec, int grid, size_t lds, hipStream_t st, Rays* d, long long n, double spin, double V, int reverse, int projradius, int motion, double lo,
-                double hi, const HotDev& D, const kr_limb_law& law, double* out)
-{
-#define KR_HOT_SPEC(S) hipLaunchKernelGGL((hotspot_kernel<FUSED, SLOTS, S>), dim3(grid), dim3(kBlock), lds, st, d, n, spin, V, reverse, projradius, motion, lo, hi, D, law, out)
-    if (spec == 0) KR_HOT_SPEC(0);
-    else if (spec == 1) KR_HOT_SPEC(1);
-    else KR_HOT_SPEC(2);
-#undef KR_HOT_SPEC
-}
-
 template <bool FUSED, typename Rays>
 int hotspot_launch(const kr_hotspot* h, const kr_limb_law& law, Rays* d, int64_t n, double spin, double V, int reverse, int projradius, int motion, double lo, double hi,
                    void* d_out, hipStream_t st)
@@ -315,13 +297,14 @@ int hotspot_launch(const kr_hotspot* h, const kr_limb_law& law, Rays* d, int64_t
     const int64_t block_words = (int64_t) h->nt * D.nes;
     const int spec = h->ne == 0 ? 0 : block_words <= kSpecBudget ? 1 : 2;
     const size_t lds = spec == 1 ? (size_t) block_words * sizeof(double) : 0;
-#define KR_HOT_SLOTS(K) launch_one<FUSED, K>(spec, grid, lds, st, d, (long long) n, spin, V, reverse, projradius, motion, lo, hi, D, law, (double*) d_out)
-    if (slots <= 1) KR_HOT_SLOTS(1);
-    else if (slots <= 2) KR_HOT_SLOTS(2);
-    else if (slots <= 4) KR_HOT_SLOTS(4);
-    else if (slots <= 8) KR_HOT_SLOTS(8);
-    else KR_HOT_SLOTS(kMaxSlots);
-#undef KR_HOT_SLOTS
+    for_slots(slots, [&](auto K) {
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, st, d, (long long) n, spin, V, reverse, projradius, motion, lo, hi, D, law, (double*) d_out);
+        };
+        if (spec == 0) launch(hotspot_kernel<FUSED, K.value, 0>);
+        else if (spec == 1) launch(hotspot_kernel<FUSED, K.value, 1>);
+        else launch(hotspot_kernel<FUSED, K.value, 2>);
+    });
     KR_LAUNCH_CHECK();
     return KR_OK;
 }
@@ -342,9 +325,7 @@ int hotspot_validate(const kr_hotspot* h, const char* who)
     if (!(h->cut > 0)) return bad("cut must be positive");
     if (!(h->r_spot > 0)) return bad("r_spot must be positive");
     if (h->ne > 0) {
-        if (!(h->de > 0)) return bad("de must be positive");
-        if (h->log_e && !(h->de > 1)) return bad("log_e: de (the ratio between edges) must be > 1");
-        if (h->log_e && !(h->e_min > 0)) return bad("log_e: e_min must be positive");
+        if (const int rc = energy_axis_validate(bad, h->de, h->log_e, h->e_min)) return rc;
         if (!(h->line_energy > 0)) return bad("line_energy must be positive");
     }
     if (h->shear != 0 && h->shear != 1) return bad("shear must be 0 or 1");
@@ -360,9 +341,7 @@ int post_hotspot_dev(double spin, double V, int reverse, int projradius, int mot
 
 int reduce_hotspot_dev(const kr_hotspot* h, const void* d, int64_t n, void* d_out, hipStream_t st)
 {
-    kr_limb_law iso;
-    iso.coeff = 0; iso.law = 0; iso.pad = 0;
-    return hotspot_launch<false>(h, iso, (const kr_ray_f64*) d, n, 0.0, 0.0, 0, 0, 0, 0.0, 0.0, d_out, st);
+    return hotspot_launch<false>(h, isotropic_limb(), (const kr_ray_f64*) d, n, 0.0, 0.0, 0, 0, 0, 0.0, 0.0, d_out, st);
 }
 
 }  // namespace kr

@@ -17,7 +17,7 @@
 #include <cstring>
 #include <string>
 
-#include "kr_pass.hpp"
+#include "kr_disc_pass.hpp"
 
 namespace kr {
 
@@ -48,10 +48,8 @@ KR_DEV bool line_item(const LineDev& L, double r, double x, double t, double lim
     const kr_line_bins& b = L.b;
     double emis, tt = 0;
     if (L.t_emis) {
-        // the emissivity app's index (emissivity.cpp:106): truncation, so (-1, table_nr) is the range that lands in [0, table_nr)
-        const double fi = b.table_logbin ? kr_log(r / b.table_r_min) / L.log_tdr : (r - b.table_r_min) / b.table_dr;
-        if (!(fi > -1 && fi < b.table_nr)) return false;
-        const int ir = (int) fi;
+        int ir;
+        if (!radial_table_index(b.table_logbin, b.table_r_min, b.table_dr, L.log_tdr, b.table_nr, r, &ir)) return false;
         emis = L.t_emis[ir];
         if (!__builtin_isfinite(emis)) return false;
         if (L.t_time) tt = L.t_time[ir];
@@ -61,7 +59,7 @@ KR_DEV bool line_item(const LineDev& L, double r, double x, double t, double lim
     const double E = PIXEL ? b.line_energy * x : b.line_energy / x;
     const double w0 = emis * (PIXEL ? kr_pow(x, b.g_index) : kr_pow(x, -1 * b.g_index));
     *w = LIMB ? w0 * limb : w0;
-    const double fe = b.log_e ? kr_log(E / b.e_min) / L.log_de : (E - b.e_min) / b.de;
+    const double fe = energy_bin_coord(b.log_e, b.e_min, b.de, L.log_de, E);
     if (!(fe >= 0 && fe < b.ne)) return false;          // NaN fails too
     int j = 0;
     if (L.time_axis) {
@@ -83,14 +81,6 @@ KR_DEV unsigned line_accumulate(double* acc, const LineDev& L, double r, double 
     atomicAdd(&acc[k], 1.0);
     atomicAdd(&acc[L.b.nt * L.b.ne + k], w);
     return 1;
-}
-
-// the disc filter of imageplane_disc_image.cpp:127-128 without the pixel-range test
-KR_DEV bool line_filter(const kr_line_bins& b, int steps, double r, double theta, double g)
-{
-    if (!(steps > 0)) return false;
-    const double z = r * kr_cos(theta);
-    return z < 1E-2 && r >= b.r_isco && r < b.r_disc && g > 0;
 }
 
 template <bool USE_LDS>
@@ -128,7 +118,7 @@ reduce_line_kernel(const kr_ray_f64* __restrict__ rays, long long n, LineDev L, 
     KR_GRID_STRIDE(i, n) {
         const kr_ray_f64* ray = &rays[i];
         const double r = ray->r, g = ray->redshift;
-        if (!line_filter(L.b, ray->steps, r, ray->theta, g)) continue;
+        if (!disc_filter(L.b.r_isco, L.b.r_disc, ray->steps, r, ray->theta, g)) continue;
         on_disc++;
         binned += line_accumulate<false>(acc, L, r, g, ray->t);
     }
@@ -152,16 +142,15 @@ post_line_kernel(kr_ray_f64* __restrict__ rays, long long n, double spin, double
         const double g = redshift_value(v, spin, V, reverse, projradius, motion);
         ray->redshift = g;
         wrap_phi(ray, steps, lo, hi);
-        if (!line_filter(L.b, steps, v.r, v.theta, g)) continue;
+        if (!disc_filter(L.b.r_isco, L.b.r_disc, steps, v.r, v.theta, g)) continue;
         on_disc++;
         binned += line_accumulate<false>(acc, L, v.r, g, ray->t);
     }
     line_end<USE_LDS>(lds, out, L.words, on_disc, binned);
 }
 
-// post_line_kernel with w *= limb(mu): g and mu come from ONE metric and momentum evaluation (frame_value; its E is redshift_value's recv to the
-// bit, so rays[] ends as after post_line_kernel).  A bad-angle ray that passed the filter counts in on_disc and bad_angle; under law 0 it is binned
-// like every other ray, under the other laws -- whose weight it would poison -- it is not.  Layout: post_line_kernel's, then bad_angle.
+// post_line_kernel with w *= limb(mu): disc_ray (kr_disc_pass.hpp) in its fused form for the orbiting observer, so rays[] ends as after
+// post_line_kernel and a bad-angle ray is counted and binned by that function's rule.  Layout: post_line_kernel's, then bad_angle.
 template <bool USE_LDS>
 __global__ void __launch_bounds__(kBlock)
 post_line_limb_kernel(kr_ray_f64* __restrict__ rays, long long n, double spin, double V, int reverse, int projradius, double lo, double hi, LineDev L,
@@ -173,20 +162,9 @@ post_line_limb_kernel(kr_ray_f64* __restrict__ rays, long long n, double spin, d
     unsigned long long on_disc = 0, binned = 0, bad_angle = 0;
     KR_GRID_STRIDE(i, n) {
         kr_ray_f64* ray = &rays[i];
-        const kr_ray_f64 v = geodesic_of(ray);
-        const int steps = ray->steps;
-        const Frame f = frame_value(v, spin, V, reverse, projradius);
-        const double g = frame_redshift(f, v.emit, reverse);
-        ray->redshift = g;
-        wrap_phi(ray, steps, lo, hi);
-        if (!line_filter(L.b, steps, v.r, v.theta, g)) continue;
-        on_disc++;
-        const double mu = frame_mu(f);
-        if (frame_bad_angle(f, mu)) {
-            bad_angle++;
-            if (law.law != 0) continue;
-        }
-        binned += line_accumulate<false, true>(acc, L, v.r, g, ray->t, limb_weight(law.law, law.coeff, mu));
+        DiscRay d;
+        if (!disc_ray<true>(ray, L.b.r_isco, L.b.r_disc, spin, V, reverse, projradius, 0, lo, hi, law, &d, on_disc, bad_angle)) continue;
+        binned += line_accumulate<false, true>(acc, L, d.r, d.g, ray->t, d.limb);
     }
     line_end<USE_LDS, true>(lds, out, words, on_disc, binned, bad_angle);
 }
@@ -212,7 +190,7 @@ post_line_stokes_kernel(kr_ray_f64* __restrict__ rays, long long n, double spin,
         const double g = q.redshift;
         ray->redshift = g;
         wrap_phi(ray, steps, lo, hi);
-        if (!line_filter(L.b, steps, v.r, v.theta, g)) continue;
+        if (!disc_filter(L.b.r_isco, L.b.r_disc, steps, v.r, v.theta, g)) continue;
         on_disc++;
         if (q.bad) { bad_pol++; continue; }
         int k;
@@ -281,9 +259,7 @@ int line_validate(const kr_line_bins* b, const char* who)
         if (!std::isfinite(v)) return bad("non-finite bin parameter");
     if (b->ne < 1 || b->nt < 1) return bad("ne and nt must be >= 1");
     if ((int64_t) b->ne * b->nt > ((int64_t) 1 << 24)) return bad("ne * nt must not exceed 2^24");
-    if (!(b->de > 0)) return bad("de must be positive");
-    if (b->log_e && !(b->de > 1)) return bad("log_e: de (the ratio between edges) must be > 1");
-    if (b->log_e && !(b->e_min > 0)) return bad("log_e: e_min must be positive");
+    if (const int rc = energy_axis_validate(bad, b->de, b->log_e, b->e_min)) return rc;
     if (b->nt > 1 && !(b->dt > 0)) return bad("nt > 1 needs dt > 0");
     if (b->table_time && !b->table_emis) return bad("table_time given without table_emis");
     if (b->table_emis) {

@@ -1,5 +1,6 @@
 // kr_pass.hpp -- what the O(N) passes either side of the trace kernel share (kr_post.hip, kr_return_map.hip, kr_line.hip, kr_spectrum.hip, kr_caustic.hip) and what kr_capi.hip calls
 // them through: the launch helpers, the per-record pieces that several kernels repeat, and the one declaration of every launcher.
+// kr_disc_pass.hpp (which includes this file) adds what the disc passes share among themselves: the disc filter, the per-ray front end, the tile compactor.
 // The device helpers are plain forced-inline functions and one loop macro: each kernel compiles to the code it had with the lines written out.
 #pragma once
 

@@ -40,7 +40,7 @@ KR_DEV long long stokes_pixel(const kr_image_bins& b, int steps, double r, doubl
 {
     if (!(steps > 0)) return -1;
     const double z = r * kr_cos(theta);
-    if (!(z < 1E-2 && r >= b.r_isco && r < b.r_disc && g > 0)) return -1;
+    if (!(z < 1E-2 && r >= b.r_isco && r < b.r_disc && g > 0)) return -1;         // disc_filter (kr_disc_pass.hpp), written out: the call changes this kernel's code
     const double qx = (alpha - b.x0) / b.img_dx, qy = (beta - b.y0) / b.img_dy;
     if (!(qx > -1 && qx < b.img_nx && qy > -1 && qy < b.img_ny)) return -1;
     const int ix = (int) qx;

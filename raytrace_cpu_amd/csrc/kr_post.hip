@@ -256,7 +256,7 @@ KR_DEV unsigned image_accumulate(double* planes, long long npix, const kr_image_
 {
     if (!(steps > 0)) return 0;
     const double z = r * kr_cos(theta);
-    if (!(z < 1E-2 && r >= b.r_isco && r < b.r_disc && g > 0)) return 0;
+    if (!(z < 1E-2 && r >= b.r_isco && r < b.r_disc && g > 0)) return 0;          // disc_filter (kr_disc_pass.hpp), written out: the call changes this kernel's code
     // the index rule of kr_image_bins per axis, on the floating quotient before the conversion (see emissivity_accumulate): NaN fails too
     const double qx = (alpha - b.x0) / b.img_dx, qy = (beta - b.y0) / b.img_dy;
     if (!(qx > -1 && qx < b.img_nx && qy > -1 && qy < b.img_ny)) return 0;

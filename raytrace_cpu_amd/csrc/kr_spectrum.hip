@@ -2,8 +2,8 @@
 // tabulated rest-frame spectrum, smeared by the rays.  Unlike the line (kr_line.hip), where a ray lands in ONE energy bin and an LDS histogram with one
 // atomic per ray does the job, every disc ray adds to EVERY output energy: n_disc x ne evaluations, each an expm1 or a table interpolation.  So the
 // kernel turns the work round between two phases, per tile of kBlock records:
-//   phase A  one RECORD per lane: the per-ray code of post_line_limb_kernel (redshift, range_phi, filter, mu, limb law); a ray that survives leaves one
-//            compact item {g, 1 / (f_col kT) or u_g and its zone, w g^-3} in LDS, compacted by a ballot and a prefix count;
+//   phase A  one RECORD per lane: disc_ray (kr_disc_pass.hpp: redshift, range_phi, filter, mu, limb law); a ray that survives leaves one compact item
+//            {g, 1 / (f_col kT) or u_g and its zone, w g^-3} in LDS, placed by tile_compact;
 //   phase B  one ENERGY per lane: lane e keeps E_e and its running sum in registers and walks the tile's items -- every lane reads the same LDS
 //            address, a broadcast.  With ne > kBlock a lane owns SLOTS energies.
 // No atomic sits in either inner loop: at the end of the launch a workgroup adds each non-zero sum it owns into the global spectrum, once.
@@ -18,7 +18,7 @@
 #include <string>
 #include <type_traits>
 
-#include "kr_pass.hpp"
+#include "kr_disc_pass.hpp"
 
 namespace kr {
 
@@ -30,7 +30,6 @@ namespace {
 // the table never lowers the occupancy of any of them.  A 64-KiB budget would cap the one- and two-slot reduce forms at 2 workgroups / CU.  Above
 // the budget S is read from global memory (a table that size is L2-resident, and every lane of a wave reads near the same node).
 constexpr int kSpecLdsWords = 4096;
-constexpr int kMaxSlots = 16;            // ne <= kMaxSlots kBlock = 4096
 
 // what the kernels need besides the records: the model by value (its host pointers are never dereferenced on the device), the device copies of the
 // tables and the logarithms that are taken once, on the host
@@ -42,21 +41,9 @@ struct SpecDev {
     double log_de, log_tdr, log_sde, log_semin, log_span, s_e_last, fcol_m4;
 };
 
-// the truncated radial-table index of line_item (kr_line.hip): false when r falls outside the table
 KR_DEV bool table_index(const SpecDev& D, double r, int* ir)
 {
-    const double fi = D.m.table_logbin ? kr_log(r / D.m.table_r_min) / D.log_tdr : (r - D.m.table_r_min) / D.m.table_dr;
-    if (!(fi > -1 && fi < D.m.table_nr)) return false;
-    *ir = (int) fi;
-    return true;
-}
-
-// the disc filter of the line (kr_line.hip, line_filter)
-KR_DEV bool spectrum_filter(const kr_spectrum_model& m, int steps, double r, double theta, double g)
-{
-    if (!(steps > 0)) return false;
-    const double z = r * kr_cos(theta);
-    return z < 1E-2 && r >= m.r_isco && r < m.r_disc && g > 0;
+    return radial_table_index(D.m.table_logbin, D.m.table_r_min, D.m.table_dr, D.log_tdr, D.m.table_nr, r, ir);
 }
 
 // one ray that passed the filter (and, under a law that needs it, has its angle) -> its item {a, b, c, zone}; false: the ray is not used
@@ -132,55 +119,14 @@ spectrum_kernel(typename std::conditional<FUSED, kr_ray_f64, const kr_ray_f64>::
         double a = 0, b = 0, c = 0;
         int zone = 0;
         if (i < n) {
-            auto* ray = &rays[i];
-            double r, theta, g, limb = 1;
-            const int steps = ray->steps;
-            bool drop = false;
-            if constexpr (FUSED) {
-                const kr_ray_f64 v = geodesic_of(ray);
-                r = v.r; theta = v.theta;
-                if (motion == 0) {
-                    const Frame f = frame_value(v, spin, V, reverse, projradius);
-                    g = frame_redshift(f, v.emit, reverse);
-                    ray->redshift = g;
-                    wrap_phi(ray, steps, lo, hi);
-                    if (spectrum_filter(m, steps, r, theta, g)) {
-                        on_disc++;
-                        const double mu = frame_mu(f);
-                        if (frame_bad_angle(f, mu)) {
-                            bad_angle++;
-                            drop = law.law != 0;
-                        }
-                        limb = limb_weight(law.law, law.coeff, mu);
-                    } else {
-                        drop = true;
-                    }
-                } else {                                 // (law 0 only: the validator refuses the rest)
-                    g = redshift_value(v, spin, V, reverse, projradius, motion);
-                    ray->redshift = g;
-                    wrap_phi(ray, steps, lo, hi);
-                    if (spectrum_filter(m, steps, r, theta, g)) on_disc++;
-                    else drop = true;
-                }
-            } else {
-                r = ray->r; theta = ray->theta; g = ray->redshift;
-                if (spectrum_filter(m, steps, r, theta, g)) on_disc++;
-                else drop = true;
-            }
-            if (!drop) live = spectrum_item<THERMAL>(D, r, g, limb, &a, &b, &c, &zone);
+            DiscRay d;
+            if (disc_ray<FUSED>(&rays[i], m.r_isco, m.r_disc, spin, V, reverse, projradius, motion, lo, hi, law, &d, on_disc, bad_angle))
+                live = spectrum_item<THERMAL>(D, d.r, d.g, d.limb, &a, &b, &c, &zone);
             if (live) used++;
         }
-        const unsigned long long mask = __ballot(live);
-        if (lane == 0) wave_count[wave] = __popcll(mask);
-        __syncthreads();
-        int at = __popcll(mask & ((1ull << lane) - 1)), items = 0;
-#pragma unroll
-        for (int w = 0; w < kBlock / 64; w++) {
-            const int cnt = wave_count[w];
-            if (w < wave) at += cnt;
-            items += cnt;
-        }
-        if (live) { it_a[at] = a; it_b[at] = b; it_c[at] = c; it_z[at] = zone; }        // at < items <= kBlock
+        int at, items;
+        tile_compact(live, wave_count, &at, &items);
+        if (live) { it_a[at] = a; it_b[at] = b; it_c[at] = c; it_z[at] = zone; }
         __syncthreads();
         // ---- phase B: one energy per lane and slot, over the tile's live items
         for (int j = 0; j < items; j++) {
@@ -200,7 +146,7 @@ spectrum_kernel(typename std::conditional<FUSED, kr_ray_f64, const kr_ray_f64>::
                 }
             }
         }
-        // (no barrier here: a wave that runs ahead writes wave_count, which every wave has read before the barrier above, and it[] only after the next one)
+        // (no barrier here: tile_compact)
     }
 
     // ---- the flush: one global atomic per energy with a non-zero sum, and the tallies
@@ -246,26 +192,6 @@ int spectrum_dev(const kr_spectrum_model* m, TablePins& pins, SpecDev* D)
     return table_on_device(pins, kSpectrumTable, m->s, (size_t) m->nz * m->s_ne, &D->s);
 }
 
-template <int MODEL, bool FUSED, int SLOTS, typename Rays>
-void launch_one(int grid, size_t lds, hipStream_t st, Rays* d, long long n, double spin, double V, int reverse, int projradius, int motion, double lo, double hi,
-                const SpecDev& D, const kr_limb_law& law, double* out)
-{
-    hipLaunchKernelGGL((spectrum_kernel<MODEL, FUSED, SLOTS>), dim3(grid), dim3(kBlock), lds, st, d, n, spin, V, reverse, projradius, motion, lo, hi, D, law, out);
-}
-
-template <int MODEL, bool FUSED, typename Rays>
-void launch_slots(int slots, int grid, size_t lds, hipStream_t st, Rays* d, long long n, double spin, double V, int reverse, int projradius, int motion, double lo,
-                  double hi, const SpecDev& D, const kr_limb_law& law, double* out)
-{
-#define KR_SPEC_SLOTS(K) launch_one<MODEL, FUSED, K>(grid, lds, st, d, n, spin, V, reverse, projradius, motion, lo, hi, D, law, out)
-    if (slots <= 1) KR_SPEC_SLOTS(1);
-    else if (slots <= 2) KR_SPEC_SLOTS(2);
-    else if (slots <= 4) KR_SPEC_SLOTS(4);
-    else if (slots <= 8) KR_SPEC_SLOTS(8);
-    else KR_SPEC_SLOTS(kMaxSlots);
-#undef KR_SPEC_SLOTS
-}
-
 template <bool FUSED, typename Rays>
 int spectrum_launch(const kr_spectrum_model* m, const kr_limb_law& law, Rays* d, int64_t n, double spin, double V, int reverse, int projradius, int motion, double lo,
                     double hi, void* d_out, hipStream_t st)
@@ -277,10 +203,14 @@ int spectrum_launch(const kr_spectrum_model* m, const kr_limb_law& law, Rays* d,
     if (rc != KR_OK) return rc;
     const int slots = (m->ne + kBlock - 1) / kBlock, grid = grid_for(n, kBlock, kCapHist);
     const int64_t s_words = (int64_t) m->nz * m->s_ne;
-    if (m->model == 0) launch_slots<0, FUSED>(slots, grid, 0, st, d, (long long) n, spin, V, reverse, projradius, motion, lo, hi, D, law, (double*) d_out);
-    else if (s_words <= kSpecLdsWords)
-        launch_slots<1, FUSED>(slots, grid, (size_t) s_words * sizeof(double), st, d, (long long) n, spin, V, reverse, projradius, motion, lo, hi, D, law, (double*) d_out);
-    else launch_slots<2, FUSED>(slots, grid, 0, st, d, (long long) n, spin, V, reverse, projradius, motion, lo, hi, D, law, (double*) d_out);
+    for_slots(slots, [&](auto K) {
+        auto launch = [&](auto kernel, size_t lds) {
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, st, d, (long long) n, spin, V, reverse, projradius, motion, lo, hi, D, law, (double*) d_out);
+        };
+        if (m->model == 0) launch(spectrum_kernel<0, FUSED, K.value>, 0);
+        else if (s_words <= kSpecLdsWords) launch(spectrum_kernel<1, FUSED, K.value>, (size_t) s_words * sizeof(double));
+        else launch(spectrum_kernel<2, FUSED, K.value>, 0);
+    });
     KR_LAUNCH_CHECK();
     return KR_OK;
 }
@@ -296,9 +226,7 @@ int spectrum_validate(const kr_spectrum_model* m, const char* who)
     for (double v : params)
         if (!std::isfinite(v)) return bad("non-finite model parameter");
     if (m->ne < 1 || m->ne > kMaxSlots * kBlock) return bad("ne must be in 1 ... 4096");
-    if (!(m->de > 0)) return bad("de must be positive");
-    if (m->log_e && !(m->de > 1)) return bad("log_e: de (the ratio between edges) must be > 1");
-    if (m->log_e && !(m->e_min > 0)) return bad("log_e: e_min must be positive");
+    if (const int rc = energy_axis_validate(bad, m->de, m->log_e, m->e_min)) return rc;
     const bool table = m->model == 0 ? true : m->table_emis != nullptr;
     if (m->model == 0) {
         if (!m->table_kt) return bad("the thermal model needs table_kt");
@@ -334,9 +262,7 @@ int post_spectrum_dev(double spin, double V, int reverse, int projradius, int mo
 
 int reduce_spectrum_dev(const kr_spectrum_model* m, const void* d, int64_t n, void* d_out, hipStream_t st)
 {
-    kr_limb_law iso;
-    iso.coeff = 0; iso.law = 0; iso.pad = 0;
-    return spectrum_launch<false>(m, iso, (const kr_ray_f64*) d, n, 0.0, 0.0, 0, 0, 0, 0.0, 0.0, d_out, st);
+    return spectrum_launch<false>(m, isotropic_limb(), (const kr_ray_f64*) d, n, 0.0, 0.0, 0, 0, 0, 0.0, 0.0, d_out, st);
 }
 
 }  // namespace kr
