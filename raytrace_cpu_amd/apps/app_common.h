@@ -5,12 +5,15 @@
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
+#include <iostream>
 #include <stdexcept>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "../../include/kr_trace.h"
+#include "../host/include/par_args.h"
+#include "../host/include/par_file.h"
 
 namespace krapp {
 
@@ -23,6 +26,47 @@ inline void check(int rc, const char* what)
 inline void require_device()
 {
     if (kr_device_count() < 0) throw std::runtime_error(kr_last_error());
+}
+
+// A program's options: `--key=value` on the command line first, then `key = value` in the parameter file (--parfile, or the program's default
+// file), then the default.  An error carries the text of ParameterArgs or ParameterFile, whichever was asked last.
+class Options {
+public:
+    Options(int argc, char** argv, const std::string& default_parfile)
+        : args(argc, argv), par(args.key_exists("--parfile") ? args.get_string_parameter("--parfile") : default_parfile) {}
+
+    bool on_command_line(const std::string& key) const { return args.key_exists("--" + key); }       // also a bare --key, such as --timing
+    bool has(const std::string& key) const { return on_command_line(key) || par.key_exists(key); }
+    double num(const std::string& key, double dflt) const { return get<double>(key, dflt); }
+    double req(const std::string& key) const { return get<double>(key); }
+    int integer(const std::string& key) const { return get<int>(key); }
+    int integer(const std::string& key, int dflt) const { return get<int>(key, dflt); }
+    bool flag(const std::string& key, bool dflt) const { return get<bool>(key, dflt); }               // 0 | 1
+    std::string str(const std::string& key) const { return get<std::string>(key); }
+    std::string str(const std::string& key, const std::string& dflt) const { return get<std::string>(key, dflt); }
+
+    const ParameterArgs args;
+    const ParameterFile par;
+
+private:
+    template <class T>
+    T get(const std::string& key) const { return on_command_line(key) ? args.get_parameter<T>("--" + key) : par.get_parameter<T>(key); }
+    template <class T>
+    T get(const std::string& key, const T& dflt) const { return on_command_line(key) ? args.get_parameter<T>("--" + key) : par.get_parameter<T>(key, dflt); }
+};
+
+// main() of a program: the process set up for HIP, the options read, `body(options)`, "Done"; whatever is thrown goes to stderr with exit status 1
+template <class Body>
+inline int run_program(int argc, char** argv, const char* default_parfile, Body body)
+try {
+    (void) kr_configure_process();       // first HIP user of this process: hardware queues for overlapping launches (include/kr_trace.h)
+    const Options opt(argc, argv, default_parfile);
+    body(opt);
+    std::cout << "Done" << std::endl;
+    return 0;
+} catch (const std::exception& e) {
+    std::cerr << e.what() << std::endl;
+    return 1;
 }
 
 // KRTRACE_ARITHMETIC = hybrid | strict | fast, as in the host mirror of the class API; unset: hybrid for the
@@ -39,6 +83,11 @@ inline std::string arithmetic_from_env()
 {
     const char* e = std::getenv("KRTRACE_ARITHMETIC");
     return e ? std::string(e) : std::string();
+}
+// --arithmetic, else the environment's (never the parameter file's)
+inline std::string arithmetic_choice(const Options& opt)
+{
+    return opt.on_command_line("arithmetic") ? opt.str("arithmetic") : arithmetic_from_env();
 }
 
 inline int integrator_code(const std::string& name, int fallback)

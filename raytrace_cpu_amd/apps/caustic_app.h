@@ -15,6 +15,7 @@
 #include "../host/include/par_args.h"
 #include "../host/include/par_file.h"
 #include "app_common.h"
+#include "imageplane_app.h"
 
 namespace krapp {
 
@@ -61,16 +62,7 @@ struct CausticSetup {
         img_ny = Ny + 1;
     }
 
-    kr_imageplane plane() const
-    {
-        kr_imageplane s;
-        memset(&s, 0, sizeof s);
-        s.dist = dist; s.inc_deg = incl;
-        s.x0 = x0; s.xmax = xmax; s.dx = dx;
-        s.y0 = y0; s.ymax = ymax; s.dy = dy;
-        s.spin = spin; s.phi0 = plane_phi0; s.precision = precision;
-        return s;
-    }
+    kr_imageplane plane() const { return imageplane(dist, incl, x0, xmax, dx, y0, ymax, dy, spin, plane_phi0, precision); }
 
     // everything of kr_params that does not depend on the stop surface
     kr_params params() const

@@ -32,13 +32,13 @@ using namespace std;
 int main(int argc, char** argv)
 try {
     (void) kr_configure_process();
-    ParameterArgs args(argc, argv);
-    const string par_name = args.key_exists("--parfile") ? args.get_string_parameter("--parfile") : string("../par/disc_source_return_angdist.par");
-    ParameterFile par(par_name);
+    const krapp::Options opt(argc, argv, "../par/disc_source_return_angdist.par");
+    const ParameterArgs& args = opt.args;
+    const ParameterFile& par = opt.par;
 
-    const string out_filename = args.key_exists("--outfile") ? args.get_parameter<string>("--outfile") : par.get_parameter<string>("outfile");
-    const bool disc_source = args.key_exists("--source_r") || par.key_exists("source_r");
-    const double spin = args.key_exists("--spin") ? args.get_parameter<double>("--spin") : par.get_parameter<double>("spin");
+    const string out_filename = opt.str("outfile");
+    const bool disc_source = opt.has("source_r");
+    const double spin = opt.req("spin");
     const double cosalpha0 = par.get_parameter<double>("cosalpha0", -0.995);
     const double cosalphamax = par.get_parameter<double>("cosalphamax", 0.995);
     const double dcosalpha = par.get_parameter<double>("dcosalpha");
@@ -54,8 +54,8 @@ try {
     const double dangle = par.get_parameter<double>("dangle", 0.1);
     const bool self_zone = par.get_parameter<bool>("self_zone", false);
     const string integ = par.get_parameter<string>("integrator", "euler");
-    const string arith = args.key_exists("--arithmetic") ? args.get_parameter<string>("--arithmetic") : krapp::arithmetic_from_env();
-    const bool timing = args.key_exists("--timing");
+    const string arith = krapp::arithmetic_choice(opt);
+    const bool timing = opt.on_command_line("timing");
 
     kr_pointsource ps;
     kr_pointsource_vel_spec vs;
@@ -64,7 +64,7 @@ try {
     double source[4];
     int64_t n = 0;
     if (disc_source) {
-        const double source_r = args.key_exists("--source_r") ? args.get_parameter<double>("--source_r") : par.get_parameter<double>("source_r");
+        const double source_r = opt.req("source_r");
         double V = par.get_parameter<double>("V", -1);
         if (V < 0) V = disc_velocity<double>(source_r, spin, +1);
         source[0] = 0.; source[1] = source_r; source[2] = M_PI_2 - 1E-6; source[3] = par.get_parameter<double>("source_phi", 1.5707);

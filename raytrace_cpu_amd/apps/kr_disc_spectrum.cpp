@@ -3,7 +3,7 @@
 // power law) smeared by the rays, relconv-style.  The rays are generated, traced, redshifted and summed into every output energy in HBM and only the
 // Nen + 4 doubles of the spectrum come back (include/kr_trace.h, kr_spectrum_model, has the per-ray rule).
 //
-// Reads the parameter file and the plane, disc, emissivity and limb keys of kr_line_profile (--parfile, outfile, dist, incl, plane_phi0, spin, r_disc,
+// Reads the plane and disc keys of imageplane_app.h and the emissivity and limb keys of kr_line_profile (--parfile, outfile, dist, incl, plane_phi0, spin, r_disc,
 // x0, xmax, Nx, y0, ymax, Ny, q1, rb1, q2, rb2, q3, emis_file, limb, limb_coeff, precision, integrator, rk45_tol; --arithmetic, --device, --timing), and
 //   e_min = 0.1, e_max = 10   energy range of the Nen = 100 bins; the spectrum is sampled at the CENTRE of each bin
 //   log_e = 1                 logarithmic bins (geometric centres)
@@ -16,11 +16,11 @@
 //                             comma-separated list (no blanks) gives one file per radial zone, innermost first (zones log-spaced over [r_isco, r_disc))
 //             Nzones          optional; must equal the number of files
 //             spec_bins = 512 nodes of the log grid the files are resampled onto (linear in log E), from the first file's first to its last energy
-// Every key may also be given as --key=value, which takes precedence over the file.
+// Every key may also be given as --key=value, which takes precedence over the file.  Nx and Ny are read as int, as kr_imageplane_disc_image reads
+// them (before imageplane_app.h: as double, then cast; the same for a key written as a plain integer).
 // Output: TextOutput (width 20, precision 8): three comment rows "# ON_DISC", "# USED", "# BAD_ANGLE" with their counts, then one row per energy:
 // E flux.  The flux is per image-plane pixel: multiply by dx dy / dist^2 for a flux density.
 #include <cmath>
-#include <cstdlib>
 #include <fstream>
 #include <iostream>
 #include <sstream>
@@ -28,12 +28,9 @@
 #include <vector>
 using namespace std;
 
-#include "../host/include/kerr.h"
-#include "../host/include/par_args.h"
-#include "../host/include/par_file.h"
 #include "../host/include/text_output.h"
-#include "app_common.h"
 #include "emissivity_table.h"
+#include "imageplane_app.h"
 
 namespace {
 
@@ -104,90 +101,56 @@ vector<string> split_commas(const string& s)
 
 }  // namespace
 
-int main(int argc, char** argv)
-try {
-    (void) kr_configure_process();       // first HIP user of this process (include/kr_trace.h)
-    ParameterArgs args(argc, argv);
-    const string par_name = args.key_exists("--parfile") ? args.get_string_parameter("--parfile") : string("../par/disc_spectrum.par");
-    ParameterFile par(par_name);
-    // --key=value first, then the parameter file, then the default
-    auto num = [&](const string& key, double dflt) { return args.key_exists("--" + key) ? args.get_parameter<double>("--" + key) : par.get_parameter<double>(key, dflt); };
-    auto req = [&](const string& key) { return args.key_exists("--" + key) ? args.get_parameter<double>("--" + key) : par.get_parameter<double>(key); };
-    auto has = [&](const string& key) { return args.key_exists("--" + key) || par.key_exists(key); };
-    auto str = [&](const string& key, const string& dflt) { return args.key_exists("--" + key) ? args.get_parameter<string>("--" + key) : par.get_parameter<string>(key, dflt); };
-
-    const string out_name = args.key_exists("--outfile") ? args.get_parameter<string>("--outfile") : par.get_parameter<string>("outfile");
-    const double dist = req("dist"), incl = req("incl"), plane_phi0 = num("plane_phi0", 0), spin = req("spin"), r_disc = req("r_disc");
-    const double x0 = num("x0", -1 * r_disc), xmax = num("xmax", r_disc);
-    const int Nx = (int) req("Nx");
-    const double y0 = num("y0", x0), ymax = num("ymax", xmax);
-    const int Ny = (int) num("Ny", Nx);
-    const double q1 = num("q1", 3), rb1 = num("rb1", 4), q2 = num("q2", 3), rb2 = num("rb2", 10), q3 = num("q3", 3);
-    const double precision = num("precision", 100);
-    const string integ = str("integrator", "rk45");
-    const double rk45_tol = num("rk45_tol", 1e-8);
-    const string arith = args.key_exists("--arithmetic") ? args.get_parameter<string>("--arithmetic") : krapp::arithmetic_from_env();
-    const bool timing = args.key_exists("--timing");
-    const string emis_file = str("emis_file", "");
+static void program(const krapp::Options& opt)
+{
+    const krapp::DiscPlaneSetup s(opt);
+    const string emis_file = opt.str("emis_file", "");
     kr_limb_law limb;
     memset(&limb, 0, sizeof limb);
-    limb.law = (int32_t) num("limb", 0);
-    limb.coeff = num("limb_coeff", 2.06);
+    limb.law = (int32_t) opt.num("limb", 0);
+    limb.coeff = opt.num("limb_coeff", 2.06);
 
-    const double e_min = num("e_min", 0.1), e_max = num("e_max", 10);
-    const int ne = (int) num("Nen", 100);
-    const bool log_e = num("log_e", 1) != 0;
+    const double e_min = opt.num("e_min", 0.1), e_max = opt.num("e_max", 10);
+    const int ne = (int) opt.num("Nen", 100);
+    const bool log_e = opt.num("log_e", 1) != 0;
     if (ne < 1) throw invalid_argument("Nen: at least one energy");
     const double de = log_e ? exp(log(e_max / e_min) / ne) : (e_max - e_min) / ne;
-    const string model_name = str("model", "thermal");
+    const string model_name = opt.str("model", "thermal");
     if (model_name != "thermal" && model_name != "table") throw invalid_argument("model: expected thermal or table, got '" + model_name + "'");
+    s.print_isco();
 
-    const double dx = (xmax - x0) / Nx, dy = (ymax - y0) / Ny;
-    const double r_isco = kerr_isco<double>(spin, +1);
-    cout << "ISCO at " << r_isco << endl;
-
-    kr_imageplane plane;
-    memset(&plane, 0, sizeof plane);
-    plane.dist = dist;
-    plane.inc_deg = incl;
-    plane.x0 = x0; plane.xmax = xmax; plane.dx = dx;
-    plane.y0 = y0; plane.ymax = ymax; plane.dy = dy;
-    plane.spin = spin;
-    plane.phi0 = plane_phi0;
-    plane.precision = precision;
-
+    const kr_imageplane plane = s.plane();
     kr_spectrum_model sm;
     memset(&sm, 0, sizeof sm);
     sm.e_min = e_min; sm.de = de; sm.ne = ne; sm.log_e = log_e ? 1 : 0;
-    sm.r_isco = r_isco; sm.r_disc = r_disc;
-    sm.q1 = q1; sm.rb1 = rb1; sm.q2 = q2; sm.rb2 = rb2; sm.q3 = q3;
+    s.fill_disc(sm);
     sm.f_col = 1;
     vector<double> kt, S;
     krapp::EmisTable table;
     if (model_name == "thermal") {
-        const double mass = num("mass", 10), mdot = num("mdot", 1e18);
-        const int kt_bins = (int) num("kt_bins", 400);
+        const double mass = opt.num("mass", 10), mdot = opt.num("mdot", 1e18);
+        const int kt_bins = (int) opt.num("kt_bins", 400);
         if (kt_bins < 1) throw invalid_argument("kt_bins: at least one radial bin");
         sm.model = 0;
-        sm.f_col = num("f_col", 1.7);
-        sm.table_r_min = r_isco;
-        sm.table_dr = pow(r_disc / r_isco, 1.0 / kt_bins);
+        sm.f_col = opt.num("f_col", 1.7);
+        sm.table_r_min = s.r_isco;
+        sm.table_dr = pow(s.r_disc / s.r_isco, 1.0 / kt_bins);
         sm.table_logbin = 1;
         sm.table_nr = kt_bins;
         const double scale = mdot * pow(kC, 6) / (kG * kG * (mass * kMsun) * (mass * kMsun));
         kt.resize((size_t) kt_bins);
         double kt_max = 0;
         for (int i = 0; i < kt_bins; ++i) {
-            kt[(size_t) i] = kBoltzmannKeV * pow(novikov_thorne_flux(sm.table_r_min * pow(sm.table_dr, i + 0.5), spin) * scale / kSigmaSB, 0.25);
+            kt[(size_t) i] = kBoltzmannKeV * pow(novikov_thorne_flux(sm.table_r_min * pow(sm.table_dr, i + 0.5), s.spin) * scale / kSigmaSB, 0.25);
             if (kt[(size_t) i] > kt_max) kt_max = kt[(size_t) i];
         }
         sm.table_kt = kt.data();
         cout << "Novikov-Thorne disc: " << mass << " Msun, " << mdot << " g/s, f_col " << sm.f_col << ", peak kT_eff " << kt_max << " keV" << endl;
     } else {
-        const vector<string> files = split_commas(str("spec_file", ""));
+        const vector<string> files = split_commas(opt.str("spec_file", ""));
         if (files.empty()) throw invalid_argument("model = table needs spec_file");
-        if (has("Nzones") && (int) num("Nzones", 1) != (int) files.size()) throw invalid_argument("Nzones: must equal the number of files in spec_file");
-        const int spec_bins = (int) num("spec_bins", 512);
+        if (opt.has("Nzones") && (int) opt.num("Nzones", 1) != (int) files.size()) throw invalid_argument("Nzones: must equal the number of files in spec_file");
+        const int spec_bins = (int) opt.num("spec_bins", 512);
         if (spec_bins < 2) throw invalid_argument("spec_bins: at least two nodes");
         vector<TwoColumns> specs;
         for (const string& f : files) specs.push_back(read_spectrum(f));
@@ -214,54 +177,29 @@ try {
         }
         cout << "rest-frame spectrum: " << files.size() << " zone(s), " << spec_bins << " nodes from " << first << ", ratio " << sm.s_de << endl;
     }
-
-    kr_params p;
-    kr_params_default(&p, -spin);            // the image plane traces backwards in time: spin enters negated (imageplane.cpp:12)
-    p.precision = precision;
-    p.integrator = krapp::integrator_code(integ, KR_RK45);
-    if (p.integrator == KR_RK45) p.rk45_tol = rk45_tol;
-    p.theta_max = M_PI_2;
-    p.r_max = 1.1 * dist;
-    p.stop_kind = KR_STOP_THETA;
-    p.flags = krapp::arithmetic_flags(arith, p.integrator);
+    const kr_params p = s.params(KR_RK45);
 
     // ---- device pipeline: init_emit -> trace -> redshift + range_phi + spectrum ---------------------------------------------------------
-    krapp::check(kr_set_device((int) num("device", 0)), "kr_set_device");
-    krapp::Stopwatch clock;
-    const int64_t n = kr_imageplane_count(&plane, nullptr, nullptr);
-    if (n <= 0) throw runtime_error("empty ray grid");
+    krapp::DiscPlaneRun run(s, plane);
     const int64_t words = (int64_t) ne + 4;
-    krapp::DeviceBuffer rays(n * (int64_t) sizeof(kr_ray_f64));
-    krapp::DeviceBuffer spec(words * (int64_t) sizeof(double));
-    spec.zero();
-    krapp::check(kr_imageplane_init_emit_dev_f64(&plane, 0, 1, 0.0, 1, 0, rays.get(), n, nullptr), "imageplane_init + redshift_start");
-    krapp::check(kr_synchronize(nullptr), "sync");
-    const double ms_init = clock.lap_ms();
-    kr_stats st;
-    krapp::check(kr_trace_dev_f64(&p, rays.get(), n, nullptr, &st), "trace");
-    const double ms_trace = clock.lap_ms();
-    krapp::check(kr_post_spectrum_dev_f64(-spin, -1.0, 1, 0, 0, -1 * M_PI, M_PI, &sm, &limb, rays.get(), n, spec.get(), nullptr), "redshift + range_phi + spectrum");
+    run.trace(plane, p, words);
+    krapp::check(kr_post_spectrum_dev_f64(-s.spin, -1.0, 1, 0, 0, -1 * M_PI, M_PI, &sm, &limb, run.rays->get(), run.n, run.acc->get(), nullptr), "redshift + range_phi + spectrum");
     vector<double> h((size_t) words);
-    krapp::check(kr_memcpy_d2h(h.data(), spec.get(), words * (int64_t) sizeof(double)), "d2h");
-    const double ms_post = clock.lap_ms();
+    krapp::check(kr_memcpy_d2h(h.data(), run.acc->get(), words * (int64_t) sizeof(double)), "d2h");
+    const double ms_post = run.clock.lap_ms();
 
     cout << static_cast<long>(h[(size_t) ne]) << " rays on the disc, " << static_cast<long>(h[(size_t) ne + 1]) << " used, " << static_cast<long>(h[(size_t) ne + 2])
          << " without an emission angle (bad-angle)" << endl;
     {
-        TextOutput outfile(out_name);
+        TextOutput outfile(s.out_name);
         outfile << "# ON_DISC" << static_cast<long>(h[(size_t) ne]) << endl;
         outfile << "# USED" << static_cast<long>(h[(size_t) ne + 1]) << endl;
         outfile << "# BAD_ANGLE" << static_cast<long>(h[(size_t) ne + 2]) << endl;
         for (int i = 0; i < ne; ++i) outfile << (log_e ? e_min * pow(de, i + 0.5) : e_min + (i + 0.5) * de) << h[(size_t) i] << endl;
     }
-    const double ms_out = clock.lap_ms();
+    const double ms_out = run.clock.lap_ms();
 
-    if (timing)
-        cout << "timing: rays " << st.rays_traced << " steps " << st.steps_total << " | init+redshift_start " << ms_init << " ms | trace " << ms_trace
-             << " ms (kernel " << st.kernel_ms << ") | redshift+range_phi+spectrum+readback " << ms_post << " ms | text file " << ms_out << " ms" << endl;
-    cout << "Done" << endl;
-    return 0;
-} catch (const exception& e) {
-    cerr << e.what() << endl;
-    return 1;
+    if (s.timing) run.print_timing() << "redshift+range_phi+spectrum+readback " << ms_post << " ms | text file " << ms_out << " ms" << endl;
 }
+
+int main(int argc, char** argv) { return krapp::run_program(argc, argv, "../par/disc_spectrum.par", program); }

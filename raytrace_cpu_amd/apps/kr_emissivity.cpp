@@ -34,27 +34,27 @@ using namespace std;
 int main(int argc, char** argv)
 try {
     (void) kr_configure_process();       // first HIP user of this process: hardware queues for overlapping launches (include/kr_trace.h)
-    ParameterArgs args(argc, argv);
-    const string par_name = args.key_exists("--parfile") ? args.get_string_parameter("--parfile") : string("../par/emissivity.par");
-    ParameterFile par(par_name);
+    const krapp::Options opt(argc, argv, "../par/emissivity.par");
+    const ParameterArgs& args = opt.args;
+    const ParameterFile& par = opt.par;
 
-    const string out_name = args.key_exists("--outfile") ? args.get_parameter<string>("--outfile") : par.get_parameter<string>("outfile");
+    const string out_name = opt.str("outfile");
     double source[4];
     par.get_parameter_array("source", source, 4);
     if (args.key_exists("--source_h")) source[1] = args.get_parameter<double>("--source_h");
     const double V = par.get_parameter<double>("V", 0);
-    const double spin = args.key_exists("--spin") ? args.get_parameter<double>("--spin") : par.get_parameter<double>("spin");
+    const double spin = opt.req("spin");
     const double r_max = par.get_parameter<double>("r_esc", 1000);
-    double r_min = args.key_exists("--rmin") ? args.get_parameter<double>("--rmin") : par.get_parameter<double>("rmin", -1);
-    const int Nr = args.key_exists("--Nr") ? args.get_parameter<int>("--Nr") : par.get_parameter<int>("Nr", 100);
+    double r_min = opt.num("rmin", -1);
+    const int Nr = opt.integer("Nr", 100);
     const double r_disc = par.get_parameter<double>("r_esc", 500);
     const bool logbin_r = par.get_parameter<bool>("logbin_r", true);
     const double gamma = par.get_parameter<double>("gamma", 2);
-    const string integ = args.key_exists("--integrator") ? args.get_parameter<string>("--integrator") : par.get_parameter<string>("integrator", "rk45");
-    const string arith = args.key_exists("--arithmetic") ? args.get_parameter<string>("--arithmetic") : krapp::arithmetic_from_env();
-    const bool timing = args.key_exists("--timing");
-    const int Nmu = args.key_exists("--Nmu") ? args.get_parameter<int>("--Nmu") : par.get_parameter<int>("Nmu", 0);
-    const string mu_out_name = args.key_exists("--mu_outfile") ? args.get_parameter<string>("--mu_outfile") : par.get_parameter<string>("mu_outfile", "");
+    const string integ = opt.str("integrator", "rk45");
+    const string arith = krapp::arithmetic_choice(opt);
+    const bool timing = opt.on_command_line("timing");
+    const int Nmu = opt.integer("Nmu", 0);
+    const string mu_out_name = opt.str("mu_outfile", "");
     if (Nmu < 0) throw invalid_argument("Nmu must be >= 0");
     if (Nmu > 0 && mu_out_name.empty()) throw invalid_argument("Nmu needs mu_outfile");
     const bool thick = par.key_exists("disc_slope") || par.key_exists("disc_scale");

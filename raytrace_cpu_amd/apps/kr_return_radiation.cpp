@@ -31,20 +31,20 @@ using namespace std;
 int main(int argc, char** argv)
 try {
     (void) kr_configure_process();       // first HIP user of this process: hardware queues for overlapping launches (include/kr_trace.h)
-    ParameterArgs args(argc, argv);
-    const string par_name = args.key_exists("--parfile") ? args.get_string_parameter("--parfile") : string("../par/disc_source_photonfrac_r.par");
-    ParameterFile par(par_name);
+    const krapp::Options opt(argc, argv, "../par/disc_source_photonfrac_r.par");
+    const ParameterArgs& args = opt.args;
+    const ParameterFile& par = opt.par;
 
-    const string out_name = args.key_exists("--outfile") ? args.get_parameter<string>("--outfile") : par.get_parameter<string>("outfile");
+    const string out_name = opt.str("outfile");
     const double source_phi = par.get_parameter<double>("source_phi", 1.5707);
-    const double spin = args.key_exists("--spin") ? args.get_parameter<double>("--spin") : par.get_parameter<double>("spin");
+    const double spin = opt.req("spin");
     const double cosalpha0 = par.get_parameter<double>("cosalpha0", -0.995);
     const double cosalphamax = par.get_parameter<double>("cosalphamax", 0.995);
     const double dcosalpha = par.get_parameter<double>("dcosalpha");
     const double dbeta = par.get_parameter<double>("dbeta");
     const double r_esc = par.get_parameter<double>("r_esc", 1000);
-    double r_min = args.key_exists("--rmin") ? args.get_parameter<double>("--rmin") : par.get_parameter<double>("rmin", -1);
-    const int Nr = args.key_exists("--Nr") ? args.get_parameter<int>("--Nr") : par.get_parameter<int>("Nr");
+    double r_min = opt.num("rmin", -1);
+    const int Nr = opt.integer("Nr");
     const bool logbin_r = par.get_parameter<bool>("logbin_r", false);
     const double r_disc = par.get_parameter<double>("r_esc", 500);
     const bool plane_iso = par.get_parameter<bool>("plane_iso", true);
@@ -52,9 +52,9 @@ try {
     const bool weight_norm = par.get_parameter<bool>("weight_norm", true);
     const double gamma = par.get_parameter<double>("gamma", 2);
     const string map_name = par.get_parameter<string>("map_outfile", "");
-    const string integ = args.key_exists("--integrator") ? args.get_parameter<string>("--integrator") : par.get_parameter<string>("integrator", "euler");
-    const string arith = args.key_exists("--arithmetic") ? args.get_parameter<string>("--arithmetic") : krapp::arithmetic_from_env();
-    const bool timing = args.key_exists("--timing");
+    const string integ = opt.str("integrator", "euler");
+    const string arith = krapp::arithmetic_choice(opt);
+    const bool timing = opt.on_command_line("timing");
     if (Nr <= 0) throw runtime_error("Nr must be positive");
 
     const double r_isco = kerr_isco<double>(spin, +1);

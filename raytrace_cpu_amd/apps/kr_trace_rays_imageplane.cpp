@@ -15,6 +15,7 @@ using namespace std;
 
 #include "../host/include/par_args.h"
 #include "../host/include/par_file.h"
+#include "imageplane_app.h"
 #include "path_recording.h"
 
 int main(int argc, char** argv)
@@ -52,15 +53,7 @@ try {
     cout << "*****" << endl << endl;
 
     // ImagePlane<double>(dist, incl, x0, xmax, dx, y0, ymax, dy, spin, tol, plane_phi0): the last two land in `phi` and `precision` (:59)
-    kr_imageplane plane;
-    memset(&plane, 0, sizeof plane);
-    plane.dist = dist;
-    plane.inc_deg = incl;
-    plane.x0 = x0; plane.xmax = xmax; plane.dx = dx;
-    plane.y0 = y0; plane.ymax = ymax; plane.dy = dy;
-    plane.spin = spin;
-    plane.phi0 = tol;
-    plane.precision = plane_phi0;
+    const kr_imageplane plane = krapp::imageplane(dist, incl, x0, xmax, dx, y0, ymax, dy, spin, tol, plane_phi0);
 
     kr_params p;
     kr_params_default(&p, -spin);            // the image plane traces backwards in time: spin enters negated (imageplane.cpp:12)

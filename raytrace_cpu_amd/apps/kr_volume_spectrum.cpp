@@ -30,6 +30,7 @@ using namespace std;
 #include "../host/include/par_args.h"
 #include "../host/include/par_file.h"
 #include "app_common.h"
+#include "imageplane_app.h"
 #include "volume_app.h"
 
 int main(int argc, char** argv)
@@ -90,10 +91,7 @@ try {
     p_plane.stop_kind = KR_STOP_THETA;
     p_plane.flags = 0;
 
-    kr_imageplane plane;
-    memset(&plane, 0, sizeof plane);
-    plane.dist = dist; plane.inc_deg = incl; plane.x0 = x0; plane.xmax = xmax; plane.dx = (xmax - x0) / (Nx - 1); plane.y0 = y0; plane.ymax = ymax;
-    plane.dy = (ymax - y0) / (Ny - 1); plane.spin = spin; plane.phi0 = plane_phi0; plane.precision = 100;
+    const kr_imageplane plane = krapp::imageplane(dist, incl, x0, xmax, (xmax - x0) / (Nx - 1), y0, ymax, (ymax - y0) / (Ny - 1), spin, plane_phi0, 100);
 
     krapp::require_device();             // before the output file is created
     krapp::check(kr_set_device(args.get_parameter<int>("--device", 0)), "kr_set_device");
