@@ -525,6 +525,43 @@ typedef struct kr_hotspot {
 static_assert(sizeof(kr_hotspot) == 136, "kr_hotspot is 136 bytes (raytrace_cpu_amd/capi.py HotSpot)");
 #endif
 
+/* Reverberation response of the disc from image-plane rays: the energy-time impulse response of a whole tabulated rest-frame reflection spectrum (iron
+ * line, soft excess and Compton hump together, ionisation zones included).  Where kr_line_bins bins ONE line into (time, energy) and kr_spectrum_model
+ * smears a spectrum into every output energy with no time axis, here every disc ray adds to EVERY energy of ONE time row.  `spec` must be the table
+ * model (spec.model == 1); the thermal model is refused.  Per ray record, after redshift(V, reverse, projradius, motion):
+ *   filter, limb, ir, zone, emis, w, S_z(g E_i)
+ *            exactly as kr_spectrum_model states them for model 1, quoted:
+ *              "filter   the one of kr_line_bins: steps > 0, r cos(theta) < 1e-2, r_isco <= r < r_disc, g > 0 with g = rays[].redshift (E_rest = g E_obs, as
+ *                        the line uses it).  A ray that passes counts in `on_disc`."
+ *              "limb     limb(mu) of kr_limb_law, mu from the frame evaluation that gives g.  A bad-angle ray that passed the filter counts in `bad_angle`;
+ *                        with law != 0 it is not used, with law 0 it is used like every other ray.  The reduce forms are isotropic (law 0, no mu,
+ *                        bad_angle = 0)."
+ *              "ir       the truncated radial-table index of kr_line_bins: fi = log(r / table_r_min) / log(table_dr) (table_logbin) or
+ *                        (r - table_r_min) / table_dr, ir = (int) fi for fi in (-1, table_nr); outside: no ir."
+ *              "model 1, table:    I_rest(E') = S_z(E'),  w = emis(r) limb(mu),  emis = powerlaw3(r), or table_emis[ir] when table_emis != NULL -- a ray
+ *                        without ir or with a non-finite table_emis[ir] is not used: exactly the line's emissivity."  S, its nodes, the interpolation, the
+ *                        zeros outside [s_e_min, s_e_last] and the zone z: as that comment goes on to state them.
+ *            ir is needed when table_emis OR table_time is present.  A record without ir, or with a non-finite table_time[ir], passes the filter but
+ *            is not used.
+ *   time     ft = (t + tt - t0) / dt with t = rays[].t (disc -> observer) and tt = table_time ? table_time[ir] : 0 (source -> disc): the same
+ *            expression, in the same order, as the line pass.  j = (int) floor(ft).  A used record whose ft is NaN or outside [0, nt) counts in `outside`
+ *            and adds nothing.
+ *   sum      resp[j ne + i] += w g^-3 S_z(g E_i)  for every i (E_i: the bin centres of spec's grid, as kr_spectrum_model samples them).
+ * Output: double[nt ne + 4] = [resp (nt x ne, time-major: [j ne + i]) | on_disc | used | bad_angle | outside], ADDED into: shards, several planes and
+ * several calls sum.  `used` counts the records that pass every test except the time window; `outside` is a subset of `used`.
+ * Refused (KR_EINVAL): everything kr_spectrum_model refuses of spec; spec.model != 1; nt < 1; dt not positive or not finite; a non-finite t0;
+ * nt ne > 2^24; table_time with table_nr < 1 (or a non-finite table_r_min / table_dr).  table_time needs no table_emis (powerlaw3 then gives emis).
+ * The tables are copied to the device once per distinct contents (the table cache of kr_line_bins). */
+typedef struct kr_response_model {
+    kr_spectrum_model spec;        /* model 1: the rest-frame spectrum, its zones, the emissivity, the output energies, the disc filter */
+    double t0, dt;                 /* time rows: row j holds t0 + j dt <= t + tt < t0 + (j + 1) dt */
+    const double* table_time;      /* HOST, spec.table_nr values of the source -> disc time by radius (spec's radial table), or NULL: no source delay */
+    int32_t nt, pad;
+} kr_response_model;
+#ifdef __cplusplus
+static_assert(sizeof(kr_response_model) == 200, "kr_response_model is 200 bytes (raytrace_cpu_amd/capi.py ResponseModel)");
+#endif
+
 /* Critical-curve (caustic) maps of the disc on an image plane: src/caustic/caustic_discplane.cpp.  Per image-plane pixel (ix, iy), from the ray through
  * the pixel (bundle mode: member 0 of its 5-ray bundle, imageplane_bundles.h) after redshift(dest, reverse) (caustic_discplane.cpp:219-251):
  *   valid_hit   steps > 0, r_isco <= r < r_disc, redshift > 0 (:177-182)
@@ -1172,6 +1209,19 @@ int kr_post_spectrum_dev_f64(double spin, double V, int reverse, int projradius,
                              const kr_limb_law* law, void* d_rays, int64_t n, void* d_out, void* stream);
 int kr_reduce_spectrum_dev_f64(const kr_spectrum_model* m, const void* d_rays, int64_t n, void* d_out, void* stream);
 int kr_reduce_spectrum_f64(const kr_spectrum_model* m, const kr_ray_f64* rays, int64_t n, double* out);
+
+/* ---- reverberation response of the disc (kr_response_model above has the rule) ---------------------------------------------------------------
+ * Every entry point validates its arguments before it touches a device: KR_EINVAL (message in kr_last_error) for a null pointer, n < 0, whatever the
+ * model's comment refuses, a limb law other than 0, 1, 2, and motion != 0 with a limb law other than 0.  n == 0 is KR_OK and adds nothing.  None of the
+ * _dev forms waits for the device or allocates, beyond the table cache's first copy of a table.
+ * kr_post_response_dev_f64: redshift(V, reverse, projradius, motion) + range_phi(lo, hi) + the response in one pass; rays[] ends up exactly as after
+ * kr_post_line_dev_f64.  ADDS into d_out (nt ne + 4 doubles; zero it first).
+ * kr_reduce_response_dev_f64: records that already carry their redshift; reads the records and never writes them; isotropic (law 0, no mu).
+ * kr_reduce_response_f64: host records, out = nt ne + 4 host doubles (overwritten). */
+int kr_post_response_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_response_model* r,
+                             const kr_limb_law* law, void* d_rays, int64_t n, void* d_out, void* stream);
+int kr_reduce_response_dev_f64(const kr_response_model* r, const void* d_rays, int64_t n, void* d_out, void* stream);
+int kr_reduce_response_f64(const kr_response_model* r, const kr_ray_f64* rays, int64_t n, double* out);
 
 /* ---- orbiting hot spot on the disc (kr_hotspot above has the rule) ------------------------------------------------------------------------------
  * Every entry point validates its arguments before it touches a device: KR_EINVAL (message in kr_last_error) for a null pointer, n < 0, whatever the

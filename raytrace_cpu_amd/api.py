@@ -1678,6 +1678,102 @@ def spectrum_text(res):
     return head + "".join(_path_field(float(e)) + _path_field(float(f)) + "\n" for e, f in zip(res["energy"], res["flux"]))
 
 
+# ---- reverberation response of the disc (include/kr_trace.h, kr_response_model) ----
+def _response_layout(model, words=None):
+    return _layout([("resp", (model.nt, model.spec.ne))], [("on_disc", _rounded), ("used", _rounded), ("bad_angle", _rounded), ("outside", _rounded)], words)
+
+
+def response_words(model):
+    """Length of the buffer of kr_post_response_dev_f64 / kr_reduce_response_dev_f64: [resp (nt x ne, time-major) | on_disc | used | bad_angle | outside]."""
+    return _response_layout(model)
+
+
+def response_from_words(model, words):
+    """The buffer of the response entry points as a dict: resp (nt, ne), the tallies on_disc, used, bad_angle, outside, `energy` (the ne sampling
+    energies of model.spec) and `time`, the centres (j + 0.5) dt of the time rows, counted from t0."""
+    out = _response_layout(model, words)
+    m = model.spec                                          # (scalar libm arithmetic: the ENERGY axis of kr_reverb_response to the bit)
+    out["energy"] = np.array([m.e_min * math.pow(m.de, i + 0.5) if m.log_e else m.e_min + (i + 0.5) * m.de for i in range(m.ne)])
+    out["time"] = (np.arange(model.nt) + 0.5) * model.dt
+    return out
+
+
+def reduce_response(model, rays):
+    """kr_reduce_response_f64: the isotropic energy-time response of host ray records that carry their redshift."""
+    _rays_arg(rays, capi.RAY_F64)
+    out = np.zeros(response_words(model))
+    capi.check(lib(), lib().kr_reduce_response_f64(C.byref(model), _ptr(rays), len(rays), _ptr(out)), "kr_reduce_response")
+    return response_from_words(model, out)
+
+
+def disc_response(imageplane_spec, params, model, limb=None, return_records=False):
+    """The energy-time response of the disc seen on an image plane, resident on the device from start to finish, as the kr_reverb_response app runs it:
+    ImagePlane ctor + redshift_start -> trace (`params` as for the image app: the stored, negated spin) -> redshift + range_phi + the response
+    (kr_post_response_dev_f64).  model: a capi.ResponseModel; limb: None (isotropic) or a limb law as for line_profile.  Only the nt ne + 4 words are read
+    back (and, with return_records, the final records: for tests).  Returns response_from_words(...) plus "stats" (the trace's kr_stats).  The response is
+    per image-plane pixel: multiply by dx dy / D^2 for a flux density."""
+    law = capi.limb_law(limb if limb is not None else "isotropic")
+    sized = 1 <= model.spec.ne <= 4096 and 1 <= model.nt and model.nt * model.spec.ne <= 1 << 24        # (the pass refuses the rest: it gets a null buffer)
+    words, stats, records = _imageplane_run("disc_response", imageplane_spec, params, response_words(model) if sized else 0, lambda L, dev, d_rays, n, d_out: capi.check(
+        L, L.kr_post_response_dev_f64(-1 * imageplane_spec.spin, -1.0, 1, 0, 0, -np.pi, np.pi, C.byref(model), C.byref(law), d_rays, n, d_out, None), "kr_post_response"),
+        return_records)
+    res = response_from_words(model, words)
+    res["stats"] = stats
+    if return_records:
+        res["records"] = records
+    return res
+
+
+def gravitational_time(mass_msun):
+    """G M / c^3 in seconds: the unit of the records' t, of t0 and of dt for a hole of mass_msun solar masses."""
+    return G_CGS * mass_msun * M_SUN_G / C_CGS ** 3
+
+
+def _band_response(resp, widths, band):
+    return (np.asarray(resp, dtype=np.float64)[:, band] * np.asarray(widths, dtype=np.float64)[band]).sum(axis=1)
+
+
+def _transfer(r_band, c_band, refl, dt, freqs):
+    """H(f) = C + refl sinc(f dt) sum_j r[j] exp(-2 pi i f (j + 0.5) dt): the direct continuum at tau = 0 and the top-hat time rows of the response."""
+    tau = (np.arange(r_band.shape[0]) + 0.5) * dt
+    sinc = np.sinc(freqs * dt).reshape((-1,) + (1,) * (r_band.ndim - 1))                   # r_band: (nt,) for one band, (nt, ne) for every energy
+    return c_band + refl * sinc * (np.exp(-2j * np.pi * freqs[:, None] * tau[None, :]) @ r_band)
+
+
+def lag_spectra(resp, dt, widths, freqs, band, ref_band, cont=None, refl=1.0):
+    """The lag-frequency spectrum of an energy band against a reference band, from an energy-time response (host numpy; O(nt ne nf)).
+      r_X[j] = sum_{i in X} resp[j, i] widths[i];   C_X = sum_{i in X} cont[i] widths[i] (0 without cont): the direct continuum, arriving at tau = 0 --
+      the response's t0 is the caller's choice of that instant;   H_X(f) = C_X + refl sinc(f dt) sum_j r_X[j] exp(-2 pi i f (j + 0.5) dt) with the
+      normalised sinc (the top-hat row);   cross = conj(H_ref) H_X;   lag = -arg(cross) / (2 pi f), positive when the band lags the reference.
+    resp: (nt, ne); widths: the ne bin widths; freqs: in 1 / (the unit of dt); band, ref_band: index arrays, slices or masks over the energies.
+    Returns {"lag", "cross", "H_band", "H_ref"}, each of len(freqs)."""
+    freqs = np.atleast_1d(np.asarray(freqs, dtype=np.float64))
+    widths = np.asarray(widths, dtype=np.float64)
+    H = []
+    for X in (band, ref_band):
+        c = float((np.asarray(cont, dtype=np.float64)[X] * widths[X]).sum()) if cont is not None else 0.0
+        H.append(_transfer(_band_response(resp, widths, X), c, refl, dt, freqs))
+    cross = np.conj(H[1]) * H[0]
+    with np.errstate(all="ignore"):
+        lag = -np.angle(cross) / (2 * np.pi * freqs)
+    return {"lag": lag, "cross": cross, "H_band": H[0], "H_ref": H[1]}
+
+
+def lag_energy(resp, dt, widths, freqs, ref_band, cont=None, refl=1.0):
+    """The lag-energy spectrum over a frequency range: lag_spectra with each energy as its own band; the cross-spectra are summed over `freqs` before
+    the argument is taken, then divided by 2 pi mean(freqs).  Returns {"lag" (ne), "cross" (ne), "H" (nf, ne), "H_ref" (nf)}."""
+    freqs = np.atleast_1d(np.asarray(freqs, dtype=np.float64))
+    widths = np.asarray(widths, dtype=np.float64)
+    resp = np.asarray(resp, dtype=np.float64)
+    c_ref = float((np.asarray(cont, dtype=np.float64)[ref_band] * widths[ref_band]).sum()) if cont is not None else 0.0
+    H_ref = _transfer(_band_response(resp, widths, ref_band), c_ref, refl, dt, freqs)
+    c_each = np.asarray(cont, dtype=np.float64) * widths if cont is not None else np.zeros(resp.shape[1])
+    H = _transfer(resp * widths[None, :], c_each[None, :], refl, dt, freqs)                  # (nf, ne)
+    cross = (np.conj(H_ref)[:, None] * H).sum(axis=0)
+    lag = -np.angle(cross) / (2 * np.pi * freqs.mean())
+    return {"lag": lag, "cross": cross, "H": H, "H_ref": H_ref}
+
+
 # ---- orbiting hot spot on the disc (include/kr_trace.h, kr_hotspot) ----
 def keplerian_omega(r, spin):
     """The angular velocity d phi / d t of a prograde circular equatorial orbit at r: 1 / (spin + r^1.5)."""

@@ -12,10 +12,7 @@
 //             mdot = 1e18     accretion rate in g / s
 //             f_col = 1.7     colour-correction factor: I = f_col^-4 B(E, f_col kT_eff)
 //             kt_bins = 400   radial bins of the kT table, log-spaced over [r_isco, r_disc); kT in keV at each bin's centre, so E is in keV
-//   table:    spec_file       two-column text, energy and value per line, energies ascending (the format of the reference's spectrum reader); a
-//                             comma-separated list (no blanks) gives one file per radial zone, innermost first (zones log-spaced over [r_isco, r_disc))
-//             Nzones          optional; must equal the number of files
-//             spec_bins = 512 nodes of the log grid the files are resampled onto (linear in log E), from the first file's first to its last energy
+//   table:    spec_file, Nzones, spec_bins = 512: the rest-frame spectrum per radial zone and the log grid it is resampled onto (rest_spectrum.h)
 // Every key may also be given as --key=value, which takes precedence over the file.  Nx and Ny are read as int, as kr_imageplane_disc_image reads
 // them (before imageplane_app.h: as double, then cast; the same for a key written as a plain integer).
 // Output: TextOutput (width 20, precision 8): three comment rows "# ON_DISC", "# USED", "# BAD_ANGLE" with their counts, then one row per energy:
@@ -31,6 +28,7 @@ using namespace std;
 #include "../host/include/text_output.h"
 #include "emissivity_table.h"
 #include "imageplane_app.h"
+#include "rest_spectrum.h"
 
 namespace {
 
@@ -59,46 +57,6 @@ double novikov_thorne_flux(double r, double a)
     return 3 / (8 * M_PI) * bracket / (x * x * x * x * (x * x * x - 3 * x + 2 * a));
 }
 
-struct TwoColumns { vector<double> energy, value; };
-
-TwoColumns read_spectrum(const string& name)
-{
-    ifstream f(name);
-    if (!f) throw runtime_error("spec_file: cannot open " + name);
-    TwoColumns t;
-    double e, v;
-    while (f >> e >> v) { t.energy.push_back(e); t.value.push_back(v); }
-    if (t.energy.size() < 2) throw runtime_error("spec_file: fewer than two rows in " + name);
-    for (size_t i = 0; i < t.energy.size(); ++i)
-        if (!(t.energy[i] > 0) || (i > 0 && !(t.energy[i] > t.energy[i - 1]))) throw runtime_error("spec_file: the energies must be positive and ascending in " + name);
-    return t;
-}
-
-// the file's value at energy e, linear in log E between its points, the end values beyond them (api.resample_spectrum: numpy.interp)
-double interpolate(const TwoColumns& t, double e)
-{
-    const size_t n = t.energy.size();
-    const double le = log(e);
-    if (le <= log(t.energy[0])) return t.value[0];
-    if (le >= log(t.energy[n - 1])) return t.value[n - 1];
-    size_t k = 0;
-    while (k + 2 < n && le >= log(t.energy[k + 1])) ++k;
-    const double l0 = log(t.energy[k]), l1 = log(t.energy[k + 1]);
-    return t.value[k] + (le - l0) / (l1 - l0) * (t.value[k + 1] - t.value[k]);
-}
-
-vector<string> split_commas(const string& s)
-{
-    vector<string> out;
-    string item;
-    istringstream ss(s);
-    while (getline(ss, item, ',')) {
-        const size_t a = item.find_first_not_of(" \t"), b = item.find_last_not_of(" \t");
-        if (a != string::npos) out.push_back(item.substr(a, b - a + 1));
-    }
-    return out;
-}
-
 }  // namespace
 
 static void program(const krapp::Options& opt)
@@ -125,7 +83,8 @@ static void program(const krapp::Options& opt)
     sm.e_min = e_min; sm.de = de; sm.ne = ne; sm.log_e = log_e ? 1 : 0;
     s.fill_disc(sm);
     sm.f_col = 1;
-    vector<double> kt, S;
+    vector<double> kt;
+    krapp::RestSpectrum rest;
     krapp::EmisTable table;
     if (model_name == "thermal") {
         const double mass = opt.num("mass", 10), mdot = opt.num("mdot", 1e18);
@@ -147,27 +106,8 @@ static void program(const krapp::Options& opt)
         sm.table_kt = kt.data();
         cout << "Novikov-Thorne disc: " << mass << " Msun, " << mdot << " g/s, f_col " << sm.f_col << ", peak kT_eff " << kt_max << " keV" << endl;
     } else {
-        const vector<string> files = split_commas(opt.str("spec_file", ""));
-        if (files.empty()) throw invalid_argument("model = table needs spec_file");
-        if (opt.has("Nzones") && (int) opt.num("Nzones", 1) != (int) files.size()) throw invalid_argument("Nzones: must equal the number of files in spec_file");
-        const int spec_bins = (int) opt.num("spec_bins", 512);
-        if (spec_bins < 2) throw invalid_argument("spec_bins: at least two nodes");
-        vector<TwoColumns> specs;
-        for (const string& f : files) specs.push_back(read_spectrum(f));
-        const double first = specs[0].energy.front(), last = specs[0].energy.back();
-        sm.model = 1;
-        sm.nz = (int32_t) files.size();
-        sm.s_ne = spec_bins;
-        sm.s_e_min = first;
-        sm.s_de = exp(log(last / first) / (spec_bins - 1));
-        S.resize(files.size() * (size_t) spec_bins);
-        for (size_t z = 0; z < files.size(); ++z)
-            for (int k = 0; k < spec_bins; ++k) {
-                double node = first * pow(sm.s_de, k);
-                if (k == spec_bins - 1 && node > last) node = last;
-                S[z * (size_t) spec_bins + (size_t) k] = interpolate(specs[z], node);
-            }
-        sm.s = S.data();
+        rest = krapp::read_rest_spectrum(opt);
+        rest.fill(sm);
         if (!emis_file.empty()) {
             table = krapp::read_emis_table(emis_file);
             sm.table_r_min = table.r_min; sm.table_dr = table.dr; sm.table_logbin = 1;
@@ -175,7 +115,7 @@ static void program(const krapp::Options& opt)
             sm.table_emis = table.emis.data();
             cout << "emissivity table " << emis_file << ": " << sm.table_nr << " bins from r = " << table.r_min << ", ratio " << table.dr << endl;
         }
-        cout << "rest-frame spectrum: " << files.size() << " zone(s), " << spec_bins << " nodes from " << first << ", ratio " << sm.s_de << endl;
+        rest.print();
     }
     const kr_params p = s.params(KR_RK45);
 

@@ -197,6 +197,33 @@ def spectrum_model(model, e_min, de, ne, log_e=False, r_isco=1.0, r_disc=1000.0,
     return m
 
 
+class ResponseModel(C.Structure):
+    """kr_response_model: the energy-time response of a tabulated rest-frame spectrum -- a SpectrumModel of the table kind, the time rows (t0, dt, nt)
+    and an optional source->disc time per radial bin of spec's table (include/kr_trace.h has the per-ray rule).  Keep the arrays alive while the struct
+    is in use (response_model does)."""
+    _fields_ = [("spec", SpectrumModel), ("t0", C.c_double), ("dt", C.c_double), ("table_time", C.POINTER(C.c_double)), ("nt", C.c_int32), ("pad", C.c_int32)]
+
+
+assert C.sizeof(ResponseModel) == 200
+
+
+def response_model(spec, t0, dt, nt, table_time=None):
+    """A ResponseModel.  spec: a SpectrumModel made by spectrum_model("table", ...), copied in (its arrays stay alive with the result); table_time: spec.table_nr
+    source->disc times binned by spec's table_r_min, table_dr, table_logbin -- with a spec that has no table_emis, table_nr is taken from its length."""
+    r = ResponseModel()
+    C.memmove(C.byref(r.spec), C.byref(spec), C.sizeof(SpectrumModel))
+    r._keep = {"spec": getattr(spec, "_keep", None)}
+    r.t0, r.dt, r.nt = t0, dt, nt
+    if table_time is not None:
+        r._keep["table_time"] = np.ascontiguousarray(table_time, dtype=np.float64).copy()
+        r.table_time = r._keep["table_time"].ctypes.data_as(C.POINTER(C.c_double))
+        if not spec.table_emis:
+            r.spec.table_nr = len(r._keep["table_time"])
+        elif len(r._keep["table_time"]) != spec.table_nr:
+            raise ValueError("response_model: table_time must have spec.table_nr values")
+    return r
+
+
 class HotSpot(C.Structure):
     """kr_hotspot: a Gaussian pattern of enhanced emission that moves over the disc -- light curve, image position and spectrogram at nt observer times
     (include/kr_trace.h has the per-ray rule).  A pattern on the disc, good for sigma << r_spot; not a body with a four-velocity of its own."""
@@ -424,6 +451,9 @@ PROTOTYPES = {
     "kr_post_spectrum_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, P(SpectrumModel), P(LimbLaw), _vp, _i64, _vp, _vp]),
     "kr_reduce_spectrum_dev_f64": (_int, [P(SpectrumModel), _vp, _i64, _vp, _vp]),
     "kr_reduce_spectrum_f64": (_int, [P(SpectrumModel), _vp, _i64, _vp]),
+    "kr_post_response_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, P(ResponseModel), P(LimbLaw), _vp, _i64, _vp, _vp]),
+    "kr_reduce_response_dev_f64": (_int, [P(ResponseModel), _vp, _i64, _vp, _vp]),
+    "kr_reduce_response_f64": (_int, [P(ResponseModel), _vp, _i64, _vp]),
     "kr_post_hotspot_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, P(HotSpot), P(LimbLaw), _vp, _i64, _vp, _vp]),
     "kr_reduce_hotspot_dev_f64": (_int, [P(HotSpot), _vp, _i64, _vp, _vp]),
     "kr_reduce_hotspot_f64": (_int, [P(HotSpot), _vp, _i64, _vp]),

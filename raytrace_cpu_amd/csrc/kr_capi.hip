@@ -1191,6 +1191,35 @@ int kr_reduce_spectrum_f64(const kr_spectrum_model* m, const kr_ray_f64* rays, i
     return rc2;
 }
 
+// ---- reverberation response of the disc (kr_response.hip): everything is validated before anything touches a device ----
+int kr_post_response_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_response_model* r, const kr_limb_law* law,
+                             void* d, int64_t n, void* d_out, void* st)
+{
+    int rc = response_validate(r, "kr_post_response");
+    if (rc == KR_OK) rc = spectrum_law_validate(law, motion, "kr_post_response");
+    if (rc != KR_OK) return rc;
+    return on_device(n >= 0 && d_out && (n == 0 || d), "kr_post_response: null argument or negative n",
+                     [&] { return post_response_dev(spin, V, reverse, projradius, motion, lo, hi, r, law, d, n, d_out, (hipStream_t) st); });
+}
+
+int kr_reduce_response_dev_f64(const kr_response_model* r, const void* d, int64_t n, void* d_out, void* st)
+{
+    const int rc = response_validate(r, "kr_reduce_response");
+    if (rc != KR_OK) return rc;
+    return on_device(n >= 0 && d_out && (n == 0 || d), "kr_reduce_response: null argument or negative n", [&] { return reduce_response_dev(r, d, n, d_out, (hipStream_t) st); });
+}
+
+int kr_reduce_response_f64(const kr_response_model* r, const kr_ray_f64* rays, int64_t n, double* out)
+{
+    const int rc = response_validate(r, "kr_reduce_response");
+    if (rc != KR_OK) return rc;
+    if (!out || n < 0 || (n > 0 && !rays)) return invalid("kr_reduce_response: null argument or negative n");
+    std::vector<double> h((size_t) r->nt * r->spec.ne + 4, 0.0);        // out is written only by a call that succeeds
+    const int rc2 = reduce_to_host(rays, n, h.size(), h.data(), [&](void* d, void* d_out) { return reduce_response_dev(r, d, n, d_out, nullptr); });
+    if (rc2 == KR_OK) std::memcpy(out, h.data(), h.size() * sizeof(double));
+    return rc2;
+}
+
 // ---- orbiting hot spot (kr_hotspot.hip): everything is validated before anything touches a device ----
 int kr_post_hotspot_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_hotspot* h, const kr_limb_law* law, void* d,
                             int64_t n, void* d_out, void* st)

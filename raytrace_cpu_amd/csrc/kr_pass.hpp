@@ -157,6 +157,12 @@ int spectrum_law_validate(const kr_limb_law* law, int motion, const char* who);
 int post_spectrum_dev(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_spectrum_model* m, const kr_limb_law* law, void* d,
                       int64_t n, void* d_out, hipStream_t st);
 int reduce_spectrum_dev(const kr_spectrum_model* m, const void* d, int64_t n, void* d_out, hipStream_t st);
+// kr_response.hip: the energy-time response of the reflection spectrum (kr_response_model); the validator refuses what spectrum_validate refuses of
+// spec, then what the struct's comment refuses (the limb law: spectrum_law_validate)
+int response_validate(const kr_response_model* r, const char* who);
+int post_response_dev(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_response_model* r, const kr_limb_law* law, void* d,
+                      int64_t n, void* d_out, hipStream_t st);
+int reduce_response_dev(const kr_response_model* r, const void* d, int64_t n, void* d_out, hipStream_t st);
 // kr_hotspot.hip: the orbiting hot spot (kr_hotspot); the validator refuses what the struct's comment refuses (the limb law: spectrum_law_validate)
 int hotspot_validate(const kr_hotspot* h, const char* who);
 int post_hotspot_dev(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_hotspot* h, const kr_limb_law* law, void* d, int64_t n,
