@@ -959,6 +959,36 @@ int kr_trace_crossings_f64(const kr_params* p, const kr_crossing_spec* spec, kr_
 int kr_reduce_crossing_image_dev_f64(const kr_image_bins* b, int32_t max_crossings, int32_t order, double lo, double hi, const void* d_rays, const void* d_rows,
                                      const void* d_seen, int64_t n, void* d_planes, void* stream);
 
+/* ---- the disc flow "Keplerian, plunging inside the ISCO" -------------------------------------------------------------------------------------
+ * V == KR_V_PLUNGE with motion = 0 selects it in the passes that take V (V == -1 stays the Keplerian observer at every radius).  With the metric's
+ * a = reverse ? -spin : spin and r_ms = kr_kerr_isco(a, +1) -- the float-rounded ISCO the programs use as the disc's inner edge:
+ *   r >= r_ms   the observer, frame and every output bit of V = -1
+ *   r <  r_ms   the gas on the equatorial geodesic that left the circular orbit at r_ms with its energy and angular momentum; u = 1 / r_ms,
+ *               Delta = r r - 2 r + a a, every square root a double one (the host area code, host/include/disc.h, keeps the reference's sqrtf):
+ *                 E_ms = (1 - 2u + a u sqrt(u)) / sqrt(1 - 3u + 2 a u sqrt(u))
+ *                 L_ms = (1 + a a u u - 2 a u sqrt(u)) / sqrt(u (1 - 3u + 2 a u sqrt(u)))
+ *                 u^t  = ((r r + a a + 2 a a / r) E_ms - 2 a L_ms / r) / Delta
+ *                 u^phi = (2 a E_ms / r + (1 - 2 / r) L_ms) / Delta
+ *                 u^r  = -sqrt(max(0, E_ms^2 - 1 + 2 / r + (a a (E_ms^2 - 1) - L_ms^2) / (r r) + 2 (L_ms - a E_ms)^2 / (r r r))),  u^theta = 0
+ *               r_ms, E_ms, L_ms are computed once per launch on the host.  The received energy is the sum over all sixteen (i, j) of g_ij u^i p^j in the
+ *               metric at the record's own (r, theta) (the disc filter admits |z| < 1e-2).  Frame: e_t = u; e2 = (0, 0, 1 / sqrt(rhosq), 0) as for V = -1,
+ *               so mu = |P_th| / E changes only through E; e3 (r-like) and e1 (phi-like) by Gram-Schmidt against the metric, seeds d/dr then d/dphi,
+ *               projections removed before any leg is normalised (v -= (g(seed, e_j) / g(e_j, e_j)) e_j, j in order), each leg divided by
+ *               sqrt(|g(e, e)|) and oriented e3^r > 0, e1^phi > 0 (host/include/gramschmidt_basis.h).  Bad-angle keeps its definition.
+ * Accepted (f64, motion = 0, both reverse values): kr_redshift_f64 / _dev_f64, kr_angles_f64 / _dev_f64, kr_post_image_dev_f64, kr_post_emissivity_dev_f64,
+ * kr_post_emissivity_mu_dev_f64, kr_post_line_dev_f64, kr_post_line_limb_dev_f64, kr_post_spectrum_dev_f64, kr_post_response_dev_f64.  The inner edge of
+ * what is binned stays the r_isco field of the bins or model: a caller who wants the plunging region sets it to the inner radius of choice.
+ * Refused with KR_EINVAL (the message names the function) before anything is launched: the f32 passes, motion = 1, kr_redshift_start_*, kr_post_hotspot_*
+ * (its shear law is Keplerian), the three polarisation entry points (Walker-Penrose writes its own legs), the return map and its batch, the HEALPix map,
+ * kr_post_angdist_*, the V of kr_volume_map and kr_crossing_spec, and every ray-source constructor.  Out of scope: polarisation, a hot spot inside the
+ * ISCO, a plunge radius other than the ISCO, gas off the equatorial plane (the thick disc's surface passes keep V = -1). */
+#define KR_V_PLUNGE (-2.0)
+/* r_ms, E_ms, L_ms of the flow for the metric's a (needs no GPU); KR_EINVAL for a null pointer, |a| > 1 or NaN */
+int kr_plunge_flow(double a, double* r_ms, double* E_ms, double* L_ms);
+/* the flow's four-velocity (u^t, u^r, u^theta, u^phi) on the equatorial plane at r: the geodesic above for r < r_ms, the circular orbit's
+ * (Omega = 1 / (a + r sqrt(r))) for r >= r_ms (needs no GPU); KR_EINVAL as above, and for r that is not finite or not outside the horizon */
+int kr_plunge_velocity(double a, double r, double u[4]);
+
 /* ---- O(N) passes either side of it ----------------------------------------------------------- */
 /* Raytracer<T>::redshift_start(V, reverse, projradius)  raytracer.cpp:342-417 */
 int kr_redshift_start_f64(double spin, double V, int reverse, int projradius, kr_ray_f64* rays, int64_t n);

@@ -540,7 +540,7 @@ def default_image_bins(spec, bins):
     return ib
 
 
-def line_profile(imageplane_spec, params, bins, mode="rays", image_bins=None, limb=None):
+def line_profile(imageplane_spec, params, bins, mode="rays", image_bins=None, limb=None, V=-1.0):
     """The emission line of an image plane, resident on the device from start to finish, as the kr_line_profile app runs it:
     ImagePlane ctor + redshift_start (kr_imageplane_init_emit_dev_f64) -> trace (kr_trace_dev_f64) -> either
       mode="rays":   redshift + range_phi + line bins per ray (kr_post_line_dev_f64), or
@@ -549,6 +549,7 @@ def line_profile(imageplane_spec, params, bins, mode="rays", image_bins=None, li
     `params` as for the image app: the stored (negated) spin, theta / r limits, integrator.  Only the histogram is read back.
     limb (mode="rays" only): None for the isotropic line through kr_post_line_dev_f64, or a limb law of the emission angle in the disc frame --
     (law, coeff) or "isotropic", "laor" (1 + 2.06 mu), "brightening" (log(1 + 1 / mu)) -- through kr_post_line_limb_dev_f64.
+    V: the disc flow of the redshift, -1 Keplerian or capi.V_PLUNGE (plunging inside the ISCO: set bins.r_isco to the inner radius wanted).
     Returns line_from_words(...) plus "stats" (the trace's kr_stats) and, with a limb law, "bad_angle"."""
     if mode not in ("rays", "pixels"):
         raise KrError(f"line_profile: mode must be 'rays' or 'pixels', got {mode!r}")
@@ -568,13 +569,13 @@ def line_profile(imageplane_spec, params, bins, mode="rays", image_bins=None, li
         capi.check(L, L.kr_imageplane_init_emit_dev_f64(C.byref(imageplane_spec), 0, 1, 0.0, 1, 0, d_rays, n, None), "kr_imageplane_init_emit")
         capi.check(L, L.kr_trace_dev_f64(C.byref(params), d_rays, n, None, C.byref(st)), "kr_trace_dev")
         if law is not None:
-            capi.check(L, L.kr_post_line_limb_dev_f64(spin, -1.0, 1, 0, 0, -np.pi, np.pi, C.byref(bins), C.byref(law), d_rays, n, d_line, None), "kr_post_line_limb")
+            capi.check(L, L.kr_post_line_limb_dev_f64(spin, V, 1, 0, 0, -np.pi, np.pi, C.byref(bins), C.byref(law), d_rays, n, d_line, None), "kr_post_line_limb")
         elif mode == "rays":
-            capi.check(L, L.kr_post_line_dev_f64(spin, -1.0, 1, 0, 0, -np.pi, np.pi, C.byref(bins), d_rays, n, d_line, None), "kr_post_line")
+            capi.check(L, L.kr_post_line_dev_f64(spin, V, 1, 0, 0, -np.pi, np.pi, C.byref(bins), d_rays, n, d_line, None), "kr_post_line")
         else:
             ib = image_bins if image_bins is not None else default_image_bins(imageplane_spec, bins)
             d_planes = dev.zeros(image_words(ib) * 8)
-            capi.check(L, L.kr_post_image_dev_f64(spin, -1.0, 1, 0, 0, -np.pi, np.pi, C.byref(ib), d_rays, n, d_planes, None), "kr_post_image")
+            capi.check(L, L.kr_post_image_dev_f64(spin, V, 1, 0, 0, -np.pi, np.pi, C.byref(ib), d_rays, n, d_planes, None), "kr_post_image")
             capi.check(L, L.kr_line_from_image_dev_f64(C.byref(bins), C.byref(ib), d_planes, d_line, None), "kr_line_from_image")
         out = dev.fetch(d_line, nw)
     res = line_from_words(bins, out)
@@ -1590,6 +1591,21 @@ def reduce_spectrum(model, rays):
     return spectrum_from_words(model, out)
 
 
+def plunge_flow(spin):
+    """kr_plunge_flow: (r_ms, E_ms, L_ms) of the disc flow V = capi.V_PLUNGE for the metric's spin (needs no GPU)."""
+    r_ms, E_ms, L_ms = C.c_double(), C.c_double(), C.c_double()
+    capi.check(lib(), lib().kr_plunge_flow(float(spin), C.byref(r_ms), C.byref(E_ms), C.byref(L_ms)), "kr_plunge_flow")
+    return r_ms.value, E_ms.value, L_ms.value
+
+
+def plunge_velocity(spin, r):
+    """kr_plunge_velocity: the flow's four-velocity (u^t, u^r, u^theta, u^phi) on the equatorial plane at r: plunging inside r_ms, the circular orbit's
+    outside (needs no GPU)."""
+    u = (C.c_double * 4)()
+    capi.check(lib(), lib().kr_plunge_velocity(float(spin), float(r), u), "kr_plunge_velocity")
+    return np.array(u[:], dtype=np.float64)
+
+
 def isco_radius(spin):
     """The prograde ISCO of Bardeen, Press & Teukolsky (1972) in double precision (kr_kerr_isco keeps the reference's float-rounded intermediates)."""
     a = float(spin)
@@ -1653,16 +1669,17 @@ def resample_spectrum(energy, counts, spec_bins):
     return float(energy[0]), s_de, np.interp(np.log(nodes), np.log(energy), counts)
 
 
-def disc_spectrum(imageplane_spec, params, model, limb=None, return_records=False):
+def disc_spectrum(imageplane_spec, params, model, limb=None, return_records=False, V=-1.0):
     """The continuum spectrum of the disc seen on an image plane, resident on the device from start to finish, as the kr_disc_spectrum app runs it:
     ImagePlane ctor + redshift_start (kr_imageplane_init_emit_dev_f64) -> trace (kr_trace_dev_f64; `params` as for the image app: the stored, negated
     spin) -> redshift + range_phi + the spectrum (kr_post_spectrum_dev_f64).  model: a capi.SpectrumModel; limb: None (isotropic) or a limb law as for
     line_profile.  Only the ne + 4 words are read back (and, with return_records, the final records: for tests).  Returns spectrum_from_words(...)
-    plus "stats" (the trace's kr_stats).  The flux is per image-plane pixel: multiply by dx dy / D^2 for a flux density."""
+    plus "stats" (the trace's kr_stats).  The flux is per image-plane pixel: multiply by dx dy / D^2 for a flux density.  V: -1 or capi.V_PLUNGE, as for
+    line_profile (model.r_isco is the inner edge)."""
     law = capi.limb_law(limb if limb is not None else "isotropic")
     sized = 1 <= model.ne <= 4096                      # (the pass refuses the rest: it gets a null buffer)
     words, stats, records = _imageplane_run("disc_spectrum", imageplane_spec, params, spectrum_words(model) if sized else 0, lambda L, dev, d_rays, n, d_out: capi.check(
-        L, L.kr_post_spectrum_dev_f64(-1 * imageplane_spec.spin, -1.0, 1, 0, 0, -np.pi, np.pi, C.byref(model), C.byref(law), d_rays, n, d_out, None), "kr_post_spectrum"),
+        L, L.kr_post_spectrum_dev_f64(-1 * imageplane_spec.spin, V, 1, 0, 0, -np.pi, np.pi, C.byref(model), C.byref(law), d_rays, n, d_out, None), "kr_post_spectrum"),
         return_records)
     res = spectrum_from_words(model, words)
     res["stats"] = stats
@@ -1706,16 +1723,16 @@ def reduce_response(model, rays):
     return response_from_words(model, out)
 
 
-def disc_response(imageplane_spec, params, model, limb=None, return_records=False):
+def disc_response(imageplane_spec, params, model, limb=None, return_records=False, V=-1.0):
     """The energy-time response of the disc seen on an image plane, resident on the device from start to finish, as the kr_reverb_response app runs it:
     ImagePlane ctor + redshift_start -> trace (`params` as for the image app: the stored, negated spin) -> redshift + range_phi + the response
     (kr_post_response_dev_f64).  model: a capi.ResponseModel; limb: None (isotropic) or a limb law as for line_profile.  Only the nt ne + 4 words are read
     back (and, with return_records, the final records: for tests).  Returns response_from_words(...) plus "stats" (the trace's kr_stats).  The response is
-    per image-plane pixel: multiply by dx dy / D^2 for a flux density."""
+    per image-plane pixel: multiply by dx dy / D^2 for a flux density.  V: -1 or capi.V_PLUNGE, as for line_profile (model.spec.r_isco is the inner edge)."""
     law = capi.limb_law(limb if limb is not None else "isotropic")
     sized = 1 <= model.spec.ne <= 4096 and 1 <= model.nt and model.nt * model.spec.ne <= 1 << 24        # (the pass refuses the rest: it gets a null buffer)
     words, stats, records = _imageplane_run("disc_response", imageplane_spec, params, response_words(model) if sized else 0, lambda L, dev, d_rays, n, d_out: capi.check(
-        L, L.kr_post_response_dev_f64(-1 * imageplane_spec.spin, -1.0, 1, 0, 0, -np.pi, np.pi, C.byref(model), C.byref(law), d_rays, n, d_out, None), "kr_post_response"),
+        L, L.kr_post_response_dev_f64(-1 * imageplane_spec.spin, V, 1, 0, 0, -np.pi, np.pi, C.byref(model), C.byref(law), d_rays, n, d_out, None), "kr_post_response"),
         return_records)
     res = response_from_words(model, words)
     res["stats"] = stats

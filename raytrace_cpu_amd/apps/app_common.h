@@ -90,6 +90,42 @@ inline std::string arithmetic_choice(const Options& opt)
     return opt.on_command_line("arithmetic") ? opt.str("arithmetic") : arithmetic_from_env();
 }
 
+// The disc flow keys of the programs that bin the disc (include/kr_trace.h, KR_V_PLUNGE): plunge = 0 | 1 and, read with plunge = 1 alone, r_in, the
+// inner edge of what the program bins in place of the ISCO (default: 1.02 x the horizon radius).  plunge = 0: V = -1 and the ISCO, the program and
+// its output files what they were.  With plunge = 1 a text file opens with the rows "# PLUNGE" and "# R_IN", a FITS header carries PLUNGE and R_IN.
+struct DiscFlowKeys {
+    bool plunge = false;
+    double r_in = 0;
+    double V() const { return plunge ? KR_V_PLUNGE : -1.0; }
+    double inner_edge(double r_isco) const { return plunge ? r_in : r_isco; }
+    template <class Text>
+    void write_rows(Text& out) const
+    {
+        if (!plunge) return;
+        out << "# PLUNGE" << 1 << std::endl;
+        out << "# R_IN" << r_in << std::endl;
+    }
+    template <class Fits>
+    void write_keywords(Fits& fits) const
+    {
+        if (!plunge) return;
+        fits.write_keyword("PLUNGE", "Disc flow: Keplerian, plunging inside the ISCO", true);
+        fits.write_keyword("R_IN", "Inner edge of what is binned", r_in);
+    }
+};
+
+inline DiscFlowKeys disc_flow_keys(const Options& opt, double spin)
+{
+    DiscFlowKeys k;
+    k.plunge = opt.flag("plunge", false);
+    if (k.plunge) {
+        const double horizon = kr_kerr_horizon(spin);
+        k.r_in = opt.num("r_in", 1.02 * horizon);
+        if (!(k.r_in > horizon)) throw std::invalid_argument("r_in: the inner edge must lie outside the horizon");
+    }
+    return k;
+}
+
 inline int integrator_code(const std::string& name, int fallback)
 {
     if (name == "euler") return KR_EULER;

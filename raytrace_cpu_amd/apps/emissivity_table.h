@@ -1,7 +1,7 @@
 // apps/emissivity_table.h -- the 7-column table of the reference's emissivity programs (emissivity.cpp:128-147):
 // r, area, count, flux/area, emis/area, <g> = sum_g/count, <t> = sum_t/count per radial bin, TextOutput format
 // (width 20, scientific, 8 digits; the count column as an integer; empty bins give nan from 0/0).  sum_z (optional: a disc with a surface) adds an
-// eighth column, <z> = sum_z/count.
+// eighth column, <z> = sum_z/count.  plunge: the comment rows "# PLUNGE" and "# R_IN" come first.
 #ifndef KR_EMISSIVITY_TABLE_H_
 #define KR_EMISSIVITY_TABLE_H_
 
@@ -19,9 +19,14 @@ namespace krapp {
 
 // raw accumulators in, table out
 inline void write_emissivity_table(const std::string& out_name, int Nr, const double* bin_r, const double* bin_area, const double* count,
-                                   const double* sum_flux, const double* sum_emis, const double* sum_g, const double* sum_t, const double* sum_z = nullptr)
+                                   const double* sum_flux, const double* sum_emis, const double* sum_g, const double* sum_t, const double* sum_z = nullptr, bool plunge = false,
+                                   double r_in = 0)
 {
     TextOutput outfile(out_name.c_str());
+    if (plunge) {                          // the rows of DiscFlowKeys::write_rows (app_common.h)
+        outfile << "# PLUNGE" << 1 << endl;
+        outfile << "# R_IN" << r_in << endl;
+    }
     for (int ir = 0; ir < Nr; ++ir) {
         const long rays = static_cast<long>(count[ir]);
         const double flux = sum_flux[ir] / bin_area[ir];
@@ -54,7 +59,7 @@ inline EmisTable read_emis_table(const std::string& name)
         std::vector<double> cols;
         std::string tok;
         while (ss >> tok) cols.push_back(strtod(tok.c_str(), nullptr));
-        if (cols.empty()) continue;
+        if (cols.empty() || line[line.find_first_not_of(" \t")] == '#') continue;          // (a table written with plunge = 1 opens with comment rows)
         if (cols.size() != 7) throw std::runtime_error("emis_file: expected 7 columns (r, area, rays, flux, emis, redshift, time) in " + name);
         r.push_back(cols[0]);
         t.emis.push_back(cols[4]);

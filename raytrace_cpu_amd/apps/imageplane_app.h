@@ -5,7 +5,8 @@
 //
 // The plane and disc keys, in the order they are read (imageplane_disc_image.cpp:30-66), each as --key=value first, then from the parameter file:
 // outfile, dist, incl, plane_phi0 = 0, spin, r_disc, x0 = -r_disc, xmax = r_disc, Nx, y0 = x0, ymax = xmax, Ny = Nx, img_Nx = Nx, img_Ny = img_Nx,
-// q1 = 3, rb1 = 4, q2 = 3, rb2 = 10, q3 = 3, precision = 100, flip_image = true, integrator (the program's default), rk45_tol = 1e-8, device = 0;
+// q1 = 3, rb1 = 4, q2 = 3, rb2 = 10, q3 = 3, precision = 100, flip_image = true, integrator (the program's default), rk45_tol = 1e-8, device = 0,
+// plunge = 0, r_in (app_common.h, DiscFlowKeys);
 // --arithmetic | KRTRACE_ARITHMETIC and --timing come from the command line only.  Nx, Ny, img_Nx, img_Ny and device are read as int.
 #ifndef KR_APP_IMAGEPLANE_APP_H_
 #define KR_APP_IMAGEPLANE_APP_H_
@@ -44,8 +45,9 @@ struct DiscPlaneSetup {
     AxisInfo ax;
     int Nx, Ny, device;
     bool flip_image, timing;
+    DiscFlowKeys flow;                       // plunge, r_in: kr_imageplane_disc_image, kr_line_profile, kr_disc_spectrum, kr_reverb_response; the rest refuse plunge = 1
 
-    explicit DiscPlaneSetup(const Options& opt)
+    explicit DiscPlaneSetup(const Options& opt, bool takes_plunge = false)
     {
         out_name = opt.str("outfile");
         dist = opt.req("dist");
@@ -72,6 +74,8 @@ struct DiscPlaneSetup {
         ax.dx = (ax.xmax - ax.x0) / Nx;
         ax.dy = (ax.ymax - ax.y0) / Ny;
         r_isco = kerr_isco<double>(spin, +1);
+        flow = disc_flow_keys(opt, spin);
+        if (flow.plunge && !takes_plunge) throw std::invalid_argument("plunge: this program does not take the plunging disc flow");
     }
 
     // a program says this once its own keys are read and checked
@@ -98,7 +102,7 @@ struct DiscPlaneSetup {
     template <class Bins>
     void fill_disc(Bins& b) const
     {
-        b.r_isco = r_isco; b.r_disc = r_disc;
+        b.r_isco = flow.inner_edge(r_isco); b.r_disc = r_disc;
         b.q1 = q1; b.rb1 = rb1; b.q2 = q2; b.rb2 = rb2; b.q3 = q3;
     }
 
@@ -116,7 +120,7 @@ struct DiscPlaneSetup {
     }
 
     // the primary header of the disc-image file
-    DiscImageInfo image_info(long disc_count) const { return {dist, incl, spin, r_isco, r_disc, q1, rb1, q2, rb2, q3, Nx * Ny, disc_count, ax}; }
+    DiscImageInfo image_info(long disc_count) const { return {dist, incl, spin, r_isco, r_disc, q1, rb1, q2, rb2, q3, Nx * Ny, disc_count, ax, flow.plunge, flow.r_in}; }
 };
 
 // The front of the resident pipeline.  The constructor: kr_set_device, the ray count, the ray buffer.  trace(): the accumulator of `words` doubles

@@ -61,7 +61,7 @@ double novikov_thorne_flux(double r, double a)
 
 static void program(const krapp::Options& opt)
 {
-    const krapp::DiscPlaneSetup s(opt);
+    const krapp::DiscPlaneSetup s(opt, true);
     const string emis_file = opt.str("emis_file", "");
     kr_limb_law limb;
     memset(&limb, 0, sizeof limb);
@@ -123,7 +123,7 @@ static void program(const krapp::Options& opt)
     krapp::DiscPlaneRun run(s, plane);
     const int64_t words = (int64_t) ne + 4;
     run.trace(plane, p, words);
-    krapp::check(kr_post_spectrum_dev_f64(-s.spin, -1.0, 1, 0, 0, -1 * M_PI, M_PI, &sm, &limb, run.rays->get(), run.n, run.acc->get(), nullptr), "redshift + range_phi + spectrum");
+    krapp::check(kr_post_spectrum_dev_f64(-s.spin, s.flow.V(), 1, 0, 0, -1 * M_PI, M_PI, &sm, &limb, run.rays->get(), run.n, run.acc->get(), nullptr), "redshift + range_phi + spectrum");
     vector<double> h((size_t) words);
     krapp::check(kr_memcpy_d2h(h.data(), run.acc->get(), words * (int64_t) sizeof(double)), "d2h");
     const double ms_post = run.clock.lap_ms();
@@ -132,6 +132,7 @@ static void program(const krapp::Options& opt)
          << " without an emission angle (bad-angle)" << endl;
     {
         TextOutput outfile(s.out_name);
+        s.flow.write_rows(outfile);
         outfile << "# ON_DISC" << static_cast<long>(h[(size_t) ne]) << endl;
         outfile << "# USED" << static_cast<long>(h[(size_t) ne + 1]) << endl;
         outfile << "# BAD_ANGLE" << static_cast<long>(h[(size_t) ne + 2]) << endl;

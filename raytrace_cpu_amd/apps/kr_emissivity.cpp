@@ -15,6 +15,9 @@
 // between disc_rin and r_disc (KR_STOP_THICKDISC, include/kr_trace.h): the rays stop on it (RK4 / RK45), the gas orbits at the cylindrical radius rho,
 // the histogram is over rho (kr_post_emissivity_surface_dev_f64), the areas are those of the surface's rings (integrate_surface_area, disc.h) and the
 // table gets an eighth column, the mean landing height <z> of the bin.  Not with Nmu.  Without the keys the program and its output are what they were.
+// plunge = 0 | 1, r_in (app_common.h, DiscFlowKeys): with plunge = 1 the gas plunges inside the ISCO (V = KR_V_PLUNGE, include/kr_trace.h), rmin
+// defaults to r_in = 1.02 x the horizon radius and the table (and the mu table) opens with the rows "# PLUNGE" and "# R_IN"; the area column is
+// integrate_disc_area's as ever, whose plunge branch serves the annuli below the ISCO.  Not with a thick disc.  plunge = 0: what the program did.
 //
 // What is NOT taken from the reference: with logbin_r = 0 its bin areas do not compile (`disc_r + dr`, :79); the
 // intended upper edge r + dr (as in emissivity_rd.cpp:88 ... which passes `dr` alone) is used here.
@@ -59,6 +62,8 @@ try {
     if (Nmu > 0 && mu_out_name.empty()) throw invalid_argument("Nmu needs mu_outfile");
     const bool thick = par.key_exists("disc_slope") || par.key_exists("disc_scale");
     const double disc_slope = par.get_parameter<double>("disc_slope", 0), disc_scale = par.get_parameter<double>("disc_scale", 0);
+    const krapp::DiscFlowKeys flow = krapp::disc_flow_keys(opt, spin);         // plunge = 0 | 1, r_in: the gas inside the ISCO, and the table from r_in
+    if (thick && flow.plunge) throw invalid_argument("plunge: the surface of a thick disc keeps the Keplerian flow (no disc_slope / disc_scale)");
     if (thick && Nmu > 0) throw invalid_argument("disc_slope / disc_scale: the incidence angle to a tilted surface is not offered (no Nmu)");
 
     kr_pointsource src;
@@ -77,7 +82,7 @@ try {
 
     // radial bins and their proper areas (host: Nr x 49 small tetrad evaluations)
     const double r_isco = kerr_isco<double>(spin, +1);
-    if (r_min < 0) r_min = r_isco;
+    if (r_min < 0) r_min = flow.inner_edge(r_isco);
     const double disc_rin = par.get_parameter<double>("disc_rin", r_isco);
     const double dr = logbin_r ? exp(log(r_disc / r_min) / Nr) : (r_disc - r_min) / Nr;
     vector<double> bin_r(Nr), bin_area(Nr);
@@ -92,7 +97,7 @@ try {
     memset(&bins, 0, sizeof bins);
     bins.r_min = r_min;
     bins.dr = dr;
-    bins.r_isco = r_isco;
+    bins.r_isco = flow.inner_edge(r_isco);
     bins.gamma = gamma;
     bins.spin = spin;
     bins.num_primary_rays = static_cast<double>(num_primary_rays);
@@ -133,13 +138,13 @@ try {
         hmu.resize((2 * (size_t) Nmu + 1) * (size_t) Nr + 3);
         krapp::DeviceBuffer by_mu((int64_t) (hmu.size() * sizeof(double)));
         by_mu.zero();
-        krapp::check(kr_post_emissivity_mu_dev_f64(spin, -1.0, 0, 0, 0, -1 * M_PI, M_PI, &bins, &mb, rays.get(), n, hist.get(), by_mu.get(), nullptr),
+        krapp::check(kr_post_emissivity_mu_dev_f64(spin, flow.V(), 0, 0, 0, -1 * M_PI, M_PI, &bins, &mb, rays.get(), n, hist.get(), by_mu.get(), nullptr),
                      "range_phi + redshift + histogram by angle");
         krapp::check(kr_memcpy_d2h(hmu.data(), by_mu.get(), (int64_t) (hmu.size() * sizeof(double))), "d2h");
     } else if (thick) {
         krapp::check(kr_post_emissivity_surface_dev_f64(spin, 0, -1 * M_PI, M_PI, &bins, rays.get(), n, hist.get(), nullptr), "range_phi + redshift + surface histogram");
     } else {
-        krapp::check(kr_post_emissivity_dev_f64(spin, -1.0, 0, 0, 0, -1 * M_PI, M_PI, &bins, rays.get(), n, hist.get(), nullptr), "range_phi + redshift + histogram");
+        krapp::check(kr_post_emissivity_dev_f64(spin, flow.V(), 0, 0, 0, -1 * M_PI, M_PI, &bins, rays.get(), n, hist.get(), nullptr), "range_phi + redshift + histogram");
     }
     vector<double> h(thick ? 6 * (size_t) Nr + 4 : 5 * (size_t) Nr + 1);
     krapp::check(kr_memcpy_d2h(h.data(), hist.get(), (int64_t) (h.size() * sizeof(double))), "d2h");
@@ -147,13 +152,14 @@ try {
 
     // ---- the divisions of emissivity.cpp:128-134 and the table ---------------------------------------------------------
     krapp::write_emissivity_table(out_name, Nr, bin_r.data(), bin_area.data(), &h[0], &h[Nr], &h[2 * (size_t) Nr], &h[3 * (size_t) Nr], &h[4 * (size_t) Nr],
-                                  thick ? &h[5 * (size_t) Nr] : nullptr);
+                                  thick ? &h[5 * (size_t) Nr] : nullptr, flow.plunge, flow.r_in);
 
     if (Nmu > 0) {
         // count2 / count per mu bin (count: the radial histogram's, so a bin's bad-angle rays are missing from its row) and the mean mu over the
         // rays that have an angle (the row sum of count2); 0/0 -> NaN in empty bins
         const size_t plane = (size_t) Nr * Nmu;
         TextOutput mu_out(mu_out_name.c_str());
+        flow.write_rows(mu_out);
         for (int ir = 0; ir < Nr; ++ir) {
             double row = 0;
             for (int im = 0; im < Nmu; ++im) row += hmu[(size_t) ir * Nmu + im];

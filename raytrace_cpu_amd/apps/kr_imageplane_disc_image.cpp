@@ -24,9 +24,10 @@ using namespace std;
 
 static void program(const krapp::Options& opt)
 {
-    const krapp::DiscPlaneSetup s(opt);
+    const krapp::DiscPlaneSetup s(opt, true);
     const bool thick = opt.has("disc_slope") || opt.has("disc_scale");
     const double disc_slope = opt.num("disc_slope", 0), disc_scale = opt.num("disc_scale", 0);
+    if (thick && s.flow.plunge) throw invalid_argument("plunge: the surface of a thick disc keeps the Keplerian flow (no disc_slope / disc_scale)");
     s.print_isco();
 
     const kr_imageplane plane = s.plane();
@@ -45,7 +46,7 @@ static void program(const krapp::Options& opt)
     if (thick)
         krapp::check(kr_post_image_surface_dev_f64(-s.spin, 1, -1 * M_PI, M_PI, &bins, rays, run.n, planes, nullptr), "redshift + range_phi + image planes of the surface");
     else
-        krapp::check(kr_post_image_dev_f64(-s.spin, -1.0, 1, 0, 0, -1 * M_PI, M_PI, &bins, rays, run.n, planes, nullptr), "redshift + range_phi + image planes");
+        krapp::check(kr_post_image_dev_f64(-s.spin, s.flow.V(), 1, 0, 0, -1 * M_PI, M_PI, &bins, rays, run.n, planes, nullptr), "redshift + range_phi + image planes");
     krapp::PinnedDoubles h(7 * npix + 1);     // 0.94 GB at 4096^2: page-locked, or the read-back runs at a tenth of the PCIe rate
     krapp::check(kr_memcpy_d2h(h.data(), planes, h.size() * (int64_t) sizeof(double)), "d2h");
     const double ms_post = run.clock.lap_ms();

@@ -34,7 +34,7 @@ using namespace std;
 
 static void program(const krapp::Options& opt)
 {
-    const krapp::DiscPlaneSetup s(opt);
+    const krapp::DiscPlaneSetup s(opt, true);
     const double line_en = opt.num("line_en", 6.4), e_min = opt.num("e_min", 1), e_max = opt.num("e_max", 10), g_index = opt.num("g_index", 3);
     const bool log_e = opt.num("log_e", 0) != 0;
     int ne;
@@ -86,14 +86,14 @@ static void program(const krapp::Options& opt)
     run.trace(plane, p, words);
     void *rays = run.rays->get(), *line = run.acc->get();
     if (with_limb) {
-        krapp::check(kr_post_line_limb_dev_f64(-s.spin, -1.0, 1, 0, 0, -1 * M_PI, M_PI, &lb, &limb, rays, run.n, line, nullptr), "redshift + range_phi + limb-law line");
+        krapp::check(kr_post_line_limb_dev_f64(-s.spin, s.flow.V(), 1, 0, 0, -1 * M_PI, M_PI, &lb, &limb, rays, run.n, line, nullptr), "redshift + range_phi + limb-law line");
     } else if (mode == "rays") {
-        krapp::check(kr_post_line_dev_f64(-s.spin, -1.0, 1, 0, 0, -1 * M_PI, M_PI, &lb, rays, run.n, line, nullptr), "redshift + range_phi + line");
+        krapp::check(kr_post_line_dev_f64(-s.spin, s.flow.V(), 1, 0, 0, -1 * M_PI, M_PI, &lb, rays, run.n, line, nullptr), "redshift + range_phi + line");
     } else {
         const int64_t npix = (int64_t) ib.img_nx * ib.img_ny;
         krapp::DeviceBuffer planes((7 * npix + 1) * (int64_t) sizeof(double));
         planes.zero();
-        krapp::check(kr_post_image_dev_f64(-s.spin, -1.0, 1, 0, 0, -1 * M_PI, M_PI, &ib, rays, run.n, planes.get(), nullptr), "redshift + range_phi + image planes");
+        krapp::check(kr_post_image_dev_f64(-s.spin, s.flow.V(), 1, 0, 0, -1 * M_PI, M_PI, &ib, rays, run.n, planes.get(), nullptr), "redshift + range_phi + image planes");
         krapp::check(kr_line_from_image_dev_f64(&lb, &ib, planes.get(), line, nullptr), "line from image planes");
         krapp::check(kr_synchronize(nullptr), "sync");
     }
@@ -106,6 +106,7 @@ static void program(const krapp::Options& opt)
     if (with_limb) cout << static_cast<long>(h[nb * 2 + 2]) << " rays on the disc have no emission angle (bad-angle)" << endl;
     {
         TextOutput outfile(s.out_name);
+        s.flow.write_rows(outfile);
         if (with_limb) {
             outfile << "# LIMB" << limb.law << endl;
             outfile << "# LIMBCOEF" << limb.coeff << endl;

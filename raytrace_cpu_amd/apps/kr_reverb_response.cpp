@@ -28,7 +28,7 @@ using namespace std;
 
 static void program(const krapp::Options& opt)
 {
-    const krapp::DiscPlaneSetup s(opt);
+    const krapp::DiscPlaneSetup s(opt, true);
     const string emis_file = opt.str("emis_file", "");
     kr_limb_law limb;
     memset(&limb, 0, sizeof limb);
@@ -71,7 +71,7 @@ static void program(const krapp::Options& opt)
     krapp::DiscPlaneRun run(s, plane);
     const int64_t cells = (int64_t) nt * ne, words = cells + 4;
     run.trace(plane, p, words);
-    krapp::check(kr_post_response_dev_f64(-s.spin, -1.0, 1, 0, 0, -1 * M_PI, M_PI, &rm, &limb, run.rays->get(), run.n, run.acc->get(), nullptr), "redshift + range_phi + response");
+    krapp::check(kr_post_response_dev_f64(-s.spin, s.flow.V(), 1, 0, 0, -1 * M_PI, M_PI, &rm, &limb, run.rays->get(), run.n, run.acc->get(), nullptr), "redshift + range_phi + response");
     vector<double> h((size_t) words);
     krapp::check(kr_memcpy_d2h(h.data(), run.acc->get(), words * (int64_t) sizeof(double)), "d2h");
     const double ms_post = run.clock.lap_ms();
@@ -92,6 +92,7 @@ static void program(const krapp::Options& opt)
         fits.write_keyword("SPIN", "Black hole spin", s.spin);
         fits.write_keyword("ISCO", "Innermost stable circular orbit", s.r_isco);
         fits.write_keyword("RDISC", "Maximum radius of disc", s.r_disc);
+        s.flow.write_keywords(fits);
         fits.write_keyword("NRAYS", "Number of rays", static_cast<long>(run.n));
         fits.write_keyword("ON_DISC", "Rays hitting disc", on_disc);
         fits.write_keyword("USED", "Rays with an emissivity and a delay", used);

@@ -21,6 +21,9 @@ FLAG_FAST_MATH = 1
 FLAG_HYBRID = 2
 FLAG_RK45_ITERATE_ALL = 4
 
+# the value of V that selects the disc flow "Keplerian, plunging inside the ISCO" in the passes that take it (KR_V_PLUNGE, include/kr_trace.h)
+V_PLUNGE = -2.0
+
 # Ray<double> / Ray<float>  (reference src/raytracer/raytracer.h:65-78)
 _F64 = [(n, "<f8") for n in ("t", "r", "theta", "phi", "pt", "pr", "ptheta", "pphi", "k", "h", "Q", "emit", "redshift")]
 _I32 = [(n, "<i4") for n in ("steps", "status", "rdot_sign", "thetadot_sign", "rdot_flips", "equatorial_crossings")]
@@ -344,6 +347,8 @@ PROTOTYPES = {
     "kr_kerr_horizon": (_dbl, [_dbl]),
     "kr_kerr_isco": (_dbl, [_dbl, _int]),
     "kr_disc_velocity": (_dbl, [_dbl, _dbl, _int]),
+    "kr_plunge_flow": (_int, [_dbl, P(_dbl), P(_dbl), P(_dbl)]),
+    "kr_plunge_velocity": (_int, [_dbl, _dbl, P(_dbl)]),
     "kr_pointsource_count": (_i64, [P(PointSourceSpec), P(_i32), P(_i32)]),
     "kr_imageplane_count": (_i64, [P(ImagePlaneSpec), P(_i32), P(_i32)]),
     "kr_bundles_count": (_i64, [P(ImagePlaneSpec), P(_i32), P(_i32)]),

@@ -24,14 +24,16 @@ namespace {
 // never lowers the occupancy.  100 x 10 bins take 2 604 words, 30 x 64 take 4 024.
 constexpr int kMuLdsWords = 6144;
 
+// PLUNGE: the disc flow of KR_V_PLUNGE (DiscFlow, kr_post_device.hpp); the host picks the instance from V
+template <bool PLUNGE>
 __global__ void __launch_bounds__(kBlock)
-angles_kernel(const kr_ray_f64* __restrict__ rays, long long n, double spin, double V, int reverse, int projradius, double* __restrict__ out)
+angles_kernel(const kr_ray_f64* __restrict__ rays, long long n, double spin, double V, int reverse, int projradius, double* __restrict__ out, DiscFlow<PLUNGE> fl)
 {
     KR_GRID_STRIDE(i, n) {
         const kr_ray_f64* ray = &rays[i];
         double mu = __builtin_nan(""), chi = __builtin_nan("");
         if (ray->steps > 0) {
-            const Frame f = frame_value(geodesic_start_of(ray), spin, V, reverse, projradius);
+            const Frame f = frame_value<PLUNGE>(geodesic_start_of(ray), spin, V, reverse, projradius, fl);
             mu = frame_mu(f);
             chi = frame_chi(f);
         }
@@ -42,10 +44,10 @@ angles_kernel(const kr_ray_f64* __restrict__ rays, long long n, double spin, dou
 
 // d_mu layout: [count2(nr nmu) | flux2(nr nmu) | sum_mu(nr) | disc_count, binned, bad_angle].  The radial histogram takes exactly what
 // emissivity_accumulate gives it (bad-angle rays included); a ray that it binned radially goes on into (ir, im), or moves only bad_angle.
-template <bool USE_LDS>
+template <bool USE_LDS, bool PLUNGE>
 __global__ void __launch_bounds__(kBlock)
 post_emissivity_mu_kernel(kr_ray_f64* __restrict__ rays, long long n, double spin, double V, int reverse, int projradius, double lo, double hi, kr_emis_bins b,
-                          int nmu, double* __restrict__ hist, double* __restrict__ out_mu)
+                          int nmu, double* __restrict__ hist, double* __restrict__ out_mu, DiscFlow<PLUNGE> fl)
 {
     extern __shared__ double lds[];
     const int nr = b.nr;
@@ -63,7 +65,7 @@ post_emissivity_mu_kernel(kr_ray_f64* __restrict__ rays, long long n, double spi
         const kr_ray_f64 v = geodesic_of(ray);
         const int steps = ray->steps;
         wrap_phi(ray, steps, lo, hi);
-        const Frame f = frame_value(v, spin, V, reverse, projradius);
+        const Frame f = frame_value<PLUNGE>(v, spin, V, reverse, projradius, fl);
         const double g = frame_redshift(f, v.emit, reverse);
         ray->redshift = g;
         emissivity_accumulate(acc, b, log_dr, steps, v.r, v.theta, g, ray->t);
@@ -122,8 +124,10 @@ int emissivity_mu_validate(const kr_emis_bins* b, const kr_mu_bins* mb, const ch
 int angles_dev(double spin, double V, int reverse, int projradius, const void* d, int64_t n, void* d_angles, hipStream_t st)
 {
     if (n <= 0) return KR_OK;
-    hipLaunchKernelGGL(angles_kernel, dim3(grid_for(n, kBlock, kCapStream)), dim3(kBlock), 0, st, (const kr_ray_f64*) d, (long long) n, spin, V, reverse, projradius,
-                       (double*) d_angles);
+    for_flow(spin, V, reverse, [&](auto flow) {
+        hipLaunchKernelGGL(angles_kernel<decltype(flow)::plunge>, dim3(grid_for(n, kBlock, kCapStream)), dim3(kBlock), 0, st, (const kr_ray_f64*) d, (long long) n, spin, V, reverse,
+                           projradius, (double*) d_angles, flow.arg);
+    });
     KR_LAUNCH_CHECK();
     return KR_OK;
 }
@@ -133,8 +137,8 @@ int post_emissivity_mu_dev(double spin, double V, int reverse, int projradius, d
 {
     if (n <= 0) return KR_OK;
     const int64_t words = (int64_t) 5 * b->nr + 1 + (2 * (int64_t) mb->nmu + 1) * b->nr + 3;
-    KR_LAUNCH_LDS_OR_GLOBAL(post_emissivity_mu_kernel, words <= kMuLdsWords, grid_for(n, kBlock, kCapHist), (size_t) words * sizeof(double), st, (kr_ray_f64*) d,
-                            (long long) n, spin, V, reverse, projradius, lo, hi, *b, mb->nmu, (double*) d_hist, (double*) d_mu);
+    KR_LAUNCH_LDS_OR_GLOBAL_FLOW(post_emissivity_mu_kernel, spin, V, reverse, words <= kMuLdsWords, grid_for(n, kBlock, kCapHist), (size_t) words * sizeof(double), st,
+                                 (kr_ray_f64*) d, (long long) n, spin, V, reverse, projradius, lo, hi, *b, mb->nmu, (double*) d_hist, (double*) d_mu);
     return KR_OK;
 }
 

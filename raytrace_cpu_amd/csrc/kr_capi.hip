@@ -435,6 +435,45 @@ double kr_kerr_isco(double a, int sign)
 // src/include/kerr.h:35-38
 double kr_disc_velocity(double r, double a, int sign) { return 1 / (a + sign * std::pow(r, 3. / 2.)); }
 
+// ---- the disc flow of KR_V_PLUNGE (include/kr_trace.h): what the passes hand their kernels, and its four-velocity on the equatorial plane in the
+//      expressions of kr_post_device.hpp (plunge_velocity inside r_ms; the e_t of redshift_value with V = 1 / (a + r sqrt(r)) outside) ----
+int kr_plunge_flow(double a, double* r_ms, double* E_ms, double* L_ms)
+{
+    if (!r_ms || !E_ms || !L_ms) return invalid("kr_plunge_flow: null argument");
+    if (!(std::fabs(a) <= 1)) return invalid("kr_plunge_flow: |a| must not exceed 1");
+    const DiscFlow<true> fl = plunge_flow(a, 0);
+    *r_ms = fl.r_ms; *E_ms = fl.E_ms; *L_ms = fl.L_ms;
+    return KR_OK;
+}
+
+int kr_plunge_velocity(double a, double r, double u[4])
+{
+    if (!u) return invalid("kr_plunge_velocity: null argument");
+    if (!(std::fabs(a) <= 1)) return invalid("kr_plunge_velocity: |a| must not exceed 1");
+    if (!std::isfinite(r) || !(r > kr_kerr_horizon(a))) return invalid("kr_plunge_velocity: r must be finite and outside the horizon");
+    const DiscFlow<true> fl = plunge_flow(a, 0);
+    if (r < fl.r_ms) {
+        const double delta = r * r - 2 * r + a * a;
+        const double k = fl.E_ms, h = fl.L_ms;
+        const double rad = k * k - 1 + 2 / r + (a * a * (k * k - 1) - h * h) / (r * r) + 2 * (h - a * k) * (h - a * k) / (r * r * r);
+        u[0] = ((r * r + a * a + 2 * a * a / r) * k - 2 * a * h / r) / delta;
+        u[1] = -1 * std::sqrt(rad > 0 ? rad : 0.0);
+        u[2] = 0;
+        u[3] = (2 * a * k / r + (1 - 2 / r) * h) / delta;
+    } else {
+        // the metric on the plane itself (sin = 1, cos = 0), kerr_metric's expressions
+        const double rhosq = r * r, delta = r * r - 2 * r + a * a;
+        const double sigmasq = (r * r + a * a) * (r * r + a * a) - a * a * delta;
+        const double e2nu = rhosq * delta / sigmasq, e2psi = sigmasq / rhosq, omega = 2 * a * r / sigmasq;
+        const double V = 1 / (a + r * std::sqrt(r));
+        u[0] = (1 / std::sqrt(e2nu)) / std::sqrt(1 - (V - omega) * (V - omega) * e2psi / e2nu);
+        u[1] = 0;
+        u[2] = 0;
+        u[3] = (1 / std::sqrt(e2nu)) * V / std::sqrt(1 - (V - omega) * (V - omega) * e2psi / e2nu);
+    }
+    return KR_OK;
+}
+
 // nRays is the int-truncated PRODUCT of doubles (pointsource.cpp:12), n_cosalpha / n_beta the truncated factors (:16-17)
 int64_t kr_pointsource_count(const kr_pointsource* s, int32_t* n_cosalpha, int32_t* n_beta)
 {
@@ -708,34 +747,44 @@ int kr_trace_observe_f64(const kr_params* p, const kr_volume_map* m, const kr_ob
 // pointers, for Raytracer<double> and for Raytracer<float> (kr_ray_f32 records, float arithmetic; the scalars are float values carried in
 // doubles).  The f64 host form copies back only the written field(s) of an attached array, the f32 host form the whole 84-byte record.
 #define KR_LIST(...) __VA_ARGS__
-#define KR_PASS_FORMS(name, T, f32, params, args, staging)                                                            \
+// guard64 / guard32: an int expression over the pass's arguments and `who` (the function's name), evaluated before anything else; a non-zero value is
+// returned (KR_V_PLUNGE, include/kr_trace.h)
+#define KR_PASS_FORMS(name, T, f32, params, args, staging, guard)                                                     \
     int kr_##name##_dev_##T(KR_LIST params, void* d, int64_t n, void* st)                                             \
     {                                                                                                                 \
+        const char* who = f32 ? "kr_" #name "_f32" : "kr_" #name;                                                     \
+        if (const int rc = (guard)) return rc;                                                                        \
         return on_device(true, nullptr, [&] { return name##_dev(KR_LIST args, d, n, (hipStream_t) st, f32); });       \
     }                                                                                                                 \
     int kr_##name##_##T(KR_LIST params, kr_ray_##T* rays, int64_t n)                                                  \
     {                                                                                                                 \
+        const char* who = f32 ? "kr_" #name "_f32" : "kr_" #name;                                                     \
+        if (const int rc = (guard)) return rc;                                                                        \
         return with_staged_rays(rays, n, sizeof(kr_ray_##T), staging, nullptr,                                        \
                                 [&](void* d) { return name##_dev(KR_LIST args, d, n, nullptr, f32); });               \
     }
-#define KR_PASS(name, params, args, field, words)                                                       \
-    KR_PASS_FORMS(name, f64, false, params, args, updates_field(offsetof(kr_ray_f64, field), words))    \
-    KR_PASS_FORMS(name, f32, true, params, args, kUpdates)
+#define KR_PASS(name, params, args, field, words, guard64, guard32)                                              \
+    KR_PASS_FORMS(name, f64, false, params, args, updates_field(offsetof(kr_ray_f64, field), words), guard64)    \
+    KR_PASS_FORMS(name, f32, true, params, args, kUpdates, guard32)
+#define KR_NO_GUARD ((void) who, (int) KR_OK)
 
-KR_PASS(redshift_start, (double spin, double V, int reverse, int projradius), (spin, V, reverse, projradius), emit, 1)
-KR_PASS(redshift, (double spin, double V, int reverse, int projradius, int motion), (spin, V, reverse, projradius, motion), redshift, 1)
-KR_PASS(redshift_dest, (double spin, int reverse), (spin, reverse), redshift, 1)
-KR_PASS(range_phi, (double lo, double hi), (lo, hi), phi, 1)
-KR_PASS(calculate_momentum, (double spin), (spin), pt, 4)
+KR_PASS(redshift_start, (double spin, double V, int reverse, int projradius), (spin, V, reverse, projradius), emit, 1, refuse_plunge(V, who), refuse_plunge(V, who))
+KR_PASS(redshift, (double spin, double V, int reverse, int projradius, int motion), (spin, V, reverse, projradius, motion), redshift, 1, accept_plunge(V, motion, who),
+        refuse_plunge(V, who))
+KR_PASS(redshift_dest, (double spin, int reverse), (spin, reverse), redshift, 1, KR_NO_GUARD, KR_NO_GUARD)
+KR_PASS(range_phi, (double lo, double hi), (lo, hi), phi, 1, KR_NO_GUARD, KR_NO_GUARD)
+KR_PASS(calculate_momentum, (double spin), (spin), pt, 4, KR_NO_GUARD, KR_NO_GUARD)
 
 // ---- sources -----------------------------------------------------------------------------------------------
 int kr_pointsource_init_dev_f64(const kr_pointsource* s, void* d, int64_t n, void* st)
 {
+    if (s && refuse_plunge(s->V, "kr_pointsource_init")) return KR_EINVAL;
     return on_device(s, "kr_pointsource_init: null spec", [&] { return pointsource_init_dev(s, d, n, 0, 1, (hipStream_t) st); });
 }
 int kr_pointsource_init_f64(const kr_pointsource* s, kr_ray_f64* rays, int64_t n)
 {
     if (!s) return invalid("kr_pointsource_init: null spec");
+    if (refuse_plunge(s->V, "kr_pointsource_init")) return KR_EINVAL;
     return with_staged_rays(rays, n, sizeof(kr_ray_f64), kConstructs, nullptr, [&](void* d) { return pointsource_init_dev(s, d, n, 0, 1, nullptr); });
 }
 
@@ -753,6 +802,7 @@ int kr_imageplane_init_f64(const kr_imageplane* s, kr_ray_f64* rays, int64_t n)
 // of R is (first = r, stride = R, count = ceil((total - r) / R)); no rank ever materialises another rank's rays.
 int kr_pointsource_init_strided_dev_f64(const kr_pointsource* s, int64_t first, int64_t stride, void* d, int64_t count, void* st)
 {
+    if (s && refuse_plunge(s->V, "kr_pointsource_init_strided")) return KR_EINVAL;
     return on_device(s, "kr_pointsource_init: null spec", [&] { return pointsource_init_dev(s, d, count, first, stride, (hipStream_t) st); });
 }
 int kr_imageplane_init_strided_dev_f64(const kr_imageplane* s, int64_t first, int64_t stride, void* d, int64_t count, void* st)
@@ -762,6 +812,7 @@ int kr_imageplane_init_strided_dev_f64(const kr_imageplane* s, int64_t first, in
 // fused pipeline ends (device-resident callers): source constructor + redshift_start() in one pass ...
 int kr_pointsource_init_emit_dev_f64(const kr_pointsource* s, int64_t first, int64_t stride, double V, int reverse, int projradius, void* d, int64_t count, void* st)
 {
+    if (refuse_plunge(V, "kr_pointsource_init_emit") || (s && refuse_plunge(s->V, "kr_pointsource_init_emit"))) return KR_EINVAL;
     return on_device(s, "kr_pointsource_init_emit: null spec",
                      [&] { return pointsource_init_emit_dev(s, d, count, first, stride, V, reverse, projradius, (hipStream_t) st); });
 }
@@ -770,16 +821,20 @@ int kr_pointsource_init_emit_batch_dev_f64(int32_t count, const kr_pointsource* 
     if (count < 0 || (count > 0 && (!s || !d || !n))) return invalid("kr_pointsource_init_emit_batch: null argument");
     for (int32_t i = 0; i < count; i++)
         if (n[i] > 0 && !d[i]) return invalid("kr_pointsource_init_emit_batch: null ray buffer");
+    for (int32_t i = 0; i < count; i++)
+        if (refuse_plunge(s[i].V, "kr_pointsource_init_emit_batch") || (V && refuse_plunge(V[i], "kr_pointsource_init_emit_batch"))) return KR_EINVAL;
     return on_device(true, nullptr, [&] { return pointsource_init_emit_batch_dev(count, s, V, reverse, projradius, d, n, (hipStream_t) st); });
 }
 int kr_imageplane_init_emit_dev_f64(const kr_imageplane* s, int64_t first, int64_t stride, double V, int reverse, int projradius, void* d, int64_t count, void* st)
 {
+    if (refuse_plunge(V, "kr_imageplane_init_emit")) return KR_EINVAL;
     return on_device(s, "kr_imageplane_init_emit: null spec",
                      [&] { return imageplane_init_emit_dev(s, d, count, first, stride, 1, -1 * s->spin, V, reverse, projradius, (hipStream_t) st); });
 }
 int kr_imageplane_init_emit_runs_dev_f64(const kr_imageplane* s, int64_t first, int64_t stride, int64_t run, double V, int reverse, int projradius, void* d,
                                          int64_t count, void* st)
 {
+    if (refuse_plunge(V, "kr_imageplane_init_emit_runs")) return KR_EINVAL;
     return on_device(s, "kr_imageplane_init_emit_runs: null spec",
                      [&] { return imageplane_init_emit_dev(s, d, count, first, stride, run, -1 * s->spin, V, reverse, projradius, (hipStream_t) st); });
 }
@@ -787,12 +842,14 @@ int kr_imageplane_init_emit_runs_dev_f64(const kr_imageplane* s, int64_t first, 
 int kr_post_emissivity_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_emis_bins* b, void* d, int64_t n,
                                void* d_hist, void* st)
 {
+    if (accept_plunge(V, motion, "kr_post_emissivity")) return KR_EINVAL;
     return on_device(b && d_hist, "kr_post_emissivity: null argument",
                      [&] { return post_emissivity_dev(spin, V, reverse, projradius, motion, lo, hi, b, d, n, d_hist, (hipStream_t) st); });
 }
 int kr_post_image_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_image_bins* b, void* d, int64_t n,
                           void* d_planes, void* st)
 {
+    if (accept_plunge(V, motion, "kr_post_image")) return KR_EINVAL;
     return on_device(b && d_planes, "kr_post_image: null argument",
                      [&] { return post_image_dev(spin, V, reverse, projradius, motion, lo, hi, b, d, n, d_planes, (hipStream_t) st); });
 }
@@ -899,7 +956,8 @@ int kr_reduce_return_map_dev_f64(const kr_return_map* m, const void* d, int64_t 
 int kr_post_return_map_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_return_map* m, void* d, int64_t n,
                                void* d_out, void* st)
 {
-    const int rc = return_map_validate(m, "kr_post_return_map");
+    int rc = refuse_plunge(V, "kr_post_return_map");
+    if (rc == KR_OK) rc = return_map_validate(m, "kr_post_return_map");
     if (rc != KR_OK) return rc;
     return on_device(n >= 0 && d_out && (n == 0 || d), "kr_post_return_map: null argument or negative n",
                      [&] { return post_return_map_dev(spin, V, reverse, projradius, motion, lo, hi, m, d, n, d_out, (hipStream_t) st); });
@@ -908,6 +966,7 @@ int kr_post_return_map_dev_f64(double spin, double V, int reverse, int projradiu
 int kr_post_return_map_batch_dev_f64(int32_t count, double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_return_map* m,
                                      void* const* d, const int64_t* n, void* const* d_out, void* st)
 {
+    if (refuse_plunge(V, "kr_post_return_map_batch")) return KR_EINVAL;
     if (count < 0 || (count > 0 && (!m || !d || !n || !d_out))) return invalid("kr_post_return_map_batch: null argument or negative count");
     for (int32_t i = 0; i < count; i++) {
         const int rc = return_map_validate(&m[i], "kr_post_return_map_batch");
@@ -971,7 +1030,8 @@ int kr_healpix_init_f64(const kr_healpix_source* s, kr_ray_f64* rays, int64_t n)
 int kr_post_healpix_map_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_healpix_map* m, void* d, int64_t n,
                                 int64_t first, int64_t stride, void* d_out, void* st)
 {
-    const int rc = healpix_map_validate(m, n, first, stride, "kr_post_healpix_map");
+    int rc = refuse_plunge(V, "kr_post_healpix_map");
+    if (rc == KR_OK) rc = healpix_map_validate(m, n, first, stride, "kr_post_healpix_map");
     if (rc != KR_OK) return rc;
     return on_device(d_out && (n == 0 || d), "kr_post_healpix_map: null argument",
                      [&] { return post_healpix_map_dev(spin, V, reverse, projradius, motion, lo, hi, m, d, n, first, stride, d_out, (hipStream_t) st); });
@@ -1065,7 +1125,8 @@ int kr_reduce_angdist_dev_f64(const kr_angdist_spec* sp, const void* d, int64_t 
 int kr_post_angdist_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_angdist_spec* sp, void* d, int64_t n,
                             void* d_out, void* st)
 {
-    const int rc = angdist_validate(sp, "kr_post_angdist");
+    int rc = refuse_plunge(V, "kr_post_angdist");
+    if (rc == KR_OK) rc = angdist_validate(sp, "kr_post_angdist");
     if (rc != KR_OK) return rc;
     return on_device(n >= 0 && d_out && (n == 0 || d), "kr_post_angdist: null argument or negative n",
                      [&] { return post_angdist_dev(spin, V, reverse, projradius, motion, lo, hi, sp, d, n, d_out, (hipStream_t) st); });
@@ -1089,7 +1150,8 @@ int kr_reduce_line_dev_f64(const kr_line_bins* b, const void* d, int64_t n, void
 int kr_post_line_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_line_bins* b, void* d, int64_t n,
                          void* d_line, void* st)
 {
-    const int rc = line_validate(b, "kr_post_line");
+    int rc = accept_plunge(V, motion, "kr_post_line");
+    if (rc == KR_OK) rc = line_validate(b, "kr_post_line");
     if (rc != KR_OK) return rc;
     return on_device(d_line && (n <= 0 || d), "kr_post_line: null argument",
                      [&] { return post_line_dev(spin, V, reverse, projradius, motion, lo, hi, b, d, n, d_line, (hipStream_t) st); });
@@ -1166,7 +1228,8 @@ int kr_post_emissivity_mu_dev_f64(double spin, double V, int reverse, int projra
 int kr_post_spectrum_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_spectrum_model* m, const kr_limb_law* law,
                              void* d, int64_t n, void* d_out, void* st)
 {
-    int rc = spectrum_validate(m, "kr_post_spectrum");
+    int rc = accept_plunge(V, motion, "kr_post_spectrum");
+    if (rc == KR_OK) rc = spectrum_validate(m, "kr_post_spectrum");
     if (rc == KR_OK) rc = spectrum_law_validate(law, motion, "kr_post_spectrum");
     if (rc != KR_OK) return rc;
     return on_device(n >= 0 && d_out && (n == 0 || d), "kr_post_spectrum: null argument or negative n",
@@ -1195,7 +1258,8 @@ int kr_reduce_spectrum_f64(const kr_spectrum_model* m, const kr_ray_f64* rays, i
 int kr_post_response_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_response_model* r, const kr_limb_law* law,
                              void* d, int64_t n, void* d_out, void* st)
 {
-    int rc = response_validate(r, "kr_post_response");
+    int rc = accept_plunge(V, motion, "kr_post_response");
+    if (rc == KR_OK) rc = response_validate(r, "kr_post_response");
     if (rc == KR_OK) rc = spectrum_law_validate(law, motion, "kr_post_response");
     if (rc != KR_OK) return rc;
     return on_device(n >= 0 && d_out && (n == 0 || d), "kr_post_response: null argument or negative n",
@@ -1224,7 +1288,8 @@ int kr_reduce_response_f64(const kr_response_model* r, const kr_ray_f64* rays, i
 int kr_post_hotspot_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_hotspot* h, const kr_limb_law* law, void* d,
                             int64_t n, void* d_out, void* st)
 {
-    int rc = hotspot_validate(h, "kr_post_hotspot");
+    int rc = refuse_plunge(V, "kr_post_hotspot");
+    if (rc == KR_OK) rc = hotspot_validate(h, "kr_post_hotspot");
     if (rc == KR_OK) rc = spectrum_law_validate(law, motion, "kr_post_hotspot");
     if (rc != KR_OK) return rc;
     return on_device(n >= 0 && d_out && (n == 0 || d), "kr_post_hotspot: null argument or negative n",
@@ -1252,7 +1317,8 @@ int kr_reduce_hotspot_f64(const kr_hotspot* h, const kr_ray_f64* rays, int64_t n
 // ---- polarisation of disc emission (kr_polarisation.hip; the Stokes line: kr_line.hip): everything is validated before anything touches a device ----
 int kr_polarisation_dev_f64(double spin, double V, int reverse, int projradius, int motion, double inc_deg, const void* d, int64_t n, void* d_out, void* st)
 {
-    const int rc = polarisation_validate(reverse, motion, inc_deg, "kr_polarisation");
+    int rc = refuse_plunge(V, "kr_polarisation");
+    if (rc == KR_OK) rc = polarisation_validate(reverse, motion, inc_deg, "kr_polarisation");
     if (rc != KR_OK) return rc;
     return on_device(n >= 0 && (n == 0 || (d && d_out)), "kr_polarisation: null argument or negative n",
                      [&] { return polarisation_dev(spin, V, reverse, projradius, inc_deg, d, n, d_out, (hipStream_t) st); });
@@ -1260,7 +1326,8 @@ int kr_polarisation_dev_f64(double spin, double V, int reverse, int projradius, 
 
 int kr_polarisation_f64(double spin, double V, int reverse, int projradius, int motion, double inc_deg, const kr_ray_f64* rays, int64_t n, double* out)
 {
-    const int rc = polarisation_validate(reverse, motion, inc_deg, "kr_polarisation");
+    int rc = refuse_plunge(V, "kr_polarisation");
+    if (rc == KR_OK) rc = polarisation_validate(reverse, motion, inc_deg, "kr_polarisation");
     if (rc != KR_OK) return rc;
     if (n < 0 || (n > 0 && (!rays || !out))) return invalid("kr_polarisation: null argument or negative n");
     return with_staged_rays((void*) rays, n, sizeof(kr_ray_f64), kReads, nullptr, [&](void* d) -> int {
@@ -1278,6 +1345,7 @@ int kr_polarisation_f64(double spin, double V, int reverse, int projradius, int 
 int kr_post_image_stokes_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, double inc_deg, const kr_image_bins* b,
                                  const kr_limb_law* limb, const kr_pol_law* pol, void* d, int64_t n, void* d_stokes, void* st)
 {
+    if (refuse_plunge(V, "kr_post_image_stokes")) return KR_EINVAL;
     if (!b) return invalid("kr_post_image_stokes: null bins");
     if (b->img_nx <= 0 || b->img_ny <= 0) return invalid("kr_post_image_stokes: image size must be positive");
     int rc = limb_validate(limb, "kr_post_image_stokes");
@@ -1291,7 +1359,8 @@ int kr_post_image_stokes_dev_f64(double spin, double V, int reverse, int projrad
 int kr_post_line_stokes_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, double inc_deg, const kr_line_bins* b,
                                 const kr_limb_law* limb, const kr_pol_law* pol, void* d, int64_t n, void* d_out, void* st)
 {
-    int rc = line_validate(b, "kr_post_line_stokes");
+    int rc = refuse_plunge(V, "kr_post_line_stokes");
+    if (rc == KR_OK) rc = line_validate(b, "kr_post_line_stokes");
     if (rc == KR_OK) rc = limb_validate(limb, "kr_post_line_stokes");
     if (rc == KR_OK) rc = pol_validate(pol, "kr_post_line_stokes");
     if (rc == KR_OK) rc = polarisation_validate(reverse, motion, inc_deg, "kr_post_line_stokes");
@@ -1304,6 +1373,7 @@ int kr_post_line_stokes_dev_f64(double spin, double V, int reverse, int projradi
 int kr_bundles_init_emit_dev_f64(const kr_imageplane* s, double eps_frac, double V, int reverse, int projradius, void* d, int64_t n, void* st)
 {
     if (!s) return invalid("kr_bundles_init_emit: null spec");
+    if (refuse_plunge(V, "kr_bundles_init_emit")) return KR_EINVAL;
     if (!std::isfinite(eps_frac) || !(eps_frac > 0) || !(eps_frac < 0.5)) return invalid("kr_bundles_init_emit: eps_frac must lie in (0, 0.5)");
     int32_t nx = 0, ny = 0;
     kr_imageplane_count(s, &nx, &ny);

@@ -18,6 +18,12 @@ int hip_fail(hipError_t e, const char* what, const char* file, int line);
 int require_device();   // KR_OK or KR_ENODEVICE (message set)
 // a refused argument: the message "<who>: <what>", KR_EINVAL
 inline int invalid_arg(const char* who, const char* what) { set_error(std::string(who) + ": " + what); return KR_EINVAL; }
+// KR_V_PLUNGE (include/kr_trace.h): refused where the flow is not built, and taken with motion = 0 alone where it is
+inline int refuse_plunge(double V, const char* who) { return V == KR_V_PLUNGE ? invalid_arg(who, "V = KR_V_PLUNGE (the plunging disc flow) is not supported here") : (int) KR_OK; }
+inline int accept_plunge(double V, int motion, const char* who)
+{
+    return V == KR_V_PLUNGE && motion != 0 ? invalid_arg(who, "V = KR_V_PLUNGE (the plunging disc flow) needs motion = 0") : (int) KR_OK;
+}
 inline bool positive_finite(double x) { return x > 0 && std::isfinite(x); }
 
 #define KR_HIP(call)                                                      \

@@ -132,6 +132,7 @@ crossings_kernel(kr_ray_f64* __restrict__ rays, long long n, TraceConsts<double>
 int crossings_validate(const kr_params* p, const kr_crossing_spec* sp, const char* who)
 {
     if (!p || !sp) return invalid_arg(who, "null argument");
+    if (const int rc = refuse_plunge(sp->V, who)) return rc;
     if (sp->max_crossings < 1 || sp->max_crossings > kMaxCrossings) return invalid_arg(who, "max_crossings must be 1..16");
     if (sp->motion != 0 && sp->motion != 1) return invalid_arg(who, "unknown motion (0: orbital, 1: radial)");
     const kr_path_spec every_row = {-1.0, -1.0, 1, 0};

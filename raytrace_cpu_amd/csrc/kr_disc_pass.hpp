@@ -31,9 +31,10 @@ struct DiscRay { double r, theta, g, phi, limb; };
 // read.  A ray that passes the filter counts in on_disc; one whose emission angle is bad counts in bad_angle too and, under law 0, is used like
 // every other ray; under the other laws -- whose weight it would poison -- it is dropped.  Returns false for a dropped ray.
 // (One drop flag and one assignment of the outputs at the end, not early returns: those cost the fused kernels two VGPRs.)
-template <bool FUSED, class Ray>
+// PLUNGE: the disc flow of KR_V_PLUNGE (DiscFlow, kr_post_device.hpp) in the fused form with motion 0; DiscFlow<false> is today's code.
+template <bool FUSED, bool PLUNGE, class Ray>
 KR_DEV bool disc_ray(Ray* ray, double r_isco, double r_disc, double spin, double V, int reverse, int projradius, int motion, double lo, double hi,
-                     const kr_limb_law& law, DiscRay* out, unsigned long long& on_disc, unsigned long long& bad_angle)
+                     const kr_limb_law& law, DiscRay* out, unsigned long long& on_disc, unsigned long long& bad_angle, const DiscFlow<PLUNGE>& fl)
 {
     double r, theta, g, phi, limb = 1;
     const int steps = ray->steps;
@@ -42,7 +43,7 @@ KR_DEV bool disc_ray(Ray* ray, double r_isco, double r_disc, double spin, double
         const kr_ray_f64 v = geodesic_of(ray);
         r = v.r; theta = v.theta;
         if (motion == 0) {
-            const Frame f = frame_value(v, spin, V, reverse, projradius);
+            const Frame f = frame_value<PLUNGE>(v, spin, V, reverse, projradius, fl);
             g = frame_redshift(f, v.emit, reverse);
             ray->redshift = g;
             phi = wrap_phi(ray, steps, lo, hi);

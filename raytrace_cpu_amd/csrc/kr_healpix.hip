@@ -250,6 +250,7 @@ int shard_check(const char* who, int64_t first, int64_t stride, int64_t records,
 int healpix_validate(const kr_healpix_source* s, const char* who)
 {
     if (!s) return invalid_arg(who, "null spec");
+    if (const int rc = refuse_plunge(s->V, who)) return rc;
     if (s->order < 0 || s->order > kMaxOrder) return invalid_arg(who, "order must be 0 ... 13");
     if (s->motion != 0 && s->motion != 1) return invalid_arg(who, "motion must be 0 (orbital) or 1 (radial)");
     if (s->basis != 0 && s->basis != 1) return invalid_arg(who, "basis must be 0 or 1");

@@ -127,10 +127,11 @@ reduce_line_kernel(const kr_ray_f64* __restrict__ rays, long long n, LineDev L, 
 
 // redshift(V, reverse, projradius, motion) + range_phi(lo, hi) + the line bins: the per-ray code of post_image_kernel (kr_post.hip) with the
 // seven planes replaced by the line, so rays[] ends bit-identical to the separate passes
-template <bool USE_LDS>
+// PLUNGE: the disc flow of KR_V_PLUNGE (DiscFlow, kr_post_device.hpp), here and in the limb-darkened line; the host picks the instance from V
+template <bool USE_LDS, bool PLUNGE>
 __global__ void __launch_bounds__(kBlock)
 post_line_kernel(kr_ray_f64* __restrict__ rays, long long n, double spin, double V, int reverse, int projradius, int motion, double lo, double hi,
-                 LineDev L, double* __restrict__ out)
+                 LineDev L, double* __restrict__ out, DiscFlow<PLUNGE> fl)
 {
     extern __shared__ double lds[];
     double* acc = line_begin<USE_LDS>(lds, out, L.words);
@@ -139,7 +140,7 @@ post_line_kernel(kr_ray_f64* __restrict__ rays, long long n, double spin, double
         kr_ray_f64* ray = &rays[i];
         const kr_ray_f64 v = geodesic_of(ray);
         const int steps = ray->steps;
-        const double g = redshift_value(v, spin, V, reverse, projradius, motion);
+        const double g = redshift_value<PLUNGE>(v, spin, V, reverse, projradius, motion, fl);
         ray->redshift = g;
         wrap_phi(ray, steps, lo, hi);
         if (!disc_filter(L.b.r_isco, L.b.r_disc, steps, v.r, v.theta, g)) continue;
@@ -151,10 +152,10 @@ post_line_kernel(kr_ray_f64* __restrict__ rays, long long n, double spin, double
 
 // post_line_kernel with w *= limb(mu): disc_ray (kr_disc_pass.hpp) in its fused form for the orbiting observer, so rays[] ends as after
 // post_line_kernel and a bad-angle ray is counted and binned by that function's rule.  Layout: post_line_kernel's, then bad_angle.
-template <bool USE_LDS>
+template <bool USE_LDS, bool PLUNGE>
 __global__ void __launch_bounds__(kBlock)
 post_line_limb_kernel(kr_ray_f64* __restrict__ rays, long long n, double spin, double V, int reverse, int projradius, double lo, double hi, LineDev L,
-                      kr_limb_law law, double* __restrict__ out)
+                      kr_limb_law law, double* __restrict__ out, DiscFlow<PLUNGE> fl)
 {
     extern __shared__ double lds[];
     const int words = L.words + 1;
@@ -163,7 +164,7 @@ post_line_limb_kernel(kr_ray_f64* __restrict__ rays, long long n, double spin, d
     KR_GRID_STRIDE(i, n) {
         kr_ray_f64* ray = &rays[i];
         DiscRay d;
-        if (!disc_ray<true>(ray, L.b.r_isco, L.b.r_disc, spin, V, reverse, projradius, 0, lo, hi, law, &d, on_disc, bad_angle)) continue;
+        if (!disc_ray<true, PLUNGE>(ray, L.b.r_isco, L.b.r_disc, spin, V, reverse, projradius, 0, lo, hi, law, &d, on_disc, bad_angle, fl)) continue;
         binned += line_accumulate<false, true>(acc, L, d.r, d.g, ray->t, d.limb);
     }
     line_end<USE_LDS, true>(lds, out, words, on_disc, binned, bad_angle);
@@ -289,8 +290,8 @@ int post_line_dev(double spin, double V, int reverse, int projradius, int motion
     LineDev L;
     int rc = line_dev(b, pins, &L);
     if (rc != KR_OK) return rc;
-    KR_LAUNCH_LDS_OR_GLOBAL(post_line_kernel, L.words <= kLineLdsWords, grid_for(n, kBlock, kCapHist), L.words * sizeof(double), st, (kr_ray_f64*) d, (long long) n,
-                            spin, V, reverse, projradius, motion, lo, hi, L, (double*) d_line);
+    KR_LAUNCH_LDS_OR_GLOBAL_FLOW(post_line_kernel, spin, V, reverse, L.words <= kLineLdsWords, grid_for(n, kBlock, kCapHist), L.words * sizeof(double), st, (kr_ray_f64*) d,
+                                 (long long) n, spin, V, reverse, projradius, motion, lo, hi, L, (double*) d_line);
     return KR_OK;
 }
 
@@ -302,8 +303,8 @@ int post_line_limb_dev(double spin, double V, int reverse, int projradius, doubl
     LineDev L;
     int rc = line_dev(b, pins, &L);
     if (rc != KR_OK) return rc;
-    KR_LAUNCH_LDS_OR_GLOBAL(post_line_limb_kernel, L.words + 1 <= kLineLdsWords, grid_for(n, kBlock, kCapHist), (L.words + 1) * sizeof(double), st, (kr_ray_f64*) d,
-                            (long long) n, spin, V, reverse, projradius, lo, hi, L, *law, (double*) d_line);
+    KR_LAUNCH_LDS_OR_GLOBAL_FLOW(post_line_limb_kernel, spin, V, reverse, L.words + 1 <= kLineLdsWords, grid_for(n, kBlock, kCapHist), (L.words + 1) * sizeof(double), st,
+                                 (kr_ray_f64*) d, (long long) n, spin, V, reverse, projradius, lo, hi, L, *law, (double*) d_line);
     return KR_OK;
 }
 

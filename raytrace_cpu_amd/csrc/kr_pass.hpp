@@ -5,6 +5,7 @@
 #pragma once
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 #include "kr_common.hpp"
@@ -34,6 +35,41 @@ constexpr int kCapHist = 256 * 4;          // few, fat workgroups: every workgro
         if (fits) hipLaunchKernelGGL(kernel<true>, dim3(grid), dim3(kBlock), lds_bytes, st, __VA_ARGS__); \
         else hipLaunchKernelGGL(kernel<false>, dim3(grid), dim3(kBlock), 0, st, __VA_ARGS__);             \
         KR_LAUNCH_CHECK();                                                                                \
+    } while (0)
+
+// ---- the disc flow of a launch (DiscFlow, kr_post_device.hpp) ------------------------------------------------------------------------------
+// r_ms = kr_kerr_isco(a, +1) of the metric's a = reverse ? -spin : spin and the energy and angular momentum of the circular orbit there, every
+// square root a double one (include/kr_trace.h, KR_V_PLUNGE)
+inline DiscFlow<true> plunge_flow(double spin, int reverse)
+{
+    const double a = reverse ? -1 * spin : spin;
+    DiscFlow<true> fl;
+    fl.r_ms = kr_kerr_isco(a, +1);
+    const double u = 1 / fl.r_ms;
+    fl.E_ms = (1 - 2 * u + a * u * std::sqrt(u)) / std::sqrt(1 - 3 * u + 2 * a * u * std::sqrt(u));
+    fl.L_ms = (1 + a * a * u * u - 2 * a * u * std::sqrt(u)) / std::sqrt(u * (1 - 3 * u + 2 * a * u * std::sqrt(u)));
+    return fl;
+}
+
+// f(choice) with choice.plunge a compile-time bool and choice.arg the kernel's trailing DiscFlow argument: the plunge instance for V == KR_V_PLUNGE,
+// today's instance for every other V
+template <bool P> struct FlowChoice { static constexpr bool plunge = P; DiscFlow<P> arg; };
+template <typename F>
+void for_flow(double spin, double V, int reverse, F f)
+{
+    if (V == KR_V_PLUNGE) f(FlowChoice<true>{plunge_flow(spin, reverse)});
+    else f(FlowChoice<false>{});
+}
+
+// KR_LAUNCH_LDS_OR_GLOBAL for kernel<USE_LDS, PLUNGE>(..., DiscFlow<PLUNGE>)
+#define KR_LAUNCH_LDS_OR_GLOBAL_FLOW(kernel, spin, V, reverse, fits, grid, lds_bytes, st, ...)                             \
+    do {                                                                                                                   \
+        for_flow(spin, V, reverse, [&](auto flow_) {                                                                       \
+            constexpr bool kPlunge_ = decltype(flow_)::plunge;                                                             \
+            if (fits) hipLaunchKernelGGL((kernel<true, kPlunge_>), dim3(grid), dim3(kBlock), lds_bytes, st, __VA_ARGS__, flow_.arg); \
+            else hipLaunchKernelGGL((kernel<false, kPlunge_>), dim3(grid), dim3(kBlock), 0, st, __VA_ARGS__, flow_.arg);   \
+        });                                                                                                                \
+        KR_LAUNCH_CHECK();                                                                                                 \
     } while (0)
 
 // Several small launches in one: the items of a chunk ride in the kernel arguments (no staging buffer whose lifetime a later call would have

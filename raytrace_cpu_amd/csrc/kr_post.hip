@@ -37,14 +37,15 @@ redshift_start_kernel(R* __restrict__ rays, long long n, T spin, T V, int revers
     }
 }
 
-template <typename R, typename T = typename ScalarOf<R>::type>
+// PLUNGE: the disc flow of KR_V_PLUNGE (DiscFlow, kr_post_device.hpp); the host picks the instance from V, here and in every kernel below that takes one
+template <typename R, typename T = typename ScalarOf<R>::type, bool PLUNGE = false>
 __global__ void __launch_bounds__(kBlock)
-redshift_kernel(R* __restrict__ rays, long long n, T spin, T V_in, int reverse, int projradius, int motion)
+redshift_kernel(R* __restrict__ rays, long long n, T spin, T V_in, int reverse, int projradius, int motion, DiscFlow<PLUNGE> fl)
 {
     KR_GRID_STRIDE(i, n) {
         R* ray = &rays[i];
         const R v = geodesic_of(ray);
-        ray->redshift = redshift_value(v, spin, V_in, reverse, projradius, motion);
+        ray->redshift = redshift_value<PLUNGE>(v, spin, V_in, reverse, projradius, motion, fl);
     }
 }
 
@@ -218,10 +219,10 @@ reduce_emissivity_kernel(const kr_ray_f64* __restrict__ rays, long long n, kr_em
 // ---- fused epilogue of the emissivity pipeline: range_phi -> redshift -> histogram in ONE pass over the records
 //      (emissivity.cpp:93-126: the three O(N) steps after run_raytrace).  Same per-ray functions as the separate
 //      kernels, so rays[] and the integer bin counts are bit-identical to running them one after another. -------------
-template <bool USE_LDS>
+template <bool USE_LDS, bool PLUNGE>
 __global__ void __launch_bounds__(kBlock)
 post_emissivity_kernel(kr_ray_f64* __restrict__ rays, long long n, double spin, double V, int reverse, int projradius, int motion, double lo, double hi,
-                       kr_emis_bins b, double* __restrict__ hist)
+                       kr_emis_bins b, double* __restrict__ hist, DiscFlow<PLUNGE> fl)
 {
     __shared__ double lds[USE_LDS ? (5 * kMaxLdsBins + 1) : 1];
     const int nr = b.nr;
@@ -237,7 +238,7 @@ post_emissivity_kernel(kr_ray_f64* __restrict__ rays, long long n, double spin, 
         const kr_ray_f64 v = geodesic_of(ray);
         const int steps = ray->steps;
         wrap_phi(ray, steps, lo, hi);
-        const double g = redshift_value(v, spin, V, reverse, projradius, motion);
+        const double g = redshift_value<PLUNGE>(v, spin, V, reverse, projradius, motion, fl);
         ray->redshift = g;
         emissivity_accumulate(acc, b, log_dr, steps, v.r, v.theta, g, ray->t);
     }
@@ -319,9 +320,10 @@ reduce_crossing_image_kernel(const kr_ray_f64* __restrict__ rays, const double* 
 
 // ---- fused epilogue of the image pipeline: redshift(V, reverse, projradius, motion) + range_phi + the seven planes in one pass
 //      (imageplane_disc_image.cpp:117-161) -----------------------------------------------------------------------------------
+template <bool PLUNGE>
 __global__ void __launch_bounds__(kBlock)
 post_image_kernel(kr_ray_f64* __restrict__ rays, long long n, double spin, double V, int reverse, int projradius, int motion, double lo, double hi,
-                  kr_image_bins b, double* __restrict__ planes)
+                  kr_image_bins b, double* __restrict__ planes, DiscFlow<PLUNGE> fl)
 {
     const long long npix = (long long) b.img_nx * b.img_ny;
     unsigned long long hits = 0;
@@ -329,7 +331,7 @@ post_image_kernel(kr_ray_f64* __restrict__ rays, long long n, double spin, doubl
         kr_ray_f64* ray = &rays[i];
         const kr_ray_f64 v = geodesic_of(ray);
         const int steps = ray->steps;
-        const double g = redshift_value(v, spin, V, reverse, projradius, motion);
+        const double g = redshift_value<PLUNGE>(v, spin, V, reverse, projradius, motion, fl);
         ray->redshift = g;
         const double wrapped = wrap_phi(ray, steps, lo, hi);
         hits += image_accumulate(planes, npix, b, steps, v.r, v.theta, wrapped, ray->t, g, ray->alpha, ray->beta);
@@ -480,7 +482,14 @@ int redshift_start_dev(double spin, double V, int reverse, int projradius, void*
 
 int redshift_dev(double spin, double V, int reverse, int projradius, int motion, void* d, int64_t n, hipStream_t st, bool f32)
 {
-    KR_POST_LAUNCH(redshift_kernel, spin, V, reverse, projradius, motion);
+    if (V == KR_V_PLUNGE) {                      // f64, motion 0: the C API has refused the rest
+        if (n <= 0) return KR_OK;
+        hipLaunchKernelGGL((redshift_kernel<kr_ray_f64, double, true>), dim3(grid_for(n, kBlock, kCapStream)), dim3(kBlock), 0, st, (kr_ray_f64*) d, (long long) n, spin, V,
+                           reverse, projradius, motion, plunge_flow(spin, reverse));
+        KR_LAUNCH_CHECK();
+        return KR_OK;
+    }
+    KR_POST_LAUNCH(redshift_kernel, spin, V, reverse, projradius, motion, DiscFlow<false>{});
 }
 
 int redshift_dest_dev(double spin, int reverse, void* d, int64_t n, hipStream_t st, bool f32)
@@ -613,8 +622,10 @@ int post_image_dev(double spin, double V, int reverse, int projradius, int motio
 {
     if (b->img_nx <= 0 || b->img_ny <= 0) { set_error("kr_post_image: image size must be positive"); return KR_EINVAL; }
     if (n <= 0) return KR_OK;
-    hipLaunchKernelGGL(post_image_kernel, dim3(grid_for(n, kBlock, kCapStream)), dim3(kBlock), 0, st, (kr_ray_f64*) d, (long long) n, spin, V, reverse, projradius, motion, lo, hi, *b,
-                       (double*) d_planes);
+    for_flow(spin, V, reverse, [&](auto fl) {
+        hipLaunchKernelGGL(post_image_kernel<decltype(fl)::plunge>, dim3(grid_for(n, kBlock, kCapStream)), dim3(kBlock), 0, st, (kr_ray_f64*) d, (long long) n, spin, V, reverse,
+                           projradius, motion, lo, hi, *b, (double*) d_planes, fl.arg);
+    });
     KR_LAUNCH_CHECK();
     return KR_OK;
 }
@@ -633,8 +644,8 @@ int post_emissivity_dev(double spin, double V, int reverse, int projradius, int 
 {
     if (b->nr <= 0) { set_error("kr_post_emissivity: nr must be positive"); return KR_EINVAL; }
     if (n <= 0) return KR_OK;
-    KR_LAUNCH_LDS_OR_GLOBAL(post_emissivity_kernel, b->nr <= kMaxLdsBins, grid_for(n, kBlock, kCapHist), 0, st, (kr_ray_f64*) d, (long long) n, spin, V, reverse,
-                            projradius, motion, lo, hi, *b, (double*) d_hist);
+    KR_LAUNCH_LDS_OR_GLOBAL_FLOW(post_emissivity_kernel, spin, V, reverse, b->nr <= kMaxLdsBins, grid_for(n, kBlock, kCapHist), 0, st, (kr_ray_f64*) d, (long long) n, spin,
+                                 V, reverse, projradius, motion, lo, hi, *b, (double*) d_hist);
     return KR_OK;
 }
 

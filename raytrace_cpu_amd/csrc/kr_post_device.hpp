@@ -139,6 +139,121 @@ KR_DEV Frame frame_value(const kr_ray_f64& ray, double spin, double V_in, int re
     return f;
 }
 
+// ---- the disc flow "Keplerian, plunging inside the ISCO" (include/kr_trace.h, KR_V_PLUNGE; a compile-time parameter of the kernels that evaluate a
+//      frame or a redshift, so that the instance of every other V is the code it was).  DiscFlow<false> carries nothing; DiscFlow<true> the ISCO of the
+//      metric's a and the energy and angular momentum of its circular orbit, computed once per launch on the host (plunge_flow, kr_pass.hpp).  At
+//      r >= r_ms the plunge instance runs the expressions of frame_value / redshift_value with V = -1, operation for operation; at r < r_ms the gas is
+//      on the equatorial geodesic with those constants (host/include/disc.h plunge_velocity, in double), e_t = u, e2 stays, and e3 (r-like), e1
+//      (phi-like) come from Gram-Schmidt against the metric seeded with d/dr, then d/dphi, oriented e3^r > 0, e1^phi > 0
+//      (host/include/gramschmidt_basis.h).  Both sides share one metric and one momentum evaluation. ----
+template <bool PLUNGE> struct DiscFlow {};
+template <> struct DiscFlow<true> { double r_ms, E_ms, L_ms; };
+
+// a four-vector in named scalars: the two sides of the per-lane r < r_ms branch hand whole vectors on, and both stay in registers (the plunge
+// instances take the 32 bytes of scratch per lane that every kernel of these files takes, -Rpass-analysis=kernel-resource-usage, and no more)
+struct Vec4 { double t, r, th, ph; };
+
+// energy_dot on two Vec4: the same sixteen terms in the same order
+KR_DEV double vec_dot(const Metric<double>& m, const Vec4& x, const Vec4& y)
+{
+    const double xa[4] = {x.t, x.r, x.th, x.ph}, ya[4] = {y.t, y.r, y.th, y.ph};
+    return energy_dot<double>(m, xa, ya);
+}
+
+KR_DEV Vec4 plunge_velocity(const DiscFlow<true>& fl, double r, double a)
+{
+    const double delta = r * r - 2 * r + a * a;
+    const double k = fl.E_ms, h = fl.L_ms;
+    const double rad = k * k - 1 + 2 / r + (a * a * (k * k - 1) - h * h) / (r * r) + 2 * (h - a * k) * (h - a * k) / (r * r * r);
+    Vec4 u;
+    u.t = ((r * r + a * a + 2 * a * a / r) * k - 2 * a * h / r) / delta;
+    u.r = -1 * kr_sqrt(rad > 0 ? rad : 0.0);
+    u.th = 0;
+    u.ph = (2 * a * k / r + (1 - 2 / r) * h) / delta;
+    return u;
+}
+
+// the r-like and phi-like legs of the observer u by Gram-Schmidt: projections removed leg by leg before any leg is normalised, as the host class does
+KR_DEV void plunge_legs(const Metric<double>& m, const Vec4& u, Vec4* e1, Vec4* e3)
+{
+    const Vec4 seed_r = {0, 1, 0, 0}, seed_phi = {0, 0, 0, 1};
+    const double uu = vec_dot(m, u, u);
+    const double c3 = vec_dot(m, seed_r, u) / uu;
+    const Vec4 v3 = {seed_r.t - c3 * u.t, seed_r.r - c3 * u.r, seed_r.th - c3 * u.th, seed_r.ph - c3 * u.ph};
+    const double n3 = vec_dot(m, v3, v3);
+    const double c1 = vec_dot(m, seed_phi, u) / uu, c13 = vec_dot(m, seed_phi, v3) / n3;
+    const Vec4 v1 = {(seed_phi.t - c1 * u.t) - c13 * v3.t, (seed_phi.r - c1 * u.r) - c13 * v3.r, (seed_phi.th - c1 * u.th) - c13 * v3.th,
+                     (seed_phi.ph - c1 * u.ph) - c13 * v3.ph};
+    const double n1 = vec_dot(m, v1, v1);
+    const double l3 = (v3.r < 0 ? -1 : 1) * kr_sqrt(kr_abs(n3)), l1 = (v1.ph < 0 ? -1 : 1) * kr_sqrt(kr_abs(n1));
+    *e3 = Vec4{v3.t / l3, v3.r / l3, v3.th / l3, v3.ph / l3};
+    *e1 = Vec4{v1.t / l1, v1.r / l1, v1.th / l1, v1.ph / l1};
+}
+
+// e_t of the flow at (r, theta): the plunging gas inside r_ms, the circular orbit of V = -1 (redshift_value's expressions) from r_ms on
+KR_DEV Vec4 flow_et(const DiscFlow<true>& fl, const Metric<double>& m, double r, double theta, double a, int projradius, bool inside)
+{
+    if (inside) return plunge_velocity(fl, r, a);
+    const double V = keplerian_V<double>(a, r, theta, projradius != 0);
+    return Vec4{(1 / kr_sqrt(m.e2nu)) / kr_sqrt(1 - (V - m.omega) * (V - m.omega) * m.e2psi / m.e2nu), 0, 0,
+                (1 / kr_sqrt(m.e2nu)) * V / kr_sqrt(1 - (V - m.omega) * (V - m.omega) * m.e2psi / m.e2nu)};
+}
+
+template <bool PLUNGE>
+KR_DEV Frame frame_value(const kr_ray_f64& ray, double spin, double V_in, int reverse, int projradius, const DiscFlow<PLUNGE>& fl)
+{
+    if constexpr (!PLUNGE) {
+        return frame_value(ray, spin, V_in, reverse, projradius);
+    } else {
+        using T = double;
+        const T a = reverse ? -1 * spin : spin;
+        const T r = ray.r, theta = ray.theta;
+        const Metric<T> m = kerr_metric<T>(r, theta, a);
+        const bool inside = r < fl.r_ms;
+        const Vec4 et = flow_et(fl, m, r, theta, a, projradius, inside);
+        Vec4 e1, e3;
+        if (inside) {
+            plunge_legs(m, et, &e1, &e3);
+        } else {
+            const T V = keplerian_V<T>(a, r, theta, projradius != 0);
+            e1 = Vec4{(V - m.omega) * kr_sqrt(m.e2psi / m.e2nu) / kr_sqrt(m.e2nu - (V - m.omega) * (V - m.omega) * m.e2psi), 0, 0,
+                      (1 / kr_sqrt(m.e2nu * m.e2psi)) * (m.e2nu + V * m.omega * m.e2psi - m.omega * m.omega * m.e2psi) /
+                          kr_sqrt(m.e2nu - (V - m.omega) * (V - m.omega) * m.e2psi)};
+            e3 = Vec4{0, kr_sqrt(m.delta / m.rhosq), 0, 0};
+        }
+        const Vec4 e2 = {0, 0, 1 / kr_sqrt(m.rhosq), 0};
+        Vec4 p;
+        momentum<T>(p.t, p.r, p.th, p.ph, ray.k, ray.h, ray.Q, ray.rdot_sign, ray.thetadot_sign, r, theta, spin);
+        if (reverse) { p.r *= -1; p.th *= -1; p.ph *= -1; }
+        Frame f;
+        f.E = vec_dot(m, et, p);
+        f.P_phi = -1 * vec_dot(m, e1, p);
+        f.P_th = -1 * vec_dot(m, e2, p);
+        f.P_r = -1 * vec_dot(m, e3, p);
+        return f;
+    }
+}
+
+// redshift_value for the flow: only e_t is evaluated.  (R, T stay template parameters so that the f32 kernels name the same function; the plunge
+// instance exists for f64 records alone.)
+template <bool PLUNGE, typename R, typename T = typename ScalarOf<R>::type>
+KR_DEV T redshift_value(const R& ray, T spin, T V_in, int reverse, int projradius, int motion, const DiscFlow<PLUNGE>& fl)
+{
+    if constexpr (!PLUNGE) {
+        return redshift_value(ray, spin, V_in, reverse, projradius, motion);
+    } else {
+        const T a = reverse ? -1 * spin : spin;
+        const T r = ray.r, theta = ray.theta;
+        const Metric<T> m = kerr_metric<T>(r, theta, a);
+        const Vec4 et = flow_et(fl, m, r, theta, a, projradius, r < fl.r_ms);
+        Vec4 p;
+        momentum<T>(p.t, p.r, p.th, p.ph, ray.k, ray.h, ray.Q, ray.rdot_sign, ray.thetadot_sign, r, theta, spin);
+        if (reverse) { p.r *= -1; p.th *= -1; p.ph *= -1; }
+        const T recv = vec_dot(m, et, p);
+        return reverse ? recv / ray.emit : ray.emit / recv;
+    }
+}
+
 KR_DEV double frame_redshift(const Frame& f, double emit, int reverse) { return reverse ? f.E / emit : emit / f.E; }
 
 // mu = |P_th| / E, the cosine of the angle to the disc normal; chi = atan2(P_phi, P_r), the azimuth about it (0 radially outward, +pi/2 along

@@ -83,10 +83,11 @@ KR_DEV bool response_item(const SpecDev& D, const RespDev& R, double r, double g
     return true;
 }
 
-template <int MODEL, bool FUSED, int SLOTS>
+// PLUNGE: the disc flow of KR_V_PLUNGE (DiscFlow, kr_post_device.hpp), fused form only; the host picks the instance from V
+template <int MODEL, bool FUSED, int SLOTS, bool PLUNGE>
 __global__ void __launch_bounds__(kBlock)
 response_kernel(typename std::conditional<FUSED, kr_ray_f64, const kr_ray_f64>::type* __restrict__ rays, long long n, double spin, double V, int reverse,
-                int projradius, int motion, double lo, double hi, SpecDev D, RespDev R, kr_limb_law law, double* __restrict__ out)
+                int projradius, int motion, double lo, double hi, SpecDev D, RespDev R, kr_limb_law law, double* __restrict__ out, DiscFlow<PLUNGE> fl)
 {
     extern __shared__ double lds_s[];                    // MODEL 1: the table
     __shared__ double it_a[kBlock], it_b[kBlock], it_c[kBlock];
@@ -138,7 +139,7 @@ response_kernel(typename std::conditional<FUSED, kr_ray_f64, const kr_ray_f64>::
         if (i < n) {
             DiscRay d;
             double ft = 0;
-            if (disc_ray<FUSED>(&rays[i], m.r_isco, m.r_disc, spin, V, reverse, projradius, motion, lo, hi, law, &d, on_disc, bad_angle))
+            if (disc_ray<FUSED, PLUNGE>(&rays[i], m.r_isco, m.r_disc, spin, V, reverse, projradius, motion, lo, hi, law, &d, on_disc, bad_angle, fl))
                 live = response_item(D, R, d.r, d.g, rays[i].t, d.limb, &a, &b, &c, &zone, &ft);
             if (live) {
                 used++;
@@ -226,15 +227,21 @@ int response_launch(const kr_response_model* r, const kr_limb_law& law, Rays* d,
     // twice with the same values; only the first launch adds the tallies)
     for (R.e0 = 0; R.e0 < m->ne; R.e0 += kLaunchSlots * kBlock) {
         R.e1 = std::min(m->ne, R.e0 + kLaunchSlots * kBlock);
-        for_slots((R.e1 - R.e0 + kBlock - 1) / kBlock, [&](auto K) {
-            if constexpr (K.value <= kLaunchSlots) {
-                auto launch = [&](auto kernel, size_t lds) {
-                    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, st, d, (long long) n, spin, V, reverse, projradius, motion, lo, hi, D, R, law, (double*) d_out);
-                };
-                if (in_lds) launch(response_kernel<1, FUSED, K.value>, (size_t) m->nz * m->s_ne * sizeof(double));
-                else launch(response_kernel<2, FUSED, K.value>, 0);
-            }
-        });
+        auto with_flow = [&](auto flow) {
+            constexpr bool P = decltype(flow)::plunge;
+            for_slots((R.e1 - R.e0 + kBlock - 1) / kBlock, [&](auto K) {
+                if constexpr (K.value <= kLaunchSlots) {
+                    auto launch = [&](auto kernel, size_t lds) {
+                        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, st, d, (long long) n, spin, V, reverse, projradius, motion, lo, hi, D, R, law, (double*) d_out,
+                                           flow.arg);
+                    };
+                    if (in_lds) launch(response_kernel<1, FUSED, K.value, P>, (size_t) m->nz * m->s_ne * sizeof(double));
+                    else launch(response_kernel<2, FUSED, K.value, P>, 0);
+                }
+            });
+        };
+        if constexpr (FUSED) for_flow(spin, V, reverse, with_flow);
+        else with_flow(FlowChoice<false>{});
         KR_LAUNCH_CHECK();
     }
     return KR_OK;

@@ -31,10 +31,11 @@ namespace {
 // the budget S is read from global memory (a table that size is L2-resident, and every lane of a wave reads near the same node).
 constexpr int kSpecLdsWords = 4096;
 
-template <int MODEL, bool FUSED, int SLOTS>
+// PLUNGE: the disc flow of KR_V_PLUNGE (DiscFlow, kr_post_device.hpp), fused form only; the host picks the instance from V
+template <int MODEL, bool FUSED, int SLOTS, bool PLUNGE>
 __global__ void __launch_bounds__(kBlock)
 spectrum_kernel(typename std::conditional<FUSED, kr_ray_f64, const kr_ray_f64>::type* __restrict__ rays, long long n, double spin, double V, int reverse,
-                int projradius, int motion, double lo, double hi, SpecDev D, kr_limb_law law, double* __restrict__ out)
+                int projradius, int motion, double lo, double hi, SpecDev D, kr_limb_law law, double* __restrict__ out, DiscFlow<PLUNGE> fl)
 {
     constexpr bool THERMAL = MODEL == 0;
     extern __shared__ double lds_s[];                    // MODEL 1: the table
@@ -72,7 +73,7 @@ spectrum_kernel(typename std::conditional<FUSED, kr_ray_f64, const kr_ray_f64>::
         int zone = 0;
         if (i < n) {
             DiscRay d;
-            if (disc_ray<FUSED>(&rays[i], m.r_isco, m.r_disc, spin, V, reverse, projradius, motion, lo, hi, law, &d, on_disc, bad_angle))
+            if (disc_ray<FUSED, PLUNGE>(&rays[i], m.r_isco, m.r_disc, spin, V, reverse, projradius, motion, lo, hi, law, &d, on_disc, bad_angle, fl))
                 live = spectrum_item<THERMAL>(D, d.r, d.g, d.limb, &a, &b, &c, &zone);
             if (live) used++;
         }
@@ -164,14 +165,19 @@ int spectrum_launch(const kr_spectrum_model* m, const kr_limb_law& law, Rays* d,
     if (rc != KR_OK) return rc;
     const int slots = (m->ne + kBlock - 1) / kBlock, grid = grid_for(n, kBlock, kCapHist);
     const int64_t s_words = (int64_t) m->nz * m->s_ne;
-    for_slots(slots, [&](auto K) {
-        auto launch = [&](auto kernel, size_t lds) {
-            hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, st, d, (long long) n, spin, V, reverse, projradius, motion, lo, hi, D, law, (double*) d_out);
-        };
-        if (m->model == 0) launch(spectrum_kernel<0, FUSED, K.value>, 0);
-        else if (s_words <= kSpecLdsWords) launch(spectrum_kernel<1, FUSED, K.value>, (size_t) s_words * sizeof(double));
-        else launch(spectrum_kernel<2, FUSED, K.value>, 0);
-    });
+    auto with_flow = [&](auto flow) {
+        constexpr bool P = decltype(flow)::plunge;
+        for_slots(slots, [&](auto K) {
+            auto launch = [&](auto kernel, size_t lds) {
+                hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, st, d, (long long) n, spin, V, reverse, projradius, motion, lo, hi, D, law, (double*) d_out, flow.arg);
+            };
+            if (m->model == 0) launch(spectrum_kernel<0, FUSED, K.value, P>, 0);
+            else if (s_words <= kSpecLdsWords) launch(spectrum_kernel<1, FUSED, K.value, P>, (size_t) s_words * sizeof(double));
+            else launch(spectrum_kernel<2, FUSED, K.value, P>, 0);
+        });
+    };
+    if constexpr (FUSED) for_flow(spin, V, reverse, with_flow);
+    else with_flow(FlowChoice<false>{});
     KR_LAUNCH_CHECK();
     return KR_OK;
 }

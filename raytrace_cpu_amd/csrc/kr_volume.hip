@@ -163,6 +163,7 @@ volume_kernel(kr_ray_f64* __restrict__ rays, long long n, TraceConsts<double> c,
 int volume_validate(const kr_params* p, const kr_volume_map* m, const char* who)
 {
     if (!p || !m) return invalid_arg(who, "null argument");
+    if (const int rc = refuse_plunge(m->V, who)) return rc;
     if (m->nr < 1 || m->ntheta < 1 || m->nphi < 1) return invalid_arg(who, "nr, ntheta and nphi must be at least 1");
     if ((long long) m->nr * m->ntheta * m->nphi > kMaxCells || (long long) m->nr * m->ntheta > kMaxCells) return invalid_arg(who, "the grid has more than 2^27 cells");
     if (!positive_finite(m->dr) || !positive_finite(m->dtheta) || !positive_finite(m->dphi)) return invalid_arg(who, "dr, dtheta and dphi must be positive and finite");
