@@ -509,7 +509,23 @@ static_assert(sizeof(kr_spectrum_model) == 168, "kr_spectrum_model is 168 bytes 
  * into: shards, several planes, several spots and several calls sum.  The centroid sx / flux, sy / flux is the caller's to take.
  * Refused (KR_EINVAL): a null spot; a non-finite parameter; nt < 1 or nt > 4096; ne < 0 or ne > 4096; nt ne > 2^20; sigma <= 0; cut <= 0; r_spot <= 0;
  * with ne > 0: de <= 0, log_e with de <= 1 or e_min <= 0, line_energy <= 0; shear other than 0 or 1; with shear == 1, a_orbit + r_isco sqrt(r_isco) <= 0.
- * The struct holds no host pointer: nothing goes through the table cache.  The pad words are reserved (Stokes light curves would select there). */
+ * The struct holds no host pointer: nothing goes through the table cache.  The pad words are reserved and not judged.
+ *
+ * STOKES LIGHT CURVES of the spot (kr_post_hotspot_stokes_dev_f64, kr_reduce_hotspot_stokes_*): the time-resolved linear polarisation, Q[k] and U[k]
+ * beside flux, sx, sy.  Everything of the rule above stands: filter, ring, Om, the weight c = limb g^-g_index, the energy bin, the samples T_k, the shifted
+ * Gaussian s.  Everything of the kr_pol_law rule stands too: frame, emitted vector, Walker-Penrose constant, observer inversion with inc_deg, c2, s2,
+ * bad-pol, the degree law delta(mu); reverse = 1 and motion = 0, as there.  mu of the limb law and of delta is that frame's.  What joins them:
+ *   bad-pol  a record that passes the filter and the ring and is NOT bad-pol counts in `used`.  One that passes both and IS bad-pol counts in `bad_pol`
+ *            and adds to nothing, whatever the limb law (as in the Stokes image and line passes, where bad-pol rays are never binned).  Bad-angle is a
+ *            subset of bad-pol: there is no separate bad_angle tally.  A bad-pol record outside the ring is not counted.
+ *   sums     for every sample with s > 0:  flux[k] += c s,  sx[k] += c s x,  sy[k] += c s y,  Q[k] += ((c delta) c2) s,  U[k] += ((c delta) s2) s,  and with
+ *            ne > 0  spec[k][ie] += c s  (intensity only: there is no Q, U spectrogram)
+ *   axes     Q and U refer to the plane's own x and y axes, as in kr_post_image_stokes_dev_f64
+ * Output: double[nt (5 + ne) + 4] = [flux | sx | sy | Q | U (nt each) | spec (nt x ne, time-major) | on_disc | used | bad_pol | 0], ADDED into.  The
+ * polarisation degree sqrt(Q^2 + U^2) / flux and the angle atan2(U, Q) / 2 are the caller's to take.
+ * The reduce forms take records that carry their redshift and wrapped phi (g and phi are READ from the record) and recompute the frame of the ring
+ * records for mu, c2, s2 and bad-pol: unlike kr_reduce_hotspot_* they take a limb law.
+ * Not covered: Q, U spectrograms, the plunging flow (KR_V_PLUNGE is refused), the thick-disc surface, higher-order images, f32 records. */
 typedef struct kr_hotspot {
     double r_spot, sigma, cut;     /* centre radius, Gaussian width and the cut-off in units of sigma */
     double phi0, omega;            /* azimuth at coordinate time 0; pattern speed (shear == 0) */
@@ -1265,6 +1281,21 @@ int kr_post_hotspot_dev_f64(double spin, double V, int reverse, int projradius, 
                             void* d_rays, int64_t n, void* d_out, void* stream);
 int kr_reduce_hotspot_dev_f64(const kr_hotspot* h, const void* d_rays, int64_t n, void* d_out, void* stream);
 int kr_reduce_hotspot_f64(const kr_hotspot* h, const kr_ray_f64* rays, int64_t n, double* out);
+/* The Stokes light curves of the spot (the Stokes rule under kr_hotspot).  KR_EINVAL (message in kr_last_error) before a device is touched, and nothing is
+ * written: V == KR_V_PLUNGE, whatever the spot's comment refuses, reverse != 1, motion != 0, a non-finite inc_deg, a limb law other than 0, 1, 2 or with a
+ * non-finite coeff, whatever kr_pol_law refuses, a null pointer, n < 0.  n == 0 is KR_OK and adds nothing.  None of the _dev forms waits for the device or
+ * allocates.
+ * kr_post_hotspot_stokes_dev_f64: redshift(V, reverse, projradius, motion) + range_phi(lo, hi) + the spot with its Stokes sums in one pass; rays[] ends up
+ * exactly as after kr_post_line_dev_f64.  ADDS into d_out (nt (5 + ne) + 4 doubles; zero it first).
+ * kr_reduce_hotspot_stokes_dev_f64: records that already carry their redshift and wrapped phi (every further spot on the same plane); reads the records
+ * and never writes them.
+ * kr_reduce_hotspot_stokes_f64: host records, out = nt (5 + ne) + 4 host doubles (overwritten). */
+int kr_post_hotspot_stokes_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, double inc_deg, const kr_hotspot* h,
+                                   const kr_limb_law* law, const kr_pol_law* pol, void* d_rays, int64_t n, void* d_out, void* stream);
+int kr_reduce_hotspot_stokes_dev_f64(double spin, double V, int reverse, int projradius, double inc_deg, const kr_hotspot* h, const kr_limb_law* law,
+                                     const kr_pol_law* pol, const void* d_rays, int64_t n, void* d_out, void* stream);
+int kr_reduce_hotspot_stokes_f64(double spin, double V, int reverse, int projradius, double inc_deg, const kr_hotspot* h, const kr_limb_law* law,
+                                 const kr_pol_law* pol, const kr_ray_f64* rays, int64_t n, double* out);
 
 /* ---- critical-curve maps (kr_caustic_map above): caustic_discplane.cpp on the device -------------------------------------------------------
  * Every entry point validates its arguments before it touches a device: KR_EINVAL (message in kr_last_error) when nx or ny < 1, eps_x or eps_y

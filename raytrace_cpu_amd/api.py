@@ -1841,14 +1841,57 @@ def reduce_hotspot(h, rays):
     return hotspot_from_words(h, out)
 
 
-def hotspot_lightcurve(imageplane_spec, params, spots, limb=None, return_records=False):
+def _hotspot_stokes_layout(h, words=None):
+    return _layout([(k, (h.nt,)) for k in ("flux", "sx", "sy", "q", "u")] + [("spectrogram", (h.nt, h.ne))],
+                   [("on_disc", _rounded), ("used", _rounded), ("bad_pol", _rounded), (None, None)], words)
+
+
+def hotspot_stokes_words(h):
+    """Length of the buffer of kr_post_hotspot_stokes_dev_f64 / kr_reduce_hotspot_stokes_dev_f64:
+    [flux | sx | sy | Q | U (nt each) | spec (nt x ne) | on_disc | used | bad_pol | 0]."""
+    return _hotspot_stokes_layout(h)
+
+
+def hotspot_stokes_from_words(h, words):
+    """The buffer of the Stokes hot-spot entry points as a dict: what hotspot_from_words gives (without bad_angle) and q, u (nt: the Stokes sums on the
+    plane's own x and y axes), pol_degree = sqrt(q^2 + u^2) / flux and pol_angle = atan2(u, q) / 2 in radians from the x axis towards the y axis (both
+    NaN where flux == 0), and the tally bad_pol."""
+    out = _hotspot_stokes_layout(h, words)
+    out["time"], out["energy"] = hotspot_times(h), hotspot_energies(h)
+    with np.errstate(all="ignore"):
+        lit = out["flux"] != 0
+        safe = np.where(lit, out["flux"], 1.0)
+        out["x"] = np.where(lit, out["sx"] / safe, np.nan)
+        out["y"] = np.where(lit, out["sy"] / safe, np.nan)
+        out["pol_degree"] = np.where(lit, np.hypot(out["q"], out["u"]) / safe, np.nan)
+        out["pol_angle"] = np.where(lit, 0.5 * np.arctan2(out["u"], out["q"]), np.nan)
+    return out
+
+
+def reduce_hotspot_stokes(spot, rays, spin, inc_deg, pol, limb=None):
+    """kr_reduce_hotspot_stokes_f64: the light curve of one spot with its Stokes sums from host ray records of an image plane that carry their redshift
+    and wrapped phi.  spin: the true spin (the a of the redshift pass with reverse = 1); inc_deg: the plane's inclination; pol, limb: as for
+    stokes_image.  Keplerian gas (V = -1), projradius 0."""
+    _rays_arg(rays, capi.RAY_F64)
+    law, plaw = capi.limb_law(limb if limb is not None else "isotropic"), capi.pol_law(pol)
+    out = np.zeros(hotspot_stokes_words(spot))
+    capi.check(lib(), lib().kr_reduce_hotspot_stokes_f64(spin, -1.0, 1, 0, inc_deg, C.byref(spot), C.byref(law), C.byref(plaw), _ptr(rays), len(rays), _ptr(out)),
+               "kr_reduce_hotspot_stokes")
+    return hotspot_stokes_from_words(spot, out)
+
+
+def hotspot_lightcurve(imageplane_spec, params, spots, limb=None, return_records=False, pol=None):
     """The light curve, centroid track and spectrogram of hot spots on the disc seen on an image plane, resident on the device from start to finish, as
     the kr_hotspot_lightcurve app runs it: ImagePlane ctor + redshift_start -> trace (`params` as for the image app: the stored, negated spin) ->
     redshift + range_phi + the first spot (kr_post_hotspot_dev_f64) -> every further spot on the records that pass left (kr_reduce_hotspot_dev_f64: those
     are isotropic, so several spots need limb=None) into the same buffer.  spots: a capi.HotSpot or a list of them on the same observer times and energy
     grid (anything else is refused; the line energies may differ); their outputs add.  Every spot is validated by the library before the plane is traced.
     Only the words are read back (and, with return_records, the final records: for tests).  Returns hotspot_from_words(...) plus "stats".  The sums are
-    per image-plane pixel: multiply by dx dy / D^2 for a flux."""
+    per image-plane pixel: multiply by dx dy / D^2 for a flux.
+    pol: None, or a polarisation degree law as for stokes_image ((law, coeff), a name of capi.POL_LAWS or a capi.PolLaw): the Stokes light curves.  The
+    first spot goes through kr_post_hotspot_stokes_dev_f64 at the plane's own inclination, every further one through kr_reduce_hotspot_stokes_dev_f64,
+    which takes the limb law too: several spots may then share any limb law.  Returns hotspot_stokes_from_words(...) plus "stats": "q", "u",
+    "pol_degree", "pol_angle" and "bad_pol" join the result (and "bad_angle" leaves it: bad-angle is a subset of bad-pol)."""
     spots = [spots] if isinstance(spots, capi.HotSpot) else list(spots)
     if not spots:
         raise KrError("hotspot_lightcurve: no spot")
@@ -1859,6 +1902,23 @@ def hotspot_lightcurve(imageplane_spec, params, spots, limb=None, return_records
     if any(axes(s) != axes(h) for s in spots):
         raise KrError("hotspot_lightcurve: the spots must share the observer times (nt, t0, dt) and the energy grid (ne, log_e, e_min, de): they add into one buffer")
     law = capi.limb_law(limb if limb is not None else "isotropic")
+    if pol is not None:
+        plaw, spin, inc = capi.pol_law(pol), -1 * imageplane_spec.spin, imageplane_spec.inc_deg
+
+        def stokes_passes(L, dev, d_rays, n, d_out):
+            capi.check(L, L.kr_post_hotspot_stokes_dev_f64(spin, -1.0, 1, 0, 0, -np.pi, np.pi, inc, C.byref(h), C.byref(law), C.byref(plaw), d_rays, n, d_out, None),
+                       "kr_post_hotspot_stokes")
+            for s in spots[1:]:
+                capi.check(L, L.kr_reduce_hotspot_stokes_dev_f64(spin, -1.0, 1, 0, inc, C.byref(s), C.byref(law), C.byref(plaw), d_rays, n, d_out, None),
+                           "kr_reduce_hotspot_stokes")
+
+        words, stats, records = _imageplane_run("hotspot_lightcurve", imageplane_spec, params, hotspot_stokes_words(h), stokes_passes, return_records,
+                                                before=lambda L, dev: stokes_passes(L, dev, None, 0, dev.zeros(8)))
+        res = hotspot_stokes_from_words(h, words)
+        res["stats"] = stats
+        if return_records:
+            res["records"] = records
+        return res
     if len(spots) > 1 and law.law != 0:
         raise KrError("hotspot_lightcurve: several spots need the isotropic law (the further spots go through the reduce form)")
     def passes(L, dev, d_rays, n, d_out):
@@ -1879,9 +1939,12 @@ def hotspot_lightcurve(imageplane_spec, params, spots, limb=None, return_records
 def hotspot_text(res):
     """The file kr_hotspot_lightcurve writes for a result of hotspot_lightcurve(): three comment rows with the tallies ("# ON_DISC", "# USED",
     "# BAD_ANGLE"), one row per observer time: T flux x_c y_c, and, with a spectrogram, one block per observer time after a blank line each: a row
-    T E_mid value per energy bin.  Every field setw(20), the numbers scientific with precision 8 (host/include/text_output.h)."""
-    head = "".join("%20s%20d\n" % (f"# {k.upper()}", res[k]) for k in ("on_disc", "used", "bad_angle"))
-    rows = "".join("".join(_path_field(float(v)) for v in row) + "\n" for row in zip(res["time"], res["flux"], res["x"], res["y"]))
+    T E_mid value per energy bin.  Every field setw(20), the numbers scientific with precision 8 (host/include/text_output.h).  A result that carries
+    Stokes sums (hotspot_lightcurve(pol=...)): the third tally is "# BAD_POL" and the rows are T flux x_c y_c Q U."""
+    stokes = "q" in res
+    head = "".join("%20s%20d\n" % (f"# {k.upper()}", res[k]) for k in ("on_disc", "used", "bad_pol" if stokes else "bad_angle"))
+    columns = [res[k] for k in (("time", "flux", "x", "y", "q", "u") if stokes else ("time", "flux", "x", "y"))]
+    rows = "".join("".join(_path_field(float(v)) for v in row) + "\n" for row in zip(*columns))
     blocks = "".join("\n" + "".join(_path_field(float(t)) + _path_field(float(e)) + _path_field(float(v)) + "\n" for e, v in zip(res["energy"], row))
                      for t, row in zip(res["time"], res["spectrogram"])) if len(res["energy"]) else ""
     return head + rows + blocks

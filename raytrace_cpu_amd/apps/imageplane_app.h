@@ -39,6 +39,16 @@ inline kr_imageplane imageplane(double dist, double incl, double x0, double xmax
     return plane;
 }
 
+// the degree law of kr_pol_law from the keys pol_law = 1 and pol_coeff = 0.1171 (kr_imageplane_polarisation, kr_hotspot_lightcurve)
+inline kr_pol_law pol_law_of(const Options& opt)
+{
+    kr_pol_law pol;
+    memset(&pol, 0, sizeof pol);
+    pol.law = (int32_t) opt.num("pol_law", 1);
+    pol.coeff = opt.num("pol_coeff", 0.1171);
+    return pol;
+}
+
 struct DiscPlaneSetup {
     std::string out_name, integ, arith;
     double dist, incl, plane_phi0, spin, r_disc, r_isco, q1, rb1, q2, rb2, q3, precision, rk45_tol;

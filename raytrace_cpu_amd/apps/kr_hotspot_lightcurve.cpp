@@ -1,6 +1,6 @@
 // apps/kr_hotspot_lightcurve.cpp -- an orbiting hot spot on the disc seen on an image plane, resident on the MI355X from start to finish: the light
 // curve of the flare with its Doppler and lensing peaks, the track of the image centroid, and the energy-time spectrogram of a line emitted by the spot.
-// The rays are generated, traced, redshifted and summed into every observer time in HBM and only the Nt (3 + Nen) + 4 doubles come back
+// The rays are generated, traced, redshifted and summed into every observer time in HBM and only the Nt (3 + Nen) + 4 doubles come back (Nt (5 + Nen) + 4 with Stokes sums)
 // (include/kr_trace.h, kr_hotspot, has the per-ray rule).  The spot is a pattern of enhanced emission on the disc, good for spot_sigma << spot_r; the gas
 // under it keeps its Keplerian orbits.  It is not a body with a four-velocity of its own.
 //
@@ -18,10 +18,14 @@
 //   g_index = 4               weight exponent g^-g_index: 4 bolometric, 3 the specific intensity of a line
 //   limb = 0, limb_coeff = 2.06   limb law of kr_limb_law
 //   line_en = 6.4, e_min = 1, e_max = 10, ne = 0, log_e = 0   the spectrogram's line energy and its ne energy bins (ne = 0: none)
+//   pol_law, pol_coeff        optional, the keys of kr_imageplane_polarisation (pol_law = 1, pol_coeff = 0.1171 when only one of them is given): the
+//                             Stokes light curves Q, U of the spot's emission (kr_post_hotspot_stokes_dev_f64) on the plane's own x and y axes
 // Every key may also be given as --key=value, which takes precedence over the file.  Nx and Ny are read as int, as kr_imageplane_disc_image reads
 // them (before imageplane_app.h: as double, then cast; the same for a key written as a plain integer).
 // Output: TextOutput (width 20, precision 8): three comment rows "# ON_DISC", "# USED", "# BAD_ANGLE" with their counts, one row per observer time:
 // T flux x_c y_c (nan where flux is 0), and with ne > 0 one block per observer time, each after a blank line: a row T E_mid value per energy bin.
+// With pol_law or pol_coeff: the third comment row is "# BAD_POL" (ring records without a polarisation angle, which add to nothing) and every row is
+// T flux x_c y_c Q U.  Without them the file is byte for byte what it was before the keys existed.
 // The sums are per image-plane pixel: multiply by dx dy / dist^2 for a flux.
 #include <cmath>
 #include <iostream>
@@ -40,6 +44,8 @@ static void program(const krapp::Options& opt)
     memset(&limb, 0, sizeof limb);
     limb.law = (int32_t) opt.num("limb", 0);
     limb.coeff = opt.num("limb_coeff", 2.06);
+    const bool stokes = opt.has("pol_law") || opt.has("pol_coeff");
+    const kr_pol_law pol = krapp::pol_law_of(opt);
     s.print_isco();
 
     kr_hotspot h;
@@ -79,9 +85,14 @@ static void program(const krapp::Options& opt)
     krapp::DiscPlaneRun run(s, plane);
     const int nt = h.nt, ne = h.ne;
     if (ne < 0 || ne > 4096 || nt > 4096) throw invalid_argument("nt and ne: at most 4096 each, ne not negative");
-    const int64_t words = (int64_t) nt * (3 + ne) + 4;
+    const int curves = stokes ? 5 : 3;
+    const int64_t words = (int64_t) nt * (curves + ne) + 4;
     run.trace(plane, p, words);
-    krapp::check(kr_post_hotspot_dev_f64(-s.spin, -1.0, 1, 0, 0, -1 * M_PI, M_PI, &h, &limb, run.rays->get(), run.n, run.acc->get(), nullptr), "redshift + range_phi + hot spot");
+    if (stokes)
+        krapp::check(kr_post_hotspot_stokes_dev_f64(-s.spin, -1.0, 1, 0, 0, -1 * M_PI, M_PI, s.incl, &h, &limb, &pol, run.rays->get(), run.n, run.acc->get(), nullptr),
+                     "redshift + range_phi + hot spot with Stokes sums");
+    else
+        krapp::check(kr_post_hotspot_dev_f64(-s.spin, -1.0, 1, 0, 0, -1 * M_PI, M_PI, &h, &limb, run.rays->get(), run.n, run.acc->get(), nullptr), "redshift + range_phi + hot spot");
     vector<double> w((size_t) words);
     krapp::check(kr_memcpy_d2h(w.data(), run.acc->get(), words * (int64_t) sizeof(double)), "d2h");
     const double ms_post = run.clock.lap_ms();
@@ -89,19 +100,23 @@ static void program(const krapp::Options& opt)
     const double* flux = w.data();
     const double* sx = flux + nt;
     const double* sy = sx + nt;
-    const double* spec = sy + nt;
+    const double* sq = sy + nt;                      // (Stokes only)
+    const double* su = sq + nt;
+    const double* spec = flux + (size_t) curves * nt;
     const double* tallies = spec + (size_t) nt * ne;
     cout << static_cast<long>(tallies[0]) << " rays on the disc, " << static_cast<long>(tallies[1]) << " in the spot's ring, " << static_cast<long>(tallies[2])
-         << " without an emission angle (bad-angle)" << endl;
+         << (stokes ? " ring records without a polarisation angle (bad-pol)" : " without an emission angle (bad-angle)") << endl;
     {
         TextOutput outfile(s.out_name);
         outfile << "# ON_DISC" << static_cast<long>(tallies[0]) << endl;
         outfile << "# USED" << static_cast<long>(tallies[1]) << endl;
-        outfile << "# BAD_ANGLE" << static_cast<long>(tallies[2]) << endl;
+        outfile << (stokes ? "# BAD_POL" : "# BAD_ANGLE") << static_cast<long>(tallies[2]) << endl;
         const double nan = numeric_limits<double>::quiet_NaN();
         for (int k = 0; k < nt; ++k) {
             const bool lit = flux[k] != 0;
-            outfile << h.t0 + k * h.dt << flux[k] << (lit ? sx[k] / flux[k] : nan) << (lit ? sy[k] / flux[k] : nan) << endl;
+            outfile << h.t0 + k * h.dt << flux[k] << (lit ? sx[k] / flux[k] : nan) << (lit ? sy[k] / flux[k] : nan);
+            if (stokes) outfile << sq[k] << su[k];
+            outfile << endl;
         }
         for (int k = 0; k < nt && ne > 0; ++k) {
             outfile.newline();

@@ -32,10 +32,7 @@ double evpa_deg_of(double Q, double U) { return 0.5 * atan2(U, Q) * 180 / M_PI; 
 static void program(const krapp::Options& opt)
 {
     const krapp::DiscPlaneSetup s(opt);
-    kr_pol_law pol;
-    memset(&pol, 0, sizeof pol);
-    pol.law = (int32_t) opt.num("pol_law", 1);
-    pol.coeff = opt.num("pol_coeff", 0.1171);
+    const kr_pol_law pol = krapp::pol_law_of(opt);
     kr_limb_law limb;
     memset(&limb, 0, sizeof limb);
     limb.law = (int32_t) opt.num("limb", 0);

@@ -462,6 +462,9 @@ PROTOTYPES = {
     "kr_post_hotspot_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, P(HotSpot), P(LimbLaw), _vp, _i64, _vp, _vp]),
     "kr_reduce_hotspot_dev_f64": (_int, [P(HotSpot), _vp, _i64, _vp, _vp]),
     "kr_reduce_hotspot_f64": (_int, [P(HotSpot), _vp, _i64, _vp]),
+    "kr_post_hotspot_stokes_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, _dbl, P(HotSpot), P(LimbLaw), P(PolLaw), _vp, _i64, _vp, _vp]),
+    "kr_reduce_hotspot_stokes_dev_f64": (_int, [_dbl, _dbl, _int, _int, _dbl, P(HotSpot), P(LimbLaw), P(PolLaw), _vp, _i64, _vp, _vp]),
+    "kr_reduce_hotspot_stokes_f64": (_int, [_dbl, _dbl, _int, _int, _dbl, P(HotSpot), P(LimbLaw), P(PolLaw), _vp, _i64, _vp]),
     "kr_bundles_init_emit_dev_f64": (_int, [P(ImagePlaneSpec), _dbl, _dbl, _int, _int, _vp, _i64, _vp]),
     "kr_post_caustic_disc_dev_f64": (_int, [_dbl, _int, P(CausticMap), _vp, _i64, _vp, _vp]),
     "kr_caustic_suppress_dev_f64": (_int, [P(CausticMap), _vp, _vp]),

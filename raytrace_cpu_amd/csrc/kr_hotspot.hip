@@ -15,8 +15,13 @@
 // The spectrogram: a lane owns its time samples, so within a workgroup row k of spec is written by one lane only.  SPEC 1 keeps the workgroup's
 // [nt x ne] block in LDS (plain read-modify-write by the owning lane, rows padded to an odd stride against bank conflicts) and flushes it once;
 // SPEC 2, above kHotSpecLdsWords, adds to global memory for the pairs with s > 0, which are sparse.  SPEC 0: ne == 0.
-//   hotspot_kernel<FUSED, SLOTS, SPEC>   FUSED: redshift + range_phi + the spot (rays[] ends as after post_line_kernel); otherwise the records carry
-//                                        their redshift and are only read.
+//   hotspot_kernel<FUSED, SLOTS, SPEC, STOKES>   FUSED: redshift + range_phi + the spot (rays[] ends as after post_line_kernel); otherwise the records
+//                                        carry their redshift and are only read.
+// STOKES: the Stokes light curves Q[k], U[k] beside flux, sx, sy (include/kr_trace.h, the Stokes rule under kr_hotspot).  Phase A evaluates polar_value
+// (kr_post_device.hpp) for a record that passed the filter AND the ring -- about one in thirty; its E and mu are frame_value's to the bit, so nothing else
+// changes value -- and the item gains cq = c delta c2 and cu = c delta s2; a bad-pol ring record is tallied and leaves no item.  Phase B keeps two more
+// register sums per slot and reads two more broadcasts per lit pair.  The spectrogram stays intensity only.  Everything of it sits behind if constexpr:
+// the instances without STOKES compile to what they were (profiles/hotspot_stokes_resources.txt).
 // Compiler report (-Rpass-analysis=kernel-resource-usage, gfx950, the flags of _build.py): the table above kHotSpecLdsWords.
 
 #include <hip/hip_runtime.h>
@@ -40,6 +45,8 @@ namespace {
 // 2 x (32 + 23) KiB fit the CU's 160 KiB: the block never lowers the residency the registers allow.  The cosine with its large-argument reduction is what
 // makes these kernels wider than kr_spectrum.hip's.
 // profiles/hotspot_ab.txt has the A/B of the block against global adds and of the register bound.
+// The STOKES instances: 27 KiB of items, so 2 x (32 + 27) KiB, still within the CU's 160 KiB; their registers and bound: profiles/hotspot_stokes_resources.txt
+// and kStokesTwoWaveSlots below.
 constexpr int kHotSpecLdsWords = 4096;
 #ifdef KR_HOTSPOT_SPEC_LDS_WORDS                 // A/B builds only (scripts/hotspot_ab.py)
 constexpr int kSpecBudget = KR_HOTSPOT_SPEC_LDS_WORDS;
@@ -65,6 +72,26 @@ constexpr int kTwoWaveMinSlots = KR_HOTSPOT_TWO_WAVE_MIN_SLOTS;
 #else
 constexpr int kTwoWaveMinSlots = 2;             // (at one slot the bound is a tie or costs 3 ... 5 %: profiles/hotspot_ab.txt (v))
 #endif
+// The Stokes instances carry two more sums per slot and polar_value's live range across phase A: sized freely they take 252 ... 256 VGPRs and some AGPRs
+// at ONE slot already.  Their bound is set by measurement like the one above (profiles/hotspot_stokes_ab.txt): two waves per SIMD up to
+// kStokesTwoWaveSlots slots -- 3.9 against 6.0 ms at two slots, 4.3 against 6.7 at four -- and at one slot too wherever that wins: the fused forms (3.5
+// against 5.4 ms) and the reduce forms with a spectrogram (3.5 against 4.9); the one-slot reduce form without one fits two waves as the compiler sizes it
+// and runs 3 % slower under the bound, so it is left alone.
+#ifdef KR_HOTSPOT_STOKES_TWO_WAVE_SLOTS          // A/B builds only (scripts/hotspot_stokes_ab.py)
+constexpr int kStokesTwoWaveSlots = KR_HOTSPOT_STOKES_TWO_WAVE_SLOTS;
+#else
+constexpr int kStokesTwoWaveSlots = 4;
+#endif
+#ifdef KR_HOTSPOT_STOKES_TWO_WAVE_MIN_SLOTS      // A/B builds only (1: the bound at one slot in every form; 2: in none)
+constexpr int kStokesOneSlotBound = KR_HOTSPOT_STOKES_TWO_WAVE_MIN_SLOTS == 1 ? 1 : 0;
+#else
+constexpr int kStokesOneSlotBound = -1;          // by form: fused, or with a spectrogram
+#endif
+#ifdef KR_HOTSPOT_STOKES_POLAR_ALL               // A/B builds only: the fused Stokes form takes polar_value for EVERY record, not for ring survivors only
+constexpr bool kStokesPolarAll = true;
+#else
+constexpr bool kStokesPolarAll = false;
+#endif
 constexpr double kTwoPi = 6.283185307179586;
 
 // what the kernels need besides the records: the spot by value and what is taken once, on the host
@@ -84,6 +111,21 @@ struct HotItem {
     double psi, om, half, A, B, phi, t, Om, c, cx, cy;
     int ie;
 };
+
+// what the Stokes instances take besides: the sine of the plane's inclination, taken once on the host, and the degree law.  The other instances take
+// an empty struct in its place, so their arguments and their code stay what they were.
+struct StokesDev {
+    double sin_incl;
+    kr_pol_law pol;
+};
+struct NoStokes {};
+
+constexpr int two_wave_bound(int slots, bool stokes, bool fused, int spec)
+{
+    if (!stokes) return slots >= kTwoWaveMinSlots && slots <= kTwoWaveSlots ? 2 : 1;
+    if (slots == 1) return (kStokesOneSlotBound < 0 ? fused || spec != 0 : kStokesOneSlotBound == 1) && kStokesTwoWaveSlots >= 1 ? 2 : 1;
+    return slots <= kStokesTwoWaveSlots ? 2 : 1;
+}
 
 // one ray that passed the filter (and, under a law that needs it, has its angle) -> its item; false: the ray is outside the ring
 template <bool SPARSE>
@@ -116,28 +158,33 @@ KR_DEV bool hotspot_item(const HotDev& D, double r, double phi, double t, double
     return true;
 }
 
-template <bool FUSED, int SLOTS, int SPEC>
-__global__ void __launch_bounds__(kBlock, (SLOTS >= kTwoWaveMinSlots && SLOTS <= kTwoWaveSlots ? 2 : 1))
+template <bool FUSED, int SLOTS, int SPEC, bool STOKES>
+__global__ void __launch_bounds__(kBlock, two_wave_bound(SLOTS, STOKES, FUSED, SPEC))
 hotspot_kernel(typename std::conditional<FUSED, kr_ray_f64, const kr_ray_f64>::type* __restrict__ rays, long long n, double spin, double V, int reverse,
-               int projradius, int motion, double lo, double hi, HotDev D, kr_limb_law law, double* __restrict__ out)
+               int projradius, int motion, double lo, double hi, HotDev D, kr_limb_law law, double* __restrict__ out,
+               typename std::conditional<STOKES, StokesDev, NoStokes>::type S)
 {
     extern __shared__ double lds_spec[];                 // SPEC 1: the workgroup's [nt x nes] block
     __shared__ double it_psi[kBlock], it_om[kBlock], it_half[kBlock];
     __shared__ double it_A[kBlock], it_B[kBlock], it_phi[kBlock], it_t[kBlock], it_Om[kBlock], it_c[kBlock], it_cx[kBlock], it_cy[kBlock];
     __shared__ int it_ie[kBlock];
     __shared__ int wave_count[kBlock / 64];
+    __shared__ double it_cq[STOKES ? kBlock : 1], it_cu[STOKES ? kBlock : 1];       // (one unused word each without STOKES: the compiler drops them)
     constexpr bool SPARSE = SLOTS >= kSparseMinSlots;
     const kr_hotspot& h = D.h;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nt = h.nt, ne = h.ne;
-    double* const g_spec = out + 3 * (size_t) nt;
+    constexpr int kCurves = STOKES ? 5 : 3;              // flux, sx, sy (, Q, U)
+    double* const g_spec = out + kCurves * (size_t) nt;
 
     // phase B's registers: the time samples this lane owns (slot q: sample q kBlock + tid) and their sums
     double T[SLOTS], flux[SLOTS], sx[SLOTS], sy[SLOTS];
+    double sq[STOKES ? SLOTS : 1], su[STOKES ? SLOTS : 1];
 #pragma unroll
     for (int q = 0; q < SLOTS; q++) {
         const int k = q * kBlock + tid;
         T[q] = h.t0 + k * h.dt;
         flux[q] = sx[q] = sy[q] = 0;
+        if constexpr (STOKES) sq[q] = su[q] = 0;
     }
     // slots in which this wave owns a sample at all (wave-uniform)
     const int first = wave * 64;
@@ -148,12 +195,13 @@ hotspot_kernel(typename std::conditional<FUSED, kr_ray_f64, const kr_ray_f64>::t
         __syncthreads();
     }
 
-    unsigned long long on_disc = 0, used = 0, bad_angle = 0;
+    unsigned long long on_disc = 0, used = 0, bad_angle = 0;      // (STOKES: bad_angle holds the bad-pol tally)
     for (long long base = blockIdx.x * (long long) kBlock; base < n; base += (long long) gridDim.x * kBlock) {
         // ---- phase A: one record per lane
         const long long i = base + tid;
         bool live = false;
         HotItem it;
+        double cq = 0, cu = 0;
         // disc_ray and tile_compact (kr_disc_pass.hpp), written out: through the calls the fused two- and four-slot forms, which spill across phase A,
         // and the one-slot reduce forms run 1 ... 3 % slower (profiles/disc_pass_shared_ab.txt)
         if (i < n) {
@@ -161,7 +209,45 @@ hotspot_kernel(typename std::conditional<FUSED, kr_ray_f64, const kr_ray_f64>::t
             double r, theta, g, phi, limb = 1;
             const int steps = ray->steps;
             bool drop = false;
-            if constexpr (FUSED) {
+            if constexpr (STOKES) {
+                // the Stokes rule: filter, then the ring, then polar_value for the survivors (motion is 0: the validator refuses the rest)
+                kr_ray_f64 v;
+                Polar pq;
+                bool have_pq = false;
+                if constexpr (FUSED) {
+                    v = polar_record_of(ray);
+                    if constexpr (kStokesPolarAll) {
+                        pq = polar_value(v, spin, V, reverse, projradius, S.sin_incl);
+                        have_pq = true;
+                        g = pq.redshift;
+                    } else {
+                        const Frame f = frame_value(v, spin, V, reverse, projradius);
+                        g = frame_redshift(f, v.emit, reverse);
+                    }
+                    r = v.r; theta = v.theta;
+                    ray->redshift = g;
+                    phi = wrap_phi(ray, steps, lo, hi);
+                } else {
+                    r = ray->r; theta = ray->theta; g = ray->redshift; phi = ray->phi;
+                }
+                if (disc_filter(h.r_isco, h.r_disc, steps, r, theta, g)) {
+                    on_disc++;
+                    if (__builtin_fabs(r - h.r_spot) < D.ring) {
+                        if constexpr (!FUSED) v = polar_record_of(ray);
+                        if (!have_pq) pq = polar_value(v, spin, V, reverse, projradius, S.sin_incl);
+                        if (pq.bad) {
+                            bad_angle++;
+                        } else {
+                            limb = limb_weight(law.law, law.coeff, pq.mu);
+                            live = hotspot_item<SPARSE>(D, r, phi, ray->t, g, limb, v.alpha, v.beta, &it);
+                            const double cd = it.c * pol_degree(S.pol.law, S.pol.coeff, pq.mu);
+                            cq = cd * pq.c2;
+                            cu = cd * pq.s2;
+                        }
+                    }
+                }
+                drop = true;                             // (the item, if any, is made)
+            } else if constexpr (FUSED) {
                 const kr_ray_f64 v = geodesic_of(ray);
                 r = v.r; theta = v.theta;
                 if (motion == 0) {
@@ -209,6 +295,7 @@ hotspot_kernel(typename std::conditional<FUSED, kr_ray_f64, const kr_ray_f64>::t
             it_psi[at] = it.psi; it_om[at] = it.om; it_half[at] = it.half;
             it_A[at] = it.A; it_B[at] = it.B; it_phi[at] = it.phi; it_t[at] = it.t; it_Om[at] = it.Om;
             it_c[at] = it.c; it_cx[at] = it.cx; it_cy[at] = it.cy; it_ie[at] = it.ie;
+            if constexpr (STOKES) { it_cq[at] = cq; it_cu[at] = cu; }
         }
         __syncthreads();
         // ---- phase B: one time sample per lane and slot, over the tile's live items
@@ -230,6 +317,10 @@ hotspot_kernel(typename std::conditional<FUSED, kr_ray_f64, const kr_ray_f64>::t
                         flux[q] += cs;
                         sx[q] += it_cx[j] * s;
                         sy[q] += it_cy[j] * s;
+                        if constexpr (STOKES) {
+                            sq[q] += it_cq[j] * s;
+                            su[q] += it_cu[j] * s;
+                        }
                         if (SPEC != 0) {
                             const int ie = it_ie[j], k = q * kBlock + tid;
                             if (ie >= 0 && k < nt) {
@@ -252,6 +343,10 @@ hotspot_kernel(typename std::conditional<FUSED, kr_ray_f64, const kr_ray_f64>::t
             if (flux[q] != 0) atomicAdd(&out[k], flux[q]);
             if (sx[q] != 0) atomicAdd(&out[nt + k], sx[q]);
             if (sy[q] != 0) atomicAdd(&out[2 * nt + k], sy[q]);
+            if constexpr (STOKES) {
+                if (sq[q] != 0) atomicAdd(&out[3 * nt + k], sq[q]);
+                if (su[q] != 0) atomicAdd(&out[4 * nt + k], su[q]);
+            }
         }
     }
     if (SPEC == 1) {
@@ -262,7 +357,7 @@ hotspot_kernel(typename std::conditional<FUSED, kr_ray_f64, const kr_ray_f64>::t
             if (v != 0) atomicAdd(&g_spec[w], v);
         }
     }
-    double* const tallies = out + (size_t) nt * (3 + ne);
+    double* const tallies = out + (size_t) nt * (kCurves + ne);
     on_disc = wave_sum(on_disc); used = wave_sum(used); bad_angle = wave_sum(bad_angle);
     if (lane == 0) {
         if (on_disc) atomicAdd(&tallies[0], (double) on_disc);
@@ -287,9 +382,9 @@ HotDev hotspot_dev(const kr_hotspot* h)
     return D;
 }
 
-template <bool FUSED, typename Rays>
+template <bool FUSED, bool STOKES, typename Rays, typename Extra>
 int hotspot_launch(const kr_hotspot* h, const kr_limb_law& law, Rays* d, int64_t n, double spin, double V, int reverse, int projradius, int motion, double lo, double hi,
-                   void* d_out, hipStream_t st)
+                   void* d_out, hipStream_t st, Extra extra)
 {
     if (n <= 0) return KR_OK;
     const HotDev D = hotspot_dev(h);
@@ -299,14 +394,22 @@ int hotspot_launch(const kr_hotspot* h, const kr_limb_law& law, Rays* d, int64_t
     const size_t lds = spec == 1 ? (size_t) block_words * sizeof(double) : 0;
     for_slots(slots, [&](auto K) {
         auto launch = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, st, d, (long long) n, spin, V, reverse, projradius, motion, lo, hi, D, law, (double*) d_out);
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, st, d, (long long) n, spin, V, reverse, projradius, motion, lo, hi, D, law, (double*) d_out, extra);
         };
-        if (spec == 0) launch(hotspot_kernel<FUSED, K.value, 0>);
-        else if (spec == 1) launch(hotspot_kernel<FUSED, K.value, 1>);
-        else launch(hotspot_kernel<FUSED, K.value, 2>);
+        if (spec == 0) launch(hotspot_kernel<FUSED, K.value, 0, STOKES>);
+        else if (spec == 1) launch(hotspot_kernel<FUSED, K.value, 1, STOKES>);
+        else launch(hotspot_kernel<FUSED, K.value, 2, STOKES>);
     });
     KR_LAUNCH_CHECK();
     return KR_OK;
+}
+
+StokesDev stokes_dev(double inc_deg, const kr_pol_law* pol)
+{
+    StokesDev S;
+    S.sin_incl = sin_inclination(inc_deg);
+    S.pol = *pol;
+    return S;
 }
 
 }  // namespace
@@ -336,12 +439,25 @@ int hotspot_validate(const kr_hotspot* h, const char* who)
 int post_hotspot_dev(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_hotspot* h, const kr_limb_law* law, void* d, int64_t n,
                      void* d_out, hipStream_t st)
 {
-    return hotspot_launch<true>(h, *law, (kr_ray_f64*) d, n, spin, V, reverse, projradius, motion, lo, hi, d_out, st);
+    return hotspot_launch<true, false>(h, *law, (kr_ray_f64*) d, n, spin, V, reverse, projradius, motion, lo, hi, d_out, st, NoStokes{});
 }
 
 int reduce_hotspot_dev(const kr_hotspot* h, const void* d, int64_t n, void* d_out, hipStream_t st)
 {
-    return hotspot_launch<false>(h, isotropic_limb(), (const kr_ray_f64*) d, n, 0.0, 0.0, 0, 0, 0, 0.0, 0.0, d_out, st);
+    return hotspot_launch<false, false>(h, isotropic_limb(), (const kr_ray_f64*) d, n, 0.0, 0.0, 0, 0, 0, 0.0, 0.0, d_out, st, NoStokes{});
+}
+
+// the Stokes forms (kr_post_hotspot_stokes_dev_f64, kr_reduce_hotspot_stokes_dev_f64): motion is 0, the validators refuse the rest
+int post_hotspot_stokes_dev(double spin, double V, int reverse, int projradius, double lo, double hi, double inc_deg, const kr_hotspot* h, const kr_limb_law* law,
+                            const kr_pol_law* pol, void* d, int64_t n, void* d_out, hipStream_t st)
+{
+    return hotspot_launch<true, true>(h, *law, (kr_ray_f64*) d, n, spin, V, reverse, projradius, 0, lo, hi, d_out, st, stokes_dev(inc_deg, pol));
+}
+
+int reduce_hotspot_stokes_dev(double spin, double V, int reverse, int projradius, double inc_deg, const kr_hotspot* h, const kr_limb_law* law, const kr_pol_law* pol,
+                              const void* d, int64_t n, void* d_out, hipStream_t st)
+{
+    return hotspot_launch<false, true>(h, *law, (const kr_ray_f64*) d, n, spin, V, reverse, projradius, 0, 0.0, 0.0, d_out, st, stokes_dev(inc_deg, pol));
 }
 
 }  // namespace kr

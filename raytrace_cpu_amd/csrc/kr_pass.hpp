@@ -204,6 +204,11 @@ int hotspot_validate(const kr_hotspot* h, const char* who);
 int post_hotspot_dev(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_hotspot* h, const kr_limb_law* law, void* d, int64_t n,
                      void* d_out, hipStream_t st);
 int reduce_hotspot_dev(const kr_hotspot* h, const void* d, int64_t n, void* d_out, hipStream_t st);
+// the Stokes light curves of the spot (the Stokes rule under kr_hotspot): motion 0 only; the reduce form recomputes the frame of the ring records
+int post_hotspot_stokes_dev(double spin, double V, int reverse, int projradius, double lo, double hi, double inc_deg, const kr_hotspot* h, const kr_limb_law* law,
+                            const kr_pol_law* pol, void* d, int64_t n, void* d_out, hipStream_t st);
+int reduce_hotspot_stokes_dev(double spin, double V, int reverse, int projradius, double inc_deg, const kr_hotspot* h, const kr_limb_law* law, const kr_pol_law* pol,
+                              const void* d, int64_t n, void* d_out, hipStream_t st);
 // kr_angles.hip: the photon's angles in the disc frame (the observer of redshift_dev with motion 0; the validators refuse any other motion, a bad
 // limb law, and nr < 1 or nmu < 1)
 int angles_validate(int motion, const char* who);
