@@ -1327,7 +1327,11 @@ int kr_post_caustic_source_dev_f64(const kr_source_map* m, const void* d_rays, i
  * 4 sin(a)  5 cos(a) (compact polar-angle sincos)  6 a*rcp(b)  7 sqrt(a) (fast-math path)  8 sin  9 cos  10 pow(a,b) (device libm)
  * 11-18 further primitives of the two arithmetic paths (kr_post.hip::arith_probe_kernel)  19 a after 20 000 additions of b (kr_replay.hpp)
  * 20 1.2345678901234567 / ((a a) b), 21 b / (a a) through the assembled reciprocals of one derivative evaluation (kr_device.hpp::StageRecips)
- * 22 acos(a)  23 asin(a)  24 atan2(a, b)  25 tan(a): the correctly rounded routines of the device ImagePlane constructor (kr_crmath.hpp) */
+ * 22 acos(a)  23 asin(a)  24 atan2(a, b)  25 tan(a): the correctly rounded routines of the device ImagePlane constructor (kr_crmath.hpp)
+ * 26-28 work on PAIRS of elements (i even): out[i] is what a lane gets that takes a wave-uniform shortcut of the fast Euler / RK4 step when its guard lets
+ * it, out[i + 1] what the code behind the guard gives for the same operands -- 26 the capped step: step = a[i], num = a[i + 1], m = b[i];  27, 28 the end of
+ * a step at r = a[i], theta = a[i + 1] from theta_prev = b[i + 1] with theta_max = b[i], horizon 1.0625, r_max 1000: 27 the outcome as finished + 2 HORIZON +
+ * 4 crossings + 8 (thetadot_sign flipped) + 16 (phi moved), 28 theta afterwards (kr_post.hip::probe_step_end) */
 int kr_debug_arith_f64(int op, const double* a, const double* b, double* out, int64_t n);
 
 /* ---- a long-lived host ray array (what Raytracer<T> holds as `rays`) ----------------------------- */

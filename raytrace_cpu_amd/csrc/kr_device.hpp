@@ -23,16 +23,37 @@
 #include "../../include/kr_trace.h"
 #include "kr_arith.hpp"
 
+// The wave-uniform guards of the fast Euler / RK4 step with a theta-limit stop (step_fixed): each puts work that nearly every step of nearly every ray
+// does for nothing behind ONE ballot, and is exact -- a wave with a lane that fails it runs the code as it was, a lane that passes provably gets what
+// that code gives.  KR_UNIFORM_GUARDS: which of them the library is built with (a sum of UniformGuards; 0: the step as it was -- A/B builds).
+// KR_GUARD_STATS=1 (diagnostic builds only, like KR_OCC_STATS): how many wave-steps each guard lets through, printed by trace_wait.
+#ifndef KR_UNIFORM_GUARDS
+#define KR_UNIFORM_GUARDS 3
+#endif
+#ifndef KR_GUARD_STATS
+#define KR_GUARD_STATS 0
+#endif
+
 namespace kr {
+
+enum UniformGuards { kGuardQuiet = 1, kGuardCap = 2 };
+// KR_GUARD_STATS: {wave-steps at the site, of them all lanes pass} for the quiet guard [0, 1], "N >= 0 and R > 0" in k1 [2, 3] (counted only) and the
+// cap guard [4, 5]; {wave-steps, all lanes in sine band 0, all in band 1} [6..8] (counted only)
+constexpr int kGuardStatWords = 9;
 
 // ---- per-launch constants (kernarg) -----------------------------------------------------------
 template <typename T> struct TraceConsts {
     T a, horizon, rlim, thetalim;
-    T precision, theta_precision, max_tstep, maxtstep_rlim, max_phistep, tol;
+    // theta_in_lo = max(theta_lo, 0), theta_in_hi = min(theta_hi, pi): the loop condition's theta interval (below) cut to [0, pi], where reflect_poles
+    // leaves an angle alone -- the quiet-step guard of the fast Euler / RK4 step (step_fixed).  A NaN thetalim: (0, -inf), empty like (theta_lo, theta_hi).
+    // (They stand where maxtstep_rlim and max_phistep stood, which no kernel read -- tstep_rlim_eff and phistep_eff are what the step compares against --
+    // so every other member, and every kernel argument after the struct, keeps its offset.)
+    T precision, theta_precision, max_tstep, theta_in_lo, theta_in_hi, tol;
     T sp0, sp1, sp2, sp3;   // stop_params
     T inv_precision, inv_theta_precision;   // RN(1/precision), RN(1/theta_precision): fast path, and div_by_uniform on the strict one
     bool inv_ok;                            // both divisors qualify for div_by_uniform
     bool rk45_extrapolate;                  // RK45: creeping captured rays are extrapolated to the step limit (default)
+    bool equator_inside;                    // theta_in_lo < pi/2 < theta_in_hi: a step that ends inside the interval may still have crossed the equator
     int32_t steplim;
     int32_t stop_kind;
     // The optional clauses of the step heuristic ("if (max_tstep > 0 && r < maxtstep_rlim) ...", "if (max_phistep > 0) ...", "if (rlim > 0 && ...)",
@@ -49,6 +70,18 @@ template <typename T> struct TraceConsts {
     // tl > 0: (-inf, tl);  tl < 0: (|tl|, +inf);  tl == 0: (-inf, +inf);  NaN: empty (theta_hi = -inf)
     T theta_lo, theta_hi;
 };
+
+// the members that follow from thetalim alone (make_consts on the host; the probe kernel of kr_post.hip on the device)
+template <typename T>
+__host__ __device__ inline void set_theta_limits(TraceConsts<T>& c)
+{
+    const T inf = (T) __builtin_inf();
+    c.theta_lo = c.thetalim < 0 ? -c.thetalim : -inf;
+    c.theta_hi = c.thetalim > 0 ? c.thetalim : (c.thetalim <= 0 ? inf : -inf);
+    c.theta_in_lo = c.theta_lo > 0 ? c.theta_lo : T(0);
+    c.theta_in_hi = c.theta_hi < T(kPi) ? c.theta_hi : T(kPi);
+    c.equator_inside = c.theta_in_lo < T(kPi2) && T(kPi2) < c.theta_in_hi;
+}
 
 // ---- per-lane ray state ---------------------------------------------------------------------
 template <typename T> struct Lane {
@@ -72,7 +105,27 @@ template <typename T> struct Lane {
     // RK45, strict arithmetic: what the accepted trial's last stage (k7) already knows about the point the next step's k1 is taken at
     bool fsal_valid;
     T f_sin2theta, f_rhosq, f_delta, f_pt, f_thetadotsq, f_abs_ptheta;
+#if KR_GUARD_STATS
+    unsigned long long guard_stats[kGuardStatWords];      // this lane's tallies (trace_body zeroes and sums them): a wave-step is counted by its first active lane
+#endif
 };
+
+#if KR_GUARD_STATS
+// word: the site's "wave-steps" word; pass0 / pass1: this lane passes (the site's first / second "all lanes" word; the second only where the site has one)
+template <typename T> KR_DEV void guard_count(Lane<T>& s, int word, bool pass0, bool pass1 = false, bool two = false)
+{
+    const unsigned long long active = __builtin_amdgcn_ballot_w64(true);
+    const bool all0 = __builtin_amdgcn_ballot_w64(!pass0) == 0, all1 = __builtin_amdgcn_ballot_w64(!pass1) == 0;
+    if ((int) (threadIdx.x & 63) == __ffsll((long long) active) - 1) {
+        ++s.guard_stats[word];
+        if (all0) ++s.guard_stats[word + 1];
+        if (two && all1) ++s.guard_stats[word + 2];
+    }
+}
+#define KR_GUARD_COUNT(...) guard_count(__VA_ARGS__)
+#else
+#define KR_GUARD_COUNT(...) ((void) 0)
+#endif
 
 // The NEG_ENERGY flag, (1 - 2r/rho^2) tdot + (2 a r sin^2/rho^2) phidot < 0 (raytracer.cpp:264-273 / :874-887 / :1403-1410), is the conserved energy k
 // evaluated from tdot and phidot.  Its two terms are <= ~(r^2 + a^2)^2 (k + |h| / r) / (rho^2 Delta) in size, so their rounding errors (1e-16 of the terms)
@@ -281,6 +334,15 @@ KR_DEV bool loop_cond(const Lane<T>& s, const TraceConsts<T>& c)
     return ok;
 }
 
+// The quiet-step guard of the fast theta-limit step (step_fixed has the argument): true only for a lane that every test at the end of the step answers
+// with "no" -- no pole reflection, no horizon, the loop condition holds.  A NaN fails it.
+// (theta_in_lo, theta_in_hi: TraceConsts' pair, from wherever the instance keeps it.  "&": five compares and their scalar ands, no short-circuit branches.)
+template <typename T>
+KR_DEV bool quiet_step(const Lane<T>& s, const TraceConsts<T>& c, T theta_in_lo, T theta_in_hi)
+{
+    return (s.r > c.horizon) & (s.r < c.rlim) & (s.theta > theta_in_lo) & (s.theta < theta_in_hi) & (s.steps < c.steplim);
+}
+
 // KR_STOP_THICKDISC (include/kr_trace.h has the rule, one IEEE operation per line): the point (r, theta) against the body |z| <= H(rho) over
 // r_in <= rho <= r_out.  False: out of range, nothing else is set.  |r| < r_in implies |rho| = |RN(r sin)| <= |r| < r_in (|sin| <= 1, rounding is
 // monotone), which is out of range whatever theta is: that test comes before any trigonometry -- it is the answer for every ray inside r_in,
@@ -401,7 +463,7 @@ template <bool CARRIED> using LaunchRegsOf = std::conditional_t<CARRIED, FastLau
 
 // What a kernel instance carries through its step loop (trace_body's STEP_REGS, a sum of these): a group that is not carried reaches the step as the
 // launch constant / literal it always was, and the step compiles to what it was without.
-enum StepRegs { kStepSigns = 1, kStepTimeCap = 2, kStepNearLead = 4, kStepRegsAll = 7 };
+enum StepRegs { kStepSigns = 1, kStepTimeCap = 2, kStepNearLead = 4, kStepQuiet = 8, kStepRegsAll = 15 };
 
 template <int WHAT> KR_DEV FastLaunchRegs fast_launch_regs(const TraceConsts<double>& c)
 {
@@ -410,6 +472,8 @@ template <int WHAT> KR_DEV FastLaunchRegs fast_launch_regs(const TraceConsts<dou
     // (opaque to the compiler from here on, as consts_into_vector_registers' are: values in vector registers, neither uniform nor constant)
     if constexpr ((WHAT & kStepTimeCap) != 0) asm("" : "+v"(l.tstep_rlim), "+v"(l.tstep_lo), "+v"(l.tstep_on_hi), "+v"(l.tstep_off_hi));
     if constexpr ((WHAT & kStepNearLead) != 0) asm("" : "+v"(l.near_s9), "+v"(l.near_c8));
+    l.theta_in_lo = c.theta_in_lo; l.theta_in_hi = c.theta_in_hi; l.equator_inside = c.equator_inside;
+    if constexpr ((WHAT & kStepQuiet) != 0) asm("" : "+v"(l.theta_in_lo), "+v"(l.theta_in_hi));
     return l;
 }
 
@@ -423,6 +487,8 @@ KR_DEV bool step_fixed(Lane<T>& s, const TraceConsts<T>& c, const FastRayConsts*
 {
     const T a = c.a;
     ++s.steps;
+    // (the wave-uniform guards: the theta-limit instances only -- the RayDestination RK4 kernels sit on their register ceiling with scratch in use, and stay as they are)
+    constexpr int kGuards = (FAST && !USE_DEST && sizeof(T) == 8) ? (KR_UNIFORM_GUARDS) : 0;
 
     T step;
     T pt1, pr1, ptheta1, pphi1;
@@ -452,11 +518,29 @@ KR_DEV bool step_fixed(Lane<T>& s, const TraceConsts<T>& c, const FastRayConsts*
             const uint32_t dt_hi = capped ? (lr ? lr->tstep_on_hi : c.tstep_on_hi) : (lr ? lr->tstep_off_hi : c.tstep_off_hi);
             const T dt_eff = __builtin_bit_cast(double, ((unsigned long long) dt_hi << 32) | (lr ? lr->tstep_lo : c.tstep_lo));
             const T num = __builtin_fmin(dt_eff * aphi, c.phistep_eff * apt);
-            step = __builtin_fmin(step, num * fast_rcp_heur(apt * aphi));
+            const T m = apt * aphi;
+            if constexpr ((kGuards & kGuardCap) != 0) {
+                // The reciprocal chain only in a wave in which the cap can bind on some lane (cap_cannot_bind, kr_fast.hpp, has the proof).
+                const bool free_lane = cap_cannot_bind(step, m, num);
+                KR_GUARD_COUNT(s, 4, free_lane);
+                if (__builtin_expect(__builtin_amdgcn_ballot_w64(!free_lane) != 0, false)) {
+                    asm volatile("");        // (as for the ERGO block below)
+                    step = __builtin_fmin(step, num * fast_rcp_heur(m));
+                }
+            } else {
+                step = __builtin_fmin(step, num * fast_rcp_heur(m));
+            }
         }
         // "if (step < MIN_STEP) step = MIN_STEP" as v_max: differs from the comparison only when `step` is NaN, i.e. when r or rdot is -- and
         // then r is NaN after this step whatever its length
-        step = __builtin_fmax(step, T(KR_MIN_STEP));
+        if constexpr ((kGuards & kGuardCap) != 0) {
+            // (the instruction itself: `step` may now reach this line straight from the select above, and the compiler then puts a canonicalising
+            // v_max step, step in front of fmax.  That one only quiets a signalling NaN -- fp64 subnormals are kept -- and `step` is the result of an
+            // arithmetic instruction on every path: the same bits without it.)
+            asm("v_max_f64 %0, %1, %2" : "=v"(step) : "v"(step), "s"(T(KR_MIN_STEP)));
+        } else {
+            step = __builtin_fmax(step, T(KR_MIN_STEP));
+        }
         // the two landing clips apply on a ray's LAST step only: one fused test each, the clip itself behind a wave-uniform branch (the empty
         // asm keeps the compiler from turning the branch back into unconditional arithmetic and selects).  The clipped step is the reference's
         // correctly rounded quotient: it decides whether theta + thetadot step lands ON the limit or an ulp short of it (= one more step).
@@ -611,7 +695,27 @@ KR_DEV bool step_fixed(Lane<T>& s, const TraceConsts<T>& c, const FastRayConsts*
             s.phi += w * (acc_phi + pphi4);
         }
     }
-    if (crossed_equator(theta_prev, s.theta)) ++s.eq_cross;
+    if constexpr ((kGuards & kGuardQuiet) != 0) {
+        // The quiet step: a lane whose new point lies strictly inside (horizon, rlim) x (theta_in_lo, theta_in_hi) with steps to spare fails every test
+        // below -- 0 <= theta_in_lo < theta < theta_in_hi <= pi: no pole reflection; r > horizon; the loop condition holds term by term (theta_in_hi <=
+        // theta_hi, theta_in_lo >= theta_lo) -- and, where the interval does not contain pi/2, cannot have crossed the equator either: theta_prev passed
+        // the loop condition before this step (at the claim or at the end of the step before; the early return above moves nothing).  With theta_in_hi <=
+        // pi/2 that limit IS theta_hi, so theta_prev < pi/2 and theta < pi/2; with theta_in_lo >= pi/2 it IS theta_lo, so both are > pi/2: either
+        // clause of crossed_equator wants one angle on each side, or the new one ON pi/2.  A NaN r or theta fails the guard.
+        // One ballot of the lanes that are not quiet: empty in every wave-step in which no ray ends or is reflected, and then the block below is
+        // skipped; else it runs as it is, for every lane (a quiet lane gets its "no" from each test).
+        // Where the interval does contain pi/2 (launch-uniform: TraceConsts::equator_inside) the equator test stays in front of the guard -- four
+        // compares and the guard's five instead of twelve; those launches count a crossing where they did.
+        const bool equator_inside = lr ? lr->equator_inside : c.equator_inside;
+        if (equator_inside) { if (crossed_equator(theta_prev, s.theta)) ++s.eq_cross; }
+        const bool quiet = quiet_step(s, c, lr ? lr->theta_in_lo : c.theta_in_lo, lr ? lr->theta_in_hi : c.theta_in_hi);
+        KR_GUARD_COUNT(s, 0, quiet);
+        if (__builtin_expect(__builtin_amdgcn_ballot_w64(!quiet) == 0, true)) return false;
+        asm volatile("");
+        if (!equator_inside) { if (crossed_equator(theta_prev, s.theta)) ++s.eq_cross; }
+    } else {
+        if (crossed_equator(theta_prev, s.theta)) ++s.eq_cross;
+    }
     reflect_poles<T, LONE>(s.theta, s.phi, s.thetadot_sign, sg ? &sg->thetadot : nullptr);
 
     if (s.r <= c.horizon) { s.status |= KR_STATUS_HORIZON; return true; }

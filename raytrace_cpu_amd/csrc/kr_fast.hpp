@@ -33,6 +33,25 @@ KR_DEV double fast_rcp_heur(double x)
 }
 KR_DEV float fast_rcp_heur(float x) { return fast_rcp(x); }
 
+// The step heuristic's shared time / azimuth cap, step = v_min(step, num * fast_rcp_heur(m)), leaves `step` as it is on a lane for which
+//     g = RN(step m + A)  <=  n' = RN(num K),      K = 1 - 2^-40, A = 2^-1000 (both exact; the sum is ONE fused operation)
+// -- "step m (1 + 2^-40) <= num" with the margin on num's side and an absolute term, so that no underflow of a product can eat the margin.  By
+// construction m = |tdot| max(|phidot|, 1e-300) and num = min(dt |phidot|, dphi |tdot|) are >= +0 or NaN.  For a lane that passes:
+//   * nothing is NaN (a NaN step, m or num, or 0 x inf, makes the compare false).  If step < 0 no quotient >= 0 lowers it; so let step >= 0.
+//   * the exact sum step m + A is >= A, a normal number: g >= (step m + A)(1 - 2^-53) >= A (1 - 2^-53).  Hence n' >= A / 2: num K did not underflow,
+//     n' <= num K (1 + 2^-53) (or num = n' = +inf), and  num >= step m (1 - 2^-53) / ((1 - 2^-40)(1 + 2^-53)) > step m (1 + 2^-41),  num > 0.
+//   * m = +0, or so small that v_rcp_f64 overflows: y = fast_rcp_heur(m) is NaN (inf - inf in its Newton step) or +inf, the quotient q = RN(num y) NaN
+//     or +inf, and v_min(step, q) = step (v_min ignores a NaN operand).  m = +inf: y is NaN likewise.
+//   * otherwise y = (1 + e) / m, |e| <= 2^-44: one Newton step on the 2^-23 seed gives 2^-46 and three roundings; a subnormal y (m > 2^1022; fp64
+//     subnormals are not flushed) keeps 2^-50 of its value.  So num y > step (1 + 2^-41)(1 - 2^-44) > step IN EXACT ARITHMETIC; rounding is monotone
+//     and `step` is a double, so q = RN(num y) >= step whatever q's own rounding or underflow does, and v_min(step, q) = step.
+// A lane that fails proves nothing, and its wave takes the reciprocal chain as before.  Cost v_mul, v_fma, v_cmp against v_rcp_f64 (a quarter-rate
+// instruction: four issue slots), two v_fma, v_mul and v_min.
+KR_DEV bool cap_cannot_bind(double step, double m, double num)
+{
+    return __builtin_fma(step, m, 0x1p-1000) <= num * 0x1.fffffffffep-1;
+}
+
 // max(|x|, 1e-300) as ONE v_max_f64 with the |.| source modifier.  (Left to the compiler, fmax(fabs(x), c) on a value that has been through
 // an integer operation or a select costs a v_and, a v_mov and a canonicalising v_max x, x first: four instructions, twice per k1.)
 KR_DEV double abs_floor(double x)
@@ -111,7 +130,10 @@ struct FastRaySigns { double rdot, thetadot; };
 // reads back from spilled scalar registers (v_readlane), or builds in vector registers again in every step (v_mov).
 //   tstep_rlim, tstep_lo, tstep_on_hi, tstep_off_hi   TraceConsts::tstep_rlim_eff / tstep_lo / tstep_on_hi / tstep_off_hi (the time cap's select)
 //   near_s9, near_c8                    1/9! and 1/8!: the leading Horner coefficients of sincos_near, whose first step has two constant operands
-struct FastLaunchRegs { double tstep_rlim, near_s9, near_c8; uint32_t tstep_lo, tstep_on_hi, tstep_off_hi; };
+//   theta_in_lo, theta_in_hi            TraceConsts' pair (the quiet-step guard): the RK4 kernels have no scalar registers left for them
+//   equator_inside                      TraceConsts' flag, read ONCE (a scalar; never made opaque): the merged kernels, which read their constants through
+//                                       a pointer, otherwise load the byte again in every step
+struct FastLaunchRegs { double tstep_rlim, near_s9, near_c8, theta_in_lo, theta_in_hi; uint32_t tstep_lo, tstep_on_hi, tstep_off_hi; bool equator_inside; };
 
 KR_DEV FastPotentials potentials_fast(double& pt, double& pphi, double k, double h, double Q, const FastRayConsts& f, double r, double s, double c, double a)
 {
@@ -197,11 +219,24 @@ KR_DEV void sincos_near(double s0, double c0, double d, double& s, double& c, co
 }
 
 // k1 with the turning-point logic (see k1_with_flips) on the fast path.  sg (optional): the ray's signs as doubles, flipped here with the integers.
+// (Its four compares stay on every step.  Behind a ballot of "N >= 0 and R > 0 on every lane", true in nearly every wave-step, the compiler keeps a
+// compare AND its negation and adds register moves where the arms join: 0 to +2 vector instructions on the hot path instead of -2.
+// profiles/uniform_guards_ab.txt.)
+#if KR_GUARD_STATS
+// (counted only: bands of theta strictly inside quadrants 0 and 1 of kr_sincos_fast_core_f64's reduction, in which k1's sine / cosine could do without it)
+constexpr double kSinBand0 = 0.78, kSinBand1Lo = 0.79, kSinBand1Hi = 2.35;
+#endif
 KR_DEV bool k1_with_flips_fast(Lane<double>& s, double a, const FastRayConsts& f, FastAux& aux, FastRaySigns* sg = nullptr)
 {
     double sn, c;
     kr_sincos_fast_f64(s.theta, sn, c);
     const FastPotentials o = potentials_fast(s.pt, s.pphi, s.k, s.h, s.Q, f, s.r, sn, c, a);
+#if KR_GUARD_STATS
+    if (sg) {       // (the theta-limit Euler / RK4 step)
+        guard_count(s, 2, o.N >= 0 && o.R > 0);
+        guard_count(s, 6, __builtin_fabs(s.theta) <= kSinBand0, s.theta >= kSinBand1Lo && s.theta <= kSinBand1Hi, true);
+    }
+#endif
     // thetadot^2 = N / rho^4 and rdot^2 = R / rho^4 have the signs of N and R
     if (o.N < 0 && s.theta_was_positive) {
         s.thetadot_sign = -s.thetadot_sign;

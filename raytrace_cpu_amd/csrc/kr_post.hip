@@ -418,9 +418,50 @@ reduce_return_multi_kernel(ReturnChunk c, double lo, double hi)
 
 // ---- diagnostics: the device arithmetic primitives the trace kernel is built from, exposed one at a time so that a
 //      test can compare them with the host's IEEE results (tests/test_gpu_primitives.py) ------------------------------
+// The end of a fast theta-limit step (kr_device.hpp::step_fixed) for ONE lane: the new point (r, theta) after a step from theta_prev, in a launch with
+// theta_max = thetalim, horizon 1.0625, r_max 1000 and steps to spare.  guarded: the lane leaves through the quiet-step guard if it passes it.
+// what 0: finished + 2 x HORIZON + 4 x equator crossings + 8 x (thetadot_sign flipped) + 16 x (phi moved);  what 1: theta afterwards
+KR_DEV double probe_step_end(double r, double theta, double thetalim, double theta_prev, bool guarded, int what)
+{
+    TraceConsts<double> c{};
+    c.horizon = 1.0625; c.rlim = 1000.0; c.thetalim = thetalim; c.steplim = 2;
+    set_theta_limits(c);
+    Lane<double> s{};
+    s.r = r; s.theta = theta; s.thetadot_sign = 1; s.steps = 1;
+    bool fin = false, left = false;
+    if (c.equator_inside || !guarded) { if (crossed_equator(theta_prev, s.theta)) ++s.eq_cross; }
+    if (guarded && quiet_step(s, c, c.theta_in_lo, c.theta_in_hi)) left = true;
+    if (!left) {
+        if (guarded && !c.equator_inside) { if (crossed_equator(theta_prev, s.theta)) ++s.eq_cross; }
+        if (theta < 0.0 || theta > kPi) {       // reflect_poles for one lane (its ballot is a whole wave's)
+            if (s.theta < 0.0) { s.theta = -s.theta; s.thetadot_sign = -s.thetadot_sign; s.phi += kPi; }
+            if (s.theta > kPi) { s.theta = 2.0 * kPi - s.theta; s.thetadot_sign = -s.thetadot_sign; s.phi += kPi; }
+        }
+        if (s.r <= c.horizon) { s.status |= KR_STATUS_HORIZON; fin = true; }
+        else fin = !loop_cond<double, false>(s, c);
+    }
+    if (what == 1) return s.theta;
+    return (fin ? 1.0 : 0.0) + ((s.status & KR_STATUS_HORIZON) ? 2.0 : 0.0) + 4.0 * s.eq_cross + (s.thetadot_sign < 0 ? 8.0 : 0.0) + (s.phi != 0.0 ? 16.0 : 0.0);
+}
+
 __global__ void __launch_bounds__(kBlock) arith_probe_kernel(int op, const double* __restrict__ a, const double* __restrict__ b, double* __restrict__ out, long long n)
 {
     KR_GRID_STRIDE(i, n) {
+        if (op >= 26 && op <= 28) {
+            // the wave-uniform guards of the fast step, lane by lane, in PAIRS of elements: out[i] is what a lane that takes the shortcut gets,
+            // out[i + 1] what the code behind the guard gives for the same operands (i even)
+            if ((i & 1) || i + 1 >= n) continue;
+            if (op == 26) {         // the cap guard: step = a[i], num = a[i + 1], m = b[i]
+                const double step = a[i], num = a[i + 1], m = b[i];
+                const double today = __builtin_fmin(step, num * fast_rcp_heur(m));
+                out[i] = cap_cannot_bind(step, m, num) ? step : today;
+                out[i + 1] = today;
+            } else {                // 27, 28: the quiet-step guard: r = a[i], theta = a[i + 1], theta_max = b[i], theta_prev = b[i + 1]
+                out[i] = probe_step_end(a[i], a[i + 1], b[i], b[i + 1], true, op - 27);
+                out[i + 1] = probe_step_end(a[i], a[i + 1], b[i], b[i + 1], false, op - 27);
+            }
+            continue;
+        }
         const double x = a[i], y = b[i];
         double r = 0, s, c;
         switch (op) {

@@ -62,7 +62,8 @@ TraceConsts<T> make_consts(const kr_params* p, int steplim)
     TraceConsts<T> c;
     c.a = (T) p->spin; c.horizon = (T) p->horizon; c.rlim = (T) p->r_max; c.thetalim = (T) p->theta_max;
     c.precision = (T) p->precision; c.theta_precision = (T) p->theta_precision;
-    c.max_tstep = (T) p->max_tstep; c.maxtstep_rlim = (T) p->maxtstep_rlim; c.max_phistep = (T) p->max_phistep;
+    c.max_tstep = (T) p->max_tstep;
+    const T maxtstep_rlim = (T) p->maxtstep_rlim, max_phistep = (T) p->max_phistep;
     c.tol = (T) p->rk45_tol;
     c.sp0 = (T) p->stop_params[0]; c.sp1 = (T) p->stop_params[1]; c.sp2 = (T) p->stop_params[2]; c.sp3 = (T) p->stop_params[3];
     c.inv_precision = (T) (1.0 / p->precision);
@@ -81,16 +82,15 @@ TraceConsts<T> make_consts(const kr_params* p, int steplim)
     c.steplim = steplim;
     c.stop_kind = p->stop_kind;
     const T inf = std::numeric_limits<T>::infinity();
-    c.theta_lo = c.thetalim < 0 ? std::fabs(c.thetalim) : -inf;
-    c.theta_hi = c.thetalim > 0 ? c.thetalim : (c.thetalim <= 0 ? inf : -inf);
-    c.tstep_rlim_eff = c.max_tstep > 0 ? c.maxtstep_rlim : -inf;
+    set_theta_limits(c);
+    c.tstep_rlim_eff = c.max_tstep > 0 ? maxtstep_rlim : -inf;
     {
         unsigned long long bits;
         const double mt = (double) p->max_tstep;
         std::memcpy(&bits, &mt, sizeof bits);
         c.tstep_lo = (uint32_t) bits; c.tstep_on_hi = (uint32_t) (bits >> 32); c.tstep_off_hi = 0x7FE00000u;
     }
-    c.phistep_eff = c.max_phistep > 0 ? c.max_phistep : inf;
+    c.phistep_eff = max_phistep > 0 ? max_phistep : inf;
     return c;
 }
 

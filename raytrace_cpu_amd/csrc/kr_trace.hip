@@ -914,6 +914,13 @@ int trace_wait(void* ticket, kr_stats* stats)
                                    100.0 * q[9] / q[8], q[9] ? (double) q[10] / (64.0 * q[9]) : 0.0, q[11], q[11] ? (double) q[12] / q[11] : 0.0, q[kLongest]);
         }
 #endif
+#if KR_GUARD_STATS
+        {
+            const unsigned long long* q = host_block(ws, kMainBlock) + kGuardStatWord;
+            if (q[2]) std::fprintf(stderr, "kr_guards: main launch wave-steps %llu | quiet: at %llu all %llu | turn: at %llu all %llu | cap: at %llu all %llu | sine band: at %llu all-0 %llu all-1 %llu\n",
+                                   q[2], q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], q[8]);
+        }
+#endif
         stats->rays_total = ws->n;
         stats->rays_strict_side = (int64_t) (host_block(ws, kSplitBlock)[kFlagged] + host_block(ws, kSplitBlock)[kRadial]);
         stats->rays_traced = (int64_t) h[kTraced];

@@ -29,8 +29,9 @@ namespace {
 // measured worse: four lone waves on one CU slow one another down more than nine waves of the main launch do; profiles/r03_ab_experiments.txt.)
 constexpr int kTraceBlock = 64;
 // A wave goes back to the queue when at least this many of its lanes are free (or none holds a ray).  The refill / finish / store code runs with
-// only the free lanes active, ~500 vector instructions per visit -- as much as an RK4 step: visiting for every single finished lane cost the image
-// plane (1.25 lanes per visit) 11 % and the Euler launches 26 %; waiting for 4 leaves ~1.5 lanes of 64 idle on average.
+// only the free lanes active: ~90 vector instructions per visit (92 in the RK4 main kernel's listing, a quarter of an RK4 step; ~500 when this was
+// measured) and a round trip to memory.  Visiting for every single finished lane cost the image plane (1.25 lanes per visit) 11 % and the Euler launches
+// 26 %; waiting for 4 leaves ~1.5 lanes of 64 idle on average.
 // Measured 1 -> 4 (8 is the same): image plane 170.4 -> 151.7 ms, Euler 1e7 rays 55.2 -> 40.8, returning radiation 318 -> 307, headline 81.8 -> 80.7,
 // RK45 412 -> 406 (profiles/r02_ab_experiments.txt).
 #ifndef KR_REFILL_MIN
@@ -46,7 +47,8 @@ enum CounterWord { kHead, kTraced, kSteps, kAttempts, kRejects, kStationary, kEx
                    // in the split bookkeeping block only (classify_kernel): the ill-conditioned rays that are not radial, the radial ones (both counts
                    // run on past what their lists hold), and whether either list overflowed
                    kFlagged = kTraced, kRadial = kSteps, kListsOverflowed = kAttempts };
-constexpr int kCounters = KR_OCC_STATS ? 13 : kCounterWords;         // words per block; KR_OCC_STATS builds: [8..12] occupancy sums
+constexpr int kGuardStatWord = 13;                                   // KR_GUARD_STATS builds: [13..21] the guards' tallies (kr_device.hpp: kGuardStatWords)
+constexpr int kCounters = KR_GUARD_STATS ? kGuardStatWord + kGuardStatWords : KR_OCC_STATS ? 13 : kCounterWords;         // words per block; KR_OCC_STATS builds: [8..12] occupancy sums
 constexpr int kRecorderWord = kCounters;                             // a launch with a recorder: the recorder's words from kRecorderWord on (at_exit)
 
 template <typename T> struct RayOf;
@@ -118,8 +120,8 @@ KR_DEV void trace_body(typename RayOf<T>::type* __restrict__ rays, long long n, 
     // The theta-limit ones among them also keep the ray's two signs as doubles (per ray, beside ray_consts) and a few of the launch's values in vector
     // registers (once, here): what k1 otherwise converts, reads back from spilled scalars or builds again in every step (kr_fast.hpp: FastRaySigns,
     // FastLaunchRegs).  Every other instance: empty structs.
-    constexpr int kStepRegs = (kRayConsts && !USE_DEST) ? (STEP_REGS & (METHOD == KR_RK4 ? kStepRegsAll : ~kStepNearLead)) : 0;      // (Euler has no stages)
-    constexpr bool kSigns = (kStepRegs & kStepSigns) != 0, kLaunchRegs = (kStepRegs & (kStepTimeCap | kStepNearLead)) != 0;
+    constexpr int kStepRegs = (kRayConsts && !USE_DEST) ? (STEP_REGS & (METHOD == KR_RK4 ? kStepRegsAll : ~(kStepNearLead | kStepQuiet))) : 0;      // (Euler has no stages, and scalar registers to spare)
+    constexpr bool kSigns = (kStepRegs & kStepSigns) != 0, kLaunchRegs = kRayConsts && !USE_DEST;      // (always: FastLaunchRegs also holds what is merely read once -- equator_inside)
     [[maybe_unused]] RaySignsOf<kSigns> ray_signs;
     [[maybe_unused]] LaunchRegsOf<kLaunchRegs> launch_regs;
     if constexpr (kLaunchRegs) launch_regs = fast_launch_regs<kStepRegs>(c);
@@ -133,6 +135,9 @@ KR_DEV void trace_body(typename RayOf<T>::type* __restrict__ rays, long long n, 
 
 #if KR_OCC_STATS
     unsigned long long occ_iters = 0, occ_tail_iters = 0, occ_tail_steps = 0, occ_refills = 0, occ_refill_lanes = 0;
+#endif
+#if KR_GUARD_STATS
+    for (int i = 0; i < kGuardStatWords; ++i) s.guard_stats[i] = 0;
 #endif
     for (;;) {
         const unsigned long long need = __builtin_amdgcn_ballot_w64(!have);      // (not __ballot: that one takes its predicate through a vector register and a compare)
@@ -287,6 +292,12 @@ KR_DEV void trace_body(typename RayOf<T>::type* __restrict__ rays, long long n, 
             atomicAdd(&counters[8], occ_iters); atomicAdd(&counters[9], occ_tail_iters); atomicAdd(&counters[10], w_tail_steps);
             atomicAdd(&counters[11], occ_refills); atomicAdd(&counters[12], occ_refill_lanes);
         }
+    }
+#endif
+#if KR_GUARD_STATS
+    for (int i = 0; i < kGuardStatWords; ++i) {
+        const unsigned long long w = wave_sum(s.guard_stats[i]);
+        if (lane == 0 && w) atomicAdd(&counters[kGuardStatWord + i], w);
     }
 #endif
     if (lane == 0) {

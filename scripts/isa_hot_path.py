@@ -9,7 +9,8 @@ Works on the compiler's assembly (labels, "Loop Header" comments), like scripts/
 step's arm of the loop ends (the target of the first s_cbranch_execz after the header: beyond it lies the queue visit; the second one, "this lane holds a
 ray", is walked through).  On the way
   * a wave-uniform forward branch (s_cbranch_vccz / vccnz / scc0 / scc1) is TAKEN: such branches jump over what a wave rarely needs -- the landing
-    clips, the ERGO and NEG_ENERGY flags, the pole reflection;
+    clips, the ERGO and NEG_ENERGY flags, the pole reflection -- unless its target lies BEHIND the step's arm of the loop: that is a rare arm the compiler
+    moved out of line (the code behind the quiet-step and cap guards; it branches back), and the walk falls through;
   * an s_cbranch_execz whose span holds a call (s_swappc_b64) is taken too, if the step's arithmetic goes on behind its target: the libm fallback of
     the sine / cosine and the redo of the three stages.  ("No polar turning point" spans the rest of the step: it is walked through, and its else arm --
     the block behind its target, where a lane that did turn counts its step -- is left out);
@@ -73,6 +74,8 @@ def hot_path(path, key):
                 if op == "s_cbranch_execz" and own < 2:
                     own += 1          # the loop's own two: the step's arm (it ends at the first one's target), the lanes that hold a ray
                     stop = target if stop is None else stop
+                elif op in UNIFORM and stop is not None and target >= stop:
+                    skipped.append(f"{t.split()[1]} (out of line)")       # a rare arm the compiler moved behind the loop (it branches back): not taken
                 elif op in UNIFORM or op == "s_branch":
                     if target > j:
                         skipped.append(f"{label_name(lines[j]) if j < len(lines) else '?'} .. {t.split()[1]} (uniform branch)")
