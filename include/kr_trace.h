@@ -463,7 +463,32 @@ static_assert(sizeof(kr_pol_law) == 16, "kr_pol_law is 16 bytes (raytrace_cpu_am
  * Output: double[ne + 4] = [flux (ne) | on_disc | used | bad_angle | 0], ADDED into: shards, several planes and several calls sum.
  * Refused (KR_EINVAL): a null model, ne < 1 or ne > 4096, de <= 0, log_e with de <= 1 or e_min <= 0, an unknown model, a non-finite parameter;
  * model 0 without table_kt, with table_nr < 1 or f_col <= 0; model 1 with s == NULL, s_ne < 2, s_de <= 1, s_e_min <= 0, nz < 1, nz s_ne > 2^20, or
- * table_emis with table_nr < 1.  The tables are copied to the device once per distinct contents (the table cache of kr_line_bins). */
+ * table_emis with table_nr < 1.  The tables are copied to the device once per distinct contents (the table cache of kr_line_bins).
+ *
+ * STOKES SPECTRA of the continuum (kr_post_spectrum_stokes_dev_f64, kr_reduce_spectrum_stokes_*): the energy-resolved linear polarisation, Q(E) and
+ * U(E) beside I(E) -- what an X-ray polarimeter measures of a thermal disc or a reflection table.  Everything of the rule above stands: filter, energies,
+ * ir, zones, both models, the table interpolation, what makes a ray usable.  Everything of the kr_pol_law rule stands too: frame, emitted vector,
+ * Walker-Penrose constant, observer inversion with inc_deg, c2, s2, bad-pol, the degree law delta(mu); reverse = 1 and motion = 0, as there.  What joins
+ * them, per record after redshift and range_phi:
+ *   on_disc  a record that passes the filter counts in `on_disc`.
+ *   bad_pol  an on-disc record that is bad-pol counts in `bad_pol` and adds to nothing, WHATEVER THE LIMB LAW (as in the Stokes image, line and hot-spot
+ *            passes).  Bad-angle is a subset of bad-pol: there is no separate bad_angle tally.
+ *   used     otherwise limb = limb(mu) with the polarisation frame's mu (frame_value's to the bit), and the model's own rule decides: no ir, a kT that
+ *            is not finite or not positive, a non-finite table_emis[ir] -> not used.  A record that adds to the sums counts in `used`.
+ *   weights  c is the item word w g^-3 as the spectrum pass forms it: with g3 = 1 / ((g g) g), thermal c = (limb g3) f_col^-4 (f_col^-4 =
+ *            1 / (((f f) f) f), once on the host), table c = (emis limb) g3.  Then cd = c delta(mu), cq = cd c2, cu = cd s2.
+ *   sums     for every energy i, E' = g E_i and ONE X = I_rest without its common factor:
+ *              thermal  X = ((E' E') E') / expm1(E' q),  q = 1 / (f_col kT) rounded once per ray
+ *              table    X = S[z][k] + (p - k) (S[z][k + 1] - S[z][k]), exactly 0 (nothing added) outside [s_e_min, s_e_last]
+ *            then  I[i] += c X,  Q[i] += cq X,  U[i] += cu X, each product and each sum rounded separately.  (The thermal I differs from the spectrum
+ *            pass's flux in the last bit: that pass divides (c E'^3) by the expm1, this one multiplies c by the quotient.)
+ *   axes     Q and U refer to the plane's own x and y axes, as in kr_post_image_stokes_dev_f64.
+ * Output: double[3 ne + 4] = [I (ne) | Q (ne) | U (ne) | on_disc | used | bad_pol | 0], ADDED into: shards, several planes and several calls sum.  The
+ * polarisation degree sqrt(Q^2 + U^2) / I and the angle atan2(U, Q) / 2 are the caller's to take.  ne in 1 ... 4096, as above.
+ * The reduce forms take records that carry their redshift (g is READ from the record) and recompute the frame of the on-disc records for mu, c2, s2
+ * and bad-pol: unlike kr_reduce_spectrum_* they take a limb law.
+ * Not covered: the plunging flow (KR_V_PLUNGE is refused: polar_value has no Gram-Schmidt form), Q and U of the reverberation response, the thick-disc
+ * surface, higher-order images, f32 records, a second pass for returning radiation. */
 typedef struct kr_spectrum_model {
     double e_min, de;              /* output energies: the centres of these bins; log_e: de is the ratio between edges */
     double r_isco, r_disc;         /* disc filter; the span of the zones */
@@ -1255,6 +1280,20 @@ int kr_post_spectrum_dev_f64(double spin, double V, int reverse, int projradius,
                              const kr_limb_law* law, void* d_rays, int64_t n, void* d_out, void* stream);
 int kr_reduce_spectrum_dev_f64(const kr_spectrum_model* m, const void* d_rays, int64_t n, void* d_out, void* stream);
 int kr_reduce_spectrum_f64(const kr_spectrum_model* m, const kr_ray_f64* rays, int64_t n, double* out);
+/* The Stokes spectra of the continuum (STOKES SPECTRA under kr_spectrum_model).  KR_EINVAL (message in kr_last_error) before a device is touched, and
+ * nothing is written: V == KR_V_PLUNGE, whatever the model's comment refuses, reverse != 1, motion != 0, a non-finite inc_deg, a limb law other than 0, 1,
+ * 2 or with a non-finite coeff, whatever kr_pol_law refuses, a null pointer, n < 0.  n == 0 is KR_OK and adds nothing.  None of the _dev forms waits for
+ * the device or allocates, beyond the table cache's first copy of a table.
+ * kr_post_spectrum_stokes_dev_f64: redshift(V, reverse, projradius, motion) + range_phi(lo, hi) + the Stokes spectra in one pass; rays[] ends up exactly
+ * as after kr_post_spectrum_dev_f64, i.e. kr_post_line_dev_f64.  ADDS into d_out (3 ne + 4 doubles; zero it first).
+ * kr_reduce_spectrum_stokes_dev_f64: records that already carry their redshift; reads the records and never writes them.
+ * kr_reduce_spectrum_stokes_f64: host records, out = 3 ne + 4 host doubles (overwritten). */
+int kr_post_spectrum_stokes_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, double inc_deg,
+                                    const kr_spectrum_model* m, const kr_limb_law* law, const kr_pol_law* pol, void* d_rays, int64_t n, void* d_out, void* stream);
+int kr_reduce_spectrum_stokes_dev_f64(double spin, double V, int reverse, int projradius, double inc_deg, const kr_spectrum_model* m,
+                                      const kr_limb_law* law, const kr_pol_law* pol, const void* d_rays, int64_t n, void* d_out, void* stream);
+int kr_reduce_spectrum_stokes_f64(double spin, double V, int reverse, int projradius, double inc_deg, const kr_spectrum_model* m,
+                                  const kr_limb_law* law, const kr_pol_law* pol, const kr_ray_f64* rays, int64_t n, double* out);
 
 /* ---- reverberation response of the disc (kr_response_model above has the rule) ---------------------------------------------------------------
  * Every entry point validates its arguments before it touches a device: KR_EINVAL (message in kr_last_error) for a null pointer, n < 0, whatever the

@@ -1591,6 +1591,41 @@ def reduce_spectrum(model, rays):
     return spectrum_from_words(model, out)
 
 
+def _spectrum_stokes_layout(model, words=None):
+    return _layout([(k, (model.ne,)) for k in ("flux", "q", "u")], [("on_disc", _rounded), ("used", _rounded), ("bad_pol", _rounded), (None, None)], words)
+
+
+def spectrum_stokes_words(model):
+    """Length of the buffer of kr_post_spectrum_stokes_dev_f64 / kr_reduce_spectrum_stokes_dev_f64: [I | Q | U (ne each) | on_disc | used | bad_pol | 0]."""
+    return _spectrum_stokes_layout(model)
+
+
+def spectrum_stokes_from_words(model, words):
+    """The buffer of the Stokes spectrum entry points as a dict: flux, q, u (ne each: the Stokes sums I, Q, U on the plane's own x and y axes),
+    pol_degree = sqrt(q^2 + u^2) / flux and pol_angle = atan2(u, q) / 2 in radians from the x axis towards the y axis (both NaN where flux == 0),
+    the tallies on_disc, used, bad_pol, and `energy`, the ne sampling energies."""
+    out = _spectrum_stokes_layout(model, words)
+    out["energy"] = spectrum_energies(model)
+    with np.errstate(all="ignore"):
+        lit = out["flux"] != 0
+        safe = np.where(lit, out["flux"], 1.0)
+        out["pol_degree"] = np.where(lit, np.hypot(out["q"], out["u"]) / safe, np.nan)
+        out["pol_angle"] = np.where(lit, 0.5 * np.arctan2(out["u"], out["q"]), np.nan)
+    return out
+
+
+def reduce_spectrum_stokes(model, rays, spin, inc_deg, pol, limb=None):
+    """kr_reduce_spectrum_stokes_f64: the Stokes spectra I, Q, U of the continuum from host ray records of an image plane that carry their redshift.
+    spin: the true spin (the a of the redshift pass with reverse = 1); inc_deg: the plane's inclination; pol, limb: as for stokes_image.  Keplerian gas
+    (V = -1), projradius 0."""
+    _rays_arg(rays, capi.RAY_F64)
+    law, plaw = capi.limb_law(limb if limb is not None else "isotropic"), capi.pol_law(pol)
+    out = np.zeros(spectrum_stokes_words(model))
+    capi.check(lib(), lib().kr_reduce_spectrum_stokes_f64(spin, -1.0, 1, 0, inc_deg, C.byref(model), C.byref(law), C.byref(plaw), _ptr(rays), len(rays), _ptr(out)),
+               "kr_reduce_spectrum_stokes")
+    return spectrum_stokes_from_words(model, out)
+
+
 def plunge_flow(spin):
     """kr_plunge_flow: (r_ms, E_ms, L_ms) of the disc flow V = capi.V_PLUNGE for the metric's spin (needs no GPU)."""
     r_ms, E_ms, L_ms = C.c_double(), C.c_double(), C.c_double()
@@ -1669,15 +1704,29 @@ def resample_spectrum(energy, counts, spec_bins):
     return float(energy[0]), s_de, np.interp(np.log(nodes), np.log(energy), counts)
 
 
-def disc_spectrum(imageplane_spec, params, model, limb=None, return_records=False, V=-1.0):
+def disc_spectrum(imageplane_spec, params, model, limb=None, return_records=False, V=-1.0, pol=None):
     """The continuum spectrum of the disc seen on an image plane, resident on the device from start to finish, as the kr_disc_spectrum app runs it:
     ImagePlane ctor + redshift_start (kr_imageplane_init_emit_dev_f64) -> trace (kr_trace_dev_f64; `params` as for the image app: the stored, negated
     spin) -> redshift + range_phi + the spectrum (kr_post_spectrum_dev_f64).  model: a capi.SpectrumModel; limb: None (isotropic) or a limb law as for
     line_profile.  Only the ne + 4 words are read back (and, with return_records, the final records: for tests).  Returns spectrum_from_words(...)
     plus "stats" (the trace's kr_stats).  The flux is per image-plane pixel: multiply by dx dy / D^2 for a flux density.  V: -1 or capi.V_PLUNGE, as for
-    line_profile (model.r_isco is the inner edge)."""
+    line_profile (model.r_isco is the inner edge).
+    pol: None, or a polarisation degree law as for stokes_image ((law, coeff), a name of capi.POL_LAWS or a capi.PolLaw): the Stokes spectra.  The last
+    pass is then kr_post_spectrum_stokes_dev_f64 at the plane's own inclination (V = capi.V_PLUNGE is refused) and the result is
+    spectrum_stokes_from_words(...) plus "stats": "q", "u", "pol_degree", "pol_angle" and "bad_pol" join it (and "bad_angle" leaves it: bad-angle is a
+    subset of bad-pol)."""
     law = capi.limb_law(limb if limb is not None else "isotropic")
     sized = 1 <= model.ne <= 4096                      # (the pass refuses the rest: it gets a null buffer)
+    if pol is not None:
+        plaw, spin, inc = capi.pol_law(pol), -1 * imageplane_spec.spin, imageplane_spec.inc_deg
+        words, stats, records = _imageplane_run("disc_spectrum", imageplane_spec, params, spectrum_stokes_words(model) if sized else 0, lambda L, dev, d_rays, n, d_out: capi.check(
+            L, L.kr_post_spectrum_stokes_dev_f64(spin, V, 1, 0, 0, -np.pi, np.pi, inc, C.byref(model), C.byref(law), C.byref(plaw), d_rays, n, d_out, None),
+            "kr_post_spectrum_stokes"), return_records)
+        res = spectrum_stokes_from_words(model, words)
+        res["stats"] = stats
+        if return_records:
+            res["records"] = records
+        return res
     words, stats, records = _imageplane_run("disc_spectrum", imageplane_spec, params, spectrum_words(model) if sized else 0, lambda L, dev, d_rays, n, d_out: capi.check(
         L, L.kr_post_spectrum_dev_f64(-1 * imageplane_spec.spin, V, 1, 0, 0, -np.pi, np.pi, C.byref(model), C.byref(law), d_rays, n, d_out, None), "kr_post_spectrum"),
         return_records)
@@ -1690,7 +1739,11 @@ def disc_spectrum(imageplane_spec, params, model, limb=None, return_records=Fals
 
 def spectrum_text(res):
     """The file kr_disc_spectrum writes for a result of disc_spectrum(): three comment rows with the tallies ("# ON_DISC", "# USED", "# BAD_ANGLE" and
-    their counts), then one row per energy: E flux.  Every field setw(20), the numbers scientific with precision 8 (host/include/text_output.h)."""
+    their counts), then one row per energy: E flux.  Every field setw(20), the numbers scientific with precision 8 (host/include/text_output.h).  A result
+    that carries Stokes sums (disc_spectrum(pol=...)): the third tally is "# BAD_POL" and the rows are E I Q U."""
+    if "q" in res:
+        head = "".join("%20s%20d\n" % (f"# {k.upper()}", res[k]) for k in ("on_disc", "used", "bad_pol"))
+        return head + "".join("".join(_path_field(float(v)) for v in row) + "\n" for row in zip(res["energy"], res["flux"], res["q"], res["u"]))
     head = "".join("%20s%20d\n" % (f"# {k.upper()}", res[k]) for k in ("on_disc", "used", "bad_angle"))
     return head + "".join(_path_field(float(e)) + _path_field(float(f)) + "\n" for e, f in zip(res["energy"], res["flux"]))
 

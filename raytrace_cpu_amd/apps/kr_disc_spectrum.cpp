@@ -1,7 +1,7 @@
 // apps/kr_disc_spectrum.cpp -- the continuum spectrum of the disc seen on an image plane, resident on the MI355X from start to finish: a multicolour
 // blackbody with the Novikov-Thorne temperature profile (what kerrbb computes), or any tabulated rest-frame spectrum (a reflection table, a cut-off
 // power law) smeared by the rays, relconv-style.  The rays are generated, traced, redshifted and summed into every output energy in HBM and only the
-// Nen + 4 doubles of the spectrum come back (include/kr_trace.h, kr_spectrum_model, has the per-ray rule).
+// Nen + 4 doubles of the spectrum come back (3 Nen + 4 with Stokes sums; include/kr_trace.h, kr_spectrum_model, has the per-ray rule).
 //
 // Reads the plane and disc keys of imageplane_app.h and the emissivity and limb keys of kr_line_profile (--parfile, outfile, dist, incl, plane_phi0, spin, r_disc,
 // x0, xmax, Nx, y0, ymax, Ny, q1, rb1, q2, rb2, q3, emis_file, limb, limb_coeff, precision, integrator, rk45_tol; --arithmetic, --device, --timing), and
@@ -13,10 +13,15 @@
 //             f_col = 1.7     colour-correction factor: I = f_col^-4 B(E, f_col kT_eff)
 //             kt_bins = 400   radial bins of the kT table, log-spaced over [r_isco, r_disc); kT in keV at each bin's centre, so E is in keV
 //   table:    spec_file, Nzones, spec_bins = 512: the rest-frame spectrum per radial zone and the log grid it is resampled onto (rest_spectrum.h)
+//   pol_law, pol_coeff        optional, the keys of kr_imageplane_polarisation (pol_law = 1, pol_coeff = 0.1171 when only one of them is given): the
+//                             Stokes spectra Q(E), U(E) of the continuum (kr_post_spectrum_stokes_dev_f64) on the plane's own x and y axes; not with
+//                             plunge = 1 (the polarisation frame has no plunging form)
 // Every key may also be given as --key=value, which takes precedence over the file.  Nx and Ny are read as int, as kr_imageplane_disc_image reads
 // them (before imageplane_app.h: as double, then cast; the same for a key written as a plain integer).
 // Output: TextOutput (width 20, precision 8): three comment rows "# ON_DISC", "# USED", "# BAD_ANGLE" with their counts, then one row per energy:
 // E flux.  The flux is per image-plane pixel: multiply by dx dy / dist^2 for a flux density.
+// With pol_law or pol_coeff: the third comment row is "# BAD_POL" (disc records without a polarisation angle, which add to nothing) and every row is
+// E I Q U.  Without them the file is byte for byte what it was before the keys existed.
 #include <cmath>
 #include <fstream>
 #include <iostream>
@@ -67,6 +72,9 @@ static void program(const krapp::Options& opt)
     memset(&limb, 0, sizeof limb);
     limb.law = (int32_t) opt.num("limb", 0);
     limb.coeff = opt.num("limb_coeff", 2.06);
+    const bool stokes = opt.has("pol_law") || opt.has("pol_coeff");
+    const kr_pol_law pol = krapp::pol_law_of(opt);
+    if (stokes && s.flow.plunge) throw invalid_argument("pol_law / pol_coeff: the Stokes spectra do not take the plunging disc flow (plunge = 1)");
 
     const double e_min = opt.num("e_min", 0.1), e_max = opt.num("e_max", 10);
     const int ne = (int) opt.num("Nen", 100);
@@ -121,22 +129,31 @@ static void program(const krapp::Options& opt)
 
     // ---- device pipeline: init_emit -> trace -> redshift + range_phi + spectrum ---------------------------------------------------------
     krapp::DiscPlaneRun run(s, plane);
-    const int64_t words = (int64_t) ne + 4;
+    const int64_t words = (int64_t) (stokes ? 3 : 1) * ne + 4;
     run.trace(plane, p, words);
-    krapp::check(kr_post_spectrum_dev_f64(-s.spin, s.flow.V(), 1, 0, 0, -1 * M_PI, M_PI, &sm, &limb, run.rays->get(), run.n, run.acc->get(), nullptr), "redshift + range_phi + spectrum");
+    if (stokes)
+        krapp::check(kr_post_spectrum_stokes_dev_f64(-s.spin, s.flow.V(), 1, 0, 0, -1 * M_PI, M_PI, s.incl, &sm, &limb, &pol, run.rays->get(), run.n, run.acc->get(), nullptr),
+                     "redshift + range_phi + spectrum with Stokes sums");
+    else
+        krapp::check(kr_post_spectrum_dev_f64(-s.spin, s.flow.V(), 1, 0, 0, -1 * M_PI, M_PI, &sm, &limb, run.rays->get(), run.n, run.acc->get(), nullptr), "redshift + range_phi + spectrum");
     vector<double> h((size_t) words);
     krapp::check(kr_memcpy_d2h(h.data(), run.acc->get(), words * (int64_t) sizeof(double)), "d2h");
     const double ms_post = run.clock.lap_ms();
 
-    cout << static_cast<long>(h[(size_t) ne]) << " rays on the disc, " << static_cast<long>(h[(size_t) ne + 1]) << " used, " << static_cast<long>(h[(size_t) ne + 2])
-         << " without an emission angle (bad-angle)" << endl;
+    const double* tallies = h.data() + (size_t) (stokes ? 3 : 1) * ne;
+    cout << static_cast<long>(tallies[0]) << " rays on the disc, " << static_cast<long>(tallies[1]) << " used, " << static_cast<long>(tallies[2])
+         << (stokes ? " without a polarisation angle (bad-pol)" : " without an emission angle (bad-angle)") << endl;
     {
         TextOutput outfile(s.out_name);
         s.flow.write_rows(outfile);
-        outfile << "# ON_DISC" << static_cast<long>(h[(size_t) ne]) << endl;
-        outfile << "# USED" << static_cast<long>(h[(size_t) ne + 1]) << endl;
-        outfile << "# BAD_ANGLE" << static_cast<long>(h[(size_t) ne + 2]) << endl;
-        for (int i = 0; i < ne; ++i) outfile << (log_e ? e_min * pow(de, i + 0.5) : e_min + (i + 0.5) * de) << h[(size_t) i] << endl;
+        outfile << "# ON_DISC" << static_cast<long>(tallies[0]) << endl;
+        outfile << "# USED" << static_cast<long>(tallies[1]) << endl;
+        outfile << (stokes ? "# BAD_POL" : "# BAD_ANGLE") << static_cast<long>(tallies[2]) << endl;
+        for (int i = 0; i < ne; ++i) {
+            outfile << (log_e ? e_min * pow(de, i + 0.5) : e_min + (i + 0.5) * de) << h[(size_t) i];
+            if (stokes) outfile << h[(size_t) ne + i] << h[(size_t) 2 * ne + i];
+            outfile << endl;
+        }
     }
     const double ms_out = run.clock.lap_ms();
 

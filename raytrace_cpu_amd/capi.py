@@ -456,6 +456,9 @@ PROTOTYPES = {
     "kr_post_spectrum_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, P(SpectrumModel), P(LimbLaw), _vp, _i64, _vp, _vp]),
     "kr_reduce_spectrum_dev_f64": (_int, [P(SpectrumModel), _vp, _i64, _vp, _vp]),
     "kr_reduce_spectrum_f64": (_int, [P(SpectrumModel), _vp, _i64, _vp]),
+    "kr_post_spectrum_stokes_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, _dbl, P(SpectrumModel), P(LimbLaw), P(PolLaw), _vp, _i64, _vp, _vp]),
+    "kr_reduce_spectrum_stokes_dev_f64": (_int, [_dbl, _dbl, _int, _int, _dbl, P(SpectrumModel), P(LimbLaw), P(PolLaw), _vp, _i64, _vp, _vp]),
+    "kr_reduce_spectrum_stokes_f64": (_int, [_dbl, _dbl, _int, _int, _dbl, P(SpectrumModel), P(LimbLaw), P(PolLaw), _vp, _i64, _vp]),
     "kr_post_response_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, P(ResponseModel), P(LimbLaw), _vp, _i64, _vp, _vp]),
     "kr_reduce_response_dev_f64": (_int, [P(ResponseModel), _vp, _i64, _vp, _vp]),
     "kr_reduce_response_f64": (_int, [P(ResponseModel), _vp, _i64, _vp]),

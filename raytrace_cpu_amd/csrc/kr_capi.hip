@@ -1314,6 +1314,48 @@ int kr_reduce_hotspot_f64(const kr_hotspot* h, const kr_ray_f64* rays, int64_t n
     return rc2;
 }
 
+// the Stokes spectra of the continuum: the refusals of the model, of the polarisation entry points and of the two laws, in that order
+static int spectrum_stokes_validate(double V, int reverse, int motion, double inc_deg, const kr_spectrum_model* m, const kr_limb_law* law, const kr_pol_law* pol, const char* who)
+{
+    int rc = refuse_plunge(V, who);
+    if (rc == KR_OK) rc = spectrum_validate(m, who);
+    if (rc == KR_OK) rc = polarisation_validate(reverse, motion, inc_deg, who);
+    if (rc == KR_OK) rc = limb_validate(law, who);
+    if (rc == KR_OK) rc = pol_validate(pol, who);
+    return rc;
+}
+
+int kr_post_spectrum_stokes_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, double inc_deg, const kr_spectrum_model* m,
+                                    const kr_limb_law* law, const kr_pol_law* pol, void* d, int64_t n, void* d_out, void* st)
+{
+    const int rc = spectrum_stokes_validate(V, reverse, motion, inc_deg, m, law, pol, "kr_post_spectrum_stokes");
+    if (rc != KR_OK) return rc;
+    return on_device(n >= 0 && d_out && (n == 0 || d), "kr_post_spectrum_stokes: null argument or negative n",
+                     [&] { return post_spectrum_stokes_dev(spin, V, reverse, projradius, lo, hi, inc_deg, m, law, pol, d, n, d_out, (hipStream_t) st); });
+}
+
+int kr_reduce_spectrum_stokes_dev_f64(double spin, double V, int reverse, int projradius, double inc_deg, const kr_spectrum_model* m, const kr_limb_law* law,
+                                      const kr_pol_law* pol, const void* d, int64_t n, void* d_out, void* st)
+{
+    const int rc = spectrum_stokes_validate(V, reverse, 0, inc_deg, m, law, pol, "kr_reduce_spectrum_stokes");
+    if (rc != KR_OK) return rc;
+    return on_device(n >= 0 && d_out && (n == 0 || d), "kr_reduce_spectrum_stokes: null argument or negative n",
+                     [&] { return reduce_spectrum_stokes_dev(spin, V, reverse, projradius, inc_deg, m, law, pol, d, n, d_out, (hipStream_t) st); });
+}
+
+int kr_reduce_spectrum_stokes_f64(double spin, double V, int reverse, int projradius, double inc_deg, const kr_spectrum_model* m, const kr_limb_law* law,
+                                  const kr_pol_law* pol, const kr_ray_f64* rays, int64_t n, double* out)
+{
+    const int rc = spectrum_stokes_validate(V, reverse, 0, inc_deg, m, law, pol, "kr_reduce_spectrum_stokes");
+    if (rc != KR_OK) return rc;
+    if (!out || n < 0 || (n > 0 && !rays)) return invalid("kr_reduce_spectrum_stokes: null argument or negative n");
+    std::vector<double> w(3 * (size_t) m->ne + 4, 0.0);        // out is written only by a call that succeeds
+    const int rc2 = reduce_to_host(rays, n, w.size(), w.data(),
+                                   [&](void* d, void* d_out) { return reduce_spectrum_stokes_dev(spin, V, reverse, projradius, inc_deg, m, law, pol, d, n, d_out, nullptr); });
+    if (rc2 == KR_OK) std::memcpy(out, w.data(), w.size() * sizeof(double));
+    return rc2;
+}
+
 // the Stokes light curves of the spot: the refusals of the spot, of the polarisation entry points and of the two laws, in that order
 static int hotspot_stokes_validate(double V, int reverse, int motion, double inc_deg, const kr_hotspot* h, const kr_limb_law* law, const kr_pol_law* pol, const char* who)
 {

@@ -193,6 +193,11 @@ int spectrum_law_validate(const kr_limb_law* law, int motion, const char* who);
 int post_spectrum_dev(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_spectrum_model* m, const kr_limb_law* law, void* d,
                       int64_t n, void* d_out, hipStream_t st);
 int reduce_spectrum_dev(const kr_spectrum_model* m, const void* d, int64_t n, void* d_out, hipStream_t st);
+// the Stokes spectra (STOKES SPECTRA under kr_spectrum_model): motion 0 only; the reduce form recomputes the frame of the on-disc records
+int post_spectrum_stokes_dev(double spin, double V, int reverse, int projradius, double lo, double hi, double inc_deg, const kr_spectrum_model* m, const kr_limb_law* law,
+                             const kr_pol_law* pol, void* d, int64_t n, void* d_out, hipStream_t st);
+int reduce_spectrum_stokes_dev(double spin, double V, int reverse, int projradius, double inc_deg, const kr_spectrum_model* m, const kr_limb_law* law, const kr_pol_law* pol,
+                               const void* d, int64_t n, void* d_out, hipStream_t st);
 // kr_response.hip: the energy-time response of the reflection spectrum (kr_response_model); the validator refuses what spectrum_validate refuses of
 // spec, then what the struct's comment refuses (the limb law: spectrum_law_validate)
 int response_validate(const kr_response_model* r, const char* who);

@@ -9,6 +9,12 @@
 // No atomic sits in either inner loop: at the end of the launch a workgroup adds each non-zero sum it owns into the global spectrum, once.
 //   spectrum_kernel<MODEL, FUSED, SLOTS>   MODEL 0: thermal; 1: table, S in LDS; 2: table, S in global memory.  FUSED: redshift + range_phi + spectrum
 //                                          (rays[] ends as after post_line_kernel); otherwise the records carry their redshift and are only read.
+// STOKES: the Stokes spectra Q(E), U(E) beside I(E) (include/kr_trace.h, STOKES SPECTRA under kr_spectrum_model).  Phase A is written out, as in
+// kr_hotspot.hip (disc_ray is shared with kernels that must keep their code): polar_value (kr_post_device.hpp) in place of frame_value -- its E and mu
+// are frame_value's to the bit, so the stored redshift keeps its value --, the filter, and for EVERY disc record the item gains cq = c delta c2 and cu = c delta s2; a bad-pol
+// disc record is tallied and leaves no item, whatever the limb law.  Phase B forms ONE X = I_rest(g E) per (item, energy) and feeds three register sums
+// with it; the flush adds up to three words per owned energy.  Everything of it sits behind if constexpr: the instances without STOKES compile to what
+// they were (profiles/spectrum_stokes_resources.txt).
 
 #include <hip/hip_runtime.h>
 
@@ -31,28 +37,66 @@ namespace {
 // the budget S is read from global memory (a table that size is L2-resident, and every lane of a wave reads near the same node).
 constexpr int kSpecLdsWords = 4096;
 
-// PLUNGE: the disc flow of KR_V_PLUNGE (DiscFlow, kr_post_device.hpp), fused form only; the host picks the instance from V
-template <int MODEL, bool FUSED, int SLOTS, bool PLUNGE>
-__global__ void __launch_bounds__(kBlock)
-spectrum_kernel(typename std::conditional<FUSED, kr_ray_f64, const kr_ray_f64>::type* __restrict__ rays, long long n, double spin, double V, int reverse,
-                int projradius, int motion, double lo, double hi, SpecDev D, kr_limb_law law, double* __restrict__ out, DiscFlow<PLUNGE> fl)
+// what the Stokes instances take besides: the sine of the plane's inclination, taken once on the host, and the degree law.  The other instances take
+// an empty struct in its place, so their code stays what it was.
+struct StokesDev {
+    double sin_incl;
+    kr_pol_law pol;
+};
+struct NoStokes {};
+
+// The Stokes instances' register bound, in waves per SIMD (the second launch bound); 1 leaves the compiler free, as the instances without STOKES are.
+// A Stokes slot holds E, (U,) and three sums, 8 ... 10 VGPRs against 4 ... 6, and polar_value is live across phase A beside them.  Sized freely every
+// form still reaches two waves per SIMD up to four slots EXCEPT the fused table forms at four slots (256 VGPRs + 8 AGPRs: one wave); held to two waves
+// those spill 8 VGPRs and run 6.4 against 10.7 ms (1024 energies, profiles/spectrum_stokes_ab.txt).  Everywhere else the bound changes no residency and
+// was a tie or a loss -- the one-slot table forms ran 11 ... 13 % slower under it at the same register count -- so only those forms carry it.
+#ifdef KR_SPECTRUM_STOKES_TWO_WAVE_SLOTS         // A/B builds only (scripts/spectrum_stokes_ab.py): hold EVERY Stokes kernel to two waves per SIMD up to this many slots (0: none)
+constexpr int kStokesTwoWaveSlots = KR_SPECTRUM_STOKES_TWO_WAVE_SLOTS;
+#else
+constexpr int kStokesTwoWaveSlots = -1;          // by form: the fused table forms at four slots
+#endif
+// Phase A of the fused Stokes form: polar_value for EVERY record in place of frame_value (as the Stokes image and line passes do), or frame_value for
+// every record and polar_value for the on-disc ones.  With a fifth of the records on the disc nearly every wave near it takes both branches of the second
+// order; measured, the first is 0.6 ... 2 % faster in four cases of four, about the scatter between builds (profiles/spectrum_stokes_ab.txt).
+#ifdef KR_SPECTRUM_STOKES_FRAME_FIRST            // A/B builds only
+constexpr bool kStokesPolarFirst = false;
+#else
+constexpr bool kStokesPolarFirst = true;
+#endif
+constexpr int stokes_wave_bound(bool stokes, int model, bool fused, int slots)
 {
+    if (!stokes) return 1;
+    if (kStokesTwoWaveSlots >= 0) return slots <= kStokesTwoWaveSlots ? 2 : 1;
+    return fused && model != 0 && slots == 4 ? 2 : 1;
+}
+
+// PLUNGE: the disc flow of KR_V_PLUNGE (DiscFlow, kr_post_device.hpp), fused form only; the host picks the instance from V (never with STOKES)
+template <int MODEL, bool FUSED, int SLOTS, bool PLUNGE, bool STOKES>
+__global__ void __launch_bounds__(kBlock, stokes_wave_bound(STOKES, MODEL, FUSED, SLOTS))
+spectrum_kernel(typename std::conditional<FUSED, kr_ray_f64, const kr_ray_f64>::type* __restrict__ rays, long long n, double spin, double V, int reverse,
+                int projradius, int motion, double lo, double hi, SpecDev D, kr_limb_law law, double* __restrict__ out, DiscFlow<PLUNGE> fl,
+                typename std::conditional<STOKES, StokesDev, NoStokes>::type P)
+{
+    static_assert(!(STOKES && PLUNGE), "polar_value has no plunging form");
     constexpr bool THERMAL = MODEL == 0;
     extern __shared__ double lds_s[];                    // MODEL 1: the table
     __shared__ double it_a[kBlock], it_b[kBlock], it_c[kBlock];
     __shared__ int it_z[kBlock];
     __shared__ int wave_count[kBlock / 64];
+    __shared__ double it_cq[STOKES ? kBlock : 1], it_cu[STOKES ? kBlock : 1];       // (one unused word each without STOKES: the compiler drops them)
     const kr_spectrum_model& m = D.m;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, ne = m.ne;
 
     // phase B's registers: the energies this lane owns (slot s: energy s kBlock + tid), their per-energy term and their sums
     double E[SLOTS], U[SLOTS], sum[SLOTS];
+    double sq[STOKES ? SLOTS : 1], su[STOKES ? SLOTS : 1];
 #pragma unroll
     for (int s = 0; s < SLOTS; s++) {
         const int e = s * kBlock + tid;
         E[s] = e < ne ? (m.log_e ? m.e_min * kr_pow(m.de, e + 0.5) : m.e_min + (e + 0.5) * m.de) : 0;      // (0: an energy beyond ne adds nothing, and is never flushed)
         U[s] = (!THERMAL && e < ne) ? (kr_log(E[s]) - D.log_semin) / D.log_sde : 0;
         sum[s] = 0;
+        if constexpr (STOKES) sq[s] = su[s] = 0;
     }
     // slots in which this wave owns an energy at all (wave-uniform)
     const int first = wave * 64;
@@ -64,14 +108,55 @@ spectrum_kernel(typename std::conditional<FUSED, kr_ray_f64, const kr_ray_f64>::
         S = lds_s;                                       // (the first barrier of the tile loop orders these stores before phase B)
     }
 
-    unsigned long long on_disc = 0, used = 0, bad_angle = 0;
+    unsigned long long on_disc = 0, used = 0, bad_angle = 0;      // (STOKES: bad_angle holds the bad-pol tally)
     for (long long base = blockIdx.x * (long long) kBlock; base < n; base += (long long) gridDim.x * kBlock) {
         // ---- phase A: one record per lane
         const long long i = base + tid;
         bool live = false;
         double a = 0, b = 0, c = 0;
         int zone = 0;
-        if (i < n) {
+        [[maybe_unused]] double cq = 0, cu = 0;
+        if constexpr (STOKES) {
+            // the Stokes rule: the front end of disc_ray written out (motion is 0: the validator refuses the rest), polar_value for the disc records
+            if (i < n) {
+                auto* ray = &rays[i];
+                const int steps = ray->steps;
+                kr_ray_f64 v;
+                Polar pq;
+                bool have_pq = false;
+                double r, theta, g;
+                if constexpr (FUSED) {
+                    v = polar_record_of(ray);
+                    if constexpr (kStokesPolarFirst) {
+                        pq = polar_value(v, spin, V, reverse, projradius, P.sin_incl);
+                        have_pq = true;
+                        g = pq.redshift;
+                    } else {
+                        const Frame f = frame_value(v, spin, V, reverse, projradius);
+                        g = frame_redshift(f, v.emit, reverse);
+                    }
+                    r = v.r; theta = v.theta;
+                    ray->redshift = g;
+                    wrap_phi(ray, steps, lo, hi);
+                } else {
+                    r = ray->r; theta = ray->theta; g = ray->redshift;
+                }
+                if (disc_filter(m.r_isco, m.r_disc, steps, r, theta, g)) {
+                    on_disc++;
+                    if constexpr (!FUSED) v = polar_record_of(ray);
+                    if (!have_pq) pq = polar_value(v, spin, V, reverse, projradius, P.sin_incl);
+                    if (pq.bad) {
+                        bad_angle++;
+                    } else {
+                        live = spectrum_item<THERMAL>(D, r, g, limb_weight(law.law, law.coeff, pq.mu), &a, &b, &c, &zone);
+                        const double cd = c * pol_degree(P.pol.law, P.pol.coeff, pq.mu);
+                        cq = cd * pq.c2;
+                        cu = cd * pq.s2;
+                    }
+                }
+                if (live) used++;
+            }
+        } else if (i < n) {
             DiscRay d;
             if (disc_ray<FUSED, PLUNGE>(&rays[i], m.r_isco, m.r_disc, spin, V, reverse, projradius, motion, lo, hi, law, &d, on_disc, bad_angle, fl))
                 live = spectrum_item<THERMAL>(D, d.r, d.g, d.limb, &a, &b, &c, &zone);
@@ -80,22 +165,41 @@ spectrum_kernel(typename std::conditional<FUSED, kr_ray_f64, const kr_ray_f64>::
         int at, items;
         tile_compact(live, wave_count, &at, &items);
         if (live) { it_a[at] = a; it_b[at] = b; it_c[at] = c; it_z[at] = zone; }
+        if constexpr (STOKES) {
+            if (live) { it_cq[at] = cq; it_cu[at] = cu; }
+        }
         __syncthreads();
         // ---- phase B: one energy per lane and slot, over the tile's live items
         for (int j = 0; j < items; j++) {
             const double g = it_a[j], q = it_b[j], w = it_c[j];
             const double* Sz = THERMAL ? nullptr : S + (size_t) it_z[j] * m.s_ne;
+            [[maybe_unused]] double wq = 0, wu = 0;
+            if constexpr (STOKES) { wq = it_cq[j]; wu = it_cu[j]; }
 #pragma unroll
             for (int s = 0; s < SLOTS; s++) {
                 if (s >= my_slots) break;
                 const double Ep = g * E[s];
                 if (THERMAL) {
-                    sum[s] += w * (Ep * Ep * Ep) / expm1(Ep * q);
+                    if constexpr (STOKES) {              // one X per (item, energy): X = E'^3 / expm1(E' q), then three products and three sums
+                        const double X = (Ep * Ep * Ep) / expm1(Ep * q);
+                        sum[s] += w * X;
+                        sq[s] += wq * X;
+                        su[s] += wu * X;
+                    } else {
+                        sum[s] += w * (Ep * Ep * Ep) / expm1(Ep * q);
+                    }
                 } else if (Ep >= m.s_e_min && Ep <= D.s_e_last) {
                     const double p = fmin(fmax(q + U[s], 0.0), (double) (m.s_ne - 1));
                     const int k = min((int) p, m.s_ne - 2);
                     const double v0 = Sz[k], v1 = Sz[k + 1];
-                    sum[s] += w * (v0 + (p - k) * (v1 - v0));
+                    if constexpr (STOKES) {
+                        const double X = v0 + (p - k) * (v1 - v0);
+                        sum[s] += w * X;
+                        sq[s] += wq * X;
+                        su[s] += wu * X;
+                    } else {
+                        sum[s] += w * (v0 + (p - k) * (v1 - v0));
+                    }
                 }
             }
         }
@@ -107,12 +211,17 @@ spectrum_kernel(typename std::conditional<FUSED, kr_ray_f64, const kr_ray_f64>::
     for (int s = 0; s < SLOTS; s++) {
         const int e = s * kBlock + tid;
         if (e < ne && sum[s] != 0) atomicAdd(&out[e], sum[s]);
+        if constexpr (STOKES) {
+            if (e < ne && sq[s] != 0) atomicAdd(&out[ne + e], sq[s]);
+            if (e < ne && su[s] != 0) atomicAdd(&out[2 * ne + e], su[s]);
+        }
     }
+    double* const tallies = out + (STOKES ? 3 : 1) * ne;
     on_disc = wave_sum(on_disc); used = wave_sum(used); bad_angle = wave_sum(bad_angle);
     if (lane == 0) {
-        if (on_disc) atomicAdd(&out[ne], (double) on_disc);
-        if (used) atomicAdd(&out[ne + 1], (double) used);
-        if (bad_angle) atomicAdd(&out[ne + 2], (double) bad_angle);
+        if (on_disc) atomicAdd(&tallies[0], (double) on_disc);
+        if (used) atomicAdd(&tallies[1], (double) used);
+        if (bad_angle) atomicAdd(&tallies[2], (double) bad_angle);
     }
 }
 
@@ -154,9 +263,9 @@ bool spectrum_table_in_lds(const kr_spectrum_model* m)
 
 namespace {
 
-template <bool FUSED, typename Rays>
+template <bool FUSED, bool STOKES, typename Rays, typename Extra>
 int spectrum_launch(const kr_spectrum_model* m, const kr_limb_law& law, Rays* d, int64_t n, double spin, double V, int reverse, int projradius, int motion, double lo,
-                    double hi, void* d_out, hipStream_t st)
+                    double hi, void* d_out, hipStream_t st, Extra extra)
 {
     if (n <= 0) return KR_OK;
     TablePins pins;
@@ -169,15 +278,15 @@ int spectrum_launch(const kr_spectrum_model* m, const kr_limb_law& law, Rays* d,
         constexpr bool P = decltype(flow)::plunge;
         for_slots(slots, [&](auto K) {
             auto launch = [&](auto kernel, size_t lds) {
-                hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, st, d, (long long) n, spin, V, reverse, projradius, motion, lo, hi, D, law, (double*) d_out, flow.arg);
+                hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, st, d, (long long) n, spin, V, reverse, projradius, motion, lo, hi, D, law, (double*) d_out, flow.arg, extra);
             };
-            if (m->model == 0) launch(spectrum_kernel<0, FUSED, K.value, P>, 0);
-            else if (s_words <= kSpecLdsWords) launch(spectrum_kernel<1, FUSED, K.value, P>, (size_t) s_words * sizeof(double));
-            else launch(spectrum_kernel<2, FUSED, K.value, P>, 0);
+            if (m->model == 0) launch(spectrum_kernel<0, FUSED, K.value, P, STOKES>, 0);
+            else if (s_words <= kSpecLdsWords) launch(spectrum_kernel<1, FUSED, K.value, P, STOKES>, (size_t) s_words * sizeof(double));
+            else launch(spectrum_kernel<2, FUSED, K.value, P, STOKES>, 0);
         });
     };
-    if constexpr (FUSED) for_flow(spin, V, reverse, with_flow);
-    else with_flow(FlowChoice<false>{});
+    if constexpr (FUSED && !STOKES) for_flow(spin, V, reverse, with_flow);
+    else with_flow(FlowChoice<false>{});               // (the Stokes forms: KR_V_PLUNGE is refused before this)
     KR_LAUNCH_CHECK();
     return KR_OK;
 }
@@ -224,12 +333,33 @@ int spectrum_law_validate(const kr_limb_law* law, int motion, const char* who)
 int post_spectrum_dev(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_spectrum_model* m, const kr_limb_law* law, void* d,
                       int64_t n, void* d_out, hipStream_t st)
 {
-    return spectrum_launch<true>(m, *law, (kr_ray_f64*) d, n, spin, V, reverse, projradius, motion, lo, hi, d_out, st);
+    return spectrum_launch<true, false>(m, *law, (kr_ray_f64*) d, n, spin, V, reverse, projradius, motion, lo, hi, d_out, st, NoStokes{});
 }
 
 int reduce_spectrum_dev(const kr_spectrum_model* m, const void* d, int64_t n, void* d_out, hipStream_t st)
 {
-    return spectrum_launch<false>(m, isotropic_limb(), (const kr_ray_f64*) d, n, 0.0, 0.0, 0, 0, 0, 0.0, 0.0, d_out, st);
+    return spectrum_launch<false, false>(m, isotropic_limb(), (const kr_ray_f64*) d, n, 0.0, 0.0, 0, 0, 0, 0.0, 0.0, d_out, st, NoStokes{});
+}
+
+// the Stokes forms (kr_post_spectrum_stokes_dev_f64, kr_reduce_spectrum_stokes_dev_f64): motion is 0, the validators refuse the rest
+static StokesDev stokes_dev(double inc_deg, const kr_pol_law* pol)
+{
+    StokesDev S;
+    S.sin_incl = sin_inclination(inc_deg);
+    S.pol = *pol;
+    return S;
+}
+
+int post_spectrum_stokes_dev(double spin, double V, int reverse, int projradius, double lo, double hi, double inc_deg, const kr_spectrum_model* m, const kr_limb_law* law,
+                             const kr_pol_law* pol, void* d, int64_t n, void* d_out, hipStream_t st)
+{
+    return spectrum_launch<true, true>(m, *law, (kr_ray_f64*) d, n, spin, V, reverse, projradius, 0, lo, hi, d_out, st, stokes_dev(inc_deg, pol));
+}
+
+int reduce_spectrum_stokes_dev(double spin, double V, int reverse, int projradius, double inc_deg, const kr_spectrum_model* m, const kr_limb_law* law, const kr_pol_law* pol,
+                               const void* d, int64_t n, void* d_out, hipStream_t st)
+{
+    return spectrum_launch<false, true>(m, *law, (const kr_ray_f64*) d, n, spin, V, reverse, projradius, 0, 0.0, 0.0, d_out, st, stokes_dev(inc_deg, pol));
 }
 
 }  // namespace kr
