@@ -789,6 +789,57 @@ typedef struct kr_angdist_spec {
 static_assert(sizeof(kr_angdist_spec) == 72, "kr_angdist_spec is 72 bytes (raytrace_cpu_amd/capi.py AngdistSpec)");
 #endif
 
+/* The source-to-observer link: the DIRECT continuum of a source, by observer inclination -- where on the sky at infinity its escaping rays go, when they
+ * reach a reference sphere and with what energy.  It gives the three numbers the lag layer takes from its caller (the arrival instant t0 of the direct
+ * continuum, its flux, and the reflection fraction R_f = return / escape) and covers the reference's lamppost/pointsource_sky programs.  The records
+ * are those of any source (kr_pointsource, kr_pointsource_vel_spec, kr_healpix_source) traced with KR_STOP_THETA to the disc plane and out to r_max.
+ * Per record with steps > 0 (in the kr_post_ form after range_phi and redshift(V, reverse, projradius, motion), whose g this rule does not read):
+ *   class      the rule of kr_return_bins exactly as kr_angdist_spec applies it, phi as stored:
+ *                return  theta >= pi/2, r_isco <= r < r_disc, and |r - source_r| > 0.1 source_r or |phi - source_phi| > 0.1
+ *                escape  not on the disc and r > r_esc;   lost  not on the disc, not escaped, r < r_isco;   anything else: other
+ *              (cls.source_r = 0 switches the self-zone off; cls.plane_iso, cls.limb and cls.weight_norm are not read: the four classes are
+ *              unweighted counts here.)  ray_count += 1 and the class's tally += 1.  Only class `escape` goes further.
+ *   momentum   (pt, pr, ptheta, pphi) = momentum_from_consts(k, h, Q, rdot_sign, thetadot_sign, r, theta, spin) at the record's own (r, theta), the
+ *              expressions redshift() evaluates, with `spin` of this struct (the trace's kr_params.spin).  pr <= 0 (a NaN too), or any of the four
+ *              not finite: inbound += 1 and nothing else.
+ *   direction  Far out d theta / d r and d phi / d r fall as r^-2, so the rest of the way to infinity adds r (d theta / d r):
+ *                theta_obs = theta + r * ptheta / pr;   phi_obs = phi + r * pphi / pr;   mu = cos(theta_obs)     (cos: csrc/kr_sincos.hpp)
+ *              The position angle alone is off by about b / r for impact parameter b, 0.01 rad at r = 1000; this takes that first-order term out.
+ *              phi_obs is part of the rule (tests/observer_rules.py returns it) and is binned nowhere.
+ *   energy     For the static observer at infinity, e_t = (1, 0, 0, 0), the received energy is g_ab e_t^a p^b -> g_tt p^t -> + p^t -> + k as r -> inf:
+ *              kerr_metric's g_tt = e2nu - omega^2 e2psi -> +1 (signature + - - -) and g_tphi -> 0, and p^t -> k.  So E_inf = + k, the conserved
+ *              rays[].k; no metric is evaluated.  shift = E_inf / emit = k / rays[].emit, the usual g = E_obs / E_emit.  shift not > 0 (a NaN too):
+ *              bad_g += 1 and nothing else.
+ *   time       dist > 0: t_ref = t + (dist - r) + 2 * log(dist / r), the flat and the Shapiro term of an outgoing ray from r to the sphere r = dist (every
+ *              ray stops one step past r_max, each at its own r).  dist == 0: t_ref = t.  With dist the image plane's dist, t_ref and the image-plane
+ *              records' t + tt share an origin; what remains is the sphere-against-plane term b^2 / (2 dist), which is NOT corrected.
+ *   weight     w = shift^gamma (pow), gamma the photon index; gamma = 0: pure solid-angle counts (every ray of the source grids carries equal solid angle).
+ *   bins       q = (mu - mu0) / dmu; the ray is binned iff -1 < q < nmu, in imu = (int) q -- the index rule of kr_emis_bins, decided on the quotient.
+ *              Otherwise (a NaN too) outside_mu += 1 and nothing else.  A binned ray: binned += 1 and
+ *                count[imu] += 1;  sum_w[imu] += w;  sum_ws[imu] += w * shift;  sum_wt[imu] += w * t_ref
+ *              nt > 0: ft = (t_ref - t0) / dt; 0 <= ft < nt: hist[imu nt + (int) floor(ft)] += w; otherwise (a NaN too) outside_time += 1 -- such a ray
+ *              has still entered the four planes above.  nt == 0: no time axis.
+ * Output: double[nmu (4 + nt) + 10], ADDED into (zero it once; shards, beta-halves and several calls sum):
+ *   [count | sum_w | sum_ws | sum_wt] (nmu each)  [hist (nmu x nt, [imu nt + j])]
+ *   {ray_count, return, escape, lost, other, binned, outside_mu, outside_time, inbound, bad_g}                                    (counts as doubles)
+ *   binned + outside_mu + inbound + bad_g == escape;   return + escape + lost + other == ray_count.
+ * Refused (KR_EINVAL, before a device is touched): a null pointer, n < 0; nmu outside 1 ... 4096; nt < 0; nmu (4 + nt) > 2^24; dmu or (with nt > 0) dt
+ * not positive or not finite; a non-finite mu0, t0, gamma or spin; dist < 0 or not finite; V = KR_V_PLUNGE (the kr_post_ form).
+ * Out of scope: the absolute scale that joins the per-pixel response to this flux (it needs the emissivity table's normalisation); f32 records;
+ * polarisation of the direct continuum; a histogram over phi_obs for an off-axis source; source_solid_angle's box test. */
+typedef struct kr_observer_spec {
+    kr_return_bins cls;      /* the classes; source_r = 0: no self-zone */
+    double spin;             /* the a of the momentum: the spin the records were traced with */
+    double mu0, dmu;         /* inclination bins: bin i holds mu0 + i dmu <= cos(theta_obs) < mu0 + (i + 1) dmu (bin 0 from mu0 - dmu) */
+    double t0, dt;           /* time rows: row j holds t0 + j dt <= t_ref < t0 + (j + 1) dt */
+    double dist;             /* radius of the reference sphere (the image plane's dist), or 0: t_ref = t */
+    double gamma;            /* photon index of the weight */
+    int32_t nmu, nt;         /* nt = 0: no time axis */
+} kr_observer_spec;
+#ifdef __cplusplus
+static_assert(sizeof(kr_observer_spec) == 120, "kr_observer_spec is 120 bytes (raytrace_cpu_amd/capi.py ObserverSpec)");
+#endif
+
 /* ---- runtime ---------------------------------------------------------------------------------- */
 int         kr_abi_version(void);
 const char* kr_last_error(void);
@@ -1211,6 +1262,16 @@ int kr_post_angdist_dev_f64(double spin, double V, int reverse, int projradius, 
                             int64_t n, void* d_out, void* stream);
 int kr_reduce_angdist_dev_f64(const kr_angdist_spec* sp, const void* d_rays, int64_t n, void* d_out, void* stream);
 int kr_reduce_angdist_f64(const kr_angdist_spec* sp, const kr_ray_f64* rays, int64_t n, double* out);
+
+/* ---- the source-to-observer link: the direct continuum by observer inclination (kr_observer_spec above has the rule) ---------------------------
+ * kr_post_: range_phi(lo, hi) + redshift(V, reverse, projradius, motion) on every record, phi and g stored back as kr_range_phi_dev_f64 +
+ * kr_redshift_dev_f64 leave them, then the reduction, in one pass.  kr_reduce_: the records read as they are and never written.  Both ADD into d_out
+ * (nmu (4 + nt) + 10 doubles on the device; zero it first).  n == 0 is KR_OK and adds nothing.  kr_reduce_observer_f64: host records, out =
+ * nmu (4 + nt) + 10 host doubles (overwritten). */
+int kr_post_observer_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_observer_spec* sp, void* d_rays,
+                             int64_t n, void* d_out, void* stream);
+int kr_reduce_observer_dev_f64(const kr_observer_spec* sp, const void* d_rays, int64_t n, void* d_out, void* stream);
+int kr_reduce_observer_f64(const kr_observer_spec* sp, const kr_ray_f64* rays, int64_t n, double* out);
 
 /* ---- emission-line profile / transfer function (kr_line_bins above) --------------------------------------------------------------------
  * Every entry point validates the bins first, before it touches a device: KR_EINVAL (message in kr_last_error) when ne < 1 or nt < 1, de <= 0,

@@ -1560,6 +1560,135 @@ def angdist_text(res):
     return "".join("".join(_path_field(float(col[i])) for col in cols) + "\n" for i in range(len(res["angle"])))
 
 
+# ---- the source-to-observer link: the direct continuum by observer inclination (include/kr_trace.h, kr_observer_spec) ----
+OBSERVER_PLANES = ("count", "sum_w", "sum_ws", "sum_wt")
+OBSERVER_TALLIES = ("ray_count", "return", "escape", "lost", "other", "binned", "outside_mu", "outside_time", "inbound", "bad_g")
+
+
+def observer_spec(spin, r_isco, r_disc, r_esc, nmu=20, mu0=0.0, dmu=None, gamma=0.0, dist=0.0, t0=0.0, dt=0.0, nt=0, source_r=0.0, source_phi=0.0):
+    """A kr_observer_spec.  spin: the spin the records were traced with.  nmu bins of cos(theta_obs) from mu0 in steps of dmu (default: (1 - mu0) / nmu,
+    the bins end at the pole).  gamma: the photon index of the weight shift^gamma (0: solid-angle counts).  dist: the radius of the reference sphere
+    of the arrival time, the image plane's dist (0: the records' t as it is).  nt rows of dt from t0 (nt = 0: no time axis).  source_r = 0 (the
+    default) switches the self-zone of kr_return_bins off."""
+    sp = capi.ObserverSpec()
+    c = sp.cls
+    c.r_isco, c.r_disc, c.r_esc, c.source_r, c.source_phi = r_isco, r_disc, r_esc, source_r, source_phi
+    c.plane_iso, c.limb, c.weight_norm, c.pad = 0, 0, 0, 0
+    sp.spin, sp.mu0, sp.dmu = spin, mu0, dmu if dmu is not None else (1.0 - mu0) / nmu
+    sp.t0, sp.dt, sp.dist, sp.gamma, sp.nmu, sp.nt = t0, dt, dist, gamma, int(nmu), int(nt)
+    return sp
+
+
+def _observer_layout(spec, words=None):
+    return _layout([(k, (spec.nmu,)) for k in OBSERVER_PLANES] + [("hist", (spec.nmu, spec.nt))], [(k, _rounded) for k in OBSERVER_TALLIES], words)
+
+
+def observer_words(spec):
+    """Length of the buffer of kr_post_observer_dev_f64 / kr_reduce_observer_dev_f64: four planes of nmu, nmu rows of nt, ten tallies."""
+    return _observer_layout(spec)
+
+
+def observer_from_words(spec, words):
+    """The buffer as a dict: count (int64), sum_w, sum_ws, sum_wt (nmu each), hist (nmu, nt), the ten tallies (ints), `mu` (the centres of the
+    inclination bins), `time` (the centres (j + 0.5) dt of the rows, counted from t0) and the bin description mu0, dmu, t0, dt that the helpers
+    observer_flux / direct_arrival read."""
+    out = _observer_layout(spec, words)
+    out["count"] = np.rint(out["count"]).astype(np.int64)
+    out["mu"] = spec.mu0 + (np.arange(spec.nmu) + 0.5) * spec.dmu
+    out["time"] = (np.arange(spec.nt) + 0.5) * spec.dt
+    out.update(mu0=spec.mu0, dmu=spec.dmu, t0=spec.t0, dt=spec.dt)
+    return out
+
+
+def reduce_observer(spec, rays):
+    """kr_reduce_observer_f64: the link of host ray records read as they are (after range_phi(), for a source with a self-zone)."""
+    _rays_arg(rays, capi.RAY_F64)
+    out = np.zeros(observer_words(spec))
+    capi.check(lib(), lib().kr_reduce_observer_f64(C.byref(spec), _ptr(rays), len(rays), _ptr(out)), "kr_reduce_observer")
+    return observer_from_words(spec, out)
+
+
+def source_to_observer(source_spec, params, spec, V=-1.0, reverse=0, projradius=0, motion=0, lo=-np.pi, hi=np.pi, return_records=False):
+    """From a source's geometry to its direct continuum by observer inclination, resident on the device: the rays with their emitted energy
+    (kr_pointsource_init_emit_dev_f64 for a PointSourceSpec, kr_pointsource_vel_init_emit_dev_f64 for a PointSourceVelSpec,
+    kr_healpix_init_emit_dev_f64 for a HealpixSource) -> kr_trace_dev_f64 with `params` (KR_STOP_THETA to the disc plane, r_max beyond the spec's
+    r_esc) -> range_phi + redshift(V, reverse, projradius, motion) + the link (kr_post_observer_dev_f64).  The records never leave the device
+    (return_records copies the final ones back, for tests).  Returns the dict of observer_from_words plus "stats"."""
+    L = lib()
+    if spec.spin != params.spin:
+        raise KrError("source_to_observer: spec.spin is not the spin of params")
+    if isinstance(source_spec, capi.PointSourceSpec):
+        n = pointsource_count(source_spec)[0]
+        init = lambda d: L.kr_pointsource_init_emit_dev_f64(C.byref(source_spec), 0, 1, source_spec.V, int(reverse), int(projradius), d, n, None)      # noqa: E731
+    elif isinstance(source_spec, capi.PointSourceVelSpec):
+        n = pointsource_vel_count(source_spec)[0]
+        init = lambda d: L.kr_pointsource_vel_init_emit_dev_f64(C.byref(source_spec), d, n, None)      # noqa: E731
+    elif isinstance(source_spec, capi.HealpixSource):
+        n = healpix_count(source_spec)[0]
+        init = lambda d: L.kr_healpix_init_emit_dev_f64(C.byref(source_spec), 0, 1, int(reverse), d, n, None)      # noqa: E731
+    else:
+        raise KrError("source_to_observer: source_spec must be a PointSourceSpec, a PointSourceVelSpec or a HealpixSource")
+    sized = 1 <= spec.nmu <= 4096 and 0 <= spec.nt and spec.nmu * (4 + spec.nt) <= 1 << 24        # (the pass refuses the rest: it gets a null buffer)
+    nw = observer_words(spec) if sized else 0
+    st = Stats()
+    with DeviceScope(L) as dev:
+        d_rays = dev.alloc(n * capi.RAY_F64.itemsize) if n > 0 else C.c_void_p()
+        d_out = dev.zeros(nw * 8) if nw else C.c_void_p()
+        capi.check(L, init(d_rays), "source_to_observer: source + emitted energy")
+        capi.check(L, L.kr_trace_dev_f64(C.byref(params), d_rays, n, None, C.byref(st)), "kr_trace_dev")
+        capi.check(L, L.kr_post_observer_dev_f64(params.spin, V, int(reverse), int(projradius), int(motion), lo, hi, C.byref(spec), d_rays, n, d_out, None),
+                   "kr_post_observer")
+        res = observer_from_words(spec, dev.fetch(d_out, nw))
+        res["stats"] = st.as_dict()
+        if return_records:
+            res["records"] = dev.fetch(d_rays, n, capi.RAY_F64)
+    return res
+
+
+def observer_flux(res):
+    """Per inclination bin, the direct flux relative to an isotropic source in flat space: (sum_w / ray_count) / (dmu / 2) -- the share of the source's
+    rays that reaches the bin over the share of the sphere the bin covers.  1 in flat space at gamma = 0.  (0 / 0 without rays: NaN.)"""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return (np.asarray(res["sum_w"], dtype=np.float64) / np.float64(res["ray_count"])) / (res["dmu"] / 2)
+
+
+def reflection_fraction(res):
+    """R_f of the system: the rays that return to the disc over those that escape (unweighted counts; no escaping ray: inf or NaN)."""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return float(np.float64(res["return"]) / np.float64(res["escape"]))
+
+
+def direct_arrival(res, inc_deg):
+    """The direct continuum as an observer at inclination inc_deg sees it, from the bin that holds cos(inc): {"bin", "t0": sum w t_ref / sum w -- the
+    instant capi.response_model(..., t0=...) and kr_reverb_response's t0 key take --, "shift": sum w shift / sum w, "flux": observer_flux there, "hist":
+    the bin's time row}.  Raises KrError for an inclination outside the bins (the index rule of the pass: -1 < (cos(inc) - mu0) / dmu < nmu) and for
+    a bin without rays."""
+    nmu = len(res["sum_w"])
+    q = (math.cos(math.radians(inc_deg)) - res["mu0"]) / res["dmu"]
+    if not (q > -1 and q < nmu):
+        raise KrError(f"direct_arrival: cos({inc_deg} deg) is outside the {nmu} inclination bins from mu0 = {res['mu0']} in steps of {res['dmu']}")
+    i = int(q)
+    sw = float(res["sum_w"][i])
+    if not sw > 0:
+        raise KrError(f"direct_arrival: no direct ray in inclination bin {i}")
+    return {"bin": i, "t0": float(res["sum_wt"][i]) / sw, "shift": float(res["sum_ws"][i]) / sw, "flux": float(observer_flux(res)[i]),
+            "hist": np.array(res["hist"][i], dtype=np.float64)}
+
+
+def observer_text(res):
+    """The table kr_source_observer writes for a result of source_to_observer(): the row `# R_f` with return / escape, then per inclination bin
+    `mu count flux shift t_ref` -- the bin's centre, its ray count, observer_flux, the mean shift and the mean arrival time (nan in an empty bin) --
+    and the nt words of the bin's time row; every field setw(20), doubles scientific with precision 8 (host/include/text_output.h)."""
+    rows = ["%20s" % "# R_f" + _path_field(reflection_fraction(res)) + "\n"]
+    flux = observer_flux(res)
+    for i in range(len(flux)):
+        sw, any_ray = float(res["sum_w"][i]), res["count"][i] > 0
+        means = [float(res[k][i]) / sw if any_ray else float("nan") for k in ("sum_ws", "sum_wt")]
+        rows.append(_path_field(float(res["mu"][i])) + "%20d" % int(res["count"][i]) + "".join(_path_field(float(x)) for x in [flux[i]] + means + list(res["hist"][i]))
+                    + "\n")
+    return "".join(rows)
+
+
 # ---- continuum spectrum of the disc (include/kr_trace.h, kr_spectrum_model) ----
 def _spectrum_layout(model, words=None):
     return _layout([("flux", (model.ne,))], [("on_disc", _rounded), ("used", _rounded), ("bad_angle", _rounded), (None, None)], words)

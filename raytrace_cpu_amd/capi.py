@@ -298,6 +298,15 @@ class AngdistSpec(C.Structure):
 assert C.sizeof(PointSourceVelSpec) == 136 and C.sizeof(AngdistSpec) == 72
 
 
+class ObserverSpec(C.Structure):
+    """kr_observer_spec: the source-to-observer link -- the classes of kr_return_bins (cls), the spin of the momentum, the inclination bins of
+    cos(theta_obs), the time rows, the reference sphere and the photon index (include/kr_trace.h has the rule)."""
+    _fields_ = [("cls", ReturnBins)] + [(n, C.c_double) for n in ("spin", "mu0", "dmu", "t0", "dt", "dist", "gamma")] + [("nmu", C.c_int32), ("nt", C.c_int32)]
+
+
+assert C.sizeof(ObserverSpec) == 120
+
+
 def line_bins(line_energy=6.4, e_min=1.0, de=0.1, ne=90, log_e=False, t0=0.0, dt=0.0, nt=1, r_isco=1.0, r_disc=1000.0, q1=3.0, rb1=4.0, q2=3.0,
               rb2=10.0, q3=3.0, g_index=3.0):
     b = LineBins()
@@ -441,6 +450,9 @@ PROTOTYPES = {
     "kr_post_angdist_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, P(AngdistSpec), _vp, _i64, _vp, _vp]),
     "kr_reduce_angdist_dev_f64": (_int, [P(AngdistSpec), _vp, _i64, _vp, _vp]),
     "kr_reduce_angdist_f64": (_int, [P(AngdistSpec), _vp, _i64, _vp]),
+    "kr_post_observer_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, P(ObserverSpec), _vp, _i64, _vp, _vp]),
+    "kr_reduce_observer_dev_f64": (_int, [P(ObserverSpec), _vp, _i64, _vp, _vp]),
+    "kr_reduce_observer_f64": (_int, [P(ObserverSpec), _vp, _i64, _vp]),
     "kr_reduce_line_f64": (_int, [P(LineBins), _vp, _i64, _vp]),
     "kr_reduce_line_dev_f64": (_int, [P(LineBins), _vp, _i64, _vp, _vp]),
     "kr_post_line_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, P(LineBins), _vp, _i64, _vp, _vp]),

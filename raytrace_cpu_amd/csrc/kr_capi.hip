@@ -1140,6 +1140,32 @@ int kr_reduce_angdist_f64(const kr_angdist_spec* sp, const kr_ray_f64* rays, int
     return reduce_to_host(rays, n, 14 * (size_t) angdist_nangle(sp) + 8, out, [&](void* d, void* d_out) { return reduce_angdist_dev(sp, d, n, d_out, nullptr); });
 }
 
+// ---- the source-to-observer link (kr_observer.hip) ---------------------------------------------------------------------------------------------
+int kr_reduce_observer_dev_f64(const kr_observer_spec* sp, const void* d, int64_t n, void* d_out, void* st)
+{
+    const int rc = observer_validate(sp, "kr_reduce_observer");
+    if (rc != KR_OK) return rc;
+    return on_device(n >= 0 && d_out && (n == 0 || d), "kr_reduce_observer: null argument or negative n", [&] { return reduce_observer_dev(sp, d, n, d_out, (hipStream_t) st); });
+}
+
+int kr_post_observer_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_observer_spec* sp, void* d, int64_t n,
+                             void* d_out, void* st)
+{
+    int rc = refuse_plunge(V, "kr_post_observer");
+    if (rc == KR_OK) rc = observer_validate(sp, "kr_post_observer");
+    if (rc != KR_OK) return rc;
+    return on_device(n >= 0 && d_out && (n == 0 || d), "kr_post_observer: null argument or negative n",
+                     [&] { return post_observer_dev(spin, V, reverse, projradius, motion, lo, hi, sp, d, n, d_out, (hipStream_t) st); });
+}
+
+int kr_reduce_observer_f64(const kr_observer_spec* sp, const kr_ray_f64* rays, int64_t n, double* out)
+{
+    const int rc = observer_validate(sp, "kr_reduce_observer");
+    if (rc != KR_OK) return rc;
+    if (!out || n < 0 || (n > 0 && !rays)) return invalid("kr_reduce_observer: null argument or negative n");
+    return reduce_to_host(rays, n, (size_t) observer_words(sp), out, [&](void* d, void* d_out) { return reduce_observer_dev(sp, d, n, d_out, nullptr); });
+}
+
 int kr_reduce_line_dev_f64(const kr_line_bins* b, const void* d, int64_t n, void* d_line, void* st)
 {
     const int rc = line_validate(b, "kr_reduce_line");

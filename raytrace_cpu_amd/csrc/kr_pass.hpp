@@ -243,6 +243,13 @@ int angdist_validate(const kr_angdist_spec* sp, const char* who);
 int reduce_angdist_dev(const kr_angdist_spec* sp, const void* d, int64_t n, void* d_out, hipStream_t st);
 int post_angdist_dev(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_angdist_spec* sp, void* d, int64_t n, void* d_out,
                      hipStream_t st);
+// kr_observer.hip: the source-to-observer link; the validator refuses what kr_observer_spec's comment refuses of the spec; observer_words:
+// nmu (4 + nt) + 10 of a spec that passed
+int observer_validate(const kr_observer_spec* sp, const char* who);
+int64_t observer_words(const kr_observer_spec* sp);
+int reduce_observer_dev(const kr_observer_spec* sp, const void* d, int64_t n, void* d_out, hipStream_t st);
+int post_observer_dev(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_observer_spec* sp, void* d, int64_t n, void* d_out,
+                      hipStream_t st);
 // kr_caustic.hip.  The validators take the records the caller has (n; "n smaller than ..." is theirs to say)
 int caustic_validate(const kr_caustic_map* m, int64_t n, const char* who);
 int bundles_init_emit_dev(const kr_imageplane* s, int nx, int ny, double eps_frac, double V, int reverse, int projradius, void* d, int64_t n, hipStream_t st);
