@@ -405,6 +405,35 @@ static_assert(sizeof(kr_limb_law) == 16, "kr_limb_law is 16 bytes (raytrace_cpu_
 static_assert(sizeof(kr_mu_bins) == 8, "kr_mu_bins is 8 bytes (raytrace_cpu_amd/capi.py MuBins)");
 #endif
 
+/* A disc with a SURFACE |z| = H(rho), H(rho) = slope rho + scale (1 - sqrt(r_in / rho)): the stop_params of KR_STOP_THICKDISC, with its validation
+ * (r_in positive and finite; r_out finite, <= 0: open; slope and scale non-negative and finite).  The line, the continuum, the response and the
+ * per-record angles of rays that LANDED on it (kr_*_surface_* below) follow one rule per record; tests/surface_pass_rules.py restates it in numpy.
+ *   observer   the one of kr_post_image_surface_dev_f64: V = -1, projradius = 1, motion = 0 -- the Keplerian gas at the cylindrical radius -- in the
+ *              metric of a = reverse ? -spin : spin.  f = the frame above for that observer (E, P_r, P_th, P_phi), g = reverse ? E / emit : emit / E:
+ *              redshift()'s bits.
+ *   filter     steps > 0, status & KR_STATUS_DEST, g > 0, r_isco <= rho < r_disc with rho = r sin(theta) (a NaN fails); r_isco and r_disc are the
+ *              bins' or the model's.  The radius that a pass hands to its item is rho: the index into an emissivity or source -> disc time table,
+ *              powerlaw3, the Novikov-Thorne and ionisation zones.  t is the record's own.
+ *   angle      with sn, cs = sin, cos(theta) and delta, rhosq of the metric at a, one IEEE operation per line in this association, no contraction:
+ *                z = r cs;  sg = z < 0 ? -1 : 1
+ *                Hp = slope + (scale 0.5 sqrt(r_in / rho)) / rho                                  H'(rho): KR_STOP_THICKDISC's step limit has the expression
+ *                f_r = sg cs - Hp sn;   f_th = -(sg (r sn)) - Hp (r cs)                           the gradient of sg z - H(rho) in r and theta
+ *                n_r = sqrt(delta / rhosq) f_r;   n_th = f_th / sqrt(rhosq)                       on the frame's legs e3 and e2
+ *                nn = sqrt(n_r n_r + n_th n_th)
+ *                P_n = (n_r P_r + n_th P_th) / nn;          mu  = |P_n| / E                        the cosine to the surface normal
+ *                P_s = sg (n_r P_th - n_th P_r) / nn;       chi = atan2(P_phi, P_s)                the azimuth about it, 0 along the surface away from the axis
+ *              The gas moves in phi only and the surface depends on neither t nor phi, so n is orthogonal to the gas four-velocity and the boost leaves
+ *              e2 and e3 alone: this is the proper normal in the gas frame, not a flat-space approximation.  At theta = pi / 2 with Hp = 0 it is
+ *              |P_th| / E and atan2(P_phi, P_r).  A ray that entered through the vertical wall at r_in or r_out is treated with the local Hp like any other.
+ *   bad-angle  mu not finite, mu > 1, E <= 0, or nn not finite or zero.  Counted, and dropped under a limb law that needs the angle, as on the flat disc.
+ * Not covered: the hot spot, the Stokes passes and KR_V_PLUNGE on a surface, kr_post_emissivity_mu_dev_f64 on a surface, higher-order images, f32. */
+typedef struct kr_disc_surface {
+    double r_in, r_out, slope, scale;
+} kr_disc_surface;
+#ifdef __cplusplus
+static_assert(sizeof(kr_disc_surface) == 32, "kr_disc_surface is 32 bytes (raytrace_cpu_amd/capi.py DiscSurface)");
+#endif
+
 /* The polarisation of disc emission seen on a distant image plane.  The records are an image plane's (reverse = 1), the gas is the orbiting observer
  * above (motion = 0), the observer sits at inclination i = inc_deg pi / 180; sin(i) is taken once on the host.
  *   frame      exactly the one above: a = reverse ? -spin : spin, the metric g(a) at the record's (r, theta), the Tetrad legs e_t, e1 (phi), e2 (theta),
@@ -487,8 +516,8 @@ static_assert(sizeof(kr_pol_law) == 16, "kr_pol_law is 16 bytes (raytrace_cpu_am
  * polarisation degree sqrt(Q^2 + U^2) / I and the angle atan2(U, Q) / 2 are the caller's to take.  ne in 1 ... 4096, as above.
  * The reduce forms take records that carry their redshift (g is READ from the record) and recompute the frame of the on-disc records for mu, c2, s2
  * and bad-pol: unlike kr_reduce_spectrum_* they take a limb law.
- * Not covered: the plunging flow (KR_V_PLUNGE is refused: polar_value has no Gram-Schmidt form), Q and U of the reverberation response, the thick-disc
- * surface, higher-order images, f32 records, a second pass for returning radiation. */
+ * Not covered: the plunging flow (KR_V_PLUNGE is refused: polar_value has no Gram-Schmidt form), Q and U of the reverberation response, Q and U on the
+ * thick-disc surface (I(E) has it: kr_post_spectrum_surface_dev_f64, kr_disc_surface above), higher-order images, f32 records, a second pass for returning radiation. */
 typedef struct kr_spectrum_model {
     double e_min, de;              /* output energies: the centres of these bins; log_e: de is the ratio between edges */
     double r_isco, r_disc;         /* disc filter; the span of the zones */
@@ -1368,6 +1397,32 @@ int kr_post_response_dev_f64(double spin, double V, int reverse, int projradius,
                              const kr_limb_law* law, void* d_rays, int64_t n, void* d_out, void* stream);
 int kr_reduce_response_dev_f64(const kr_response_model* r, const void* d_rays, int64_t n, void* d_out, void* stream);
 int kr_reduce_response_f64(const kr_response_model* r, const kr_ray_f64* rays, int64_t n, double* out);
+
+/* ---- the line, the continuum, the response and the angles of rays that LANDED ON THE SURFACE of a disc (kr_disc_surface above has the rule) -------
+ * Each entry point takes the surface and what its flat twin takes without V, projradius and motion: the observer is the Keplerian gas at rho.  Every
+ * one validates its arguments before it touches a device: KR_EINVAL (message in kr_last_error, naming the parameter) for a null surface, whatever
+ * KR_STOP_THICKDISC refuses of its stop_params, a null pointer, n < 0, and whatever the flat twin refuses of the bins, the model and the limb law.
+ * n == 0 is KR_OK and adds nothing.
+ * kr_angles_surface_dev_f64: d_angles[2 i] = mu, d_angles[2 i + 1] = chi to the surface normal for every record with steps > 0, whatever it landed on
+ * (NaN in both otherwise); reads the records and never writes them.  kr_angles_surface_f64: host records, host angles.
+ * kr_post_*_surface_dev_f64: range_phi(lo, hi) + redshift(V = -1, reverse, projradius = 1, motion = 0) + the pass; rays[] ends up exactly as after
+ * kr_post_image_surface_dev_f64.  The layouts are the flat passes' word for word: the line 2 nt ne + 3 doubles (kr_post_line_limb_dev_f64's), the
+ * spectrum ne + 4, the response nt ne + 4.  All ADD into their output.
+ * kr_reduce_*_surface_dev_f64: records that carry their redshift and wrapped phi; read only; isotropic (the line's bad_angle word stays 0).  The _f64
+ * forms take host records and overwrite host output. */
+int kr_angles_surface_dev_f64(const kr_disc_surface* s, double spin, int reverse, const void* d_rays, int64_t n, void* d_angles, void* stream);
+int kr_angles_surface_f64(const kr_disc_surface* s, double spin, int reverse, const kr_ray_f64* rays, int64_t n, double* angles);
+int kr_post_line_surface_dev_f64(const kr_disc_surface* s, double spin, int reverse, double lo, double hi, const kr_line_bins* b, const kr_limb_law* law,
+                                 void* d_rays, int64_t n, void* d_line, void* stream);
+int kr_reduce_line_surface_dev_f64(const kr_disc_surface* s, const kr_line_bins* b, const void* d_rays, int64_t n, void* d_line, void* stream);
+int kr_post_spectrum_surface_dev_f64(const kr_disc_surface* s, double spin, int reverse, double lo, double hi, const kr_spectrum_model* m,
+                                     const kr_limb_law* law, void* d_rays, int64_t n, void* d_out, void* stream);
+int kr_reduce_spectrum_surface_dev_f64(const kr_disc_surface* s, const kr_spectrum_model* m, const void* d_rays, int64_t n, void* d_out, void* stream);
+int kr_reduce_spectrum_surface_f64(const kr_disc_surface* s, const kr_spectrum_model* m, const kr_ray_f64* rays, int64_t n, double* out);
+int kr_post_response_surface_dev_f64(const kr_disc_surface* s, double spin, int reverse, double lo, double hi, const kr_response_model* r,
+                                     const kr_limb_law* law, void* d_rays, int64_t n, void* d_out, void* stream);
+int kr_reduce_response_surface_dev_f64(const kr_disc_surface* s, const kr_response_model* r, const void* d_rays, int64_t n, void* d_out, void* stream);
+int kr_reduce_response_surface_f64(const kr_disc_surface* s, const kr_response_model* r, const kr_ray_f64* rays, int64_t n, double* out);
 
 /* ---- orbiting hot spot on the disc (kr_hotspot above has the rule) ------------------------------------------------------------------------------
  * Every entry point validates its arguments before it touches a device: KR_EINVAL (message in kr_last_error) for a null pointer, n < 0, whatever the

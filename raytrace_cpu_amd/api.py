@@ -540,7 +540,16 @@ def default_image_bins(spec, bins):
     return ib
 
 
-def line_profile(imageplane_spec, params, bins, mode="rays", image_bins=None, limb=None, V=-1.0):
+def _surface_arg(what, surface, V=-1.0, pol=None):
+    """The capi.DiscSurface of a surface= argument; the surface passes keep the Keplerian observer at rho and carry no polarisation."""
+    if V == capi.V_PLUNGE:
+        raise KrError(f"{what}: surface cannot be combined with V = V_PLUNGE (the surface passes keep the Keplerian observer at rho)")
+    if pol is not None:
+        raise KrError(f"{what}: surface cannot be combined with pol (the Stokes passes know no surface)")
+    return capi.disc_surface(surface)
+
+
+def line_profile(imageplane_spec, params, bins, mode="rays", image_bins=None, limb=None, V=-1.0, surface=None):
     """The emission line of an image plane, resident on the device from start to finish, as the kr_line_profile app runs it:
     ImagePlane ctor + redshift_start (kr_imageplane_init_emit_dev_f64) -> trace (kr_trace_dev_f64) -> either
       mode="rays":   redshift + range_phi + line bins per ray (kr_post_line_dev_f64), or
@@ -550,7 +559,22 @@ def line_profile(imageplane_spec, params, bins, mode="rays", image_bins=None, li
     limb (mode="rays" only): None for the isotropic line through kr_post_line_dev_f64, or a limb law of the emission angle in the disc frame --
     (law, coeff) or "isotropic", "laor" (1 + 2.06 mu), "brightening" (log(1 + 1 / mu)) -- through kr_post_line_limb_dev_f64.
     V: the disc flow of the redshift, -1 Keplerian or capi.V_PLUNGE (plunging inside the ISCO: set bins.r_isco to the inner radius wanted).
+    surface (mode="rays" only): None, or the surface of a disc of finite thickness -- (r_in, r_out, slope, scale) or a capi.DiscSurface; trace to it with
+    thick_disc_params(...), as for surface_image.  The line is then that of the rays that LANDED on the surface, binned by rho = r sin(theta), the
+    emission angle taken to the surface normal (kr_post_line_surface_dev_f64; limb None is the isotropic law) and "bad_angle" is always there.
+    V = capi.V_PLUNGE is refused with a surface.
     Returns line_from_words(...) plus "stats" (the trace's kr_stats) and, with a limb law, "bad_angle"."""
+    if surface is not None:
+        sf = _surface_arg("line_profile", surface, V)
+        if mode != "rays":
+            raise KrError("line_profile: a surface needs mode='rays'")
+        law = capi.limb_law(limb if limb is not None else "isotropic")
+        words, stats, _ = _imageplane_run("line_profile", imageplane_spec, params, line_words(bins) + 1, lambda L, dev, d_rays, n, d_out: capi.check(
+            L, L.kr_post_line_surface_dev_f64(C.byref(sf), -1 * imageplane_spec.spin, 1, -np.pi, np.pi, C.byref(bins), C.byref(law), d_rays, n, d_out, None),
+            "kr_post_line_surface"))
+        res = line_from_words(bins, words[:-1])
+        res["stats"], res["bad_angle"], res["surface"] = stats, _rounded(words[-1]), (sf.r_in, sf.r_out, sf.slope, sf.scale)
+        return res
     if mode not in ("rays", "pixels"):
         raise KrError(f"line_profile: mode must be 'rays' or 'pixels', got {mode!r}")
     if limb is not None and mode != "rays":
@@ -585,23 +609,33 @@ def line_profile(imageplane_spec, params, bins, mode="rays", image_bins=None, li
     return res
 
 
-def arrival_angles(rays, spin, V=-1.0, reverse=0, projradius=0):
+def arrival_angles(rays, spin, V=-1.0, reverse=0, projradius=0, surface=None):
     """kr_angles_f64 / kr_angles_dev_f64: (mu, chi) of every record in the rest frame of the orbiting gas, the observer of redshift(spin, V, reverse,
     projradius).  mu = |P_th| / E is the cosine of the angle to the disc normal, chi = atan2(P_phi, P_r) the azimuth about it; NaN for records with
     steps <= 0; a bad-angle record (mu not finite or > 1: include/kr_trace.h) keeps its values.  rays: a host array of Ray<double> records, or
-    (device pointer, n) for records that are already on the device."""
+    (device pointer, n) for records that are already on the device.
+    surface: None, or (r_in, r_out, slope, scale) / a capi.DiscSurface: the angles to the normal of that surface in the frame of the Keplerian gas at
+    rho = r sin(theta) (kr_angles_surface_f64 / kr_angles_surface_dev_f64: mu = |P_n| / E, chi = atan2(P_phi, P_s)); V and projradius are then not read
+    (V = capi.V_PLUNGE is refused)."""
     L = lib()
+    sf = _surface_arg("arrival_angles", surface, V) if surface is not None else None
     if isinstance(rays, tuple):
         d_ptr, n = rays
         d = d_ptr if isinstance(d_ptr, C.c_void_p) else C.c_void_p(d_ptr)
         with DeviceScope(L) as dev:
             d_out = dev.alloc(2 * n * 8) if n > 0 else C.c_void_p()
-            capi.check(L, L.kr_angles_dev_f64(spin, V, int(reverse), int(projradius), 0, d, n, d_out, None), "kr_angles_dev")
+            if sf is not None:
+                capi.check(L, L.kr_angles_surface_dev_f64(C.byref(sf), spin, int(reverse), d, n, d_out, None), "kr_angles_surface_dev")
+            else:
+                capi.check(L, L.kr_angles_dev_f64(spin, V, int(reverse), int(projradius), 0, d, n, d_out, None), "kr_angles_dev")
             out = dev.fetch(d_out, 2 * n)
     else:
         _rays_arg(rays, capi.RAY_F64)
         out = np.zeros(2 * len(rays))
-        capi.check(L, L.kr_angles_f64(spin, V, int(reverse), int(projradius), 0, _ptr(rays), len(rays), _ptr(out)), "kr_angles")
+        if sf is not None:
+            capi.check(L, L.kr_angles_surface_f64(C.byref(sf), spin, int(reverse), _ptr(rays), len(rays), _ptr(out)), "kr_angles_surface")
+        else:
+            capi.check(L, L.kr_angles_f64(spin, V, int(reverse), int(projradius), 0, _ptr(rays), len(rays), _ptr(out)), "kr_angles")
     return out[0::2].copy(), out[1::2].copy()
 
 
@@ -1833,7 +1867,7 @@ def resample_spectrum(energy, counts, spec_bins):
     return float(energy[0]), s_de, np.interp(np.log(nodes), np.log(energy), counts)
 
 
-def disc_spectrum(imageplane_spec, params, model, limb=None, return_records=False, V=-1.0, pol=None):
+def disc_spectrum(imageplane_spec, params, model, limb=None, return_records=False, V=-1.0, pol=None, surface=None):
     """The continuum spectrum of the disc seen on an image plane, resident on the device from start to finish, as the kr_disc_spectrum app runs it:
     ImagePlane ctor + redshift_start (kr_imageplane_init_emit_dev_f64) -> trace (kr_trace_dev_f64; `params` as for the image app: the stored, negated
     spin) -> redshift + range_phi + the spectrum (kr_post_spectrum_dev_f64).  model: a capi.SpectrumModel; limb: None (isotropic) or a limb law as for
@@ -1843,9 +1877,21 @@ def disc_spectrum(imageplane_spec, params, model, limb=None, return_records=Fals
     pol: None, or a polarisation degree law as for stokes_image ((law, coeff), a name of capi.POL_LAWS or a capi.PolLaw): the Stokes spectra.  The last
     pass is then kr_post_spectrum_stokes_dev_f64 at the plane's own inclination (V = capi.V_PLUNGE is refused) and the result is
     spectrum_stokes_from_words(...) plus "stats": "q", "u", "pol_degree", "pol_angle" and "bad_pol" join it (and "bad_angle" leaves it: bad-angle is a
-    subset of bad-pol)."""
+    subset of bad-pol).
+    surface: None, or (r_in, r_out, slope, scale) / a capi.DiscSurface, as for line_profile: the continuum of the rays that landed on that surface
+    (kr_post_spectrum_surface_dev_f64; trace to it with thick_disc_params(...)).  Refused together with V = capi.V_PLUNGE or pol."""
     law = capi.limb_law(limb if limb is not None else "isotropic")
     sized = 1 <= model.ne <= 4096                      # (the pass refuses the rest: it gets a null buffer)
+    if surface is not None:
+        sf = _surface_arg("disc_spectrum", surface, V, pol)
+        words, stats, records = _imageplane_run("disc_spectrum", imageplane_spec, params, spectrum_words(model) if sized else 0, lambda L, dev, d_rays, n, d_out: capi.check(
+            L, L.kr_post_spectrum_surface_dev_f64(C.byref(sf), -1 * imageplane_spec.spin, 1, -np.pi, np.pi, C.byref(model), C.byref(law), d_rays, n, d_out, None),
+            "kr_post_spectrum_surface"), return_records)
+        res = spectrum_from_words(model, words)
+        res["stats"], res["surface"] = stats, (sf.r_in, sf.r_out, sf.slope, sf.scale)
+        if return_records:
+            res["records"] = records
+        return res
     if pol is not None:
         plaw, spin, inc = capi.pol_law(pol), -1 * imageplane_spec.spin, imageplane_spec.inc_deg
         words, stats, records = _imageplane_run("disc_spectrum", imageplane_spec, params, spectrum_stokes_words(model) if sized else 0, lambda L, dev, d_rays, n, d_out: capi.check(
@@ -1866,14 +1912,43 @@ def disc_spectrum(imageplane_spec, params, model, limb=None, return_records=Fals
     return res
 
 
+def _surface_rows(res):
+    """The rows "# DISCSLOP", "# DISCSCAL", "# DISCRIN" with which a program's text file opens for a disc with a surface ("" for a result without one)."""
+    if "surface" not in res:
+        return ""
+    r_in, _, slope, scale = res["surface"]
+    return "".join("%20s" % k + _path_field(float(v)) + "\n" for k, v in (("# DISCSLOP", slope), ("# DISCSCAL", scale), ("# DISCRIN", r_in)))
+
+
+def line_text(res, bins, limb=None):
+    """The file kr_line_profile writes for a result of line_profile(..., bins, ...): with a surface the rows of _surface_rows, with `limb` (what the
+    program's limb key was given: (law, coeff) or a name) the rows "# LIMB" and "# LIMBCOEF", then one row per bin: t_mid E_mid flux count, a blank
+    line after each time bin.  Every field setw(20), the numbers scientific with precision 8 (host/include/text_output.h)."""
+    head = _surface_rows(res)
+    if limb is not None:
+        law = capi.limb_law(limb)
+        head += "%20s%20d\n" % ("# LIMB", law.law) + "%20s" % "# LIMBCOEF" + _path_field(law.coeff) + "\n"
+    time_axis = not (bins.nt == 1 and bins.dt <= 0)
+    parts = [head]
+    for j in range(bins.nt):
+        t_mid = bins.t0 + (j + 0.5) * bins.dt if time_axis else float("nan")
+        for i in range(bins.ne):
+            lo = bins.e_min * math.pow(bins.de, i) if bins.log_e else bins.e_min + i * bins.de
+            hi = bins.e_min * math.pow(bins.de, i + 1) if bins.log_e else bins.e_min + (i + 1) * bins.de
+            parts.append(_path_field(t_mid) + _path_field(0.5 * (lo + hi)) + _path_field(float(res["flux"][j, i])) + "%20d\n" % int(res["count"][j, i]))
+        parts.append("\n")
+    return "".join(parts)
+
+
 def spectrum_text(res):
     """The file kr_disc_spectrum writes for a result of disc_spectrum(): three comment rows with the tallies ("# ON_DISC", "# USED", "# BAD_ANGLE" and
     their counts), then one row per energy: E flux.  Every field setw(20), the numbers scientific with precision 8 (host/include/text_output.h).  A result
-    that carries Stokes sums (disc_spectrum(pol=...)): the third tally is "# BAD_POL" and the rows are E I Q U."""
+    that carries Stokes sums (disc_spectrum(pol=...)): the third tally is "# BAD_POL" and the rows are E I Q U.  A result for a disc with a surface
+    (disc_spectrum(surface=...)) opens with the rows "# DISCSLOP", "# DISCSCAL", "# DISCRIN"."""
     if "q" in res:
         head = "".join("%20s%20d\n" % (f"# {k.upper()}", res[k]) for k in ("on_disc", "used", "bad_pol"))
         return head + "".join("".join(_path_field(float(v)) for v in row) + "\n" for row in zip(res["energy"], res["flux"], res["q"], res["u"]))
-    head = "".join("%20s%20d\n" % (f"# {k.upper()}", res[k]) for k in ("on_disc", "used", "bad_angle"))
+    head = _surface_rows(res) + "".join("%20s%20d\n" % (f"# {k.upper()}", res[k]) for k in ("on_disc", "used", "bad_angle"))
     return head + "".join(_path_field(float(e)) + _path_field(float(f)) + "\n" for e, f in zip(res["energy"], res["flux"]))
 
 
@@ -1905,14 +1980,26 @@ def reduce_response(model, rays):
     return response_from_words(model, out)
 
 
-def disc_response(imageplane_spec, params, model, limb=None, return_records=False, V=-1.0):
+def disc_response(imageplane_spec, params, model, limb=None, return_records=False, V=-1.0, surface=None):
     """The energy-time response of the disc seen on an image plane, resident on the device from start to finish, as the kr_reverb_response app runs it:
     ImagePlane ctor + redshift_start -> trace (`params` as for the image app: the stored, negated spin) -> redshift + range_phi + the response
     (kr_post_response_dev_f64).  model: a capi.ResponseModel; limb: None (isotropic) or a limb law as for line_profile.  Only the nt ne + 4 words are read
     back (and, with return_records, the final records: for tests).  Returns response_from_words(...) plus "stats" (the trace's kr_stats).  The response is
-    per image-plane pixel: multiply by dx dy / D^2 for a flux density.  V: -1 or capi.V_PLUNGE, as for line_profile (model.spec.r_isco is the inner edge)."""
+    per image-plane pixel: multiply by dx dy / D^2 for a flux density.  V: -1 or capi.V_PLUNGE, as for line_profile (model.spec.r_isco is the inner edge).
+    surface: None, or (r_in, r_out, slope, scale) / a capi.DiscSurface, as for line_profile: the response of the rays that landed on that surface
+    (kr_post_response_surface_dev_f64; trace to it with thick_disc_params(...)).  Refused together with V = capi.V_PLUNGE."""
     law = capi.limb_law(limb if limb is not None else "isotropic")
     sized = 1 <= model.spec.ne <= 4096 and 1 <= model.nt and model.nt * model.spec.ne <= 1 << 24        # (the pass refuses the rest: it gets a null buffer)
+    if surface is not None:
+        sf = _surface_arg("disc_response", surface, V)
+        words, stats, records = _imageplane_run("disc_response", imageplane_spec, params, response_words(model) if sized else 0, lambda L, dev, d_rays, n, d_out: capi.check(
+            L, L.kr_post_response_surface_dev_f64(C.byref(sf), -1 * imageplane_spec.spin, 1, -np.pi, np.pi, C.byref(model), C.byref(law), d_rays, n, d_out, None),
+            "kr_post_response_surface"), return_records)
+        res = response_from_words(model, words)
+        res["stats"], res["surface"] = stats, (sf.r_in, sf.r_out, sf.slope, sf.scale)
+        if return_records:
+            res["records"] = records
+        return res
     words, stats, records = _imageplane_run("disc_response", imageplane_spec, params, response_words(model) if sized else 0, lambda L, dev, d_rays, n, d_out: capi.check(
         L, L.kr_post_response_dev_f64(-1 * imageplane_spec.spin, V, 1, 0, 0, -np.pi, np.pi, C.byref(model), C.byref(law), d_rays, n, d_out, None), "kr_post_response"),
         return_records)

@@ -49,6 +49,55 @@ inline kr_pol_law pol_law_of(const Options& opt)
     return pol;
 }
 
+// The surface keys of the programs that bin a disc of finite thickness seen from an image plane (kr_line_profile, kr_disc_spectrum, kr_reverb_response),
+// read as kr_imageplane_disc_image reads them: disc_slope and disc_scale, either of which gives the disc the surface z = +-H(rho),
+// H = disc_slope rho + disc_scale (1 - sqrt(disc_rin / rho)), between disc_rin (default: the ISCO) and r_disc (KR_STOP_THICKDISC and kr_disc_surface,
+// include/kr_trace.h).  The rays stop on the surface, the gas orbits at the cylindrical radius rho and the pass is the program's kr_post_*_surface_dev_f64.
+// Without the keys: nothing, the program and its output files what they were.  With them a text file gains the rows "# DISCSLOP", "# DISCSCAL" and
+// "# DISCRIN", a FITS header the keywords of those names.
+struct DiscSurfaceKeys {
+    bool thick = false;
+    kr_disc_surface surface = {0, 0, 0, 0};
+
+    DiscSurfaceKeys(const Options& opt, double r_isco, double r_disc)
+    {
+        thick = opt.has("disc_slope") || opt.has("disc_scale");
+        surface.slope = opt.num("disc_slope", 0);
+        surface.scale = opt.num("disc_scale", 0);
+        surface.r_in = opt.num("disc_rin", r_isco);
+        surface.r_out = r_disc;
+    }
+    // the refusals: the surface keeps the Keplerian flow and carries no polarisation
+    void refuse_with(bool plunge, bool stokes) const
+    {
+        if (thick && plunge) throw std::invalid_argument("plunge: the surface of a thick disc keeps the Keplerian flow (no disc_slope / disc_scale)");
+        if (thick && stokes) throw std::invalid_argument("pol_law / pol_coeff: the Stokes passes know no disc surface (no disc_slope / disc_scale)");
+    }
+    // the trace stops on the surface
+    void stop_on(kr_params& p) const
+    {
+        if (!thick) return;
+        p.stop_kind = KR_STOP_THICKDISC;
+        p.stop_params[0] = surface.r_in; p.stop_params[1] = surface.r_out; p.stop_params[2] = surface.slope; p.stop_params[3] = surface.scale;
+    }
+    template <class Text>
+    void write_rows(Text& out) const
+    {
+        if (!thick) return;
+        out << "# DISCSLOP" << surface.slope << std::endl;
+        out << "# DISCSCAL" << surface.scale << std::endl;
+        out << "# DISCRIN" << surface.r_in << std::endl;
+    }
+    template <class Fits>
+    void write_keywords(Fits& fits) const
+    {
+        if (!thick) return;
+        fits.write_keyword("DISCSLOP", "Disc surface: slope of H(rho)", surface.slope);
+        fits.write_keyword("DISCSCAL", "Disc surface: scale of H(rho)", surface.scale);
+        fits.write_keyword("DISCRIN", "Disc surface: inner radius", surface.r_in);
+    }
+};
+
 struct DiscPlaneSetup {
     std::string out_name, integ, arith;
     double dist, incl, plane_phi0, spin, r_disc, r_isco, q1, rb1, q2, rb2, q3, precision, rk45_tol;

@@ -16,6 +16,10 @@
 //   pol_law, pol_coeff        optional, the keys of kr_imageplane_polarisation (pol_law = 1, pol_coeff = 0.1171 when only one of them is given): the
 //                             Stokes spectra Q(E), U(E) of the continuum (kr_post_spectrum_stokes_dev_f64) on the plane's own x and y axes; not with
 //                             plunge = 1 (the polarisation frame has no plunging form)
+//   disc_slope, disc_scale    (and disc_rin = ISCO; imageplane_app.h, DiscSurfaceKeys) with either key the disc has the surface of KR_STOP_THICKDISC and the
+//                             spectrum is that of the rays that landed on it, every radius the cylindrical rho (kr_post_spectrum_surface_dev_f64); not
+//                             with plunge = 1 or pol_law.  The file opens with the rows "# DISCSLOP", "# DISCSCAL", "# DISCRIN"; without the keys it is
+//                             byte for byte what it was
 // Every key may also be given as --key=value, which takes precedence over the file.  Nx and Ny are read as int, as kr_imageplane_disc_image reads
 // them (before imageplane_app.h: as double, then cast; the same for a key written as a plain integer).
 // Output: TextOutput (width 20, precision 8): three comment rows "# ON_DISC", "# USED", "# BAD_ANGLE" with their counts, then one row per energy:
@@ -75,6 +79,8 @@ static void program(const krapp::Options& opt)
     const bool stokes = opt.has("pol_law") || opt.has("pol_coeff");
     const kr_pol_law pol = krapp::pol_law_of(opt);
     if (stokes && s.flow.plunge) throw invalid_argument("pol_law / pol_coeff: the Stokes spectra do not take the plunging disc flow (plunge = 1)");
+    const krapp::DiscSurfaceKeys disc(opt, s.r_isco, s.r_disc);
+    disc.refuse_with(s.flow.plunge, stokes);
 
     const double e_min = opt.num("e_min", 0.1), e_max = opt.num("e_max", 10);
     const int ne = (int) opt.num("Nen", 100);
@@ -125,13 +131,17 @@ static void program(const krapp::Options& opt)
         }
         rest.print();
     }
-    const kr_params p = s.params(KR_RK45);
+    kr_params p = s.params(KR_RK45);
+    disc.stop_on(p);
 
     // ---- device pipeline: init_emit -> trace -> redshift + range_phi + spectrum ---------------------------------------------------------
     krapp::DiscPlaneRun run(s, plane);
     const int64_t words = (int64_t) (stokes ? 3 : 1) * ne + 4;
     run.trace(plane, p, words);
-    if (stokes)
+    if (disc.thick)
+        krapp::check(kr_post_spectrum_surface_dev_f64(&disc.surface, -s.spin, 1, -1 * M_PI, M_PI, &sm, &limb, run.rays->get(), run.n, run.acc->get(), nullptr),
+                     "redshift + range_phi + spectrum of the surface");
+    else if (stokes)
         krapp::check(kr_post_spectrum_stokes_dev_f64(-s.spin, s.flow.V(), 1, 0, 0, -1 * M_PI, M_PI, s.incl, &sm, &limb, &pol, run.rays->get(), run.n, run.acc->get(), nullptr),
                      "redshift + range_phi + spectrum with Stokes sums");
     else
@@ -146,6 +156,7 @@ static void program(const krapp::Options& opt)
     {
         TextOutput outfile(s.out_name);
         s.flow.write_rows(outfile);
+        disc.write_rows(outfile);
         outfile << "# ON_DISC" << static_cast<long>(tallies[0]) << endl;
         outfile << "# USED" << static_cast<long>(tallies[1]) << endl;
         outfile << (stokes ? "# BAD_POL" : "# BAD_ANGLE") << static_cast<long>(tallies[2]) << endl;

@@ -17,6 +17,10 @@
 //                            the r column must be log-spaced
 //   limb, limb_coeff = 2.06  optional limb law of the emission angle mu in the disc frame (line_mode = rays): 0 isotropic, 1 the weight
 //                            1 + limb_coeff mu (Laor), 2 log(1 + 1 / mu) (limb brightening); kr_limb_law in include/kr_trace.h
+//   disc_slope, disc_scale   (and disc_rin = ISCO; imageplane_app.h, DiscSurfaceKeys) with either key the disc has the surface of KR_STOP_THICKDISC: the
+//                            rays stop on it and the line is that of the rays that landed on it, binned by the cylindrical radius rho, the limb law
+//                            taken to the surface normal (kr_post_line_surface_dev_f64; line_mode = rays, no plunge); the file opens with the rows
+//                            "# DISCSLOP", "# DISCSCAL", "# DISCRIN".  Without the keys the program and its file are what they were.
 // Every key may also be given as --key=value, which takes precedence over the file.  Nx, Ny, img_Nx and img_Ny are read as int, as
 // kr_imageplane_disc_image reads them (before imageplane_app.h: as double, then cast; the same for a key written as a plain integer).
 // Output: TextOutput (width 20, precision 8), one row per bin: t_mid E_mid flux count (t_mid is nan without a time axis), a blank line
@@ -57,6 +61,9 @@ static void program(const krapp::Options& opt)
     limb.law = (int32_t) opt.num("limb", 0);
     limb.coeff = opt.num("limb_coeff", 2.06);
     if (with_limb && mode != "rays") throw invalid_argument("limb: a limb law needs line_mode = rays (a pixel's mean has no emission angle)");
+    const krapp::DiscSurfaceKeys disc(opt, s.r_isco, s.r_disc);
+    disc.refuse_with(s.flow.plunge, opt.has("pol_law") || opt.has("pol_coeff"));
+    if (disc.thick && mode != "rays") throw invalid_argument("disc_slope / disc_scale: the line of a disc surface needs line_mode = rays");
     s.print_isco();
 
     const kr_imageplane plane = s.plane();
@@ -78,14 +85,18 @@ static void program(const krapp::Options& opt)
     }
 
     const kr_image_bins ib = s.image_bins();
-    const kr_params p = s.params(KR_RK45);
+    kr_params p = s.params(KR_RK45);
+    disc.stop_on(p);
 
     // ---- device pipeline: init_emit -> trace -> (redshift + range_phi + line) or (redshift + range_phi + planes -> line) ----------------
     krapp::DiscPlaneRun run(s, plane);
-    const int64_t words = 2 * (int64_t) nt * ne + 2 + (with_limb ? 1 : 0);      // the limb pass closes its histogram with bad_angle
+    const bool with_angle = with_limb || disc.thick;
+    const int64_t words = 2 * (int64_t) nt * ne + 2 + (with_angle ? 1 : 0);      // the limb and surface passes close their histogram with bad_angle
     run.trace(plane, p, words);
     void *rays = run.rays->get(), *line = run.acc->get();
-    if (with_limb) {
+    if (disc.thick) {
+        krapp::check(kr_post_line_surface_dev_f64(&disc.surface, -s.spin, 1, -1 * M_PI, M_PI, &lb, &limb, rays, run.n, line, nullptr), "redshift + range_phi + line of the surface");
+    } else if (with_limb) {
         krapp::check(kr_post_line_limb_dev_f64(-s.spin, s.flow.V(), 1, 0, 0, -1 * M_PI, M_PI, &lb, &limb, rays, run.n, line, nullptr), "redshift + range_phi + limb-law line");
     } else if (mode == "rays") {
         krapp::check(kr_post_line_dev_f64(-s.spin, s.flow.V(), 1, 0, 0, -1 * M_PI, M_PI, &lb, rays, run.n, line, nullptr), "redshift + range_phi + line");
@@ -103,10 +114,11 @@ static void program(const krapp::Options& opt)
 
     const int64_t nb = (int64_t) nt * ne;
     cout << static_cast<long>(h[nb * 2]) << (mode == "rays" ? " rays" : " pixels") << " on the disc, " << static_cast<long>(h[nb * 2 + 1]) << " binned" << endl;
-    if (with_limb) cout << static_cast<long>(h[nb * 2 + 2]) << " rays on the disc have no emission angle (bad-angle)" << endl;
+    if (with_angle) cout << static_cast<long>(h[nb * 2 + 2]) << " rays on the disc have no emission angle (bad-angle)" << endl;
     {
         TextOutput outfile(s.out_name);
         s.flow.write_rows(outfile);
+        disc.write_rows(outfile);
         if (with_limb) {
             outfile << "# LIMB" << limb.law << endl;
             outfile << "# LIMBCOEF" << limb.coeff << endl;

@@ -11,6 +11,9 @@
 //                             delay by radius; without it the program uses the powerlaw3 emissivity and no source delay
 //   t0 = dist, dt = 1, Nt = 100   the time rows: row j holds t0 + j dt <= t + delay < t0 + (j + 1) dt, in GM / c^3.  t0 is the caller's choice of the
 //                             instant the direct continuum arrives.
+//   disc_slope, disc_scale    (and disc_rin = ISCO; imageplane_app.h, DiscSurfaceKeys) with either key the disc has the surface of KR_STOP_THICKDISC and the
+//                             response is that of the rays that landed on it (kr_post_response_surface_dev_f64; no plunge); the header gains DISCSLOP,
+//                             DISCSCAL and DISCRIN.  Without the keys the program and its file are what they were.
 // Every key may also be given as --key=value, which takes precedence over the file.
 // Output: a FITS file (host/include/fits_output.h).  The primary HDU holds the response, Nen pixels along axis 1 and Nt along axis 2, with the tallies
 // ON_DISC, USED, BADANGLE and OUTSIDE and the axes' parameters as header keys; the HDUs ENERGY (Nen x 1) and TIME (Nt x 1) hold the sampling energies and
@@ -43,6 +46,8 @@ static void program(const krapp::Options& opt)
     const double t0 = opt.num("t0", s.dist), dt = opt.num("dt", 1);
     const int nt = (int) opt.num("Nt", 100);
     if (nt < 1) throw invalid_argument("Nt: at least one time row");
+    const krapp::DiscSurfaceKeys disc(opt, s.r_isco, s.r_disc);
+    disc.refuse_with(s.flow.plunge, opt.has("pol_law") || opt.has("pol_coeff"));
     s.print_isco();
 
     const kr_imageplane plane = s.plane();
@@ -65,13 +70,18 @@ static void program(const krapp::Options& opt)
         cout << "emissivity and delay table " << emis_file << ": " << sm.table_nr << " bins from r = " << table.r_min << ", ratio " << table.dr << endl;
     }
     rest.print();
-    const kr_params p = s.params(KR_RK45);
+    kr_params p = s.params(KR_RK45);
+    disc.stop_on(p);
 
     // ---- device pipeline: init_emit -> trace -> redshift + range_phi + response ---------------------------------------------------------
     krapp::DiscPlaneRun run(s, plane);
     const int64_t cells = (int64_t) nt * ne, words = cells + 4;
     run.trace(plane, p, words);
-    krapp::check(kr_post_response_dev_f64(-s.spin, s.flow.V(), 1, 0, 0, -1 * M_PI, M_PI, &rm, &limb, run.rays->get(), run.n, run.acc->get(), nullptr), "redshift + range_phi + response");
+    if (disc.thick)
+        krapp::check(kr_post_response_surface_dev_f64(&disc.surface, -s.spin, 1, -1 * M_PI, M_PI, &rm, &limb, run.rays->get(), run.n, run.acc->get(), nullptr),
+                     "redshift + range_phi + response of the surface");
+    else
+        krapp::check(kr_post_response_dev_f64(-s.spin, s.flow.V(), 1, 0, 0, -1 * M_PI, M_PI, &rm, &limb, run.rays->get(), run.n, run.acc->get(), nullptr), "redshift + range_phi + response");
     vector<double> h((size_t) words);
     krapp::check(kr_memcpy_d2h(h.data(), run.acc->get(), words * (int64_t) sizeof(double)), "d2h");
     const double ms_post = run.clock.lap_ms();
@@ -93,6 +103,7 @@ static void program(const krapp::Options& opt)
         fits.write_keyword("ISCO", "Innermost stable circular orbit", s.r_isco);
         fits.write_keyword("RDISC", "Maximum radius of disc", s.r_disc);
         s.flow.write_keywords(fits);
+        disc.write_keywords(fits);
         fits.write_keyword("NRAYS", "Number of rays", static_cast<long>(run.n));
         fits.write_keyword("ON_DISC", "Rays hitting disc", on_disc);
         fits.write_keyword("USED", "Rays with an emissivity and a delay", used);

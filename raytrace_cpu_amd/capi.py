@@ -140,6 +140,22 @@ def limb_law(limb):
     return out
 
 
+class DiscSurface(C.Structure):
+    """kr_disc_surface: the disc surface |z| = slope rho + scale (1 - sqrt(r_in / rho)), the stop_params of STOP_THICKDISC (include/kr_trace.h)."""
+    _fields_ = [("r_in", C.c_double), ("r_out", C.c_double), ("slope", C.c_double), ("scale", C.c_double)]
+
+
+assert C.sizeof(DiscSurface) == 32
+
+
+def disc_surface(surface):
+    """A DiscSurface from (r_in, r_out, slope, scale) -- the stop_params that api.thick_disc_params sets -- or a DiscSurface."""
+    if isinstance(surface, DiscSurface):
+        return surface
+    r_in, r_out, slope, scale = surface
+    return DiscSurface(float(r_in), float(r_out), float(slope), float(scale))
+
+
 class PolLaw(C.Structure):
     """kr_pol_law: the emitted polarisation degree at mu.  law 0: coeff; 1: coeff (1 - mu) / (1 + 3.582 mu) (include/kr_trace.h)."""
     _fields_ = [("coeff", C.c_double), ("law", C.c_int32), ("pad", C.c_int32)]
@@ -474,6 +490,16 @@ PROTOTYPES = {
     "kr_post_response_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, P(ResponseModel), P(LimbLaw), _vp, _i64, _vp, _vp]),
     "kr_reduce_response_dev_f64": (_int, [P(ResponseModel), _vp, _i64, _vp, _vp]),
     "kr_reduce_response_f64": (_int, [P(ResponseModel), _vp, _i64, _vp]),
+    "kr_angles_surface_dev_f64": (_int, [P(DiscSurface), _dbl, _int, _vp, _i64, _vp, _vp]),
+    "kr_angles_surface_f64": (_int, [P(DiscSurface), _dbl, _int, _vp, _i64, _vp]),
+    "kr_post_line_surface_dev_f64": (_int, [P(DiscSurface), _dbl, _int, _dbl, _dbl, P(LineBins), P(LimbLaw), _vp, _i64, _vp, _vp]),
+    "kr_reduce_line_surface_dev_f64": (_int, [P(DiscSurface), P(LineBins), _vp, _i64, _vp, _vp]),
+    "kr_post_spectrum_surface_dev_f64": (_int, [P(DiscSurface), _dbl, _int, _dbl, _dbl, P(SpectrumModel), P(LimbLaw), _vp, _i64, _vp, _vp]),
+    "kr_reduce_spectrum_surface_dev_f64": (_int, [P(DiscSurface), P(SpectrumModel), _vp, _i64, _vp, _vp]),
+    "kr_reduce_spectrum_surface_f64": (_int, [P(DiscSurface), P(SpectrumModel), _vp, _i64, _vp]),
+    "kr_post_response_surface_dev_f64": (_int, [P(DiscSurface), _dbl, _int, _dbl, _dbl, P(ResponseModel), P(LimbLaw), _vp, _i64, _vp, _vp]),
+    "kr_reduce_response_surface_dev_f64": (_int, [P(DiscSurface), P(ResponseModel), _vp, _i64, _vp, _vp]),
+    "kr_reduce_response_surface_f64": (_int, [P(DiscSurface), P(ResponseModel), _vp, _i64, _vp]),
     "kr_post_hotspot_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, P(HotSpot), P(LimbLaw), _vp, _i64, _vp, _vp]),
     "kr_reduce_hotspot_dev_f64": (_int, [P(HotSpot), _vp, _i64, _vp, _vp]),
     "kr_reduce_hotspot_f64": (_int, [P(HotSpot), _vp, _i64, _vp]),

@@ -12,7 +12,7 @@
 #include <cmath>
 #include <string>
 
-#include "kr_pass.hpp"
+#include "kr_disc_pass.hpp"
 
 namespace kr {
 
@@ -36,6 +36,33 @@ angles_kernel(const kr_ray_f64* __restrict__ rays, long long n, double spin, dou
             const Frame f = frame_value<PLUNGE>(geodesic_start_of(ray), spin, V, reverse, projradius, fl);
             mu = frame_mu(f);
             chi = frame_chi(f);
+        }
+        out[2 * i] = mu;
+        out[2 * i + 1] = chi;
+    }
+}
+
+// the angles to the normal of a disc surface (include/kr_trace.h, kr_angles_surface_dev_f64): mu = |P_n| / E, chi = atan2(P_phi, P_s) of every record
+// with steps > 0, whatever it landed on, in the frame of the Keplerian observer at rho.  Sized freely the kernel takes 170 VGPRs, two over the three-wave
+// line that angles_kernel sits on at 168; held to three waves per SIMD it takes 168 and spills two (profiles/surface_pass_ab.txt has both timed).
+#ifdef KR_ANGLES_SURFACE_FREE                    // A/B builds only (scripts/surface_pass_ab.py --free-angles): no second launch bound
+#define KR_ANGLES_SURFACE_BOUNDS __launch_bounds__(kBlock)
+#else
+#define KR_ANGLES_SURFACE_BOUNDS __launch_bounds__(kBlock, 3)
+#endif
+__global__ void KR_ANGLES_SURFACE_BOUNDS
+angles_surface_kernel(const kr_ray_f64* __restrict__ rays, long long n, double spin, int reverse, double* __restrict__ out, DiscSurface<true> sf)
+{
+    KR_GRID_STRIDE(i, n) {
+        const kr_ray_f64* ray = &rays[i];
+        double mu = __builtin_nan(""), chi = __builtin_nan("");
+        if (ray->steps > 0) {
+            const kr_ray_f64 v = geodesic_start_of(ray);
+            FrameCoef mc;
+            const Frame f = frame_value_coef(v, spin, -1.0, reverse, 1, &mc);
+            const SurfaceAngle s = surface_angle(sf, f, mc, v.r);
+            mu = s.mu;
+            chi = atan2(f.P_phi, s.P_s);
         }
         out[2 * i] = mu;
         out[2 * i + 1] = chi;
@@ -128,6 +155,15 @@ int angles_dev(double spin, double V, int reverse, int projradius, const void* d
         hipLaunchKernelGGL(angles_kernel<decltype(flow)::plunge>, dim3(grid_for(n, kBlock, kCapStream)), dim3(kBlock), 0, st, (const kr_ray_f64*) d, (long long) n, spin, V, reverse,
                            projradius, (double*) d_angles, flow.arg);
     });
+    KR_LAUNCH_CHECK();
+    return KR_OK;
+}
+
+int angles_surface_dev(const kr_disc_surface* s, double spin, int reverse, const void* d, int64_t n, void* d_angles, hipStream_t st)
+{
+    if (n <= 0) return KR_OK;
+    hipLaunchKernelGGL(angles_surface_kernel, dim3(grid_for(n, kBlock, kCapStream)), dim3(kBlock), 0, st, (const kr_ray_f64*) d, (long long) n, spin, reverse,
+                       (double*) d_angles, surface_dev(s));
     KR_LAUNCH_CHECK();
     return KR_OK;
 }

@@ -1310,6 +1310,117 @@ int kr_reduce_response_f64(const kr_response_model* r, const kr_ray_f64* rays, i
     return rc2;
 }
 
+// ---- the passes over rays that landed on a disc surface (kr_disc_surface; the SURFACE flavour of kr_line.hip, kr_spectrum.hip, kr_response.hip and the
+//      per-record angles of kr_angles.hip): the surface first, then what the flat twin validates; nothing touches a device before that ----
+int kr_angles_surface_dev_f64(const kr_disc_surface* s, double spin, int reverse, const void* d, int64_t n, void* d_angles, void* st)
+{
+    const int rc = surface_validate(s, "kr_angles_surface");
+    if (rc != KR_OK) return rc;
+    return on_device(n >= 0 && (n == 0 || (d && d_angles)), "kr_angles_surface: null argument or negative n",
+                     [&] { return angles_surface_dev(s, spin, reverse, d, n, d_angles, (hipStream_t) st); });
+}
+
+int kr_angles_surface_f64(const kr_disc_surface* s, double spin, int reverse, const kr_ray_f64* rays, int64_t n, double* angles)
+{
+    const int rc = surface_validate(s, "kr_angles_surface");
+    if (rc != KR_OK) return rc;
+    if (n < 0 || (n > 0 && (!rays || !angles))) return invalid("kr_angles_surface: null argument or negative n");
+    return with_staged_rays((void*) rays, n, sizeof(kr_ray_f64), kReads, nullptr, [&](void* d) -> int {
+        if (n == 0) return KR_OK;
+        DeviceBuffer d_angles;
+        int rc2 = d_angles.alloc((size_t) n * 2 * sizeof(double));
+        if (rc2 != KR_OK) return rc2;
+        rc2 = angles_surface_dev(s, spin, reverse, d, n, d_angles.p, nullptr);
+        if (rc2 != KR_OK) return rc2;
+        KR_HIP(hipMemcpy(angles, d_angles.p, (size_t) n * 2 * sizeof(double), hipMemcpyDeviceToHost));
+        return (int) KR_OK;
+    });
+}
+
+int kr_post_line_surface_dev_f64(const kr_disc_surface* s, double spin, int reverse, double lo, double hi, const kr_line_bins* b, const kr_limb_law* law, void* d, int64_t n,
+                                 void* d_line, void* st)
+{
+    int rc = surface_validate(s, "kr_post_line_surface");
+    if (rc == KR_OK) rc = line_validate(b, "kr_post_line_surface");
+    if (rc == KR_OK) rc = limb_validate(law, "kr_post_line_surface");
+    if (rc != KR_OK) return rc;
+    return on_device(n >= 0 && d_line && (n == 0 || d), "kr_post_line_surface: null argument or negative n",
+                     [&] { return post_line_surface_dev(s, spin, reverse, lo, hi, b, law, d, n, d_line, (hipStream_t) st); });
+}
+
+int kr_reduce_line_surface_dev_f64(const kr_disc_surface* s, const kr_line_bins* b, const void* d, int64_t n, void* d_line, void* st)
+{
+    int rc = surface_validate(s, "kr_reduce_line_surface");
+    if (rc == KR_OK) rc = line_validate(b, "kr_reduce_line_surface");
+    if (rc != KR_OK) return rc;
+    return on_device(n >= 0 && d_line && (n == 0 || d), "kr_reduce_line_surface: null argument or negative n",
+                     [&] { return reduce_line_surface_dev(b, d, n, d_line, (hipStream_t) st); });
+}
+
+int kr_post_spectrum_surface_dev_f64(const kr_disc_surface* s, double spin, int reverse, double lo, double hi, const kr_spectrum_model* m, const kr_limb_law* law, void* d,
+                                     int64_t n, void* d_out, void* st)
+{
+    int rc = surface_validate(s, "kr_post_spectrum_surface");
+    if (rc == KR_OK) rc = spectrum_validate(m, "kr_post_spectrum_surface");
+    if (rc == KR_OK) rc = limb_validate(law, "kr_post_spectrum_surface");
+    if (rc != KR_OK) return rc;
+    return on_device(n >= 0 && d_out && (n == 0 || d), "kr_post_spectrum_surface: null argument or negative n",
+                     [&] { return post_spectrum_surface_dev(s, spin, reverse, lo, hi, m, law, d, n, d_out, (hipStream_t) st); });
+}
+
+int kr_reduce_spectrum_surface_dev_f64(const kr_disc_surface* s, const kr_spectrum_model* m, const void* d, int64_t n, void* d_out, void* st)
+{
+    int rc = surface_validate(s, "kr_reduce_spectrum_surface");
+    if (rc == KR_OK) rc = spectrum_validate(m, "kr_reduce_spectrum_surface");
+    if (rc != KR_OK) return rc;
+    return on_device(n >= 0 && d_out && (n == 0 || d), "kr_reduce_spectrum_surface: null argument or negative n",
+                     [&] { return reduce_spectrum_surface_dev(m, d, n, d_out, (hipStream_t) st); });
+}
+
+int kr_reduce_spectrum_surface_f64(const kr_disc_surface* s, const kr_spectrum_model* m, const kr_ray_f64* rays, int64_t n, double* out)
+{
+    int rc = surface_validate(s, "kr_reduce_spectrum_surface");
+    if (rc == KR_OK) rc = spectrum_validate(m, "kr_reduce_spectrum_surface");
+    if (rc != KR_OK) return rc;
+    if (!out || n < 0 || (n > 0 && !rays)) return invalid("kr_reduce_spectrum_surface: null argument or negative n");
+    std::vector<double> h((size_t) m->ne + 4, 0.0);        // out is written only by a call that succeeds
+    const int rc2 = reduce_to_host(rays, n, h.size(), h.data(), [&](void* d, void* d_out) { return reduce_spectrum_surface_dev(m, d, n, d_out, nullptr); });
+    if (rc2 == KR_OK) std::memcpy(out, h.data(), h.size() * sizeof(double));
+    return rc2;
+}
+
+int kr_post_response_surface_dev_f64(const kr_disc_surface* s, double spin, int reverse, double lo, double hi, const kr_response_model* r, const kr_limb_law* law, void* d,
+                                     int64_t n, void* d_out, void* st)
+{
+    int rc = surface_validate(s, "kr_post_response_surface");
+    if (rc == KR_OK) rc = response_validate(r, "kr_post_response_surface");
+    if (rc == KR_OK) rc = limb_validate(law, "kr_post_response_surface");
+    if (rc != KR_OK) return rc;
+    return on_device(n >= 0 && d_out && (n == 0 || d), "kr_post_response_surface: null argument or negative n",
+                     [&] { return post_response_surface_dev(s, spin, reverse, lo, hi, r, law, d, n, d_out, (hipStream_t) st); });
+}
+
+int kr_reduce_response_surface_dev_f64(const kr_disc_surface* s, const kr_response_model* r, const void* d, int64_t n, void* d_out, void* st)
+{
+    int rc = surface_validate(s, "kr_reduce_response_surface");
+    if (rc == KR_OK) rc = response_validate(r, "kr_reduce_response_surface");
+    if (rc != KR_OK) return rc;
+    return on_device(n >= 0 && d_out && (n == 0 || d), "kr_reduce_response_surface: null argument or negative n",
+                     [&] { return reduce_response_surface_dev(r, d, n, d_out, (hipStream_t) st); });
+}
+
+int kr_reduce_response_surface_f64(const kr_disc_surface* s, const kr_response_model* r, const kr_ray_f64* rays, int64_t n, double* out)
+{
+    int rc = surface_validate(s, "kr_reduce_response_surface");
+    if (rc == KR_OK) rc = response_validate(r, "kr_reduce_response_surface");
+    if (rc != KR_OK) return rc;
+    if (!out || n < 0 || (n > 0 && !rays)) return invalid("kr_reduce_response_surface: null argument or negative n");
+    std::vector<double> h((size_t) r->nt * r->spec.ne + 4, 0.0);        // out is written only by a call that succeeds
+    const int rc2 = reduce_to_host(rays, n, h.size(), h.data(), [&](void* d, void* d_out) { return reduce_response_surface_dev(r, d, n, d_out, nullptr); });
+    if (rc2 == KR_OK) std::memcpy(out, h.data(), h.size() * sizeof(double));
+    return rc2;
+}
+
 // ---- orbiting hot spot (kr_hotspot.hip): everything is validated before anything touches a device ----
 int kr_post_hotspot_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_hotspot* h, const kr_limb_law* law, void* d,
                             int64_t n, void* d_out, void* st)

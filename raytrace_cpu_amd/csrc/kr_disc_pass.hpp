@@ -22,6 +22,55 @@ KR_DEV bool disc_filter(double r_isco, double r_disc, int steps, double r, doubl
     return z < 1E-2 && r >= r_isco && r < r_disc && g > 0;
 }
 
+// ---- the emission angle on a disc with a SURFACE |z| = H(rho) (include/kr_trace.h, kr_disc_surface; a compile-time parameter of the disc passes like
+//      DiscFlow (kr_post_device.hpp), so that every flat instance is the code it was).  DiscSurface<false> carries nothing; DiscSurface<true> what
+//      H'(rho) needs.  The frame is frame_value_coef's (kr_post_device.hpp) with V = -1 and projradius = 1 (the Keplerian observer at
+//      rho = r sin(theta)): frame_value expression for expression -- E keeps redshift_value's bits -- handing on the sine and cosine of theta and the
+//      two metric coefficients that put the gradient of sg z - H(rho) on the legs e3, e2.  The gas moves in phi only and the surface depends on
+//      neither t nor phi: the normal is orthogonal to the gas four-velocity and the boost leaves e2, e3 alone, so this is the proper normal in the
+//      gas frame. ----
+template <bool SURFACE> struct DiscSurface {};
+template <> struct DiscSurface<true> { double r_in, slope, scale; };
+
+// mu = |P_n| / E, the cosine to the surface normal, and P_s, the momentum along the surface away from the axis (chi = atan2(P_phi, P_s)); nn is the
+// length of the unnormalised normal.  One IEEE operation per line of the rule in include/kr_trace.h, in its association.
+struct SurfaceAngle { double mu, P_s, nn; };
+
+KR_DEV SurfaceAngle surface_angle(const DiscSurface<true>& sf, const Frame& f, const FrameCoef& mc, double r)
+{
+    const double sn = mc.sn, cs = mc.cs;
+    const double rho = r * sn, z = r * cs;
+    const double sg = z < 0 ? -1.0 : 1.0;
+    const double Hp = sf.slope + (sf.scale * 0.5 * kr_sqrt(sf.r_in / rho)) / rho;
+    const double f_r = sg * cs - Hp * sn;
+    const double f_th = -1 * (sg * (r * sn)) - Hp * (r * cs);
+    const double n_r = kr_sqrt(mc.delta / mc.rhosq) * f_r;
+    const double n_th = f_th / kr_sqrt(mc.rhosq);
+    SurfaceAngle s;
+    s.nn = kr_sqrt(n_r * n_r + n_th * n_th);
+    const double P_n = (n_r * f.P_r + n_th * f.P_th) / s.nn;
+    s.mu = kr_abs(P_n) / f.E;
+    s.P_s = sg * (n_r * f.P_th - n_th * f.P_r) / s.nn;
+    return s;
+}
+
+KR_DEV bool surface_bad_angle(const Frame& f, const SurfaceAngle& s) { return frame_bad_angle(f, s.mu) || !__builtin_isfinite(s.nn) || s.nn == 0; }
+
+// what H'(rho) needs of a kr_disc_surface that surface_validate has passed (host side)
+inline DiscSurface<true> surface_dev(const kr_disc_surface* s)
+{
+    DiscSurface<true> sf;
+    sf.r_in = s->r_in; sf.slope = s->slope; sf.scale = s->scale;
+    return sf;
+}
+
+// the filter of a record that LANDED ON A SURFACE (image_surface_kernel, kr_surface.hip): traced, stopped by the destination, with a redshift, and its
+// cylindrical radius rho = r sin(theta) between r_isco and r_disc (a NaN in rho or g fails)
+KR_DEV bool disc_filter_surface(double r_isco, double r_disc, int steps, int status, double rho, double g)
+{
+    return steps > 0 && (status & KR_STATUS_DEST) != 0 && g > 0 && rho >= r_isco && rho < r_disc;
+}
+
 // what the front end hands to a pass's own *_item: the end point, the redshift, the wrapped phi and the limb weight (1 where no law applies)
 struct DiscRay { double r, theta, g, phi, limb; };
 
@@ -32,14 +81,50 @@ struct DiscRay { double r, theta, g, phi, limb; };
 // every other ray; under the other laws -- whose weight it would poison -- it is dropped.  Returns false for a dropped ray.
 // (One drop flag and one assignment of the outputs at the end, not early returns: those cost the fused kernels two VGPRs.)
 // PLUNGE: the disc flow of KR_V_PLUNGE (DiscFlow, kr_post_device.hpp) in the fused form with motion 0; DiscFlow<false> is today's code.
-template <bool FUSED, bool PLUNGE, class Ray>
+// SURFACE: the record landed on the surface of kr_disc_surface (DiscSurface, kr_post_device.hpp).  The observer is V = -1 at rho with motion 0 whatever
+// V, projradius and motion say, the filter is disc_filter_surface, mu is the cosine to the surface normal, and out->r is rho: every radius that a pass's
+// item takes is the cylindrical one.  DiscSurface<false> is today's code.
+template <bool FUSED, bool PLUNGE, bool SURFACE = false, class Ray>
 KR_DEV bool disc_ray(Ray* ray, double r_isco, double r_disc, double spin, double V, int reverse, int projradius, int motion, double lo, double hi,
-                     const kr_limb_law& law, DiscRay* out, unsigned long long& on_disc, unsigned long long& bad_angle, const DiscFlow<PLUNGE>& fl)
+                     const kr_limb_law& law, DiscRay* out, unsigned long long& on_disc, unsigned long long& bad_angle, const DiscFlow<PLUNGE>& fl,
+                     const DiscSurface<SURFACE>& sf = DiscSurface<SURFACE>{})
 {
+    static_assert(!(SURFACE && PLUNGE), "the surface passes keep the Keplerian observer at rho");
     double r, theta, g, phi, limb = 1;
     const int steps = ray->steps;
     bool drop = false;
-    if constexpr (FUSED) {
+    if constexpr (SURFACE) {
+        double rho;
+        [[maybe_unused]] Frame f;
+        [[maybe_unused]] FrameCoef mc;
+        if constexpr (FUSED) {
+            const kr_ray_f64 v = geodesic_of(ray);
+            theta = v.theta;
+            f = frame_value_coef(v, spin, -1.0, reverse, 1, &mc);
+            g = frame_redshift(f, v.emit, reverse);
+            ray->redshift = g;
+            phi = wrap_phi(ray, steps, lo, hi);
+            r = v.r;
+            rho = r * mc.sn;
+        } else {
+            r = ray->r; theta = ray->theta; g = ray->redshift; phi = ray->phi;
+            rho = r * kr_sin(theta);
+        }
+        if (disc_filter_surface(r_isco, r_disc, steps, ray->status, rho, g)) {
+            on_disc++;
+            if constexpr (FUSED) {
+                const SurfaceAngle s = surface_angle(sf, f, mc, r);
+                if (surface_bad_angle(f, s)) {
+                    bad_angle++;
+                    drop = law.law != 0;
+                }
+                limb = limb_weight(law.law, law.coeff, s.mu);
+            }
+        } else {
+            drop = true;
+        }
+        r = rho;
+    } else if constexpr (FUSED) {
         const kr_ray_f64 v = geodesic_of(ray);
         r = v.r; theta = v.theta;
         if (motion == 0) {

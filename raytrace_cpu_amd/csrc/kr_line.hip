@@ -108,21 +108,30 @@ KR_DEV void line_end(double* lds, double* out, int words, unsigned long long on_
     }
 }
 
-template <bool USE_LDS>
+// SURFACE: the records landed on a surface (disc_filter_surface, kr_disc_pass.hpp), the radius is rho, and the layout is the limb line's with a
+// bad_angle word that stays 0 (the records carry no emission angle)
+template <bool USE_LDS, bool SURFACE = false>
 __global__ void __launch_bounds__(kBlock)
 reduce_line_kernel(const kr_ray_f64* __restrict__ rays, long long n, LineDev L, double* __restrict__ out)
 {
     extern __shared__ double lds[];
-    double* acc = line_begin<USE_LDS>(lds, out, L.words);
+    const int words = SURFACE ? L.words + 1 : L.words;
+    double* acc = line_begin<USE_LDS>(lds, out, words);
     unsigned long long on_disc = 0, binned = 0;
     KR_GRID_STRIDE(i, n) {
         const kr_ray_f64* ray = &rays[i];
-        const double r = ray->r, g = ray->redshift;
-        if (!disc_filter(L.b.r_isco, L.b.r_disc, ray->steps, r, ray->theta, g)) continue;
+        const double g = ray->redshift;
+        double r = ray->r;
+        if constexpr (SURFACE) {
+            r = r * kr_sin(ray->theta);
+            if (!disc_filter_surface(L.b.r_isco, L.b.r_disc, ray->steps, ray->status, r, g)) continue;
+        } else {
+            if (!disc_filter(L.b.r_isco, L.b.r_disc, ray->steps, r, ray->theta, g)) continue;
+        }
         on_disc++;
         binned += line_accumulate<false>(acc, L, r, g, ray->t);
     }
-    line_end<USE_LDS>(lds, out, L.words, on_disc, binned);
+    line_end<USE_LDS, SURFACE>(lds, out, words, on_disc, binned);
 }
 
 // redshift(V, reverse, projradius, motion) + range_phi(lo, hi) + the line bins: the per-ray code of post_image_kernel (kr_post.hip) with the
@@ -152,10 +161,11 @@ post_line_kernel(kr_ray_f64* __restrict__ rays, long long n, double spin, double
 
 // post_line_kernel with w *= limb(mu): disc_ray (kr_disc_pass.hpp) in its fused form for the orbiting observer, so rays[] ends as after
 // post_line_kernel and a bad-angle ray is counted and binned by that function's rule.  Layout: post_line_kernel's, then bad_angle.
-template <bool USE_LDS, bool PLUNGE>
+// SURFACE: the line of a disc with a surface (DiscSurface, kr_post_device.hpp): the filter, the radius and the angle of disc_ray's surface flavour
+template <bool USE_LDS, bool PLUNGE, bool SURFACE = false>
 __global__ void __launch_bounds__(kBlock)
 post_line_limb_kernel(kr_ray_f64* __restrict__ rays, long long n, double spin, double V, int reverse, int projradius, double lo, double hi, LineDev L,
-                      kr_limb_law law, double* __restrict__ out, DiscFlow<PLUNGE> fl)
+                      kr_limb_law law, double* __restrict__ out, DiscFlow<PLUNGE> fl, DiscSurface<SURFACE> sf)
 {
     extern __shared__ double lds[];
     const int words = L.words + 1;
@@ -164,7 +174,7 @@ post_line_limb_kernel(kr_ray_f64* __restrict__ rays, long long n, double spin, d
     KR_GRID_STRIDE(i, n) {
         kr_ray_f64* ray = &rays[i];
         DiscRay d;
-        if (!disc_ray<true, PLUNGE>(ray, L.b.r_isco, L.b.r_disc, spin, V, reverse, projradius, 0, lo, hi, law, &d, on_disc, bad_angle, fl)) continue;
+        if (!disc_ray<true, PLUNGE, SURFACE>(ray, L.b.r_isco, L.b.r_disc, spin, V, reverse, projradius, 0, lo, hi, law, &d, on_disc, bad_angle, fl, sf)) continue;
         binned += line_accumulate<false, true>(acc, L, d.r, d.g, ray->t, d.limb);
     }
     line_end<USE_LDS, true>(lds, out, words, on_disc, binned, bad_angle);
@@ -303,8 +313,54 @@ int post_line_limb_dev(double spin, double V, int reverse, int projradius, doubl
     LineDev L;
     int rc = line_dev(b, pins, &L);
     if (rc != KR_OK) return rc;
-    KR_LAUNCH_LDS_OR_GLOBAL_FLOW(post_line_limb_kernel, spin, V, reverse, L.words + 1 <= kLineLdsWords, grid_for(n, kBlock, kCapHist), (L.words + 1) * sizeof(double), st,
-                                 (kr_ray_f64*) d, (long long) n, spin, V, reverse, projradius, lo, hi, L, *law, (double*) d_line);
+    const int grid = grid_for(n, kBlock, kCapHist);
+    for_flow(spin, V, reverse, [&](auto flow) {
+        constexpr bool P = decltype(flow)::plunge;
+        if (L.words + 1 <= kLineLdsWords)
+            hipLaunchKernelGGL((post_line_limb_kernel<true, P>), dim3(grid), dim3(kBlock), (L.words + 1) * sizeof(double), st, (kr_ray_f64*) d, (long long) n, spin, V, reverse,
+                               projradius, lo, hi, L, *law, (double*) d_line, flow.arg, DiscSurface<false>{});
+        else
+            hipLaunchKernelGGL((post_line_limb_kernel<false, P>), dim3(grid), dim3(kBlock), 0, st, (kr_ray_f64*) d, (long long) n, spin, V, reverse, projradius, lo, hi, L, *law,
+                               (double*) d_line, flow.arg, DiscSurface<false>{});
+    });
+    KR_LAUNCH_CHECK();
+    return KR_OK;
+}
+
+// the surface forms (kr_post_line_surface_dev_f64, kr_reduce_line_surface_dev_f64): the Keplerian observer at rho, whatever the flat form's V would say
+int post_line_surface_dev(const kr_disc_surface* s, double spin, int reverse, double lo, double hi, const kr_line_bins* b, const kr_limb_law* law, void* d, int64_t n,
+                          void* d_line, hipStream_t st)
+{
+    if (n <= 0) return KR_OK;
+    TablePins pins;
+    LineDev L;
+    int rc = line_dev(b, pins, &L);
+    if (rc != KR_OK) return rc;
+    const int grid = grid_for(n, kBlock, kCapHist);
+    const DiscSurface<true> sf = surface_dev(s);
+    if (L.words + 1 <= kLineLdsWords)
+        hipLaunchKernelGGL((post_line_limb_kernel<true, false, true>), dim3(grid), dim3(kBlock), (L.words + 1) * sizeof(double), st, (kr_ray_f64*) d, (long long) n, spin, -1.0,
+                           reverse, 1, lo, hi, L, *law, (double*) d_line, DiscFlow<false>{}, sf);
+    else
+        hipLaunchKernelGGL((post_line_limb_kernel<false, false, true>), dim3(grid), dim3(kBlock), 0, st, (kr_ray_f64*) d, (long long) n, spin, -1.0, reverse, 1, lo, hi, L, *law,
+                           (double*) d_line, DiscFlow<false>{}, sf);
+    KR_LAUNCH_CHECK();
+    return KR_OK;
+}
+
+int reduce_line_surface_dev(const kr_line_bins* b, const void* d, int64_t n, void* d_line, hipStream_t st)
+{
+    if (n <= 0) return KR_OK;
+    TablePins pins;
+    LineDev L;
+    int rc = line_dev(b, pins, &L);
+    if (rc != KR_OK) return rc;
+    const int grid = grid_for(n, kBlock, kCapHist);
+    if (L.words + 1 <= kLineLdsWords)
+        hipLaunchKernelGGL((reduce_line_kernel<true, true>), dim3(grid), dim3(kBlock), (L.words + 1) * sizeof(double), st, (const kr_ray_f64*) d, (long long) n, L, (double*) d_line);
+    else
+        hipLaunchKernelGGL((reduce_line_kernel<false, true>), dim3(grid), dim3(kBlock), 0, st, (const kr_ray_f64*) d, (long long) n, L, (double*) d_line);
+    KR_LAUNCH_CHECK();
     return KR_OK;
 }
 

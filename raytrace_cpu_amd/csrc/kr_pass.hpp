@@ -160,6 +160,19 @@ int reduce_emissivity_surface_dev(const kr_emis_bins* b, const void* d, int64_t 
 int post_emissivity_surface_dev(double spin, int reverse, double lo, double hi, const kr_emis_bins* b, void* d, int64_t n, void* d_hist, hipStream_t st);
 int reduce_image_surface_dev(const kr_image_bins* b, const void* d, int64_t n, void* d_planes, hipStream_t st);
 int post_image_surface_dev(double spin, int reverse, double lo, double hi, const kr_image_bins* b, void* d, int64_t n, void* d_planes, hipStream_t st);
+// the line, the continuum and the response of rays that landed on the surface of a kr_disc_surface (kr_line.hip, kr_spectrum.hip, kr_response.hip;
+// the per-record angles: kr_angles.hip).  surface_validate (kr_surface.hip) refuses a null surface and what KR_STOP_THICKDISC refuses of its stop_params
+int surface_validate(const kr_disc_surface* s, const char* who);
+int angles_surface_dev(const kr_disc_surface* s, double spin, int reverse, const void* d, int64_t n, void* d_angles, hipStream_t st);
+int post_line_surface_dev(const kr_disc_surface* s, double spin, int reverse, double lo, double hi, const kr_line_bins* b, const kr_limb_law* law, void* d, int64_t n,
+                          void* d_line, hipStream_t st);
+int reduce_line_surface_dev(const kr_line_bins* b, const void* d, int64_t n, void* d_line, hipStream_t st);
+int post_spectrum_surface_dev(const kr_disc_surface* s, double spin, int reverse, double lo, double hi, const kr_spectrum_model* m, const kr_limb_law* law, void* d,
+                              int64_t n, void* d_out, hipStream_t st);
+int reduce_spectrum_surface_dev(const kr_spectrum_model* m, const void* d, int64_t n, void* d_out, hipStream_t st);
+int post_response_surface_dev(const kr_disc_surface* s, double spin, int reverse, double lo, double hi, const kr_response_model* r, const kr_limb_law* law, void* d,
+                              int64_t n, void* d_out, hipStream_t st);
+int reduce_response_surface_dev(const kr_response_model* r, const void* d, int64_t n, void* d_out, hipStream_t st);
 // kr_return_map.hip: the landing map of the returning radiation (kr_return_map); the validator refuses a null map and nr <= 0
 int return_map_validate(const kr_return_map* m, const char* who);
 int reduce_return_map_dev(const kr_return_map* m, const void* d, int64_t n, void* d_out, hipStream_t st);

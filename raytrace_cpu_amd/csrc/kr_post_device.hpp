@@ -271,6 +271,39 @@ KR_DEV double limb_weight(int law, double coeff, double mu)
     return 1;
 }
 
+// ---- frame_value with the sine and cosine of theta and the two metric coefficients that the normal of a disc SURFACE needs (DiscSurface,
+//      kr_disc_pass.hpp), from the one metric evaluation: expression for expression frame_value, so E keeps redshift_value's bits ----
+struct FrameCoef { double sn, cs, delta, rhosq; };
+
+KR_DEV Frame frame_value_coef(const kr_ray_f64& ray, double spin, double V_in, int reverse, int projradius, FrameCoef* mc)
+{
+    using T = double;
+    const T a = reverse ? -1 * spin : spin;
+    const T r = ray.r, theta = ray.theta;
+    const Metric<T> m = kerr_metric<T>(r, theta, a);
+    kr_sincos(theta, mc->sn, mc->cs);            // (kerr_metric's own pair: one evaluation after inlining)
+    mc->delta = m.delta;
+    mc->rhosq = m.rhosq;
+    T V = V_in;
+    if (V == -1) V = keplerian_V<T>(a, r, theta, projradius != 0);
+    const T et[4] = {(1 / kr_sqrt(m.e2nu)) / kr_sqrt(1 - (V - m.omega) * (V - m.omega) * m.e2psi / m.e2nu), 0, 0,
+                     (1 / kr_sqrt(m.e2nu)) * V / kr_sqrt(1 - (V - m.omega) * (V - m.omega) * m.e2psi / m.e2nu)};
+    const T e1[4] = {(V - m.omega) * kr_sqrt(m.e2psi / m.e2nu) / kr_sqrt(m.e2nu - (V - m.omega) * (V - m.omega) * m.e2psi), 0, 0,
+                     (1 / kr_sqrt(m.e2nu * m.e2psi)) * (m.e2nu + V * m.omega * m.e2psi - m.omega * m.omega * m.e2psi) /
+                         kr_sqrt(m.e2nu - (V - m.omega) * (V - m.omega) * m.e2psi)};
+    const T e2[4] = {0, 0, 1 / kr_sqrt(m.rhosq), 0};
+    const T e3[4] = {0, kr_sqrt(m.delta / m.rhosq), 0, 0};
+    T p[4];
+    momentum<T>(p[0], p[1], p[2], p[3], ray.k, ray.h, ray.Q, ray.rdot_sign, ray.thetadot_sign, r, theta, spin);
+    if (reverse) { p[1] *= -1; p[2] *= -1; p[3] *= -1; }
+    Frame f;
+    f.E = energy_dot<T>(m, et, p);
+    f.P_phi = -1 * energy_dot<T>(m, e1, p);
+    f.P_th = -1 * energy_dot<T>(m, e2, p);
+    f.P_r = -1 * energy_dot<T>(m, e3, p);
+    return f;
+}
+
 // ---- the polarisation of disc emission carried to a distant image plane (include/kr_trace.h, kr_polarisation_dev_f64).  The frame is frame_value's,
 //      expression for expression -- E and mu keep its bits, so `redshift` is redshift_value's return value -- and the legs e1, e3 and the momentum p it
 //      is built from go on into the emitted polarisation vector f = (P_phi e3 - P_r e1) / nrm and the Walker-Penrose constant

@@ -84,11 +84,13 @@ KR_DEV bool response_item(const SpecDev& D, const RespDev& R, double r, double g
 }
 
 // PLUNGE: the disc flow of KR_V_PLUNGE (DiscFlow, kr_post_device.hpp), fused form only; the host picks the instance from V
-template <int MODEL, bool FUSED, int SLOTS, bool PLUNGE>
+// SURFACE: the response of a disc with a surface (DiscSurface, kr_post_device.hpp): the filter, the radius and the angle of disc_ray's surface flavour
+template <int MODEL, bool FUSED, int SLOTS, bool PLUNGE, bool SURFACE = false>
 __global__ void __launch_bounds__(kBlock)
 response_kernel(typename std::conditional<FUSED, kr_ray_f64, const kr_ray_f64>::type* __restrict__ rays, long long n, double spin, double V, int reverse,
-                int projradius, int motion, double lo, double hi, SpecDev D, RespDev R, kr_limb_law law, double* __restrict__ out, DiscFlow<PLUNGE> fl)
+                int projradius, int motion, double lo, double hi, SpecDev D, RespDev R, kr_limb_law law, double* __restrict__ out, DiscFlow<PLUNGE> fl, DiscSurface<SURFACE> sf)
 {
+    static_assert(!(SURFACE && PLUNGE), "the surface passes keep the Keplerian observer at rho");
     extern __shared__ double lds_s[];                    // MODEL 1: the table
     __shared__ double it_a[kBlock], it_b[kBlock], it_c[kBlock];
     __shared__ int it_z[kBlock], it_j[kBlock];
@@ -139,7 +141,7 @@ response_kernel(typename std::conditional<FUSED, kr_ray_f64, const kr_ray_f64>::
         if (i < n) {
             DiscRay d;
             double ft = 0;
-            if (disc_ray<FUSED, PLUNGE>(&rays[i], m.r_isco, m.r_disc, spin, V, reverse, projradius, motion, lo, hi, law, &d, on_disc, bad_angle, fl))
+            if (disc_ray<FUSED, PLUNGE, SURFACE>(&rays[i], m.r_isco, m.r_disc, spin, V, reverse, projradius, motion, lo, hi, law, &d, on_disc, bad_angle, fl, sf))
                 live = response_item(D, R, d.r, d.g, rays[i].t, d.limb, &a, &b, &c, &zone, &ft);
             if (live) {
                 used++;
@@ -204,9 +206,9 @@ response_kernel(typename std::conditional<FUSED, kr_ray_f64, const kr_ray_f64>::
     }
 }
 
-template <bool FUSED, typename Rays>
+template <bool FUSED, bool SURFACE = false, typename Rays>
 int response_launch(const kr_response_model* r, const kr_limb_law& law, Rays* d, int64_t n, double spin, double V, int reverse, int projradius, int motion, double lo,
-                    double hi, void* d_out, hipStream_t st)
+                    double hi, void* d_out, hipStream_t st, DiscSurface<SURFACE> sf = DiscSurface<SURFACE>{})
 {
     if (n <= 0) return KR_OK;
     const kr_spectrum_model* m = &r->spec;
@@ -233,14 +235,14 @@ int response_launch(const kr_response_model* r, const kr_limb_law& law, Rays* d,
                 if constexpr (K.value <= kLaunchSlots) {
                     auto launch = [&](auto kernel, size_t lds) {
                         hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, st, d, (long long) n, spin, V, reverse, projradius, motion, lo, hi, D, R, law, (double*) d_out,
-                                           flow.arg);
+                                           flow.arg, sf);
                     };
-                    if (in_lds) launch(response_kernel<1, FUSED, K.value, P>, (size_t) m->nz * m->s_ne * sizeof(double));
-                    else launch(response_kernel<2, FUSED, K.value, P>, 0);
+                    if (in_lds) launch(response_kernel<1, FUSED, K.value, P, SURFACE>, (size_t) m->nz * m->s_ne * sizeof(double));
+                    else launch(response_kernel<2, FUSED, K.value, P, SURFACE>, 0);
                 }
             });
         };
-        if constexpr (FUSED) for_flow(spin, V, reverse, with_flow);
+        if constexpr (FUSED && !SURFACE) for_flow(spin, V, reverse, with_flow);
         else with_flow(FlowChoice<false>{});
         KR_LAUNCH_CHECK();
     }
@@ -277,6 +279,20 @@ int post_response_dev(double spin, double V, int reverse, int projradius, int mo
 int reduce_response_dev(const kr_response_model* r, const void* d, int64_t n, void* d_out, hipStream_t st)
 {
     return response_launch<false>(r, isotropic_limb(), (const kr_ray_f64*) d, n, 0.0, 0.0, 0, 0, 0, 0.0, 0.0, d_out, st);
+}
+
+// the surface forms (kr_post_response_surface_dev_f64, kr_reduce_response_surface_dev_f64): the Keplerian observer at rho
+int post_response_surface_dev(const kr_disc_surface* s, double spin, int reverse, double lo, double hi, const kr_response_model* r, const kr_limb_law* law, void* d,
+                              int64_t n, void* d_out, hipStream_t st)
+{
+    return response_launch<true, true>(r, *law, (kr_ray_f64*) d, n, spin, -1.0, reverse, 1, 0, lo, hi, d_out, st, surface_dev(s));
+}
+
+int reduce_response_surface_dev(const kr_response_model* r, const void* d, int64_t n, void* d_out, hipStream_t st)
+{
+    DiscSurface<true> none;
+    none.r_in = none.slope = none.scale = 0;             // (the reduce form reads no angle)
+    return response_launch<false, true>(r, isotropic_limb(), (const kr_ray_f64*) d, n, 0.0, 0.0, 0, 0, 0, 0.0, 0.0, d_out, st, none);
 }
 
 }  // namespace kr

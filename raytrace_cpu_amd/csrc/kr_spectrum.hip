@@ -71,13 +71,16 @@ constexpr int stokes_wave_bound(bool stokes, int model, bool fused, int slots)
 }
 
 // PLUNGE: the disc flow of KR_V_PLUNGE (DiscFlow, kr_post_device.hpp), fused form only; the host picks the instance from V (never with STOKES)
-template <int MODEL, bool FUSED, int SLOTS, bool PLUNGE, bool STOKES>
+// SURFACE: the continuum of a disc with a surface (DiscSurface, kr_post_device.hpp): the filter, the radius and the angle of disc_ray's surface flavour,
+// in both forms (never with PLUNGE or STOKES)
+template <int MODEL, bool FUSED, int SLOTS, bool PLUNGE, bool STOKES, bool SURFACE = false>
 __global__ void __launch_bounds__(kBlock, stokes_wave_bound(STOKES, MODEL, FUSED, SLOTS))
 spectrum_kernel(typename std::conditional<FUSED, kr_ray_f64, const kr_ray_f64>::type* __restrict__ rays, long long n, double spin, double V, int reverse,
                 int projradius, int motion, double lo, double hi, SpecDev D, kr_limb_law law, double* __restrict__ out, DiscFlow<PLUNGE> fl,
-                typename std::conditional<STOKES, StokesDev, NoStokes>::type P)
+                typename std::conditional<STOKES, StokesDev, NoStokes>::type P, DiscSurface<SURFACE> sf)
 {
     static_assert(!(STOKES && PLUNGE), "polar_value has no plunging form");
+    static_assert(!(SURFACE && (PLUNGE || STOKES)), "the surface passes keep the Keplerian observer at rho and carry no polarisation");
     constexpr bool THERMAL = MODEL == 0;
     extern __shared__ double lds_s[];                    // MODEL 1: the table
     __shared__ double it_a[kBlock], it_b[kBlock], it_c[kBlock];
@@ -158,7 +161,7 @@ spectrum_kernel(typename std::conditional<FUSED, kr_ray_f64, const kr_ray_f64>::
             }
         } else if (i < n) {
             DiscRay d;
-            if (disc_ray<FUSED, PLUNGE>(&rays[i], m.r_isco, m.r_disc, spin, V, reverse, projradius, motion, lo, hi, law, &d, on_disc, bad_angle, fl))
+            if (disc_ray<FUSED, PLUNGE, SURFACE>(&rays[i], m.r_isco, m.r_disc, spin, V, reverse, projradius, motion, lo, hi, law, &d, on_disc, bad_angle, fl, sf))
                 live = spectrum_item<THERMAL>(D, d.r, d.g, d.limb, &a, &b, &c, &zone);
             if (live) used++;
         }
@@ -263,9 +266,9 @@ bool spectrum_table_in_lds(const kr_spectrum_model* m)
 
 namespace {
 
-template <bool FUSED, bool STOKES, typename Rays, typename Extra>
+template <bool FUSED, bool STOKES, bool SURFACE = false, typename Rays, typename Extra>
 int spectrum_launch(const kr_spectrum_model* m, const kr_limb_law& law, Rays* d, int64_t n, double spin, double V, int reverse, int projradius, int motion, double lo,
-                    double hi, void* d_out, hipStream_t st, Extra extra)
+                    double hi, void* d_out, hipStream_t st, Extra extra, DiscSurface<SURFACE> sf = DiscSurface<SURFACE>{})
 {
     if (n <= 0) return KR_OK;
     TablePins pins;
@@ -278,15 +281,15 @@ int spectrum_launch(const kr_spectrum_model* m, const kr_limb_law& law, Rays* d,
         constexpr bool P = decltype(flow)::plunge;
         for_slots(slots, [&](auto K) {
             auto launch = [&](auto kernel, size_t lds) {
-                hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, st, d, (long long) n, spin, V, reverse, projradius, motion, lo, hi, D, law, (double*) d_out, flow.arg, extra);
+                hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, st, d, (long long) n, spin, V, reverse, projradius, motion, lo, hi, D, law, (double*) d_out, flow.arg, extra, sf);
             };
-            if (m->model == 0) launch(spectrum_kernel<0, FUSED, K.value, P, STOKES>, 0);
-            else if (s_words <= kSpecLdsWords) launch(spectrum_kernel<1, FUSED, K.value, P, STOKES>, (size_t) s_words * sizeof(double));
-            else launch(spectrum_kernel<2, FUSED, K.value, P, STOKES>, 0);
+            if (m->model == 0) launch(spectrum_kernel<0, FUSED, K.value, P, STOKES, SURFACE>, 0);
+            else if (s_words <= kSpecLdsWords) launch(spectrum_kernel<1, FUSED, K.value, P, STOKES, SURFACE>, (size_t) s_words * sizeof(double));
+            else launch(spectrum_kernel<2, FUSED, K.value, P, STOKES, SURFACE>, 0);
         });
     };
-    if constexpr (FUSED && !STOKES) for_flow(spin, V, reverse, with_flow);
-    else with_flow(FlowChoice<false>{});               // (the Stokes forms: KR_V_PLUNGE is refused before this)
+    if constexpr (FUSED && !STOKES && !SURFACE) for_flow(spin, V, reverse, with_flow);
+    else with_flow(FlowChoice<false>{});               // (the Stokes forms: KR_V_PLUNGE is refused before this; the surface forms have no V)
     KR_LAUNCH_CHECK();
     return KR_OK;
 }
@@ -339,6 +342,20 @@ int post_spectrum_dev(double spin, double V, int reverse, int projradius, int mo
 int reduce_spectrum_dev(const kr_spectrum_model* m, const void* d, int64_t n, void* d_out, hipStream_t st)
 {
     return spectrum_launch<false, false>(m, isotropic_limb(), (const kr_ray_f64*) d, n, 0.0, 0.0, 0, 0, 0, 0.0, 0.0, d_out, st, NoStokes{});
+}
+
+// the surface forms (kr_post_spectrum_surface_dev_f64, kr_reduce_spectrum_surface_dev_f64): the Keplerian observer at rho
+int post_spectrum_surface_dev(const kr_disc_surface* s, double spin, int reverse, double lo, double hi, const kr_spectrum_model* m, const kr_limb_law* law, void* d,
+                              int64_t n, void* d_out, hipStream_t st)
+{
+    return spectrum_launch<true, false, true>(m, *law, (kr_ray_f64*) d, n, spin, -1.0, reverse, 1, 0, lo, hi, d_out, st, NoStokes{}, surface_dev(s));
+}
+
+int reduce_spectrum_surface_dev(const kr_spectrum_model* m, const void* d, int64_t n, void* d_out, hipStream_t st)
+{
+    DiscSurface<true> none;
+    none.r_in = none.slope = none.scale = 0;             // (the reduce form reads no angle)
+    return spectrum_launch<false, false, true>(m, isotropic_limb(), (const kr_ray_f64*) d, n, 0.0, 0.0, 0, 0, 0, 0.0, 0.0, d_out, st, NoStokes{}, none);
 }
 
 // the Stokes forms (kr_post_spectrum_stokes_dev_f64, kr_reduce_spectrum_stokes_dev_f64): motion is 0, the validators refuse the rest

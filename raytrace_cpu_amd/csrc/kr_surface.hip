@@ -10,6 +10,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <string>
 
 #include "kr_pass.hpp"
@@ -170,6 +171,19 @@ int image_surface_launch(const char* who, double spin, int reverse, double lo, d
 }
 
 }  // namespace
+
+// the surface of the line, continuum and response passes: validate_run's rules for the stop_params of KR_STOP_THICKDISC (kr_trace.hip), word for word
+int surface_validate(const kr_disc_surface* s, const char* who)
+{
+    const char* what = nullptr;
+    if (!s) what = "null surface";
+    else if (!std::isfinite(s->r_in) || !(s->r_in > 0)) what = "surface: r_in must be positive and finite";
+    else if (!std::isfinite(s->r_out)) what = "surface: r_out must be finite (<= 0: open)";
+    else if (!std::isfinite(s->slope) || s->slope < 0) what = "surface: slope must be non-negative and finite";
+    else if (!std::isfinite(s->scale) || s->scale < 0) what = "surface: scale must be non-negative and finite";
+    if (what) set_error(std::string(who) + ": " + what);
+    return what ? KR_EINVAL : KR_OK;
+}
 
 int reduce_emissivity_surface_dev(const kr_emis_bins* b, const void* d, int64_t n, void* d_hist, hipStream_t st)
 {
