@@ -869,6 +869,67 @@ typedef struct kr_observer_spec {
 static_assert(sizeof(kr_observer_spec) == 120, "kr_observer_spec is 120 bytes (raytrace_cpu_amd/capi.py ObserverSpec)");
 #endif
 
+/* The illumination map of the disc: the emissivity histogram of kr_emis_bins with the AZIMUTH of the landing point kept -- what a source that is
+ * not on the axis (any kr_pointsource position, a kr_pointsource_vel_spec blob, a moving kr_healpix_source) does to the disc: the near side lit
+ * first, brightest and most blueshifted, the far side behind the hole.  Per ray record (in the kr_post_ form after range_phi and redshift(V,
+ * reverse, projradius, motion), phi as stored back):
+ *   filter   that of kr_emis_bins: steps > 0, z = r cos(theta) < 1e-2, g > 0 with g = rays[].redshift, r >= rad.r_isco.  A ray that passes counts
+ *            in disc_count, binned or not.
+ *   radius   q = log(r / rad.r_min) / log(rad.dr) (rad.logbin) or (r - rad.r_min) / rad.dr; the ray goes on iff -1 < q < rad.nr, at ir = (int) q --
+ *            the quotient and index rule of kr_emis_bins, the test made on q itself (a NaN fails; the band -1 < q <= 0 belongs to ir = 0).
+ *   azimuth  nphi == 1: no phi test, ip = 0 (a NaN phi IS binned: the map is then the emissivity histogram).  Otherwise
+ *              p = phi + phi_shift;   phi_w = p - 2 M_PI floor((p + M_PI) / (2 M_PI));   q_ph = (phi_w + M_PI) / dphi
+ *            with dphi = 2 M_PI / nphi rounded once on the host (the wrap of kr_volume_map); the ray is binned iff q_ph >= 0 (a NaN or an
+ *            infinite phi fails), at ip = min((int) q_ph, nphi - 1).  The wrap is floating arithmetic: a p one ulp below -M_PI wraps to just
+ *            below M_PI, where q_ph rounds to nphi itself -- the last cell, hence the min; a p one ulp below M_PI has p + M_PI round up to 2 M_PI
+ *            and wraps to one ulp below -M_PI, q_ph < 0: such a record is in no cell (it shows in disc_count - binned).
+ *   binned   at cell c = ir nphi + ip, the per-ray terms of the emissivity histogram:
+ *              count[c] += 1;  flux[c] += 1 / (rad.num_primary_rays g);  emis[c] += g^-rad.gamma;  sum_redshift[c] += g;  sum_time[c] += t;
+ *            binned += 1.
+ * Output: double[5 ncell + 2] with ncell = nr nphi = [count | flux | emis | sum_redshift | sum_time] (ncell each, [ir nphi + ip]), disc_count, binned;
+ * counts are doubles.  ADDED into (zero it once; shards and several calls sum).  Summed over ip the five planes are those of
+ * kr_reduce_emissivity_dev_f64 less the rays whose azimuth failed (disc_count - binned counts those and the rays outside the radial range).
+ * phi_shift turns the map against the records: the metric is axisymmetric, so the trace of a source at phi_s = 0 serves a source at phi_s = delta
+ * with phi_shift = +delta here (and -delta in a table that is applied to disc records).
+ * Refused (KR_EINVAL, before a device is touched): a null pointer, n < 0, nr < 1, nphi < 1, nr nphi > 2^20, a non-finite phi_shift, V = KR_V_PLUNGE
+ * (the kr_post_ form).  Out of scope: the plunging flow, records that ended on a surface (kr_reduce_emissivity_surface_dev_f64), f32 records, and
+ * the passes other than the line and the response (kr_illum_table below) that could read such a map as a table. */
+typedef struct kr_illum_bins {
+    kr_emis_bins rad;        /* filter, radial edges, gamma, num_primary_rays: exactly the emissivity histogram's */
+    double phi_shift;        /* added to the record's phi before the wrap */
+    int32_t nphi, pad;       /* azimuthal cells of 2 pi / nphi from phi = -pi */
+} kr_illum_bins;
+#ifdef __cplusplus
+static_assert(sizeof(kr_illum_bins) == 72, "kr_illum_bins is 72 bytes (raytrace_cpu_amd/capi.py IllumBins)");
+#endif
+
+/* An illumination map as an (r, phi) TABLE of the line and of the response: the emissivity and the source -> disc delay that a source which is not on
+ * the axis gives every cell of the disc, read by the passes over the DISC records of an image plane (kr_post_line_illum_dev_f64 and the five entry
+ * points beside it).  Everything is as the flat twin of the entry point states it for a radial table, except where the two values come from.  Per disc
+ * record that passed the twin's filter, with r and the record's stored (wrapped) phi:
+ *   radius   fi = log(r / r_min) / log(dr) (logbin) or (r - r_min) / dr; the record has a ring iff -1 < fi < nr, ir = (int) fi -- the truncated table
+ *            index of kr_line_bins.
+ *   azimuth  the wrap and the ip rule of kr_illum_bins on the record's phi: p = phi + phi_shift, phi_w, q_ph = (phi_w + M_PI) / dphi, a cell iff
+ *            q_ph >= 0, ip = min((int) q_ph, nphi - 1); nphi == 1: ip = 0 and no phi test.
+ *   values   emis = emis[ir nphi + ip];   tt = time ? time[ir nphi + ip] : 0.
+ * A record without ir, with a q_ph that is not >= 0 (a NaN), or whose cell holds a non-finite emis or tt passed the filter (it counts in on_disc) and is
+ * not used -- as the radial tables treat such a record.  The time expression keeps its operand order, (t + tt - t0) / dt.
+ * phi_shift is the orbital phase: the metric is axisymmetric, so ONE source trace at phi_s = 0 (a map made with phi_shift = 0) serves the source at
+ * every phase delta through phi_shift = -delta here.
+ * Refused (KR_EINVAL, before a device is touched): what the twin refuses; a null table or a table without emis; nr < 1; nphi < 1; nr nphi > 2^20; a
+ * non-finite r_min, dr or phi_shift; bins or a model that carry table_emis or table_time of their own; V = KR_V_PLUNGE.
+ * Not covered: the continuum spectrum pass (it has no time axis), the hot spot, the Stokes passes, the surface passes, the plunging flow, f32. */
+typedef struct kr_illum_table {
+    double r_min, dr;        /* radial index: the truncated table index of kr_line_bins */
+    double phi_shift;        /* the map's wrap and ip rule, on the DISC record's phi */
+    const double* emis;      /* HOST, nr x nphi, [ir nphi + ip]; required */
+    const double* time;      /* HOST, nr x nphi source -> disc delay, or NULL */
+    int32_t nr, nphi, logbin, pad;
+} kr_illum_table;
+#ifdef __cplusplus
+static_assert(sizeof(kr_illum_table) == 56, "kr_illum_table is 56 bytes (raytrace_cpu_amd/capi.py IllumTable)");
+#endif
+
 /* ---- runtime ---------------------------------------------------------------------------------- */
 int         kr_abi_version(void);
 const char* kr_last_error(void);
@@ -1301,6 +1362,28 @@ int kr_post_observer_dev_f64(double spin, double V, int reverse, int projradius,
                              int64_t n, void* d_out, void* stream);
 int kr_reduce_observer_dev_f64(const kr_observer_spec* sp, const void* d_rays, int64_t n, void* d_out, void* stream);
 int kr_reduce_observer_f64(const kr_observer_spec* sp, const kr_ray_f64* rays, int64_t n, double* out);
+
+/* ---- the (r, phi) illumination map of the disc (kr_illum_bins above has the rule) ---------------------------------------------------------------
+ * kr_post_: range_phi(lo, hi) + redshift(V, reverse, projradius, motion) on every record, stored back, then the map, in one pass: rays[] ends up
+ * byte for byte as kr_post_emissivity_dev_f64 leaves it.  kr_reduce_: the records read as they are and never written.  Both ADD into d_out
+ * (5 nr nphi + 2 doubles on the device; zero it first).  n == 0 is KR_OK and adds nothing.  kr_reduce_illum_f64: host records, out = 5 nr nphi + 2
+ * host doubles (overwritten). */
+int kr_post_illum_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_illum_bins* m, void* d_rays, int64_t n,
+                          void* d_out, void* stream);
+int kr_reduce_illum_dev_f64(const kr_illum_bins* m, const void* d_rays, int64_t n, void* d_out, void* stream);
+int kr_reduce_illum_f64(const kr_illum_bins* m, const kr_ray_f64* rays, int64_t n, double* out);
+/* the line and the response of an image plane's disc records driven by an (r, phi) table (kr_illum_table above has the rule): each is its flat twin with
+ * the table as one more argument and the twin's output layout -- kr_post_line_illum: kr_post_line_limb_dev_f64 (2 nt ne + 3 doubles); kr_reduce_line_illum:
+ * kr_reduce_line_dev_f64 / kr_reduce_line_f64 (2 nt ne + 2); kr_post_response_illum / kr_reduce_response_illum: kr_post_response_dev_f64 /
+ * kr_reduce_response_dev_f64 / kr_reduce_response_f64 (nt ne + 4).  The device forms ADD into their buffer; the host forms overwrite out.  n == 0 is KR_OK. */
+int kr_post_line_illum_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_line_bins* b, const kr_limb_law* law,
+                               const kr_illum_table* t, void* d_rays, int64_t n, void* d_line, void* stream);
+int kr_reduce_line_illum_dev_f64(const kr_line_bins* b, const kr_illum_table* t, const void* d_rays, int64_t n, void* d_line, void* stream);
+int kr_reduce_line_illum_f64(const kr_line_bins* b, const kr_illum_table* t, const kr_ray_f64* rays, int64_t n, double* out);
+int kr_post_response_illum_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_response_model* r,
+                                   const kr_limb_law* law, const kr_illum_table* t, void* d_rays, int64_t n, void* d_out, void* stream);
+int kr_reduce_response_illum_dev_f64(const kr_response_model* r, const kr_illum_table* t, const void* d_rays, int64_t n, void* d_out, void* stream);
+int kr_reduce_response_illum_f64(const kr_response_model* r, const kr_illum_table* t, const kr_ray_f64* rays, int64_t n, double* out);
 
 /* ---- emission-line profile / transfer function (kr_line_bins above) --------------------------------------------------------------------
  * Every entry point validates the bins first, before it touches a device: KR_EINVAL (message in kr_last_error) when ne < 1 or nt < 1, de <= 0,

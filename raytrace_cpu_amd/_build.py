@@ -12,7 +12,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["kr_trace.hip", "kr_post.hip", "kr_capi.hip", "kr_line.hip", "kr_caustic.hip", "kr_paths.hip", "kr_return_map.hip", "kr_volume.hip", "kr_observe.hip", "kr_crossings.hip", "kr_healpix.hip", "kr_angles.hip", "kr_polarisation.hip", "kr_source_vel.hip", "kr_angdist.hip", "kr_surface.hip", "kr_spectrum.hip", "kr_hotspot.hip", "kr_response.hip", "kr_observer.hip"]
+SOURCES = ["kr_trace.hip", "kr_post.hip", "kr_capi.hip", "kr_line.hip", "kr_caustic.hip", "kr_paths.hip", "kr_return_map.hip", "kr_volume.hip", "kr_observe.hip", "kr_crossings.hip", "kr_healpix.hip", "kr_angles.hip", "kr_polarisation.hip", "kr_source_vel.hip", "kr_angdist.hip", "kr_surface.hip", "kr_spectrum.hip", "kr_hotspot.hip", "kr_response.hip", "kr_observer.hip", "kr_illum.hip"]
 HEADERS = ["kr_device.hpp", "kr_crmath.hpp", "kr_arith.hpp", "kr_fast.hpp", "kr_rk45.hpp", "kr_post_device.hpp", "kr_sincos.hpp", "kr_replay.hpp", "kr_common.hpp", "kr_pass.hpp", "kr_disc_pass.hpp", "kr_spectrum_dev.hpp", "kr_ray_io.hpp", "kr_trace_loop.hpp", "kr_recorder.hpp", "kr_healpix_geom.hpp", "kr_vel_tetrad.hpp", os.path.join("..", "..", "include", "kr_trace.h")]
 LIB = os.path.join(CSRC, "libkrtrace.so")
 ARCH = "gfx950"

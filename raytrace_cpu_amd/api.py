@@ -549,7 +549,14 @@ def _surface_arg(what, surface, V=-1.0, pol=None):
     return capi.disc_surface(surface)
 
 
-def line_profile(imageplane_spec, params, bins, mode="rays", image_bins=None, limb=None, V=-1.0, surface=None):
+def _illum_arg(what, illum, V=-1.0, surface=None, pol=None):
+    """The capi.IllumTable of an illum= argument (an IllumTable, or the dict of illumination_table); the table passes are flat, unpolarised and Keplerian."""
+    if surface is not None or pol is not None or V == capi.V_PLUNGE:
+        raise KrError(f"{what}: illum cannot be combined with surface, pol or V = V_PLUNGE (the table passes are the flat, unpolarised, Keplerian ones)")
+    return illum if isinstance(illum, capi.IllumTable) else capi.illum_table(illum)
+
+
+def line_profile(imageplane_spec, params, bins, mode="rays", image_bins=None, limb=None, V=-1.0, surface=None, illum=None):
     """The emission line of an image plane, resident on the device from start to finish, as the kr_line_profile app runs it:
     ImagePlane ctor + redshift_start (kr_imageplane_init_emit_dev_f64) -> trace (kr_trace_dev_f64) -> either
       mode="rays":   redshift + range_phi + line bins per ray (kr_post_line_dev_f64), or
@@ -563,7 +570,22 @@ def line_profile(imageplane_spec, params, bins, mode="rays", image_bins=None, li
     thick_disc_params(...), as for surface_image.  The line is then that of the rays that LANDED on the surface, binned by rho = r sin(theta), the
     emission angle taken to the surface normal (kr_post_line_surface_dev_f64; limb None is the isotropic law) and "bad_angle" is always there.
     V = capi.V_PLUNGE is refused with a surface.
+    illum (mode="rays" only): None, or an (r, phi) illumination table -- a capi.IllumTable or the dict of illumination_table -- that gives every disc cell
+    its emissivity and source -> disc delay in place of powerlaw3 / the bins' radial table (kr_post_line_illum_dev_f64; limb None is the isotropic law,
+    and "bad_angle" is always there).  Its phi_shift is the orbital phase of the source (capi.illum_table).  Refused with surface or V = capi.V_PLUNGE.
+    With illum=None the calls are exactly those made without the argument.
     Returns line_from_words(...) plus "stats" (the trace's kr_stats) and, with a limb law, "bad_angle"."""
+    if illum is not None:
+        table = _illum_arg("line_profile", illum, V, surface)
+        if mode != "rays":
+            raise KrError("line_profile: illum needs mode='rays'")
+        law = capi.limb_law(limb if limb is not None else "isotropic")
+        words, stats, _ = _imageplane_run("line_profile", imageplane_spec, params, line_words(bins) + 1, lambda L, dev, d_rays, n, d_out: capi.check(
+            L, L.kr_post_line_illum_dev_f64(-1 * imageplane_spec.spin, V, 1, 0, 0, -np.pi, np.pi, C.byref(bins), C.byref(law), C.byref(table), d_rays, n, d_out, None),
+            "kr_post_line_illum"))
+        res = line_from_words(bins, words[:-1])
+        res["stats"], res["bad_angle"] = stats, _rounded(words[-1])
+        return res
     if surface is not None:
         sf = _surface_arg("line_profile", surface, V)
         if mode != "rays":
@@ -1642,15 +1664,8 @@ def reduce_observer(spec, rays):
     return observer_from_words(spec, out)
 
 
-def source_to_observer(source_spec, params, spec, V=-1.0, reverse=0, projradius=0, motion=0, lo=-np.pi, hi=np.pi, return_records=False):
-    """From a source's geometry to its direct continuum by observer inclination, resident on the device: the rays with their emitted energy
-    (kr_pointsource_init_emit_dev_f64 for a PointSourceSpec, kr_pointsource_vel_init_emit_dev_f64 for a PointSourceVelSpec,
-    kr_healpix_init_emit_dev_f64 for a HealpixSource) -> kr_trace_dev_f64 with `params` (KR_STOP_THETA to the disc plane, r_max beyond the spec's
-    r_esc) -> range_phi + redshift(V, reverse, projradius, motion) + the link (kr_post_observer_dev_f64).  The records never leave the device
-    (return_records copies the final ones back, for tests).  Returns the dict of observer_from_words plus "stats"."""
-    L = lib()
-    if spec.spin != params.spin:
-        raise KrError("source_to_observer: spec.spin is not the spin of params")
+def _source_init(what, L, source_spec, reverse, projradius):
+    """(n, init) of a source: its ray count and init(d_rays), the call that builds its rays with their emitted energy on the device."""
     if isinstance(source_spec, capi.PointSourceSpec):
         n = pointsource_count(source_spec)[0]
         init = lambda d: L.kr_pointsource_init_emit_dev_f64(C.byref(source_spec), 0, 1, source_spec.V, int(reverse), int(projradius), d, n, None)      # noqa: E731
@@ -1661,7 +1676,20 @@ def source_to_observer(source_spec, params, spec, V=-1.0, reverse=0, projradius=
         n = healpix_count(source_spec)[0]
         init = lambda d: L.kr_healpix_init_emit_dev_f64(C.byref(source_spec), 0, 1, int(reverse), d, n, None)      # noqa: E731
     else:
-        raise KrError("source_to_observer: source_spec must be a PointSourceSpec, a PointSourceVelSpec or a HealpixSource")
+        raise KrError(f"{what}: source_spec must be a PointSourceSpec, a PointSourceVelSpec or a HealpixSource")
+    return n, init
+
+
+def source_to_observer(source_spec, params, spec, V=-1.0, reverse=0, projradius=0, motion=0, lo=-np.pi, hi=np.pi, return_records=False):
+    """From a source's geometry to its direct continuum by observer inclination, resident on the device: the rays with their emitted energy
+    (kr_pointsource_init_emit_dev_f64 for a PointSourceSpec, kr_pointsource_vel_init_emit_dev_f64 for a PointSourceVelSpec,
+    kr_healpix_init_emit_dev_f64 for a HealpixSource) -> kr_trace_dev_f64 with `params` (KR_STOP_THETA to the disc plane, r_max beyond the spec's
+    r_esc) -> range_phi + redshift(V, reverse, projradius, motion) + the link (kr_post_observer_dev_f64).  The records never leave the device
+    (return_records copies the final ones back, for tests).  Returns the dict of observer_from_words plus "stats"."""
+    L = lib()
+    if spec.spin != params.spin:
+        raise KrError("source_to_observer: spec.spin is not the spin of params")
+    n, init = _source_init("source_to_observer", L, source_spec, reverse, projradius)
     sized = 1 <= spec.nmu <= 4096 and 0 <= spec.nt and spec.nmu * (4 + spec.nt) <= 1 << 24        # (the pass refuses the rest: it gets a null buffer)
     nw = observer_words(spec) if sized else 0
     st = Stats()
@@ -1721,6 +1749,87 @@ def observer_text(res):
         rows.append(_path_field(float(res["mu"][i])) + "%20d" % int(res["count"][i]) + "".join(_path_field(float(x)) for x in [flux[i]] + means + list(res["hist"][i]))
                     + "\n")
     return "".join(rows)
+
+
+# ---- the (r, phi) illumination map of the disc (include/kr_trace.h, kr_illum_bins) ----
+ILLUM_PLANES = ("count", "flux", "emis", "sum_redshift", "sum_time")
+ILLUM_TALLIES = ("disc_count", "binned")
+ILLUM_MAX_CELLS = 1 << 20
+
+
+def _illum_layout(bins, words=None):
+    return _layout([(k, (bins.rad.nr, bins.nphi)) for k in ILLUM_PLANES], [(k, _rounded) for k in ILLUM_TALLIES], words)
+
+
+def _illum_sized(bins):
+    return bins.rad.nr >= 1 and bins.nphi >= 1 and bins.rad.nr * bins.nphi <= ILLUM_MAX_CELLS
+
+
+def illum_words(bins):
+    """Length of the buffer of kr_post_illum_dev_f64 / kr_reduce_illum_dev_f64: five planes of nr x nphi and two tallies."""
+    return _illum_layout(bins)
+
+
+def illum_from_words(bins, words):
+    """That buffer as a dict: count (int64), flux, emis, sum_redshift, sum_time (raw sums), each shaped (nr, nphi); disc_count, binned; `phi` (the
+    centres of the azimuthal cells, counted from -pi) and the bin description r_min, dr, logbin, phi_shift that illumination_table reads."""
+    out = _illum_layout(bins, words)
+    out["count"] = np.rint(out["count"]).astype(np.int64)
+    out["phi"] = -np.pi + (np.arange(bins.nphi) + 0.5) * (2 * np.pi / bins.nphi)
+    out.update(r_min=bins.rad.r_min, dr=bins.rad.dr, logbin=int(bins.rad.logbin), phi_shift=bins.phi_shift)
+    return out
+
+
+def reduce_illum(bins, rays):
+    """kr_reduce_illum_f64: the (r, phi) map of host ray records read as they are (after range_phi() and redshift())."""
+    _rays_arg(rays, capi.RAY_F64)
+    out = np.zeros(illum_words(bins) if _illum_sized(bins) else 1)      # (the call refuses the rest before it writes)
+    capi.check(lib(), lib().kr_reduce_illum_f64(C.byref(bins), _ptr(rays), len(rays), _ptr(out)), "kr_reduce_illum")
+    return illum_from_words(bins, out)
+
+
+def illumination_map(source_spec, params, bins, V=-1.0, reverse=0, projradius=0, motion=0, lo=-np.pi, hi=np.pi, return_records=False):
+    """From a source's geometry to the (r, phi) map of how it lights the disc, resident on the device: the rays with their emitted energy
+    (kr_pointsource_init_emit_dev_f64 for a PointSourceSpec, kr_pointsource_vel_init_emit_dev_f64 for a PointSourceVelSpec,
+    kr_healpix_init_emit_dev_f64 for a HealpixSource) -> kr_trace_dev_f64 with `params` (KR_STOP_THETA to the disc plane) -> range_phi +
+    redshift(V, reverse, projradius, motion) + the map (kr_post_illum_dev_f64).  The records never leave the device (return_records copies the final
+    ones back, for tests).
+    bins.phi_shift is the orbital phase: the metric is axisymmetric, so ONE trace of the source at phi_s = 0 serves every phase delta -- the map of the
+    source at phi_s = delta is this map made with phi_shift = +delta, and a table made from the phi_s = 0 map is applied to disc records with
+    phi_shift = -delta.  Returns the dict of illum_from_words plus "stats"."""
+    L = lib()
+    n, init = _source_init("illumination_map", L, source_spec, reverse, projradius)
+    nw = illum_words(bins) if _illum_sized(bins) else 0                 # (the pass refuses the rest: it gets a null buffer)
+    st = Stats()
+    with DeviceScope(L) as dev:
+        d_rays = dev.alloc(n * capi.RAY_F64.itemsize) if n > 0 else C.c_void_p()
+        d_out = dev.zeros(nw * 8) if nw else C.c_void_p()
+        capi.check(L, init(d_rays), "illumination_map: source + emitted energy")
+        capi.check(L, L.kr_trace_dev_f64(C.byref(params), d_rays, n, None, C.byref(st)), "kr_trace_dev")
+        capi.check(L, L.kr_post_illum_dev_f64(params.spin, V, int(reverse), int(projradius), int(motion), lo, hi, C.byref(bins), d_rays, n, d_out, None),
+                   "kr_post_illum")
+        res = illum_from_words(bins, dev.fetch(d_out, nw))
+        res["stats"] = st.as_dict()
+        if return_records:
+            res["records"] = dev.fetch(d_rays, n, capi.RAY_F64)
+    return res
+
+
+def illumination_table(res, areas):
+    """The (r, phi) tables of a map (illum_from_words, illumination_map): per cell the emissivity emis = emis_sum / (areas[ir] / nphi) -- areas: the
+    proper area of every annulus, nr values, e.g. surface_area(edges, r_in, 0, 0, spin, dphi=2 pi) of the flat disc or integrate_disc_area of
+    host/include/disc.h -- and the mean source -> disc delay time = sum_time / count, NaN where no ray landed (a pass that reads the table leaves
+    the records of such a cell out, as with a non-finite entry of a radial table).  Returns {"emis", "time"} shaped (nr, nphi) and the map's r_min, dr,
+    logbin, phi_shift, nr, nphi.  Host numpy."""
+    emis_sum, count = np.asarray(res["emis"], dtype=np.float64), np.asarray(res["count"])
+    nr, nphi = emis_sum.shape
+    areas = np.asarray(areas, dtype=np.float64)
+    if areas.shape != (nr,):
+        raise KrError(f"illumination_table: areas must hold one area per annulus, {nr} values")
+    with np.errstate(invalid="ignore", divide="ignore"):
+        emis = emis_sum / (areas / nphi)[:, None]
+        time = np.where(count > 0, np.asarray(res["sum_time"], dtype=np.float64) / count, np.nan)
+    return {"emis": emis, "time": time, "r_min": res["r_min"], "dr": res["dr"], "logbin": res["logbin"], "phi_shift": res["phi_shift"], "nr": nr, "nphi": nphi}
 
 
 # ---- continuum spectrum of the disc (include/kr_trace.h, kr_spectrum_model) ----
@@ -1980,16 +2089,30 @@ def reduce_response(model, rays):
     return response_from_words(model, out)
 
 
-def disc_response(imageplane_spec, params, model, limb=None, return_records=False, V=-1.0, surface=None):
+def disc_response(imageplane_spec, params, model, limb=None, return_records=False, V=-1.0, surface=None, illum=None):
     """The energy-time response of the disc seen on an image plane, resident on the device from start to finish, as the kr_reverb_response app runs it:
     ImagePlane ctor + redshift_start -> trace (`params` as for the image app: the stored, negated spin) -> redshift + range_phi + the response
     (kr_post_response_dev_f64).  model: a capi.ResponseModel; limb: None (isotropic) or a limb law as for line_profile.  Only the nt ne + 4 words are read
     back (and, with return_records, the final records: for tests).  Returns response_from_words(...) plus "stats" (the trace's kr_stats).  The response is
     per image-plane pixel: multiply by dx dy / D^2 for a flux density.  V: -1 or capi.V_PLUNGE, as for line_profile (model.spec.r_isco is the inner edge).
     surface: None, or (r_in, r_out, slope, scale) / a capi.DiscSurface, as for line_profile: the response of the rays that landed on that surface
-    (kr_post_response_surface_dev_f64; trace to it with thick_disc_params(...)).  Refused together with V = capi.V_PLUNGE."""
+    (kr_post_response_surface_dev_f64; trace to it with thick_disc_params(...)).  Refused together with V = capi.V_PLUNGE.
+    illum: None, or an (r, phi) illumination table -- a capi.IllumTable or the dict of illumination_table -- that gives every disc cell its emissivity and
+    source -> disc delay in place of powerlaw3 / the model's radial tables, which the model must then not carry (kr_post_response_illum_dev_f64).  Its
+    phi_shift is the orbital phase of the source: one source trace at phi_s = 0 serves every phase (capi.illum_table).  Refused with surface or
+    V = capi.V_PLUNGE.  With illum=None the calls are exactly those made without the argument."""
     law = capi.limb_law(limb if limb is not None else "isotropic")
     sized = 1 <= model.spec.ne <= 4096 and 1 <= model.nt and model.nt * model.spec.ne <= 1 << 24        # (the pass refuses the rest: it gets a null buffer)
+    if illum is not None:
+        table = _illum_arg("disc_response", illum, V, surface)
+        words, stats, records = _imageplane_run("disc_response", imageplane_spec, params, response_words(model) if sized else 0, lambda L, dev, d_rays, n, d_out: capi.check(
+            L, L.kr_post_response_illum_dev_f64(-1 * imageplane_spec.spin, V, 1, 0, 0, -np.pi, np.pi, C.byref(model), C.byref(law), C.byref(table), d_rays, n, d_out, None),
+            "kr_post_response_illum"), return_records)
+        res = response_from_words(model, words)
+        res["stats"] = stats
+        if return_records:
+            res["records"] = records
+        return res
     if surface is not None:
         sf = _surface_arg("disc_response", surface, V)
         words, stats, records = _imageplane_run("disc_response", imageplane_spec, params, response_words(model) if sized else 0, lambda L, dev, d_rays, n, d_out: capi.check(

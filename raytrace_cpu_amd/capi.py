@@ -323,6 +323,60 @@ class ObserverSpec(C.Structure):
 assert C.sizeof(ObserverSpec) == 120
 
 
+class IllumBins(C.Structure):
+    """kr_illum_bins: the (r, phi) illumination map of the disc -- the emissivity histogram's bins (rad), the azimuthal cells and the shift added to a
+    record's phi before the wrap (include/kr_trace.h has the rule)."""
+    _fields_ = [("rad", EmisBins), ("phi_shift", C.c_double), ("nphi", C.c_int32), ("pad", C.c_int32)]
+
+
+assert C.sizeof(IllumBins) == 72
+
+
+def illum_bins(rad, nphi, phi_shift=0.0):
+    """An IllumBins: rad, an EmisBins, copied in; nphi cells of 2 pi / nphi from phi = -pi; phi_shift added to every record's phi before the wrap."""
+    m = IllumBins()
+    C.memmove(C.byref(m.rad), C.byref(rad), C.sizeof(EmisBins))
+    m.phi_shift, m.nphi, m.pad = float(phi_shift), int(nphi), 0
+    return m
+
+
+class IllumTable(C.Structure):
+    """kr_illum_table: an (r, phi) table of the emissivity and the source -> disc delay for the line and the response (include/kr_trace.h has the rule).
+    emis / time are host double arrays of nr x nphi or None; keep them alive while the struct is in use (illum_table does)."""
+    _fields_ = [("r_min", C.c_double), ("dr", C.c_double), ("phi_shift", C.c_double), ("emis", C.POINTER(C.c_double)), ("time", C.POINTER(C.c_double))] + \
+               [(n, C.c_int32) for n in ("nr", "nphi", "logbin", "pad")]
+
+
+assert C.sizeof(IllumTable) == 56
+
+
+def illum_table(emis, r_min=None, dr=None, logbin=True, time=None, phi_shift=None):
+    """An IllumTable from emis (and time) of shape (nr, nphi) -- or from the dict of api.illumination_table as the only argument: its planes, its radial
+    grid and the phi_shift its map was made with (a cell must mean the same azimuth in the map and in the table), which the keyword replaces when
+    given.  phi_shift is the orbital phase: a table made from the map of a source at phi_s = 0 with shift s serves the source at phase delta with
+    phi_shift = s - delta.  The arrays are copied and kept alive by the struct."""
+    if isinstance(emis, dict):
+        d = emis
+        emis, time, r_min, dr, logbin = d["emis"], d.get("time"), d["r_min"], d["dr"], d["logbin"]
+        phi_shift = d["phi_shift"] if phi_shift is None else phi_shift
+    phi_shift = 0.0 if phi_shift is None else phi_shift
+    if r_min is None or dr is None:
+        raise ValueError("illum_table: r_min and dr are needed with arrays")
+    t = IllumTable()
+    t._keep = {"emis": np.ascontiguousarray(emis, dtype=np.float64).copy()}
+    if t._keep["emis"].ndim != 2:
+        raise ValueError("illum_table: emis must be shaped (nr, nphi)")
+    t.nr, t.nphi = t._keep["emis"].shape
+    t.emis = t._keep["emis"].ctypes.data_as(C.POINTER(C.c_double))
+    if time is not None:
+        t._keep["time"] = np.ascontiguousarray(time, dtype=np.float64).copy()
+        if t._keep["time"].shape != t._keep["emis"].shape:
+            raise ValueError("illum_table: time must have the shape of emis")
+        t.time = t._keep["time"].ctypes.data_as(C.POINTER(C.c_double))
+    t.r_min, t.dr, t.logbin, t.phi_shift, t.pad = float(r_min), float(dr), int(bool(logbin)), float(phi_shift), 0
+    return t
+
+
 def line_bins(line_energy=6.4, e_min=1.0, de=0.1, ne=90, log_e=False, t0=0.0, dt=0.0, nt=1, r_isco=1.0, r_disc=1000.0, q1=3.0, rb1=4.0, q2=3.0,
               rb2=10.0, q3=3.0, g_index=3.0):
     b = LineBins()
@@ -469,6 +523,15 @@ PROTOTYPES = {
     "kr_post_observer_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, P(ObserverSpec), _vp, _i64, _vp, _vp]),
     "kr_reduce_observer_dev_f64": (_int, [P(ObserverSpec), _vp, _i64, _vp, _vp]),
     "kr_reduce_observer_f64": (_int, [P(ObserverSpec), _vp, _i64, _vp]),
+    "kr_post_illum_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, P(IllumBins), _vp, _i64, _vp, _vp]),
+    "kr_reduce_illum_dev_f64": (_int, [P(IllumBins), _vp, _i64, _vp, _vp]),
+    "kr_reduce_illum_f64": (_int, [P(IllumBins), _vp, _i64, _vp]),
+    "kr_post_line_illum_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, P(LineBins), P(LimbLaw), P(IllumTable), _vp, _i64, _vp, _vp]),
+    "kr_reduce_line_illum_dev_f64": (_int, [P(LineBins), P(IllumTable), _vp, _i64, _vp, _vp]),
+    "kr_reduce_line_illum_f64": (_int, [P(LineBins), P(IllumTable), _vp, _i64, _vp]),
+    "kr_post_response_illum_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, P(ResponseModel), P(LimbLaw), P(IllumTable), _vp, _i64, _vp, _vp]),
+    "kr_reduce_response_illum_dev_f64": (_int, [P(ResponseModel), P(IllumTable), _vp, _i64, _vp, _vp]),
+    "kr_reduce_response_illum_f64": (_int, [P(ResponseModel), P(IllumTable), _vp, _i64, _vp]),
     "kr_reduce_line_f64": (_int, [P(LineBins), _vp, _i64, _vp]),
     "kr_reduce_line_dev_f64": (_int, [P(LineBins), _vp, _i64, _vp, _vp]),
     "kr_post_line_dev_f64": (_int, [_dbl, _dbl, _int, _int, _int, _dbl, _dbl, P(LineBins), _vp, _i64, _vp, _vp]),

@@ -1166,6 +1166,32 @@ int kr_reduce_observer_f64(const kr_observer_spec* sp, const kr_ray_f64* rays, i
     return reduce_to_host(rays, n, (size_t) observer_words(sp), out, [&](void* d, void* d_out) { return reduce_observer_dev(sp, d, n, d_out, nullptr); });
 }
 
+// ---- the (r, phi) illumination map (kr_illum.hip) --------------------------------------------------------------------------------------------------
+int kr_reduce_illum_dev_f64(const kr_illum_bins* m, const void* d, int64_t n, void* d_out, void* st)
+{
+    const int rc = illum_validate(m, "kr_reduce_illum");
+    if (rc != KR_OK) return rc;
+    return on_device(n >= 0 && d_out && (n == 0 || d), "kr_reduce_illum: null argument or negative n", [&] { return reduce_illum_dev(m, d, n, d_out, (hipStream_t) st); });
+}
+
+int kr_post_illum_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_illum_bins* m, void* d, int64_t n, void* d_out,
+                          void* st)
+{
+    int rc = refuse_plunge(V, "kr_post_illum");
+    if (rc == KR_OK) rc = illum_validate(m, "kr_post_illum");
+    if (rc != KR_OK) return rc;
+    return on_device(n >= 0 && d_out && (n == 0 || d), "kr_post_illum: null argument or negative n",
+                     [&] { return post_illum_dev(spin, V, reverse, projradius, motion, lo, hi, m, d, n, d_out, (hipStream_t) st); });
+}
+
+int kr_reduce_illum_f64(const kr_illum_bins* m, const kr_ray_f64* rays, int64_t n, double* out)
+{
+    const int rc = illum_validate(m, "kr_reduce_illum");
+    if (rc != KR_OK) return rc;
+    if (!out || n < 0 || (n > 0 && !rays)) return invalid("kr_reduce_illum: null argument or negative n");
+    return reduce_to_host(rays, n, (size_t) illum_words(m), out, [&](void* d, void* d_out) { return reduce_illum_dev(m, d, n, d_out, nullptr); });
+}
+
 int kr_reduce_line_dev_f64(const kr_line_bins* b, const void* d, int64_t n, void* d_line, void* st)
 {
     const int rc = line_validate(b, "kr_reduce_line");
@@ -1306,6 +1332,86 @@ int kr_reduce_response_f64(const kr_response_model* r, const kr_ray_f64* rays, i
     if (!out || n < 0 || (n > 0 && !rays)) return invalid("kr_reduce_response: null argument or negative n");
     std::vector<double> h((size_t) r->nt * r->spec.ne + 4, 0.0);        // out is written only by a call that succeeds
     const int rc2 = reduce_to_host(rays, n, h.size(), h.data(), [&](void* d, void* d_out) { return reduce_response_dev(r, d, n, d_out, nullptr); });
+    if (rc2 == KR_OK) std::memcpy(out, h.data(), h.size() * sizeof(double));
+    return rc2;
+}
+
+// ---- the line and the response driven by an (r, phi) illumination table (kr_illum_table; the ILLUM flavour of kr_line.hip and kr_response.hip): what the
+//      flat twin validates, then the table, then that the bins / the model carry no radial table of their own; nothing touches a device before that ----
+namespace {
+int line_illum_validate(const kr_line_bins* b, const kr_illum_table* t, const char* who)
+{
+    int rc = line_validate(b, who);
+    if (rc == KR_OK) rc = illum_table_validate(t, who);
+    if (rc == KR_OK && (b->table_emis || b->table_time)) rc = invalid_arg(who, "the bins carry a radial table as well as the (r, phi) table");
+    return rc;
+}
+int response_illum_validate(const kr_response_model* r, const kr_illum_table* t, const char* who)
+{
+    int rc = response_validate(r, who);
+    if (rc == KR_OK) rc = illum_table_validate(t, who);
+    if (rc == KR_OK && (r->spec.table_emis || r->table_time)) rc = invalid_arg(who, "the model carries a radial table as well as the (r, phi) table");
+    return rc;
+}
+}  // namespace
+
+int kr_post_line_illum_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_line_bins* b, const kr_limb_law* law,
+                               const kr_illum_table* t, void* d, int64_t n, void* d_line, void* st)
+{
+    int rc = refuse_plunge(V, "kr_post_line_illum");
+    if (rc == KR_OK) rc = line_illum_validate(b, t, "kr_post_line_illum");
+    if (rc == KR_OK) rc = limb_validate(law, "kr_post_line_illum");
+    if (rc == KR_OK) rc = angles_validate(motion, "kr_post_line_illum");
+    if (rc != KR_OK) return rc;
+    return on_device(n >= 0 && d_line && (n == 0 || d), "kr_post_line_illum: null argument or negative n",
+                     [&] { return post_line_illum_dev(spin, V, reverse, projradius, lo, hi, b, law, t, d, n, d_line, (hipStream_t) st); });
+}
+
+int kr_reduce_line_illum_dev_f64(const kr_line_bins* b, const kr_illum_table* t, const void* d, int64_t n, void* d_line, void* st)
+{
+    const int rc = line_illum_validate(b, t, "kr_reduce_line_illum");
+    if (rc != KR_OK) return rc;
+    return on_device(n >= 0 && d_line && (n == 0 || d), "kr_reduce_line_illum: null argument or negative n",
+                     [&] { return reduce_line_illum_dev(b, t, d, n, d_line, (hipStream_t) st); });
+}
+
+int kr_reduce_line_illum_f64(const kr_line_bins* b, const kr_illum_table* t, const kr_ray_f64* rays, int64_t n, double* out)
+{
+    const int rc = line_illum_validate(b, t, "kr_reduce_line_illum");
+    if (rc != KR_OK) return rc;
+    if (!out || n < 0 || (n > 0 && !rays)) return invalid("kr_reduce_line_illum: null argument or negative n");
+    std::vector<double> h((size_t) 2 * b->nt * b->ne + 2, 0.0);        // out is written only by a call that succeeds
+    const int rc2 = reduce_to_host(rays, n, h.size(), h.data(), [&](void* d, void* d_line) { return reduce_line_illum_dev(b, t, d, n, d_line, nullptr); });
+    if (rc2 == KR_OK) std::memcpy(out, h.data(), h.size() * sizeof(double));
+    return rc2;
+}
+
+int kr_post_response_illum_dev_f64(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_response_model* r,
+                                   const kr_limb_law* law, const kr_illum_table* t, void* d, int64_t n, void* d_out, void* st)
+{
+    int rc = refuse_plunge(V, "kr_post_response_illum");
+    if (rc == KR_OK) rc = response_illum_validate(r, t, "kr_post_response_illum");
+    if (rc == KR_OK) rc = spectrum_law_validate(law, motion, "kr_post_response_illum");
+    if (rc != KR_OK) return rc;
+    return on_device(n >= 0 && d_out && (n == 0 || d), "kr_post_response_illum: null argument or negative n",
+                     [&] { return post_response_illum_dev(spin, V, reverse, projradius, motion, lo, hi, r, law, t, d, n, d_out, (hipStream_t) st); });
+}
+
+int kr_reduce_response_illum_dev_f64(const kr_response_model* r, const kr_illum_table* t, const void* d, int64_t n, void* d_out, void* st)
+{
+    const int rc = response_illum_validate(r, t, "kr_reduce_response_illum");
+    if (rc != KR_OK) return rc;
+    return on_device(n >= 0 && d_out && (n == 0 || d), "kr_reduce_response_illum: null argument or negative n",
+                     [&] { return reduce_response_illum_dev(r, t, d, n, d_out, (hipStream_t) st); });
+}
+
+int kr_reduce_response_illum_f64(const kr_response_model* r, const kr_illum_table* t, const kr_ray_f64* rays, int64_t n, double* out)
+{
+    const int rc = response_illum_validate(r, t, "kr_reduce_response_illum");
+    if (rc != KR_OK) return rc;
+    if (!out || n < 0 || (n > 0 && !rays)) return invalid("kr_reduce_response_illum: null argument or negative n");
+    std::vector<double> h((size_t) r->nt * r->spec.ne + 4, 0.0);        // out is written only by a call that succeeds
+    const int rc2 = reduce_to_host(rays, n, h.size(), h.data(), [&](void* d, void* d_out) { return reduce_response_illum_dev(r, t, d, n, d_out, nullptr); });
     if (rc2 == KR_OK) std::memcpy(out, h.data(), h.size() * sizeof(double));
     return rc2;
 }

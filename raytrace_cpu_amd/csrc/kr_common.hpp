@@ -66,9 +66,9 @@ struct DeviceBuffer {
 // read the arrays have been enqueued.  When a device holds kMaxDeviceTables entries (kr_capi.hip), a miss drains that device and frees its unpinned
 // entries: a kernel that reads one was enqueued before its pin was released, so the drain has finished it.  Pinned entries and other devices'
 // entries are never freed by a lookup; while every entry is pinned the count may exceed the cap.
-enum TableKind { kAngleTable, kLineTable, kSpectrumKtTable, kSpectrumEmisTable, kSpectrumTable, kResponseTimeTable };
+enum TableKind { kAngleTable, kLineTable, kSpectrumKtTable, kSpectrumEmisTable, kSpectrumTable, kResponseTimeTable, kIllumEmisTable, kIllumTimeTable };
 // key of kAngleTable: (alpha / beta, x0, dx, n); of kLineTable: the table's bytes, columns; of the three of kr_spectrum.hip (kT and emissivity by
-// radius, the rest-frame spectrum S) and of kr_response.hip's source->disc time by radius: the table's bytes
+// radius, the rest-frame spectrum S) and of kr_response.hip's source->disc time by radius: the table's bytes; of the two planes of a kr_illum_table: the plane's bytes
 struct DeviceTable;
 class TablePins {
 public:

@@ -192,6 +192,38 @@ KR_DEV bool radial_table_index(int logbin, double r_min, double dr, double log_d
     return true;
 }
 
+// ---- the (r, phi) illumination table of the line and the response (include/kr_trace.h, kr_illum_table): a compile-time parameter of their kernels like
+//      DiscFlow and DiscSurface, so that every instance without it is the code it was.  IllumTab<false> carries nothing; IllumTab<true> the table's
+//      grid, the device copies of its planes (global memory: nr nphi doubles each) and the two values taken once on the host. ----
+template <bool ILLUM> struct IllumTab {};
+template <> struct IllumTab<true> {
+    double r_min, dr, log_dr, phi_shift, dphi;       // log_dr: log(dr) with logbin; dphi = 2 M_PI / nphi
+    const double* emis;                              // [nr nphi] on the device
+    const double* time;                              // [nr nphi] on the device, or null
+    int nr, nphi, logbin;
+};
+
+// emis and tt of a disc record at (r, phi): the radial index of radial_table_index, the azimuthal cell of kr_illum_bins (kr_illum.hip).  false: the
+// record has no cell (no ir, a q_ph that is not >= 0) or its cell holds a non-finite emis or tt -- it is not used
+KR_DEV bool illum_table_entry(const IllumTab<true>& T, double r, double phi, double* emis, double* tt)
+{
+    int ir, ip = 0;
+    if (!radial_table_index(T.logbin, T.r_min, T.dr, T.log_dr, T.nr, r, &ir)) return false;
+    if (T.nphi != 1) {
+        const double p = phi + T.phi_shift;
+        const double phi_w = p - (2 * kPi) * floor((p + kPi) / (2 * kPi));
+        const double q_ph = (phi_w + kPi) / T.dphi;
+        if (!(q_ph >= 0)) return false;
+        ip = q_ph < T.nphi ? (int) q_ph : T.nphi - 1;
+    }
+    const int c = ir * T.nphi + ip;
+    if (!(c >= 0 && c < T.nr * T.nphi)) return false;
+    const double e = T.emis[c], t = T.time ? T.time[c] : 0;
+    if (!__builtin_isfinite(e) || !__builtin_isfinite(t)) return false;
+    *emis = e; *tt = t;
+    return true;
+}
+
 // the energy E in units of bins from e_min; the bin is (int) of it where 0 <= it < ne (the caller's test: a NaN fails)
 KR_DEV double energy_bin_coord(int log_e, double e_min, double de, double log_de, double E)
 {
@@ -219,6 +251,10 @@ inline kr_limb_law isotropic_limb()
     iso.coeff = 0; iso.law = 0; iso.pad = 0;
     return iso;
 }
+
+// a kr_illum_table that illum_table_validate (kr_pass.hpp) has passed: its planes on the device through the table store (kr_illum.hip), pinned in
+// `pins`: keep it until the kernel that reads them has been enqueued
+int illum_table_dev(const kr_illum_table* t, TablePins& pins, IllumTab<true>* T);
 
 // the energy axis of kr_line_bins, kr_spectrum_model and kr_hotspot; bad(why) sets the error and returns its code
 template <typename Bad>

@@ -5,6 +5,8 @@
 //   reduce_line_kernel      records after redshift(-1, reverse=1) -> line bins
 //   post_line_kernel        redshift + range_phi + line bins in one pass (the sibling of post_image_kernel; same per-ray functions)
 //   post_line_limb_kernel   the same with the weight times a limb law of the emission angle mu in the disc frame (kr_limb_law; frame_value)
+//                           ILLUM: emis and the source -> disc time from an (r, phi) table (kr_illum_table; IllumTab, kr_disc_pass.hpp), here and
+//                           in reduce_line_kernel
 //   post_line_stokes_kernel the limb-law line with the Stokes parameters I, Q, U of the polarised emission per bin (kr_pol_law; polar_value)
 //   line_from_image_kernel  raw-sum image planes (kr_reduce_image_dev_f64 layout) -> line bins, per pixel
 // All of them are streaming passes, one record / pixel per work-item.  The histogram is privatised per workgroup in LDS when it fits
@@ -42,12 +44,16 @@ struct LineDev {
 
 // one item that passed the filter -> at most one bin k = j ne + i and its weight w; false: the item is not binned.  PIXEL: x is the pixel's mean 1/g
 // (E = line_energy x, w = emis x^g_index); otherwise x is g (E = line_energy / g, w = emis g^-g_index).  LIMB: w times `limb`.
-template <bool PIXEL, bool LIMB>
-KR_DEV bool line_item(const LineDev& L, double r, double x, double t, double limb, int* k, double* w)
+// ILLUM: emis and tt from the cell of the (r, phi) table T that holds the record (the bins carry no radial table then)
+template <bool PIXEL, bool LIMB, bool ILLUM = false>
+KR_DEV bool line_item(const LineDev& L, double r, double x, double t, double limb, int* k, double* w, [[maybe_unused]] const IllumTab<ILLUM>& T = IllumTab<ILLUM>{},
+                      [[maybe_unused]] double phi = 0)
 {
     const kr_line_bins& b = L.b;
     double emis, tt = 0;
-    if (L.t_emis) {
+    if constexpr (ILLUM) {
+        if (!illum_table_entry(T, r, phi, &emis, &tt)) return false;
+    } else if (L.t_emis) {
         int ir;
         if (!radial_table_index(b.table_logbin, b.table_r_min, b.table_dr, L.log_tdr, b.table_nr, r, &ir)) return false;
         emis = L.t_emis[ir];
@@ -72,12 +78,12 @@ KR_DEV bool line_item(const LineDev& L, double r, double x, double t, double lim
 }
 
 // the item into [count | flux].  Returns 1 if the item was binned.
-template <bool PIXEL, bool LIMB = false>
-KR_DEV unsigned line_accumulate(double* acc, const LineDev& L, double r, double x, double t, double limb = 1)
+template <bool PIXEL, bool LIMB = false, bool ILLUM = false>
+KR_DEV unsigned line_accumulate(double* acc, const LineDev& L, double r, double x, double t, double limb = 1, const IllumTab<ILLUM>& T = IllumTab<ILLUM>{}, double phi = 0)
 {
     int k;
     double w;
-    if (!line_item<PIXEL, LIMB>(L, r, x, t, limb, &k, &w)) return 0;
+    if (!line_item<PIXEL, LIMB, ILLUM>(L, r, x, t, limb, &k, &w, T, phi)) return 0;
     atomicAdd(&acc[k], 1.0);
     atomicAdd(&acc[L.b.nt * L.b.ne + k], w);
     return 1;
@@ -110,9 +116,9 @@ KR_DEV void line_end(double* lds, double* out, int words, unsigned long long on_
 
 // SURFACE: the records landed on a surface (disc_filter_surface, kr_disc_pass.hpp), the radius is rho, and the layout is the limb line's with a
 // bad_angle word that stays 0 (the records carry no emission angle)
-template <bool USE_LDS, bool SURFACE = false>
+template <bool USE_LDS, bool SURFACE = false, bool ILLUM = false>
 __global__ void __launch_bounds__(kBlock)
-reduce_line_kernel(const kr_ray_f64* __restrict__ rays, long long n, LineDev L, double* __restrict__ out)
+reduce_line_kernel(const kr_ray_f64* __restrict__ rays, long long n, LineDev L, double* __restrict__ out, IllumTab<ILLUM> T)
 {
     extern __shared__ double lds[];
     const int words = SURFACE ? L.words + 1 : L.words;
@@ -129,7 +135,8 @@ reduce_line_kernel(const kr_ray_f64* __restrict__ rays, long long n, LineDev L, 
             if (!disc_filter(L.b.r_isco, L.b.r_disc, ray->steps, r, ray->theta, g)) continue;
         }
         on_disc++;
-        binned += line_accumulate<false>(acc, L, r, g, ray->t);
+        if constexpr (ILLUM) binned += line_accumulate<false, false, true>(acc, L, r, g, ray->t, 1, T, ray->phi);
+        else binned += line_accumulate<false>(acc, L, r, g, ray->t);
     }
     line_end<USE_LDS, SURFACE>(lds, out, words, on_disc, binned);
 }
@@ -162,10 +169,10 @@ post_line_kernel(kr_ray_f64* __restrict__ rays, long long n, double spin, double
 // post_line_kernel with w *= limb(mu): disc_ray (kr_disc_pass.hpp) in its fused form for the orbiting observer, so rays[] ends as after
 // post_line_kernel and a bad-angle ray is counted and binned by that function's rule.  Layout: post_line_kernel's, then bad_angle.
 // SURFACE: the line of a disc with a surface (DiscSurface, kr_post_device.hpp): the filter, the radius and the angle of disc_ray's surface flavour
-template <bool USE_LDS, bool PLUNGE, bool SURFACE = false>
+template <bool USE_LDS, bool PLUNGE, bool SURFACE = false, bool ILLUM = false>
 __global__ void __launch_bounds__(kBlock)
 post_line_limb_kernel(kr_ray_f64* __restrict__ rays, long long n, double spin, double V, int reverse, int projradius, double lo, double hi, LineDev L,
-                      kr_limb_law law, double* __restrict__ out, DiscFlow<PLUNGE> fl, DiscSurface<SURFACE> sf)
+                      kr_limb_law law, double* __restrict__ out, DiscFlow<PLUNGE> fl, DiscSurface<SURFACE> sf, IllumTab<ILLUM> T)
 {
     extern __shared__ double lds[];
     const int words = L.words + 1;
@@ -175,7 +182,8 @@ post_line_limb_kernel(kr_ray_f64* __restrict__ rays, long long n, double spin, d
         kr_ray_f64* ray = &rays[i];
         DiscRay d;
         if (!disc_ray<true, PLUNGE, SURFACE>(ray, L.b.r_isco, L.b.r_disc, spin, V, reverse, projradius, 0, lo, hi, law, &d, on_disc, bad_angle, fl, sf)) continue;
-        binned += line_accumulate<false, true>(acc, L, d.r, d.g, ray->t, d.limb);
+        if constexpr (ILLUM) binned += line_accumulate<false, true, true>(acc, L, d.r, d.g, ray->t, d.limb, T, d.phi);
+        else binned += line_accumulate<false, true>(acc, L, d.r, d.g, ray->t, d.limb);
     }
     line_end<USE_LDS, true>(lds, out, words, on_disc, binned, bad_angle);
 }
@@ -288,7 +296,7 @@ int reduce_line_dev(const kr_line_bins* b, const void* d, int64_t n, void* d_lin
     int rc = line_dev(b, pins, &L);
     if (rc != KR_OK) return rc;
     KR_LAUNCH_LDS_OR_GLOBAL(reduce_line_kernel, L.words <= kLineLdsWords, grid_for(n, kBlock, kCapHist), L.words * sizeof(double), st, (const kr_ray_f64*) d,
-                            (long long) n, L, (double*) d_line);
+                            (long long) n, L, (double*) d_line, IllumTab<false>{});
     return KR_OK;
 }
 
@@ -318,10 +326,10 @@ int post_line_limb_dev(double spin, double V, int reverse, int projradius, doubl
         constexpr bool P = decltype(flow)::plunge;
         if (L.words + 1 <= kLineLdsWords)
             hipLaunchKernelGGL((post_line_limb_kernel<true, P>), dim3(grid), dim3(kBlock), (L.words + 1) * sizeof(double), st, (kr_ray_f64*) d, (long long) n, spin, V, reverse,
-                               projradius, lo, hi, L, *law, (double*) d_line, flow.arg, DiscSurface<false>{});
+                               projradius, lo, hi, L, *law, (double*) d_line, flow.arg, DiscSurface<false>{}, IllumTab<false>{});
         else
             hipLaunchKernelGGL((post_line_limb_kernel<false, P>), dim3(grid), dim3(kBlock), 0, st, (kr_ray_f64*) d, (long long) n, spin, V, reverse, projradius, lo, hi, L, *law,
-                               (double*) d_line, flow.arg, DiscSurface<false>{});
+                               (double*) d_line, flow.arg, DiscSurface<false>{}, IllumTab<false>{});
     });
     KR_LAUNCH_CHECK();
     return KR_OK;
@@ -340,10 +348,10 @@ int post_line_surface_dev(const kr_disc_surface* s, double spin, int reverse, do
     const DiscSurface<true> sf = surface_dev(s);
     if (L.words + 1 <= kLineLdsWords)
         hipLaunchKernelGGL((post_line_limb_kernel<true, false, true>), dim3(grid), dim3(kBlock), (L.words + 1) * sizeof(double), st, (kr_ray_f64*) d, (long long) n, spin, -1.0,
-                           reverse, 1, lo, hi, L, *law, (double*) d_line, DiscFlow<false>{}, sf);
+                           reverse, 1, lo, hi, L, *law, (double*) d_line, DiscFlow<false>{}, sf, IllumTab<false>{});
     else
         hipLaunchKernelGGL((post_line_limb_kernel<false, false, true>), dim3(grid), dim3(kBlock), 0, st, (kr_ray_f64*) d, (long long) n, spin, -1.0, reverse, 1, lo, hi, L, *law,
-                           (double*) d_line, DiscFlow<false>{}, sf);
+                           (double*) d_line, DiscFlow<false>{}, sf, IllumTab<false>{});
     KR_LAUNCH_CHECK();
     return KR_OK;
 }
@@ -357,9 +365,51 @@ int reduce_line_surface_dev(const kr_line_bins* b, const void* d, int64_t n, voi
     if (rc != KR_OK) return rc;
     const int grid = grid_for(n, kBlock, kCapHist);
     if (L.words + 1 <= kLineLdsWords)
-        hipLaunchKernelGGL((reduce_line_kernel<true, true>), dim3(grid), dim3(kBlock), (L.words + 1) * sizeof(double), st, (const kr_ray_f64*) d, (long long) n, L, (double*) d_line);
+        hipLaunchKernelGGL((reduce_line_kernel<true, true>), dim3(grid), dim3(kBlock), (L.words + 1) * sizeof(double), st, (const kr_ray_f64*) d, (long long) n, L, (double*) d_line,
+                           IllumTab<false>{});
     else
-        hipLaunchKernelGGL((reduce_line_kernel<false, true>), dim3(grid), dim3(kBlock), 0, st, (const kr_ray_f64*) d, (long long) n, L, (double*) d_line);
+        hipLaunchKernelGGL((reduce_line_kernel<false, true>), dim3(grid), dim3(kBlock), 0, st, (const kr_ray_f64*) d, (long long) n, L, (double*) d_line, IllumTab<false>{});
+    KR_LAUNCH_CHECK();
+    return KR_OK;
+}
+
+// the forms with an (r, phi) illumination table (kr_post_line_illum_dev_f64, kr_reduce_line_illum_dev_f64): the limb-law line and the reducing line with
+// emis and the source -> disc time read from the table's cell
+int post_line_illum_dev(double spin, double V, int reverse, int projradius, double lo, double hi, const kr_line_bins* b, const kr_limb_law* law, const kr_illum_table* t,
+                        void* d, int64_t n, void* d_line, hipStream_t st)
+{
+    if (n <= 0) return KR_OK;
+    TablePins pins;
+    LineDev L;
+    IllumTab<true> T;
+    int rc = line_dev(b, pins, &L);
+    if (rc == KR_OK) rc = illum_table_dev(t, pins, &T);
+    if (rc != KR_OK) return rc;
+    const int grid = grid_for(n, kBlock, kCapHist);
+    if (L.words + 1 <= kLineLdsWords)
+        hipLaunchKernelGGL((post_line_limb_kernel<true, false, false, true>), dim3(grid), dim3(kBlock), (L.words + 1) * sizeof(double), st, (kr_ray_f64*) d, (long long) n, spin, V,
+                           reverse, projradius, lo, hi, L, *law, (double*) d_line, DiscFlow<false>{}, DiscSurface<false>{}, T);
+    else
+        hipLaunchKernelGGL((post_line_limb_kernel<false, false, false, true>), dim3(grid), dim3(kBlock), 0, st, (kr_ray_f64*) d, (long long) n, spin, V, reverse, projradius, lo,
+                           hi, L, *law, (double*) d_line, DiscFlow<false>{}, DiscSurface<false>{}, T);
+    KR_LAUNCH_CHECK();
+    return KR_OK;
+}
+
+int reduce_line_illum_dev(const kr_line_bins* b, const kr_illum_table* t, const void* d, int64_t n, void* d_line, hipStream_t st)
+{
+    if (n <= 0) return KR_OK;
+    TablePins pins;
+    LineDev L;
+    IllumTab<true> T;
+    int rc = line_dev(b, pins, &L);
+    if (rc == KR_OK) rc = illum_table_dev(t, pins, &T);
+    if (rc != KR_OK) return rc;
+    const int grid = grid_for(n, kBlock, kCapHist);
+    if (L.words <= kLineLdsWords)
+        hipLaunchKernelGGL((reduce_line_kernel<true, false, true>), dim3(grid), dim3(kBlock), L.words * sizeof(double), st, (const kr_ray_f64*) d, (long long) n, L, (double*) d_line, T);
+    else
+        hipLaunchKernelGGL((reduce_line_kernel<false, false, true>), dim3(grid), dim3(kBlock), 0, st, (const kr_ray_f64*) d, (long long) n, L, (double*) d_line, T);
     KR_LAUNCH_CHECK();
     return KR_OK;
 }

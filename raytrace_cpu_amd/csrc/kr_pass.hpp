@@ -263,6 +263,22 @@ int64_t observer_words(const kr_observer_spec* sp);
 int reduce_observer_dev(const kr_observer_spec* sp, const void* d, int64_t n, void* d_out, hipStream_t st);
 int post_observer_dev(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_observer_spec* sp, void* d, int64_t n, void* d_out,
                       hipStream_t st);
+// kr_illum.hip: the (r, phi) illumination map; the validator refuses what kr_illum_bins' comment refuses of the bins; illum_words: 5 nr nphi + 2 of
+// bins that passed
+int illum_validate(const kr_illum_bins* m, const char* who);
+int64_t illum_words(const kr_illum_bins* m);
+int reduce_illum_dev(const kr_illum_bins* m, const void* d, int64_t n, void* d_out, hipStream_t st);
+int post_illum_dev(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_illum_bins* m, void* d, int64_t n, void* d_out,
+                   hipStream_t st);
+// the line and the response with an (r, phi) illumination table (kr_line.hip, kr_response.hip); the validator (kr_illum.hip) refuses what
+// kr_illum_table's comment refuses of the table itself
+int illum_table_validate(const kr_illum_table* t, const char* who);
+int post_line_illum_dev(double spin, double V, int reverse, int projradius, double lo, double hi, const kr_line_bins* b, const kr_limb_law* law, const kr_illum_table* t,
+                        void* d, int64_t n, void* d_line, hipStream_t st);
+int reduce_line_illum_dev(const kr_line_bins* b, const kr_illum_table* t, const void* d, int64_t n, void* d_line, hipStream_t st);
+int post_response_illum_dev(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_response_model* r, const kr_limb_law* law,
+                            const kr_illum_table* t, void* d, int64_t n, void* d_out, hipStream_t st);
+int reduce_response_illum_dev(const kr_response_model* r, const kr_illum_table* t, const void* d, int64_t n, void* d_out, hipStream_t st);
 // kr_caustic.hip.  The validators take the records the caller has (n; "n smaller than ..." is theirs to say)
 int caustic_validate(const kr_caustic_map* m, int64_t n, const char* who);
 int bundles_init_emit_dev(const kr_imageplane* s, int nx, int ny, double eps_frac, double V, int reverse, int projradius, void* d, int64_t n, hipStream_t st);

@@ -53,6 +53,19 @@ struct RespDev {
     int e0, e1;                // the energies [e0, e1) of this launch; the launch with e0 == 0 adds the tallies
 };
 
+// what both item functions end with: the item of a used record from its emissivity and source -> disc time
+KR_DEV void response_item_tail(const SpecDev& D, const RespDev& R, double r, double g, double t, double limb, double emis, double tt, double g3, double* a, double* b, double* c,
+                               int* zone, double* ft)
+{
+    const kr_spectrum_model& m = D.m;
+    const double fz = m.nz * kr_log(r / m.r_isco) / D.log_span;
+    *a = g;
+    *zone = (int) fmin(fmax(fz, 0.0), (double) (m.nz - 1));         // (a NaN becomes zone 0)
+    *b = kr_log(g) / D.log_sde;
+    *c = emis * limb * g3;
+    *ft = (t + tt - R.t0) / R.dt;
+}
+
 // one ray that passed the filter (and, under a law that needs it, has its angle) -> its item {a, b, c, zone} as spectrum_item<false> gives it, and the
 // coordinate of its time row; false: the ray is not used.  (spectrum_item's table branch written out: ir also serves table_time, without table_emis too.)
 KR_DEV bool response_item(const SpecDev& D, const RespDev& R, double r, double g, double t, double limb, double* a, double* b, double* c, int* zone, double* ft)
@@ -74,21 +87,34 @@ KR_DEV bool response_item(const SpecDev& D, const RespDev& R, double r, double g
         tt = R.t_time[ir];
         if (!__builtin_isfinite(tt)) return false;
     }
-    const double fz = m.nz * kr_log(r / m.r_isco) / D.log_span;
-    *a = g;
-    *zone = (int) fmin(fmax(fz, 0.0), (double) (m.nz - 1));         // (a NaN becomes zone 0)
-    *b = kr_log(g) / D.log_sde;
-    *c = emis * limb * g3;
-    *ft = (t + tt - R.t0) / R.dt;
+    response_item_tail(D, R, r, g, t, limb, emis, tt, g3, a, b, c, zone, ft);
+    return true;
+}
+
+// ILLUM (include/kr_trace.h, kr_illum_table): emis and the source -> disc time from the cell of an (r, phi) table that holds the record, in place of
+// powerlaw3 and the radial tables, which the model then does not carry.  The table rides behind the time axis in the kernel argument R: RespArg<false>
+// is RespDev itself in size and layout, so the instances without a table are the kernels they were (profiles/illum_pass_resources.txt).
+template <bool ILLUM> struct RespArg : RespDev {};
+template <> struct RespArg<true> : RespDev { IllumTab<true> tab; };
+
+KR_DEV bool response_item_illum(const SpecDev& D, const RespDev& R, const IllumTab<true>& T, double r, double phi, double g, double t, double limb, double* a, double* b,
+                                double* c, int* zone, double* ft)
+{
+    const kr_spectrum_model& m = D.m;
+    const double g3 = 1 / (g * g * g);
+    double emis, tt;
+    if (!illum_table_entry(T, r, phi, &emis, &tt)) return false;
+    response_item_tail(D, R, r, g, t, limb, emis, tt, g3, a, b, c, zone, ft);
     return true;
 }
 
 // PLUNGE: the disc flow of KR_V_PLUNGE (DiscFlow, kr_post_device.hpp), fused form only; the host picks the instance from V
 // SURFACE: the response of a disc with a surface (DiscSurface, kr_post_device.hpp): the filter, the radius and the angle of disc_ray's surface flavour
-template <int MODEL, bool FUSED, int SLOTS, bool PLUNGE, bool SURFACE = false>
+template <int MODEL, bool FUSED, int SLOTS, bool PLUNGE, bool SURFACE = false, bool ILLUM = false>
 __global__ void __launch_bounds__(kBlock)
 response_kernel(typename std::conditional<FUSED, kr_ray_f64, const kr_ray_f64>::type* __restrict__ rays, long long n, double spin, double V, int reverse,
-                int projradius, int motion, double lo, double hi, SpecDev D, RespDev R, kr_limb_law law, double* __restrict__ out, DiscFlow<PLUNGE> fl, DiscSurface<SURFACE> sf)
+                int projradius, int motion, double lo, double hi, SpecDev D, RespArg<ILLUM> R, kr_limb_law law, double* __restrict__ out, DiscFlow<PLUNGE> fl,
+                DiscSurface<SURFACE> sf)
 {
     static_assert(!(SURFACE && PLUNGE), "the surface passes keep the Keplerian observer at rho");
     extern __shared__ double lds_s[];                    // MODEL 1: the table
@@ -141,8 +167,10 @@ response_kernel(typename std::conditional<FUSED, kr_ray_f64, const kr_ray_f64>::
         if (i < n) {
             DiscRay d;
             double ft = 0;
-            if (disc_ray<FUSED, PLUNGE, SURFACE>(&rays[i], m.r_isco, m.r_disc, spin, V, reverse, projradius, motion, lo, hi, law, &d, on_disc, bad_angle, fl, sf))
-                live = response_item(D, R, d.r, d.g, rays[i].t, d.limb, &a, &b, &c, &zone, &ft);
+            if (disc_ray<FUSED, PLUNGE, SURFACE>(&rays[i], m.r_isco, m.r_disc, spin, V, reverse, projradius, motion, lo, hi, law, &d, on_disc, bad_angle, fl, sf)) {
+                if constexpr (ILLUM) live = response_item_illum(D, R, R.tab, d.r, d.phi, d.g, rays[i].t, d.limb, &a, &b, &c, &zone, &ft);
+                else live = response_item(D, R, d.r, d.g, rays[i].t, d.limb, &a, &b, &c, &zone, &ft);
+            }
             if (live) {
                 used++;
                 if (ft >= 0 && ft < R.nt) {              // (a NaN fails)
@@ -206,9 +234,9 @@ response_kernel(typename std::conditional<FUSED, kr_ray_f64, const kr_ray_f64>::
     }
 }
 
-template <bool FUSED, bool SURFACE = false, typename Rays>
+template <bool FUSED, bool SURFACE = false, bool ILLUM = false, typename Rays>
 int response_launch(const kr_response_model* r, const kr_limb_law& law, Rays* d, int64_t n, double spin, double V, int reverse, int projradius, int motion, double lo,
-                    double hi, void* d_out, hipStream_t st, DiscSurface<SURFACE> sf = DiscSurface<SURFACE>{})
+                    double hi, void* d_out, hipStream_t st, DiscSurface<SURFACE> sf = DiscSurface<SURFACE>{}, const kr_illum_table* table = nullptr)
 {
     if (n <= 0) return KR_OK;
     const kr_spectrum_model* m = &r->spec;
@@ -216,11 +244,15 @@ int response_launch(const kr_response_model* r, const kr_limb_law& law, Rays* d,
     SpecDev D;
     int rc = spectrum_dev(m, pins, &D);
     if (rc != KR_OK) return rc;
-    RespDev R;
+    RespArg<ILLUM> R;
     R.t0 = r->t0; R.dt = r->dt; R.nt = r->nt; R.t_time = nullptr;
     if (r->table_time) {
         if (m->table_logbin) D.log_tdr = std::log(m->table_dr);         // (spectrum_dev takes it only with table_emis)
         rc = table_on_device(pins, kResponseTimeTable, r->table_time, (size_t) m->table_nr, &R.t_time);
+        if (rc != KR_OK) return rc;
+    }
+    if constexpr (ILLUM) {
+        rc = illum_table_dev(table, pins, &R.tab);
         if (rc != KR_OK) return rc;
     }
     const int grid = grid_for(n, kBlock, kCapHist);
@@ -237,12 +269,12 @@ int response_launch(const kr_response_model* r, const kr_limb_law& law, Rays* d,
                         hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, st, d, (long long) n, spin, V, reverse, projradius, motion, lo, hi, D, R, law, (double*) d_out,
                                            flow.arg, sf);
                     };
-                    if (in_lds) launch(response_kernel<1, FUSED, K.value, P, SURFACE>, (size_t) m->nz * m->s_ne * sizeof(double));
-                    else launch(response_kernel<2, FUSED, K.value, P, SURFACE>, 0);
+                    if (in_lds) launch(response_kernel<1, FUSED, K.value, P, SURFACE, ILLUM>, (size_t) m->nz * m->s_ne * sizeof(double));
+                    else launch(response_kernel<2, FUSED, K.value, P, SURFACE, ILLUM>, 0);
                 }
             });
         };
-        if constexpr (FUSED && !SURFACE) for_flow(spin, V, reverse, with_flow);
+        if constexpr (FUSED && !SURFACE && !ILLUM) for_flow(spin, V, reverse, with_flow);
         else with_flow(FlowChoice<false>{});
         KR_LAUNCH_CHECK();
     }
@@ -279,6 +311,18 @@ int post_response_dev(double spin, double V, int reverse, int projradius, int mo
 int reduce_response_dev(const kr_response_model* r, const void* d, int64_t n, void* d_out, hipStream_t st)
 {
     return response_launch<false>(r, isotropic_limb(), (const kr_ray_f64*) d, n, 0.0, 0.0, 0, 0, 0, 0.0, 0.0, d_out, st);
+}
+
+// the forms with an (r, phi) illumination table (kr_post_response_illum_dev_f64, kr_reduce_response_illum_dev_f64)
+int post_response_illum_dev(double spin, double V, int reverse, int projradius, int motion, double lo, double hi, const kr_response_model* r, const kr_limb_law* law,
+                            const kr_illum_table* t, void* d, int64_t n, void* d_out, hipStream_t st)
+{
+    return response_launch<true, false, true>(r, *law, (kr_ray_f64*) d, n, spin, V, reverse, projradius, motion, lo, hi, d_out, st, DiscSurface<false>{}, t);
+}
+
+int reduce_response_illum_dev(const kr_response_model* r, const kr_illum_table* t, const void* d, int64_t n, void* d_out, hipStream_t st)
+{
+    return response_launch<false, false, true>(r, isotropic_limb(), (const kr_ray_f64*) d, n, 0.0, 0.0, 0, 0, 0, 0.0, 0.0, d_out, st, DiscSurface<false>{}, t);
 }
 
 // the surface forms (kr_post_response_surface_dev_f64, kr_reduce_response_surface_dev_f64): the Keplerian observer at rho
