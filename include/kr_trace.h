@@ -1569,7 +1569,11 @@ int kr_post_caustic_source_dev_f64(const kr_source_map* m, const void* d_rays, i
  * 26-28 work on PAIRS of elements (i even): out[i] is what a lane gets that takes a wave-uniform shortcut of the fast Euler / RK4 step when its guard lets
  * it, out[i + 1] what the code behind the guard gives for the same operands -- 26 the capped step: step = a[i], num = a[i + 1], m = b[i];  27, 28 the end of
  * a step at r = a[i], theta = a[i + 1] from theta_prev = b[i + 1] with theta_max = b[i], horizon 1.0625, r_max 1000: 27 the outcome as finished + 2 HORIZON +
- * 4 crossings + 8 (thetadot_sign flipped) + 16 (phi moved), 28 theta afterwards (kr_post.hip::probe_step_end) */
+ * 4 crossings + 8 (thetadot_sign flipped) + 16 (phi moved), 28 theta afterwards (kr_post.hip::probe_step_end)
+ * 29 works on GROUPS of eight elements (i a multiple of 8; b is not read): one stage evaluation of the fast RK4 step at a[i .. i + 7] = r, theta0, d, k,
+ * h, Q, spin, signs (bit 0: rdot_sign = -1, bit 1: thetadot_sign = -1) -- the stage angle is theta0 + d, its sine and cosine by angle addition from the base
+ * point's pair: out[i .. i + 7] = tdot, rdot, thetadot, phidot, tdot and phidot as they were associated before P / (rho^2 Delta) was shared, the sine, the
+ * cosine (kr_post.hip::probe_fast_stage) */
 int kr_debug_arith_f64(int op, const double* a, const double* b, double* out, int64_t n);
 
 /* ---- a long-lived host ray array (what Raytracer<T> holds as `rays`) ----------------------------- */

@@ -151,8 +151,11 @@ KR_DEV FastPotentials potentials_fast(double& pt, double& pphi, double k, double
     const double inv_s2 = inv * rd;                // 1 / sin^2
     // (a k, a h, a (a k), h^2, (a k)^2 and Q + (h - a k)^2 are invariant along a ray: FastRayConsts, computed once per ray)
     const double P = __builtin_fma(r2a2, k, -f.ah);
-    pt = __builtin_fma(-(__builtin_fma(f.a_ak, s2, -f.ah)), inv_rho, (r2a2 * P) * inv_rd);
-    pphi = __builtin_fma(__builtin_fma(h, inv_s2, -f.ak), inv_rho, (a * P) * inv_rd);
+    // P / (rho^2 Delta) ONCE, for tdot and phidot: seven operations where (r2a2 P) inv_rd and (a P) inv_rd took eight.  (Either derivative moves by
+    // about an ulp against that association; the single-trace and the merged kernels share this text, hence their bits.)
+    const double PD = P * inv_rd;
+    pt = __builtin_fma(r2a2, PD, -(__builtin_fma(f.a_ak, s2, -f.ah) * inv_rho));
+    pphi = __builtin_fma(a, PD, __builtin_fma(h, inv_s2, -f.ak) * inv_rho);
     FastPotentials o;
     o.N = __builtin_fma(c2, __builtin_fma(-f.h2, inv_s2, f.ak2), Q);
     o.R = __builtin_fma(-delta, __builtin_fabs(o.N) - o.N, __builtin_fma(-delta, f.q_hmak, P * P));

@@ -444,9 +444,40 @@ KR_DEV double probe_step_end(double r, double theta, double thetalim, double the
     return (fin ? 1.0 : 0.0) + ((s.status & KR_STATUS_HORIZON) ? 2.0 : 0.0) + 4.0 * s.eq_cross + (s.thetadot_sign < 0 ? 8.0 : 0.0) + (s.phi != 0.0 ? 16.0 : 0.0);
 }
 
+// One stage evaluation of the fast RK4 step (kr_device.hpp::step_fixed, the near branch of `stage`) for ONE lane: in[0..7] = r_stage, theta0, d, k, h, Q, a,
+// signs (bit 0: rdot_sign = -1, bit 1: thetadot_sign = -1); the base point's pair from k1's routine, the stage's by sincos_near, the derivatives by
+// momentum_fast_sc.  out = pt, pr, ptheta, pphi, then tdot and phidot in the association they had before P / (rho^2 Delta) was shared -- (r2a2 P) inv_rd
+// and (a P) inv_rd, on the operands potentials_fast forms -- then the stage's sine and cosine.
+KR_DEV void probe_fast_stage(const double* in, double* out)
+{
+    const double r = in[0], theta0 = in[1], d = in[2], k = in[3], h = in[4], Q = in[5], a = in[6];
+    const int code = (int) in[7];
+    const FastRaySigns sg{(code & 1) ? -1.0 : 1.0, (code & 2) ? -1.0 : 1.0};
+    const FastRayConsts f = fast_ray_consts(k, h, Q, a);
+    double s0, c0, sn, cs;
+    kr_sincos_fast_f64(theta0, s0, c0);
+    sincos_near(s0, c0, d, sn, cs);
+    momentum_fast_sc(out[0], out[1], out[2], out[3], k, h, Q, f, sg.rdot, sg.thetadot, r, sn, cs, a);
+    {
+        const double s2 = sn * sn, c2 = cs * cs, r2 = r * r, a2 = a * a, r2a2 = r2 + a2;
+        const double rhosq = __builtin_fma(a2, c2, r2), delta = __builtin_fma(-2.0, r, r2a2), rd = rhosq * delta;
+        const double inv = fast_rcp(rd * s2), inv_rd = inv * s2, inv_rho = inv_rd * delta, inv_s2 = inv * rd;
+        const double P = __builtin_fma(r2a2, k, -f.ah);
+        out[4] = __builtin_fma(-(__builtin_fma(f.a_ak, s2, -f.ah)), inv_rho, (r2a2 * P) * inv_rd);
+        out[5] = __builtin_fma(__builtin_fma(h, inv_s2, -f.ak), inv_rho, (a * P) * inv_rd);
+    }
+    out[6] = sn; out[7] = cs;
+}
+
 __global__ void __launch_bounds__(kBlock) arith_probe_kernel(int op, const double* __restrict__ a, const double* __restrict__ b, double* __restrict__ out, long long n)
 {
     KR_GRID_STRIDE(i, n) {
+        if (op == 29) {
+            // one stage evaluation per GROUP of eight elements (i a multiple of 8; b is not read)
+            if ((i & 7) || i + 7 >= n) continue;
+            probe_fast_stage(a + i, out + i);
+            continue;
+        }
         if (op >= 26 && op <= 28) {
             // the wave-uniform guards of the fast step, lane by lane, in PAIRS of elements: out[i] is what a lane that takes the shortcut gets,
             // out[i + 1] what the code behind the guard gives for the same operands (i even)
